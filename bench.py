@@ -13,11 +13,17 @@ hands out the RCCL unique id and provides the barriers around the timed region).
 query groups, exchanged through torch.distributed), --exchange torch the same collectives through
 torch.distributed.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant
-kernel, timed with HIP events on its stream inside the library), `cpu_baseline` (the CPU
-oracle timed on this box's host cores on a bounded sample; N=1 only) and the bench's own proof of
-its claim: `recall_measured`, `verified_queries`, `bit_exact` (the GPU result of the timed step
-against the oracle on a sample of the step's queries; a mismatch exits non-zero).
+Prints ONE JSON line on rank 0 (contract in the task statement) with `ms_per_step` (one timed
+step; --steps of them are timed after one untimed first step and --warmup steps) and `roofline`
+(dominant kernel, timed with HIP events on its stream inside the library during the timed steps).
+A plain run does nothing else.  With --full the line also carries `cpu_baseline` (the CPU oracle
+timed on this box's host cores on a bounded sample; N=1 only) and the bench's own proof of its
+claim: `recall_measured`, `verified_queries`, `bit_exact` (one extra step after the timed ones,
+against the oracle on a sample of its queries; a mismatch exits non-zero).
+--dump-outputs DIR writes the ids and distances of the last timed step (dump_outputs()); the inputs
+are fixed by seeds, so two builds can be compared output for output.
+--workload c4 times the graph tool's sweep (one batched query launch per ef_search after one warm
+launch): --steps / --warmup do not apply there.
 """
 import argparse
 import json
@@ -68,9 +74,9 @@ def parse():
                          "rank merges m/G queries; allgather -- round 2's one all-gather of whole chunks")
     ap.add_argument("--verify-queries", type=int, default=0,
                     help="queries of the step checked against the CPU oracle when no cpu_baseline leg "
-                         "runs (G > 1 or --no-cpu-baseline); default 8, 0 with --no-verify")
-    ap.add_argument("--no-verify", action="store_true", help="skip the oracle check of the result")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                         "runs (G > 1 or --no-cpu-baseline); default 8, 0 with --no-verify (--full only)")
+    ap.add_argument("--no-verify", action="store_true", help="skip the oracle check of the result (--full only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline leg (--full only)")
     ap.add_argument("--verify", action="store_true",
                     help="after the timed loop rank 0 checks the sharded result bit for bit against an "
                          "unsharded search of the whole base (f32 only)")
@@ -92,7 +98,15 @@ def parse():
                     help="0 auto, 1 direct, 2 GEMM form fp32/int8 MFMA, 3 GEMM form bf16x3")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
                     help="rough budget of the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the checks: the CPU baseline, one extra step checked "
+                         "against the CPU oracle (bit_exact, recall_measured); a plain run only times")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result of the last timed step as DIR/<name>.npy (ids float64, distances "
+                         "float32; over 64 MB in all, a fixed seeded sample of the query rows, listed in rows.npy)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.workload == "c3":
         if a.n == 1_000_000:
             a.n = 10_000_000
@@ -175,6 +189,28 @@ def oracle_check(oracle_ids, oracle_d, gpu_ids, gpu_d):
     bit_exact = bool(np.array_equal(g_ids, oracle_ids)) and \
         bool(np.array_equal(g_d.view(np.uint32), oracle_d.view(np.uint32)))
     return found / max(1, valid), nq, bit_exact
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write arrays {name: array whose first axis is the query} as out_dir/<name>.npy: integer ids as
+    float64 (exact below 2^53), the rest as float32.  When they exceed DUMP_BYTES in all, the same
+    fixed seeded sample of query rows is taken from every array and its indices go to rows.npy."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if np.issubdtype(v.dtype, np.integer) else np.float32)
+              for k, v in arrays.items()}
+    m = next(iter(arrays.values())).shape[0]
+    per_row = sum(v[:1].nbytes for v in arrays.values())
+    if m * per_row > DUMP_BYTES - 4096:      # (4096: room for the .npy headers)
+        keep = (DUMP_BYTES - 4096) // (per_row + 8)
+        rows = np.sort(np.random.RandomState(0).choice(m, keep, replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def profiled_traffic(kernel_name):
@@ -260,8 +296,18 @@ def bench_c4(a):
                         "kernel": f"graph_search<{a.d},fp32>", "kernel_ms": best["kernel_ms"],
                         "note": "random 512-B row gathers: latency-bound, not bandwidth-bound; "
                                 "algorithmic bytes = distcomps x d x 4 (SURVEY 8d)"}}
+    if a.dump_outputs:
+        # results file: per configuration of the sweep (compression 0 then 1, ef_search ascending):
+        # ids m*k u64, dists m*k f32, distcomps m u32 -> arrays [query][configuration](...)
+        mk = a.m * a.k
+        raw = np.fromfile(rf, dtype=np.uint8).reshape(len(sweep), mk * 12 + a.m * 4)
+        dump_outputs(a.dump_outputs, {
+            "ids": np.ascontiguousarray(raw[:, :mk * 8]).view(np.uint64).reshape(-1, a.m, a.k).transpose(1, 0, 2),
+            "distances": np.ascontiguousarray(raw[:, mk * 8:mk * 12]).view(np.float32)
+            .reshape(-1, a.m, a.k).transpose(1, 0, 2),
+            "distcomps": np.ascontiguousarray(raw[:, mk * 12:]).view(np.uint32).T})
     rc = 0
-    if not a.no_cpu_baseline or not a.no_verify:
+    if a.full and (not a.no_cpu_baseline or not a.no_verify):
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle_ctypes as oc
         g = oc.Graph(idx)
@@ -633,14 +679,16 @@ def main():
                 return ss.search(queries, a.k)
 
     def timed(n_steps):
-        """(seconds, ok): ok is False when a deferred search of the loop needed the synchronous
-        retry (agreed between the ranks: every rank then repeats the steps the waiting way)"""
+        """(seconds, ok, what the last step returned): ok is False when a deferred search of the loop
+        needed the synchronous retry (agreed between the ranks: every rank then repeats the steps the
+        waiting way)"""
         if world > 1:
             dist.barrier()
         sync_devices()
         t_start = time.perf_counter()
+        res = None
         for _ in range(n_steps):
-            step()
+            res = step()
         ok = True
         if use_async:
             try:
@@ -656,23 +704,23 @@ def main():
             flag = torch.tensor([0 if ok else 1], device="cpu" if rehearsal else dev, dtype=torch.int32)
             dist.all_reduce(flag, op=dist.ReduceOp.MAX)
             ok = int(flag.item()) == 0
-        return dt, ok
+        return dt, ok, res
 
     # one-time lazy initialisation outside any count: derived copies of the index (fp16 / uint8),
     # workspace allocation and -- with G > 1 -- the communicators
-    _, ok = timed(1)
+    _, ok, _ = timed(1)
     if ok:
-        _, ok = timed(a.warmup)
+        _, ok, _ = timed(a.warmup)
     eng.set_profiling(True)
     if ok:
-        elapsed, ok = timed(a.steps)
+        elapsed, ok, last = timed(a.steps)
     if not ok:   # (never on the iid workloads) a deferred search needed the retry: time the waiting form
         print("bench: repeating the timed steps with --sync-search", file=sys.stderr)
         use_async = False
         eng.set_option("async_search", 0)
         eng.get_profile()
         timed(1)
-        elapsed, _ = timed(a.steps)
+        elapsed, _, last = timed(a.steps)
     if world > 1:
         t = torch.tensor([elapsed], device="cpu" if rehearsal else dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -680,15 +728,20 @@ def main():
     prof = eng.get_profile()
     enqueue_ms = eng.last_enqueue_ms() if inproc else None
     eng.set_profiling(False)
-    # one more step, outside the timed region, whose result the checks below look at (it is the
-    # same search on the same inputs as every timed step)
-    got_ids, got_d = step()
-    if use_async:
-        eng.sync()
-    sync_devices()
-    if inproc:
-        got_ids, got_d = collect()
-    got_ids, got_d = got_ids[:a.m], got_d[:a.m]
+    if a.dump_outputs and rank == 0:
+        # the last timed step's result (timed() ended with every device synchronised)
+        ids, dd = collect() if inproc else last
+        dump_outputs(a.dump_outputs, {"ids": ids[:a.m].cpu().numpy(), "distances": dd[:a.m].cpu().numpy()})
+    if a.full or a.verify:
+        # one more step, outside the timed region, whose result the checks below look at (it is the
+        # same search on the same inputs as every timed step)
+        got_ids, got_d = step()
+        if use_async:
+            eng.sync()
+        sync_devices()
+        if inproc:
+            got_ids, got_d = collect()
+        got_ids, got_d = got_ids[:a.m], got_d[:a.m]
 
     def whole_base():
         if R == 1:
@@ -833,8 +886,9 @@ def main():
                                        f"{'all' if Q == 1 else 'its slice of the'} queries; transport = {transport}; "
                                        f"exchange = {pattern}; rank 0 scans {n_local} rows for {m_local} queries, "
                                        f"roofline figures are rank 0's launch") if G > 1 else "none"},
-               "roofline": roofline,
-               "verified_step": "one extra step after the timed loop (the same search on the same inputs)"}
+               "roofline": roofline}
+        if a.full:
+            out["verified_step"] = "one extra step after the timed loop (the same search on the same inputs)"
         if rehearsal:
             out["config"]["rehearsal"] = ("EXPANN_BENCH_REHEARSAL: shards / ranks share the visible GPU(s); "
                                           "a functional rehearsal, not a multi-GPU measurement")
@@ -846,14 +900,14 @@ def main():
                  ("i8", "l2"): "METRIC_L2_I8", ("i8", "ip"): "METRIC_IP_I8",
                  ("u8", "l2"): "METRIC_L2_U8"}[(a.dtype, a.metric)]
         base_host = queries_host = None
-        if G == 1 and not a.no_cpu_baseline:
+        if G == 1 and a.full and not a.no_cpu_baseline:
             try:
                 base_host, queries_host = base.cpu().numpy(), queries.cpu().numpy()
                 out["cpu_baseline"], checked = cpu_baseline(base_host, queries_host, a.k, a.cpu_seconds, mname)
             except Exception as e:  # the baseline is a reported extra, never the product
                 out["cpu_baseline"] = {"value": None, "unit": "queries/s", "cores": 0,
                                        "kind": "port", "sample": f"failed: {e}"}
-        if checked is None and not a.no_verify:
+        if checked is None and a.full and not a.no_verify:
             nv = a.verify_queries or 8
             try:
                 sys.path.insert(0, os.path.join(ROOT, "oracle"))

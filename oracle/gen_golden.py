@@ -1,4 +1,4 @@
-"""Generate tests/golden/topk_ref.json by running the REFERENCE's own topk_t<float>
+"""Generate tests/golden/topk_ref.json and topk_ref_trials.json by running the REFERENCE's own topk_t<float>
 (upstream src/topk_t.h compiled unmodified into oracle/_ref/libtopk_ref.so by
 oracle/Makefile).  Run in the build container only (needs /root/reference):
 
@@ -20,6 +20,7 @@ import oracle_ctypes as oc  # noqa: E402
 
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden",
                    "topk_ref.json")
+OUT_TRIALS = os.path.join(os.path.dirname(OUT), "topk_ref_trials.json")
 
 
 def case(name, k, d, v, discard_goal=-1):
@@ -69,6 +70,34 @@ def main():
                        source="reference src/topk_t.h via oracle/_ref/libtopk_ref.so",
                        cases=cases), f)
     print("wrote", OUT, len(cases), "cases", os.path.getsize(OUT), "bytes")
+    trials = random_trials()
+    with open(OUT_TRIALS, "w") as f:
+        json.dump(dict(generator="oracle/gen_golden.py",
+                       source="reference src/topk_t.h via oracle/_ref/libtopk_ref.so",
+                       trials=trials), f)
+    print("wrote", OUT_TRIALS, len(trials), "trials", os.path.getsize(OUT_TRIALS), "bytes")
+
+
+def random_trials():
+    """40 random consider() sequences (random n, k, tie levels; unique increasing or repeated
+    ids) with the reference's per-step admission and its final ascending list."""
+    rng = np.random.RandomState(7)
+    out = []
+    for trial in range(40):
+        n = int(rng.randint(1, 400))
+        k = int(rng.randint(1, 40))
+        levels = int(rng.choice([0, 2, 5, 50]))
+        d = (rng.randint(0, levels, size=n).astype(np.float32) if levels
+             else rng.standard_normal(n).astype(np.float32))
+        v = rng.randint(0, max(2, n // int(rng.choice([1, 1, 3]))), size=n)
+        if trial % 2 == 0:
+            v = np.arange(n)
+        r = oc.ref_topk_run(k, d, v)
+        out.append(dict(k=k, d=[float(x) for x in d], v=[int(x) for x in v],
+                        is_good=[int(x) for x in r["is_good"]],
+                        out_ids=[int(x) for x in r["out_ids"]],
+                        out_dists=[float(x) for x in r["out_dists"]]))
+    return out
 
 
 if __name__ == "__main__":

@@ -7,12 +7,12 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 TAG=${1:-r03}
 OUT=$ROOT/gpurun_out/final; mkdir -p $OUT
 cd $ROOT
-python bench.py --steps 20 --warmup 5 > $OUT/${TAG}_bench_line.json 2>$OUT/bench_line.err
+python bench.py --full --steps 20 --warmup 5 > $OUT/${TAG}_bench_line.json 2>$OUT/bench_line.err
 echo "c2 done"
-python bench.py --workload c3 --steps 3 --warmup 1 > $OUT/${TAG}_bench_c3_10m_k100.json 2>$OUT/bench_c3.err
-python bench.py --workload c5 --steps 3 --warmup 1 > $OUT/${TAG}_bench_c5_int8_ip.json 2>$OUT/bench_c5.err
+python bench.py --full --workload c3 --steps 3 --warmup 1 > $OUT/${TAG}_bench_c3_10m_k100.json 2>$OUT/bench_c3.err
+python bench.py --full --workload c5 --steps 3 --warmup 1 > $OUT/${TAG}_bench_c5_int8_ip.json 2>$OUT/bench_c5.err
 echo "c3 c5 done"
-python bench.py --workload c4 > $OUT/${TAG}_bench_c4_graph_1m.json 2>$OUT/bench_c4.err
+python bench.py --full --workload c4 > $OUT/${TAG}_bench_c4_graph_1m.json 2>$OUT/bench_c4.err
 echo "c4 done"
 bash profiles/run_rocprof.sh $TAG > $OUT/run_rocprof.log 2>&1 && python profiles/summarize.py $TAG > $OUT/summarize.log 2>&1
 echo "rocprof done"

@@ -1,7 +1,7 @@
 #!/bin/bash
 # regenerate the secondary bench lines quoted in DESIGN.md (one JSON line each) into gpurun_out/lines/
 OUT=gpurun_out/lines; mkdir -p $OUT
-B="python bench.py --no-cpu-baseline"
+B="python bench.py --full --no-cpu-baseline"
 $B --workload c5 --steps 3 --warmup 2 > $OUT/r01_bench_c5_int8_ip.json 2>/dev/null
 $B --dim 256 --steps 5 --warmup 2 > $OUT/r01_bench_d256_f32.json 2>/dev/null
 $B --dim 512 --steps 5 --warmup 2 > $OUT/r01_bench_d512_f32.json 2>/dev/null

@@ -45,7 +45,7 @@ def test_rank_grid_with_the_real_engine(ranks, row_shards, k, exchange, pattern)
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--row-shards", str(row_shards),
            "--rows", "200000", "--queries", "1000", "--k", str(k), "--steps", "1", "--warmup", "0", "--verify",
-           "--no-cpu-baseline", "--exchange", exchange, "--exchange-pattern", pattern]
+           "--full", "--no-cpu-baseline", "--exchange", exchange, "--exchange-pattern", pattern]
     res = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     assert "IDENTICAL to the unsharded search" in res.stderr, res.stderr[-2000:]
@@ -72,7 +72,7 @@ def test_plain_launch_drives_all_shards_in_one_process(gpus, k, pattern, rows):
     launch form, the rows per rank, the communicator's size (0: no RCCL communicator on one device).
     rows = 5 over 4 shards: 2, 2, 1, 0 -- the shard without rows is left out."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--rows", str(rows), "--queries", "1000",
-           "--k", str(k), "--steps", "2", "--warmup", "1", "--verify", "--no-cpu-baseline", "--exchange-pattern", pattern]
+           "--k", str(k), "--steps", "2", "--warmup", "1", "--verify", "--full", "--no-cpu-baseline", "--exchange-pattern", pattern]
     res = subprocess.run(cmd, env=_plain_env(EXPANN_BENCH_REHEARSAL="1"), cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     assert "IDENTICAL to the unsharded search" in res.stderr, res.stderr[-2000:]
@@ -101,7 +101,7 @@ def test_plain_launch_one_gpu_is_the_headline_path():
     """`python bench.py --gpus 1` (what the driver runs) on a reduced shape: the single-device handle, no
     sharding, the fields the judge reads."""
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--rows", "300000", "--queries",
-                          "2000", "--steps", "3", "--warmup", "1", "--cpu-seconds", "2"],
+                          "2000", "--steps", "3", "--warmup", "1", "--full", "--cpu-seconds", "2"],
                          env=_plain_env(), cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     line = json.loads(res.stdout.strip().splitlines()[-1])
@@ -109,3 +109,29 @@ def test_plain_launch_one_gpu_is_the_headline_path():
     assert line["config"]["launch"] == "one process, one GPU" and line["bit_exact"] and line["recall_measured"] == 1.0
     assert line["roofline"]["kernel"].startswith("scan_gemm_f16x") and "cpu_baseline" in line
     assert "verified_step" in line
+
+
+def test_plain_run_only_times_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) prints the headline fields and none of the checks; --dump-outputs writes the
+    ids and distances of the last timed step, the same arrays as a --full run whose extra step the oracle checks."""
+    import numpy as np
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--rows", "300000", "--queries", "2000",
+           "--steps", "3", "--warmup", "1"]
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        res = subprocess.run(cmd + extra + ["--dump-outputs", str(tmp_path / mode)], env=_plain_env(), cwd=ROOT,
+                             capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-2000:]
+        lines[mode] = json.loads(res.stdout.strip().splitlines()[-1])
+    plain, full = lines["plain"], lines["full"]
+    assert plain["steps"] == 3 and plain["ms_per_step"] > 0 and plain["unit"] == "queries/s"
+    assert abs(plain["value"] * plain["ms_per_step"] / 1e3 - 2000) < 20
+    assert not {"cpu_baseline", "bit_exact", "recall_measured", "verified_step"} & set(plain)
+    assert full["bit_exact"] and full["recall_measured"] == 1.0
+    got = {}
+    for mode in lines:
+        got[mode] = (np.load(tmp_path / mode / "ids.npy"), np.load(tmp_path / mode / "distances.npy"))
+        ids, dists = got[mode]
+        assert ids.dtype == np.float64 and dists.dtype == np.float32 and ids.shape == dists.shape == (2000, 10)
+        assert ((ids >= 0) & (ids < 300000)).all() and (np.diff(dists, axis=1) >= 0).all()
+    assert np.array_equal(got["plain"][0], got["full"][0]) and np.array_equal(got["plain"][1], got["full"][1])
