@@ -25,6 +25,7 @@
 #include "scan_gemm_f16x.hpp"
 #include "scan_gemm_f16y.hpp"
 #include "scan_gemm_f16kx.hpp"
+#include "scan_gemm_f16kl.hpp"
 #include "scan_direct_f16.hpp"
 #include "scan_gemm_i8.hpp"
 #include "scan_gemm_i8q.hpp"
@@ -193,11 +194,26 @@ const ScanVariant kScanF32[] = {
     SCAN_V(832, 1), SCAN_V(832, 2), SCAN_V(960, 1),  SCAN_V(960, 2), SCAN_V(1024, 1),
     SCAN_V(1024, 2)};
 #undef SCAN_V
+// every other f32 dim (multiples of 16 up to kMaxAnyDim): the run-time-dim scan (d = 0 in the table)
+#define SCAN_ANY_V(TQ)                                                                           \
+	{0, TQ, false, scan_filter_f32_any_kernel<TQ, false>, "scan_filter_f32_any<" #TQ ",L2>"},   \
+	{0, TQ, true, scan_filter_f32_any_kernel<TQ, true>, "scan_filter_f32_any<" #TQ ",IP>"}
+const ScanVariant kScanF32Any[] = {SCAN_ANY_V(1), SCAN_ANY_V(2), SCAN_ANY_V(4)};
+#undef SCAN_ANY_V
+inline bool any_dim_f32(int d) { return d >= 16 && d <= kMaxAnyDim && d % 16 == 0; }
 
 const ScanVariant* pick_scan_f32(int d, bool ip, size_t m, long forced_tq) {
 	const ScanVariant* best = nullptr;
-	for (const auto& v : kScanF32) {
-		if (v.d != d || v.ip != ip)
+	bool compiled = false;
+	for (const auto& v : kScanF32)
+		compiled = compiled || v.d == d;
+	if (!compiled && !any_dim_f32(d))
+		return nullptr;
+	const ScanVariant* tab = compiled ? kScanF32 : kScanF32Any;
+	const size_t n_tab = compiled ? sizeof(kScanF32) / sizeof(kScanF32[0]) : sizeof(kScanF32Any) / sizeof(kScanF32Any[0]);
+	for (size_t i = 0; i < n_tab; ++i) {
+		const ScanVariant& v = tab[i];
+		if ((compiled && v.d != d) || v.ip != ip)
 			continue;
 		if (forced_tq > 0) {
 			if (v.tq == forced_tq)
@@ -228,6 +244,7 @@ struct ScoreVariant {
 const ScoreVariant kScoreF32[] = {SCORE_V(64),  SCORE_V(128), SCORE_V(256), SCORE_V(512),
                                   SCORE_V(768), SCORE_V(832), SCORE_V(960), SCORE_V(1024)};
 #undef SCORE_V
+const ScoreVariant kScoreF32Any[] = {{0, false, score_ids_f32_any_kernel<false>}, {0, true, score_ids_f32_any_kernel<true>}};
 
 // 8-bit rows
 struct ScanI8Variant {
@@ -445,6 +462,21 @@ const GemmF16Variant kGemmF16XDbg[] = {{128, scan_gemm_f16x_kernel<128, false, 1
                                         sqnorm_kernel<128>, f16_query_prep_kernel<128>, "scan_gemm_f16x<128, false>",
                                         kF16TB, kF16TQ, kF16Threads, 2, gemm_f16_lds_bytes<128>(), 1}};
 inline bool f16_choice(long opt) { return opt == 0 || opt == 4 || opt == 6; }
+// the fp16 filter with the dim known at run time (scan_gemm_f16kl.hpp): every f32 dim from 64 up without a
+// form of its own (d = 0 here; prelude: sqnorm_any_kernel / f16_query_prep_any_kernel)
+const GemmF16Variant kGemmF16KL = {0, scan_gemm_f16kl_kernel<false>, scan_gemm_f16kl_kernel<true>, nullptr, nullptr,
+                                   "scan_gemm_f16kl", kF16klTB, kF16TQ, kF16Threads, 1, kF16klLds, 1};
+inline bool f16kl_dim(int d) {
+	if (d < 64 || !any_dim_f32(d))
+		return false;
+	for (const auto& v : kGemmF16X)
+		if (v.d == d)
+			return false;
+	return true;
+}
+// row length of the index's fp16 copy: whole 32-element MFMA k-steps for the run-time-dim form
+inline int f16_ld(int d) { return f16kl_dim(d) ? (d + 31) / 32 * 32 : d; }
+const GemmVariant kGemmF16KLOnly = {0, nullptr, nullptr, nullptr, "-"};  // (pick_gemm's placeholder, as kGemmF16Only)
 
 // a handful of queries: the same filter streamed from HBM without the matrix cores
 // (scan_direct_f16.hpp); tq = queries per pass
@@ -502,22 +534,31 @@ int ensure_f16(expann_index* h, const GemmF16Variant* gf, hipStream_t st) {
 		h->f16_scale = -1.0f;
 		return EXPANN_OK;
 	}
-	// padded to whole 64-row tiles: zero rows whose bn' is NaN (never a candidate)
-	const size_t n_pad = (h->n + kF16TB - 1) / kF16TB * kF16TB;
-	HIP_TRY(h, hipMalloc(&h->d_base_f16, n_pad * h->dim * 2));
+	// padded to whole tiles (64 rows; 128 for scan_gemm_f16kl): zero rows whose bn' is NaN (never a candidate)
+	const size_t tb = (size_t)std::max(kF16TB, gf->tb);
+	const size_t n_pad = (h->n + tb - 1) / tb * tb;
+	const size_t ld = (size_t)f16_ld(h->dim);
+	HIP_TRY(h, hipMalloc(&h->d_base_f16, n_pad * ld * 2));
 	HIP_TRY(h, hipMalloc(&h->d_bnorm_f16, sizeof(float) * n_pad));
 	HIP_TRY(h, hipMalloc(&h->d_bns_f16, sizeof(float) * n_pad));
-	HIP_TRY(h, hipMemsetAsync(h->d_base_f16, 0, n_pad * h->dim * 2, st));
+	HIP_TRY(h, hipMemsetAsync(h->d_base_f16, 0, n_pad * ld * 2, st));
 	HIP_TRY(h, hipMemsetAsync(h->d_bnorm_f16, 0xFF, sizeof(float) * n_pad, st));  // 0xFFFFFFFF: a NaN
 	HIP_TRY(h, hipMemsetAsync(h->d_bns_f16, 0xFF, sizeof(float) * n_pad, st));
 	if (!h->d_bnmax)
 		HIP_TRY(h, hipMalloc(&h->d_bnmax, 4 * sizeof(float)));
-	hipLaunchKernelGGL(convert_f16_kernel, dim3((uint32_t)std::min<size_t>((nv + kBlock - 1) / kBlock, 8192)),
-	                   dim3(kBlock), 0, st, (const float*)h->d_base, nv, scale, h->d_base_f16.as<_Float16>(),
-	                   (uint32_t*)nullptr);
 	const uint32_t blocks16 = (uint32_t)((h->n + kRowsPerGroup - 1) / kRowsPerGroup);
-	hipLaunchKernelGGL(gf->sqnorm, dim3(blocks16), dim3(kBlock), 0, st, (const float*)h->d_base,
-	                   (uint32_t)h->n, nrm.as<float>());
+	if (gf->d == 0) {  // run-time dim: rows of ld elements, zero past d; norms over the d real ones
+		hipLaunchKernelGGL(convert_f16_pad_kernel, dim3(8192), dim3(kBlock), 0, st, (const float*)h->d_base, h->n,
+		                   (uint32_t)h->dim, (uint32_t)ld, scale, h->d_base_f16.as<_Float16>());
+		hipLaunchKernelGGL(sqnorm_any_kernel, dim3(blocks16), dim3(kBlock), 0, st, (const float*)h->d_base,
+		                   (uint32_t)h->n, (uint32_t)h->dim, nrm.as<float>());
+	} else {
+		hipLaunchKernelGGL(convert_f16_kernel, dim3((uint32_t)std::min<size_t>((nv + kBlock - 1) / kBlock, 8192)),
+		                   dim3(kBlock), 0, st, (const float*)h->d_base, nv, scale, h->d_base_f16.as<_Float16>(),
+		                   (uint32_t*)nullptr);
+		hipLaunchKernelGGL(gf->sqnorm, dim3(blocks16), dim3(kBlock), 0, st, (const float*)h->d_base,
+		                   (uint32_t)h->n, nrm.as<float>());
+	}
 	hipLaunchKernelGGL(max_f32_kernel, dim3(1), dim3(1024), 0, st, (const float*)nrm.p, h->n,
 	                   h->d_bnmax + 2);
 	const float abs_coef = std::ldexp(1.0f, -24) / scale * std::sqrt((float)h->dim);
@@ -541,17 +582,20 @@ const GemmVariant* pick_gemm(const expann_index* h, size_t m) {
 		// inner product: only the fp16 form has it (a placeholder variant keeps the GEMM branch alive)
 		const bool ok = f16_choice(h->opt_scan_kernel) && h->f16_scale >= 0.0f &&
 		                !(h->opt_scan_kernel == 0 && ((m < 5 && !pick_direct_f16(h->dim, m)) || h->n < 4096));
-		if (ok)
+		if (ok) {
 			for (const auto& v : kGemmF16Only)
 				if (v.d == h->dim)
 					return &v;
+			if (f16kl_dim(h->dim))
+				return &kGemmF16KLOnly;
+		}
 		return nullptr;
 	}
 	// measured crossovers at N = 1M, d = 128.  bf16x3 / fp32 forms: m = 16: 0.34 vs 0.37 ms per
 	// step, m = 32: 0.49 vs 0.41 ms -- below ~24 queries the HBM-bound direct scan wins.  fp16
 	// form (half the bytes per row, one sampled pass): 0.175 vs 0.175 ms at m = 4, 0.173 vs 0.199
 	// at m = 8, 0.185 vs 0.31 at m = 16 -- from 5 queries on it wins.
-	bool f16_dims = false;
+	bool f16_dims = f16kl_dim(h->dim) && h->f16_scale >= 0.0f;
 	for (const auto& v : kGemmF16Only)
 		f16_dims = f16_dims || (v.d == h->dim && h->f16_scale >= 0.0f);
 	if (h->opt_scan_kernel == 0 &&
@@ -560,10 +604,13 @@ const GemmVariant* pick_gemm(const expann_index* h, size_t m) {
 	for (const auto& v : kGemmF32)
 		if (v.d == h->dim)
 			return &v;
-	if (f16_choice(h->opt_scan_kernel))
+	if (f16_choice(h->opt_scan_kernel)) {
 		for (const auto& v : kGemmF16Only)
 			if (v.d == h->dim)
 				return &v;
+		if (f16kl_dim(h->dim))
+			return &kGemmF16KLOnly;
+	}
 	return nullptr;
 }
 
@@ -1279,6 +1326,7 @@ int sampled_pass_f16(expann_index* h, const GemmF16Variant* gvf, size_t m, size_
 	fp.m = (uint32_t)m;
 	fp.sample_out = h->d_sample;
 	fp.n_chunks = chunks;
+	fp.ksteps = (uint32_t)f16_ld(h->dim) / 32;
 	hipLaunchKernelGGL(gvf->sample, dim3(chunks * nqt), dim3((uint32_t)gvf->threads), gvf->lds, st, fp);
 	tp.vals = h->d_sample;
 	tp.n_vals = chunks * 32;
@@ -1336,6 +1384,7 @@ int launch_scan_f16(expann_index* h, const GemmF16Variant* gvf, uint32_t rows_se
 		}
 	}
 	fp.queries_f16 = h->d_q_split;
+	fp.ksteps = (uint32_t)f16_ld(h->dim) / 32;
 	fp.theta = h->d_theta;
 	fp.two_inv_s2 = (ip ? 1.0f : 2.0f) / (h->f16_scale * h->f16_scale);
 	fp.m = (uint32_t)m;
@@ -1499,9 +1548,11 @@ int SearchPass::choose_kernels() {
 				gvf = &v;
 		if (dbg && kGemmF16XDbg[0].d == h->dim)
 			gvf = &kGemmF16XDbg[0];
+		if (!gvf && f16kl_dim(h->dim))
+			gvf = &kGemmF16KL;
 	}
 	if ((h->opt_scan_kernel == 4 || h->opt_scan_kernel == 6) && !gvf && !no_f16)
-		return h->fail(EXPANN_ERR_UNSUPPORTED, "fp16 GEMM-form scan: f32 with dim 64, 128, 256, 512, 768, 832 or 960 only");
+		return h->fail(EXPANN_ERR_UNSUPPORTED, "fp16 GEMM-form scan: f32 with dim a multiple of 16 from 64 to 4096 only");
 	if (gvf)
 		gvb = nullptr;
 	else if ((h->opt_scan_kernel == 0 && m < 24) || !gvb)
@@ -1539,12 +1590,19 @@ int SearchPass::prepare_queries(bool* restart) {
 		if (!one_wg)
 			HIP_TRY(h, hipMemsetAsync(h->d_overflow, 0, 32, st));
 		flags_clean = true;
-		hipLaunchKernelGGL(gvf->prep, dim3((uint32_t)((m + kRowsPerGroup - 1) / kRowsPerGroup)), dim3(kBlock),
-		                   0, st, (const float*)d_queries, (uint32_t)m, h->f16_scale, h->d_q_split.as<_Float16>(),
-		                   h->d_qnrm, h->d_overflow + 2, from_host ? h->d_q.as<float>() : (float*)nullptr,
-		                   one_wg ? h->d_overflow : (uint32_t*)nullptr,
-		                   (ip && h->opt_ip_rescale) ? (const float*)(h->d_bnmax + 2) : (const float*)nullptr,
-		                   h->d_qscale.as<float>());
+		const dim3 prep_grid((uint32_t)((m + kRowsPerGroup - 1) / kRowsPerGroup));
+		const float* ip_ref = (ip && h->opt_ip_rescale) ? (const float*)(h->d_bnmax + 2) : (const float*)nullptr;
+		if (gvf->d == 0)  // (run-time dim: rows of f16_ld(d) elements, zero-padded)
+			hipLaunchKernelGGL(f16_query_prep_any_kernel, prep_grid, dim3(kBlock), 0, st, (const float*)d_queries,
+			                   (uint32_t)m, (uint32_t)h->dim, (uint32_t)f16_ld(h->dim), h->f16_scale,
+			                   h->d_q_split.as<_Float16>(), h->d_qnrm, h->d_overflow + 2,
+			                   from_host ? h->d_q.as<float>() : (float*)nullptr, one_wg ? h->d_overflow : (uint32_t*)nullptr,
+			                   ip_ref, h->d_qscale.as<float>());
+		else
+			hipLaunchKernelGGL(gvf->prep, prep_grid, dim3(kBlock), 0, st, (const float*)d_queries, (uint32_t)m,
+			                   h->f16_scale, h->d_q_split.as<_Float16>(), h->d_qnrm, h->d_overflow + 2,
+			                   from_host ? h->d_q.as<float>() : (float*)nullptr, one_wg ? h->d_overflow : (uint32_t*)nullptr,
+			                   ip_ref, h->d_qscale.as<float>());
 		HIP_TRY(h, hipGetLastError());
 		if (from_host) {
 			d_queries = h->d_q;
@@ -1622,6 +1680,7 @@ int SearchPass::run_level(size_t li) {
 	sp.cand_cnt = h->d_cnt;
 	sp.cand = h->d_cand;
 	sp.cap = cap;
+	sp.dim = (uint32_t)h->dim;
 	// ~16 workgroups per CU in total, at least 8 groups (128 rows) per workgroup
 	uint32_t target_chunks = (uint32_t)std::max<long>(1, (16L * cus + n_qtiles - 1) / n_qtiles);
 	uint32_t max_chunks = std::max<uint32_t>(1, L.n_groups_sel / 8);
@@ -2005,6 +2064,11 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 			g_create_error = "metric must be EXPANN_METRIC_L2 or EXPANN_METRIC_IP for f32 rows";
 			return EXPANN_ERR_INVALID_ARG;
 		}
+		if (dim > kMaxAnyDim) {
+			g_create_error = "unsupported dim " + std::to_string(dim) + ": f32 rows take dim <= " +
+			                 std::to_string(kMaxAnyDim);
+			return EXPANN_ERR_UNSUPPORTED;
+		}
 	} else if (dtype == EXPANN_DTYPE_U8) {
 		if (metric != EXPANN_METRIC_L2) {
 			g_create_error = "uint8 rows support EXPANN_METRIC_L2 only (dist2_compressed)";
@@ -2048,7 +2112,7 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 	if ((int_mode < 0 && !pick_scan_f32(dim, metric == EXPANN_METRIC_IP, 1, 0)) ||
 	    (int_mode >= 0 && !pick_scan_i8(dim, int_mode, 1, 0))) {
 		g_create_error = "unsupported dim " + std::to_string(dim) +
-		                 " (built: f32 64,128,256,512,768,832,960,1024; 8-bit 64,128,256,768,832,960)";
+		                 " (built: f32 any multiple of 16 up to 4096; 8-bit 64,128,256,768,832,960)";
 		return EXPANN_ERR_UNSUPPORTED;
 	}
 	expann_index* h = new expann_index();
@@ -2086,6 +2150,14 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 			delete h;
 			return EXPANN_ERR_HIP;
 		}
+	if (dtype == EXPANN_DTYPE_F32 && f16kl_dim(dim) &&
+	    (hipFuncSetAttribute((const void*)kGemmF16KL.scan, hipFuncAttributeMaxDynamicSharedMemorySize, kGemmF16KL.lds) != hipSuccess ||
+	     hipFuncSetAttribute((const void*)kGemmF16KL.sample, hipFuncAttributeMaxDynamicSharedMemorySize, kGemmF16KL.lds) != hipSuccess)) {
+		g_create_error = "hipFuncSetAttribute(scan_gemm_f16kl_kernel) failed";
+		hipStreamDestroy(h->stream);
+		delete h;
+		return EXPANN_ERR_HIP;
+	}
 	for (const auto* tab : {kGemmF16XDbg})
 		if (tab[0].d == dim)
 			if (hipFuncSetAttribute((const void*)tab[0].scan, hipFuncAttributeMaxDynamicSharedMemorySize, tab[0].lds) !=
@@ -2188,13 +2260,19 @@ int expann_build(expann_index* h) {
 	std::vector<unsigned char>().swap(h->staging);
 	// the fp16 copy every fp32 search of a built dim filters through: made here, inside the
 	// reference's timed build span (basic_bench.h:63-71), not inside the first query
-	if (h->dtype == EXPANN_DTYPE_F32 && h->n >= 4096 && h->opt_scan_kernel == 0)
+	if (h->dtype == EXPANN_DTYPE_F32 && h->n >= 4096 && h->opt_scan_kernel == 0) {
 		for (const auto& v : kGemmF16X)
 			if (v.d == h->dim) {
 				const int rc = ensure_f16(h, &v, h->stream);
 				if (rc != EXPANN_OK)
 					return rc;
 			}
+		if (f16kl_dim(h->dim)) {
+			const int rc = ensure_f16(h, &kGemmF16KL, h->stream);
+			if (rc != EXPANN_OK)
+				return rc;
+		}
+	}
 	return EXPANN_OK;
 }
 
@@ -2443,10 +2521,12 @@ int expann_score_ids(expann_index* h, const void* query, const uint64_t* ids, si
 		for (const auto& v : kScoreF32)
 			if (v.d == h->dim && v.ip == (h->metric == EXPANN_METRIC_IP))
 				sv = &v;
+		if (!sv && any_dim_f32(h->dim))
+			sv = &kScoreF32Any[h->metric == EXPANN_METRIC_IP ? 1 : 0];
 		if (!sv)
 			return h->fail(EXPANN_ERR_UNSUPPORTED, "no score kernel for this dim");
 		ScoreIdsParams sp{h->d_base, d_query, (const uint64_t*)d_idl, h->id_offset,
-		                  (uint32_t)n_ids, (float*)d_sc};
+		                  (uint32_t)n_ids, (float*)d_sc, (uint32_t)h->dim};
 		hipLaunchKernelGGL(sv->fn, dim3(blocks), dim3(kBlock), 0, h->stream, sp);
 	} else {
 		const ScoreI8Variant* sv = nullptr;

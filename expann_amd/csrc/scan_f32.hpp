@@ -40,6 +40,7 @@ struct ScanParams {
 	// The k smallest class minima are k different rows, so their k-th is a valid (score, row)
 	// threshold -- from a 16x larger sample than a keep-all level can afford, in one launch.
 	uint32_t classmin;
+	uint32_t dim;             // scan_filter_f32_any_kernel only: the row length (the templates have it as D)
 };
 
 template <int D, int TQ, bool IP>
@@ -188,6 +189,137 @@ __global__ __launch_bounds__(kBlock) void scan_filter_f32_kernel(ScanParams p) {
 	}
 	if (g < g1)
 		process(ra, g);
+	if (level0 && p.classmin) {
+		const uint32_t slot = chunk * 16 + wave * 4 + rg;
+		if (l == 0 && slot < p.cap) {
+#pragma unroll
+			for (int j = 0; j < TQ; ++j)
+				if (q0 + j < p.m)
+					p.cand[(size_t)(q0 + j) * p.cap + slot] = best[j];
+		}
+	}
+}
+
+// The same scan with the dim known at run time (any multiple of 16 up to kMaxAnyDim): the dims without
+// an instance of their own.  Same contract (thresholds or level-0 class minima, (score, row) keys,
+// per-query lists) and the same arithmetic: lane l of a DPP row owns dims l, l+16, ... of one base row,
+// v_fma_f32 in increasing order per query, reduce16_ref_order -- the loop simply runs d/16 times, so an
+// odd d/16 needs nothing special.  The TQ queries of the workgroup sit in LDS (TQ x kMaxAnyDim floats,
+// 16 lanes of a row read the same 64 B: broadcast), so a 4096-wide query costs no registers.
+constexpr int kMaxAnyDim = 4096;
+template <int TQ, bool IP>
+__global__ __launch_bounds__(kBlock) void scan_filter_f32_any_kernel(ScanParams p) {
+	__shared__ float qs[TQ * kMaxAnyDim];
+	const uint32_t D = p.dim, DPL = D / 16;
+	const int lane = threadIdx.x & 63;
+	const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+	const int l = lane & 15, rg = lane >> 4;
+	const uint32_t qtile = blockIdx.x % p.n_qtiles;
+	const uint32_t chunk = blockIdx.x / p.n_qtiles;
+	const uint32_t q0 = qtile * TQ;
+	const float* __restrict__ base = (const float*)p.base;
+	const float* __restrict__ queries = (const float*)p.queries;
+	const bool level0 = (p.tau == nullptr);
+
+	for (uint32_t i = threadIdx.x; i < TQ * D; i += kBlock) {
+		const uint32_t j = i / D;
+		const uint32_t qi = (q0 + j < p.m) ? q0 + j : p.m - 1;
+		qs[i] = queries[(size_t)qi * D + (i - j * D)];
+	}
+	float tau[TQ];
+#pragma unroll
+	for (int j = 0; j < TQ; ++j) {
+		const uint32_t qi = (q0 + j < p.m) ? q0 + j : p.m - 1;
+		float tj = level0 ? __builtin_inff() : p.tau[qi];
+		tj = (q0 + j < p.m) ? tj : -__builtin_inff();
+		tau[j] = __builtin_bit_cast(float,
+		                            __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, tj)));
+	}
+	__syncthreads();
+
+	const uint32_t g0 = chunk * p.groups_per_block;
+	uint32_t g1 = g0 + p.groups_per_block;
+	if (g1 > p.n_groups_sel)
+		g1 = p.n_groups_sel;
+	uint64_t best[TQ];  // class minima (classmin level)
+#pragma unroll
+	for (int j = 0; j < TQ; ++j)
+		best[j] = kSentinelKey;
+	for (uint32_t g = g0; g < g1; ++g) {
+		const uint32_t row = g * p.group_stride * kRowsPerGroup + wave * kRowsPerWaveStep + rg;
+		const bool rvalid = row < p.n_rows;
+		const float* src = base + (size_t)(rvalid ? row : p.n_rows - 1) * D + l;
+		const float* qsl = qs + l;
+		float acc[TQ];
+#pragma unroll
+		for (int j = 0; j < TQ; ++j)
+			acc[j] = 0.0f;
+		uint32_t t = 0;
+		for (; t + 4 <= DPL; t += 4) {  // (four loads in flight per lane)
+			float r[4];
+#pragma unroll
+			for (int u = 0; u < 4; ++u)
+				r[u] = src[16 * (t + u)];
+#pragma unroll
+			for (int u = 0; u < 4; ++u)
+#pragma unroll
+				for (int j = 0; j < TQ; ++j) {
+					const float qv = qsl[j * D + 16 * (t + u)];
+					if (IP) {
+						acc[j] = __builtin_fmaf(qv, r[u], acc[j]);
+					} else {
+						const float diff = qv - r[u];
+						acc[j] = __builtin_fmaf(diff, diff, acc[j]);
+					}
+				}
+		}
+		for (; t < DPL; ++t) {
+			const float rv = src[16 * t];
+#pragma unroll
+			for (int j = 0; j < TQ; ++j) {
+				const float qv = qsl[j * D + 16 * t];
+				if (IP) {
+					acc[j] = __builtin_fmaf(qv, rv, acc[j]);
+				} else {
+					const float diff = qv - rv;
+					acc[j] = __builtin_fmaf(diff, diff, acc[j]);
+				}
+			}
+		}
+		float s[TQ];
+		unsigned long long any = 0;
+#pragma unroll
+		for (int j = 0; j < TQ; ++j) {
+			const float red = reduce16_ref_order(acc[j]);
+			s[j] = IP ? -red : red;
+			any |= __builtin_amdgcn_ballot_w64(s[j] <= tau[j]);
+		}
+		if (level0 && p.classmin) {
+#pragma unroll
+			for (int j = 0; j < TQ; ++j) {
+				const uint64_t key = rvalid ? make_key(s[j], row) : kSentinelKey;
+				best[j] = key < best[j] ? key : best[j];
+			}
+		} else if (level0) {
+			const uint32_t slot = g * kRowsPerGroup + wave * kRowsPerWaveStep + rg;
+			if (l == 0 && slot < p.cap) {
+#pragma unroll
+				for (int j = 0; j < TQ; ++j)
+					if (q0 + j < p.m)
+						p.cand[(size_t)(q0 + j) * p.cap + slot] = rvalid ? make_key(s[j], row) : kSentinelKey;
+			}
+		} else if (any) {
+#pragma unroll
+			for (int j = 0; j < TQ; ++j) {
+				if (l == 0 && rvalid && q0 + j < p.m &&
+				    (s[j] < tau[j] || (s[j] == tau[j] && row <= p.tau_row[q0 + j]))) {
+					const uint32_t slot = atomicAdd(&p.cand_cnt[q0 + j], 1u);
+					if (slot < p.cap)
+						p.cand[(size_t)(q0 + j) * p.cap + slot] = make_key(s[j], row);
+				}
+			}
+		}
+	}
 	if (level0 && p.classmin) {
 		const uint32_t slot = chunk * 16 + wave * 4 + rg;
 		if (l == 0 && slot < p.cap) {

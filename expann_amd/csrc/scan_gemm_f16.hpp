@@ -1,7 +1,8 @@
 // scan_gemm_f16.hpp -- the GEMM-form fp32 L2 candidate filter with ONE fp16 product per element
 // on the matrix cores: a third of the MFMA work of the bf16x3 form (scan_gemm_bf16.hpp) and half its
 // tile bytes.  This header holds the analysis and everything the fp16 kernels share; the kernels
-// themselves are scan_gemm_f16x.hpp / f16y / f16kx (v_mfma_f32_16x16x32_f16).
+// themselves are scan_gemm_f16x.hpp / f16y / f16kx (v_mfma_f32_16x16x32_f16), and f16kl at the dims known only
+// at run time.
 //
 // Every value is scaled by a per-index power of two s (so that max|x|*s <= 2^15) and rounded
 // once to fp16:  |x*s - fp16(x*s)| <= 2^-11 |x*s| + 2^-25  (normal + subnormal range).  Hence
@@ -192,6 +193,99 @@ __global__ __launch_bounds__(kBlock) void f16_query_prep_kernel(const float* q, 
 	}
 }
 
+// The prelude at a dim known at run time (scan_gemm_f16kl.hpp: the dims without a compiled fp16 form).
+// The fp16 copies there have rows of ld = d rounded up to a multiple of 32 elements (whole MFMA k-steps),
+// zero past d; norms and the range check are those of the d real elements.
+__global__ __launch_bounds__(kBlock) void sqnorm_any_kernel(const float* x, uint32_t n, uint32_t d, float* out) {
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const int l = lane & 15, rg = lane >> 4;
+	const uint32_t i = blockIdx.x * kRowsPerGroup + wave * kRowsPerWaveStep + rg;
+	const uint32_t ii = i < n ? i : n - 1;
+	const float* src = x + (size_t)ii * d + l;
+	float acc = 0.0f;
+	for (uint32_t t = 0; t < d / 16; ++t)
+		acc = __builtin_fmaf(src[16 * t], src[16 * t], acc);
+	acc = reduce16_ref_order(acc);
+	if (i < n && l == 0)
+		out[i] = acc;
+}
+// fp32 [n][d] * scale -> fp16 [n][ld] (zero columns d .. ld-1)
+__global__ __launch_bounds__(kBlock) void convert_f16_pad_kernel(const float* in, size_t n, uint32_t d, uint32_t ld,
+                                                                 float scale, _Float16* out) {
+	for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n * ld; i += (size_t)gridDim.x * kBlock) {
+		const size_t r = i / ld;
+		const uint32_t c = (uint32_t)(i - r * ld);
+		out[i] = c < d ? (_Float16)(in[r * d + c] * scale) : (_Float16)0.0f;
+	}
+}
+// f16_query_prep_kernel<D> at run-time d: same outputs (q16 with rows of ld, zero-padded), same per-query
+// ip_rescale power of two, same range flag, same one-workgroup latency path (zero_flags, q_copy).  The
+// query is read twice (norm and max |q| first, then the scaled copy) instead of being held in registers.
+__global__ __launch_bounds__(kBlock) void f16_query_prep_any_kernel(const float* q, uint32_t m, uint32_t d, uint32_t ld,
+                                                                    float scale, _Float16* q16, float* qnrm,
+                                                                    uint32_t* maxabs_bits, float* q_copy,
+                                                                    uint32_t* zero_flags, const float* ip_ref,
+                                                                    float* qscale) {
+	__shared__ uint32_t red[kBlock / 64];
+	if (zero_flags) {
+		if (threadIdx.x < 8)
+			zero_flags[threadIdx.x] = 0;
+		__syncthreads();
+	}
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const int l = lane & 15, rg = lane >> 4;
+	const uint32_t i = blockIdx.x * kRowsPerGroup + wave * kRowsPerWaveStep + rg;
+	const uint32_t ii = i < m ? i : m - 1;
+	const float* src = q + (size_t)ii * d + l;
+	float acc = 0.0f;
+	uint32_t b = 0;
+	for (uint32_t t = 0; t < d / 16; ++t) {
+		const float v = src[16 * t];
+		acc = __builtin_fmaf(v, v, acc);
+		const uint32_t vb = __builtin_bit_cast(uint32_t, v) & 0x7fffffffu;
+		b = vb > b ? vb : b;
+	}
+	acc = reduce16_ref_order(acc);
+	acc = __shfl(acc, lane & ~15);
+	float c = 1.0f;
+	if (ip_ref) {
+		const float ref = ip_ref[0];
+		if (acc > 0.0f && ref > 0.0f && acc < 3.0e38f && ref < 3.0e38f) {
+			int e = (int)__builtin_rintf(0.5f * (__builtin_log2f(ref) - __builtin_log2f(acc)));
+			e = e < -40 ? -40 : (e > 40 ? 40 : e);
+			c = __builtin_ldexpf(1.0f, e);
+		}
+	}
+	if (i < m) {
+		for (uint32_t t = 0; t < ld / 16; ++t) {
+			const uint32_t col = l + 16 * t;
+			const float v = col < d ? src[16 * t] : 0.0f;
+			q16[(size_t)i * ld + col] = (_Float16)(v * c * scale);
+			if (q_copy && col < d)
+				q_copy[(size_t)i * d + col] = v;
+		}
+		if (l == 0) {
+			qnrm[i] = acc * c * c;
+			if (qscale)
+				qscale[i] = c;
+		}
+	}
+	b = __builtin_bit_cast(uint32_t, __builtin_bit_cast(float, b) * c);
+	for (int off = 32; off > 0; off >>= 1) {
+		const uint32_t o = (uint32_t)__shfl_xor((int)b, off);
+		b = o > b ? o : b;
+	}
+	if (lane == 0)
+		red[wave] = b;
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		for (int w = 1; w < kBlock / 64; ++w)
+			b = red[w] > b ? red[w] : b;
+		if (b != 0)
+			atomicMax(maxabs_bits, b);
+	}
+}
+
 // rows:    out = (nrm*(1-eps) - abs*sqrt(nrm)) * mul                (tau == nullptr)
 // queries: out = (tau - (nrm*(1-eps) - abs*sqrt(nrm))) * mul
 // mul = s^2/2, a power of two: the scaling is exact
@@ -263,6 +357,8 @@ struct GemmF16Params {
 	// (zero at launch, one cache line each), n_items = the plain launch's grid; nullptr = plain launch
 	uint32_t* work_ctr;
 	uint32_t n_items;
+	// scan_gemm_f16kl_kernel only: MFMA k-steps of 32 elements per row (the fp16 rows' length / 32)
+	uint32_t ksteps;
 };
 
 // Per-wave hit logs -> per-query candidate lists.  The 64 queries of (query tile, wave w) receive

@@ -14,6 +14,7 @@ struct ScoreIdsParams {
 	uint64_t id_offset;
 	uint32_t n_ids;
 	float* scores;          // [n_ids]
+	uint32_t dim;           // score_ids_f32_any_kernel only
 };
 
 template <int D, bool IP>
@@ -30,6 +31,32 @@ __global__ __launch_bounds__(kBlock) void score_ids_f32_kernel(ScoreIdsParams p)
 	float acc = 0.0f;
 #pragma unroll
 	for (int t = 0; t < DPL; ++t) {
+		if (IP) {
+			acc = __builtin_fmaf(q[16 * t], r[16 * t], acc);
+		} else {
+			const float diff = q[16 * t] - r[16 * t];
+			acc = __builtin_fmaf(diff, diff, acc);
+		}
+	}
+	acc = reduce16_ref_order(acc);
+	if (valid && l == 0)
+		p.scores[i] = IP ? -acc : acc;
+}
+
+// the same with the dim known at run time (the dims without an instance of their own)
+template <bool IP>
+__global__ __launch_bounds__(kBlock) void score_ids_f32_any_kernel(ScoreIdsParams p) {
+	const uint32_t D = p.dim;
+	const int lane = threadIdx.x & 63;
+	const int wave = threadIdx.x >> 6;
+	const int l = lane & 15, rg = lane >> 4;
+	const uint32_t i = blockIdx.x * kRowsPerGroup + wave * kRowsPerWaveStep + rg;
+	const bool valid = i < p.n_ids;
+	const uint64_t row = p.ids[valid ? i : p.n_ids - 1] - p.id_offset;
+	const float* __restrict__ r = (const float*)p.base + (size_t)row * D + l;
+	const float* __restrict__ q = (const float*)p.query + l;
+	float acc = 0.0f;
+	for (uint32_t t = 0; t < D / 16; ++t) {
 		if (IP) {
 			acc = __builtin_fmaf(q[16 * t], r[16 * t], acc);
 		} else {

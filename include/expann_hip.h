@@ -67,6 +67,9 @@ int expann_abi_version(void);
 int expann_device_count(void);
 
 /* lifecycle (replaces: engine construction, src/bench_runner.h:33) -------------------- */
+/* dim: a multiple of 16 (else EXPANN_ERR_INVALID_ARG).  f32 rows: any such dim up to 4096 (over it:
+ * EXPANN_ERR_UNSUPPORTED, checked before the device); 8-bit rows: 64, 128, 256, 768, 832, 960;
+ * int16 rows: 64, 128. */
 int expann_create(int dim, int dtype, int metric, int device, expann_index** out);
 void expann_destroy(expann_index* h);
 /* message of the last error on h (or of the last failed expann_create when h == NULL). */
