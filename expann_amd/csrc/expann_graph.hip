@@ -54,8 +54,43 @@ struct GraphVariant {
 };
 #define GRAPH_V(D) {D, false, graph_search_kernel<D, false>}, {D, true, graph_search_kernel<D, true>}
 const GraphVariant kGraph[] = {GRAPH_V(64),  GRAPH_V(128), GRAPH_V(256), GRAPH_V(512),
-                               GRAPH_V(768), GRAPH_V(832), GRAPH_V(960)};
+                               GRAPH_V(768), GRAPH_V(832), GRAPH_V(960), GRAPH_V(0)};
 #undef GRAPH_V
+// quantizer_simple<uint8_t> of n_values floats: launches of at most 2^30 values (a dispatch's grid is
+// counted in 32-bit work-items: 1.05 M rows x 4096 in one launch would wrap)
+void launch_quantize_simple_u8(const float* in, size_t n_values, uint8_t* out, hipStream_t st) {
+	const size_t chunk = size_t(1) << 30;
+	for (size_t off = 0; off < n_values; off += chunk) {
+		const size_t nv = std::min(chunk, n_values - off);
+		hipLaunchKernelGGL(quantize_simple_u8_kernel, dim3((uint32_t)((nv + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+		                   in + off, nv, out + off);
+	}
+}
+// the compiled instance of `dim`, else the run-time-dim one (d = 0)
+const GraphVariant* graph_variant(int dim, bool compressed) {
+	const GraphVariant* any = nullptr;
+	for (const auto& v : kGraph)
+		if (v.compressed == compressed) {
+			if (v.d == dim)
+				return &v;
+			if (v.d == 0)
+				any = &v;
+		}
+	return any;
+}
+// the dims the graph path takes (checked before any device lookup): a multiple of 16 up to 4096;
+// returns EXPANN_OK or the error, with its message in g_create_error
+int graph_dim_error(const char* fn, int dim) {
+	if (dim <= 0 || dim % 16 != 0) {
+		g_create_error = std::string(fn) + ": dim must be a positive multiple of 16";
+		return EXPANN_ERR_INVALID_ARG;
+	}
+	if ((uint32_t)dim > kGraphMaxAnyDim) {
+		g_create_error = std::string(fn) + ": dim " + std::to_string(dim) + " exceeds the graph path's limit of 4096";
+		return EXPANN_ERR_UNSUPPORTED;
+	}
+	return EXPANN_OK;
+}
 // the instrumented instance (EXPANN_GRAPH_STAMPS=1, d = 128): per-phase shader clocks of a hop
 const GraphVariant kGraphDbg[] = {{128, false, graph_search_kernel<128, false, 1>}, {128, true, graph_search_kernel<128, true, 1>}};
 }  // namespace
@@ -70,6 +105,8 @@ int expann_graph_create(int dim, int device, const float* vectors, size_t n, uin
 		return EXPANN_ERR_INVALID_ARG;
 	}
 	*out = nullptr;
+	if (int rc = graph_dim_error("expann_graph_create", dim))
+		return rc;
 	if (!vectors || !layer_offsets || n == 0 || n_layers == 0 || starting_vertex >= n ||
 	    n >= (1ull << 32) - 64 || (!neighbours && layer_offsets[(size_t)n_layers * (n + 1) - 1])) {
 		g_create_error = "expann_graph_create: bad arguments";
@@ -86,13 +123,6 @@ int expann_graph_create(int dim, int device, const float* vectors, size_t n, uin
 			g_create_error = "expann_graph_create: layer_offsets decrease";
 			return EXPANN_ERR_INVALID_ARG;
 		}
-	bool dim_ok = false;
-	for (const auto& v : kGraph)
-		dim_ok |= v.d == dim;
-	if (!dim_ok) {
-		g_create_error = "graph search is built for dim 64, 128, 256, 512, 768, 832, 960";
-		return EXPANN_ERR_UNSUPPORTED;
-	}
 	const uint64_t n_edges = layer_offsets[(size_t)n_layers * (n + 1) - 1];
 	if (n_edges >= (1ull << 32)) {
 		g_create_error = "more than 2^32 edges";
@@ -220,11 +250,10 @@ int expann_graph_search(expann_graph* g, const float* queries, size_t m, size_t 
 		return g->fail(EXPANN_ERR_INVALID_ARG, "NULL pointer");
 	if (ef_search > 4096)
 		return g->fail(EXPANN_ERR_UNSUPPORTED, "ef_search > 4096");
+	if (use_compression && g->dim % 64 != 0)  // (the reference's dist2_compressed works in 64-dim blocks)
+		return g->fail(EXPANN_ERR_UNSUPPORTED, "the uint8 walk (use_compression) needs dim % 64 == 0");
 	HIP_TRY(g, hipSetDevice(g->device));
-	const GraphVariant* gv = nullptr;
-	for (const auto& v : kGraph)
-		if (v.d == g->dim && v.compressed == (use_compression != 0))
-			gv = &v;
+	const GraphVariant* gv = graph_variant(g->dim, use_compression != 0);
 	if (!gv)
 		return g->fail(EXPANN_ERR_UNSUPPORTED, "no graph kernel for this dim");
 	const bool stamps = std::getenv("EXPANN_GRAPH_STAMPS") != nullptr && g->dim == 128;
@@ -234,9 +263,7 @@ int expann_graph_search(expann_graph* g, const float* queries, size_t m, size_t 
 	if (use_compression && !g->d_compressed) {  // quantizer_simple<uint8_t>::build, :485-486
 		HIP_TRY(g, hipMalloc(&g->d_compressed, g->n * (size_t)g->dim));
 		const size_t nv = g->n * (size_t)g->dim;
-		hipLaunchKernelGGL(quantize_simple_u8_kernel, dim3((uint32_t)((nv + kBlock - 1) / kBlock)),
-		                   dim3(kBlock), 0, g->stream, (const float*)g->d_vectors, nv,
-		                   g->d_compressed);
+		launch_quantize_simple_u8(g->d_vectors, nv, g->d_compressed, g->stream);
 		HIP_TRY(g, hipGetLastError());
 	}
 	DevBuf b_q, b_ids, b_d, b_dc;
@@ -282,6 +309,7 @@ int expann_graph_search(expann_graph* g, const float* queries, size_t m, size_t 
 		p.out_distcomps = d_dc;
 		p.error = g->d_error;
 		p.next_query = g->d_error + 1;
+		p.dim = (uint32_t)g->dim;
 		if (const char* e = std::getenv("EXPANN_GRAPH_DEBUG"))
 			p.debug = (uint32_t)std::atol(e);
 		if (stamps) {
@@ -290,8 +318,10 @@ int expann_graph_search(expann_graph* g, const float* queries, size_t m, size_t 
 			HIP_TRY(g, hipMemsetAsync(b_stamps.p, 0, sizeof(unsigned long long) * 8 * g->slots, g->stream));
 			p.stamps = b_stamps.as<unsigned long long>();
 		}
-		const size_t lds = sizeof(md_pair) * (p.ef + 1 + p.cand_cap + 1) +
-		                   (sizeof(uint32_t) + sizeof(float)) * p.list_cap;
+		size_t lds = sizeof(md_pair) * (p.ef + 1 + p.cand_cap + 1) +
+		             (sizeof(uint32_t) + sizeof(float)) * p.list_cap;
+		if (gv->d == 0)  // the run-time-dim instance: the query (and its bytes) in LDS
+			lds += (size_t)g->dim * (sizeof(float) + (use_compression ? 1 : 0));
 		if (lds > 160 * 1024)
 			return g->fail(EXPANN_ERR_UNSUPPORTED, "graph search working set exceeds LDS");
 		HIP_TRY(g, hipFuncSetAttribute((const void*)gv->fn, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -406,7 +436,7 @@ struct BuildVariant {
 };
 #define BUILD_V(D) {D, build_search_kernel<D>, build_prune_kernel<D>}
 const BuildVariant kBuild[] = {BUILD_V(64),  BUILD_V(128), BUILD_V(256), BUILD_V(512),
-                               BUILD_V(768), BUILD_V(832), BUILD_V(960)};
+                               BUILD_V(768), BUILD_V(832), BUILD_V(960), BUILD_V(0)};
 #undef BUILD_V
 struct BuildFail {
 	std::string msg;
@@ -419,14 +449,12 @@ int expann_graph_build_batched(int dim, int device, const float* vectors, size_t
                                float ortho_bias, size_t max_batch, uint32_t* ids0, float* d0, uint32_t* deg0,
                                size_t stride0, const int32_t* upper_idx, size_t U, size_t n_upper_layers,
                                uint32_t* idsu, float* du, uint32_t* degu, size_t strideu, uint64_t* stats) {
-	const BuildVariant* bv = nullptr;
+	if (int rc = graph_dim_error("expann_graph_build_batched", dim))
+		return rc;
+	const BuildVariant* bv = &kBuild[sizeof(kBuild) / sizeof(kBuild[0]) - 1];  // (d = 0: run-time dim)
 	for (const auto& v : kBuild)
 		if (v.d == dim)
 			bv = &v;
-	if (!bv) {
-		g_create_error = "graph build is compiled for dim 64, 128, 256, 512, 768, 832, 960";
-		return EXPANN_ERR_UNSUPPORTED;
-	}
 	if (!vectors || !levels || !max_layer_io || !starting_vertex_io || !ids0 || !d0 || !deg0 || !upper_idx ||
 	    n == 0 || n_built == 0 || n_built > n || n >= (1ull << 32) - 64 || M < 2 || M0 < M || stride0 < M0 ||
 	    (n_upper_layers && (!idsu || !du || !degu || strideu < M)) || ef_construction == 0 ||
@@ -504,7 +532,10 @@ int expann_graph_build_batched(int dim, int device, const float* vectors, size_t
 	const uint32_t list_cap = (uint32_t)std::max(stride0, std::max(strideu, ef_construction));
 	uint32_t cand_cap = 8192;
 	const size_t search_lds = sizeof(md_pair) * (ef_construction + 1 + cand_cap + 1) +
-	                          (sizeof(uint32_t) + sizeof(float)) * list_cap + 8 * sizeof(uint32_t);
+	                          (sizeof(uint32_t) + sizeof(float)) * list_cap + 8 * sizeof(uint32_t) +
+	                          (bv->d == 0 ? (size_t)dim * sizeof(float) : 0);  // (run-time dim: the new row in LDS)
+	// the prune kernel of the run-time-dim instance keeps the kept edge's row in dynamic LDS
+	const size_t prune_lds = bv->d == 0 ? (size_t)dim * sizeof(float) : 0;
 	HIP_TRY(fh, hipFuncSetAttribute((const void*)bv->search, hipFuncAttributeMaxDynamicSharedMemorySize, (int)search_lds));
 	uint64_t slots = (uint64_t)cus * 2;  // resident search workgroups (two 72 KB workgroups per CU)
 	// one visited bitset per resident workgroup, all zero between searches (graph_search.hpp)
@@ -574,6 +605,7 @@ int expann_graph_build_batched(int dim, int device, const float* vectors, size_t
 		sp.out = b_out.as<md_pair>();
 		sp.out_cnt = b_outc.as<uint32_t>();
 		sp.error = ctr + 2;
+		sp.dim = (uint32_t)dim;
 		hipLaunchKernelGGL(bv->search, dim3((uint32_t)std::min<uint64_t>(B, slots)), dim3(64), search_lds, st, sp);
 		BuildPruneParams pp{};
 		pp.g = g;
@@ -585,7 +617,8 @@ int expann_graph_build_batched(int dim, int device, const float* vectors, size_t
 		pp.ortho_factor = ortho_factor;
 		pp.ortho_bias = ortho_bias;
 		pp.prune_overflow = (uint32_t)prune_overflow;
-		hipLaunchKernelGGL(bv->prune, dim3(std::min<uint32_t>(n_tasks, (uint32_t)cus * 16)), dim3(kPruneThreads), 0, st, pp);
+		pp.dim = (uint32_t)dim;
+		hipLaunchKernelGGL(bv->prune, dim3(std::min<uint32_t>(n_tasks, (uint32_t)cus * 16)), dim3(kPruneThreads), prune_lds, st, pp);
 		BuildReverseParams rp{};
 		rp.g = g;
 		rp.tasks = b_tasks.as<PruneTask>();
@@ -602,7 +635,7 @@ int expann_graph_build_batched(int dim, int device, const float* vectors, size_t
 		dp.tasks = nullptr;
 		dp.n_tasks = ctr;
 		dp.dirty = b_dirty.as<uint2>();
-		hipLaunchKernelGGL(bv->prune, dim3((uint32_t)cus * 16), dim3(kPruneThreads), 0, st, dp);
+		hipLaunchKernelGGL(bv->prune, dim3((uint32_t)cus * 16), dim3(kPruneThreads), prune_lds, st, dp);
 		HIP_TRY(fh, hipGetLastError());
 		uint32_t h_ctr[4];
 		HIP_TRY(fh, hipMemcpyAsync(h_ctr, ctr, sizeof(h_ctr), hipMemcpyDeviceToHost, st));
@@ -666,8 +699,14 @@ extern "C" {
 int expann_antitopo_create(int dim, int device, size_t M, size_t ef_construction,
                            size_t ortho_count, size_t prune_overflow, int use_compression,
                            expann_antitopo** out) {
-	if (!out || dim <= 0 || dim % 64 != 0 || M < 2 || ef_construction == 0) {
-		g_create_error = "expann_antitopo_create: bad arguments (dim % 64 == 0, M >= 2)";
+	if (!out || dim <= 0 || dim % 16 != 0 || M < 2 || ef_construction == 0) {
+		g_create_error = "expann_antitopo_create: bad arguments (dim % 16 == 0, M >= 2)";
+		return EXPANN_ERR_INVALID_ARG;
+	}
+	if (int rc = graph_dim_error("expann_antitopo_create", dim))
+		return rc;
+	if (use_compression && dim % 64 != 0) {  // (the uint8 walk works in 64-dim blocks)
+		g_create_error = "expann_antitopo_create: use_compression needs dim % 64 == 0";
 		return EXPANN_ERR_INVALID_ARG;
 	}
 	if (expann_device_count() <= 0) {
@@ -768,8 +807,7 @@ int expann_quantize_simple_u8_device(int device, const float* d_rows, size_t n_v
 		g_create_error = "hipSetDevice failed";
 		return EXPANN_ERR_HIP;
 	}
-	hipLaunchKernelGGL(quantize_simple_u8_kernel, dim3((uint32_t)((n_values + kBlock - 1) / kBlock)),
-	                   dim3(kBlock), 0, (hipStream_t)stream, d_rows, n_values, d_out);
+	launch_quantize_simple_u8(d_rows, n_values, d_out, (hipStream_t)stream);
 	if (hipGetLastError() != hipSuccess) {
 		g_create_error = "quantize_simple_u8_kernel launch failed";
 		return EXPANN_ERR_HIP;

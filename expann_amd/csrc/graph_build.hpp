@@ -71,17 +71,20 @@ struct BuildSearchParams {
 	md_pair* out;
 	uint32_t* out_cnt;            // [slots]
 	uint32_t* error;              // candidates heap overflow
+	uint32_t dim;                 // D = 0 instance only: the row length
 };
 
+// D = 0: the run-time-dim instance (p.dim, graph_search.hpp); the new vertex's row sits in LDS behind ndist
 template <int D>
 __global__ __launch_bounds__(64) void build_search_kernel(BuildSearchParams p) {
-	constexpr int DPL = D / 16;
+	constexpr int DPL = D ? D / 16 : 1;
 	constexpr int U = graph_rows_f32<D>();  // rows in flight per 16-lane group
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
 	md_pair* nearest = reinterpret_cast<md_pair*>(smem_raw);             // [ef + 1]
 	md_pair* candidates = nearest + (p.ef + 1);                          // [cand_cap + 1]
 	uint32_t* nlist = reinterpret_cast<uint32_t*>(candidates + (p.cand_cap + 1));  // [list_cap]
 	float* ndist = reinterpret_cast<float*>(nlist + p.list_cap);
+	float* qs = ndist + p.list_cap;  // D = 0: [dim]
 	const int lane = threadIdx.x;
 	const int l = lane & 15, rg = lane >> 4;
 	// visited set of this workgroup: a bitset, all zero between searches (graph_search.hpp)
@@ -90,13 +93,21 @@ __global__ __launch_bounds__(64) void build_search_kernel(BuildSearchParams p) {
 
 	for (uint32_t v = p.b0 + blockIdx.x; v < p.b1; v += gridDim.x) {
 		float q[DPL];
+		if constexpr (D == 0) {
+			(void)stage_query_any(p.g.vec + (size_t)v * p.dim, p.dim, qs, nullptr, false, lane);
+		} else {
 #pragma unroll
-		for (int t = 0; t < DPL; ++t)
-			q[t] = p.g.vec[(size_t)v * D + l + 16 * t];
+			for (int t = 0; t < DPL; ++t)
+				q[t] = p.g.vec[(size_t)v * D + l + 16 * t];
+		}
 		// exact fp32 squared L2 of the new vertex against UU rows per 16-lane group (reference order), all
 		// rows requested before the first is consumed
 		auto dist_rows = [&](auto u_tag, const uint32_t* rows, float* d) {
 			constexpr int UU = decltype(u_tag)::value;
+			if constexpr (D == 0) {
+				dist_f32_rows_any<UU>(p.g.vec, p.dim, qs, rows, d, l);
+				return;
+			}
 			float r[UU][DPL];
 #pragma unroll
 			for (int u = 0; u < UU; ++u) {
@@ -309,6 +320,7 @@ struct BuildPruneParams {
 	uint32_t ef;
 	float ortho_factor, ortho_bias;
 	uint32_t prune_overflow;
+	uint32_t dim;                 // D = 0 instance only: the row length (row_s is dynamic LDS, dim floats)
 };
 constexpr int kPruneThreads = 256;
 constexpr int kPruneMaxCand = 1024;  // candidates per list (ef_construction, or cap + slack)
@@ -320,7 +332,10 @@ __global__ __launch_bounds__(kPruneThreads) void build_prune_kernel(BuildPrunePa
 	__shared__ float red_v[kPruneThreads / 64];
 	__shared__ uint32_t red_i[kPruneThreads / 64];
 	__shared__ uint32_t sel_s;
-	__shared__ float row_s[D];
+	__shared__ float row_st[D ? D : 1];
+	extern __shared__ __attribute__((aligned(16))) float row_dyn[];
+	float* row_s = D ? row_st : row_dyn;
+	const uint32_t dim = D ? D : p.dim;
 	const uint32_t tid = threadIdx.x;
 	const uint32_t n_tasks = *p.n_tasks;
 	for (uint32_t t = blockIdx.x; t < n_tasks; t += gridDim.x) {
@@ -428,8 +443,8 @@ __global__ __launch_bounds__(kPruneThreads) void build_prune_kernel(BuildPrunePa
 				row_ids[kept] = sid;
 				row_d[kept] = key_score(ks);
 			}
-			for (uint32_t i = tid; i < D; i += kPruneThreads)
-				row_s[i] = p.g.vec[(size_t)sid * D + i];
+			for (uint32_t i = tid; i < dim; i += kPruneThreads)
+				row_s[i] = p.g.vec[(size_t)sid * dim + i];
 #pragma unroll
 			for (int j = 0; j < PER; ++j)
 				if (tid + j * kPruneThreads == s)
@@ -443,12 +458,12 @@ __global__ __launch_bounds__(kPruneThreads) void build_prune_kernel(BuildPrunePa
 			for (int j = 0; j < PER; ++j) {
 				if (!alive[j] || res[j] == 3.402823466e+38f)
 					continue;
-				const float* rc = p.g.vec + (size_t)cid[j] * D;
+				const float* rc = p.g.vec + (size_t)cid[j] * dim;
 				float acc[16];
 #pragma unroll
 				for (int ll = 0; ll < 16; ++ll)
 					acc[ll] = 0.0f;
-				for (int t0 = 0; t0 < D; t0 += 16) {
+				for (int t0 = 0; t0 < (int)dim; t0 += 16) {
 					const float4* r4 = reinterpret_cast<const float4*>(rc + t0);
 					const float4 v0 = r4[0], v1 = r4[1], v2 = r4[2], v3 = r4[3];
 					const float rv[16] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w,

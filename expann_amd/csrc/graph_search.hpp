@@ -65,6 +65,7 @@ struct GraphSearchParams {
 	// workgroup spent in {0 per-query setup + descent, 1 pop + broadcast, 2 adjacency + visited tests,
 	// 3 row gathers + scoring, 4 serial queue update, 5 output}, 6 = hops, 7 = queue insertions
 	unsigned long long* stamps;
+	uint32_t dim;                 // run-time-dim instance (D = 0) only: the row length (the others have it as D)
 };
 
 struct md_pair {
@@ -347,15 +348,163 @@ __global__ __launch_bounds__(64) void heap_trace_kernel(HeapTraceParams p) {
 		heap_trace_body<false>(p, v, (int)threadIdx.x);
 }
 
+// ---- run-time dim (D = 0 instances of the walk and of the builder's search) ----------------------
+// Any dim that is a multiple of 16 up to kGraphMaxAnyDim (uint8: of 64).  The query sits in LDS (a
+// register copy would be dim / 16 floats per lane); a row is read in chunks of kGraphAnyChunk dims per
+// lane with kGraphAnyRows rows in flight per 16-lane group, and every row's accumulator is carried from
+// chunk to chunk: lane l still runs fma(diff, diff, acc) over t = 0 ... dim/16 - 1 in ascending order,
+// then reduce16_ref_order -- the compiled instances' (and the reference's) arithmetic, bit for bit.
+constexpr uint32_t kGraphMaxAnyDim = 4096;
+constexpr int kGraphAnyRows = 4;
+constexpr int kGraphAnyChunk = 16;   // fp32: dims per lane and chunk (256 per row)
+constexpr int kGraphAnyChunkU8 = 8;  // uint8: dwords per lane and chunk (512 B per row)
+
+// fp32 squared L2 of the query qs[dim] (LDS) against U rows per 16-lane group
+template <int U>
+__device__ inline void dist_f32_rows_any(const float* vectors, uint32_t dim, const float* qs, const uint32_t* rows,
+                                         float* d, int l) {
+	const uint32_t dpl = dim / 16;
+	const float* src[U];
+	float acc[U];
+#pragma unroll
+	for (int u = 0; u < U; ++u) {
+		src[u] = vectors + (size_t)rows[u] * dim + l;
+		acc[u] = 0.0f;
+	}
+	uint32_t t0 = 0;
+	for (; t0 + kGraphAnyChunk <= dpl; t0 += kGraphAnyChunk) {
+		float r[U][kGraphAnyChunk];
+#pragma unroll
+		for (int u = 0; u < U; ++u)
+#pragma unroll
+			for (int t = 0; t < kGraphAnyChunk; ++t)
+				r[u][t] = src[u][16 * (t0 + t)];
+#pragma unroll
+		for (int t = 0; t < kGraphAnyChunk; ++t) {
+			const float qv = qs[l + 16 * (t0 + t)];
+#pragma unroll
+			for (int u = 0; u < U; ++u) {
+				const float diff = qv - r[u][t];
+				acc[u] = __builtin_fmaf(diff, diff, acc[u]);
+			}
+		}
+	}
+	if (t0 < dpl) {  // the last, partial chunk (wave-uniform tests: nothing is read past the row)
+		float r[U][kGraphAnyChunk];
+#pragma unroll
+		for (int t = 0; t < kGraphAnyChunk; ++t)
+			if (t0 + t < dpl)
+#pragma unroll
+				for (int u = 0; u < U; ++u)
+					r[u][t] = src[u][16 * (t0 + t)];
+#pragma unroll
+		for (int t = 0; t < kGraphAnyChunk; ++t) {
+			if (t0 + t < dpl) {
+				const float qv = qs[l + 16 * (t0 + t)];
+#pragma unroll
+				for (int u = 0; u < U; ++u) {
+					const float diff = qv - r[u][t];
+					acc[u] = __builtin_fmaf(diff, diff, acc[u]);
+				}
+			}
+		}
+	}
+#pragma unroll
+	for (int u = 0; u < U; ++u)
+		d[u] = reduce16_ref_order(acc[u]);
+}
+
+// uint8 squared L2 (kU8L2, exact integers: any lane split gives the same sum) of the query's truncated
+// bytes q8s[dim / 4] (LDS, packed) against U rows per 16-lane group; lane l takes dwords l, l + 16, ...
+// of a row (dim % 64 == 0).  q8self = the query's sum of squares.
+template <int U>
+__device__ inline void dist_u8_rows_any(const uint8_t* compressed, uint32_t dim, const int* q8s, int q8self,
+                                        const uint32_t* rows, float* d, int l) {
+	const uint32_t nw = dim / 64;
+	const int* src[U];
+	int acc[U], bself[U];
+#pragma unroll
+	for (int u = 0; u < U; ++u) {
+		src[u] = reinterpret_cast<const int*>(compressed + (size_t)rows[u] * dim) + l;
+		acc[u] = 0;
+		bself[u] = 0;
+	}
+	uint32_t w0 = 0;
+	for (; w0 + kGraphAnyChunkU8 <= nw; w0 += kGraphAnyChunkU8) {
+		int b[U][kGraphAnyChunkU8];
+#pragma unroll
+		for (int u = 0; u < U; ++u)
+#pragma unroll
+			for (int w = 0; w < kGraphAnyChunkU8; ++w)
+				b[u][w] = src[u][16 * (w0 + w)];
+#pragma unroll
+		for (int w = 0; w < kGraphAnyChunkU8; ++w) {
+			const int qv = q8s[l + 16 * (w0 + w)];
+#pragma unroll
+			for (int u = 0; u < U; ++u) {
+				bself[u] = dot4<kU8L2>(b[u][w], b[u][w], bself[u]);
+				acc[u] = dot4<kU8L2>(qv, b[u][w], acc[u]);
+			}
+		}
+	}
+	if (w0 < nw) {
+		int b[U][kGraphAnyChunkU8];
+#pragma unroll
+		for (int w = 0; w < kGraphAnyChunkU8; ++w)
+			if (w0 + w < nw)
+#pragma unroll
+				for (int u = 0; u < U; ++u)
+					b[u][w] = src[u][16 * (w0 + w)];
+#pragma unroll
+		for (int w = 0; w < kGraphAnyChunkU8; ++w) {
+			if (w0 + w < nw) {
+				const int qv = q8s[l + 16 * (w0 + w)];
+#pragma unroll
+				for (int u = 0; u < U; ++u) {
+					bself[u] = dot4<kU8L2>(b[u][w], b[u][w], bself[u]);
+					acc[u] = dot4<kU8L2>(qv, b[u][w], acc[u]);
+				}
+			}
+		}
+	}
+#pragma unroll
+	for (int u = 0; u < U; ++u)
+		d[u] = (float)(reduce16_i32(bself[u] - 2 * acc[u]) + q8self);
+}
+
+// row `row` of `src` (fp32, dim floats) -> qs; for the uint8 walk also its truncated bytes -> q8s
+// (packed as the rows are) and their sum of squares.  Called by the whole wave; ends with the LDS in place.
+__device__ inline int stage_query_any(const float* src, uint32_t dim, float* qs, int* q8s, bool bytes, int lane) {
+	for (uint32_t i = lane; i < dim; i += 64)
+		qs[i] = src[i];
+	if (bytes)
+		for (uint32_t w = lane; w < dim / 4; w += 64) {
+			unsigned packed = 0;
+#pragma unroll
+			for (int b = 0; b < 4; ++b)
+				packed |= ((unsigned)(uint8_t)(uint32_t)src[4 * w + b]) << (8 * b);
+			q8s[w] = (int)packed;
+		}
+	wave_lds_sync();
+	int self = 0;
+	if (bytes) {
+		for (uint32_t w = lane & 15; w < dim / 4; w += 16)
+			self = dot4<kU8L2>(q8s[w], q8s[w], self);
+		self = reduce16_i32(self);
+	}
+	return self;
+}
+
 // rows in flight per 16-lane group while a hop's neighbours are scored
-template <int D> constexpr int graph_rows_f32() { return D <= 128 ? 8 : (D <= 256 ? 4 : 2); }
-template <int D> constexpr int graph_rows_u8() { return D <= 128 ? 16 : (D <= 256 ? 8 : 4); }
+template <int D> constexpr int graph_rows_f32() { return D == 0 ? kGraphAnyRows : (D <= 128 ? 8 : (D <= 256 ? 4 : 2)); }
+template <int D> constexpr int graph_rows_u8() { return D == 0 ? kGraphAnyRows : (D <= 128 ? 16 : (D <= 256 ? 8 : 4)); }
 
 // (the uint8 walk waits on latency, not bandwidth: 128 registers = 16 waves per CU instead of 12)
+// D = 0: the run-time-dim instance (p.dim); the query and its bytes sit in LDS behind ndist
 template <int D, bool COMPRESSED, int DBG = 0>
-__global__ __launch_bounds__(64, (COMPRESSED && D <= 128) ? 4 : 1) void graph_search_kernel(GraphSearchParams p) {
-	constexpr int DPL = D / 16;
-	constexpr int NW = D / 64;
+__global__ __launch_bounds__(64, D == 0 ? 3 : ((COMPRESSED && D <= 128) ? 4 : 1)) void graph_search_kernel(GraphSearchParams p) {
+	constexpr int DPL = D ? D / 16 : 1;
+	constexpr int NW = D ? D / 64 : 1;
 	unsigned long long seg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ts = DBG ? clock64() : 0;
 	auto stamp = [&](int i) {
 		if (DBG) {
@@ -369,6 +518,8 @@ __global__ __launch_bounds__(64, (COMPRESSED && D <= 128) ? 4 : 1) void graph_se
 	md_pair* candidates = nearest + (p.ef + 1);                          // [cand_cap + 1]
 	uint32_t* nlist = reinterpret_cast<uint32_t*>(candidates + (p.cand_cap + 1));  // [list_cap]
 	float* ndist = reinterpret_cast<float*>(nlist + p.list_cap);          // [list_cap]
+	float* qs = ndist + p.list_cap;                                       // D = 0: [dim] the query
+	int* q8s = reinterpret_cast<int*>(qs + p.dim);                        // D = 0, COMPRESSED: [dim / 4] its bytes
 
 	const int lane = threadIdx.x;
 	const int l = lane & 15, rg = lane >> 4;
@@ -404,29 +555,37 @@ __global__ __launch_bounds__(64, (COMPRESSED && D <= 128) ? 4 : 1) void graph_se
 		}
 		const uint8_t ep8 = (uint8_t)epoch;
 		float q[DPL];
-#pragma unroll
-		for (int t = 0; t < DPL; ++t)
-			q[t] = p.queries[(size_t)qi * D + l + 16 * t];
 		int q8[NW];  // trunc(query) bytes of this lane (compressed path)
 		int q8self = 0;
-		if (COMPRESSED) {
+		if constexpr (D == 0) {
+			q8self = stage_query_any(p.queries + (size_t)qi * p.dim, p.dim, qs, q8s, COMPRESSED, lane);
+		} else {
 #pragma unroll
-			for (int w = 0; w < NW; ++w) {
-				unsigned packed = 0;
+			for (int t = 0; t < DPL; ++t)
+				q[t] = p.queries[(size_t)qi * D + l + 16 * t];
+			if (COMPRESSED) {
 #pragma unroll
-				for (int b = 0; b < 4; ++b) {
-					const float v = p.queries[(size_t)qi * D + l * (D / 16) + 4 * w + b];
-					packed |= ((unsigned)(uint8_t)(uint32_t)v) << (8 * b);
+				for (int w = 0; w < NW; ++w) {
+					unsigned packed = 0;
+#pragma unroll
+					for (int b = 0; b < 4; ++b) {
+						const float v = p.queries[(size_t)qi * D + l * (D / 16) + 4 * w + b];
+						packed |= ((unsigned)(uint8_t)(uint32_t)v) << (8 * b);
+					}
+					q8[w] = (int)packed;
+					q8self = dot4<kU8L2>(q8[w], q8[w], q8self);
 				}
-				q8[w] = (int)packed;
-				q8self = dot4<kU8L2>(q8[w], q8[w], q8self);
+				q8self = reduce16_i32(q8self);
 			}
-			q8self = reduce16_i32(q8self);
 		}
 		// exact fp32 squared L2 of the query against U rows per 16-lane group (reference order), all
 		// rows requested before the first is consumed
 		auto dist_f32_rows = [&](auto u_tag, const uint32_t* rows, float* d) {
 			constexpr int U = decltype(u_tag)::value;
+			if constexpr (D == 0) {
+				dist_f32_rows_any<U>(p.vectors, p.dim, qs, rows, d, l);
+				return;
+			}
 			float r[U][DPL];
 #pragma unroll
 			for (int u = 0; u < U; ++u) {
@@ -448,6 +607,10 @@ __global__ __launch_bounds__(64, (COMPRESSED && D <= 128) ? 4 : 1) void graph_se
 		};
 		auto dist_u8_rows = [&](auto u_tag, const uint32_t* rows, float* d) {
 			constexpr int U = decltype(u_tag)::value;
+			if constexpr (D == 0) {
+				dist_u8_rows_any<U>(p.compressed, p.dim, q8s, q8self, rows, d, l);
+				return;
+			}
 			int b[U][NW];
 #pragma unroll
 			for (int u = 0; u < U; ++u) {
@@ -485,7 +648,8 @@ __global__ __launch_bounds__(64, (COMPRESSED && D <= 128) ? 4 : 1) void graph_se
 				const uint32_t e0 = off[entry], deg = off[entry + 1] - e0;
 				// first-improvement chain == first occurrence of the minimum, if it improves: the smallest
 				// (distance bits, list position) key of the list (distances are >= 0: their bits order them)
-				constexpr int UD = COMPRESSED ? (graph_rows_f32<D>() > 4 ? 4 : graph_rows_f32<D>()) : graph_rows_f32<D>();
+				// (run-time dim, uint8 walk: 2 rows, so that both row scorers fit the 168 registers without spilling)
+				constexpr int UD = COMPRESSED ? (D == 0 ? 2 : (graph_rows_f32<D>() > 4 ? 4 : graph_rows_f32<D>())) : graph_rows_f32<D>();
 				uint64_t best_key = ~0ull;
 				uint32_t best_nb = 0;
 				for (uint32_t i0 = 0; i0 < deg; i0 += 4 * UD) {

@@ -7,7 +7,8 @@
 //       --data sift|gauss --index out.index --queries out.queries --results out.results \
 //       [--ef 10,20,40] [--build-only 1] [--read-index 1] [--prune_overflow 0|1] [--batched 2048]
 //
-// Files: <queries> raw m*d float32; <results> for each (compression in {0,1}) x (ef in list):
+// Files: <queries> raw m*d float32; <results> for each (compression in {0,1}; 0 only when d % 64 != 0,
+// the uint8 walk works in 64-dim blocks) x (ef in list):
 // m*k uint64 ids, m*k float32 dists, m uint32 distcomps, in that order.  One JSON line per
 // configuration on stdout (time per query, distance evaluations), like the reference's
 // bench_data + RECORD_STATS (src/bench_data.h:20-28, src/antitopo_engine.h:254-257).
@@ -129,7 +130,7 @@ int main(int argc, char** argv) {
 		std::ofstream rf;
 		if (a.count("results"))
 			rf.open(a["results"], std::ios::binary);
-		for (int comp = 0; comp <= 1; ++comp)
+		for (int comp = 0; comp <= (d % 64 == 0 ? 1 : 0); ++comp)
 			for (size_t ef : efs) {
 				eng.conf.use_compression = comp != 0;
 				eng.set_ef_search(ef);

@@ -5,8 +5,9 @@ set_ef_search / name / param_list, plus `query_many` (batched) and index save/lo
 
 The reference compiles one module per dimension (expann_py_64/128/256/832/960,
 CMakeLists.txt:102-153) and zero-pads every row to that DIM (src/pyrunner.cpp:20-27); here the
-dimension is a constructor argument (default: the smallest supported multiple of 64 that holds
-the first rows) and rows are zero-padded the same way.  take_norms = L2-normalise each row before
+dimension is a constructor argument (default: from the first rows -- up to 960 the smallest dim
+with a compiled graph kernel that holds them, from 961 to 4096 the next multiple of 64, so that
+both compression modes work) and rows are zero-padded the same way.  Wider rows raise ValueError.  take_norms = L2-normalise each row before
 storing (angular data = normalise + L2, src/pyrunner.cpp:78-79); the normalisation itself is
 Eigen's in the reference (summation order unpinned) and numpy float32 here.
 """
@@ -16,7 +17,8 @@ import numpy as np
 
 from . import _lib
 
-_SUPPORTED_DIMS = (64, 128, 256, 512, 768, 832, 960)
+_SUPPORTED_DIMS = (64, 128, 256, 512, 768, 832, 960)  # dims with compiled graph kernels
+_MAX_DIM = 4096  # the graph path's limit (run-time-dim kernels above 960)
 
 
 class AntitopoEngine:
@@ -32,9 +34,11 @@ class AntitopoEngine:
             self._open(int(dim))
 
     def _open(self, dim):
+        if dim > _MAX_DIM:
+            raise ValueError(f"dimension {dim} exceeds the graph engine's limit of {_MAX_DIM}")
         padded = next((d for d in _SUPPORTED_DIMS if d >= dim), None)
         if padded is None:
-            raise ValueError(f"dimension {dim} exceeds the built graph kernels {_SUPPORTED_DIMS}")
+            padded = (dim + 63) // 64 * 64
         h = C.c_void_p()
         M, efc, oc, po, uc = self._args
         rc = self._L.expann_antitopo_create(padded, self.device, M, efc, oc, po, int(uc), C.byref(h))

@@ -234,7 +234,10 @@ typedef struct expann_graph expann_graph;
 /* Upload a built graph (replaces the tail of antitopo_engine::_build, src/antitopo_engine.h:
  * 467-493, after deserialize :994-1074): `vectors` [n][dim] fp32 (all_entries), CSR adjacency
  * per layer as flattened by include/expann/antitopo_index.h (hadj_flat): layer_offsets is
- * [n_layers][n+1] into `neighbours`; layer 0 is hadj_bottom.  Host arrays, copied. */
+ * [n_layers][n+1] into `neighbours`; layer 0 is hadj_bottom.  Host arrays, copied.
+ * dim: any multiple of 16 up to 4096 (64, 128, 256, 512, 768, 832, 960 compiled, the others
+ * run-time-dim kernels); not a multiple of 16 -> EXPANN_ERR_INVALID_ARG, over 4096 ->
+ * EXPANN_ERR_UNSUPPORTED, both before any device lookup. */
 int expann_graph_create(int dim, int device, const float* vectors, size_t n, uint32_t n_layers,
                         uint32_t starting_vertex, const uint64_t* layer_offsets,
                         const uint32_t* neighbours, expann_graph** out);
@@ -244,7 +247,8 @@ const char* expann_graph_last_error(const expann_graph* g);
  * the bottom-layer best-first search with queue size ef_search (:495-708), or with
  * use_compression != 0 over uint8 rows + final fp32 re-score (:710-851).  Host buffers:
  * ids[m][k] / dists[m][k] padded with UINT64_MAX / +inf; distcomps[m] (RECORD_STATS'
- * num_distcomps per query, :125-129) may be NULL. */
+ * num_distcomps per query, :125-129) may be NULL.  use_compression != 0 needs dim % 64 == 0
+ * (EXPANN_ERR_UNSUPPORTED otherwise, checked before the device is touched). */
 int expann_graph_search(expann_graph* g, const float* queries, size_t m, size_t k,
                         size_t ef_search, int use_compression, uint64_t* ids, float* dists,
                         uint32_t* distcomps);
@@ -261,7 +265,8 @@ double expann_graph_last_kernel_ms(const expann_graph* g);
  * layer 0 ids0 / d0 [n][stride0] + deg0[n]; layers 1.. idsu / du [(l-1) * U + upper_idx[v]][strideu] +
  * degu, upper_idx[v] = -1 for level-0 vertices.  On return rows hold at most M0 / M edges (id,
  * reference-order distance).  stats[4] (optional): batches, reverse edges dropped for want of slack,
- * rows re-pruned, 0.  ortho_count = 1 only (the reference's sweep, src/bench_runner.h:138). */
+ * rows re-pruned, 0.  ortho_count = 1 only (the reference's sweep, src/bench_runner.h:138).  dim: as
+ * expann_graph_create (multiple of 16 up to 4096, checked before any device lookup). */
 int expann_graph_build_batched(int dim, int device, const float* vectors, size_t n, const uint8_t* levels,
                                size_t n_built, uint32_t* max_layer_io, uint32_t* starting_vertex_io, size_t M,
                                size_t M0, size_t ef_construction, size_t prune_overflow, float ortho_factor,
@@ -274,7 +279,9 @@ int expann_graph_build_batched(int dim, int device, const float* vectors, size_t
  * host (include/expann/antitopo_index.h), queries on the GPU (expann_graph_search). */
 typedef struct expann_antitopo expann_antitopo;
 /* antitopo_engine(M, ef_construction, ortho_count, prune_overflow, use_compression),
- * src/antitopo_engine.h:157-166: M0 = 2M, ortho_factor = 0.5, ortho_bias = 0, ef_search_mult = 1 */
+ * src/antitopo_engine.h:157-166: M0 = 2M, ortho_factor = 0.5, ortho_bias = 0, ef_search_mult = 1.
+ * dim: any multiple of 16 up to 4096 (EXPANN_ERR_INVALID_ARG / EXPANN_ERR_UNSUPPORTED otherwise);
+ * use_compression != 0 needs dim % 64 == 0 (EXPANN_ERR_INVALID_ARG); all checked before the device. */
 int expann_antitopo_create(int dim, int device, size_t M, size_t ef_construction,
                            size_t ortho_count, size_t prune_overflow, int use_compression,
                            expann_antitopo** out);
