@@ -111,6 +111,7 @@ struct expann_index {
 		float key_mul = 0.0f;
 		const int *i_thp = nullptr, *i_bias = nullptr, *i_qself = nullptr;  // 8-bit logs: raw accumulators, scored by the gather
 		int i_mode = 0;
+		const float* i_rw = nullptr;  // (i_mode 3: the int8 filter of fp32 rows)
 	} pending_scatter;
 	GrowPtr<float> d_sample;         // [m][n_chunks][32] class maxima of the fp16 / int8 sample pass
 	GrowPtr<void> d_q_split;         // [m][2][dim] bf16 (or [m][dim] fp16)
@@ -121,6 +122,16 @@ struct expann_index {
 	DevPtr<float> d_qscale;          // [m_alloc] c_q: the power of two the fp16 filter sees a query multiplied by (inner product; L2: 1)
 	float f16_scale = 0.0f;          // power of two; 0 = not built
 	float f16_bnmax = 0.0f;          // max ||b||^2 (host copy lives in d_bnmax[2])
+	// int8 filter of fp32 rows (scan_gemm_i8f.hpp), built lazily beside the fp16 copy (whose sampled pass
+	// gives its thresholds) and dropped with it
+	DevPtr<void> d_base_i8f;         // [n padded to 64][dim] int8
+	DevPtr<int> d_bp_i8f;            // [n padded] integer row terms; kI8qPadBp on the padding
+	DevPtr<float> d_rw_i8f;          // [n] w_b (select pruning), +inf where bp was clamped
+	DevPtr<float> d_i8f_q;           // [3][m_alloc]: A_q, W_q (prelude), w_q (thresholds)
+	GrowPtr<void> d_q8f;             // [m][dim] int8 queries
+	size_t i8f_q_m = 0;
+	I8fConsts i8f{};
+	int i8f_state = 0;               // 0 not built, 1 built, 2 built but off for auto (lists too long), -1 unusable
 	DevPtr<float> d_theta;           // [m_alloc] (int32 thetas for the 8-bit GEMM form)
 	DevPtr<int> d_bias_i;            // [n] sum b^2 per row (8-bit L2 GEMM form), built lazily
 	DevPtr<int> d_qself;             // [m_alloc]
@@ -149,6 +160,7 @@ struct expann_index {
 	long opt_tail_chunks = 1;        // scan_gemm_f16x: the last round's row chunks three times finer (pick_tail_chunks)
 	long opt_persist = 1;            // scan_gemm_f16x: resident workgroups pull (query tile, row chunk) items per XCD
 	long opt_ip_rescale = 1;         // fp16 form, inner product: the filter sees each query times a power of two (f16_query_prep_kernel)
+	long opt_i8_filter = 1;          // fp32 L2 d = 128: the int8 filter (scan_gemm_i8f.hpp): 0 off, 1 auto, 2 wherever supported
 	long opt_scan_kernel = 0;        // 0 auto, 1 direct (scan_filter), 2 GEMM form on fp32 / int8
 	                                 // MFMA, 3 GEMM form on bf16 MFMA with the 3-term split
 	// profiling
@@ -425,7 +437,8 @@ const GemmBf16Variant kGemmBf16[] = {{64, scan_gemm_bf16x3_kernel<64>, "scan_gem
 
 using GemmF16Fn = void (*)(GemmF16Params);
 using SqnormFn = void (*)(const float*, uint32_t, float*);
-using F16PrepFn = void (*)(const float*, uint32_t, float, _Float16*, float*, uint32_t*, float*, uint32_t*, const float*, float*);
+using F16PrepFn = void (*)(const float*, uint32_t, float, _Float16*, float*, uint32_t*, float*, uint32_t*, const float*, float*,
+                          I8fQueryArgs);
 struct GemmF16Variant {
 	int d;
 	GemmF16Fn scan;
@@ -753,7 +766,7 @@ void launch_gather_logs(expann_index* h, hipStream_t st) {
 	const uint32_t n_groups = (ps.n_chunks + cpb - 1) / cpb;
 	GatherLogParams gp{h->d_log.as<const uint4>(), h->d_log_cnt.as<const uint32_t>(), ps.log_cap, ps.n_chunks,
 	                   ps.n_qtiles, ps.xcd_map, ps.m, n_groups, cpb, h->d_cnt, h->d_cand, ps.cap, ps.theta, ps.key_mul,
-	                   ps.i_thp, ps.i_bias, ps.i_qself, ps.i_mode};
+	                   ps.i_thp, ps.i_bias, ps.i_qself, ps.i_mode, ps.i_rw};
 	hipLaunchKernelGGL(gather_logs_kernel, dim3(ps.n_qtiles * 4 * n_groups), dim3(kBlock), 0, st, gp);
 }
 
@@ -900,6 +913,8 @@ const GemmI8qVariant kGemmI8x[] = {
 const GemmI8qVariant kGemmI8w[] = {
     GEMM_I8W(128, kU8L2, true, "U8L2"), GEMM_I8W(128, kI8L2, true, "I8L2"), GEMM_I8W(128, kI8IP, false, "I8IP"),
     GEMM_I8W(256, kU8L2, true, "U8L2"), GEMM_I8W(256, kI8L2, true, "I8L2"), GEMM_I8W(256, kI8IP, false, "I8IP")};
+// the int8 filter of fp32 rows (scan_gemm_i8f.hpp): the d = 128 i8w full scan on the index's int8 copy
+const GemmI8qVariant kGemmI8F = GEMM_I8W(128, kI8L2, true, "F32L2");
 #undef GEMM_I8W
 constexpr int kRetryGeneric = -1000;  // internal: the caller falls back to the threshold ladder
 constexpr int kStrictReject = -1001;  // internal (uint8 shadow): these queries are not 8-bit integers
@@ -918,6 +933,89 @@ const GemmI8qVariant* pick_gemm_i8q(const expann_index* h, size_t m, size_t k) {
 		if (v.d == h->dim && v.mode == h->int_mode)
 			return &v;
 	return nullptr;
+}
+
+// int8 filter of fp32 rows: clip of the scale (s = min(max |x|, kI8fClipRms rms) / 127)
+constexpr double kI8fClipRms = 5.5;
+// its lists over the fp16 form's expectation 1.2 k frac per query on iid rows (501 vs 176.5 at C2): the select's
+// stages are sized by it
+constexpr double kI8fListRatio = 2.8;
+// ... and where it stops paying: at C2's shape the form gains 0.36 ms per step at 501 candidates per query (iid rows)
+// and loses 0.67 ms at 963 (1 000 clusters); the straight line between crosses at ~660 = 3.4 x 1.2 k frac
+constexpr double kI8fBreakEvenRatio = 3.4;
+// The auto region, from the A/B sweep of the two forms over n = 0.5 / 0.75 / 1 / 2 M rows, m = 2 048 / 4 096 / 10 000
+// queries, k = 1 / 10 / 16 / 32 on iid rows (profiles/r06_i8f_sweep.json): every measured point inside is faster
+// by 4.8 % or more; k = 32 lost everywhere (up to -58 %), k = 10 at 500 k rows and at 1 M rows x 2 048 queries lost.
+// Shapes between the grid points take the nearest grid point below them in n and m, above them in k.
+bool i8f_auto_region(size_t n, size_t m, size_t k) {
+	if (k <= 1)
+		return n >= 500000 && m >= 2048;  // (+13 % .. +41 %)
+	if (k <= 10)
+		return (n >= 1000000 && m >= 4096) || (n >= 2000000 && m >= 2048);  // (+10 % .. +27 %)
+	if (k <= 16)
+		return (n >= 2000000 && m >= 2048) || (n >= 1000000 && m >= 10000);  // (+4.8 % .. +20 %)
+	return false;
+}
+// The int8 filter for fp32 rows (scan_gemm_i8f.hpp) serves this search?  fp32 rows, L2, d = 128, the uint8
+// shortcut not serving the index, no debug instance, the scan_kernel option on auto; option i8_filter = 2
+// wherever that holds, 1 (auto) above the thresholds below.
+bool i8f_wanted(const expann_index* h, size_t m, size_t k) {
+	if (h->opt_i8_filter == 0 || h->opt_scan_kernel != 0 || h->dtype != EXPANN_DTYPE_F32 ||
+	    h->metric != EXPANN_METRIC_L2 || h->dim != 128 || h->u8_exact == 1 || (h->opt_debug & ~16L) != 0 ||
+	    h->i8f_state < 0 || k > 256 || h->n < 2 * 256 * kF16TB)
+		return false;
+	if (h->opt_i8_filter == 2)
+		return true;
+	return h->i8f_state != 2 && i8f_auto_region(h->n, m, k);
+}
+// Candidates of one search above which the int8 filter loses to the fp16 form (kI8fBreakEvenRatio): rows in tight
+// clusters give it far longer lists than iid rows do.  Past this total an auto search turns the form off for the
+// index (i8f_state 2, until set_base_device brings other rows): the rows, not the shape, decided, and they do not
+// change between searches.
+uint64_t i8f_cand_limit(const expann_index* h, size_t m, size_t k) {
+	return (uint64_t)(kI8fBreakEvenRatio * 1.2 * (double)k * sample_frac_for(h, k) * (double)m);
+}
+
+// the index side of the int8 filter: scale from the rows' rms and max |x| (one fp64 reduction), the padded
+// int8 copy, bp and w_b per row (i8f_rows_kernel)
+int ensure_i8f(expann_index* h, hipStream_t st) {
+	if (h->i8f_state != 0)
+		return EXPANN_OK;
+	const size_t nv = h->n * (size_t)h->dim;
+	DevBuf tmp;
+	HIP_TRY(h, tmp.alloc(16));
+	HIP_TRY(h, hipMemsetAsync(tmp.p, 0, 16, st));
+	hipLaunchKernelGGL(i8f_stats_kernel, dim3(2048), dim3(kBlock), 0, st, (const float*)h->d_base, nv, tmp.as<double>(),
+	                   reinterpret_cast<uint32_t*>(tmp.as<double>() + 1));
+	unsigned char hb[16];
+	float bnmax = 0.0f;  // (the fp16 prelude's largest ||b||^2: B of the analysis)
+	HIP_TRY(h, hipMemcpyAsync(hb, tmp.p, 16, hipMemcpyDeviceToHost, st));
+	HIP_TRY(h, hipMemcpyAsync(&bnmax, h->d_bnmax + 2, sizeof(float), hipMemcpyDeviceToHost, st));
+	HIP_TRY(h, hipStreamSynchronize(st));
+	double sumsq;
+	float maxabs;
+	std::memcpy(&sumsq, hb, 8);
+	std::memcpy(&maxabs, hb + 8, 4);
+	const double rms = std::sqrt(sumsq / (double)nv);
+	const float clip = (float)std::min<double>(maxabs, kI8fClipRms * rms);
+	if (!(clip > 0.0f) || !std::isfinite(clip) || !std::isfinite(rms) || !std::isfinite(bnmax)) {
+		h->i8f_state = -1;
+		return EXPANN_OK;
+	}
+	h->i8f = i8f_consts(clip / 127.0f, (float)rms, bnmax, h->dim);
+	const size_t n_pad = (h->n + kF16TB - 1) / kF16TB * kF16TB;
+	HIP_TRY(h, hipMalloc(&h->d_base_i8f, n_pad * (size_t)h->dim));
+	HIP_TRY(h, hipMalloc(&h->d_bp_i8f, sizeof(int) * n_pad));
+	HIP_TRY(h, hipMalloc(&h->d_rw_i8f, sizeof(float) * h->n));
+	HIP_TRY(h, hipMemsetAsync(h->d_base_i8f, 0, n_pad * (size_t)h->dim, st));
+	hipLaunchKernelGGL(i8q_bp_kernel, dim3((uint32_t)((n_pad + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+	                   (const int*)nullptr, (uint32_t)h->n, (uint32_t)n_pad, h->d_bp_i8f.as<int>());
+	hipLaunchKernelGGL(i8f_rows_kernel<128>, dim3((uint32_t)((h->n + kRowsPerGroup - 1) / kRowsPerGroup)), dim3(kBlock), 0,
+	                   st, (const float*)h->d_base, (uint32_t)h->n, h->i8f, h->d_base_i8f.as<int8_t>(),
+	                   h->d_bp_i8f.as<int>(), h->d_rw_i8f.as<float>());
+	HIP_TRY(h, hipGetLastError());
+	h->i8f_state = 1;
+	return EXPANN_OK;
 }
 
 int ensure_i8q(expann_index* h, const GemmI8qVariant* gq, hipStream_t st) {
@@ -1237,8 +1335,9 @@ int absorb_shadow_profile(expann_index* h) {
 // (scan_direct_f16.hpp); otherwise the MFMA SAMPLE kernel + sample_tau_kernel.  *done stays false
 // when the index is too small for a sample (the caller runs the threshold ladder instead).
 int sampled_pass_f16(expann_index* h, const GemmF16Variant* gvf, size_t m, size_t k, bool ip, int cus,
-                     float* d_tau, uint32_t* d_tau_row, hipStream_t st, bool* done) {
+                     float* d_tau, uint32_t* d_tau_row, hipStream_t st, bool* done, bool i8f, bool* i8f_done) {
 	*done = false;
+	*i8f_done = false;
 	auto ensure_sample = [&](size_t need) -> int {
 		HIP_TRY(h, grow_ws(h, h->d_sample, need));
 		return EXPANN_OK;
@@ -1257,8 +1356,15 @@ int sampled_pass_f16(expann_index* h, const GemmF16Variant* gvf, size_t m, size_
 	tp.theta = h->d_theta;
 	tp.mul = 0.5f * h->f16_scale * h->f16_scale;
 	tp.cand_cnt = h->d_cnt;
+	if (i8f) {  // the int8 filter's thresholds from the same tau (scan_gemm_i8f.hpp)
+		tp.i8_aq = h->d_i8f_q;
+		tp.i8_wq_in = h->d_i8f_q + h->i8f_q_m;
+		tp.i8_wq = h->d_i8f_q + 2 * h->i8f_q_m;
+		tp.i8_thp = reinterpret_cast<int*>(h->d_i8f_q + 3 * h->i8f_q_m);
+		tp.i8_inv_2s2 = h->i8f.inv_2s2;
+	}
 
-	const DirectF16Variant* dvs = h->opt_scan_kernel == 0 ? pick_direct_f16(h->dim, m) : nullptr;
+	const DirectF16Variant* dvs = (h->opt_scan_kernel == 0 && !i8f) ? pick_direct_f16(h->dim, m) : nullptr;
 	if (dvs && dvs->sample) {
 		const uint32_t steps_all = (uint32_t)((h->n + dvs->rps - 1) / dvs->rps);
 		const uint32_t sel =
@@ -1335,6 +1441,47 @@ int sampled_pass_f16(expann_index* h, const GemmF16Variant* gvf, size_t m, size_
 	                   dim3((uint32_t)((m + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0, st, tp);
 	HIP_TRY(h, hipGetLastError());
 	*done = true;
+	*i8f_done = i8f;
+	return EXPANN_OK;
+}
+
+// The full scan of the int8 filter (scan_gemm_i8f.hpp): scan_gemm_i8w_kernel<128> over the index's int8 copy with
+// the thresholds of the fp16 sampled pass, hit logs filed by gather_logs_kernel in i_mode 3
+int launch_scan_i8f(expann_index* h, size_t m, int cus, uint32_t cap, hipStream_t st) {
+	const GemmI8qVariant* gs = &kGemmI8F;
+	const uint32_t nt = (uint32_t)((h->n + kF16TB - 1) / kF16TB);
+	const uint32_t nqt = (uint32_t)((m + kF16TQ - 1) / kF16TQ);
+	GemmI8qParams fp{};
+	fp.base = h->d_base_i8f;
+	fp.bp = h->d_bp_i8f;
+	fp.n_rows = (uint32_t)h->n;
+	fp.n_tiles_sel = nt;
+	fp.tile_stride = 1;
+	fp.tile_run = 1;
+	fp.n_qtiles = nqt;
+	fp.queries = h->d_q8f;
+	fp.thp = reinterpret_cast<const int*>(h->d_i8f_q + 3 * h->i8f_q_m);
+	fp.m = (uint32_t)m;
+	fp.cand_cnt = h->d_cnt;
+	fp.cand = h->d_cand;
+	fp.cap = cap;
+	uint32_t fchunks = pick_row_chunks(nt, nqt, (uint32_t)gs->wg_per_cu_w * (uint32_t)cus, 4.0, 8, 2048,
+	                                   h->opt_xcd_tolerance, (h->opt_debug & 1024) ? nullptr : &fp.xcd_map);
+	fp.tiles_per_block = (nt + fchunks - 1) / fchunks;
+	fchunks = (nt + fp.tiles_per_block - 1) / fp.tiles_per_block;
+	GemmI8wParams wp{};
+	wp.q = fp;
+	const int rc = ensure_hit_logs(h, fchunks * nqt, 4, m, cap, fchunks, nqt, fp.xcd_map, st, &wp.log, &wp.log_cnt,
+	                               &wp.log_cap);
+	if (rc != EXPANN_OK)
+		return rc;
+	wp.lost = h->d_overflow;
+	h->pending_scatter.i_thp = fp.thp;
+	h->pending_scatter.i_bias = fp.bp;
+	h->pending_scatter.i_qself = nullptr;
+	h->pending_scatter.i_rw = h->d_rw_i8f;
+	h->pending_scatter.i_mode = 3;
+	hipLaunchKernelGGL(gs->scan_w, dim3(fchunks * nqt), dim3((uint32_t)gs->threads_w), gs->lds_w, st, wp);
 	return EXPANN_OK;
 }
 
@@ -1500,6 +1647,10 @@ struct SearchPass {
 	const GemmI8Variant* gvi = nullptr;
 	const GemmBf16Variant* gvb = nullptr;
 	const GemmF16Variant* gvf = nullptr;
+	bool i8f = false;           // the int8 filter runs the full scan (fp16 prelude, scan_gemm_i8f.hpp)
+	bool i8f_ready = false;     // its thresholds of this attempt are written
+	bool i8f_off = false;       // its lists overflowed: the retry runs the fp16 form
+	bool i8f_ran = false;       // the last level of this attempt ran it
 	// what an attempt learned
 	bool flags_clean = false;   // the fp16 prelude has just zeroed the flag block
 	bool force_direct = false;  // a GEMM-form filter overflowed: massive near-ties
@@ -1551,6 +1702,7 @@ int SearchPass::choose_kernels() {
 		if (!gvf && f16kl_dim(h->dim))
 			gvf = &kGemmF16KL;
 	}
+	i8f = gvf && !i8f_off && i8f_wanted(h, m, k);
 	if ((h->opt_scan_kernel == 4 || h->opt_scan_kernel == 6) && !gvf && !no_f16)
 		return h->fail(EXPANN_ERR_UNSUPPORTED, "fp16 GEMM-form scan: f32 with dim a multiple of 16 from 64 to 4096 only");
 	if (gvf)
@@ -1579,6 +1731,30 @@ int SearchPass::prepare_queries(bool* restart) {
 		rc = ensure_workspace(h, m, cap);
 		if (rc != EXPANN_OK)
 			return rc;
+		I8fQueryArgs qa{};
+		if (i8f) {
+			rc = ensure_i8f(h, st);
+			if (rc != EXPANN_OK)
+				return rc;
+			i8f = h->i8f_state > 0;
+			if (i8f && h->opt_cand_capacity <= 0)  // (room for the lists of queries with a clipped component)
+				cap = std::max<uint32_t>(cap, 4096);
+		}
+		if (i8f) {  // int8 queries and the per-query terms [A_q | W_q | w_q | thp]
+			HIP_TRY(h, grow_ws(h, h->d_q8f, m * (size_t)h->dim));
+			if (m > h->i8f_q_m) {
+				if (h->async_pending > 0)
+					HIP_TRY(h, hipStreamSynchronize(h->async_stream));
+				h->d_i8f_q.reset();
+				h->i8f_q_m = 0;
+				HIP_TRY(h, hipMalloc(&h->d_i8f_q, 4 * sizeof(float) * m));
+				h->i8f_q_m = m;
+			}
+			qa.q8 = h->d_q8f.as<int8_t>();
+			qa.aq = h->d_i8f_q;
+			qa.wq = h->d_i8f_q + h->i8f_q_m;
+			qa.k = h->i8f;
+		}
 		const size_t nv = m * (size_t)h->dim;
 		HIP_TRY(h, grow_ws(h, h->d_q_split, nv * 4));
 		// scaled fp16 queries, ||q||^2, and the largest |q| (range check, read back at the end):
@@ -1602,7 +1778,7 @@ int SearchPass::prepare_queries(bool* restart) {
 			hipLaunchKernelGGL(gvf->prep, prep_grid, dim3(kBlock), 0, st, (const float*)d_queries, (uint32_t)m,
 			                   h->f16_scale, h->d_q_split.as<_Float16>(), h->d_qnrm, h->d_overflow + 2,
 			                   from_host ? h->d_q.as<float>() : (float*)nullptr, one_wg ? h->d_overflow : (uint32_t*)nullptr,
-			                   ip_ref, h->d_qscale.as<float>());
+			                   ip_ref, h->d_qscale.as<float>(), qa);
 		HIP_TRY(h, hipGetLastError());
 		if (from_host) {
 			d_queries = h->d_q;
@@ -1653,9 +1829,10 @@ int SearchPass::plan_thresholds() {
 	// intermediate candidate lists and selects
 	li_start = 0;
 	theta_ready = false;
+	i8f_ready = false;
 	if (gvf && h->opt_sample_pass && levels.size() >= 2) {
 		const int rs = sampled_pass_f16(h, gvf, m, k, ip, cus, h->d_tau[levels.size() & 1],
-		                                h->d_tau_row[levels.size() & 1], st, &theta_ready);
+		                                h->d_tau_row[levels.size() & 1], st, &theta_ready, i8f && !i8f_off, &i8f_ready);
 		if (rs != EXPANN_OK)
 			return rs;
 		if (theta_ready)
@@ -1694,6 +1871,9 @@ int SearchPass::run_level(size_t li) {
 	if (!first && !theta_ready)
 		HIP_TRY(h, hipMemsetAsync(h->d_cnt, 0, sizeof(uint32_t) * m, st));
 	const bool use_gemm = gv && !first;
+	const bool use_i8f = use_gemm && gvf && last && i8f && i8f_ready;  // (else the fp16 form scans)
+	if (last)
+		i8f_ran = use_i8f;
 	const bool timed = last && h->profiling && h->ev_used < kEventPairs;
 	uint32_t passes = n_qtiles;
 	const char* kname = sv->name;
@@ -1741,7 +1921,13 @@ int SearchPass::run_level(size_t li) {
 		gchunks = (gp.n_tiles_sel + gp.tiles_per_block - 1) / gp.tiles_per_block;
 		if (timed)
 			HIP_TRY(h, hipEventRecord(h->ev[h->ev_used][0], st));
-		if (gvf) {
+		if (use_i8f) {
+			const int rl = launch_scan_i8f(h, m, cus, cap, st);
+			if (rl != EXPANN_OK)
+				return rl;
+			kname = kGemmI8F.name;
+			gp.n_qtiles = (uint32_t)((m + kF16TQ - 1) / kF16TQ);
+		} else if (gvf) {
 			const int rl = launch_scan_f16(h, gvf, L.n_groups_sel * kRowsPerGroup, last, m, cus, ip, cap, st, &kname,
 			                               &gp.n_qtiles, &tq_small);
 			if (rl != EXPANN_OK)
@@ -1860,15 +2046,22 @@ int SearchPass::run_level(size_t li) {
 	                    : 0.0f;
 	sel.bn_max = h->d_bnmax ? h->d_bnmax + (gvf ? 2 : (gvb ? 1 : 0)) : nullptr;
 	sel.qnrm = (use_gemm && gvf) ? h->d_qnrm : nullptr;
+	if (use_i8f) {  // the int8 filter's own margins (scan_gemm_i8f.hpp) instead of the fp16 slack
+		sel.prune_eps = 0.0f;
+		sel.prune_abs = 0.0f;
+		sel.row_w = h->d_rw_i8f;
+		sel.q_w = h->d_i8f_q + 2 * h->i8f_q_m;
+	}
 	sel.overflow = h->d_overflow;
-	if (last && sel.cand_cnt && h->profiling)  // statistics: candidates of the full scan
+	if (last && sel.cand_cnt && (h->profiling || use_i8f))  // statistics: candidates of the full scan (i8f_cand_limit)
 		hipLaunchKernelGGL(sum_u32_kernel, dim3(1), dim3(1024), 0, st, sel.cand_cnt, (uint32_t)m,
 		                   h->d_total);
 	if (m <= 64) {
 		sel.wave0_short = 1;  // latency mode: one launch, wave 0 orders the short lists
 	} else if (sel.rerank_base && sel.cand_cnt) {
 		// short lists (the usual case after a GEMM-form scan): one wave per query
-		launch_select_wave(sel, m, cap, st, (uint32_t)(1.2 * (double)k * sample_frac_for(h, k)));
+		// (int8 filter: longer lists, ~500 at k = 10 -- DESIGN.md 4.4i)
+		launch_select_wave(sel, m, cap, st, (uint32_t)((use_i8f ? kI8fListRatio : 1.0) * 1.2 * (double)k * sample_frac_for(h, k)));
 	}
 	hipLaunchKernelGGL(select_topk_kernel, dim3((uint32_t)m), dim3(kBlock),
 	                   sizeof(uint64_t) * cap + 16, st, sel);
@@ -1882,6 +2075,9 @@ int SearchPass::check(int attempt, Next* next) {
 	if (defer_flags(h, st, attempt)) {  // deferred check: expann_sync reads the flags
 		float sc = gvf ? h->f16_scale : 0.0f;  // (fp16 form: the range check of max |q| needs the scale)
 		std::memcpy(&h->h_flag_ring[8 * (h->async_pending - 1) + 6], &sc, sizeof(float));
+		if (i8f_ran && h->opt_i8_filter == 1)  // (word 7, high bit: the int8 filter's candidate limit follows)
+			h->h_flag_ring[8 * (h->async_pending - 1) + 7] =
+			    0x80000000u | (uint32_t)std::min<uint64_t>(i8f_cand_limit(h, m, k), 0x7FFFFFFFu);
 		return EXPANN_OK;
 	}
 	HIP_TRY(h, hipMemcpyAsync(h->h_flags, h->d_overflow, sizeof(uint32_t) * 4 + sizeof(unsigned long long),
@@ -1890,6 +2086,8 @@ int SearchPass::check(int attempt, Next* next) {
 	unsigned long long tot;
 	std::memcpy(&tot, h->h_flags + 4, sizeof(tot));
 	h->prof.candidates = tot;
+	if (i8f_ran && h->opt_i8_filter == 1 && tot > i8f_cand_limit(h, m, k))
+		h->i8f_state = 2;
 	if (std::getenv("EXPANN_DEBUG_LISTS")) {  // (diagnostics: the distribution of the candidate lists' lengths)
 		std::vector<uint32_t> cnt(m);
 		HIP_TRY(h, hipMemcpy(cnt.data(), h->d_cnt, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
@@ -1918,6 +2116,11 @@ int SearchPass::check(int attempt, Next* next) {
 		return EXPANN_OK;
 	// some candidate list overflowed: retry with 4x the capacity
 	h->prof.retries++;
+	if (i8f_ran) {  // the int8 filter's lists: the retry runs the fp16 form at the same capacity
+		i8f_off = true;
+		*next = kRestart;
+		return EXPANN_OK;
+	}
 	// (a hit log of the 16x16x32 form that overflowed counts like a list: the logs grow with the lists)
 	if ((cap >= kMaxCap || attempt >= 3) && (gv || gvi) && h->opt_scan_kernel == 0) {
 		// the GEMM forms cannot break exact ties by row number; the direct scan can
@@ -2127,6 +2330,8 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 		h->opt_tail_chunks = std::atol(e);
 	if (const char* e = std::getenv("EXPANN_PERSIST"))
 		h->opt_persist = std::atol(e);
+	if (const char* e = std::getenv("EXPANN_I8_FILTER"))
+		h->opt_i8_filter = std::min(2L, std::max(0L, std::atol(e)));  // (as set_option)
 	if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&h->stream) != hipSuccess) {
 		g_create_error = "hipSetDevice/hipStreamCreate failed";
 		delete h;
@@ -2292,6 +2497,10 @@ int expann_set_base_device(expann_index* h, const void* d_rows, size_t n, uint64
 	h->d_bnorm_bf.reset();
 	h->d_base_split.reset();
 	h->d_base_f16.reset();
+	h->d_base_i8f.reset();
+	h->d_bp_i8f.reset();
+	h->d_rw_i8f.reset();
+	h->i8f_state = 0;
 	if (h->d_base_i8q && h->base_i8q_owned)
 		hipFree(h->d_base_i8q);
 	h->d_base_i8q = nullptr;
@@ -2356,11 +2565,13 @@ int expann_sync(expann_index* h) {
 		float qmax, scale;
 		std::memcpy(&qmax, &f[2], sizeof(float));
 		std::memcpy(&scale, &f[6], sizeof(float));
-		if (f[0] != 0 || (f[7] != 0 && f[1] != 0) || (scale > 0.0f && !(qmax * scale <= 60000.0f)))
+		if (f[0] != 0 || (f[7] == 1 && f[1] != 0) || (scale > 0.0f && !(qmax * scale <= 60000.0f)))
 			++bad;
 		unsigned long long tot;
 		std::memcpy(&tot, f + 4, sizeof(tot));
 		h->prof.candidates = tot;
+		if ((f[7] & 0x80000000u) && tot > (f[7] & 0x7FFFFFFFu) && h->i8f_state == 1)  // (i8f_cand_limit)
+			h->i8f_state = 2;
 	}
 	if (bad)
 		return h->fail(EXPANN_ERR_OVERFLOW, std::to_string(bad) + " of " + std::to_string(n) +
@@ -2639,6 +2850,8 @@ int expann_set_option(expann_index* h, const char* name, long value) {
 		h->opt_tail_chunks = value;
 	else if (!std::strcmp(name, "persist"))
 		h->opt_persist = value;
+	else if (!std::strcmp(name, "i8_filter"))
+		h->opt_i8_filter = value < 0 ? 0 : (value > 2 ? 2 : value);
 	else if (!std::strcmp(name, "ip_rescale"))
 		h->opt_ip_rescale = value;
 	else if (!std::strcmp(name, "sample_pass"))

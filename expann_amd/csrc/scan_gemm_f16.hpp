@@ -34,6 +34,7 @@
 #pragma once
 #include "common.hpp"
 #include "scan_gemm_bf16.hpp"
+#include "scan_gemm_i8f.hpp"
 #include "select.hpp"
 
 namespace expann {
@@ -125,12 +126,13 @@ __global__ __launch_bounds__(kBlock) void sqnorm_kernel(const float* x, uint32_t
 // q16, qnrm and the range check are those of c_q q, qscale[i] = c_q; thresholds that arrive in true units are
 // multiplied by it (f16_terms_kernel), the sampled pass's own are in the scaled domain already, and the exact
 // re-rank reads the caller's queries.  (L2: c_q = 1.)
+// i8f.q8 != nullptr (int8 filter, scan_gemm_i8f.hpp): the same launch also writes q~ and the query's terms.
 template <int D>
 __global__ __launch_bounds__(kBlock) void f16_query_prep_kernel(const float* q, uint32_t m, float scale,
                                                                 _Float16* q16, float* qnrm,
                                                                 uint32_t* maxabs_bits, float* q_copy,
                                                                 uint32_t* zero_flags, const float* ip_ref,
-                                                                float* qscale) {
+                                                                float* qscale, I8fQueryArgs i8f) {
 	__shared__ uint32_t red[kBlock / 64];
 	if (zero_flags) {
 		if (threadIdx.x < 8)
@@ -177,6 +179,8 @@ __global__ __launch_bounds__(kBlock) void f16_query_prep_kernel(const float* q, 
 		if (qscale)
 			qscale[i] = c;
 	}
+	if (i8f.q8)  // (wave-uniform: the 16-lane sums inside need every lane)
+		i8f_query_terms<D>(i8f, i, m, l, vals);
 	b = __builtin_bit_cast(uint32_t, __builtin_bit_cast(float, b) * c);  // (max |c_q q|: what the fp16 range check is about)
 	for (int off = 32; off > 0; off >>= 1) {
 		const uint32_t o = (uint32_t)__shfl_xor((int)b, off);
@@ -384,10 +388,13 @@ struct GatherLogParams {
 	// HERE -- dot = acc - i_thp[query], L2 forms: i_bias[row] - 2 dot + i_qself[query], inner product: -dot --
 	// instead of two global gathers per hit inside the MFMA kernel (whose vmcnt they shared with the stage
 	// loads).  i_mode: 0 = not an 8-bit log, 1 = L2 forms, 2 = inner product.
+	// i_mode 3, the int8 filter of fp32 rows (scan_gemm_i8f.hpp): i_bias = bp, the key is kappa = bp - acc (units of
+	// 2 s^2, -inf for a row whose bp was clamped: i_rw[row] = +inf), re-scored exactly by the select.
 	const int* i_thp;
 	const int* i_bias;
 	const int* i_qself;
 	int i_mode;
+	const float* i_rw;
 };
 __global__ __launch_bounds__(kBlock) void gather_logs_kernel(GatherLogParams p) {
 	__shared__ uint32_t cnt[64], base[64];
@@ -430,7 +437,10 @@ __global__ __launch_bounds__(kBlock) void gather_logs_kernel(GatherLogParams p) 
 			const uint32_t slot = base[ql] + atomicAdd(&cnt[ql], 1u);
 			if (slot < p.cap) {
 				uint64_t key;
-				if (p.i_mode) {
+				if (p.i_mode == 3) {
+					const float kappa = (float)(p.i_bias[e.y] - (int)e.x);
+					key = make_key(p.i_rw[e.y] < __builtin_inff() ? kappa : -__builtin_inff(), e.y);
+				} else if (p.i_mode) {
 					const int dot = (int)e.x - p.i_thp[e.z];
 					const int score = p.i_mode == 1 ? p.i_bias[e.y] - 2 * dot + p.i_qself[e.z] : -dot;
 					key = make_key((float)score, e.y);
@@ -525,6 +535,12 @@ struct SampleTauParams {
 	float mul;
 	uint32_t* cand_cnt;  // [m] <- 0 (the full scan's list counters)
 	const float* qscale; // inner product: the queries' filter-side factors c_q (tau is stored in true units: / c_q); or nullptr
+	// int8 filter (scan_gemm_i8f.hpp), or i8_thp == nullptr: thp[q] and w_q from tau and the prelude's A_q, W_q
+	int* i8_thp;
+	const float* i8_aq;
+	const float* i8_wq_in;  // W_q, true units
+	float* i8_wq;           // w_q, units of 2 s^2, for the select's pruning
+	double i8_inv_2s2;
 };
 // one thread: ord = ordered bits of the k-th largest g (0: fewer than k values) -> tau, theta', counter
 __device__ inline void sample_tau_finish(const SampleTauParams& p, uint32_t qi, uint32_t ord) {
@@ -543,6 +559,8 @@ __device__ inline void sample_tau_finish(const SampleTauParams& p, uint32_t qi, 
 	p.tau_row[qi] = 0xFFFFFFFFu;
 	p.theta[qi] = p.ip ? (2.0f * tau + qn * p.eps + p.abs_coef * __builtin_sqrtf(qn)) * p.mul
 	                   : (tau - (qn * (1.0f - p.eps) - p.abs_coef * __builtin_sqrtf(qn))) * p.mul;
+	if (p.i8_thp)
+		i8f_thresholds(p.i8_aq[qi], p.i8_wq_in[qi], tau, p.i8_inv_2s2, &p.i8_thp[qi], &p.i8_wq[qi]);
 	p.cand_cnt[qi] = 0;
 }
 // The same threshold by a whole 256-thread workgroup (n_vals <= 2048): radix select on the ordered

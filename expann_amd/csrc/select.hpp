@@ -38,7 +38,26 @@ struct SelectParams {
 	uint32_t wave_done;       // select_wave_kernel already served the lists of <= wave_done keys
 	uint32_t wave0_short;     // select_topk_kernel: lists of <= 2048 keys go through wave 0's wave path
 	const float* qnrm;        // [m] ||q||^2 if the caller has it (pruning margin), else nullptr
+	// rerank pruning of the int8 filter (scan_gemm_i8f.hpp), replacing prune_eps / prune_abs when row_w != nullptr:
+	// key = kappa (units of 2 s^2), a row's upper bound is kappa + row_w[row] + q_w[query], its lower bound kappa;
+	// a candidate whose kappa exceeds the k-th smallest upper bound cannot be among the k best
+	const float* row_w;
+	const float* q_w;
 };
+
+// the cutoff of the int8 filter's pruning from the k-th smallest (ordered) kappa + w_b: + w_q, + the margin
+// for the fp32 rounding of keys and sums (scan_gemm_i8f.hpp); no k-th value (or an infinite one): no cut
+__device__ inline float i8f_cutoff(uint32_t kth_ord, float wq) {
+	if (kth_ord >= 0xFF800000u)
+		return __builtin_inff();
+	const float c = ordered_to_float(kth_ord) + wq;
+	return c + __builtin_fabsf(c) * 0x1p-18f + 1.0f;
+}
+// ordered kappa + w_b of one candidate key (+inf when the row's w_b is, whatever its key)
+__device__ inline uint32_t i8f_upper_ord(const SelectParams& p, uint64_t key) {
+	const float v = key_score(key) + p.row_w[key_idx(key)];
+	return float_to_ordered(v == v ? v : __builtin_inff());
+}
 
 // statistics: *out = sum of counts (one workgroup; one same-address atomic per query in the
 // select kernel would cost ~10 ns each, 100 us at 10^4 queries)
@@ -245,9 +264,9 @@ __device__ inline void select_wave_body(const SelectParams& p, uint32_t qi, uint
 	// what is left to rank is k keys + ties instead of the whole list (k = 100 on uint8 rows: 535 keys, each
 	// ranked against all of them, were 0.31 ms of a 2.4 ms step)
 	const bool final_scores = p.rerank_base == nullptr;
-	if ((p.prune_eps > 0.0f || final_scores) && c > p.k) {
+	if ((p.prune_eps > 0.0f || final_scores || p.row_w) && c > p.k) {
 		float qn = 0.0f;
-		if (final_scores) {
+		if (final_scores || p.row_w) {
 		} else if (p.qnrm) {
 			qn = p.qnrm[qi];
 		} else {
@@ -259,7 +278,7 @@ __device__ inline void select_wave_body(const SelectParams& p, uint32_t qi, uint
 		uint32_t sc[PER];
 #pragma unroll
 		for (int j = 0; j < PER; ++j)
-			sc[j] = (uint32_t)(kk[j] >> 32);
+			sc[j] = (p.row_w && kk[j] != kSentinelKey) ? i8f_upper_ord(p, kk[j]) : (uint32_t)(kk[j] >> 32);
 		uint32_t kth = 0xFFFFFFFFu;
 		if (p.k > 24) {
 			kth = wave_kth_smallest_u32<PER>(sc, p.k);
@@ -279,6 +298,8 @@ __device__ inline void select_wave_body(const SelectParams& p, uint32_t qi, uint
 		}
 		if (final_scores) {
 			cutoff = ordered_to_float(kth);
+		} else if (p.row_w) {
+			cutoff = i8f_cutoff(kth, p.q_w[qi]);
 		} else {
 			const float bmax = p.bn_max[0];
 			cutoff = ordered_to_float(kth) + p.prune_eps * (qn + 1.5f * bmax) +
@@ -423,16 +444,32 @@ __global__ __launch_bounds__(kBlock) void select_topk_kernel(SelectParams p) {
 		const uint32_t l = tid & 15, grp = tid >> 4;  // 16 lanes per candidate row
 		const float* q = p.rerank_queries + (size_t)qi * p.dim + l;
 		uint32_t n_rescore = c;
-		if (p.prune_eps > 0.0f && c > p.k) {
+		if ((p.prune_eps > 0.0f || p.row_w) && c > p.k) {
 			// order by the approximate key, keep what can still reach the k best
 			bitonic(n2);
-			float qn = 0.0f;
-			for (uint32_t t = 0; t < p.dim / 16; ++t)
-				qn = __builtin_fmaf(q[16 * t], q[16 * t], qn);
-			qn = reduce16_ref_order(qn);
-			const float bmax = p.bn_max[0];
-			const float cutoff = key_score(keys[p.k - 1]) + p.prune_eps * (qn + 1.5f * bmax) +
-			                     p.prune_abs * (__builtin_sqrtf(qn) + __builtin_sqrtf(bmax));
+			float cutoff;
+			if (p.row_w) {
+				// the k-th smallest upper bound is at most the largest of the first k keys' (sorted by kappa)
+				uint32_t* s_max = reinterpret_cast<uint32_t*>(keys + p.cap) + 1;
+				if (tid == 0)
+					*s_max = 0;
+				__syncthreads();
+				uint32_t mx = 0;
+				for (uint32_t i = tid; i < p.k; i += kBlock)
+					mx = max(mx, i8f_upper_ord(p, keys[i]));
+				if (mx)
+					atomicMax(s_max, mx);
+				__syncthreads();
+				cutoff = i8f_cutoff(*s_max, p.q_w[qi]);
+			} else {
+				float qn = 0.0f;
+				for (uint32_t t = 0; t < p.dim / 16; ++t)
+					qn = __builtin_fmaf(q[16 * t], q[16 * t], qn);
+				qn = reduce16_ref_order(qn);
+				const float bmax = p.bn_max[0];
+				cutoff = key_score(keys[p.k - 1]) + p.prune_eps * (qn + 1.5f * bmax) +
+				         p.prune_abs * (__builtin_sqrtf(qn) + __builtin_sqrtf(bmax));
+			}
 			uint32_t cnt = 0;
 			for (uint32_t i = tid; i < c; i += kBlock)
 				cnt += key_score(keys[i]) <= cutoff ? 1u : 0u;

@@ -364,7 +364,10 @@ int expann_sharded_get_profile(expann_sharded* h, int shard, expann_profile* out
  * "sample_run", "debug" (bench / ablation switches),
  * "persist" (1 (default): the d = 128 fp16 scan runs as resident workgroups pulling work per XCD; 0: plain launch),
  * "ip_rescale" (1 (default): inner product, fp16 form: the filter sees each query times a power of two that brings
- * its norm to the largest row's -- ranks unchanged, results exact; 0: rounds 1-2's unscaled filter). */
+ * its norm to the largest row's -- ranks unchanged, results exact; 0: rounds 1-2's unscaled filter),
+ * "i8_filter" (fp32 L2, d = 128, scan_kernel on auto: the full scan on the int8 matrix cores with a rigorous
+ * slack and the exact re-rank, thresholds from the fp16 sampled pass; 1 (default): from the planner's crossover
+ * on, 2: wherever supported, 0: never; the environment variable EXPANN_I8_FILTER sets the starting value). */
 int expann_set_option(expann_index* h, const char* name, long value);
 
 #ifdef __cplusplus
