@@ -17,7 +17,7 @@ ABI_SYMBOLS = [
     "expann_abi_version", "expann_device_count", "expann_create", "expann_destroy",
     "expann_last_error", "expann_add", "expann_build", "expann_set_base_device", "expann_size",
     "expann_search", "expann_search_device", "expann_sync", "expann_merge_topk_device", "expann_merge_topk_strided_device", "expann_score_ids",
-    "expann_set_profiling", "expann_get_profile", "expann_set_option",
+    "expann_set_profiling", "expann_get_profile", "expann_set_option", "expann_get_stat", "expann_spec_rank_auto",
     "expann_quantize_simple_u8_device", "expann_quantize_ranged_q8_device",
     "expann_graph_create", "expann_graph_destroy", "expann_graph_last_error",
     "expann_graph_search", "expann_graph_last_kernel_ms",
@@ -234,6 +234,11 @@ def load():
     L.expann_get_profile.argtypes = [vp, C.POINTER(Profile)]
     L.expann_set_option.restype = C.c_int
     L.expann_set_option.argtypes = [vp, C.c_char_p, C.c_long]
+    if hasattr(L, "expann_get_stat"):  # (EXPANN_LIB may name an older build for an A/B run)
+        L.expann_get_stat.restype = C.c_int
+        L.expann_get_stat.argtypes = [vp, C.c_char_p, C.POINTER(C.c_uint64)]
+        L.expann_spec_rank_auto.restype = C.c_uint32
+        L.expann_spec_rank_auto.argtypes = [C.c_size_t, C.c_uint32]
     _lib = L
     return L
 

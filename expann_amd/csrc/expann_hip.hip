@@ -73,6 +73,8 @@ struct expann_index {
 	GrowPtr<uint64_t> d_cand;
 	DevPtr<uint32_t> d_cnt;          // [m_alloc]
 	DevPtr<float> d_tau[2];
+	DevPtr<float> d_tau_s;           // [m_alloc] speculative thresholds of the sampled pass, true units
+	GrowPtr<void> d_redo;            // the redo pass's workspace: failing queries, their compact operands, their lists
 	DevPtr<uint32_t> d_tau_row[2];
 	size_t m_alloc = 0;
 	DevPtr<uint32_t> d_overflow;     // [4]: overflow count
@@ -160,6 +162,10 @@ struct expann_index {
 	long opt_tail_chunks = 1;        // scan_gemm_f16x: the last round's row chunks three times finer (pick_tail_chunks)
 	long opt_persist = 1;            // scan_gemm_f16x: resident workgroups pull (query tile, row chunk) items per XCD
 	long opt_ip_rescale = 1;         // fp16 form, inner product: the filter sees each query times a power of two (f16_query_prep_kernel)
+	long opt_spec_rank = 0;          // speculative thresholds: 0 auto, j >= 1: the j-th class maximum (j >= k: off)
+	uint64_t stat_redo_queries = 0;  // queries the redo pass served in the last search (waiting form) / the last synced one
+	uint64_t stat_redo_overflows = 0;  // searches whose failing queries (or redo lists) did not fit the redo pass
+	uint64_t stat_spec_rank = 0;     // j of the last search's thresholds (= k: proven thresholds)
 	long opt_i8_filter = 1;          // fp32 L2 d = 128: the int8 filter (scan_gemm_i8f.hpp): 0 off, 1 auto, 2 wherever supported
 	long opt_scan_kernel = 0;        // 0 auto, 1 direct (scan_filter), 2 GEMM form on fp32 / int8
 	                                 // MFMA, 3 GEMM form on bf16 MFMA with the 3-term split
@@ -374,7 +380,7 @@ int ensure_workspace(expann_index* h, size_t m, uint32_t cap) {
 	if (m > h->m_alloc) {  // the per-query arrays grow together
 		h->m_alloc = 0;
 		for (DevPtr<float>* b : {std::addressof(h->d_qnrm), std::addressof(h->d_qscale), std::addressof(h->d_theta),
-		                         std::addressof(h->d_tau[0]), std::addressof(h->d_tau[1])}) {
+		                         std::addressof(h->d_tau[0]), std::addressof(h->d_tau[1]), std::addressof(h->d_tau_s)}) {
 			b->reset();
 			HIP_TRY(h, hipMalloc(&*b, sizeof(float) * m));
 		}
@@ -448,12 +454,13 @@ struct GemmF16Variant {
 	const char* name;
 	int tb, wgq, threads, wg_per_cu, lds;  // rows per tile, queries per workgroup, launch geometry
 	int hit_log;                           // scan writes per-wave hit logs (scan_gemm_f16x.hpp) + scatter_log_kernel
+	GemmF16Fn scan_redo = nullptr;         // the scan's instance for the redo pass of the speculative thresholds, if built
 };
 // the 16x16x32 form of the full scan and of the sampled pass (scan_gemm_f16x.hpp)
 #define F16X_V(D)                                                                                  \
 	{D, scan_gemm_f16x_kernel<D, false>, scan_gemm_f16x_kernel<D, true>, sqnorm_kernel<D>,          \
 	 f16_query_prep_kernel<D>, "scan_gemm_f16x<" #D ", false>", kF16TB, kF16TQ, kF16Threads,         \
-	 f16x_wg_per_cu<D>(), gemm_f16x_lds_bytes<D>(), 1}
+	 f16x_wg_per_cu<D>(), gemm_f16x_lds_bytes<D>(), 1, scan_gemm_f16x_kernel<D, false, 0, true>}
 // (d = 64 with two workgroups per CU measured slower than scan_gemm_f16_kernel<64>'s three: 6.55 M vs
 // 6.83 M QPS at 1 M rows -- two k-steps per column leave too little MFMA per step; hence three here too)
 // d = 256 / 512: the 8-waves-per-tile geometry on 16x16x32 (scan_gemm_f16y.hpp), hits appended directly
@@ -695,22 +702,31 @@ int ensure_bias_i8(expann_index* h, const GemmI8Variant* gv, hipStream_t st) {
 
 // one wave per query for lists of <= 512 keys, then (when the buffers allow longer lists) for
 // <= 1024 and <= 2048; select_topk_kernel takes what is left (sel.wave_done = longest list served)
-// `expect` = the list length the thresholds aim at (~1.2 k frac): a stage whose lists would be the rare tail
-// is not launched -- an empty launch still costs ~5 us of the stream, 3 % of a step on a 125 k-row shard --
-// and select_topk_kernel's workgroup-per-query sort takes those few lists.
-void launch_select_wave(SelectParams& sel, size_t m, uint32_t cap, hipStream_t st, uint32_t expect) {
+// `longest` = the longest list the batch is expected to hold (select_longest_list): a stage whose lists would be
+// the rare tail is not launched -- an empty launch still costs ~5 us of the stream, 3 % of a step on a 125 k-row
+// shard -- and select_topk_kernel's workgroup-per-query sort takes those few lists.  (The sort of a 600-key list
+// with its re-rank takes 40-70 us, so a stage is worth its launch as soon as a handful of lists need it.)
+// The longest list of a batch from the length `expect` the thresholds aim at (~1.2 frac x the rank of the class
+// maximum the threshold is).  Proven thresholds (rank k): twice the expectation, the stages' classes since round 2.
+// A speculative threshold of rank j: the lists' relative spread grows as the rank falls -- 10 000 queries at C2,
+// longest / mean: 2.35 (int8 filter) and 2.5 (fp16 form) at rank 10, 3.3 / 3.4 at rank 5, 3.8 / 3.8 at rank 4
+// (profiles/r07_spec_tau_ab.txt) -- which 1 + 4.5 / sqrt(j) follows.
+uint32_t select_longest_list(double expect, uint32_t spec_j) {
+	return spec_j ? (uint32_t)(expect * (1.0 + 4.5 / std::sqrt((double)spec_j))) : 2u * (uint32_t)expect;
+}
+void launch_select_wave(SelectParams& sel, size_t m, uint32_t cap, hipStream_t st, uint32_t longest) {
 	sel.wave_done = 0;
 	hipLaunchKernelGGL((select_wave_kernel<8, 4>), dim3((uint32_t)((m + 3) / 4)), dim3(256), 0, st, sel,
 	                   (uint32_t)m);
 	sel.wave_done = 512;
-	if (expect <= 256)
+	if (longest <= 512)
 		return;
 	if (cap > 512) {
 		// (k = 100: ~920-entry lists -- half the registers and ballots of the 2048-key form)
 		hipLaunchKernelGGL((select_wave_kernel<16, 2>), dim3((uint32_t)((m + 1) / 2)), dim3(128), 0, st, sel, (uint32_t)m);
 		sel.wave_done = 1024;
 	}
-	if (cap > 1024 && expect > 512) {
+	if (cap > 1024 && longest > 1024) {
 		hipLaunchKernelGGL((select_wave_kernel<32, 1>), dim3((uint32_t)m), dim3(64), 0, st, sel, (uint32_t)m);
 		sel.wave_done = 2048;
 	}
@@ -851,6 +867,40 @@ bool pick_tail_chunks(uint32_t n_tiles, uint32_t g, uint32_t n_qtiles, uint32_t 
 	return true;
 }
 
+// ---- speculative thresholds -----------------------------------------------------
+// tau_s = the j-th largest class maximum of the sampled pass, j < k.  A query fails the select's check when its
+// k-th exact score lies above tau_s, i.e. when j rows of the sample beat the k-th best row of the index: at least
+// j of the k - 1 better rows are in the sample, each with probability f (the sampled share of the rows) -- at most
+// P(Bin(k - 1, f) >= j) (two of them in one class only loosen tau_s).
+constexpr double kSpecFailTarget = 0.01;  // the auto rank's share of failing queries, at most
+double spec_fail_share(size_t k, double f, uint32_t j) {
+	if (j == 0)
+		return 1.0;
+	if (k <= 1 || j > k - 1)
+		return 0.0;
+	f = std::min(1.0, std::max(0.0, f));
+	// 1 - sum_{i < j} C(k-1, i) f^i (1-f)^(k-1-i), term by term
+	const double n = (double)(k - 1);
+	double term = std::pow(1.0 - f, n), below = 0.0;
+	for (uint32_t i = 0; i < j; ++i) {
+		below += term;
+		term = f < 1.0 ? term * (n - i) / (i + 1.0) * f / (1.0 - f) : 0.0;
+	}
+	return f < 1.0 ? std::max(0.0, 1.0 - below) : 1.0;
+}
+// the smallest j whose failing share is at most the target; k = speculation off (every j < k fails too often)
+uint32_t spec_rank_auto(size_t k, double f) {
+	for (uint32_t j = 1; j < k; ++j)
+		if (spec_fail_share(k, f, j) <= kSpecFailTarget)
+			return j;
+	return (uint32_t)k;
+}
+// query slots of the redo pass: four times the failures the target allows, in whole query tiles
+uint32_t spec_redo_slots(size_t m) {
+	const size_t want = (size_t)std::ceil(4.0 * kSpecFailTarget * (double)m);
+	return (uint32_t)(std::max<size_t>(1, (want + kF16TQ - 1) / kF16TQ) * kF16TQ);
+}
+
 // Rows read by the sampled pass = 1/frac.  Its cost falls with frac, the candidates of the full
 // scan (~1.2 k frac per query) grow with it.  Measured optima: 12-16 at k = 10 (flat), 8 at
 // k = 100 (3.44 ms per 2500 queries x 5 M rows against 3.65 at 5 and 3.62 at 16).
@@ -937,11 +987,14 @@ const GemmI8qVariant* pick_gemm_i8q(const expann_index* h, size_t m, size_t k) {
 
 // int8 filter of fp32 rows: clip of the scale (s = min(max |x|, kI8fClipRms rms) / 127)
 constexpr double kI8fClipRms = 5.5;
-// its lists over the fp16 form's expectation 1.2 k frac per query on iid rows (501 vs 176.5 at C2): the select's
+// its lists over the expectation 1.2 x rank x frac per query on iid rows, rank = k or the speculative threshold's j
+// (C2: 501.3 at rank 10 = 2.61 x, 214.6 at rank 4 = 2.79 x; the fp16 form measures 176.5 and 69.9): the select's
 // stages are sized by it
 constexpr double kI8fListRatio = 2.8;
 // ... and where it stops paying: at C2's shape the form gains 0.36 ms per step at 501 candidates per query (iid rows)
 // and loses 0.67 ms at 963 (1 000 clusters); the straight line between crosses at ~660 = 3.4 x 1.2 k frac
+// (measured with proven thresholds; under a speculative threshold of rank j the limit scales with j / k as the
+// lists do -- i8f_cand_limit -- and the clustered rows still pass it on their first search)
 constexpr double kI8fBreakEvenRatio = 3.4;
 // The auto region, from the A/B sweep of the two forms over n = 0.5 / 0.75 / 1 / 2 M rows, m = 2 048 / 4 096 / 10 000
 // queries, k = 1 / 10 / 16 / 32 on iid rows (profiles/r06_i8f_sweep.json): every measured point inside is faster
@@ -972,8 +1025,10 @@ bool i8f_wanted(const expann_index* h, size_t m, size_t k) {
 // clusters give it far longer lists than iid rows do.  Past this total an auto search turns the form off for the
 // index (i8f_state 2, until set_base_device brings other rows): the rows, not the shape, decided, and they do not
 // change between searches.
-uint64_t i8f_cand_limit(const expann_index* h, size_t m, size_t k) {
-	return (uint64_t)(kI8fBreakEvenRatio * 1.2 * (double)k * sample_frac_for(h, k) * (double)m);
+// (speculative thresholds: the lists' expectation is linear in the rank j of the class maximum, so is the limit)
+uint64_t i8f_cand_limit(const expann_index* h, size_t m, size_t k, uint32_t spec_j = 0) {
+	const double rank = spec_j ? (double)spec_j : (double)k;
+	return (uint64_t)(kI8fBreakEvenRatio * 1.2 * rank * sample_frac_for(h, k) * (double)m);
 }
 
 // the index side of the int8 filter: scale from the rows' rms and max |x| (one fp64 reduction), the padded
@@ -1218,7 +1273,7 @@ int search_i8q(expann_index* h, const GemmI8qVariant* gq, const void* d_queries,
 		if (h->profiling)
 			hipLaunchKernelGGL(sum_u32_kernel, dim3(1), dim3(1024), 0, st, sel.cand_cnt, (uint32_t)m,
 			                   h->d_total);
-		launch_select_wave(sel, m, cap, st, (uint32_t)(1.2 * (double)k * sample_frac_for(h, k)));
+		launch_select_wave(sel, m, cap, st, select_longest_list(1.2 * (double)k * sample_frac_for(h, k), 0));
 		mark("select_wave");
 		hipLaunchKernelGGL(select_topk_kernel, dim3((uint32_t)m), dim3(kBlock), sizeof(uint64_t) * cap + 16,
 		                   st, sel);
@@ -1335,9 +1390,14 @@ int absorb_shadow_profile(expann_index* h) {
 // (scan_direct_f16.hpp); otherwise the MFMA SAMPLE kernel + sample_tau_kernel.  *done stays false
 // when the index is too small for a sample (the caller runs the threshold ladder instead).
 int sampled_pass_f16(expann_index* h, const GemmF16Variant* gvf, size_t m, size_t k, bool ip, int cus,
-                     float* d_tau, uint32_t* d_tau_row, hipStream_t st, bool* done, bool i8f, bool* i8f_done) {
+                     float* d_tau, uint32_t* d_tau_row, hipStream_t st, bool* done, bool i8f, bool* i8f_done,
+                     uint32_t* spec_j) {
 	*done = false;
 	*i8f_done = false;
+	// speculative thresholds (*spec_j != 0 on entry: this search may have them): the MFMA SAMPLE pass below decides
+	// the rank from the share of the rows it reads; the fused direct pass keeps proven thresholds
+	const bool spec_ok = *spec_j != 0;
+	*spec_j = 0;
 	auto ensure_sample = [&](size_t need) -> int {
 		HIP_TRY(h, grow_ws(h, h->d_sample, need));
 		return EXPANN_OK;
@@ -1436,6 +1496,15 @@ int sampled_pass_f16(expann_index* h, const GemmF16Variant* gvf, size_t m, size_
 	hipLaunchKernelGGL(gvf->sample, dim3(chunks * nqt), dim3((uint32_t)gvf->threads), gvf->lds, st, fp);
 	tp.vals = h->d_sample;
 	tp.n_vals = chunks * 32;
+	if (spec_ok) {
+		const uint32_t j = h->opt_spec_rank > 0 ? (uint32_t)std::min<size_t>((size_t)h->opt_spec_rank, k)
+		                                        : spec_rank_auto(k, (double)t_sel / (double)nt);
+		if (j < k) {
+			*spec_j = j;
+			tp.j = j;
+			tp.tau_s = h->d_tau_s;
+		}
+	}
 	hipLaunchKernelGGL(tp.n_vals <= 512 ? sample_tau_kernel<8>
 	                                   : (tp.n_vals <= 1024 ? sample_tau_kernel<16> : sample_tau_kernel<32>),
 	                   dim3((uint32_t)((m + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0, st, tp);
@@ -1625,6 +1694,37 @@ int launch_scan_f16(expann_index* h, const GemmF16Variant* gvf, uint32_t rows_se
 // plan_thresholds()  threshold levels of this attempt: the ladder, class minima, or one sampled pass
 // run_level(li)      scan of level li (direct / fp32 / bf16x3 / fp16 / int8 MFMA filter) + selection
 // check(attempt)     the one host wait: flags read back, retry with larger lists / another family
+// the redo pass's workspace for R query slots (expann_index::d_redo), offsets in bytes: the failing queries'
+// numbers, the per-slot list counters, theta', ||q||^2, w_q, thp, the fp16 and int8 copies, the candidate lists
+struct RedoWs {
+	size_t list, cnt, theta, qnrm, wq, thp, q16, q8, cand, total;
+	RedoWs(uint32_t R, int dim, uint32_t cap) {
+		list = 0;
+		cnt = 4 * (size_t)R;
+		theta = 8 * (size_t)R;
+		qnrm = 12 * (size_t)R;
+		wq = 16 * (size_t)R;
+		thp = 20 * (size_t)R;
+		q16 = 24 * (size_t)R;  // (R is a multiple of 256: every part starts on a 16-byte boundary)
+		q8 = q16 + 2 * (size_t)R * (size_t)dim;
+		cand = q8 + (size_t)R * (size_t)dim;
+		total = cand + 8 * (size_t)R * (size_t)cap;
+	}
+};
+// Where the auto rank speculates (opt_spec_rank = 0), from the A/B against proven thresholds over bench.py's shapes
+// (profiles/r07_spec_tau_ab.txt): the shorter lists have to pay for the redo pass, four launches that cost ~20 us
+// when no query failed and ~100 us when some did (a scan of the index for one query tile, a select of a few lists).
+// They do where the lists are long: the int8 filter's (C2: 501 -> 215 per query, -11 % per step) and the fp16 form's
+// at large k (1.25 M rows, k = 100: 703 -> 183, -5.1 %).  The fp16 form at k = 10 loses ~1 % (d = 64, 1 000 clusters:
+// 176 -> 70 keys saves less than the chain costs), so does any form at 1 000 queries.  Shapes between the measured
+// ones keep proven thresholds.
+bool spec_auto_region(const expann_index* h, size_t m, size_t k, bool i8f) {
+	(void)h;
+	if (m < 4096)
+		return false;
+	return i8f || k > 32;
+}
+
 struct ScanSel {
 	ScanFn fn = nullptr;
 	int tq = 0;
@@ -1660,12 +1760,17 @@ struct SearchPass {
 	uint32_t n_qtiles = 0;
 	size_t li_start = 0;
 	bool theta_ready = false;   // the sampled pass also wrote theta' and zeroed the list counters
+	// speculative thresholds
+	uint32_t spec_j = 0;        // this attempt's lists are filtered with the j-th class maximum, j < k (0: proven thresholds)
+	bool spec_off = false;      // an attempt's failing queries did not fit the redo pass: proven thresholds from here on
+	uint32_t redo_slots = 0;    // R: query slots of the redo pass
 
 	enum Next { kDone, kRestart, kRetry };
 	int choose_kernels();
 	int prepare_queries(bool* restart);
 	int plan_thresholds();
 	int run_level(size_t li);
+	int run_redo(bool use_i8f);
 	int check(int attempt, Next* next);
 	int run();
 };
@@ -1737,7 +1842,9 @@ int SearchPass::prepare_queries(bool* restart) {
 			if (rc != EXPANN_OK)
 				return rc;
 			i8f = h->i8f_state > 0;
-			if (i8f && h->opt_cand_capacity <= 0)  // (room for the lists of queries with a clipped component)
+			// (room for the lists of queries with a clipped component; with speculative thresholds the main lists are
+			// shorter -- 819 at most at C2 -- but the redo pass's are proven-threshold lists: 1 178 at most)
+			if (i8f && h->opt_cand_capacity <= 0)
 				cap = std::max<uint32_t>(cap, 4096);
 		}
 		if (i8f) {  // int8 queries and the per-query terms [A_q | W_q | w_q | thp]
@@ -1830,13 +1937,26 @@ int SearchPass::plan_thresholds() {
 	li_start = 0;
 	theta_ready = false;
 	i8f_ready = false;
+	spec_j = 0;
 	if (gvf && h->opt_sample_pass && levels.size() >= 2) {
+		// (speculation: the scan_gemm_f16x / i8w streams -- the kernels with the redo pass's early exit --, batches
+		// beyond the latency mode's, no debug instance)
+		const bool spec_form = gvf->hit_log && gvf->scan_redo && (h->opt_debug & ~16L) == 0 && m > 64;
+		if (spec_form && !spec_off && h->opt_spec_rank >= 0 &&
+		    (h->opt_spec_rank > 0 || spec_auto_region(h, m, k, i8f && !i8f_off)))
+			spec_j = 1;
 		const int rs = sampled_pass_f16(h, gvf, m, k, ip, cus, h->d_tau[levels.size() & 1],
-		                                h->d_tau_row[levels.size() & 1], st, &theta_ready, i8f && !i8f_off, &i8f_ready);
+		                                h->d_tau_row[levels.size() & 1], st, &theta_ready, i8f && !i8f_off, &i8f_ready,
+		                                &spec_j);
 		if (rs != EXPANN_OK)
 			return rs;
 		if (theta_ready)
 			li_start = levels.size() - 1;
+	}
+	h->stat_spec_rank = spec_j ? spec_j : k;
+	if (spec_j) {  // the redo pass's workspace (the main select appends to its list)
+		redo_slots = spec_redo_slots(m);
+		HIP_TRY(h, grow_ws(h, h->d_redo, RedoWs(redo_slots, h->dim, cap).total));
 	}
 	return EXPANN_OK;
 }
@@ -2053,6 +2173,13 @@ int SearchPass::run_level(size_t li) {
 		sel.q_w = h->d_i8f_q + 2 * h->i8f_q_m;
 	}
 	sel.overflow = h->d_overflow;
+	if (last && spec_j) {  // the check of the speculative thresholds; failing queries go to the redo pass's list
+		const RedoWs ws(redo_slots, h->dim, cap);
+		sel.spec_tau = h->d_tau_s;
+		sel.redo_word = h->d_overflow + 3;
+		sel.redo_list = reinterpret_cast<uint32_t*>(h->d_redo.as<unsigned char>() + ws.list);
+		sel.redo_cap = redo_slots;
+	}
 	if (last && sel.cand_cnt && (h->profiling || use_i8f))  // statistics: candidates of the full scan (i8f_cand_limit)
 		hipLaunchKernelGGL(sum_u32_kernel, dim3(1), dim3(1024), 0, st, sel.cand_cnt, (uint32_t)m,
 		                   h->d_total);
@@ -2061,10 +2188,167 @@ int SearchPass::run_level(size_t li) {
 	} else if (sel.rerank_base && sel.cand_cnt) {
 		// short lists (the usual case after a GEMM-form scan): one wave per query
 		// (int8 filter: longer lists, ~500 at k = 10 -- DESIGN.md 4.4i)
-		launch_select_wave(sel, m, cap, st, (uint32_t)((use_i8f ? kI8fListRatio : 1.0) * 1.2 * (double)k * sample_frac_for(h, k)));
+		// (speculative thresholds: the expectation is linear in the rank of the class maximum)
+		const uint32_t sj = last ? spec_j : 0u;
+		const double expect = (use_i8f ? kI8fListRatio : 1.0) * 1.2 * (sj ? (double)sj : (double)k) * sample_frac_for(h, k);
+		launch_select_wave(sel, m, cap, st, select_longest_list(expect, sj));
 	}
 	hipLaunchKernelGGL(select_topk_kernel, dim3((uint32_t)m), dim3(kBlock),
 	                   sizeof(uint64_t) * cap + 16, st, sel);
+	HIP_TRY(h, hipGetLastError());
+	if (last && spec_j)
+		return run_redo(use_i8f);
+	return EXPANN_OK;
+}
+
+// The redo pass of the speculative thresholds, always enqueued behind the select of a speculating
+// search: compact operands of the failing queries with thresholds from the proven tau, the same scan kernel over
+// R query slots (workgroups of a query tile no failing query took leave at once), the logs' gather, one select
+// launch that writes the failing queries' output rows.  No host wait: the counts are read on the device.
+int SearchPass::run_redo(bool use_i8f) {
+	const RedoWs ws(redo_slots, h->dim, cap);
+	unsigned char* const b = h->d_redo.as<unsigned char>();
+	uint32_t* const word = h->d_overflow + 3;
+	const uint32_t R = redo_slots;
+	RedoCompactParams cp{};
+	cp.word = word;
+	cp.list = reinterpret_cast<const uint32_t*>(b + ws.list);
+	cp.n_slots = R;
+	cp.row_bytes = (uint32_t)h->dim * 2;
+	cp.q16 = h->d_q_split;
+	cp.rq16 = b + ws.q16;
+	cp.qnrm = h->d_qnrm;
+	cp.r_qnrm = reinterpret_cast<float*>(b + ws.qnrm);
+	cp.tau = h->d_tau[levels.size() & 1];
+	cp.qscale = (ip && h->opt_ip_rescale) ? h->d_qscale.as<const float>() : nullptr;
+	cp.eps = gemm_f16_filter_eps(h->dim);
+	cp.abs_coef = std::ldexp(1.0f, -24) / h->f16_scale * std::sqrt((float)h->dim);
+	cp.mul = 0.5f * h->f16_scale * h->f16_scale;
+	cp.ip = ip ? 1 : 0;
+	cp.r_theta = reinterpret_cast<float*>(b + ws.theta);
+	cp.r_cnt = reinterpret_cast<uint32_t*>(b + ws.cnt);
+	if (use_i8f) {
+		cp.q8 = h->d_q8f;
+		cp.rq8 = b + ws.q8;
+		cp.i8_aq = h->d_i8f_q;
+		cp.i8_wq_in = h->d_i8f_q + h->i8f_q_m;
+		cp.r_thp = reinterpret_cast<int*>(b + ws.thp);
+		cp.r_wq = reinterpret_cast<float*>(b + ws.wq);
+		cp.i8_inv_2s2 = h->i8f.inv_2s2;
+	}
+	hipLaunchKernelGGL(redo_compact_kernel, dim3(R / (kBlock / 64)), dim3(kBlock), 0, st, cp);
+
+	// the scan: one round of the resident workgroups per query tile (a batch inside the target fills one tile);
+	// its hit logs are the main scan's, which the main gather has read by now
+	const uint32_t nt = (uint32_t)((h->n + kF16TB - 1) / kF16TB);
+	const uint32_t nqt = R / kF16TQ;
+	const uint32_t wg_per_cu = use_i8f ? (uint32_t)kGemmI8F.wg_per_cu_w : (uint32_t)gvf->wg_per_cu;
+	uint32_t chunks = pick_row_chunks(nt, 1, wg_per_cu * (uint32_t)cus, 4.0, 8, 2048, 0, nullptr);
+	chunks = std::min<uint32_t>(chunks, (uint32_t)(h->log_cnt_n / (4 * (size_t)nqt)));
+	if (chunks == 0 || !h->d_log)
+		return h->fail(EXPANN_ERR_HIP, "redo pass: the main scan left no hit logs");  // (both main scans allocate them)
+	const uint32_t tpb = (nt + chunks - 1) / chunks;
+	chunks = (nt + tpb - 1) / tpb;
+	const uint32_t n_logs = chunks * nqt * 4;
+	const uint32_t log_cap = (uint32_t)std::min<size_t>(1u << 16, h->log_bytes / ((size_t)n_logs * 16));
+	GatherLogParams gp{};
+	gp.log = h->d_log.as<const uint4>();
+	gp.log_cnt = h->d_log_cnt.as<const uint32_t>();
+	gp.log_cap = log_cap;
+	gp.n_chunks = chunks;
+	gp.n_qtiles = nqt;
+	gp.m = R;
+	gp.cand_cnt = cp.r_cnt;
+	gp.cand = reinterpret_cast<uint64_t*>(b + ws.cand);
+	gp.cap = cap;
+	gp.live_q = word;
+	if (use_i8f) {
+		GemmI8wParams wp{};
+		wp.q.base = h->d_base_i8f;
+		wp.q.bp = h->d_bp_i8f;
+		wp.q.n_rows = (uint32_t)h->n;
+		wp.q.n_tiles_sel = nt;
+		wp.q.tile_stride = 1;
+		wp.q.tile_run = 1;
+		wp.q.tiles_per_block = tpb;
+		wp.q.n_qtiles = nqt;
+		wp.q.queries = cp.rq8;
+		wp.q.thp = cp.r_thp;
+		wp.q.m = R;
+		wp.q.cand_cnt = gp.cand_cnt;
+		wp.q.cand = gp.cand;
+		wp.q.cap = cap;
+		wp.q.live_q = word;
+		wp.log = h->d_log.as<uint4>();
+		wp.log_cnt = h->d_log_cnt;
+		wp.log_cap = log_cap;
+		wp.lost = h->d_overflow;
+		hipLaunchKernelGGL(kGemmI8F.scan_w, dim3(chunks * nqt), dim3((uint32_t)kGemmI8F.threads_w), kGemmI8F.lds_w, st, wp);
+		gp.i_thp = cp.r_thp;
+		gp.i_bias = h->d_bp_i8f;
+		gp.i_rw = h->d_rw_i8f;
+		gp.i_mode = 3;
+	} else {
+		GemmF16Params fp{};
+		fp.base_f16 = h->d_base_f16;
+		fp.bnorm = h->d_bnorm_f16;
+		fp.n_rows = (uint32_t)h->n;
+		fp.n_tiles_sel = nt;
+		fp.tile_stride = 1;
+		fp.tile_run = 1;
+		fp.tiles_per_block = tpb;
+		fp.n_qtiles = nqt;
+		fp.queries_f16 = cp.rq16;
+		fp.theta = cp.r_theta;
+		fp.two_inv_s2 = (ip ? 1.0f : 2.0f) / (h->f16_scale * h->f16_scale);
+		fp.m = R;
+		fp.cand_cnt = gp.cand_cnt;
+		fp.cand = gp.cand;
+		fp.cap = cap;
+		fp.ksteps = (uint32_t)f16_ld(h->dim) / 32;
+		fp.log = h->d_log.as<uint4>();
+		fp.log_cnt = h->d_log_cnt;
+		fp.log_cap = log_cap;
+		fp.lost = h->d_overflow;
+		fp.live_q = word;
+		hipLaunchKernelGGL(gvf->scan_redo, dim3(chunks * nqt), dim3((uint32_t)gvf->threads), gvf->lds, st, fp);
+		gp.theta = cp.r_theta;
+		gp.key_mul = fp.two_inv_s2;
+	}
+	const uint32_t want = std::max<uint32_t>(1, (1024 + nqt * 4 - 1) / (nqt * 4));
+	gp.chunks_per_block = std::max<uint32_t>(1, (chunks + want - 1) / want);
+	gp.n_groups = (chunks + gp.chunks_per_block - 1) / gp.chunks_per_block;
+	hipLaunchKernelGGL(gather_logs_kernel, dim3(nqt * 4 * gp.n_groups), dim3(kBlock), 0, st, gp);
+
+	// the select of the R slots in one launch: wave 0 of a slot's workgroup orders a list of <= 2048 keys, the
+	// whole workgroup a longer one; no check (these lists come from proven thresholds)
+	SelectParams sel{};
+	sel.cand = gp.cand;
+	sel.cand_cnt = gp.cand_cnt;
+	sel.cap = cap;
+	sel.k = (uint32_t)k;
+	sel.id_offset = h->id_offset;
+	sel.out_ids = d_ids;
+	sel.out_dists = d_dists;
+	sel.rerank_base = (const float*)h->d_base;
+	sel.rerank_queries = (const float*)d_queries;
+	sel.dim = (uint32_t)h->dim;
+	sel.metric_ip = ip ? 1u : 0u;
+	const float pr = ip ? 1.0f : 2.0f;
+	sel.bn_max = h->d_bnmax + 2;
+	sel.qnrm = cp.r_qnrm;
+	if (use_i8f) {
+		sel.row_w = h->d_rw_i8f;
+		sel.q_w = cp.r_wq;
+	} else {
+		sel.prune_eps = pr * gemm_f16_filter_eps(h->dim);
+		sel.prune_abs = pr * std::ldexp(1.0f, -24) / h->f16_scale * std::sqrt((float)h->dim);
+	}
+	sel.overflow = word;
+	sel.wave0_short = 1;
+	sel.slot_map = cp.list;
+	sel.live_slots = word;
+	hipLaunchKernelGGL(select_topk_kernel, dim3(R), dim3(kBlock), sizeof(uint64_t) * cap + 16, st, sel);
 	HIP_TRY(h, hipGetLastError());
 	return EXPANN_OK;
 }
@@ -2077,7 +2361,9 @@ int SearchPass::check(int attempt, Next* next) {
 		std::memcpy(&h->h_flag_ring[8 * (h->async_pending - 1) + 6], &sc, sizeof(float));
 		if (i8f_ran && h->opt_i8_filter == 1)  // (word 7, high bit: the int8 filter's candidate limit follows)
 			h->h_flag_ring[8 * (h->async_pending - 1) + 7] =
-			    0x80000000u | (uint32_t)std::min<uint64_t>(i8f_cand_limit(h, m, k), 0x7FFFFFFFu);
+			    0x80000000u | (uint32_t)std::min<uint64_t>(i8f_cand_limit(h, m, k, spec_j), 0x3FFFFFFFu);
+		if (spec_j)  // (word 7, bit 30: word 3 is this search's redo word)
+			h->h_flag_ring[8 * (h->async_pending - 1) + 7] |= 0x40000000u;
 		return EXPANN_OK;
 	}
 	HIP_TRY(h, hipMemcpyAsync(h->h_flags, h->d_overflow, sizeof(uint32_t) * 4 + sizeof(unsigned long long),
@@ -2086,7 +2372,7 @@ int SearchPass::check(int attempt, Next* next) {
 	unsigned long long tot;
 	std::memcpy(&tot, h->h_flags + 4, sizeof(tot));
 	h->prof.candidates = tot;
-	if (i8f_ran && h->opt_i8_filter == 1 && tot > i8f_cand_limit(h, m, k))
+	if (i8f_ran && h->opt_i8_filter == 1 && tot > i8f_cand_limit(h, m, k, spec_j))
 		h->i8f_state = 2;
 	if (std::getenv("EXPANN_DEBUG_LISTS")) {  // (diagnostics: the distribution of the candidate lists' lengths)
 		std::vector<uint32_t> cnt(m);
@@ -2112,10 +2398,24 @@ int SearchPass::check(int attempt, Next* next) {
 		               std::to_string(h->h_flags[1]) +
 		                   " query values outside [0,255]: the uint8 metric "
 		                   "(dist2_compressed) is only defined for 8-bit valued queries");
-	if (h->h_flags[0] == 0)
+	// speculative thresholds: word 3 = failing queries (low 20 bits) + 2^20 per redo overflow (more of them than
+	// redo slots, or a redo list beyond its capacity): the search is repeated with proven thresholds
+	const uint32_t redo_word = spec_j ? h->h_flags[3] : 0u;
+	if (h->h_flags[0] == 0 && redo_word < kRedoOverflowUnit) {
+		h->stat_redo_queries += redo_word;
 		return EXPANN_OK;
-	// some candidate list overflowed: retry with 4x the capacity
+	}
 	h->prof.retries++;
+	if (spec_j) {  // (whatever overflowed: no speculation from here on)
+		spec_off = true;
+		if (redo_word >= kRedoOverflowUnit)
+			h->stat_redo_overflows++;
+		if (h->h_flags[0] == 0) {
+			*next = kRestart;
+			return EXPANN_OK;
+		}
+	}
+	// some candidate list overflowed: retry with 4x the capacity
 	if (i8f_ran) {  // the int8 filter's lists: the retry runs the fp16 form at the same capacity
 		i8f_off = true;
 		*next = kRestart;
@@ -2330,6 +2630,8 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 		h->opt_tail_chunks = std::atol(e);
 	if (const char* e = std::getenv("EXPANN_PERSIST"))
 		h->opt_persist = std::atol(e);
+	if (const char* e = std::getenv("EXPANN_SPEC_RANK"))
+		h->opt_spec_rank = std::max(0L, std::atol(e));  // (as set_option)
 	if (const char* e = std::getenv("EXPANN_I8_FILTER"))
 		h->opt_i8_filter = std::min(2L, std::max(0L, std::atol(e)));  // (as set_option)
 	if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&h->stream) != hipSuccess) {
@@ -2349,7 +2651,9 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 	for (const auto& v : kGemmF16X)
 		if (v.d == dim &&  // (the sampled pass is launched with the scan's LDS size, never less than its own)
 		    (hipFuncSetAttribute((const void*)v.scan, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds) != hipSuccess ||
-		     hipFuncSetAttribute((const void*)v.sample, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds) != hipSuccess)) {
+		     hipFuncSetAttribute((const void*)v.sample, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds) != hipSuccess ||
+		     (v.scan_redo &&
+		      hipFuncSetAttribute((const void*)v.scan_redo, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds) != hipSuccess))) {
 			g_create_error = "hipFuncSetAttribute(scan_gemm_f16x_kernel) failed";
 			hipStreamDestroy(h->stream);
 			delete h;
@@ -2540,6 +2844,7 @@ int expann_search_device(expann_index* h, const void* d_queries, size_t m, size_
 		h->async_stream = st;
 	}
 	const size_t qbytes = (size_t)h->dim * h->q_elem;
+	h->stat_redo_queries = 0;
 	for (size_t q0 = 0; q0 < m; q0 += kMaxQueriesPerPass) {
 		const size_t mm = std::min(kMaxQueriesPerPass, m - q0);
 		int rc = search_pass(h, (const char*)d_queries + q0 * qbytes, mm, k, d_ids + q0 * k,
@@ -2560,19 +2865,27 @@ int expann_sync(expann_index* h) {
 	h->async_pending = 0;
 	HIP_TRY(h, hipStreamSynchronize(h->async_stream));
 	uint32_t bad = 0;
+	uint64_t redo_queries = 0;
 	for (uint32_t i = 0; i < n; ++i) {
 		const uint32_t* f = h->h_flag_ring + 8 * i;
 		float qmax, scale;
 		std::memcpy(&qmax, &f[2], sizeof(float));
 		std::memcpy(&scale, &f[6], sizeof(float));
-		if (f[0] != 0 || (f[7] == 1 && f[1] != 0) || (scale > 0.0f && !(qmax * scale <= 60000.0f)))
+		const bool redo_word = (f[7] & 0x40000000u) != 0;  // (speculative thresholds: word 3 is the search's redo word)
+		if (redo_word && f[3] >= kRedoOverflowUnit)
+			h->stat_redo_overflows++;
+		else if (redo_word)
+			redo_queries += f[3];
+		if (f[0] != 0 || (f[7] == 1 && f[1] != 0) || (scale > 0.0f && !(qmax * scale <= 60000.0f)) ||
+		    (redo_word && f[3] >= kRedoOverflowUnit))
 			++bad;
 		unsigned long long tot;
 		std::memcpy(&tot, f + 4, sizeof(tot));
 		h->prof.candidates = tot;
-		if ((f[7] & 0x80000000u) && tot > (f[7] & 0x7FFFFFFFu) && h->i8f_state == 1)  // (i8f_cand_limit)
+		if ((f[7] & 0x80000000u) && tot > (f[7] & 0x3FFFFFFFu) && h->i8f_state == 1)  // (i8f_cand_limit)
 			h->i8f_state = 2;
 	}
+	h->stat_redo_queries = redo_queries;
 	if (bad)
 		return h->fail(EXPANN_ERR_OVERFLOW, std::to_string(bad) + " of " + std::to_string(n) +
 		                                        " deferred searches need the synchronous retry "
@@ -2830,6 +3143,24 @@ int expann_get_profile(expann_index* h, expann_profile* out) {
 	return EXPANN_OK;
 }
 
+int expann_get_stat(expann_index* h, const char* name, uint64_t* out) {
+	if (!h || !name || !out)
+		return EXPANN_ERR_INVALID_ARG;
+	if (!std::strcmp(name, "redo_queries"))
+		*out = h->stat_redo_queries;
+	else if (!std::strcmp(name, "redo_overflows"))
+		*out = h->stat_redo_overflows;
+	else if (!std::strcmp(name, "spec_rank"))
+		*out = h->stat_spec_rank;
+	else
+		return h->fail(EXPANN_ERR_INVALID_ARG, std::string("unknown statistic ") + name);
+	return EXPANN_OK;
+}
+
+uint32_t expann_spec_rank_auto(size_t k, uint32_t sample_frac) {
+	return spec_rank_auto(k, sample_frac ? 1.0 / (double)sample_frac : 1.0);
+}
+
 int expann_set_option(expann_index* h, const char* name, long value) {
 	if (!h || !name)
 		return EXPANN_ERR_INVALID_ARG;
@@ -2852,6 +3183,8 @@ int expann_set_option(expann_index* h, const char* name, long value) {
 		h->opt_persist = value;
 	else if (!std::strcmp(name, "i8_filter"))
 		h->opt_i8_filter = value < 0 ? 0 : (value > 2 ? 2 : value);
+	else if (!std::strcmp(name, "spec_rank"))
+		h->opt_spec_rank = value < 0 ? 0 : value;
 	else if (!std::strcmp(name, "ip_rescale"))
 		h->opt_ip_rescale = value;
 	else if (!std::strcmp(name, "sample_pass"))

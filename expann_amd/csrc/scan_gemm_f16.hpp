@@ -363,6 +363,11 @@ struct GemmF16Params {
 	uint32_t n_items;
 	// scan_gemm_f16kl_kernel only: MFMA k-steps of 32 elements per row (the fp16 rows' length / 32)
 	uint32_t ksteps;
+	// scan_gemm_f16x_kernel's REDO instance only, the redo pass of the speculative thresholds: the m query slots are
+	// compact copies of the failing queries; *live_q (low 20 bits) of them are taken -- a workgroup whose query
+	// tile starts at or beyond that count leaves at once (the slots behind the count inside a tile hold theta' =
+	// -inf).  nullptr: every query is live.
+	const uint32_t* live_q;
 };
 
 // Per-wave hit logs -> per-query candidate lists.  The 64 queries of (query tile, wave w) receive
@@ -395,12 +400,15 @@ struct GatherLogParams {
 	const int* i_qself;
 	int i_mode;
 	const float* i_rw;
+	const uint32_t* live_q;  // redo pass: as GemmF16Params::live_q (the query tiles no workgroup scanned have no logs)
 };
 __global__ __launch_bounds__(kBlock) void gather_logs_kernel(GatherLogParams p) {
 	__shared__ uint32_t cnt[64], base[64];
 	const uint32_t grp = blockIdx.x % p.n_groups, qw = blockIdx.x / p.n_groups;
 	const uint32_t qtile = qw >> 2, w = qw & 3;
 	const uint32_t q0 = qtile * 256 + w * 64;
+	if (p.live_q && qtile * 256 >= (*p.live_q & kRedoCountMask))
+		return;
 	if (threadIdx.x < 64)
 		cnt[threadIdx.x] = 0;
 	__syncthreads();
@@ -541,11 +549,15 @@ struct SampleTauParams {
 	const float* i8_wq_in;  // W_q, true units
 	float* i8_wq;           // w_q, units of 2 s^2, for the select's pruning
 	double i8_inv_2s2;
+	// speculative threshold, or tau_s == nullptr: tau_s[q] comes from the j-th largest class
+	// maximum, j < k, and theta', thp, w_q are made from IT -- the select checks the result against tau_s and the
+	// redo pass searches the failing queries again with the proven tau.  Both are stored in true units.
+	uint32_t j;
+	float* tau_s;           // [m]
 };
-// one thread: ord = ordered bits of the k-th largest g (0: fewer than k values) -> tau, theta', counter
-__device__ inline void sample_tau_finish(const SampleTauParams& p, uint32_t qi, uint32_t ord) {
+// the threshold (the filter's domain) that the class maximum with ordered bits ord stands for (0: no such value)
+__device__ inline float sample_tau_of(const SampleTauParams& p, float qn, uint32_t ord) {
 	float tau = __builtin_inff();
-	const float qn = p.qnrm[qi];
 	if (ord != 0) {
 		const float g = ordered_to_float(ord);
 		if (p.ip)
@@ -555,7 +567,17 @@ __device__ inline void sample_tau_finish(const SampleTauParams& p, uint32_t qi, 
 		if (!(tau == tau))
 			tau = __builtin_inff();
 	}
-	p.tau[qi] = (p.ip && p.qscale) ? tau / p.qscale[qi] : tau;  // (true units; theta' below stays in the filter's domain)
+	return tau;
+}
+// one thread: ord = ordered bits of the k-th largest g (0: fewer than k values) -> tau; ord_s = those of the
+// j-th largest (= ord: no speculation) -> tau_s, theta', the int8 thresholds; the list counter
+__device__ inline void sample_tau_finish(const SampleTauParams& p, uint32_t qi, uint32_t ord, uint32_t ord_s) {
+	const float qn = p.qnrm[qi];
+	const float tau_k = sample_tau_of(p, qn, ord);
+	const float tau = (p.tau_s && ord_s != ord) ? sample_tau_of(p, qn, ord_s) : tau_k;  // what the full scan filters with
+	p.tau[qi] = (p.ip && p.qscale) ? tau_k / p.qscale[qi] : tau_k;  // (true units; theta' below stays in the filter's domain)
+	if (p.tau_s)
+		p.tau_s[qi] = (p.ip && p.qscale) ? tau / p.qscale[qi] : tau;
 	p.tau_row[qi] = 0xFFFFFFFFu;
 	p.theta[qi] = p.ip ? (2.0f * tau + qn * p.eps + p.abs_coef * __builtin_sqrtf(qn)) * p.mul
 	                   : (tau - (qn * (1.0f - p.eps) - p.abs_coef * __builtin_sqrtf(qn))) * p.mul;
@@ -614,7 +636,7 @@ __device__ inline void sample_tau_query_wg(const SampleTauParams& p, uint32_t qi
 		mask |= 0xFFu << sh;
 	}
 	if (tid == 0)
-		sample_tau_finish(p, qi, prefix);
+		sample_tau_finish(p, qi, prefix, prefix);  // (the direct kernels' queries keep proven thresholds)
 }
 // the work of one wave for query qi; scratch = 64 words of LDS of this wave's own
 template <int PER>  // values per lane: n_vals <= 64 * PER
@@ -633,11 +655,16 @@ __device__ inline void sample_tau_query(const SampleTauParams& p, uint32_t qi, i
 #pragma unroll
 	for (int j = 0; j < PER; ++j)
 		ord[j] = (uint32_t)(keys[j] >> 32);
-	const uint64_t kth = (uint64_t)(p.k <= 64 ? wave_kth_largest_sparse_u32<PER>(ord, p.k, scratch, lane)
-	                                          : wave_kth_largest_u32<PER>(ord, p.k))
-	                     << 32;
+	const bool spec = p.tau_s != nullptr && p.j < p.k;
+	uint2 kj;  // the k-th and the j-th largest
+	if (p.k <= 64) {
+		kj = wave_kth_largest_sparse_u32<PER>(ord, p.k, scratch, lane, spec ? p.j : 0u);
+	} else {
+		kj.x = wave_kth_largest_u32<PER>(ord, p.k);
+		kj.y = spec ? wave_kth_largest_u32<PER>(ord, p.j) : 0u;
+	}
 	if (lane == 0)
-		sample_tau_finish(p, qi, (uint32_t)(kth >> 32));
+		sample_tau_finish(p, qi, kj.x, spec ? kj.y : kj.x);
 }
 template <int PER>
 __global__ __launch_bounds__(kBlock) void sample_tau_kernel(SampleTauParams p) {
@@ -646,6 +673,83 @@ __global__ __launch_bounds__(kBlock) void sample_tau_kernel(SampleTauParams p) {
 	if (qi >= p.m)
 		return;  // (whole wave)
 	sample_tau_query<PER>(p, qi, threadIdx.x & 63, scratch[threadIdx.x >> 6]);
+}
+
+// ---- the redo pass of the speculative thresholds -------------------------------
+// The select has appended the queries whose result the speculative threshold does not prove to `list` and counted
+// them in *word (SelectParams::redo_word).  One wave per slot s < n_slots makes the compact operands of the redo scan:
+// the fp16 (and int8) copy of query list[s], its norm, and theta' (thp, w_q) from the PROVEN tau; a slot nobody took
+// gets zero rows and the thresholds no row passes.  More failing queries than slots: + 2^20 to *word, which the host
+// reads with the other flags (the search is repeated without speculation).
+struct RedoCompactParams {
+	uint32_t* word;
+	const uint32_t* list;    // [n_slots]
+	uint32_t n_slots;
+	uint32_t row_bytes;      // of a query's fp16 copy (a multiple of 16)
+	const void* q16;         // [m] fp16 queries -> rq16 [n_slots]
+	void* rq16;
+	const float* qnrm;       // -> r_qnrm
+	float* r_qnrm;
+	const float* tau;        // [m] proven thresholds, true units
+	const float* qscale;     // inner product with ip_rescale: c_q (the filter's domain = true units * c_q); or nullptr
+	float eps, abs_coef, mul;
+	int ip;
+	float* r_theta;
+	uint32_t* r_cnt;         // [n_slots] <- 0: the redo lists' counters
+	// int8 filter (q8 != nullptr): rows of row_bytes / 2
+	const void* q8;
+	void* rq8;
+	const float* i8_aq;
+	const float* i8_wq_in;
+	int* r_thp;
+	float* r_wq;
+	double i8_inv_2s2;
+};
+__global__ __launch_bounds__(kBlock) void redo_compact_kernel(RedoCompactParams p) {
+	const uint32_t lane = threadIdx.x & 63;
+	const uint32_t s = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+	const uint32_t failed = *p.word & kRedoCountMask;
+	if (blockIdx.x == 0 && threadIdx.x == 0 && failed > p.n_slots)
+		atomicAdd(p.word, kRedoOverflowUnit);
+	if (s >= p.n_slots)
+		return;  // (whole wave)
+	const bool live = s < failed;
+	const uint32_t qi = live ? p.list[s] : 0u;
+	const uint4* src = reinterpret_cast<const uint4*>((const unsigned char*)p.q16 + (size_t)qi * p.row_bytes);
+	uint4* dst = reinterpret_cast<uint4*>((unsigned char*)p.rq16 + (size_t)s * p.row_bytes);
+	for (uint32_t i = lane; i < p.row_bytes / 16; i += 64) {
+		uint4 v = make_uint4(0u, 0u, 0u, 0u);
+		if (live)
+			v = src[i];
+		dst[i] = v;
+	}
+	if (p.q8) {
+		const uint32_t rb = p.row_bytes / 2;
+		const uint32_t* s8 = reinterpret_cast<const uint32_t*>((const unsigned char*)p.q8 + (size_t)qi * rb);
+		uint32_t* d8 = reinterpret_cast<uint32_t*>((unsigned char*)p.rq8 + (size_t)s * rb);
+		for (uint32_t i = lane; i < rb / 4; i += 64)
+			d8[i] = live ? s8[i] : 0u;
+	}
+	if (lane != 0)
+		return;
+	p.r_cnt[s] = 0;
+	if (!live) {
+		p.r_qnrm[s] = 0.0f;
+		p.r_theta[s] = -__builtin_inff();
+		if (p.q8) {
+			p.r_thp[s] = (-2147483647 - 1) / 2;  // (the start value of a padded query slot, scan_gemm_i8w.hpp)
+			p.r_wq[s] = __builtin_inff();
+		}
+		return;
+	}
+	const float qn = p.qnrm[qi];
+	const float tau = p.tau[qi];
+	const float tau_f = (p.ip && p.qscale) ? tau * p.qscale[qi] : tau;  // (c_q is a power of two: exact)
+	p.r_qnrm[s] = qn;
+	p.r_theta[s] = p.ip ? (2.0f * tau_f + qn * p.eps + p.abs_coef * __builtin_sqrtf(qn)) * p.mul
+	                    : (tau_f - (qn * (1.0f - p.eps) - p.abs_coef * __builtin_sqrtf(qn))) * p.mul;
+	if (p.q8)
+		i8f_thresholds(p.i8_aq[qi], p.i8_wq_in[qi], tau, p.i8_inv_2s2, p.r_thp + s, p.r_wq + s);
 }
 
 }  // namespace expann

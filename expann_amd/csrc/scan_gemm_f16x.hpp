@@ -41,7 +41,9 @@ template <int D> constexpr int gemm_f16x_lds_bytes() {
 static_assert(gemm_f16x_lds_bytes<64>() * 3 <= 160 * 1024, "three workgroups per CU at d = 64");
 static_assert(gemm_f16x_lds_bytes<128>() == gemm_f16_lds_bytes<128>(), "same LDS map as scan_gemm_f16_kernel<128>");
 
-template <int D, bool SAMPLE, int DBG = 0>
+// (REDO: the instance the redo pass of the speculative thresholds launches -- it alone reads p.live_q, so the
+// full scan's instance is the code it was before that pass existed)
+template <int D, bool SAMPLE, int DBG = 0, bool REDO = false>
 __global__ __launch_bounds__(kF16Threads, f16x_wg_per_cu<D>()) void scan_gemm_f16x_kernel(GemmF16Params p) {
 	const uint32_t dbg = DBG ? p.debug : 0u;
 	static_assert(D == 64 || D == 128, "built for d = 64, 128");
@@ -80,6 +82,8 @@ __global__ __launch_bounds__(kF16Threads, f16x_wg_per_cu<D>()) void scan_gemm_f1
 		chunk = (bid & 7) + 8 * (j / p.n_qtiles);
 	}
 	const uint32_t wg_q0 = qtile * WGQ;
+	if (REDO && p.live_q && wg_q0 >= (*p.live_q & kRedoCountMask))
+		return;  // (redo pass: no failing query took a slot of this tile; the gather skips its logs)
 	const uint32_t q0 = wg_q0 + wave * 64;
 	// 16-query tiles of this wave that hold real queries (4 everywhere but in the batch's last query
 	// tile: m = 10 000 leaves 16 queries for it, i.e. one tile of wave 0 and none of waves 1-3)

@@ -44,6 +44,7 @@ struct GemmI8qParams {
 	int* sample_out;         // SAMPLE: [(q * n_chunks + chunk) * 32 + class] max g
 	uint32_t n_chunks;
 	uint32_t xcd_map;        // XCD-aware block placement, as GemmF16Params::xcd_map
+	const uint32_t* live_q;  // scan_gemm_i8w_kernel, redo pass (GemmF16Params::live_q): live query slots, or nullptr
 };
 
 // bp[i] = bias[i] >> 1 for i < n, kI8qPadBp for n <= i < n_pad (bias == nullptr: zeros)

@@ -68,6 +68,8 @@ __global__ __launch_bounds__(kF16Threads, I8wGeom<D>::WG_PER_CU) void scan_gemm_
 		chunk = (blockIdx.x & 7) + 8 * (j / p.n_qtiles);
 	}
 	const uint32_t wg_q0 = qtile * WGQ;
+	if (!SAMPLE && p.live_q && wg_q0 >= (*p.live_q & kRedoCountMask))
+		return;  // (redo pass of the speculative thresholds, as scan_gemm_f16x_kernel)
 	const uint32_t q0 = wg_q0 + wave * 64;
 
 	const uint32_t t0 = chunk * p.tiles_per_block;

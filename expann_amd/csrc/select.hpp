@@ -43,7 +43,31 @@ struct SelectParams {
 	// a candidate whose kappa exceeds the k-th smallest upper bound cannot be among the k best
 	const float* row_w;
 	const float* q_w;
+	// speculative thresholds: the lists were filtered with spec_tau[q] (true units), tighter than
+	// the proven threshold.  Where a query's result is emitted its k-th exact score S_k is known: fewer than k rows,
+	// or S_k > spec_tau[q], and the query number is appended to redo_list through the counter in *redo_word (low
+	// 20 bits: failing queries; from bit 20: redo overflows).  spec_tau == nullptr: no check.
+	const float* spec_tau;
+	uint32_t* redo_word;
+	uint32_t* redo_list;      // [redo_cap]
+	uint32_t redo_cap;
+	// the redo pass's own select: query slot s (lists, counters, qnrm, q_w) belongs to query slot_map[s] (the
+	// re-rank's query row, the output rows); slots at and beyond the failing count (*live_slots, low 20 bits) leave
+	// at once, and an overflowing list adds 2^20 to *overflow (= the redo word) instead of 1
+	const uint32_t* slot_map;
+	const uint32_t* live_slots;
 };
+constexpr uint32_t kRedoCountMask = 0xFFFFFu;  // (a pass has at most 32 768 queries)
+constexpr uint32_t kRedoOverflowUnit = 1u << 20;
+
+// the check of a speculative threshold for query qi: has_kth = the list held k rows, s_k = the k-th exact score
+__device__ inline void spec_check(const SelectParams& p, uint32_t qi, bool has_kth, float s_k) {
+	if (!p.spec_tau || (has_kth && s_k <= p.spec_tau[qi]))
+		return;
+	const uint32_t slot = atomicAdd(p.redo_word, 1u) & kRedoCountMask;
+	if (slot < p.redo_cap)
+		p.redo_list[slot] = qi;
+}
 
 // the cutoff of the int8 filter's pruning from the k-th smallest (ordered) kappa + w_b: + w_q, + the margin
 // for the fp32 rounding of keys and sums (scan_gemm_i8f.hpp); no k-th value (or an infinite one): no cut
@@ -135,6 +159,8 @@ __device__ inline void wave_emit_sorted(const SelectParams& p, const uint64_t* l
 				p.out_ids[(size_t)qi * p.k + r[j]] = (uint64_t)key_idx(e[j]) + p.id_offset;
 			if (p.out_dists)
 				p.out_dists[(size_t)qi * p.k + r[j]] = key_score(e[j]);
+			if (r[j] == p.k - 1)
+				spec_check(p, qi, true, key_score(e[j]));
 			if (r[j] == p.k - 1 && p.tau_out) {
 				p.tau_out[qi] = key_score(e[j]);
 				if (p.tau_row_out)
@@ -147,6 +173,8 @@ __device__ inline void wave_emit_sorted(const SelectParams& p, const uint64_t* l
 			if (p.out_dists)
 				p.out_dists[(size_t)qi * p.k + i] = __builtin_inff();
 		}
+		if (lane == 0 && n_s < p.k)
+			spec_check(p, qi, false, 0.0f);
 		if (lane == 0 && n_s < p.k && p.tau_out) {
 			p.tau_out[qi] = p.tau_prev ? p.tau_prev[qi] : __builtin_inff();
 			if (p.tau_row_out)
@@ -166,6 +194,8 @@ __device__ inline void wave_emit_sorted(const SelectParams& p, const uint64_t* l
 				p.out_ids[(size_t)qi * p.k + r] = ok ? (uint64_t)key_idx(mn) + p.id_offset : ~0ull;
 			if (p.out_dists)
 				p.out_dists[(size_t)qi * p.k + r] = ok ? key_score(mn) : __builtin_inff();
+			if (r == p.k - 1)
+				spec_check(p, qi, ok, key_score(mn));
 			if (r == p.k - 1 && p.tau_out) {
 				p.tau_out[qi] = ok ? key_score(mn) : (p.tau_prev ? p.tau_prev[qi] : __builtin_inff());
 				if (p.tau_row_out)
@@ -218,9 +248,11 @@ template <int PER> __device__ inline uint32_t wave_kth_largest_u32(const uint32_
 // reach it -- they are compacted into `scratch` (64 words of LDS, this wave's own) and the
 // bisection runs over one value per lane instead of PER.  Falls back to the full bisection when
 // more than 64 values reach B (ties, k close to the number of values).
+// (j != 0: the j-th largest as well, j <= k, in .y -- it is among the values that reach B, so one more one-value
+// bisection; .x = the k-th largest)
 template <int PER>
-__device__ inline uint32_t wave_kth_largest_sparse_u32(const uint32_t (&v)[PER], uint32_t k, uint32_t* scratch,
-                                                       int lane) {
+__device__ inline uint2 wave_kth_largest_sparse_u32(const uint32_t (&v)[PER], uint32_t k, uint32_t* scratch,
+                                                    int lane, uint32_t j = 0) {
 	uint32_t mx[1] = {v[0]};
 #pragma unroll
 	for (int j = 1; j < PER; ++j)
@@ -231,7 +263,7 @@ __device__ inline uint32_t wave_kth_largest_sparse_u32(const uint32_t (&v)[PER],
 	for (int j = 0; j < PER; ++j)
 		total += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(v[j] >= B));
 	if (total > 64)
-		return wave_kth_largest_u32<PER>(v, k);
+		return make_uint2(wave_kth_largest_u32<PER>(v, k), j ? wave_kth_largest_u32<PER>(v, j) : 0u);
 	uint32_t base = 0;  // wave-uniform
 #pragma unroll
 	for (int j = 0; j < PER; ++j) {
@@ -245,10 +277,10 @@ __device__ inline uint32_t wave_kth_largest_sparse_u32(const uint32_t (&v)[PER],
 	__builtin_amdgcn_wave_barrier();
 	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 	uint32_t w[1] = {lane < (int)total ? scratch[lane] : 0u};
-	return wave_kth_largest_u32<1>(w, k);
+	return make_uint2(wave_kth_largest_u32<1>(w, k), j ? wave_kth_largest_u32<1>(w, j) : 0u);
 }
 
-// one wave orders the list of query qi (c <= 64 * PER keys); list = 64 * PER keys of LDS
+// one wave orders the list of query slot qi (c <= 64 * PER keys); list = 64 * PER keys of LDS
 template <int PER>
 __device__ inline void select_wave_body(const SelectParams& p, uint32_t qi, uint32_t c, uint64_t* list,
                                         int lane) {
@@ -258,7 +290,8 @@ __device__ inline void select_wave_body(const SelectParams& p, uint32_t qi, uint
 	for (int j = 0; j < PER; ++j)
 		kk[j] = lane + 64 * j < (int)c ? src[lane + 64 * j] : kSentinelKey;
 	const uint32_t l = lane & 15, grp = lane >> 4;  // 16 lanes per candidate row
-	const float* q = p.rerank_queries + (size_t)qi * p.dim + l;
+	const uint32_t qo = p.slot_map ? p.slot_map[qi] : qi;  // (the query whose row is re-ranked and whose outputs are written)
+	const float* q = p.rerank_queries + (size_t)qo * p.dim + l;
 	float cutoff = __builtin_inff();
 	// lists with FINAL scores (the 8-bit forms: no re-score) are cut at their k-th smallest score itself --
 	// what is left to rank is k keys + ties instead of the whole list (k = 100 on uint8 rows: 535 keys, each
@@ -370,9 +403,9 @@ __device__ inline void select_wave_body(const SelectParams& p, uint32_t qi, uint
 	}
 	asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 	if (n_s <= 256)
-		wave_emit_sorted<(PER < 4 ? PER : 4)>(p, list, n_s, qi, lane);
+		wave_emit_sorted<(PER < 4 ? PER : 4)>(p, list, n_s, qo, lane);
 	else
-		wave_emit_sorted<PER>(p, list, n_s, qi, lane);
+		wave_emit_sorted<PER>(p, list, n_s, qo, lane);
 }
 
 // lists of at most 64 * PER keys; WAVES queries per workgroup (PER = 32: one, its list is 16 KB)
@@ -397,6 +430,9 @@ __global__ __launch_bounds__(kBlock) void select_topk_kernel(SelectParams p) {
 	uint64_t* keys = reinterpret_cast<uint64_t*>(smem_raw);
 	const uint32_t qi = blockIdx.x;
 	const uint32_t tid = threadIdx.x;
+	if (p.live_slots && qi >= (*p.live_slots & kRedoCountMask))
+		return;  // (redo pass: a slot no failing query took)
+	const uint32_t qo = p.slot_map ? p.slot_map[qi] : qi;
 	uint32_t c = p.cand_cnt ? p.cand_cnt[qi] : p.fixed_count;
 	if (p.wave_done && c <= p.wave_done && c <= p.cap)
 		return;  // served by a wave kernel (those leave overflowed lists, c > cap, to this one)
@@ -413,7 +449,7 @@ __global__ __launch_bounds__(kBlock) void select_topk_kernel(SelectParams p) {
 	}
 	if (c > p.cap) {
 		if (tid == 0)
-			atomicAdd(p.overflow, 1u);
+			atomicAdd(p.overflow, p.live_slots ? kRedoOverflowUnit : 1u);
 		c = p.cap;
 	}
 	uint32_t n2 = 2;
@@ -442,7 +478,7 @@ __global__ __launch_bounds__(kBlock) void select_topk_kernel(SelectParams p) {
 	};
 	if (p.rerank_base) {
 		const uint32_t l = tid & 15, grp = tid >> 4;  // 16 lanes per candidate row
-		const float* q = p.rerank_queries + (size_t)qi * p.dim + l;
+		const float* q = p.rerank_queries + (size_t)qo * p.dim + l;
 		uint32_t n_rescore = c;
 		if ((p.prune_eps > 0.0f || p.row_w) && c > p.k) {
 			// order by the approximate key, keep what can still reach the k best
@@ -518,9 +554,13 @@ __global__ __launch_bounds__(kBlock) void select_topk_kernel(SelectParams p) {
 		const uint64_t key = i < n2 ? keys[i] : kSentinelKey;
 		const bool ok = key != kSentinelKey;
 		if (p.out_ids)
-			p.out_ids[(size_t)qi * p.k + i] = ok ? (uint64_t)key_idx(key) + p.id_offset : ~0ull;
+			p.out_ids[(size_t)qo * p.k + i] = ok ? (uint64_t)key_idx(key) + p.id_offset : ~0ull;
 		if (p.out_dists)
-			p.out_dists[(size_t)qi * p.k + i] = ok ? key_score(key) : __builtin_inff();
+			p.out_dists[(size_t)qo * p.k + i] = ok ? key_score(key) : __builtin_inff();
+	}
+	if (tid == 0) {
+		const uint64_t key = (p.k - 1 < n2) ? keys[p.k - 1] : kSentinelKey;
+		spec_check(p, qo, key != kSentinelKey, key_score(key));
 	}
 	if (tid == 0 && p.tau_out) {
 		const uint64_t key = (p.k - 1 < n2) ? keys[p.k - 1] : kSentinelKey;

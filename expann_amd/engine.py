@@ -104,6 +104,12 @@ class GpuBruteForceEngine:
     def set_option(self, name, value):
         _lib.check(self._h, self._L.expann_set_option(self._h, name.encode(), int(value)))
 
+    def get_stat(self, name):
+        """expann_get_stat: "redo_queries", "redo_overflows", "spec_rank" (speculative thresholds)."""
+        v = C.c_uint64(0)
+        _lib.check(self._h, self._L.expann_get_stat(self._h, name.encode(), C.byref(v)))
+        return int(v.value)
+
     def set_profiling(self, enable=True):
         _lib.check(self._h, self._L.expann_set_profiling(self._h, int(bool(enable))))
 

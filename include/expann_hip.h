@@ -367,8 +367,24 @@ int expann_sharded_get_profile(expann_sharded* h, int shard, expann_profile* out
  * its norm to the largest row's -- ranks unchanged, results exact; 0: rounds 1-2's unscaled filter),
  * "i8_filter" (fp32 L2, d = 128, scan_kernel on auto: the full scan on the int8 matrix cores with a rigorous
  * slack and the exact re-rank, thresholds from the fp16 sampled pass; 1 (default): from the planner's crossover
- * on, 2: wherever supported, 0: never; the environment variable EXPANN_I8_FILTER sets the starting value). */
+ * on, 2: wherever supported, 0: never; the environment variable EXPANN_I8_FILTER sets the starting value),
+ * "spec_rank" (fp32 rows, d = 64 / 128, batches of more than 64 queries: the full scan filters with a SPECULATIVE
+ * threshold, the j-th largest class maximum of the sampled pass instead of the k-th; the select checks every
+ * query's result against it and the few failing queries are searched again on the device with the proven
+ * threshold -- ids and distances do not change.  0 (default): j from k, the sampled share of the rows and a share
+ * of failing queries of at most 1 %, where the planner found a gain; j >= 1: that rank wherever the check exists;
+ * j >= k: off.  The environment variable EXPANN_SPEC_RANK sets the starting value). */
 int expann_set_option(expann_index* h, const char* name, long value);
+
+/* counters outside expann_profile (whose layout is fixed): "redo_queries" = queries of the last search that the
+ * redo pass of the speculative thresholds served (deferred searches: of the searches the last expann_sync
+ * checked), "redo_overflows" = searches since the handle was made whose failing queries did not fit the redo
+ * pass (repeated with proven thresholds: a retry), "spec_rank" = the rank j of the last search's thresholds
+ * (= k: proven thresholds). */
+int expann_get_stat(expann_index* h, const char* name, uint64_t* out);
+/* the auto rank for k neighbours when the sampled pass reads 1/sample_frac of the rows: the smallest j with
+ * P(Bin(k - 1, 1/sample_frac) >= j) <= 1 %; k = no speculation.  Host arithmetic only. */
+uint32_t expann_spec_rank_auto(size_t k, uint32_t sample_frac);
 
 #ifdef __cplusplus
 }
