@@ -32,6 +32,8 @@
 #include "scan_gemm_i8x.hpp"
 #include "scan_gemm_i8w.hpp"
 #include "scan_int8.hpp"
+#include "scan_int8_any.hpp"
+#include "scan_gemm_i8kl.hpp"
 #include "score_ids.hpp"
 #include "select.hpp"
 
@@ -285,11 +287,31 @@ const ScanI8Variant kScanI8[] = {SCAN_I8(64, 1),  SCAN_I8(64, 16), SCAN_I8(128, 
 #undef SCAN_I16
 #undef SCAN_I8
 #undef SCAN_I8_M
+// every other 8-bit dim (multiples of 64 up to kMaxAnyDim): the run-time-dim scan (d = 0 in the table)
+#define SCAN_I8_ANY_M(TQ, MODE, MN) {0, TQ, MODE, scan_filter_i8_any_kernel<TQ, MODE>, "scan_filter_i8_any<" #TQ "," MN ">"}
+#define SCAN_I8_ANY(TQ) SCAN_I8_ANY_M(TQ, kU8L2, "U8L2"), SCAN_I8_ANY_M(TQ, kI8L2, "I8L2"), \
+	SCAN_I8_ANY_M(TQ, kI8L2Ref, "I8L2REF"), SCAN_I8_ANY_M(TQ, kI8IP, "I8IP")
+const ScanI8Variant kScanI8Any[] = {SCAN_I8_ANY(1), SCAN_I8_ANY(4), SCAN_I8_ANY(8)};
+#undef SCAN_I8_ANY
+#undef SCAN_I8_ANY_M
+// 8-bit rows (not int16) of a dim without a compiled instance
+inline bool any_dim_i8(int d, int mode) {
+	if (mode < 0 || mode == kI16L2Ref || d < 64 || d > kMaxAnyDim || d % 64 != 0)
+		return false;
+	for (const auto& v : kScanI8)
+		if (v.d == d && v.mode == mode)
+			return false;
+	return true;
+}
 
 const ScanI8Variant* pick_scan_i8(int d, int mode, size_t m, long forced_tq) {
 	const ScanI8Variant* best = nullptr;
-	for (const auto& v : kScanI8) {
-		if (v.d != d || v.mode != mode)
+	const bool any = any_dim_i8(d, mode);
+	const ScanI8Variant* tab = any ? kScanI8Any : kScanI8;
+	const size_t n_tab = any ? sizeof(kScanI8Any) / sizeof(kScanI8Any[0]) : sizeof(kScanI8) / sizeof(kScanI8[0]);
+	for (size_t i = 0; i < n_tab; ++i) {
+		const ScanI8Variant& v = tab[i];
+		if ((!any && v.d != d) || v.mode != mode)
 			continue;
 		if (forced_tq > 0) {
 			if (v.tq == forced_tq)
@@ -320,6 +342,8 @@ const ScoreI8Variant kScoreI8[] = {SCORE_I8(64), SCORE_I8(128), SCORE_I8(256), S
                                    {64, kI16L2Ref, score_ids_i8_kernel<128, kI16L2Ref>},
                                    {128, kI16L2Ref, score_ids_i8_kernel<256, kI16L2Ref>}};
 #undef SCORE_I8
+const ScoreI8Variant kScoreI8Any[] = {{0, kU8L2, score_ids_i8_any_kernel<kU8L2>}, {0, kI8L2, score_ids_i8_any_kernel<kI8L2>},
+                                      {0, kI8L2Ref, score_ids_i8_any_kernel<kI8L2Ref>}, {0, kI8IP, score_ids_i8_any_kernel<kI8IP>}};
 
 uint32_t pow2ceil(uint32_t x) {
 	uint32_t p = 1;
@@ -930,6 +954,8 @@ uint32_t sample_frac_for(const expann_index* h, size_t k) {
 
 // ---- 8-bit GEMM form, queue geometry (scan_gemm_i8q.hpp), d = 128 / 256 / 768 / 832 / 960 -----
 using GemmI8qFn = void (*)(GemmI8qParams);
+using SelfI8AnyFn = void (*)(const void*, uint32_t, int*, uint32_t);
+using ThetaI8AnyFn = void (*)(const void*, uint32_t, const float*, int*, int*, uint32_t);
 struct GemmI8qVariant {
 	int d, mode;
 	GemmI8qFn scan, sample;
@@ -942,6 +968,10 @@ struct GemmI8qVariant {
 	void (*scan_w)(GemmI8wParams) = nullptr;
 	int lds_w = 0, threads_w = 0, wg_per_cu_w = 0;
 	void (*sample_w)(GemmI8wParams) = nullptr;  // the sampled pass on the same stream (SAMPLE instance; same launch geometry)
+	// scan_gemm_i8kl.hpp (d = 0): rows per tile, and the preludes that take the dim at run time
+	int tb = kF16TB;
+	SelfI8AnyFn self_any = nullptr;
+	ThetaI8AnyFn theta_any = nullptr;
 };
 // the 16x16x64 kernels of the 8-waves-per-tile geometries (scan_gemm_i8x.hpp): d = 768, and d = 832 / 960 -- rows in
 // 1024-byte slots -- with DR = d (the zero-padded k-steps are left out); scan and SAMPLE instance
@@ -953,7 +983,9 @@ const GemmI8qVariant kGemmI8x[] = {
     GEMM_I8X_P(832, 1024, kU8L2, true, "U8L2"), GEMM_I8X_P(832, 1024, kI8L2, true, "I8L2"),
     GEMM_I8X_P(832, 1024, kI8IP, false, "I8IP"),
     GEMM_I8X_P(960, 1024, kU8L2, true, "U8L2"), GEMM_I8X_P(960, 1024, kI8L2, true, "I8L2"),
-    GEMM_I8X_P(960, 1024, kI8IP, false, "I8IP")};
+    GEMM_I8X_P(960, 1024, kI8IP, false, "I8IP"),
+    GEMM_I8X_P(896, 1024, kU8L2, true, "U8L2"), GEMM_I8X_P(896, 1024, kI8L2, true, "I8L2"),
+    GEMM_I8X_P(896, 1024, kI8IP, false, "I8IP")};
 #undef GEMM_I8X_P
 // d = 128 / 256: f16x's step structure on 16x16x64 with hit logs (scan_gemm_i8w.hpp)
 #define GEMM_I8W(D, MODE, L2F, MN) {D, MODE, nullptr, nullptr, row_self_i8_kernel<D, MODE>, \
@@ -966,6 +998,13 @@ const GemmI8qVariant kGemmI8w[] = {
 // the int8 filter of fp32 rows (scan_gemm_i8f.hpp): the d = 128 i8w full scan on the index's int8 copy
 const GemmI8qVariant kGemmI8F = GEMM_I8W(128, kI8L2, true, "F32L2");
 #undef GEMM_I8W
+// every other 8-bit dim (multiples of 64 up to 4096): the K-loop form with the dim known at run time
+// (scan_gemm_i8kl.hpp; d = 0 here, rows in the index's own d bytes, 128-row tiles, hit logs)
+#define GEMM_I8KL(MODE, MN) {0, MODE, nullptr, nullptr, nullptr, nullptr, "scan_gemm_i8kl<" MN ">", 0, kI8klLds, kF16Threads, 1, \
+	scan_gemm_i8kl_kernel<false>, kI8klLds, kF16Threads, 1, scan_gemm_i8kl_kernel<true>, kI8klTB, \
+	row_self_i8_any_kernel<MODE>, query_theta_i8_any_kernel<MODE>}
+const GemmI8qVariant kGemmI8KL[] = {GEMM_I8KL(kU8L2, "U8L2"), GEMM_I8KL(kI8L2, "I8L2"), GEMM_I8KL(kI8IP, "I8IP")};
+#undef GEMM_I8KL
 constexpr int kRetryGeneric = -1000;  // internal: the caller falls back to the threshold ladder
 constexpr int kStrictReject = -1001;  // internal (uint8 shadow): these queries are not 8-bit integers
 
@@ -982,6 +1021,10 @@ const GemmI8qVariant* pick_gemm_i8q(const expann_index* h, size_t m, size_t k) {
 	for (const auto& v : kGemmI8x)
 		if (v.d == h->dim && v.mode == h->int_mode)
 			return &v;
+	if (any_dim_i8(h->dim, h->int_mode))  // no compiled form: the run-time-dim one
+		for (const auto& v : kGemmI8KL)
+			if (v.mode == h->int_mode)
+				return &v;
 	return nullptr;
 }
 
@@ -1076,29 +1119,34 @@ int ensure_i8f(expann_index* h, hipStream_t st) {
 int ensure_i8q(expann_index* h, const GemmI8qVariant* gq, hipStream_t st) {
 	if (h->d_base_i8q)
 		return EXPANN_OK;
-	const size_t n_pad = (h->n + kF16TB - 1) / kF16TB * kF16TB;
+	const size_t n_pad = (h->n + gq->tb - 1) / gq->tb * gq->tb;
+	const int dq = gq->dq ? gq->dq : h->dim;  // (the run-time-dim form keeps the index's row length)
 	if (h->int_mode != kI8IP && !h->d_bias_i) {
 		HIP_TRY(h, hipMalloc(&h->d_bias_i, sizeof(int) * h->n));
-		hipLaunchKernelGGL(gq->self, dim3((uint32_t)((h->n + kRowsPerGroup - 1) / kRowsPerGroup)),
-		                   dim3(kBlock), 0, st, (const void*)h->d_base, (uint32_t)h->n, h->d_bias_i);
+		const dim3 grid((uint32_t)((h->n + kRowsPerGroup - 1) / kRowsPerGroup));
+		if (gq->self_any)
+			hipLaunchKernelGGL(gq->self_any, grid, dim3(kBlock), 0, st, (const void*)h->d_base, (uint32_t)h->n,
+			                   h->d_bias_i.as<int>(), (uint32_t)h->dim);
+		else
+			hipLaunchKernelGGL(gq->self, grid, dim3(kBlock), 0, st, (const void*)h->d_base, (uint32_t)h->n, h->d_bias_i);
 	}
 	HIP_TRY(h, hipMalloc(&h->d_bp_i8q, sizeof(int) * n_pad));
 	hipLaunchKernelGGL(i8q_bp_kernel, dim3((uint32_t)((n_pad + kBlock - 1) / kBlock)), dim3(kBlock), 0,
 	                   st, h->int_mode != kI8IP ? h->d_bias_i.as<const int>() : (const int*)nullptr,
 	                   (uint32_t)h->n, (uint32_t)n_pad, h->d_bp_i8q);
-	if (gq->dq != h->dim) {
+	if (dq != h->dim) {
 		// own copy with rows padded to dq bytes (zeros in the int8 domain), whole 64-row tiles
 		void* copy = nullptr;
-		HIP_TRY(h, hipMalloc(&copy, n_pad * (size_t)gq->dq));
+		HIP_TRY(h, hipMalloc(&copy, n_pad * (size_t)dq));
 		hipLaunchKernelGGL(i8q_pad_rows_kernel, dim3(8192), dim3(kBlock), 0, st, (const uint32_t*)h->d_base, h->n,
-		                   (uint32_t)h->dim / 4, (uint32_t)gq->dq / 4, n_pad,
+		                   (uint32_t)h->dim / 4, (uint32_t)dq / 4, n_pad,
 		                   h->int_mode == kU8L2 ? 0x80808080u : 0u, (uint32_t*)copy);
 		h->d_base_i8q = copy;
 		h->base_i8q_owned = true;
 	} else if (h->int_mode == kU8L2 || n_pad != h->n) {
 		// own copy: whole 64-row tiles (zero rows behind the end), uint8 rows mapped to int8
 		void* copy = nullptr;
-		HIP_TRY(h, hipMalloc(&copy, n_pad * h->dim));
+		HIP_TRY(h, hipMalloc(&copy, n_pad * (size_t)h->dim));
 		const size_t words = h->n * (size_t)h->dim / 4, words_pad = n_pad * (size_t)h->dim / 4;
 		hipLaunchKernelGGL(i8q_copy_xor_kernel, dim3(4096), dim3(kBlock), 0, st, (const uint32_t*)h->d_base,
 		                   words, words_pad, h->int_mode == kU8L2 ? 0x80808080u : 0u, (uint32_t*)copy);
@@ -1129,12 +1177,13 @@ int search_i8q(expann_index* h, const GemmI8qVariant* gq, const void* d_queries,
 	if (rc != EXPANN_OK)
 		return rc;
 	const void* q8 = d_queries;
-	if (gq->dq != h->dim) {  // rows of the padded geometry: queries padded (and mapped) the same way
-		const size_t nb = m * (size_t)gq->dq;
+	const int dq = gq->dq ? gq->dq : h->dim;
+	if (dq != h->dim) {  // rows of the padded geometry: queries padded (and mapped) the same way
+		const size_t nb = m * (size_t)dq;
 		HIP_TRY(h, grow_ws(h, h->d_q_split, nb));
 		hipLaunchKernelGGL(i8q_pad_rows_kernel, dim3((uint32_t)std::min<size_t>((nb / 4 + kBlock - 1) / kBlock, 1024)),
 		                   dim3(kBlock), 0, st, (const uint32_t*)d_queries, m, (uint32_t)h->dim / 4,
-		                   (uint32_t)gq->dq / 4, m, h->int_mode == kU8L2 ? 0x80808080u : 0u,
+		                   (uint32_t)dq / 4, m, h->int_mode == kU8L2 ? 0x80808080u : 0u,
 		                   h->d_q_split.as<uint32_t>());
 		q8 = h->d_q_split;
 	} else if (h->int_mode == kU8L2) {  // queries ^ 0x80 (d_queries is the uint8 conversion, d_q8)
@@ -1145,9 +1194,10 @@ int search_i8q(expann_index* h, const GemmI8qVariant* gq, const void* d_queries,
 		                   h->d_q_split.as<uint32_t>());
 		q8 = h->d_q_split;
 	}
-	const uint32_t nt = (uint32_t)((h->n + kF16TB - 1) / kF16TB);
+	const uint32_t nt = (uint32_t)((h->n + gq->tb - 1) / gq->tb);
 	const uint32_t run = (uint32_t)h->opt_sample_run;
-	const uint32_t t_sel = std::max<uint32_t>(256, nt / sample_frac_for(h, k)) / run * run;
+	// (at least 256 tiles of 64 rows: the same rows with the 128-row tiles of the run-time-dim form)
+	const uint32_t t_sel = std::max<uint32_t>(256 * kF16TB / gq->tb, nt / sample_frac_for(h, k)) / run * run;
 	const uint32_t nqt = (uint32_t)((m + kF16TQ - 1) / kF16TQ);
 	const uint32_t wg_slots = (uint32_t)(gq->sample_w ? gq->wg_per_cu_w : gq->wg_per_cu) * (uint32_t)cus;
 	uint32_t chunks = std::max<uint32_t>(1, wg_slots / nqt);
@@ -1163,7 +1213,11 @@ int search_i8q(expann_index* h, const GemmI8qVariant* gq, const void* d_queries,
 			return rc;
 		HIP_TRY(h, hipMemsetAsync(h->d_overflow, 0, sizeof(uint32_t), st));
 		HIP_TRY(h, hipMemsetAsync(h->d_total, 0, sizeof(unsigned long long) * 2, st));
-		if (h->int_mode != kI8IP)
+		if (h->int_mode != kI8IP && gq->theta_any)
+			hipLaunchKernelGGL(gq->theta_any, dim3((uint32_t)((m + kRowsPerGroup - 1) / kRowsPerGroup)),
+			                   dim3(kBlock), 0, st, d_queries, (uint32_t)m, (const float*)nullptr,
+			                   (int*)nullptr, h->d_qself.as<int>(), (uint32_t)h->dim);
+		else if (h->int_mode != kI8IP)
 			hipLaunchKernelGGL(gq->theta, dim3((uint32_t)((m + kRowsPerGroup - 1) / kRowsPerGroup)),
 			                   dim3(kBlock), 0, st, d_queries, (uint32_t)m, (const float*)nullptr,
 			                   (int*)nullptr, h->d_qself);
@@ -1183,6 +1237,7 @@ int search_i8q(expann_index* h, const GemmI8qVariant* gq, const void* d_queries,
 		sp.m = (uint32_t)m;
 		sp.sample_out = h->d_sample.as<int>();
 		sp.n_chunks = schunks;
+		sp.ksteps = (uint32_t)h->dim / 64;
 		if (dbg)
 			std::fprintf(stderr, "[i8q] sample: grid %u x %u, t_sel %u stride %u tpb %u chunks %u nt %u m %zu base %p bp %p q %p out %p (%zu B)\n",
 			             schunks, nqt, t_sel, sp.tile_stride, sp.tiles_per_block, schunks, nt, m, sp.base,
@@ -2603,6 +2658,11 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 		g_create_error = "8-bit rows need dim % 64 == 0 (src/distance.h:29-53, antitopo_engine.h:726)";
 		return EXPANN_ERR_INVALID_ARG;
 	}
+	if (int_mode >= 0 && int_mode != kI16L2Ref && dim > kMaxAnyDim) {
+		g_create_error = "unsupported dim " + std::to_string(dim) + ": 8-bit rows take dim <= " +
+		                 std::to_string(kMaxAnyDim);
+		return EXPANN_ERR_UNSUPPORTED;
+	}
 	int ndev = expann_device_count();
 	if (ndev <= 0) {
 		g_create_error = "no HIP device visible: libexpann_hip has no CPU fallback";
@@ -2615,7 +2675,7 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 	if ((int_mode < 0 && !pick_scan_f32(dim, metric == EXPANN_METRIC_IP, 1, 0)) ||
 	    (int_mode >= 0 && !pick_scan_i8(dim, int_mode, 1, 0))) {
 		g_create_error = "unsupported dim " + std::to_string(dim) +
-		                 " (built: f32 any multiple of 16 up to 4096; 8-bit 64,128,256,768,832,960)";
+		                 " (built: f32 any multiple of 16 up to 4096; 8-bit any multiple of 64 up to 4096; int16 64,128)";
 		return EXPANN_ERR_UNSUPPORTED;
 	}
 	expann_index* h = new expann_index();
@@ -2694,6 +2754,16 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 			delete h;
 			return EXPANN_ERR_HIP;
 		}
+	if (any_dim_i8(dim, int_mode))
+		for (const auto& v : kGemmI8KL)
+			if (v.mode == int_mode &&
+			    (hipFuncSetAttribute((const void*)v.scan_w, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds_w) != hipSuccess ||
+			     hipFuncSetAttribute((const void*)v.sample_w, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds_w) != hipSuccess)) {
+				g_create_error = "hipFuncSetAttribute(scan_gemm_i8kl_kernel) failed";
+				hipStreamDestroy(h->stream);
+				delete h;
+				return EXPANN_ERR_HIP;
+			}
 	for (const auto& v : kGemmBf16)
 		if (v.d == dim)
 			if (hipFuncSetAttribute((const void*)v.scan, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -3057,6 +3127,10 @@ int expann_score_ids(expann_index* h, const void* query, const uint64_t* ids, si
 		for (const auto& v : kScoreI8)
 			if (v.d == h->dim && v.mode == h->int_mode)
 				sv = &v;
+		if (!sv && any_dim_i8(h->dim, h->int_mode))
+			for (const auto& v : kScoreI8Any)
+				if (v.mode == h->int_mode)
+					sv = &v;
 		if (!sv)
 			return h->fail(EXPANN_ERR_UNSUPPORTED, "no 8-bit score kernel for this dim");
 		const void* qptr = d_query;
@@ -3074,7 +3148,7 @@ int expann_score_ids(expann_index* h, const void* query, const uint64_t* ids, si
 			qptr = d_q8s;
 		}
 		ScoreIdsI8Params sp{h->d_base, qptr, (const uint64_t*)d_idl, h->id_offset, (uint32_t)n_ids,
-		                    (float*)d_sc};
+		                    (float*)d_sc, (uint32_t)h->dim};
 		hipLaunchKernelGGL(sv->fn, dim3(blocks), dim3(kBlock), 0, h->stream, sp);
 	}
 	// the `d < cutoff` filter, order kept (src/quantizer.h:42-46): compacted on the device, only the

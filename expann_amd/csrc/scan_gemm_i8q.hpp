@@ -45,6 +45,7 @@ struct GemmI8qParams {
 	uint32_t n_chunks;
 	uint32_t xcd_map;        // XCD-aware block placement, as GemmF16Params::xcd_map
 	const uint32_t* live_q;  // scan_gemm_i8w_kernel, redo pass (GemmF16Params::live_q): live query slots, or nullptr
+	uint32_t ksteps;         // scan_gemm_i8kl_kernel only: 64-byte MFMA k-steps per row (= dim / 64)
 };
 
 // bp[i] = bias[i] >> 1 for i < n, kI8qPadBp for n <= i < n_pad (bias == nullptr: zeros)

@@ -240,6 +240,7 @@ struct ScoreIdsI8Params {
 	uint64_t id_offset;
 	uint32_t n_ids;
 	float* scores;
+	uint32_t dim;       // score_ids_i8_any_kernel only: bytes per row
 };
 template <int D, int MODE>
 __global__ __launch_bounds__(kBlock) void score_ids_i8_kernel(ScoreIdsI8Params p) {

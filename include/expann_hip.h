@@ -68,7 +68,10 @@ int expann_device_count(void);
 
 /* lifecycle (replaces: engine construction, src/bench_runner.h:33) -------------------- */
 /* dim: a multiple of 16 (else EXPANN_ERR_INVALID_ARG).  f32 rows: any such dim up to 4096 (over it:
- * EXPANN_ERR_UNSUPPORTED, checked before the device); 8-bit rows: 64, 128, 256, 768, 832, 960;
+ * EXPANN_ERR_UNSUPPORTED, checked before the device); 8-bit rows (U8, I8): any multiple of 64 up to 4096
+ * (not a multiple of 64: EXPANN_ERR_INVALID_ARG; over 4096: EXPANN_ERR_UNSUPPORTED, checked before the device;
+ * 64, 128, 256, 768, 832, 960 have kernels compiled for them, the others run with the dim known at run time --
+ * d = 896 on the matrix cores through the 1024-byte-slot form of 832 / 960);
  * int16 rows: 64, 128. */
 int expann_create(int dim, int dtype, int metric, int device, expann_index** out);
 void expann_destroy(expann_index* h);
@@ -348,7 +351,8 @@ int expann_sharded_get_profile(expann_sharded* h, int shard, expann_profile* out
  * "scan_kernel" (0 = auto, 1 = direct VALU scan, 2 = GEMM form on the fp32 / int8 matrix
  * cores, 3 = GEMM form on the bf16 matrix cores with the 3-term split, 4 = GEMM form with one
  * scaled fp16 product, 5 = 8-bit rows: int8 MFMA form with per-wave hit queues (d = 128,
- * 256, 768, 832, 960); the final ids and distances are identical for every choice),
+ * 256, 768, 832, 896, 960 compiled; every other multiple of 64 up to 4096 with the dim known at
+ * run time); the final ids and distances are identical for every choice),
  * "sample_ratio" (rows ratio between the levels of the threshold ladder, default 32),
  * "sample_pass" (fp16 form: 1 = one sampled pass gives the threshold (default), 0 = ladder),
  * "sample_frac" (the sampled pass reads 1/frac of the rows; 0 = chosen from k (default)),
