@@ -11,6 +11,7 @@ OK = 0
 ERR_INVALID_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_NOT_BUILT, ERR_UNSUPPORTED, ERR_OVERFLOW = 1, 2, 3, 4, 5, 6
 DTYPE_F32, DTYPE_U8, DTYPE_I8, DTYPE_I16 = 0, 1, 2, 3
 METRIC_L2, METRIC_IP, METRIC_L2_I8_REFCOMPAT = 0, 1, 2
+GRAPH_FP32, GRAPH_U8_CAST, GRAPH_RANGED_Q8 = 0, 1, 2  # expann_graph_compression
 
 # every symbol include/expann_hip.h declares
 ABI_SYMBOLS = [
@@ -34,6 +35,7 @@ ABI_SYMBOLS = [
     "expann_sharded_get_profile", "expann_sharded_exchange_pattern", "expann_sharded_comm_ranks",
     "expann_sharded_last_enqueue_ms", "expann_sharded_set_alltoallv_fn", "expann_sharded_search_devices",
     "expann_sharded_slice", "expann_device_heap_trace",
+    "expann_graph_search_mode", "expann_graph_ranged_params", "expann_antitopo_set_compression",
 ]
 
 
@@ -153,6 +155,12 @@ def load():
     L.expann_graph_last_error.argtypes = [vp]
     L.expann_graph_search.restype = C.c_int
     L.expann_graph_search.argtypes = [vp, vp, sz, sz, sz, C.c_int, vp, vp, vp]
+    L.expann_graph_search_mode.restype = C.c_int
+    L.expann_graph_search_mode.argtypes = [vp, vp, sz, sz, sz, C.c_int, vp, vp, vp]
+    L.expann_graph_ranged_params.restype = C.c_int
+    L.expann_graph_ranged_params.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.expann_antitopo_set_compression.restype = C.c_int
+    L.expann_antitopo_set_compression.argtypes = [vp, C.c_int]
     L.expann_graph_last_kernel_ms.restype = C.c_double
     L.expann_graph_last_kernel_ms.argtypes = [vp]
     L.expann_antitopo_create.restype = C.c_int

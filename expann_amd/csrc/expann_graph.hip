@@ -26,6 +26,11 @@ struct expann_graph {
 	uint32_t n_layers = 0, starting_vertex = 0, max_degree0 = 0;
 	float* d_vectors = nullptr;
 	uint8_t* d_compressed = nullptr;
+	// quantizer_ranged_q8 copy of the rows (bytes in [0, 127]) with its scale_factor / offset, built at the first
+	// use of the ranged mode; ranged_state: 0 = not built yet, 1 = usable, -1 = the quantiser is unusable
+	uint8_t* d_ranged = nullptr;
+	float ranged_scale = 0, ranged_offset = 0;
+	int ranged_state = 0;
 	uint32_t* d_layer_off = nullptr;
 	uint32_t* d_neighbours = nullptr;
 	uint32_t* d_adj0 = nullptr;   // [n][stride0] layer-0 lists at a fixed stride, padded with UINT32_MAX
@@ -49,10 +54,12 @@ namespace {
 using GraphFn = void (*)(GraphSearchParams);
 struct GraphVariant {
 	int d;
-	bool compressed;
+	int mode;  // expann_graph_compression
 	GraphFn fn;
 };
-#define GRAPH_V(D) {D, false, graph_search_kernel<D, false>}, {D, true, graph_search_kernel<D, true>}
+#define GRAPH_V(D)                                                                                              \
+	{D, kGraphF32, graph_search_kernel<D, kGraphF32>}, {D, kGraphU8Cast, graph_search_kernel<D, kGraphU8Cast>}, \
+	{D, kGraphRangedQ8, graph_search_kernel<D, kGraphRangedQ8>}
 const GraphVariant kGraph[] = {GRAPH_V(64),  GRAPH_V(128), GRAPH_V(256), GRAPH_V(512),
                                GRAPH_V(768), GRAPH_V(832), GRAPH_V(960), GRAPH_V(0)};
 #undef GRAPH_V
@@ -67,10 +74,10 @@ void launch_quantize_simple_u8(const float* in, size_t n_values, uint8_t* out, h
 	}
 }
 // the compiled instance of `dim`, else the run-time-dim one (d = 0)
-const GraphVariant* graph_variant(int dim, bool compressed) {
+const GraphVariant* graph_variant(int dim, int mode) {
 	const GraphVariant* any = nullptr;
 	for (const auto& v : kGraph)
-		if (v.compressed == compressed) {
+		if (v.mode == mode) {
 			if (v.d == dim)
 				return &v;
 			if (v.d == 0)
@@ -92,7 +99,63 @@ int graph_dim_error(const char* fn, int dim) {
 	return EXPANN_OK;
 }
 // the instrumented instance (EXPANN_GRAPH_STAMPS=1, d = 128): per-phase shader clocks of a hop
-const GraphVariant kGraphDbg[] = {{128, false, graph_search_kernel<128, false, 1>}, {128, true, graph_search_kernel<128, true, 1>}};
+const GraphVariant kGraphDbg[] = {{128, kGraphF32, graph_search_kernel<128, kGraphF32, 1>},
+                                  {128, kGraphU8Cast, graph_search_kernel<128, kGraphU8Cast, 1>},
+                                  {128, kGraphRangedQ8, graph_search_kernel<128, kGraphRangedQ8, 1>}};
+const char* const kGraphModeName[] = {"f32", "u8", "q8"};
+
+// min / max of n_values floats, then their quantizer_ranged_q8 bytes and scale_factor / offset (quantize.hpp);
+// d_minmax[2] is scratch.  Launches of at most 2^30 values, as launch_quantize_simple_u8.
+hipError_t launch_quantize_ranged_q8(const float* in, size_t n_values, uint32_t* d_minmax, int8_t* out,
+                                     float* d_scale_offset, hipStream_t st) {
+	// min starts at FLT_MAX, max at FLT_MIN (smallest positive normal): src/quantizer.h:217-218
+	const uint32_t init[2] = {float_to_ordered(3.402823466e+38f), float_to_ordered(1.175494351e-38f)};
+	hipError_t e = hipMemcpyAsync(d_minmax, init, sizeof(init), hipMemcpyHostToDevice, st);
+	if (e == hipSuccess) e = hipStreamSynchronize(st);  // `init` is a stack buffer
+	if (e != hipSuccess)
+		return e;
+	const uint32_t blocks = (uint32_t)std::min<size_t>((n_values + kBlock - 1) / kBlock, 4096);
+	hipLaunchKernelGGL(minmax_f32_kernel, dim3(blocks), dim3(kBlock), 0, st, in, n_values, d_minmax);
+	const size_t chunk = size_t(1) << 30;
+	for (size_t off = 0; off < n_values; off += chunk) {
+		const size_t nv = std::min(chunk, n_values - off);
+		hipLaunchKernelGGL(quantize_ranged_q8_kernel, dim3((uint32_t)((nv + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+		                   in + off, nv, (const uint32_t*)d_minmax, out + off, d_scale_offset);
+	}
+	e = hipGetLastError();
+	if (e == hipSuccess) e = hipStreamSynchronize(st);
+	return e;
+}
+
+// the ranged mode's copy of the rows and its quantiser, made at first use (EXPANN_OK, or the error on g)
+int graph_ensure_ranged(expann_graph* g) {
+	const char* unusable = "the ranged quantiser is unusable on these rows: scale_factor is not finite and positive "
+	                       "(all components equal?)";
+	if (g->ranged_state < 0)
+		return g->fail(EXPANN_ERR_INVALID_ARG, unusable);
+	if (g->ranged_state > 0)
+		return EXPANN_OK;
+	HIP_TRY(g, hipSetDevice(g->device));
+	const size_t nv = g->n * (size_t)g->dim;
+	DevBuf b_mm, b_so, b_rows;
+	HIP_TRY(g, b_mm.alloc(2 * sizeof(uint32_t)));
+	HIP_TRY(g, b_so.alloc(2 * sizeof(float)));
+	HIP_TRY(g, b_rows.alloc(nv));
+	HIP_TRY(g, launch_quantize_ranged_q8(g->d_vectors, nv, b_mm.as<uint32_t>(), b_rows.as<int8_t>(), b_so.as<float>(),
+	                                     g->stream));
+	float so[2] = {0, 0};
+	HIP_TRY(g, hipMemcpy(so, b_so.p, sizeof(so), hipMemcpyDeviceToHost));
+	if (!std::isfinite(so[0]) || !(so[0] > 0.0f) || !std::isfinite(so[1])) {
+		g->ranged_state = -1;  // (the copy is dropped with b_rows)
+		return g->fail(EXPANN_ERR_INVALID_ARG, unusable);
+	}
+	g->d_ranged = b_rows.as<uint8_t>();
+	b_rows.p = nullptr;
+	g->ranged_scale = so[0];
+	g->ranged_offset = so[1];
+	g->ranged_state = 1;
+	return EXPANN_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -219,6 +282,7 @@ void expann_graph_destroy(expann_graph* g) {
 	if (g->stream) hipStreamSynchronize(g->stream);
 	if (g->d_vectors) hipFree(g->d_vectors);
 	if (g->d_compressed) hipFree(g->d_compressed);
+	if (g->d_ranged) hipFree(g->d_ranged);
 	if (g->d_layer_off) hipFree(g->d_layer_off);
 	if (g->d_neighbours) hipFree(g->d_neighbours);
 	if (g->d_adj0) hipFree(g->d_adj0);
@@ -240,8 +304,31 @@ double expann_graph_last_kernel_ms(const expann_graph* g) { return g ? g->last_m
 int expann_graph_search(expann_graph* g, const float* queries, size_t m, size_t k,
                         size_t ef_search, int use_compression, uint64_t* ids, float* dists,
                         uint32_t* distcomps) {
+	return expann_graph_search_mode(g, queries, m, k, ef_search, use_compression ? EXPANN_GRAPH_U8_CAST : EXPANN_GRAPH_FP32,
+	                                ids, dists, distcomps);
+}
+
+int expann_graph_ranged_params(expann_graph* g, float* scale_factor, float* offset) {
 	if (!g)
 		return EXPANN_ERR_INVALID_ARG;
+	if (!scale_factor || !offset)
+		return g->fail(EXPANN_ERR_INVALID_ARG, "NULL pointer");
+	if (g->dim % 64 != 0)
+		return g->fail(EXPANN_ERR_UNSUPPORTED, "the ranged int8 walk needs dim % 64 == 0");
+	if (int rc = graph_ensure_ranged(g))
+		return rc;
+	*scale_factor = g->ranged_scale;
+	*offset = g->ranged_offset;
+	return EXPANN_OK;
+}
+
+int expann_graph_search_mode(expann_graph* g, const float* queries, size_t m, size_t k, size_t ef_search, int mode,
+                             uint64_t* ids, float* dists, uint32_t* distcomps) {
+	if (!g)
+		return EXPANN_ERR_INVALID_ARG;
+	if (mode < EXPANN_GRAPH_FP32 || mode > EXPANN_GRAPH_RANGED_Q8)
+		return g->fail(EXPANN_ERR_INVALID_ARG, "mode must be 0 (fp32), 1 (uint8 cast) or 2 (ranged int8)");
+	const int use_compression = mode != EXPANN_GRAPH_FP32;
 	if (k == 0 || ef_search == 0)
 		return g->fail(EXPANN_ERR_INVALID_ARG, "k == 0 or ef_search == 0");
 	if (m == 0)
@@ -251,16 +338,21 @@ int expann_graph_search(expann_graph* g, const float* queries, size_t m, size_t 
 	if (ef_search > 4096)
 		return g->fail(EXPANN_ERR_UNSUPPORTED, "ef_search > 4096");
 	if (use_compression && g->dim % 64 != 0)  // (the reference's dist2_compressed works in 64-dim blocks)
-		return g->fail(EXPANN_ERR_UNSUPPORTED, "the uint8 walk (use_compression) needs dim % 64 == 0");
+		return g->fail(EXPANN_ERR_UNSUPPORTED, mode == EXPANN_GRAPH_RANGED_Q8
+		                                           ? "the ranged int8 walk needs dim % 64 == 0"
+		                                           : "the uint8 walk (use_compression) needs dim % 64 == 0");
 	HIP_TRY(g, hipSetDevice(g->device));
-	const GraphVariant* gv = graph_variant(g->dim, use_compression != 0);
+	const GraphVariant* gv = graph_variant(g->dim, mode);
 	if (!gv)
 		return g->fail(EXPANN_ERR_UNSUPPORTED, "no graph kernel for this dim");
 	const bool stamps = std::getenv("EXPANN_GRAPH_STAMPS") != nullptr && g->dim == 128;
 	if (stamps)
-		gv = &kGraphDbg[use_compression ? 1 : 0];
+		gv = &kGraphDbg[mode];
 	DevBuf b_stamps;
-	if (use_compression && !g->d_compressed) {  // quantizer_simple<uint8_t>::build, :485-486
+	if (mode == EXPANN_GRAPH_RANGED_Q8) {  // quantizer_ranged_q8::build, src/quantizer.h:213-232
+		if (int rc = graph_ensure_ranged(g))
+			return rc;
+	} else if (use_compression && !g->d_compressed) {  // quantizer_simple<uint8_t>::build, :485-486
 		HIP_TRY(g, hipMalloc(&g->d_compressed, g->n * (size_t)g->dim));
 		const size_t nv = g->n * (size_t)g->dim;
 		launch_quantize_simple_u8(g->d_vectors, nv, g->d_compressed, g->stream);
@@ -285,7 +377,9 @@ int expann_graph_search(expann_graph* g, const float* queries, size_t m, size_t 
 	for (;;) {  // until no candidates heap overflows, or its LDS capacity limit (8192) is reached
 		GraphSearchParams p{};
 		p.vectors = g->d_vectors;
-		p.compressed = g->d_compressed;
+		p.compressed = mode == EXPANN_GRAPH_RANGED_Q8 ? g->d_ranged : g->d_compressed;
+		p.q_scale = g->ranged_scale;
+		p.q_offset = g->ranged_offset;
 		p.layer_off = g->d_layer_off;
 		p.neighbours = g->d_neighbours;
 		p.adj0 = g->d_adj0;
@@ -355,7 +449,7 @@ int expann_graph_search(expann_graph* g, const float* queries, size_t m, size_t 
 			             "shader clocks per hop: pop + broadcast %.0f, adjacency + visited %.0f, gathers + scoring %.0f, "
 			             "serial queue update %.0f; per query: setup + descent %.0f, output %.0f; shares %.1f / %.1f / %.1f / "
 			             "%.1f / %.1f / %.1f %%\n",
-			             g->dim, use_compression ? "u8" : "f32", ef_search, ms, grid, tot[6] / (double)m, tot[7] / hops,
+			             g->dim, kGraphModeName[mode], ef_search, ms, grid, tot[6] / (double)m, tot[7] / hops,
 			             tot[1] / hops, tot[2] / hops, tot[3] / hops, tot[4] / hops, tot[0] / (double)m, tot[5] / (double)m,
 			             100 * tot[1] / all, 100 * tot[2] / all, 100 * tot[3] / all, 100 * tot[4] / all, 100 * tot[0] / all,
 			             100 * tot[5] / all);
@@ -790,6 +884,17 @@ int expann_antitopo_load(expann_antitopo* e, const char* index_path) {
 	return EXPANN_OK;
 }
 
+int expann_antitopo_set_compression(expann_antitopo* e, int mode) {
+	if (!e)
+		return EXPANN_ERR_INVALID_ARG;
+	if (mode < EXPANN_GRAPH_FP32 || mode > EXPANN_GRAPH_RANGED_Q8)
+		return e->fail(EXPANN_ERR_INVALID_ARG, "mode must be 0 (fp32), 1 (uint8 cast) or 2 (ranged int8)");
+	if (mode != EXPANN_GRAPH_FP32 && e->dim % 64 != 0)  // (both byte walks work in 64-dim blocks)
+		return e->fail(EXPANN_ERR_INVALID_ARG, "a compressed bottom layer needs dim % 64 == 0");
+	e->eng->conf.compression_mode = mode;
+	return EXPANN_OK;
+}
+
 size_t expann_antitopo_size(const expann_antitopo* e) { return e ? e->eng->index.size() : 0; }
 uint64_t expann_antitopo_num_distcomps(const expann_antitopo* e) {
 	return e ? e->eng->num_distcomps : 0;
@@ -831,19 +936,7 @@ int expann_quantize_ranged_q8_device(int device, const float* d_rows, size_t n_v
 		g_create_error = "hipMalloc failed";
 		return EXPANN_ERR_HIP;
 	}
-	// min starts at FLT_MAX, max at FLT_MIN (smallest positive normal): src/quantizer.h:217-218
-	const uint32_t init[2] = {float_to_ordered(3.402823466e+38f), float_to_ordered(1.175494351e-38f)};
-	hipError_t e = hipMemcpyAsync(d_mm, init, sizeof(init), hipMemcpyHostToDevice, st);
-	if (e == hipSuccess) e = hipStreamSynchronize(st);  // `init` is a stack buffer
-	if (e == hipSuccess) {
-		const uint32_t blocks = (uint32_t)std::min<size_t>((n_values + kBlock - 1) / kBlock, 4096);
-		hipLaunchKernelGGL(minmax_f32_kernel, dim3(blocks), dim3(kBlock), 0, st, d_rows, n_values, d_mm);
-		hipLaunchKernelGGL(quantize_ranged_q8_kernel, dim3((uint32_t)((n_values + kBlock - 1) / kBlock)),
-		                   dim3(kBlock), 0, st, d_rows, n_values, (const uint32_t*)d_mm, d_out,
-		                   d_scale_offset);
-		e = hipGetLastError();
-		if (e == hipSuccess) e = hipStreamSynchronize(st);
-	}
+	const hipError_t e = launch_quantize_ranged_q8(d_rows, n_values, d_mm, d_out, d_scale_offset, st);
 	hipFree(d_mm);
 	if (e != hipSuccess) {
 		g_create_error = std::string("expann_quantize_ranged_q8_device: ") + hipGetErrorString(e);

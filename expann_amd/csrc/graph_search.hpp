@@ -3,6 +3,8 @@
 //   query_k_at_layer<true,false,false>   src/antitopo_engine.h:495-708   (fp32 bottom layer)
 //   query_k_bottom_compressed            src/antitopo_engine.h:710-851   (uint8 bottom layer +
 //                                        final fp32 re-score :845-848)
+// and the same compressed walk over quantizer_ranged_q8 rows (src/quantizer.h:152-238, never instantiated by
+// the reference): MODE kGraphRangedQ8, bytes in [0, 127] from the index's global scale / offset.
 // One wavefront (= one 64-thread workgroup) walks one query; workgroups are persistent and pull
 // queries round-robin.  The traversal is a dependent chain, so the parallelism inside a query is
 // the neighbour batch of a hop: the "visited" tests of a vertex's <= M0 neighbours run one lane
@@ -29,13 +31,19 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "quantize.hpp"
 #include "scan_int8.hpp"
 
 namespace expann {
 
+// bottom-layer scoring of the walk (expann_graph_compression): fp32 rows; quantizer_simple<uint8_t> bytes
+// (a plain cast); quantizer_ranged_q8 bytes (global affine, [0, 127]).  The last two share everything
+// but the conversion of the query.
+constexpr int kGraphF32 = 0, kGraphU8Cast = 1, kGraphRangedQ8 = 2;
+
 struct GraphSearchParams {
 	const float* vectors;         // [n][D]
-	const uint8_t* compressed;    // [n][D] (quantizer_simple<uint8_t>) or nullptr
+	const uint8_t* compressed;    // [n][D] (quantizer_simple<uint8_t>, or quantizer_ranged_q8 in the ranged mode) or nullptr
 	const uint32_t* layer_off;    // [n_layers][n+1] (CSR; the walk uses it for the layers above 0)
 	const uint32_t* neighbours;
 	const uint32_t* adj0;         // [n][stride0] layer-0 lists at a fixed stride, padded with UINT32_MAX: a
@@ -66,6 +74,7 @@ struct GraphSearchParams {
 	// 3 row gathers + scoring, 4 serial queue update, 5 output}, 6 = hops, 7 = queue insertions
 	unsigned long long* stamps;
 	uint32_t dim;                 // run-time-dim instance (D = 0) only: the row length (the others have it as D)
+	float q_scale, q_offset;      // kGraphRangedQ8 only: the rows' quantiser, applied to the query as it is staged
 };
 
 struct md_pair {
@@ -473,16 +482,23 @@ __device__ inline void dist_u8_rows_any(const uint8_t* compressed, uint32_t dim,
 }
 
 // row `row` of `src` (fp32, dim floats) -> qs; for the uint8 walk also its truncated bytes -> q8s
-// (packed as the rows are) and their sum of squares.  Called by the whole wave; ends with the LDS in place.
-__device__ inline int stage_query_any(const float* src, uint32_t dim, float* qs, int* q8s, bool bytes, int lane) {
+// (packed as the rows are) and their sum of squares; RANGED: the bytes are the rows' affine conversion
+// (ranged_q8_convert with the index's scale / offset) instead.  Called by the whole wave; ends with the LDS in place.
+template <bool RANGED = false>
+__device__ inline int stage_query_any(const float* src, uint32_t dim, float* qs, int* q8s, bool bytes, int lane,
+                                      float scale = 0.0f, float offset = 0.0f) {
 	for (uint32_t i = lane; i < dim; i += 64)
 		qs[i] = src[i];
 	if (bytes)
 		for (uint32_t w = lane; w < dim / 4; w += 64) {
 			unsigned packed = 0;
 #pragma unroll
-			for (int b = 0; b < 4; ++b)
-				packed |= ((unsigned)(uint8_t)(uint32_t)src[4 * w + b]) << (8 * b);
+			for (int b = 0; b < 4; ++b) {
+				if constexpr (RANGED)
+					packed |= (unsigned)ranged_q8_convert(src[4 * w + b], scale, offset) << (8 * b);
+				else
+					packed |= ((unsigned)(uint8_t)(uint32_t)src[4 * w + b]) << (8 * b);
+			}
 			q8s[w] = (int)packed;
 		}
 	wave_lds_sync();
@@ -501,8 +517,11 @@ template <int D> constexpr int graph_rows_u8() { return D == 0 ? kGraphAnyRows :
 
 // (the uint8 walk waits on latency, not bandwidth: 128 registers = 16 waves per CU instead of 12)
 // D = 0: the run-time-dim instance (p.dim); the query and its bytes sit in LDS behind ndist
-template <int D, bool COMPRESSED, int DBG = 0>
-__global__ __launch_bounds__(64, D == 0 ? 3 : ((COMPRESSED && D <= 128) ? 4 : 1)) void graph_search_kernel(GraphSearchParams p) {
+// MODE: kGraphF32 / kGraphU8Cast / kGraphRangedQ8; the two byte modes are one walk (COMPRESSED), the ranged
+// one differs where the query's bytes are made
+template <int D, int MODE, int DBG = 0>
+__global__ __launch_bounds__(64, D == 0 ? 3 : ((MODE != kGraphF32 && D <= 128) ? 4 : 1)) void graph_search_kernel(GraphSearchParams p) {
+	constexpr bool COMPRESSED = MODE != kGraphF32, RANGED = MODE == kGraphRangedQ8;
 	constexpr int DPL = D ? D / 16 : 1;
 	constexpr int NW = D ? D / 64 : 1;
 	unsigned long long seg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ts = DBG ? clock64() : 0;
@@ -558,7 +577,10 @@ __global__ __launch_bounds__(64, D == 0 ? 3 : ((COMPRESSED && D <= 128) ? 4 : 1)
 		int q8[NW];  // trunc(query) bytes of this lane (compressed path)
 		int q8self = 0;
 		if constexpr (D == 0) {
-			q8self = stage_query_any(p.queries + (size_t)qi * p.dim, p.dim, qs, q8s, COMPRESSED, lane);
+			if constexpr (RANGED)
+				q8self = stage_query_any<true>(p.queries + (size_t)qi * p.dim, p.dim, qs, q8s, true, lane, p.q_scale, p.q_offset);
+			else
+				q8self = stage_query_any(p.queries + (size_t)qi * p.dim, p.dim, qs, q8s, COMPRESSED, lane);
 		} else {
 #pragma unroll
 			for (int t = 0; t < DPL; ++t)
@@ -570,7 +592,10 @@ __global__ __launch_bounds__(64, D == 0 ? 3 : ((COMPRESSED && D <= 128) ? 4 : 1)
 #pragma unroll
 					for (int b = 0; b < 4; ++b) {
 						const float v = p.queries[(size_t)qi * D + l * (D / 16) + 4 * w + b];
-						packed |= ((unsigned)(uint8_t)(uint32_t)v) << (8 * b);
+						if constexpr (RANGED)
+							packed |= (unsigned)ranged_q8_convert(v, p.q_scale, p.q_offset) << (8 * b);
+						else
+							packed |= ((unsigned)(uint8_t)(uint32_t)v) << (8 * b);
 					}
 					q8[w] = (int)packed;
 					q8self = dot4<kU8L2>(q8[w], q8[w], q8self);

@@ -38,6 +38,17 @@ __global__ __launch_bounds__(kBlock) void minmax_f32_kernel(const float* in, siz
 	}
 }
 
+// convert_single (src/quantizer.h:196-200) with a given scale / offset: the one convert of the rows
+// (quantize_ranged_q8_kernel) and of the queries of the ranged walk (graph_search.hpp), so the two sides
+// cannot drift apart.  scale*x + offset as a separate multiply and add (no FMA contraction), then
+// std::round; the reference converts through size_t (negative -> UB): negatives -- and NaN -- clamp to
+// q_min = 0, values above q_max to 127.
+__device__ inline int ranged_q8_convert(float x, float scale, float offset) {
+	const float r = roundf(__fadd_rn(__fmul_rn(scale, x), offset));
+	const float c = r > 0.0f ? (r >= 127.0f ? 127.0f : r) : 0.0f;
+	return (int)c;
+}
+
 __global__ __launch_bounds__(kBlock) void quantize_ranged_q8_kernel(const float* in, size_t n_values,
                                                                     const uint32_t* minmax,
                                                                     int8_t* out, float* scale_offset) {
@@ -52,11 +63,7 @@ __global__ __launch_bounds__(kBlock) void quantize_ranged_q8_kernel(const float*
 	}
 	if (i >= n_values)
 		return;
-	// scale*x + offset as a separate multiply and add (no FMA contraction), then std::round
-	const float r = roundf(__fadd_rn(__fmul_rn(scale, in[i]), offset));
-	// the reference converts through size_t (negative -> UB); negatives clamp to q_min = 0
-	const float c = r <= 0.0f ? 0.0f : (r >= 127.0f ? 127.0f : r);
-	out[i] = (int8_t)(int)c;
+	out[i] = (int8_t)ranged_q8_convert(in[i], scale, offset);
 }
 
 }  // namespace expann

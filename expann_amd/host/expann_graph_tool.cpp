@@ -6,9 +6,13 @@
 //   expann_graph_tool --n 5000 --m 200 --d 128 --k 10 --M 16 --ef_construction 100 \
 //       --data sift|gauss --index out.index --queries out.queries --results out.results \
 //       [--ef 10,20,40] [--build-only 1] [--read-index 1] [--prune_overflow 0|1] [--batched 2048]
+//       [--compression none|cast|ranged|all] [--clip 255]
 //
-// Files: <queries> raw m*d float32; <results> for each (compression in {0,1}; 0 only when d % 64 != 0,
-// the uint8 walk works in 64-dim blocks) x (ef in list):
+// --compression: the bottom-layer modes to run -- none = fp32, cast = the uint8 cast, ranged = the affine
+// int8 quantiser (expann_graph_compression 0 / 1 / 2), all = the three; without it fp32 and cast.
+// --clip: the largest value of the SIFT-like rows (127: rows every mode can represent).
+// Files: <queries> raw m*d float32; <results> for each (compression mode of the run; fp32 only when
+// d % 64 != 0, the byte walks work in 64-dim blocks) x (ef in list):
 // m*k uint64 ids, m*k float32 dists, m uint32 distcomps, in that order.  One JSON line per
 // configuration on stdout (time per query, distance evaluations), like the reference's
 // bench_data + RECORD_STATS (src/bench_data.h:20-28, src/antitopo_engine.h:254-257).
@@ -38,6 +42,7 @@ int main(int argc, char** argv) {
 	// --batched S: rows beyond the first S go through the batched GPU builder (0 = serial host build)
 	const size_t batched = std::stoul(get("batched", "0"));
 	const bool sift = get("data", "sift") == "sift";
+	const double clip = std::stod(get("clip", "255"));
 	const bool build_only = get("build-only", "0") == "1", read_index = get("read-index", "0") == "1";
 	const std::string index_path = get("index", "graph.index");
 
@@ -48,7 +53,7 @@ int main(int argc, char** argv) {
 		if (!sift)
 			return float(x);
 		double v = std::round(std::fabs(x) * 40.0);  // SIFT-like stand-in
-		return float(v < 0 ? 0 : (v > 255 ? 255 : v));
+		return float(v < 0 ? 0 : (v > clip ? clip : v));
 	};
 	std::vector<float> base(n * d), queries(m * d);
 	for (auto& x : base) x = draw();
@@ -56,7 +61,7 @@ int main(int argc, char** argv) {
 	for (auto& x : queries) {
 		x = draw();
 		if (sift)  // fractional parts: the uint8 path truncates the query (antitopo_engine.h:726-737)
-			x = std::min(255.5f, x + float(frac(gen)));
+			x = std::min(float(clip) + 0.5f, x + float(frac(gen)));
 	}
 
 	try {
@@ -130,9 +135,20 @@ int main(int argc, char** argv) {
 		std::ofstream rf;
 		if (a.count("results"))
 			rf.open(a["results"], std::ios::binary);
-		for (int comp = 0; comp <= (d % 64 == 0 ? 1 : 0); ++comp)
+		std::vector<int> modes = {EXPANN_GRAPH_FP32, EXPANN_GRAPH_U8_CAST};
+		if (a.count("compression")) {
+			const std::string c = a["compression"];
+			if (c == "none") modes = {EXPANN_GRAPH_FP32};
+			else if (c == "cast") modes = {EXPANN_GRAPH_U8_CAST};
+			else if (c == "ranged") modes = {EXPANN_GRAPH_RANGED_Q8};
+			else if (c == "all") modes = {EXPANN_GRAPH_FP32, EXPANN_GRAPH_U8_CAST, EXPANN_GRAPH_RANGED_Q8};
+			else throw std::runtime_error("--compression must be none, cast, ranged or all");
+		}
+		for (int comp : modes)
 			for (size_t ef : efs) {
-				eng.conf.use_compression = comp != 0;
+				if (comp != EXPANN_GRAPH_FP32 && d % 64 != 0)
+					continue;
+				eng.conf.compression_mode = comp;
 				eng.set_ef_search(ef);
 				std::vector<uint64_t> ids(m * k);
 				std::vector<float> dists(m * k);

@@ -7,9 +7,15 @@ The reference compiles one module per dimension (expann_py_64/128/256/832/960,
 CMakeLists.txt:102-153) and zero-pads every row to that DIM (src/pyrunner.cpp:20-27); here the
 dimension is a constructor argument (default: from the first rows -- up to 960 the smallest dim
 with a compiled graph kernel that holds them, from 961 to 4096 the next multiple of 64, so that
-both compression modes work) and rows are zero-padded the same way.  Wider rows raise ValueError.  take_norms = L2-normalise each row before
+every compression mode works) and rows are zero-padded the same way.  Wider rows raise ValueError.  take_norms = L2-normalise each row before
 storing (angular data = normalise + L2, src/pyrunner.cpp:78-79); the normalisation itself is
 Eigen's in the reference (summation order unpinned) and numpy float32 here.
+
+`use_compression` also takes "ranged" (and `set_compression("none" | "cast" | "ranged")` switches a live
+engine): the bottom layer walks an int8 copy of the rows made by one global affine quantiser (the
+reference's quantizer_ranged_q8, src/quantizer.h:152-238, which it never runs), so rows that are not
+integers in [0, 255] -- Gaussian, embeddings, take_norms=True -- get a compressed walk too.  True / False
+keep the reference's meaning (the uint8 cast / fp32).
 """
 import ctypes as C
 
@@ -19,14 +25,28 @@ from . import _lib
 
 _SUPPORTED_DIMS = (64, 128, 256, 512, 768, 832, 960)  # dims with compiled graph kernels
 _MAX_DIM = 4096  # the graph path's limit (run-time-dim kernels above 960)
+_COMPRESSION_MODES = {"none": _lib.GRAPH_FP32, "cast": _lib.GRAPH_U8_CAST, "ranged": _lib.GRAPH_RANGED_Q8}
+
+
+def _compression_mode(value):
+    """expann_graph_compression of a use_compression / set_compression argument"""
+    if isinstance(value, str):
+        if value not in _COMPRESSION_MODES:
+            raise ValueError(f"compression must be one of {sorted(_COMPRESSION_MODES)}, not {value!r}")
+        return _COMPRESSION_MODES[value]
+    return _lib.GRAPH_U8_CAST if value else _lib.GRAPH_FP32
 
 
 class AntitopoEngine:
     def __init__(self, M, ef_construction, ortho_count, prune_overflow, use_compression, dim=None,
                  device=0):
+        self._mode = _compression_mode(use_compression)
+        if self._mode == _lib.GRAPH_RANGED_Q8 and dim is not None and int(dim) % 64 != 0:
+            raise ValueError(f"the ranged walk needs a dimension that is a multiple of 64, not {dim}")
         self._L = _lib.load()
+        # (the handle is created with the reference's flag: "ranged" is a run-time mode set on top of it)
         self._args = (int(M), int(ef_construction), int(ortho_count), int(prune_overflow),
-                      bool(use_compression))
+                      self._mode == _lib.GRAPH_U8_CAST)
         self.device = int(device)
         self.dim = None
         self._h = None
@@ -45,6 +65,8 @@ class AntitopoEngine:
         if rc != _lib.OK:
             raise _lib.ExpannError(rc, self._L.expann_antitopo_last_error(None).decode())
         self._h, self.dim = h, padded
+        if self._mode != int(uc):
+            self._check(self._L.expann_antitopo_set_compression(h, self._mode))
 
     def _check(self, rc):
         if rc != _lib.OK:
@@ -72,9 +94,12 @@ class AntitopoEngine:
 
     def param_list(self):
         M, efc, oc, po, uc = self._args
-        return {"M": str(M), "M0": str(2 * M), "ef_construction": str(efc), "ortho_count": str(oc),
-                "prune_overflow": str(po), "use_compression": str(int(uc)),
-                "num_distcomps": str(self._L.expann_antitopo_num_distcomps(self._h) if self._h else 0)}
+        pl = {"M": str(M), "M0": str(2 * M), "ef_construction": str(efc), "ortho_count": str(oc),
+              "prune_overflow": str(po), "use_compression": str(int(self._mode != _lib.GRAPH_FP32)),
+              "num_distcomps": str(self._L.expann_antitopo_num_distcomps(self._h) if self._h else 0)}
+        if self._mode == _lib.GRAPH_RANGED_Q8:
+            pl["compression_mode"] = "ranged"
+        return pl
 
     def store_vector(self, v):
         self.store_many_vectors(np.asarray(v, dtype=np.float32).reshape(1, -1), False)
@@ -112,6 +137,16 @@ class AntitopoEngine:
         self._check(self._L.expann_antitopo_set_ef_search(self._h, int(ef_search)))
 
     # ---- extensions ------------------------------------------------------------------
+    def set_compression(self, mode):
+        """Bottom-layer scoring of the queries from now on: "none" (fp32), "cast" (the reference's uint8
+        cast) or "ranged" (the affine int8 quantiser).  The index and its file do not change."""
+        if not isinstance(mode, str):
+            raise ValueError('compression must be "none", "cast" or "ranged"')
+        m = _compression_mode(mode)
+        if self._h is not None:
+            self._check(self._L.expann_antitopo_set_compression(self._h, m))
+        self._mode = m
+
     def query_many(self, queries, k):
         q = self._pad(queries)
         ids = np.empty((q.shape[0], k), dtype=np.uint64)

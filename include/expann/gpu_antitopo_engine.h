@@ -24,6 +24,10 @@ struct gpu_antitopo_engine_config : public expann::antitopo_config {
 	int device = 0;
 	std::string index_filename;
 	bool read_index = false, write_index = false;
+	// bottom-layer scoring of the walk (expann_graph_compression); -1: what use_compression says (0 or 1).
+	// 2 = the ranged int8 walk, which the reference has no switch for.
+	int compression_mode = -1;
+	int mode() const { return compression_mode < 0 ? (use_compression ? 1 : 0) : compression_mode; }
 	gpu_antitopo_engine_config() = default;
 	// same argument order as antitopo_engine_config (src/antitopo_engine.h:88-101)
 	gpu_antitopo_engine_config(size_t _M, size_t _M0, size_t _ef_search_mult, size_t _ef_construction,
@@ -150,8 +154,8 @@ struct gpu_antitopo_engine : public ann_engine<T, gpu_antitopo_engine<T>> {
 		if (!ef_search.has_value())
 			set_ef_search(k * conf.ef_search_mult);  // :858-859
 		std::vector<uint32_t> dc(m);
-		int rc = expann_graph_search(graph, queries, m, k, ef_search.value(),
-		                             conf.use_compression ? 1 : 0, ids, dists, dc.data());
+		int rc = expann_graph_search_mode(graph, queries, m, k, ef_search.value(), conf.mode(), ids, dists,
+		                                  dc.data());
 		if (rc != EXPANN_OK)
 			throw std::runtime_error(std::string("expann_graph_search: ") +
 			                         expann_graph_last_error(graph));
@@ -172,7 +176,9 @@ struct gpu_antitopo_engine : public ann_engine<T, gpu_antitopo_engine<T>> {
 		pl["ortho_factor"] = std::to_string(conf.ortho_factor);
 		pl["ortho_bias"] = std::to_string(conf.ortho_bias);
 		pl["prune_overflow"] = std::to_string(conf.prune_overflow);
-		pl["use_compression"] = std::to_string(conf.use_compression);
+		pl["use_compression"] = std::to_string(conf.mode() != EXPANN_GRAPH_FP32);
+		if (conf.mode() == EXPANN_GRAPH_RANGED_Q8)
+			pl["compression_mode"] = "ranged";
 		pl["use_largest_direction_filtering"] = std::to_string(conf.use_largest_direction_filtering);
 		pl["num_distcomps"] = std::to_string(num_distcomps);
 		return pl;

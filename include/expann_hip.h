@@ -258,6 +258,30 @@ int expann_graph_search(expann_graph* g, const float* queries, size_t m, size_t 
 /* device time of the last expann_graph_search's traversal kernel, milliseconds */
 double expann_graph_last_kernel_ms(const expann_graph* g);
 
+/* how the bottom layer of the walk scores a row */
+enum expann_graph_compression {
+	EXPANN_GRAPH_FP32 = 0,     /* fp32 rows (:495-708)                                                    */
+	EXPANN_GRAPH_U8_CAST = 1,  /* quantizer_simple<uint8_t> bytes, a plain cast: rows that already hold
+	                            * integers in [0, 255] (:710-851) -- what use_compression means            */
+	EXPANN_GRAPH_RANGED_Q8 = 2 /* quantizer_ranged_q8 bytes (src/quantizer.h:152-238, which the reference
+	                            * never instantiates): one global scale_factor / offset from the rows' min
+	                            * and max, bytes in [0, 127] -- any fp32 rows                             */
+};
+/* expann_graph_search with the bottom-layer scoring as a mode (expann_graph_search(..., use_compression, ...)
+ * is this call with use_compression ? 1 : 0).  Mode 2 is the uint8 walk in every respect -- fp32 entry
+ * evaluation and descent, exact integer sum (q8_i - r8_i)^2 on the bottom layer, same queues, stop rule and
+ * distcomps, results in the order of the integer distances, re-scored in fp32 on the original rows -- over an
+ * int8 copy of the rows made at the first use (n * dim bytes of device memory, next to the uint8 copy), with
+ * the queries converted by the same scale_factor / offset inside the walk kernel (components outside the
+ * rows' range clamp).  Errors, all before the device is touched: mode outside 0..2 EXPANN_ERR_INVALID_ARG;
+ * modes 1 and 2 need dim % 64 == 0 (EXPANN_ERR_UNSUPPORTED).  Mode 2 on rows whose scale_factor is not
+ * finite and positive (all components equal): EXPANN_ERR_INVALID_ARG, nothing is walked. */
+int expann_graph_search_mode(expann_graph* g, const float* queries, size_t m, size_t k, size_t ef_search,
+                             int mode, uint64_t* ids, float* dists, uint32_t* distcomps);
+/* scale_factor / offset of the handle's affine quantiser; builds the int8 copy if it does not exist yet
+ * (errors as mode 2 of expann_graph_search_mode) */
+int expann_graph_ranged_params(expann_graph* g, float* scale_factor, float* offset);
+
 /* GPU-assisted batched construction of the graph (csrc/graph_build.hpp; replaces the inner loop of
  * antitopo_engine::_store_vector / prune_edges, src/antitopo_engine.h:263-465, for the vectors
  * [n_built, n) -- the first n_built come with their rows already built, by the serial host builder
@@ -301,6 +325,10 @@ int expann_antitopo_query(expann_antitopo* e, const float* queries, size_t m, si
                           uint64_t* ids, float* dists);
 int expann_antitopo_save(expann_antitopo* e, const char* index_path);  /* serialize, :932-991 */
 int expann_antitopo_load(expann_antitopo* e, const char* index_path);  /* deserialize + upload */
+/* mode (expann_graph_compression) of expann_antitopo_query's bottom layer; default: what use_compression at
+ * create says (0 or 1).  A run-time property: the index file does not record it.  A mode outside 0..2, or
+ * mode 1 / 2 on an engine whose dim is not a multiple of 64: EXPANN_ERR_INVALID_ARG (no device call). */
+int expann_antitopo_set_compression(expann_antitopo* e, int mode);
 size_t expann_antitopo_size(const expann_antitopo* e);
 uint64_t expann_antitopo_num_distcomps(const expann_antitopo* e);
 
