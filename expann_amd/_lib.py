@@ -36,6 +36,8 @@ ABI_SYMBOLS = [
     "expann_sharded_last_enqueue_ms", "expann_sharded_set_alltoallv_fn", "expann_sharded_search_devices",
     "expann_sharded_slice", "expann_device_heap_trace",
     "expann_graph_search_mode", "expann_graph_ranged_params", "expann_antitopo_set_compression",
+    "expann_graph_search_device", "expann_graph_sync", "expann_graph_set_option", "expann_graph_get_stat",
+    "expann_antitopo_query_device", "expann_antitopo_sync",
 ]
 
 
@@ -157,6 +159,19 @@ def load():
     L.expann_graph_search.argtypes = [vp, vp, sz, sz, sz, C.c_int, vp, vp, vp]
     L.expann_graph_search_mode.restype = C.c_int
     L.expann_graph_search_mode.argtypes = [vp, vp, sz, sz, sz, C.c_int, vp, vp, vp]
+    if hasattr(L, "expann_graph_search_device"):  # (EXPANN_LIB may name an older build for an A/B run)
+        L.expann_graph_search_device.restype = C.c_int
+        L.expann_graph_search_device.argtypes = [vp, vp, sz, sz, sz, C.c_int, vp, vp, vp, vp]
+        L.expann_graph_sync.restype = C.c_int
+        L.expann_graph_sync.argtypes = [vp]
+        L.expann_graph_set_option.restype = C.c_int
+        L.expann_graph_set_option.argtypes = [vp, C.c_char_p, C.c_long]
+        L.expann_graph_get_stat.restype = C.c_int
+        L.expann_graph_get_stat.argtypes = [vp, C.c_char_p, C.POINTER(C.c_uint64)]
+        L.expann_antitopo_query_device.restype = C.c_int
+        L.expann_antitopo_query_device.argtypes = [vp, vp, sz, sz, vp, vp, vp]
+        L.expann_antitopo_sync.restype = C.c_int
+        L.expann_antitopo_sync.argtypes = [vp]
     L.expann_graph_ranged_params.restype = C.c_int
     L.expann_graph_ranged_params.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.expann_antitopo_set_compression.restype = C.c_int

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -43,6 +44,31 @@ struct expann_graph {
 	hipStream_t stream = nullptr;
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
 	double last_ms = 0;
+	// ---- device-buffer searches (expann_graph_search_device / expann_graph_sync) ----
+	// One counter slot per outstanding search: {overflow flag, first launch's query counter, redo count, redo
+	// launch's query counter, 4 spare}; a search resets its slot in stream order, the sync reads them all.
+	DevPtr<uint32_t> d_dev_ctr;            // [kGraphMaxOutstanding][kGraphCtrWords]
+	PinPtr<uint32_t> h_dev_ctr;            // the same, read back by the sync
+	DevPtr<unsigned long long> d_dc_total; // [1] distcomps of every device search since create
+	PinPtr<unsigned long long> h_dc_total;
+	GrowPtr<uint32_t> d_redo_list;         // [largest m seen]
+	hipStream_t dev_stream = nullptr;      // the stream of the outstanding searches
+	uint32_t dev_outstanding = 0;          // searches enqueued since the last drain (= slots in use)
+	hipEvent_t ev_dev[3] = {nullptr, nullptr, nullptr};  // before the first launch, after it, after the redo launch
+	bool dev_timed = false, dev_timed_redo = false;       // ev_dev hold the last search (and its redo launch)
+	long opt_cand_cap = 0, opt_redo_cap = 0;
+	// what the drains since the last sync found, and the counters behind expann_graph_get_stat
+	uint64_t pend_redo_queries = 0, pend_overflows = 0;
+	uint64_t stat_redo_queries = 0, stat_redo_overflows = 0, stat_deferred = 0, stat_distcomps = 0;
+	double stat_redo_ms = 0;
+	// attribute, occupancy and grid of a launch, per (instance, LDS size)
+	struct LaunchPlan {
+		const void* fn;
+		size_t lds;
+		uint32_t resident;
+		uint64_t attr_gen;  // g_graph_attr_gen when this plan last set the instance's dynamic-LDS attribute
+	};
+	std::vector<LaunchPlan> plans;
 	mutable std::string err;
 	int fail(int code, const std::string& msg) const {
 		err = msg;
@@ -154,6 +180,147 @@ int graph_ensure_ranged(expann_graph* g) {
 	g->ranged_scale = so[0];
 	g->ranged_offset = so[1];
 	g->ranged_state = 1;
+	return EXPANN_OK;
+}
+
+constexpr size_t kGraphMaxLds = 160 * 1024;     // the working set a search may take of a CU's LDS
+constexpr uint32_t kGraphMaxOutstanding = 256;  // device-buffer searches between two drains
+constexpr uint32_t kGraphCtrWords = 8;          // counter words per outstanding search
+
+// Bumped whenever the host-buffer path sets an instance's dynamic-LDS attribute (to that call's size): the
+// device-buffer path, which caches its launch set-up, then sets the attribute again before its next launch.
+std::atomic<uint64_t> g_graph_attr_gen{1};
+
+// the argument checks of a search, in the order the header documents, all before the device is touched;
+// *empty: m == 0, nothing to do
+int graph_search_args(expann_graph* g, const void* queries, size_t m, size_t k, size_t ef_search, int mode,
+                      const void* ids, const void* dists, bool* empty) {
+	*empty = false;
+	if (mode < EXPANN_GRAPH_FP32 || mode > EXPANN_GRAPH_RANGED_Q8)
+		return g->fail(EXPANN_ERR_INVALID_ARG, "mode must be 0 (fp32), 1 (uint8 cast) or 2 (ranged int8)");
+	if (k == 0 || ef_search == 0)
+		return g->fail(EXPANN_ERR_INVALID_ARG, "k == 0 or ef_search == 0");
+	if (m == 0) {
+		*empty = true;
+		return EXPANN_OK;
+	}
+	if (!queries || !ids || !dists)
+		return g->fail(EXPANN_ERR_INVALID_ARG, "NULL pointer");
+	if (ef_search > 4096)
+		return g->fail(EXPANN_ERR_UNSUPPORTED, "ef_search > 4096");
+	if (mode != EXPANN_GRAPH_FP32 && g->dim % 64 != 0)  // (the reference's dist2_compressed works in 64-dim blocks)
+		return g->fail(EXPANN_ERR_UNSUPPORTED, mode == EXPANN_GRAPH_RANGED_Q8
+		                                           ? "the ranged int8 walk needs dim % 64 == 0"
+		                                           : "the uint8 walk (use_compression) needs dim % 64 == 0");
+	return EXPANN_OK;
+}
+
+// the heap capacity a search starts with
+uint32_t graph_first_cand_cap(size_t ef_search) {
+	uint32_t cand_cap = 256;
+	while (cand_cap < 16 * ef_search && cand_cap < 8192)
+		cand_cap *= 2;
+	return cand_cap;
+}
+
+// everything of a launch's parameters that the handle, the mode and (k, ef) decide; the caller adds the
+// queries, the outputs, cand_cap and the counters
+GraphSearchParams graph_base_params(const expann_graph* g, int mode, size_t k, size_t ef_search) {
+	GraphSearchParams p{};
+	p.vectors = g->d_vectors;
+	p.compressed = mode == EXPANN_GRAPH_RANGED_Q8 ? g->d_ranged : g->d_compressed;
+	p.q_scale = g->ranged_scale;
+	p.q_offset = g->ranged_offset;
+	p.layer_off = g->d_layer_off;
+	p.neighbours = g->d_neighbours;
+	p.adj0 = g->d_adj0;
+	p.stride0 = g->stride0;
+	p.n = (uint32_t)g->n;
+	p.n_layers = g->n_layers;
+	p.starting_vertex = g->starting_vertex;
+	p.k = (uint32_t)k;
+	p.ef = (uint32_t)ef_search;
+	p.max_degree = g->max_degree0;
+	p.list_cap = std::max<uint32_t>(std::max<uint32_t>(g->stride0, (uint32_t)ef_search), 4);
+	p.visited = g->d_visited;
+	p.vis_bits = reinterpret_cast<uint32_t*>(g->d_visited);
+	p.vis_words = g->vis_words;
+	p.epochs = g->d_epochs;
+	p.dim = (uint32_t)g->dim;
+	if (const char* e = std::getenv("EXPANN_GRAPH_DEBUG"))
+		p.debug = (uint32_t)std::atol(e);
+	return p;
+}
+
+// dynamic LDS of a launch: the two heaps, a hop's list, and -- run-time-dim instance -- the query (and its bytes)
+size_t graph_lds_bytes(const GraphSearchParams& p, uint32_t cand_cap, bool run_time_dim, bool use_compression) {
+	size_t lds = sizeof(md_pair) * ((size_t)p.ef + 1 + cand_cap + 1) + (sizeof(uint32_t) + sizeof(float)) * p.list_cap;
+	if (run_time_dim)
+		lds += (size_t)p.dim * (sizeof(float) + (use_compression ? 1 : 0));
+	return lds;
+}
+
+// host wait for the device-buffer searches still in flight (their counters stay where they are)
+hipError_t graph_wait_outstanding(expann_graph* g) {
+	return g->dev_outstanding ? hipStreamSynchronize(g->dev_stream) : hipSuccess;
+}
+
+// wait for the outstanding device-buffer searches and collect their counters for the next sync
+int graph_drain(expann_graph* g) {
+	if (!g->dev_outstanding)
+		return EXPANN_OK;
+	HIP_TRY(g, hipStreamSynchronize(g->dev_stream));
+	HIP_TRY(g, hipMemcpy(g->h_dev_ctr, g->d_dev_ctr, sizeof(uint32_t) * kGraphCtrWords * g->dev_outstanding,
+	                     hipMemcpyDeviceToHost));
+	HIP_TRY(g, hipMemcpy(g->h_dc_total, g->d_dc_total, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+	for (uint32_t s = 0; s < g->dev_outstanding; ++s) {
+		const uint32_t* c = g->h_dev_ctr + (size_t)s * kGraphCtrWords;
+		g->pend_overflows += c[0] != 0;
+		g->pend_redo_queries += c[2];
+	}
+	g->stat_distcomps = *g->h_dc_total;
+	g->dev_outstanding = 0;
+	return EXPANN_OK;
+}
+
+// counters, their pinned mirror and the events of the device-buffer path, made at its first search
+int graph_dev_init(expann_graph* g) {
+	if (g->d_dev_ctr)
+		return EXPANN_OK;
+	for (hipEvent_t& ev : g->ev_dev)
+		if (!ev)
+			HIP_TRY(g, hipEventCreate(&ev));
+	if (!g->h_dev_ctr)
+		HIP_TRY(g, hipHostMalloc((void**)&g->h_dev_ctr, sizeof(uint32_t) * kGraphCtrWords * kGraphMaxOutstanding));
+	if (!g->h_dc_total)
+		HIP_TRY(g, hipHostMalloc((void**)&g->h_dc_total, sizeof(unsigned long long)));
+	if (!g->d_dc_total) {
+		HIP_TRY(g, hipMalloc(&g->d_dc_total, sizeof(unsigned long long)));
+		HIP_TRY(g, hipMemset(g->d_dc_total, 0, sizeof(unsigned long long)));
+	}
+	HIP_TRY(g, hipMalloc(&g->d_dev_ctr, sizeof(uint32_t) * kGraphCtrWords * kGraphMaxOutstanding));
+	return EXPANN_OK;
+}
+
+// workgroups of `fn` resident at once with `lds` bytes each; the attribute and the occupancy query run once per
+// (instance, LDS size) and handle.  The attribute is set to the largest working set a search may have, so that
+// plans of one instance do not undo each other's.
+int graph_plan(expann_graph* g, const void* fn, size_t lds, uint32_t* resident) {
+	const uint64_t gen = g_graph_attr_gen.load(std::memory_order_relaxed);
+	for (auto& pl : g->plans)
+		if (pl.fn == fn && pl.lds == lds) {
+			if (pl.attr_gen != gen) {
+				HIP_TRY(g, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGraphMaxLds));
+				pl.attr_gen = gen;
+			}
+			*resident = pl.resident;
+			return EXPANN_OK;
+		}
+	HIP_TRY(g, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGraphMaxLds));
+	int per_cu = 0;
+	HIP_TRY(g, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, lds));
+	*resident = (uint32_t)std::max(1, per_cu) * (uint32_t)num_cus(g->device);
+	g->plans.push_back({fn, lds, *resident, gen});
 	return EXPANN_OK;
 }
 }  // namespace
@@ -280,6 +447,7 @@ void expann_graph_destroy(expann_graph* g) {
 		return;
 	hipSetDevice(g->device);
 	if (g->stream) hipStreamSynchronize(g->stream);
+	if (g->dev_outstanding) hipStreamSynchronize(g->dev_stream);
 	if (g->d_vectors) hipFree(g->d_vectors);
 	if (g->d_compressed) hipFree(g->d_compressed);
 	if (g->d_ranged) hipFree(g->d_ranged);
@@ -289,6 +457,8 @@ void expann_graph_destroy(expann_graph* g) {
 	if (g->d_visited) hipFree(g->d_visited);
 	if (g->d_epochs) hipFree(g->d_epochs);
 	if (g->d_error) hipFree(g->d_error);
+	for (hipEvent_t ev : g->ev_dev)
+		if (ev) hipEventDestroy(ev);
 	if (g->ev0) hipEventDestroy(g->ev0);
 	if (g->ev1) hipEventDestroy(g->ev1);
 	if (g->stream) hipStreamDestroy(g->stream);
@@ -326,22 +496,14 @@ int expann_graph_search_mode(expann_graph* g, const float* queries, size_t m, si
                              uint64_t* ids, float* dists, uint32_t* distcomps) {
 	if (!g)
 		return EXPANN_ERR_INVALID_ARG;
-	if (mode < EXPANN_GRAPH_FP32 || mode > EXPANN_GRAPH_RANGED_Q8)
-		return g->fail(EXPANN_ERR_INVALID_ARG, "mode must be 0 (fp32), 1 (uint8 cast) or 2 (ranged int8)");
-	const int use_compression = mode != EXPANN_GRAPH_FP32;
-	if (k == 0 || ef_search == 0)
-		return g->fail(EXPANN_ERR_INVALID_ARG, "k == 0 or ef_search == 0");
-	if (m == 0)
+	bool empty = false;
+	if (int rc = graph_search_args(g, queries, m, k, ef_search, mode, ids, dists, &empty))
+		return rc;
+	if (empty)
 		return EXPANN_OK;
-	if (!queries || !ids || !dists)
-		return g->fail(EXPANN_ERR_INVALID_ARG, "NULL pointer");
-	if (ef_search > 4096)
-		return g->fail(EXPANN_ERR_UNSUPPORTED, "ef_search > 4096");
-	if (use_compression && g->dim % 64 != 0)  // (the reference's dist2_compressed works in 64-dim blocks)
-		return g->fail(EXPANN_ERR_UNSUPPORTED, mode == EXPANN_GRAPH_RANGED_Q8
-		                                           ? "the ranged int8 walk needs dim % 64 == 0"
-		                                           : "the uint8 walk (use_compression) needs dim % 64 == 0");
+	const int use_compression = mode != EXPANN_GRAPH_FP32;
 	HIP_TRY(g, hipSetDevice(g->device));
+	HIP_TRY(g, graph_wait_outstanding(g));  // (one set of visited arrays: device-buffer searches in flight go first)
 	const GraphVariant* gv = graph_variant(g->dim, mode);
 	if (!gv)
 		return g->fail(EXPANN_ERR_UNSUPPORTED, "no graph kernel for this dim");
@@ -371,55 +533,29 @@ int expann_graph_search_mode(expann_graph* g, const float* queries, size_t m, si
 	HIP_TRY(g, hipMemcpyAsync(d_q, queries, qb, hipMemcpyHostToDevice, g->stream));
 	HIP_TRY(g, hipMemsetAsync(g->d_error, 0, 2 * sizeof(uint32_t), g->stream));
 	uint32_t err_host = 0;
-	uint32_t cand_cap = 256;
-	while (cand_cap < 16 * ef_search && cand_cap < 8192)
-		cand_cap *= 2;
+	uint32_t cand_cap = graph_first_cand_cap(ef_search);
 	for (;;) {  // until no candidates heap overflows, or its LDS capacity limit (8192) is reached
-		GraphSearchParams p{};
-		p.vectors = g->d_vectors;
-		p.compressed = mode == EXPANN_GRAPH_RANGED_Q8 ? g->d_ranged : g->d_compressed;
-		p.q_scale = g->ranged_scale;
-		p.q_offset = g->ranged_offset;
-		p.layer_off = g->d_layer_off;
-		p.neighbours = g->d_neighbours;
-		p.adj0 = g->d_adj0;
-		p.stride0 = g->stride0;
-		p.n = (uint32_t)g->n;
-		p.n_layers = g->n_layers;
-		p.starting_vertex = g->starting_vertex;
+		GraphSearchParams p = graph_base_params(g, mode, k, ef_search);
 		p.queries = d_q;
 		p.m = (uint32_t)m;
-		p.k = (uint32_t)k;
-		p.ef = (uint32_t)ef_search;
 		p.cand_cap = cand_cap;
-		p.max_degree = g->max_degree0;
-		p.list_cap = std::max<uint32_t>(std::max<uint32_t>(g->stride0, (uint32_t)ef_search), 4);
-		p.visited = g->d_visited;
-		p.vis_bits = reinterpret_cast<uint32_t*>(g->d_visited);
-		p.vis_words = g->vis_words;
-		p.epochs = g->d_epochs;
 		p.out_ids = d_ids;
 		p.out_dists = d_d;
 		p.out_distcomps = d_dc;
 		p.error = g->d_error;
 		p.next_query = g->d_error + 1;
-		p.dim = (uint32_t)g->dim;
-		if (const char* e = std::getenv("EXPANN_GRAPH_DEBUG"))
-			p.debug = (uint32_t)std::atol(e);
 		if (stamps) {
 			if (!b_stamps.p)
 				HIP_TRY(g, b_stamps.alloc(sizeof(unsigned long long) * 8 * g->slots));
 			HIP_TRY(g, hipMemsetAsync(b_stamps.p, 0, sizeof(unsigned long long) * 8 * g->slots, g->stream));
 			p.stamps = b_stamps.as<unsigned long long>();
 		}
-		size_t lds = sizeof(md_pair) * (p.ef + 1 + p.cand_cap + 1) +
-		             (sizeof(uint32_t) + sizeof(float)) * p.list_cap;
-		if (gv->d == 0)  // the run-time-dim instance: the query (and its bytes) in LDS
-			lds += (size_t)g->dim * (sizeof(float) + (use_compression ? 1 : 0));
-		if (lds > 160 * 1024)
+		const size_t lds = graph_lds_bytes(p, cand_cap, gv->d == 0, use_compression != 0);
+		if (lds > kGraphMaxLds)
 			return g->fail(EXPANN_ERR_UNSUPPORTED, "graph search working set exceeds LDS");
 		HIP_TRY(g, hipFuncSetAttribute((const void*)gv->fn, hipFuncAttributeMaxDynamicSharedMemorySize,
 		                               (int)lds));
+		g_graph_attr_gen.fetch_add(1, std::memory_order_relaxed);
 		// as many workgroups as are resident at once (registers and LDS of this instance), each with a
 		// visited array of its own; they pull queries from a counter
 		int per_cu = 0;
@@ -467,6 +603,169 @@ int expann_graph_search_mode(expann_graph* g, const float* queries, size_t m, si
 		HIP_TRY(g, hipMemcpy(distcomps, d_dc, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
 	if (err_host)
 		return g->fail(EXPANN_ERR_OVERFLOW, "graph search: candidates queue overflowed its LDS capacity");
+	return EXPANN_OK;
+}
+
+int expann_graph_search_device(expann_graph* g, const float* d_queries, size_t m, size_t k, size_t ef_search, int mode,
+                               uint64_t* d_ids, float* d_dists, uint32_t* d_distcomps, void* stream) {
+	if (!g)
+		return EXPANN_ERR_INVALID_ARG;
+	bool empty = false;
+	if (int rc = graph_search_args(g, d_queries, m, k, ef_search, mode, d_ids, d_dists, &empty))
+		return rc;
+	if (empty)
+		return EXPANN_OK;
+	const bool use_compression = mode != EXPANN_GRAPH_FP32;
+	HIP_TRY(g, hipSetDevice(g->device));
+	bool any_dim = false;
+	const GraphSearchFn fn = graph_search_device_instance(g->dim, mode, &any_dim);
+	if (!fn)
+		return g->fail(EXPANN_ERR_UNSUPPORTED, "no graph kernel for this dim");
+	hipStream_t st = stream ? (hipStream_t)stream : g->stream;
+	if (int rc = graph_dev_init(g))
+		return rc;
+	// one set of visited arrays: searches overlap in stream order only
+	if (g->dev_outstanding && st != g->dev_stream)
+		HIP_TRY(g, graph_wait_outstanding(g));
+	if (g->dev_outstanding >= kGraphMaxOutstanding)
+		if (int rc = graph_drain(g))
+			return rc;
+	// the byte copy of the rows is complete before the walk starts, on whichever stream that runs
+	if (mode == EXPANN_GRAPH_RANGED_Q8) {
+		if (int rc = graph_ensure_ranged(g))
+			return rc;
+	} else if (use_compression && !g->d_compressed) {
+		HIP_TRY(g, hipMalloc(&g->d_compressed, g->n * (size_t)g->dim));
+		launch_quantize_simple_u8(g->d_vectors, g->n * (size_t)g->dim, g->d_compressed, g->stream);
+		HIP_TRY(g, hipGetLastError());
+		HIP_TRY(g, hipStreamSynchronize(g->stream));
+	}
+	GraphSearchParams p = graph_base_params(g, mode, k, ef_search);
+	const uint32_t cand_cap = g->opt_cand_cap ? (uint32_t)g->opt_cand_cap : graph_first_cand_cap(ef_search);
+	const size_t lds = graph_lds_bytes(p, cand_cap, any_dim, use_compression);
+	if (lds > kGraphMaxLds)
+		return g->fail(EXPANN_ERR_UNSUPPORTED, "graph search working set exceeds LDS");
+	// the redo launch's heap: the largest power of two up to 8192 whose working set fits
+	uint32_t redo_cap = (uint32_t)g->opt_redo_cap;
+	if (!redo_cap)
+		for (redo_cap = 8192; redo_cap > cand_cap && graph_lds_bytes(p, redo_cap, any_dim, use_compression) > kGraphMaxLds;)
+			redo_cap /= 2;
+	const bool redo = redo_cap > cand_cap;  // (else an overflow of the first launch is final)
+	const size_t lds_redo = redo ? graph_lds_bytes(p, redo_cap, any_dim, use_compression) : 0;
+	if (lds_redo > kGraphMaxLds)
+		return g->fail(EXPANN_ERR_UNSUPPORTED, "graph search: the working set at \"redo_capacity\" exceeds LDS");
+	uint32_t resident = 0, resident_redo = 0;
+	if (int rc = graph_plan(g, (const void*)fn, lds, &resident))
+		return rc;
+	if (redo) {
+		if (int rc = graph_plan(g, (const void*)fn, lds_redo, &resident_redo))
+			return rc;
+		if (sizeof(uint32_t) * m > g->d_redo_list.bytes || !g->d_redo_list) {  // (a grow frees the list in use)
+			HIP_TRY(g, graph_wait_outstanding(g));
+			HIP_TRY(g, g->d_redo_list.ensure(sizeof(uint32_t) * m));
+		}
+	}
+	uint32_t* ctr = g->d_dev_ctr + (size_t)g->dev_outstanding * kGraphCtrWords;
+	HIP_TRY(g, hipMemsetAsync(ctr, 0, sizeof(uint32_t) * kGraphCtrWords, st));
+	p.queries = d_queries;
+	p.m = (uint32_t)m;
+	p.cand_cap = cand_cap;
+	p.out_ids = d_ids;
+	p.out_dists = d_dists;
+	p.out_distcomps = d_distcomps;
+	p.error = ctr;
+	p.next_query = ctr + 1;
+	p.distcomps_total = g->d_dc_total;
+	if (redo) {
+		p.redo_list = g->d_redo_list;
+		p.redo_count = ctr + 2;
+	}
+	const uint32_t grid = (uint32_t)std::min<size_t>(m, std::min<uint32_t>(g->slots, resident));
+	HIP_TRY(g, hipEventRecord(g->ev_dev[0], st));
+	hipLaunchKernelGGL(fn, dim3(grid), dim3(64), lds, st, p);
+	HIP_TRY(g, hipEventRecord(g->ev_dev[1], st));
+	if (redo) {
+		// the overflowed queries again, at the larger heap: sized without knowing how many there are -- the
+		// workgroups that find the list empty leave after one atomic
+		GraphSearchParams r = p;
+		r.cand_cap = redo_cap;
+		r.redo_list = nullptr;  // an overflow here raises the error flag
+		r.redo_count = nullptr;
+		r.query_map = g->d_redo_list;
+		r.m_dev = ctr + 2;
+		r.next_query = ctr + 3;
+		const uint32_t grid_redo = (uint32_t)std::min<size_t>(m, std::min<uint32_t>(g->slots, resident_redo));
+		hipLaunchKernelGGL(fn, dim3(grid_redo), dim3(64), lds_redo, st, r);
+		HIP_TRY(g, hipEventRecord(g->ev_dev[2], st));
+	}
+	HIP_TRY(g, hipGetLastError());
+	g->dev_stream = st;
+	++g->dev_outstanding;
+	++g->stat_deferred;
+	g->dev_timed = true;
+	g->dev_timed_redo = redo;
+	return EXPANN_OK;
+}
+
+int expann_graph_sync(expann_graph* g) {
+	if (!g)
+		return EXPANN_ERR_INVALID_ARG;
+	HIP_TRY(g, hipSetDevice(g->device));
+	if (int rc = graph_drain(g))
+		return rc;
+	if (g->dev_timed) {  // the last search's launches, from its events
+		float ms = 0, ms_redo = 0;
+		HIP_TRY(g, hipEventElapsedTime(&ms, g->ev_dev[0], g->ev_dev[1]));
+		if (g->dev_timed_redo)
+			HIP_TRY(g, hipEventElapsedTime(&ms_redo, g->ev_dev[1], g->ev_dev[2]));
+		g->last_ms = (double)ms + (double)ms_redo;
+		g->stat_redo_ms = ms_redo;
+		g->dev_timed = false;
+	}
+	const uint64_t overflows = g->pend_overflows;
+	g->stat_redo_queries = g->pend_redo_queries;
+	g->stat_redo_overflows += overflows;
+	g->pend_overflows = g->pend_redo_queries = 0;
+	if (overflows)
+		return g->fail(EXPANN_ERR_OVERFLOW, "graph search: candidates queue overflowed its LDS capacity in " +
+		                                        std::to_string(overflows) + " search(es) since the last sync");
+	return EXPANN_OK;
+}
+
+int expann_graph_set_option(expann_graph* g, const char* name, long value) {
+	if (!g)
+		return EXPANN_ERR_INVALID_ARG;
+	if (!name)
+		return g->fail(EXPANN_ERR_INVALID_ARG, "NULL option name");
+	const std::string o(name);
+	const bool cand = o == "cand_capacity";
+	if (!cand && o != "redo_capacity")
+		return g->fail(EXPANN_ERR_INVALID_ARG, "unknown option: " + o);
+	// 0 = auto, else a power of two >= 8 (the redo launch's at most 8192, the LDS limit of the heap)
+	if (value != 0 && (value < 8 || (value & (value - 1)) != 0 || value > (cand ? (1L << 20) : 8192L)))
+		return g->fail(EXPANN_ERR_INVALID_ARG, o + " must be 0 or a power of two >= 8" + (cand ? "" : " and <= 8192"));
+	(cand ? g->opt_cand_cap : g->opt_redo_cap) = value;
+	return EXPANN_OK;
+}
+
+int expann_graph_get_stat(expann_graph* g, const char* name, uint64_t* out) {
+	if (!g)
+		return EXPANN_ERR_INVALID_ARG;
+	if (!name || !out)
+		return g->fail(EXPANN_ERR_INVALID_ARG, "NULL pointer");
+	const std::string o(name);
+	if (o == "redo_queries")
+		*out = g->stat_redo_queries;
+	else if (o == "redo_overflows")
+		*out = g->stat_redo_overflows;
+	else if (o == "deferred_searches")
+		*out = g->stat_deferred;
+	else if (o == "distcomps")
+		*out = g->stat_distcomps;
+	else if (o == "redo_kernel_ns")
+		*out = (uint64_t)(g->stat_redo_ms * 1e6);
+	else
+		return g->fail(EXPANN_ERR_INVALID_ARG, "unknown stat: " + o);
 	return EXPANN_OK;
 }
 
@@ -863,6 +1162,25 @@ int expann_antitopo_query(expann_antitopo* e, const float* queries, size_t m, si
 		return e ? e->fail(EXPANN_ERR_INVALID_ARG, "bad arguments") : EXPANN_ERR_INVALID_ARG;
 	ANTITOPO_TRY(e, e->eng->query_k_batch(queries, m, k, ids, dists));
 	return EXPANN_OK;
+}
+
+int expann_antitopo_query_device(expann_antitopo* e, const float* d_queries, size_t m, size_t k, uint64_t* d_ids,
+                                 float* d_dists, void* stream) {
+	if (!e)
+		return EXPANN_ERR_INVALID_ARG;
+	if (!e->eng->graph)
+		return e->fail(EXPANN_ERR_NOT_BUILT, "expann_antitopo_query_device before build()");
+	const int rc = e->eng->query_k_batch_device(d_queries, m, k, d_ids, d_dists, stream);
+	return rc == EXPANN_OK ? rc : e->fail(rc, expann_graph_last_error(e->eng->graph));
+}
+
+int expann_antitopo_sync(expann_antitopo* e) {
+	if (!e)
+		return EXPANN_ERR_INVALID_ARG;
+	if (!e->eng->graph)
+		return e->fail(EXPANN_ERR_NOT_BUILT, "expann_antitopo_sync before build()");
+	const int rc = e->eng->sync();
+	return rc == EXPANN_OK ? rc : e->fail(rc, expann_graph_last_error(e->eng->graph));
 }
 
 int expann_antitopo_save(expann_antitopo* e, const char* index_path) {

@@ -75,6 +75,20 @@ struct GraphSearchParams {
 	unsigned long long* stamps;
 	uint32_t dim;                 // run-time-dim instance (D = 0) only: the row length (the others have it as D)
 	float q_scale, q_offset;      // kGraphRangedQ8 only: the rows' quantiser, applied to the query as it is staged
+	// Device-buffer searches (expann_graph_search_device): read by the DEV instances only, and inert when nullptr.
+	// redo_list != nullptr: a walk that met a full candidates heap appends its query number to
+	// redo_list[atomicAdd(redo_count, 1)] instead of raising `error` (its output row is still written).
+	uint32_t* redo_list;          // [m]
+	uint32_t* redo_count;         // [1] zero at launch
+	// query_map != nullptr: the number pulled from next_query indexes query_map, and the bound is *m_dev (at most m).
+	// A second launch with query_map = the first one's redo_list and m_dev = its redo_count walks the overflowed
+	// queries again at this launch's cand_cap and overwrites their rows; workgroups that find nothing leave after
+	// one atomic.
+	const uint32_t* query_map;
+	const uint32_t* m_dev;
+	// != nullptr: every query adds its distcomps (one atomic from one lane); a query put on the redo list does
+	// not, the launch that walks it again does
+	unsigned long long* distcomps_total;
 };
 
 struct md_pair {
@@ -348,7 +362,7 @@ template <bool MAXH> __device__ inline void heap_trace_body(const HeapTraceParam
 	if (lane == 0)
 		*p.n_drain = nd;
 }
-__global__ __launch_bounds__(64) void heap_trace_kernel(HeapTraceParams p) {
+static __global__ __launch_bounds__(64) void heap_trace_kernel(HeapTraceParams p) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char heap_trace_smem[];
 	md_pair* v = reinterpret_cast<md_pair*>(heap_trace_smem);
 	if (p.max_heap)
@@ -519,8 +533,14 @@ template <int D> constexpr int graph_rows_u8() { return D == 0 ? kGraphAnyRows :
 // D = 0: the run-time-dim instance (p.dim); the query and its bytes sit in LDS behind ndist
 // MODE: kGraphF32 / kGraphU8Cast / kGraphRangedQ8; the two byte modes are one walk (COMPRESSED), the ranged
 // one differs where the query's bytes are made
-template <int D, int MODE, int DBG = 0>
-__global__ __launch_bounds__(64, D == 0 ? 3 : ((MODE != kGraphF32 && D <= 128) ? 4 : 1)) void graph_search_kernel(GraphSearchParams p) {
+// waves per SIMD the run-time-dim instances are held to: 3; the byte walks of the device-buffer instances 4 -- their
+// host-buffer twins fit 128 registers without being asked, the extra parameters would cost these the fourth wave
+template <int MODE, bool DEV> constexpr int graph_any_dim_waves() { return (DEV && MODE != kGraphF32) ? 4 : 3; }
+
+// DEV: the instances of the device-buffer searches (redo list, query indirection, distcomps total); the others do
+// not contain that code and ignore its parameters
+template <int D, int MODE, int DBG = 0, bool DEV = false>
+__global__ __launch_bounds__(64, D == 0 ? (graph_any_dim_waves<MODE, DEV>()) : ((MODE != kGraphF32 && D <= 128) ? 4 : 1)) void graph_search_kernel(GraphSearchParams p) {
 	constexpr bool COMPRESSED = MODE != kGraphF32, RANGED = MODE == kGraphRangedQ8;
 	constexpr int DPL = D ? D / 16 : 1;
 	constexpr int NW = D ? D / 64 : 1;
@@ -564,8 +584,14 @@ __global__ __launch_bounds__(64, D == 0 ? 3 : ((MODE != kGraphF32 && D <= 128) ?
 		if (lane == 0)
 			qi = atomicAdd(p.next_query, 1u);
 		qi = (uint32_t)__builtin_amdgcn_readfirstlane((int)qi);
-		if (qi >= p.m)
+		if (DEV && p.query_map) {  // a redo launch: the queries the list names, as many as the device counted
+			const uint32_t m_redo = *p.m_dev;
+			if (qi >= (m_redo < p.m ? m_redo : p.m))
+				break;
+			qi = p.query_map[qi];
+		} else if (qi >= p.m)
 			break;
+		bool q_overflowed = false;  // wave-uniform: this walk met a full candidates heap
 		// ---- per-query setup ----------------------------------------------------------
 		if (!bits && ++epoch > 255) {  // epoch bytes wrapped: clear this workgroup's visited array
 			for (uint32_t i = lane; i < p.n; i += 64)
@@ -823,9 +849,12 @@ __global__ __launch_bounds__(64, D == 0 ? 3 : ((MODE != kGraphF32 && D <= 128) ?
 				const float dn = ndist[j];
 				if (n_near < p.ef || dn < nearest[0].d) {
 					const md_pair e{dn, nlist[j]};
-					if (n_cand >= p.cand_cap)
-						overflowed = 1;
-					else
+					if (n_cand >= p.cand_cap) {
+						if (DEV)
+							q_overflowed = true;
+						else
+							overflowed = 1;
+					} else
 						coop_push<false>(candidates, n_cand, e, lane, p.debug & 1);
 					coop_push<true>(nearest, n_near, e, lane, p.debug & 1);
 					wave_lds_sync();
@@ -865,6 +894,19 @@ __global__ __launch_bounds__(64, D == 0 ? 3 : ((MODE != kGraphF32 && D <= 128) ?
 		}
 		if (lane == 0 && p.out_distcomps)
 			p.out_distcomps[qi] = distcomps;
+		// an overflowed walk goes on the redo list when there is one (its row is rewritten by the redo launch, which
+		// also counts its distcomps), else it raises the launch's error flag
+		if constexpr (DEV) {
+			const bool to_redo = q_overflowed && p.redo_list;
+			if (q_overflowed && !to_redo)
+				overflowed = 1;
+			if (lane == 0) {
+				if (to_redo)
+					p.redo_list[atomicAdd(p.redo_count, 1u)] = qi;
+				else if (p.distcomps_total)
+					atomicAdd(p.distcomps_total, (unsigned long long)distcomps);
+			}
+		}
 		if (bits) {  // the set goes back to all-zero: 16 bytes per lane and store, nothing waits for them
 			uint4* w = reinterpret_cast<uint4*>(vbits);
 			for (uint32_t i = lane; i < p.vis_words / 4; i += 64)
@@ -883,5 +925,10 @@ __global__ __launch_bounds__(64, D == 0 ? 3 : ((MODE != kGraphF32 && D <= 128) ?
 			atomicAdd(p.error, 1u);
 	}
 }
+
+// the DEV instance of (dim, mode) -- compiled for that dim, else the run-time-dim one; they are a translation unit
+// of their own (expann_graph_device.hip), so the build compiles them next to the others
+using GraphSearchFn = void (*)(GraphSearchParams);
+GraphSearchFn graph_search_device_instance(int dim, int mode, bool* run_time_dim);
 
 }  // namespace expann

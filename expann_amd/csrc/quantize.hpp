@@ -9,7 +9,7 @@
 
 namespace expann {
 
-__global__ __launch_bounds__(kBlock) void quantize_simple_u8_kernel(const float* in, size_t n_values,
+static __global__ __launch_bounds__(kBlock) void quantize_simple_u8_kernel(const float* in, size_t n_values,
                                                                     uint8_t* out) {
 	const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
 	if (i < n_values)
@@ -18,7 +18,7 @@ __global__ __launch_bounds__(kBlock) void quantize_simple_u8_kernel(const float*
 
 // minmax[0] = ordered(min), minmax[1] = ordered(max); initialised by the host to
 // ordered(FLT_MAX) / ordered(FLT_MIN) as the reference initialises min_val / max_val
-__global__ __launch_bounds__(kBlock) void minmax_f32_kernel(const float* in, size_t n_values,
+static __global__ __launch_bounds__(kBlock) void minmax_f32_kernel(const float* in, size_t n_values,
                                                             uint32_t* minmax) {
 	float lo = 3.402823466e+38f, hi = -3.402823466e+38f;
 	for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n_values;
@@ -49,7 +49,7 @@ __device__ inline int ranged_q8_convert(float x, float scale, float offset) {
 	return (int)c;
 }
 
-__global__ __launch_bounds__(kBlock) void quantize_ranged_q8_kernel(const float* in, size_t n_values,
+static __global__ __launch_bounds__(kBlock) void quantize_ranged_q8_kernel(const float* in, size_t n_values,
                                                                     const uint32_t* minmax,
                                                                     int8_t* out, float* scale_offset) {
 	const float min_val = ordered_to_float(minmax[0]);

@@ -155,6 +155,25 @@ class AntitopoEngine:
                                                   ids.ctypes.data, dists.ctypes.data))
         return ids, dists
 
+    def query_many_device(self, q_ptr, m, k, ids_ptr, dists_ptr, stream=0):
+        """query_many on device buffers, enqueued on `stream` (a hipStream_t as an integer; 0 = the engine's own)
+        without waiting for it: q_ptr -> m rows of float32 that ALREADY have the engine's padded `dim` (there is no
+        padding on this path), ids_ptr -> uint64 [m][k], dists_ptr -> float32 [m][k], raw device addresses (a torch
+        tensor's data_ptr()).  The same sticky ef_search and compression mode as query_many.  The results are valid
+        after sync(); searches of one engine overlap only in stream order."""
+        if self._h is None:
+            raise _lib.ExpannError(_lib.ERR_NOT_BUILT, "query_many_device() before build()")
+        self._check(self._L.expann_antitopo_query_device(self._h, C.c_void_p(q_ptr), int(m), int(k),
+                                                         C.c_void_p(ids_ptr), C.c_void_p(dists_ptr),
+                                                         C.c_void_p(stream or None)))
+
+    def sync(self):
+        """Wait for the stream of the last query_many_device and check every such search since the last sync()
+        (raises ExpannError with ERR_OVERFLOW when a walk overflowed its queue even in the redo launch)."""
+        if self._h is None:
+            raise _lib.ExpannError(_lib.ERR_NOT_BUILT, "sync() before build()")
+        self._check(self._L.expann_antitopo_sync(self._h))
+
     def save_index(self, path):
         self._check(self._L.expann_antitopo_save(self._h, str(path).encode()))
 

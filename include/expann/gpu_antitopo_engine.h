@@ -52,6 +52,7 @@ struct gpu_antitopo_engine : public ann_engine<T, gpu_antitopo_engine<T>> {
 	expann_graph* graph = nullptr;
 	std::optional<size_t> ef_search;
 	size_t num_distcomps = 0;  // RECORD_STATS counter (src/antitopo_engine.h:125-129)
+	uint64_t device_distcomps_seen = 0;  // the graph handle's device counter at the last sync()
 
 	explicit gpu_antitopo_engine(config c) : conf(c) { index.conf = c; }
 	gpu_antitopo_engine(const gpu_antitopo_engine&) = delete;
@@ -127,6 +128,7 @@ struct gpu_antitopo_engine : public ann_engine<T, gpu_antitopo_engine<T>> {
 		const auto fg = index.flatten();
 		expann_graph_destroy(graph);
 		graph = nullptr;
+		device_distcomps_seen = 0;
 		int rc = expann_graph_create(int(index.dim), conf.device, index.vectors.data(), index.size(),
 		                             fg.n_layers, fg.starting_vertex, fg.layer_offsets.data(),
 		                             fg.neighbours.data(), &graph);
@@ -164,6 +166,31 @@ struct gpu_antitopo_engine : public ann_engine<T, gpu_antitopo_engine<T>> {
 			if (distcomps)
 				distcomps[i] = dc[i];
 		}
+	}
+	// Extension: the same on device buffers, enqueued on `stream` (nullptr = the graph handle's) without waiting:
+	// expann_graph_search_device with the sticky ef_search and conf.mode() of query_k_batch.  Returns the
+	// expann_status (message: expann_graph_last_error(graph)); results are valid after sync().
+	int query_k_batch_device(const float* d_queries, size_t m, size_t k, uint64_t* d_ids, float* d_dists, void* stream) {
+		if (!graph)
+			return EXPANN_ERR_NOT_BUILT;
+		if (k == 0)
+			return expann_graph_search_device(graph, d_queries, m, k, 1, conf.mode(), d_ids, d_dists, nullptr, stream);
+		if (!ef_search.has_value())
+			set_ef_search(k * conf.ef_search_mult);  // :858-859
+		return expann_graph_search_device(graph, d_queries, m, k, ef_search.value(), conf.mode(), d_ids, d_dists, nullptr,
+		                                  stream);
+	}
+	// expann_graph_sync; the distance evaluations the device counted since the last sync go to num_distcomps
+	int sync() {
+		if (!graph)
+			return EXPANN_ERR_NOT_BUILT;
+		const int rc = expann_graph_sync(graph);
+		uint64_t total = 0;
+		if (expann_graph_get_stat(graph, "distcomps", &total) == EXPANN_OK && total >= device_distcomps_seen) {
+			num_distcomps += size_t(total - device_distcomps_seen);
+			device_distcomps_seen = total;
+		}
+		return rc;
 	}
 	const std::string _name() { return "GPU Anti-Topo Engine+ (MI355X)"; }
 	const param_list_t _param_list() {  // :242-259

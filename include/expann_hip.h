@@ -282,6 +282,42 @@ int expann_graph_search_mode(expann_graph* g, const float* queries, size_t m, si
  * (errors as mode 2 of expann_graph_search_mode) */
 int expann_graph_ranged_params(expann_graph* g, float* scale_factor, float* offset);
 
+/* Graph search on device buffers (appended; EXPANN_ABI_VERSION stays 2: nothing that existed changed).
+ * expann_graph_search_device is expann_graph_search_mode with the queries [m][dim], ids [m][k], dists [m][k] and
+ * distcomps [m] (may be NULL) in device memory: same arguments, same checks in the same order, same error codes,
+ * all before the device is touched; m == 0 is EXPANN_OK and enqueues nothing.  The call ENQUEUES on `stream` (a
+ * hipStream_t; NULL = the handle's own) and returns without waiting for it: the resets of its counters, the walk
+ * at the heap capacity the host-buffer call starts with, and a REDO launch that walks only the queries whose
+ * candidates heap overflowed again, at the largest power-of-two capacity up to 8192 whose working set fits the
+ * LDS, and overwrites their rows (sized without knowing their number: with none, its workgroups leave after one
+ * atomic).  A walk that does not overflow never looks at the capacity, so ids, distances and distcomps equal the
+ * host-buffer call's, whose answer to an overflow is to walk the whole batch again.  When the redo capacity is not
+ * larger than the first launch's there is no redo launch and an overflow is final.  In steady state -- the same
+ * kernel instance, a working set and an m no larger than seen before -- a call makes no allocation, no copy
+ * between host and device, no attribute or occupancy query and no synchronisation.
+ * expann_graph_sync waits for the stream of the last such search and reports on all of them since the previous
+ * sync: EXPANN_OK, or EXPANN_ERR_OVERFLOW when a walk overflowed the redo capacity too (that search's rows of those
+ * queries are what the last walk left, as the host-buffer call returns them).  After it
+ * expann_graph_last_kernel_ms is the last search's first launch plus redo launch.
+ * ONE set of visited arrays per handle, so the rule is expann_sync's: searches of a handle overlap only in stream
+ * order; one enqueued on a different stream than the outstanding ones first waits for those on the host, and so do
+ * expann_graph_search / expann_graph_search_mode; at most 256 searches may be outstanding (further ones wait by
+ * themselves).  The first use of mode 1 or 2 on a handle builds its byte copy of the rows on the handle's own
+ * stream and waits for it on the host, so the copy is complete before the walk starts on whichever stream. */
+int expann_graph_search_device(expann_graph* g, const float* d_queries, size_t m, size_t k, size_t ef_search,
+                               int mode, uint64_t* d_ids, float* d_dists, uint32_t* d_distcomps, void* stream);
+int expann_graph_sync(expann_graph* g);
+/* options of the device-buffer path only (0 = auto): "cand_capacity" = the first launch's heap, "redo_capacity" =
+ * the redo launch's (at most 8192); a power of two >= 8, anything else -- and an unknown name -- is
+ * EXPANN_ERR_INVALID_ARG. */
+int expann_graph_set_option(expann_graph* g, const char* name, long value);
+/* "redo_queries" = queries the redo launches served, over the searches the last expann_graph_sync checked;
+ * "redo_overflows" = searches since create that ended in EXPANN_ERR_OVERFLOW; "deferred_searches" = device-buffer
+ * searches since create; "distcomps" = distance evaluations of all device-buffer searches since create, as of the
+ * last sync; "redo_kernel_ns" = device time of the last search's redo launch, as of the last sync.  An unknown
+ * name is EXPANN_ERR_INVALID_ARG. */
+int expann_graph_get_stat(expann_graph* g, const char* name, uint64_t* out);
+
 /* GPU-assisted batched construction of the graph (csrc/graph_build.hpp; replaces the inner loop of
  * antitopo_engine::_store_vector / prune_edges, src/antitopo_engine.h:263-465, for the vectors
  * [n_built, n) -- the first n_built come with their rows already built, by the serial host builder
@@ -323,6 +359,13 @@ int expann_antitopo_set_ef_search(expann_antitopo* e, size_t ef_search);     /* 
 /* query_k for a batch; ef_search defaults to k * ef_search_mult and is sticky (:858-859) */
 int expann_antitopo_query(expann_antitopo* e, const float* queries, size_t m, size_t k,
                           uint64_t* ids, float* dists);
+/* (appended with expann_graph_search_device) expann_antitopo_query on device buffers: the same sticky ef_search
+ * and the same mode, enqueued on `stream` (NULL = the graph handle's) without waiting; expann_antitopo_sync is
+ * expann_graph_sync and adds the distance evaluations the device counted to num_distcomps.  Before build() both
+ * return EXPANN_ERR_NOT_BUILT. */
+int expann_antitopo_query_device(expann_antitopo* e, const float* d_queries, size_t m, size_t k,
+                                 uint64_t* d_ids, float* d_dists, void* stream);
+int expann_antitopo_sync(expann_antitopo* e);
 int expann_antitopo_save(expann_antitopo* e, const char* index_path);  /* serialize, :932-991 */
 int expann_antitopo_load(expann_antitopo* e, const char* index_path);  /* deserialize + upload */
 /* mode (expann_graph_compression) of expann_antitopo_query's bottom layer; default: what use_compression at
