@@ -6,7 +6,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -39,16 +38,16 @@ struct expann_graph {
 	uint8_t* d_visited = nullptr;  // epoch bytes [slots][n], or -- vis_words != 0 -- bitsets [slots][vis_words]
 	uint32_t vis_words = 0;
 	uint32_t* d_epochs = nullptr;
-	uint32_t* d_error = nullptr;   // [2]: overflow flag, query counter of the launch
 	uint32_t slots = 0;
 	hipStream_t stream = nullptr;
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
 	double last_ms = 0;
+	// One counter slot per search: {overflow flag, first launch's query counter, redo count, redo launch's query
+	// counter, 4 spare}; a search resets its slot in stream order.  Slots [0, kGraphMaxOutstanding) belong to the
+	// outstanding device-buffer searches (the sync reads them all), the last one to the host-buffer call.
+	DevPtr<uint32_t> d_dev_ctr;            // [kGraphMaxOutstanding + 1][kGraphCtrWords]
+	PinPtr<uint32_t> h_dev_ctr;            // the same, read back
 	// ---- device-buffer searches (expann_graph_search_device / expann_graph_sync) ----
-	// One counter slot per outstanding search: {overflow flag, first launch's query counter, redo count, redo
-	// launch's query counter, 4 spare}; a search resets its slot in stream order, the sync reads them all.
-	DevPtr<uint32_t> d_dev_ctr;            // [kGraphMaxOutstanding][kGraphCtrWords]
-	PinPtr<uint32_t> h_dev_ctr;            // the same, read back by the sync
 	DevPtr<unsigned long long> d_dc_total; // [1] distcomps of every device search since create
 	PinPtr<unsigned long long> h_dc_total;
 	GrowPtr<uint32_t> d_redo_list;         // [largest m seen]
@@ -66,7 +65,6 @@ struct expann_graph {
 		const void* fn;
 		size_t lds;
 		uint32_t resident;
-		uint64_t attr_gen;  // g_graph_attr_gen when this plan last set the instance's dynamic-LDS attribute
 	};
 	std::vector<LaunchPlan> plans;
 	mutable std::string err;
@@ -185,11 +183,7 @@ int graph_ensure_ranged(expann_graph* g) {
 
 constexpr size_t kGraphMaxLds = 160 * 1024;     // the working set a search may take of a CU's LDS
 constexpr uint32_t kGraphMaxOutstanding = 256;  // device-buffer searches between two drains
-constexpr uint32_t kGraphCtrWords = 8;          // counter words per outstanding search
-
-// Bumped whenever the host-buffer path sets an instance's dynamic-LDS attribute (to that call's size): the
-// device-buffer path, which caches its launch set-up, then sets the attribute again before its next launch.
-std::atomic<uint64_t> g_graph_attr_gen{1};
+constexpr uint32_t kGraphCtrWords = 8;          // counter words per search
 
 // the argument checks of a search, in the order the header documents, all before the device is touched;
 // *empty: m == 0, nothing to do
@@ -283,7 +277,8 @@ int graph_drain(expann_graph* g) {
 	return EXPANN_OK;
 }
 
-// counters, their pinned mirror and the events of the device-buffer path, made at its first search
+// counter slots, their pinned mirror, and the events and distcomps total of the device-buffer searches, made at
+// the handle's first search
 int graph_dev_init(expann_graph* g) {
 	if (g->d_dev_ctr)
 		return EXPANN_OK;
@@ -291,14 +286,14 @@ int graph_dev_init(expann_graph* g) {
 		if (!ev)
 			HIP_TRY(g, hipEventCreate(&ev));
 	if (!g->h_dev_ctr)
-		HIP_TRY(g, hipHostMalloc((void**)&g->h_dev_ctr, sizeof(uint32_t) * kGraphCtrWords * kGraphMaxOutstanding));
+		HIP_TRY(g, hipHostMalloc((void**)&g->h_dev_ctr, sizeof(uint32_t) * kGraphCtrWords * (kGraphMaxOutstanding + 1)));
 	if (!g->h_dc_total)
 		HIP_TRY(g, hipHostMalloc((void**)&g->h_dc_total, sizeof(unsigned long long)));
 	if (!g->d_dc_total) {
 		HIP_TRY(g, hipMalloc(&g->d_dc_total, sizeof(unsigned long long)));
 		HIP_TRY(g, hipMemset(g->d_dc_total, 0, sizeof(unsigned long long)));
 	}
-	HIP_TRY(g, hipMalloc(&g->d_dev_ctr, sizeof(uint32_t) * kGraphCtrWords * kGraphMaxOutstanding));
+	HIP_TRY(g, hipMalloc(&g->d_dev_ctr, sizeof(uint32_t) * kGraphCtrWords * (kGraphMaxOutstanding + 1)));
 	return EXPANN_OK;
 }
 
@@ -306,13 +301,8 @@ int graph_dev_init(expann_graph* g) {
 // (instance, LDS size) and handle.  The attribute is set to the largest working set a search may have, so that
 // plans of one instance do not undo each other's.
 int graph_plan(expann_graph* g, const void* fn, size_t lds, uint32_t* resident) {
-	const uint64_t gen = g_graph_attr_gen.load(std::memory_order_relaxed);
-	for (auto& pl : g->plans)
+	for (const auto& pl : g->plans)
 		if (pl.fn == fn && pl.lds == lds) {
-			if (pl.attr_gen != gen) {
-				HIP_TRY(g, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGraphMaxLds));
-				pl.attr_gen = gen;
-			}
 			*resident = pl.resident;
 			return EXPANN_OK;
 		}
@@ -320,7 +310,119 @@ int graph_plan(expann_graph* g, const void* fn, size_t lds, uint32_t* resident) 
 	int per_cu = 0;
 	HIP_TRY(g, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, lds));
 	*resident = (uint32_t)std::max(1, per_cu) * (uint32_t)num_cus(g->device);
-	g->plans.push_back({fn, lds, *resident, gen});
+	g->plans.push_back({fn, lds, *resident});
+	return EXPANN_OK;
+}
+
+// the byte copy of the rows that `mode` walks, made at its first use on the handle's own stream and complete on
+// return, on whichever stream the walk then runs (EXPANN_OK, or the error on g)
+int graph_ensure_bytes(expann_graph* g, int mode) {
+	if (mode == EXPANN_GRAPH_RANGED_Q8)  // quantizer_ranged_q8::build, src/quantizer.h:213-232
+		return graph_ensure_ranged(g);
+	if (mode == EXPANN_GRAPH_U8_CAST && !g->d_compressed) {  // quantizer_simple<uint8_t>::build, :485-486
+		HIP_TRY(g, hipMalloc(&g->d_compressed, g->n * (size_t)g->dim));
+		launch_quantize_simple_u8(g->d_vectors, g->n * (size_t)g->dim, g->d_compressed, g->stream);
+		HIP_TRY(g, hipGetLastError());
+		HIP_TRY(g, hipStreamSynchronize(g->stream));
+	}
+	return EXPANN_OK;
+}
+
+// A search, planned: the walk of all queries at the first heap capacity, and the REDO launch that walks the
+// queries whose candidates heap overflowed again at a larger one and overwrites their rows.
+struct GraphSearchPlan {
+	GraphFn fn = nullptr;
+	GraphSearchParams first{}, redo{};
+	size_t lds = 0, lds_redo = 0;
+	uint32_t grid = 0, grid_redo = 0;
+	bool has_redo = false;  // false: no larger capacity to go to, an overflow of the first launch is final
+};
+
+// Plans the search whose queries, outputs (and distcomps total / stamps) `p` names, with the counter slot `ctr`:
+// capacities, working sets, grids and both launches' parameters.  Enqueues nothing, except that growing the redo
+// list first waits for the searches that may still use it.
+int graph_search_plan(expann_graph* g, const GraphVariant* gv, GraphSearchParams p, uint32_t* ctr, GraphSearchPlan* pl) {
+	const bool any_dim = gv->d == 0, use_compression = gv->mode != EXPANN_GRAPH_FP32;
+	const uint32_t cand_cap = g->opt_cand_cap ? (uint32_t)g->opt_cand_cap : graph_first_cand_cap(p.ef);
+	pl->fn = gv->fn;
+	pl->lds = graph_lds_bytes(p, cand_cap, any_dim, use_compression);
+	if (pl->lds > kGraphMaxLds)
+		return g->fail(EXPANN_ERR_UNSUPPORTED, "graph search working set exceeds LDS");
+	// the redo launch's heap: the largest power of two up to 8192 whose working set fits
+	uint32_t redo_cap = (uint32_t)g->opt_redo_cap;
+	if (!redo_cap)
+		for (redo_cap = 8192; redo_cap > cand_cap && graph_lds_bytes(p, redo_cap, any_dim, use_compression) > kGraphMaxLds;)
+			redo_cap /= 2;
+	pl->has_redo = redo_cap > cand_cap;
+	pl->lds_redo = pl->has_redo ? graph_lds_bytes(p, redo_cap, any_dim, use_compression) : 0;
+	if (pl->lds_redo > kGraphMaxLds)
+		return g->fail(EXPANN_ERR_UNSUPPORTED, "graph search: the working set at \"redo_capacity\" exceeds LDS");
+	// as many workgroups as are resident at once (registers and LDS of this instance), each with a visited array
+	// of its own; they pull queries from a counter
+	uint32_t resident = 0;
+	if (int rc = graph_plan(g, (const void*)gv->fn, pl->lds, &resident))
+		return rc;
+	pl->grid = (uint32_t)std::min<size_t>(p.m, std::min<uint32_t>(g->slots, resident));
+	p.cand_cap = cand_cap;
+	p.error = ctr;
+	p.next_query = ctr + 1;
+	pl->first = p;
+	if (!pl->has_redo)
+		return EXPANN_OK;
+	if (int rc = graph_plan(g, (const void*)gv->fn, pl->lds_redo, &resident))
+		return rc;
+	// sized without knowing how many queries overflowed: the workgroups that find the list empty leave after one atomic
+	pl->grid_redo = (uint32_t)std::min<size_t>(p.m, std::min<uint32_t>(g->slots, resident));
+	if (sizeof(uint32_t) * p.m > g->d_redo_list.bytes || !g->d_redo_list) {  // (a grow frees the list in use)
+		HIP_TRY(g, graph_wait_outstanding(g));
+		HIP_TRY(g, g->d_redo_list.ensure(sizeof(uint32_t) * p.m));
+	}
+	pl->first.redo_list = g->d_redo_list;
+	pl->first.redo_count = ctr + 2;
+	pl->redo = p;  // (no redo list: an overflow here raises the error flag)
+	pl->redo.cand_cap = redo_cap;
+	pl->redo.query_map = g->d_redo_list;
+	pl->redo.m_dev = ctr + 2;
+	pl->redo.next_query = ctr + 3;
+	return EXPANN_OK;
+}
+
+// the reset of the search's counter slot and its first launch on `st`, between two events
+int graph_enqueue_first(expann_graph* g, const GraphSearchPlan& pl, hipStream_t st, hipEvent_t before, hipEvent_t after) {
+	HIP_TRY(g, hipMemsetAsync(pl.first.error, 0, sizeof(uint32_t) * kGraphCtrWords, st));
+	HIP_TRY(g, hipEventRecord(before, st));
+	hipLaunchKernelGGL(pl.fn, dim3(pl.grid), dim3(64), pl.lds, st, pl.first);
+	HIP_TRY(g, hipEventRecord(after, st));
+	HIP_TRY(g, hipGetLastError());
+	return EXPANN_OK;
+}
+
+// the redo launch (pl.has_redo) on `st`, behind the first one, and the event after it
+int graph_enqueue_redo(expann_graph* g, const GraphSearchPlan& pl, hipStream_t st, hipEvent_t after) {
+	hipLaunchKernelGGL(pl.fn, dim3(pl.grid_redo), dim3(64), pl.lds_redo, st, pl.redo);
+	HIP_TRY(g, hipEventRecord(after, st));
+	HIP_TRY(g, hipGetLastError());
+	return EXPANN_OK;
+}
+
+// EXPANN_GRAPH_STAMPS: a launch's shader clocks, mean over the workgroups of its grid, per hop
+int graph_print_stamps(expann_graph* g, int mode, size_t ef_search, float ms, uint32_t grid, size_t m, const void* d_stamps) {
+	std::vector<unsigned long long> st(8 * (size_t)grid);
+	HIP_TRY(g, hipMemcpy(st.data(), d_stamps, st.size() * 8, hipMemcpyDeviceToHost));
+	double tot[8] = {0};
+	for (uint32_t b = 0; b < grid; ++b)
+		for (int i = 0; i < 8; ++i)
+			tot[i] += (double)st[8 * (size_t)b + i];
+	const double hops = tot[6] > 0 ? tot[6] : 1, all = tot[0] + tot[1] + tot[2] + tot[3] + tot[4] + tot[5];
+	std::fprintf(stderr,
+	             "graph_search<%d,%s> ef %zu: %.3f ms, %u workgroups, %.1f hops / query, %.1f queue insertions / hop; "
+	             "shader clocks per hop: pop + broadcast %.0f, adjacency + visited %.0f, gathers + scoring %.0f, "
+	             "serial queue update %.0f; per query: setup + descent %.0f, output %.0f; shares %.1f / %.1f / %.1f / "
+	             "%.1f / %.1f / %.1f %%\n",
+	             g->dim, kGraphModeName[mode], ef_search, ms, grid, tot[6] / (double)m, tot[7] / hops,
+	             tot[1] / hops, tot[2] / hops, tot[3] / hops, tot[4] / hops, tot[0] / (double)m, tot[5] / (double)m,
+	             100 * tot[1] / all, 100 * tot[2] / all, 100 * tot[3] / all, 100 * tot[4] / all, 100 * tot[0] / all,
+	             100 * tot[5] / all);
 	return EXPANN_OK;
 }
 }  // namespace
@@ -398,8 +500,7 @@ int expann_graph_create(int dim, int device, const float* vectors, size_t n, uin
 	const size_t vbytes = n * (size_t)dim * sizeof(float);
 	if (hipMalloc(&g->d_vectors, vbytes) != hipSuccess ||
 	    hipMalloc(&g->d_layer_off, off32.size() * sizeof(uint32_t)) != hipSuccess ||
-	    hipMalloc(&g->d_neighbours, std::max<uint64_t>(n_edges, 1) * sizeof(uint32_t)) != hipSuccess ||
-	    hipMalloc(&g->d_error, 2 * sizeof(uint32_t)) != hipSuccess)
+	    hipMalloc(&g->d_neighbours, std::max<uint64_t>(n_edges, 1) * sizeof(uint32_t)) != hipSuccess)
 		return bail("hipMalloc");
 	if (hipMemcpy(g->d_vectors, vectors, vbytes, hipMemcpyHostToDevice) != hipSuccess ||
 	    hipMemcpy(g->d_layer_off, off32.data(), off32.size() * sizeof(uint32_t),
@@ -456,7 +557,6 @@ void expann_graph_destroy(expann_graph* g) {
 	if (g->d_adj0) hipFree(g->d_adj0);
 	if (g->d_visited) hipFree(g->d_visited);
 	if (g->d_epochs) hipFree(g->d_epochs);
-	if (g->d_error) hipFree(g->d_error);
 	for (hipEvent_t ev : g->ev_dev)
 		if (ev) hipEventDestroy(ev);
 	if (g->ev0) hipEventDestroy(g->ev0);
@@ -501,7 +601,6 @@ int expann_graph_search_mode(expann_graph* g, const float* queries, size_t m, si
 		return rc;
 	if (empty)
 		return EXPANN_OK;
-	const int use_compression = mode != EXPANN_GRAPH_FP32;
 	HIP_TRY(g, hipSetDevice(g->device));
 	HIP_TRY(g, graph_wait_outstanding(g));  // (one set of visited arrays: device-buffer searches in flight go first)
 	const GraphVariant* gv = graph_variant(g->dim, mode);
@@ -510,98 +609,62 @@ int expann_graph_search_mode(expann_graph* g, const float* queries, size_t m, si
 	const bool stamps = std::getenv("EXPANN_GRAPH_STAMPS") != nullptr && g->dim == 128;
 	if (stamps)
 		gv = &kGraphDbg[mode];
-	DevBuf b_stamps;
-	if (mode == EXPANN_GRAPH_RANGED_Q8) {  // quantizer_ranged_q8::build, src/quantizer.h:213-232
-		if (int rc = graph_ensure_ranged(g))
-			return rc;
-	} else if (use_compression && !g->d_compressed) {  // quantizer_simple<uint8_t>::build, :485-486
-		HIP_TRY(g, hipMalloc(&g->d_compressed, g->n * (size_t)g->dim));
-		const size_t nv = g->n * (size_t)g->dim;
-		launch_quantize_simple_u8(g->d_vectors, nv, g->d_compressed, g->stream);
-		HIP_TRY(g, hipGetLastError());
-	}
-	DevBuf b_q, b_ids, b_d, b_dc;
-	const size_t qb = m * (size_t)g->dim * sizeof(float);
+	if (int rc = graph_dev_init(g))
+		return rc;
+	if (int rc = graph_ensure_bytes(g, mode))
+		return rc;
+	hipStream_t st = g->stream;
+	DevBuf b_q, b_ids, b_d, b_dc, b_stamps;
+	const size_t qb = m * (size_t)g->dim * sizeof(float), stamp_bytes = sizeof(unsigned long long) * 8 * g->slots;
 	HIP_TRY(g, b_q.alloc(qb));
 	HIP_TRY(g, b_ids.alloc(sizeof(uint64_t) * m * k));
 	HIP_TRY(g, b_d.alloc(sizeof(float) * m * k));
 	HIP_TRY(g, b_dc.alloc(sizeof(uint32_t) * m));
-	float* d_q = b_q.as<float>();
-	uint64_t* d_ids = b_ids.as<uint64_t>();
-	float* d_d = b_d.as<float>();
-	uint32_t* d_dc = b_dc.as<uint32_t>();
-	HIP_TRY(g, hipMemcpyAsync(d_q, queries, qb, hipMemcpyHostToDevice, g->stream));
-	HIP_TRY(g, hipMemsetAsync(g->d_error, 0, 2 * sizeof(uint32_t), g->stream));
-	uint32_t err_host = 0;
-	uint32_t cand_cap = graph_first_cand_cap(ef_search);
-	for (;;) {  // until no candidates heap overflows, or its LDS capacity limit (8192) is reached
-		GraphSearchParams p = graph_base_params(g, mode, k, ef_search);
-		p.queries = d_q;
-		p.m = (uint32_t)m;
-		p.cand_cap = cand_cap;
-		p.out_ids = d_ids;
-		p.out_dists = d_d;
-		p.out_distcomps = d_dc;
-		p.error = g->d_error;
-		p.next_query = g->d_error + 1;
-		if (stamps) {
-			if (!b_stamps.p)
-				HIP_TRY(g, b_stamps.alloc(sizeof(unsigned long long) * 8 * g->slots));
-			HIP_TRY(g, hipMemsetAsync(b_stamps.p, 0, sizeof(unsigned long long) * 8 * g->slots, g->stream));
-			p.stamps = b_stamps.as<unsigned long long>();
-		}
-		const size_t lds = graph_lds_bytes(p, cand_cap, gv->d == 0, use_compression != 0);
-		if (lds > kGraphMaxLds)
-			return g->fail(EXPANN_ERR_UNSUPPORTED, "graph search working set exceeds LDS");
-		HIP_TRY(g, hipFuncSetAttribute((const void*)gv->fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-		                               (int)lds));
-		g_graph_attr_gen.fetch_add(1, std::memory_order_relaxed);
-		// as many workgroups as are resident at once (registers and LDS of this instance), each with a
-		// visited array of its own; they pull queries from a counter
-		int per_cu = 0;
-		HIP_TRY(g, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)gv->fn, 64, lds));
-		const uint32_t resident = (uint32_t)std::max(1, per_cu) * (uint32_t)num_cus(g->device);
-		const uint32_t grid = (uint32_t)std::min<size_t>(m, std::min<uint32_t>(g->slots, resident));
-		HIP_TRY(g, hipEventRecord(g->ev0, g->stream));
-		hipLaunchKernelGGL(gv->fn, dim3(grid), dim3(64), lds, g->stream, p);
-		HIP_TRY(g, hipEventRecord(g->ev1, g->stream));
-		HIP_TRY(g, hipGetLastError());
-		HIP_TRY(g, hipMemcpyAsync(&err_host, g->d_error, sizeof(uint32_t), hipMemcpyDeviceToHost,
-		                          g->stream));
-		HIP_TRY(g, hipStreamSynchronize(g->stream));
+	if (stamps)
+		HIP_TRY(g, b_stamps.alloc(stamp_bytes));
+	HIP_TRY(g, hipMemcpyAsync(b_q.p, queries, qb, hipMemcpyHostToDevice, st));
+	GraphSearchParams p = graph_base_params(g, mode, k, ef_search);
+	p.queries = b_q.as<float>();
+	p.m = (uint32_t)m;
+	p.out_ids = b_ids.as<uint64_t>();
+	p.out_dists = b_d.as<float>();
+	p.out_distcomps = b_dc.as<uint32_t>();
+	p.stamps = b_stamps.as<unsigned long long>();
+	// the slot behind those of the device-buffer searches: theirs stay as they are for the next sync
+	uint32_t* ctr = g->d_dev_ctr + (size_t)kGraphMaxOutstanding * kGraphCtrWords;
+	uint32_t* h_ctr = g->h_dev_ctr + (size_t)kGraphMaxOutstanding * kGraphCtrWords;
+	GraphSearchPlan pl;
+	if (int rc = graph_search_plan(g, gv, p, ctr, &pl))
+		return rc;
+	double ms_total = 0;
+	// a launch, the wait for it and the slot read back
+	auto run = [&](bool redo, size_t walked) -> int {
+		if (stamps)
+			HIP_TRY(g, hipMemsetAsync(b_stamps.p, 0, stamp_bytes, st));
+		if (redo)
+			HIP_TRY(g, hipEventRecord(g->ev0, st));
+		if (int rc = redo ? graph_enqueue_redo(g, pl, st, g->ev1) : graph_enqueue_first(g, pl, st, g->ev0, g->ev1))
+			return rc;
+		HIP_TRY(g, hipMemcpyAsync(h_ctr, ctr, sizeof(uint32_t) * kGraphCtrWords, hipMemcpyDeviceToHost, st));
+		HIP_TRY(g, hipStreamSynchronize(st));
 		float ms = 0;
 		HIP_TRY(g, hipEventElapsedTime(&ms, g->ev0, g->ev1));
-		g->last_ms = ms;
-		if (stamps) {  // mean over the workgroups of the grid, per hop
-			std::vector<unsigned long long> st(8 * (size_t)grid);
-			HIP_TRY(g, hipMemcpy(st.data(), b_stamps.p, st.size() * 8, hipMemcpyDeviceToHost));
-			double tot[8] = {0};
-			for (uint32_t b = 0; b < grid; ++b)
-				for (int i = 0; i < 8; ++i)
-					tot[i] += (double)st[8 * (size_t)b + i];
-			const double hops = tot[6] > 0 ? tot[6] : 1, all = tot[0] + tot[1] + tot[2] + tot[3] + tot[4] + tot[5];
-			std::fprintf(stderr,
-			             "graph_search<%d,%s> ef %zu: %.3f ms, %u workgroups, %.1f hops / query, %.1f queue insertions / hop; "
-			             "shader clocks per hop: pop + broadcast %.0f, adjacency + visited %.0f, gathers + scoring %.0f, "
-			             "serial queue update %.0f; per query: setup + descent %.0f, output %.0f; shares %.1f / %.1f / %.1f / "
-			             "%.1f / %.1f / %.1f %%\n",
-			             g->dim, kGraphModeName[mode], ef_search, ms, grid, tot[6] / (double)m, tot[7] / hops,
-			             tot[1] / hops, tot[2] / hops, tot[3] / hops, tot[4] / hops, tot[0] / (double)m, tot[5] / (double)m,
-			             100 * tot[1] / all, 100 * tot[2] / all, 100 * tot[3] / all, 100 * tot[4] / all, 100 * tot[0] / all,
-			             100 * tot[5] / all);
-		}
-		if (!err_host || cand_cap >= 8192)
-			break;
-		cand_cap *= 4;  // a candidates heap overflowed: retry with a larger one
-		if (cand_cap > 8192)
-			cand_cap = 8192;
-		HIP_TRY(g, hipMemsetAsync(g->d_error, 0, 2 * sizeof(uint32_t), g->stream));
-	}
-	HIP_TRY(g, hipMemcpy(ids, d_ids, sizeof(uint64_t) * m * k, hipMemcpyDeviceToHost));
-	HIP_TRY(g, hipMemcpy(dists, d_d, sizeof(float) * m * k, hipMemcpyDeviceToHost));
+		ms_total += ms;
+		return stamps ? graph_print_stamps(g, mode, ef_search, ms, redo ? pl.grid_redo : pl.grid, walked, b_stamps.p)
+		              : EXPANN_OK;
+	};
+	if (int rc = run(false, m))
+		return rc;
+	// this call has waited anyway, so the redo launch goes out only when the first one listed queries for it
+	if (h_ctr[2])
+		if (int rc = run(true, h_ctr[2]))
+			return rc;
+	g->last_ms = ms_total;
+	HIP_TRY(g, hipMemcpy(ids, b_ids.p, sizeof(uint64_t) * m * k, hipMemcpyDeviceToHost));
+	HIP_TRY(g, hipMemcpy(dists, b_d.p, sizeof(float) * m * k, hipMemcpyDeviceToHost));
 	if (distcomps)
-		HIP_TRY(g, hipMemcpy(distcomps, d_dc, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
-	if (err_host)
+		HIP_TRY(g, hipMemcpy(distcomps, b_dc.p, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
+	if (h_ctr[0])
 		return g->fail(EXPANN_ERR_OVERFLOW, "graph search: candidates queue overflowed its LDS capacity");
 	return EXPANN_OK;
 }
@@ -615,11 +678,9 @@ int expann_graph_search_device(expann_graph* g, const float* d_queries, size_t m
 		return rc;
 	if (empty)
 		return EXPANN_OK;
-	const bool use_compression = mode != EXPANN_GRAPH_FP32;
 	HIP_TRY(g, hipSetDevice(g->device));
-	bool any_dim = false;
-	const GraphSearchFn fn = graph_search_device_instance(g->dim, mode, &any_dim);
-	if (!fn)
+	const GraphVariant* gv = graph_variant(g->dim, mode);
+	if (!gv)
 		return g->fail(EXPANN_ERR_UNSUPPORTED, "no graph kernel for this dim");
 	hipStream_t st = stream ? (hipStream_t)stream : g->stream;
 	if (int rc = graph_dev_init(g))
@@ -630,80 +691,29 @@ int expann_graph_search_device(expann_graph* g, const float* d_queries, size_t m
 	if (g->dev_outstanding >= kGraphMaxOutstanding)
 		if (int rc = graph_drain(g))
 			return rc;
-	// the byte copy of the rows is complete before the walk starts, on whichever stream that runs
-	if (mode == EXPANN_GRAPH_RANGED_Q8) {
-		if (int rc = graph_ensure_ranged(g))
-			return rc;
-	} else if (use_compression && !g->d_compressed) {
-		HIP_TRY(g, hipMalloc(&g->d_compressed, g->n * (size_t)g->dim));
-		launch_quantize_simple_u8(g->d_vectors, g->n * (size_t)g->dim, g->d_compressed, g->stream);
-		HIP_TRY(g, hipGetLastError());
-		HIP_TRY(g, hipStreamSynchronize(g->stream));
-	}
-	GraphSearchParams p = graph_base_params(g, mode, k, ef_search);
-	const uint32_t cand_cap = g->opt_cand_cap ? (uint32_t)g->opt_cand_cap : graph_first_cand_cap(ef_search);
-	const size_t lds = graph_lds_bytes(p, cand_cap, any_dim, use_compression);
-	if (lds > kGraphMaxLds)
-		return g->fail(EXPANN_ERR_UNSUPPORTED, "graph search working set exceeds LDS");
-	// the redo launch's heap: the largest power of two up to 8192 whose working set fits
-	uint32_t redo_cap = (uint32_t)g->opt_redo_cap;
-	if (!redo_cap)
-		for (redo_cap = 8192; redo_cap > cand_cap && graph_lds_bytes(p, redo_cap, any_dim, use_compression) > kGraphMaxLds;)
-			redo_cap /= 2;
-	const bool redo = redo_cap > cand_cap;  // (else an overflow of the first launch is final)
-	const size_t lds_redo = redo ? graph_lds_bytes(p, redo_cap, any_dim, use_compression) : 0;
-	if (lds_redo > kGraphMaxLds)
-		return g->fail(EXPANN_ERR_UNSUPPORTED, "graph search: the working set at \"redo_capacity\" exceeds LDS");
-	uint32_t resident = 0, resident_redo = 0;
-	if (int rc = graph_plan(g, (const void*)fn, lds, &resident))
+	if (int rc = graph_ensure_bytes(g, mode))
 		return rc;
-	if (redo) {
-		if (int rc = graph_plan(g, (const void*)fn, lds_redo, &resident_redo))
-			return rc;
-		if (sizeof(uint32_t) * m > g->d_redo_list.bytes || !g->d_redo_list) {  // (a grow frees the list in use)
-			HIP_TRY(g, graph_wait_outstanding(g));
-			HIP_TRY(g, g->d_redo_list.ensure(sizeof(uint32_t) * m));
-		}
-	}
-	uint32_t* ctr = g->d_dev_ctr + (size_t)g->dev_outstanding * kGraphCtrWords;
-	HIP_TRY(g, hipMemsetAsync(ctr, 0, sizeof(uint32_t) * kGraphCtrWords, st));
+	GraphSearchParams p = graph_base_params(g, mode, k, ef_search);
 	p.queries = d_queries;
 	p.m = (uint32_t)m;
-	p.cand_cap = cand_cap;
 	p.out_ids = d_ids;
 	p.out_dists = d_dists;
 	p.out_distcomps = d_distcomps;
-	p.error = ctr;
-	p.next_query = ctr + 1;
 	p.distcomps_total = g->d_dc_total;
-	if (redo) {
-		p.redo_list = g->d_redo_list;
-		p.redo_count = ctr + 2;
-	}
-	const uint32_t grid = (uint32_t)std::min<size_t>(m, std::min<uint32_t>(g->slots, resident));
-	HIP_TRY(g, hipEventRecord(g->ev_dev[0], st));
-	hipLaunchKernelGGL(fn, dim3(grid), dim3(64), lds, st, p);
-	HIP_TRY(g, hipEventRecord(g->ev_dev[1], st));
-	if (redo) {
-		// the overflowed queries again, at the larger heap: sized without knowing how many there are -- the
-		// workgroups that find the list empty leave after one atomic
-		GraphSearchParams r = p;
-		r.cand_cap = redo_cap;
-		r.redo_list = nullptr;  // an overflow here raises the error flag
-		r.redo_count = nullptr;
-		r.query_map = g->d_redo_list;
-		r.m_dev = ctr + 2;
-		r.next_query = ctr + 3;
-		const uint32_t grid_redo = (uint32_t)std::min<size_t>(m, std::min<uint32_t>(g->slots, resident_redo));
-		hipLaunchKernelGGL(fn, dim3(grid_redo), dim3(64), lds_redo, st, r);
-		HIP_TRY(g, hipEventRecord(g->ev_dev[2], st));
-	}
-	HIP_TRY(g, hipGetLastError());
+	GraphSearchPlan pl;
+	if (int rc = graph_search_plan(g, gv, p, g->d_dev_ctr + (size_t)g->dev_outstanding * kGraphCtrWords, &pl))
+		return rc;
+	// both launches go out without a wait: the redo launch finds its queries, or none, in device memory
+	if (int rc = graph_enqueue_first(g, pl, st, g->ev_dev[0], g->ev_dev[1]))
+		return rc;
+	if (pl.has_redo)
+		if (int rc = graph_enqueue_redo(g, pl, st, g->ev_dev[2]))
+			return rc;
 	g->dev_stream = st;
 	++g->dev_outstanding;
 	++g->stat_deferred;
 	g->dev_timed = true;
-	g->dev_timed_redo = redo;
+	g->dev_timed_redo = pl.has_redo;
 	return EXPANN_OK;
 }
 

@@ -75,7 +75,7 @@ struct GraphSearchParams {
 	unsigned long long* stamps;
 	uint32_t dim;                 // run-time-dim instance (D = 0) only: the row length (the others have it as D)
 	float q_scale, q_offset;      // kGraphRangedQ8 only: the rows' quantiser, applied to the query as it is staged
-	// Device-buffer searches (expann_graph_search_device): read by the DEV instances only, and inert when nullptr.
+	// Overflow per query, for the redo launch; all inert when nullptr.
 	// redo_list != nullptr: a walk that met a full candidates heap appends its query number to
 	// redo_list[atomicAdd(redo_count, 1)] instead of raising `error` (its output row is still written).
 	uint32_t* redo_list;          // [m]
@@ -533,14 +533,12 @@ template <int D> constexpr int graph_rows_u8() { return D == 0 ? kGraphAnyRows :
 // D = 0: the run-time-dim instance (p.dim); the query and its bytes sit in LDS behind ndist
 // MODE: kGraphF32 / kGraphU8Cast / kGraphRangedQ8; the two byte modes are one walk (COMPRESSED), the ranged
 // one differs where the query's bytes are made
-// waves per SIMD the run-time-dim instances are held to: 3; the byte walks of the device-buffer instances 4 -- their
-// host-buffer twins fit 128 registers without being asked, the extra parameters would cost these the fourth wave
-template <int MODE, bool DEV> constexpr int graph_any_dim_waves() { return (DEV && MODE != kGraphF32) ? 4 : 3; }
+// waves per SIMD the run-time-dim instances are held to: fp32 3, the byte walks 4 (128 registers; left to itself the
+// compiler takes one or two more and loses the fourth wave)
+template <int MODE> constexpr int graph_any_dim_waves() { return MODE != kGraphF32 ? 4 : 3; }
 
-// DEV: the instances of the device-buffer searches (redo list, query indirection, distcomps total); the others do
-// not contain that code and ignore its parameters
-template <int D, int MODE, int DBG = 0, bool DEV = false>
-__global__ __launch_bounds__(64, D == 0 ? (graph_any_dim_waves<MODE, DEV>()) : ((MODE != kGraphF32 && D <= 128) ? 4 : 1)) void graph_search_kernel(GraphSearchParams p) {
+template <int D, int MODE, int DBG = 0>
+__global__ __launch_bounds__(64, D == 0 ? graph_any_dim_waves<MODE>() : ((MODE != kGraphF32 && D <= 128) ? 4 : 1)) void graph_search_kernel(GraphSearchParams p) {
 	constexpr bool COMPRESSED = MODE != kGraphF32, RANGED = MODE == kGraphRangedQ8;
 	constexpr int DPL = D ? D / 16 : 1;
 	constexpr int NW = D ? D / 64 : 1;
@@ -584,7 +582,7 @@ __global__ __launch_bounds__(64, D == 0 ? (graph_any_dim_waves<MODE, DEV>()) : (
 		if (lane == 0)
 			qi = atomicAdd(p.next_query, 1u);
 		qi = (uint32_t)__builtin_amdgcn_readfirstlane((int)qi);
-		if (DEV && p.query_map) {  // a redo launch: the queries the list names, as many as the device counted
+		if (p.query_map) {  // a redo launch: the queries the list names, as many as the device counted
 			const uint32_t m_redo = *p.m_dev;
 			if (qi >= (m_redo < p.m ? m_redo : p.m))
 				break;
@@ -849,12 +847,9 @@ __global__ __launch_bounds__(64, D == 0 ? (graph_any_dim_waves<MODE, DEV>()) : (
 				const float dn = ndist[j];
 				if (n_near < p.ef || dn < nearest[0].d) {
 					const md_pair e{dn, nlist[j]};
-					if (n_cand >= p.cand_cap) {
-						if (DEV)
-							q_overflowed = true;
-						else
-							overflowed = 1;
-					} else
+					if (n_cand >= p.cand_cap)
+						q_overflowed = true;
+					else
 						coop_push<false>(candidates, n_cand, e, lane, p.debug & 1);
 					coop_push<true>(nearest, n_near, e, lane, p.debug & 1);
 					wave_lds_sync();
@@ -896,16 +891,14 @@ __global__ __launch_bounds__(64, D == 0 ? (graph_any_dim_waves<MODE, DEV>()) : (
 			p.out_distcomps[qi] = distcomps;
 		// an overflowed walk goes on the redo list when there is one (its row is rewritten by the redo launch, which
 		// also counts its distcomps), else it raises the launch's error flag
-		if constexpr (DEV) {
-			const bool to_redo = q_overflowed && p.redo_list;
-			if (q_overflowed && !to_redo)
-				overflowed = 1;
-			if (lane == 0) {
-				if (to_redo)
-					p.redo_list[atomicAdd(p.redo_count, 1u)] = qi;
-				else if (p.distcomps_total)
-					atomicAdd(p.distcomps_total, (unsigned long long)distcomps);
-			}
+		const bool to_redo = q_overflowed && p.redo_list;
+		if (q_overflowed && !to_redo)
+			overflowed = 1;
+		if (lane == 0) {
+			if (to_redo)
+				p.redo_list[atomicAdd(p.redo_count, 1u)] = qi;
+			else if (p.distcomps_total)
+				atomicAdd(p.distcomps_total, (unsigned long long)distcomps);
 		}
 		if (bits) {  // the set goes back to all-zero: 16 bytes per lane and store, nothing waits for them
 			uint4* w = reinterpret_cast<uint4*>(vbits);
@@ -925,10 +918,5 @@ __global__ __launch_bounds__(64, D == 0 ? (graph_any_dim_waves<MODE, DEV>()) : (
 			atomicAdd(p.error, 1u);
 	}
 }
-
-// the DEV instance of (dim, mode) -- compiled for that dim, else the run-time-dim one; they are a translation unit
-// of their own (expann_graph_device.hip), so the build compiles them next to the others
-using GraphSearchFn = void (*)(GraphSearchParams);
-GraphSearchFn graph_search_device_instance(int dim, int mode, bool* run_time_dim);
 
 }  // namespace expann

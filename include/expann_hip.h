@@ -255,7 +255,8 @@ const char* expann_graph_last_error(const expann_graph* g);
 int expann_graph_search(expann_graph* g, const float* queries, size_t m, size_t k,
                         size_t ef_search, int use_compression, uint64_t* ids, float* dists,
                         uint32_t* distcomps);
-/* device time of the last expann_graph_search's traversal kernel, milliseconds */
+/* device time of the last search's traversal kernel, milliseconds: its first launch plus its redo launch when
+ * there was one (below), after a host-buffer call as after an expann_graph_sync */
 double expann_graph_last_kernel_ms(const expann_graph* g);
 
 /* how the bottom layer of the walk scores a row */
@@ -275,7 +276,11 @@ enum expann_graph_compression {
  * the queries converted by the same scale_factor / offset inside the walk kernel (components outside the
  * rows' range clamp).  Errors, all before the device is touched: mode outside 0..2 EXPANN_ERR_INVALID_ARG;
  * modes 1 and 2 need dim % 64 == 0 (EXPANN_ERR_UNSUPPORTED).  Mode 2 on rows whose scale_factor is not
- * finite and positive (all components equal): EXPANN_ERR_INVALID_ARG, nothing is walked. */
+ * finite and positive (all components equal): EXPANN_ERR_INVALID_ARG, nothing is walked.
+ * A walk whose candidates heap overflows is walked again by the redo launch of expann_graph_search_device (below),
+ * which this call enqueues only when there are such queries; EXPANN_ERR_OVERFLOW when one overflows there too or
+ * there is no larger capacity to go to (the rows of those queries are what the last walk left).  A larger capacity
+ * whose working set exceeds the LDS is never tried: the redo launch runs at the largest that fits. */
 int expann_graph_search_mode(expann_graph* g, const float* queries, size_t m, size_t k, size_t ef_search,
                              int mode, uint64_t* ids, float* dists, uint32_t* distcomps);
 /* scale_factor / offset of the handle's affine quantiser; builds the int8 copy if it does not exist yet
@@ -287,12 +292,12 @@ int expann_graph_ranged_params(expann_graph* g, float* scale_factor, float* offs
  * distcomps [m] (may be NULL) in device memory: same arguments, same checks in the same order, same error codes,
  * all before the device is touched; m == 0 is EXPANN_OK and enqueues nothing.  The call ENQUEUES on `stream` (a
  * hipStream_t; NULL = the handle's own) and returns without waiting for it: the resets of its counters, the walk
- * at the heap capacity the host-buffer call starts with, and a REDO launch that walks only the queries whose
+ * at the first heap capacity, and a REDO launch that walks only the queries whose
  * candidates heap overflowed again, at the largest power-of-two capacity up to 8192 whose working set fits the
  * LDS, and overwrites their rows (sized without knowing their number: with none, its workgroups leave after one
- * atomic).  A walk that does not overflow never looks at the capacity, so ids, distances and distcomps equal the
- * host-buffer call's, whose answer to an overflow is to walk the whole batch again.  When the redo capacity is not
- * larger than the first launch's there is no redo launch and an overflow is final.  In steady state -- the same
+ * atomic).  A walk that does not overflow never looks at the capacity, so ids, distances and distcomps do not
+ * depend on which launch served a query; the host-buffer call plans and launches the same way.  When the redo
+ * capacity is not larger than the first launch's there is no redo launch and an overflow is final.  In steady state -- the same
  * kernel instance, a working set and an m no larger than seen before -- a call makes no allocation, no copy
  * between host and device, no attribute or occupancy query and no synchronisation.
  * expann_graph_sync waits for the stream of the last such search and reports on all of them since the previous
@@ -307,11 +312,11 @@ int expann_graph_ranged_params(expann_graph* g, float* scale_factor, float* offs
 int expann_graph_search_device(expann_graph* g, const float* d_queries, size_t m, size_t k, size_t ef_search,
                                int mode, uint64_t* d_ids, float* d_dists, uint32_t* d_distcomps, void* stream);
 int expann_graph_sync(expann_graph* g);
-/* options of the device-buffer path only (0 = auto): "cand_capacity" = the first launch's heap, "redo_capacity" =
- * the redo launch's (at most 8192); a power of two >= 8, anything else -- and an unknown name -- is
- * EXPANN_ERR_INVALID_ARG. */
+/* options of both entry points (0 = auto): "cand_capacity" = the first launch's heap, "redo_capacity" = the redo
+ * launch's (at most 8192); a power of two >= 8, anything else -- and an unknown name -- is EXPANN_ERR_INVALID_ARG. */
 int expann_graph_set_option(expann_graph* g, const char* name, long value);
-/* "redo_queries" = queries the redo launches served, over the searches the last expann_graph_sync checked;
+/* Device-buffer searches only (a host-buffer call changes none of them): "redo_queries" = queries the redo
+ * launches served, over the searches the last expann_graph_sync checked;
  * "redo_overflows" = searches since create that ended in EXPANN_ERR_OVERFLOW; "deferred_searches" = device-buffer
  * searches since create; "distcomps" = distance evaluations of all device-buffer searches since create, as of the
  * last sync; "redo_kernel_ns" = device time of the last search's redo launch, as of the last sync.  An unknown

@@ -1,5 +1,7 @@
 """Host-to-host latency of a graph search: host buffers (expann_graph_search_mode) against device buffers
-(expann_graph_search_device + expann_graph_sync), on one MI355X.
+(expann_graph_search_device + expann_graph_sync), on one MI355X.  The two are entry points of one search path (one
+set of kernel instances, one plan, the same launches), so their kernel ms should agree; what differs is the staging
+and the host waits around them.
 
     python profiles/graph_device_latency.py [--rows 100000] [--parent-lib DIR] > profiles/graph_device_latency.txt
 
@@ -9,9 +11,10 @@ m in {1, 32, 1000, 10000}, k = 10, ef = 60, modes 0 and 1, alternating within th
   (b) expann_graph_search_device + expann_graph_sync on resident torch tensors,
   (c) 16 device searches and one sync, divided by 16,
 every shape warmed up first, at least 200 calls per point or at least 0.5 s; kernel ms of (a) and (b) from the
-handle's events, and the redo launch's share of (b) (no walk overflows at these shapes: it finds an empty list).
+handle's events, and the redo launch's share of (b) (no walk overflows at these shapes: it finds an empty list;
+(a) reads the count after its first launch and does not enqueue one).
 
-Part 2 (--parent-lib DIR, a directory holding another build's libexpann_hip.so): the host-buffer path's kernel
+Part 2 (--parent-lib DIR, a directory holding another build's libexpann_hip.so): the host-buffer call's kernel
 time in the C4 shape of `bench.py --workload c4` (1 M rows, M = 60, ef_construction = 480, 10 k queries, k = 10,
 ef = 60), the other build and this one alternating through expann_graph_tool on one index file."""
 import argparse
@@ -55,7 +58,8 @@ def read_index_csr(path):
     take("QQ"), take("ff"), take("Q"), take("BB")
     n_layers, n = take("Q"), take("Q")
     for _ in range(n):
-        pos += 4 * take("Q")
+        d = take("Q")
+        pos += 4 * d
     assert take("Q") == n
     rec = np.dtype([("d", "<f4"), ("id", "<u8")])
     lists = [[] for _ in range(n_layers)]

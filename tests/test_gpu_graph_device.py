@@ -1,7 +1,8 @@
 """Graph search on device buffers (expann_graph_search_device / expann_graph_sync and the engine calls on top):
 queries and results are torch tensors, the search is enqueued on a torch stream, and ids, distance bits and
 per-query distcomps must equal the oracle's walk of the same index file -- whichever launch served a query (the
-first one, or the redo launch that walks the overflowed queries again at the larger heap).  The yardsticks are
+first one, or the redo launch that walks the overflowed queries again at the larger heap), and whichever entry
+point asked: the host-buffer call (expann_graph_search_mode) rides the same launches.  The yardsticks are
 oracle.Graph(index).query_k for modes 0 and 1 and graph_ranged_helpers.ranged_expected for mode 2, never the
 device path itself."""
 import ctypes as C
@@ -220,6 +221,78 @@ def test_overflow_is_reported_and_leaves_the_handle_clean(world, stream):
     for mode in (0, 1):  # visited sets and counters were left clean
         _search_and_check(world, 128, h, mode, 40, stream)
     assert _stat(L, h, "redo_overflows") == overflows + 1
+
+
+def _host_call_and_check(world, d, h, mode, ef, what, m=M_PARITY, k=K):
+    """a host-buffer call (expann_graph_search_mode) that must succeed and equal the oracle"""
+    from graph_ranged_helpers import search_mode
+    L, w = world.L, world.dim(d)
+    rc, ids, dists, dc = search_mode(L, h, w["q"][:m], k, ef, mode)
+    assert rc == 0, (what, L.expann_graph_last_error(h))
+    _assert_equal((ids, dists, dc), world.expected(d, mode, k, ef), m, what)
+
+
+@pytest.mark.parametrize("d,mode", [(128, 0), (128, 1), (192, 0)])
+def test_host_buffer_call_redoes_overflowed_queries(world, d, mode):
+    """a heap of 8 overflows in the first launch of a host-buffer call; without a redo launch that is final
+    (EXPANN_ERR_OVERFLOW), so rc == 0 with the oracle's rows shows that the redo launch served those queries"""
+    L, h = world.L, world.dim(d)["h"]
+    assert L.expann_graph_set_option(h, b"cand_capacity", 8) == 0
+    try:
+        _host_call_and_check(world, d, h, mode, 40, "heap of 8")
+        assert L.expann_graph_last_kernel_ms(h) > 0
+    finally:
+        assert L.expann_graph_set_option(h, b"cand_capacity", 0) == 0
+    _host_call_and_check(world, d, h, mode, 40, "automatic capacity")
+
+
+def test_host_buffer_call_reports_a_final_overflow(world, stream):
+    from expann_amd import _lib
+    from graph_ranged_helpers import search_mode
+    L, w = world.L, world.dim(128)
+    h = w["h"]
+    assert L.expann_graph_set_option(h, b"cand_capacity", 8) == 0
+    assert L.expann_graph_set_option(h, b"redo_capacity", 16) == 0
+    try:
+        rc, _, _, _ = search_mode(L, h, w["q"][:M_PARITY], K, 40, 0)
+        assert rc == _lib.ERR_OVERFLOW
+        assert b"overflow" in L.expann_graph_last_error(h)
+    finally:
+        assert L.expann_graph_set_option(h, b"cand_capacity", 0) == 0
+        assert L.expann_graph_set_option(h, b"redo_capacity", 0) == 0
+    # visited sets and counters were left clean, for both entry points
+    _host_call_and_check(world, 128, h, 0, 40, "host-buffer call after the overflow")
+    _search_and_check(world, 128, h, 0, 40, stream)
+
+
+def test_entry_points_keep_their_reports_apart(world, stream):
+    """a device search that ends in overflow, not yet synced; a host-buffer call in between succeeds and neither
+    takes that report nor adds to the device-buffer statistics; the next sync reports the overflow exactly once"""
+    from expann_amd import _lib
+    L, w = world.L, world.dim(128)
+    h = w["h"]
+    assert L.expann_graph_sync(h) == 0
+    assert L.expann_graph_set_option(h, b"cand_capacity", 8) == 0
+    assert L.expann_graph_set_option(h, b"redo_capacity", 16) == 0
+    try:
+        rc, ids, dists, dc = _enqueue(L, h, w["tq"], M_PARITY, K, 40, 0, stream)
+        assert rc == 0, L.expann_graph_last_error(h)
+    finally:
+        assert L.expann_graph_set_option(h, b"cand_capacity", 0) == 0
+        assert L.expann_graph_set_option(h, b"redo_capacity", 0) == 0
+    deferred, distcomps = _stat(L, h, "deferred_searches"), _stat(L, h, "distcomps")
+    _host_call_and_check(world, 128, h, 0, 40, "host-buffer call before the sync")
+    assert _stat(L, h, "deferred_searches") == deferred
+    assert _stat(L, h, "distcomps") == distcomps
+    assert L.expann_graph_sync(h) == _lib.ERR_OVERFLOW
+    assert b"overflow" in L.expann_graph_last_error(h)
+    assert L.expann_graph_sync(h) == 0
+    assert _stat(L, h, "deferred_searches") == deferred
+    # the device total behind "distcomps" does not see a host-buffer call either
+    distcomps = _stat(L, h, "distcomps")
+    _host_call_and_check(world, 128, h, 0, 40, "host-buffer call after the sync")
+    _search_and_check(world, 128, h, 0, 40, stream)
+    assert _stat(L, h, "distcomps") - distcomps == int(world.expected(128, 0, K, 40)[2][:M_PARITY].sum())
 
 
 def test_searches_in_flight(world, stream):
