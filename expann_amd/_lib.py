@@ -38,6 +38,7 @@ ABI_SYMBOLS = [
     "expann_graph_search_mode", "expann_graph_ranged_params", "expann_antitopo_set_compression",
     "expann_graph_search_device", "expann_graph_sync", "expann_graph_set_option", "expann_graph_get_stat",
     "expann_antitopo_query_device", "expann_antitopo_sync",
+    "expann_set_row_filter", "expann_set_row_filter_device", "expann_clear_row_filter",
 ]
 
 
@@ -262,6 +263,13 @@ def load():
         L.expann_get_stat.argtypes = [vp, C.c_char_p, C.POINTER(C.c_uint64)]
         L.expann_spec_rank_auto.restype = C.c_uint32
         L.expann_spec_rank_auto.argtypes = [C.c_size_t, C.c_uint32]
+    if hasattr(L, "expann_set_row_filter"):  # (as above: an older build has no row filter)
+        L.expann_set_row_filter.restype = C.c_int
+        L.expann_set_row_filter.argtypes = [vp, vp, sz]
+        L.expann_set_row_filter_device.restype = C.c_int
+        L.expann_set_row_filter_device.argtypes = [vp, vp, sz, vp]
+        L.expann_clear_row_filter.restype = C.c_int
+        L.expann_clear_row_filter.argtypes = [vp]
     _lib = L
     return L
 

@@ -34,6 +34,7 @@
 #include "scan_int8.hpp"
 #include "scan_int8_any.hpp"
 #include "scan_gemm_i8kl.hpp"
+#include "filter_rows.hpp"
 #include "score_ids.hpp"
 #include "select.hpp"
 
@@ -49,11 +50,14 @@ constexpr uint32_t kMaxCap = 16384;      // keys per query that fit the select k
 constexpr size_t kMaxQueriesPerPass = 32768;
 constexpr int kEventPairs = 64;
 constexpr uint32_t kAsyncRing = 256;  // outstanding searches of the deferred-check mode
+constexpr uint32_t kFilterListCap = kMaxCap;  // rows in the row filter's list (the longest candidate list)
 
 struct Level {
 	uint32_t n_groups_sel;
 	uint32_t group_stride;
 	uint32_t classmin_blocks = 0;  // > 0: level 0 keeps class minima (scan_f32.hpp), this many workgroups
+	uint32_t list_rows = 0;        // > 0 (row filter, level 0): the keys of this many rows of the filter's list ...
+	uint32_t list_step = 1;        // ... every list_step-th entry
 };
 
 }  // namespace
@@ -125,6 +129,24 @@ struct expann_index {
 	DevPtr<float> d_qnrm;            // [m_alloc] ||q||^2 (fp16 form, inner product: of the filter-side query c_q q)
 	DevPtr<float> d_qscale;          // [m_alloc] c_q: the power of two the fp16 filter sees a query multiplied by (inner product; L2: 1)
 	float f16_scale = 0.0f;          // power of two; 0 = not built
+	size_t f16_n_pad = 0;            // rows of the fp16 copy and of its row-term arrays (whole tiles)
+	// row filter (expann_set_row_filter): the engine's copy of the bitmap, the allowed rows'
+	// count, an ascending list of them (complete up to kFilterListCap rows, an even sample beyond) and the masked
+	// copies of the fp16 forms' row terms (NaN on every disallowed row), made lazily after ensure_f16
+	bool filter_on = false;
+	DevPtr<uint32_t> d_filter_bits;  // [filter_words]: whole 128-row tiles, zero from row n on
+	size_t filter_words = 0;
+	DevPtr<uint32_t> d_filter_stat;  // [2 + kFilterSegs]: count, OR of the words, per-segment counts
+	DevPtr<uint32_t> d_filter_list;  // [kFilterListCap]
+	uint32_t filter_list_len = 0, filter_list_stride = 1;
+	size_t n_allowed = 0;
+	uint32_t filter_residues = 0;    // bit r: some allowed row has row % 32 == r
+	DevPtr<float> d_bnorm_f16_m;     // [f16_n_pad] d_bnorm_f16 under the filter
+	DevPtr<float> d_bns_f16_m;       // [f16_n_pad] d_bns_f16 under the filter
+	bool filter_terms_valid = false;
+	// the row terms the fp16 forms read: the masked copies while a filter is set
+	const float* bnorm_f16() const { return filter_on ? d_bnorm_f16_m.p : d_bnorm_f16.p; }
+	const float* bns_f16() const { return filter_on ? d_bns_f16_m.p : d_bns_f16.p; }
 	float f16_bnmax = 0.0f;          // max ||b||^2 (host copy lives in d_bnmax[2])
 	// int8 filter of fp32 rows (scan_gemm_i8f.hpp), built lazily beside the fp16 copy (whose sampled pass
 	// gives its thresholds) and dropped with it
@@ -203,10 +225,14 @@ struct ScanVariant {
 	bool ip;
 	ScanFn fn;
 	const char* name;
+	ScanFn fn_bits = nullptr;  // the instance that reads the row filter's bitmap (kRowsBitmap)
+	ScanFn fn_list = nullptr;  // the instance that walks a list of rows (kRowsList)
 };
 #define SCAN_V(D, TQ)                                                                      \
-	{D, TQ, false, scan_filter_f32_kernel<D, TQ, false>, "scan_filter_f32<" #D "," #TQ ",L2>"}, \
-	{D, TQ, true, scan_filter_f32_kernel<D, TQ, true>, "scan_filter_f32<" #D "," #TQ ",IP>"}
+	{D, TQ, false, scan_filter_f32_kernel<D, TQ, false>, "scan_filter_f32<" #D "," #TQ ",L2>", \
+	 scan_filter_f32_kernel<D, TQ, false, kRowsBitmap>, scan_filter_f32_kernel<D, TQ, false, kRowsList>}, \
+	{D, TQ, true, scan_filter_f32_kernel<D, TQ, true>, "scan_filter_f32<" #D "," #TQ ",IP>", \
+	 scan_filter_f32_kernel<D, TQ, true, kRowsBitmap>, scan_filter_f32_kernel<D, TQ, true, kRowsList>}
 const ScanVariant kScanF32[] = {
     SCAN_V(64, 1),  SCAN_V(64, 4),  SCAN_V(64, 16), SCAN_V(128, 1), SCAN_V(128, 2),
     SCAN_V(128, 4), SCAN_V(128, 8), SCAN_V(128, 16), SCAN_V(256, 1), SCAN_V(256, 4),
@@ -216,8 +242,10 @@ const ScanVariant kScanF32[] = {
 #undef SCAN_V
 // every other f32 dim (multiples of 16 up to kMaxAnyDim): the run-time-dim scan (d = 0 in the table)
 #define SCAN_ANY_V(TQ)                                                                           \
-	{0, TQ, false, scan_filter_f32_any_kernel<TQ, false>, "scan_filter_f32_any<" #TQ ",L2>"},   \
-	{0, TQ, true, scan_filter_f32_any_kernel<TQ, true>, "scan_filter_f32_any<" #TQ ",IP>"}
+	{0, TQ, false, scan_filter_f32_any_kernel<TQ, false>, "scan_filter_f32_any<" #TQ ",L2>",   \
+	 scan_filter_f32_any_kernel<TQ, false, kRowsBitmap>, scan_filter_f32_any_kernel<TQ, false, kRowsList>}, \
+	{0, TQ, true, scan_filter_f32_any_kernel<TQ, true>, "scan_filter_f32_any<" #TQ ",IP>",     \
+	 scan_filter_f32_any_kernel<TQ, true, kRowsBitmap>, scan_filter_f32_any_kernel<TQ, true, kRowsList>}
 const ScanVariant kScanF32Any[] = {SCAN_ANY_V(1), SCAN_ANY_V(2), SCAN_ANY_V(4)};
 #undef SCAN_ANY_V
 inline bool any_dim_f32(int d) { return d >= 16 && d <= kMaxAnyDim && d % 16 == 0; }
@@ -384,6 +412,41 @@ std::vector<Level> plan_levels(size_t n, size_t k, uint32_t cap, long ratio_opt)
 		lv.push_back({sel, std::max<uint32_t>(1, n_groups / sel)});
 	}
 	lv.push_back({n_groups, 1});
+	return lv;
+}
+
+// The same ladder under a row filter.  It is planned on the ALLOWED rows -- a level's survivors
+// are ~ratio * k when it holds ratio times the allowed rows of the level before -- and stretched by n / n_allowed
+// to the physical groups a strided scan must visit to meet that many.  Level 0 cannot be a strided scan: a
+// sample of 1 024 rows holds 1 024 p allowed ones, fewer than k under a selective filter (+inf thresholds, every
+// list overflows).  It takes its rows from the filter's list instead -- an even sample of the allowed rows
+// whatever their share and position.  n_allowed <= cap: the list is complete and is the whole search (one level,
+// every allowed row's exact key, the select finishes).
+std::vector<Level> plan_levels_filtered(size_t n, size_t n_allowed, uint32_t list_len, size_t k, uint32_t cap,
+                                        long ratio_opt) {
+	std::vector<Level> lv;
+	if ((n_allowed + kRowsPerGroup - 1) / kRowsPerGroup * kRowsPerGroup <= cap && list_len == n_allowed) {
+		Level l{(uint32_t)((n_allowed + kRowsPerGroup - 1) / kRowsPerGroup), 1};
+		l.list_rows = (uint32_t)n_allowed;
+		lv.push_back(l);
+		return lv;
+	}
+	const uint32_t n_groups = (uint32_t)((n + kRowsPerGroup - 1) / kRowsPerGroup);
+	lv = plan_levels(n_allowed, k, cap, ratio_opt);
+	const double stretch = (double)n / (double)n_allowed;
+	Level& l0 = lv.front();
+	l0.list_rows = std::min<uint32_t>(l0.n_groups_sel * kRowsPerGroup, list_len);
+	l0.list_step = std::max<uint32_t>(1, list_len / l0.list_rows);
+	l0.n_groups_sel = (l0.list_rows + kRowsPerGroup - 1) / kRowsPerGroup;
+	l0.group_stride = 1;
+	for (size_t i = 1; i < lv.size(); ++i) {
+		const uint32_t sel = (uint32_t)std::min<double>(n_groups, std::ceil(lv[i].n_groups_sel * stretch));
+		lv[i].n_groups_sel = sel;
+		lv[i].group_stride = std::max<uint32_t>(1, n_groups / sel);
+	}
+	if (lv.size() < 2)
+		lv.push_back(Level{n_groups, 1});
+	lv.back() = Level{n_groups, 1};
 	return lv;
 }
 
@@ -616,7 +679,42 @@ int ensure_f16(expann_index* h, const GemmF16Variant* gf, hipStream_t st) {
 	HIP_TRY(h, hipGetLastError());
 	HIP_TRY(h, hipStreamSynchronize(st));  // tmp/nrm are freed on return
 	h->f16_scale = scale;
+	h->f16_n_pad = n_pad;
 	return EXPANN_OK;
+}
+
+// The fp16 forms' row terms under the row filter: NaN on every disallowed row, made after ensure_f16 and again
+// whenever the filter changed (one pass over n_pad floats per array, on the search's stream)
+int ensure_filter_terms(expann_index* h, hipStream_t st) {
+	if (!h->filter_on || !h->d_bnorm_f16 || (h->filter_terms_valid && h->d_bnorm_f16_m))
+		return EXPANN_OK;
+	if (h->f16_n_pad > h->filter_words * 32)
+		return h->fail(EXPANN_ERR_HIP, "row filter: the bitmap is shorter than the fp16 copy");  // (both are whole 128-row tiles)
+	if (!h->d_bnorm_f16_m) {
+		HIP_TRY(h, hipMalloc(&h->d_bnorm_f16_m, sizeof(float) * h->f16_n_pad));
+		HIP_TRY(h, hipMalloc(&h->d_bns_f16_m, sizeof(float) * h->f16_n_pad));
+	}
+	const dim3 grid((uint32_t)std::min<size_t>((h->f16_n_pad + kBlock - 1) / kBlock, 4096));
+	hipLaunchKernelGGL(filter_row_terms_kernel, grid, dim3(kBlock), 0, st, h->d_filter_bits.as<const uint32_t>(),
+	                   h->d_bnorm_f16.as<const float>(), h->d_bnorm_f16_m.as<float>(), (uint32_t)h->f16_n_pad);
+	hipLaunchKernelGGL(filter_row_terms_kernel, grid, dim3(kBlock), 0, st, h->d_filter_bits.as<const uint32_t>(),
+	                   h->d_bns_f16.as<const float>(), h->d_bns_f16_m.as<float>(), (uint32_t)h->f16_n_pad);
+	HIP_TRY(h, hipGetLastError());
+	h->filter_terms_valid = true;
+	return EXPANN_OK;
+}
+// forget everything the filter derived (the rows changed, or the handle is rebuilt)
+void drop_row_filter(expann_index* h) {
+	h->filter_on = false;
+	h->filter_terms_valid = false;
+	h->d_bnorm_f16_m.reset();
+	h->d_bns_f16_m.reset();
+	h->d_filter_bits.reset();
+	h->filter_words = 0;
+	h->filter_list_len = 0;
+	h->filter_list_stride = 1;
+	h->n_allowed = 0;
+	h->filter_residues = 0;
 }
 
 const GemmVariant* pick_gemm(const expann_index* h, size_t m) {
@@ -1479,16 +1577,35 @@ int sampled_pass_f16(expann_index* h, const GemmF16Variant* gvf, size_t m, size_
 		tp.i8_inv_2s2 = h->i8f.inv_2s2;
 	}
 
+	// Row filter: the sample sees allowed rows only (masked row terms), so it is sized by them.  The thresholds
+	// are the k-th largest of the class maxima, a class being (chunk, row mod 32) -- (workgroup, row mod RPS) in
+	// the fused pass.  They are finite when k classes hold an allowed row and tight when the sample's best rows
+	// seldom share a class: the sample is widened until it holds 8 k allowed rows in expectation (the unfiltered
+	// plan's 8 k classes of >= 1 row), and the classes a filter can fill -- it may leave whole residues empty, all
+	// but one when it allows every 32nd row -- must number 2 k: the k-th of C classes is then reached after
+	// C ln(C / (C - k)) <= 1.39 k rows of the sample, lists 1.4 times the usual at worst.  Otherwise no sampled
+	// pass: the ladder (plan_levels_filtered) serves.
+	const bool filt = h->filter_on;
+	const double dens = filt ? (double)h->n_allowed / (double)h->n : 1.0;
+	const size_t need_classes = filt ? 2 * k : 8 * k;
 	const DirectF16Variant* dvs = (h->opt_scan_kernel == 0 && !i8f) ? pick_direct_f16(h->dim, m) : nullptr;
 	if (dvs && dvs->sample) {
 		const uint32_t steps_all = (uint32_t)((h->n + dvs->rps - 1) / dvs->rps);
-		const uint32_t sel =
+		uint32_t sel =
 		    std::max<uint32_t>(256u * 64u / (uint32_t)dvs->rps, steps_all / sample_frac_for(h, k));
+		uint32_t live_cpw = (uint32_t)dvs->cpw;  // classes of a workgroup that can hold an allowed row
+		if (filt) {
+			sel = std::max<uint32_t>(sel, (uint32_t)std::min<double>(steps_all, std::ceil(8.0 * (double)k / (dvs->rps * dens))));
+			uint32_t res = h->filter_residues;
+			for (int w = 32; w > dvs->rps; w >>= 1)  // residues mod RPS (RPS = 64: at least those mod 32)
+				res = (res | (res >> (w / 2))) & ((1u << (w / 2)) - 1u);
+			live_cpw = (uint32_t)__builtin_popcount(res);
+		}
 		uint32_t wgs = std::min<uint32_t>(2048u / (uint32_t)dvs->cpw, sel / 4);
-		if (sel * 2 <= steps_all && (size_t)wgs * dvs->cpw >= 8 * k) {
+		if (sel * 2 <= steps_all && (size_t)wgs * live_cpw >= need_classes) {
 			SampleDirectParams sp{};
 			sp.g.base_f16 = h->d_base_f16;
-			sp.g.bnorm = h->d_bns_f16;  // upper row term: thresholds hold row by row
+			sp.g.bnorm = h->bns_f16();  // upper row term: thresholds hold row by row
 			sp.g.n_rows = (uint32_t)h->n;
 			sp.g.n_tiles_sel = sel;
 			sp.g.tile_stride = steps_all / sel;
@@ -1523,19 +1640,23 @@ int sampled_pass_f16(expann_index* h, const GemmF16Variant* gvf, size_t m, size_
 	}
 	const uint32_t nt = (uint32_t)((h->n + gvf->tb - 1) / gvf->tb);
 	const uint32_t run = (uint32_t)h->opt_sample_run;
-	const uint32_t t_sel = std::max<uint32_t>(256, nt / sample_frac_for(h, k)) / run * run;
+	uint32_t t_want = std::max<uint32_t>(256, nt / sample_frac_for(h, k));
+	const uint32_t live_res = filt ? (uint32_t)__builtin_popcount(h->filter_residues) : 32u;
+	if (filt)
+		t_want = std::max<uint32_t>(t_want, (uint32_t)std::min<double>(nt, std::ceil(8.0 * (double)k / (gvf->tb * dens))));
+	const uint32_t t_sel = t_want / run * run;
 	const uint32_t nqt = (uint32_t)((m + gvf->wgq - 1) / gvf->wgq);
 	uint32_t chunks = std::max<uint32_t>(1, ((uint32_t)gvf->wg_per_cu * (uint32_t)cus) / nqt);
-	chunks = std::max<uint32_t>(chunks, (uint32_t)((8 * k + 31) / 32));
+	chunks = std::max<uint32_t>(chunks, (uint32_t)((8 * k + live_res - 1) / std::max(1u, live_res)));
 	chunks = std::min<uint32_t>(chunks, std::min<uint32_t>(64, t_sel / 4));
-	if (t_sel * 2 > nt || (size_t)chunks * 32 < 8 * k)
+	if (t_sel * 2 > nt || (size_t)chunks * live_res < need_classes)
 		return EXPANN_OK;
 	const int ra = ensure_sample(m * (size_t)chunks * 32 * sizeof(float));
 	if (ra != EXPANN_OK)
 		return ra;
 	GemmF16Params fp{};
 	fp.base_f16 = h->d_base_f16;
-	fp.bnorm = h->d_bns_f16;
+	fp.bnorm = h->bns_f16();
 	fp.n_rows = (uint32_t)h->n;
 	fp.n_tiles_sel = t_sel;
 	fp.tile_stride = nt / t_sel;
@@ -1619,7 +1740,7 @@ int launch_scan_f16(expann_index* h, const GemmF16Variant* gvf, uint32_t rows_se
 	// 64-row tiles, 256 queries per workgroup, two workgroups resident per CU
 	GemmF16Params fp{};
 	fp.base_f16 = h->d_base_f16;
-	fp.bnorm = h->d_bnorm_f16;
+	fp.bnorm = h->bnorm_f16();
 	fp.n_rows = (uint32_t)h->n;
 	const uint32_t nt = (uint32_t)((h->n + gvf->tb - 1) / gvf->tb);
 	fp.n_tiles_sel = last ? nt : std::min(nt, (rows_sel + gvf->tb - 1) / gvf->tb);
@@ -1784,6 +1905,7 @@ struct ScanSel {
 	ScanFn fn = nullptr;
 	int tq = 0;
 	const char* name = "";
+	ScanFn fn_bits = nullptr, fn_list = nullptr;  // (f32 rows: the row filter's instances)
 };
 struct SearchPass {
 	expann_index* h;
@@ -1831,7 +1953,13 @@ struct SearchPass {
 };
 
 int SearchPass::choose_kernels() {
+	// A row filter reaches the matrix cores through the fp16 forms' masked row terms only: no
+	// bf16x3 form (queries outside the fp16 range go to the exact direct scan), no int8 filter, no speculative
+	// thresholds, whatever the options say; a filter selective enough for the list path streams no base at all
+	const bool filt = h->filter_on;
 	gv = force_direct ? nullptr : pick_gemm(h, m);
+	if (filt && (no_f16 || !f16_choice(h->opt_scan_kernel) || h->n_allowed <= cap))
+		gv = nullptr;
 	gvi = force_direct ? nullptr : pick_gemm_i8(h, m);
 	gvb = nullptr;
 	gvf = nullptr;
@@ -1848,7 +1976,7 @@ int SearchPass::choose_kernels() {
 		for (const auto& v : kGemmBf16)
 			if (v.d == h->dim)
 				gvb = &v;
-	if (h->opt_scan_kernel == 3 && !gvb)
+	if (h->opt_scan_kernel == 3 && !gvb && !filt)
 		return h->fail(EXPANN_ERR_UNSUPPORTED, "bf16x3 GEMM-form scan: f32 L2 with dim 64 or 128 only");
 	// fp16 single-product form: default when available; a search whose queries leave the fp16
 	// range after scaling is redone with the bf16x3 form (no_f16)
@@ -1862,8 +1990,10 @@ int SearchPass::choose_kernels() {
 		if (!gvf && f16kl_dim(h->dim))
 			gvf = &kGemmF16KL;
 	}
-	i8f = gvf && !i8f_off && i8f_wanted(h, m, k);
-	if ((h->opt_scan_kernel == 4 || h->opt_scan_kernel == 6) && !gvf && !no_f16)
+	i8f = gvf && !i8f_off && !filt && i8f_wanted(h, m, k);
+	if (filt && !gvf)
+		gv = nullptr;
+	if ((h->opt_scan_kernel == 4 || h->opt_scan_kernel == 6) && !gvf && !no_f16 && !(filt && h->n_allowed <= cap))
 		return h->fail(EXPANN_ERR_UNSUPPORTED, "fp16 GEMM-form scan: f32 with dim a multiple of 16 from 64 to 4096 only");
 	if (gvf)
 		gvb = nullptr;
@@ -1888,6 +2018,9 @@ int SearchPass::prepare_queries(bool* restart) {
 			*restart = true;
 			return EXPANN_OK;
 		}
+		rc = ensure_filter_terms(h, st);
+		if (rc != EXPANN_OK)
+			return rc;
 		rc = ensure_workspace(h, m, cap);
 		if (rc != EXPANN_OK)
 			return rc;
@@ -1962,9 +2095,11 @@ int SearchPass::plan_thresholds() {
 	int rc = ensure_workspace(h, m, cap);
 	if (rc != EXPANN_OK)
 		return rc;
-	levels = plan_levels(h->n, k, cap, h->opt_sample_ratio);
+	const bool filt = h->filter_on;
+	levels = filt ? plan_levels_filtered(h->n, h->n_allowed, h->filter_list_len, k, cap, h->opt_sample_ratio)
+	              : plan_levels(h->n, k, cap, h->opt_sample_ratio);
 	n_qtiles = (uint32_t)((m + sv->tq - 1) / sv->tq);
-	if (!gv && !gvi && levels.size() >= 3 && h->opt_sample_pass) {
+	if (!gv && !gvi && levels.size() >= 3 && h->opt_sample_pass && !filt) {
 		// direct path: ONE sampled level of class minima (1/16 of the rows) instead of the
 		// first two levels of the ladder -- a launch chain shorter by a scan, a select and a
 		// memset, and ~10 k instead of ~32 k candidates in the full scan
@@ -1997,7 +2132,7 @@ int SearchPass::plan_thresholds() {
 		// (speculation: the scan_gemm_f16x / i8w streams -- the kernels with the redo pass's early exit --, batches
 		// beyond the latency mode's, no debug instance)
 		const bool spec_form = gvf->hit_log && gvf->scan_redo && (h->opt_debug & ~16L) == 0 && m > 64;
-		if (spec_form && !spec_off && h->opt_spec_rank >= 0 &&
+		if (spec_form && !spec_off && !filt && h->opt_spec_rank >= 0 &&
 		    (h->opt_spec_rank > 0 || spec_auto_region(h, m, k, i8f && !i8f_off)))
 			spec_j = 1;
 		const int rs = sampled_pass_f16(h, gvf, m, k, ip, cus, h->d_tau[levels.size() & 1],
@@ -2033,6 +2168,16 @@ int SearchPass::run_level(size_t li) {
 	sp.cand = h->d_cand;
 	sp.cap = cap;
 	sp.dim = (uint32_t)h->dim;
+	ScanFn scan_fn = sv->fn;
+	if (h->filter_on) {  // level 0 walks the filter's list, the later levels read its bitmap
+		scan_fn = L.list_rows ? sv->fn_list : sv->fn_bits;
+		if (!scan_fn || (first && !L.list_rows))
+			return h->fail(EXPANN_ERR_UNSUPPORTED, "row filter: no filtered instance of the direct scan");  // (f32 rows have both)
+		sp.allow_bits = h->d_filter_bits;
+		sp.row_list = h->d_filter_list;
+		sp.list_len = L.list_rows;
+		sp.list_stride = L.list_step;
+	}
 	// ~16 workgroups per CU in total, at least 8 groups (128 rows) per workgroup
 	uint32_t target_chunks = (uint32_t)std::max<long>(1, (16L * cus + n_qtiles - 1) / n_qtiles);
 	uint32_t max_chunks = std::max<uint32_t>(1, L.n_groups_sel / 8);
@@ -2176,7 +2321,7 @@ int SearchPass::run_level(size_t li) {
 	} else {
 		if (timed)
 			HIP_TRY(h, hipEventRecord(h->ev[h->ev_used][0], st));
-		hipLaunchKernelGGL(sv->fn, dim3(n_chunks * n_qtiles), dim3(kBlock), 0, st, sp);
+		hipLaunchKernelGGL(scan_fn, dim3(n_chunks * n_qtiles), dim3(kBlock), 0, st, sp);
 	}
 	if (timed) {
 		HIP_TRY(h, hipEventRecord(h->ev[h->ev_used][1], st));
@@ -2346,7 +2491,7 @@ int SearchPass::run_redo(bool use_i8f) {
 	} else {
 		GemmF16Params fp{};
 		fp.base_f16 = h->d_base_f16;
-		fp.bnorm = h->d_bnorm_f16;
+		fp.bnorm = h->bnorm_f16();
 		fp.n_rows = (uint32_t)h->n;
 		fp.n_tiles_sel = nt;
 		fp.tile_stride = 1;
@@ -2525,7 +2670,16 @@ int SearchPass::run() {
 int search_pass(expann_index* h, const void* d_queries, size_t m, size_t k, uint64_t* d_ids,
                 float* d_dists, hipStream_t st) {
 	const bool ip = (h->metric == EXPANN_METRIC_IP);
-	if (h->dtype == EXPANN_DTYPE_F32 && !ip && h->opt_scan_kernel == 0 && h->opt_u8_exact &&
+	if (h->filter_on && h->n_allowed == 0) {  // nothing is allowed: the outputs' padding is the whole answer
+		hipLaunchKernelGGL(fill_pad_kernel, dim3((uint32_t)std::min<size_t>((m * k + kBlock - 1) / kBlock, 1024)), dim3(kBlock),
+		                   0, st, d_ids, d_dists, m * k);
+		HIP_TRY(h, hipGetLastError());
+		if (!h->opt_async || h->host_call)
+			HIP_TRY(h, hipStreamSynchronize(st));
+		return EXPANN_OK;
+	}
+	// (the uint8 shadow is a second handle that knows nothing of a row filter)
+	if (h->dtype == EXPANN_DTYPE_F32 && !ip && h->opt_scan_kernel == 0 && h->opt_u8_exact && !h->filter_on &&
 	    (h->dim == 128 || h->dim == 256) && m >= 96 && h->n >= 65536 && k <= 256 && h->u8_exact >= 0) {
 		// rows that are all integers in [0, 255] (SIFT): with integer queries the uint8 engine's
 		// exact integer scores ARE the fp32 scores (d * 255^2 < 2^24: every partial sum of the
@@ -2548,7 +2702,7 @@ int search_pass(expann_index* h, const void* d_queries, size_t m, size_t k, uint
 	if (h->dtype == EXPANN_DTYPE_F32) {
 		const ScanVariant* v = pick_scan_f32(h->dim, ip, m, h->opt_query_tile);
 		if (v)
-			svs = ScanSel{v->fn, v->tq, v->name};
+			svs = ScanSel{v->fn, v->tq, v->name, v->fn_bits, v->fn_list};
 	} else {
 		const ScanI8Variant* v = pick_scan_i8(h->dim, h->int_mode, m, h->opt_query_tile);
 		if (v)
@@ -2832,6 +2986,7 @@ int expann_build(expann_index* h) {
 	if (h->n_staged >= (1ull << 32) - 32)
 		return h->fail(EXPANN_ERR_UNSUPPORTED, "more than 2^32 rows per shard");
 	HIP_TRY(h, hipSetDevice(h->device));
+	drop_row_filter(h);
 	HIP_TRY(h, hipMalloc(&h->d_base, h->staging.size()));
 	h->owns_base = true;
 	HIP_TRY(h, hipMemcpy(h->d_base, h->staging.data(), h->staging.size(), hipMemcpyHostToDevice));
@@ -2883,6 +3038,8 @@ int expann_set_base_device(expann_index* h, const void* d_rows, size_t n, uint64
 	h->d_bnorm_f16.reset();
 	h->d_bns_f16.reset();
 	h->f16_scale = 0.0f;
+	h->f16_n_pad = 0;
+	drop_row_filter(h);  // (a filter belongs to the rows it was set for)
 	h->d_base = const_cast<void*>(d_rows);
 	h->owns_base = false;
 	h->n = n;
@@ -3002,7 +3159,8 @@ int expann_search(expann_index* h, const void* queries, size_t m, size_t k, uint
 		// one async copy
 		const void* dq = h->d_q;
 		if (h->dtype == EXPANN_DTYPE_F32 && h->d_base_f16 && h->f16_scale > 0.0f && h->opt_scan_kernel == 0 &&
-		    m <= (size_t)kRowsPerGroup && h->n >= 4096 && pick_gemm(h, m) != nullptr) {
+		    m <= (size_t)kRowsPerGroup && h->n >= 4096 && pick_gemm(h, m) != nullptr &&
+		    !(h->filter_on && h->n_allowed <= kMaxCap)) {  // (the list path runs no prep kernel)
 			h->q_in_pinned_host = true;
 			dq = pin;
 		} else {
@@ -3226,6 +3384,10 @@ int expann_get_stat(expann_index* h, const char* name, uint64_t* out) {
 		*out = h->stat_redo_overflows;
 	else if (!std::strcmp(name, "spec_rank"))
 		*out = h->stat_spec_rank;
+	else if (!std::strcmp(name, "filter_active"))
+		*out = h->filter_on ? 1 : 0;
+	else if (!std::strcmp(name, "filter_rows"))
+		*out = h->filter_on ? h->n_allowed : expann_size(h);
 	else
 		return h->fail(EXPANN_ERR_INVALID_ARG, std::string("unknown statistic ") + name);
 	return EXPANN_OK;
@@ -3233,6 +3395,88 @@ int expann_get_stat(expann_index* h, const char* name, uint64_t* out) {
 
 uint32_t expann_spec_rank_auto(size_t k, uint32_t sample_frac) {
 	return spec_rank_auto(k, sample_frac ? 1.0 / (double)sample_frac : 1.0);
+}
+
+// ---- row filter ------------------------------------------------------------------------
+namespace {
+// bits: n_words words in host (on_device = false) or device memory, read in the order of `st`
+int set_row_filter(expann_index* h, const uint32_t* bits, size_t n_words, bool on_device, hipStream_t user_st) {
+	if (!h)
+		return EXPANN_ERR_INVALID_ARG;
+	if (!bits)
+		return h->fail(EXPANN_ERR_INVALID_ARG, "row filter: NULL bits");
+	if (h->dtype != EXPANN_DTYPE_F32)
+		return h->fail(EXPANN_ERR_UNSUPPORTED, "row filter: fp32 rows only (8-bit and int16 rows have integer row terms)");
+	if (!h->d_base)
+		return h->fail(EXPANN_ERR_NOT_BUILT, "row filter before build()");
+	const size_t need_words = (h->n + 31) / 32;
+	if (n_words < need_words)
+		return h->fail(EXPANN_ERR_INVALID_ARG, "row filter: " + std::to_string(n_words) + " words for " +
+		                                           std::to_string(h->n) + " rows (need " + std::to_string(need_words) + ")");
+	HIP_TRY(h, hipSetDevice(h->device));
+	// deferred searches still read the old filter: as before a search on another stream, they are waited for
+	// (their flag blocks stay in the ring for expann_sync)
+	if (h->async_pending > 0)
+		HIP_TRY(h, hipStreamSynchronize(h->async_stream));
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
+	hipStream_t st = user_st ? user_st : h->stream;
+	const size_t words = (h->n + 127) / 128 * 4;  // whole tiles of the fp16 copy (<= 128 rows each)
+	if (words != h->filter_words || !h->d_filter_bits) {
+		h->filter_on = false;
+		h->d_filter_bits.reset();
+		h->filter_words = 0;
+		HIP_TRY(h, hipMalloc(&h->d_filter_bits, sizeof(uint32_t) * words));
+		h->filter_words = words;
+	}
+	if (!h->d_filter_stat)
+		HIP_TRY(h, hipMalloc(&h->d_filter_stat, sizeof(uint32_t) * (2 + kFilterSegs)));
+	if (!h->d_filter_list)
+		HIP_TRY(h, hipMalloc(&h->d_filter_list, sizeof(uint32_t) * kFilterListCap));
+	h->filter_on = false;  // (until the new filter is complete)
+	h->filter_terms_valid = false;
+	HIP_TRY(h, hipMemsetAsync(h->d_filter_bits, 0, sizeof(uint32_t) * words, st));
+	HIP_TRY(h, hipMemcpyAsync(h->d_filter_bits, bits, sizeof(uint32_t) * need_words,
+	                          on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+	HIP_TRY(h, hipMemsetAsync(h->d_filter_stat, 0, sizeof(uint32_t) * (2 + kFilterSegs), st));
+	hipLaunchKernelGGL(filter_count_kernel, dim3(kFilterSegs), dim3(kBlock), 0, st, h->d_filter_bits.as<uint32_t>(),
+	                   (uint32_t)h->n, (uint32_t)words, h->d_filter_stat.as<uint32_t>(), h->d_filter_stat + 2);
+	HIP_TRY(h, hipGetLastError());
+	uint32_t stat[2] = {0, 0};
+	HIP_TRY(h, hipMemcpyAsync(stat, h->d_filter_stat, sizeof(stat), hipMemcpyDeviceToHost, st));
+	HIP_TRY(h, hipStreamSynchronize(st));  // the planner needs the count on the host: one wait per filter change
+	h->n_allowed = stat[0];
+	h->filter_residues = stat[1];
+	h->filter_list_stride = (uint32_t)std::max<size_t>(1, (h->n_allowed + kFilterListCap - 1) / kFilterListCap);
+	h->filter_list_len = (uint32_t)((h->n_allowed + h->filter_list_stride - 1) / h->filter_list_stride);
+	if (h->n_allowed) {
+		hipLaunchKernelGGL(filter_compact_kernel, dim3(kFilterSegs), dim3(kBlock), 0, st, h->d_filter_bits.as<const uint32_t>(),
+		                   (uint32_t)words, h->d_filter_stat.as<const uint32_t>() + 2, h->filter_list_stride,
+		                   h->d_filter_list.as<uint32_t>(), kFilterListCap);
+		HIP_TRY(h, hipGetLastError());
+		HIP_TRY(h, hipStreamSynchronize(st));
+	}
+	h->filter_on = true;
+	return EXPANN_OK;
+}
+}  // namespace
+
+int expann_set_row_filter(expann_index* h, const uint32_t* allow_bits, size_t n_words) {
+	return set_row_filter(h, allow_bits, n_words, false, nullptr);
+}
+
+int expann_set_row_filter_device(expann_index* h, const uint32_t* d_allow_bits, size_t n_words, void* stream) {
+	return set_row_filter(h, d_allow_bits, n_words, true, (hipStream_t)stream);
+}
+
+int expann_clear_row_filter(expann_index* h) {
+	if (!h)
+		return EXPANN_ERR_INVALID_ARG;
+	if (h->async_pending > 0) {  // (searches enqueued under the filter finish under it)
+		HIP_TRY(h, hipSetDevice(h->device));
+		HIP_TRY(h, hipStreamSynchronize(h->async_stream));
+	}
+	h->filter_on = false;
+	return EXPANN_OK;
 }
 
 int expann_set_option(expann_index* h, const char* name, long value) {

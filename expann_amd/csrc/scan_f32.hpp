@@ -41,9 +41,19 @@ struct ScanParams {
 	// threshold -- from a 16x larger sample than a keep-all level can afford, in one launch.
 	uint32_t classmin;
 	uint32_t dim;             // scan_filter_f32_any_kernel only: the row length (the templates have it as D)
+	// row filter (the RF instances of the f32 kernels; filter_rows.hpp)
+	const uint32_t* allow_bits;  // kRowsBitmap: bit r & 31 of word r >> 5 allows row r (read only for r < n_rows)
+	const uint32_t* row_list;    // kRowsList: step g visits the rows row_list[(g * 16 + i) * list_stride], i < 16 ...
+	uint32_t list_len;           // ... while g * 16 + i < list_len (level 0 only: every key at its list position)
+	uint32_t list_stride;
 };
 
-template <int D, int TQ, bool IP>
+// which rows a launch of the f32 scans may keep
+constexpr int kRowsAll = 0;     // every row below n_rows
+constexpr int kRowsBitmap = 1;  // ... that the bitmap allows
+constexpr int kRowsList = 2;    // the rows of a list, in list order
+
+template <int D, int TQ, bool IP, int RF = kRowsAll>
 __global__ __launch_bounds__(kBlock) void scan_filter_f32_kernel(ScanParams p) {
 	static_assert(D % 32 == 0, "the reference kernels need dim % 16 == 0");
 	constexpr int DPL = D / 16;  // dims per lane
@@ -87,6 +97,10 @@ __global__ __launch_bounds__(kBlock) void scan_filter_f32_kernel(ScanParams p) {
 		g1 = p.n_groups_sel;
 
 	auto row_of = [&](uint32_t g) -> uint32_t {
+		if (RF == kRowsList) {  // (past the end of the list: no row)
+			const uint32_t slot = g * kRowsPerGroup + wave * kRowsPerWaveStep + rg;
+			return slot < p.list_len ? p.row_list[(size_t)slot * p.list_stride] : 0xFFFFFFFFu;
+		}
 		return g * p.group_stride * kRowsPerGroup + wave * kRowsPerWaveStep + rg;
 	};
 	// a lane's dims t and t+1 share one 64-bit register pair (op_sel picks the half)
@@ -103,7 +117,9 @@ __global__ __launch_bounds__(kBlock) void scan_filter_f32_kernel(ScanParams p) {
 		best[j] = kSentinelKey;
 	auto process = [&](const f32x2 (&r)[DPL / 2], uint32_t g) {
 		const uint32_t row = row_of(g);
-		const bool rvalid = row < p.n_rows;
+		bool rvalid = row < p.n_rows;
+		if (RF == kRowsBitmap && rvalid)
+			rvalid = (p.allow_bits[row >> 5] >> (row & 31)) & 1u;
 		// per-pair accumulators; each component is one (row, query) chain of the reference:
 		// acc = fma(diff, diff, acc) over this lane's dims in increasing order
 		f32x2 acc[NP];
@@ -207,7 +223,7 @@ __global__ __launch_bounds__(kBlock) void scan_filter_f32_kernel(ScanParams p) {
 // odd d/16 needs nothing special.  The TQ queries of the workgroup sit in LDS (TQ x kMaxAnyDim floats,
 // 16 lanes of a row read the same 64 B: broadcast), so a 4096-wide query costs no registers.
 constexpr int kMaxAnyDim = 4096;
-template <int TQ, bool IP>
+template <int TQ, bool IP, int RF = kRowsAll>
 __global__ __launch_bounds__(kBlock) void scan_filter_f32_any_kernel(ScanParams p) {
 	__shared__ float qs[TQ * kMaxAnyDim];
 	const uint32_t D = p.dim, DPL = D / 16;
@@ -246,9 +262,16 @@ __global__ __launch_bounds__(kBlock) void scan_filter_f32_any_kernel(ScanParams 
 	for (int j = 0; j < TQ; ++j)
 		best[j] = kSentinelKey;
 	for (uint32_t g = g0; g < g1; ++g) {
-		const uint32_t row = g * p.group_stride * kRowsPerGroup + wave * kRowsPerWaveStep + rg;
-		const bool rvalid = row < p.n_rows;
-		const float* src = base + (size_t)(rvalid ? row : p.n_rows - 1) * D + l;
+		uint32_t row = g * p.group_stride * kRowsPerGroup + wave * kRowsPerWaveStep + rg;
+		if (RF == kRowsList) {
+			const uint32_t slot = g * kRowsPerGroup + wave * kRowsPerWaveStep + rg;
+			row = slot < p.list_len ? p.row_list[(size_t)slot * p.list_stride] : 0xFFFFFFFFu;
+		}
+		const bool in_range = row < p.n_rows;
+		bool rvalid = in_range;
+		if (RF == kRowsBitmap && in_range)
+			rvalid = (p.allow_bits[row >> 5] >> (row & 31)) & 1u;
+		const float* src = base + (size_t)(in_range ? row : p.n_rows - 1) * D + l;
 		const float* qsl = qs + l;
 		float acc[TQ];
 #pragma unroll

@@ -17,6 +17,16 @@ _NP_DTYPE = {_lib.DTYPE_F32: np.float32, _lib.DTYPE_U8: np.uint8, _lib.DTYPE_I8:
              _lib.DTYPE_I16: np.int16}
 
 
+def pack_row_filter(allow):
+    """A boolean array [n] as the little-endian uint32 words of expann_set_row_filter: bit r & 31 of word
+    r >> 5 is allow[r]; the bits past n in the last word are zero.  A pure function."""
+    allow = np.asarray(allow).astype(bool).reshape(-1)
+    by = np.packbits(allow, bitorder="little")
+    out = np.zeros((allow.size + 31) // 32 * 4, dtype=np.uint8)
+    out[:by.size] = by
+    return out.view("<u4").astype(np.uint32)
+
+
 class GpuBruteForceEngine:
     """Exact k-NN by a full scan on one MI355X (drop-in for brute_force_engine<float>)."""
 
@@ -104,8 +114,25 @@ class GpuBruteForceEngine:
     def set_option(self, name, value):
         _lib.check(self._h, self._L.expann_set_option(self._h, name.encode(), int(value)))
 
+    def set_row_filter(self, allow):
+        """expann_set_row_filter: searches return the nearest among the rows where the boolean array
+        allow[n] is true (local row numbers, before id_offset), exactly as an index of those rows would;
+        None clears the filter (expann_clear_row_filter).  fp32 rows only."""
+        if allow is None:
+            _lib.check(self._h, self._L.expann_clear_row_filter(self._h))
+            return
+        words = pack_row_filter(allow)
+        _lib.check(self._h, self._L.expann_set_row_filter(self._h, words.ctypes.data, words.size))
+
+    def set_row_filter_device(self, ptr, n_words, stream=0):
+        """expann_set_row_filter_device: the same from n_words uint32 words in device memory (the layout of
+        pack_row_filter), read in the order of `stream`; returns once the allowed rows are counted."""
+        _lib.check(self._h, self._L.expann_set_row_filter_device(self._h, C.c_void_p(ptr), int(n_words),
+                                                                 C.c_void_p(stream)))
+
     def get_stat(self, name):
-        """expann_get_stat: "redo_queries", "redo_overflows", "spec_rank" (speculative thresholds)."""
+        """expann_get_stat: "redo_queries", "redo_overflows", "spec_rank" (speculative thresholds);
+        "filter_active" (0 / 1) and "filter_rows" (rows the row filter allows; n when none is set)."""
         v = C.c_uint64(0)
         _lib.check(self._h, self._L.expann_get_stat(self._h, name.encode(), C.byref(v)))
         return int(v.value)

@@ -101,6 +101,22 @@ struct gpu_brute_force_engine : public ann_engine<T, gpu_brute_force_engine<T>> 
 		check(sharded ? expann_sharded_search(sharded, queries, m, k, ids, dists)
 		              : expann_search(handle, queries, m, k, ids, dists));
 	}
+	// Extension: row filter (expann_set_row_filter).  Bit r & 31 of word r >> 5 allows row r; while it is set,
+	// queries return the nearest among the allowed rows, as an index of only those rows would.  One device, float
+	// rows; the sharded form does not offer it.
+	void set_row_filter(const uint32_t* bits, size_t n_words) {
+		single("set_row_filter");
+		check(expann_set_row_filter(handle, bits, n_words));
+	}
+	// the same from device memory, read in the order of `stream` (a hipStream_t; nullptr = the engine's own)
+	void set_row_filter_device(const uint32_t* d_bits, size_t n_words, void* stream = nullptr) {
+		single("set_row_filter_device");
+		check(expann_set_row_filter_device(handle, d_bits, n_words, stream));
+	}
+	void clear_row_filter() {
+		single("clear_row_filter");
+		check(expann_clear_row_filter(handle));
+	}
 	const std::string _name() { return "GPU Brute-Force Engine (MI355X)"; }
 	const param_list_t _param_list() {
 		param_list_t pl;
@@ -130,6 +146,12 @@ private:
 		                                         : EXPANN_DTYPE_I16;
 	}
 	bool opened() const { return handle || sharded; }
+	// the row filter's entry points: a built single-device engine
+	void single(const char* what) const {
+		if (!handle)
+			throw std::runtime_error(std::string("gpu_brute_force_engine: ") + what +
+			                         (sharded ? ": the sharded engine has no row filter" : " before build()"));
+	}
 	void open(size_t dim) {
 		dimension = dim;
 		if (conf.devices.size() > 1) {

@@ -466,6 +466,36 @@ int expann_get_stat(expann_index* h, const char* name, uint64_t* out);
  * P(Bin(k - 1, 1/sample_frac) >= j) <= 1 %; k = no speculation.  Host arithmetic only. */
 uint32_t expann_spec_rank_auto(size_t k, uint32_t sample_frac);
 
+/* Row filter of the brute-force index (appended; EXPANN_ABI_VERSION stays 2: nothing that existed changed).
+ * Bit r & 31 of word r >> 5 (least significant bit first) says whether LOCAL row r -- the row number before
+ * id_offset -- is allowed; bits at and beyond expann_size(h) are ignored.  The library copies the bits, the
+ * caller may free them on return; its own copy covers the padded row count of the fp16 copy, is zero from row n
+ * on, and no kernel reads a bit word outside it.
+ * While a filter is set, expann_search, expann_search_device (also under "async_search") and the latency mode
+ * return the min(k, allowed) smallest (score, id) among the allowed rows, ascending, padded with UINT64_MAX /
+ * +inf: exactly what an index holding only the allowed rows, in the same order, would return, with its ids
+ * mapped back.  Ids and distance bits are those of the reference's arithmetic, as everywhere else.
+ * expann_score_ids takes explicit ids and is not affected.
+ * Both set calls and the clear call first wait on the host for outstanding deferred searches (the rule of a
+ * search on another stream), so every search runs under the filter that was in force when it was enqueued.
+ * expann_set_row_filter_device reads d_allow_bits in the order of `stream` (a hipStream_t; NULL = the handle's
+ * own) and returns after that stream and the handle's own have drained: the allowed-row count is needed on the
+ * host for planning -- one host wait per filter change, none per search.  expann_build and
+ * expann_set_base_device clear the filter.
+ * Errors, in this order: h == NULL or bits == NULL EXPANN_ERR_INVALID_ARG; a dtype other than EXPANN_DTYPE_F32
+ * EXPANN_ERR_UNSUPPORTED (8-bit and int16 rows have integer row terms without a NaN: not offered) -- both before
+ * the device is touched --; no rows on the device yet EXPANN_ERR_NOT_BUILT; n_words < ceil(n / 32)
+ * EXPANN_ERR_INVALID_ARG.  A failed call leaves the filter as it was.
+ * A filtered search never takes the uint8 shadow index ("u8_exact"), the int8 filter ("i8_filter") or
+ * speculative thresholds ("spec_rank"), whatever those options say, and never the bf16x3 form ("scan_kernel" 3
+ * runs the exact direct scan, as do queries outside the fp16 range).
+ * expann_sharded_* does not offer the filter (its set_option pass-through is unchanged and there is no
+ * sharded entry point for it); a per-query filter and the graph engine are not offered either.
+ * expann_get_stat: "filter_active" (0 / 1), "filter_rows" (allowed rows; n when no filter is set). */
+int expann_set_row_filter(expann_index* h, const uint32_t* allow_bits, size_t n_words);        /* host bits   */
+int expann_set_row_filter_device(expann_index* h, const uint32_t* d_allow_bits, size_t n_words, void* stream);
+int expann_clear_row_filter(expann_index* h);
+
 #ifdef __cplusplus
 }
 #endif
