@@ -47,6 +47,7 @@ thread_local std::string g_create_error;
 namespace {
 
 constexpr uint32_t kMaxCap = 16384;      // keys per query that fit the select kernel's LDS
+static_assert(kMaxK == kMaxCap / 2, "the bound on k: a candidate list holds at least 2k keys");
 constexpr size_t kMaxQueriesPerPass = 32768;
 constexpr int kEventPairs = 64;
 constexpr uint32_t kAsyncRing = 256;  // outstanding searches of the deferred-check mode
@@ -381,6 +382,26 @@ uint32_t pow2ceil(uint32_t x) {
 }
 
 
+// Does a level of ratio r fit lists of `cap` keys?  A level that scans r times the rows of the level before keeps
+// C = #(its rows under the k-th best of the level before) rows per query; on iid rows E C = r k and
+// Var C <= r (r + 1) k (r k from the draw of its own rows, r^2 k from the spread of the threshold; r (r - 1) k when
+// the samples are nested).  It fits when mean + 6 standard deviations do -- at m * levels ~ 10^5 lists per search
+// an overflow by chance then has probability ~ 10^-4 -- with cap / 32 left to the fp16 and int8 filters, which
+// also keep the rows within their rounding error of the threshold, and two groups to the rounding of the levels'
+// sizes.  (r k + 6 sqrt(v) <= room, written without the root.)
+// Under a row filter (plan_levels_filtered) k-th bests and counts are over the allowed rows, of which a level's
+// strided scan meets a random number: for a random filter of density p that adds at most r k (1 - p) to the
+// variance, under 100 rows in quadrature at k = 8192 -- inside the cap / 32, not in the 6 sigma, and not covered by a
+// test (the row filter's cases stop at k = 1000).
+constexpr bool ratio_fits(double r, double k, uint32_t cap) {
+	const double slack = (double)cap - cap / 32 - 2 * kRowsPerGroup - r * k;
+	return slack >= 0 && 36.0 * r * (r + 1.0) * k <= slack * slack;
+}
+// the plans of k <= 7200 rest on this: at the floor of ratio 2 they fit the longest lists; k = cap / 2 does not
+static_assert(ratio_fits(2.0, 7200, kMaxCap) && !ratio_fits(2.0, 7300, kMaxCap) && !ratio_fits(2.0, kMaxCap / 2, kMaxCap) &&
+                  ratio_fits(1.78125, kMaxCap / 2, kMaxCap),
+              "plan_levels: ratio 2 up to k = 7200, 1.78 at the bound");
+
 // Threshold levels: level 0 keeps every row of a small strided sample (tau = +inf), each
 // later level scans `ratio` times more rows with tau = k-th best score of the level before,
 // the last level scans every row.  Expected survivors per query and level ~ ratio * k.
@@ -398,6 +419,13 @@ std::vector<Level> plan_levels(size_t n, size_t k, uint32_t cap, long ratio_opt)
 	double ratio = std::min<double>((double)ratio_opt, max_ratio);
 	if (ratio < 2.0)
 		ratio = 2.0;
+	// At the largest capacity no retry can lengthen the lists, and from k = 7293 on ratio 2 no longer fits them
+	// (ratio_fits above).  Take the largest ratio that does: more levels, each shorter; k = cap / 2 ends at 1.78.
+	// Only a plan that stands at the floor of 2 is touched, and every k <= 7200 fits there (the static_assert), so
+	// those plan as before at every capacity; smaller capacities still grow on overflow.
+	if (cap >= kMaxCap && ratio <= 2.0)
+		while (ratio > 1.25 && !ratio_fits(ratio, (double)k, cap))
+			ratio -= 1.0 / 64.0;
 	const double span = (double)n_groups / (double)s0;
 	int steps = (int)std::ceil(std::log(span) / std::log(ratio) - 1e-9);
 	if (steps < 1)
@@ -2734,8 +2762,7 @@ int search_pass(expann_index* h, const void* d_queries, size_t m, size_t k, uint
 	if (h->opt_cand_capacity > 0 && (size_t)cap < 2 * k)  // the option is a starting size, never below 2k
 		cap = std::min(pow2ceil((uint32_t)(2 * k)), kMaxCap);
 	if ((size_t)cap < 2 * k)
-		return h->fail(EXPANN_ERR_UNSUPPORTED, "k too large for the candidate buffers (k <= " +
-		                                           std::to_string(kMaxCap / 2) + ")");
+		return h->fail(EXPANN_ERR_UNSUPPORTED, k_too_large());
 	const int cus = num_cus(h->device);
 	if (const GemmI8qVariant* gq = pick_gemm_i8q(h, m, k)) {
 		const int rq = search_i8q(h, gq, d_queries, m, k, d_ids, d_dists, st, cap);
@@ -3057,6 +3084,8 @@ int expann_search_device(expann_index* h, const void* d_queries, size_t m, size_
 		return h->fail(EXPANN_ERR_NOT_BUILT, "search before build()");
 	if (k == 0)
 		return h->fail(EXPANN_ERR_INVALID_ARG, "k == 0");
+	if (k > kMaxK)  // (by value, before any GPU work: never a matter of the data)
+		return h->fail(EXPANN_ERR_UNSUPPORTED, k_too_large());
 	if (m == 0)
 		return EXPANN_OK;
 	if (!d_queries || !d_ids)
@@ -3129,6 +3158,8 @@ int expann_search(expann_index* h, const void* queries, size_t m, size_t k, uint
 		return h->fail(EXPANN_ERR_NOT_BUILT, "search before build()");
 	if (k == 0)
 		return h->fail(EXPANN_ERR_INVALID_ARG, "k == 0");
+	if (k > kMaxK)  // (by value, before any GPU work: never a matter of the data)
+		return h->fail(EXPANN_ERR_UNSUPPORTED, k_too_large());
 	if (m == 0)
 		return EXPANN_OK;
 	if (!queries || !ids)

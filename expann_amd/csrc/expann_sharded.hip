@@ -749,6 +749,8 @@ int expann_sharded_search(expann_sharded* h, const void* queries, size_t m, size
 		return h->fail(EXPANN_ERR_NOT_BUILT, "search before build()");
 	if (k == 0)
 		return h->fail(EXPANN_ERR_INVALID_ARG, "k == 0");
+	if (k > kMaxK)  // (as expann_search: by value, before the communicator, the chunks or any shard's search)
+		return h->fail(EXPANN_ERR_UNSUPPORTED, k_too_large());
 	if (m == 0)
 		return EXPANN_OK;
 	if (!queries || !ids)
@@ -790,6 +792,8 @@ int expann_sharded_search_devices(expann_sharded* h, const void* const* d_querie
 		return h->fail(EXPANN_ERR_NOT_BUILT, "search before build()");
 	if (k == 0)
 		return h->fail(EXPANN_ERR_INVALID_ARG, "k == 0");
+	if (k > kMaxK)  // (as expann_search: by value, before the communicator, the chunks or any shard's search)
+		return h->fail(EXPANN_ERR_UNSUPPORTED, k_too_large());
 	if (m == 0)
 		return EXPANN_OK;
 	if (!d_queries || !d_ids || !d_dists)
@@ -838,6 +842,8 @@ int expann_sharded_search_device(expann_sharded* h, const void* d_queries, size_
 		return h->fail(EXPANN_ERR_NOT_BUILT, "search before expann_sharded_set_shard_device");
 	if (k == 0)
 		return h->fail(EXPANN_ERR_INVALID_ARG, "k == 0");
+	if (k > kMaxK)  // (as expann_search: by value, before the communicator, the chunks or any shard's search)
+		return h->fail(EXPANN_ERR_UNSUPPORTED, k_too_large());
 	if (m == 0)
 		return EXPANN_OK;
 	if (!d_queries || !d_ids || !d_dists)

@@ -9,6 +9,11 @@
 
 namespace expann {
 
+// the bound on k of every brute-force search (half the longest candidate list, kMaxCap in expann_hip.hip):
+// a larger k is refused by value at the entry point, before any GPU work
+constexpr size_t kMaxK = 8192;
+inline std::string k_too_large() { return "k too large for the candidate buffers (k <= " + std::to_string(kMaxK) + ")"; }
+
 // scoped device allocation for the entry points that need per-call temporaries
 struct DevBuf {
 	void* p = nullptr;

@@ -97,7 +97,9 @@ size_t expann_size(const expann_index* h);
 /* query_k for a batch (src/ann_engine.h:27-29, src/brute_force_engine.h:28-46; the
  * reference has no batch API -- m = 1 is query_k).  Host buffers.  For each query the k
  * rows with the smallest (score, id), ascending; ids[m][k], dists[m][k] (dists may be
- * NULL).  When fewer than k rows exist the tail is padded with UINT64_MAX / +inf. */
+ * NULL).  When fewer than k rows exist the tail is padded with UINT64_MAX / +inf.
+ * 1 <= k <= 8192 (half the longest candidate list): a larger k is refused by value with
+ * EXPANN_ERR_UNSUPPORTED before any GPU work, whatever the index holds. */
 int expann_search(expann_index* h, const void* queries, size_t m, size_t k, uint64_t* ids,
                   float* dists);
 
@@ -122,7 +124,8 @@ int expann_search_device(expann_index* h, const void* d_queries, size_t m, size_
 int expann_sync(expann_index* h);
 
 /* k-way merge of per-shard results after an all-gather (RCCL): in_ids/in_dists are
- * [n_lists][m][k], each row ascending by (score, id) and padded as above; out is [m][k]. */
+ * [n_lists][m][k], each row ascending by (score, id) and padded as above; out is [m][k].
+ * 1 <= n_lists <= 64 and k >= 1, else EXPANN_ERR_INVALID_ARG; m = 0 is EXPANN_OK. */
 int expann_merge_topk_device(int device, const uint64_t* d_in_ids, const float* d_in_dists,
                              size_t n_lists, size_t m, size_t k, uint64_t* d_out_ids,
                              float* d_out_dists, void* stream);

@@ -215,6 +215,46 @@ def test_k_100(big, big_eng, oracle):
     _same(big_eng.query_k_batch(queries[:130], 100), _expected(oracle, base, queries[:130], 100, allow))
 
 
+# 7b. k = 1000 ----------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def k1000(gpu):
+    """70 001 rows of d = 128, 100 queries and one engine for the k = 1000 cases"""
+    rng = np.random.RandomState(1000)
+    base = rng.standard_normal((70_001, D)).astype(np.float32)
+    queries = rng.standard_normal((100, D)).astype(np.float32)
+    eng = _engine(base)
+    yield base, queries, eng
+    eng.close()
+
+
+def _k1000_case(oracle, k1000, allow, m):
+    base, queries, eng = k1000
+    eng.set_row_filter(allow)
+    assert eng.get_stat("filter_rows") == int(allow.sum())
+    eng.get_profile()
+    got = eng.query_k_batch(queries[:m], 1000)
+    prof = eng.get_profile()
+    _same(got, _expected(oracle, base, queries[:m], 1000, allow), prof)
+    return got, prof
+
+
+def test_k_1000_list_regime(oracle, k1000):
+    """10 000 allowed rows fit the filter's list (16 384) and are the whole search -- five times the list length
+    any k <= 32 ever selects from"""
+    _k1000_case(oracle, k1000, _exactly(70_001, 10_000, 1), 100)
+
+
+@pytest.mark.parametrize("m", [100, 3])
+def test_k_1000_ladder_regime(oracle, k1000, m):
+    """half the rows allowed: the threshold ladder, planned on the allowed rows"""
+    _k1000_case(oracle, k1000, _random_filter(70_001, 0.5, 2), m)
+
+
+def test_k_1000_padding(oracle, k1000):
+    (ids, dists), _ = _k1000_case(oracle, k1000, _exactly(70_001, 600, 3), 100)
+    assert (ids[:, :600] != PAD).all() and (ids[:, 600:] == PAD).all() and np.isposinf(dists[:, 600:]).all()
+
+
 # 8. massive ties ---------------------------------------------------------------------------------
 def test_massive_ties(gpu, oracle):
     rng = np.random.RandomState(8)

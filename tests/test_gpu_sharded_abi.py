@@ -83,6 +83,62 @@ def test_fewer_rows_than_shards_and_padding(oracle):
     eng.close()
 
 
+@pytest.mark.parametrize("pattern", [1, 2])
+def test_k_2048_merges_from_global_memory(oracle, pattern):
+    """3 shards x k = 2048: 6144 entries per query are more than the merge stages in LDS (4096), so the instance
+    that searches the lists where they lie runs, behind both exchange patterns"""
+    from expann_amd import ShardedBruteForceEngine
+    rng = np.random.RandomState(2048)
+    n, d, m, k = 70_001, 64, 50, 2048
+    base = rng.standard_normal((n, d)).astype(np.float32)
+    q = rng.standard_normal((m, d)).astype(np.float32)
+    eng = ShardedBruteForceEngine(d, "l2", "f32", devices=[0] * 3)
+    eng.set_option("exchange_pattern", pattern)
+    eng.store_many_vectors(base)
+    eng.build()
+    assert eng.shards() == 3 and eng.exchange_pattern() == pattern
+    got = eng.query_k_batch(q, k)
+    eng.close()
+    assert _same(got, oracle.brute_force(base, q, k, oracle.METRIC_L2_F32, n_threads=16)), "oracle"
+    assert _same(got, _plain(base, q, k)), "plain index"
+
+
+def test_k_beyond_the_rows_of_a_shard(oracle):
+    """5000 rows over 8 shards, k = 1000: every shard's list holds its 625 rows and 375 entries of padding"""
+    from expann_amd import ShardedBruteForceEngine
+    rng = np.random.RandomState(625)
+    n, d, m, k = 5000, 64, 50, 1000
+    base = rng.standard_normal((n, d)).astype(np.float32)
+    q = rng.standard_normal((m, d)).astype(np.float32)
+    eng = ShardedBruteForceEngine(d, "l2", "f32", devices=[0] * 8)
+    eng.store_many_vectors(base)
+    eng.build()
+    assert eng.shards() == 8
+    got = eng.query_k_batch(q, k)
+    eng.close()
+    assert (got[0] != np.uint64(2 ** 64 - 1)).all()
+    assert _same(got, oracle.brute_force(base, q, k, oracle.METRIC_L2_F32, n_threads=16)), "oracle"
+    assert _same(got, _plain(base, q, k)), "plain index"
+
+
+def test_k_beyond_the_bound_is_refused_by_value(oracle):
+    """k = 8193 through the sharded handle: EXPANN_ERR_UNSUPPORTED that names the bound, from the entry point
+    itself; the handle then serves k = 8192 (padded: 5000 rows) and k = 10"""
+    from expann_amd import ShardedBruteForceEngine, _lib
+    rng = np.random.RandomState(8193)
+    base = rng.standard_normal((5000, 64)).astype(np.float32)
+    q = rng.standard_normal((5, 64)).astype(np.float32)
+    eng = ShardedBruteForceEngine(64, "l2", "f32", devices=[0] * 3)
+    eng.store_many_vectors(base)
+    eng.build()
+    with pytest.raises(_lib.ExpannError) as ei:
+        eng.query_k_batch(q, 8193)
+    assert ei.value.code == _lib.ERR_UNSUPPORTED and "k <= 8192" in str(ei.value), ei.value
+    for k in (8192, 10):
+        assert _same(eng.query_k_batch(q, k), oracle.brute_force(base, q, k, oracle.METRIC_L2_F32, n_threads=8)), k
+    eng.close()
+
+
 def test_int8_ip_shards(oracle):
     from expann_amd import ShardedBruteForceEngine
     rng = np.random.RandomState(12)
