@@ -483,6 +483,9 @@ __global__ __launch_bounds__(kPruneThreads) void build_prune_kernel(BuildPrunePa
 					t4[ll] = t8[ll + 4] + t8[ll];
 				const float co = (t4[0] + t4[2]) + (t4[1] + t4[3]);
 				if (co < basic[j]) {
+					// the reference's expression, each operation rounded: hipcc would fuse term + bias into one
+					// FMA (the host builder does not), which shows with a nonzero ortho_bias
+#pragma clang fp contract(off)
 					const float term = p.ortho_factor * (basic[j] - co);
 					res[j] += term + p.ortho_bias;
 					if (--len[j] == 0)

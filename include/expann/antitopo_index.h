@@ -13,7 +13,8 @@
 //   * flatten()                     CSR arrays for the device (expann_graph_create)
 // Distances during construction use the reference's 16-lane FMA order (src/distance.h:86-111 via
 // src/antitopo_engine.h:25-37), written as plain loops.  Floating-point contraction of the
-// "ortho" score expression is compiler-dependent in the reference; this code does not contract.
+// "ortho" score expression is compiler-dependent in the reference; this code does not contract,
+// whatever -ffp-contract says (ortho_term below), and neither does the GPU builder.
 #pragma once
 
 #include <algorithm>
@@ -75,6 +76,27 @@ public:
 		return r;
 	}
 };
+
+// ortho_factor * x + ortho_bias of the "ortho" scores as two rounded operations, never one fused
+// multiply-add: compilers contract across statements by default where the target has FMA (g++ always,
+// hipcc for host and device), and with a nonzero bias the one rounding less can change which edge wins.
+#if defined(__clang__)
+inline float ortho_term(float factor, float x, float bias) {
+#pragma clang fp contract(off)
+	const float term = factor * x;
+	return term + bias;
+}
+#elif defined(__GNUC__)
+__attribute__((optimize("fp-contract=off"))) inline float ortho_term(float factor, float x, float bias) {
+	const float term = factor * x;
+	return term + bias;
+}
+#else
+inline float ortho_term(float factor, float x, float bias) {
+	volatile float term = factor * x;
+	return term + bias;
+}
+#endif
 
 // fp32 squared L2 in the lane order of src/distance.h:86-111 / :136-147
 inline float dist2_ref_order(const float* a, const float* b, size_t d) {
@@ -213,8 +235,7 @@ struct antitopo_index {
 			for (auto& pr : ret) {
 				const float co = d2(row(pr.second), row(e.second));
 				if (co < basic) {
-					const float term = conf.ortho_factor * (basic - co);
-					res += term + conf.ortho_bias;
+					res += ortho_term(conf.ortho_factor, basic - co, conf.ortho_bias);
 					if (--leniency == 0)
 						return prune_score;
 				}
@@ -252,8 +273,7 @@ struct antitopo_index {
 				for (size_t prev : ortho_points) {
 					const float co = d2(row(prev), row(idx));
 					if (co < basic) {
-						const float term = conf.ortho_factor * (basic - co);
-						res += term + conf.ortho_bias;
+						res += ortho_term(conf.ortho_factor, basic - co, conf.ortho_bias);
 					}
 				}
 				return res;
@@ -338,8 +358,7 @@ struct antitopo_index {
 						for (size_t prev : entry_points) {
 							const float co = d2(row(prev), row(idx));
 							if (co < basic) {
-								const float term = conf.ortho_factor * (basic - co);
-								res += term + conf.ortho_bias;
+								res += ortho_term(conf.ortho_factor, basic - co, conf.ortho_bias);
 							}
 						}
 						return res;

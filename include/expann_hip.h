@@ -337,7 +337,22 @@ int expann_graph_get_stat(expann_graph* g, const char* name, uint64_t* out);
  * degu, upper_idx[v] = -1 for level-0 vertices.  On return rows hold at most M0 / M edges (id,
  * reference-order distance).  stats[4] (optional): batches, reverse edges dropped for want of slack,
  * rows re-pruned, 0.  ortho_count = 1 only (the reference's sweep, src/bench_runner.h:138).  dim: as
- * expann_graph_create (multiple of 16 up to 4096, checked before any device lookup). */
+ * expann_graph_create (multiple of 16 up to 4096, checked before any device lookup).
+ * THE BATCH RULE.  The first batch is [b0, b1) with b0 = n_built and b1 = min(n, b0 + min(max_batch, max(1,
+ * b0 / 16))) (max_batch = 0: 32768): at most 1/16 of the graph so far.  It is cut short before the first vertex
+ * whose level is >= max_layer; such a vertex, when it comes first, is a batch of its own.  After a batch,
+ * max_layer and starting_vertex advance as in :459-462, once per layer a vertex of the batch opens (a level may
+ * skip layers); the next batch starts at b1.  Within a batch: every search runs on the graph as it stood before
+ * the batch (greedy descent from starting_vertex through the layers above the vertex's level -- per pass the
+ * first occurrence of the row's minimum, taken only if strictly better -- then the ef_construction search of
+ * every layer <= min(level, max_layer - 1), top down, each seeded with the nearest of the layer above; a row is
+ * read up to min(degree, stride)); prune_edges on every candidate list in (distance, id) order, the score
+ * res += ortho_factor * (basic - co) + ortho_bias with every operation rounded (no fused multiply-add), the
+ * first of equal scores wins; the reverse edge (distance, new vertex) goes to every kept neighbour's row -- a
+ * row takes `stride` entries, further ones are dropped and counted in stats[1]; every row whose length passed
+ * M0 / M is sorted and pruned once.  Everything but the order of the appended entries in a row that was not
+ * re-pruned is determined (tests/test_gpu_graph_build_exact.py compares it batch by batch, bit for bit, with a
+ * CPU restatement of this paragraph). */
 int expann_graph_build_batched(int dim, int device, const float* vectors, size_t n, const uint8_t* levels,
                                size_t n_built, uint32_t* max_layer_io, uint32_t* starting_vertex_io, size_t M,
                                size_t M0, size_t ef_construction, size_t prune_overflow, float ortho_factor,

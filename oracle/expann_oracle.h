@@ -152,6 +152,31 @@ size_t oracle_graph_query_k(oracle_graph* g, const float* q, size_t k, size_t ef
                             uint64_t* n_distcomps);
 
 
+/* expann_graph_build_batched (include/expann_hip.h) restated on the CPU from the reference's _store_vector /
+ * prune_edges / query_k_at_layer (src/antitopo_engine.h:263-465, :495-708, ortho_count = 1) and the header's
+ * contract: the same arguments and strided arrays (no device), in place.  Batches: the first is [b0, b1) with
+ * b0 = n_built, b1 = oracle_graph_batch_end(levels, n, b0, max_layer, max_batch) = min(n, b0 + min(max_batch or
+ * 32768, max(1, b0 / 16))), cut short before the first vertex whose level is >= max_layer (which goes alone when
+ * it comes first); max_layer / starting_vertex advance after the batch (:459-462).  Per batch: every new vertex
+ * is searched against the graph before the batch (greedy descent, then the ef_construction search of each layer
+ * it joins, rows read up to min(deg, stride)); prune_edges on each candidate list; the reverse edges appended in
+ * ascending new-vertex order (a row takes `stride` entries, further ones are counted in stats[1] and the degree
+ * counts on); prune_edges once on every row whose length passed M0 / M.  Scores are unfused, each operation
+ * rounded (-ffp-contract=off).  With max_batch = 1 this is the serial algorithm.
+ * Extra outputs (each optional): *tie_hazards = pairs of distinct vertices with bit-equal distances that were
+ * pushed into the queues of one (vertex, layer) search or compared in one pass of the descent -- the only places
+ * where the order of a row's entries can change the result; ordered0[n] / orderedu[U * n_upper_layers] = 1 for
+ * the rows whose last change in this call was a prune (their entries are in a determined order), 0 for rows
+ * that were appended to afterwards or not touched.  Returns 0, or -1 for bad arguments. */
+size_t oracle_graph_batch_end(const uint8_t* levels, size_t n, size_t b0, uint32_t max_layer, size_t max_batch);
+int oracle_graph_build_batched(size_t dim, const float* vectors, size_t n, const uint8_t* levels, size_t n_built,
+                               uint32_t* max_layer_io, uint32_t* starting_vertex_io, size_t M, size_t M0,
+                               size_t ef_construction, size_t prune_overflow, float ortho_factor, float ortho_bias,
+                               size_t max_batch, uint32_t* ids0, float* d0, uint32_t* deg0, size_t stride0,
+                               const int32_t* upper_idx, size_t U, size_t n_upper_layers, uint32_t* idsu, float* du,
+                               uint32_t* degu, size_t strideu, uint64_t* stats, uint64_t* tie_hazards,
+                               uint8_t* ordered0, uint8_t* orderedu);
+
 /* Test hook: a trace of priority-queue operations through the heap code the graph search above
  * uses (libstdc++'s make_heap / push_heap / pop_heap as restated in expann_oracle_graph.c),
  * comparator on the distance only (src/antitopo_engine.h:540-545).  Pinned against the image's real

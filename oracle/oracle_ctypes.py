@@ -97,6 +97,14 @@ def _sig(lib):
     lib.oracle_graph_query_k.restype = C.c_size_t
     lib.oracle_graph_query_k.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int,
                                          C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.oracle_graph_batch_end.restype = C.c_size_t
+    lib.oracle_graph_batch_end.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_size_t]
+    lib.oracle_graph_build_batched.restype = C.c_int
+    lib.oracle_graph_build_batched.argtypes = \
+        [C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p] + \
+        [C.c_size_t] * 4 + [C.c_float, C.c_float, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                            C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + \
+        [C.c_void_p] * 4
     lib.oracle_heap_trace.restype = C.c_size_t
     lib.oracle_heap_trace.argtypes = [C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t] + \
         [C.c_void_p] * 8
@@ -315,3 +323,35 @@ class Graph:
         if getattr(self, "_g", None):
             lib().oracle_graph_destroy(self._g)
             self._g = None
+
+
+def graph_batch_end(levels, n, b0, max_layer, max_batch=0):
+    """where the batched builder's batch that starts at b0 ends (oracle_graph_batch_end)"""
+    levels = np.ascontiguousarray(levels, dtype=np.uint8)
+    return int(lib().oracle_graph_batch_end(_ptr(levels), n, b0, max_layer, max_batch))
+
+
+def graph_build_batched(vectors, n, levels, n_built, max_layer, starting_vertex, M, M0, ef_construction,
+                        prune_overflow, ortho_factor, ortho_bias, max_batch, ids0, d0, deg0, upper_idx, U,
+                        n_upper_layers, idsu, du, degu):
+    """oracle_graph_build_batched on the caller's strided arrays (C-contiguous numpy arrays of the ABI's
+    types, changed in place; row strides = their second dimension).  Returns a dict: max_layer,
+    starting_vertex, stats[4], tie_hazards, ordered0[n], orderedu[U * n_upper_layers]."""
+    for a, dt in ((vectors, np.float32), (levels, np.uint8), (ids0, np.uint32), (d0, np.float32),
+                  (deg0, np.uint32), (upper_idx, np.int32), (idsu, np.uint32), (du, np.float32),
+                  (degu, np.uint32)):
+        assert a.dtype == dt and a.flags.c_contiguous
+    ml, sv = C.c_uint32(max_layer), C.c_uint32(starting_vertex)
+    stats = np.zeros(4, np.uint64)
+    hazards = C.c_uint64(0)
+    ordered0 = np.zeros(n, np.uint8)
+    orderedu = np.zeros(max(1, U * n_upper_layers), np.uint8)
+    rc = lib().oracle_graph_build_batched(
+        vectors.shape[1], _ptr(vectors), n, _ptr(levels), n_built, C.addressof(ml), C.addressof(sv), M, M0,
+        ef_construction, prune_overflow, ortho_factor, ortho_bias, max_batch, _ptr(ids0), _ptr(d0), _ptr(deg0),
+        ids0.shape[1], _ptr(upper_idx), U, n_upper_layers, _ptr(idsu), _ptr(du), _ptr(degu), idsu.shape[1],
+        _ptr(stats), C.addressof(hazards), _ptr(ordered0), _ptr(orderedu))
+    if rc != 0:
+        raise ValueError("oracle_graph_build_batched: bad arguments")
+    return dict(max_layer=ml.value, starting_vertex=sv.value, stats=stats, tie_hazards=hazards.value,
+                ordered0=ordered0, orderedu=orderedu[:U * n_upper_layers])
