@@ -39,6 +39,8 @@ ABI_SYMBOLS = [
     "expann_graph_search_device", "expann_graph_sync", "expann_graph_set_option", "expann_graph_get_stat",
     "expann_antitopo_query_device", "expann_antitopo_sync",
     "expann_set_row_filter", "expann_set_row_filter_device", "expann_clear_row_filter",
+    "expann_graph_set_row_filter", "expann_graph_set_row_filter_device", "expann_graph_clear_row_filter",
+    "expann_antitopo_set_row_filter", "expann_antitopo_set_row_filter_device",
 ]
 
 
@@ -270,6 +272,17 @@ def load():
         L.expann_set_row_filter_device.argtypes = [vp, vp, sz, vp]
         L.expann_clear_row_filter.restype = C.c_int
         L.expann_clear_row_filter.argtypes = [vp]
+    if hasattr(L, "expann_graph_set_row_filter"):  # (as above: an older build has no graph filter)
+        L.expann_graph_set_row_filter.restype = C.c_int
+        L.expann_graph_set_row_filter.argtypes = [vp, vp, sz]
+        L.expann_graph_set_row_filter_device.restype = C.c_int
+        L.expann_graph_set_row_filter_device.argtypes = [vp, vp, sz, vp]
+        L.expann_graph_clear_row_filter.restype = C.c_int
+        L.expann_graph_clear_row_filter.argtypes = [vp]
+        L.expann_antitopo_set_row_filter.restype = C.c_int
+        L.expann_antitopo_set_row_filter.argtypes = [vp, vp, sz]
+        L.expann_antitopo_set_row_filter_device.restype = C.c_int
+        L.expann_antitopo_set_row_filter_device.argtypes = [vp, vp, sz, vp]
     _lib = L
     return L
 

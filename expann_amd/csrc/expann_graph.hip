@@ -10,10 +10,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <vector>
 
+#include "filter_rows.hpp"
 #include "graph_build.hpp"
+#include "graph_flat_scan.hpp"
 #include "graph_search.hpp"
 #include "host_common.hpp"
 #include "quantize.hpp"
@@ -56,6 +59,14 @@ struct expann_graph {
 	hipEvent_t ev_dev[3] = {nullptr, nullptr, nullptr};  // before the first launch, after it, after the redo launch
 	bool dev_timed = false, dev_timed_redo = false;       // ev_dev hold the last search (and its redo launch)
 	long opt_cand_cap = 0, opt_redo_cap = 0;
+	// ---- row filter (expann_graph_set_row_filter): the handle's copy of the bitmap, zero from n on, and the
+	// allowed vertices as an ascending list (what the scan of a sparse filter reads), both made at set time
+	DevPtr<uint32_t> d_allow;       // [ceil(n / 32)]
+	DevPtr<uint32_t> d_allow_list;  // [n_allowed]
+	bool filter_on = false;
+	uint32_t n_allowed = 0;
+	long opt_flat_rows = 0;         // "filter_flat_rows": 0 = kGraphFlatRowsAuto
+	uint64_t stat_flat = 0;         // searches answered without a walk
 	// what the drains since the last sync found, and the counters behind expann_graph_get_stat
 	uint64_t pend_redo_queries = 0, pend_overflows = 0;
 	uint64_t stat_redo_queries = 0, stat_redo_overflows = 0, stat_deferred = 0, stat_distcomps = 0;
@@ -78,15 +89,19 @@ namespace {
 using GraphFn = void (*)(GraphSearchParams);
 struct GraphVariant {
 	int d;
-	int mode;  // expann_graph_compression
+	int mode;       // expann_graph_compression
+	bool filtered;  // the instance that walks under a row filter (THE FILTER RULE, graph_search.hpp)
 	GraphFn fn;
 };
-#define GRAPH_V(D)                                                                                              \
-	{D, kGraphF32, graph_search_kernel<D, kGraphF32>}, {D, kGraphU8Cast, graph_search_kernel<D, kGraphU8Cast>}, \
-	{D, kGraphRangedQ8, graph_search_kernel<D, kGraphRangedQ8>}
+#define GRAPH_VF(D, F)                                                          \
+	{D, kGraphF32, F, graph_search_kernel<D, kGraphF32, 0, F>},                 \
+	{D, kGraphU8Cast, F, graph_search_kernel<D, kGraphU8Cast, 0, F>},           \
+	{D, kGraphRangedQ8, F, graph_search_kernel<D, kGraphRangedQ8, 0, F>}
+#define GRAPH_V(D) GRAPH_VF(D, false), GRAPH_VF(D, true)
 const GraphVariant kGraph[] = {GRAPH_V(64),  GRAPH_V(128), GRAPH_V(256), GRAPH_V(512),
                                GRAPH_V(768), GRAPH_V(832), GRAPH_V(960), GRAPH_V(0)};
 #undef GRAPH_V
+#undef GRAPH_VF
 // quantizer_simple<uint8_t> of n_values floats: launches of at most 2^30 values (a dispatch's grid is
 // counted in 32-bit work-items: 1.05 M rows x 4096 in one launch would wrap)
 void launch_quantize_simple_u8(const float* in, size_t n_values, uint8_t* out, hipStream_t st) {
@@ -98,10 +113,10 @@ void launch_quantize_simple_u8(const float* in, size_t n_values, uint8_t* out, h
 	}
 }
 // the compiled instance of `dim`, else the run-time-dim one (d = 0)
-const GraphVariant* graph_variant(int dim, int mode) {
+const GraphVariant* graph_variant(int dim, int mode, bool filtered) {
 	const GraphVariant* any = nullptr;
 	for (const auto& v : kGraph)
-		if (v.mode == mode) {
+		if (v.mode == mode && v.filtered == filtered) {
 			if (v.d == dim)
 				return &v;
 			if (v.d == 0)
@@ -123,9 +138,9 @@ int graph_dim_error(const char* fn, int dim) {
 	return EXPANN_OK;
 }
 // the instrumented instance (EXPANN_GRAPH_STAMPS=1, d = 128): per-phase shader clocks of a hop
-const GraphVariant kGraphDbg[] = {{128, kGraphF32, graph_search_kernel<128, kGraphF32, 1>},
-                                  {128, kGraphU8Cast, graph_search_kernel<128, kGraphU8Cast, 1>},
-                                  {128, kGraphRangedQ8, graph_search_kernel<128, kGraphRangedQ8, 1>}};
+const GraphVariant kGraphDbg[] = {{128, kGraphF32, false, graph_search_kernel<128, kGraphF32, 1>},
+                                  {128, kGraphU8Cast, false, graph_search_kernel<128, kGraphU8Cast, 1>},
+                                  {128, kGraphRangedQ8, false, graph_search_kernel<128, kGraphRangedQ8, 1>}};
 const char* const kGraphModeName[] = {"f32", "u8", "q8"};
 
 // min / max of n_values floats, then their quantizer_ranged_q8 bytes and scale_factor / offset (quantize.hpp);
@@ -184,6 +199,15 @@ int graph_ensure_ranged(expann_graph* g) {
 constexpr size_t kGraphMaxLds = 160 * 1024;     // the working set a search may take of a CU's LDS
 constexpr uint32_t kGraphMaxOutstanding = 256;  // device-buffer searches between two drains
 constexpr uint32_t kGraphCtrWords = 8;          // counter words per search
+// "filter_flat_rows" on auto: a filter that allows at most this many rows is scanned, not walked.  The largest
+// measured count at which the scan still beats the walk or the walk still overflows, on the C4 graph (DESIGN 4.9f,
+// profiles/graph_filter_ab.txt: at 128 000 rows the scan takes 49 ms against the walk's 110 ms, at 256 000 rows
+// 125 ms against 42 ms; the walk overflows its redo capacity up to 32 000 rows).
+constexpr uint32_t kGraphFlatRowsAuto = 128000;
+// min(k, allowed) the scan keeps in LDS; beyond it the search walks.  Not measured: the scan's final ranking reads
+// keys^2 / 64 LDS words per lane and each replacement scans keys / 64, so the bound is held where that work (16 k
+// reads per lane and query) stays small next to scoring the rows.
+constexpr uint32_t kGraphFlatMaxKeys = 1024;
 
 // the argument checks of a search, in the order the header documents, all before the device is touched;
 // *empty: m == 0, nothing to do
@@ -241,6 +265,7 @@ GraphSearchParams graph_base_params(const expann_graph* g, int mode, size_t k, s
 	p.vis_words = g->vis_words;
 	p.epochs = g->d_epochs;
 	p.dim = (uint32_t)g->dim;
+	p.allow_bits = g->filter_on ? g->d_allow.get() : nullptr;
 	if (const char* e = std::getenv("EXPANN_GRAPH_DEBUG"))
 		p.debug = (uint32_t)std::atol(e);
 	return p;
@@ -402,6 +427,114 @@ int graph_enqueue_redo(expann_graph* g, const GraphSearchPlan& pl, hipStream_t s
 	hipLaunchKernelGGL(pl.fn, dim3(pl.grid_redo), dim3(64), pl.lds_redo, st, pl.redo);
 	HIP_TRY(g, hipEventRecord(after, st));
 	HIP_TRY(g, hipGetLastError());
+	return EXPANN_OK;
+}
+
+// ---- searches under a row filter that do not walk ---------------------------------------------
+// how a search of k neighbours is served under the filter in force: by the walk (no filter, or a dense one), by the
+// exact scan of the allowed rows (at most "filter_flat_rows" of them), or -- no row allowed -- by padding alone
+enum GraphServe { kServeWalk, kServeScan, kServePad };
+GraphServe graph_serve(const expann_graph* g, size_t k) {
+	if (!g->filter_on)
+		return kServeWalk;
+	if (g->n_allowed == 0)
+		return kServePad;
+	const uint32_t flat_rows = g->opt_flat_rows ? (uint32_t)std::min<long>(g->opt_flat_rows, 0x7FFFFFFFL) : kGraphFlatRowsAuto;
+	const size_t kk = std::min<size_t>(k, g->n_allowed);
+	if (g->n_allowed > flat_rows || kk > kGraphFlatMaxKeys || graph_flat_lds_bytes((uint32_t)kk, (uint32_t)g->dim) > kGraphMaxLds)
+		return kServeWalk;
+	return kServeScan;
+}
+
+// the scan of the allowed rows for the search whose queries and outputs `w` names (a walk's parameters: the scan
+// takes what it shares with them), with the counter slot `ctr`, on `st` between two events
+int graph_enqueue_flat(expann_graph* g, const GraphSearchParams& w, uint32_t* ctr, hipStream_t st, hipEvent_t before,
+                       hipEvent_t after) {
+	GraphFlatParams f{};
+	f.vectors = g->d_vectors;
+	f.dim = (uint32_t)g->dim;
+	f.list = g->d_allow_list;
+	f.n_list = g->n_allowed;
+	f.queries = w.queries;
+	f.m = w.m;
+	f.k = w.k;
+	f.kk = std::min<uint32_t>(w.k, g->n_allowed);
+	f.out_ids = w.out_ids;
+	f.out_dists = w.out_dists;
+	f.out_distcomps = w.out_distcomps;
+	f.next_query = ctr + 1;
+	f.distcomps_total = w.distcomps_total;
+	const size_t lds = graph_flat_lds_bytes(f.kk, f.dim);
+	uint32_t resident = 0;
+	if (int rc = graph_plan(g, (const void*)graph_flat_scan_kernel, lds, &resident))
+		return rc;
+	HIP_TRY(g, hipMemsetAsync(ctr, 0, sizeof(uint32_t) * kGraphCtrWords, st));
+	HIP_TRY(g, hipEventRecord(before, st));
+	hipLaunchKernelGGL(graph_flat_scan_kernel, dim3((uint32_t)std::min<size_t>(w.m, resident)), dim3(64), lds, st, f);
+	HIP_TRY(g, hipEventRecord(after, st));
+	HIP_TRY(g, hipGetLastError());
+	++g->stat_flat;
+	return EXPANN_OK;
+}
+
+// a filter that allows no row, device buffers: padding and distcomps 0 in the order of `st`
+int graph_enqueue_pad(expann_graph* g, const GraphSearchParams& w, uint32_t* ctr, hipStream_t st) {
+	const size_t cells = (size_t)w.m * w.k;
+	HIP_TRY(g, hipMemsetAsync(ctr, 0, sizeof(uint32_t) * kGraphCtrWords, st));
+	hipLaunchKernelGGL(fill_pad_kernel, dim3((uint32_t)std::min<size_t>((cells + kBlock - 1) / kBlock, 1024)), dim3(kBlock), 0,
+	                   st, w.out_ids, w.out_dists, cells);
+	HIP_TRY(g, hipGetLastError());
+	if (w.out_distcomps)
+		HIP_TRY(g, hipMemsetAsync(w.out_distcomps, 0, sizeof(uint32_t) * w.m, st));
+	++g->stat_flat;
+	return EXPANN_OK;
+}
+
+// bits: n_words words in host (on_device = false) or device memory, read in the order of `user_st` (nullptr = the
+// handle's own stream).  The new copy and list are made aside and put in place when complete: a failed call
+// leaves the filter as it was.
+int graph_set_row_filter(expann_graph* g, const uint32_t* bits, size_t n_words, bool on_device, hipStream_t user_st) {
+	if (!g)
+		return EXPANN_ERR_INVALID_ARG;
+	if (!bits)
+		return g->fail(EXPANN_ERR_INVALID_ARG, "row filter: NULL bits");
+	const size_t need_words = (g->n + 31) / 32;
+	if (n_words < need_words)
+		return g->fail(EXPANN_ERR_INVALID_ARG, "row filter: " + std::to_string(n_words) + " words for " +
+		                                           std::to_string(g->n) + " rows (need " + std::to_string(need_words) + ")");
+	HIP_TRY(g, hipSetDevice(g->device));
+	// searches in flight still read the old filter: they are waited for (their counters stay for the next sync)
+	HIP_TRY(g, graph_wait_outstanding(g));
+	hipStream_t st = user_st ? user_st : g->stream;
+	DevPtr<uint32_t> b_bits, b_stat, b_list;
+	HIP_TRY(g, hipMalloc(&b_bits, sizeof(uint32_t) * need_words));
+	HIP_TRY(g, hipMalloc(&b_stat, sizeof(uint32_t) * (2 + kFilterSegs)));
+	HIP_TRY(g, hipMemcpyAsync(b_bits, bits, sizeof(uint32_t) * need_words,
+	                          on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+	HIP_TRY(g, hipMemsetAsync(b_stat, 0, sizeof(uint32_t) * (2 + kFilterSegs), st));
+	hipLaunchKernelGGL(filter_count_kernel, dim3(kFilterSegs), dim3(kBlock), 0, st, b_bits.get(), (uint32_t)g->n,
+	                   (uint32_t)need_words, b_stat.get(), b_stat.get() + 2);
+	HIP_TRY(g, hipGetLastError());
+	uint32_t stat[2] = {0, 0};
+	HIP_TRY(g, hipMemcpyAsync(stat, b_stat, sizeof(stat), hipMemcpyDeviceToHost, st));
+	HIP_TRY(g, hipStreamSynchronize(st));  // walk or scan is chosen on the host: one wait per filter change
+	const uint32_t allowed = stat[0];
+	if (allowed) {
+		HIP_TRY(g, hipMalloc(&b_list, sizeof(uint32_t) * allowed));
+		hipLaunchKernelGGL(filter_compact_kernel, dim3(kFilterSegs), dim3(kBlock), 0, st, (const uint32_t*)b_bits.get(),
+		                   (uint32_t)need_words, (const uint32_t*)b_stat.get() + 2, 1u, b_list.get(), allowed);
+		HIP_TRY(g, hipGetLastError());
+		HIP_TRY(g, hipStreamSynchronize(st));
+	}
+	if (st != g->stream)
+		HIP_TRY(g, hipStreamSynchronize(g->stream));
+	g->d_allow.reset();
+	g->d_allow_list.reset();
+	g->d_allow.p = b_bits.p;
+	g->d_allow_list.p = b_list.p;
+	b_bits.p = b_list.p = nullptr;
+	g->n_allowed = allowed;
+	g->filter_on = true;
 	return EXPANN_OK;
 }
 
@@ -603,16 +736,27 @@ int expann_graph_search_mode(expann_graph* g, const float* queries, size_t m, si
 		return EXPANN_OK;
 	HIP_TRY(g, hipSetDevice(g->device));
 	HIP_TRY(g, graph_wait_outstanding(g));  // (one set of visited arrays: device-buffer searches in flight go first)
-	const GraphVariant* gv = graph_variant(g->dim, mode);
+	const GraphServe serve = graph_serve(g, k);
+	if (serve == kServePad) {  // the filter allows no row: nothing to walk or scan
+		std::fill(ids, ids + m * k, UINT64_MAX);
+		std::fill(dists, dists + m * k, std::numeric_limits<float>::infinity());
+		if (distcomps)
+			std::fill(distcomps, distcomps + m, 0u);
+		++g->stat_flat;
+		g->last_ms = 0;
+		return EXPANN_OK;
+	}
+	const GraphVariant* gv = graph_variant(g->dim, mode, g->filter_on);
 	if (!gv)
 		return g->fail(EXPANN_ERR_UNSUPPORTED, "no graph kernel for this dim");
-	const bool stamps = std::getenv("EXPANN_GRAPH_STAMPS") != nullptr && g->dim == 128;
+	const bool stamps = std::getenv("EXPANN_GRAPH_STAMPS") != nullptr && g->dim == 128 && !g->filter_on;
 	if (stamps)
 		gv = &kGraphDbg[mode];
 	if (int rc = graph_dev_init(g))
 		return rc;
-	if (int rc = graph_ensure_bytes(g, mode))
-		return rc;
+	if (serve == kServeWalk)
+		if (int rc = graph_ensure_bytes(g, mode))
+			return rc;
 	hipStream_t st = g->stream;
 	DevBuf b_q, b_ids, b_d, b_dc, b_stamps;
 	const size_t qb = m * (size_t)g->dim * sizeof(float), stamp_bytes = sizeof(unsigned long long) * 8 * g->slots;
@@ -633,6 +777,19 @@ int expann_graph_search_mode(expann_graph* g, const float* queries, size_t m, si
 	// the slot behind those of the device-buffer searches: theirs stay as they are for the next sync
 	uint32_t* ctr = g->d_dev_ctr + (size_t)kGraphMaxOutstanding * kGraphCtrWords;
 	uint32_t* h_ctr = g->h_dev_ctr + (size_t)kGraphMaxOutstanding * kGraphCtrWords;
+	if (serve == kServeScan) {  // a sparse filter: the exact scan of the allowed rows
+		if (int rc = graph_enqueue_flat(g, p, ctr, st, g->ev0, g->ev1))
+			return rc;
+		HIP_TRY(g, hipStreamSynchronize(st));
+		float ms = 0;
+		HIP_TRY(g, hipEventElapsedTime(&ms, g->ev0, g->ev1));
+		g->last_ms = ms;
+		HIP_TRY(g, hipMemcpy(ids, b_ids.p, sizeof(uint64_t) * m * k, hipMemcpyDeviceToHost));
+		HIP_TRY(g, hipMemcpy(dists, b_d.p, sizeof(float) * m * k, hipMemcpyDeviceToHost));
+		if (distcomps)
+			HIP_TRY(g, hipMemcpy(distcomps, b_dc.p, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
+		return EXPANN_OK;
+	}
 	GraphSearchPlan pl;
 	if (int rc = graph_search_plan(g, gv, p, ctr, &pl))
 		return rc;
@@ -679,7 +836,8 @@ int expann_graph_search_device(expann_graph* g, const float* d_queries, size_t m
 	if (empty)
 		return EXPANN_OK;
 	HIP_TRY(g, hipSetDevice(g->device));
-	const GraphVariant* gv = graph_variant(g->dim, mode);
+	const GraphServe serve = graph_serve(g, k);
+	const GraphVariant* gv = graph_variant(g->dim, mode, g->filter_on);
 	if (!gv)
 		return g->fail(EXPANN_ERR_UNSUPPORTED, "no graph kernel for this dim");
 	hipStream_t st = stream ? (hipStream_t)stream : g->stream;
@@ -691,8 +849,9 @@ int expann_graph_search_device(expann_graph* g, const float* d_queries, size_t m
 	if (g->dev_outstanding >= kGraphMaxOutstanding)
 		if (int rc = graph_drain(g))
 			return rc;
-	if (int rc = graph_ensure_bytes(g, mode))
-		return rc;
+	if (serve == kServeWalk)
+		if (int rc = graph_ensure_bytes(g, mode))
+			return rc;
 	GraphSearchParams p = graph_base_params(g, mode, k, ef_search);
 	p.queries = d_queries;
 	p.m = (uint32_t)m;
@@ -700,6 +859,20 @@ int expann_graph_search_device(expann_graph* g, const float* d_queries, size_t m
 	p.out_dists = d_dists;
 	p.out_distcomps = d_distcomps;
 	p.distcomps_total = g->d_dc_total;
+	if (serve != kServeWalk) {  // a sparse or empty filter: the scan, or padding alone, in the same stream order
+		uint32_t* ctr = g->d_dev_ctr + (size_t)g->dev_outstanding * kGraphCtrWords;
+		if (int rc = serve == kServeScan ? graph_enqueue_flat(g, p, ctr, st, g->ev_dev[0], g->ev_dev[1])
+		                                 : graph_enqueue_pad(g, p, ctr, st))
+			return rc;
+		g->dev_stream = st;
+		++g->dev_outstanding;
+		++g->stat_deferred;
+		g->dev_timed = serve == kServeScan;
+		g->dev_timed_redo = false;
+		if (serve == kServePad)
+			g->last_ms = 0;
+		return EXPANN_OK;
+	}
 	GraphSearchPlan pl;
 	if (int rc = graph_search_plan(g, gv, p, g->d_dev_ctr + (size_t)g->dev_outstanding * kGraphCtrWords, &pl))
 		return rc;
@@ -748,6 +921,12 @@ int expann_graph_set_option(expann_graph* g, const char* name, long value) {
 	if (!name)
 		return g->fail(EXPANN_ERR_INVALID_ARG, "NULL option name");
 	const std::string o(name);
+	if (o == "filter_flat_rows") {  // rows, not a capacity: any count, 0 = auto
+		if (value < 0)
+			return g->fail(EXPANN_ERR_INVALID_ARG, "filter_flat_rows must be >= 0 (0 = auto)");
+		g->opt_flat_rows = value;
+		return EXPANN_OK;
+	}
 	const bool cand = o == "cand_capacity";
 	if (!cand && o != "redo_capacity")
 		return g->fail(EXPANN_ERR_INVALID_ARG, "unknown option: " + o);
@@ -755,6 +934,25 @@ int expann_graph_set_option(expann_graph* g, const char* name, long value) {
 	if (value != 0 && (value < 8 || (value & (value - 1)) != 0 || value > (cand ? (1L << 20) : 8192L)))
 		return g->fail(EXPANN_ERR_INVALID_ARG, o + " must be 0 or a power of two >= 8" + (cand ? "" : " and <= 8192"));
 	(cand ? g->opt_cand_cap : g->opt_redo_cap) = value;
+	return EXPANN_OK;
+}
+
+int expann_graph_set_row_filter(expann_graph* g, const uint32_t* allow_bits, size_t n_words) {
+	return graph_set_row_filter(g, allow_bits, n_words, false, nullptr);
+}
+
+int expann_graph_set_row_filter_device(expann_graph* g, const uint32_t* d_allow_bits, size_t n_words, void* stream) {
+	return graph_set_row_filter(g, d_allow_bits, n_words, true, (hipStream_t)stream);
+}
+
+int expann_graph_clear_row_filter(expann_graph* g) {
+	if (!g)
+		return EXPANN_ERR_INVALID_ARG;
+	if (g->dev_outstanding) {  // (searches enqueued under the filter finish under it)
+		HIP_TRY(g, hipSetDevice(g->device));
+		HIP_TRY(g, graph_wait_outstanding(g));
+	}
+	g->filter_on = false;
 	return EXPANN_OK;
 }
 
@@ -774,6 +972,12 @@ int expann_graph_get_stat(expann_graph* g, const char* name, uint64_t* out) {
 		*out = g->stat_distcomps;
 	else if (o == "redo_kernel_ns")
 		*out = (uint64_t)(g->stat_redo_ms * 1e6);
+	else if (o == "filter_active")
+		*out = g->filter_on ? 1 : 0;
+	else if (o == "filter_rows")
+		*out = g->filter_on ? g->n_allowed : g->n;
+	else if (o == "flat_searches")
+		*out = g->stat_flat;
 	else
 		return g->fail(EXPANN_ERR_INVALID_ARG, "unknown stat: " + o);
 	return EXPANN_OK;
@@ -1141,6 +1345,7 @@ const char* expann_antitopo_last_error(const expann_antitopo* e) {
 int expann_antitopo_store(expann_antitopo* e, const float* rows, size_t n) {
 	if (!e || (!rows && n))
 		return EXPANN_ERR_INVALID_ARG;
+	e->eng->clear_row_filter();
 	ANTITOPO_TRY(e, for (size_t i = 0; i < n; ++i) e->eng->index.insert(rows + i * (size_t)e->dim));
 	return EXPANN_OK;
 }
@@ -1148,6 +1353,7 @@ int expann_antitopo_store(expann_antitopo* e, const float* rows, size_t n) {
 int expann_antitopo_store_batched(expann_antitopo* e, const float* rows, size_t n, size_t n_serial) {
 	if (!e || (!rows && n))
 		return EXPANN_ERR_INVALID_ARG;
+	e->eng->clear_row_filter();
 	ANTITOPO_TRY(e, e->eng->store_rows_batched(rows, n, n_serial ? n_serial : 2048));
 	return EXPANN_OK;
 }
@@ -1190,6 +1396,24 @@ int expann_antitopo_sync(expann_antitopo* e) {
 	if (!e->eng->graph)
 		return e->fail(EXPANN_ERR_NOT_BUILT, "expann_antitopo_sync before build()");
 	const int rc = e->eng->sync();
+	return rc == EXPANN_OK ? rc : e->fail(rc, expann_graph_last_error(e->eng->graph));
+}
+
+int expann_antitopo_set_row_filter(expann_antitopo* e, const uint32_t* allow_bits_or_NULL, size_t n_words) {
+	if (!e)
+		return EXPANN_ERR_INVALID_ARG;
+	if (!e->eng->graph)
+		return e->fail(EXPANN_ERR_NOT_BUILT, "expann_antitopo_set_row_filter before build()");
+	const int rc = e->eng->set_row_filter(allow_bits_or_NULL, n_words);
+	return rc == EXPANN_OK ? rc : e->fail(rc, expann_graph_last_error(e->eng->graph));
+}
+
+int expann_antitopo_set_row_filter_device(expann_antitopo* e, const uint32_t* d_allow_bits, size_t n_words, void* stream) {
+	if (!e)
+		return EXPANN_ERR_INVALID_ARG;
+	if (!e->eng->graph)
+		return e->fail(EXPANN_ERR_NOT_BUILT, "expann_antitopo_set_row_filter_device before build()");
+	const int rc = e->eng->set_row_filter_device(d_allow_bits, n_words, stream);
 	return rc == EXPANN_OK ? rc : e->fail(rc, expann_graph_last_error(e->eng->graph));
 }
 

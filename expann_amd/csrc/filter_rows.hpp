@@ -10,6 +10,7 @@
 // The engine's copy of the bitmap covers the padded row count of the fp16 copy and is zero from
 // row n on (filter_count_kernel clears what the caller left there), so no kernel reads a word
 // outside it and no padding row is ever allowed.
+// (The kernels are `static`: expann_hip.hip and expann_graph.hip both include this header.)
 #pragma once
 #include "common.hpp"
 
@@ -22,7 +23,7 @@ __host__ __device__ inline uint32_t filter_seg_words(uint32_t n_words) { return 
 
 // out[r] = allowed(r) ? in[r] : NaN over the n_pad floats of one row-term array (the NaN padding stays NaN:
 // its bits are zero).  n_pad is a multiple of 32 and at most 32 x the words of `bits`.
-__global__ __launch_bounds__(kBlock) void filter_row_terms_kernel(const uint32_t* __restrict__ bits,
+static __global__ __launch_bounds__(kBlock) void filter_row_terms_kernel(const uint32_t* __restrict__ bits,
                                                                     const float* __restrict__ in, float* __restrict__ out,
                                                                     uint32_t n_pad) {
 	for (size_t r = (size_t)blockIdx.x * kBlock + threadIdx.x; r < n_pad; r += (size_t)gridDim.x * kBlock) {
@@ -35,7 +36,7 @@ __global__ __launch_bounds__(kBlock) void filter_row_terms_kernel(const uint32_t
 // total, and the residues mod 32 that hold an allowed row are collected (a class of the sampled passes is
 // (chunk, row mod 32): the planner needs to know how many classes a filter can fill).
 // stat[0] = allowed rows, stat[1] = OR of all words; seg_cnt[kFilterSegs].  stat is zero on entry.
-__global__ __launch_bounds__(kBlock) void filter_count_kernel(uint32_t* __restrict__ bits, uint32_t n_rows, uint32_t n_words,
+static __global__ __launch_bounds__(kBlock) void filter_count_kernel(uint32_t* __restrict__ bits, uint32_t n_rows, uint32_t n_words,
                                                                 uint32_t* __restrict__ stat, uint32_t* __restrict__ seg_cnt) {
 	__shared__ uint32_t s_cnt, s_or;
 	if (threadIdx.x == 0)
@@ -75,7 +76,7 @@ __global__ __launch_bounds__(kBlock) void filter_count_kernel(uint32_t* __restri
 // list[j] = the allowed row of rank j * stride.  stride = 1 gives the complete list (the list path of a very
 // selective filter); a larger stride an even sample of the allowed rows (level 0 of the threshold ladder).
 // Same segments as pass 1, whose counts place each workgroup.
-__global__ __launch_bounds__(kBlock) void filter_compact_kernel(const uint32_t* __restrict__ bits, uint32_t n_words,
+static __global__ __launch_bounds__(kBlock) void filter_compact_kernel(const uint32_t* __restrict__ bits, uint32_t n_words,
                                                                   const uint32_t* __restrict__ seg_cnt, uint32_t stride,
                                                                   uint32_t* __restrict__ list, uint32_t list_cap) {
 	__shared__ uint32_t s_part[kBlock];
@@ -115,7 +116,7 @@ __global__ __launch_bounds__(kBlock) void filter_compact_kernel(const uint32_t* 
 }
 
 // a filter that allows no row: the outputs are padding only
-__global__ __launch_bounds__(kBlock) void fill_pad_kernel(uint64_t* __restrict__ ids, float* __restrict__ dists, size_t n) {
+static __global__ __launch_bounds__(kBlock) void fill_pad_kernel(uint64_t* __restrict__ ids, float* __restrict__ dists, size_t n) {
 	for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
 		ids[i] = ~0ull;
 		if (dists)

@@ -89,6 +89,9 @@ struct GraphSearchParams {
 	// != nullptr: every query adds its distcomps (one atomic from one lane); a query put on the redo list does
 	// not, the launch that walks it again does
 	unsigned long long* distcomps_total;
+	// FILTERED instances only (nullptr in unfiltered launches): the row filter, bit v & 31 of word v >> 5 says
+	// whether vertex v may appear in a result; the handle's own copy, zero from n on (THE FILTER RULE below)
+	const uint32_t* allow_bits;
 };
 
 struct md_pair {
@@ -537,7 +540,28 @@ template <int D> constexpr int graph_rows_u8() { return D == 0 ? kGraphAnyRows :
 // compiler takes one or two more and loses the fourth wave)
 template <int MODE> constexpr int graph_any_dim_waves() { return MODE != kGraphF32 ? 4 : 3; }
 
-template <int D, int MODE, int DBG = 0>
+// THE FILTER RULE (FILTERED instances; p.allow_bits is a bitmap over vertex numbers, bit v & 31 of word v >> 5,
+// least significant bit first; bits at and beyond n are ignored: the library keeps its own copy, zero from n on).
+//   Descent: the entry evaluation and the greedy descent through the upper layers are unchanged and never look at
+//   the filter.
+//   Bottom-layer entry: the entry vertex is scored, marked visited and pushed on `candidates`; it is pushed on
+//   `nearest` only if it is allowed.
+//   Stop rule: stop when `candidates` is empty, or when nearest.size() == ef && cur.d > nearest.top().d.  While
+//   `nearest` holds fewer than ef entries -- none included: nearest[0] means nothing then -- only an empty
+//   `candidates` stops the walk.
+//   Neighbour update: for each unvisited neighbour in adjacency order with distance dn: if nearest.size() < ef ||
+//   dn < nearest.top().d, push it on `candidates`; if it is also allowed, push it on `nearest` and pop `nearest`
+//   when it exceeds ef.  A disallowed vertex is traversed but never kept.
+//   Pre-drop: a full `nearest` and !(dn < worst0) still drops a neighbour before the queue update (worst0 only
+//   falls while the queue is full).
+//   distcomps count every scored vertex, allowed or not.  Output as without a filter: drain `nearest`, reverse,
+//   re-score in fp32 in the byte modes, truncate to k, pad with UINT64_MAX / +inf.
+// With every bit set this is the unfiltered walk exactly (ids, distance bits, distcomps, all modes).
+// How the flag travels: the lane that holds a neighbour for the visited test also reads its allow word (both
+// requests are in flight together: no round trip is added to a hop) and leaves the flag in the SIGN BIT of the
+// neighbour's ndist slot -- distances are >= 0 --, the lane that stores the score keeps that bit, and every reader
+// strips it before it compares or stores.  No LDS, scratch or serial read is added.
+template <int D, int MODE, int DBG = 0, bool FILTERED = false>
 __global__ __launch_bounds__(64, D == 0 ? graph_any_dim_waves<MODE>() : ((MODE != kGraphF32 && D <= 128) ? 4 : 1)) void graph_search_kernel(GraphSearchParams p) {
 	constexpr bool COMPRESSED = MODE != kGraphF32, RANGED = MODE == kGraphRangedQ8;
 	constexpr int DPL = D ? D / 16 : 1;
@@ -749,7 +773,11 @@ __global__ __launch_bounds__(64, D == 0 ? graph_any_dim_waves<MODE>() : ((MODE !
 		{
 			const md_pair e{d_entry, entry};
 			coop_push<false>(candidates, n_cand, e, lane, p.debug & 1);
-			coop_push<true>(nearest, n_near, e, lane, p.debug & 1);
+			bool keep_entry = true;  // wave-uniform
+			if constexpr (FILTERED)
+				keep_entry = (p.allow_bits[entry >> 5] >> (entry & 31)) & 1u;
+			if (keep_entry)
+				coop_push<true>(nearest, n_near, e, lane, p.debug & 1);
 			if (lane == 0)
 				(void)test_and_set(entry, ep8);
 		}
@@ -760,8 +788,9 @@ __global__ __launch_bounds__(64, D == 0 ? graph_any_dim_waves<MODE>() : ((MODE !
 				break;
 			const md_pair cur = candidates[0];
 			coop_pop<false>(candidates, n_cand, lane, p.debug & 1);
-			const float worst0 = nearest[0].d;
 			const bool full0 = n_near == p.ef;
+			// (FILTERED: `nearest` may be empty, its slot 0 never written; worst0 only counts when the queue is full)
+			const float worst0 = FILTERED ? (full0 ? nearest[0].d : __builtin_inff()) : nearest[0].d;
 			stamp(1);
 			if (cur.d > worst0 && full0)
 				break;
@@ -772,10 +801,23 @@ __global__ __launch_bounds__(64, D == 0 ? graph_any_dim_waves<MODE>() : ((MODE !
 			const uint32_t* adj = p.adj0 + (size_t)cur.id * p.stride0;
 			uint32_t nbv[2];
 			bool fresh[2];
+			// FILTERED: 0x80000000 when the neighbour is disallowed, else 0 -- the sign bit of its ndist slot
+			uint32_t* nflag = reinterpret_cast<uint32_t*>(ndist);
+			// (a list's padding, UINT32_MAX, reads the last word: it is never fresh, its flag goes nowhere)
+			auto disallowed = [&](uint32_t nb) -> uint32_t {
+				const uint32_t w = nb >> 5, w_last = (p.n - 1) >> 5;
+				return (~(p.allow_bits[w < w_last ? w : w_last] >> (nb & 31)) & 1u) << 31;
+			};
+			uint32_t dis[2] = {0u, 0u};
 #pragma unroll
 			for (int h = 0; h < 2; ++h) {
 				const uint32_t i = 64u * h + lane;
 				nbv[h] = i < p.stride0 ? adj[i] : 0xFFFFFFFFu;
+			}
+			if constexpr (FILTERED) {
+#pragma unroll
+				for (int h = 0; h < 2; ++h)
+					dis[h] = disallowed(nbv[h]);
 			}
 #pragma unroll
 			for (int h = 0; h < 2; ++h)
@@ -784,17 +826,28 @@ __global__ __launch_bounds__(64, D == 0 ? graph_any_dim_waves<MODE>() : ((MODE !
 #pragma unroll
 			for (int h = 0; h < 2; ++h) {
 				const unsigned long long mask = __builtin_amdgcn_ballot_w64(fresh[h]);
-				if (fresh[h])
-					nlist[n_list + __builtin_popcountll(mask & ((1ull << lane) - 1ull))] = nbv[h];
+				if (fresh[h]) {
+					const uint32_t pos = n_list + __builtin_popcountll(mask & ((1ull << lane) - 1ull));
+					nlist[pos] = nbv[h];
+					if constexpr (FILTERED)
+						nflag[pos] = dis[h];
+				}
 				n_list += (uint32_t)__builtin_popcountll(mask);
 			}
 			for (uint32_t i0 = 128; i0 < p.stride0; i0 += 64) {  // (lists beyond 128: M0 > 128)
 				const uint32_t i = i0 + lane;
 				const uint32_t nb = i < p.stride0 ? adj[i] : 0xFFFFFFFFu;
+				uint32_t ds = 0u;
+				if constexpr (FILTERED)
+					ds = disallowed(nb);
 				const bool fr = nb != 0xFFFFFFFFu && test_and_set(nb, ep8);
 				const unsigned long long mask = __builtin_amdgcn_ballot_w64(fr);
-				if (fr)
-					nlist[n_list + __builtin_popcountll(mask & ((1ull << lane) - 1ull))] = nb;
+				if (fr) {
+					const uint32_t pos = n_list + __builtin_popcountll(mask & ((1ull << lane) - 1ull));
+					nlist[pos] = nb;
+					if constexpr (FILTERED)
+						nflag[pos] = ds;
+				}
 				n_list += (uint32_t)__builtin_popcountll(mask);
 			}
 			wave_lds_sync();
@@ -817,8 +870,13 @@ __global__ __launch_bounds__(64, D == 0 ? graph_any_dim_waves<MODE>() : ((MODE !
 #pragma unroll
 				for (int u = 0; u < U; ++u) {
 					const uint32_t i = i0 + 4 * u + rg;
-					if (l == 0 && i < n_list)
-						ndist[i] = d[u];
+					if (l == 0 && i < n_list) {
+						if constexpr (FILTERED)  // (the slot holds the neighbour's flag, its sign bit, and nothing else: one LDS or)
+							(void)__hip_atomic_fetch_or(&nflag[i], __builtin_bit_cast(uint32_t, d[u]), __ATOMIC_RELAXED,
+							                            __HIP_MEMORY_SCOPE_WAVEFRONT);
+						else
+							ndist[i] = d[u];
+					}
 				}
 			}
 			distcomps += n_list;
@@ -831,30 +889,36 @@ __global__ __launch_bounds__(64, D == 0 ? graph_any_dim_waves<MODE>() : ((MODE !
 			for (uint32_t i0 = 0; i0 < n_list; i0 += 64) {  // (a chunk only writes slots it has already read)
 				const uint32_t i = i0 + lane;
 				const uint32_t id = i < n_list ? nlist[i] : 0u;
-				const float dn = i < n_list ? ndist[i] : 0.0f;
+				const float dn_raw = i < n_list ? ndist[i] : 0.0f;  // FILTERED: with the flag in its sign bit
+				const float dn = FILTERED ? __builtin_fabsf(dn_raw) : dn_raw;
 				const bool keep = i < n_list && !(full0 && !(dn < worst0));
 				wave_lds_sync();
 				const unsigned long long mask = __builtin_amdgcn_ballot_w64(keep);
 				const uint32_t pos = n_s + __builtin_popcountll(mask & ((1ull << lane) - 1ull));
 				if (keep) {
 					nlist[pos] = id;
-					ndist[pos] = dn;
+					ndist[pos] = dn_raw;
 				}
 				n_s += (uint32_t)__builtin_popcountll(mask);
 			}
 			wave_lds_sync();
 			for (uint32_t j = 0; j < n_s; ++j) {
-				const float dn = ndist[j];
+				const float dn_raw = ndist[j];
+				const float dn = FILTERED ? __builtin_fabsf(dn_raw) : dn_raw;
+				const bool allowed = !FILTERED || !(__builtin_bit_cast(uint32_t, dn_raw) & 0x80000000u);  // wave-uniform
 				if (n_near < p.ef || dn < nearest[0].d) {
 					const md_pair e{dn, nlist[j]};
 					if (n_cand >= p.cand_cap)
 						q_overflowed = true;
 					else
 						coop_push<false>(candidates, n_cand, e, lane, p.debug & 1);
-					coop_push<true>(nearest, n_near, e, lane, p.debug & 1);
-					wave_lds_sync();
-					if (n_near > p.ef)
-						coop_pop<true>(nearest, n_near, lane, p.debug & 1);
+					if (allowed) {
+						coop_push<true>(nearest, n_near, e, lane, p.debug & 1);
+						wave_lds_sync();
+						if (n_near > p.ef)
+							coop_pop<true>(nearest, n_near, lane, p.debug & 1);
+					} else if (FILTERED)
+						wave_lds_sync();
 					if (DBG)
 						seg[7]++;
 				}

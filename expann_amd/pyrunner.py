@@ -167,6 +167,28 @@ class AntitopoEngine:
                                                          C.c_void_p(ids_ptr), C.c_void_p(dists_ptr),
                                                          C.c_void_p(stream or None)))
 
+    def set_row_filter(self, allow):
+        """expann_antitopo_set_row_filter: queries from now on return only rows where the boolean (or 0 / 1 uint8)
+        array allow[size()] is true; None clears the filter.  Dense filters are walked under the filter rule of
+        include/expann_hip.h, sparse ones are answered by an exact scan of the allowed rows.  A run-time property:
+        store*, build() and load_index() clear it, and it is not saved with the index."""
+        if self._h is None:
+            raise _lib.ExpannError(_lib.ERR_NOT_BUILT, "set_row_filter() before build()")
+        if allow is None:
+            self._check(self._L.expann_antitopo_set_row_filter(self._h, None, 0))
+            return
+        from .engine import pack_row_filter
+        words = pack_row_filter(allow)
+        self._check(self._L.expann_antitopo_set_row_filter(self._h, words.ctypes.data, words.size))
+
+    def set_row_filter_device(self, ptr, n_words, stream=0):
+        """The same from n_words uint32 words in device memory (the layout of pack_row_filter), read in the order of
+        `stream` (a hipStream_t as an integer; 0 = the engine's own); returns once the allowed rows are counted."""
+        if self._h is None:
+            raise _lib.ExpannError(_lib.ERR_NOT_BUILT, "set_row_filter_device() before build()")
+        self._check(self._L.expann_antitopo_set_row_filter_device(self._h, C.c_void_p(ptr), int(n_words),
+                                                                  C.c_void_p(stream or None)))
+
     def sync(self):
         """Wait for the stream of the last query_many_device and check every such search since the last sync()
         (raises ExpannError with ERR_OVERFLOW when a walk overflowed its queue even in the redo launch)."""

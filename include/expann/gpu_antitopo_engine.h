@@ -180,6 +180,24 @@ struct gpu_antitopo_engine : public ann_engine<T, gpu_antitopo_engine<T>> {
 		return expann_graph_search_device(graph, d_queries, m, k, ef_search.value(), conf.mode(), d_ids, d_dists, nullptr,
 		                                  stream);
 	}
+	// Extension: the row filter of the queries from now on (expann_graph_set_row_filter; nullptr clears it).  A
+	// run-time property of the uploaded graph: upload() -- build and load -- starts without one, and it is not
+	// written to the index file.  Returns the expann_status (message: expann_graph_last_error(graph)).
+	int set_row_filter(const uint32_t* allow_bits, size_t n_words) {
+		if (!graph)
+			return EXPANN_ERR_NOT_BUILT;
+		return allow_bits ? expann_graph_set_row_filter(graph, allow_bits, n_words) : expann_graph_clear_row_filter(graph);
+	}
+	// the same from device bits, read in the order of `stream` (expann_graph_set_row_filter_device)
+	int set_row_filter_device(const uint32_t* d_allow_bits, size_t n_words, void* stream) {
+		if (!graph)
+			return EXPANN_ERR_NOT_BUILT;
+		return expann_graph_set_row_filter_device(graph, d_allow_bits, n_words, stream);
+	}
+	void clear_row_filter() {
+		if (graph)
+			(void)expann_graph_clear_row_filter(graph);
+	}
 	// expann_graph_sync; the distance evaluations the device counted since the last sync go to num_distcomps
 	int sync() {
 		if (!graph)

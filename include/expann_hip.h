@@ -316,14 +316,16 @@ int expann_graph_search_device(expann_graph* g, const float* d_queries, size_t m
                                int mode, uint64_t* d_ids, float* d_dists, uint32_t* d_distcomps, void* stream);
 int expann_graph_sync(expann_graph* g);
 /* options of both entry points (0 = auto): "cand_capacity" = the first launch's heap, "redo_capacity" = the redo
- * launch's (at most 8192); a power of two >= 8, anything else -- and an unknown name -- is EXPANN_ERR_INVALID_ARG. */
+ * launch's (at most 8192); a power of two >= 8, anything else -- and an unknown name -- is EXPANN_ERR_INVALID_ARG.
+ * "filter_flat_rows" (a row count >= 0, no power-of-two rule): see expann_graph_set_row_filter. */
 int expann_graph_set_option(expann_graph* g, const char* name, long value);
 /* Device-buffer searches only (a host-buffer call changes none of them): "redo_queries" = queries the redo
  * launches served, over the searches the last expann_graph_sync checked;
  * "redo_overflows" = searches since create that ended in EXPANN_ERR_OVERFLOW; "deferred_searches" = device-buffer
  * searches since create; "distcomps" = distance evaluations of all device-buffer searches since create, as of the
- * last sync; "redo_kernel_ns" = device time of the last search's redo launch, as of the last sync.  An unknown
- * name is EXPANN_ERR_INVALID_ARG. */
+ * last sync; "redo_kernel_ns" = device time of the last search's redo launch, as of the last sync;
+ * "filter_active", "filter_rows", "flat_searches": see expann_graph_set_row_filter.  An unknown name is
+ * EXPANN_ERR_INVALID_ARG. */
 int expann_graph_get_stat(expann_graph* g, const char* name, uint64_t* out);
 
 /* GPU-assisted batched construction of the graph (csrc/graph_build.hpp; replaces the inner loop of
@@ -508,11 +510,65 @@ uint32_t expann_spec_rank_auto(size_t k, uint32_t sample_frac);
  * speculative thresholds ("spec_rank"), whatever those options say, and never the bf16x3 form ("scan_kernel" 3
  * runs the exact direct scan, as do queries outside the fp16 range).
  * expann_sharded_* does not offer the filter (its set_option pass-through is unchanged and there is no
- * sharded entry point for it); a per-query filter and the graph engine are not offered either.
+ * sharded entry point for it); a per-query filter is not offered either.  The graph engine has a row filter of its
+ * own: expann_graph_set_row_filter, below.
  * expann_get_stat: "filter_active" (0 / 1), "filter_rows" (allowed rows; n when no filter is set). */
 int expann_set_row_filter(expann_index* h, const uint32_t* allow_bits, size_t n_words);        /* host bits   */
 int expann_set_row_filter_device(expann_index* h, const uint32_t* d_allow_bits, size_t n_words, void* stream);
 int expann_clear_row_filter(expann_index* h);
+
+/* Row filter of the graph engine (appended; EXPANN_ABI_VERSION stays 2: nothing that existed changed; with no
+ * filter set every launch uses the kernel instances it used before).
+ * THE FILTER RULE.  A filter is a bitmap over vertex numbers: bit v & 31 of word v >> 5, least significant bit
+ * first, says whether vertex v may appear in a result.  Bits at and beyond n are ignored; the library keeps its own
+ * copy, which is zero from n on (the caller may free its bits on return).  Under a filter the walk runs as follows.
+ *   Descent: the entry evaluation and the greedy descent through the upper layers are unchanged; they never look
+ *   at the filter.
+ *   Bottom-layer entry: the entry vertex is scored and marked visited; it is pushed on `candidates`; it is pushed
+ *   on `nearest` only if it is allowed.
+ *   Stop rule: stop when `candidates` is empty; also stop when nearest.size() == ef && cur.d > nearest.top().d.
+ *   While `nearest` holds fewer than ef entries -- none included -- nothing stops the walk but an empty
+ *   `candidates`.
+ *   Neighbour update: for each unvisited neighbour in adjacency order, with distance dn: if nearest.size() < ef ||
+ *   dn < nearest.top().d, push it on `candidates`; if it is also allowed, push it on `nearest` and pop `nearest`
+ *   when it exceeds ef.  A disallowed vertex is traversed but never kept.
+ *   The pre-drop of a neighbour (a full `nearest` and !(dn < its top at the start of the hop)) stays valid: the
+ *   top only falls while the queue is full.  distcomps count every scored vertex, allowed or not.
+ *   Output as without a filter: drain `nearest`, reverse, re-score in fp32 in modes 1 and 2, truncate to k, pad
+ *   with UINT64_MAX / +inf.
+ * With every bit set this is the unfiltered walk exactly: ids, distance bits and distcomps equal it in all three
+ * modes.  The redo launch, the counters and EXPANN_ERR_OVERFLOW work as without a filter.
+ * SPARSE FILTERS ARE SCANNED.  A walk under a filter that allows few rows visits most of the graph with `nearest`
+ * never full, and `candidates` grows with the frontier.  So when the filter allows at most "filter_flat_rows" rows
+ * (expann_graph_set_option: v >= 0, anything else EXPANN_ERR_INVALID_ARG; 0 = auto: 128 000, measured on
+ * a 1 M x d128 graph at ef_search = 60, k = 10 (profiles/graph_filter_ab.txt); v > 0: filters allowing
+ * at most v rows are scanned, so 1 is in effect "always walk") a search does not walk: it scores exactly the
+ * allowed rows in fp32, in the reference's FMA order, whatever the mode, and returns the min(k, allowed) smallest by
+ * (distance, id), ascending, padded -- what the brute-force index returns over those rows -- with distcomps per
+ * query = the allowed count.  (A search with min(k, allowed) > 1024 walks whatever the option says: the scan keeps
+ * its k best in LDS.)  A filter that allows no row returns padding and distcomps 0, with no walk and no scan.
+ * expann_graph_search, _mode, _device and the expann_antitopo_query calls all honour the filter, the device-buffer
+ * call in stream order and with its steady-state promise (no allocation, copy, query or synchronisation).
+ * Both set calls and the clear call first wait on the host for outstanding device-buffer searches (their counters
+ * stay for the next expann_graph_sync), so every search runs under the filter that was in force when it was
+ * enqueued.  expann_graph_set_row_filter_device reads d_allow_bits in the order of `stream` (a hipStream_t; NULL =
+ * the handle's own) and returns after that stream and the handle's own have drained: the allowed count is needed on
+ * the host to choose between walk and scan -- one host wait per filter change, none per search.
+ * Errors, in this order, both before the device is touched: handle or bits NULL EXPANN_ERR_INVALID_ARG; n_words <
+ * ceil(n / 32) EXPANN_ERR_INVALID_ARG.  A failed call leaves the filter as it was.
+ * expann_graph_get_stat: "filter_active" (0 / 1), "filter_rows" (allowed rows; n when no filter is set),
+ * "flat_searches" (searches since create, of either entry point, that were answered without a walk: by the scan, or
+ * by padding alone under a filter that allows no row).
+ * expann_antitopo_set_row_filter is the same on the engine's graph (NULL bits clear the filter); before build()
+ * EXPANN_ERR_NOT_BUILT.  expann_antitopo_store*, _build and _load clear the filter: it is a run-time property and is
+ * not written to the index file.  expann_antitopo_set_row_filter_device takes device bits as
+ * expann_graph_set_row_filter_device does.
+ * Not offered: per-query filters, a filter for expann_graph_build_batched's searches, deleting rows. */
+int expann_graph_set_row_filter(expann_graph* g, const uint32_t* allow_bits, size_t n_words);
+int expann_graph_set_row_filter_device(expann_graph* g, const uint32_t* d_allow_bits, size_t n_words, void* stream);
+int expann_graph_clear_row_filter(expann_graph* g);
+int expann_antitopo_set_row_filter(expann_antitopo* e, const uint32_t* allow_bits_or_NULL, size_t n_words);
+int expann_antitopo_set_row_filter_device(expann_antitopo* e, const uint32_t* d_allow_bits, size_t n_words, void* stream);
 
 #ifdef __cplusplus
 }
