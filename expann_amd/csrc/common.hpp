@@ -44,6 +44,33 @@ template <int SEL> __device__ inline f32x2 pk_fma_bcast(f32x2 a, f32x2 r, f32x2 
 	return d;
 }
 
+// ---- row elements of the exact kernels ------------------------------------------------
+// The exact kernels (direct scan, re-rank, score_ids) take the stored element type TR: float, or
+// _Float16 for EXPANN_DTYPE_F16 rows.  binary16 -> fp32 is exact (subnormals included: the f16
+// denormal mode is on), so a kernel over _Float16 rows computes, bit for bit, what the float
+// instance computes over the upcast rows.  The two per-dim steps of the reference's lanes:
+//   ref_diff(q, r)   = q - (float)r      (one rounding)
+//   ref_dot(q, r, a) = fma(q, (float)r, a)
+// For _Float16 both are ONE v_fma_mix_f32 (fp32 fused multiply-add whose op_sel_hi-marked source is
+// an f16 register half, converted inside the operand; fma(r, -1, q) rounds q - r once, as the
+// subtraction does): the same VALU count per dim as the float instances, no v_cvt per element.
+// Spelled out because hipcc converts first and subtracts wherever a row value meets several queries.
+// (for float the helpers are the plain subtraction and fmaf the kernels had before the element type became a parameter)
+template <typename TR> __device__ __attribute__((always_inline)) inline float ref_diff(float q, TR r) { return q - r; }
+template <> __device__ __attribute__((always_inline)) inline float ref_diff<_Float16>(float q, _Float16 r) {
+	float d;
+	asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(d) : "v"(r), "v"(q));
+	return d;
+}
+template <typename TR> __device__ __attribute__((always_inline)) inline float ref_dot(float q, TR r, float acc) {
+	return __builtin_fmaf(q, r, acc);
+}
+template <> __device__ __attribute__((always_inline)) inline float ref_dot<_Float16>(float q, _Float16 r, float acc) {
+	float d;
+	asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel_hi:[0,1,0]" : "=v"(d) : "v"(q), "v"(r), "v"(acc));
+	return d;
+}
+
 constexpr uint64_t kSentinelKey = ~0ull;  // sorts after every real (score, id) key
 
 // Monotone map float -> uint32: a < b  <=>  ord(a) < ord(b) for all non-NaN floats

@@ -208,6 +208,13 @@ struct expann_index {
 	}
 };
 
+// rows of floating-point values scored in fp32 by the reference's lane order: fp32 storage, or binary16 storage
+// (EXPANN_DTYPE_F16: every exact kernel converts on load, every filter is built from the converted values, so an
+// F16 index answers as the F32 index of the upcast rows does).  `dtype == EXPANN_DTYPE_F32` stays where fp32
+// STORAGE is meant: the uint8 shadow, the int8 filter and the bf16x3 planes read d_base as float.
+inline bool f16_rows(const expann_index* h) { return h->dtype == EXPANN_DTYPE_F16; }
+inline bool float_rows(const expann_index* h) { return h->dtype == EXPANN_DTYPE_F32 || f16_rows(h); }
+
 namespace expann {
 int num_cus(int device) {
 	hipDeviceProp_t prop;
@@ -249,16 +256,26 @@ const ScanVariant kScanF32[] = {
 	 scan_filter_f32_any_kernel<TQ, true, kRowsBitmap>, scan_filter_f32_any_kernel<TQ, true, kRowsList>}
 const ScanVariant kScanF32Any[] = {SCAN_ANY_V(1), SCAN_ANY_V(2), SCAN_ANY_V(4)};
 #undef SCAN_ANY_V
+// binary16 rows (EXPANN_DTYPE_F16), every dim: the run-time-dim scan over _Float16 rows
+#define SCAN_ANY_H(TQ)                                                                                              \
+	{0, TQ, false, scan_filter_f32_any_kernel<TQ, false, kRowsAll, _Float16>, "scan_filter_f32_any<" #TQ ",L2,F16>", \
+	 scan_filter_f32_any_kernel<TQ, false, kRowsBitmap, _Float16>, scan_filter_f32_any_kernel<TQ, false, kRowsList, _Float16>}, \
+	{0, TQ, true, scan_filter_f32_any_kernel<TQ, true, kRowsAll, _Float16>, "scan_filter_f32_any<" #TQ ",IP,F16>", \
+	 scan_filter_f32_any_kernel<TQ, true, kRowsBitmap, _Float16>, scan_filter_f32_any_kernel<TQ, true, kRowsList, _Float16>}
+const ScanVariant kScanF16Any[] = {SCAN_ANY_H(1), SCAN_ANY_H(2), SCAN_ANY_H(4)};
+#undef SCAN_ANY_H
 inline bool any_dim_f32(int d) { return d >= 16 && d <= kMaxAnyDim && d % 16 == 0; }
 
-const ScanVariant* pick_scan_f32(int d, bool ip, size_t m, long forced_tq) {
+// (rows_f16: binary16 rows -- no compiled-dim instances, the run-time-dim table of that element type at every dim)
+const ScanVariant* pick_scan_f32(int d, bool ip, size_t m, long forced_tq, bool rows_f16 = false) {
 	const ScanVariant* best = nullptr;
 	bool compiled = false;
 	for (const auto& v : kScanF32)
-		compiled = compiled || v.d == d;
+		compiled = compiled || (v.d == d && !rows_f16);
 	if (!compiled && !any_dim_f32(d))
 		return nullptr;
-	const ScanVariant* tab = compiled ? kScanF32 : kScanF32Any;
+	static_assert(sizeof(kScanF16Any) == sizeof(kScanF32Any), "one F16 instance per run-time-dim F32 instance");
+	const ScanVariant* tab = compiled ? kScanF32 : (rows_f16 ? kScanF16Any : kScanF32Any);
 	const size_t n_tab = compiled ? sizeof(kScanF32) / sizeof(kScanF32[0]) : sizeof(kScanF32Any) / sizeof(kScanF32Any[0]);
 	for (size_t i = 0; i < n_tab; ++i) {
 		const ScanVariant& v = tab[i];
@@ -294,6 +311,8 @@ const ScoreVariant kScoreF32[] = {SCORE_V(64),  SCORE_V(128), SCORE_V(256), SCOR
                                   SCORE_V(768), SCORE_V(832), SCORE_V(960), SCORE_V(1024)};
 #undef SCORE_V
 const ScoreVariant kScoreF32Any[] = {{0, false, score_ids_f32_any_kernel<false>}, {0, true, score_ids_f32_any_kernel<true>}};
+const ScoreVariant kScoreF16Any[] = {{0, false, score_ids_f32_any_kernel<false, _Float16>},
+                                     {0, true, score_ids_f32_any_kernel<true, _Float16>}};
 
 // 8-bit rows
 struct ScanI8Variant {
@@ -654,8 +673,13 @@ int ensure_f16(expann_index* h, const GemmF16Variant* gf, hipStream_t st) {
 	HIP_TRY(h, tmp.alloc(sizeof(float)));
 	HIP_TRY(h, nrm.alloc(sizeof(float) * h->n));
 	HIP_TRY(h, hipMemsetAsync(tmp.p, 0, sizeof(uint32_t), st));
-	hipLaunchKernelGGL(maxabs_bits_kernel, dim3(2048), dim3(kBlock), 0, st, (const float*)h->d_base, nv,
-	                   tmp.as<uint32_t>());
+	const bool hrows = f16_rows(h);  // binary16 source: converted on load, then the same prelude (same bits out)
+	const _Float16* const base_h = (const _Float16*)h->d_base;
+	if (hrows)
+		hipLaunchKernelGGL(maxabs_bits_kernel<_Float16>, dim3(2048), dim3(kBlock), 0, st, base_h, nv, tmp.as<uint32_t>());
+	else
+		hipLaunchKernelGGL(maxabs_bits_kernel<float>, dim3(2048), dim3(kBlock), 0, st, (const float*)h->d_base, nv,
+		                   tmp.as<uint32_t>());
 	float maxabs = 0.0f;  // (a NaN pattern stays a NaN and fails the range check below)
 	HIP_TRY(h, hipMemcpyAsync(&maxabs, tmp.p, sizeof(float), hipMemcpyDeviceToHost, st));
 	HIP_TRY(h, hipStreamSynchronize(st));
@@ -682,10 +706,15 @@ int ensure_f16(expann_index* h, const GemmF16Variant* gf, hipStream_t st) {
 	if (!h->d_bnmax)
 		HIP_TRY(h, hipMalloc(&h->d_bnmax, 4 * sizeof(float)));
 	const uint32_t blocks16 = (uint32_t)((h->n + kRowsPerGroup - 1) / kRowsPerGroup);
-	if (gf->d == 0) {  // run-time dim: rows of ld elements, zero past d; norms over the d real ones
-		hipLaunchKernelGGL(convert_f16_pad_kernel, dim3(8192), dim3(kBlock), 0, st, (const float*)h->d_base, h->n,
+	if (hrows) {  // (ld == d on the dims with a compiled form: the padded convert is the plain one there)
+		hipLaunchKernelGGL(convert_f16_pad_kernel<_Float16>, dim3(8192), dim3(kBlock), 0, st, base_h, h->n, (uint32_t)h->dim,
+		                   (uint32_t)ld, scale, h->d_base_f16.as<_Float16>());
+		hipLaunchKernelGGL(sqnorm_any_kernel<_Float16>, dim3(blocks16), dim3(kBlock), 0, st, base_h, (uint32_t)h->n,
+		                   (uint32_t)h->dim, nrm.as<float>());
+	} else if (gf->d == 0) {  // run-time dim: rows of ld elements, zero past d; norms over the d real ones
+		hipLaunchKernelGGL(convert_f16_pad_kernel<float>, dim3(8192), dim3(kBlock), 0, st, (const float*)h->d_base, h->n,
 		                   (uint32_t)h->dim, (uint32_t)ld, scale, h->d_base_f16.as<_Float16>());
-		hipLaunchKernelGGL(sqnorm_any_kernel, dim3(blocks16), dim3(kBlock), 0, st, (const float*)h->d_base,
+		hipLaunchKernelGGL(sqnorm_any_kernel<float>, dim3(blocks16), dim3(kBlock), 0, st, (const float*)h->d_base,
 		                   (uint32_t)h->n, (uint32_t)h->dim, nrm.as<float>());
 	} else {
 		hipLaunchKernelGGL(convert_f16_kernel, dim3((uint32_t)std::min<size_t>((nv + kBlock - 1) / kBlock, 8192)),
@@ -746,7 +775,9 @@ void drop_row_filter(expann_index* h) {
 }
 
 const GemmVariant* pick_gemm(const expann_index* h, size_t m) {
-	if (h->opt_scan_kernel == 1 || h->dtype != EXPANN_DTYPE_F32)
+	if (h->opt_scan_kernel == 1 || !float_rows(h))
+		return nullptr;
+	if (f16_rows(h) && !f16_choice(h->opt_scan_kernel))  // (binary16 rows: the fp16 form is the only matrix-core one)
 		return nullptr;
 	if (h->metric == EXPANN_METRIC_IP) {
 		// inner product: only the fp16 form has it (a placeholder variant keeps the GEMM branch alive)
@@ -829,7 +860,7 @@ const GemmI8Variant kGemmI8[] = {
 #undef GEMM_I8
 
 const GemmI8Variant* pick_gemm_i8(const expann_index* h, size_t m) {
-	if (h->opt_scan_kernel == 1 || h->dtype == EXPANN_DTYPE_F32)
+	if (h->opt_scan_kernel == 1 || float_rows(h))
 		return nullptr;
 	if (h->opt_scan_kernel == 0 && (m < 96 || h->n < 4096))
 		return nullptr;
@@ -864,22 +895,30 @@ int ensure_bias_i8(expann_index* h, const GemmI8Variant* gv, hipStream_t st) {
 uint32_t select_longest_list(double expect, uint32_t spec_j) {
 	return spec_j ? (uint32_t)(expect * (1.0 + 4.5 / std::sqrt((double)spec_j))) : 2u * (uint32_t)expect;
 }
-void launch_select_wave(SelectParams& sel, size_t m, uint32_t cap, hipStream_t st, uint32_t longest) {
+// (rows_f16: sel.rerank_base holds binary16 rows -- the _Float16 instances of the same kernels)
+void launch_select_wave(SelectParams& sel, size_t m, uint32_t cap, hipStream_t st, uint32_t longest, bool rows_f16 = false) {
+	using WaveFn = void (*)(SelectParams, uint32_t);
+	const WaveFn w8 = rows_f16 ? select_wave_kernel<8, 4, _Float16> : select_wave_kernel<8, 4>;
+	const WaveFn w16 = rows_f16 ? select_wave_kernel<16, 2, _Float16> : select_wave_kernel<16, 2>;
+	const WaveFn w32 = rows_f16 ? select_wave_kernel<32, 1, _Float16> : select_wave_kernel<32, 1>;
 	sel.wave_done = 0;
-	hipLaunchKernelGGL((select_wave_kernel<8, 4>), dim3((uint32_t)((m + 3) / 4)), dim3(256), 0, st, sel,
-	                   (uint32_t)m);
+	hipLaunchKernelGGL(w8, dim3((uint32_t)((m + 3) / 4)), dim3(256), 0, st, sel, (uint32_t)m);
 	sel.wave_done = 512;
 	if (longest <= 512)
 		return;
 	if (cap > 512) {
 		// (k = 100: ~920-entry lists -- half the registers and ballots of the 2048-key form)
-		hipLaunchKernelGGL((select_wave_kernel<16, 2>), dim3((uint32_t)((m + 1) / 2)), dim3(128), 0, st, sel, (uint32_t)m);
+		hipLaunchKernelGGL(w16, dim3((uint32_t)((m + 1) / 2)), dim3(128), 0, st, sel, (uint32_t)m);
 		sel.wave_done = 1024;
 	}
 	if (cap > 1024 && longest > 1024) {
-		hipLaunchKernelGGL((select_wave_kernel<32, 1>), dim3((uint32_t)m), dim3(64), 0, st, sel, (uint32_t)m);
+		hipLaunchKernelGGL(w32, dim3((uint32_t)m), dim3(64), 0, st, sel, (uint32_t)m);
 		sel.wave_done = 2048;
 	}
+}
+using SelectTopkFn = void (*)(SelectParams);
+inline SelectTopkFn select_topk_fn(const expann_index* h) {
+	return f16_rows(h) ? select_topk_kernel<_Float16> : select_topk_kernel<float>;
 }
 
 // Per-wave hit logs of the scans that write them (scan_gemm_f16x.hpp, scan_gemm_i8w.hpp): one log
@@ -1066,13 +1105,13 @@ uint32_t spec_redo_slots(size_t m) {
 uint32_t sample_frac_for(const expann_index* h, size_t k) {
 	if (h->opt_sample_frac > 0)
 		return (uint32_t)h->opt_sample_frac;
-	const double expo = h->dtype == EXPANN_DTYPE_F32 ? 0.3 : 0.5;
-	const double bytes = (double)h->n * (double)h->dim * (h->dtype == EXPANN_DTYPE_F32 ? 2.0 : 1.0);
+	const double expo = float_rows(h) ? 0.3 : 0.5;
+	const double bytes = (double)h->n * (double)h->dim * (float_rows(h) ? 2.0 : 1.0);
 	double size = (bytes >= 8 * 2.56e8 && k <= 32) ? std::min(3.0, std::pow(bytes / 2.56e8, 0.3)) : 1.0;
 	// (round 3, after the hits got cheaper -- lighter flush, keys made by the gather, pruned selects --
 	// profiles/sweep_frac_r3.sh: k = 100 on 1.25 M rows: 6 beats 8 by 2.3 % (3.28 vs 3.36 ms), on 10 M rows 8 - 12 are
 	// even: ~bytes^0.25 from C3's per-GPU shard on)
-	if (h->dtype == EXPANN_DTYPE_F32 && k > 32)
+	if (float_rows(h) && k > 32)
 		size = 0.75 * std::pow(std::max(1.0, bytes / 3.2e8), 0.25);
 	const double f = 16.0 * std::pow(10.0 / (double)std::max<size_t>(1, k), expo) * size;
 	return (uint32_t)std::min(48.0, std::max(4.0, std::round(f)));
@@ -1135,7 +1174,7 @@ constexpr int kRetryGeneric = -1000;  // internal: the caller falls back to the 
 constexpr int kStrictReject = -1001;  // internal (uint8 shadow): these queries are not 8-bit integers
 
 const GemmI8qVariant* pick_gemm_i8q(const expann_index* h, size_t m, size_t k) {
-	if (h->dtype == EXPANN_DTYPE_F32 || !(h->opt_scan_kernel == 0 || h->opt_scan_kernel == 5))
+	if (float_rows(h) || !(h->opt_scan_kernel == 0 || h->opt_scan_kernel == 5))
 		return nullptr;
 	if (h->opt_scan_kernel == 0 && (m < 96 || h->n < 65536))
 		return nullptr;
@@ -1456,7 +1495,7 @@ int search_i8q(expann_index* h, const GemmI8qVariant* gq, const void* d_queries,
 			                   h->d_total);
 		launch_select_wave(sel, m, cap, st, select_longest_list(1.2 * (double)k * sample_frac_for(h, k), 0));
 		mark("select_wave");
-		hipLaunchKernelGGL(select_topk_kernel, dim3((uint32_t)m), dim3(kBlock), sizeof(uint64_t) * cap + 16,
+		hipLaunchKernelGGL(select_topk_kernel<float>, dim3((uint32_t)m), dim3(kBlock), sizeof(uint64_t) * cap + 16,
 		                   st, sel);
 		HIP_TRY(h, hipGetLastError());
 		if (defer_flags(h, st, attempt)) {  // deferred check: expann_sync reads the flags
@@ -1984,6 +2023,8 @@ int SearchPass::choose_kernels() {
 	// A row filter reaches the matrix cores through the fp16 forms' masked row terms only: no
 	// bf16x3 form (queries outside the fp16 range go to the exact direct scan), no int8 filter, no speculative
 	// thresholds, whatever the options say; a filter selective enough for the list path streams no base at all
+	// Binary16 rows (EXPANN_DTYPE_F16) have neither a bf16x3 form nor an int8 filter -- both build their operands
+	// from fp32 storage -- so "scan_kernel" 3 and queries outside the fp16 range run the exact direct scan there too.
 	const bool filt = h->filter_on;
 	gv = force_direct ? nullptr : pick_gemm(h, m);
 	if (filt && (no_f16 || !f16_choice(h->opt_scan_kernel) || h->n_allowed <= cap))
@@ -2000,11 +2041,11 @@ int SearchPass::choose_kernels() {
 		if (rc != EXPANN_OK)
 			return rc;
 	}
-	if (gv)
+	if (gv && h->dtype == EXPANN_DTYPE_F32)
 		for (const auto& v : kGemmBf16)
 			if (v.d == h->dim)
 				gvb = &v;
-	if (h->opt_scan_kernel == 3 && !gvb && !filt)
+	if (h->opt_scan_kernel == 3 && !gvb && !filt && !f16_rows(h))
 		return h->fail(EXPANN_ERR_UNSUPPORTED, "bf16x3 GEMM-form scan: f32 L2 with dim 64 or 128 only");
 	// fp16 single-product form: default when available; a search whose queries leave the fp16
 	// range after scaling is redone with the bf16x3 form (no_f16)
@@ -2379,7 +2420,7 @@ int SearchPass::run_level(size_t li) {
 	sel.tau_prev = first ? nullptr : h->d_tau[(li + 1) & 1];
 	sel.tau_row_out = last ? nullptr : h->d_tau_row[li & 1];
 	sel.tau_row_prev = first ? nullptr : h->d_tau_row[(li + 1) & 1];
-	sel.rerank_base = use_gemm ? (const float*)h->d_base : nullptr;
+	sel.rerank_base = use_gemm ? (const float*)h->d_base : nullptr;  // (binary16 rows: the _Float16 select instances)
 	sel.rerank_queries = use_gemm ? (const float*)d_queries : nullptr;
 	sel.dim = (uint32_t)h->dim;
 	sel.metric_ip = ip ? 1u : 0u;
@@ -2419,9 +2460,9 @@ int SearchPass::run_level(size_t li) {
 		// (speculative thresholds: the expectation is linear in the rank of the class maximum)
 		const uint32_t sj = last ? spec_j : 0u;
 		const double expect = (use_i8f ? kI8fListRatio : 1.0) * 1.2 * (sj ? (double)sj : (double)k) * sample_frac_for(h, k);
-		launch_select_wave(sel, m, cap, st, select_longest_list(expect, sj));
+		launch_select_wave(sel, m, cap, st, select_longest_list(expect, sj), f16_rows(h));
 	}
-	hipLaunchKernelGGL(select_topk_kernel, dim3((uint32_t)m), dim3(kBlock),
+	hipLaunchKernelGGL(select_topk_fn(h), dim3((uint32_t)m), dim3(kBlock),
 	                   sizeof(uint64_t) * cap + 16, st, sel);
 	HIP_TRY(h, hipGetLastError());
 	if (last && spec_j)
@@ -2576,7 +2617,7 @@ int SearchPass::run_redo(bool use_i8f) {
 	sel.wave0_short = 1;
 	sel.slot_map = cp.list;
 	sel.live_slots = word;
-	hipLaunchKernelGGL(select_topk_kernel, dim3(R), dim3(kBlock), sizeof(uint64_t) * cap + 16, st, sel);
+	hipLaunchKernelGGL(select_topk_fn(h), dim3(R), dim3(kBlock), sizeof(uint64_t) * cap + 16, st, sel);
 	HIP_TRY(h, hipGetLastError());
 	return EXPANN_OK;
 }
@@ -2727,8 +2768,8 @@ int search_pass(expann_index* h, const void* d_queries, size_t m, size_t k, uint
 		}
 	}
 	ScanSel svs;
-	if (h->dtype == EXPANN_DTYPE_F32) {
-		const ScanVariant* v = pick_scan_f32(h->dim, ip, m, h->opt_query_tile);
+	if (float_rows(h)) {
+		const ScanVariant* v = pick_scan_f32(h->dim, ip, m, h->opt_query_tile, f16_rows(h));
 		if (v)
 			svs = ScanSel{v->fn, v->tq, v->name, v->fn_bits, v->fn_list};
 	} else {
@@ -2798,13 +2839,13 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 		return EXPANN_ERR_INVALID_ARG;
 	}
 	int int_mode = -1;
-	if (dtype == EXPANN_DTYPE_F32) {
+	if (dtype == EXPANN_DTYPE_F32 || dtype == EXPANN_DTYPE_F16) {  // (binary16 rows: the f32 rules)
 		if (metric != EXPANN_METRIC_L2 && metric != EXPANN_METRIC_IP) {
-			g_create_error = "metric must be EXPANN_METRIC_L2 or EXPANN_METRIC_IP for f32 rows";
+			g_create_error = "metric must be EXPANN_METRIC_L2 or EXPANN_METRIC_IP for f32 / f16 rows";
 			return EXPANN_ERR_INVALID_ARG;
 		}
 		if (dim > kMaxAnyDim) {
-			g_create_error = "unsupported dim " + std::to_string(dim) + ": f32 rows take dim <= " +
+			g_create_error = "unsupported dim " + std::to_string(dim) + ": f32 / f16 rows take dim <= " +
 			                 std::to_string(kMaxAnyDim);
 			return EXPANN_ERR_UNSUPPORTED;
 		}
@@ -2853,7 +2894,7 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 		g_create_error = "device index out of range";
 		return EXPANN_ERR_INVALID_ARG;
 	}
-	if ((int_mode < 0 && !pick_scan_f32(dim, metric == EXPANN_METRIC_IP, 1, 0)) ||
+	if ((int_mode < 0 && !pick_scan_f32(dim, metric == EXPANN_METRIC_IP, 1, 0, dtype == EXPANN_DTYPE_F16)) ||
 	    (int_mode >= 0 && !pick_scan_i8(dim, int_mode, 1, 0))) {
 		g_create_error = "unsupported dim " + std::to_string(dim) +
 		                 " (built: f32 any multiple of 16 up to 4096; 8-bit any multiple of 64 up to 4096; int16 64,128)";
@@ -2864,7 +2905,7 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 	h->dtype = dtype;
 	h->metric = metric;
 	h->device = device;
-	h->elem = (dtype == EXPANN_DTYPE_F32) ? 4 : (dtype == EXPANN_DTYPE_I16 ? 2 : 1);
+	h->elem = (dtype == EXPANN_DTYPE_F32) ? 4 : ((dtype == EXPANN_DTYPE_I16 || dtype == EXPANN_DTYPE_F16) ? 2 : 1);
 	h->q_elem = (dtype == EXPANN_DTYPE_I8) ? 1 : (dtype == EXPANN_DTYPE_I16 ? 2 : 4);
 	h->int_mode = int_mode;
 	if (const char* e = std::getenv("EXPANN_TAIL_CHUNKS"))
@@ -2881,8 +2922,9 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 		return EXPANN_ERR_HIP;
 	}
 	// the select kernel sorts up to kMaxCap 8-byte keys in LDS (128 KiB of the CU's 160 KiB)
-	if (hipFuncSetAttribute((const void*)select_topk_kernel,
-	                        hipFuncAttributeMaxDynamicSharedMemorySize,
+	if (hipFuncSetAttribute((const void*)select_topk_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize,
+	                        (int)(sizeof(uint64_t) * kMaxCap + 16)) != hipSuccess ||
+	    hipFuncSetAttribute((const void*)select_topk_kernel<_Float16>, hipFuncAttributeMaxDynamicSharedMemorySize,
 	                        (int)(sizeof(uint64_t) * kMaxCap + 16)) != hipSuccess) {
 		g_create_error = "hipFuncSetAttribute(select_topk_kernel) failed";
 		hipStreamDestroy(h->stream);
@@ -2900,7 +2942,7 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 			delete h;
 			return EXPANN_ERR_HIP;
 		}
-	if (dtype == EXPANN_DTYPE_F32 && f16kl_dim(dim) &&
+	if ((dtype == EXPANN_DTYPE_F32 || dtype == EXPANN_DTYPE_F16) && f16kl_dim(dim) &&
 	    (hipFuncSetAttribute((const void*)kGemmF16KL.scan, hipFuncAttributeMaxDynamicSharedMemorySize, kGemmF16KL.lds) != hipSuccess ||
 	     hipFuncSetAttribute((const void*)kGemmF16KL.sample, hipFuncAttributeMaxDynamicSharedMemorySize, kGemmF16KL.lds) != hipSuccess)) {
 		g_create_error = "hipFuncSetAttribute(scan_gemm_f16kl_kernel) failed";
@@ -3021,7 +3063,7 @@ int expann_build(expann_index* h) {
 	std::vector<unsigned char>().swap(h->staging);
 	// the fp16 copy every fp32 search of a built dim filters through: made here, inside the
 	// reference's timed build span (basic_bench.h:63-71), not inside the first query
-	if (h->dtype == EXPANN_DTYPE_F32 && h->n >= 4096 && h->opt_scan_kernel == 0) {
+	if (float_rows(h) && h->n >= 4096 && h->opt_scan_kernel == 0) {
 		for (const auto& v : kGemmF16X)
 			if (v.d == h->dim) {
 				const int rc = ensure_f16(h, &v, h->stream);
@@ -3189,7 +3231,7 @@ int expann_search(expann_index* h, const void* queries, size_t m, size_t k, uint
 		// prep kernel reads them straight from pinned memory (and makes the device copy); otherwise
 		// one async copy
 		const void* dq = h->d_q;
-		if (h->dtype == EXPANN_DTYPE_F32 && h->d_base_f16 && h->f16_scale > 0.0f && h->opt_scan_kernel == 0 &&
+		if (float_rows(h) && h->d_base_f16 && h->f16_scale > 0.0f && h->opt_scan_kernel == 0 &&
 		    m <= (size_t)kRowsPerGroup && h->n >= 4096 && pick_gemm(h, m) != nullptr &&
 		    !(h->filter_on && h->n_allowed <= kMaxCap)) {  // (the list path runs no prep kernel)
 			h->q_in_pinned_host = true;
@@ -3299,13 +3341,14 @@ int expann_score_ids(expann_index* h, const void* query, const uint64_t* ids, si
 	HIP_TRY(h, hipMemcpyAsync(d_idl, ids, sizeof(uint64_t) * n_ids, hipMemcpyHostToDevice, h->stream));
 	const uint32_t blocks = (uint32_t)((n_ids + kRowsPerGroup - 1) / kRowsPerGroup);
 	uint32_t bad_host = 0;
-	if (h->dtype == EXPANN_DTYPE_F32) {
+	if (float_rows(h)) {
 		const ScoreVariant* sv = nullptr;
 		for (const auto& v : kScoreF32)
-			if (v.d == h->dim && v.ip == (h->metric == EXPANN_METRIC_IP))
+			if (v.d == h->dim && v.ip == (h->metric == EXPANN_METRIC_IP) && !f16_rows(h))
 				sv = &v;
 		if (!sv && any_dim_f32(h->dim))
-			sv = &kScoreF32Any[h->metric == EXPANN_METRIC_IP ? 1 : 0];
+			sv = f16_rows(h) ? &kScoreF16Any[h->metric == EXPANN_METRIC_IP ? 1 : 0]
+			                 : &kScoreF32Any[h->metric == EXPANN_METRIC_IP ? 1 : 0];
 		if (!sv)
 			return h->fail(EXPANN_ERR_UNSUPPORTED, "no score kernel for this dim");
 		ScoreIdsParams sp{h->d_base, d_query, (const uint64_t*)d_idl, h->id_offset,
@@ -3415,6 +3458,8 @@ int expann_get_stat(expann_index* h, const char* name, uint64_t* out) {
 		*out = h->stat_redo_overflows;
 	else if (!std::strcmp(name, "spec_rank"))
 		*out = h->stat_spec_rank;
+	else if (!std::strcmp(name, "base_bytes"))
+		*out = h->d_base ? (uint64_t)h->n * (uint64_t)h->dim * h->elem : 0;
 	else if (!std::strcmp(name, "filter_active"))
 		*out = h->filter_on ? 1 : 0;
 	else if (!std::strcmp(name, "filter_rows"))
@@ -3436,8 +3481,9 @@ int set_row_filter(expann_index* h, const uint32_t* bits, size_t n_words, bool o
 		return EXPANN_ERR_INVALID_ARG;
 	if (!bits)
 		return h->fail(EXPANN_ERR_INVALID_ARG, "row filter: NULL bits");
-	if (h->dtype != EXPANN_DTYPE_F32)
-		return h->fail(EXPANN_ERR_UNSUPPORTED, "row filter: fp32 rows only (8-bit and int16 rows have integer row terms)");
+	if (!float_rows(h))
+		return h->fail(EXPANN_ERR_UNSUPPORTED,
+		               "row filter: fp32 / fp16 rows only (8-bit and int16 rows have integer row terms)");
 	if (!h->d_base)
 		return h->fail(EXPANN_ERR_NOT_BUILT, "row filter before build()");
 	const size_t need_words = (h->n + 31) / 32;

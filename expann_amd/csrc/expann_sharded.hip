@@ -205,7 +205,7 @@ int common_create(int dim, int dtype, int metric, expann_sharded** out, expann_s
 	h->dim = dim;
 	h->dtype = dtype;
 	h->metric = metric;
-	h->elem = (dtype == EXPANN_DTYPE_F32) ? 4 : (dtype == EXPANN_DTYPE_I16 ? 2 : 1);
+	h->elem = (dtype == EXPANN_DTYPE_F32) ? 4 : ((dtype == EXPANN_DTYPE_I16 || dtype == EXPANN_DTYPE_F16) ? 2 : 1);
 	h->q_elem = (dtype == EXPANN_DTYPE_I8) ? 1 : (dtype == EXPANN_DTYPE_I16 ? 2 : 4);
 	return EXPANN_OK;
 }

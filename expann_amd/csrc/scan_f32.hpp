@@ -223,7 +223,10 @@ __global__ __launch_bounds__(kBlock) void scan_filter_f32_kernel(ScanParams p) {
 // odd d/16 needs nothing special.  The TQ queries of the workgroup sit in LDS (TQ x kMaxAnyDim floats,
 // 16 lanes of a row read the same 64 B: broadcast), so a 4096-wide query costs no registers.
 constexpr int kMaxAnyDim = 4096;
-template <int TQ, bool IP, int RF = kRowsAll>
+// TR = the rows' element type (common.hpp: ref_diff / ref_dot).  _Float16 rows (EXPANN_DTYPE_F16, served at every
+// dim by these instances) are half the bytes per load, so twice as many loads are kept in flight per lane: the
+// same bytes on the way as the float instance has.
+template <int TQ, bool IP, int RF = kRowsAll, typename TR = float>
 __global__ __launch_bounds__(kBlock) void scan_filter_f32_any_kernel(ScanParams p) {
 	__shared__ float qs[TQ * kMaxAnyDim];
 	const uint32_t D = p.dim, DPL = D / 16;
@@ -233,9 +236,10 @@ __global__ __launch_bounds__(kBlock) void scan_filter_f32_any_kernel(ScanParams 
 	const uint32_t qtile = blockIdx.x % p.n_qtiles;
 	const uint32_t chunk = blockIdx.x / p.n_qtiles;
 	const uint32_t q0 = qtile * TQ;
-	const float* __restrict__ base = (const float*)p.base;
+	const TR* __restrict__ base = (const TR*)p.base;
 	const float* __restrict__ queries = (const float*)p.queries;
 	const bool level0 = (p.tau == nullptr);
+	constexpr int U = sizeof(TR) == 2 ? 8 : 4;  // loads in flight per lane
 
 	for (uint32_t i = threadIdx.x; i < TQ * D; i += kBlock) {
 		const uint32_t j = i / D;
@@ -271,40 +275,40 @@ __global__ __launch_bounds__(kBlock) void scan_filter_f32_any_kernel(ScanParams 
 		bool rvalid = in_range;
 		if (RF == kRowsBitmap && in_range)
 			rvalid = (p.allow_bits[row >> 5] >> (row & 31)) & 1u;
-		const float* src = base + (size_t)(in_range ? row : p.n_rows - 1) * D + l;
+		const TR* src = base + (size_t)(in_range ? row : p.n_rows - 1) * D + l;
 		const float* qsl = qs + l;
 		float acc[TQ];
 #pragma unroll
 		for (int j = 0; j < TQ; ++j)
 			acc[j] = 0.0f;
 		uint32_t t = 0;
-		for (; t + 4 <= DPL; t += 4) {  // (four loads in flight per lane)
-			float r[4];
+		for (; t + U <= DPL; t += U) {  // (U loads in flight per lane)
+			TR r[U];
 #pragma unroll
-			for (int u = 0; u < 4; ++u)
+			for (int u = 0; u < U; ++u)
 				r[u] = src[16 * (t + u)];
 #pragma unroll
-			for (int u = 0; u < 4; ++u)
+			for (int u = 0; u < U; ++u)
 #pragma unroll
 				for (int j = 0; j < TQ; ++j) {
 					const float qv = qsl[j * D + 16 * (t + u)];
 					if (IP) {
-						acc[j] = __builtin_fmaf(qv, r[u], acc[j]);
+						acc[j] = ref_dot<TR>(qv, r[u], acc[j]);
 					} else {
-						const float diff = qv - r[u];
+						const float diff = ref_diff<TR>(qv, r[u]);
 						acc[j] = __builtin_fmaf(diff, diff, acc[j]);
 					}
 				}
 		}
 		for (; t < DPL; ++t) {
-			const float rv = src[16 * t];
+			const TR rv = src[16 * t];
 #pragma unroll
 			for (int j = 0; j < TQ; ++j) {
 				const float qv = qsl[j * D + 16 * t];
 				if (IP) {
-					acc[j] = __builtin_fmaf(qv, rv, acc[j]);
+					acc[j] = ref_dot<TR>(qv, rv, acc[j]);
 				} else {
-					const float diff = qv - rv;
+					const float diff = ref_diff<TR>(qv, rv);
 					acc[j] = __builtin_fmaf(diff, diff, acc[j]);
 				}
 			}

@@ -84,10 +84,14 @@ __global__ __launch_bounds__(kBlock) void convert_f16_kernel(const float* in, si
 }
 
 // bit pattern of max |x| over an array (see convert_f16_kernel); *out zeroed by the caller
-__global__ __launch_bounds__(kBlock) void maxabs_bits_kernel(const float* in, size_t n, uint32_t* out) {
+// (TS = the source's element type, here and in sqnorm_any_kernel / convert_f16_pad_kernel -- the prelude of an
+// EXPANN_DTYPE_F16 index at every dim: _Float16 rows are converted to fp32 -- exactly -- and then treated as fp32
+// rows are, so the scaled copy, the norms and max |x| are the bits an fp32 index of the same values gets)
+template <typename TS = float>
+__global__ __launch_bounds__(kBlock) void maxabs_bits_kernel(const TS* in, size_t n, uint32_t* out) {
 	uint32_t b = 0;
 	for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
-		const uint32_t v = __builtin_bit_cast(uint32_t, in[i]) & 0x7fffffffu;
+		const uint32_t v = __builtin_bit_cast(uint32_t, (float)in[i]) & 0x7fffffffu;
 		b = v > b ? v : b;
 	}
 	for (int off = 32; off > 0; off >>= 1) {
@@ -200,26 +204,29 @@ __global__ __launch_bounds__(kBlock) void f16_query_prep_kernel(const float* q, 
 // The prelude at a dim known at run time (scan_gemm_f16kl.hpp: the dims without a compiled fp16 form).
 // The fp16 copies there have rows of ld = d rounded up to a multiple of 32 elements (whole MFMA k-steps),
 // zero past d; norms and the range check are those of the d real elements.
-__global__ __launch_bounds__(kBlock) void sqnorm_any_kernel(const float* x, uint32_t n, uint32_t d, float* out) {
+// (_Float16 rows take this kernel at every dim: the same FMA chain and reduction as sqnorm_kernel<D>, same bits)
+template <typename TS = float>
+__global__ __launch_bounds__(kBlock) void sqnorm_any_kernel(const TS* x, uint32_t n, uint32_t d, float* out) {
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	const int l = lane & 15, rg = lane >> 4;
 	const uint32_t i = blockIdx.x * kRowsPerGroup + wave * kRowsPerWaveStep + rg;
 	const uint32_t ii = i < n ? i : n - 1;
-	const float* src = x + (size_t)ii * d + l;
+	const TS* src = x + (size_t)ii * d + l;
 	float acc = 0.0f;
 	for (uint32_t t = 0; t < d / 16; ++t)
-		acc = __builtin_fmaf(src[16 * t], src[16 * t], acc);
+		acc = __builtin_fmaf((float)src[16 * t], (float)src[16 * t], acc);
 	acc = reduce16_ref_order(acc);
 	if (i < n && l == 0)
 		out[i] = acc;
 }
 // fp32 [n][d] * scale -> fp16 [n][ld] (zero columns d .. ld-1)
-__global__ __launch_bounds__(kBlock) void convert_f16_pad_kernel(const float* in, size_t n, uint32_t d, uint32_t ld,
+template <typename TS = float>
+__global__ __launch_bounds__(kBlock) void convert_f16_pad_kernel(const TS* in, size_t n, uint32_t d, uint32_t ld,
                                                                  float scale, _Float16* out) {
 	for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n * ld; i += (size_t)gridDim.x * kBlock) {
 		const size_t r = i / ld;
 		const uint32_t c = (uint32_t)(i - r * ld);
-		out[i] = c < d ? (_Float16)(in[r * d + c] * scale) : (_Float16)0.0f;
+		out[i] = c < d ? (_Float16)((float)in[r * d + c] * scale) : (_Float16)0.0f;
 	}
 }
 // f16_query_prep_kernel<D> at run-time d: same outputs (q16 with rows of ld, zero-padded), same per-query

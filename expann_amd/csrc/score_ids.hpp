@@ -43,8 +43,9 @@ __global__ __launch_bounds__(kBlock) void score_ids_f32_kernel(ScoreIdsParams p)
 		p.scores[i] = IP ? -acc : acc;
 }
 
-// the same with the dim known at run time (the dims without an instance of their own)
-template <bool IP>
+// the same with the dim known at run time (the dims without an instance of their own; TR = _Float16: the
+// rows of an EXPANN_DTYPE_F16 index at every dim, common.hpp: ref_diff / ref_dot)
+template <bool IP, typename TR = float>
 __global__ __launch_bounds__(kBlock) void score_ids_f32_any_kernel(ScoreIdsParams p) {
 	const uint32_t D = p.dim;
 	const int lane = threadIdx.x & 63;
@@ -53,14 +54,14 @@ __global__ __launch_bounds__(kBlock) void score_ids_f32_any_kernel(ScoreIdsParam
 	const uint32_t i = blockIdx.x * kRowsPerGroup + wave * kRowsPerWaveStep + rg;
 	const bool valid = i < p.n_ids;
 	const uint64_t row = p.ids[valid ? i : p.n_ids - 1] - p.id_offset;
-	const float* __restrict__ r = (const float*)p.base + (size_t)row * D + l;
+	const TR* __restrict__ r = (const TR*)p.base + (size_t)row * D + l;
 	const float* __restrict__ q = (const float*)p.query + l;
 	float acc = 0.0f;
 	for (uint32_t t = 0; t < D / 16; ++t) {
 		if (IP) {
-			acc = __builtin_fmaf(q[16 * t], r[16 * t], acc);
+			acc = ref_dot<TR>(q[16 * t], r[16 * t], acc);
 		} else {
-			const float diff = q[16 * t] - r[16 * t];
+			const float diff = ref_diff<TR>(q[16 * t], r[16 * t]);
 			acc = __builtin_fmaf(diff, diff, acc);
 		}
 	}

@@ -22,7 +22,7 @@ struct SelectParams {
 	const uint32_t* tau_row_prev;
 	// re-rank (GEMM-form scan): when rerank_base != nullptr the keys hold only a row number
 	// (low 32 bits); the exact reference-order score is recomputed here before the sort
-	const float* rerank_base;     // [n][dim]
+	const float* rerank_base;     // [n][dim] (the _Float16 instances of the select kernels: binary16 rows behind the pointer)
 	const float* rerank_queries;  // [m][dim]
 	uint32_t dim;
 	uint32_t metric_ip;
@@ -281,7 +281,8 @@ __device__ inline uint2 wave_kth_largest_sparse_u32(const uint32_t (&v)[PER], ui
 }
 
 // one wave orders the list of query slot qi (c <= 64 * PER keys); list = 64 * PER keys of LDS
-template <int PER>
+// (TR = element type of the re-rank rows: common.hpp ref_diff / ref_dot)
+template <int PER, typename TR = float>
 __device__ inline void select_wave_body(const SelectParams& p, uint32_t qi, uint32_t c, uint64_t* list,
                                         int lane) {
 	const uint64_t* src = p.cand + (size_t)qi * p.cap;
@@ -357,12 +358,12 @@ __device__ inline void select_wave_body(const SelectParams& p, uint32_t qi, uint
 		constexpr int U = 4;  // candidates per 16-lane group in flight
 		float acc[U];
 		uint32_t row[U];
-		const float* r[U];
+		const TR* r[U];
 #pragma unroll
 		for (int u = 0; u < U; ++u) {
 			const uint32_t i = i0 + 4 * u + grp;
 			row[u] = key_idx(list[i < n_s ? i : 0]);
-			r[u] = p.rerank_base + (size_t)row[u] * p.dim + l;
+			r[u] = (const TR*)p.rerank_base + (size_t)row[u] * p.dim + l;
 			acc[u] = 0.0f;
 		}
 		// 8 dims of every candidate are requested before any is consumed (the trip count is a
@@ -370,7 +371,8 @@ __device__ inline void select_wave_body(const SelectParams& p, uint32_t qi, uint
 		// FMA chain still runs over t in increasing order, as the reference's lane does
 		const uint32_t nt = p.dim / 16;
 		for (uint32_t t0 = 0; t0 < nt; t0 += 8) {
-			float qv[8], rv[U][8];
+			float qv[8];
+			TR rv[U][8];
 #pragma unroll
 			for (int t = 0; t < 8; ++t)
 				qv[t] = t0 + t < nt ? q[16 * (t0 + t)] : 0.0f;
@@ -378,7 +380,7 @@ __device__ inline void select_wave_body(const SelectParams& p, uint32_t qi, uint
 			for (int u = 0; u < U; ++u)
 #pragma unroll
 				for (int t = 0; t < 8; ++t)
-					rv[u][t] = t0 + t < nt ? r[u][16 * (t0 + t)] : 0.0f;
+					rv[u][t] = t0 + t < nt ? r[u][16 * (t0 + t)] : (TR)0.0f;
 #pragma unroll
 			for (int u = 0; u < U; ++u)
 #pragma unroll
@@ -386,9 +388,9 @@ __device__ inline void select_wave_body(const SelectParams& p, uint32_t qi, uint
 					if (t0 + t >= nt)
 						continue;  // (d = 64: four dims per lane)
 					if (p.metric_ip) {
-						acc[u] = __builtin_fmaf(qv[t], rv[u][t], acc[u]);
+						acc[u] = ref_dot<TR>(qv[t], rv[u][t], acc[u]);
 					} else {
-						const float diff = qv[t] - rv[u][t];
+						const float diff = ref_diff<TR>(qv[t], rv[u][t]);
 						acc[u] = __builtin_fmaf(diff, diff, acc[u]);
 					}
 				}
@@ -409,7 +411,7 @@ __device__ inline void select_wave_body(const SelectParams& p, uint32_t qi, uint
 }
 
 // lists of at most 64 * PER keys; WAVES queries per workgroup (PER = 32: one, its list is 16 KB)
-template <int PER, int WAVES>
+template <int PER, int WAVES, typename TR = float>
 __global__ __launch_bounds__(64 * WAVES) void select_wave_kernel(SelectParams p, uint32_t m) {
 	constexpr uint32_t kSelectWaveMax = 64 * PER;
 	__shared__ uint64_t lists[WAVES][kSelectWaveMax];
@@ -421,10 +423,12 @@ __global__ __launch_bounds__(64 * WAVES) void select_wave_kernel(SelectParams p,
 	const uint32_t c = p.cand_cnt ? p.cand_cnt[qi] : p.fixed_count;
 	if (c > kSelectWaveMax || c > p.cap || (c <= p.wave_done && p.wave_done != 0))
 		return;  // longer lists: the next size up; shorter ones: already served
-	select_wave_body<PER>(p, qi, c, lists[wave], lane);
+	select_wave_body<PER, TR>(p, qi, c, lists[wave], lane);
 }
 
 // One workgroup per query: bitonic sort of the (power-of-two padded) key list in LDS.
+// (select_topk_kernel<float>: the rows behind rerank_base are float; <_Float16>: the rows of an EXPANN_DTYPE_F16 index)
+template <typename TR>
 __global__ __launch_bounds__(kBlock) void select_topk_kernel(SelectParams p) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
 	uint64_t* keys = reinterpret_cast<uint64_t*>(smem_raw);
@@ -441,9 +445,9 @@ __global__ __launch_bounds__(kBlock) void select_topk_kernel(SelectParams p) {
 		// short list, the other waves leave
 		if (tid < 64) {
 			if (c <= 512)
-				select_wave_body<8>(p, qi, c, keys, (int)tid);
+				select_wave_body<8, TR>(p, qi, c, keys, (int)tid);
 			else
-				select_wave_body<32>(p, qi, c, keys, (int)tid);
+				select_wave_body<32, TR>(p, qi, c, keys, (int)tid);
 		}
 		return;
 	}
@@ -531,13 +535,13 @@ __global__ __launch_bounds__(kBlock) void select_topk_kernel(SelectParams p) {
 			const uint32_t i = i0 + grp;
 			const bool live = i < n_rescore;
 			const uint32_t row = live ? key_idx(keys[i]) : 0u;
-			const float* r = p.rerank_base + (size_t)row * p.dim + l;
+			const TR* r = (const TR*)p.rerank_base + (size_t)row * p.dim + l;
 			float acc = 0.0f;
 			for (uint32_t t = 0; t < p.dim / 16; ++t) {
 				if (p.metric_ip) {
-					acc = __builtin_fmaf(q[16 * t], r[16 * t], acc);
+					acc = ref_dot<TR>(q[16 * t], r[16 * t], acc);
 				} else {
-					const float diff = q[16 * t] - r[16 * t];
+					const float diff = ref_diff<TR>(q[16 * t], r[16 * t]);
 					acc = __builtin_fmaf(diff, diff, acc);
 				}
 			}

@@ -14,7 +14,11 @@ import numpy as np
 from . import _lib
 
 _NP_DTYPE = {_lib.DTYPE_F32: np.float32, _lib.DTYPE_U8: np.uint8, _lib.DTYPE_I8: np.int8,
-             _lib.DTYPE_I16: np.int16}
+             _lib.DTYPE_I16: np.int16, _lib.DTYPE_F16: np.float16}
+_DTYPE = {"f32": _lib.DTYPE_F32, "u8": _lib.DTYPE_U8, "i8": _lib.DTYPE_I8, "i16": _lib.DTYPE_I16,
+          "f16": _lib.DTYPE_F16}
+# row types whose queries are fp32 at the ABI (the others take queries of the rows' own type)
+_F32_QUERIES = (_lib.DTYPE_F32, _lib.DTYPE_U8, _lib.DTYPE_F16)
 
 
 def pack_row_filter(allow):
@@ -28,15 +32,18 @@ def pack_row_filter(allow):
 
 
 class GpuBruteForceEngine:
-    """Exact k-NN by a full scan on one MI355X (drop-in for brute_force_engine<float>)."""
+    """Exact k-NN by a full scan on one MI355X (drop-in for brute_force_engine<float>).
+
+    dtype="f16": the rows are kept as IEEE binary16 (numpy casts what is stored, rounding to nearest even),
+    half the device memory of "f32"; queries stay float32 and every result is, bit for bit, that of an "f32"
+    engine over rows.astype(np.float16).astype(np.float32)."""
 
     def __init__(self, dim, metric="l2", dtype="f32", device=0):
         self._L = _lib.load()
         self.dim = int(dim)
         self.metric = {"l2": _lib.METRIC_L2, "ip": _lib.METRIC_IP,
                        "l2_i8_refcompat": _lib.METRIC_L2_I8_REFCOMPAT}[metric]
-        self.dtype = {"f32": _lib.DTYPE_F32, "u8": _lib.DTYPE_U8, "i8": _lib.DTYPE_I8,
-                      "i16": _lib.DTYPE_I16}[dtype]
+        self.dtype = _DTYPE[dtype]
         self.device = int(device)
         self._metric_name, self._dtype_name = metric, dtype
         h = C.c_void_p()
@@ -74,7 +81,7 @@ class GpuBruteForceEngine:
     # ---- extensions ---------------------------------------------------------------
     def query_k_batch(self, queries, k):
         """(ids[m,k] uint64, dists[m,k] float32); short rows padded with 2^64-1 / +inf."""
-        qdt = np.float32 if self.dtype in (_lib.DTYPE_F32, _lib.DTYPE_U8) else _NP_DTYPE[self.dtype]
+        qdt = np.float32 if self.dtype in _F32_QUERIES else _NP_DTYPE[self.dtype]
         queries = np.ascontiguousarray(queries, dtype=qdt)
         if queries.ndim != 2 or queries.shape[1] != self.dim:
             raise ValueError(f"queries must be [m, {self.dim}]")
@@ -100,7 +107,7 @@ class GpuBruteForceEngine:
 
     def score_ids(self, query, ids, cutoff=float("inf")):
         """quantized_scorer::filter_by_score (src/quantizer.h:20-59): (kept_ids, kept_scores)."""
-        qdt = np.float32 if self.dtype in (_lib.DTYPE_F32, _lib.DTYPE_U8) else _NP_DTYPE[self.dtype]
+        qdt = np.float32 if self.dtype in _F32_QUERIES else _NP_DTYPE[self.dtype]
         query = np.ascontiguousarray(query, dtype=qdt)
         ids = np.ascontiguousarray(ids, dtype=np.uint64)
         kept = np.empty(ids.size, dtype=np.uint64)
@@ -117,7 +124,7 @@ class GpuBruteForceEngine:
     def set_row_filter(self, allow):
         """expann_set_row_filter: searches return the nearest among the rows where the boolean array
         allow[n] is true (local row numbers, before id_offset), exactly as an index of those rows would;
-        None clears the filter (expann_clear_row_filter).  fp32 rows only."""
+        None clears the filter (expann_clear_row_filter).  fp32 and fp16 rows only."""
         if allow is None:
             _lib.check(self._h, self._L.expann_clear_row_filter(self._h))
             return
@@ -132,7 +139,8 @@ class GpuBruteForceEngine:
 
     def get_stat(self, name):
         """expann_get_stat: "redo_queries", "redo_overflows", "spec_rank" (speculative thresholds);
-        "filter_active" (0 / 1) and "filter_rows" (rows the row filter allows; n when none is set)."""
+        "filter_active" (0 / 1) and "filter_rows" (rows the row filter allows; n when none is set);
+        "base_bytes" (device bytes of the rows themselves: n * dim * element size)."""
         v = C.c_uint64(0)
         _lib.check(self._h, self._L.expann_get_stat(self._h, name.encode(), C.byref(v)))
         return int(v.value)
@@ -174,8 +182,8 @@ class ShardedBruteForceEngine:
         self.dim = int(dim)
         self.metric = {"l2": _lib.METRIC_L2, "ip": _lib.METRIC_IP,
                        "l2_i8_refcompat": _lib.METRIC_L2_I8_REFCOMPAT}[metric]
-        self.dtype = {"f32": _lib.DTYPE_F32, "u8": _lib.DTYPE_U8, "i8": _lib.DTYPE_I8,
-                      "i16": _lib.DTYPE_I16}[dtype]
+        self.dtype = _DTYPE[dtype]
+        self._dtype_name = dtype
         h = C.c_void_p()
         if rank is None:
             devs = list(devices if devices is not None else [device])
@@ -209,7 +217,7 @@ class ShardedBruteForceEngine:
         return "GPU Brute-Force Engine, row-sharded (MI355X)"
 
     def param_list(self):
-        return {"devices": ",".join(map(str, self.devices)), "shards": str(self.shards()),
+        return {"devices": ",".join(map(str, self.devices)), "shards": str(self.shards()), "dtype": self._dtype_name,
                 "exchange": {0: "none", 1: "rccl", 2: "device copies", 3: "caller"}[self.exchange()],
                 "exchange_pattern": {0: "none", 1: "all-gather", 2: "all-to-all of query slices"}[self.exchange_pattern()]}
 
@@ -229,7 +237,7 @@ class ShardedBruteForceEngine:
         self._check(self._L.expann_sharded_set_shard_device(self._h, int(shard), C.c_void_p(ptr), n, id_offset))
 
     def query_k_batch(self, queries, k):
-        qdt = np.float32 if self.dtype in (_lib.DTYPE_F32, _lib.DTYPE_U8) else _NP_DTYPE[self.dtype]
+        qdt = np.float32 if self.dtype in _F32_QUERIES else _NP_DTYPE[self.dtype]
         queries = np.ascontiguousarray(queries, dtype=qdt)
         if queries.ndim != 2 or queries.shape[1] != self.dim:
             raise ValueError(f"queries must be [m, {self.dim}]")

@@ -24,6 +24,7 @@
 
 #include "ann_engine.h"
 #include "expann_hip.h"
+#include "half.h"
 
 struct gpu_brute_force_engine_config {
 	int device = 0;
@@ -41,9 +42,24 @@ struct gpu_brute_force_engine_config {
 	      devices(std::move(_devices)) {}
 };
 
+// gpu_brute_force_engine<float>::config: the same, plus rows_f16.  When set, every stored float is rounded to
+// IEEE binary16 (expann::f32_to_f16_bits: nearest even, overflow to +-inf, NaN kept, subnormals produced) and the
+// library holds EXPANN_DTYPE_F16 rows: half the device memory and upload, results those of an engine over the
+// rounded values, bit for bit.  Queries stay vec<float>.  Only the float engine's config has the member, so
+// naming it for any other T does not compile.
+struct gpu_brute_force_engine_config_f32 : gpu_brute_force_engine_config {
+	using gpu_brute_force_engine_config::gpu_brute_force_engine_config;
+	gpu_brute_force_engine_config_f32() = default;
+	gpu_brute_force_engine_config_f32(const gpu_brute_force_engine_config& c) : gpu_brute_force_engine_config(c) {}
+	bool rows_f16 = false;
+};
+inline bool gpu_brute_force_rows_f16(const gpu_brute_force_engine_config_f32& c) { return c.rows_f16; }
+inline bool gpu_brute_force_rows_f16(const gpu_brute_force_engine_config&) { return false; }
+
 template <typename T>
 struct gpu_brute_force_engine : public ann_engine<T, gpu_brute_force_engine<T>> {
-	using config = gpu_brute_force_engine_config;
+	using config = typename std::conditional<std::is_same<T, float>::value, gpu_brute_force_engine_config_f32,
+	                                         gpu_brute_force_engine_config>::type;
 	config conf;
 	expann_index* handle = nullptr;
 	expann_sharded* sharded = nullptr;  // conf.devices.size() > 1
@@ -67,14 +83,14 @@ struct gpu_brute_force_engine : public ann_engine<T, gpu_brute_force_engine<T>> 
 		std::vector<T> row(dimension);
 		for (size_t i = 0; i < dimension; ++i)
 			row[i] = v.at(i);
-		check(sharded ? expann_sharded_add(sharded, row.data(), 1) : expann_add(handle, row.data(), 1));
+		add_rows(row.data(), 1);
 		++stored;
 	}
 	// batch form of store_vector (cf. store_many_vectors, src/pyrunner.cpp:60-82)
 	void store_rows(const T* rows, size_t n, size_t dim) {
 		if (!opened())
 			open(dim);
-		check(sharded ? expann_sharded_add(sharded, rows, n) : expann_add(handle, rows, n));
+		add_rows(rows, n);
 		stored += n;
 	}
 	void _build() {
@@ -130,6 +146,8 @@ struct gpu_brute_force_engine : public ann_engine<T, gpu_brute_force_engine<T>> 
 		}
 		pl["metric"] = conf.metric == EXPANN_METRIC_IP ? "ip" : "l2";
 		pl["query_tile"] = std::to_string(conf.query_tile);
+		if (gpu_brute_force_rows_f16(conf))
+			pl["rows"] = "f16";
 		return pl;
 	}
 
@@ -146,6 +164,18 @@ private:
 		                                         : EXPANN_DTYPE_I16;
 	}
 	bool opened() const { return handle || sharded; }
+	// n rows of `dimension` elements to the library: as they are, or rounded to binary16 (config::rows_f16)
+	void add_rows(const T* rows, size_t n) {
+		const void* src = rows;
+		std::vector<uint16_t> half;
+		if (gpu_brute_force_rows_f16(conf)) {
+			half.resize(n * dimension);
+			for (size_t i = 0; i < half.size(); ++i)
+				half[i] = expann::f32_to_f16_bits(float(rows[i]));
+			src = half.data();
+		}
+		check(sharded ? expann_sharded_add(sharded, src, n) : expann_add(handle, src, n));
+	}
 	// the row filter's entry points: a built single-device engine
 	void single(const char* what) const {
 		if (!handle)
@@ -154,8 +184,9 @@ private:
 	}
 	void open(size_t dim) {
 		dimension = dim;
+		const int dtype = gpu_brute_force_rows_f16(conf) ? int(EXPANN_DTYPE_F16) : dtype_of();
 		if (conf.devices.size() > 1) {
-			int rc = expann_sharded_create(int(dim), dtype_of(), conf.metric, conf.devices.data(),
+			int rc = expann_sharded_create(int(dim), dtype, conf.metric, conf.devices.data(),
 			                               int(conf.devices.size()), &sharded);
 			if (rc != EXPANN_OK)
 				throw std::runtime_error(std::string("expann_sharded_create: ") + expann_sharded_last_error(nullptr));
@@ -163,7 +194,7 @@ private:
 				check(expann_sharded_set_option(sharded, "query_tile", conf.query_tile));
 			return;
 		}
-		int rc = expann_create(int(dim), dtype_of(), conf.metric, conf.devices.empty() ? conf.device : conf.devices[0],
+		int rc = expann_create(int(dim), dtype, conf.metric, conf.devices.empty() ? conf.device : conf.devices[0],
 		                       &handle);
 		if (rc != EXPANN_OK)
 			throw std::runtime_error(std::string("expann_create: ") + expann_last_error(nullptr));

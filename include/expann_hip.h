@@ -42,11 +42,30 @@ enum expann_dtype {
 	EXPANN_DTYPE_F32 = 0, /* vec<float> rows, src/vec.h:17-23                         */
 	EXPANN_DTYPE_U8 = 1,  /* quantizer_simple<uint8_t> rows, src/quantizer.h:127      */
 	EXPANN_DTYPE_I8 = 2,  /* quantizer_ranged_q8 rows, src/quantizer.h:152-238        */
-	EXPANN_DTYPE_I16 = 3  /* int16 rows scored by src/distance.h:14-27 bit for bit
+	EXPANN_DTYPE_I16 = 3, /* int16 rows scored by src/distance.h:14-27 bit for bit
 	                       * (distance_compare_avx512f_i32: 16-bit wrapping arithmetic,
 	                       * exact only while |a_i - b_i| <= 181); EXPANN_METRIC_L2 only,
 	                       * dim 64 or 128; queries int16                            */
+	EXPANN_DTYPE_F16 = 4  /* IEEE binary16 rows, see below (appended; EXPANN_ABI_VERSION stays 2:
+	                       * nothing that existed changed)                            */
 };
+/* EXPANN_DTYPE_F16: rows are IEEE binary16, [n][dim], 2 bytes per element -- in expann_add's staging, on the
+ * device and for expann_set_base_device -- and stay binary16 on the device (expann_get_stat "base_bytes").  Queries
+ * are fp32 [m][dim], as for F32 and U8 rows.  Metrics EXPANN_METRIC_L2 and EXPANN_METRIC_IP (anything else
+ * EXPANN_ERR_INVALID_ARG); dim: the f32 rule (any multiple of 16 up to 4096).
+ * THE RULE: every entry point returns, bit for bit (ids and fp32 distance bits, ties by lower id, padding as
+ * everywhere), what an EXPANN_DTYPE_F32 index holding (float)row would return -- the reference's FMA lane order on
+ * the exactly converted values.  binary16 subnormals convert exactly, nothing is flushed; rows with +-inf or NaN
+ * behave as the same values do in an F32 index.  Covered: expann_search and expann_search_device (latency mode,
+ * "async_search" with expann_sync, k up to 8192), expann_score_ids, expann_set_base_device with id_offset, the
+ * row filter, and the expann_sharded_* handles created with this dtype.
+ * How: the fp16 filter copy, its row terms and max ||b||^2 are built from the converted values and are the bits
+ * the F32 index of the same values builds, so the matrix-core filters, their candidate lists and the speculative
+ * thresholds ("spec_rank") run unchanged; the exact side -- the direct scan, the re-rank inside the select
+ * kernels, expann_score_ids -- reads the binary16 rows and converts on load (at every dim through the run-time-dim
+ * instances).  An F16 index never takes the uint8 shadow ("u8_exact"), the int8 filter ("i8_filter") or the
+ * bf16x3 form, which build their operands from fp32 storage: the options are accepted and ignored, "scan_kernel" 3
+ * runs the exact direct scan (as do queries outside the fp16 range), as under a row filter. */
 
 /* how a (query, row) pair is scored; smaller score = nearer */
 enum expann_metric {
@@ -67,7 +86,7 @@ int expann_abi_version(void);
 int expann_device_count(void);
 
 /* lifecycle (replaces: engine construction, src/bench_runner.h:33) -------------------- */
-/* dim: a multiple of 16 (else EXPANN_ERR_INVALID_ARG).  f32 rows: any such dim up to 4096 (over it:
+/* dim: a multiple of 16 (else EXPANN_ERR_INVALID_ARG).  f32 and f16 rows: any such dim up to 4096 (over it:
  * EXPANN_ERR_UNSUPPORTED, checked before the device); 8-bit rows (U8, I8): any multiple of 64 up to 4096
  * (not a multiple of 64: EXPANN_ERR_INVALID_ARG; over 4096: EXPANN_ERR_UNSUPPORTED, checked before the device;
  * 64, 128, 256, 768, 832, 960 have kernels compiled for them, the others run with the dim known at run time --
@@ -480,7 +499,8 @@ int expann_set_option(expann_index* h, const char* name, long value);
  * redo pass of the speculative thresholds served (deferred searches: of the searches the last expann_sync
  * checked), "redo_overflows" = searches since the handle was made whose failing queries did not fit the redo
  * pass (repeated with proven thresholds: a retry), "spec_rank" = the rank j of the last search's thresholds
- * (= k: proven thresholds). */
+ * (= k: proven thresholds), "base_bytes" = bytes of device memory that hold the rows themselves (n * dim * bytes
+ * per element, every dtype; 0 before the rows are on the device). */
 int expann_get_stat(expann_index* h, const char* name, uint64_t* out);
 /* the auto rank for k neighbours when the sampled pass reads 1/sample_frac of the rows: the smallest j with
  * P(Bin(k - 1, 1/sample_frac) >= j) <= 1 %; k = no speculation.  Host arithmetic only. */
@@ -502,8 +522,8 @@ uint32_t expann_spec_rank_auto(size_t k, uint32_t sample_frac);
  * own) and returns after that stream and the handle's own have drained: the allowed-row count is needed on the
  * host for planning -- one host wait per filter change, none per search.  expann_build and
  * expann_set_base_device clear the filter.
- * Errors, in this order: h == NULL or bits == NULL EXPANN_ERR_INVALID_ARG; a dtype other than EXPANN_DTYPE_F32
- * EXPANN_ERR_UNSUPPORTED (8-bit and int16 rows have integer row terms without a NaN: not offered) -- both before
+ * Errors, in this order: h == NULL or bits == NULL EXPANN_ERR_INVALID_ARG; a dtype other than EXPANN_DTYPE_F32 /
+ * EXPANN_DTYPE_F16 EXPANN_ERR_UNSUPPORTED (8-bit and int16 rows have integer row terms without a NaN: not offered) -- both before
  * the device is touched --; no rows on the device yet EXPANN_ERR_NOT_BUILT; n_words < ceil(n / 32)
  * EXPANN_ERR_INVALID_ARG.  A failed call leaves the filter as it was.
  * A filtered search never takes the uint8 shadow index ("u8_exact"), the int8 filter ("i8_filter") or
