@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "expann_set_row_filter", "expann_set_row_filter_device", "expann_clear_row_filter",
     "expann_graph_set_row_filter", "expann_graph_set_row_filter_device", "expann_graph_clear_row_filter",
     "expann_antitopo_set_row_filter", "expann_antitopo_set_row_filter_device",
+    "expann_graph_create_f16", "expann_antitopo_set_rows_f16",
 ]
 
 
@@ -283,6 +284,11 @@ def load():
         L.expann_antitopo_set_row_filter.argtypes = [vp, vp, sz]
         L.expann_antitopo_set_row_filter_device.restype = C.c_int
         L.expann_antitopo_set_row_filter_device.argtypes = [vp, vp, sz, vp]
+    if hasattr(L, "expann_graph_create_f16"):  # (as above: an older build has no binary16 graph rows)
+        L.expann_graph_create_f16.restype = C.c_int
+        L.expann_graph_create_f16.argtypes = [C.c_int, C.c_int, vp, sz, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(vp)]
+        L.expann_antitopo_set_rows_f16.restype = C.c_int
+        L.expann_antitopo_set_rows_f16.argtypes = [vp, C.c_int]
     _lib = L
     return L
 

@@ -27,7 +27,10 @@ struct expann_graph {
 	int dim = 0, device = 0;
 	size_t n = 0;
 	uint32_t n_layers = 0, starting_vertex = 0, max_degree0 = 0;
-	float* d_vectors = nullptr;
+	// the rows: [n][dim] floats, or -- rows_f16, a handle made by expann_graph_create_f16 -- [n][dim] binary16 values;
+	// the flag picks the _Float16 instances of the walk, the scan and the quantisers, and nothing else
+	void* d_vectors = nullptr;
+	bool rows_f16 = false;
 	uint8_t* d_compressed = nullptr;
 	// quantizer_ranged_q8 copy of the rows (bytes in [0, 127]) with its scale_factor / offset, built at the first
 	// use of the ranged mode; ranged_state: 0 = not built yet, 1 = usable, -1 = the quantiser is unusable
@@ -91,32 +94,42 @@ struct GraphVariant {
 	int d;
 	int mode;       // expann_graph_compression
 	bool filtered;  // the instance that walks under a row filter (THE FILTER RULE, graph_search.hpp)
+	bool f16;       // the instance over binary16 rows (TR = _Float16)
 	GraphFn fn;
 };
-#define GRAPH_VF(D, F)                                                          \
-	{D, kGraphF32, F, graph_search_kernel<D, kGraphF32, 0, F>},                 \
-	{D, kGraphU8Cast, F, graph_search_kernel<D, kGraphU8Cast, 0, F>},           \
-	{D, kGraphRangedQ8, F, graph_search_kernel<D, kGraphRangedQ8, 0, F>}
+#define GRAPH_VF(D, F)                                                                 \
+	{D, kGraphF32, F, false, graph_search_kernel<D, kGraphF32, 0, F>},                 \
+	{D, kGraphU8Cast, F, false, graph_search_kernel<D, kGraphU8Cast, 0, F>},           \
+	{D, kGraphRangedQ8, F, false, graph_search_kernel<D, kGraphRangedQ8, 0, F>}
 #define GRAPH_V(D) GRAPH_VF(D, false), GRAPH_VF(D, true)
+// binary16 rows: the run-time-dim instances serve every dim and mode; d = 128 has compiled instances as well
+#define GRAPH_HF(D, MODE, F) {D, MODE, F, true, graph_search_kernel<D, MODE, 0, F, _Float16>}
+#define GRAPH_H(D, MODE) GRAPH_HF(D, MODE, false), GRAPH_HF(D, MODE, true)
 const GraphVariant kGraph[] = {GRAPH_V(64),  GRAPH_V(128), GRAPH_V(256), GRAPH_V(512),
-                               GRAPH_V(768), GRAPH_V(832), GRAPH_V(960), GRAPH_V(0)};
+                               GRAPH_V(768), GRAPH_V(832), GRAPH_V(960), GRAPH_V(0),
+                               GRAPH_H(128, kGraphF32), GRAPH_H(128, kGraphU8Cast), GRAPH_H(128, kGraphRangedQ8),
+                               GRAPH_H(0, kGraphF32), GRAPH_H(0, kGraphU8Cast), GRAPH_H(0, kGraphRangedQ8)};
+#undef GRAPH_H
+#undef GRAPH_HF
 #undef GRAPH_V
 #undef GRAPH_VF
 // quantizer_simple<uint8_t> of n_values floats: launches of at most 2^30 values (a dispatch's grid is
 // counted in 32-bit work-items: 1.05 M rows x 4096 in one launch would wrap)
-void launch_quantize_simple_u8(const float* in, size_t n_values, uint8_t* out, hipStream_t st) {
+// (TS: float, or _Float16 for the rows of an expann_graph_create_f16 handle)
+template <typename TS>
+void launch_quantize_simple_u8(const TS* in, size_t n_values, uint8_t* out, hipStream_t st) {
 	const size_t chunk = size_t(1) << 30;
 	for (size_t off = 0; off < n_values; off += chunk) {
 		const size_t nv = std::min(chunk, n_values - off);
-		hipLaunchKernelGGL(quantize_simple_u8_kernel, dim3((uint32_t)((nv + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+		hipLaunchKernelGGL(quantize_simple_u8_kernel<TS>, dim3((uint32_t)((nv + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
 		                   in + off, nv, out + off);
 	}
 }
 // the compiled instance of `dim`, else the run-time-dim one (d = 0)
-const GraphVariant* graph_variant(int dim, int mode, bool filtered) {
+const GraphVariant* graph_variant(int dim, int mode, bool filtered, bool f16) {
 	const GraphVariant* any = nullptr;
 	for (const auto& v : kGraph)
-		if (v.mode == mode && v.filtered == filtered) {
+		if (v.mode == mode && v.filtered == filtered && v.f16 == f16) {
 			if (v.d == dim)
 				return &v;
 			if (v.d == 0)
@@ -138,14 +151,17 @@ int graph_dim_error(const char* fn, int dim) {
 	return EXPANN_OK;
 }
 // the instrumented instance (EXPANN_GRAPH_STAMPS=1, d = 128): per-phase shader clocks of a hop
-const GraphVariant kGraphDbg[] = {{128, kGraphF32, false, graph_search_kernel<128, kGraphF32, 1>},
-                                  {128, kGraphU8Cast, false, graph_search_kernel<128, kGraphU8Cast, 1>},
-                                  {128, kGraphRangedQ8, false, graph_search_kernel<128, kGraphRangedQ8, 1>}};
+const GraphVariant kGraphDbg[] = {{128, kGraphF32, false, false, graph_search_kernel<128, kGraphF32, 1>},
+                                  {128, kGraphU8Cast, false, false, graph_search_kernel<128, kGraphU8Cast, 1>},
+                                  {128, kGraphRangedQ8, false, false, graph_search_kernel<128, kGraphRangedQ8, 1>}};
+// the same over binary16 rows (fp32 walk only)
+const GraphVariant kGraphDbgF16 = {128, kGraphF32, false, true, graph_search_kernel<128, kGraphF32, 1, false, _Float16>};
 const char* const kGraphModeName[] = {"f32", "u8", "q8"};
 
 // min / max of n_values floats, then their quantizer_ranged_q8 bytes and scale_factor / offset (quantize.hpp);
 // d_minmax[2] is scratch.  Launches of at most 2^30 values, as launch_quantize_simple_u8.
-hipError_t launch_quantize_ranged_q8(const float* in, size_t n_values, uint32_t* d_minmax, int8_t* out,
+template <typename TS>
+hipError_t launch_quantize_ranged_q8(const TS* in, size_t n_values, uint32_t* d_minmax, int8_t* out,
                                      float* d_scale_offset, hipStream_t st) {
 	// min starts at FLT_MAX, max at FLT_MIN (smallest positive normal): src/quantizer.h:217-218
 	const uint32_t init[2] = {float_to_ordered(3.402823466e+38f), float_to_ordered(1.175494351e-38f)};
@@ -154,11 +170,11 @@ hipError_t launch_quantize_ranged_q8(const float* in, size_t n_values, uint32_t*
 	if (e != hipSuccess)
 		return e;
 	const uint32_t blocks = (uint32_t)std::min<size_t>((n_values + kBlock - 1) / kBlock, 4096);
-	hipLaunchKernelGGL(minmax_f32_kernel, dim3(blocks), dim3(kBlock), 0, st, in, n_values, d_minmax);
+	hipLaunchKernelGGL(minmax_f32_kernel<TS>, dim3(blocks), dim3(kBlock), 0, st, in, n_values, d_minmax);
 	const size_t chunk = size_t(1) << 30;
 	for (size_t off = 0; off < n_values; off += chunk) {
 		const size_t nv = std::min(chunk, n_values - off);
-		hipLaunchKernelGGL(quantize_ranged_q8_kernel, dim3((uint32_t)((nv + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+		hipLaunchKernelGGL(quantize_ranged_q8_kernel<TS>, dim3((uint32_t)((nv + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
 		                   in + off, nv, (const uint32_t*)d_minmax, out + off, d_scale_offset);
 	}
 	e = hipGetLastError();
@@ -180,8 +196,10 @@ int graph_ensure_ranged(expann_graph* g) {
 	HIP_TRY(g, b_mm.alloc(2 * sizeof(uint32_t)));
 	HIP_TRY(g, b_so.alloc(2 * sizeof(float)));
 	HIP_TRY(g, b_rows.alloc(nv));
-	HIP_TRY(g, launch_quantize_ranged_q8(g->d_vectors, nv, b_mm.as<uint32_t>(), b_rows.as<int8_t>(), b_so.as<float>(),
-	                                     g->stream));
+	HIP_TRY(g, g->rows_f16 ? launch_quantize_ranged_q8((const _Float16*)g->d_vectors, nv, b_mm.as<uint32_t>(),
+	                                                   b_rows.as<int8_t>(), b_so.as<float>(), g->stream)
+	                       : launch_quantize_ranged_q8((const float*)g->d_vectors, nv, b_mm.as<uint32_t>(),
+	                                                   b_rows.as<int8_t>(), b_so.as<float>(), g->stream));
 	float so[2] = {0, 0};
 	HIP_TRY(g, hipMemcpy(so, b_so.p, sizeof(so), hipMemcpyDeviceToHost));
 	if (!std::isfinite(so[0]) || !(so[0] > 0.0f) || !std::isfinite(so[1])) {
@@ -245,7 +263,7 @@ uint32_t graph_first_cand_cap(size_t ef_search) {
 // queries, the outputs, cand_cap and the counters
 GraphSearchParams graph_base_params(const expann_graph* g, int mode, size_t k, size_t ef_search) {
 	GraphSearchParams p{};
-	p.vectors = g->d_vectors;
+	p.vectors = (const float*)g->d_vectors;  // (rows_f16: halves, read by the _Float16 instances only)
 	p.compressed = mode == EXPANN_GRAPH_RANGED_Q8 ? g->d_ranged : g->d_compressed;
 	p.q_scale = g->ranged_scale;
 	p.q_offset = g->ranged_offset;
@@ -346,7 +364,10 @@ int graph_ensure_bytes(expann_graph* g, int mode) {
 		return graph_ensure_ranged(g);
 	if (mode == EXPANN_GRAPH_U8_CAST && !g->d_compressed) {  // quantizer_simple<uint8_t>::build, :485-486
 		HIP_TRY(g, hipMalloc(&g->d_compressed, g->n * (size_t)g->dim));
-		launch_quantize_simple_u8(g->d_vectors, g->n * (size_t)g->dim, g->d_compressed, g->stream);
+		if (g->rows_f16)
+			launch_quantize_simple_u8((const _Float16*)g->d_vectors, g->n * (size_t)g->dim, g->d_compressed, g->stream);
+		else
+			launch_quantize_simple_u8((const float*)g->d_vectors, g->n * (size_t)g->dim, g->d_compressed, g->stream);
 		HIP_TRY(g, hipGetLastError());
 		HIP_TRY(g, hipStreamSynchronize(g->stream));
 	}
@@ -451,7 +472,7 @@ GraphServe graph_serve(const expann_graph* g, size_t k) {
 int graph_enqueue_flat(expann_graph* g, const GraphSearchParams& w, uint32_t* ctr, hipStream_t st, hipEvent_t before,
                        hipEvent_t after) {
 	GraphFlatParams f{};
-	f.vectors = g->d_vectors;
+	f.vectors = (const float*)g->d_vectors;
 	f.dim = (uint32_t)g->dim;
 	f.list = g->d_allow_list;
 	f.n_list = g->n_allowed;
@@ -466,11 +487,12 @@ int graph_enqueue_flat(expann_graph* g, const GraphSearchParams& w, uint32_t* ct
 	f.distcomps_total = w.distcomps_total;
 	const size_t lds = graph_flat_lds_bytes(f.kk, f.dim);
 	uint32_t resident = 0;
-	if (int rc = graph_plan(g, (const void*)graph_flat_scan_kernel, lds, &resident))
+	void (*const scan)(GraphFlatParams) = g->rows_f16 ? graph_flat_scan_kernel<_Float16> : graph_flat_scan_kernel<float>;
+	if (int rc = graph_plan(g, (const void*)scan, lds, &resident))
 		return rc;
 	HIP_TRY(g, hipMemsetAsync(ctr, 0, sizeof(uint32_t) * kGraphCtrWords, st));
 	HIP_TRY(g, hipEventRecord(before, st));
-	hipLaunchKernelGGL(graph_flat_scan_kernel, dim3((uint32_t)std::min<size_t>(w.m, resident)), dim3(64), lds, st, f);
+	hipLaunchKernelGGL(scan, dim3((uint32_t)std::min<size_t>(w.m, resident)), dim3(64), lds, st, f);
 	HIP_TRY(g, hipEventRecord(after, st));
 	HIP_TRY(g, hipGetLastError());
 	++g->stat_flat;
@@ -560,32 +582,33 @@ int graph_print_stamps(expann_graph* g, int mode, size_t ef_search, float ms, ui
 }
 }  // namespace
 
-extern "C" {
-
-int expann_graph_create(int dim, int device, const float* vectors, size_t n, uint32_t n_layers,
-                        uint32_t starting_vertex, const uint64_t* layer_offsets,
+// expann_graph_create (elem_bytes = 4, `fn` its name) and expann_graph_create_f16 (2): one body, so both make the
+// same checks in the same order, all before the device is touched
+static int graph_create(const char* fn_name, size_t elem_bytes, int dim, int device, const void* vectors, size_t n,
+                        uint32_t n_layers, uint32_t starting_vertex, const uint64_t* layer_offsets,
                         const uint32_t* neighbours, expann_graph** out) {
+	const std::string fn(fn_name);
 	if (!out) {
 		g_create_error = "out == NULL";
 		return EXPANN_ERR_INVALID_ARG;
 	}
 	*out = nullptr;
-	if (int rc = graph_dim_error("expann_graph_create", dim))
+	if (int rc = graph_dim_error(fn_name, dim))
 		return rc;
 	if (!vectors || !layer_offsets || n == 0 || n_layers == 0 || starting_vertex >= n ||
 	    n >= (1ull << 32) - 64 || (!neighbours && layer_offsets[(size_t)n_layers * (n + 1) - 1])) {
-		g_create_error = "expann_graph_create: bad arguments";
+		g_create_error = fn + ": bad arguments";
 		return EXPANN_ERR_INVALID_ARG;
 	}
 	// CSR offsets: start at 0, never decrease (a corrupt index file must not turn into
 	// out-of-bounds reads on the device)
 	if (layer_offsets[0] != 0) {
-		g_create_error = "expann_graph_create: layer_offsets[0] != 0";
+		g_create_error = fn + ": layer_offsets[0] != 0";
 		return EXPANN_ERR_INVALID_ARG;
 	}
 	for (size_t i = 1; i < (size_t)n_layers * (n + 1); ++i)
 		if (layer_offsets[i] < layer_offsets[i - 1]) {
-			g_create_error = "expann_graph_create: layer_offsets decrease";
+			g_create_error = fn + ": layer_offsets decrease";
 			return EXPANN_ERR_INVALID_ARG;
 		}
 	const uint64_t n_edges = layer_offsets[(size_t)n_layers * (n + 1) - 1];
@@ -608,6 +631,7 @@ int expann_graph_create(int dim, int device, const float* vectors, size_t n, uin
 	g->n = n;
 	g->n_layers = n_layers;
 	g->starting_vertex = starting_vertex;
+	g->rows_f16 = elem_bytes == 2;
 	std::vector<uint32_t> off32((size_t)n_layers * (n + 1));
 	for (size_t i = 0; i < off32.size(); ++i)
 		off32[i] = (uint32_t)layer_offsets[i];
@@ -622,7 +646,7 @@ int expann_graph_create(int dim, int device, const float* vectors, size_t n, uin
 			return EXPANN_ERR_INVALID_ARG;
 		}
 	auto bail = [&](const char* what) {
-		g_create_error = std::string("expann_graph_create: ") + what;
+		g_create_error = fn + ": " + what;
 		expann_graph_destroy(g);
 		return EXPANN_ERR_HIP;
 	};
@@ -630,7 +654,7 @@ int expann_graph_create(int dim, int device, const float* vectors, size_t n, uin
 		return bail("hipSetDevice/hipStreamCreate");
 	if (hipEventCreate(&g->ev0) != hipSuccess || hipEventCreate(&g->ev1) != hipSuccess)
 		return bail("hipEventCreate");
-	const size_t vbytes = n * (size_t)dim * sizeof(float);
+	const size_t vbytes = n * (size_t)dim * elem_bytes;
 	if (hipMalloc(&g->d_vectors, vbytes) != hipSuccess ||
 	    hipMalloc(&g->d_layer_off, off32.size() * sizeof(uint32_t)) != hipSuccess ||
 	    hipMalloc(&g->d_neighbours, std::max<uint64_t>(n_edges, 1) * sizeof(uint32_t)) != hipSuccess)
@@ -674,6 +698,22 @@ int expann_graph_create(int dim, int device, const float* vectors, size_t n, uin
 		return bail("hipMemset");
 	*out = g;
 	return EXPANN_OK;
+}
+
+extern "C" {
+
+int expann_graph_create(int dim, int device, const float* vectors, size_t n, uint32_t n_layers,
+                        uint32_t starting_vertex, const uint64_t* layer_offsets,
+                        const uint32_t* neighbours, expann_graph** out) {
+	return graph_create("expann_graph_create", sizeof(float), dim, device, vectors, n, n_layers, starting_vertex,
+	                    layer_offsets, neighbours, out);
+}
+
+int expann_graph_create_f16(int dim, int device, const void* rows_f16, size_t n, uint32_t n_layers,
+                            uint32_t starting_vertex, const uint64_t* layer_offsets,
+                            const uint32_t* neighbours, expann_graph** out) {
+	return graph_create("expann_graph_create_f16", 2, dim, device, rows_f16, n, n_layers, starting_vertex, layer_offsets,
+	                    neighbours, out);
 }
 
 void expann_graph_destroy(expann_graph* g) {
@@ -746,12 +786,13 @@ int expann_graph_search_mode(expann_graph* g, const float* queries, size_t m, si
 		g->last_ms = 0;
 		return EXPANN_OK;
 	}
-	const GraphVariant* gv = graph_variant(g->dim, mode, g->filter_on);
+	const GraphVariant* gv = graph_variant(g->dim, mode, g->filter_on, g->rows_f16);
 	if (!gv)
 		return g->fail(EXPANN_ERR_UNSUPPORTED, "no graph kernel for this dim");
-	const bool stamps = std::getenv("EXPANN_GRAPH_STAMPS") != nullptr && g->dim == 128 && !g->filter_on;
+	const bool stamps = std::getenv("EXPANN_GRAPH_STAMPS") != nullptr && g->dim == 128 && !g->filter_on &&
+	                    (!g->rows_f16 || mode == EXPANN_GRAPH_FP32);
 	if (stamps)
-		gv = &kGraphDbg[mode];
+		gv = g->rows_f16 ? &kGraphDbgF16 : &kGraphDbg[mode];
 	if (int rc = graph_dev_init(g))
 		return rc;
 	if (serve == kServeWalk)
@@ -837,7 +878,7 @@ int expann_graph_search_device(expann_graph* g, const float* d_queries, size_t m
 		return EXPANN_OK;
 	HIP_TRY(g, hipSetDevice(g->device));
 	const GraphServe serve = graph_serve(g, k);
-	const GraphVariant* gv = graph_variant(g->dim, mode, g->filter_on);
+	const GraphVariant* gv = graph_variant(g->dim, mode, g->filter_on, g->rows_f16);
 	if (!gv)
 		return g->fail(EXPANN_ERR_UNSUPPORTED, "no graph kernel for this dim");
 	hipStream_t st = stream ? (hipStream_t)stream : g->stream;
@@ -978,6 +1019,8 @@ int expann_graph_get_stat(expann_graph* g, const char* name, uint64_t* out) {
 		*out = g->filter_on ? g->n_allowed : g->n;
 	else if (o == "flat_searches")
 		*out = g->stat_flat;
+	else if (o == "vector_bytes")  // the device bytes of the rows themselves
+		*out = (uint64_t)g->n * (uint64_t)g->dim * (g->rows_f16 ? 2u : 4u);
 	else
 		return g->fail(EXPANN_ERR_INVALID_ARG, "unknown stat: " + o);
 	return EXPANN_OK;
@@ -1346,7 +1389,7 @@ int expann_antitopo_store(expann_antitopo* e, const float* rows, size_t n) {
 	if (!e || (!rows && n))
 		return EXPANN_ERR_INVALID_ARG;
 	e->eng->clear_row_filter();
-	ANTITOPO_TRY(e, for (size_t i = 0; i < n; ++i) e->eng->index.insert(rows + i * (size_t)e->dim));
+	ANTITOPO_TRY(e, e->eng->store_rows(rows, n));
 	return EXPANN_OK;
 }
 
@@ -1355,6 +1398,15 @@ int expann_antitopo_store_batched(expann_antitopo* e, const float* rows, size_t 
 		return EXPANN_ERR_INVALID_ARG;
 	e->eng->clear_row_filter();
 	ANTITOPO_TRY(e, e->eng->store_rows_batched(rows, n, n_serial ? n_serial : 2048));
+	return EXPANN_OK;
+}
+
+int expann_antitopo_set_rows_f16(expann_antitopo* e, int on) {
+	if (!e)
+		return EXPANN_ERR_INVALID_ARG;
+	if (e->eng->index.size() != 0)
+		return e->fail(EXPANN_ERR_INVALID_ARG, "expann_antitopo_set_rows_f16: the engine already holds rows");
+	e->eng->conf.rows_f16 = on != 0;
 	return EXPANN_OK;
 }
 

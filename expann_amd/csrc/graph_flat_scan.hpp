@@ -20,7 +20,7 @@
 namespace expann {
 
 struct GraphFlatParams {
-	const float* vectors;       // [n][dim]
+	const float* vectors;       // [n][dim]; TR = _Float16: the same address holds [n][dim] binary16 rows
 	uint32_t dim;               // a multiple of 16
 	const uint32_t* list;       // [n_list] the allowed vertices, ascending
 	uint32_t n_list;            // >= 1
@@ -47,7 +47,8 @@ __device__ inline uint64_t wave_max_key64(uint64_t v) {
 	return v;
 }
 
-static __global__ __launch_bounds__(64) void graph_flat_scan_kernel(GraphFlatParams p) {
+// TR: the rows' element type, as in graph_search_kernel
+template <typename TR = float> __global__ __launch_bounds__(64) void graph_flat_scan_kernel(GraphFlatParams p) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char flat_smem[];
 	uint64_t* keys = reinterpret_cast<uint64_t*>(flat_smem);  // [kk]
 	float* qs = reinterpret_cast<float*>(keys + p.kk);        // [dim]
@@ -90,7 +91,7 @@ static __global__ __launch_bounds__(64) void graph_flat_scan_kernel(GraphFlatPar
 				const uint32_t i = i0 + 4 * u + rg;
 				rows[u] = p.list[i < p.n_list ? i : p.n_list - 1];
 			}
-			dist_f32_rows_any<U>(p.vectors, p.dim, qs, rows, d, l);
+			dist_f32_rows_any<U, TR>(reinterpret_cast<const TR*>(p.vectors), p.dim, qs, rows, d, l);
 #pragma unroll
 			for (int u = 0; u < U; ++u) {
 				const uint32_t i = i0 + 4 * u + rg;

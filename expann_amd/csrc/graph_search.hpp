@@ -42,7 +42,7 @@ namespace expann {
 constexpr int kGraphF32 = 0, kGraphU8Cast = 1, kGraphRangedQ8 = 2;
 
 struct GraphSearchParams {
-	const float* vectors;         // [n][D]
+	const float* vectors;         // [n][D]; TR = _Float16 instances: the same address holds [n][D] binary16 rows
 	const uint8_t* compressed;    // [n][D] (quantizer_simple<uint8_t>, or quantizer_ranged_q8 in the ranged mode) or nullptr
 	const uint32_t* layer_off;    // [n_layers][n+1] (CSR; the walk uses it for the layers above 0)
 	const uint32_t* neighbours;
@@ -385,12 +385,21 @@ constexpr int kGraphAnyRows = 4;
 constexpr int kGraphAnyChunk = 16;   // fp32: dims per lane and chunk (256 per row)
 constexpr int kGraphAnyChunkU8 = 8;  // uint8: dwords per lane and chunk (512 B per row)
 
-// fp32 squared L2 of the query qs[dim] (LDS) against U rows per 16-lane group
-template <int U>
-__device__ inline void dist_f32_rows_any(const float* vectors, uint32_t dim, const float* qs, const uint32_t* rows,
+// _Float16 rows: every load of a batch is issued before the first value is consumed.  Left to itself the scheduler
+// sinks each 2-byte load next to the v_fma_mix that uses it (fewer registers) and the batch becomes one dependent
+// memory round trip per dim.  Nothing for float rows: their instances stay as they are.
+template <typename TR> __device__ __attribute__((always_inline)) inline void rows_requested() {
+	if constexpr (!std::is_same<TR, float>::value)
+		__builtin_amdgcn_sched_barrier(0);
+}
+
+// fp32 squared L2 of the query qs[dim] (LDS) against U rows per 16-lane group; TR: the rows' element type (float, or
+// _Float16: lane l reads its dims as 2-byte loads, the per-dim step is ref_diff<_Float16>, common.hpp)
+template <int U, typename TR = float>
+__device__ inline void dist_f32_rows_any(const TR* vectors, uint32_t dim, const float* qs, const uint32_t* rows,
                                          float* d, int l) {
 	const uint32_t dpl = dim / 16;
-	const float* src[U];
+	const TR* src[U];
 	float acc[U];
 #pragma unroll
 	for (int u = 0; u < U; ++u) {
@@ -399,37 +408,39 @@ __device__ inline void dist_f32_rows_any(const float* vectors, uint32_t dim, con
 	}
 	uint32_t t0 = 0;
 	for (; t0 + kGraphAnyChunk <= dpl; t0 += kGraphAnyChunk) {
-		float r[U][kGraphAnyChunk];
+		TR r[U][kGraphAnyChunk];
 #pragma unroll
 		for (int u = 0; u < U; ++u)
 #pragma unroll
 			for (int t = 0; t < kGraphAnyChunk; ++t)
 				r[u][t] = src[u][16 * (t0 + t)];
+		rows_requested<TR>();
 #pragma unroll
 		for (int t = 0; t < kGraphAnyChunk; ++t) {
 			const float qv = qs[l + 16 * (t0 + t)];
 #pragma unroll
 			for (int u = 0; u < U; ++u) {
-				const float diff = qv - r[u][t];
+				const float diff = ref_diff<TR>(qv, r[u][t]);
 				acc[u] = __builtin_fmaf(diff, diff, acc[u]);
 			}
 		}
 	}
 	if (t0 < dpl) {  // the last, partial chunk (wave-uniform tests: nothing is read past the row)
-		float r[U][kGraphAnyChunk];
+		TR r[U][kGraphAnyChunk];
 #pragma unroll
 		for (int t = 0; t < kGraphAnyChunk; ++t)
 			if (t0 + t < dpl)
 #pragma unroll
 				for (int u = 0; u < U; ++u)
 					r[u][t] = src[u][16 * (t0 + t)];
+		rows_requested<TR>();
 #pragma unroll
 		for (int t = 0; t < kGraphAnyChunk; ++t) {
 			if (t0 + t < dpl) {
 				const float qv = qs[l + 16 * (t0 + t)];
 #pragma unroll
 				for (int u = 0; u < U; ++u) {
-					const float diff = qv - r[u][t];
+					const float diff = ref_diff<TR>(qv, r[u][t]);
 					acc[u] = __builtin_fmaf(diff, diff, acc[u]);
 				}
 			}
@@ -530,6 +541,7 @@ __device__ inline int stage_query_any(const float* src, uint32_t dim, float* qs,
 
 // rows in flight per 16-lane group while a hop's neighbours are scored
 template <int D> constexpr int graph_rows_f32() { return D == 0 ? kGraphAnyRows : (D <= 128 ? 8 : (D <= 256 ? 4 : 2)); }
+// (binary16 rows keep the float instances' rows in flight)
 template <int D> constexpr int graph_rows_u8() { return D == 0 ? kGraphAnyRows : (D <= 128 ? 16 : (D <= 256 ? 8 : 4)); }
 
 // (the uint8 walk waits on latency, not bandwidth: 128 registers = 16 waves per CU instead of 12)
@@ -561,7 +573,10 @@ template <int MODE> constexpr int graph_any_dim_waves() { return MODE != kGraphF
 // requests are in flight together: no round trip is added to a hop) and leaves the flag in the SIGN BIT of the
 // neighbour's ndist slot -- distances are >= 0 --, the lane that stores the score keeps that bit, and every reader
 // strips it before it compares or stores.  No LDS, scratch or serial read is added.
-template <int D, int MODE, int DBG = 0, bool FILTERED = false>
+// TR: the element type of p.vectors -- float, or _Float16 for a handle made by expann_graph_create_f16.  It covers
+// every read of the rows (entry evaluation, descent, fp32 bottom layer, final re-score of the byte modes); the
+// arithmetic is the float instance's over (float)row, bit for bit (ref_diff, common.hpp).
+template <int D, int MODE, int DBG = 0, bool FILTERED = false, typename TR = float>
 __global__ __launch_bounds__(64, D == 0 ? graph_any_dim_waves<MODE>() : ((MODE != kGraphF32 && D <= 128) ? 4 : 1)) void graph_search_kernel(GraphSearchParams p) {
 	constexpr bool COMPRESSED = MODE != kGraphF32, RANGED = MODE == kGraphRangedQ8;
 	constexpr int DPL = D ? D / 16 : 1;
@@ -584,6 +599,7 @@ __global__ __launch_bounds__(64, D == 0 ? graph_any_dim_waves<MODE>() : ((MODE !
 
 	const int lane = threadIdx.x;
 	const int l = lane & 15, rg = lane >> 4;
+	const TR* vectors = reinterpret_cast<const TR*>(p.vectors);
 	const bool bits = p.vis_words != 0;
 	uint8_t* visited = bits ? nullptr : p.visited + (size_t)blockIdx.x * p.n;
 	uint32_t* vbits = bits ? p.vis_bits + (size_t)blockIdx.x * p.vis_words : nullptr;
@@ -656,23 +672,24 @@ __global__ __launch_bounds__(64, D == 0 ? graph_any_dim_waves<MODE>() : ((MODE !
 		auto dist_f32_rows = [&](auto u_tag, const uint32_t* rows, float* d) {
 			constexpr int U = decltype(u_tag)::value;
 			if constexpr (D == 0) {
-				dist_f32_rows_any<U>(p.vectors, p.dim, qs, rows, d, l);
+				dist_f32_rows_any<U, TR>(vectors, p.dim, qs, rows, d, l);
 				return;
 			}
-			float r[U][DPL];
+			TR r[U][DPL];
 #pragma unroll
 			for (int u = 0; u < U; ++u) {
-				const float* src = p.vectors + (size_t)rows[u] * D + l;
+				const TR* src = vectors + (size_t)rows[u] * D + l;
 #pragma unroll
 				for (int t = 0; t < DPL; ++t)
 					r[u][t] = src[16 * t];
 			}
+			rows_requested<TR>();
 #pragma unroll
 			for (int u = 0; u < U; ++u) {
 				float acc = 0.0f;
 #pragma unroll
 				for (int t = 0; t < DPL; ++t) {
-					const float diff = q[t] - r[u][t];
+					const float diff = ref_diff<TR>(q[t], r[u][t]);
 					acc = __builtin_fmaf(diff, diff, acc);
 				}
 				d[u] = reduce16_ref_order(acc);

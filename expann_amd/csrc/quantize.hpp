@@ -9,21 +9,24 @@
 
 namespace expann {
 
-static __global__ __launch_bounds__(kBlock) void quantize_simple_u8_kernel(const float* in, size_t n_values,
-                                                                    uint8_t* out) {
+// TS (here and below): the source element type -- float, or _Float16 for the binary16 rows of a graph handle made by
+// expann_graph_create_f16.  A half is converted to fp32 as it is loaded (exact), everything after that is the float
+// instance's arithmetic: bytes, scale_factor and offset are those of the upcast rows, bit for bit.
+template <typename TS = float>
+__global__ __launch_bounds__(kBlock) void quantize_simple_u8_kernel(const TS* in, size_t n_values, uint8_t* out) {
 	const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
 	if (i < n_values)
-		out[i] = (uint8_t)(uint32_t)in[i];  // defined for 0 <= x < 256 (UB in C++ beyond that)
+		out[i] = (uint8_t)(uint32_t)(float)in[i];  // defined for 0 <= x < 256 (UB in C++ beyond that)
 }
 
 // minmax[0] = ordered(min), minmax[1] = ordered(max); initialised by the host to
 // ordered(FLT_MAX) / ordered(FLT_MIN) as the reference initialises min_val / max_val
-static __global__ __launch_bounds__(kBlock) void minmax_f32_kernel(const float* in, size_t n_values,
-                                                            uint32_t* minmax) {
+template <typename TS = float>
+__global__ __launch_bounds__(kBlock) void minmax_f32_kernel(const TS* in, size_t n_values, uint32_t* minmax) {
 	float lo = 3.402823466e+38f, hi = -3.402823466e+38f;
 	for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n_values;
 	     i += (size_t)gridDim.x * kBlock) {
-		const float v = in[i];
+		const float v = (float)in[i];
 		lo = v < lo ? v : lo;
 		hi = v > hi ? v : hi;
 	}
@@ -49,9 +52,9 @@ __device__ inline int ranged_q8_convert(float x, float scale, float offset) {
 	return (int)c;
 }
 
-static __global__ __launch_bounds__(kBlock) void quantize_ranged_q8_kernel(const float* in, size_t n_values,
-                                                                    const uint32_t* minmax,
-                                                                    int8_t* out, float* scale_offset) {
+template <typename TS = float>
+__global__ __launch_bounds__(kBlock) void quantize_ranged_q8_kernel(const TS* in, size_t n_values, const uint32_t* minmax,
+                                                             int8_t* out, float* scale_offset) {
 	const float min_val = ordered_to_float(minmax[0]);
 	const float max_val = ordered_to_float(minmax[1]);
 	const float scale = 128.0f / (max_val - min_val);  // q_range() = 127 - 0 + 1
@@ -63,7 +66,7 @@ static __global__ __launch_bounds__(kBlock) void quantize_ranged_q8_kernel(const
 	}
 	if (i >= n_values)
 		return;
-	out[i] = (int8_t)ranged_q8_convert(in[i], scale, offset);
+	out[i] = (int8_t)ranged_q8_convert((float)in[i], scale, offset);
 }
 
 }  // namespace expann

@@ -16,6 +16,10 @@ engine): the bottom layer walks an int8 copy of the rows made by one global affi
 reference's quantizer_ranged_q8, src/quantizer.h:152-238, which it never runs), so rows that are not
 integers in [0, 255] -- Gaussian, embeddings, take_norms=True -- get a compressed walk too.  True / False
 keep the reference's meaning (the uint8 cast / fp32).
+
+`rows="f16"` keeps the rows as IEEE binary16 on the device (expann_antitopo_set_rows_f16): every stored float is
+rounded to the nearest-even binary16 as it comes in, the builders and the index file see the rounded values, and the
+walk gathers half the bytes.  Rows with a NaN or a value beyond binary16's range are refused.
 """
 import ctypes as C
 
@@ -39,7 +43,10 @@ def _compression_mode(value):
 
 class AntitopoEngine:
     def __init__(self, M, ef_construction, ortho_count, prune_overflow, use_compression, dim=None,
-                 device=0):
+                 device=0, rows="f32"):
+        if rows not in ("f32", "f16"):
+            raise ValueError(f'rows must be "f32" or "f16", not {rows!r}')
+        self._rows_f16 = rows == "f16"
         self._mode = _compression_mode(use_compression)
         if self._mode == _lib.GRAPH_RANGED_Q8 and dim is not None and int(dim) % 64 != 0:
             raise ValueError(f"the ranged walk needs a dimension that is a multiple of 64, not {dim}")
@@ -65,6 +72,8 @@ class AntitopoEngine:
         if rc != _lib.OK:
             raise _lib.ExpannError(rc, self._L.expann_antitopo_last_error(None).decode())
         self._h, self.dim = h, padded
+        if self._rows_f16:
+            self._check(self._L.expann_antitopo_set_rows_f16(h, 1))
         if self._mode != int(uc):
             self._check(self._L.expann_antitopo_set_compression(h, self._mode))
 
@@ -99,6 +108,8 @@ class AntitopoEngine:
               "num_distcomps": str(self._L.expann_antitopo_num_distcomps(self._h) if self._h else 0)}
         if self._mode == _lib.GRAPH_RANGED_Q8:
             pl["compression_mode"] = "ranged"
+        if self._rows_f16:
+            pl["rows"] = "f16"
         return pl
 
     def store_vector(self, v):

@@ -11,6 +11,7 @@
 #pragma once
 
 #include <cstdint>
+#include <cstring>
 #include <optional>
 #include <stdexcept>
 #include <string>
@@ -19,6 +20,7 @@
 #include "ann_engine.h"
 #include "antitopo_index.h"
 #include "expann_hip.h"
+#include "half.h"
 
 struct gpu_antitopo_engine_config : public expann::antitopo_config {
 	int device = 0;
@@ -28,6 +30,11 @@ struct gpu_antitopo_engine_config : public expann::antitopo_config {
 	// 2 = the ranged int8 walk, which the reference has no switch for.
 	int compression_mode = -1;
 	int mode() const { return compression_mode < 0 ? (use_compression ? 1 : 0) : compression_mode; }
+	// Extension: the device keeps the rows as IEEE binary16 (expann_graph_create_f16): half the gathered bytes of a
+	// hop and half the device copy.  Every stored float is rounded to the nearest-even binary16 AS IT COMES IN and
+	// (float) of that is what the host keeps: the builders and the index file see exactly the values the device
+	// holds, so no rounding happens after the edges were chosen.  Set before the first row is stored.
+	bool rows_f16 = false;
 	gpu_antitopo_engine_config() = default;
 	// same argument order as antitopo_engine_config (src/antitopo_engine.h:88-101)
 	gpu_antitopo_engine_config(size_t _M, size_t _M0, size_t _ef_search_mult, size_t _ef_construction,
@@ -65,6 +72,19 @@ struct gpu_antitopo_engine : public ann_engine<T, gpu_antitopo_engine<T>> {
 		index.ef_search = e;
 	}
 
+	// rows_f16: `count` floats rounded to binary16 and back; a NaN, or a value that rounds to +-inf, is refused
+	// before anything is stored
+	static std::vector<float> rounded_to_f16(const float* x, size_t count) {
+		std::vector<float> r(count);
+		for (size_t i = 0; i < count; ++i) {
+			const uint16_t h = expann::f32_to_f16_bits(x[i]);
+			if ((h & 0x7c00u) == 0x7c00u)
+				throw std::invalid_argument("gpu_antitopo_engine: rows_f16 refuses a NaN or a value beyond binary16's range "
+				                            "(component " + std::to_string(i) + ")");
+			r[i] = expann::f16_bits_to_f32(h);
+		}
+		return r;
+	}
 	void _store_vector(const vec<T>& v) {
 		if (conf.read_index)
 			return;  // :312-313
@@ -73,7 +93,23 @@ struct gpu_antitopo_engine : public ann_engine<T, gpu_antitopo_engine<T>> {
 		std::vector<float> row(index.dim);
 		for (size_t i = 0; i < index.dim; ++i)
 			row[i] = float(v.at(i));
+		if (conf.rows_f16)
+			row = rounded_to_f16(row.data(), row.size());
 		index.insert(row.data());
+	}
+	// Extension: `n` rows of index.dim floats through the serial builder (rows_f16: rounded first, all or none)
+	void store_rows(const float* rows, size_t n) {
+		if (conf.read_index || n == 0)
+			return;
+		if (index.dim == 0)
+			throw std::runtime_error("gpu_antitopo_engine: dimension not set");
+		std::vector<float> rounded;
+		if (conf.rows_f16) {
+			rounded = rounded_to_f16(rows, n * index.dim);
+			rows = rounded.data();
+		}
+		for (size_t i = 0; i < n; ++i)
+			index.insert(rows + i * index.dim);
 	}
 	// Extension: `n` rows through the batched GPU builder (expann_graph_build_batched,
 	// csrc/graph_build.hpp).  The first rows of an empty engine -- until n_serial are stored -- go
@@ -85,6 +121,11 @@ struct gpu_antitopo_engine : public ann_engine<T, gpu_antitopo_engine<T>> {
 			return stats;
 		if (index.dim == 0)
 			throw std::runtime_error("gpu_antitopo_engine: dimension not set");
+		std::vector<float> rounded;  // (rows_f16: the batched builder receives the upcast fp32 rows)
+		if (conf.rows_f16) {
+			rounded = rounded_to_f16(rows, n * index.dim);
+			rows = rounded.data();
+		}
 		if (conf.ortho_count != 1) {  // (several ortho entry points: serial path only)
 			for (size_t i = 0; i < n; ++i)
 				index.insert(rows + i * index.dim);
@@ -124,16 +165,36 @@ struct gpu_antitopo_engine : public ann_engine<T, gpu_antitopo_engine<T>> {
 		upload();
 		num_distcomps = 0;
 	}
+	// rows_f16: the host rows as binary16 bit patterns.  Every value must be one already -- rows stored through this
+	// engine are; an index file read from elsewhere may not be, and is refused rather than rounded under its edges.
+	std::vector<uint16_t> pack_rows_f16() const {
+		std::vector<uint16_t> h(index.vectors.size());
+		for (size_t i = 0; i < h.size(); ++i) {
+			const float x = index.vectors[i];
+			h[i] = expann::f32_to_f16_bits(x);
+			const float back = expann::f16_bits_to_f32(h[i]);
+			if ((h[i] & 0x7c00u) == 0x7c00u || std::memcmp(&back, &x, sizeof(x)) != 0)
+				throw std::invalid_argument("gpu_antitopo_engine: rows_f16 needs rows that are exactly binary16 values (row " +
+				                            std::to_string(i / index.dim) + ")");
+		}
+		return h;
+	}
 	void upload() {
+		std::vector<uint16_t> halves;
+		if (conf.rows_f16)
+			halves = pack_rows_f16();  // (throws before the device is touched and before the old graph goes)
 		const auto fg = index.flatten();
 		expann_graph_destroy(graph);
 		graph = nullptr;
 		device_distcomps_seen = 0;
-		int rc = expann_graph_create(int(index.dim), conf.device, index.vectors.data(), index.size(),
-		                             fg.n_layers, fg.starting_vertex, fg.layer_offsets.data(),
-		                             fg.neighbours.data(), &graph);
+		int rc = conf.rows_f16
+		             ? expann_graph_create_f16(int(index.dim), conf.device, halves.data(), index.size(), fg.n_layers,
+		                                       fg.starting_vertex, fg.layer_offsets.data(), fg.neighbours.data(), &graph)
+		             : expann_graph_create(int(index.dim), conf.device, index.vectors.data(), index.size(),
+		                                   fg.n_layers, fg.starting_vertex, fg.layer_offsets.data(),
+		                                   fg.neighbours.data(), &graph);
 		if (rc != EXPANN_OK)
-			throw std::runtime_error(std::string("expann_graph_create: ") +
+			throw std::runtime_error(std::string(conf.rows_f16 ? "expann_graph_create_f16: " : "expann_graph_create: ") +
 			                         expann_graph_last_error(nullptr));
 	}
 	std::vector<size_t> _query_k(const vec<T>& v, size_t k) {
@@ -226,6 +287,8 @@ struct gpu_antitopo_engine : public ann_engine<T, gpu_antitopo_engine<T>> {
 			pl["compression_mode"] = "ranged";
 		pl["use_largest_direction_filtering"] = std::to_string(conf.use_largest_direction_filtering);
 		pl["num_distcomps"] = std::to_string(num_distcomps);
+		if (conf.rows_f16)
+			pl["rows"] = "f16";
 		return pl;
 	}
 };

@@ -37,4 +37,27 @@ inline uint16_t f32_to_f16_bits(float f) {
 	return uint16_t(sign | q);
 }
 
+// binary16 bits -> fp32, exact (subnormals included; inf and NaN map to inf and NaN)
+inline float f16_bits_to_f32(uint16_t h) {
+	const uint32_t sign = uint32_t(h & 0x8000u) << 16, e = (h >> 10) & 0x1fu, m = h & 0x03ffu;
+	uint32_t x;
+	if (e == 0x1fu) {
+		x = sign | 0x7f800000u | (m << 13);
+	} else if (e != 0) {
+		x = sign | ((e + 112u) << 23) | (m << 13);
+	} else if (m == 0) {
+		x = sign;
+	} else {  // subnormal half m * 2^-24: normalise
+		uint32_t mm = m, ee = 113u;
+		while (!(mm & 0x0400u)) {
+			mm <<= 1;
+			--ee;
+		}
+		x = sign | (ee << 23) | ((mm & 0x03ffu) << 13);
+	}
+	float f;
+	std::memcpy(&f, &x, sizeof(f));
+	return f;
+}
+
 }  // namespace expann

@@ -590,6 +590,34 @@ int expann_graph_clear_row_filter(expann_graph* g);
 int expann_antitopo_set_row_filter(expann_antitopo* e, const uint32_t* allow_bits_or_NULL, size_t n_words);
 int expann_antitopo_set_row_filter_device(expann_antitopo* e, const uint32_t* d_allow_bits, size_t n_words, void* stream);
 
+/* Graph engine over IEEE binary16 rows (appended; EXPANN_ABI_VERSION stays 2: nothing that existed changed; a handle
+ * made by expann_graph_create launches exactly the kernel instances it launched before).
+ * THE F16 ROW RULE.  A graph handle whose rows are binary16 returns what the handle made by expann_graph_create from
+ * (float)row returns, from every entry point and in every mode, bit for bit: ids, fp32 distance bits, distcomps,
+ * padding, the redo launch's behaviour and the EXPANN_ERR_OVERFLOW cases -- expann_graph_search, _search_mode (modes
+ * 0, 1, 2), _search_device + _sync, the row filter (walk and scan) and expann_graph_ranged_params.  binary16 -> fp32
+ * is exact, subnormals included: nothing is flushed.  The byte copies of modes 1 and 2 are made from the halves
+ * converted on load, so bytes, scale_factor and offset are the fp32 handle's bits.  Queries stay fp32.
+ * expann_graph_create_f16 is expann_graph_create with rows [n][dim] of 2 bytes each (host memory): the same checks
+ * in the same order, all before the device is touched; the rows stay binary16 on the device (half the bytes a hop
+ * gathers, half the device copy).  expann_graph_get_stat "vector_bytes" = the device bytes of the rows themselves,
+ * n * dim * 2 or n * dim * 4.
+ * expann_antitopo_set_rows_f16(e, on): allowed only while the engine holds no rows, else EXPANN_ERR_INVALID_ARG (a
+ * NULL handle too; no device call is made).  With it on, expann_antitopo_store / _store_batched round every incoming
+ * float to the nearest-even binary16 (expann::f32_to_f16_bits, include/expann/half.h) and keep (float) of that on
+ * the host, so the serial builder, the batched builder and the index file see exactly the values the device will
+ * hold; a call whose rows hold a NaN, or a value that rounds to +-inf, is refused with EXPANN_ERR_INVALID_ARG before
+ * any of its rows is inserted.  _build / _load upload through expann_graph_create_f16.  _save writes the usual
+ * file (fp32 values, the reference's layout).  _load into such an engine fails with EXPANN_ERR_INVALID_ARG, and
+ * uploads nothing, when any stored value is not exactly a binary16 value: no rounding is ever silent after the
+ * edges were chosen.
+ * Not offered: binary16 device rows for expann_graph_build_batched (it receives the upcast fp32 rows), fp16
+ * queries, bf16 rows. */
+int expann_graph_create_f16(int dim, int device, const void* rows_f16, size_t n, uint32_t n_layers,
+                            uint32_t starting_vertex, const uint64_t* layer_offsets, const uint32_t* neighbours,
+                            expann_graph** out);
+int expann_antitopo_set_rows_f16(expann_antitopo* e, int on);
+
 #ifdef __cplusplus
 }
 #endif
