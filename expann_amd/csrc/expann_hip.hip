@@ -51,6 +51,10 @@ static_assert(kMaxK == kMaxCap / 2, "the bound on k: a candidate list holds at l
 constexpr size_t kMaxQueriesPerPass = 32768;
 constexpr int kEventPairs = 64;
 constexpr uint32_t kAsyncRing = 256;  // outstanding searches of the deferred-check mode
+// a ring slot: words 0-6 = the device's flag block (kFlagCopyBytes of it), words 8 / 9 the host's (defer_flags)
+constexpr uint32_t kRingWords = 10, kRingScale = 8, kRingMark = 9;
+// what a search reads back: flags (words 0-3), the candidate total (4-5), the redo lists' keys (6)
+constexpr size_t kFlagCopyBytes = sizeof(uint32_t) * 7;
 constexpr uint32_t kFilterListCap = kMaxCap;  // rows in the row filter's list (the longest candidate list)
 
 struct Level {
@@ -171,7 +175,7 @@ struct expann_index {
 	// deferred check (expann_sync): flag blocks of the outstanding searches, read back into a ring
 	long opt_async = 0;
 	bool host_call = false;          // (expann_search: always the synchronous path)
-	PinPtr<uint32_t> h_flag_ring;    // pinned [kAsyncRing][8]
+	PinPtr<uint32_t> h_flag_ring;    // pinned [kAsyncRing][kRingWords]
 	uint32_t async_pending = 0;
 	hipStream_t async_stream = nullptr;
 	long opt_xcd_tolerance = 3;  // % of modelled cost given up for an XCD-aligned chunk count
@@ -188,7 +192,14 @@ struct expann_index {
 	long opt_persist = 1;            // scan_gemm_f16x: resident workgroups pull (query tile, row chunk) items per XCD
 	long opt_ip_rescale = 1;         // fp16 form, inner product: the filter sees each query times a power of two (f16_query_prep_kernel)
 	long opt_spec_rank = 0;          // speculative thresholds: 0 auto, j >= 1: the j-th class maximum (j >= k: off)
+	long opt_redo_bound = 1;         // debug: 0 = the redo pass's thresholds from the proven tau alone
+	long opt_select_overlap = 1;     // debug: 0 = the select stages of long lists on the caller's stream
+	// the side stream of the select's long-list stages (launch_select_wave), and the events of its fork and join;
+	// made at the first search that has such a stage
+	hipStream_t side_stream = nullptr;
+	hipEvent_t side_ev[2] = {nullptr, nullptr};
 	uint64_t stat_redo_queries = 0;  // queries the redo pass served in the last search (waiting form) / the last synced one
+	uint64_t stat_redo_candidates = 0;  // keys the redo lists of those queries held (the redo select counts them)
 	uint64_t stat_redo_overflows = 0;  // searches whose failing queries (or redo lists) did not fit the redo pass
 	uint64_t stat_spec_rank = 0;     // j of the last search's thresholds (= k: proven thresholds)
 	long opt_i8_filter = 1;          // fp32 L2 d = 128: the int8 filter (scan_gemm_i8f.hpp): 0 off, 1 auto, 2 wherever supported
@@ -536,7 +547,7 @@ int ensure_workspace(expann_index* h, size_t m, uint32_t cap) {
 		HIP_TRY(h, hipMemset(h->d_overflow, 0, sizeof(uint32_t) * 4 + sizeof(unsigned long long) * 2));
 		h->d_total = reinterpret_cast<unsigned long long*>(h->d_overflow + 4);
 		HIP_TRY(h, hipHostMalloc((void**)&h->h_flags, sizeof(uint32_t) * 8, 0));
-		HIP_TRY(h, hipHostMalloc((void**)&h->h_flag_ring, sizeof(uint32_t) * 8 * kAsyncRing, 0));
+		HIP_TRY(h, hipHostMalloc((void**)&h->h_flag_ring, sizeof(uint32_t) * kRingWords * kAsyncRing, 0));
 		HIP_TRY(h, hipMalloc(&h->d_ticket, sizeof(uint32_t)));
 		HIP_TRY(h, hipMemset(h->d_ticket, 0, sizeof(uint32_t)));
 		HIP_TRY(h, hipDeviceSynchronize());  // (once per handle: the counter is zero before any stream uses it)
@@ -896,11 +907,16 @@ uint32_t select_longest_list(double expect, uint32_t spec_j) {
 	return spec_j ? (uint32_t)(expect * (1.0 + 4.5 / std::sqrt((double)spec_j))) : 2u * (uint32_t)expect;
 }
 // (rows_f16: sel.rerank_base holds binary16 rows -- the _Float16 instances of the same kernels)
-void launch_select_wave(SelectParams& sel, size_t m, uint32_t cap, hipStream_t st, uint32_t longest, bool rows_f16 = false) {
+// `side` (or nullptr): the stream of the stages behind the first.  The stages serve disjoint queries, write disjoint
+// output rows and share only atomic counters, so with a side stream -- which the caller has made wait for the
+// gather -- the long lists' stages run beside the short lists' <8,4> launch instead of behind it.
+void launch_select_wave(SelectParams& sel, size_t m, uint32_t cap, hipStream_t st, uint32_t longest, bool rows_f16 = false,
+                        hipStream_t side = nullptr) {
 	using WaveFn = void (*)(SelectParams, uint32_t);
 	const WaveFn w8 = rows_f16 ? select_wave_kernel<8, 4, _Float16> : select_wave_kernel<8, 4>;
 	const WaveFn w16 = rows_f16 ? select_wave_kernel<16, 2, _Float16> : select_wave_kernel<16, 2>;
 	const WaveFn w32 = rows_f16 ? select_wave_kernel<32, 1, _Float16> : select_wave_kernel<32, 1>;
+	const hipStream_t st2 = side ? side : st;
 	sel.wave_done = 0;
 	hipLaunchKernelGGL(w8, dim3((uint32_t)((m + 3) / 4)), dim3(256), 0, st, sel, (uint32_t)m);
 	sel.wave_done = 512;
@@ -908,17 +924,47 @@ void launch_select_wave(SelectParams& sel, size_t m, uint32_t cap, hipStream_t s
 		return;
 	if (cap > 512) {
 		// (k = 100: ~920-entry lists -- half the registers and ballots of the 2048-key form)
-		hipLaunchKernelGGL(w16, dim3((uint32_t)((m + 1) / 2)), dim3(128), 0, st, sel, (uint32_t)m);
+		hipLaunchKernelGGL(w16, dim3((uint32_t)((m + 1) / 2)), dim3(128), 0, st2, sel, (uint32_t)m);
 		sel.wave_done = 1024;
 	}
 	if (cap > 1024 && longest > 1024) {
-		hipLaunchKernelGGL(w32, dim3((uint32_t)m), dim3(64), 0, st, sel, (uint32_t)m);
+		hipLaunchKernelGGL(w32, dim3((uint32_t)m), dim3(64), 0, st2, sel, (uint32_t)m);
 		sel.wave_done = 2048;
 	}
 }
 using SelectTopkFn = void (*)(SelectParams);
 inline SelectTopkFn select_topk_fn(const expann_index* h) {
 	return f16_rows(h) ? select_topk_kernel<_Float16> : select_topk_kernel<float>;
+}
+// The select of a full scan's lists: the statistics sum, the wave stages, the left-over launch.
+// When a second wave stage is launched at all (longest > 512) and "select_overlap" allows it, everything but the
+// <8,4> stage goes to the handle's side stream: forked behind the gather by one event, joined into `st` by another
+// before this returns -- whatever follows on `st` (the redo pass, the flag copy, the next search) sees every
+// stage's output rows and counters.  No host wait.
+int launch_select(expann_index* h, SelectParams& sel, size_t m, uint32_t cap, hipStream_t st, uint32_t longest,
+                  bool sum_counts) {
+	hipStream_t side = nullptr;
+	if (h->opt_select_overlap && longest > 512 && cap > 512) {
+		if (!h->side_stream) {
+			HIP_TRY(h, hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking));
+			for (hipEvent_t& e : h->side_ev)
+				HIP_TRY(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+		}
+		side = h->side_stream;
+		HIP_TRY(h, hipEventRecord(h->side_ev[0], st));
+		HIP_TRY(h, hipStreamWaitEvent(side, h->side_ev[0], 0));
+	}
+	const hipStream_t st2 = side ? side : st;
+	if (sum_counts)  // statistics: candidates of the full scan (i8f_cand_limit)
+		hipLaunchKernelGGL(sum_u32_kernel, dim3(1), dim3(1024), 0, st2, sel.cand_cnt, (uint32_t)m, h->d_total);
+	launch_select_wave(sel, m, cap, st, longest, f16_rows(h), side);
+	hipLaunchKernelGGL(select_topk_fn(h), dim3((uint32_t)m), dim3(kBlock), sizeof(uint64_t) * cap + 16, st2, sel);
+	HIP_TRY(h, hipGetLastError());
+	if (side) {
+		HIP_TRY(h, hipEventRecord(h->side_ev[1], side));
+		HIP_TRY(h, hipStreamWaitEvent(st, h->side_ev[1], 0));
+	}
+	return EXPANN_OK;
 }
 
 // Per-wave hit logs of the scans that write them (scan_gemm_f16x.hpp, scan_gemm_i8w.hpp): one log
@@ -980,13 +1026,13 @@ void launch_gather_logs(expann_index* h, hipStream_t st) {
 bool defer_flags(expann_index* h, hipStream_t st, int attempt) {
 	if (!h->opt_async || h->host_call || attempt != 0 || h->strict_u8 || h->async_pending >= kAsyncRing)
 		return false;
-	if (hipMemcpyAsync(h->h_flag_ring + 8 * h->async_pending, h->d_overflow,
-	                   sizeof(uint32_t) * 4 + sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess)
+	if (hipMemcpyAsync(h->h_flag_ring + kRingWords * h->async_pending, h->d_overflow, kFlagCopyBytes,
+	                   hipMemcpyDeviceToHost, st) != hipSuccess)
 		return false;
-	// ring words 6 / 7 are the host's: 6 = fp16 scale of the search (set by the caller, 0 = none),
-	// 7 = 1 when word 1 (query values outside [0, 255]) belongs to this search (uint8 rows)
-	h->h_flag_ring[8 * h->async_pending + 6] = 0;
-	h->h_flag_ring[8 * h->async_pending + 7] = h->dtype == EXPANN_DTYPE_U8 ? 1u : 0u;
+	// ring words kRingScale / kRingMark are the host's: the fp16 scale of the search (set by the caller, 0 = none),
+	// and 1 when word 1 (query values outside [0, 255]) belongs to this search (uint8 rows)
+	h->h_flag_ring[kRingWords * h->async_pending + kRingScale] = 0;
+	h->h_flag_ring[kRingWords * h->async_pending + kRingMark] = h->dtype == EXPANN_DTYPE_U8 ? 1u : 0u;
 	h->async_pending++;
 	h->async_stream = st;
 	h->prof.deferred_searches++;
@@ -1162,6 +1208,8 @@ const GemmI8qVariant kGemmI8w[] = {
     GEMM_I8W(256, kU8L2, true, "U8L2"), GEMM_I8W(256, kI8L2, true, "I8L2"), GEMM_I8W(256, kI8IP, false, "I8IP")};
 // the int8 filter of fp32 rows (scan_gemm_i8f.hpp): the d = 128 i8w full scan on the index's int8 copy
 const GemmI8qVariant kGemmI8F = GEMM_I8W(128, kI8L2, true, "F32L2");
+// its instance for the redo pass of the speculative thresholds (waves without a live query slot only stage)
+void (*const kGemmI8FRedo)(GemmI8wParams) = scan_gemm_i8w_kernel<128, true, false, true>;
 #undef GEMM_I8W
 // every other 8-bit dim (multiples of 64 up to 4096): the K-loop form with the dim known at run time
 // (scan_gemm_i8kl.hpp; d = 0 here, rows in the index's own d bytes, 128-row tiles, hit logs)
@@ -1499,7 +1547,7 @@ int search_i8q(expann_index* h, const GemmI8qVariant* gq, const void* d_queries,
 		                   st, sel);
 		HIP_TRY(h, hipGetLastError());
 		if (defer_flags(h, st, attempt)) {  // deferred check: expann_sync reads the flags
-			h->h_flag_ring[8 * (h->async_pending - 1) + 6] = 0;
+			h->h_flag_ring[kRingWords * (h->async_pending - 1) + kRingScale] = 0;
 			return EXPANN_OK;
 		}
 		HIP_TRY(h, hipMemcpyAsync(h->h_flags, h->d_overflow, sizeof(uint32_t) * 4 + sizeof(unsigned long long),
@@ -1938,9 +1986,10 @@ int launch_scan_f16(expann_index* h, const GemmF16Variant* gvf, uint32_t rows_se
 // run_level(li)      scan of level li (direct / fp32 / bf16x3 / fp16 / int8 MFMA filter) + selection
 // check(attempt)     the one host wait: flags read back, retry with larger lists / another family
 // the redo pass's workspace for R query slots (expann_index::d_redo), offsets in bytes: the failing queries'
-// numbers, the per-slot list counters, theta', ||q||^2, w_q, thp, the fp16 and int8 copies, the candidate lists
+// numbers, the per-slot list counters, theta', ||q||^2, w_q, thp, the bounds S_k' of the failed lists, the fp16 and
+// int8 copies, the candidate lists
 struct RedoWs {
-	size_t list, cnt, theta, qnrm, wq, thp, q16, q8, cand, total;
+	size_t list, cnt, theta, qnrm, wq, thp, bound, q16, q8, cand, total;
 	RedoWs(uint32_t R, int dim, uint32_t cap) {
 		list = 0;
 		cnt = 4 * (size_t)R;
@@ -1948,7 +1997,8 @@ struct RedoWs {
 		qnrm = 12 * (size_t)R;
 		wq = 16 * (size_t)R;
 		thp = 20 * (size_t)R;
-		q16 = 24 * (size_t)R;  // (R is a multiple of 256: every part starts on a 16-byte boundary)
+		bound = 24 * (size_t)R;
+		q16 = 28 * (size_t)R;  // (R is a multiple of 256: every part starts on a 16-byte boundary)
 		q8 = q16 + 2 * (size_t)R * (size_t)dim;
 		cand = q8 + (size_t)R * (size_t)dim;
 		total = cand + 8 * (size_t)R * (size_t)cap;
@@ -2448,23 +2498,26 @@ int SearchPass::run_level(size_t li) {
 		sel.redo_word = h->d_overflow + 3;
 		sel.redo_list = reinterpret_cast<uint32_t*>(h->d_redo.as<unsigned char>() + ws.list);
 		sel.redo_cap = redo_slots;
+		sel.redo_bound = reinterpret_cast<float*>(h->d_redo.as<unsigned char>() + ws.bound);
 	}
-	if (last && sel.cand_cnt && (h->profiling || use_i8f))  // statistics: candidates of the full scan (i8f_cand_limit)
-		hipLaunchKernelGGL(sum_u32_kernel, dim3(1), dim3(1024), 0, st, sel.cand_cnt, (uint32_t)m,
-		                   h->d_total);
-	if (m <= 64) {
-		sel.wave0_short = 1;  // latency mode: one launch, wave 0 orders the short lists
-	} else if (sel.rerank_base && sel.cand_cnt) {
+	const bool sum_counts = last && sel.cand_cnt && (h->profiling || use_i8f);  // statistics: candidates of the full scan (i8f_cand_limit)
+	if (m > 64 && sel.rerank_base && sel.cand_cnt) {
 		// short lists (the usual case after a GEMM-form scan): one wave per query
 		// (int8 filter: longer lists, ~500 at k = 10 -- DESIGN.md 4.4i)
 		// (speculative thresholds: the expectation is linear in the rank of the class maximum)
 		const uint32_t sj = last ? spec_j : 0u;
 		const double expect = (use_i8f ? kI8fListRatio : 1.0) * 1.2 * (sj ? (double)sj : (double)k) * sample_frac_for(h, k);
-		launch_select_wave(sel, m, cap, st, select_longest_list(expect, sj), f16_rows(h));
+		const int rs = launch_select(h, sel, m, cap, st, select_longest_list(expect, sj), sum_counts);
+		if (rs != EXPANN_OK)
+			return rs;
+	} else {
+		if (sum_counts)
+			hipLaunchKernelGGL(sum_u32_kernel, dim3(1), dim3(1024), 0, st, sel.cand_cnt, (uint32_t)m, h->d_total);
+		if (m <= 64)
+			sel.wave0_short = 1;  // latency mode: one launch, wave 0 orders the short lists
+		hipLaunchKernelGGL(select_topk_fn(h), dim3((uint32_t)m), dim3(kBlock), sizeof(uint64_t) * cap + 16, st, sel);
+		HIP_TRY(h, hipGetLastError());
 	}
-	hipLaunchKernelGGL(select_topk_fn(h), dim3((uint32_t)m), dim3(kBlock),
-	                   sizeof(uint64_t) * cap + 16, st, sel);
-	HIP_TRY(h, hipGetLastError());
 	if (last && spec_j)
 		return run_redo(use_i8f);
 	return EXPANN_OK;
@@ -2489,6 +2542,7 @@ int SearchPass::run_redo(bool use_i8f) {
 	cp.qnrm = h->d_qnrm;
 	cp.r_qnrm = reinterpret_cast<float*>(b + ws.qnrm);
 	cp.tau = h->d_tau[levels.size() & 1];
+	cp.bound = h->opt_redo_bound ? reinterpret_cast<const float*>(b + ws.bound) : nullptr;
 	cp.qscale = (ip && h->opt_ip_rescale) ? h->d_qscale.as<const float>() : nullptr;
 	cp.eps = gemm_f16_filter_eps(h->dim);
 	cp.abs_coef = std::ldexp(1.0f, -24) / h->f16_scale * std::sqrt((float)h->dim);
@@ -2552,7 +2606,7 @@ int SearchPass::run_redo(bool use_i8f) {
 		wp.log_cnt = h->d_log_cnt;
 		wp.log_cap = log_cap;
 		wp.lost = h->d_overflow;
-		hipLaunchKernelGGL(kGemmI8F.scan_w, dim3(chunks * nqt), dim3((uint32_t)kGemmI8F.threads_w), kGemmI8F.lds_w, st, wp);
+		hipLaunchKernelGGL(kGemmI8FRedo, dim3(chunks * nqt), dim3((uint32_t)kGemmI8F.threads_w), kGemmI8F.lds_w, st, wp);
 		gp.i_thp = cp.r_thp;
 		gp.i_bias = h->d_bp_i8f;
 		gp.i_rw = h->d_rw_i8f;
@@ -2590,7 +2644,7 @@ int SearchPass::run_redo(bool use_i8f) {
 	hipLaunchKernelGGL(gather_logs_kernel, dim3(nqt * 4 * gp.n_groups), dim3(kBlock), 0, st, gp);
 
 	// the select of the R slots in one launch: wave 0 of a slot's workgroup orders a list of <= 2048 keys, the
-	// whole workgroup a longer one; no check (these lists come from proven thresholds)
+	// whole workgroup a longer one; no check (these lists come from thresholds that are proven bounds)
 	SelectParams sel{};
 	sel.cand = gp.cand;
 	sel.cand_cnt = gp.cand_cnt;
@@ -2617,6 +2671,7 @@ int SearchPass::run_redo(bool use_i8f) {
 	sel.wave0_short = 1;
 	sel.slot_map = cp.list;
 	sel.live_slots = word;
+	sel.redo_cand = h->d_overflow + 6;
 	hipLaunchKernelGGL(select_topk_fn(h), dim3(R), dim3(kBlock), sizeof(uint64_t) * cap + 16, st, sel);
 	HIP_TRY(h, hipGetLastError());
 	return EXPANN_OK;
@@ -2627,16 +2682,15 @@ int SearchPass::check(int attempt, Next* next) {
 	// overflow check (the only host sync of a search); flags and statistics are contiguous
 	if (defer_flags(h, st, attempt)) {  // deferred check: expann_sync reads the flags
 		float sc = gvf ? h->f16_scale : 0.0f;  // (fp16 form: the range check of max |q| needs the scale)
-		std::memcpy(&h->h_flag_ring[8 * (h->async_pending - 1) + 6], &sc, sizeof(float));
-		if (i8f_ran && h->opt_i8_filter == 1)  // (word 7, high bit: the int8 filter's candidate limit follows)
-			h->h_flag_ring[8 * (h->async_pending - 1) + 7] =
-			    0x80000000u | (uint32_t)std::min<uint64_t>(i8f_cand_limit(h, m, k, spec_j), 0x3FFFFFFFu);
-		if (spec_j)  // (word 7, bit 30: word 3 is this search's redo word)
-			h->h_flag_ring[8 * (h->async_pending - 1) + 7] |= 0x40000000u;
+		uint32_t* const slot = h->h_flag_ring + kRingWords * (h->async_pending - 1);
+		std::memcpy(&slot[kRingScale], &sc, sizeof(float));
+		if (i8f_ran && h->opt_i8_filter == 1)  // (the mark's high bit: the int8 filter's candidate limit follows)
+			slot[kRingMark] = 0x80000000u | (uint32_t)std::min<uint64_t>(i8f_cand_limit(h, m, k, spec_j), 0x3FFFFFFFu);
+		if (spec_j)  // (the mark's bit 30: word 3 is this search's redo word, word 6 its redo lists' keys)
+			slot[kRingMark] |= 0x40000000u;
 		return EXPANN_OK;
 	}
-	HIP_TRY(h, hipMemcpyAsync(h->h_flags, h->d_overflow, sizeof(uint32_t) * 4 + sizeof(unsigned long long),
-	                          hipMemcpyDeviceToHost, st));
+	HIP_TRY(h, hipMemcpyAsync(h->h_flags, h->d_overflow, kFlagCopyBytes, hipMemcpyDeviceToHost, st));
 	HIP_TRY(h, hipStreamSynchronize(st));
 	unsigned long long tot;
 	std::memcpy(&tot, h->h_flags + 4, sizeof(tot));
@@ -2672,6 +2726,7 @@ int SearchPass::check(int attempt, Next* next) {
 	const uint32_t redo_word = spec_j ? h->h_flags[3] : 0u;
 	if (h->h_flags[0] == 0 && redo_word < kRedoOverflowUnit) {
 		h->stat_redo_queries += redo_word;
+		h->stat_redo_candidates += spec_j ? h->h_flags[6] : 0u;
 		return EXPANN_OK;
 	}
 	h->prof.retries++;
@@ -2914,6 +2969,10 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 		h->opt_persist = std::atol(e);
 	if (const char* e = std::getenv("EXPANN_SPEC_RANK"))
 		h->opt_spec_rank = std::max(0L, std::atol(e));  // (as set_option)
+	if (const char* e = std::getenv("EXPANN_REDO_BOUND"))  // (the two debug options of the search's tail: A/B runs)
+		h->opt_redo_bound = std::atol(e);
+	if (const char* e = std::getenv("EXPANN_SELECT_OVERLAP"))
+		h->opt_select_overlap = std::atol(e);
 	if (const char* e = std::getenv("EXPANN_I8_FILTER"))
 		h->opt_i8_filter = std::min(2L, std::max(0L, std::atol(e)));  // (as set_option)
 	if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&h->stream) != hipSuccess) {
@@ -2977,6 +3036,13 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 			delete h;
 			return EXPANN_ERR_HIP;
 		}
+	if (dim == kGemmI8F.d && hipFuncSetAttribute((const void*)kGemmI8FRedo, hipFuncAttributeMaxDynamicSharedMemorySize,
+	                                             kGemmI8F.lds_w) != hipSuccess) {
+		g_create_error = "hipFuncSetAttribute(scan_gemm_i8w_kernel, redo instance) failed";
+		hipStreamDestroy(h->stream);
+		delete h;
+		return EXPANN_ERR_HIP;
+	}
 	if (any_dim_i8(dim, int_mode))
 		for (const auto& v : kGemmI8KL)
 			if (v.mode == int_mode &&
@@ -3023,6 +3089,12 @@ void expann_destroy(expann_index* h) {
 			hipEventDestroy(h->ev[i][0]);
 			hipEventDestroy(h->ev[i][1]);
 		}
+	if (h->side_stream) {
+		hipStreamSynchronize(h->side_stream);
+		hipStreamDestroy(h->side_stream);
+	}
+	for (hipEvent_t e : h->side_ev)
+		if (e) hipEventDestroy(e);
 	if (h->stream) hipStreamDestroy(h->stream);
 	delete h;
 }
@@ -3143,6 +3215,7 @@ int expann_search_device(expann_index* h, const void* d_queries, size_t m, size_
 	}
 	const size_t qbytes = (size_t)h->dim * h->q_elem;
 	h->stat_redo_queries = 0;
+	h->stat_redo_candidates = 0;
 	for (size_t q0 = 0; q0 < m; q0 += kMaxQueriesPerPass) {
 		const size_t mm = std::min(kMaxQueriesPerPass, m - q0);
 		int rc = search_pass(h, (const char*)d_queries + q0 * qbytes, mm, k, d_ids + q0 * k,
@@ -3163,27 +3236,29 @@ int expann_sync(expann_index* h) {
 	h->async_pending = 0;
 	HIP_TRY(h, hipStreamSynchronize(h->async_stream));
 	uint32_t bad = 0;
-	uint64_t redo_queries = 0;
+	uint64_t redo_queries = 0, redo_candidates = 0;
 	for (uint32_t i = 0; i < n; ++i) {
-		const uint32_t* f = h->h_flag_ring + 8 * i;
+		const uint32_t* f = h->h_flag_ring + kRingWords * i;
+		const uint32_t mark = f[kRingMark];
 		float qmax, scale;
 		std::memcpy(&qmax, &f[2], sizeof(float));
-		std::memcpy(&scale, &f[6], sizeof(float));
-		const bool redo_word = (f[7] & 0x40000000u) != 0;  // (speculative thresholds: word 3 is the search's redo word)
+		std::memcpy(&scale, &f[kRingScale], sizeof(float));
+		const bool redo_word = (mark & 0x40000000u) != 0;  // (speculative thresholds: word 3 is the search's redo word)
 		if (redo_word && f[3] >= kRedoOverflowUnit)
 			h->stat_redo_overflows++;
 		else if (redo_word)
-			redo_queries += f[3];
-		if (f[0] != 0 || (f[7] == 1 && f[1] != 0) || (scale > 0.0f && !(qmax * scale <= 60000.0f)) ||
+			redo_queries += f[3], redo_candidates += f[6];
+		if (f[0] != 0 || (mark == 1 && f[1] != 0) || (scale > 0.0f && !(qmax * scale <= 60000.0f)) ||
 		    (redo_word && f[3] >= kRedoOverflowUnit))
 			++bad;
 		unsigned long long tot;
 		std::memcpy(&tot, f + 4, sizeof(tot));
 		h->prof.candidates = tot;
-		if ((f[7] & 0x80000000u) && tot > (f[7] & 0x3FFFFFFFu) && h->i8f_state == 1)  // (i8f_cand_limit)
+		if ((mark & 0x80000000u) && tot > (mark & 0x3FFFFFFFu) && h->i8f_state == 1)  // (i8f_cand_limit)
 			h->i8f_state = 2;
 	}
 	h->stat_redo_queries = redo_queries;
+	h->stat_redo_candidates = redo_candidates;
 	if (bad)
 		return h->fail(EXPANN_ERR_OVERFLOW, std::to_string(bad) + " of " + std::to_string(n) +
 		                                        " deferred searches need the synchronous retry "
@@ -3454,6 +3529,8 @@ int expann_get_stat(expann_index* h, const char* name, uint64_t* out) {
 		return EXPANN_ERR_INVALID_ARG;
 	if (!std::strcmp(name, "redo_queries"))
 		*out = h->stat_redo_queries;
+	else if (!std::strcmp(name, "redo_candidates"))
+		*out = h->stat_redo_candidates;
 	else if (!std::strcmp(name, "redo_overflows"))
 		*out = h->stat_redo_overflows;
 	else if (!std::strcmp(name, "spec_rank"))
@@ -3580,6 +3657,10 @@ int expann_set_option(expann_index* h, const char* name, long value) {
 		h->opt_i8_filter = value < 0 ? 0 : (value > 2 ? 2 : value);
 	else if (!std::strcmp(name, "spec_rank"))
 		h->opt_spec_rank = value < 0 ? 0 : value;
+	else if (!std::strcmp(name, "redo_bound"))
+		h->opt_redo_bound = value;
+	else if (!std::strcmp(name, "select_overlap"))
+		h->opt_select_overlap = value;
 	else if (!std::strcmp(name, "ip_rescale"))
 		h->opt_ip_rescale = value;
 	else if (!std::strcmp(name, "sample_pass"))

@@ -685,8 +685,8 @@ __global__ __launch_bounds__(kBlock) void sample_tau_kernel(SampleTauParams p) {
 // ---- the redo pass of the speculative thresholds -------------------------------
 // The select has appended the queries whose result the speculative threshold does not prove to `list` and counted
 // them in *word (SelectParams::redo_word).  One wave per slot s < n_slots makes the compact operands of the redo scan:
-// the fp16 (and int8) copy of query list[s], its norm, and theta' (thp, w_q) from the PROVEN tau; a slot nobody took
-// gets zero rows and the thresholds no row passes.  More failing queries than slots: + 2^20 to *word, which the host
+// the fp16 (and int8) copy of query list[s], its norm, and theta' (thp, w_q) from tau_r = min(the PROVEN tau, the
+// bound S_k' of the failed list: bound[s]); a slot nobody took gets zero rows and the thresholds no row passes.  More failing queries than slots: + 2^20 to *word, which the host
 // reads with the other flags (the search is repeated without speculation).
 struct RedoCompactParams {
 	uint32_t* word;
@@ -698,6 +698,7 @@ struct RedoCompactParams {
 	const float* qnrm;       // -> r_qnrm
 	float* r_qnrm;
 	const float* tau;        // [m] proven thresholds, true units
+	const float* bound;      // [n_slots] SelectParams::redo_bound (true units, +inf: none), or nullptr: the proven tau alone
 	const float* qscale;     // inner product with ip_rescale: c_q (the filter's domain = true units * c_q); or nullptr
 	float eps, abs_coef, mul;
 	int ip;
@@ -750,7 +751,7 @@ __global__ __launch_bounds__(kBlock) void redo_compact_kernel(RedoCompactParams 
 		return;
 	}
 	const float qn = p.qnrm[qi];
-	const float tau = p.tau[qi];
+	const float tau = p.bound ? __builtin_fminf(p.tau[qi], p.bound[s]) : p.tau[qi];
 	const float tau_f = (p.ip && p.qscale) ? tau * p.qscale[qi] : tau;  // (c_q is a power of two: exact)
 	p.r_qnrm[s] = qn;
 	p.r_theta[s] = p.ip ? (2.0f * tau_f + qn * p.eps + p.abs_coef * __builtin_sqrtf(qn)) * p.mul

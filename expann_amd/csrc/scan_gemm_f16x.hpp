@@ -42,7 +42,9 @@ static_assert(gemm_f16x_lds_bytes<64>() * 3 <= 160 * 1024, "three workgroups per
 static_assert(gemm_f16x_lds_bytes<128>() == gemm_f16_lds_bytes<128>(), "same LDS map as scan_gemm_f16_kernel<128>");
 
 // (REDO: the instance the redo pass of the speculative thresholds launches -- it alone reads p.live_q, so the
-// full scan's instance is the code it was before that pass existed)
+// full scan's instance is the code it was before that pass existed.  redo_compact_kernel fills the query slots in
+// order: a wave whose 64 slots start at or beyond the live count holds no query and takes part in the staging
+// alone -- its share of the stage loads, every wait and barrier of the step -- behind one wave-uniform branch.)
 template <int D, bool SAMPLE, int DBG = 0, bool REDO = false>
 __global__ __launch_bounds__(kF16Threads, f16x_wg_per_cu<D>()) void scan_gemm_f16x_kernel(GemmF16Params p) {
 	const uint32_t dbg = DBG ? p.debug : 0u;
@@ -292,9 +294,30 @@ __global__ __launch_bounds__(kF16Threads, f16x_wg_per_cu<D>()) void scan_gemm_f1
 #pragma unroll
 		for (int tq = 0; tq < 4; ++tq)
 			smax[par][tq] = f32x4{-__builtin_inff(), -__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+	const bool idle = REDO && p.live_q && q0 >= (*p.live_q & kRedoCountMask);  // wave-uniform: no live slot in this wave
+	if (REDO && idle && lane == 0)
+		fills[wave] = 0;  // (what the live waves read when they look at the queues)
 	stage(t0, 0);
 	stage(t0 + 1, 1);
 	asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");  // tiles t0, t0+1 landed, fills visible
+	if (REDO && idle) {
+		// the step of a wave without a query: the barrier where the live waves have theirs (tile t+1 landed, tile
+		// t-1 released), then this wave's pieces of tile t+2 into the released buffer
+		int ibuf = 0;
+		for (uint32_t t = t0; t < t1; ++t) {
+			const int pbuf = ibuf == 0 ? NBUF - 1 : ibuf - 1;
+			asm volatile("" ::: "memory");
+			__builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0) lgkmcnt(0)
+			__builtin_amdgcn_s_barrier();
+			asm volatile("" ::: "memory");
+			stage(t + 2, pbuf);
+			ibuf = ibuf + 1 == NBUF ? 0 : ibuf + 1;
+		}
+		if (lane == 0)
+			*my_log_cnt = 0;
+		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+		return;
+	}
 
 	f32x4 acc[4][4];
 	int buf = 0;

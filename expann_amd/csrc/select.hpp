@@ -47,15 +47,19 @@ struct SelectParams {
 	// the proven threshold.  Where a query's result is emitted its k-th exact score S_k is known: fewer than k rows,
 	// or S_k > spec_tau[q], and the query number is appended to redo_list through the counter in *redo_word (low
 	// 20 bits: failing queries; from bit 20: redo overflows).  spec_tau == nullptr: no check.
+	// With the query number goes what the failed list itself proves: redo_bound[slot] = S_k when the list held k
+	// rows -- k distinct rows score <= S_k, so the index's k-th best does -- else +inf.
 	const float* spec_tau;
 	uint32_t* redo_word;
 	uint32_t* redo_list;      // [redo_cap]
 	uint32_t redo_cap;
+	float* redo_bound;        // [redo_cap]
 	// the redo pass's own select: query slot s (lists, counters, qnrm, q_w) belongs to query slot_map[s] (the
 	// re-rank's query row, the output rows); slots at and beyond the failing count (*live_slots, low 20 bits) leave
 	// at once, and an overflowing list adds 2^20 to *overflow (= the redo word) instead of 1
 	const uint32_t* slot_map;
 	const uint32_t* live_slots;
+	uint32_t* redo_cand;      // [1] statistics: += the keys of every live slot's list
 };
 constexpr uint32_t kRedoCountMask = 0xFFFFFu;  // (a pass has at most 32 768 queries)
 constexpr uint32_t kRedoOverflowUnit = 1u << 20;
@@ -65,8 +69,10 @@ __device__ inline void spec_check(const SelectParams& p, uint32_t qi, bool has_k
 	if (!p.spec_tau || (has_kth && s_k <= p.spec_tau[qi]))
 		return;
 	const uint32_t slot = atomicAdd(p.redo_word, 1u) & kRedoCountMask;
-	if (slot < p.redo_cap)
+	if (slot < p.redo_cap) {
 		p.redo_list[slot] = qi;
+		p.redo_bound[slot] = has_kth ? s_k : __builtin_inff();
+	}
 }
 
 // the cutoff of the int8 filter's pruning from the k-th smallest (ordered) kappa + w_b: + w_q, + the margin
@@ -438,6 +444,8 @@ __global__ __launch_bounds__(kBlock) void select_topk_kernel(SelectParams p) {
 		return;  // (redo pass: a slot no failing query took)
 	const uint32_t qo = p.slot_map ? p.slot_map[qi] : qi;
 	uint32_t c = p.cand_cnt ? p.cand_cnt[qi] : p.fixed_count;
+	if (p.redo_cand && tid == 0)
+		atomicAdd(p.redo_cand, c);
 	if (p.wave_done && c <= p.wave_done && c <= p.cap)
 		return;  // served by a wave kernel (those leave overflowed lists, c > cap, to this one)
 	if (p.wave0_short && c <= 2048 && c <= p.cap && 8 * (size_t)p.cap >= 16384) {

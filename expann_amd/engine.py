@@ -138,7 +138,7 @@ class GpuBruteForceEngine:
                                                                  C.c_void_p(stream)))
 
     def get_stat(self, name):
-        """expann_get_stat: "redo_queries", "redo_overflows", "spec_rank" (speculative thresholds);
+        """expann_get_stat: "redo_queries", "redo_candidates", "redo_overflows", "spec_rank" (speculative thresholds);
         "filter_active" (0 / 1) and "filter_rows" (rows the row filter allows; n when none is set);
         "base_bytes" (device bytes of the rows themselves: n * dim * element size)."""
         v = C.c_uint64(0)

@@ -492,12 +492,17 @@ int expann_sharded_get_profile(expann_sharded* h, int shard, expann_profile* out
  * query's result against it and the few failing queries are searched again on the device with the proven
  * threshold -- ids and distances do not change.  0 (default): j from k, the sampled share of the rows and a share
  * of failing queries of at most 1 %, where the planner found a gain; j >= 1: that rank wherever the check exists;
- * j >= k: off.  The environment variable EXPANN_SPEC_RANK sets the starting value). */
+ * j >= k: off.  The environment variable EXPANN_SPEC_RANK sets the starting value),
+ * and two debug switches of a speculating search's tail, for tests and A/B runs (results are the same either way;
+ * EXPANN_REDO_BOUND / EXPANN_SELECT_OVERLAP set the starting values): "redo_bound" (1, default: the redo pass filters
+ * with the smaller of the proven threshold and the k-th exact score of the failed list; 0: the proven threshold
+ * alone) and "select_overlap" (1, default: the select stages of lists beyond 512 keys run on an internal side
+ * stream beside the short lists' stage, joined before anything that follows; 0: one stream). */
 int expann_set_option(expann_index* h, const char* name, long value);
 
 /* counters outside expann_profile (whose layout is fixed): "redo_queries" = queries of the last search that the
  * redo pass of the speculative thresholds served (deferred searches: of the searches the last expann_sync
- * checked), "redo_overflows" = searches since the handle was made whose failing queries did not fit the redo
+ * checked), "redo_candidates" = the keys the redo lists of those queries held, "redo_overflows" = searches since the handle was made whose failing queries did not fit the redo
  * pass (repeated with proven thresholds: a retry), "spec_rank" = the rank j of the last search's thresholds
  * (= k: proven thresholds), "base_bytes" = bytes of device memory that hold the rows themselves (n * dim * bytes
  * per element, every dtype; 0 before the rows are on the device). */
