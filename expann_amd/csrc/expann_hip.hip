@@ -86,6 +86,7 @@ struct expann_index {
 	DevPtr<float> d_tau[2];
 	DevPtr<float> d_tau_s;           // [m_alloc] speculative thresholds of the sampled pass, true units
 	GrowPtr<void> d_redo;            // the redo pass's workspace: failing queries, their compact operands, their lists
+	GrowPtr<void> d_rerank;          // "rerank_stats": [sum (8 bytes, 8 unused) | rows re-scored per query [m]]
 	DevPtr<uint32_t> d_tau_row[2];
 	size_t m_alloc = 0;
 	DevPtr<uint32_t> d_overflow;     // [4]: overflow count
@@ -194,12 +195,15 @@ struct expann_index {
 	long opt_spec_rank = 0;          // speculative thresholds: 0 auto, j >= 1: the j-th class maximum (j >= k: off)
 	long opt_redo_bound = 1;         // debug: 0 = the redo pass's thresholds from the proven tau alone
 	long opt_select_overlap = 1;     // debug: 0 = the select stages of long lists on the caller's stream
+	long opt_rerank_rounds = 2;      // int8 filter's lists: 2 = re-ranked in two rounds, 1 = the single cut
+	long opt_rerank_stats = 0;       // 1 = count the rows the selects re-score ("rerank_rows"; adds launches and a host wait)
 	// the side stream of the select's long-list stages (launch_select_wave), and the events of its fork and join;
 	// made at the first search that has such a stage
 	hipStream_t side_stream = nullptr;
 	hipEvent_t side_ev[2] = {nullptr, nullptr};
 	uint64_t stat_redo_queries = 0;  // queries the redo pass served in the last search (waiting form) / the last synced one
 	uint64_t stat_redo_candidates = 0;  // keys the redo lists of those queries held (the redo select counts them)
+	uint64_t stat_rerank_rows = 0;   // rows the last search's selects re-scored exactly (opt_rerank_stats)
 	uint64_t stat_redo_overflows = 0;  // searches whose failing queries (or redo lists) did not fit the redo pass
 	uint64_t stat_spec_rank = 0;     // j of the last search's thresholds (= k: proven thresholds)
 	long opt_i8_filter = 1;          // fp32 L2 d = 128: the int8 filter (scan_gemm_i8f.hpp): 0 off, 1 auto, 2 wherever supported
@@ -910,12 +914,17 @@ uint32_t select_longest_list(double expect, uint32_t spec_j) {
 // `side` (or nullptr): the stream of the stages behind the first.  The stages serve disjoint queries, write disjoint
 // output rows and share only atomic counters, so with a side stream -- which the caller has made wait for the
 // gather -- the long lists' stages run beside the short lists' <8,4> launch instead of behind it.
+// (sel.tau_f set -- the int8 filter's lists, fp32 rows -- : the two-round instances)
 void launch_select_wave(SelectParams& sel, size_t m, uint32_t cap, hipStream_t st, uint32_t longest, bool rows_f16 = false,
                         hipStream_t side = nullptr) {
 	using WaveFn = void (*)(SelectParams, uint32_t);
-	const WaveFn w8 = rows_f16 ? select_wave_kernel<8, 4, _Float16> : select_wave_kernel<8, 4>;
-	const WaveFn w16 = rows_f16 ? select_wave_kernel<16, 2, _Float16> : select_wave_kernel<16, 2>;
-	const WaveFn w32 = rows_f16 ? select_wave_kernel<32, 1, _Float16> : select_wave_kernel<32, 1>;
+	const bool two = sel.tau_f != nullptr;
+	const WaveFn w8 = rows_f16 ? select_wave_kernel<8, 4, _Float16>
+	                           : (two ? select_wave_kernel<8, 4, float, true> : select_wave_kernel<8, 4>);
+	const WaveFn w16 = rows_f16 ? select_wave_kernel<16, 2, _Float16>
+	                            : (two ? select_wave_kernel<16, 2, float, true> : select_wave_kernel<16, 2>);
+	const WaveFn w32 = rows_f16 ? select_wave_kernel<32, 1, _Float16>
+	                            : (two ? select_wave_kernel<32, 1, float, true> : select_wave_kernel<32, 1>);
 	const hipStream_t st2 = side ? side : st;
 	sel.wave_done = 0;
 	hipLaunchKernelGGL(w8, dim3((uint32_t)((m + 3) / 4)), dim3(256), 0, st, sel, (uint32_t)m);
@@ -933,7 +942,9 @@ void launch_select_wave(SelectParams& sel, size_t m, uint32_t cap, hipStream_t s
 	}
 }
 using SelectTopkFn = void (*)(SelectParams);
-inline SelectTopkFn select_topk_fn(const expann_index* h) {
+inline SelectTopkFn select_topk_fn(const expann_index* h, const SelectParams& sel) {
+	if (sel.tau_f)  // (the int8 filter's lists: fp32 rows)
+		return select_topk_kernel<float, true>;
 	return f16_rows(h) ? select_topk_kernel<_Float16> : select_topk_kernel<float>;
 }
 // The select of a full scan's lists: the statistics sum, the wave stages, the left-over launch.
@@ -958,7 +969,7 @@ int launch_select(expann_index* h, SelectParams& sel, size_t m, uint32_t cap, hi
 	if (sum_counts)  // statistics: candidates of the full scan (i8f_cand_limit)
 		hipLaunchKernelGGL(sum_u32_kernel, dim3(1), dim3(1024), 0, st2, sel.cand_cnt, (uint32_t)m, h->d_total);
 	launch_select_wave(sel, m, cap, st, longest, f16_rows(h), side);
-	hipLaunchKernelGGL(select_topk_fn(h), dim3((uint32_t)m), dim3(kBlock), sizeof(uint64_t) * cap + 16, st2, sel);
+	hipLaunchKernelGGL(select_topk_fn(h, sel), dim3((uint32_t)m), dim3(kBlock), sizeof(uint64_t) * cap + 16, st2, sel);
 	HIP_TRY(h, hipGetLastError());
 	if (side) {
 		HIP_TRY(h, hipEventRecord(h->side_ev[1], side));
@@ -1986,10 +1997,11 @@ int launch_scan_f16(expann_index* h, const GemmF16Variant* gvf, uint32_t rows_se
 // run_level(li)      scan of level li (direct / fp32 / bf16x3 / fp16 / int8 MFMA filter) + selection
 // check(attempt)     the one host wait: flags read back, retry with larger lists / another family
 // the redo pass's workspace for R query slots (expann_index::d_redo), offsets in bytes: the failing queries'
-// numbers, the per-slot list counters, theta', ||q||^2, w_q, thp, the bounds S_k' of the failed lists, the fp16 and
-// int8 copies, the candidate lists
+// numbers, the per-slot list counters, theta', ||q||^2, w_q, thp, the bounds S_k' of the failed lists, the thresholds
+// tau_r the redo scan filters with (true units: the two-round re-rank's tau_f), the fp16 and int8 copies, the
+// candidate lists
 struct RedoWs {
-	size_t list, cnt, theta, qnrm, wq, thp, bound, q16, q8, cand, total;
+	size_t list, cnt, theta, qnrm, wq, thp, bound, tau, q16, q8, cand, total;
 	RedoWs(uint32_t R, int dim, uint32_t cap) {
 		list = 0;
 		cnt = 4 * (size_t)R;
@@ -1998,7 +2010,8 @@ struct RedoWs {
 		wq = 16 * (size_t)R;
 		thp = 20 * (size_t)R;
 		bound = 24 * (size_t)R;
-		q16 = 28 * (size_t)R;  // (R is a multiple of 256: every part starts on a 16-byte boundary)
+		tau = 28 * (size_t)R;
+		q16 = 32 * (size_t)R;  // (R is a multiple of 256: every part starts on a 16-byte boundary)
 		q8 = q16 + 2 * (size_t)R * (size_t)dim;
 		cand = q8 + (size_t)R * (size_t)dim;
 		total = cand + 8 * (size_t)R * (size_t)cap;
@@ -2058,6 +2071,7 @@ struct SearchPass {
 	uint32_t spec_j = 0;        // this attempt's lists are filtered with the j-th class maximum, j < k (0: proven thresholds)
 	bool spec_off = false;      // an attempt's failing queries did not fit the redo pass: proven thresholds from here on
 	uint32_t redo_slots = 0;    // R: query slots of the redo pass
+	bool rerank_counted = false;  // "rerank_stats": the last level's selects counted the rows they re-scored
 
 	enum Next { kDone, kRestart, kRetry };
 	int choose_kernels();
@@ -2490,6 +2504,17 @@ int SearchPass::run_level(size_t li) {
 		sel.prune_abs = 0.0f;
 		sel.row_w = h->d_rw_i8f;
 		sel.q_w = h->d_i8f_q + 2 * h->i8f_q_m;
+		if (h->opt_rerank_rounds != 1) {  // two rounds: tau_f = the threshold thp came from (sample_tau_finish)
+			sel.tau_f = spec_j ? (const float*)h->d_tau_s : (const float*)h->d_tau[levels.size() & 1];
+			sel.inv_2s2 = h->i8f.inv_2s2;
+		}
+	}
+	rerank_counted = false;
+	if (last && sel.rerank_base && h->opt_rerank_stats) {
+		HIP_TRY(h, grow_ws(h, h->d_rerank, 16 + sizeof(uint32_t) * m));
+		HIP_TRY(h, hipMemsetAsync(h->d_rerank, 0, 16 + sizeof(uint32_t) * m, st));
+		sel.rerank_cnt = reinterpret_cast<uint32_t*>(h->d_rerank.as<unsigned char>() + 16);
+		rerank_counted = true;
 	}
 	sel.overflow = h->d_overflow;
 	if (last && spec_j) {  // the check of the speculative thresholds; failing queries go to the redo pass's list
@@ -2515,7 +2540,7 @@ int SearchPass::run_level(size_t li) {
 			hipLaunchKernelGGL(sum_u32_kernel, dim3(1), dim3(1024), 0, st, sel.cand_cnt, (uint32_t)m, h->d_total);
 		if (m <= 64)
 			sel.wave0_short = 1;  // latency mode: one launch, wave 0 orders the short lists
-		hipLaunchKernelGGL(select_topk_fn(h), dim3((uint32_t)m), dim3(kBlock), sizeof(uint64_t) * cap + 16, st, sel);
+		hipLaunchKernelGGL(select_topk_fn(h, sel), dim3((uint32_t)m), dim3(kBlock), sizeof(uint64_t) * cap + 16, st, sel);
 		HIP_TRY(h, hipGetLastError());
 	}
 	if (last && spec_j)
@@ -2557,6 +2582,7 @@ int SearchPass::run_redo(bool use_i8f) {
 		cp.i8_wq_in = h->d_i8f_q + h->i8f_q_m;
 		cp.r_thp = reinterpret_cast<int*>(b + ws.thp);
 		cp.r_wq = reinterpret_cast<float*>(b + ws.wq);
+		cp.r_tau = reinterpret_cast<float*>(b + ws.tau);
 		cp.i8_inv_2s2 = h->i8f.inv_2s2;
 	}
 	hipLaunchKernelGGL(redo_compact_kernel, dim3(R / (kBlock / 64)), dim3(kBlock), 0, st, cp);
@@ -2663,6 +2689,10 @@ int SearchPass::run_redo(bool use_i8f) {
 	if (use_i8f) {
 		sel.row_w = h->d_rw_i8f;
 		sel.q_w = cp.r_wq;
+		if (h->opt_rerank_rounds != 1) {
+			sel.tau_f = cp.r_tau;
+			sel.inv_2s2 = h->i8f.inv_2s2;
+		}
 	} else {
 		sel.prune_eps = pr * gemm_f16_filter_eps(h->dim);
 		sel.prune_abs = pr * std::ldexp(1.0f, -24) / h->f16_scale * std::sqrt((float)h->dim);
@@ -2672,15 +2702,28 @@ int SearchPass::run_redo(bool use_i8f) {
 	sel.slot_map = cp.list;
 	sel.live_slots = word;
 	sel.redo_cand = h->d_overflow + 6;
-	hipLaunchKernelGGL(select_topk_fn(h), dim3(R), dim3(kBlock), sizeof(uint64_t) * cap + 16, st, sel);
+	if (rerank_counted)
+		sel.rerank_cnt = reinterpret_cast<uint32_t*>(h->d_rerank.as<unsigned char>() + 16);
+	hipLaunchKernelGGL(select_topk_fn(h, sel), dim3(R), dim3(kBlock), sizeof(uint64_t) * cap + 16, st, sel);
 	HIP_TRY(h, hipGetLastError());
 	return EXPANN_OK;
 }
 
 int SearchPass::check(int attempt, Next* next) {
 	*next = kDone;
+	uint64_t reranked = 0;
+	if (rerank_counted) {  // statistics on request: one more launch and a host wait, also in the deferred form
+		unsigned long long* const total = h->d_rerank.as<unsigned long long>();
+		hipLaunchKernelGGL(sum_u32_kernel, dim3(1), dim3(1024), 0, st, reinterpret_cast<const uint32_t*>(total + 2),
+		                   (uint32_t)m, total);
+		unsigned long long v = 0;
+		HIP_TRY(h, hipMemcpyAsync(&v, total, sizeof(v), hipMemcpyDeviceToHost, st));
+		HIP_TRY(h, hipStreamSynchronize(st));
+		reranked = v;
+	}
 	// overflow check (the only host sync of a search); flags and statistics are contiguous
-	if (defer_flags(h, st, attempt)) {  // deferred check: expann_sync reads the flags
+	if (defer_flags(h, st, attempt)) {
+		h->stat_rerank_rows += reranked;  // deferred check: expann_sync reads the flags
 		float sc = gvf ? h->f16_scale : 0.0f;  // (fp16 form: the range check of max |q| needs the scale)
 		uint32_t* const slot = h->h_flag_ring + kRingWords * (h->async_pending - 1);
 		std::memcpy(&slot[kRingScale], &sc, sizeof(float));
@@ -2727,6 +2770,7 @@ int SearchPass::check(int attempt, Next* next) {
 	if (h->h_flags[0] == 0 && redo_word < kRedoOverflowUnit) {
 		h->stat_redo_queries += redo_word;
 		h->stat_redo_candidates += spec_j ? h->h_flags[6] : 0u;
+		h->stat_rerank_rows += reranked;
 		return EXPANN_OK;
 	}
 	h->prof.retries++;
@@ -2973,6 +3017,8 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 		h->opt_redo_bound = std::atol(e);
 	if (const char* e = std::getenv("EXPANN_SELECT_OVERLAP"))
 		h->opt_select_overlap = std::atol(e);
+	if (const char* e = std::getenv("EXPANN_RERANK_ROUNDS"))  // (A/B runs against the single cut)
+		h->opt_rerank_rounds = std::atol(e) == 1 ? 1 : 2;
 	if (const char* e = std::getenv("EXPANN_I8_FILTER"))
 		h->opt_i8_filter = std::min(2L, std::max(0L, std::atol(e)));  // (as set_option)
 	if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&h->stream) != hipSuccess) {
@@ -2984,6 +3030,8 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 	if (hipFuncSetAttribute((const void*)select_topk_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize,
 	                        (int)(sizeof(uint64_t) * kMaxCap + 16)) != hipSuccess ||
 	    hipFuncSetAttribute((const void*)select_topk_kernel<_Float16>, hipFuncAttributeMaxDynamicSharedMemorySize,
+	                        (int)(sizeof(uint64_t) * kMaxCap + 16)) != hipSuccess ||
+	    hipFuncSetAttribute((const void*)select_topk_kernel<float, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
 	                        (int)(sizeof(uint64_t) * kMaxCap + 16)) != hipSuccess) {
 		g_create_error = "hipFuncSetAttribute(select_topk_kernel) failed";
 		hipStreamDestroy(h->stream);
@@ -3216,6 +3264,7 @@ int expann_search_device(expann_index* h, const void* d_queries, size_t m, size_
 	const size_t qbytes = (size_t)h->dim * h->q_elem;
 	h->stat_redo_queries = 0;
 	h->stat_redo_candidates = 0;
+	h->stat_rerank_rows = 0;
 	for (size_t q0 = 0; q0 < m; q0 += kMaxQueriesPerPass) {
 		const size_t mm = std::min(kMaxQueriesPerPass, m - q0);
 		int rc = search_pass(h, (const char*)d_queries + q0 * qbytes, mm, k, d_ids + q0 * k,
@@ -3535,6 +3584,8 @@ int expann_get_stat(expann_index* h, const char* name, uint64_t* out) {
 		*out = h->stat_redo_overflows;
 	else if (!std::strcmp(name, "spec_rank"))
 		*out = h->stat_spec_rank;
+	else if (!std::strcmp(name, "rerank_rows"))
+		*out = h->stat_rerank_rows;
 	else if (!std::strcmp(name, "base_bytes"))
 		*out = h->d_base ? (uint64_t)h->n * (uint64_t)h->dim * h->elem : 0;
 	else if (!std::strcmp(name, "filter_active"))
@@ -3661,6 +3712,10 @@ int expann_set_option(expann_index* h, const char* name, long value) {
 		h->opt_redo_bound = value;
 	else if (!std::strcmp(name, "select_overlap"))
 		h->opt_select_overlap = value;
+	else if (!std::strcmp(name, "rerank_rounds"))
+		h->opt_rerank_rounds = value == 1 ? 1 : 2;
+	else if (!std::strcmp(name, "rerank_stats"))
+		h->opt_rerank_stats = value ? 1 : 0;
 	else if (!std::strcmp(name, "ip_rescale"))
 		h->opt_ip_rescale = value;
 	else if (!std::strcmp(name, "sample_pass"))

@@ -400,8 +400,11 @@ struct GatherLogParams {
 	// HERE -- dot = acc - i_thp[query], L2 forms: i_bias[row] - 2 dot + i_qself[query], inner product: -dot --
 	// instead of two global gathers per hit inside the MFMA kernel (whose vmcnt they shared with the stage
 	// loads).  i_mode: 0 = not an 8-bit log, 1 = L2 forms, 2 = inner product.
-	// i_mode 3, the int8 filter of fp32 rows (scan_gemm_i8f.hpp): i_bias = bp, the key is kappa = bp - acc (units of
-	// 2 s^2, -inf for a row whose bp was clamped: i_rw[row] = +inf), re-scored exactly by the select.
+	// i_mode 3, the int8 filter of fp32 rows (scan_gemm_i8f.hpp): the entry's fourth word is the row's bp (the scan
+	// had it in a register), the key is kappa = bp - acc (units of 2 s^2), re-scored exactly by the select; -inf for a
+	// row whose bp sits at a clamp limit -- a clamped row always does, and an unclamped row that lands exactly on a
+	// limit is merely always re-scored.  No read of i_bias / i_rw per hit (two random 4-byte gathers, 2.1 M hits a
+	// step at C2).
 	const int* i_thp;
 	const int* i_bias;
 	const int* i_qself;
@@ -453,8 +456,9 @@ __global__ __launch_bounds__(kBlock) void gather_logs_kernel(GatherLogParams p) 
 			if (slot < p.cap) {
 				uint64_t key;
 				if (p.i_mode == 3) {
-					const float kappa = (float)(p.i_bias[e.y] - (int)e.x);
-					key = make_key(p.i_rw[e.y] < __builtin_inff() ? kappa : -__builtin_inff(), e.y);
+					const int bp = (int)e.w;
+					const float kappa = (float)(bp - (int)e.x);
+					key = make_key(bp > kI8fBpMin && bp < kI8fBpMax ? kappa : -__builtin_inff(), e.y);
 				} else if (p.i_mode) {
 					const int dot = (int)e.x - p.i_thp[e.z];
 					const int score = p.i_mode == 1 ? p.i_bias[e.y] - 2 * dot + p.i_qself[e.z] : -dot;
@@ -711,6 +715,7 @@ struct RedoCompactParams {
 	const float* i8_wq_in;
 	int* r_thp;
 	float* r_wq;
+	float* r_tau;            // [n_slots] <- tau_r, the threshold r_thp is derived from (the select's second round, SelectParams::tau_f)
 	double i8_inv_2s2;
 };
 __global__ __launch_bounds__(kBlock) void redo_compact_kernel(RedoCompactParams p) {
@@ -747,6 +752,7 @@ __global__ __launch_bounds__(kBlock) void redo_compact_kernel(RedoCompactParams 
 		if (p.q8) {
 			p.r_thp[s] = (-2147483647 - 1) / 2;  // (the start value of a padded query slot, scan_gemm_i8w.hpp)
 			p.r_wq[s] = __builtin_inff();
+			p.r_tau[s] = __builtin_inff();
 		}
 		return;
 	}
@@ -756,8 +762,10 @@ __global__ __launch_bounds__(kBlock) void redo_compact_kernel(RedoCompactParams 
 	p.r_qnrm[s] = qn;
 	p.r_theta[s] = p.ip ? (2.0f * tau_f + qn * p.eps + p.abs_coef * __builtin_sqrtf(qn)) * p.mul
 	                    : (tau_f - (qn * (1.0f - p.eps) - p.abs_coef * __builtin_sqrtf(qn))) * p.mul;
-	if (p.q8)
+	if (p.q8) {
 		i8f_thresholds(p.i8_aq[qi], p.i8_wq_in[qi], tau, p.i8_inv_2s2, p.r_thp + s, p.r_wq + s);
+		p.r_tau[s] = tau;
+	}
 }
 
 }  // namespace expann

@@ -188,8 +188,10 @@ __global__ __launch_bounds__(kF16Threads, I8wGeom<D>::WG_PER_CU) void scan_gemm_
 	uint4* const my_log = SAMPLE ? nullptr : pw.log + ((size_t)blockIdx.x * WAVES + wave) * pw.log_cap;
 	auto flush_own = [&]() {
 		const uint32_t n = wfill < (uint32_t)QCAP ? wfill : (uint32_t)QCAP;
-		// 16 lanes per entry, two rounds of 4 entries in flight; a log entry is {raw accumulator, row, query}:
-		// gather_logs_kernel makes the exact score (GatherLogParams::i_mode)
+		// 16 lanes per entry, two rounds of 4 entries in flight; a log entry is {raw accumulator, row, query, bp}:
+		// gather_logs_kernel makes the exact score (GatherLogParams::i_mode; bp spares the int8 filter's gather two
+		// random 4-byte reads per hit -- the other modes ignore it.  It is read from the queue again at the store, a
+		// hit lane's own entry: held in a register from the compare on, it cost the full scan 6 VGPRs)
 		for (uint32_t base = 0; base < n * 16; base += 128) {
 			bool hit[2];
 			int cv[2];
@@ -212,7 +214,7 @@ __global__ __launch_bounds__(kF16Threads, I8wGeom<D>::WG_PER_CU) void scan_gemm_
 				const uint32_t pos = glog_n + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
 				                                                        __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 				if (hit[u] && pos < pw.log_cap)
-					my_log[pos] = make_uint4((uint32_t)cv[u], row[u], qi[u], 0u);
+					my_log[pos] = make_uint4((uint32_t)cv[u], row[u], qi[u], (uint32_t)queue[(base + 64 * u + lane) >> 4].bp);
 				glog_n += (uint32_t)__builtin_popcountll(mask);
 			}
 		}

@@ -43,6 +43,15 @@ struct SelectParams {
 	// a candidate whose kappa exceeds the k-th smallest upper bound cannot be among the k best
 	const float* row_w;
 	const float* q_w;
+	// two-round re-rank of the int8 filter's lists (the TWO instances of the wave body; scan_gemm_i8f.hpp, "Two
+	// rounds"): tau_f[slot] = the fp32 threshold thp[slot] was derived from (true units), inv_2s2 = 1 / (2 s^2).  The
+	// R1 keys of smallest kappa are re-scored first, T = their k-th exact score; of the others only those with
+	// tau_f + 2 s^2 kappa <= T are.  tau_f == nullptr: the single cut above ("rerank_rounds" = 1).
+	const float* tau_f;
+	double inv_2s2;
+	// statistics ("rerank_stats"), or nullptr: rerank_cnt[query] = rows this select re-scored exactly (+= in the
+	// redo pass's select, whose queries the main select has counted before)
+	uint32_t* rerank_cnt;
 	// speculative thresholds: the lists were filtered with spec_tau[q] (true units), tighter than
 	// the proven threshold.  Where a query's result is emitted its k-th exact score S_k is known: fewer than k rows,
 	// or S_k > spec_tau[q], and the query number is appended to redo_list through the counter in *redo_word (low
@@ -87,6 +96,21 @@ __device__ inline float i8f_cutoff(uint32_t kth_ord, float wq) {
 __device__ inline uint32_t i8f_upper_ord(const SelectParams& p, uint64_t key) {
 	const float v = key_score(key) + p.row_w[key_idx(key)];
 	return float_to_ordered(v == v ? v : __builtin_inff());
+}
+
+// the kappa at and below which a row of the second round may still reach T (the k-th exact score of the first
+// round): S >= tau_f + 2 s^2 kappa (scan_gemm_i8f.hpp), so a row can be dropped when kappa > x = (T - tau_f) / 2s^2.
+// x is formed in fp64 (T - tau_f: one rounding, the stored 1 / 2s^2 and the product one each: < 2^-50 relative,
+// covered by 2^-40 |x| + 2^-10) and rounded UP to fp32; a key is the fp32 rounding of its integer kappa and rounding
+// is monotone, so kappa <= x implies key <= cut.  A NaN (no finite T or tau_f) keeps every row: !(key > cut).
+__device__ inline float i8f_round2_cut(float t, float tau_f, double inv_2s2) {
+	const double x = ((double)t - (double)tau_f) * inv_2s2;
+	const double xu = x + (__builtin_fabs(x) * 0x1p-40 + 0x1p-10);
+	float f = (float)xu;
+	if ((double)f < xu)  // (the conversion rounded down: one step up; +inf stays)
+		f = f == 0.0f ? __builtin_bit_cast(float, 1u)
+		              : __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, f) + (f > 0.0f ? 1u : 0xFFFFFFFFu));
+	return f;
 }
 
 // statistics: *out = sum of counts (one workgroup; one same-address atomic per query in the
@@ -288,7 +312,9 @@ __device__ inline uint2 wave_kth_largest_sparse_u32(const uint32_t (&v)[PER], ui
 
 // one wave orders the list of query slot qi (c <= 64 * PER keys); list = 64 * PER keys of LDS
 // (TR = element type of the re-rank rows: common.hpp ref_diff / ref_dot)
-template <int PER, typename TR = float>
+// TWO: the instances of the int8 filter's lists with the two-round re-rank (SelectParams::tau_f); the others hold
+// none of its code
+template <int PER, typename TR = float, bool TWO = false>
 __device__ inline void select_wave_body(const SelectParams& p, uint32_t qi, uint32_t c, uint64_t* list,
                                         int lane) {
 	const uint64_t* src = p.cand + (size_t)qi * p.cap;
@@ -304,7 +330,7 @@ __device__ inline void select_wave_body(const SelectParams& p, uint32_t qi, uint
 	// what is left to rank is k keys + ties instead of the whole list (k = 100 on uint8 rows: 535 keys, each
 	// ranked against all of them, were 0.31 ms of a 2.4 ms step)
 	const bool final_scores = p.rerank_base == nullptr;
-	if ((p.prune_eps > 0.0f || final_scores || p.row_w) && c > p.k) {
+	if (!TWO && (p.prune_eps > 0.0f || final_scores || p.row_w) && c > p.k) {
 		float qn = 0.0f;
 		if (final_scores || p.row_w) {
 		} else if (p.qnrm) {
@@ -347,68 +373,165 @@ __device__ inline void select_wave_body(const SelectParams& p, uint32_t qi, uint
 		}
 	}
 	uint32_t n_s = 0;  // wave-uniform
+	uint32_t n1 = 0;   // TWO: keys of the first round, list[0, n1)
+	if (TWO) {
+		const uint32_t r1 = p.k <= 16 ? 16u : (p.k + 15u) & ~15u;
+		if (c > r1 && p.q_w[qi] < __builtin_inff()) {
+			// v = the r1-th smallest kappa (repeated values counted); -inf keys, rows without an interval, come first
+			uint32_t sc[PER];
 #pragma unroll
-	for (int j = 0; j < PER; ++j) {
-		const bool hit = lane + 64 * j < (int)c && key_score(kk[j]) <= cutoff;
-		const unsigned long long mask = __builtin_amdgcn_ballot_w64(hit);
-		const uint32_t pos = n_s + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
-		                                                      __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-		if (hit)
-			list[pos] = kk[j];
-		n_s += (uint32_t)__builtin_popcountll(mask);
-	}
-	asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (one wave: LDS ops are in order)
-	// exact re-score, two candidates per 16-lane group in flight; slot i is read and rewritten
-	// by the one group that owns it.  (Lists with final scores -- the 8-bit forms -- skip it.)
-	for (uint32_t i0 = 0; p.rerank_base && i0 < n_s; i0 += 16) {
-		constexpr int U = 4;  // candidates per 16-lane group in flight
-		float acc[U];
-		uint32_t row[U];
-		const TR* r[U];
+			for (int j = 0; j < PER; ++j)
+				sc[j] = (uint32_t)(kk[j] >> 32);
+			uint32_t v = 0xFFFFFFFFu;
+			if (p.k > 24) {
+				v = wave_kth_smallest_u32<PER>(sc, r1);
+			} else {
+				for (uint32_t cnt = 0; cnt < r1;) {
+					uint32_t mn = sc[0];
 #pragma unroll
-		for (int u = 0; u < U; ++u) {
-			const uint32_t i = i0 + 4 * u + grp;
-			row[u] = key_idx(list[i < n_s ? i : 0]);
-			r[u] = (const TR*)p.rerank_base + (size_t)row[u] * p.dim + l;
-			acc[u] = 0.0f;
-		}
-		// 8 dims of every candidate are requested before any is consumed (the trip count is a
-		// run-time value: without this the loop waits for each load in turn); per candidate the
-		// FMA chain still runs over t in increasing order, as the reference's lane does
-		const uint32_t nt = p.dim / 16;
-		for (uint32_t t0 = 0; t0 < nt; t0 += 8) {
-			float qv[8];
-			TR rv[U][8];
+					for (int j = 1; j < PER; ++j)
+						mn = min(mn, sc[j]);
+					mn = wave_min_u32(mn);
+					if (mn == 0xFFFFFFFFu)
+						break;
+					v = mn;
 #pragma unroll
-			for (int t = 0; t < 8; ++t)
-				qv[t] = t0 + t < nt ? q[16 * (t0 + t)] : 0.0f;
-#pragma unroll
-			for (int u = 0; u < U; ++u)
-#pragma unroll
-				for (int t = 0; t < 8; ++t)
-					rv[u][t] = t0 + t < nt ? r[u][16 * (t0 + t)] : (TR)0.0f;
-#pragma unroll
-			for (int u = 0; u < U; ++u)
-#pragma unroll
-				for (int t = 0; t < 8; ++t) {
-					if (t0 + t >= nt)
-						continue;  // (d = 64: four dims per lane)
-					if (p.metric_ip) {
-						acc[u] = ref_dot<TR>(qv[t], rv[u][t], acc[u]);
-					} else {
-						const float diff = ref_diff<TR>(qv[t], rv[u][t]);
-						acc[u] = __builtin_fmaf(diff, diff, acc[u]);
+					for (int j = 0; j < PER; ++j) {
+						const bool eq = sc[j] == mn;
+						cnt += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(eq));
+						sc[j] = eq ? 0xFFFFFFFFu : sc[j];
 					}
 				}
-		}
+			}
+			// the first round's keys to the front of the list, the others behind them
 #pragma unroll
-		for (int u = 0; u < U; ++u) {
-			acc[u] = reduce16_ref_order(acc[u]);
-			const uint32_t i = i0 + 4 * u + grp;
-			if (l == 0 && i < n_s)
-				list[i] = make_key(p.metric_ip ? -acc[u] : acc[u], row[u]);
+			for (int j = 0; j < PER; ++j) {
+				const bool hit = lane + 64 * j < (int)c && (uint32_t)(kk[j] >> 32) <= v;
+				const unsigned long long mask = __builtin_amdgcn_ballot_w64(hit);
+				const uint32_t pos = n1 + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
+				                                                     __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+				if (hit)
+					list[pos] = kk[j];
+				n1 += (uint32_t)__builtin_popcountll(mask);
+			}
+			uint32_t n_o = n1;
+#pragma unroll
+			for (int j = 0; j < PER; ++j) {
+				const bool hit = lane + 64 * j < (int)c && (uint32_t)(kk[j] >> 32) > v;
+				const unsigned long long mask = __builtin_amdgcn_ballot_w64(hit);
+				const uint32_t pos = n_o + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
+				                                                      __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+				if (hit)
+					list[pos] = kk[j];
+				n_o += (uint32_t)__builtin_popcountll(mask);
+			}
+			n_s = n1;
 		}
 	}
+	if (!TWO || n1 == 0) {
+		n_s = 0;
+#pragma unroll
+		for (int j = 0; j < PER; ++j) {
+			const bool hit = lane + 64 * j < (int)c && key_score(kk[j]) <= cutoff;
+			const unsigned long long mask = __builtin_amdgcn_ballot_w64(hit);
+			const uint32_t pos = n_s + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
+			                                                      __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+			if (hit)
+				list[pos] = kk[j];
+			n_s += (uint32_t)__builtin_popcountll(mask);
+		}
+	}
+	asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (one wave: LDS ops are in order)
+	auto rescore = [&](uint32_t begin) {
+		// exact re-score, two candidates per 16-lane group in flight; slot i is read and rewritten
+		// by the one group that owns it.  (Lists with final scores -- the 8-bit forms -- skip it.)
+		for (uint32_t i0 = begin; p.rerank_base && i0 < n_s; i0 += 16) {
+			constexpr int U = 4;  // candidates per 16-lane group in flight
+			float acc[U];
+			uint32_t row[U];
+			const TR* r[U];
+#pragma unroll
+			for (int u = 0; u < U; ++u) {
+				const uint32_t i = i0 + 4 * u + grp;
+				row[u] = key_idx(list[i < n_s ? i : 0]);
+				r[u] = (const TR*)p.rerank_base + (size_t)row[u] * p.dim + l;
+				acc[u] = 0.0f;
+			}
+			// 8 dims of every candidate are requested before any is consumed (the trip count is a
+			// run-time value: without this the loop waits for each load in turn); per candidate the
+			// FMA chain still runs over t in increasing order, as the reference's lane does
+			const uint32_t nt = p.dim / 16;
+			for (uint32_t t0 = 0; t0 < nt; t0 += 8) {
+				float qv[8];
+				TR rv[U][8];
+#pragma unroll
+				for (int t = 0; t < 8; ++t)
+					qv[t] = t0 + t < nt ? q[16 * (t0 + t)] : 0.0f;
+#pragma unroll
+				for (int u = 0; u < U; ++u)
+#pragma unroll
+					for (int t = 0; t < 8; ++t)
+						rv[u][t] = t0 + t < nt ? r[u][16 * (t0 + t)] : (TR)0.0f;
+#pragma unroll
+				for (int u = 0; u < U; ++u)
+#pragma unroll
+					for (int t = 0; t < 8; ++t) {
+						if (t0 + t >= nt)
+							continue;  // (d = 64: four dims per lane)
+						if (p.metric_ip) {
+							acc[u] = ref_dot<TR>(qv[t], rv[u][t], acc[u]);
+						} else {
+							const float diff = ref_diff<TR>(qv[t], rv[u][t]);
+							acc[u] = __builtin_fmaf(diff, diff, acc[u]);
+						}
+					}
+			}
+#pragma unroll
+			for (int u = 0; u < U; ++u) {
+				acc[u] = reduce16_ref_order(acc[u]);
+				const uint32_t i = i0 + 4 * u + grp;
+				if (l == 0 && i < n_s)
+					list[i] = make_key(p.metric_ip ? -acc[u] : acc[u], row[u]);
+			}
+		}
+	};
+	rescore(0);
+	if (TWO && n1 != 0) {
+		asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+		// T = the k-th smallest exact score of the first round (n1 >= r1 >= k keys; not finite: no cut)
+		uint32_t t_ord;
+		if (n1 <= 64) {
+			const uint32_t w[1] = {lane < (int)n1 ? (uint32_t)(list[lane] >> 32) : 0xFFFFFFFFu};
+			t_ord = wave_kth_smallest_u32<1>(w, p.k);
+		} else {
+			uint32_t w[PER];
+#pragma unroll
+			for (int j = 0; j < PER; ++j)
+				w[j] = lane + 64 * j < (int)n1 ? (uint32_t)(list[lane + 64 * j] >> 32) : 0xFFFFFFFFu;
+			t_ord = wave_kth_smallest_u32<PER>(w, p.k);
+		}
+		float cut = __builtin_inff();
+		if (t_ord < 0xFF800000u)
+			cut = i8f_round2_cut(ordered_to_float(t_ord), p.tau_f[qi], p.inv_2s2);
+		// the second round: the others that can still reach T, compacted in place behind the first round's keys (a
+		// key moves towards the front, and every lane has read its key before any lane writes)
+		for (uint32_t i0 = n1; i0 < c; i0 += 64) {
+			const uint32_t i = i0 + lane;
+			const uint64_t key = list[i < c ? i : 0];
+			const bool hit = i < c && !(key_score(key) > cut);
+			const unsigned long long mask = __builtin_amdgcn_ballot_w64(hit);
+			const uint32_t pos = n_s + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
+			                                                      __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+			asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+			if (hit)
+				list[pos] = key;
+			n_s += (uint32_t)__builtin_popcountll(mask);
+		}
+		asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+		rescore(n1);
+	}
+	if (p.rerank_cnt && p.rerank_base && lane == 0)
+		p.rerank_cnt[qo] = (p.slot_map ? p.rerank_cnt[qo] : 0u) + n_s;
 	asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 	if (n_s <= 256)
 		wave_emit_sorted<(PER < 4 ? PER : 4)>(p, list, n_s, qo, lane);
@@ -417,7 +540,7 @@ __device__ inline void select_wave_body(const SelectParams& p, uint32_t qi, uint
 }
 
 // lists of at most 64 * PER keys; WAVES queries per workgroup (PER = 32: one, its list is 16 KB)
-template <int PER, int WAVES, typename TR = float>
+template <int PER, int WAVES, typename TR = float, bool TWO = false>
 __global__ __launch_bounds__(64 * WAVES) void select_wave_kernel(SelectParams p, uint32_t m) {
 	constexpr uint32_t kSelectWaveMax = 64 * PER;
 	__shared__ uint64_t lists[WAVES][kSelectWaveMax];
@@ -429,12 +552,13 @@ __global__ __launch_bounds__(64 * WAVES) void select_wave_kernel(SelectParams p,
 	const uint32_t c = p.cand_cnt ? p.cand_cnt[qi] : p.fixed_count;
 	if (c > kSelectWaveMax || c > p.cap || (c <= p.wave_done && p.wave_done != 0))
 		return;  // longer lists: the next size up; shorter ones: already served
-	select_wave_body<PER, TR>(p, qi, c, lists[wave], lane);
+	select_wave_body<PER, TR, TWO>(p, qi, c, lists[wave], lane);
 }
 
 // One workgroup per query: bitonic sort of the (power-of-two padded) key list in LDS.
 // (select_topk_kernel<float>: the rows behind rerank_base are float; <_Float16>: the rows of an EXPANN_DTYPE_F16 index)
-template <typename TR>
+// (TWO: the wave path's two-round instances, for the int8 filter's lists)
+template <typename TR, bool TWO = false>
 __global__ __launch_bounds__(kBlock) void select_topk_kernel(SelectParams p) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
 	uint64_t* keys = reinterpret_cast<uint64_t*>(smem_raw);
@@ -453,9 +577,9 @@ __global__ __launch_bounds__(kBlock) void select_topk_kernel(SelectParams p) {
 		// short list, the other waves leave
 		if (tid < 64) {
 			if (c <= 512)
-				select_wave_body<8, TR>(p, qi, c, keys, (int)tid);
+				select_wave_body<8, TR, TWO>(p, qi, c, keys, (int)tid);
 			else
-				select_wave_body<32, TR>(p, qi, c, keys, (int)tid);
+				select_wave_body<32, TR, TWO>(p, qi, c, keys, (int)tid);
 		}
 		return;
 	}
@@ -533,6 +657,8 @@ __global__ __launch_bounds__(kBlock) void select_topk_kernel(SelectParams p) {
 			n_rescore = *s_cnt;  // keys are sorted: exactly the first *s_cnt qualify
 			__syncthreads();
 		}
+		if (p.rerank_cnt && tid == 0)
+			p.rerank_cnt[qo] = (p.slot_map ? p.rerank_cnt[qo] : 0u) + n_rescore;
 		uint32_t n2r = 2;
 		while (n2r < n_rescore)
 			n2r <<= 1;

@@ -119,6 +119,9 @@ class GpuBruteForceEngine:
         return kept[:n.value], sc[:n.value]
 
     def set_option(self, name, value):
+        """expann_set_option (include/expann_hip.h lists the names); among them the select's "rerank_rounds"
+        (int8 filter: 2 = two-round exact re-rank, the default; 1 = one round) and "rerank_stats" (1: count the
+        re-scored rows for get_stat("rerank_rows"))."""
         _lib.check(self._h, self._L.expann_set_option(self._h, name.encode(), int(value)))
 
     def set_row_filter(self, allow):
@@ -139,6 +142,7 @@ class GpuBruteForceEngine:
 
     def get_stat(self, name):
         """expann_get_stat: "redo_queries", "redo_candidates", "redo_overflows", "spec_rank" (speculative thresholds);
+        "rerank_rows" (rows the last search's selects re-scored exactly; counted under the option "rerank_stats");
         "filter_active" (0 / 1) and "filter_rows" (rows the row filter allows; n when none is set);
         "base_bytes" (device bytes of the rows themselves: n * dim * element size)."""
         v = C.c_uint64(0)
@@ -321,6 +325,9 @@ class ShardedBruteForceEngine:
         self._check(self._L.expann_sharded_set_exchange_fn(self._h, self._xfn, None))
 
     def set_option(self, name, value):
+        """expann_set_option (include/expann_hip.h lists the names); among them the select's "rerank_rounds"
+        (int8 filter: 2 = two-round exact re-rank, the default; 1 = one round) and "rerank_stats" (1: count the
+        re-scored rows for get_stat("rerank_rows"))."""
         self._check(self._L.expann_sharded_set_option(self._h, name.encode(), int(value)))
 
     def set_profiling(self, enable=True):

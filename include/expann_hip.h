@@ -497,14 +497,22 @@ int expann_sharded_get_profile(expann_sharded* h, int shard, expann_profile* out
  * EXPANN_REDO_BOUND / EXPANN_SELECT_OVERLAP set the starting values): "redo_bound" (1, default: the redo pass filters
  * with the smaller of the proven threshold and the k-th exact score of the failed list; 0: the proven threshold
  * alone) and "select_overlap" (1, default: the select stages of lists beyond 512 keys run on an internal side
- * stream beside the short lists' stage, joined before anything that follows; 0: one stream). */
+ * stream beside the short lists' stage, joined before anything that follows; 0: one stream),
+ * "rerank_rounds" (int8 filter: how the select re-ranks a candidate list exactly.  2 (default): the rows of the 16
+ * (k rounded up to 16) smallest filter keys first, then only the rows whose proven lower bound does not exceed the
+ * k-th exact score of that first round; 1: every row the filter's interval bounds cannot rule out, in one round.
+ * Ids and distances are the same either way; EXPANN_RERANK_ROUNDS sets the starting value),
+ * "rerank_stats" (0 (default); 1: the selects count the rows they re-score exactly, read as the statistic
+ * "rerank_rows" -- adds a counter store per query, two small launches and a host wait to every search, deferred
+ * ones included: for tests and measurements, not for timed runs). */
 int expann_set_option(expann_index* h, const char* name, long value);
 
 /* counters outside expann_profile (whose layout is fixed): "redo_queries" = queries of the last search that the
  * redo pass of the speculative thresholds served (deferred searches: of the searches the last expann_sync
  * checked), "redo_candidates" = the keys the redo lists of those queries held, "redo_overflows" = searches since the handle was made whose failing queries did not fit the redo
  * pass (repeated with proven thresholds: a retry), "spec_rank" = the rank j of the last search's thresholds
- * (= k: proven thresholds), "base_bytes" = bytes of device memory that hold the rows themselves (n * dim * bytes
+ * (= k: proven thresholds), "rerank_rows" = rows of the index the last search's selects (the redo pass's included)
+ * re-scored exactly, counted only under the option "rerank_stats" (else 0), "base_bytes" = bytes of device memory that hold the rows themselves (n * dim * bytes
  * per element, every dtype; 0 before the rows are on the device). */
 int expann_get_stat(expann_index* h, const char* name, uint64_t* out);
 /* the auto rank for k neighbours when the sampled pass reads 1/sample_frac of the rows: the smallest j with
