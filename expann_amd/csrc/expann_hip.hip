@@ -21,19 +21,16 @@
 #include "scan_f32.hpp"
 #include "scan_gemm_bf16.hpp"
 #include "scan_gemm_f16.hpp"
-#include "scan_gemm_f16k.hpp"
 #include "scan_gemm_f16x.hpp"
-#include "scan_gemm_f16y.hpp"
 #include "scan_gemm_f16kx.hpp"
-#include "scan_gemm_f16kl.hpp"
 #include "scan_direct_f16.hpp"
 #include "scan_gemm_i8.hpp"
 #include "scan_gemm_i8q.hpp"
-#include "scan_gemm_i8x.hpp"
 #include "scan_gemm_i8w.hpp"
+#include "scan_gemm_w8.hpp"
+#include "scan_gemm_kl.hpp"
 #include "scan_int8.hpp"
 #include "scan_int8_any.hpp"
-#include "scan_gemm_i8kl.hpp"
 #include "filter_rows.hpp"
 #include "score_ids.hpp"
 #include "select.hpp"
@@ -612,9 +609,9 @@ struct GemmF16Variant {
 	 f16x_wg_per_cu<D>(), gemm_f16x_lds_bytes<D>(), 1, scan_gemm_f16x_kernel<D, false, 0, true>}
 // (d = 64 with two workgroups per CU measured slower than scan_gemm_f16_kernel<64>'s three: 6.55 M vs
 // 6.83 M QPS at 1 M rows -- two k-steps per column leave too little MFMA per step; hence three here too)
-// d = 256 / 512: the 8-waves-per-tile geometry on 16x16x32 (scan_gemm_f16y.hpp), hits appended directly
+// d = 256 / 512: the 8-waves-per-tile geometry on 16x16x32 (scan_gemm_w8.hpp, fp16 instances), hits appended directly
 #define F16Y_V(D)                                                                                  \
-	{D, scan_gemm_f16y_kernel<D, false>, scan_gemm_f16y_kernel<D, true>, sqnorm_kernel<D>, f16_query_prep_kernel<D>, \
+	{D, scan_gemm_w8_kernel<F16Elem, D, false>, scan_gemm_w8_kernel<F16Elem, D, true>, sqnorm_kernel<D>, f16_query_prep_kernel<D>, \
 	 "scan_gemm_f16y<" #D ", false>", kF16TB, F16Geom<D>::WGQ, F16Geom<D>::THREADS, F16Geom<D>::WG_PER_CU, \
 	 gemm_f16_lds_bytes<D>(), 0}
 // 512 < d <= 960: the k-split geometry on 16x16x32 (scan_gemm_f16kx.hpp)
@@ -631,10 +628,10 @@ const GemmF16Variant kGemmF16XDbg[] = {{128, scan_gemm_f16x_kernel<128, false, 1
                                         sqnorm_kernel<128>, f16_query_prep_kernel<128>, "scan_gemm_f16x<128, false>",
                                         kF16TB, kF16TQ, kF16Threads, 2, gemm_f16_lds_bytes<128>(), 1}};
 inline bool f16_choice(long opt) { return opt == 0 || opt == 4 || opt == 6; }
-// the fp16 filter with the dim known at run time (scan_gemm_f16kl.hpp): every f32 dim from 64 up without a
+// the fp16 filter with the dim known at run time (scan_gemm_kl.hpp, fp16 instances): every f32 dim from 64 up without a
 // form of its own (d = 0 here; prelude: sqnorm_any_kernel / f16_query_prep_any_kernel)
-const GemmF16Variant kGemmF16KL = {0, scan_gemm_f16kl_kernel<false>, scan_gemm_f16kl_kernel<true>, nullptr, nullptr,
-                                   "scan_gemm_f16kl", kF16klTB, kF16TQ, kF16Threads, 1, kF16klLds, 1};
+const GemmF16Variant kGemmF16KL = {0, scan_gemm_kl_kernel<F16Elem, false>, scan_gemm_kl_kernel<F16Elem, true>, nullptr, nullptr,
+                                   "scan_gemm_f16kl", kKlTB, kF16TQ, kF16Threads, 1, kKlLds, 1};
 inline bool f16kl_dim(int d) {
 	if (d < 64 || !any_dim_f32(d))
 		return false;
@@ -708,7 +705,7 @@ int ensure_f16(expann_index* h, const GemmF16Variant* gf, hipStream_t st) {
 		h->f16_scale = -1.0f;
 		return EXPANN_OK;
 	}
-	// padded to whole tiles (64 rows; 128 for scan_gemm_f16kl): zero rows whose bn' is NaN (never a candidate)
+	// padded to whole tiles (64 rows; 128 for scan_gemm_kl): zero rows whose bn' is NaN (never a candidate)
 	const size_t tb = (size_t)std::max(kF16TB, gf->tb);
 	const size_t n_pad = (h->n + tb - 1) / tb * tb;
 	const size_t ld = (size_t)f16_ld(h->dim);
@@ -1190,15 +1187,15 @@ struct GemmI8qVariant {
 	void (*scan_w)(GemmI8wParams) = nullptr;
 	int lds_w = 0, threads_w = 0, wg_per_cu_w = 0;
 	void (*sample_w)(GemmI8wParams) = nullptr;  // the sampled pass on the same stream (SAMPLE instance; same launch geometry)
-	// scan_gemm_i8kl.hpp (d = 0): rows per tile, and the preludes that take the dim at run time
+	// scan_gemm_kl.hpp (d = 0): rows per tile, and the preludes that take the dim at run time
 	int tb = kF16TB;
 	SelfI8AnyFn self_any = nullptr;
 	ThetaI8AnyFn theta_any = nullptr;
 };
-// the 16x16x64 kernels of the 8-waves-per-tile geometries (scan_gemm_i8x.hpp): d = 768, and d = 832 / 960 -- rows in
+// the 16x16x64 kernels of the 8-waves-per-tile geometries (scan_gemm_w8.hpp, int8 instances): d = 768, and d = 832 / 960 -- rows in
 // 1024-byte slots -- with DR = d (the zero-padded k-steps are left out); scan and SAMPLE instance
-#define GEMM_I8X_P(D, DQ, MODE, L2F, MN) {D, MODE, scan_gemm_i8x_kernel<DQ, L2F, D>, \
-	scan_gemm_i8x_kernel<DQ, L2F, D, true>, row_self_i8_kernel<D, MODE>, query_theta_i8_kernel<D, MODE>, \
+#define GEMM_I8X_P(D, DQ, MODE, L2F, MN) {D, MODE, scan_gemm_w8_kernel<I8Elem, DQ, false, D, L2F>, \
+	scan_gemm_w8_kernel<I8Elem, DQ, true, D, L2F>, row_self_i8_kernel<D, MODE>, query_theta_i8_kernel<D, MODE>, \
 	"scan_gemm_i8x<" #DQ "," MN ">", DQ, gemm_i8q_lds_bytes<DQ>(), I8qGeom<DQ>::THREADS, I8qGeom<DQ>::WG_PER_CU}
 const GemmI8qVariant kGemmI8x[] = {
     GEMM_I8X_P(768, 768, kU8L2, true, "U8L2"), GEMM_I8X_P(768, 768, kI8L2, true, "I8L2"), GEMM_I8X_P(768, 768, kI8IP, false, "I8IP"),
@@ -1223,9 +1220,9 @@ const GemmI8qVariant kGemmI8F = GEMM_I8W(128, kI8L2, true, "F32L2");
 void (*const kGemmI8FRedo)(GemmI8wParams) = scan_gemm_i8w_kernel<128, true, false, true>;
 #undef GEMM_I8W
 // every other 8-bit dim (multiples of 64 up to 4096): the K-loop form with the dim known at run time
-// (scan_gemm_i8kl.hpp; d = 0 here, rows in the index's own d bytes, 128-row tiles, hit logs)
-#define GEMM_I8KL(MODE, MN) {0, MODE, nullptr, nullptr, nullptr, nullptr, "scan_gemm_i8kl<" MN ">", 0, kI8klLds, kF16Threads, 1, \
-	scan_gemm_i8kl_kernel<false>, kI8klLds, kF16Threads, 1, scan_gemm_i8kl_kernel<true>, kI8klTB, \
+// (scan_gemm_kl.hpp, int8 instances; d = 0 here, rows in the index's own d bytes, 128-row tiles, hit logs)
+#define GEMM_I8KL(MODE, MN) {0, MODE, nullptr, nullptr, nullptr, nullptr, "scan_gemm_i8kl<" MN ">", 0, kKlLds, kF16Threads, 1, \
+	scan_gemm_kl_kernel<I8Elem, false>, kKlLds, kF16Threads, 1, scan_gemm_kl_kernel<I8Elem, true>, kKlTB, \
 	row_self_i8_any_kernel<MODE>, query_theta_i8_any_kernel<MODE>}
 const GemmI8qVariant kGemmI8KL[] = {GEMM_I8KL(kU8L2, "U8L2"), GEMM_I8KL(kI8L2, "I8L2"), GEMM_I8KL(kI8IP, "I8IP")};
 #undef GEMM_I8KL
@@ -3052,7 +3049,7 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 	if ((dtype == EXPANN_DTYPE_F32 || dtype == EXPANN_DTYPE_F16) && f16kl_dim(dim) &&
 	    (hipFuncSetAttribute((const void*)kGemmF16KL.scan, hipFuncAttributeMaxDynamicSharedMemorySize, kGemmF16KL.lds) != hipSuccess ||
 	     hipFuncSetAttribute((const void*)kGemmF16KL.sample, hipFuncAttributeMaxDynamicSharedMemorySize, kGemmF16KL.lds) != hipSuccess)) {
-		g_create_error = "hipFuncSetAttribute(scan_gemm_f16kl_kernel) failed";
+		g_create_error = "hipFuncSetAttribute(scan_gemm_kl_kernel, fp16) failed";
 		hipStreamDestroy(h->stream);
 		delete h;
 		return EXPANN_ERR_HIP;
@@ -3070,7 +3067,7 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 		if (v.d == dim &&
 		    (hipFuncSetAttribute((const void*)v.scan, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds) != hipSuccess ||
 		     hipFuncSetAttribute((const void*)v.sample, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds) != hipSuccess)) {
-			g_create_error = "hipFuncSetAttribute(scan_gemm_i8x_kernel) failed";
+			g_create_error = "hipFuncSetAttribute(scan_gemm_w8_kernel, int8) failed";
 			hipStreamDestroy(h->stream);
 			delete h;
 			return EXPANN_ERR_HIP;
@@ -3096,7 +3093,7 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 			if (v.mode == int_mode &&
 			    (hipFuncSetAttribute((const void*)v.scan_w, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds_w) != hipSuccess ||
 			     hipFuncSetAttribute((const void*)v.sample_w, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds_w) != hipSuccess)) {
-				g_create_error = "hipFuncSetAttribute(scan_gemm_i8kl_kernel) failed";
+				g_create_error = "hipFuncSetAttribute(scan_gemm_kl_kernel, int8) failed";
 				hipStreamDestroy(h->stream);
 				delete h;
 				return EXPANN_ERR_HIP;

@@ -1,8 +1,8 @@
 // scan_gemm_f16.hpp -- the GEMM-form fp32 L2 candidate filter with ONE fp16 product per element
 // on the matrix cores: a third of the MFMA work of the bf16x3 form (scan_gemm_bf16.hpp) and half its
 // tile bytes.  This header holds the analysis and everything the fp16 kernels share; the kernels
-// themselves are scan_gemm_f16x.hpp / f16y / f16kx (v_mfma_f32_16x16x32_f16), and f16kl at the dims known only
-// at run time.
+// themselves are scan_gemm_f16x.hpp (d = 64 / 128), scan_gemm_f16kx.hpp (768 - 960) and the fp16 instances of
+// scan_gemm_w8.hpp (256 / 512) and scan_gemm_kl.hpp (the dims known only at run time), all on v_mfma_f32_16x16x32_f16.
 //
 // Every value is scaled by a per-index power of two s (so that max|x|*s <= 2^15) and rounded
 // once to fp16:  |x*s - fp16(x*s)| <= 2^-11 |x*s| + 2^-25  (normal + subnormal range).  Hence
@@ -201,7 +201,7 @@ __global__ __launch_bounds__(kBlock) void f16_query_prep_kernel(const float* q, 
 	}
 }
 
-// The prelude at a dim known at run time (scan_gemm_f16kl.hpp: the dims without a compiled fp16 form).
+// The prelude at a dim known at run time (scan_gemm_kl.hpp: the dims without a compiled fp16 form).
 // The fp16 copies there have rows of ld = d rounded up to a multiple of 32 elements (whole MFMA k-steps),
 // zero past d; norms and the range check are those of the d real elements.
 // (_Float16 rows take this kernel at every dim: the same FMA chain and reduction as sqnorm_kernel<D>, same bits)
@@ -368,7 +368,7 @@ struct GemmF16Params {
 	// (zero at launch, one cache line each), n_items = the plain launch's grid; nullptr = plain launch
 	uint32_t* work_ctr;
 	uint32_t n_items;
-	// scan_gemm_f16kl_kernel only: MFMA k-steps of 32 elements per row (the fp16 rows' length / 32)
+	// scan_gemm_kl_kernel only: MFMA k-steps of 32 elements per row (the fp16 rows' length / 32)
 	uint32_t ksteps;
 	// scan_gemm_f16x_kernel's REDO instance only, the redo pass of the speculative thresholds: the m query slots are
 	// compact copies of the failing queries; *live_q (low 20 bits) of them are taken -- a workgroup whose query
@@ -529,7 +529,7 @@ static_assert(gemm_f16_lds_bytes<64>() * 3 <= 160 * 1024 &&
 
 // (Rounds 1-2 ran this filter -- full scan and sampled pass -- on v_mfma_f32_32x32x16_f16 in a kernel of this
 // file, scan_gemm_f16_kernel<D, SAMPLE>; since round 3 every fp16 stream is one of the 16 x 16 x 32 kernels
-// scan_gemm_f16x (d = 64 / 128), f16y (256 / 512), f16kx (768 - 960), each with a SAMPLE instance.  What stays
+// scan_gemm_f16x (d = 64 / 128), scan_gemm_w8 (256 / 512), f16kx (768 - 960), each with a SAMPLE instance.  What stays
 // here is what they share: parameters, geometry and LDS budget, the index / query conversions, the hit logs'
 // gather, the thresholds from the sampled pass.)
 

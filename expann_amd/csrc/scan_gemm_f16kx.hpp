@@ -1,17 +1,48 @@
-// scan_gemm_f16kx.hpp -- scan_gemm_f16k.hpp's k-split filter (512 < d <= 960: the k range of a 32-query
-// group split over a pair of waves, 32-row tiles, partial sums handed over through LDS) on
-// v_mfma_f32_16x16x32_f16: same geometry (F16kGeom), LDS map, staging, exchange and queues; the MFMA
-// shape differs (the higher clock the chip holds on 16 x 16 shapes: DESIGN.md 4.4x).  A wave's step is
-// 2 query tiles x 2 row-tile columns x its k-steps of 32 elements; lane l holds query l & 15 of
-// tile tq and row l & 15 of column tc, 16-byte chunk 4 s + (l >> 4); the swizzles of the 32-row
-// form stay conflict-free for 16-row reads (rows r and r + 16 share a swizzle term; within a
-// ds_read_b128 lane group the (row, chunk) pairs {rows 0-3, 12-15: chunk c; rows 4-11: chunk c + 1}
-// land on 16 distinct bank quads for 0- and 128-mod-256 row strides alike).
+// scan_gemm_f16kx.hpp -- the fp16 single-product filter of scan_gemm_f16.hpp for 512 < d <= 960 (d = 768, 832,
+// 960) on v_mfma_f32_16x16x32_f16 (the higher clock the chip holds on 16 x 16 shapes: DESIGN.md 4.4x).
+//
+// Beyond d = 512 the fragments of even 32 queries no longer fit one wave's registers (d = 960: 240 VGPRs), so
+// the k range is SPLIT over a pair of waves (F16kGeom): 8 waves = 4 query groups of 32 x 2 k-halves, 128 queries
+// per workgroup, 32-row tiles.  Wave (g, kh) holds the fragments of group g for its half of the k-steps; the
+// kh = 1 wave hands its partial sums to its partner through LDS (4 KiB per pair, two copies by step parity so
+// that one workgroup barrier per step orders both the tile buffers and the exchange), the kh = 0 wave adds them
+// and runs the epilogue and the candidate queue.  Both waves of a pair sit on the same SIMD (waves w and w + 4).
+// Sum order: theta' + (first half) and (second half) are accumulated separately and added once; the slack
+// gemm_f16_filter_eps(d) covers d roundings at ANY association (see there).
+//
+// A wave's step is 2 query tiles x 2 row-tile columns x its k-steps of 32 elements; lane l holds query l & 15 of
+// tile tq and row l & 15 of column tc, 16-byte chunk 4 s + (l >> 4).  A 1920- or 1664-byte row stride is 128 mod
+// 256, so consecutive rows alternate between the two halves of the 256-byte bank row and the XOR swizzle works on
+// groups of 8 chunks with (row >> 1) & 7; d = 768 (stride 0 mod 256) swizzles 16 chunks with row & 15.  Rows r
+// and r + 16 share a swizzle term, and within a ds_read_b128 lane group the (row, chunk) pairs {rows 0-3, 12-15:
+// chunk c; rows 4-11: chunk c + 1} land on 16 distinct bank quads for 0- and 128-mod-256 row strides alike.
 #pragma once
-#include "scan_gemm_f16k.hpp"
 #include "scan_gemm_f16x.hpp"
 
 namespace expann {
+
+// LDS (d = 960): 2 x 60 KiB tiles + 32 KiB exchange + 4 x 22 queue entries.  The k-steps (of 16 elements here;
+// the kernel pairs them) are split at a multiple of the swizzle group (24/24, 24/28, 28/32 of 48/52/60): the
+// kh = 0 waves, which also run the epilogue, take the smaller share.
+template <int D> struct F16kGeom {
+	static constexpr int THREADS = 512, WAVES = 8, PAIRS = 4;
+	static constexpr int WGQ = 32 * PAIRS;  // queries per workgroup
+	static constexpr int TB = 32;           // rows per tile
+	static constexpr int ROWB = D * 2, CH = ROWB / 16, KS = D / 16;
+	static constexpr bool HALF = ROWB % 256 != 0;
+	static constexpr int SWG = HALF ? 8 : 16;       // chunks per swizzle group
+	static constexpr int NA = SWG / 2;              // k-steps per swizzle group
+	static constexpr int KSA = (KS / 2) / NA * NA;  // k-steps of the kh = 0 waves
+	static constexpr int KSB = KS - KSA;            // ... of the kh = 1 waves
+	static constexpr int TILE_BYTES = TB * ROWB;
+	static constexpr int NBUF = 2;
+	static constexpr int XCH_BYTES = 2 * PAIRS * 4096;
+	static constexpr int FIXED = NBUF * TILE_BYTES + NBUF * 256 + XCH_BYTES + WGQ * 4 + 32;
+	static constexpr int QROOM = (160 * 1024 - FIXED) / (PAIRS * kF16EntryBytes);
+	static constexpr int QCAP = QROOM < 56 ? QROOM : 56;
+	static constexpr int LDS_BYTES = FIXED + PAIRS * QCAP * kF16EntryBytes;
+	static_assert(ROWB % 128 == 0 && KSB >= KSA && KSB - KSA <= NA && QCAP >= 16, "geometry");
+};
 
 // SAMPLE (round 3): the sampled pass on the same stream -- the first-half wave's accumulators start at -bn'
 // (the row term as the MFMA's C operand), after the exchange it keeps the running maximum of g per (query

@@ -123,7 +123,7 @@ __global__ __launch_bounds__(kF16Threads, f16x_wg_per_cu<D>()) void scan_gemm_f1
 	};
 	static_assert(sizeof(QEntry) == kF16EntryBytes, "queue entry size");
 	QEntry* const queue = reinterpret_cast<QEntry*>(bn_slots + NBUF * WAVES * 256) + wave * QCAP;
-	// (behind the queues: WGQ words that held theta' for the flush's keys until round 3 -- the map is shared with f16y)
+	// (behind the queues: WGQ words that held theta' for the flush's keys until round 3 -- the map is shared with scan_gemm_w8.hpp)
 	uint32_t* const fills = reinterpret_cast<uint32_t*>(bn_slots + NBUF * WAVES * 256 + WAVES * QCAP * kF16EntryBytes) + WGQ;
 
 	f16x8 a[4][KS];

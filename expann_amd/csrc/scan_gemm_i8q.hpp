@@ -1,8 +1,8 @@
-// scan_gemm_i8q.hpp -- the 8-bit GEMM-form filter in the geometry of scan_gemm_f16.hpp
-// (256-thread workgroups, two per CU; 64 queries x 64 rows per wave and step; LDS-DMA staging; per-wave
-// hit queues in LDS; one sampled pass for the threshold) on the int8 matrix cores: the analysis and
-// everything the kernels share.  The kernels themselves are scan_gemm_i8w.hpp / scan_gemm_i8x.hpp.
-// (I8qGeom below: d = 768 trades the two-workgroups-per-CU layout for 8 waves on one tile.)
+// scan_gemm_i8q.hpp -- what the 8-bit GEMM-form filters on the int8 matrix cores share: the g-domain analysis
+// below, the parameter structs, geometry and LDS budget, the index / query conversions, and the thresholds from
+// the sampled pass (sample_tau_i8_kernel).  The kernels themselves are scan_gemm_i8w.hpp (d = 128 / 256, hit
+// logs) and the int8 instances of scan_gemm_w8.hpp (d = 768, 1024-byte slots) and scan_gemm_kl.hpp (run-time dim);
+// all work in the geometry of scan_gemm_f16.hpp (LDS-DMA staging, per-wave hit queues in LDS, one sampled pass).
 //
 // Integer arithmetic is exact, so the filter needs no slack and no re-rank.  Everything runs in
 // the "g domain":  g(q, b) = q.b - bp[b],  bp[b] = floor(bias[b] / 2),  bias[b] = sum b^2 (L2
@@ -45,7 +45,16 @@ struct GemmI8qParams {
 	uint32_t n_chunks;
 	uint32_t xcd_map;        // XCD-aware block placement, as GemmF16Params::xcd_map
 	const uint32_t* live_q;  // scan_gemm_i8w_kernel, redo pass (GemmF16Params::live_q): live query slots, or nullptr
-	uint32_t ksteps;         // scan_gemm_i8kl_kernel only: 64-byte MFMA k-steps per row (= dim / 64)
+	uint32_t ksteps;         // scan_gemm_kl_kernel only: 64-byte MFMA k-steps per row (= dim / 64)
+};
+
+// the hit logs (GemmF16Params::log ... of scan_gemm_f16x.hpp) next to the parameters above: the kernels that write per-wave logs
+struct GemmI8wParams {
+	GemmI8qParams q;
+	uint4* log;
+	uint32_t* log_cnt;
+	uint32_t log_cap;
+	uint32_t* lost;
 };
 
 // bp[i] = bias[i] >> 1 for i < n, kI8qPadBp for n <= i < n_pad (bias == nullptr: zeros)
@@ -114,12 +123,6 @@ static_assert(gemm_i8q_lds_bytes<768>() <= 160 * 1024 && gemm_i8q_lds_bytes<1024
                   gemm_i8q_lds_bytes<256>() * 2 <= 160 * 1024 &&
                   gemm_i8q_lds_bytes<128>() * 3 <= 160 * 1024,
               "LDS budget per CU");
-
-// (Rounds 1-2 ran this filter -- full scan and sampled pass -- on v_mfma_i32_32x32x32_i8 in a kernel of this
-// file, scan_gemm_i8q_kernel<D, L2FORM, SAMPLE, DR>; since round 3 every 8-bit stream is one of the 16 x 16 x 64
-// kernels scan_gemm_i8w (d = 128 / 256) and scan_gemm_i8x (d = 768 and the 1024-byte slots of d = 832 / 960),
-// each with a SAMPLE instance.  What stays here is what they share: the g-domain arithmetic above, parameters,
-// geometry and LDS budget, the index / query conversions, the thresholds from the sampled pass.)
 
 // thp[q] = -g_k, g_k the k-th largest of the n_vals class maxima of the SAMPLE pass (fewer than k
 // real values: pass everything); also zeroes the query's list counter.  One wave per query.

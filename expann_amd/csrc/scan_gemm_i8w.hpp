@@ -27,15 +27,6 @@ template <int D> constexpr int gemm_i8w_lds_bytes() {
 static_assert(gemm_i8w_lds_bytes<128>() * 3 <= 160 * 1024 && gemm_i8w_lds_bytes<256>() * 2 <= 160 * 1024,
               "LDS budget per CU");
 
-// the hit logs (GemmF16Params::log ... of scan_gemm_f16x.hpp) next to scan_gemm_i8q's parameters
-struct GemmI8wParams {
-	GemmI8qParams q;
-	uint4* log;
-	uint32_t* log_cnt;
-	uint32_t log_cap;
-	uint32_t* lost;
-};
-
 // SAMPLE (round 3: the threshold pass on the same stream, as scan_gemm_f16x_kernel<D, true>): no thresholds, no
 // candidate path; a lane's accumulators of one tile column belong to ONE row, so the row term enters as the
 // MFMA's C operand -- they start at -bp -- and the epilogue is the running maximum of g = dot - bp per (query

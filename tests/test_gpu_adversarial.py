@@ -1,4 +1,4 @@
-"""Adversarial soundness of the conservative fp16 filter (scan_gemm_f16.hpp / scan_gemm_f16k.hpp).
+"""Adversarial soundness of the conservative fp16 filter (scan_gemm_f16.hpp / scan_gemm_f16kx.hpp).
 
 The filter may only DROP a row when its reference-order score is certainly above the threshold;
 its slack  eps_d (|q|^2 + |b|^2) + abs (|q| + |b|)  is 12.5 % (d <= 256) above the worst case of

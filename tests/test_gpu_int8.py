@@ -162,7 +162,7 @@ def test_gemm_form_int8_queues(oracle, dtype, metric, ometric, d, n, m, k):
     eng.set_option("scan_kernel", 5)
     eng.set_profiling(True)
     _check(oracle, eng, base, queries, k, getattr(oracle, ometric))
-    # (d >= 768: the 16x16x64 form scan_gemm_i8x of the same geometry, scan_gemm_i8x.hpp; d = 128 / 256:
+    # (d >= 768: the 16x16x64 form scan_gemm_i8x of the same geometry, scan_gemm_w8.hpp; d = 128 / 256:
     # scan_gemm_i8w, the 16x16x64 form in scan_gemm_f16x's step structure with hit logs)
     want = "scan_gemm_i8x" if d >= 768 else "scan_gemm_i8w"
     assert eng.get_profile()["scan_kernel"].startswith(want), eng.get_profile()["scan_kernel"]
