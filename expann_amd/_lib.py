@@ -42,7 +42,12 @@ ABI_SYMBOLS = [
     "expann_graph_set_row_filter", "expann_graph_set_row_filter_device", "expann_graph_clear_row_filter",
     "expann_antitopo_set_row_filter", "expann_antitopo_set_row_filter_device",
     "expann_graph_create_f16", "expann_antitopo_set_rows_f16",
+    "expann_graph_set_row_groups", "expann_graph_set_row_groups_device", "expann_graph_clear_row_groups",
+    "expann_graph_search_grouped", "expann_graph_search_grouped_device",
+    "expann_antitopo_set_row_groups", "expann_antitopo_set_row_groups_device",
+    "expann_antitopo_query_grouped", "expann_antitopo_query_grouped_device",
 ]
+GROUP_ANY = 0xFFFFFFFF  # EXPANN_GROUP_ANY: the group a query names to search every row
 
 
 # expann_exchange_fn(ctx, d_send, d_recv, bytes, rank, world, stream) -> 0 = ok
@@ -284,6 +289,25 @@ def load():
         L.expann_antitopo_set_row_filter.argtypes = [vp, vp, sz]
         L.expann_antitopo_set_row_filter_device.restype = C.c_int
         L.expann_antitopo_set_row_filter_device.argtypes = [vp, vp, sz, vp]
+    if hasattr(L, "expann_graph_set_row_groups"):  # (as above: an older build has no row groups)
+        L.expann_graph_set_row_groups.restype = C.c_int
+        L.expann_graph_set_row_groups.argtypes = [vp, vp, sz]
+        L.expann_graph_set_row_groups_device.restype = C.c_int
+        L.expann_graph_set_row_groups_device.argtypes = [vp, vp, sz, vp]
+        L.expann_graph_clear_row_groups.restype = C.c_int
+        L.expann_graph_clear_row_groups.argtypes = [vp]
+        L.expann_graph_search_grouped.restype = C.c_int
+        L.expann_graph_search_grouped.argtypes = [vp, vp, vp, sz, sz, sz, C.c_int, vp, vp, vp]
+        L.expann_graph_search_grouped_device.restype = C.c_int
+        L.expann_graph_search_grouped_device.argtypes = [vp, vp, vp, sz, sz, sz, C.c_int, vp, vp, vp, vp]
+        L.expann_antitopo_set_row_groups.restype = C.c_int
+        L.expann_antitopo_set_row_groups.argtypes = [vp, vp, sz]
+        L.expann_antitopo_set_row_groups_device.restype = C.c_int
+        L.expann_antitopo_set_row_groups_device.argtypes = [vp, vp, sz, vp]
+        L.expann_antitopo_query_grouped.restype = C.c_int
+        L.expann_antitopo_query_grouped.argtypes = [vp, vp, vp, sz, sz, vp, vp]
+        L.expann_antitopo_query_grouped_device.restype = C.c_int
+        L.expann_antitopo_query_grouped_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
     if hasattr(L, "expann_graph_create_f16"):  # (as above: an older build has no binary16 graph rows)
         L.expann_graph_create_f16.restype = C.c_int
         L.expann_graph_create_f16.argtypes = [C.c_int, C.c_int, vp, sz, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(vp)]

@@ -47,9 +47,11 @@ struct expann_graph {
 	uint32_t slots = 0;
 	hipStream_t stream = nullptr;
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
+	hipEvent_t ev2 = nullptr;  // behind the redo launch of a host-buffer grouped search (made at the first one)
 	double last_ms = 0;
 	// One counter slot per search: {overflow flag, first launch's query counter, redo count, redo launch's query
-	// counter, 4 spare}; a search resets its slot in stream order.  Slots [0, kGraphMaxOutstanding) belong to the
+	// counter, and -- grouped searches -- the scan's query counter and the queries walked, scanned, padded}; a search
+	// resets its slot in stream order.  Slots [0, kGraphMaxOutstanding) belong to the
 	// outstanding device-buffer searches (the sync reads them all), the last one to the host-buffer call.
 	DevPtr<uint32_t> d_dev_ctr;            // [kGraphMaxOutstanding + 1][kGraphCtrWords]
 	PinPtr<uint32_t> h_dev_ctr;            // the same, read back
@@ -70,6 +72,17 @@ struct expann_graph {
 	uint32_t n_allowed = 0;
 	long opt_flat_rows = 0;         // "filter_flat_rows": 0 = kGraphFlatRowsAuto
 	uint64_t stat_flat = 0;         // searches answered without a walk
+	// ---- row groups (expann_graph_set_row_groups): every row's label, and the directory made on the host at set
+	// time -- the distinct labels ascending (0xFFFFFFFF left out), their offsets, and each group's rows ascending
+	DevPtr<uint32_t> d_row_groups;  // [n]
+	DevPtr<uint32_t> d_group_keys;  // [n_groups]
+	DevPtr<uint32_t> d_group_off;   // [n_groups + 1]
+	DevPtr<uint32_t> d_group_rows;  // [rows that carry a label other than 0xFFFFFFFF]
+	bool groups_on = false;
+	uint32_t n_groups = 0;
+	// queries of grouped searches by how they were served {walk, scan, pad}: counted in words 5..7 of a search's
+	// counter slot, folded in when the search is checked
+	uint64_t stat_group[3] = {0, 0, 0};
 	// what the drains since the last sync found, and the counters behind expann_graph_get_stat
 	uint64_t pend_redo_queries = 0, pend_overflows = 0;
 	uint64_t stat_redo_queries = 0, stat_redo_overflows = 0, stat_deferred = 0, stat_distcomps = 0;
@@ -93,7 +106,7 @@ using GraphFn = void (*)(GraphSearchParams);
 struct GraphVariant {
 	int d;
 	int mode;       // expann_graph_compression
-	bool filtered;  // the instance that walks under a row filter (THE FILTER RULE, graph_search.hpp)
+	int filtered;   // kFilterNone, kFilterBitmap (THE FILTER RULE, graph_search.hpp) or kFilterGroups (THE GROUP RULE)
 	bool f16;       // the instance over binary16 rows (TR = _Float16)
 	GraphFn fn;
 };
@@ -101,14 +114,19 @@ struct GraphVariant {
 	{D, kGraphF32, F, false, graph_search_kernel<D, kGraphF32, 0, F>},                 \
 	{D, kGraphU8Cast, F, false, graph_search_kernel<D, kGraphU8Cast, 0, F>},           \
 	{D, kGraphRangedQ8, F, false, graph_search_kernel<D, kGraphRangedQ8, 0, F>}
-#define GRAPH_V(D) GRAPH_VF(D, false), GRAPH_VF(D, true)
+#define GRAPH_V(D) GRAPH_VF(D, kFilterNone), GRAPH_VF(D, kFilterBitmap)
 // binary16 rows: the run-time-dim instances serve every dim and mode; d = 128 has compiled instances as well
 #define GRAPH_HF(D, MODE, F) {D, MODE, F, true, graph_search_kernel<D, MODE, 0, F, _Float16>}
-#define GRAPH_H(D, MODE) GRAPH_HF(D, MODE, false), GRAPH_HF(D, MODE, true)
+#define GRAPH_H(D, MODE) GRAPH_HF(D, MODE, kFilterNone), GRAPH_HF(D, MODE, kFilterBitmap)
 const GraphVariant kGraph[] = {GRAPH_V(64),  GRAPH_V(128), GRAPH_V(256), GRAPH_V(512),
                                GRAPH_V(768), GRAPH_V(832), GRAPH_V(960), GRAPH_V(0),
                                GRAPH_H(128, kGraphF32), GRAPH_H(128, kGraphU8Cast), GRAPH_H(128, kGraphRangedQ8),
-                               GRAPH_H(0, kGraphF32), GRAPH_H(0, kGraphU8Cast), GRAPH_H(0, kGraphRangedQ8)};
+                               GRAPH_H(0, kGraphF32), GRAPH_H(0, kGraphU8Cast), GRAPH_H(0, kGraphRangedQ8),
+                               // row groups: d = 128 and the run-time-dim instance, as for binary16 rows
+                               GRAPH_VF(128, kFilterGroups), GRAPH_VF(0, kFilterGroups),
+                               GRAPH_HF(128, kGraphF32, kFilterGroups), GRAPH_HF(128, kGraphU8Cast, kFilterGroups),
+                               GRAPH_HF(128, kGraphRangedQ8, kFilterGroups), GRAPH_HF(0, kGraphF32, kFilterGroups),
+                               GRAPH_HF(0, kGraphU8Cast, kFilterGroups), GRAPH_HF(0, kGraphRangedQ8, kFilterGroups)};
 #undef GRAPH_H
 #undef GRAPH_HF
 #undef GRAPH_V
@@ -126,7 +144,7 @@ void launch_quantize_simple_u8(const TS* in, size_t n_values, uint8_t* out, hipS
 	}
 }
 // the compiled instance of `dim`, else the run-time-dim one (d = 0)
-const GraphVariant* graph_variant(int dim, int mode, bool filtered, bool f16) {
+const GraphVariant* graph_variant(int dim, int mode, int filtered, bool f16) {
 	const GraphVariant* any = nullptr;
 	for (const auto& v : kGraph)
 		if (v.mode == mode && v.filtered == filtered && v.f16 == f16) {
@@ -151,11 +169,11 @@ int graph_dim_error(const char* fn, int dim) {
 	return EXPANN_OK;
 }
 // the instrumented instance (EXPANN_GRAPH_STAMPS=1, d = 128): per-phase shader clocks of a hop
-const GraphVariant kGraphDbg[] = {{128, kGraphF32, false, false, graph_search_kernel<128, kGraphF32, 1>},
-                                  {128, kGraphU8Cast, false, false, graph_search_kernel<128, kGraphU8Cast, 1>},
-                                  {128, kGraphRangedQ8, false, false, graph_search_kernel<128, kGraphRangedQ8, 1>}};
+const GraphVariant kGraphDbg[] = {{128, kGraphF32, kFilterNone, false, graph_search_kernel<128, kGraphF32, 1>},
+                                  {128, kGraphU8Cast, kFilterNone, false, graph_search_kernel<128, kGraphU8Cast, 1>},
+                                  {128, kGraphRangedQ8, kFilterNone, false, graph_search_kernel<128, kGraphRangedQ8, 1>}};
 // the same over binary16 rows (fp32 walk only)
-const GraphVariant kGraphDbgF16 = {128, kGraphF32, false, true, graph_search_kernel<128, kGraphF32, 1, false, _Float16>};
+const GraphVariant kGraphDbgF16 = {128, kGraphF32, kFilterNone, true, graph_search_kernel<128, kGraphF32, 1, kFilterNone, _Float16>};
 const char* const kGraphModeName[] = {"f32", "u8", "q8"};
 
 // min / max of n_values floats, then their quantizer_ranged_q8 bytes and scale_factor / offset (quantize.hpp);
@@ -222,10 +240,7 @@ constexpr uint32_t kGraphCtrWords = 8;          // counter words per search
 // profiles/graph_filter_ab.txt: at 128 000 rows the scan takes 49 ms against the walk's 110 ms, at 256 000 rows
 // 125 ms against 42 ms; the walk overflows its redo capacity up to 32 000 rows).
 constexpr uint32_t kGraphFlatRowsAuto = 128000;
-// min(k, allowed) the scan keeps in LDS; beyond it the search walks.  Not measured: the scan's final ranking reads
-// keys^2 / 64 LDS words per lane and each replacement scans keys / 64, so the bound is held where that work (16 k
-// reads per lane and query) stays small next to scoring the rows.
-constexpr uint32_t kGraphFlatMaxKeys = 1024;
+// (kGraphFlatMaxKeys, the min(k, allowed) the scan keeps in LDS, is graph_search.hpp's: the group kernels decide by it)
 
 // the argument checks of a search, in the order the header documents, all before the device is touched;
 // *empty: m == 0, nothing to do
@@ -314,6 +329,8 @@ int graph_drain(expann_graph* g) {
 		const uint32_t* c = g->h_dev_ctr + (size_t)s * kGraphCtrWords;
 		g->pend_overflows += c[0] != 0;
 		g->pend_redo_queries += c[2];
+		for (int j = 0; j < 3; ++j)  // (zero after any search but a grouped one)
+			g->stat_group[j] += c[5 + j];
 	}
 	g->stat_distcomps = *g->h_dc_total;
 	g->dev_outstanding = 0;
@@ -560,6 +577,135 @@ int graph_set_row_filter(expann_graph* g, const uint32_t* bits, size_t n_words, 
 	return EXPANN_OK;
 }
 
+// ---- row groups (THE GROUP RULE) ---------------------------------------------------------------
+// groups: n labels in host (on_device = false) or device memory, read in the order of `user_st` (nullptr = the
+// handle's own stream).  The directory is made on the host with a stable sort by label -- set time is no hot path --
+// and everything is built aside and swapped in when complete: a failed call leaves the groups as they were.
+int graph_set_row_groups(expann_graph* g, const uint32_t* groups, size_t n, bool on_device, hipStream_t user_st) {
+	if (!g)
+		return EXPANN_ERR_INVALID_ARG;
+	if (!groups)
+		return g->fail(EXPANN_ERR_INVALID_ARG, "row groups: NULL labels");
+	if (n != g->n)
+		return g->fail(EXPANN_ERR_INVALID_ARG, "row groups: " + std::to_string(n) + " labels for " + std::to_string(g->n) + " rows");
+	HIP_TRY(g, hipSetDevice(g->device));
+	// searches in flight still read the old groups: they are waited for (their counters stay for the next sync)
+	HIP_TRY(g, graph_wait_outstanding(g));
+	hipStream_t st = user_st ? user_st : g->stream;
+	std::vector<uint32_t> lab(n);
+	if (on_device) {
+		HIP_TRY(g, hipMemcpyAsync(lab.data(), groups, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
+		HIP_TRY(g, hipStreamSynchronize(st));
+	} else
+		std::memcpy(lab.data(), groups, sizeof(uint32_t) * n);
+	std::vector<uint32_t> order(n);
+	for (size_t v = 0; v < n; ++v)
+		order[v] = (uint32_t)v;
+	std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return lab[a] < lab[b]; });
+	size_t n_rows = n;  // rows labelled 0xFFFFFFFF sort last and belong to no group
+	while (n_rows && lab[order[n_rows - 1]] == kGroupAny)
+		--n_rows;
+	std::vector<uint32_t> keys, off;
+	for (size_t i = 0; i < n_rows; ++i)
+		if (i == 0 || lab[order[i]] != lab[order[i - 1]]) {
+			keys.push_back(lab[order[i]]);
+			off.push_back((uint32_t)i);
+		}
+	off.push_back((uint32_t)n_rows);
+	DevPtr<uint32_t> b_lab, b_keys, b_off, b_rows;
+	HIP_TRY(g, hipMalloc(&b_lab, sizeof(uint32_t) * n));
+	HIP_TRY(g, hipMalloc(&b_keys, sizeof(uint32_t) * std::max<size_t>(keys.size(), 1)));
+	HIP_TRY(g, hipMalloc(&b_off, sizeof(uint32_t) * off.size()));
+	HIP_TRY(g, hipMalloc(&b_rows, sizeof(uint32_t) * std::max<size_t>(n_rows, 1)));
+	HIP_TRY(g, hipMemcpy(b_lab, lab.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+	if (!keys.empty())
+		HIP_TRY(g, hipMemcpy(b_keys, keys.data(), sizeof(uint32_t) * keys.size(), hipMemcpyHostToDevice));
+	HIP_TRY(g, hipMemcpy(b_off, off.data(), sizeof(uint32_t) * off.size(), hipMemcpyHostToDevice));
+	if (n_rows)
+		HIP_TRY(g, hipMemcpy(b_rows, order.data(), sizeof(uint32_t) * n_rows, hipMemcpyHostToDevice));
+	HIP_TRY(g, hipStreamSynchronize(g->stream));
+	std::swap(g->d_row_groups.p, b_lab.p);  // (the old buffers go with the locals)
+	std::swap(g->d_group_keys.p, b_keys.p);
+	std::swap(g->d_group_off.p, b_off.p);
+	std::swap(g->d_group_rows.p, b_rows.p);
+	g->n_groups = (uint32_t)keys.size();
+	g->groups_on = true;
+	return EXPANN_OK;
+}
+
+// the checks of a grouped search behind graph_search_args, in the header's order, before the device is touched
+int graph_grouped_args(expann_graph* g, const void* query_groups) {
+	if (!query_groups)
+		return g->fail(EXPANN_ERR_INVALID_ARG, "NULL query_groups");
+	if (!g->groups_on)
+		return g->fail(EXPANN_ERR_NOT_BUILT, "grouped search: no row groups are set (expann_graph_set_row_groups)");
+	if (g->filter_on)
+		return g->fail(EXPANN_ERR_UNSUPPORTED, "grouped search under a row filter: combining the bitmap with groups is not offered");
+	return EXPANN_OK;
+}
+
+// A grouped search, enqueued on `st` with the counter slot `ctr` and nothing waited for: the slot's reset, the scan
+// launch (the queries group_serve sends to it, and the padding of empty groups), the walk's first launch (the
+// others) and its redo launch as graph_search_plan plans it.  (The scan goes first, not last: the launches are
+// serialised on one stream and write disjoint rows, so the answer is the same; this way the two events around scan +
+// first walk and the one behind the redo launch give expann_graph_last_kernel_ms the sum of all launches while
+// "redo_kernel_ns" stays the redo launch alone, and the redo launch keeps its place right behind the walk.)  `p` names queries and outputs (graph_base_params
+// after graph_ensure_bytes: the walk reads the mode's byte copy of the rows); events: before the
+// launches, after scan + first walk, after the redo launch (when *has_redo).
+int graph_enqueue_grouped(expann_graph* g, GraphSearchParams p, const uint32_t* d_query_groups, int mode, uint32_t* ctr,
+                          hipStream_t st, hipEvent_t* ev, bool* has_redo) {
+	const GraphVariant* gv = graph_variant(g->dim, mode, kFilterGroups, g->rows_f16);
+	if (!gv)
+		return g->fail(EXPANN_ERR_UNSUPPORTED, "no graph kernel for this dim");
+	p.allow_bits = nullptr;
+	p.row_groups = g->d_row_groups;
+	p.query_groups = d_query_groups;
+	p.group_keys = g->d_group_keys;
+	p.group_off = g->d_group_off;
+	p.n_groups = g->n_groups;
+	p.flat_rows = g->opt_flat_rows ? (uint32_t)std::min<long>(g->opt_flat_rows, 0x7FFFFFFFL) : kGraphFlatRowsAuto;
+	p.group_walked = ctr + 5;
+	GraphSearchPlan pl;
+	if (int rc = graph_search_plan(g, gv, p, ctr, &pl))
+		return rc;
+	GraphGroupScanParams s{};
+	s.f.vectors = (const float*)g->d_vectors;
+	s.f.dim = (uint32_t)g->dim;
+	s.f.queries = p.queries;
+	s.f.m = p.m;
+	s.f.k = p.k;
+	s.f.kk = std::min<uint32_t>(p.k, kGraphFlatMaxKeys);
+	s.f.out_ids = p.out_ids;
+	s.f.out_dists = p.out_dists;
+	s.f.out_distcomps = p.out_distcomps;
+	s.f.next_query = ctr + 4;
+	s.f.distcomps_total = p.distcomps_total;
+	s.query_groups = d_query_groups;
+	s.group_keys = g->d_group_keys;
+	s.group_off = g->d_group_off;
+	s.group_rows = g->d_group_rows;
+	s.n_groups = g->n_groups;
+	s.flat_rows = p.flat_rows;
+	s.scanned = ctr + 6;
+	s.padded = ctr + 7;
+	const size_t lds = graph_flat_lds_bytes(s.f.kk, s.f.dim);
+	uint32_t resident = 0;
+	void (*const scan)(GraphGroupScanParams) = g->rows_f16 ? graph_group_scan_kernel<_Float16> : graph_group_scan_kernel<float>;
+	if (int rc = graph_plan(g, (const void*)scan, lds, &resident))
+		return rc;
+	HIP_TRY(g, hipMemsetAsync(ctr, 0, sizeof(uint32_t) * kGraphCtrWords, st));
+	HIP_TRY(g, hipEventRecord(ev[0], st));
+	hipLaunchKernelGGL(scan, dim3((uint32_t)std::min<size_t>(p.m, resident)), dim3(64), lds, st, s);
+	hipLaunchKernelGGL(pl.fn, dim3(pl.grid), dim3(64), pl.lds, st, pl.first);
+	HIP_TRY(g, hipEventRecord(ev[1], st));
+	HIP_TRY(g, hipGetLastError());
+	*has_redo = pl.has_redo;
+	if (pl.has_redo)
+		if (int rc = graph_enqueue_redo(g, pl, st, ev[2]))
+			return rc;
+	return EXPANN_OK;
+}
+
 // EXPANN_GRAPH_STAMPS: a launch's shader clocks, mean over the workgroups of its grid, per hop
 int graph_print_stamps(expann_graph* g, int mode, size_t ef_search, float ms, uint32_t grid, size_t m, const void* d_stamps) {
 	std::vector<unsigned long long> st(8 * (size_t)grid);
@@ -734,6 +880,7 @@ void expann_graph_destroy(expann_graph* g) {
 		if (ev) hipEventDestroy(ev);
 	if (g->ev0) hipEventDestroy(g->ev0);
 	if (g->ev1) hipEventDestroy(g->ev1);
+	if (g->ev2) hipEventDestroy(g->ev2);
 	if (g->stream) hipStreamDestroy(g->stream);
 	delete g;
 }
@@ -786,7 +933,7 @@ int expann_graph_search_mode(expann_graph* g, const float* queries, size_t m, si
 		g->last_ms = 0;
 		return EXPANN_OK;
 	}
-	const GraphVariant* gv = graph_variant(g->dim, mode, g->filter_on, g->rows_f16);
+	const GraphVariant* gv = graph_variant(g->dim, mode, g->filter_on ? kFilterBitmap : kFilterNone, g->rows_f16);
 	if (!gv)
 		return g->fail(EXPANN_ERR_UNSUPPORTED, "no graph kernel for this dim");
 	const bool stamps = std::getenv("EXPANN_GRAPH_STAMPS") != nullptr && g->dim == 128 && !g->filter_on &&
@@ -878,7 +1025,7 @@ int expann_graph_search_device(expann_graph* g, const float* d_queries, size_t m
 		return EXPANN_OK;
 	HIP_TRY(g, hipSetDevice(g->device));
 	const GraphServe serve = graph_serve(g, k);
-	const GraphVariant* gv = graph_variant(g->dim, mode, g->filter_on, g->rows_f16);
+	const GraphVariant* gv = graph_variant(g->dim, mode, g->filter_on ? kFilterBitmap : kFilterNone, g->rows_f16);
 	if (!gv)
 		return g->fail(EXPANN_ERR_UNSUPPORTED, "no graph kernel for this dim");
 	hipStream_t st = stream ? (hipStream_t)stream : g->stream;
@@ -997,6 +1144,133 @@ int expann_graph_clear_row_filter(expann_graph* g) {
 	return EXPANN_OK;
 }
 
+int expann_graph_set_row_groups(expann_graph* g, const uint32_t* groups, size_t n) {
+	return graph_set_row_groups(g, groups, n, false, nullptr);
+}
+
+int expann_graph_set_row_groups_device(expann_graph* g, const uint32_t* d_groups, size_t n, void* stream) {
+	return graph_set_row_groups(g, d_groups, n, true, (hipStream_t)stream);
+}
+
+int expann_graph_clear_row_groups(expann_graph* g) {
+	if (!g)
+		return EXPANN_ERR_INVALID_ARG;
+	if (g->dev_outstanding) {  // (searches enqueued under the groups finish under them)
+		HIP_TRY(g, hipSetDevice(g->device));
+		HIP_TRY(g, graph_wait_outstanding(g));
+	}
+	g->groups_on = false;
+	g->n_groups = 0;
+	g->d_row_groups.reset();
+	g->d_group_keys.reset();
+	g->d_group_off.reset();
+	g->d_group_rows.reset();
+	return EXPANN_OK;
+}
+
+int expann_graph_search_grouped_device(expann_graph* g, const float* d_queries, const uint32_t* d_query_groups, size_t m,
+                                       size_t k, size_t ef_search, int mode, uint64_t* d_ids, float* d_dists,
+                                       uint32_t* d_distcomps, void* stream) {
+	if (!g)
+		return EXPANN_ERR_INVALID_ARG;
+	bool empty = false;
+	if (int rc = graph_search_args(g, d_queries, m, k, ef_search, mode, d_ids, d_dists, &empty))
+		return rc;
+	if (empty)
+		return EXPANN_OK;
+	if (int rc = graph_grouped_args(g, d_query_groups))
+		return rc;
+	HIP_TRY(g, hipSetDevice(g->device));
+	hipStream_t st = stream ? (hipStream_t)stream : g->stream;
+	if (int rc = graph_dev_init(g))
+		return rc;
+	// one set of visited arrays: searches overlap in stream order only
+	if (g->dev_outstanding && st != g->dev_stream)
+		HIP_TRY(g, graph_wait_outstanding(g));
+	if (g->dev_outstanding >= kGraphMaxOutstanding)
+		if (int rc = graph_drain(g))
+			return rc;
+	if (int rc = graph_ensure_bytes(g, mode))  // (before the parameters: they name the byte copy)
+		return rc;
+	GraphSearchParams p = graph_base_params(g, mode, k, ef_search);
+	p.queries = d_queries;
+	p.m = (uint32_t)m;
+	p.out_ids = d_ids;
+	p.out_dists = d_dists;
+	p.out_distcomps = d_distcomps;
+	p.distcomps_total = g->d_dc_total;
+	bool has_redo = false;
+	if (int rc = graph_enqueue_grouped(g, p, d_query_groups, mode, g->d_dev_ctr + (size_t)g->dev_outstanding * kGraphCtrWords,
+	                                   st, g->ev_dev, &has_redo))
+		return rc;
+	g->dev_stream = st;
+	++g->dev_outstanding;
+	++g->stat_deferred;
+	g->dev_timed = true;
+	g->dev_timed_redo = has_redo;
+	return EXPANN_OK;
+}
+
+// host buffers: the same launches on the handle's own stream with the host-buffer calls' counter slot, waited for here
+int expann_graph_search_grouped(expann_graph* g, const float* queries, const uint32_t* query_groups, size_t m, size_t k,
+                                size_t ef_search, int mode, uint64_t* ids, float* dists, uint32_t* distcomps) {
+	if (!g)
+		return EXPANN_ERR_INVALID_ARG;
+	bool empty = false;
+	if (int rc = graph_search_args(g, queries, m, k, ef_search, mode, ids, dists, &empty))
+		return rc;
+	if (empty)
+		return EXPANN_OK;
+	if (int rc = graph_grouped_args(g, query_groups))
+		return rc;
+	HIP_TRY(g, hipSetDevice(g->device));
+	HIP_TRY(g, graph_wait_outstanding(g));  // (one set of visited arrays: device-buffer searches in flight go first)
+	if (int rc = graph_dev_init(g))
+		return rc;
+	if (!g->ev2)
+		HIP_TRY(g, hipEventCreate(&g->ev2));
+	if (int rc = graph_ensure_bytes(g, mode))  // (before the parameters: they name the byte copy)
+		return rc;
+	hipStream_t st = g->stream;
+	DevBuf b_q, b_qg, b_ids, b_d, b_dc;
+	const size_t qb = m * (size_t)g->dim * sizeof(float);
+	HIP_TRY(g, b_q.alloc(qb));
+	HIP_TRY(g, b_qg.alloc(sizeof(uint32_t) * m));
+	HIP_TRY(g, b_ids.alloc(sizeof(uint64_t) * m * k));
+	HIP_TRY(g, b_d.alloc(sizeof(float) * m * k));
+	HIP_TRY(g, b_dc.alloc(sizeof(uint32_t) * m));
+	HIP_TRY(g, hipMemcpyAsync(b_q.p, queries, qb, hipMemcpyHostToDevice, st));
+	HIP_TRY(g, hipMemcpyAsync(b_qg.p, query_groups, sizeof(uint32_t) * m, hipMemcpyHostToDevice, st));
+	GraphSearchParams p = graph_base_params(g, mode, k, ef_search);
+	p.queries = b_q.as<float>();
+	p.m = (uint32_t)m;
+	p.out_ids = b_ids.as<uint64_t>();
+	p.out_dists = b_d.as<float>();
+	p.out_distcomps = b_dc.as<uint32_t>();
+	uint32_t* ctr = g->d_dev_ctr + (size_t)kGraphMaxOutstanding * kGraphCtrWords;
+	uint32_t* h_ctr = g->h_dev_ctr + (size_t)kGraphMaxOutstanding * kGraphCtrWords;
+	hipEvent_t ev[3] = {g->ev0, g->ev1, g->ev2};
+	bool has_redo = false;
+	if (int rc = graph_enqueue_grouped(g, p, b_qg.as<uint32_t>(), mode, ctr, st, ev, &has_redo))
+		return rc;
+	HIP_TRY(g, hipMemcpyAsync(h_ctr, ctr, sizeof(uint32_t) * kGraphCtrWords, hipMemcpyDeviceToHost, st));
+	HIP_TRY(g, hipStreamSynchronize(st));
+	float ms = 0, ms_redo = 0;
+	HIP_TRY(g, hipEventElapsedTime(&ms, g->ev0, g->ev1));
+	if (has_redo)
+		HIP_TRY(g, hipEventElapsedTime(&ms_redo, g->ev1, g->ev2));
+	g->last_ms = (double)ms + (double)ms_redo;
+	for (int j = 0; j < 3; ++j)
+		g->stat_group[j] += h_ctr[5 + j];
+	HIP_TRY(g, hipMemcpy(ids, b_ids.p, sizeof(uint64_t) * m * k, hipMemcpyDeviceToHost));
+	HIP_TRY(g, hipMemcpy(dists, b_d.p, sizeof(float) * m * k, hipMemcpyDeviceToHost));
+	if (distcomps)
+		HIP_TRY(g, hipMemcpy(distcomps, b_dc.p, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
+	if (h_ctr[0])
+		return g->fail(EXPANN_ERR_OVERFLOW, "graph search: candidates queue overflowed its LDS capacity");
+	return EXPANN_OK;
+}
+
 int expann_graph_get_stat(expann_graph* g, const char* name, uint64_t* out) {
 	if (!g)
 		return EXPANN_ERR_INVALID_ARG;
@@ -1019,6 +1293,16 @@ int expann_graph_get_stat(expann_graph* g, const char* name, uint64_t* out) {
 		*out = g->filter_on ? g->n_allowed : g->n;
 	else if (o == "flat_searches")
 		*out = g->stat_flat;
+	else if (o == "groups_active")
+		*out = g->groups_on ? 1 : 0;
+	else if (o == "group_count")  // distinct labels other than 0xFFFFFFFF
+		*out = g->groups_on ? g->n_groups : 0;
+	else if (o == "group_walk_queries")
+		*out = g->stat_group[0];
+	else if (o == "group_scan_queries")
+		*out = g->stat_group[1];
+	else if (o == "group_pad_queries")
+		*out = g->stat_group[2];
 	else if (o == "vector_bytes")  // the device bytes of the rows themselves
 		*out = (uint64_t)g->n * (uint64_t)g->dim * (g->rows_f16 ? 2u : 4u);
 	else
@@ -1389,6 +1673,7 @@ int expann_antitopo_store(expann_antitopo* e, const float* rows, size_t n) {
 	if (!e || (!rows && n))
 		return EXPANN_ERR_INVALID_ARG;
 	e->eng->clear_row_filter();
+	e->eng->clear_row_groups();
 	ANTITOPO_TRY(e, e->eng->store_rows(rows, n));
 	return EXPANN_OK;
 }
@@ -1397,6 +1682,7 @@ int expann_antitopo_store_batched(expann_antitopo* e, const float* rows, size_t 
 	if (!e || (!rows && n))
 		return EXPANN_ERR_INVALID_ARG;
 	e->eng->clear_row_filter();
+	e->eng->clear_row_groups();
 	ANTITOPO_TRY(e, e->eng->store_rows_batched(rows, n, n_serial ? n_serial : 2048));
 	return EXPANN_OK;
 }
@@ -1466,6 +1752,44 @@ int expann_antitopo_set_row_filter_device(expann_antitopo* e, const uint32_t* d_
 	if (!e->eng->graph)
 		return e->fail(EXPANN_ERR_NOT_BUILT, "expann_antitopo_set_row_filter_device before build()");
 	const int rc = e->eng->set_row_filter_device(d_allow_bits, n_words, stream);
+	return rc == EXPANN_OK ? rc : e->fail(rc, expann_graph_last_error(e->eng->graph));
+}
+
+int expann_antitopo_set_row_groups(expann_antitopo* e, const uint32_t* groups_or_NULL, size_t n) {
+	if (!e)
+		return EXPANN_ERR_INVALID_ARG;
+	if (!e->eng->graph)
+		return e->fail(EXPANN_ERR_NOT_BUILT, "expann_antitopo_set_row_groups before build()");
+	const int rc = e->eng->set_row_groups(groups_or_NULL, n);
+	return rc == EXPANN_OK ? rc : e->fail(rc, expann_graph_last_error(e->eng->graph));
+}
+
+int expann_antitopo_set_row_groups_device(expann_antitopo* e, const uint32_t* d_groups, size_t n, void* stream) {
+	if (!e)
+		return EXPANN_ERR_INVALID_ARG;
+	if (!e->eng->graph)
+		return e->fail(EXPANN_ERR_NOT_BUILT, "expann_antitopo_set_row_groups_device before build()");
+	const int rc = e->eng->set_row_groups_device(d_groups, n, stream);
+	return rc == EXPANN_OK ? rc : e->fail(rc, expann_graph_last_error(e->eng->graph));
+}
+
+int expann_antitopo_query_grouped(expann_antitopo* e, const float* queries, const uint32_t* query_groups, size_t m,
+                                  size_t k, uint64_t* ids, float* dists) {
+	if (!e)
+		return EXPANN_ERR_INVALID_ARG;
+	if (!e->eng->graph)
+		return e->fail(EXPANN_ERR_NOT_BUILT, "expann_antitopo_query_grouped before build()");
+	const int rc = e->eng->query_k_batch_grouped(queries, query_groups, m, k, ids, dists);
+	return rc == EXPANN_OK ? rc : e->fail(rc, expann_graph_last_error(e->eng->graph));
+}
+
+int expann_antitopo_query_grouped_device(expann_antitopo* e, const float* d_queries, const uint32_t* d_query_groups,
+                                         size_t m, size_t k, uint64_t* d_ids, float* d_dists, void* stream) {
+	if (!e)
+		return EXPANN_ERR_INVALID_ARG;
+	if (!e->eng->graph)
+		return e->fail(EXPANN_ERR_NOT_BUILT, "expann_antitopo_query_grouped_device before build()");
+	const int rc = e->eng->query_k_batch_grouped_device(d_queries, d_query_groups, m, k, d_ids, d_dists, stream);
 	return rc == EXPANN_OK ? rc : e->fail(rc, expann_graph_last_error(e->eng->graph));
 }
 

@@ -92,7 +92,53 @@ struct GraphSearchParams {
 	// FILTERED instances only (nullptr in unfiltered launches): the row filter, bit v & 31 of word v >> 5 says
 	// whether vertex v may appear in a result; the handle's own copy, zero from n on (THE FILTER RULE below)
 	const uint32_t* allow_bits;
+	// group instances only (THE GROUP RULE below): the label of every row, the group each query names, and the
+	// directory made at set time -- the distinct labels ascending (0xFFFFFFFF left out) with their row counts as
+	// offsets; flat_rows is "filter_flat_rows" resolved; group_walked counts the queries the first launch walks
+	const uint32_t* row_groups;    // [n]
+	const uint32_t* query_groups;  // [m]
+	const uint32_t* group_keys;    // [n_groups]
+	const uint32_t* group_off;     // [n_groups + 1]
+	uint32_t n_groups, flat_rows;
+	uint32_t* group_walked;        // [1] or nullptr
 };
+
+// what a walk instance is filtered by: nothing, the handle's bitmap (THE FILTER RULE), or row groups (THE GROUP RULE)
+constexpr int kFilterNone = 0, kFilterBitmap = 1, kFilterGroups = 2;
+// the group a query names to search every row
+constexpr uint32_t kGroupAny = 0xFFFFFFFFu;
+// min(k, allowed) the exact scan keeps in LDS; beyond it the search walks.  Not measured: the scan's final ranking reads
+// keys^2 / 64 LDS words per lane and each replacement scans keys / 64, so the bound is held where that work (16 k
+// reads per lane and query) stays small next to scoring the rows.
+constexpr uint32_t kGraphFlatMaxKeys = 1024;
+
+// How a query that names group `qg` (not kGroupAny) is served, decided the same way by the walk and by the scan:
+// *gi = the group's place in the directory, *s = its row count (0: no row carries the label).  Wave-uniform: a
+// binary search of the ascending keys.
+// (The bitmap path's graph_serve has a third clause: a scan whose LDS -- 8 bytes x min(k, rows) keys plus 4 x dim for
+// the query -- exceeds the 160 KB a search may take walks instead.  With min(k, rows) <= kGraphFlatMaxKeys and dim <=
+// 4096, the graph path's limit, that is at most 24 KB, so the clause can never hold and is not restated here; "bit for
+// bit the bitmap path" rests on those two limits.)
+constexpr int kGroupServeWalk = 0, kGroupServeScan = 1, kGroupServePad = 2;
+__device__ inline int group_serve(const uint32_t* keys, const uint32_t* off, uint32_t n_groups, uint32_t qg, uint32_t k,
+                                  uint32_t flat_rows, uint32_t* gi, uint32_t* s) {
+	uint32_t lo = 0, hi = n_groups;  // the first key >= qg
+	while (lo < hi) {
+		const uint32_t mid = lo + (hi - lo) / 2;
+		if (keys[mid] < qg)
+			lo = mid + 1;
+		else
+			hi = mid;
+	}
+	*gi = lo;
+	*s = 0;
+	if (lo == n_groups || keys[lo] != qg)
+		return kGroupServePad;
+	const uint32_t rows = off[lo + 1] - off[lo];
+	*s = rows;
+	const uint32_t kk = k < rows ? k : rows;
+	return rows <= flat_rows && kk <= kGraphFlatMaxKeys ? kGroupServeScan : kGroupServeWalk;
+}
 
 struct md_pair {
 	float d;
@@ -550,7 +596,9 @@ template <int D> constexpr int graph_rows_u8() { return D == 0 ? kGraphAnyRows :
 // one differs where the query's bytes are made
 // waves per SIMD the run-time-dim instances are held to: fp32 3, the byte walks 4 (128 registers; left to itself the
 // compiler takes one or two more and loses the fourth wave)
-template <int MODE> constexpr int graph_any_dim_waves() { return MODE != kGraphF32 ? 4 : 3; }
+// (GROUPS: the group instances carry the query's group and the directory's pointers; at the same bound they spill
+// 8-12 bytes per lane to scratch, so they are held to one wave less)
+template <int MODE, bool GROUPS = false> constexpr int graph_any_dim_waves() { return (MODE != kGraphF32 ? 4 : 3) - (GROUPS ? 1 : 0); }
 
 // THE FILTER RULE (FILTERED instances; p.allow_bits is a bitmap over vertex numbers, bit v & 31 of word v >> 5,
 // least significant bit first; bits at and beyond n are ignored: the library keeps its own copy, zero from n on).
@@ -573,12 +621,19 @@ template <int MODE> constexpr int graph_any_dim_waves() { return MODE != kGraphF
 // requests are in flight together: no round trip is added to a hop) and leaves the flag in the SIGN BIT of the
 // neighbour's ndist slot -- distances are >= 0 --, the lane that stores the score keeps that bit, and every reader
 // strips it before it compares or stores.  No LDS, scratch or serial read is added.
+// THE GROUP RULE (kFilterGroups instances; the header states it in full).  p.row_groups[v] is the label of vertex v,
+// p.query_groups[qi] the group query qi names.  A query that names kGroupAny walks as if unfiltered: no label is
+// loaded.  Any other query is walked here only when group_serve says so (the scan kernel serves the rest: a pulled
+// query that is not walk-served is skipped); for it "allowed" means row_groups[v] == its group, and everything else
+// is THE FILTER RULE word for word.  The label request stands where the allow word's does, beside the visited test;
+// a list's padding reads the last row's label.
 // TR: the element type of p.vectors -- float, or _Float16 for a handle made by expann_graph_create_f16.  It covers
 // every read of the rows (entry evaluation, descent, fp32 bottom layer, final re-score of the byte modes); the
 // arithmetic is the float instance's over (float)row, bit for bit (ref_diff, common.hpp).
-template <int D, int MODE, int DBG = 0, bool FILTERED = false, typename TR = float>
-__global__ __launch_bounds__(64, D == 0 ? graph_any_dim_waves<MODE>() : ((MODE != kGraphF32 && D <= 128) ? 4 : 1)) void graph_search_kernel(GraphSearchParams p) {
+template <int D, int MODE, int DBG = 0, int KIND = kFilterNone, typename TR = float>
+__global__ __launch_bounds__(64, (D == 0 ? graph_any_dim_waves<MODE, (KIND == kFilterGroups)>() : ((MODE != kGraphF32 && D <= 128) ? 4 : 1))) void graph_search_kernel(GraphSearchParams p) {
 	constexpr bool COMPRESSED = MODE != kGraphF32, RANGED = MODE == kGraphRangedQ8;
+	constexpr bool FILTERED = KIND != kFilterNone, GROUPS = KIND == kFilterGroups;
 	constexpr int DPL = D ? D / 16 : 1;
 	constexpr int NW = D ? D / 64 : 1;
 	unsigned long long seg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ts = DBG ? clock64() : 0;
@@ -614,6 +669,7 @@ __global__ __launch_bounds__(64, D == 0 ? graph_any_dim_waves<MODE>() : ((MODE !
 		return fresh;
 	};
 	uint32_t overflowed = 0;
+	uint32_t n_walked = 0;  // GROUPS: queries this workgroup walked (wave-uniform; one atomic when it leaves)
 
 	for (;;) {
 		// queries are pulled, not dealt: walks differ in length, and a grid sized to what is resident
@@ -629,6 +685,19 @@ __global__ __launch_bounds__(64, D == 0 ? graph_any_dim_waves<MODE>() : ((MODE !
 			qi = p.query_map[qi];
 		} else if (qi >= p.m)
 			break;
+		uint32_t qgroup = kGroupAny;  // GROUPS: the group this query names; wave-uniform
+		if constexpr (GROUPS) {
+			qgroup = (uint32_t)__builtin_amdgcn_readfirstlane((int)p.query_groups[qi]);
+			if (qgroup != kGroupAny) {
+				uint32_t gi, s;
+				if (group_serve(p.group_keys, p.group_off, p.n_groups, qgroup, p.k, p.flat_rows, &gi, &s) != kGroupServeWalk) {
+					wave_lds_sync();  // (every iteration ends in the wave barrier, as a walked one does)
+					continue;         // the scan kernel's
+				}
+			}
+			++n_walked;
+		}
+		const bool any_group = qgroup == kGroupAny;
 		bool q_overflowed = false;  // wave-uniform: this walk met a full candidates heap
 		// ---- per-query setup ----------------------------------------------------------
 		if (!bits && ++epoch > 255) {  // epoch bytes wrapped: clear this workgroup's visited array
@@ -791,7 +860,9 @@ __global__ __launch_bounds__(64, D == 0 ? graph_any_dim_waves<MODE>() : ((MODE !
 			const md_pair e{d_entry, entry};
 			coop_push<false>(candidates, n_cand, e, lane, p.debug & 1);
 			bool keep_entry = true;  // wave-uniform
-			if constexpr (FILTERED)
+			if constexpr (GROUPS)
+				keep_entry = any_group || p.row_groups[entry] == qgroup;
+			else if constexpr (FILTERED)
 				keep_entry = (p.allow_bits[entry >> 5] >> (entry & 31)) & 1u;
 			if (keep_entry)
 				coop_push<true>(nearest, n_near, e, lane, p.debug & 1);
@@ -822,6 +893,8 @@ __global__ __launch_bounds__(64, D == 0 ? graph_any_dim_waves<MODE>() : ((MODE !
 			uint32_t* nflag = reinterpret_cast<uint32_t*>(ndist);
 			// (a list's padding, UINT32_MAX, reads the last word: it is never fresh, its flag goes nowhere)
 			auto disallowed = [&](uint32_t nb) -> uint32_t {
+				if constexpr (GROUPS)
+					return any_group ? 0u : (p.row_groups[nb < p.n ? nb : p.n - 1] != qgroup ? 0x80000000u : 0u);
 				const uint32_t w = nb >> 5, w_last = (p.n - 1) >> 5;
 				return (~(p.allow_bits[w < w_last ? w : w_last] >> (nb & 31)) & 1u) << 31;
 			};
@@ -997,6 +1070,8 @@ __global__ __launch_bounds__(64, D == 0 ? graph_any_dim_waves<MODE>() : ((MODE !
 			p.epochs[blockIdx.x] = epoch;
 		if (overflowed)
 			atomicAdd(p.error, 1u);
+		if (GROUPS && n_walked && !p.query_map && p.group_walked)
+			atomicAdd(p.group_walked, n_walked);
 	}
 }
 

@@ -158,22 +158,39 @@ class AntitopoEngine:
             self._check(self._L.expann_antitopo_set_compression(self._h, m))
         self._mode = m
 
-    def query_many(self, queries, k):
+    def query_many(self, queries, k, groups=None):
+        """groups: None, or one uint32 per query -- the row group it may return (set_row_groups; _lib.GROUP_ANY:
+        every row)"""
+        if groups is not None and self._h is None:
+            raise _lib.ExpannError(_lib.ERR_NOT_BUILT, "query_many(groups=) before build()")
         q = self._pad(queries)
         ids = np.empty((q.shape[0], k), dtype=np.uint64)
         dists = np.empty((q.shape[0], k), dtype=np.float32)
-        self._check(self._L.expann_antitopo_query(self._h, q.ctypes.data, q.shape[0], k,
-                                                  ids.ctypes.data, dists.ctypes.data))
+        if groups is None:
+            self._check(self._L.expann_antitopo_query(self._h, q.ctypes.data, q.shape[0], k,
+                                                      ids.ctypes.data, dists.ctypes.data))
+            return ids, dists
+        qg = np.ascontiguousarray(groups, dtype=np.uint32).reshape(-1)
+        if qg.size != q.shape[0]:
+            raise ValueError("groups must hold one uint32 per query")
+        self._check(self._L.expann_antitopo_query_grouped(self._h, q.ctypes.data, qg.ctypes.data, q.shape[0], k,
+                                                          ids.ctypes.data, dists.ctypes.data))
         return ids, dists
 
-    def query_many_device(self, q_ptr, m, k, ids_ptr, dists_ptr, stream=0):
+    def query_many_device(self, q_ptr, m, k, ids_ptr, dists_ptr, stream=0, groups_ptr=0):
         """query_many on device buffers, enqueued on `stream` (a hipStream_t as an integer; 0 = the engine's own)
         without waiting for it: q_ptr -> m rows of float32 that ALREADY have the engine's padded `dim` (there is no
         padding on this path), ids_ptr -> uint64 [m][k], dists_ptr -> float32 [m][k], raw device addresses (a torch
         tensor's data_ptr()).  The same sticky ef_search and compression mode as query_many.  The results are valid
-        after sync(); searches of one engine overlap only in stream order."""
+        after sync(); searches of one engine overlap only in stream order.  groups_ptr != 0 -> m uint32 in device
+        memory: the row group each query may return (set_row_groups)."""
         if self._h is None:
             raise _lib.ExpannError(_lib.ERR_NOT_BUILT, "query_many_device() before build()")
+        if groups_ptr:
+            self._check(self._L.expann_antitopo_query_grouped_device(self._h, C.c_void_p(q_ptr), C.c_void_p(groups_ptr),
+                                                                     int(m), int(k), C.c_void_p(ids_ptr),
+                                                                     C.c_void_p(dists_ptr), C.c_void_p(stream or None)))
+            return
         self._check(self._L.expann_antitopo_query_device(self._h, C.c_void_p(q_ptr), int(m), int(k),
                                                          C.c_void_p(ids_ptr), C.c_void_p(dists_ptr),
                                                          C.c_void_p(stream or None)))
@@ -198,6 +215,27 @@ class AntitopoEngine:
         if self._h is None:
             raise _lib.ExpannError(_lib.ERR_NOT_BUILT, "set_row_filter_device() before build()")
         self._check(self._L.expann_antitopo_set_row_filter_device(self._h, C.c_void_p(ptr), int(n_words),
+                                                                  C.c_void_p(stream or None)))
+
+    def set_row_groups(self, groups):
+        """expann_antitopo_set_row_groups: groups[size()] uint32, the group of every row (THE GROUP RULE,
+        include/expann_hip.h); None clears them.  query_many(..., groups=) then lets every query name the group it
+        may return; queries without groups= ignore the labels.  A run-time property: store*, build() and
+        load_index() clear it, and it is not saved with the index."""
+        if self._h is None:
+            raise _lib.ExpannError(_lib.ERR_NOT_BUILT, "set_row_groups() before build()")
+        if groups is None:
+            self._check(self._L.expann_antitopo_set_row_groups(self._h, None, 0))
+            return
+        g = np.ascontiguousarray(groups, dtype=np.uint32).reshape(-1)
+        self._check(self._L.expann_antitopo_set_row_groups(self._h, g.ctypes.data, g.size))
+
+    def set_row_groups_device(self, ptr, n, stream=0):
+        """The same from n uint32 labels in device memory, read in the order of `stream` (a hipStream_t as an
+        integer; 0 = the engine's own)."""
+        if self._h is None:
+            raise _lib.ExpannError(_lib.ERR_NOT_BUILT, "set_row_groups_device() before build()")
+        self._check(self._L.expann_antitopo_set_row_groups_device(self._h, C.c_void_p(ptr), int(n),
                                                                   C.c_void_p(stream or None)))
 
     def sync(self):

@@ -259,6 +259,59 @@ struct gpu_antitopo_engine : public ann_engine<T, gpu_antitopo_engine<T>> {
 		if (graph)
 			(void)expann_graph_clear_row_filter(graph);
 	}
+	// Extension: row groups (THE GROUP RULE, expann_hip.h): a label per row, and searches in which every query names
+	// the group it may return.  Like the row filter a run-time property of the uploaded graph: upload() starts
+	// without groups and they are not written to the index file.  nullptr clears them.  All return the
+	// expann_status (message: expann_graph_last_error(graph)).
+	int set_row_groups(const uint32_t* groups, size_t n) {
+		if (!graph)
+			return EXPANN_ERR_NOT_BUILT;
+		return groups ? expann_graph_set_row_groups(graph, groups, n) : expann_graph_clear_row_groups(graph);
+	}
+	int set_row_groups_device(const uint32_t* d_groups, size_t n, void* stream) {
+		if (!graph)
+			return EXPANN_ERR_NOT_BUILT;
+		return expann_graph_set_row_groups_device(graph, d_groups, n, stream);
+	}
+	void clear_row_groups() {
+		if (graph)
+			(void)expann_graph_clear_row_groups(graph);
+	}
+	// m queries, query i within group query_groups[i] (EXPANN_GROUP_ANY: every row), with the sticky ef_search and
+	// conf.mode() of query_k_batch; distcomps (per query) may be nullptr
+	int query_k_batch_grouped(const float* queries, const uint32_t* query_groups, size_t m, size_t k, uint64_t* ids,
+	                          float* dists, uint32_t* distcomps = nullptr) {
+		if (!graph)
+			return EXPANN_ERR_NOT_BUILT;
+		if (k == 0)
+			return expann_graph_search_grouped(graph, queries, query_groups, m, k, 1, conf.mode(), ids, dists, nullptr);
+		if (!ef_search.has_value())
+			set_ef_search(k * conf.ef_search_mult);  // :858-859
+		std::vector<uint32_t> dc(m);
+		const int rc = expann_graph_search_grouped(graph, queries, query_groups, m, k, ef_search.value(), conf.mode(), ids,
+		                                           dists, dc.data());
+		if (rc != EXPANN_OK)
+			return rc;
+		for (size_t i = 0; i < m; ++i) {
+			num_distcomps += dc[i];
+			if (distcomps)
+				distcomps[i] = dc[i];
+		}
+		return rc;
+	}
+	// the same on device buffers, enqueued on `stream` without waiting; results are valid after sync()
+	int query_k_batch_grouped_device(const float* d_queries, const uint32_t* d_query_groups, size_t m, size_t k,
+	                                 uint64_t* d_ids, float* d_dists, void* stream) {
+		if (!graph)
+			return EXPANN_ERR_NOT_BUILT;
+		if (k == 0)
+			return expann_graph_search_grouped_device(graph, d_queries, d_query_groups, m, k, 1, conf.mode(), d_ids, d_dists,
+			                                          nullptr, stream);
+		if (!ef_search.has_value())
+			set_ef_search(k * conf.ef_search_mult);  // :858-859
+		return expann_graph_search_grouped_device(graph, d_queries, d_query_groups, m, k, ef_search.value(), conf.mode(),
+		                                          d_ids, d_dists, nullptr, stream);
+	}
 	// expann_graph_sync; the distance evaluations the device counted since the last sync go to num_distcomps
 	int sync() {
 		if (!graph)

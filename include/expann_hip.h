@@ -343,7 +343,8 @@ int expann_graph_set_option(expann_graph* g, const char* name, long value);
  * "redo_overflows" = searches since create that ended in EXPANN_ERR_OVERFLOW; "deferred_searches" = device-buffer
  * searches since create; "distcomps" = distance evaluations of all device-buffer searches since create, as of the
  * last sync; "redo_kernel_ns" = device time of the last search's redo launch, as of the last sync;
- * "filter_active", "filter_rows", "flat_searches": see expann_graph_set_row_filter.  An unknown name is
+ * "filter_active", "filter_rows", "flat_searches": see expann_graph_set_row_filter; "groups_active", "group_count",
+ * "group_walk_queries", "group_scan_queries", "group_pad_queries": see expann_graph_set_row_groups.  An unknown name is
  * EXPANN_ERR_INVALID_ARG. */
 int expann_graph_get_stat(expann_graph* g, const char* name, uint64_t* out);
 
@@ -544,7 +545,7 @@ uint32_t expann_spec_rank_auto(size_t k, uint32_t sample_frac);
  * runs the exact direct scan, as do queries outside the fp16 range).
  * expann_sharded_* does not offer the filter (its set_option pass-through is unchanged and there is no
  * sharded entry point for it); a per-query filter is not offered either.  The graph engine has a row filter of its
- * own: expann_graph_set_row_filter, below.
+ * own: expann_graph_set_row_filter, below, and a per-query form of it: expann_graph_set_row_groups.
  * expann_get_stat: "filter_active" (0 / 1), "filter_rows" (allowed rows; n when no filter is set). */
 int expann_set_row_filter(expann_index* h, const uint32_t* allow_bits, size_t n_words);        /* host bits   */
 int expann_set_row_filter_device(expann_index* h, const uint32_t* d_allow_bits, size_t n_words, void* stream);
@@ -596,7 +597,8 @@ int expann_clear_row_filter(expann_index* h);
  * EXPANN_ERR_NOT_BUILT.  expann_antitopo_store*, _build and _load clear the filter: it is a run-time property and is
  * not written to the index file.  expann_antitopo_set_row_filter_device takes device bits as
  * expann_graph_set_row_filter_device does.
- * Not offered: per-query filters, a filter for expann_graph_build_batched's searches, deleting rows. */
+ * Not offered: a filter for expann_graph_build_batched's searches, deleting rows.  (Per query: row groups, at the
+ * end of this header.) */
 int expann_graph_set_row_filter(expann_graph* g, const uint32_t* allow_bits, size_t n_words);
 int expann_graph_set_row_filter_device(expann_graph* g, const uint32_t* d_allow_bits, size_t n_words, void* stream);
 int expann_graph_clear_row_filter(expann_graph* g);
@@ -630,6 +632,68 @@ int expann_graph_create_f16(int dim, int device, const void* rows_f16, size_t n,
                             uint32_t starting_vertex, const uint64_t* layer_offsets, const uint32_t* neighbours,
                             expann_graph** out);
 int expann_antitopo_set_rows_f16(expann_antitopo* e, int on);
+
+/* Row groups of the graph engine: every query of a batch names the rows it may return (appended; EXPANN_ABI_VERSION
+ * stays 2: nothing that existed changed).
+ * THE GROUP RULE.  groups[v] is the group of vertex v and may be any uint32.  Query i of a grouped search may return
+ * exactly the vertices with groups[v] == query_groups[i].  A query that names EXPANN_GROUP_ANY may return every
+ * vertex: for it the search is the unfiltered search bit for bit -- ids, distance bits and distcomps, in all three
+ * modes.  A row labelled 0xFFFFFFFF therefore belongs to no group: only ANY queries return it.
+ * Let s_i be the number of rows in query i's group and F the option "filter_flat_rows" (0 = auto = 128 000: the row
+ * filter's option, with the same meaning).  Each query is served on its own:
+ *   s_i == 0 (a group that no row carries): padding with UINT64_MAX / +inf, distcomps 0.
+ *   s_i <= F and min(k, s_i) <= 1024 (scan): the exact fp32 scan of the group's rows -- what SPARSE FILTERS ARE
+ *   SCANNED above returns for a bitmap of the same rows, in every mode: the min(k, s_i) smallest by (distance, id),
+ *   ascending and padded, distcomps = s_i.
+ *   otherwise (walk): THE FILTER RULE's walk with "allowed" meaning groups[v] == query_groups[i].  Descent, stop rule,
+ *   neighbour update, pre-drop, distcomps and output are word for word the same; the redo launch and
+ *   EXPANN_ERR_OVERFLOW behave as under a bitmap.
+ * So for a fixed group X the grouped answer is what expann_graph_set_row_filter(bits of groups == X) plus the plain
+ * search give at the same "filter_flat_rows", bit for bit, distcomps included.
+ * The plain searches (expann_graph_search, _mode, _device, expann_antitopo_query*) ignore the groups entirely and
+ * launch the kernel instances they launch without them.
+ * Set calls.  They first wait on the host for outstanding device-buffer searches (their counters stay for the next
+ * expann_graph_sync), so every search runs under the groups that were in force when it was enqueued.  The library
+ * keeps its own copy -- the labels, and a directory of the distinct labels with each group's rows, made on the host --
+ * so the caller may free its array on return.  expann_graph_set_row_groups_device reads d_groups in the order of
+ * `stream` (a hipStream_t; NULL = the handle's own) and returns after that stream and the handle's own have drained.
+ * Errors, before the device is touched: handle or array NULL EXPANN_ERR_INVALID_ARG; n != the handle's row count
+ * EXPANN_ERR_INVALID_ARG.  A failed call leaves the groups as they were.  expann_graph_clear_row_groups drops them.
+ * Grouped searches.  The checks are expann_graph_search_mode's, in its order (m == 0 is EXPANN_OK); then query_groups
+ * NULL EXPANN_ERR_INVALID_ARG; then no groups set EXPANN_ERR_NOT_BUILT; then a row filter in force
+ * EXPANN_ERR_UNSUPPORTED -- all before the device is touched.  expann_graph_search_grouped_device keeps
+ * expann_graph_search_device's promises: it enqueues on `stream` -- the counter reset, the scan of the scan-served
+ * queries, the walk of the others and its redo launch -- and returns without waiting; in steady state it makes no
+ * allocation, host/device copy, attribute query or synchronisation; expann_graph_sync reports.
+ * expann_graph_search_grouped (host buffers) enqueues the same launches and waits.  expann_graph_last_kernel_ms is
+ * the sum of the grouped search's launches.
+ * expann_graph_get_stat: "groups_active" (0 / 1); "group_count" (distinct labels other than 0xFFFFFFFF);
+ * "group_walk_queries", "group_scan_queries", "group_pad_queries" (queries of grouped searches since create, by how
+ * they were served; counted on the device and folded in when a search is checked: on return of the host-buffer call,
+ * or at expann_graph_sync).
+ * expann_antitopo_set_row_groups is the same on the engine's graph (a NULL array clears the groups; before build()
+ * EXPANN_ERR_NOT_BUILT; _set_row_groups_device takes device labels as expann_graph_set_row_groups_device does);
+ * expann_antitopo_query_grouped / _device search with the engine's ef_search and compression.
+ * expann_antitopo_store*, _build and _load clear the groups: they are a run-time property and are not written to
+ * the index file.
+ * Not offered: a grouped search while a row filter is in force (bitmap x groups), several groups per row or a set
+ * of groups per query, groups for expann_graph_build_batched's searches, groups on the brute-force and sharded
+ * handles. */
+#define EXPANN_GROUP_ANY 0xFFFFFFFFu
+int expann_graph_set_row_groups(expann_graph* g, const uint32_t* groups, size_t n);            /* host [n] */
+int expann_graph_set_row_groups_device(expann_graph* g, const uint32_t* d_groups, size_t n, void* stream);
+int expann_graph_clear_row_groups(expann_graph* g);
+int expann_graph_search_grouped(expann_graph* g, const float* queries, const uint32_t* query_groups, size_t m,
+                                size_t k, size_t ef_search, int mode, uint64_t* ids, float* dists, uint32_t* distcomps);
+int expann_graph_search_grouped_device(expann_graph* g, const float* d_queries, const uint32_t* d_query_groups,
+                                       size_t m, size_t k, size_t ef_search, int mode, uint64_t* d_ids,
+                                       float* d_dists, uint32_t* d_distcomps, void* stream);
+int expann_antitopo_set_row_groups(expann_antitopo* e, const uint32_t* groups_or_NULL, size_t n);
+int expann_antitopo_set_row_groups_device(expann_antitopo* e, const uint32_t* d_groups, size_t n, void* stream);
+int expann_antitopo_query_grouped(expann_antitopo* e, const float* queries, const uint32_t* query_groups,
+                                  size_t m, size_t k, uint64_t* ids, float* dists);
+int expann_antitopo_query_grouped_device(expann_antitopo* e, const float* d_queries, const uint32_t* d_query_groups,
+                                         size_t m, size_t k, uint64_t* d_ids, float* d_dists, void* stream);
 
 #ifdef __cplusplus
 }
