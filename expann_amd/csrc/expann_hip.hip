@@ -156,6 +156,8 @@ struct expann_index {
 	DevPtr<void> d_base_i8f;         // [n padded to 64][dim] int8
 	DevPtr<int> d_bp_i8f;            // [n padded] integer row terms; kI8qPadBp on the padding
 	DevPtr<float> d_rw_i8f;          // [n] w_b (select pruning), +inf where bp was clamped
+	DevPtr<int> d_cb_i8f;            // [n padded] centre row terms of the int8 sampled pass; kI8fCbNone: no such row
+	DevPtr<float> d_wbmax_i8f;       // [1] the largest w_b among the rows with a centre term
 	DevPtr<float> d_i8f_q;           // [3][m_alloc]: A_q, W_q (prelude), w_q (thresholds)
 	GrowPtr<void> d_q8f;             // [m][dim] int8 queries
 	size_t i8f_q_m = 0;
@@ -204,6 +206,8 @@ struct expann_index {
 	uint64_t stat_redo_overflows = 0;  // searches whose failing queries (or redo lists) did not fit the redo pass
 	uint64_t stat_spec_rank = 0;     // j of the last search's thresholds (= k: proven thresholds)
 	long opt_i8_filter = 1;          // fp32 L2 d = 128: the int8 filter (scan_gemm_i8f.hpp): 0 off, 1 auto, 2 wherever supported
+	long opt_i8_sample = 1;          // its sampled pass on int8 too: 0 off, 1 where it speculates at the auto rank, 2 wherever it speculates
+	uint64_t stat_i8_sample = 0;     // 1: the last search's sampled pass ran on int8
 	long opt_scan_kernel = 0;        // 0 auto, 1 direct (scan_filter), 2 GEMM form on fp32 / int8
 	                                 // MFMA, 3 GEMM form on bf16 MFMA with the 3-term split
 	// profiling
@@ -944,7 +948,7 @@ inline SelectTopkFn select_topk_fn(const expann_index* h, const SelectParams& se
 		return select_topk_kernel<float, true>;
 	return f16_rows(h) ? select_topk_kernel<_Float16> : select_topk_kernel<float>;
 }
-// The select of a full scan's lists: the statistics sum, the wave stages, the left-over launch.
+// The select of a full scan's lists: the wave stages, the left-over launch, the statistics sum.
 // When a second wave stage is launched at all (longest > 512) and "select_overlap" allows it, everything but the
 // <8,4> stage goes to the handle's side stream: forked behind the gather by one event, joined into `st` by another
 // before this returns -- whatever follows on `st` (the redo pass, the flag copy, the next search) sees every
@@ -963,10 +967,12 @@ int launch_select(expann_index* h, SelectParams& sel, size_t m, uint32_t cap, hi
 		HIP_TRY(h, hipStreamWaitEvent(side, h->side_ev[0], 0));
 	}
 	const hipStream_t st2 = side ? side : st;
-	if (sum_counts)  // statistics: candidates of the full scan (i8f_cand_limit)
-		hipLaunchKernelGGL(sum_u32_kernel, dim3(1), dim3(1024), 0, st2, sel.cand_cnt, (uint32_t)m, h->d_total);
 	launch_select_wave(sel, m, cap, st, longest, f16_rows(h), side);
 	hipLaunchKernelGGL(select_topk_fn(h, sel), dim3((uint32_t)m), dim3(kBlock), sizeof(uint64_t) * cap + 16, st2, sel);
+	// statistics: candidates of the full scan (i8f_cand_limit).  LAST on the side stream: one 1 024-thread workgroup that
+	// runs 35 us beside the <8,4> stage (5 us alone), and in front of the <16,2> stage it made the side chain the span
+	if (sum_counts)
+		hipLaunchKernelGGL(sum_u32_kernel, dim3(1), dim3(1024), 0, st2, sel.cand_cnt, (uint32_t)m, h->d_total);
 	HIP_TRY(h, hipGetLastError());
 	if (side) {
 		HIP_TRY(h, hipEventRecord(h->side_ev[1], side));
@@ -1251,6 +1257,10 @@ const GemmI8qVariant* pick_gemm_i8q(const expann_index* h, size_t m, size_t k) {
 
 // int8 filter of fp32 rows: clip of the scale (s = min(max |x|, kI8fClipRms rms) / 127)
 constexpr double kI8fClipRms = 5.5;
+// ... and the share of the index's energy below which the components within that clip, not all of them, set the rms
+// (ensure_i8f): far below anything rows of one population give (tests' 10 rows x 50 plus 200 components up to 200
+// among 40 000 rows: 0.47)
+constexpr double kI8fTrimEnergy = 1.0 / 16.0;
 // its lists over the expectation 1.2 x rank x frac per query on iid rows, rank = k or the speculative threshold's j
 // (C2: 501.3 at rank 10 = 2.61 x, 214.6 at rank 4 = 2.79 x; the fp16 form measures 176.5 and 69.9): the select's
 // stages are sized by it
@@ -1315,8 +1325,27 @@ int ensure_i8f(expann_index* h, hipStream_t st) {
 	float maxabs;
 	std::memcpy(&sumsq, hb, 8);
 	std::memcpy(&maxabs, hb + 8, 4);
-	const double rms = std::sqrt(sumsq / (double)nv);
-	const float clip = (float)std::min<double>(maxabs, kI8fClipRms * rms);
+	double rms = std::sqrt(sumsq / (double)nv);
+	float clip = (float)std::min<double>(maxabs, kI8fClipRms * rms);
+	if (maxabs > clip && std::isfinite(clip) && clip > 0.0f) {
+		// a few far-out rows may carry nearly all the energy (eight rows of 1e4 x N(0, 1) among 266 240 of N(0, 1): rms
+		// 54, a scale 50 x too coarse for every other row, whose lists then overflow on every search): where the
+		// components within the clip hold less than kI8fTrimEnergy of it, the scale comes from THEIR rms -- the
+		// far-out rows are clipped (or their row term clamped) and always re-scored, as any clipped row is
+		HIP_TRY(h, hipMemsetAsync(tmp.p, 0, 16, st));
+		hipLaunchKernelGGL(i8f_trimmed_stats_kernel, dim3(2048), dim3(kBlock), 0, st, (const float*)h->d_base, nv, clip,
+		                   tmp.as<double>(), reinterpret_cast<unsigned long long*>(tmp.as<double>() + 1));
+		HIP_TRY(h, hipMemcpyAsync(hb, tmp.p, 16, hipMemcpyDeviceToHost, st));
+		HIP_TRY(h, hipStreamSynchronize(st));
+		double sumsq_in;
+		unsigned long long n_in;
+		std::memcpy(&sumsq_in, hb, 8);
+		std::memcpy(&n_in, hb + 8, 8);
+		if (n_in > 0 && sumsq_in < kI8fTrimEnergy * sumsq) {
+			rms = std::sqrt(sumsq_in / (double)n_in);
+			clip = (float)std::min<double>(maxabs, kI8fClipRms * rms);
+		}
+	}
 	if (!(clip > 0.0f) || !std::isfinite(clip) || !std::isfinite(rms) || !std::isfinite(bnmax)) {
 		h->i8f_state = -1;
 		return EXPANN_OK;
@@ -1326,12 +1355,19 @@ int ensure_i8f(expann_index* h, hipStream_t st) {
 	HIP_TRY(h, hipMalloc(&h->d_base_i8f, n_pad * (size_t)h->dim));
 	HIP_TRY(h, hipMalloc(&h->d_bp_i8f, sizeof(int) * n_pad));
 	HIP_TRY(h, hipMalloc(&h->d_rw_i8f, sizeof(float) * h->n));
+	HIP_TRY(h, hipMalloc(&h->d_cb_i8f, sizeof(int) * n_pad));
+	HIP_TRY(h, hipMalloc(&h->d_wbmax_i8f, sizeof(float)));
 	HIP_TRY(h, hipMemsetAsync(h->d_base_i8f, 0, n_pad * (size_t)h->dim, st));
-	hipLaunchKernelGGL(i8q_bp_kernel, dim3((uint32_t)((n_pad + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-	                   (const int*)nullptr, (uint32_t)h->n, (uint32_t)n_pad, h->d_bp_i8f.as<int>());
+	HIP_TRY(h, hipMemsetAsync(h->d_wbmax_i8f, 0, sizeof(float), st));
+	static_assert(kI8fCbNone == kI8qPadBp, "the padding's row term serves both passes");
+	for (int* terms : {h->d_bp_i8f.as<int>(), h->d_cb_i8f.as<int>()})  // (the padding: kI8qPadBp)
+		hipLaunchKernelGGL(i8q_bp_kernel, dim3((uint32_t)((n_pad + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+		                   (const int*)nullptr, (uint32_t)h->n, (uint32_t)n_pad, terms);
 	hipLaunchKernelGGL(i8f_rows_kernel<128>, dim3((uint32_t)((h->n + kRowsPerGroup - 1) / kRowsPerGroup)), dim3(kBlock), 0,
 	                   st, (const float*)h->d_base, (uint32_t)h->n, h->i8f, h->d_base_i8f.as<int8_t>(),
-	                   h->d_bp_i8f.as<int>(), h->d_rw_i8f.as<float>());
+	                   h->d_bp_i8f.as<int>(), h->d_rw_i8f.as<float>(), h->d_cb_i8f.as<int>());
+	hipLaunchKernelGGL(i8f_wbmax_kernel, dim3(1024), dim3(kBlock), 0, st, h->d_rw_i8f.as<const float>(), h->d_cb_i8f.as<const int>(),
+	                   (uint32_t)h->n, reinterpret_cast<uint32_t*>(h->d_wbmax_i8f.as<float>()));
 	HIP_TRY(h, hipGetLastError());
 	h->i8f_state = 1;
 	return EXPANN_OK;
@@ -1769,6 +1805,58 @@ int sampled_pass_f16(expann_index* h, const GemmF16Variant* gvf, size_t m, size_
 		t_want = std::max<uint32_t>(t_want, (uint32_t)std::min<double>(nt, std::ceil(8.0 * (double)k / (gvf->tb * dens))));
 	const uint32_t t_sel = t_want / run * run;
 	const uint32_t nqt = (uint32_t)((m + gvf->wgq - 1) / gvf->wgq);
+	// A speculating int8-filter search: the sampled pass on the int8 matrix cores too (scan_gemm_i8f.hpp, "Sampled
+	// pass on int8"; option "i8_sample") -- the SAMPLE instance of the full scan's kernel over the same tiles, centre
+	// row terms in place of bp, chunks as search_i8q picks them (C2: 19, 608 class maxima and the <16> tau instance;
+	// capped at 16 to keep the <8> instance the step measured the same, 1.368-1.371 against 1.367-1.373 ms).  tau_s is
+	// an estimate the select checks; the proven tau for the redo pass comes from the same maxima.
+	if (i8f && spec_ok && !filt && gvf->tb == kF16TB && gvf->wgq == kF16TQ && h->opt_i8_sample > 0 &&
+	    (h->opt_i8_sample == 2 || h->opt_spec_rank == 0)) {
+		const uint32_t j = h->opt_spec_rank > 0 ? (uint32_t)std::min<size_t>((size_t)h->opt_spec_rank, k)
+		                                        : spec_rank_auto(k, (double)t_sel / (double)nt);
+		uint32_t ic = std::max<uint32_t>(1, ((uint32_t)kGemmI8F.wg_per_cu_w * (uint32_t)cus) / nqt);
+		ic = std::max<uint32_t>(ic, (uint32_t)((8 * k + 31) / 32));
+		ic = std::min<uint32_t>(ic, std::min<uint32_t>(64, t_sel / 4));
+		if (j < k && t_sel * 2 <= nt && (size_t)ic * 32 >= 8 * k) {
+			GemmI8wParams wsp{};
+			GemmI8qParams& sp = wsp.q;
+			sp.base = h->d_base_i8f;
+			sp.bp = h->d_cb_i8f;
+			sp.n_rows = (uint32_t)h->n;
+			sp.n_tiles_sel = t_sel;
+			sp.tile_stride = nt / t_sel;
+			sp.tile_run = run;
+			sp.tiles_per_block = (t_sel + ic - 1) / ic;
+			ic = (t_sel + sp.tiles_per_block - 1) / sp.tiles_per_block;
+			const int ri = ensure_sample(m * (size_t)ic * 32 * sizeof(int));
+			if (ri != EXPANN_OK)
+				return ri;
+			sp.n_qtiles = nqt;
+			sp.queries = h->d_q8f;
+			sp.m = (uint32_t)m;
+			sp.sample_out = h->d_sample.as<int>();
+			sp.n_chunks = ic;
+			sp.ksteps = (uint32_t)h->dim / 64;
+			hipLaunchKernelGGL(kGemmI8F.sample_w, dim3(ic * nqt), dim3((uint32_t)kGemmI8F.threads_w), kGemmI8F.lds_w, st, wsp);
+			SampleTauI8cParams cp{};
+			cp.t = tp;
+			cp.t.n_vals = ic * 32;
+			cp.t.j = j;
+			cp.t.tau_s = h->d_tau_s;
+			cp.vals = h->d_sample.as<const int>();
+			cp.wb_max = h->d_wbmax_i8f;
+			cp.two_s2 = 2.0 * (double)h->i8f.s * (double)h->i8f.s;
+			hipLaunchKernelGGL(cp.t.n_vals <= 512 ? sample_tau_i8c_kernel<8>
+			                                      : (cp.t.n_vals <= 1024 ? sample_tau_i8c_kernel<16> : sample_tau_i8c_kernel<32>),
+			                   dim3((uint32_t)((m + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0, st, cp);
+			HIP_TRY(h, hipGetLastError());
+			*spec_j = j;
+			*done = true;
+			*i8f_done = true;
+			h->stat_i8_sample = 1;
+			return EXPANN_OK;
+		}
+	}
 	uint32_t chunks = std::max<uint32_t>(1, ((uint32_t)gvf->wg_per_cu * (uint32_t)cus) / nqt);
 	chunks = std::max<uint32_t>(chunks, (uint32_t)((8 * k + live_res - 1) / std::max(1u, live_res)));
 	chunks = std::min<uint32_t>(chunks, std::min<uint32_t>(64, t_sel / 4));
@@ -2258,6 +2346,7 @@ int SearchPass::plan_thresholds() {
 	theta_ready = false;
 	i8f_ready = false;
 	spec_j = 0;
+	h->stat_i8_sample = 0;
 	if (gvf && h->opt_sample_pass && levels.size() >= 2) {
 		// (speculation: the scan_gemm_f16x / i8w streams -- the kernels with the redo pass's early exit --, batches
 		// beyond the latency mode's, no debug instance)
@@ -3018,6 +3107,8 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 		h->opt_rerank_rounds = std::atol(e) == 1 ? 1 : 2;
 	if (const char* e = std::getenv("EXPANN_I8_FILTER"))
 		h->opt_i8_filter = std::min(2L, std::max(0L, std::atol(e)));  // (as set_option)
+	if (const char* e = std::getenv("EXPANN_I8_SAMPLE"))
+		h->opt_i8_sample = std::min(2L, std::max(0L, std::atol(e)));  // (as set_option)
 	if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&h->stream) != hipSuccess) {
 		g_create_error = "hipSetDevice/hipStreamCreate failed";
 		delete h;
@@ -3215,6 +3306,8 @@ int expann_set_base_device(expann_index* h, const void* d_rows, size_t n, uint64
 	h->d_base_i8f.reset();
 	h->d_bp_i8f.reset();
 	h->d_rw_i8f.reset();
+	h->d_cb_i8f.reset();
+	h->d_wbmax_i8f.reset();
 	h->i8f_state = 0;
 	if (h->d_base_i8q && h->base_i8q_owned)
 		hipFree(h->d_base_i8q);
@@ -3581,6 +3674,8 @@ int expann_get_stat(expann_index* h, const char* name, uint64_t* out) {
 		*out = h->stat_redo_overflows;
 	else if (!std::strcmp(name, "spec_rank"))
 		*out = h->stat_spec_rank;
+	else if (!std::strcmp(name, "i8_sample"))
+		*out = h->stat_i8_sample;
 	else if (!std::strcmp(name, "rerank_rows"))
 		*out = h->stat_rerank_rows;
 	else if (!std::strcmp(name, "base_bytes"))
@@ -3703,6 +3798,8 @@ int expann_set_option(expann_index* h, const char* name, long value) {
 		h->opt_persist = value;
 	else if (!std::strcmp(name, "i8_filter"))
 		h->opt_i8_filter = value < 0 ? 0 : (value > 2 ? 2 : value);
+	else if (!std::strcmp(name, "i8_sample"))
+		h->opt_i8_sample = value < 0 ? 0 : (value > 2 ? 2 : value);
 	else if (!std::strcmp(name, "spec_rank"))
 		h->opt_spec_rank = value < 0 ? 0 : value;
 	else if (!std::strcmp(name, "redo_bound"))

@@ -582,10 +582,15 @@ __device__ inline float sample_tau_of(const SampleTauParams& p, float qn, uint32
 }
 // one thread: ord = ordered bits of the k-th largest g (0: fewer than k values) -> tau; ord_s = those of the
 // j-th largest (= ord: no speculation) -> tau_s, theta', the int8 thresholds; the list counter
+__device__ inline void sample_tau_store(const SampleTauParams& p, uint32_t qi, float qn, float tau_k, float tau);
 __device__ inline void sample_tau_finish(const SampleTauParams& p, uint32_t qi, uint32_t ord, uint32_t ord_s) {
 	const float qn = p.qnrm[qi];
 	const float tau_k = sample_tau_of(p, qn, ord);
 	const float tau = (p.tau_s && ord_s != ord) ? sample_tau_of(p, qn, ord_s) : tau_k;  // what the full scan filters with
+	sample_tau_store(p, qi, qn, tau_k, tau);
+}
+// ... and what is stored: tau_k the proven threshold, tau the one the full scan filters with (both in the filter's domain)
+__device__ inline void sample_tau_store(const SampleTauParams& p, uint32_t qi, float qn, float tau_k, float tau) {
 	p.tau[qi] = (p.ip && p.qscale) ? tau_k / p.qscale[qi] : tau_k;  // (true units; theta' below stays in the filter's domain)
 	if (p.tau_s)
 		p.tau_s[qi] = (p.ip && p.qscale) ? tau / p.qscale[qi] : tau;
@@ -684,6 +689,62 @@ __global__ __launch_bounds__(kBlock) void sample_tau_kernel(SampleTauParams p) {
 	if (qi >= p.m)
 		return;  // (whole wave)
 	sample_tau_query<PER>(p, qi, threadIdx.x & 63, scratch[threadIdx.x >> 6]);
+}
+
+// The thresholds of a speculating int8-filter search from the INT8 sampled pass (scan_gemm_i8f.hpp, "Sampled pass on
+// int8"): vals = the class maxima of g = q~.b~ - cb written by scan_gemm_i8w_kernel<128, true, true>.  L2 only.
+// tau_s = ||q||^2 - 2s^2 g_j is the centre of the j-th maximum's interval -- an estimate the select checks --, tau the
+// proven bound from g_k; theta', thp, w_q and the zeroed counter come from the stored tau_s as after the fp16 pass.
+struct SampleTauI8cParams {
+	SampleTauParams t;     // (vals, eps, abs_coef, inv_mul unused; tau_s, j set)
+	const int* vals;       // [m][n_vals]
+	const float* wb_max;   // the largest finite row_w of the index (units of 2 s^2)
+	double two_s2;         // 2 s^2, exact
+};
+template <int PER>
+__global__ __launch_bounds__(kBlock) void sample_tau_i8c_kernel(SampleTauI8cParams pc) {
+	__shared__ uint32_t scratch[kBlock / 64][64];
+	const SampleTauParams& p = pc.t;
+	const int lane = threadIdx.x & 63;
+	const uint32_t qi = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+	if (qi >= p.m)
+		return;  // (whole wave)
+	const int* v = pc.vals + (size_t)qi * p.n_vals;
+	// ordered like g; 0 = no value (INT_MIN: the class saw no row); the maximum of a class that held only rows
+	// without a centre term (cb = kI8fCbNone) is below -2^29 and counts as none
+	uint32_t ord[PER];
+#pragma unroll
+	for (int j = 0; j < PER; ++j) {
+		const uint32_t i = j * 64 + lane;
+		const int g = i < p.n_vals ? v[i] : -2147483647 - 1;
+		ord[j] = g < -kI8fCbMax ? 0u : (uint32_t)g ^ 0x80000000u;
+	}
+	uint2 kj;  // the k-th and the j-th largest (j < k: the host launches this kernel for speculating searches only)
+	if (p.k <= 64) {
+		kj = wave_kth_largest_sparse_u32<PER>(ord, p.k, scratch[threadIdx.x >> 6], lane, p.j);
+	} else {
+		kj.x = wave_kth_largest_u32<PER>(ord, p.k);
+		kj.y = wave_kth_largest_u32<PER>(ord, p.j);
+	}
+	if (lane == 0) {
+		const float qn = p.qnrm[qi];
+		float tau_k = __builtin_inff(), tau = __builtin_inff();
+		if (kj.x != 0) {
+			const double aq = (double)p.i8_aq[qi], wq = (double)p.i8_wq_in[qi];
+			const double ulp_aq = __builtin_fabs(aq) * 0x1p-23 + 0x1p-149;
+			const double term = pc.two_s2 * ((0.5 + 0x1p-9 + 0.5 * (double)pc.wb_max[0]) - (double)(int)(kj.x ^ 0x80000000u));
+			const double b = aq + ulp_aq + wq + term;
+			tau_k = f32_up(b + (__builtin_fabs(aq) + wq + __builtin_fabs(term)) * 0x1p-40);
+			if (!(tau_k == tau_k))
+				tau_k = __builtin_inff();
+		}
+		if (kj.y != 0) {
+			tau = (float)((double)qn - pc.two_s2 * (double)(int)(kj.y ^ 0x80000000u));
+			if (!(tau == tau))
+				tau = __builtin_inff();
+		}
+		sample_tau_store(p, qi, qn, tau_k, tau);
+	}
 }
 
 // ---- the redo pass of the speculative thresholds -------------------------------

@@ -1,13 +1,17 @@
 // scan_gemm_i8f.hpp -- the fp32 L2 candidate filter on the INT8 matrix cores: rows and queries quantised
 // to int8 with ONE per-index scale, scanned by scan_gemm_i8w_kernel<128> (v_mfma_i32_16x16x64_i8: twice the
 // K per cycle of the fp16 form's v_mfma_f32_16x16x32_f16), candidates re-scored exactly in fp32 by the
-// select as after the fp16 filter -- ids and distances stay bit-identical.  The threshold tau still comes
-// from the fp16 sampled pass (scan_gemm_f16.hpp); this header holds the analysis and the prelude kernels.
+// select as after the fp16 filter -- ids and distances stay bit-identical.  The threshold tau comes from the fp16
+// sampled pass (scan_gemm_f16.hpp) or, for a speculating search, from the int8 one ("Sampled pass on int8" below);
+// this header holds the analysis and the prelude kernels.
 //
 // Quantisation.  One scale s > 0 per index (fp32; s^2 is exact in fp64).  For a row b and a query q
 //     b~ = clamp(rint(b / s), -127, 127),   e_b = b - s b~      (q~, e_q alike)
 // Any b~ is allowed: the errors are measured after the fact, so clipping (s = min(max|x|, 5.5 rms) / 127)
 // only loosens the bound of the rows / queries that were clipped, never its validity.
+// (rms: of all components -- unless those within the clip carry less than 1/16 of the index's energy, i.e. a few
+// far-out rows set the rms and the scale would be several times too coarse for all the others: then the rms of the
+// components within the clip, once, kI8fTrimEnergy; every other index keeps its scale bit for bit.)
 //
 // Exact bound.  q.b = (s q~ + e_q).(s b~ + e_b) = s^2 q~.b~ + q.e_b + e_q.b - e_q.e_b, so with
 // P = s^2 q~.b~ (an exact integer q~.b~, |q~.b~| <= 128 * 127^2 < 2^21),
@@ -42,6 +46,29 @@
 // 2^21), a bp lowered to kI8fBpMax only adds hits; a thp raised to -2^29 only adds hits, one lowered to 2^29
 // still hits every row (acc >= 2^29 - 2^21 > kI8fBpMax).  Padded query slots start at -2^30 and never reach
 // kI8fBpMin, padding rows carry kI8qPadBp = 2^30, and |acc| <= 2^30 + 2^21 never wraps.
+//
+// Sampled pass on int8 (option "i8_sample"; sample_tau_i8c_kernel, scan_gemm_f16.hpp).  A speculating search needs
+// no proven threshold before the scan -- the select checks tau_s -- so its sampled pass runs on the
+// int8 copy too: scan_gemm_i8w_kernel<128, true, true> with the row term  cb[b] = rint(N_b / 2s^2)  in place of bp,
+// class maxima of  g = q~.b~ - cb[b].  From the bounds above  A_x + W_x / 2 = N_x (+ eta on the query's side), so the
+// centre of a pair's interval [L, L + W_q + W_b] is  N_q + N_b - 2 P - eta:  the score the quantised product stands
+// for, off the true one by the quantisation noise alone (sd 0.40 on N(0, 1) rows at d = 128 against a mean width of
+// 13.6).  tau_s = ||q||^2 - 2s^2 g_j, g_j the j-th largest class maximum: an estimate, no bound, and needs to be none.
+// The PROVEN tau (the redo pass's threshold for a failed list with fewer than k rows) comes from g_k, the k-th
+// largest class maximum.  For a row b:  S <= L + W_q + W_b = (A_q - eta) + W_q + (A_b + W_b) - 2 P  and
+// A_b + W_b = N_b (1 + lambda + eps) + c V_b = N_b + W_b / 2.  The fp64 sum nn of i8f_rows_kernel has N_b <=
+// nn (1 + 2^-40) and cb >= nn / 2s^2 - 1/2 - 2^-50 nn / 2s^2, so with cb <= kI8fCbMax = 2^29:  N_b <= 2s^2 (cb + 1/2 + 2^-9);
+// P = 2s^2 q~.b~ = 2s^2 (g + cb) exactly; the stored aq is A_q - eta rounded down, A_q - eta <= aq + ulp(aq); and
+// W_b / 2 <= 2s^2 wb_max / 2, wb_max = the largest row_w among the rows the pass can see.  It sees a row only when the
+// row has an interval, its cb fits kI8fCbMax and row_w <= w_cap = twice the width of a row of the index's rms norm
+// with unclipped components, 2 (2 (lambda + eps) d rms^2 + 2 c d s^2 / 12) / 2s^2 (I8fConsts::w_cap): every other row
+// carries cb = kI8fCbNone and is no class maximum -- any subset of the rows may be sampled -- so one row with a
+// clipped component (row_w 24 against a mean of 6.8 on 266 240 N(0, 1) rows) does not widen every query's tau.  Together
+//     S  <=  aq + ulp(aq) + W_q + 2s^2 (1/2 + 2^-9 - g + wb_max / 2)
+// for every row whose g the pass saw, decreasing in g.  The k largest class maxima belong to k different rows, each
+// with g >= g_k, so the k-th smallest S of the index is at most that bound at g = g_k: tau, evaluated in fp64
+// (five operations, < 2^-50 relative each, covered by a factor 1 + 2^-40 on every positive term) and rounded UP to
+// fp32.  Fewer than k real maxima (g of a cb = kI8fCbNone row is below -2^29): tau = +inf, as the fp16 pass.
 //
 // Keys and pruning.  A hit's log entry is its raw accumulator and the row's bp; gather_logs_kernel (i_mode 3) keys it
 // by kappa = -(acc - bp[b]) = bp - thp - q~.b~.  From the two floors (each below its real value by less than
@@ -85,6 +112,8 @@ namespace expann {
 constexpr int kI8fBpMin = -(1 << 29) - (1 << 22);
 constexpr int kI8fBpMax = (1 << 29) - (1 << 22);
 constexpr int kI8fThpLim = 1 << 29;
+constexpr int kI8fCbMax = 1 << 29;   // largest centre row term of the int8 sampled pass (cb >= 0: N_b >= 0)
+constexpr int kI8fCbNone = 1 << 30;  // cb of a row the sampled pass must not see (= kI8qPadBp, the padding rows')
 
 // the analysis's per-index constants (host: i8f_consts)
 struct I8fConsts {
@@ -96,6 +125,7 @@ struct I8fConsts {
 	double wn;       // 2 (lambda + eps)
 	double inv_2s2;  // 1 / (2 s^2)
 	double eta;
+	double w_cap;    // int8 sampled pass: rows with row_w above this are left out ("Sampled pass on int8")
 };
 // bnmax = the largest fp32 reference-order ||b||^2 (relative error < (d/16 + 6) u, far below the 2^-16 added)
 inline I8fConsts i8f_consts(float s, float rms, float bnmax, int d) {
@@ -112,6 +142,7 @@ inline I8fConsts i8f_consts(float s, float rms, float bnmax, int d) {
 	k.wn = 2.0 * (lambda + eps);
 	k.inv_2s2 = 1.0 / (2.0 * (double)s * (double)s);
 	k.eta = ((double)d + 16.0) * 1.401298464324817e-45;
+	k.w_cap = 2.0 * (k.wn * (double)d * (double)rms * (double)rms + 2.0 * k.c * (double)d * (double)s * (double)s / 12.0) * k.inv_2s2;
 	return k;
 }
 
@@ -170,13 +201,49 @@ __global__ __launch_bounds__(kBlock) void i8f_stats_kernel(const float* in, size
 	}
 }
 
+// The same sum over the components with |x| <= limit alone, and their number (the scale of an index whose few far-out
+// rows carry nearly all of its energy: ensure_i8f); out zeroed by the caller
+__global__ __launch_bounds__(kBlock) void i8f_trimmed_stats_kernel(const float* in, size_t n, float limit, double* sumsq,
+                                                                   unsigned long long* count) {
+	__shared__ double red[kBlock / 64];
+	__shared__ unsigned long long redc[kBlock / 64];
+	double s = 0.0;
+	unsigned long long c = 0;
+	for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (size_t)gridDim.x * kBlock) {
+		const float v = in[i];
+		if (__builtin_fabsf(v) <= limit) {
+			s += (double)v * (double)v;
+			++c;
+		}
+	}
+	for (int off = 32; off > 0; off >>= 1) {
+		s += __shfl_xor(s, off);
+		c += __shfl_xor(c, off);
+	}
+	if ((threadIdx.x & 63) == 0) {
+		red[threadIdx.x >> 6] = s;
+		redc[threadIdx.x >> 6] = c;
+	}
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		for (int w = 1; w < kBlock / 64; ++w) {
+			s += red[w];
+			c += redc[w];
+		}
+		atomicAdd(sumsq, s);
+		atomicAdd(count, c);
+	}
+}
+
 // Index side, one pass over the fp32 rows: the padded int8 copy (rows of D bytes, n_pad rows, zero rows
 // behind the end), bp[b] and row_w[b] = w_b (+inf when bp was clamped).  16 lanes per row, each lane D / 16
 // consecutive components (one 8-byte store at d = 128); padding rows get bp = kI8qPadBp (set by the caller's
 // fill of bp, as scan_gemm_i8q's i8q_bp_kernel).
+// cb[b] = rint(N_b / 2s^2), the centre row term of the int8 sampled pass ("Sampled pass on int8" above), or kI8fCbNone
+// for a row without an interval, wider than w_cap or with a centre term beyond kI8fCbMax: never a class maximum.
 template <int D>
 __global__ __launch_bounds__(kBlock) void i8f_rows_kernel(const float* x, uint32_t n, I8fConsts k, int8_t* out,
-                                                          int* bp, float* row_w) {
+                                                          int* bp, float* row_w, int* cb) {
 	static_assert(D % 64 == 0, "whole 4-byte groups per lane");
 	constexpr int PER = D / 16;
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -218,11 +285,32 @@ __global__ __launch_bounds__(kBlock) void i8f_rows_kernel(const float* x, uint32
 		if (xl >= (double)kI8fBpMin && xl <= (double)kI8fBpMax) {
 			bp[i] = (int)__builtin_floor(xl);
 			row_w[i] = f32_up((k.wn * nn * (1.0 + 0x1p-40) + 2.0 * k.c * v_up) * k.inv_2s2 * (1.0 + 0x1p-40));
+			const double xc = __builtin_rint(nn * k.inv_2s2);
+			cb[i] = (xc <= (double)kI8fCbMax && (double)row_w[i] <= k.w_cap) ? (int)xc : kI8fCbNone;
 		} else {  // (NaN lands here too)
 			bp[i] = xl > 0.0 ? kI8fBpMax : kI8fBpMin;
 			row_w[i] = __builtin_inff();
+			cb[i] = kI8fCbNone;
 		}
 	}
+}
+
+// wb_max = the largest row_w among the rows with a centre term (the proven tau of the int8 sampled pass); row_w >= 0,
+// so the bit patterns order like the values; *out_bits zeroed by the caller
+__global__ __launch_bounds__(kBlock) void i8f_wbmax_kernel(const float* row_w, const int* cb, uint32_t n, uint32_t* out_bits) {
+	uint32_t b = 0;
+	for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += gridDim.x * kBlock) {
+		const float w = row_w[i];
+		const uint32_t wb = __builtin_bit_cast(uint32_t, w);
+		if (cb[i] != kI8fCbNone && w >= 0.0f && w < __builtin_inff() && wb > b)
+			b = wb;
+	}
+	for (int off = 32; off > 0; off >>= 1) {
+		const uint32_t o = (uint32_t)__shfl_xor((int)b, off);
+		b = o > b ? o : b;
+	}
+	if ((threadIdx.x & 63) == 0 && b != 0)
+		atomicMax(out_bits, b);
 }
 
 // Query side (f16_query_prep_kernel): q~ and the query's terms.  aq = A_q - eta rounded down, wq = W_q

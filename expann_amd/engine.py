@@ -142,6 +142,7 @@ class GpuBruteForceEngine:
 
     def get_stat(self, name):
         """expann_get_stat: "redo_queries", "redo_candidates", "redo_overflows", "spec_rank" (speculative thresholds);
+        "i8_sample" (1: the last search's sampled pass ran on the int8 matrix cores);
         "rerank_rows" (rows the last search's selects re-scored exactly; counted under the option "rerank_stats");
         "filter_active" (0 / 1) and "filter_rows" (rows the row filter allows; n when none is set);
         "base_bytes" (device bytes of the rows themselves: n * dim * element size)."""

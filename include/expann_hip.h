@@ -488,6 +488,13 @@ int expann_sharded_get_profile(expann_sharded* h, int shard, expann_profile* out
  * "i8_filter" (fp32 L2, d = 128, scan_kernel on auto: the full scan on the int8 matrix cores with a rigorous
  * slack and the exact re-rank, thresholds from the fp16 sampled pass; 1 (default): from the planner's crossover
  * on, 2: wherever supported, 0: never; the environment variable EXPANN_I8_FILTER sets the starting value),
+ * "i8_sample" (int8 filter with speculative thresholds: the sampled pass runs on the int8 matrix cores too, over the
+ * index's int8 copy with a centre row term of 4 bytes per row kept beside it -- the speculative threshold is then an
+ * estimate from the int8 products, which the select's check covers as it covers any other, and the proven threshold
+ * of the redo pass comes from the same pass; ids and distances do not change.  1 (default): where the int8 filter
+ * speculates at its auto rank ("spec_rank" 0) and no row filter is set; 2: wherever it speculates, forced ranks
+ * included; 0: never -- the fp16 sampled pass, as every proven-threshold, fp16-form, filtered or repeated search
+ * takes.  EXPANN_I8_SAMPLE sets the starting value),
  * "spec_rank" (fp32 rows, d = 64 / 128, batches of more than 64 queries: the full scan filters with a SPECULATIVE
  * threshold, the j-th largest class maximum of the sampled pass instead of the k-th; the select checks every
  * query's result against it and the few failing queries are searched again on the device with the proven
@@ -512,7 +519,8 @@ int expann_set_option(expann_index* h, const char* name, long value);
  * redo pass of the speculative thresholds served (deferred searches: of the searches the last expann_sync
  * checked), "redo_candidates" = the keys the redo lists of those queries held, "redo_overflows" = searches since the handle was made whose failing queries did not fit the redo
  * pass (repeated with proven thresholds: a retry), "spec_rank" = the rank j of the last search's thresholds
- * (= k: proven thresholds), "rerank_rows" = rows of the index the last search's selects (the redo pass's included)
+ * (= k: proven thresholds), "i8_sample" = 1 when the last search's sampled pass ran on the int8 matrix cores (option
+ * "i8_sample"; 0 after a search whose last attempt took the fp16 pass or none), "rerank_rows" = rows of the index the last search's selects (the redo pass's included)
  * re-scored exactly, counted only under the option "rerank_stats" (else 0), "base_bytes" = bytes of device memory that hold the rows themselves (n * dim * bytes
  * per element, every dtype; 0 before the rows are on the device). */
 int expann_get_stat(expann_index* h, const char* name, uint64_t* out);
