@@ -46,6 +46,8 @@ ABI_SYMBOLS = [
     "expann_graph_search_grouped", "expann_graph_search_grouped_device",
     "expann_antitopo_set_row_groups", "expann_antitopo_set_row_groups_device",
     "expann_antitopo_query_grouped", "expann_antitopo_query_grouped_device",
+    "expann_set_row_groups", "expann_set_row_groups_device", "expann_clear_row_groups",
+    "expann_search_grouped", "expann_search_grouped_device",
 ]
 GROUP_ANY = 0xFFFFFFFF  # EXPANN_GROUP_ANY: the group a query names to search every row
 
@@ -308,6 +310,17 @@ def load():
         L.expann_antitopo_query_grouped.argtypes = [vp, vp, vp, sz, sz, vp, vp]
         L.expann_antitopo_query_grouped_device.restype = C.c_int
         L.expann_antitopo_query_grouped_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
+    if hasattr(L, "expann_set_row_groups"):  # (as above: an older build has no brute-force row groups)
+        L.expann_set_row_groups.restype = C.c_int
+        L.expann_set_row_groups.argtypes = [vp, vp, sz]
+        L.expann_set_row_groups_device.restype = C.c_int
+        L.expann_set_row_groups_device.argtypes = [vp, vp, sz, vp]
+        L.expann_clear_row_groups.restype = C.c_int
+        L.expann_clear_row_groups.argtypes = [vp]
+        L.expann_search_grouped.restype = C.c_int
+        L.expann_search_grouped.argtypes = [vp, vp, vp, sz, sz, vp, vp]
+        L.expann_search_grouped_device.restype = C.c_int
+        L.expann_search_grouped_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
     if hasattr(L, "expann_graph_create_f16"):  # (as above: an older build has no binary16 graph rows)
         L.expann_graph_create_f16.restype = C.c_int
         L.expann_graph_create_f16.argtypes = [C.c_int, C.c_int, vp, sz, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(vp)]

@@ -598,20 +598,9 @@ int graph_set_row_groups(expann_graph* g, const uint32_t* groups, size_t n, bool
 		HIP_TRY(g, hipStreamSynchronize(st));
 	} else
 		std::memcpy(lab.data(), groups, sizeof(uint32_t) * n);
-	std::vector<uint32_t> order(n);
-	for (size_t v = 0; v < n; ++v)
-		order[v] = (uint32_t)v;
-	std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return lab[a] < lab[b]; });
-	size_t n_rows = n;  // rows labelled 0xFFFFFFFF sort last and belong to no group
-	while (n_rows && lab[order[n_rows - 1]] == kGroupAny)
-		--n_rows;
-	std::vector<uint32_t> keys, off;
-	for (size_t i = 0; i < n_rows; ++i)
-		if (i == 0 || lab[order[i]] != lab[order[i - 1]]) {
-			keys.push_back(lab[order[i]]);
-			off.push_back((uint32_t)i);
-		}
-	off.push_back((uint32_t)n_rows);
+	const GroupDirectory dir = build_group_directory(lab.data(), n);  // (host_common.hpp: shared with the brute-force index)
+	const std::vector<uint32_t>&keys = dir.keys, &off = dir.off, &order = dir.rows;
+	const size_t n_rows = dir.n_rows();
 	DevPtr<uint32_t> b_lab, b_keys, b_off, b_rows;
 	HIP_TRY(g, hipMalloc(&b_lab, sizeof(uint32_t) * n));
 	HIP_TRY(g, hipMalloc(&b_keys, sizeof(uint32_t) * std::max<size_t>(keys.size(), 1)));

@@ -32,6 +32,7 @@
 #include "scan_int8.hpp"
 #include "scan_int8_any.hpp"
 #include "filter_rows.hpp"
+#include "scan_groups.hpp"
 #include "score_ids.hpp"
 #include "select.hpp"
 
@@ -150,6 +151,21 @@ struct expann_index {
 	// the row terms the fp16 forms read: the masked copies while a filter is set
 	const float* bnorm_f16() const { return filter_on ? d_bnorm_f16_m.p : d_bnorm_f16.p; }
 	const float* bns_f16() const { return filter_on ? d_bns_f16_m.p : d_bns_f16.p; }
+	// row groups (expann_set_row_groups): the labels and each group's rows on the device, the
+	// directory's labels and offsets on the host, where a grouped search is planned; and that search's staging
+	bool groups_on = false;
+	DevPtr<uint32_t> d_row_groups;   // [n]
+	DevPtr<uint32_t> d_group_rows;   // [rows that carry a label other than 0xFFFFFFFF], by (label, row)
+	GroupDirectory group_dir;        // keys and off (the rows live in d_group_rows)
+	long opt_group_list_rows = 0;    // "group_list_rows": 0 = kGroupListRowsAuto
+	uint64_t stat_group[5] = {0, 0, 0, 0, 0};  // the last grouped search: list, filter, any, pad queries; filter passes
+	PinPtr<void> h_group_tab;        // pinned: [sorted query numbers | list slots' queries | work items]
+	size_t h_group_tab_bytes = 0;
+	GrowPtr<void> d_group_tab;
+	GrowPtr<void> d_group_q;         // gathered queries of one tier
+	GrowPtr<uint64_t> d_group_ids;   // ... and their result rows
+	GrowPtr<float> d_group_dists;
+	bool group_lds_set = false;      // the list kernel's LDS limit is raised (dims whose query tile exceeds 64 KiB)
 	float f16_bnmax = 0.0f;          // max ||b||^2 (host copy lives in d_bnmax[2])
 	// int8 filter of fp32 rows (scan_gemm_i8f.hpp), built lazily beside the fp16 copy (whose sampled pass
 	// gives its thresholds) and dropped with it
@@ -788,6 +804,13 @@ void drop_row_filter(expann_index* h) {
 	h->filter_list_stride = 1;
 	h->n_allowed = 0;
 	h->filter_residues = 0;
+}
+// forget the row groups (they belong to the rows they were set for)
+void drop_row_groups(expann_index* h) {
+	h->groups_on = false;
+	h->d_row_groups.reset();
+	h->d_group_rows.reset();
+	h->group_dir = GroupDirectory{};
 }
 
 const GemmVariant* pick_gemm(const expann_index* h, size_t m) {
@@ -3264,6 +3287,7 @@ int expann_build(expann_index* h) {
 		return h->fail(EXPANN_ERR_UNSUPPORTED, "more than 2^32 rows per shard");
 	HIP_TRY(h, hipSetDevice(h->device));
 	drop_row_filter(h);
+	drop_row_groups(h);
 	HIP_TRY(h, hipMalloc(&h->d_base, h->staging.size()));
 	h->owns_base = true;
 	HIP_TRY(h, hipMemcpy(h->d_base, h->staging.data(), h->staging.size(), hipMemcpyHostToDevice));
@@ -3319,6 +3343,7 @@ int expann_set_base_device(expann_index* h, const void* d_rows, size_t n, uint64
 	h->f16_scale = 0.0f;
 	h->f16_n_pad = 0;
 	drop_row_filter(h);  // (a filter belongs to the rows it was set for)
+	drop_row_groups(h);
 	h->d_base = const_cast<void*>(d_rows);
 	h->owns_base = false;
 	h->n = n;
@@ -3684,6 +3709,20 @@ int expann_get_stat(expann_index* h, const char* name, uint64_t* out) {
 		*out = h->filter_on ? 1 : 0;
 	else if (!std::strcmp(name, "filter_rows"))
 		*out = h->filter_on ? h->n_allowed : expann_size(h);
+	else if (!std::strcmp(name, "groups_active"))
+		*out = h->groups_on ? 1 : 0;
+	else if (!std::strcmp(name, "group_count"))
+		*out = h->groups_on ? h->group_dir.keys.size() : 0;
+	else if (!std::strcmp(name, "group_list_queries"))
+		*out = h->stat_group[0];
+	else if (!std::strcmp(name, "group_filter_queries"))
+		*out = h->stat_group[1];
+	else if (!std::strcmp(name, "group_any_queries"))
+		*out = h->stat_group[2];
+	else if (!std::strcmp(name, "group_pad_queries"))
+		*out = h->stat_group[3];
+	else if (!std::strcmp(name, "group_filter_passes"))
+		*out = h->stat_group[4];
 	else
 		return h->fail(EXPANN_ERR_INVALID_ARG, std::string("unknown statistic ") + name);
 	return EXPANN_OK;
@@ -3695,6 +3734,51 @@ uint32_t expann_spec_rank_auto(size_t k, uint32_t sample_frac) {
 
 // ---- row filter ------------------------------------------------------------------------
 namespace {
+// The engine's own buffers for a filter of the current rows; the filter is off until filter_finish.  *words = the
+// words of the engine's bitmap: whole tiles of the fp16 copy (<= 128 rows each).
+int filter_begin(expann_index* h, size_t* words_out) {
+	const size_t words = (h->n + 127) / 128 * 4;
+	if (words != h->filter_words || !h->d_filter_bits) {
+		h->filter_on = false;
+		h->d_filter_bits.reset();
+		h->filter_words = 0;
+		HIP_TRY(h, hipMalloc(&h->d_filter_bits, sizeof(uint32_t) * words));
+		h->filter_words = words;
+	}
+	if (!h->d_filter_stat)
+		HIP_TRY(h, hipMalloc(&h->d_filter_stat, sizeof(uint32_t) * (2 + kFilterSegs)));
+	if (!h->d_filter_list)
+		HIP_TRY(h, hipMalloc(&h->d_filter_list, sizeof(uint32_t) * kFilterListCap));
+	h->filter_on = false;  // (until the new filter is complete)
+	h->filter_terms_valid = false;
+	*words_out = words;
+	return EXPANN_OK;
+}
+
+// The bits are in d_filter_bits (in the order of `st`): count, residues and the list of allowed rows; the filter is on.
+int filter_finish(expann_index* h, hipStream_t st, size_t words) {
+	HIP_TRY(h, hipMemsetAsync(h->d_filter_stat, 0, sizeof(uint32_t) * (2 + kFilterSegs), st));
+	hipLaunchKernelGGL(filter_count_kernel, dim3(kFilterSegs), dim3(kBlock), 0, st, h->d_filter_bits.as<uint32_t>(),
+	                   (uint32_t)h->n, (uint32_t)words, h->d_filter_stat.as<uint32_t>(), h->d_filter_stat + 2);
+	HIP_TRY(h, hipGetLastError());
+	uint32_t stat[2] = {0, 0};
+	HIP_TRY(h, hipMemcpyAsync(stat, h->d_filter_stat, sizeof(stat), hipMemcpyDeviceToHost, st));
+	HIP_TRY(h, hipStreamSynchronize(st));  // the planner needs the count on the host: one wait per filter change
+	h->n_allowed = stat[0];
+	h->filter_residues = stat[1];
+	h->filter_list_stride = (uint32_t)std::max<size_t>(1, (h->n_allowed + kFilterListCap - 1) / kFilterListCap);
+	h->filter_list_len = (uint32_t)((h->n_allowed + h->filter_list_stride - 1) / h->filter_list_stride);
+	if (h->n_allowed) {
+		hipLaunchKernelGGL(filter_compact_kernel, dim3(kFilterSegs), dim3(kBlock), 0, st, h->d_filter_bits.as<const uint32_t>(),
+		                   (uint32_t)words, h->d_filter_stat.as<const uint32_t>() + 2, h->filter_list_stride,
+		                   h->d_filter_list.as<uint32_t>(), kFilterListCap);
+		HIP_TRY(h, hipGetLastError());
+		HIP_TRY(h, hipStreamSynchronize(st));
+	}
+	h->filter_on = true;
+	return EXPANN_OK;
+}
+
 // bits: n_words words in host (on_device = false) or device memory, read in the order of `st`
 int set_row_filter(expann_index* h, const uint32_t* bits, size_t n_words, bool on_device, hipStream_t user_st) {
 	if (!h)
@@ -3717,44 +3801,388 @@ int set_row_filter(expann_index* h, const uint32_t* bits, size_t n_words, bool o
 		HIP_TRY(h, hipStreamSynchronize(h->async_stream));
 	HIP_TRY(h, hipStreamSynchronize(h->stream));
 	hipStream_t st = user_st ? user_st : h->stream;
-	const size_t words = (h->n + 127) / 128 * 4;  // whole tiles of the fp16 copy (<= 128 rows each)
-	if (words != h->filter_words || !h->d_filter_bits) {
-		h->filter_on = false;
-		h->d_filter_bits.reset();
-		h->filter_words = 0;
-		HIP_TRY(h, hipMalloc(&h->d_filter_bits, sizeof(uint32_t) * words));
-		h->filter_words = words;
-	}
-	if (!h->d_filter_stat)
-		HIP_TRY(h, hipMalloc(&h->d_filter_stat, sizeof(uint32_t) * (2 + kFilterSegs)));
-	if (!h->d_filter_list)
-		HIP_TRY(h, hipMalloc(&h->d_filter_list, sizeof(uint32_t) * kFilterListCap));
-	h->filter_on = false;  // (until the new filter is complete)
-	h->filter_terms_valid = false;
+	size_t words = 0;
+	if (const int rc = filter_begin(h, &words))
+		return rc;
 	HIP_TRY(h, hipMemsetAsync(h->d_filter_bits, 0, sizeof(uint32_t) * words, st));
 	HIP_TRY(h, hipMemcpyAsync(h->d_filter_bits, bits, sizeof(uint32_t) * need_words,
 	                          on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-	HIP_TRY(h, hipMemsetAsync(h->d_filter_stat, 0, sizeof(uint32_t) * (2 + kFilterSegs), st));
-	hipLaunchKernelGGL(filter_count_kernel, dim3(kFilterSegs), dim3(kBlock), 0, st, h->d_filter_bits.as<uint32_t>(),
-	                   (uint32_t)h->n, (uint32_t)words, h->d_filter_stat.as<uint32_t>(), h->d_filter_stat + 2);
-	HIP_TRY(h, hipGetLastError());
-	uint32_t stat[2] = {0, 0};
-	HIP_TRY(h, hipMemcpyAsync(stat, h->d_filter_stat, sizeof(stat), hipMemcpyDeviceToHost, st));
-	HIP_TRY(h, hipStreamSynchronize(st));  // the planner needs the count on the host: one wait per filter change
-	h->n_allowed = stat[0];
-	h->filter_residues = stat[1];
-	h->filter_list_stride = (uint32_t)std::max<size_t>(1, (h->n_allowed + kFilterListCap - 1) / kFilterListCap);
-	h->filter_list_len = (uint32_t)((h->n_allowed + h->filter_list_stride - 1) / h->filter_list_stride);
-	if (h->n_allowed) {
-		hipLaunchKernelGGL(filter_compact_kernel, dim3(kFilterSegs), dim3(kBlock), 0, st, h->d_filter_bits.as<const uint32_t>(),
-		                   (uint32_t)words, h->d_filter_stat.as<const uint32_t>() + 2, h->filter_list_stride,
-		                   h->d_filter_list.as<uint32_t>(), kFilterListCap);
-		HIP_TRY(h, hipGetLastError());
+	return filter_finish(h, st, words);
+}
+
+// ---- row groups ---------------------------------------------------------
+// "group_list_rows" = 0: every group the select can sort takes the list kernel.  Measured on 1 M x d128, k = 10
+// (profiles/bf_groups_ab.txt, part c): groups of 1 024 .. 16 384 rows, 10 and 100 queries per group -- the list kernel
+// was never slower than the filter passes (x 0.005 .. x 0.82 of their time), so there is no crossover below kMaxCap
+constexpr uint32_t kGroupListRowsAuto = kMaxCap;
+// keys of one list pass's candidate lists (1 GiB): bounds the slots of a pass together with kMaxQueriesPerPass
+constexpr size_t kGroupPassKeys = (size_t)1 << 27;
+
+// labels: n of them in host (on_device = false) or device memory, read in the order of `user_st`
+int set_row_groups(expann_index* h, const uint32_t* groups, size_t n, bool on_device, hipStream_t user_st) {
+	if (!h)
+		return EXPANN_ERR_INVALID_ARG;
+	if (!groups)
+		return h->fail(EXPANN_ERR_INVALID_ARG, "row groups: NULL labels");
+	if (!float_rows(h))
+		return h->fail(EXPANN_ERR_UNSUPPORTED,
+		               "row groups: fp32 / fp16 rows only (the filter passes of large groups need the row filter)");
+	if (n != expann_size(h))
+		return h->fail(EXPANN_ERR_INVALID_ARG,
+		               "row groups: " + std::to_string(n) + " labels for " + std::to_string(expann_size(h)) + " rows");
+	if (!h->d_base)
+		return h->fail(EXPANN_ERR_NOT_BUILT, "row groups before build()");
+	HIP_TRY(h, hipSetDevice(h->device));
+	// deferred searches are waited for, as before a filter change (their flag blocks stay in the ring for expann_sync)
+	if (h->async_pending > 0)
+		HIP_TRY(h, hipStreamSynchronize(h->async_stream));
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
+	hipStream_t st = user_st ? user_st : h->stream;
+	std::vector<uint32_t> lab(n);
+	if (on_device) {
+		HIP_TRY(h, hipMemcpyAsync(lab.data(), groups, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
 		HIP_TRY(h, hipStreamSynchronize(st));
-	}
-	h->filter_on = true;
+	} else
+		std::memcpy(lab.data(), groups, sizeof(uint32_t) * n);
+	GroupDirectory dir = build_group_directory(lab.data(), n);
+	DevPtr<uint32_t> b_lab, b_rows;  // built aside: a failed call leaves the groups as they were
+	HIP_TRY(h, hipMalloc(&b_lab, sizeof(uint32_t) * n));
+	HIP_TRY(h, hipMalloc(&b_rows, sizeof(uint32_t) * std::max<size_t>(dir.n_rows(), 1)));
+	HIP_TRY(h, hipMemcpy(b_lab, lab.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+	if (dir.n_rows())
+		HIP_TRY(h, hipMemcpy(b_rows, dir.rows.data(), sizeof(uint32_t) * dir.n_rows(), hipMemcpyHostToDevice));
+	std::vector<uint32_t>().swap(dir.rows);  // (the rows live on the device)
+	std::swap(h->d_row_groups.p, b_lab.p);   // (the old buffers go with the locals)
+	std::swap(h->d_group_rows.p, b_rows.p);
+	h->group_dir = std::move(dir);
+	h->groups_on = true;
 	return EXPANN_OK;
 }
+
+// the checks of a grouped search, expann_search's first and in its order; *empty: m == 0, nothing to do
+int grouped_args(expann_index* h, const void* queries, const uint32_t* query_groups, size_t m, size_t k, const uint64_t* ids,
+                 bool* empty) {
+	*empty = false;
+	if (!h)
+		return EXPANN_ERR_INVALID_ARG;
+	if (!h->d_base)
+		return h->fail(EXPANN_ERR_NOT_BUILT, "search before build()");
+	if (k == 0)
+		return h->fail(EXPANN_ERR_INVALID_ARG, "k == 0");
+	if (k > kMaxK)
+		return h->fail(EXPANN_ERR_UNSUPPORTED, k_too_large());
+	if (m == 0) {
+		*empty = true;
+		return EXPANN_OK;
+	}
+	if (!queries || !ids)
+		return h->fail(EXPANN_ERR_INVALID_ARG, "NULL query/ids pointer");
+	if (!query_groups)
+		return h->fail(EXPANN_ERR_INVALID_ARG, "NULL query_groups");
+	if (!h->groups_on)
+		return h->fail(EXPANN_ERR_NOT_BUILT, "grouped search: no row groups are set (expann_set_row_groups)");
+	if (h->filter_on)
+		return h->fail(EXPANN_ERR_UNSUPPORTED, "grouped search under a row filter: combining the bitmap with groups is not offered");
+	return EXPANN_OK;
+}
+
+// One tier of a grouped batch through the plain pipeline: the queries idx[0, cnt) (device array of the caller's query
+// numbers) are gathered into contiguous staging, search_pass serves them -- under whatever filter is in force --
+// and the result rows are scattered back.
+int grouped_tier(expann_index* h, const void* d_queries, const uint32_t* d_idx, size_t cnt, size_t k, uint64_t* d_ids,
+                 float* d_dists, hipStream_t st) {
+	const uint32_t row_words = (uint32_t)h->dim;  // (fp32 queries)
+	for (size_t q0 = 0; q0 < cnt; q0 += kMaxQueriesPerPass) {
+		const size_t mm = std::min(kMaxQueriesPerPass, cnt - q0);
+		const size_t q_need = sizeof(uint32_t) * mm * row_words, i_need = sizeof(uint64_t) * mm * k;
+		const size_t d_need = d_dists ? sizeof(float) * mm * k : 0;
+		if (q_need > h->d_group_q.bytes || i_need > h->d_group_ids.bytes || d_need > h->d_group_dists.bytes)
+			HIP_TRY(h, hipStreamSynchronize(st));  // (growing frees the old block: the tier before has drained first)
+		HIP_TRY(h, h->d_group_q.ensure(q_need));
+		HIP_TRY(h, h->d_group_ids.ensure(i_need));
+		if (d_dists)
+			HIP_TRY(h, h->d_group_dists.ensure(d_need));
+		const uint32_t grid = (uint32_t)std::min<size_t>((mm * row_words + kBlock - 1) / kBlock, 4096);
+		hipLaunchKernelGGL(group_gather_rows_kernel, dim3(grid), dim3(kBlock), 0, st, (const uint32_t*)d_queries, d_idx + q0,
+		                   (uint32_t)mm, row_words, h->d_group_q.as<uint32_t>());
+		HIP_TRY(h, hipGetLastError());
+		float* const t_dists = d_dists ? h->d_group_dists.get() : nullptr;
+		const int rc = search_pass(h, h->d_group_q, mm, k, h->d_group_ids, t_dists, st);
+		if (rc != EXPANN_OK)
+			return rc;
+		const uint32_t grid2 = (uint32_t)std::min<size_t>((mm * k + kBlock - 1) / kBlock, 4096);
+		hipLaunchKernelGGL(group_scatter_results_kernel, dim3(grid2), dim3(kBlock), 0, st, (const uint64_t*)h->d_group_ids.get(),
+		                   (const float*)t_dists, d_idx + q0, (uint32_t)mm, (uint32_t)k, d_ids, d_dists);
+		HIP_TRY(h, hipGetLastError());
+		// (the staging is reused by the next pass and the next tier: in stream order)
+	}
+	return EXPANN_OK;
+}
+
+using GroupScanFn = void (*)(GroupScanParams);
+GroupScanFn group_scan_fn(const expann_index* h) {
+	const bool ip = h->metric == EXPANN_METRIC_IP;
+	if (f16_rows(h))
+		return ip ? group_list_scan_kernel<kGroupScanTQ, true, _Float16> : group_list_scan_kernel<kGroupScanTQ, false, _Float16>;
+	return ip ? group_list_scan_kernel<kGroupScanTQ, true, float> : group_list_scan_kernel<kGroupScanTQ, false, float>;
+}
+
+// A grouped search on device buffers (the checks are done): plan on the host, enqueue on `st`, return when it has drained.
+int grouped_search_device(expann_index* h, const void* d_queries, const uint32_t* qg, size_t m, size_t k, uint64_t* d_ids,
+                          float* d_dists, hipStream_t st) {
+	if (m >= (1ull << 32))
+		return h->fail(EXPANN_ERR_UNSUPPORTED, "grouped search: more than 2^32 queries");
+	struct HostCall {  // every pass below is the waiting form, whatever "async_search" says; no filter is left behind
+		expann_index* h;
+		bool was;
+		~HostCall() {
+			h->host_call = was;
+			h->filter_on = false;
+		}
+	} guard{h, h->host_call};
+	h->host_call = true;
+	for (uint64_t& s : h->stat_group)
+		s = 0;
+	h->stat_redo_queries = 0;
+	h->stat_redo_candidates = 0;
+	h->stat_rerank_rows = 0;
+	const GroupDirectory& dir = h->group_dir;
+	const size_t G = dir.keys.size();
+	const uint32_t L = h->opt_group_list_rows > 0 ? (uint32_t)h->opt_group_list_rows : kGroupListRowsAuto;
+
+	// all ANY, in order: the plain search in place
+	bool all_any = true;
+	for (size_t i = 0; i < m && all_any; ++i)
+		all_any = qg[i] == EXPANN_GROUP_ANY;
+	if (all_any) {
+		h->stat_group[2] = m;
+		const size_t qbytes = (size_t)h->dim * h->q_elem;
+		for (size_t q0 = 0; q0 < m; q0 += kMaxQueriesPerPass) {
+			const size_t mm = std::min(kMaxQueriesPerPass, m - q0);
+			const int rc = search_pass(h, (const char*)d_queries + q0 * qbytes, mm, k, d_ids + q0 * k,
+			                           d_dists ? d_dists + q0 * k : nullptr, st);
+			if (rc != EXPANN_OK)
+				return rc;
+		}
+		HIP_TRY(h, hipStreamSynchronize(st));
+		return EXPANN_OK;
+	}
+
+	// bucket the queries: group number, G = ANY, G + 1 = a label no row carries; a stable counting sort when the
+	// directory is small beside the batch, a sort of (bucket, query) pairs otherwise
+	std::vector<uint32_t> bucket(m), perm(m);
+	for (size_t i = 0; i < m; ++i) {
+		const size_t gi = qg[i] == EXPANN_GROUP_ANY ? G : dir.find(qg[i]);
+		bucket[i] = (uint32_t)(qg[i] != EXPANN_GROUP_ANY && gi == G ? G + 1 : gi);
+	}
+	if (G + 2 <= 4 * m + 4096) {
+		std::vector<uint32_t> start(G + 3, 0);
+		for (size_t i = 0; i < m; ++i)
+			start[bucket[i] + 1]++;
+		for (size_t b = 0; b < G + 2; ++b)
+			start[b + 1] += start[b];
+		for (size_t i = 0; i < m; ++i)
+			perm[start[bucket[i]]++] = (uint32_t)i;
+	} else {
+		std::vector<uint64_t> ord(m);
+		for (size_t i = 0; i < m; ++i)
+			ord[i] = ((uint64_t)bucket[i] << 32) | i;
+		std::sort(ord.begin(), ord.end());
+		for (size_t i = 0; i < m; ++i)
+			perm[i] = (uint32_t)ord[i];
+	}
+
+	// the tiers: runs of one bucket in perm
+	struct Run {
+		uint32_t bucket, begin, end;
+	};
+	std::vector<Run> list_runs, filter_runs;
+	Run any_run{0, 0, 0}, pad_run{0, 0, 0};
+	uint32_t max_s = 0;
+	for (size_t a = 0; a < m;) {
+		const uint32_t b = bucket[perm[a]];
+		size_t e = a + 1;
+		while (e < m && bucket[perm[e]] == b)
+			++e;
+		const Run r{b, (uint32_t)a, (uint32_t)e};
+		if (b == G + 1)
+			pad_run = r, h->stat_group[3] = e - a;
+		else if (b == G)
+			any_run = r, h->stat_group[2] = e - a;
+		else {
+			const uint32_t s = dir.off[b + 1] - dir.off[b];
+			if (s <= L) {
+				list_runs.push_back(r);
+				h->stat_group[0] += e - a;
+				max_s = std::max(max_s, s);
+			} else {
+				filter_runs.push_back(r);
+				h->stat_group[1] += e - a;
+			}
+		}
+		a = e;
+	}
+	h->stat_group[4] = filter_runs.size();
+
+	// the list tier: slots (one per query, a group's consecutive), passes of slots, work items
+	const int cus = num_cus(h->device);
+	uint32_t cap = std::max<uint32_t>(2048, pow2ceil(max_s));  // (2048: the select's wave path; a whole number of 16-row steps)
+	cap = std::min(std::max(cap, pow2ceil((uint32_t)(2 * k))), kMaxCap);
+	const size_t pass_slots = std::min(kMaxQueriesPerPass, kGroupPassKeys / cap);
+	struct ListPass {
+		uint32_t slot_begin, slots, item_begin, items;
+	};
+	std::vector<ListPass> passes;
+	std::vector<uint32_t> slot_query;
+	std::vector<GroupItem> items;
+	if (!list_runs.empty()) {
+		constexpr uint32_t TQ = kGroupScanTQ;
+		uint64_t tile_steps = 0;
+		for (const Run& r : list_runs) {
+			const uint32_t s = dir.off[r.bucket + 1] - dir.off[r.bucket];
+			tile_steps += (uint64_t)((r.end - r.begin + TQ - 1) / TQ) * ((s + kRowsPerGroup - 1) / kRowsPerGroup);
+		}
+		// ~16 workgroups per CU in total, at least 8 steps (128 rows) per workgroup: the direct scan's rule
+		const uint32_t steps_per_item = (uint32_t)std::max<uint64_t>(8, (tile_steps + 16ull * cus - 1) / (16ull * cus));
+		slot_query.reserve(h->stat_group[0]);
+		ListPass cur{0, 0, 0, 0};
+		for (const Run& r : list_runs) {
+			const uint32_t s = dir.off[r.bucket + 1] - dir.off[r.bucket];
+			const uint32_t steps = (s + kRowsPerGroup - 1) / kRowsPerGroup;
+			for (uint32_t a = r.begin; a < r.end; a += TQ) {
+				const uint32_t nq = std::min<uint32_t>(TQ, r.end - a);
+				if (cur.slots + nq > pass_slots) {  // (a tile never straddles two passes)
+					passes.push_back(cur);
+					cur = ListPass{cur.slot_begin + cur.slots, 0, (uint32_t)items.size(), 0};
+				}
+				for (uint32_t g0 = 0; g0 < steps; g0 += steps_per_item) {
+					GroupItem it{};
+					it.slot0 = cur.slots;  // (relative to the pass)
+					it.nq = nq;
+					it.list_off = dir.off[r.bucket];
+					it.list_len = s;
+					it.g0 = g0;
+					it.g1 = std::min(steps, g0 + steps_per_item);
+					items.push_back(it);
+					cur.items++;
+				}
+				for (uint32_t j = 0; j < nq; ++j)
+					slot_query.push_back(perm[a + j]);
+				cur.slots += nq;
+			}
+		}
+		passes.push_back(cur);
+	}
+
+	// one upload through pinned staging: [perm | slot_query | items]
+	const size_t off_slot = sizeof(uint32_t) * m;
+	const size_t off_items = (off_slot + sizeof(uint32_t) * slot_query.size() + 31) / 32 * 32;
+	const size_t tab_bytes = off_items + sizeof(GroupItem) * items.size();
+	if (tab_bytes > h->h_group_tab_bytes) {
+		h->h_group_tab.reset();
+		h->h_group_tab_bytes = 0;
+		const size_t want = std::max<size_t>(tab_bytes + tab_bytes / 2, 64u << 10);
+		HIP_TRY(h, hipHostMalloc(&h->h_group_tab, want, hipHostMallocDefault));
+		h->h_group_tab_bytes = want;
+	}
+	HIP_TRY(h, h->d_group_tab.ensure(h->h_group_tab_bytes));
+	char* const tab = h->h_group_tab.as<char>();
+	std::memcpy(tab, perm.data(), sizeof(uint32_t) * m);
+	if (!slot_query.empty())
+		std::memcpy(tab + off_slot, slot_query.data(), sizeof(uint32_t) * slot_query.size());
+	if (!items.empty())
+		std::memcpy(tab + off_items, items.data(), sizeof(GroupItem) * items.size());
+	HIP_TRY(h, hipMemcpyAsync(h->d_group_tab, tab, tab_bytes, hipMemcpyHostToDevice, st));
+	const char* const d_tab = h->d_group_tab.as<char>();
+	const uint32_t* const d_perm = reinterpret_cast<const uint32_t*>(d_tab);
+	const uint32_t* const d_slot_query = reinterpret_cast<const uint32_t*>(d_tab + off_slot);
+	const GroupItem* const d_items = reinterpret_cast<const GroupItem*>(d_tab + off_items);
+
+	// labels no row carries: padding
+	if (pad_run.end > pad_run.begin) {
+		const size_t cnt = pad_run.end - pad_run.begin;
+		hipLaunchKernelGGL(group_pad_rows_kernel, dim3((uint32_t)std::min<size_t>((cnt * k + kBlock - 1) / kBlock, 4096)),
+		                   dim3(kBlock), 0, st, d_perm + pad_run.begin, (uint32_t)cnt, (uint32_t)k, d_ids, d_dists);
+		HIP_TRY(h, hipGetLastError());
+	}
+	// ANY: the plain search
+	if (any_run.end > any_run.begin) {
+		const int rc = grouped_tier(h, d_queries, d_perm + any_run.begin, any_run.end - any_run.begin, k, d_ids, d_dists, st);
+		if (rc != EXPANN_OK)
+			return rc;
+	}
+	// filter groups, in turn: the group's bitmap through the row filter's own path (one host wait each), the filtered
+	// search of its queries
+	for (const Run& r : filter_runs) {
+		size_t words = 0;
+		if (const int rc = filter_begin(h, &words))
+			return rc;
+		hipLaunchKernelGGL(group_bits_kernel, dim3((uint32_t)((words + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+		                   h->d_row_groups.as<const uint32_t>(), (uint32_t)h->n, dir.keys[r.bucket],
+		                   h->d_filter_bits.as<uint32_t>(), (uint32_t)words);
+		HIP_TRY(h, hipGetLastError());
+		if (const int rc = filter_finish(h, st, words))
+			return rc;
+		const int rc = grouped_tier(h, d_queries, d_perm + r.begin, r.end - r.begin, k, d_ids, d_dists, st);
+		h->filter_on = false;
+		if (rc != EXPANN_OK)
+			return rc;
+	}
+	// list groups: one scan launch and one select launch per pass (the passes above have drained: the workspace is free)
+	if (!passes.empty()) {
+		const size_t lds = sizeof(float) * kGroupScanTQ * (size_t)h->dim;
+		const GroupScanFn fn = group_scan_fn(h);
+		if (lds > (64u << 10) && !h->group_lds_set) {
+			HIP_TRY(h, hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+			h->group_lds_set = true;
+		}
+		uint32_t most_slots = 0;
+		for (const ListPass& lp : passes)
+			most_slots = std::max(most_slots, lp.slots);
+		if (const int rc = ensure_workspace(h, most_slots, cap))  // (once: no buffer grows under a pass in flight)
+			return rc;
+		for (const ListPass& lp : passes) {
+			GroupScanParams gp{};
+			gp.base = h->d_base;
+			gp.n_rows = (uint32_t)h->n;
+			gp.dim = (uint32_t)h->dim;
+			gp.queries = d_queries;
+			gp.slot_query = d_slot_query + lp.slot_begin;
+			gp.group_rows = h->d_group_rows;
+			gp.items = d_items + lp.item_begin;
+			gp.cand_cnt = h->d_cnt;
+			gp.cand = h->d_cand;
+			gp.cap = cap;
+			const bool timed = h->profiling && h->ev_used < kEventPairs;
+			if (timed)
+				HIP_TRY(h, hipEventRecord(h->ev[h->ev_used][0], st));
+			hipLaunchKernelGGL(fn, dim3(lp.items), dim3(kBlock), lds, st, gp);
+			if (timed) {
+				HIP_TRY(h, hipEventRecord(h->ev[h->ev_used][1], st));
+				h->ev_used++;
+			}
+			HIP_TRY(h, hipGetLastError());
+			SelectParams sel{};
+			sel.cand = h->d_cand;
+			sel.cand_cnt = h->d_cnt;
+			sel.cap = cap;
+			sel.k = (uint32_t)k;
+			sel.id_offset = h->id_offset;
+			sel.out_ids = d_ids;
+			sel.out_dists = d_dists;
+			sel.dim = (uint32_t)h->dim;
+			sel.metric_ip = h->metric == EXPANN_METRIC_IP ? 1u : 0u;
+			sel.overflow = h->d_overflow;
+			sel.wave0_short = 1;  // (lists of <= 2048 keys: one wave orders them; longer ones: the whole workgroup)
+			sel.slot_map = d_slot_query + lp.slot_begin;
+			hipLaunchKernelGGL(select_topk_fn(h, sel), dim3(lp.slots), dim3(kBlock), sizeof(uint64_t) * cap + 16, st, sel);
+			HIP_TRY(h, hipGetLastError());
+		}
+	}
+	HIP_TRY(h, hipStreamSynchronize(st));
+	return EXPANN_OK;
+}
+
 }  // namespace
 
 int expann_set_row_filter(expann_index* h, const uint32_t* allow_bits, size_t n_words) {
@@ -3773,6 +4201,69 @@ int expann_clear_row_filter(expann_index* h) {
 		HIP_TRY(h, hipStreamSynchronize(h->async_stream));
 	}
 	h->filter_on = false;
+	return EXPANN_OK;
+}
+
+int expann_set_row_groups(expann_index* h, const uint32_t* groups, size_t n) {
+	return set_row_groups(h, groups, n, false, nullptr);
+}
+
+int expann_set_row_groups_device(expann_index* h, const uint32_t* d_groups, size_t n, void* stream) {
+	return set_row_groups(h, d_groups, n, true, (hipStream_t)stream);
+}
+
+int expann_clear_row_groups(expann_index* h) {
+	if (!h)
+		return EXPANN_ERR_INVALID_ARG;
+	if (h->async_pending > 0) {
+		HIP_TRY(h, hipSetDevice(h->device));
+		HIP_TRY(h, hipStreamSynchronize(h->async_stream));
+	}
+	drop_row_groups(h);
+	return EXPANN_OK;
+}
+
+int expann_search_grouped_device(expann_index* h, const void* d_queries, const uint32_t* query_groups, size_t m, size_t k,
+                                 uint64_t* d_ids, float* d_dists, void* stream) {
+	bool empty = false;
+	if (const int rc = grouped_args(h, d_queries, query_groups, m, k, d_ids, &empty))
+		return rc;
+	if (empty)
+		return EXPANN_OK;
+	if (h->async_pending) {  // deferred searches first
+		const int rs = expann_sync(h);
+		if (rs != EXPANN_OK)
+			return rs;
+	}
+	HIP_TRY(h, hipSetDevice(h->device));
+	return grouped_search_device(h, d_queries, query_groups, m, k, d_ids, d_dists, stream ? (hipStream_t)stream : h->stream);
+}
+
+int expann_search_grouped(expann_index* h, const void* queries, const uint32_t* query_groups, size_t m, size_t k,
+                          uint64_t* ids, float* dists) {
+	bool empty = false;
+	if (const int rc = grouped_args(h, queries, query_groups, m, k, ids, &empty))
+		return rc;
+	if (empty)
+		return EXPANN_OK;
+	if (h->async_pending) {  // deferred searches first
+		const int rs = expann_sync(h);
+		if (rs != EXPANN_OK)
+			return rs;
+	}
+	HIP_TRY(h, hipSetDevice(h->device));
+	const size_t qbytes = m * (size_t)h->dim * h->q_elem;
+	HIP_TRY(h, h->d_q.ensure(qbytes));
+	HIP_TRY(h, h->d_ids.ensure(sizeof(uint64_t) * m * k));
+	HIP_TRY(h, h->d_dists.ensure(sizeof(float) * m * k));
+	HIP_TRY(h, hipMemcpyAsync(h->d_q, queries, qbytes, hipMemcpyHostToDevice, h->stream));
+	const int rc = grouped_search_device(h, h->d_q, query_groups, m, k, h->d_ids, h->d_dists, h->stream);
+	if (rc != EXPANN_OK)
+		return rc;
+	HIP_TRY(h, hipMemcpyAsync(ids, h->d_ids, sizeof(uint64_t) * m * k, hipMemcpyDeviceToHost, h->stream));
+	if (dists)
+		HIP_TRY(h, hipMemcpyAsync(dists, h->d_dists, sizeof(float) * m * k, hipMemcpyDeviceToHost, h->stream));
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
 	return EXPANN_OK;
 }
 
@@ -3830,6 +4321,11 @@ int expann_set_option(expann_index* h, const char* name, long value) {
 		h->opt_sample_frac = value < 0 ? 0 : value;
 	else if (!std::strcmp(name, "sample_ratio"))
 		h->opt_sample_ratio = value < 2 ? 2 : value;
+	else if (!std::strcmp(name, "group_list_rows")) {
+		if (value < 0 || value > (long)kMaxCap)
+			return h->fail(EXPANN_ERR_INVALID_ARG, "group_list_rows: 0 (auto) or 1.." + std::to_string(kMaxCap));
+		h->opt_group_list_rows = value;
+	}
 	else
 		return h->fail(EXPANN_ERR_INVALID_ARG, std::string("unknown option ") + name);
 	return EXPANN_OK;

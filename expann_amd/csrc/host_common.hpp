@@ -3,7 +3,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <string>
+#include <vector>
 
 #include "../../include/expann_hip.h"
 
@@ -85,6 +87,39 @@ template <typename T> struct GrowPtr : DevPtr<T> {
 		bytes = 0;
 	}
 };
+
+// The directory of a row-group labelling (expann_graph_set_row_groups, expann_set_row_groups): the distinct labels
+// ascending with 0xFFFFFFFF (EXPANN_GROUP_ANY: the row belongs to no group) left out, their offsets, and each
+// group's rows ascending -- rows[off[g], off[g + 1]) carry keys[g].  Made on the host with a stable sort by label:
+// set time is no hot path.
+struct GroupDirectory {
+	std::vector<uint32_t> keys;  // [groups]
+	std::vector<uint32_t> off;   // [groups + 1]
+	std::vector<uint32_t> rows;  // [n]: the rows by (label, row); the first off.back() of them belong to a group
+	size_t n_rows() const { return off.back(); }
+	// the group that carries `label`, or keys.size() when no row does
+	size_t find(uint32_t label) const {
+		const auto it = std::lower_bound(keys.begin(), keys.end(), label);
+		return (it != keys.end() && *it == label) ? (size_t)(it - keys.begin()) : keys.size();
+	}
+};
+inline GroupDirectory build_group_directory(const uint32_t* lab, size_t n) {
+	GroupDirectory d;
+	d.rows.resize(n);
+	for (size_t v = 0; v < n; ++v)
+		d.rows[v] = (uint32_t)v;
+	std::stable_sort(d.rows.begin(), d.rows.end(), [&](uint32_t a, uint32_t b) { return lab[a] < lab[b]; });
+	size_t n_rows = n;  // rows labelled 0xFFFFFFFF sort last and belong to no group
+	while (n_rows && lab[d.rows[n_rows - 1]] == 0xFFFFFFFFu)
+		--n_rows;
+	for (size_t i = 0; i < n_rows; ++i)
+		if (i == 0 || lab[d.rows[i]] != lab[d.rows[i - 1]]) {
+			d.keys.push_back(lab[d.rows[i]]);
+			d.off.push_back((uint32_t)i);
+		}
+	d.off.push_back((uint32_t)n_rows);
+	return d;
+}
 
 // what expann_*_last_error(NULL) reports: the failure of the last create call of this thread
 extern thread_local std::string g_create_error;

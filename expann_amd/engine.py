@@ -79,8 +79,10 @@ class GpuBruteForceEngine:
         return [int(x) for x in row[row != np.uint64(2 ** 64 - 1)]]
 
     # ---- extensions ---------------------------------------------------------------
-    def query_k_batch(self, queries, k):
-        """(ids[m,k] uint64, dists[m,k] float32); short rows padded with 2^64-1 / +inf."""
+    def query_k_batch(self, queries, k, groups=None):
+        """(ids[m,k] uint64, dists[m,k] float32); short rows padded with 2^64-1 / +inf.
+        groups: a uint32 array [m] (host) -- query i returns only rows of the group it names
+        (expann_search_grouped after set_row_groups; _lib.GROUP_ANY = every row)."""
         qdt = np.float32 if self.dtype in _F32_QUERIES else _NP_DTYPE[self.dtype]
         queries = np.ascontiguousarray(queries, dtype=qdt)
         if queries.ndim != 2 or queries.shape[1] != self.dim:
@@ -88,14 +90,34 @@ class GpuBruteForceEngine:
         m = queries.shape[0]
         ids = np.empty((m, k), dtype=np.uint64)
         dists = np.empty((m, k), dtype=np.float32)
+        if groups is not None:
+            groups = self._query_groups(groups, m)
+            _lib.check(self._h, self._L.expann_search_grouped(self._h, queries.ctypes.data, groups.ctypes.data, m, k,
+                                                              ids.ctypes.data, dists.ctypes.data))
+            return ids, dists
         _lib.check(self._h, self._L.expann_search(self._h, queries.ctypes.data, m, k,
                                                   ids.ctypes.data, dists.ctypes.data))
         return ids, dists
 
+    @staticmethod
+    def _query_groups(groups, m):
+        groups = np.ascontiguousarray(groups, dtype=np.uint32).reshape(-1)
+        if groups.size != m:
+            raise ValueError(f"groups must be [{m}]")
+        return groups
+
     def set_base_device(self, ptr, n, id_offset=0):
         _lib.check(self._h, self._L.expann_set_base_device(self._h, C.c_void_p(ptr), n, id_offset))
 
-    def search_device(self, q_ptr, m, k, ids_ptr, dists_ptr, stream=0):
+    def search_device(self, q_ptr, m, k, ids_ptr, dists_ptr, stream=0, groups=None):
+        """expann_search_device; with groups (a HOST uint32 array [m]) expann_search_grouped_device, which
+        returns after `stream` has drained."""
+        if groups is not None:
+            groups = self._query_groups(groups, m)
+            _lib.check(self._h, self._L.expann_search_grouped_device(
+                self._h, C.c_void_p(q_ptr), groups.ctypes.data, m, k, C.c_void_p(ids_ptr), C.c_void_p(dists_ptr),
+                C.c_void_p(stream)))
+            return
         _lib.check(self._h, self._L.expann_search_device(
             self._h, C.c_void_p(q_ptr), m, k, C.c_void_p(ids_ptr), C.c_void_p(dists_ptr),
             C.c_void_p(stream)))
@@ -140,12 +162,29 @@ class GpuBruteForceEngine:
         _lib.check(self._h, self._L.expann_set_row_filter_device(self._h, C.c_void_p(ptr), int(n_words),
                                                                  C.c_void_p(stream)))
 
+    def set_row_groups(self, groups):
+        """expann_set_row_groups: groups[n] (uint32) names the group of every local row; query_k_batch(...,
+        groups=) and search_device(..., groups=) then serve each query from the group it names.  A row labelled
+        _lib.GROUP_ANY belongs to no group.  None drops the groups (expann_clear_row_groups).  fp32 / fp16 rows."""
+        if groups is None:
+            _lib.check(self._h, self._L.expann_clear_row_groups(self._h))
+            return
+        groups = np.ascontiguousarray(groups, dtype=np.uint32).reshape(-1)
+        _lib.check(self._h, self._L.expann_set_row_groups(self._h, groups.ctypes.data, groups.size))
+
+    def set_row_groups_device(self, ptr, n, stream=0):
+        """expann_set_row_groups_device: the same from n uint32 labels in device memory, read in the order of
+        `stream`."""
+        _lib.check(self._h, self._L.expann_set_row_groups_device(self._h, C.c_void_p(ptr), int(n), C.c_void_p(stream)))
+
     def get_stat(self, name):
         """expann_get_stat: "redo_queries", "redo_candidates", "redo_overflows", "spec_rank" (speculative thresholds);
         "i8_sample" (1: the last search's sampled pass ran on the int8 matrix cores);
         "rerank_rows" (rows the last search's selects re-scored exactly; counted under the option "rerank_stats");
         "filter_active" (0 / 1) and "filter_rows" (rows the row filter allows; n when none is set);
-        "base_bytes" (device bytes of the rows themselves: n * dim * element size)."""
+        "base_bytes" (device bytes of the rows themselves: n * dim * element size);
+        "groups_active", "group_count", and of the last grouped search "group_list_queries", "group_filter_queries",
+        "group_any_queries", "group_pad_queries", "group_filter_passes"."""
         v = C.c_uint64(0)
         _lib.check(self._h, self._L.expann_get_stat(self._h, name.encode(), C.byref(v)))
         return int(v.value)

@@ -133,6 +133,17 @@ struct gpu_brute_force_engine : public ann_engine<T, gpu_brute_force_engine<T>> 
 		single("clear_row_filter");
 		check(expann_clear_row_filter(handle));
 	}
+	// Extension: row groups (expann_set_row_groups).  groups[n] gives every local row a uint32 label; a grouped batch
+	// then names one label per query (host memory) and query i returns only rows with groups[r] == query_groups[i]
+	// (EXPANN_GROUP_ANY: every row, the plain search bit for bit).  nullptr drops the groups.  One device, float rows.
+	void set_row_groups(const uint32_t* groups, size_t n) {
+		single("set_row_groups");
+		check(groups ? expann_set_row_groups(handle, groups, n) : expann_clear_row_groups(handle));
+	}
+	void query_k_batch_grouped(const T* queries, const uint32_t* query_groups, size_t m, size_t k, uint64_t* ids, float* dists) {
+		single("query_k_batch_grouped");
+		check(expann_search_grouped(handle, queries, query_groups, m, k, ids, dists));
+	}
 	const std::string _name() { return "GPU Brute-Force Engine (MI355X)"; }
 	const param_list_t _param_list() {
 		param_list_t pl;

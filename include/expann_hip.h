@@ -552,8 +552,9 @@ uint32_t expann_spec_rank_auto(size_t k, uint32_t sample_frac);
  * speculative thresholds ("spec_rank"), whatever those options say, and never the bf16x3 form ("scan_kernel" 3
  * runs the exact direct scan, as do queries outside the fp16 range).
  * expann_sharded_* does not offer the filter (its set_option pass-through is unchanged and there is no
- * sharded entry point for it); a per-query filter is not offered either.  The graph engine has a row filter of its
- * own: expann_graph_set_row_filter, below, and a per-query form of it: expann_graph_set_row_groups.
+ * sharded entry point for it).  Per query: row groups, expann_set_row_groups at the end of this header.  The graph
+ * engine has a row filter of its own: expann_graph_set_row_filter, below, and a per-query form of it:
+ * expann_graph_set_row_groups.
  * expann_get_stat: "filter_active" (0 / 1), "filter_rows" (allowed rows; n when no filter is set). */
 int expann_set_row_filter(expann_index* h, const uint32_t* allow_bits, size_t n_words);        /* host bits   */
 int expann_set_row_filter_device(expann_index* h, const uint32_t* d_allow_bits, size_t n_words, void* stream);
@@ -685,8 +686,8 @@ int expann_antitopo_set_rows_f16(expann_antitopo* e, int on);
  * expann_antitopo_store*, _build and _load clear the groups: they are a run-time property and are not written to
  * the index file.
  * Not offered: a grouped search while a row filter is in force (bitmap x groups), several groups per row or a set
- * of groups per query, groups for expann_graph_build_batched's searches, groups on the brute-force and sharded
- * handles. */
+ * of groups per query, groups for expann_graph_build_batched's searches, groups on the sharded handles.  (The
+ * brute-force index has row groups of its own: expann_set_row_groups, at the end of this header.) */
 #define EXPANN_GROUP_ANY 0xFFFFFFFFu
 int expann_graph_set_row_groups(expann_graph* g, const uint32_t* groups, size_t n);            /* host [n] */
 int expann_graph_set_row_groups_device(expann_graph* g, const uint32_t* d_groups, size_t n, void* stream);
@@ -702,6 +703,68 @@ int expann_antitopo_query_grouped(expann_antitopo* e, const float* queries, cons
                                   size_t m, size_t k, uint64_t* ids, float* dists);
 int expann_antitopo_query_grouped_device(expann_antitopo* e, const float* d_queries, const uint32_t* d_query_groups,
                                          size_t m, size_t k, uint64_t* d_ids, float* d_dists, void* stream);
+
+/* Row groups of the brute-force index: every query of a batch names the rows it may return (appended;
+ * EXPANN_ABI_VERSION stays 2: nothing that existed changed).
+ * THE GROUP RULE.  groups[r] is the group of LOCAL row r -- the row number before id_offset -- and may be any
+ * uint32.  Query i of a grouped search may return exactly the rows with groups[r] == query_groups[i].  For a fixed
+ * label X the answer is, bit for bit (ids with id_offset applied, fp32 distance bits, ties by lower id, padding with
+ * UINT64_MAX / +inf), what expann_set_row_filter(bits of groups == X) followed by expann_search returns on the same
+ * handle: what an index of only those rows returns, with its ids mapped back.  A query that names EXPANN_GROUP_ANY
+ * gets the unfiltered search, bit for bit.  A row labelled 0xFFFFFFFF therefore belongs to no group: only ANY queries
+ * return it.  The exact top-k by (score, id) in the reference's arithmetic is unique, so how a query is served never
+ * shows in its answer.
+ * query_groups IS HOST MEMORY in both search calls, on purpose: the queries of a batch are bucketed by group on the
+ * host before anything is launched, a serving process knows its requests' tenants on the host, and a device array
+ * would put a copy and a host wait in front of every search.  (The graph engine takes device labels because its
+ * kernels serve each query on its own.)
+ * How a batch is served.  Let s be the number of rows that carry a query's label and L the option "group_list_rows"
+ * (expann_set_option: 0 = auto; v > 0: groups of at most v rows take the list kernel, so 1 is in effect "always a
+ * filter pass"; v > 16384 -- the longest list the select sorts in LDS -- EXPANN_ERR_INVALID_ARG).  Auto = 16384,
+ * measured on 1 M x d128 fp32 rows at k = 10 (profiles/bf_groups_ab.txt): with groups of 1 024 .. 16 384 rows tiling
+ * the index, at 10 and at 100 queries per group, the list kernel was never the slower way (x 0.005 of the filter
+ * passes' time at 1 024 rows and 10 queries per group, x 0.82 at 16 384 rows and 100).
+ *   s == 0: padding only.
+ *   ANY: the plain search over these queries (gathered into contiguous staging, scattered back; a batch that is
+ *   all ANY runs in place), exactly the launches expann_search_device makes.
+ *   s <= L (list): ONE launch of the list kernel (csrc/scan_groups.hpp) serves every such group of the batch -- a
+ *   workgroup per (tile of queries that share a group, chunk of that group's rows), exact keys of every row of the
+ *   group -- and one select launch writes the callers' rows.  No host wait.
+ *   s > L (filter): at most n / L distinct labels are this large.  For each one present in the batch, in turn: the
+ *   group's bitmap is made from the labels on the device and installed through the row filter's own path, the
+ *   filtered search (all of its regimes and retries) serves the group's gathered queries, the rows are scattered
+ *   back.  ONE HOST WAIT PER DISTINCT SUCH GROUP IN THE BATCH.  Afterwards the handle has no filter, also when a step
+ *   failed.
+ * A grouped search returns after its stream has drained: it ignores "async_search" and first waits for outstanding
+ * deferred searches (as expann_search does).  The plain searches ignore the groups entirely and launch exactly what
+ * they launch without them.
+ * Set calls.  They first wait on the host for outstanding deferred searches.  The library keeps its own copy -- the
+ * labels on the device, and a directory made on the host: the distinct labels ascending, their offsets, each group's
+ * rows ascending -- so the caller may free its array on return.  Everything is built aside and swapped in when
+ * complete: a failed call leaves the groups as they were.  expann_set_row_groups_device reads d_groups in the order
+ * of `stream` (a hipStream_t; NULL = the handle's own) and returns after that stream and the handle's own have
+ * drained.  expann_build and expann_set_base_device clear the groups, as they clear the filter;
+ * expann_clear_row_groups drops them.
+ * Errors of the set calls, in this order, the first three before the device is touched: handle or array NULL
+ * EXPANN_ERR_INVALID_ARG; a dtype other than EXPANN_DTYPE_F32 / EXPANN_DTYPE_F16 EXPANN_ERR_UNSUPPORTED (the row
+ * filter's rule, for its reason); n != expann_size(h) EXPANN_ERR_INVALID_ARG; no rows on the device yet
+ * EXPANN_ERR_NOT_BUILT.
+ * Grouped searches run expann_search's checks in its order (k in 1..8192; m == 0 is EXPANN_OK); then query_groups
+ * NULL EXPANN_ERR_INVALID_ARG; then no groups set EXPANN_ERR_NOT_BUILT; then a row filter in force
+ * EXPANN_ERR_UNSUPPORTED.
+ * expann_get_stat: "groups_active" (0 / 1); "group_count" (distinct labels other than 0xFFFFFFFF); of the last
+ * grouped search: "group_list_queries", "group_filter_queries", "group_any_queries", "group_pad_queries" (they add
+ * up to m) and "group_filter_passes" (distinct filter groups it served).  "filter_active" reads 0 after a grouped
+ * search.
+ * Not offered: groups on the sharded handles, on 8-bit / int16 rows, groups together with the bitmap, several groups
+ * per row or a set of groups per query, deferred grouped searches. */
+int expann_set_row_groups(expann_index* h, const uint32_t* groups, size_t n);                 /* host [n] */
+int expann_set_row_groups_device(expann_index* h, const uint32_t* d_groups, size_t n, void* stream);
+int expann_clear_row_groups(expann_index* h);
+int expann_search_grouped(expann_index* h, const void* queries, const uint32_t* query_groups, size_t m,
+                          size_t k, uint64_t* ids, float* dists);                              /* host buffers */
+int expann_search_grouped_device(expann_index* h, const void* d_queries, const uint32_t* query_groups /* HOST [m] */,
+                                 size_t m, size_t k, uint64_t* d_ids, float* d_dists, void* stream);
 
 #ifdef __cplusplus
 }
