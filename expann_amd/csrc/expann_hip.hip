@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "bf_options.hpp"
 #include "host_common.hpp"
 #include "scan_f32.hpp"
 #include "scan_gemm_bf16.hpp"
@@ -44,7 +45,7 @@ thread_local std::string g_create_error;
 
 namespace {
 
-constexpr uint32_t kMaxCap = 16384;      // keys per query that fit the select kernel's LDS
+// (kMaxCap, the keys per query that fit the select kernel's LDS: bf_options.hpp, where an option's bound names it)
 static_assert(kMaxK == kMaxCap / 2, "the bound on k: a candidate list holds at least 2k keys");
 constexpr size_t kMaxQueriesPerPass = 32768;
 constexpr int kEventPairs = 64;
@@ -65,20 +66,102 @@ struct Level {
 
 }  // namespace
 
-struct expann_index {
+// The handle's state, grouped by who makes it and when it dies: each group is a base of expann_index (use sites
+// read h->d_base_f16), and a group is forgotten as a value -- h->forget<RowCopies>() frees and resets every member
+// it has, so a member added to a group needs no edit anywhere else.
+
+// what expann_create fixes, and the options (bf_options.hpp)
+struct Config : Options {
 	int dim = 0, dtype = 0, metric = 0, device = 0;
 	size_t elem = 4;    // bytes per stored element
 	size_t q_elem = 4;  // bytes per query element at the ABI (f32 for F32/U8 rows, int8 for I8)
 	int int_mode = -1;  // IntMode for 8-bit rows
-	GrowPtr<uint8_t> d_q8;  // U8 rows: queries truncated to uint8
+	bool strict_u8 = false;          // (on the shadow) non-8-bit / fractional queries: hand back, no error
+};
+
+// the rows: staged on the host until build(), then on the device -- the handle's own copy, or the caller's memory
+// (expann_set_base_device)
+struct Rows {
 	std::vector<unsigned char> staging;  // store_vector() rows until build()
 	size_t n_staged = 0;
-	void* d_base = nullptr;
-	bool owns_base = false;
+	MaybeOwnedPtr d_base;
 	size_t n = 0;
 	uint64_t id_offset = 0;
-	hipStream_t stream = nullptr;
-	// workspace (grown on demand)
+};
+
+struct HandleDeleter {
+	void operator()(expann_index* h) const { expann_destroy(h); }
+};
+// fp32 index whose values are all integers in [0, 255] (SIFT): searches with integer queries
+// go through an internal uint8 engine -- exact integer scores, equal to the fp32 ones bit for
+// bit while d * 255^2 < 2^24 -- at the 8-bit kernels' speed
+struct U8Shadow {
+	int u8_exact = 0;                // 0 not examined, 1 yes (shadow built), -1 no
+	DevPtr<void> d_base_u8;
+	std::unique_ptr<expann_index, HandleDeleter> u8_shadow;  // (reads d_base_u8: declared after it, so it goes first)
+};
+
+// copies and terms derived from the rows, built lazily, dead when the rows change
+struct RowCopies : U8Shadow {
+	DevPtr<float> d_bnorm;           // ||b||^2 (1-eps) per row (GEMM-form scan), built lazily
+	DevPtr<float> d_bnorm_bf;        // same with the bf16x3 slack
+	DevPtr<float> d_bnmax;           // [2]: max of d_bnorm, max of d_bnorm_bf
+	float f16_bnmax = 0.0f;          // max ||b||^2 (host copy lives in d_bnmax[2])
+	DevPtr<void> d_base_split;       // [n][2][dim] bf16 hi/lo planes (bf16x3 GEMM form), lazily
+	DevPtr<void> d_base_f16;         // [n][dim] fp16 rows scaled by f16_scale (fp16 GEMM form), lazily
+	DevPtr<float> d_bnorm_f16;       // [n] ||b||^2 (1-eps) - abs |b|
+	DevPtr<float> d_bns_f16;         // [n] ||b||^2 (1+eps) + abs |b|: the sampled pass's row term
+	float f16_scale = 0.0f;          // power of two; 0 = not built
+	size_t f16_n_pad = 0;            // rows of the fp16 copy and of its row-term arrays (whole tiles)
+	// int8 filter of fp32 rows (scan_gemm_i8f.hpp), built lazily beside the fp16 copy (whose sampled pass
+	// gives its thresholds) and dropped with it
+	DevPtr<void> d_base_i8f;         // [n padded to 64][dim] int8
+	DevPtr<int> d_bp_i8f;            // [n padded] integer row terms; kI8qPadBp on the padding
+	DevPtr<float> d_rw_i8f;          // [n] w_b (select pruning), +inf where bp was clamped
+	DevPtr<int> d_cb_i8f;            // [n padded] centre row terms of the int8 sampled pass; kI8fCbNone: no such row
+	DevPtr<float> d_wbmax_i8f;       // [1] the largest w_b among the rows with a centre term
+	I8fConsts i8f{};
+	int i8f_state = 0;               // 0 not built, 1 built, 2 built but off for auto (lists too long), -1 unusable
+	DevPtr<int> d_bias_i;            // [n] sum b^2 per row (8-bit L2 GEMM form), built lazily
+	MaybeOwnedPtr d_base_i8q;        // padded int8 copy of an 8-bit index (uint8 rows ^ 0x80) or alias of d_base
+	DevPtr<int> d_bp_i8q;            // [n padded] floor(bias/2), scan_gemm_i8q.hpp
+};
+
+// row filter (expann_set_row_filter): the engine's copy of the bitmap, the allowed rows'
+// count, an ascending list of them (complete up to kFilterListCap rows, an even sample beyond) and the masked
+// copies of the fp16 forms' row terms (NaN on every disallowed row), made lazily after ensure_f16
+struct RowFilter {
+	bool filter_on = false;
+	DevPtr<uint32_t> d_filter_bits;  // [filter_words]: whole 128-row tiles, zero from row n on
+	size_t filter_words = 0;
+	DevPtr<uint32_t> d_filter_stat;  // [2 + kFilterSegs]: count, OR of the words, per-segment counts
+	DevPtr<uint32_t> d_filter_list;  // [kFilterListCap]
+	uint32_t filter_list_len = 0, filter_list_stride = 1;
+	size_t n_allowed = 0;
+	uint32_t filter_residues = 0;    // bit r: some allowed row has row % 32 == r
+	DevPtr<float> d_bnorm_f16_m;     // [f16_n_pad] d_bnorm_f16 under the filter
+	DevPtr<float> d_bns_f16_m;       // [f16_n_pad] d_bns_f16 under the filter
+	bool filter_terms_valid = false;
+};
+
+// row groups (expann_set_row_groups): the labels and each group's rows on the device, the
+// directory's labels and offsets on the host, where a grouped search is planned; and that search's staging
+struct RowGroups {
+	bool groups_on = false;
+	DevPtr<uint32_t> d_row_groups;   // [n]
+	DevPtr<uint32_t> d_group_rows;   // [rows that carry a label other than 0xFFFFFFFF], by (label, row)
+	GroupDirectory group_dir;        // keys and off (the rows live in d_group_rows)
+	PinPtr<void> h_group_tab;        // pinned: [sorted query numbers | list slots' queries | work items]
+	size_t h_group_tab_bytes = 0;
+	GrowPtr<void> d_group_tab;
+	GrowPtr<void> d_group_q;         // gathered queries of one tier
+	GrowPtr<uint64_t> d_group_ids;   // ... and their result rows
+	GrowPtr<float> d_group_dists;
+};
+
+// per-search workspace (grown on demand); survives a change of rows
+struct Workspace {
+	GrowPtr<uint8_t> d_q8;  // U8 rows: queries truncated to uint8
 	GrowPtr<uint64_t> d_cand;
 	DevPtr<uint32_t> d_cnt;          // [m_alloc]
 	DevPtr<float> d_tau[2];
@@ -88,7 +171,7 @@ struct expann_index {
 	DevPtr<uint32_t> d_tau_row[2];
 	size_t m_alloc = 0;
 	DevPtr<uint32_t> d_overflow;     // [4]: overflow count
-	unsigned long long* d_total = nullptr;
+	unsigned long long* d_total = nullptr;  // (inside d_overflow's block)
 	PinPtr<uint32_t> h_flags;        // pinned [4]
 	// latency mode (expann_search with few queries): pinned staging [queries | ids | dists]; the
 	// select kernels store the results straight into it, so a search costs one async H2D copy of
@@ -97,22 +180,6 @@ struct expann_index {
 	bool q_in_pinned_host = false;  // (expann_search -> search_pass: d_queries is pinned host memory)
 	DevPtr<uint32_t> d_ticket;  // last-workgroup counter of sample_direct_f16_kernel (0 between launches)
 	size_t h_pin_bytes = 0;
-	DevPtr<float> d_bnorm;           // ||b||^2 (1-eps) per row (GEMM-form scan), built lazily
-	DevPtr<float> d_bnorm_bf;        // same with the bf16x3 slack
-	DevPtr<float> d_bnmax;           // [2]: max of d_bnorm, max of d_bnorm_bf
-	DevPtr<void> d_base_split;       // [n][2][dim] bf16 hi/lo planes (bf16x3 GEMM form), lazily
-	// fp32 index whose values are all integers in [0, 255] (SIFT): searches with integer queries
-	// go through an internal uint8 engine -- exact integer scores, equal to the fp32 ones bit for
-	// bit while d * 255^2 < 2^24 -- at the 8-bit kernels' speed
-	int u8_exact = 0;                // 0 not examined, 1 yes (shadow built), -1 no
-	expann_index* u8_shadow = nullptr;
-	DevPtr<void> d_base_u8;
-	bool strict_u8 = false;          // (on the shadow) non-8-bit / fractional queries: hand back, no error
-	double prof_extra_ms = 0;        // scan time absorbed from the shadow
-	long opt_u8_exact = 1;
-	void* d_base_i8q = nullptr;      // padded int8 copy of an 8-bit index (uint8 rows ^ 0x80) or alias of d_base
-	bool base_i8q_owned = false;
-	DevPtr<int> d_bp_i8q;            // [n padded] floor(bias/2), scan_gemm_i8q.hpp
 	DevPtr<void> d_log;              // per-wave hit logs of scan_gemm_f16x ([n_logs][log_cap] x 16 B)
 	DevPtr<uint32_t> d_log_cnt;      // [n_logs]
 	DevPtr<uint32_t> d_work_ctr;     // [8][16]: per-XCD item counters of the persistent scan launch
@@ -127,112 +194,57 @@ struct expann_index {
 	} pending_scatter;
 	GrowPtr<float> d_sample;         // [m][n_chunks][32] class maxima of the fp16 / int8 sample pass
 	GrowPtr<void> d_q_split;         // [m][2][dim] bf16 (or [m][dim] fp16)
-	DevPtr<void> d_base_f16;         // [n][dim] fp16 rows scaled by f16_scale (fp16 GEMM form), lazily
-	DevPtr<float> d_bnorm_f16;       // [n] ||b||^2 (1-eps) - abs |b|
-	DevPtr<float> d_bns_f16;         // [n] ||b||^2 (1+eps) + abs |b|: the sampled pass's row term
 	DevPtr<float> d_qnrm;            // [m_alloc] ||q||^2 (fp16 form, inner product: of the filter-side query c_q q)
 	DevPtr<float> d_qscale;          // [m_alloc] c_q: the power of two the fp16 filter sees a query multiplied by (inner product; L2: 1)
-	float f16_scale = 0.0f;          // power of two; 0 = not built
-	size_t f16_n_pad = 0;            // rows of the fp16 copy and of its row-term arrays (whole tiles)
-	// row filter (expann_set_row_filter): the engine's copy of the bitmap, the allowed rows'
-	// count, an ascending list of them (complete up to kFilterListCap rows, an even sample beyond) and the masked
-	// copies of the fp16 forms' row terms (NaN on every disallowed row), made lazily after ensure_f16
-	bool filter_on = false;
-	DevPtr<uint32_t> d_filter_bits;  // [filter_words]: whole 128-row tiles, zero from row n on
-	size_t filter_words = 0;
-	DevPtr<uint32_t> d_filter_stat;  // [2 + kFilterSegs]: count, OR of the words, per-segment counts
-	DevPtr<uint32_t> d_filter_list;  // [kFilterListCap]
-	uint32_t filter_list_len = 0, filter_list_stride = 1;
-	size_t n_allowed = 0;
-	uint32_t filter_residues = 0;    // bit r: some allowed row has row % 32 == r
-	DevPtr<float> d_bnorm_f16_m;     // [f16_n_pad] d_bnorm_f16 under the filter
-	DevPtr<float> d_bns_f16_m;       // [f16_n_pad] d_bns_f16 under the filter
-	bool filter_terms_valid = false;
-	// the row terms the fp16 forms read: the masked copies while a filter is set
-	const float* bnorm_f16() const { return filter_on ? d_bnorm_f16_m.p : d_bnorm_f16.p; }
-	const float* bns_f16() const { return filter_on ? d_bns_f16_m.p : d_bns_f16.p; }
-	// row groups (expann_set_row_groups): the labels and each group's rows on the device, the
-	// directory's labels and offsets on the host, where a grouped search is planned; and that search's staging
-	bool groups_on = false;
-	DevPtr<uint32_t> d_row_groups;   // [n]
-	DevPtr<uint32_t> d_group_rows;   // [rows that carry a label other than 0xFFFFFFFF], by (label, row)
-	GroupDirectory group_dir;        // keys and off (the rows live in d_group_rows)
-	long opt_group_list_rows = 0;    // "group_list_rows": 0 = kGroupListRowsAuto
-	uint64_t stat_group[5] = {0, 0, 0, 0, 0};  // the last grouped search: list, filter, any, pad queries; filter passes
-	PinPtr<void> h_group_tab;        // pinned: [sorted query numbers | list slots' queries | work items]
-	size_t h_group_tab_bytes = 0;
-	GrowPtr<void> d_group_tab;
-	GrowPtr<void> d_group_q;         // gathered queries of one tier
-	GrowPtr<uint64_t> d_group_ids;   // ... and their result rows
-	GrowPtr<float> d_group_dists;
-	bool group_lds_set = false;      // the list kernel's LDS limit is raised (dims whose query tile exceeds 64 KiB)
-	float f16_bnmax = 0.0f;          // max ||b||^2 (host copy lives in d_bnmax[2])
-	// int8 filter of fp32 rows (scan_gemm_i8f.hpp), built lazily beside the fp16 copy (whose sampled pass
-	// gives its thresholds) and dropped with it
-	DevPtr<void> d_base_i8f;         // [n padded to 64][dim] int8
-	DevPtr<int> d_bp_i8f;            // [n padded] integer row terms; kI8qPadBp on the padding
-	DevPtr<float> d_rw_i8f;          // [n] w_b (select pruning), +inf where bp was clamped
-	DevPtr<int> d_cb_i8f;            // [n padded] centre row terms of the int8 sampled pass; kI8fCbNone: no such row
-	DevPtr<float> d_wbmax_i8f;       // [1] the largest w_b among the rows with a centre term
 	DevPtr<float> d_i8f_q;           // [3][m_alloc]: A_q, W_q (prelude), w_q (thresholds)
 	GrowPtr<void> d_q8f;             // [m][dim] int8 queries
 	size_t i8f_q_m = 0;
-	I8fConsts i8f{};
-	int i8f_state = 0;               // 0 not built, 1 built, 2 built but off for auto (lists too long), -1 unusable
 	DevPtr<float> d_theta;           // [m_alloc] (int32 thetas for the 8-bit GEMM form)
-	DevPtr<int> d_bias_i;            // [n] sum b^2 per row (8-bit L2 GEMM form), built lazily
 	DevPtr<int> d_qself;             // [m_alloc]
 	GrowPtr<void> d_q;               // host-API staging
 	GrowPtr<uint64_t> d_ids;
 	GrowPtr<float> d_dists;
-	// options
-	long opt_query_tile = 0, opt_cand_capacity = 0, opt_sample_ratio = 32;
-	long opt_scan_chunks = 0;
 	// deferred check (expann_sync): flag blocks of the outstanding searches, read back into a ring
-	long opt_async = 0;
 	bool host_call = false;          // (expann_search: always the synchronous path)
 	PinPtr<uint32_t> h_flag_ring;    // pinned [kAsyncRing][kRingWords]
 	uint32_t async_pending = 0;
-	hipStream_t async_stream = nullptr;
-	long opt_xcd_tolerance = 3;  // % of modelled cost given up for an XCD-aligned chunk count
-	long opt_latency_mode = 1;  // few queries from host buffers: results land in pinned memory
-	long opt_debug = 0;
-	long opt_sample_frac = 0;        // the sampled pass reads 1/frac of the rows; 0 = by k (sample_frac_for)
-	long opt_sample_run = 1;         // consecutive 64-row tiles per sampled stretch.  1: the sample
-	                                 // is spread as finely as tiles allow -- with rows stored by
-	                                 // cluster, stretches of 16 tiles skipped whole clusters and the
-	                                 // full scan drowned in candidates (90 k instead of 2.8 M QPS on
-	                                 // 1000 contiguous clusters); on iid rows the two differ by < 1 %
-	long opt_sample_pass = 1;        // fp16 form: one sampled class-maxima pass instead of the level ladder
-	long opt_tail_chunks = 1;        // scan_gemm_f16x: the last round's row chunks three times finer (pick_tail_chunks)
-	long opt_persist = 1;            // scan_gemm_f16x: resident workgroups pull (query tile, row chunk) items per XCD
-	long opt_ip_rescale = 1;         // fp16 form, inner product: the filter sees each query times a power of two (f16_query_prep_kernel)
-	long opt_spec_rank = 0;          // speculative thresholds: 0 auto, j >= 1: the j-th class maximum (j >= k: off)
-	long opt_redo_bound = 1;         // debug: 0 = the redo pass's thresholds from the proven tau alone
-	long opt_select_overlap = 1;     // debug: 0 = the select stages of long lists on the caller's stream
-	long opt_rerank_rounds = 2;      // int8 filter's lists: 2 = re-ranked in two rounds, 1 = the single cut
-	long opt_rerank_stats = 0;       // 1 = count the rows the selects re-score ("rerank_rows"; adds launches and a host wait)
-	// the side stream of the select's long-list stages (launch_select_wave), and the events of its fork and join;
-	// made at the first search that has such a stage
-	hipStream_t side_stream = nullptr;
-	hipEvent_t side_ev[2] = {nullptr, nullptr};
+	bool group_lds_set = false;      // the grouped search's list kernel has its LDS limit raised (dims whose query tile exceeds 64 KiB)
+};
+
+// the counters expann_get_stat reads (kStatTable)
+struct Stats {
 	uint64_t stat_redo_queries = 0;  // queries the redo pass served in the last search (waiting form) / the last synced one
 	uint64_t stat_redo_candidates = 0;  // keys the redo lists of those queries held (the redo select counts them)
 	uint64_t stat_rerank_rows = 0;   // rows the last search's selects re-scored exactly (opt_rerank_stats)
 	uint64_t stat_redo_overflows = 0;  // searches whose failing queries (or redo lists) did not fit the redo pass
 	uint64_t stat_spec_rank = 0;     // j of the last search's thresholds (= k: proven thresholds)
-	long opt_i8_filter = 1;          // fp32 L2 d = 128: the int8 filter (scan_gemm_i8f.hpp): 0 off, 1 auto, 2 wherever supported
-	long opt_i8_sample = 1;          // its sampled pass on int8 too: 0 off, 1 where it speculates at the auto rank, 2 wherever it speculates
 	uint64_t stat_i8_sample = 0;     // 1: the last search's sampled pass ran on int8
-	long opt_scan_kernel = 0;        // 0 auto, 1 direct (scan_filter), 2 GEMM form on fp32 / int8
-	                                 // MFMA, 3 GEMM form on bf16 MFMA with the 3-term split
-	// profiling
+	uint64_t stat_group[5] = {0, 0, 0, 0, 0};  // the last grouped search: list, filter, any, pad queries; filter passes
+};
+
+// streams, events, profiling, statistics, the last error
+struct Runtime : Stats {
+	OwnedStream stream;
+	hipStream_t async_stream = nullptr;  // the stream of the outstanding deferred searches (the caller's, or `stream`)
+	// the side stream of the select's long-list stages (launch_select_wave), and the events of its fork and join;
+	// made at the first search that has such a stage
+	OwnedStream side_stream;
+	OwnedEvent side_ev[2];
 	bool profiling = false;
-	hipEvent_t ev[kEventPairs][2];
+	OwnedEvent ev[kEventPairs][2];
 	bool ev_created = false;
 	int ev_used = 0;
 	expann_profile prof{};
+	double prof_extra_ms = 0;        // scan time absorbed from the shadow
 	mutable std::string err;
+};
+
+// (base order: the streams and events outlive every buffer when a handle is deleted)
+struct expann_index : Config, Runtime, Workspace, Rows, RowCopies, RowFilter, RowGroups {
+	// the row terms the fp16 forms read: the masked copies while a filter is set
+	const float* bnorm_f16() const { return filter_on ? d_bnorm_f16_m.p : d_bnorm_f16.p; }
+	const float* bns_f16() const { return filter_on ? d_bns_f16_m.p : d_bns_f16.p; }
+	template <typename Group> void forget() { static_cast<Group&>(*this) = Group{}; }
 
 	int fail(int code, const std::string& msg) const {
 		err = msg;
@@ -793,25 +805,9 @@ int ensure_filter_terms(expann_index* h, hipStream_t st) {
 	return EXPANN_OK;
 }
 // forget everything the filter derived (the rows changed, or the handle is rebuilt)
-void drop_row_filter(expann_index* h) {
-	h->filter_on = false;
-	h->filter_terms_valid = false;
-	h->d_bnorm_f16_m.reset();
-	h->d_bns_f16_m.reset();
-	h->d_filter_bits.reset();
-	h->filter_words = 0;
-	h->filter_list_len = 0;
-	h->filter_list_stride = 1;
-	h->n_allowed = 0;
-	h->filter_residues = 0;
-}
+void drop_row_filter(expann_index* h) { h->forget<RowFilter>(); }
 // forget the row groups (they belong to the rows they were set for)
-void drop_row_groups(expann_index* h) {
-	h->groups_on = false;
-	h->d_row_groups.reset();
-	h->d_group_rows.reset();
-	h->group_dir = GroupDirectory{};
-}
+void drop_row_groups(expann_index* h) { h->forget<RowGroups>(); }
 
 const GemmVariant* pick_gemm(const expann_index* h, size_t m) {
 	if (h->opt_scan_kernel == 1 || !float_rows(h))
@@ -982,7 +978,7 @@ int launch_select(expann_index* h, SelectParams& sel, size_t m, uint32_t cap, hi
 	if (h->opt_select_overlap && longest > 512 && cap > 512) {
 		if (!h->side_stream) {
 			HIP_TRY(h, hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking));
-			for (hipEvent_t& e : h->side_ev)
+			for (OwnedEvent& e : h->side_ev)
 				HIP_TRY(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
 		}
 		side = h->side_stream;
@@ -1421,8 +1417,7 @@ int ensure_i8q(expann_index* h, const GemmI8qVariant* gq, hipStream_t st) {
 		hipLaunchKernelGGL(i8q_pad_rows_kernel, dim3(8192), dim3(kBlock), 0, st, (const uint32_t*)h->d_base, h->n,
 		                   (uint32_t)h->dim / 4, (uint32_t)dq / 4, n_pad,
 		                   h->int_mode == kU8L2 ? 0x80808080u : 0u, (uint32_t*)copy);
-		h->d_base_i8q = copy;
-		h->base_i8q_owned = true;
+		h->d_base_i8q.own(copy);
 	} else if (h->int_mode == kU8L2 || n_pad != h->n) {
 		// own copy: whole 64-row tiles (zero rows behind the end), uint8 rows mapped to int8
 		void* copy = nullptr;
@@ -1430,11 +1425,9 @@ int ensure_i8q(expann_index* h, const GemmI8qVariant* gq, hipStream_t st) {
 		const size_t words = h->n * (size_t)h->dim / 4, words_pad = n_pad * (size_t)h->dim / 4;
 		hipLaunchKernelGGL(i8q_copy_xor_kernel, dim3(4096), dim3(kBlock), 0, st, (const uint32_t*)h->d_base,
 		                   words, words_pad, h->int_mode == kU8L2 ? 0x80808080u : 0u, (uint32_t*)copy);
-		h->d_base_i8q = copy;
-		h->base_i8q_owned = true;
+		h->d_base_i8q.own(copy);
 	} else {
-		h->d_base_i8q = h->d_base;
-		h->base_i8q_owned = false;
+		h->d_base_i8q.borrow(h->d_base);
 	}
 	HIP_TRY(h, hipGetLastError());
 	return EXPANN_OK;
@@ -1641,12 +1634,6 @@ int search_i8q(expann_index* h, const GemmI8qVariant* gq, const void* d_queries,
 
 int search_pass(expann_index* h, const void* d_queries, size_t m, size_t k, uint64_t* d_ids,
                 float* d_dists, hipStream_t st);
-}  // namespace
-extern "C" int expann_create(int dim, int dtype, int metric, int device, expann_index** out);
-extern "C" int expann_set_base_device(expann_index* h, const void* d_rows, size_t n, uint64_t id_offset);
-extern "C" int expann_set_profiling(expann_index* h, int enable);
-extern "C" void expann_destroy(expann_index* h);
-namespace {
 
 // Exact-uint8 shortcut of an fp32 index (fields of expann_index): examine the rows once; if all
 // are integers in [0, 255] keep a uint8 copy behind an internal uint8 engine.
@@ -1683,20 +1670,14 @@ int build_u8_shadow(expann_index* h, hipStream_t st) {
 		return EXPANN_OK;
 	}
 	sh->strict_u8 = true;
-	h->u8_shadow = sh;
+	h->u8_shadow.reset(sh);
 	h->u8_exact = 1;
 	return EXPANN_OK;
 }
-void drop_u8_shadow(expann_index* h) {
-	if (h->u8_shadow)
-		expann_destroy(h->u8_shadow);
-	h->u8_shadow = nullptr;
-	h->d_base_u8.reset();
-	h->u8_exact = 0;
-}
+void drop_u8_shadow(expann_index* h) { h->forget<U8Shadow>(); }
 // the shadow's counters and scan time become the parent's
 int absorb_shadow_profile(expann_index* h) {
-	expann_index* sh = h->u8_shadow;
+	expann_index* sh = h->u8_shadow.get();
 	double ms = 0;
 	for (int i = 0; i < sh->ev_used; ++i) {
 		HIP_TRY(h, hipEventSynchronize(sh->ev[i][1]));
@@ -2967,7 +2948,7 @@ int search_pass(expann_index* h, const void* d_queries, size_t m, size_t k, uint
 				return rb;
 		}
 		if (h->u8_exact == 1) {
-			const int rq = search_pass(h->u8_shadow, d_queries, m, k, d_ids, d_dists, st);
+			const int rq = search_pass(h->u8_shadow.get(), d_queries, m, k, d_ids, d_dists, st);
 			const int ra = absorb_shadow_profile(h);
 			if (rq == EXPANN_OK)
 				return ra;
@@ -3108,7 +3089,8 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 		                 " (built: f32 any multiple of 16 up to 4096; 8-bit any multiple of 64 up to 4096; int16 64,128)";
 		return EXPANN_ERR_UNSUPPORTED;
 	}
-	expann_index* h = new expann_index();
+	// (owned until the last step: every early return destroys the handle, its stream included)
+	std::unique_ptr<expann_index, HandleDeleter> h(new expann_index());
 	h->dim = dim;
 	h->dtype = dtype;
 	h->metric = metric;
@@ -3116,121 +3098,66 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 	h->elem = (dtype == EXPANN_DTYPE_F32) ? 4 : ((dtype == EXPANN_DTYPE_I16 || dtype == EXPANN_DTYPE_F16) ? 2 : 1);
 	h->q_elem = (dtype == EXPANN_DTYPE_I8) ? 1 : (dtype == EXPANN_DTYPE_I16 ? 2 : 4);
 	h->int_mode = int_mode;
-	if (const char* e = std::getenv("EXPANN_TAIL_CHUNKS"))
-		h->opt_tail_chunks = std::atol(e);
-	if (const char* e = std::getenv("EXPANN_PERSIST"))
-		h->opt_persist = std::atol(e);
-	if (const char* e = std::getenv("EXPANN_SPEC_RANK"))
-		h->opt_spec_rank = std::max(0L, std::atol(e));  // (as set_option)
-	if (const char* e = std::getenv("EXPANN_REDO_BOUND"))  // (the two debug options of the search's tail: A/B runs)
-		h->opt_redo_bound = std::atol(e);
-	if (const char* e = std::getenv("EXPANN_SELECT_OVERLAP"))
-		h->opt_select_overlap = std::atol(e);
-	if (const char* e = std::getenv("EXPANN_RERANK_ROUNDS"))  // (A/B runs against the single cut)
-		h->opt_rerank_rounds = std::atol(e) == 1 ? 1 : 2;
-	if (const char* e = std::getenv("EXPANN_I8_FILTER"))
-		h->opt_i8_filter = std::min(2L, std::max(0L, std::atol(e)));  // (as set_option)
-	if (const char* e = std::getenv("EXPANN_I8_SAMPLE"))
-		h->opt_i8_sample = std::min(2L, std::max(0L, std::atol(e)));  // (as set_option)
+	static_cast<Options&>(*h) = options_from_env();
 	if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&h->stream) != hipSuccess) {
 		g_create_error = "hipSetDevice/hipStreamCreate failed";
-		delete h;
 		return EXPANN_ERR_HIP;
 	}
+	// every kernel this (dim, dtype, int_mode) can reach that needs more dynamic LDS than the default limit
+	struct LdsNeed {
+		const void* fn;
+		int bytes;
+		const char* label;
+	};
+	std::vector<LdsNeed> needs;
 	// the select kernel sorts up to kMaxCap 8-byte keys in LDS (128 KiB of the CU's 160 KiB)
-	if (hipFuncSetAttribute((const void*)select_topk_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize,
-	                        (int)(sizeof(uint64_t) * kMaxCap + 16)) != hipSuccess ||
-	    hipFuncSetAttribute((const void*)select_topk_kernel<_Float16>, hipFuncAttributeMaxDynamicSharedMemorySize,
-	                        (int)(sizeof(uint64_t) * kMaxCap + 16)) != hipSuccess ||
-	    hipFuncSetAttribute((const void*)select_topk_kernel<float, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-	                        (int)(sizeof(uint64_t) * kMaxCap + 16)) != hipSuccess) {
-		g_create_error = "hipFuncSetAttribute(select_topk_kernel) failed";
-		hipStreamDestroy(h->stream);
-		delete h;
-		return EXPANN_ERR_HIP;
-	}
+	const int sel_lds = (int)(sizeof(uint64_t) * kMaxCap + 16);
+	needs.push_back({(const void*)select_topk_kernel<float>, sel_lds, "select_topk_kernel"});
+	needs.push_back({(const void*)select_topk_kernel<_Float16>, sel_lds, "select_topk_kernel"});
+	needs.push_back({(const void*)select_topk_kernel<float, true>, sel_lds, "select_topk_kernel"});
 	for (const auto& v : kGemmF16X)
-		if (v.d == dim &&  // (the sampled pass is launched with the scan's LDS size, never less than its own)
-		    (hipFuncSetAttribute((const void*)v.scan, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds) != hipSuccess ||
-		     hipFuncSetAttribute((const void*)v.sample, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds) != hipSuccess ||
-		     (v.scan_redo &&
-		      hipFuncSetAttribute((const void*)v.scan_redo, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds) != hipSuccess))) {
-			g_create_error = "hipFuncSetAttribute(scan_gemm_f16x_kernel) failed";
-			hipStreamDestroy(h->stream);
-			delete h;
-			return EXPANN_ERR_HIP;
+		if (v.d == dim) {  // (the sampled pass is launched with the scan's LDS size, never less than its own)
+			needs.push_back({(const void*)v.scan, v.lds, "scan_gemm_f16x_kernel"});
+			needs.push_back({(const void*)v.sample, v.lds, "scan_gemm_f16x_kernel"});
+			if (v.scan_redo)
+				needs.push_back({(const void*)v.scan_redo, v.lds, "scan_gemm_f16x_kernel"});
 		}
-	if ((dtype == EXPANN_DTYPE_F32 || dtype == EXPANN_DTYPE_F16) && f16kl_dim(dim) &&
-	    (hipFuncSetAttribute((const void*)kGemmF16KL.scan, hipFuncAttributeMaxDynamicSharedMemorySize, kGemmF16KL.lds) != hipSuccess ||
-	     hipFuncSetAttribute((const void*)kGemmF16KL.sample, hipFuncAttributeMaxDynamicSharedMemorySize, kGemmF16KL.lds) != hipSuccess)) {
-		g_create_error = "hipFuncSetAttribute(scan_gemm_kl_kernel, fp16) failed";
-		hipStreamDestroy(h->stream);
-		delete h;
-		return EXPANN_ERR_HIP;
+	if ((dtype == EXPANN_DTYPE_F32 || dtype == EXPANN_DTYPE_F16) && f16kl_dim(dim)) {
+		needs.push_back({(const void*)kGemmF16KL.scan, kGemmF16KL.lds, "scan_gemm_kl_kernel, fp16"});
+		needs.push_back({(const void*)kGemmF16KL.sample, kGemmF16KL.lds, "scan_gemm_kl_kernel, fp16"});
 	}
-	for (const auto* tab : {kGemmF16XDbg})
-		if (tab[0].d == dim)
-			if (hipFuncSetAttribute((const void*)tab[0].scan, hipFuncAttributeMaxDynamicSharedMemorySize, tab[0].lds) !=
-			    hipSuccess) {
-				g_create_error = "hipFuncSetAttribute(scan_gemm_f16x_kernel) failed";
-				hipStreamDestroy(h->stream);
-				delete h;
-				return EXPANN_ERR_HIP;
-			}
+	if (kGemmF16XDbg[0].d == dim)
+		needs.push_back({(const void*)kGemmF16XDbg[0].scan, kGemmF16XDbg[0].lds, "scan_gemm_f16x_kernel"});
 	for (const auto& v : kGemmI8x)
-		if (v.d == dim &&
-		    (hipFuncSetAttribute((const void*)v.scan, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds) != hipSuccess ||
-		     hipFuncSetAttribute((const void*)v.sample, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds) != hipSuccess)) {
-			g_create_error = "hipFuncSetAttribute(scan_gemm_w8_kernel, int8) failed";
-			hipStreamDestroy(h->stream);
-			delete h;
-			return EXPANN_ERR_HIP;
+		if (v.d == dim) {
+			needs.push_back({(const void*)v.scan, v.lds, "scan_gemm_w8_kernel, int8"});
+			needs.push_back({(const void*)v.sample, v.lds, "scan_gemm_w8_kernel, int8"});
 		}
 	for (const auto& v : kGemmI8w)
-		if (v.d == dim &&
-		    (hipFuncSetAttribute((const void*)v.scan_w, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds_w) != hipSuccess ||
-		     hipFuncSetAttribute((const void*)v.sample_w, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds_w) != hipSuccess)) {
-			g_create_error = "hipFuncSetAttribute(scan_gemm_i8w_kernel) failed";
-			hipStreamDestroy(h->stream);
-			delete h;
-			return EXPANN_ERR_HIP;
+		if (v.d == dim) {
+			needs.push_back({(const void*)v.scan_w, v.lds_w, "scan_gemm_i8w_kernel"});
+			needs.push_back({(const void*)v.sample_w, v.lds_w, "scan_gemm_i8w_kernel"});
 		}
-	if (dim == kGemmI8F.d && hipFuncSetAttribute((const void*)kGemmI8FRedo, hipFuncAttributeMaxDynamicSharedMemorySize,
-	                                             kGemmI8F.lds_w) != hipSuccess) {
-		g_create_error = "hipFuncSetAttribute(scan_gemm_i8w_kernel, redo instance) failed";
-		hipStreamDestroy(h->stream);
-		delete h;
-		return EXPANN_ERR_HIP;
-	}
+	if (dim == kGemmI8F.d)
+		needs.push_back({(const void*)kGemmI8FRedo, kGemmI8F.lds_w, "scan_gemm_i8w_kernel, redo instance"});
 	if (any_dim_i8(dim, int_mode))
 		for (const auto& v : kGemmI8KL)
-			if (v.mode == int_mode &&
-			    (hipFuncSetAttribute((const void*)v.scan_w, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds_w) != hipSuccess ||
-			     hipFuncSetAttribute((const void*)v.sample_w, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds_w) != hipSuccess)) {
-				g_create_error = "hipFuncSetAttribute(scan_gemm_kl_kernel, int8) failed";
-				hipStreamDestroy(h->stream);
-				delete h;
-				return EXPANN_ERR_HIP;
+			if (v.mode == int_mode) {
+				needs.push_back({(const void*)v.scan_w, v.lds_w, "scan_gemm_kl_kernel, int8"});
+				needs.push_back({(const void*)v.sample_w, v.lds_w, "scan_gemm_kl_kernel, int8"});
 			}
 	for (const auto& v : kGemmBf16)
 		if (v.d == dim)
-			if (hipFuncSetAttribute((const void*)v.scan, hipFuncAttributeMaxDynamicSharedMemorySize,
-			                        2 * kGemmTB * dim * (int)sizeof(float)) != hipSuccess) {
-				g_create_error = "hipFuncSetAttribute(scan_gemm_bf16x3_kernel) failed";
-				hipStreamDestroy(h->stream);
-				delete h;
-				return EXPANN_ERR_HIP;
-			}
+			needs.push_back({(const void*)v.scan, 2 * kGemmTB * dim * (int)sizeof(float), "scan_gemm_bf16x3_kernel"});
 	for (const auto& v : kGemmI8)
 		if (v.d == dim && v.mode == int_mode)
-			if (hipFuncSetAttribute((const void*)v.scan, hipFuncAttributeMaxDynamicSharedMemorySize,
-			                        2 * gemm_i8_tb(dim) * dim) != hipSuccess) {
-				g_create_error = "hipFuncSetAttribute(scan_gemm_i8_kernel) failed";
-				hipStreamDestroy(h->stream);
-				delete h;
-				return EXPANN_ERR_HIP;
-			}
-	*out = h;
+			needs.push_back({(const void*)v.scan, 2 * gemm_i8_tb(dim) * dim, "scan_gemm_i8_kernel"});
+	for (const LdsNeed& need : needs)
+		if (hipFuncSetAttribute(need.fn, hipFuncAttributeMaxDynamicSharedMemorySize, need.bytes) != hipSuccess) {
+			g_create_error = std::string("hipFuncSetAttribute(") + need.label + ") failed";
+			return EXPANN_ERR_HIP;
+		}
+	*out = h.release();
 	return EXPANN_OK;
 }
 
@@ -3239,22 +3166,8 @@ void expann_destroy(expann_index* h) {
 		return;
 	hipSetDevice(h->device);
 	if (h->stream) hipStreamSynchronize(h->stream);
-	drop_u8_shadow(h);
-	if (h->owns_base && h->d_base) hipFree(h->d_base);
-	if (h->d_base_i8q && h->base_i8q_owned) hipFree(h->d_base_i8q);
-	// (every other buffer is a DevPtr / PinPtr member: freed by `delete h` below, device still current)
-	if (h->ev_created)
-		for (int i = 0; i < kEventPairs; ++i) {
-			hipEventDestroy(h->ev[i][0]);
-			hipEventDestroy(h->ev[i][1]);
-		}
-	if (h->side_stream) {
-		hipStreamSynchronize(h->side_stream);
-		hipStreamDestroy(h->side_stream);
-	}
-	for (hipEvent_t e : h->side_ev)
-		if (e) hipEventDestroy(e);
-	if (h->stream) hipStreamDestroy(h->stream);
+	if (h->side_stream) hipStreamSynchronize(h->side_stream);
+	// (every buffer, stream and event, and the shadow handle, is a member that frees itself, device still current)
 	delete h;
 }
 
@@ -3288,8 +3201,9 @@ int expann_build(expann_index* h) {
 	HIP_TRY(h, hipSetDevice(h->device));
 	drop_row_filter(h);
 	drop_row_groups(h);
-	HIP_TRY(h, hipMalloc(&h->d_base, h->staging.size()));
-	h->owns_base = true;
+	void* rows = nullptr;
+	HIP_TRY(h, hipMalloc(&rows, h->staging.size()));
+	h->d_base.own(rows);
 	HIP_TRY(h, hipMemcpy(h->d_base, h->staging.data(), h->staging.size(), hipMemcpyHostToDevice));
 	h->n = h->n_staged;
 	std::vector<unsigned char>().swap(h->staging);
@@ -3318,34 +3232,12 @@ int expann_set_base_device(expann_index* h, const void* d_rows, size_t n, uint64
 		return h->fail(EXPANN_ERR_INVALID_ARG, "empty device base");
 	if (n >= (1ull << 32) - 32)
 		return h->fail(EXPANN_ERR_UNSUPPORTED, "more than 2^32 rows per shard");
-	if (h->owns_base && h->d_base)
-		hipFree(h->d_base);
-	drop_u8_shadow(h);
-	// the derived copies belong to the rows they were made from
-	h->d_bnorm.reset();
-	h->d_bias_i.reset();
-	h->d_bnorm_bf.reset();
-	h->d_base_split.reset();
-	h->d_base_f16.reset();
-	h->d_base_i8f.reset();
-	h->d_bp_i8f.reset();
-	h->d_rw_i8f.reset();
-	h->d_cb_i8f.reset();
-	h->d_wbmax_i8f.reset();
-	h->i8f_state = 0;
-	if (h->d_base_i8q && h->base_i8q_owned)
-		hipFree(h->d_base_i8q);
-	h->d_base_i8q = nullptr;
-	h->base_i8q_owned = false;
-	h->d_bp_i8q.reset();
-	h->d_bnorm_f16.reset();
-	h->d_bns_f16.reset();
-	h->f16_scale = 0.0f;
-	h->f16_n_pad = 0;
-	drop_row_filter(h);  // (a filter belongs to the rows it was set for)
+	// the derived copies, a filter and the groups belong to the rows they were made from; the workspace, the
+	// options, the profiling state and the statistics stay
+	h->forget<RowCopies>();
+	drop_row_filter(h);
 	drop_row_groups(h);
-	h->d_base = const_cast<void*>(d_rows);
-	h->owns_base = false;
+	h->d_base.borrow(d_rows);
 	h->n = n;
 	h->id_offset = id_offset;
 	return EXPANN_OK;
@@ -3664,7 +3556,7 @@ int expann_set_profiling(expann_index* h, int enable) {
 	h->prof = expann_profile{};
 	h->prof_extra_ms = 0;
 	if (h->u8_shadow)
-		return expann_set_profiling(h->u8_shadow, enable);
+		return expann_set_profiling(h->u8_shadow.get(), enable);
 	return EXPANN_OK;
 }
 
@@ -3691,41 +3583,34 @@ int expann_get_profile(expann_index* h, expann_profile* out) {
 int expann_get_stat(expann_index* h, const char* name, uint64_t* out) {
 	if (!h || !name || !out)
 		return EXPANN_ERR_INVALID_ARG;
-	if (!std::strcmp(name, "redo_queries"))
-		*out = h->stat_redo_queries;
-	else if (!std::strcmp(name, "redo_candidates"))
-		*out = h->stat_redo_candidates;
-	else if (!std::strcmp(name, "redo_overflows"))
-		*out = h->stat_redo_overflows;
-	else if (!std::strcmp(name, "spec_rank"))
-		*out = h->stat_spec_rank;
-	else if (!std::strcmp(name, "i8_sample"))
-		*out = h->stat_i8_sample;
-	else if (!std::strcmp(name, "rerank_rows"))
-		*out = h->stat_rerank_rows;
-	else if (!std::strcmp(name, "base_bytes"))
-		*out = h->d_base ? (uint64_t)h->n * (uint64_t)h->dim * h->elem : 0;
-	else if (!std::strcmp(name, "filter_active"))
-		*out = h->filter_on ? 1 : 0;
-	else if (!std::strcmp(name, "filter_rows"))
-		*out = h->filter_on ? h->n_allowed : expann_size(h);
-	else if (!std::strcmp(name, "groups_active"))
-		*out = h->groups_on ? 1 : 0;
-	else if (!std::strcmp(name, "group_count"))
-		*out = h->groups_on ? h->group_dir.keys.size() : 0;
-	else if (!std::strcmp(name, "group_list_queries"))
-		*out = h->stat_group[0];
-	else if (!std::strcmp(name, "group_filter_queries"))
-		*out = h->stat_group[1];
-	else if (!std::strcmp(name, "group_any_queries"))
-		*out = h->stat_group[2];
-	else if (!std::strcmp(name, "group_pad_queries"))
-		*out = h->stat_group[3];
-	else if (!std::strcmp(name, "group_filter_passes"))
-		*out = h->stat_group[4];
-	else
-		return h->fail(EXPANN_ERR_INVALID_ARG, std::string("unknown statistic ") + name);
-	return EXPANN_OK;
+	using H = const expann_index*;
+	static const struct {
+		const char* name;
+		uint64_t (*read)(H);
+	} kStatTable[] = {
+	    {"redo_queries", [](H h) { return h->stat_redo_queries; }},
+	    {"redo_candidates", [](H h) { return h->stat_redo_candidates; }},
+	    {"redo_overflows", [](H h) { return h->stat_redo_overflows; }},
+	    {"spec_rank", [](H h) { return h->stat_spec_rank; }},
+	    {"i8_sample", [](H h) { return h->stat_i8_sample; }},
+	    {"rerank_rows", [](H h) { return h->stat_rerank_rows; }},
+	    {"base_bytes", [](H h) { return h->d_base ? (uint64_t)h->n * (uint64_t)h->dim * h->elem : 0; }},
+	    {"filter_active", [](H h) -> uint64_t { return h->filter_on ? 1 : 0; }},
+	    {"filter_rows", [](H h) -> uint64_t { return h->filter_on ? h->n_allowed : expann_size(h); }},
+	    {"groups_active", [](H h) -> uint64_t { return h->groups_on ? 1 : 0; }},
+	    {"group_count", [](H h) -> uint64_t { return h->groups_on ? h->group_dir.keys.size() : 0; }},
+	    {"group_list_queries", [](H h) { return h->stat_group[0]; }},
+	    {"group_filter_queries", [](H h) { return h->stat_group[1]; }},
+	    {"group_any_queries", [](H h) { return h->stat_group[2]; }},
+	    {"group_pad_queries", [](H h) { return h->stat_group[3]; }},
+	    {"group_filter_passes", [](H h) { return h->stat_group[4]; }},
+	};
+	for (const auto& s : kStatTable)
+		if (!std::strcmp(name, s.name)) {
+			*out = s.read(h);
+			return EXPANN_OK;
+		}
+	return h->fail(EXPANN_ERR_INVALID_ARG, std::string("unknown statistic ") + name);
 }
 
 uint32_t expann_spec_rank_auto(size_t k, uint32_t sample_frac) {
@@ -4270,65 +4155,9 @@ int expann_search_grouped(expann_index* h, const void* queries, const uint32_t* 
 int expann_set_option(expann_index* h, const char* name, long value) {
 	if (!h || !name)
 		return EXPANN_ERR_INVALID_ARG;
-	if (!std::strcmp(name, "query_tile"))
-		h->opt_query_tile = value;
-	else if (!std::strcmp(name, "cand_capacity"))
-		h->opt_cand_capacity = value;
-	else if (!std::strcmp(name, "debug"))
-		h->opt_debug = value;
-	else if (!std::strcmp(name, "scan_kernel"))
-		h->opt_scan_kernel = value;
-	else if (!std::strcmp(name, "f16x") || !std::strcmp(name, "i8x") || !std::strcmp(name, "i8w")) {
-		// (rounds 1-2: A/B switches between the 32x32 kernels and the 16x16 ones; the 32x32 kernels are gone)
-		if (value == 0)
-			return h->fail(EXPANN_ERR_UNSUPPORTED, std::string(name) + " = 0: the 32 x 32 MFMA forms of rounds 1-2 were removed in round 3");
-	}
-	else if (!std::strcmp(name, "tail_chunks"))
-		h->opt_tail_chunks = value;
-	else if (!std::strcmp(name, "persist"))
-		h->opt_persist = value;
-	else if (!std::strcmp(name, "i8_filter"))
-		h->opt_i8_filter = value < 0 ? 0 : (value > 2 ? 2 : value);
-	else if (!std::strcmp(name, "i8_sample"))
-		h->opt_i8_sample = value < 0 ? 0 : (value > 2 ? 2 : value);
-	else if (!std::strcmp(name, "spec_rank"))
-		h->opt_spec_rank = value < 0 ? 0 : value;
-	else if (!std::strcmp(name, "redo_bound"))
-		h->opt_redo_bound = value;
-	else if (!std::strcmp(name, "select_overlap"))
-		h->opt_select_overlap = value;
-	else if (!std::strcmp(name, "rerank_rounds"))
-		h->opt_rerank_rounds = value == 1 ? 1 : 2;
-	else if (!std::strcmp(name, "rerank_stats"))
-		h->opt_rerank_stats = value ? 1 : 0;
-	else if (!std::strcmp(name, "ip_rescale"))
-		h->opt_ip_rescale = value;
-	else if (!std::strcmp(name, "sample_pass"))
-		h->opt_sample_pass = value;
-	else if (!std::strcmp(name, "u8_exact"))
-		h->opt_u8_exact = value;
-	else if (!std::strcmp(name, "latency_mode"))
-		h->opt_latency_mode = value;
-	else if (!std::strcmp(name, "async_search"))
-		h->opt_async = value;
-	else if (!std::strcmp(name, "scan_chunks"))
-		h->opt_scan_chunks = value;
-	else if (!std::strcmp(name, "xcd_tolerance"))
-		h->opt_xcd_tolerance = value < 0 ? 0 : value;
-	else if (!std::strcmp(name, "sample_run"))
-		h->opt_sample_run = value < 1 ? 1 : (value > 64 ? 64 : value);
-	else if (!std::strcmp(name, "sample_frac"))
-		h->opt_sample_frac = value < 0 ? 0 : value;
-	else if (!std::strcmp(name, "sample_ratio"))
-		h->opt_sample_ratio = value < 2 ? 2 : value;
-	else if (!std::strcmp(name, "group_list_rows")) {
-		if (value < 0 || value > (long)kMaxCap)
-			return h->fail(EXPANN_ERR_INVALID_ARG, "group_list_rows: 0 (auto) or 1.." + std::to_string(kMaxCap));
-		h->opt_group_list_rows = value;
-	}
-	else
-		return h->fail(EXPANN_ERR_INVALID_ARG, std::string("unknown option ") + name);
-	return EXPANN_OK;
+	std::string msg;
+	const int rc = set_option(*h, name, value, &msg);  // (bf_options.hpp: the table of names and rules)
+	return rc == EXPANN_OK ? rc : h->fail(rc, msg);
 }
 
 }  // extern "C"

@@ -5,13 +5,14 @@
 
 #include <algorithm>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/expann_hip.h"
 
 namespace expann {
 
-// the bound on k of every brute-force search (half the longest candidate list, kMaxCap in expann_hip.hip):
+// the bound on k of every brute-force search (half the longest candidate list, kMaxCap in bf_options.hpp):
 // a larger k is refused by value at the entry point, before any GPU work
 constexpr size_t kMaxK = 8192;
 inline std::string k_too_large() { return "k too large for the candidate buffers (k <= " + std::to_string(kMaxK) + ")"; }
@@ -30,48 +31,47 @@ struct DevBuf {
 	template <typename T> T* as() const { return static_cast<T*>(p); }
 };
 
-// Device / pinned-host memory OWNED by a handle: frees itself when the handle goes away, converts
-// to the raw pointer the kernels and HIP calls take (`hipMalloc(&h->d_x, n)` still works).
-// Not copyable; `reset()` frees now.
-template <typename T> struct DevPtr {
-	T* p = nullptr;
-	DevPtr() = default;
-	DevPtr(const DevPtr&) = delete;
-	DevPtr& operator=(const DevPtr&) = delete;
-	~DevPtr() { reset(); }
+// What a handle OWNS through HIP -- device memory, pinned host memory, a stream, an event: released when the handle
+// goes away, converts to the raw pointer the kernels and HIP calls take (`hipMalloc(&h->d_x, n)` still works).
+// Not copyable; movable, so that a group of them is forgotten as a value (`group = Group{}`); `reset()` releases now.
+template <typename P, auto Release> struct HipOwned {
+	P p = nullptr;
+	HipOwned() = default;
+	HipOwned(const HipOwned&) = delete;
+	HipOwned& operator=(const HipOwned&) = delete;
+	HipOwned(HipOwned&& o) noexcept : p(std::exchange(o.p, nullptr)) {}
+	HipOwned& operator=(HipOwned&& o) noexcept {  // (what this one held goes with `o`)
+		std::swap(p, o.p);
+		return *this;
+	}
+	~HipOwned() { reset(); }
 	void reset() {
 		if (p)
-			(void)hipFree(p);
+			(void)Release(p);
 		p = nullptr;
 	}
-	T* get() const { return p; }
+	P get() const { return p; }
 	template <typename U> U* as() const { return (U*)p; }  // the same bytes as another element type
-	operator T*() const { return p; }
-	T** operator&() { return &p; }
+	operator P() const { return p; }
+	P* operator&() { return &p; }
 	explicit operator bool() const { return p != nullptr; }
 };
-template <typename T> struct PinPtr {
-	T* p = nullptr;
-	PinPtr() = default;
-	PinPtr(const PinPtr&) = delete;
-	PinPtr& operator=(const PinPtr&) = delete;
-	~PinPtr() { reset(); }
-	void reset() {
-		if (p)
-			(void)hipHostFree(p);
-		p = nullptr;
-	}
-	T* get() const { return p; }
-	template <typename U> U* as() const { return (U*)p; }
-	operator T*() const { return p; }
-	T** operator&() { return &p; }
-	explicit operator bool() const { return p != nullptr; }
-};
+template <typename T> using DevPtr = HipOwned<T*, hipFree>;
+template <typename T> using PinPtr = HipOwned<T*, hipHostFree>;
+using OwnedStream = HipOwned<hipStream_t, hipStreamDestroy>;
+using OwnedEvent = HipOwned<hipEvent_t, hipEventDestroy>;
 // a DevPtr that only ever grows: ensure(n) keeps the allocation when it is large enough.  Growing
 // frees the old block: work still in flight that reads it must have drained first (the callers with
 // deferred searches outstanding synchronise their stream before they grow a shared buffer).
 template <typename T> struct GrowPtr : DevPtr<T> {
 	size_t bytes = 0;
+	GrowPtr() = default;
+	GrowPtr(GrowPtr&& o) noexcept : DevPtr<T>(std::move(o)), bytes(std::exchange(o.bytes, 0)) {}
+	GrowPtr& operator=(GrowPtr&& o) noexcept {
+		std::swap(this->p, o.p);
+		std::swap(bytes, o.bytes);
+		return *this;
+	}
 	hipError_t ensure(size_t need) {
 		if (need <= bytes && this->p)
 			return hipSuccess;
@@ -86,6 +86,23 @@ template <typename T> struct GrowPtr : DevPtr<T> {
 		this->reset();
 		bytes = 0;
 	}
+};
+// Device memory a handle reads and may or may not own -- rows handed in by the caller, a padded copy that is an
+// alias when no padding is needed: own() takes memory to free, borrow() memory of someone else.  Converts to any
+// pointer type the kernels' parameter blocks take.  (Moved from, it borrows what it held: nothing is freed twice.)
+struct MaybeOwnedPtr {
+	void* p = nullptr;  // what is read
+	DevPtr<void> mine;  // the same block where the handle owns it
+	void own(void* q) {
+		mine.reset();
+		mine.p = p = q;
+	}
+	void borrow(const void* q) {
+		mine.reset();
+		p = const_cast<void*>(q);
+	}
+	template <typename U> operator U*() const { return (U*)p; }
+	explicit operator bool() const { return p != nullptr; }
 };
 
 // The directory of a row-group labelling (expann_graph_set_row_groups, expann_set_row_groups): the distinct labels

@@ -463,7 +463,8 @@ int expann_get_profile(expann_index* h, expann_profile* out);
 int expann_sharded_set_profiling(expann_sharded* h, int enable);
 int expann_sharded_get_profile(expann_sharded* h, int shard, expann_profile* out);
 
-/* integer options: "query_tile" (0 = auto), "cand_capacity" (0 = auto),
+/* integer options (expann_amd/csrc/bf_options.hpp is the one list of them: names, defaults, environment variables
+ * and the rule each value passes through): "query_tile" (0 = auto), "cand_capacity" (0 = auto),
  * "scan_kernel" (0 = auto, 1 = direct VALU scan, 2 = GEMM form on the fp32 / int8 matrix
  * cores, 3 = GEMM form on the bf16 matrix cores with the 3-term split, 4 = GEMM form with one
  * scaled fp16 product, 5 = 8-bit rows: int8 MFMA form with per-wave hit queues (d = 128,
@@ -482,7 +483,13 @@ int expann_sharded_get_profile(expann_sharded* h, int shard, expann_profile* out
  * "xcd_tolerance" (percent of modelled launch cost given up for an XCD-aligned row-chunk count,
  * default 3), "scan_chunks" (experiments: force the row-chunk count of the fp16 scan; 0 = model),
  * "sample_run", "debug" (bench / ablation switches),
- * "persist" (1 (default): the d = 128 fp16 scan runs as resident workgroups pulling work per XCD; 0: plain launch),
+ * "persist" (1 (default): the d = 128 fp16 scan runs as resident workgroups pulling work per XCD; 0: plain launch;
+ * EXPANN_PERSIST sets the starting value),
+ * "tail_chunks" (1 (default): that scan cuts the row chunks of its last round three times finer; 0: one size;
+ * EXPANN_TAIL_CHUNKS sets the starting value),
+ * "group_list_rows" (row groups: the longest group the list kernel serves, see expann_set_row_groups),
+ * "f16x", "i8x", "i8w" (A/B switches whose 0 side was removed: 0 is EXPANN_ERR_UNSUPPORTED, any other value is
+ * accepted and changes nothing),
  * "ip_rescale" (1 (default): inner product, fp16 form: the filter sees each query times a power of two that brings
  * its norm to the largest row's -- ranks unchanged, results exact; 0: rounds 1-2's unscaled filter),
  * "i8_filter" (fp32 L2, d = 128, scan_kernel on auto: the full scan on the int8 matrix cores with a rigorous
