@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "expann_antitopo_query_grouped", "expann_antitopo_query_grouped_device",
     "expann_set_row_groups", "expann_set_row_groups_device", "expann_clear_row_groups",
     "expann_search_grouped", "expann_search_grouped_device",
+    "expann_range_search", "expann_range_search_device",
 ]
 GROUP_ANY = 0xFFFFFFFF  # EXPANN_GROUP_ANY: the group a query names to search every row
 
@@ -321,6 +322,11 @@ def load():
         L.expann_search_grouped.argtypes = [vp, vp, vp, sz, sz, vp, vp]
         L.expann_search_grouped_device.restype = C.c_int
         L.expann_search_grouped_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
+    if hasattr(L, "expann_range_search"):  # (as above: an older build has no range search)
+        L.expann_range_search.restype = C.c_int
+        L.expann_range_search.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
+        L.expann_range_search_device.restype = C.c_int
+        L.expann_range_search_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
     if hasattr(L, "expann_graph_create_f16"):  # (as above: an older build has no binary16 graph rows)
         L.expann_graph_create_f16.restype = C.c_int
         L.expann_graph_create_f16.argtypes = [C.c_int, C.c_int, vp, sz, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(vp)]

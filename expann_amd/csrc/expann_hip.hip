@@ -36,6 +36,7 @@
 #include "scan_groups.hpp"
 #include "score_ids.hpp"
 #include "select.hpp"
+#include "select_range.hpp"
 
 using namespace expann;
 
@@ -209,6 +210,16 @@ struct Workspace {
 	PinPtr<uint32_t> h_flag_ring;    // pinned [kAsyncRing][kRingWords]
 	uint32_t async_pending = 0;
 	bool group_lds_set = false;      // the grouped search's list kernel has its LDS limit raised (dims whose query tile exceeds 64 KiB)
+	// range search (RangePass): [the three lists' lengths, 0 | queries stage 1's lists could not hold [m] | ... nor the
+	// fp16 form's at kMaxCap keys [m] | queries with more than kMaxCap rows in range [m]], the gathered queries of
+	// stages 2 / 3, stage 3's result rows, and the host-buffer call's radii and counts
+	GrowPtr<uint32_t> d_range;
+	GrowPtr<void> d_range_q;
+	GrowPtr<uint64_t> d_range_ids;
+	GrowPtr<float> d_range_dists;
+	GrowPtr<float> d_range_radii;
+	GrowPtr<uint32_t> d_range_counts;
+	bool range_lds_set = false;      // the range select's 1 024-thread instances have their LDS limit raised
 };
 
 // the counters expann_get_stat reads (kStatTable)
@@ -220,6 +231,7 @@ struct Stats {
 	uint64_t stat_spec_rank = 0;     // j of the last search's thresholds (= k: proven thresholds)
 	uint64_t stat_i8_sample = 0;     // 1: the last search's sampled pass ran on int8
 	uint64_t stat_group[5] = {0, 0, 0, 0, 0};  // the last grouped search: list, filter, any, pad queries; filter passes
+	uint64_t stat_range[3] = {0, 0, 0};  // the last range search: queries answered from a list, by the top-k pipeline; stage-1 retries
 };
 
 // streams, events, profiling, statistics, the last error
@@ -2078,6 +2090,34 @@ int launch_scan_f16(expann_index* h, const GemmF16Variant* gvf, uint32_t rows_se
 	return EXPANN_OK;
 }
 
+// The query side of the fp16 forms (SearchPass::prepare_queries, RangePass): scaled fp16 queries, ||q||^2, and the
+// largest |q| (range check, read back at the end): one memset of the flag block, one kernel
+// (latency mode, one workgroup: the kernel clears the flag block itself and, when the queries
+// still sit in pinned host memory -- from_host --, leaves the device copy the later kernels read)
+int launch_f16_query_prep(expann_index* h, const GemmF16Variant* gvf, const void* d_queries, size_t m, bool ip, bool from_host,
+                          const I8fQueryArgs& qa, hipStream_t st) {
+	const size_t nv = m * (size_t)h->dim;
+	HIP_TRY(h, grow_ws(h, h->d_q_split, nv * 4));
+	const bool one_wg = m <= (size_t)kRowsPerGroup;
+	if (!one_wg)
+		HIP_TRY(h, hipMemsetAsync(h->d_overflow, 0, 32, st));
+	const dim3 prep_grid((uint32_t)((m + kRowsPerGroup - 1) / kRowsPerGroup));
+	const float* ip_ref = (ip && h->opt_ip_rescale) ? (const float*)(h->d_bnmax + 2) : (const float*)nullptr;
+	if (gvf->d == 0)  // (run-time dim: rows of f16_ld(d) elements, zero-padded)
+		hipLaunchKernelGGL(f16_query_prep_any_kernel, prep_grid, dim3(kBlock), 0, st, (const float*)d_queries,
+		                   (uint32_t)m, (uint32_t)h->dim, (uint32_t)f16_ld(h->dim), h->f16_scale,
+		                   h->d_q_split.as<_Float16>(), h->d_qnrm, h->d_overflow + 2,
+		                   from_host ? h->d_q.as<float>() : (float*)nullptr, one_wg ? h->d_overflow : (uint32_t*)nullptr,
+		                   ip_ref, h->d_qscale.as<float>());
+	else
+		hipLaunchKernelGGL(gvf->prep, prep_grid, dim3(kBlock), 0, st, (const float*)d_queries, (uint32_t)m,
+		                   h->f16_scale, h->d_q_split.as<_Float16>(), h->d_qnrm, h->d_overflow + 2,
+		                   from_host ? h->d_q.as<float>() : (float*)nullptr, one_wg ? h->d_overflow : (uint32_t*)nullptr,
+		                   ip_ref, h->d_qscale.as<float>(), qa);
+	HIP_TRY(h, hipGetLastError());
+	return EXPANN_OK;
+}
+
 // ---- one pass over <= kMaxQueriesPerPass queries, as a planner + steps -------------------------
 // choose_kernels()   which kernel family serves this pass (the planner: row type, metric, batch size,
 //                    options, what an earlier attempt learned) and the index's derived copies it needs
@@ -2272,31 +2312,11 @@ int SearchPass::prepare_queries(bool* restart) {
 			qa.wq = h->d_i8f_q + h->i8f_q_m;
 			qa.k = h->i8f;
 		}
-		const size_t nv = m * (size_t)h->dim;
-		HIP_TRY(h, grow_ws(h, h->d_q_split, nv * 4));
-		// scaled fp16 queries, ||q||^2, and the largest |q| (range check, read back at the end):
-		// one memset of the flag block, one kernel
-		// (latency mode, one workgroup: the kernel clears the flag block itself and, when the queries
-		// still sit in pinned host memory, leaves the device copy the later kernels read)
-		const bool one_wg = m <= (size_t)kRowsPerGroup;
-		const bool from_host = h->q_in_pinned_host && one_wg;
-		if (!one_wg)
-			HIP_TRY(h, hipMemsetAsync(h->d_overflow, 0, 32, st));
+		const bool from_host = h->q_in_pinned_host && m <= (size_t)kRowsPerGroup;
+		rc = launch_f16_query_prep(h, gvf, d_queries, m, ip, from_host, qa, st);
+		if (rc != EXPANN_OK)
+			return rc;
 		flags_clean = true;
-		const dim3 prep_grid((uint32_t)((m + kRowsPerGroup - 1) / kRowsPerGroup));
-		const float* ip_ref = (ip && h->opt_ip_rescale) ? (const float*)(h->d_bnmax + 2) : (const float*)nullptr;
-		if (gvf->d == 0)  // (run-time dim: rows of f16_ld(d) elements, zero-padded)
-			hipLaunchKernelGGL(f16_query_prep_any_kernel, prep_grid, dim3(kBlock), 0, st, (const float*)d_queries,
-			                   (uint32_t)m, (uint32_t)h->dim, (uint32_t)f16_ld(h->dim), h->f16_scale,
-			                   h->d_q_split.as<_Float16>(), h->d_qnrm, h->d_overflow + 2,
-			                   from_host ? h->d_q.as<float>() : (float*)nullptr, one_wg ? h->d_overflow : (uint32_t*)nullptr,
-			                   ip_ref, h->d_qscale.as<float>());
-		else
-			hipLaunchKernelGGL(gvf->prep, prep_grid, dim3(kBlock), 0, st, (const float*)d_queries, (uint32_t)m,
-			                   h->f16_scale, h->d_q_split.as<_Float16>(), h->d_qnrm, h->d_overflow + 2,
-			                   from_host ? h->d_q.as<float>() : (float*)nullptr, one_wg ? h->d_overflow : (uint32_t*)nullptr,
-			                   ip_ref, h->d_qscale.as<float>(), qa);
-		HIP_TRY(h, hipGetLastError());
 		if (from_host) {
 			d_queries = h->d_q;
 			h->q_in_pinned_host = false;
@@ -3604,6 +3624,9 @@ int expann_get_stat(expann_index* h, const char* name, uint64_t* out) {
 	    {"group_any_queries", [](H h) { return h->stat_group[2]; }},
 	    {"group_pad_queries", [](H h) { return h->stat_group[3]; }},
 	    {"group_filter_passes", [](H h) { return h->stat_group[4]; }},
+	    {"range_list_queries", [](H h) { return h->stat_range[0]; }},
+	    {"range_topk_queries", [](H h) { return h->stat_range[1]; }},
+	    {"range_retries", [](H h) { return h->stat_range[2]; }},
 	};
 	for (const auto& s : kStatTable)
 		if (!std::strcmp(name, s.name)) {
@@ -4068,6 +4091,395 @@ int grouped_search_device(expann_index* h, const void* d_queries, const uint32_t
 	return EXPANN_OK;
 }
 
+// ---- range search (THE RANGE RULE, include/expann_hip.h) ----------------------------------------
+// The threshold machine with the caller's radii as tau: no sampled pass, no threshold estimate.  A pass of its own
+// beside SearchPass, built from the same launch helpers; the plain and grouped searches launch what they did.
+//   stage 1  every query, lists of cap0 keys: the fp16 single-product form (its keys re-scored exactly by the range
+//            select) where pick_gemm gives one and the queries fit its range, else the exact direct scan
+//   stage 2  the queries whose list did not fit, gathered, at kMaxCap keys: the fp16 form again where stage 1 ran it
+//            with shorter lists, then -- for what is left -- the exact direct scan, whose counter goes on counting, so
+//            the count is exact whatever it is, and the range select over exact keys
+//   stage 3  the queries with more than kMaxCap rows in range: their max_results nearest rows are all in range, so
+//            they are what the plain pipeline returns for k = max_results
+// One host wait per stage that runs (it reads the next stage's list length); a search whose every list fit has one.
+// cap0 and the split between the one-wave and the workgroup forms of the select: profiles/range_search_ab.txt.
+constexpr uint32_t kRangeCap0 = 1024;      // stage 1's list capacity at least, unless "cand_capacity" sets it (range_search_device)
+constexpr uint32_t kRangeWaveMax = 512;    // lists up to this many keys: the one-wave select
+constexpr uint32_t kRangeBlockMax = 4096;  // ... up to this many: 256 threads; beyond: 1 024 threads
+constexpr size_t kRangeRetryChunk = 2048;  // queries of one stage-2 launch (2 048 x kMaxCap keys = 256 MiB of lists)
+
+// (a diagnostic like EXPANN_DEBUG_LISTS, not an option: EXPANN_RANGE_WAVE_MAX moves the split for the sweep of
+// profiles/range_search_ab.py, which found no difference up to 512 keys; unset, the constant holds)
+inline uint32_t range_wave_max() {
+	static const uint32_t v = [] {
+		const char* e = std::getenv("EXPANN_RANGE_WAVE_MAX");
+		return e ? (uint32_t)std::min(2048L, std::max(0L, std::atol(e))) : kRangeWaveMax;
+	}();
+	return v;
+}
+
+// the range select over n_slots lists of capacity cap (a power of two): one launch per form that has lists to serve
+int launch_range_select(expann_index* h, RangeSelectParams rp, uint32_t n_slots, uint32_t cap, hipStream_t st) {
+	using Fn = void (*)(RangeSelectParams);
+	const bool hr = f16_rows(h);
+	const Fn f64 = hr ? range_select_kernel<_Float16, 64> : range_select_kernel<float, 64>;
+	const Fn f256 = hr ? range_select_kernel<_Float16, 256> : range_select_kernel<float, 256>;
+	const Fn f1024 = hr ? range_select_kernel<_Float16, 1024> : range_select_kernel<float, 1024>;
+	if (!h->range_lds_set) {  // (kMaxCap keys: 128 KiB of the CU's 160 KiB, as select_topk_kernel)
+		const int lds = (int)(sizeof(uint64_t) * kMaxCap + 16);
+		HIP_TRY(h, hipFuncSetAttribute((const void*)range_select_kernel<float, 1024>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+		HIP_TRY(h, hipFuncSetAttribute((const void*)range_select_kernel<_Float16, 1024>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+		h->range_lds_set = true;
+	}
+	rp.cap = cap;
+	rp.n_slots = n_slots;
+	const uint32_t wave_max = std::min(range_wave_max(), cap);
+	auto launch = [&](Fn fn, uint32_t threads, uint32_t len_min, uint32_t len_hi) {
+		rp.len_min = len_min;
+		rp.len_hi = len_hi;
+		rp.takes_overflow = len_hi >= cap ? 1u : 0u;
+		rp.lds_keys = std::max<uint32_t>(2, pow2ceil(len_hi));
+		hipLaunchKernelGGL(fn, dim3(n_slots), dim3(threads), sizeof(uint64_t) * rp.lds_keys + 16, st, rp);
+	};
+	uint32_t from = 0;
+	if (wave_max > 0) {
+		launch(f64, 64, 0, wave_max);
+		from = wave_max + 1;
+	}
+	if (from <= cap && from <= kRangeBlockMax) {
+		launch(f256, 256, from, std::min(cap, kRangeBlockMax));
+		from = std::min(cap, kRangeBlockMax) + 1;
+	}
+	if (from <= cap)
+		launch(f1024, 1024, from, cap);
+	HIP_TRY(h, hipGetLastError());
+	return EXPANN_OK;
+}
+
+struct RangePass {
+	expann_index* h;
+	const void* d_queries;
+	const float* d_radii;
+	size_t m;
+	uint32_t max_results;
+	uint64_t* d_ids;
+	float* d_dists;
+	uint32_t* d_counts;
+	hipStream_t st;
+	bool ip;
+	int cus;
+	uint32_t cap0;
+	uint32_t n_retry = 0, n_mid = 0, n_big = 0;
+
+	// d_range: [0] / [1] / [2] the lengths of the three lists behind them, m query numbers each
+	uint32_t* word(int w) const { return h->d_range.get() + w; }
+	uint32_t* retry_list() const { return h->d_range.get() + 4; }          // stage 1's lists could not hold them
+	uint32_t* mid_list() const { return h->d_range.get() + 4 + m; }        // nor the fp16 form's at kMaxCap keys
+	uint32_t* big_list() const { return h->d_range.get() + 4 + 2 * m; }    // more than kMaxCap rows in range
+
+	const GemmF16Variant* f16_form(size_t mq) const;
+	int direct_scan(const void* d_q, size_t mq, uint32_t cap, const char** kname);
+	int filter_stage(bool want_f16, const uint32_t* list, size_t mq, uint32_t cap, int over_word, uint32_t* over_list,
+	                 uint32_t* n_over, bool* used_f16, bool* out_of_range);
+	int stage3();
+	int run();
+};
+
+// the fp16 single-product form that serves this index and a batch of mq queries, or nullptr: the exact direct scan
+// (pick_gemm's crossovers; never the bf16x3 form, whatever "scan_kernel" says)
+const GemmF16Variant* RangePass::f16_form(size_t mq) const {
+	if (!pick_gemm(h, mq) || !f16_choice(h->opt_scan_kernel))
+		return nullptr;
+	for (const auto& v : kGemmF16X)
+		if (v.d == h->dim)
+			return &v;
+	return f16kl_dim(h->dim) ? &kGemmF16KL : nullptr;
+}
+
+// the exact direct scan of every row for the mq queries at d_q: tau = h->d_tau[0], tau_row all ones (every row
+// that ties with the radius is in range), lists and counters in h->d_cand / h->d_cnt
+int RangePass::direct_scan(const void* d_q, size_t mq, uint32_t cap, const char** kname) {
+	const ScanVariant* v = pick_scan_f32(h->dim, ip, mq, h->opt_query_tile, f16_rows(h));
+	if (!v)
+		return h->fail(EXPANN_ERR_UNSUPPORTED, "no scan kernel for dim " + std::to_string(h->dim) + " / query_tile " +
+		                                           std::to_string(h->opt_query_tile));
+	HIP_TRY(h, hipMemsetAsync(h->d_cnt, 0, sizeof(uint32_t) * mq, st));
+	HIP_TRY(h, hipMemsetAsync(h->d_tau_row[0], 0xFF, sizeof(uint32_t) * mq, st));
+	ScanParams sp{};
+	sp.base = h->d_base;
+	sp.n_rows = (uint32_t)h->n;
+	sp.n_groups_sel = (uint32_t)((h->n + kRowsPerGroup - 1) / kRowsPerGroup);
+	sp.group_stride = 1;
+	sp.n_qtiles = (uint32_t)((mq + v->tq - 1) / v->tq);
+	sp.queries = d_q;
+	sp.m = (uint32_t)mq;
+	sp.tau = h->d_tau[0];
+	sp.tau_row = h->d_tau_row[0];
+	sp.cand_cnt = h->d_cnt;
+	sp.cand = h->d_cand;
+	sp.cap = cap;
+	sp.dim = (uint32_t)h->dim;
+	// ~16 workgroups per CU in total, at least 8 groups (128 rows) per workgroup (SearchPass::run_level)
+	const uint32_t target_chunks = (uint32_t)std::max<long>(1, (16L * cus + sp.n_qtiles - 1) / sp.n_qtiles);
+	uint32_t n_chunks = std::min(target_chunks, std::max<uint32_t>(1, sp.n_groups_sel / 8));
+	sp.groups_per_block = (sp.n_groups_sel + n_chunks - 1) / n_chunks;
+	n_chunks = (sp.n_groups_sel + sp.groups_per_block - 1) / sp.groups_per_block;
+	hipLaunchKernelGGL(v->fn, dim3(n_chunks * sp.n_qtiles), dim3(kBlock), 0, st, sp);
+	HIP_TRY(h, hipGetLastError());
+	*kname = v->name;
+	return EXPANN_OK;
+}
+
+// One stage over mq queries -- the whole pass (list == nullptr), or the queries list[0, mq) gathered into staging --
+// with candidate lists of `cap` keys: the scan (the fp16 form where wanted and available, else the exact direct
+// scan), the range select, which answers every query whose list fit and appends the others' numbers to over_list
+// (its length: word(over_word), *n_over on the host), and the stage's one host wait.  A hit log that overflowed
+// leaves entries missing from lists that look complete, so then EVERY query of the stage is passed on.
+int RangePass::filter_stage(bool want_f16, const uint32_t* list, size_t mq, uint32_t cap, int over_word, uint32_t* over_list,
+                            uint32_t* n_over, bool* used_f16, bool* out_of_range) {
+	*out_of_range = false;
+	const GemmF16Variant* gvf = want_f16 ? f16_form(mq) : nullptr;
+	if (gvf) {
+		const int rc = ensure_f16(h, gvf, st);
+		if (rc != EXPANN_OK)
+			return rc;
+		if (h->f16_scale < 0.0f)  // the index does not fit the fp16 range at any allowed scale
+			gvf = nullptr;
+	}
+	*used_f16 = gvf != nullptr;
+	int rc = ensure_workspace(h, mq, cap);  // (it may grow the lists: the stage before has drained)
+	if (rc != EXPANN_OK)
+		return rc;
+	const void* dq = d_queries;
+	const float* dr = d_radii;
+	if (list) {  // the stage's queries and radii into contiguous staging, as a grouped search's tier
+		const uint32_t row_words = (uint32_t)h->dim;  // (fp32 queries)
+		HIP_TRY(h, h->d_range_q.ensure(sizeof(uint32_t) * mq * row_words));  // (grows only while the stream is drained)
+		const uint32_t grid = (uint32_t)std::min<size_t>((mq * row_words + kBlock - 1) / kBlock, 4096);
+		hipLaunchKernelGGL(group_gather_rows_kernel, dim3(grid), dim3(kBlock), 0, st, (const uint32_t*)d_queries, list,
+		                   (uint32_t)mq, row_words, h->d_range_q.as<uint32_t>());
+		hipLaunchKernelGGL(group_gather_rows_kernel, dim3((uint32_t)((mq + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+		                   (const uint32_t*)d_radii, list, (uint32_t)mq, 1u, h->d_tau[0].as<uint32_t>());
+		HIP_TRY(h, hipGetLastError());
+		dq = h->d_range_q;
+		dr = h->d_tau[0];
+	}
+	const bool name_scan = list == nullptr;  // ("scan_kernel" and the scan's time are stage 1's)
+	const bool timed = name_scan && h->profiling && h->ev_used < kEventPairs;
+	const char* kname = "";
+	uint32_t passes = 0, qt_used = 0;
+	if (gvf) {
+		rc = ensure_filter_terms(h, st);  // (no filter is in force: the row terms are the plain ones)
+		if (rc != EXPANN_OK)
+			return rc;
+		rc = launch_f16_query_prep(h, gvf, dq, mq, ip, false, I8fQueryArgs{}, st);
+		if (rc != EXPANN_OK)
+			return rc;
+		// theta' from the caller's radii: a true-unit tau, times c_q under the inner product's rescale
+		hipLaunchKernelGGL(f16_terms_kernel, dim3((uint32_t)((mq + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+		                   h->d_qnrm.as<const float>(), (uint32_t)mq, gemm_f16_filter_eps(h->dim),
+		                   std::ldexp(1.0f, -24) / h->f16_scale * std::sqrt((float)h->dim), dr,
+		                   0.5f * h->f16_scale * h->f16_scale, h->d_theta, ip ? 1 : 0,
+		                   ip ? h->d_qscale.as<const float>() : (const float*)nullptr);
+		HIP_TRY(h, hipMemsetAsync(h->d_cnt, 0, sizeof(uint32_t) * mq, st));
+		if (timed)
+			HIP_TRY(h, hipEventRecord(h->ev[h->ev_used][0], st));
+		rc = launch_scan_f16(h, gvf, (uint32_t)h->n, true, mq, cus, ip, cap, st, &kname, &passes, &qt_used);
+		if (rc != EXPANN_OK)
+			return rc;
+	} else {
+		HIP_TRY(h, hipMemsetAsync(h->d_overflow, 0, 32, st));
+		if (!list)
+			HIP_TRY(h, hipMemcpyAsync(h->d_tau[0], d_radii, sizeof(float) * mq, hipMemcpyDeviceToDevice, st));
+		if (timed)
+			HIP_TRY(h, hipEventRecord(h->ev[h->ev_used][0], st));
+		rc = direct_scan(dq, mq, cap, &kname);
+		if (rc != EXPANN_OK)
+			return rc;
+	}
+	if (timed) {
+		HIP_TRY(h, hipEventRecord(h->ev[h->ev_used][1], st));
+		h->ev_used++;
+	}
+	launch_gather_logs(h, st);
+	HIP_TRY(h, hipGetLastError());
+	RangeSelectParams rp{};
+	rp.cand = h->d_cand;
+	rp.cand_cnt = h->d_cnt;
+	rp.slot_map = list;
+	rp.radii = d_radii;
+	rp.rerank_base = gvf ? (const void*)h->d_base : nullptr;
+	rp.queries = (const float*)d_queries;
+	rp.n_rows = (uint32_t)h->n;
+	rp.dim = (uint32_t)h->dim;
+	rp.metric_ip = ip ? 1u : 0u;
+	rp.max_results = max_results;
+	rp.id_offset = h->id_offset;
+	rp.out_ids = d_ids;
+	rp.out_dists = d_dists;
+	rp.out_counts = d_counts;
+	rp.over_cnt = word(over_word);
+	rp.over_list = over_list;
+	rp.over_cap = (uint32_t)m;
+	rc = launch_range_select(h, rp, (uint32_t)mq, cap, st);
+	if (rc != EXPANN_OK)
+		return rc;
+	// the host wait of the stage: the scan's flags (lost log entries, the largest |q|) and the overflow list's length
+	HIP_TRY(h, hipMemcpyAsync(h->h_flags, h->d_overflow, sizeof(uint32_t) * 4, hipMemcpyDeviceToHost, st));
+	HIP_TRY(h, hipMemcpyAsync(h->h_flags + 4, word(over_word), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+	HIP_TRY(h, hipStreamSynchronize(st));
+	const uint32_t before = *n_over;
+	*n_over = h->h_flags[4];
+	bool far = false;  // queries outside the fp16 range of this index
+	if (gvf) {
+		float qmax;  // bit pattern of max |q| (flags word 2)
+		std::memcpy(&qmax, &h->h_flags[2], sizeof(float));
+		far = !(qmax * h->f16_scale <= 60000.0f);
+	}
+	if (name_scan && !far && (timed || !h->profiling)) {  // the profile's counters and "scan_kernel": stage 1's scan that stands
+		h->prof.scan_launches++;
+		h->prof.scan_rows += h->n;
+		h->prof.scan_query_tiles += passes;
+		h->prof.query_tile = qt_used;
+		h->prof.levels = 1;
+		std::snprintf(h->prof.scan_kernel, sizeof(h->prof.scan_kernel), "%s", kname);
+	}
+	if (gvf) {
+		if (far && !list) {
+			// stage 1: the pass starts again on the exact direct scan.  This attempt's select has already appended the
+			// queries whose list overflowed: the list is emptied, and the attempt leaves neither a timed event pair nor
+			// a count in the profile -- the direct scan is the scan of stage 1
+			HIP_TRY(h, hipMemsetAsync(word(over_word), 0, sizeof(uint32_t), st));
+			*n_over = before;
+			if (timed)
+				h->ev_used--;
+			*out_of_range = true;
+			return EXPANN_OK;
+		}
+		if (far || h->h_flags[0] != 0) {  // every query of the stage goes on, once: the list's length is put back first
+			if (list)
+				HIP_TRY(h, hipMemcpyAsync(over_list + before, list, sizeof(uint32_t) * mq, hipMemcpyDeviceToDevice, st));
+			else
+				hipLaunchKernelGGL(range_iota_kernel, dim3((uint32_t)((mq + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+				                   over_list + before, (uint32_t)mq);
+			HIP_TRY(h, hipGetLastError());
+			*n_over = before + (uint32_t)mq;
+			h->h_flags[7] = *n_over;
+			HIP_TRY(h, hipMemcpyAsync(word(over_word), h->h_flags + 7, sizeof(uint32_t), hipMemcpyHostToDevice, st));
+			HIP_TRY(h, hipStreamSynchronize(st));  // (h_flags[7] is read by the copy)
+		}
+	}
+	return EXPANN_OK;
+}
+
+int RangePass::stage3() {
+	const uint32_t row_words = (uint32_t)h->dim;
+	const size_t k = max_results, nb = n_big;  // (nb <= m <= kMaxQueriesPerPass: one pass of the plain pipeline)
+	HIP_TRY(h, h->d_range_q.ensure(sizeof(uint32_t) * nb * row_words));
+	HIP_TRY(h, h->d_range_ids.ensure(sizeof(uint64_t) * nb * k));
+	if (d_dists)
+		HIP_TRY(h, h->d_range_dists.ensure(sizeof(float) * nb * k));
+	const uint32_t grid = (uint32_t)std::min<size_t>((nb * row_words + kBlock - 1) / kBlock, 4096);
+	hipLaunchKernelGGL(group_gather_rows_kernel, dim3(grid), dim3(kBlock), 0, st, (const uint32_t*)d_queries, big_list(), (uint32_t)nb,
+	                   row_words, h->d_range_q.as<uint32_t>());
+	HIP_TRY(h, hipGetLastError());
+	float* const t_dists = d_dists ? h->d_range_dists.get() : nullptr;
+	const int rc = search_pass(h, h->d_range_q, nb, k, h->d_range_ids, t_dists, st);
+	if (rc != EXPANN_OK)
+		return rc;
+	const uint32_t grid2 = (uint32_t)std::min<size_t>((nb * k + kBlock - 1) / kBlock, 4096);
+	hipLaunchKernelGGL(group_scatter_results_kernel, dim3(grid2), dim3(kBlock), 0, st, (const uint64_t*)h->d_range_ids.get(),
+	                   (const float*)t_dists, big_list(), (uint32_t)nb, (uint32_t)k, d_ids, d_dists);
+	HIP_TRY(h, hipGetLastError());
+	return EXPANN_OK;
+}
+
+int RangePass::run() {
+	HIP_TRY(h, grow_ws(h, h->d_range, sizeof(uint32_t) * (4 + 3 * m)));
+	HIP_TRY(h, hipMemsetAsync(h->d_range, 0, sizeof(uint32_t) * 4, st));
+	bool f16 = false, far = false, unused = false;
+	int rc = filter_stage(true, nullptr, m, cap0, 0, retry_list(), &n_retry, &f16, &far);
+	if (rc == EXPANN_OK && far)
+		rc = filter_stage(false, nullptr, m, cap0, 0, retry_list(), &n_retry, &f16, &far);
+	if (rc != EXPANN_OK)
+		return rc;
+	char stage1_kernel[sizeof(h->prof.scan_kernel)];  // ("scan_kernel" names the scan of stage 1)
+	std::memcpy(stage1_kernel, h->prof.scan_kernel, sizeof(stage1_kernel));
+	// stage 2: at kMaxCap keys.  Where stage 1 ran the fp16 form with shorter lists, that form again first -- the
+	// direct scan of many queries is the slow one -- and the exact direct scan for what is left
+	for (size_t q0 = 0; rc == EXPANN_OK && q0 < n_retry; q0 += kRangeRetryChunk) {
+		const size_t R = std::min(kRangeRetryChunk, (size_t)n_retry - q0);
+		if (f16 && cap0 < kMaxCap && f16_form(R))
+			rc = filter_stage(true, retry_list() + q0, R, kMaxCap, 1, mid_list(), &n_mid, &unused, &far);
+		else
+			rc = filter_stage(false, retry_list() + q0, R, kMaxCap, 2, big_list(), &n_big, &unused, &far);
+	}
+	for (size_t q0 = 0; rc == EXPANN_OK && q0 < n_mid; q0 += kRangeRetryChunk)
+		rc = filter_stage(false, mid_list() + q0, std::min(kRangeRetryChunk, (size_t)n_mid - q0), kMaxCap, 2, big_list(), &n_big,
+		                  &unused, &far);
+	if (rc == EXPANN_OK && n_big > 0 && max_results > 0)
+		rc = stage3();
+	std::memcpy(h->prof.scan_kernel, stage1_kernel, sizeof(stage1_kernel));
+	if (rc != EXPANN_OK)
+		return rc;
+	h->stat_range[0] += m - n_big;
+	h->stat_range[1] += n_big;
+	h->stat_range[2] += n_retry;
+	return EXPANN_OK;
+}
+
+// the checks of a range search, in the header's order, all before the device is touched
+int range_args(expann_index* h, const void* queries, const float* radii, size_t max_results, const uint64_t* ids,
+               const uint32_t* counts) {
+	if (!h)
+		return EXPANN_ERR_INVALID_ARG;
+	if (!queries || !radii || !counts || (!ids && max_results > 0))
+		return h->fail(EXPANN_ERR_INVALID_ARG, "range search: NULL queries / radii / counts / ids pointer");
+	if (max_results > kMaxK)  // (by value, before any GPU work, as k is)
+		return h->fail(EXPANN_ERR_UNSUPPORTED, "range search: max_results beyond " + std::to_string(kMaxK));
+	if (!float_rows(h))
+		return h->fail(EXPANN_ERR_UNSUPPORTED, "range search: EXPANN_DTYPE_F32 and EXPANN_DTYPE_F16 rows only");
+	if (!h->d_base)
+		return h->fail(EXPANN_ERR_NOT_BUILT, "range search before build()");
+	if (h->filter_on)
+		return h->fail(EXPANN_ERR_UNSUPPORTED, "range search under a row filter is not offered");
+	return EXPANN_OK;
+}
+
+// A range search on device buffers (the checks are done): enqueue on `st`, return when it has drained.
+int range_search_device(expann_index* h, const void* d_queries, const float* d_radii, size_t m, size_t max_results,
+                        uint64_t* d_ids, float* d_dists, uint32_t* d_counts, hipStream_t st) {
+	struct HostCall {  // stage 3's passes are the waiting form, whatever "async_search" says
+		expann_index* h;
+		bool was;
+		~HostCall() { h->host_call = was; }
+	} guard{h, h->host_call};
+	h->host_call = true;
+	for (uint64_t& s : h->stat_range)
+		s = 0;
+	// stage 1's capacity: "cand_capacity", else room for twice the rows the caller asks for -- a caller that expects
+	// long rows sizes max_results for them -- within 1 GiB of lists per pass
+	uint32_t cap0 = h->opt_cand_capacity > 0 ? (uint32_t)std::min<long>(h->opt_cand_capacity, kMaxCap)
+	                                         : std::max<uint32_t>(kRangeCap0, pow2ceil((uint32_t)(2 * max_results)));
+	cap0 = std::min(std::max<uint32_t>(pow2ceil(cap0), 64), kMaxCap);
+	if (h->opt_cand_capacity <= 0)
+		while (cap0 > kRangeCap0 && (size_t)cap0 * std::min(m, kMaxQueriesPerPass) > ((size_t)1 << 27))
+			cap0 >>= 1;
+	const int cus = num_cus(h->device);
+	const size_t qbytes = (size_t)h->dim * h->q_elem;
+	for (size_t q0 = 0; q0 < m; q0 += kMaxQueriesPerPass) {
+		const size_t mm = std::min(kMaxQueriesPerPass, m - q0);
+		RangePass pass{h, (const char*)d_queries + q0 * qbytes, d_radii + q0, mm, (uint32_t)max_results,
+		               d_ids ? d_ids + q0 * max_results : nullptr, d_dists ? d_dists + q0 * max_results : nullptr, d_counts + q0,
+		               st, h->metric == EXPANN_METRIC_IP, cus, cap0};
+		const int rc = pass.run();
+		if (rc != EXPANN_OK)
+			return rc;
+	}
+	HIP_TRY(h, hipStreamSynchronize(st));
+	return EXPANN_OK;
+}
+
 }  // namespace
 
 int expann_set_row_filter(expann_index* h, const uint32_t* allow_bits, size_t n_words) {
@@ -4148,6 +4560,59 @@ int expann_search_grouped(expann_index* h, const void* queries, const uint32_t* 
 	HIP_TRY(h, hipMemcpyAsync(ids, h->d_ids, sizeof(uint64_t) * m * k, hipMemcpyDeviceToHost, h->stream));
 	if (dists)
 		HIP_TRY(h, hipMemcpyAsync(dists, h->d_dists, sizeof(float) * m * k, hipMemcpyDeviceToHost, h->stream));
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
+	return EXPANN_OK;
+}
+
+int expann_range_search_device(expann_index* h, const void* d_queries, const float* d_radii, size_t m, size_t max_results,
+                               uint64_t* d_ids, float* d_dists, uint32_t* d_counts, void* stream) {
+	if (const int rc = range_args(h, d_queries, d_radii, max_results, d_ids, d_counts))
+		return rc;
+	if (m == 0)
+		return EXPANN_OK;
+	if (h->async_pending) {  // deferred searches first
+		const int rs = expann_sync(h);
+		if (rs != EXPANN_OK)
+			return rs;
+	}
+	HIP_TRY(h, hipSetDevice(h->device));
+	return range_search_device(h, d_queries, d_radii, m, max_results, d_ids, d_dists, d_counts,
+	                           stream ? (hipStream_t)stream : h->stream);
+}
+
+int expann_range_search(expann_index* h, const void* queries, const float* radii, size_t m, size_t max_results, uint64_t* ids,
+                        float* dists, uint32_t* counts) {
+	if (const int rc = range_args(h, queries, radii, max_results, ids, counts))
+		return rc;
+	if (m == 0)
+		return EXPANN_OK;
+	if (h->async_pending) {  // deferred searches first
+		const int rs = expann_sync(h);
+		if (rs != EXPANN_OK)
+			return rs;
+	}
+	HIP_TRY(h, hipSetDevice(h->device));
+	const size_t qbytes = m * (size_t)h->dim * h->q_elem, cells = m * max_results;
+	HIP_TRY(h, h->d_q.ensure(qbytes));
+	HIP_TRY(h, h->d_range_radii.ensure(sizeof(float) * m));
+	HIP_TRY(h, h->d_range_counts.ensure(sizeof(uint32_t) * m));
+	if (cells) {
+		HIP_TRY(h, h->d_ids.ensure(sizeof(uint64_t) * cells));
+		if (dists)
+			HIP_TRY(h, h->d_dists.ensure(sizeof(float) * cells));
+	}
+	HIP_TRY(h, hipMemcpyAsync(h->d_q, queries, qbytes, hipMemcpyHostToDevice, h->stream));
+	HIP_TRY(h, hipMemcpyAsync(h->d_range_radii, radii, sizeof(float) * m, hipMemcpyHostToDevice, h->stream));
+	const int rc = range_search_device(h, h->d_q, h->d_range_radii, m, max_results, cells ? h->d_ids.get() : nullptr,
+	                                   (cells && dists) ? h->d_dists.get() : nullptr, h->d_range_counts, h->stream);
+	if (rc != EXPANN_OK)
+		return rc;
+	HIP_TRY(h, hipMemcpyAsync(counts, h->d_range_counts, sizeof(uint32_t) * m, hipMemcpyDeviceToHost, h->stream));
+	if (cells) {
+		HIP_TRY(h, hipMemcpyAsync(ids, h->d_ids, sizeof(uint64_t) * cells, hipMemcpyDeviceToHost, h->stream));
+		if (dists)
+			HIP_TRY(h, hipMemcpyAsync(dists, h->d_dists, sizeof(float) * cells, hipMemcpyDeviceToHost, h->stream));
+	}
 	HIP_TRY(h, hipStreamSynchronize(h->stream));
 	return EXPANN_OK;
 }

@@ -122,6 +122,40 @@ class GpuBruteForceEngine:
             self._h, C.c_void_p(q_ptr), m, k, C.c_void_p(ids_ptr), C.c_void_p(dists_ptr),
             C.c_void_p(stream)))
 
+    def range_search(self, queries, radius, max_results):
+        """expann_range_search: every row with score <= radius (a scalar, or an array [m] of per-query radii; for
+        the inner product the score is -dot).  Returns (ids[m, max_results] uint64, dists[m, max_results] float32,
+        counts[m] uint32): counts is the exact number of rows in range, the rows are the min(count, max_results)
+        nearest ones, ascending by (score, id), padded with 2^64-1 / +inf.  max_results = 0 only counts.  fp32 and
+        fp16 rows; no row filter in force."""
+        queries = np.ascontiguousarray(queries, dtype=np.float32)
+        if queries.ndim != 2 or queries.shape[1] != self.dim:
+            raise ValueError(f"queries must be [m, {self.dim}]")
+        m, max_results = queries.shape[0], int(max_results)
+        radii = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float32), (m,)))
+        ids = np.empty((m, max_results), dtype=np.uint64)
+        dists = np.empty((m, max_results), dtype=np.float32)
+        counts = np.zeros(m, dtype=np.uint32)
+        nul = C.c_void_p(None)
+        _lib.check(self._h, self._L.expann_range_search(
+            self._h, queries.ctypes.data, radii.ctypes.data, m, max_results,
+            ids.ctypes.data if max_results else nul, dists.ctypes.data if max_results else nul,
+            counts.ctypes.data))
+        return ids, dists, counts
+
+    @staticmethod
+    def range_lims(counts, max_results):
+        """CSR offsets [m + 1] of the rows range_search returned: the running sum of min(counts, max_results)."""
+        kept = np.minimum(np.asarray(counts, dtype=np.int64), int(max_results))
+        return np.concatenate([[0], np.cumsum(kept)]).astype(np.int64)
+
+    def range_search_device(self, q_ptr, radii_ptr, m, max_results, ids_ptr, dists_ptr, counts_ptr, stream=0):
+        """expann_range_search_device: queries, radii [m] float32 and the outputs are device pointers (ids_ptr /
+        dists_ptr may be 0 where the C call allows NULL); returns after `stream` has drained."""
+        _lib.check(self._h, self._L.expann_range_search_device(
+            self._h, C.c_void_p(q_ptr), C.c_void_p(radii_ptr), m, int(max_results), C.c_void_p(ids_ptr or None),
+            C.c_void_p(dists_ptr or None), C.c_void_p(counts_ptr), C.c_void_p(stream)))
+
     def sync(self):
         """expann_sync: wait for the searches enqueued under set_option("async_search", 1) and
         report on them (raises if one needs the synchronous retry)."""
@@ -184,7 +218,8 @@ class GpuBruteForceEngine:
         "filter_active" (0 / 1) and "filter_rows" (rows the row filter allows; n when none is set);
         "base_bytes" (device bytes of the rows themselves: n * dim * element size);
         "groups_active", "group_count", and of the last grouped search "group_list_queries", "group_filter_queries",
-        "group_any_queries", "group_pad_queries", "group_filter_passes"."""
+        "group_any_queries", "group_pad_queries", "group_filter_passes";
+        of the last range search "range_list_queries", "range_topk_queries", "range_retries"."""
         v = C.c_uint64(0)
         _lib.check(self._h, self._L.expann_get_stat(self._h, name.encode(), C.byref(v)))
         return int(v.value)

@@ -144,6 +144,14 @@ struct gpu_brute_force_engine : public ann_engine<T, gpu_brute_force_engine<T>> 
 		single("query_k_batch_grouped");
 		check(expann_search_grouped(handle, queries, query_groups, m, k, ids, dists));
 	}
+	// Extension: range search (expann_range_search, THE RANGE RULE).  counts[i] = the exact number of rows with
+	// score <= radii[i]; ids / dists [m][max_results] hold the min(counts[i], max_results) nearest of them, ascending,
+	// padded with UINT64_MAX / +inf (dists may be nullptr; max_results == 0 only counts).  One device, float rows.
+	void range_query_batch(const T* queries, const float* radii, size_t m, size_t max_results, uint64_t* ids, float* dists,
+	                       uint32_t* counts) {
+		single("range_query_batch");
+		check(expann_range_search(handle, queries, radii, m, max_results, ids, dists, counts));
+	}
 	const std::string _name() { return "GPU Brute-Force Engine (MI355X)"; }
 	const param_list_t _param_list() {
 		param_list_t pl;

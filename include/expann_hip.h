@@ -773,6 +773,51 @@ int expann_search_grouped(expann_index* h, const void* queries, const uint32_t* 
 int expann_search_grouped_device(expann_index* h, const void* d_queries, const uint32_t* query_groups /* HOST [m] */,
                                  size_t m, size_t k, uint64_t* d_ids, float* d_dists, void* stream);
 
+/* Range search of the brute-force index: every row within a per-query radius, exact (appended; EXPANN_ABI_VERSION
+ * stays 2: nothing that existed changed).
+ * THE RANGE RULE.  score is what expann_search reports: for EXPANN_METRIC_L2 the squared L2 in the reference's FMA
+ * lane order, for EXPANN_METRIC_IP -dot (so "dot >= 0.8" is radii[i] = -0.8f).  Row b is in range of query i iff
+ * score(q_i, b) <= radii[i] -- inclusive, the comparison every threshold of this engine makes.  A NaN radius is in
+ * range of nothing.
+ *   counts[i] is the exact number of rows in range, whatever it is, up to n: never an estimate, never saturated.
+ *   ids[i][0 .. max_results) and dists[i][...] hold the min(counts[i], max_results) in-range rows with the smallest
+ *   (score, id), ascending: ids with id_offset applied, the fp32 distance bits expann_search returns, ties by lower
+ *   id, the tail padded with UINT64_MAX / +inf.  dists may be NULL.  counts[i] > max_results tells the caller that
+ *   the row was truncated and that what it holds are the nearest rows.
+ *   0 <= max_results <= 8192.  With max_results == 0 the call only counts, and ids / dists may be NULL.
+ * Served: EXPANN_DTYPE_F32 and EXPANN_DTYPE_F16 rows (an F16 index returns bit for bit what the F32 index of the
+ * upcast rows returns: THE RULE of that dtype), both metrics, every dim the index takes, expann_set_base_device rows
+ * with their id_offset, m beyond one pass (32 768 queries).
+ * Errors, in this order, all before the device is touched: handle NULL EXPANN_ERR_INVALID_ARG; queries, radii or
+ * counts NULL, or ids NULL with max_results > 0, EXPANN_ERR_INVALID_ARG; max_results > 8192 EXPANN_ERR_UNSUPPORTED
+ * (by value, as k is); a dtype other than F32 / F16 EXPANN_ERR_UNSUPPORTED; no rows on the device
+ * EXPANN_ERR_NOT_BUILT; a row filter in force EXPANN_ERR_UNSUPPORTED.  Row groups that are merely set are ignored, as
+ * the plain searches ignore them.  m == 0 is EXPANN_OK.  A failed call leaves the handle usable.
+ * Both calls return after their stream has drained: they ignore "async_search" and first wait for outstanding
+ * deferred searches (expann_search_grouped's rule).  The device call reads d_radii and writes its outputs in the
+ * order of `stream` (a hipStream_t; NULL = the handle's own).
+ * How a batch is served (csrc/select_range.hpp).  The engine's filters keep every row with
+ * score <= tau for ANY tau, so the caller's radii are the thresholds: no sampled pass, no estimate.  Stage 1: every
+ * query, candidate lists of "cand_capacity" keys (expann_set_option; unset: room for twice max_results, at least
+ * 1 024) -- the fp16 single-product form where the plain search would use a matrix-core form and the queries fit the
+ * index's fp16 range, every candidate re-scored exactly and cut at the radius; else the exact direct scan.  Stage 2:
+ * the queries whose list did not fit, at 16 384 keys: the fp16 form again where stage 1 ran it with shorter lists,
+ * then the exact direct scan, whose counter is the exact count.  Stage 3: queries with more than 16 384
+ * rows in range -- their max_results nearest rows are all in range, so the plain pipeline at k = max_results writes
+ * them.  One host wait per stage that runs.  Never the uint8 shadow, the int8 filter, speculative thresholds, the
+ * bf16x3 form or the latency mode in stages 1 and 2, whatever the options say.
+ * expann_get_stat, of the last range search: "range_list_queries" (answered from a candidate list, stages 1 and 2),
+ * "range_topk_queries" (more than 16 384 rows in range; the two add up to m), "range_retries" (queries that stage
+ * 1's lists could not hold).  expann_get_profile's scan_kernel names the scan of stage 1.
+ * Not offered: range search under a row filter or per row group, on 8-bit / int16 rows, on the sharded handles, in
+ * the graph engine; deferred ("async_search") range searches; a CSR-packed output (lims are the running sum of
+ * min(counts, max_results)); more than 8192 rows per query. */
+int expann_range_search(expann_index* h, const void* queries, const float* radii, size_t m,
+                        size_t max_results, uint64_t* ids, float* dists, uint32_t* counts);      /* host buffers */
+int expann_range_search_device(expann_index* h, const void* d_queries, const float* d_radii, size_t m,
+                               size_t max_results, uint64_t* d_ids, float* d_dists, uint32_t* d_counts,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif
