@@ -11,82 +11,112 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "filter_rows.hpp"
 #include "graph_build.hpp"
 #include "graph_flat_scan.hpp"
+#include "graph_options.hpp"
 #include "graph_search.hpp"
 #include "host_common.hpp"
 #include "quantize.hpp"
 
 using namespace expann;
 
-struct expann_graph {
+// The handle's state, grouped by who makes it and when it dies, as expann_index's (expann_hip.hip, whose groups have
+// the names without "Graph"): bases of expann_graph (use sites read g->d_adj0) whose members free themselves, so a
+// group is forgotten as a value, g->forget<GraphRowGroups>(), and a member added to one needs no edit anywhere else.
+
+// what expann_graph_create fixes
+struct GraphRows {
 	int dim = 0, device = 0;
 	size_t n = 0;
 	uint32_t n_layers = 0, starting_vertex = 0, max_degree0 = 0;
 	// the rows: [n][dim] floats, or -- rows_f16, a handle made by expann_graph_create_f16 -- [n][dim] binary16 values;
 	// the flag picks the _Float16 instances of the walk, the scan and the quantisers, and nothing else
-	void* d_vectors = nullptr;
+	DevPtr<void> d_vectors;
 	bool rows_f16 = false;
-	uint8_t* d_compressed = nullptr;
-	// quantizer_ranged_q8 copy of the rows (bytes in [0, 127]) with its scale_factor / offset, built at the first
-	// use of the ranged mode; ranged_state: 0 = not built yet, 1 = usable, -1 = the quantiser is unusable
-	uint8_t* d_ranged = nullptr;
+	DevPtr<uint32_t> d_layer_off;
+	DevPtr<uint32_t> d_neighbours;
+	DevPtr<uint32_t> d_adj0;  // [n][stride0] layer-0 lists at a fixed stride, padded with UINT32_MAX
+	uint32_t stride0 = 0;
+};
+
+// the byte copies of the rows, each made at the first use of its mode
+struct GraphRowBytes {
+	DevPtr<uint8_t> d_compressed;
+	// quantizer_ranged_q8 copy of the rows (bytes in [0, 127]) with its scale_factor / offset;
+	// ranged_state: 0 = not built yet, 1 = usable, -1 = the quantiser is unusable
+	DevPtr<uint8_t> d_ranged;
 	float ranged_scale = 0, ranged_offset = 0;
 	int ranged_state = 0;
-	uint32_t* d_layer_off = nullptr;
-	uint32_t* d_neighbours = nullptr;
-	uint32_t* d_adj0 = nullptr;   // [n][stride0] layer-0 lists at a fixed stride, padded with UINT32_MAX
-	uint32_t stride0 = 0;
-	uint8_t* d_visited = nullptr;  // epoch bytes [slots][n], or -- vis_words != 0 -- bitsets [slots][vis_words]
+};
+
+// one visited set per workgroup of the search grid, made at create
+struct GraphVisited {
+	DevPtr<uint8_t> d_visited;  // epoch bytes [slots][n], or -- vis_words != 0 -- bitsets [slots][vis_words]
 	uint32_t vis_words = 0;
-	uint32_t* d_epochs = nullptr;
+	DevPtr<uint32_t> d_epochs;
 	uint32_t slots = 0;
-	hipStream_t stream = nullptr;
-	hipEvent_t ev0 = nullptr, ev1 = nullptr;
-	hipEvent_t ev2 = nullptr;  // behind the redo launch of a host-buffer grouped search (made at the first one)
-	double last_ms = 0;
+};
+
+// what the searches share, made at the handle's first one (graph_dev_init), and the bookkeeping of the device-buffer
+// searches (expann_graph_search_device / expann_graph_sync)
+struct GraphDeviceSearches {
 	// One counter slot per search: {overflow flag, first launch's query counter, redo count, redo launch's query
 	// counter, and -- grouped searches -- the scan's query counter and the queries walked, scanned, padded}; a search
 	// resets its slot in stream order.  Slots [0, kGraphMaxOutstanding) belong to the
 	// outstanding device-buffer searches (the sync reads them all), the last one to the host-buffer call.
 	DevPtr<uint32_t> d_dev_ctr;            // [kGraphMaxOutstanding + 1][kGraphCtrWords]
 	PinPtr<uint32_t> h_dev_ctr;            // the same, read back
-	// ---- device-buffer searches (expann_graph_search_device / expann_graph_sync) ----
 	DevPtr<unsigned long long> d_dc_total; // [1] distcomps of every device search since create
 	PinPtr<unsigned long long> h_dc_total;
 	GrowPtr<uint32_t> d_redo_list;         // [largest m seen]
-	hipStream_t dev_stream = nullptr;      // the stream of the outstanding searches
+	hipStream_t dev_stream = nullptr;      // the stream of the outstanding searches (the caller's, or `stream`: borrowed)
 	uint32_t dev_outstanding = 0;          // searches enqueued since the last drain (= slots in use)
-	hipEvent_t ev_dev[3] = {nullptr, nullptr, nullptr};  // before the first launch, after it, after the redo launch
-	bool dev_timed = false, dev_timed_redo = false;       // ev_dev hold the last search (and its redo launch)
-	long opt_cand_cap = 0, opt_redo_cap = 0;
-	// ---- row filter (expann_graph_set_row_filter): the handle's copy of the bitmap, zero from n on, and the
-	// allowed vertices as an ascending list (what the scan of a sparse filter reads), both made at set time
+	OwnedEvent ev_dev[3];                  // before the first launch, after it, after the redo launch
+	bool dev_timed = false, dev_timed_redo = false;  // ev_dev hold the last search (and its redo launch)
+	uint64_t pend_redo_queries = 0, pend_overflows = 0;  // what the drains since the last sync found
+};
+
+// row filter (expann_graph_set_row_filter): the handle's copy of the bitmap, zero from n on, and the allowed
+// vertices as an ascending list (what the scan of a sparse filter reads), both made at set time
+struct GraphRowFilter {
 	DevPtr<uint32_t> d_allow;       // [ceil(n / 32)]
 	DevPtr<uint32_t> d_allow_list;  // [n_allowed]
 	bool filter_on = false;
 	uint32_t n_allowed = 0;
-	long opt_flat_rows = 0;         // "filter_flat_rows": 0 = kGraphFlatRowsAuto
-	uint64_t stat_flat = 0;         // searches answered without a walk
-	// ---- row groups (expann_graph_set_row_groups): every row's label, and the directory made on the host at set
-	// time -- the distinct labels ascending (0xFFFFFFFF left out), their offsets, and each group's rows ascending
+};
+
+// row groups (expann_graph_set_row_groups): every row's label, and the directory made on the host at set time -- the
+// distinct labels ascending (0xFFFFFFFF left out), their offsets, and each group's rows ascending
+struct GraphRowGroups {
 	DevPtr<uint32_t> d_row_groups;  // [n]
 	DevPtr<uint32_t> d_group_keys;  // [n_groups]
 	DevPtr<uint32_t> d_group_off;   // [n_groups + 1]
 	DevPtr<uint32_t> d_group_rows;  // [rows that carry a label other than 0xFFFFFFFF]
 	bool groups_on = false;
 	uint32_t n_groups = 0;
+};
+
+// the counters behind expann_graph_get_stat (kGraphStatTable)
+struct GraphStats {
+	uint64_t stat_flat = 0;  // searches answered without a walk
 	// queries of grouped searches by how they were served {walk, scan, pad}: counted in words 5..7 of a search's
 	// counter slot, folded in when the search is checked
 	uint64_t stat_group[3] = {0, 0, 0};
-	// what the drains since the last sync found, and the counters behind expann_graph_get_stat
-	uint64_t pend_redo_queries = 0, pend_overflows = 0;
 	uint64_t stat_redo_queries = 0, stat_redo_overflows = 0, stat_deferred = 0, stat_distcomps = 0;
 	double stat_redo_ms = 0;
+};
+
+// the handle's own stream, the host-buffer calls' events, launch plans, statistics, the last error
+struct GraphRuntime : GraphStats {
+	OwnedStream stream;
+	OwnedEvent ev0, ev1;
+	OwnedEvent ev2;  // behind the redo launch of a host-buffer grouped search (made at the first one)
+	double last_ms = 0;
 	// attribute, occupancy and grid of a launch, per (instance, LDS size)
 	struct LaunchPlan {
 		const void* fn;
@@ -95,6 +125,12 @@ struct expann_graph {
 	};
 	std::vector<LaunchPlan> plans;
 	mutable std::string err;
+};
+
+// (base order: the stream and its events outlive every buffer when a handle is deleted)
+struct expann_graph : GraphOptions, GraphRuntime, GraphRows, GraphRowBytes, GraphVisited, GraphDeviceSearches, GraphRowFilter,
+                      GraphRowGroups {
+	template <typename Group> void forget() { static_cast<Group&>(*this) = Group{}; }
 	int fail(int code, const std::string& msg) const {
 		err = msg;
 		return code;
@@ -210,13 +246,14 @@ int graph_ensure_ranged(expann_graph* g) {
 		return EXPANN_OK;
 	HIP_TRY(g, hipSetDevice(g->device));
 	const size_t nv = g->n * (size_t)g->dim;
-	DevBuf b_mm, b_so, b_rows;
+	DevBuf b_mm, b_so;
+	DevPtr<uint8_t> b_rows;  // built aside: the handle takes it when the quantiser is usable
 	HIP_TRY(g, b_mm.alloc(2 * sizeof(uint32_t)));
 	HIP_TRY(g, b_so.alloc(2 * sizeof(float)));
-	HIP_TRY(g, b_rows.alloc(nv));
-	HIP_TRY(g, g->rows_f16 ? launch_quantize_ranged_q8((const _Float16*)g->d_vectors, nv, b_mm.as<uint32_t>(),
+	HIP_TRY(g, hipMalloc(&b_rows, nv));
+	HIP_TRY(g, g->rows_f16 ? launch_quantize_ranged_q8(g->d_vectors.as<const _Float16>(), nv, b_mm.as<uint32_t>(),
 	                                                   b_rows.as<int8_t>(), b_so.as<float>(), g->stream)
-	                       : launch_quantize_ranged_q8((const float*)g->d_vectors, nv, b_mm.as<uint32_t>(),
+	                       : launch_quantize_ranged_q8(g->d_vectors.as<const float>(), nv, b_mm.as<uint32_t>(),
 	                                                   b_rows.as<int8_t>(), b_so.as<float>(), g->stream));
 	float so[2] = {0, 0};
 	HIP_TRY(g, hipMemcpy(so, b_so.p, sizeof(so), hipMemcpyDeviceToHost));
@@ -224,8 +261,7 @@ int graph_ensure_ranged(expann_graph* g) {
 		g->ranged_state = -1;  // (the copy is dropped with b_rows)
 		return g->fail(EXPANN_ERR_INVALID_ARG, unusable);
 	}
-	g->d_ranged = b_rows.as<uint8_t>();
-	b_rows.p = nullptr;
+	g->d_ranged = std::move(b_rows);
 	g->ranged_scale = so[0];
 	g->ranged_offset = so[1];
 	g->ranged_state = 1;
@@ -242,11 +278,13 @@ constexpr uint32_t kGraphCtrWords = 8;          // counter words per search
 constexpr uint32_t kGraphFlatRowsAuto = 128000;
 // (kGraphFlatMaxKeys, the min(k, allowed) the scan keeps in LDS, is graph_search.hpp's: the group kernels decide by it)
 
-// the argument checks of a search, in the order the header documents, all before the device is touched;
-// *empty: m == 0, nothing to do
+// the argument checks of a search, a NULL handle first, in the order the header documents, all before the device is
+// touched; *empty: m == 0, nothing to do
 int graph_search_args(expann_graph* g, const void* queries, size_t m, size_t k, size_t ef_search, int mode,
                       const void* ids, const void* dists, bool* empty) {
 	*empty = false;
+	if (!g)
+		return EXPANN_ERR_INVALID_ARG;
 	if (mode < EXPANN_GRAPH_FP32 || mode > EXPANN_GRAPH_RANGED_Q8)
 		return g->fail(EXPANN_ERR_INVALID_ARG, "mode must be 0 (fp32), 1 (uint8 cast) or 2 (ranged int8)");
 	if (k == 0 || ef_search == 0)
@@ -278,7 +316,7 @@ uint32_t graph_first_cand_cap(size_t ef_search) {
 // queries, the outputs, cand_cap and the counters
 GraphSearchParams graph_base_params(const expann_graph* g, int mode, size_t k, size_t ef_search) {
 	GraphSearchParams p{};
-	p.vectors = (const float*)g->d_vectors;  // (rows_f16: halves, read by the _Float16 instances only)
+	p.vectors = g->d_vectors.as<const float>();  // (rows_f16: halves, read by the _Float16 instances only)
 	p.compressed = mode == EXPANN_GRAPH_RANGED_Q8 ? g->d_ranged : g->d_compressed;
 	p.q_scale = g->ranged_scale;
 	p.q_offset = g->ranged_offset;
@@ -294,7 +332,7 @@ GraphSearchParams graph_base_params(const expann_graph* g, int mode, size_t k, s
 	p.max_degree = g->max_degree0;
 	p.list_cap = std::max<uint32_t>(std::max<uint32_t>(g->stride0, (uint32_t)ef_search), 4);
 	p.visited = g->d_visited;
-	p.vis_bits = reinterpret_cast<uint32_t*>(g->d_visited);
+	p.vis_bits = g->d_visited.as<uint32_t>();
 	p.vis_words = g->vis_words;
 	p.epochs = g->d_epochs;
 	p.dim = (uint32_t)g->dim;
@@ -342,7 +380,7 @@ int graph_drain(expann_graph* g) {
 int graph_dev_init(expann_graph* g) {
 	if (g->d_dev_ctr)
 		return EXPANN_OK;
-	for (hipEvent_t& ev : g->ev_dev)
+	for (OwnedEvent& ev : g->ev_dev)
 		if (!ev)
 			HIP_TRY(g, hipEventCreate(&ev));
 	if (!g->h_dev_ctr)
@@ -382,9 +420,9 @@ int graph_ensure_bytes(expann_graph* g, int mode) {
 	if (mode == EXPANN_GRAPH_U8_CAST && !g->d_compressed) {  // quantizer_simple<uint8_t>::build, :485-486
 		HIP_TRY(g, hipMalloc(&g->d_compressed, g->n * (size_t)g->dim));
 		if (g->rows_f16)
-			launch_quantize_simple_u8((const _Float16*)g->d_vectors, g->n * (size_t)g->dim, g->d_compressed, g->stream);
+			launch_quantize_simple_u8(g->d_vectors.as<const _Float16>(), g->n * (size_t)g->dim, g->d_compressed, g->stream);
 		else
-			launch_quantize_simple_u8((const float*)g->d_vectors, g->n * (size_t)g->dim, g->d_compressed, g->stream);
+			launch_quantize_simple_u8(g->d_vectors.as<const float>(), g->n * (size_t)g->dim, g->d_compressed, g->stream);
 		HIP_TRY(g, hipGetLastError());
 		HIP_TRY(g, hipStreamSynchronize(g->stream));
 	}
@@ -484,24 +522,31 @@ GraphServe graph_serve(const expann_graph* g, size_t k) {
 	return kServeScan;
 }
 
+// what an exact scan takes from the parameters `w` of the walk it stands in for -- the rows, the queries, the
+// outputs, the distcomps total -- with the keys it keeps in LDS and its query counter
+GraphFlatParams graph_flat_params(const GraphSearchParams& w, uint32_t kk, uint32_t* next_query) {
+	GraphFlatParams f{};
+	f.vectors = w.vectors;
+	f.dim = w.dim;
+	f.queries = w.queries;
+	f.m = w.m;
+	f.k = w.k;
+	f.kk = kk;
+	f.out_ids = w.out_ids;
+	f.out_dists = w.out_dists;
+	f.out_distcomps = w.out_distcomps;
+	f.next_query = next_query;
+	f.distcomps_total = w.distcomps_total;
+	return f;
+}
+
 // the scan of the allowed rows for the search whose queries and outputs `w` names (a walk's parameters: the scan
 // takes what it shares with them), with the counter slot `ctr`, on `st` between two events
 int graph_enqueue_flat(expann_graph* g, const GraphSearchParams& w, uint32_t* ctr, hipStream_t st, hipEvent_t before,
                        hipEvent_t after) {
-	GraphFlatParams f{};
-	f.vectors = (const float*)g->d_vectors;
-	f.dim = (uint32_t)g->dim;
+	GraphFlatParams f = graph_flat_params(w, std::min<uint32_t>(w.k, g->n_allowed), ctr + 1);
 	f.list = g->d_allow_list;
 	f.n_list = g->n_allowed;
-	f.queries = w.queries;
-	f.m = w.m;
-	f.k = w.k;
-	f.kk = std::min<uint32_t>(w.k, g->n_allowed);
-	f.out_ids = w.out_ids;
-	f.out_dists = w.out_dists;
-	f.out_distcomps = w.out_distcomps;
-	f.next_query = ctr + 1;
-	f.distcomps_total = w.distcomps_total;
 	const size_t lds = graph_flat_lds_bytes(f.kk, f.dim);
 	uint32_t resident = 0;
 	void (*const scan)(GraphFlatParams) = g->rows_f16 ? graph_flat_scan_kernel<_Float16> : graph_flat_scan_kernel<float>;
@@ -545,35 +590,31 @@ int graph_set_row_filter(expann_graph* g, const uint32_t* bits, size_t n_words, 
 	// searches in flight still read the old filter: they are waited for (their counters stay for the next sync)
 	HIP_TRY(g, graph_wait_outstanding(g));
 	hipStream_t st = user_st ? user_st : g->stream;
-	DevPtr<uint32_t> b_bits, b_stat, b_list;
-	HIP_TRY(g, hipMalloc(&b_bits, sizeof(uint32_t) * need_words));
+	GraphRowFilter f;
+	DevPtr<uint32_t> b_stat;
+	HIP_TRY(g, hipMalloc(&f.d_allow, sizeof(uint32_t) * need_words));
 	HIP_TRY(g, hipMalloc(&b_stat, sizeof(uint32_t) * (2 + kFilterSegs)));
-	HIP_TRY(g, hipMemcpyAsync(b_bits, bits, sizeof(uint32_t) * need_words,
+	HIP_TRY(g, hipMemcpyAsync(f.d_allow, bits, sizeof(uint32_t) * need_words,
 	                          on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
 	HIP_TRY(g, hipMemsetAsync(b_stat, 0, sizeof(uint32_t) * (2 + kFilterSegs), st));
-	hipLaunchKernelGGL(filter_count_kernel, dim3(kFilterSegs), dim3(kBlock), 0, st, b_bits.get(), (uint32_t)g->n,
+	hipLaunchKernelGGL(filter_count_kernel, dim3(kFilterSegs), dim3(kBlock), 0, st, f.d_allow.get(), (uint32_t)g->n,
 	                   (uint32_t)need_words, b_stat.get(), b_stat.get() + 2);
 	HIP_TRY(g, hipGetLastError());
 	uint32_t stat[2] = {0, 0};
 	HIP_TRY(g, hipMemcpyAsync(stat, b_stat, sizeof(stat), hipMemcpyDeviceToHost, st));
 	HIP_TRY(g, hipStreamSynchronize(st));  // walk or scan is chosen on the host: one wait per filter change
-	const uint32_t allowed = stat[0];
-	if (allowed) {
-		HIP_TRY(g, hipMalloc(&b_list, sizeof(uint32_t) * allowed));
-		hipLaunchKernelGGL(filter_compact_kernel, dim3(kFilterSegs), dim3(kBlock), 0, st, (const uint32_t*)b_bits.get(),
-		                   (uint32_t)need_words, (const uint32_t*)b_stat.get() + 2, 1u, b_list.get(), allowed);
+	f.n_allowed = stat[0];
+	if (f.n_allowed) {
+		HIP_TRY(g, hipMalloc(&f.d_allow_list, sizeof(uint32_t) * f.n_allowed));
+		hipLaunchKernelGGL(filter_compact_kernel, dim3(kFilterSegs), dim3(kBlock), 0, st, (const uint32_t*)f.d_allow.get(),
+		                   (uint32_t)need_words, (const uint32_t*)b_stat.get() + 2, 1u, f.d_allow_list.get(), f.n_allowed);
 		HIP_TRY(g, hipGetLastError());
 		HIP_TRY(g, hipStreamSynchronize(st));
 	}
 	if (st != g->stream)
 		HIP_TRY(g, hipStreamSynchronize(g->stream));
-	g->d_allow.reset();
-	g->d_allow_list.reset();
-	g->d_allow.p = b_bits.p;
-	g->d_allow_list.p = b_list.p;
-	b_bits.p = b_list.p = nullptr;
-	g->n_allowed = allowed;
-	g->filter_on = true;
+	f.filter_on = true;
+	static_cast<GraphRowFilter&>(*g) = std::move(f);  // (the old filter goes with the local)
 	return EXPANN_OK;
 }
 
@@ -592,33 +633,27 @@ int graph_set_row_groups(expann_graph* g, const uint32_t* groups, size_t n, bool
 	// searches in flight still read the old groups: they are waited for (their counters stay for the next sync)
 	HIP_TRY(g, graph_wait_outstanding(g));
 	hipStream_t st = user_st ? user_st : g->stream;
-	std::vector<uint32_t> lab(n);
-	if (on_device) {
-		HIP_TRY(g, hipMemcpyAsync(lab.data(), groups, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
-		HIP_TRY(g, hipStreamSynchronize(st));
-	} else
-		std::memcpy(lab.data(), groups, sizeof(uint32_t) * n);
+	std::vector<uint32_t> lab;
+	if (int rc = fetch_group_labels(g, groups, n, on_device, st, lab))
+		return rc;
 	const GroupDirectory dir = build_group_directory(lab.data(), n);  // (host_common.hpp: shared with the brute-force index)
 	const std::vector<uint32_t>&keys = dir.keys, &off = dir.off, &order = dir.rows;
 	const size_t n_rows = dir.n_rows();
-	DevPtr<uint32_t> b_lab, b_keys, b_off, b_rows;
-	HIP_TRY(g, hipMalloc(&b_lab, sizeof(uint32_t) * n));
-	HIP_TRY(g, hipMalloc(&b_keys, sizeof(uint32_t) * std::max<size_t>(keys.size(), 1)));
-	HIP_TRY(g, hipMalloc(&b_off, sizeof(uint32_t) * off.size()));
-	HIP_TRY(g, hipMalloc(&b_rows, sizeof(uint32_t) * std::max<size_t>(n_rows, 1)));
-	HIP_TRY(g, hipMemcpy(b_lab, lab.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+	GraphRowGroups b;
+	HIP_TRY(g, hipMalloc(&b.d_row_groups, sizeof(uint32_t) * n));
+	HIP_TRY(g, hipMalloc(&b.d_group_keys, sizeof(uint32_t) * std::max<size_t>(keys.size(), 1)));
+	HIP_TRY(g, hipMalloc(&b.d_group_off, sizeof(uint32_t) * off.size()));
+	HIP_TRY(g, hipMalloc(&b.d_group_rows, sizeof(uint32_t) * std::max<size_t>(n_rows, 1)));
+	HIP_TRY(g, hipMemcpy(b.d_row_groups, lab.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
 	if (!keys.empty())
-		HIP_TRY(g, hipMemcpy(b_keys, keys.data(), sizeof(uint32_t) * keys.size(), hipMemcpyHostToDevice));
-	HIP_TRY(g, hipMemcpy(b_off, off.data(), sizeof(uint32_t) * off.size(), hipMemcpyHostToDevice));
+		HIP_TRY(g, hipMemcpy(b.d_group_keys, keys.data(), sizeof(uint32_t) * keys.size(), hipMemcpyHostToDevice));
+	HIP_TRY(g, hipMemcpy(b.d_group_off, off.data(), sizeof(uint32_t) * off.size(), hipMemcpyHostToDevice));
 	if (n_rows)
-		HIP_TRY(g, hipMemcpy(b_rows, order.data(), sizeof(uint32_t) * n_rows, hipMemcpyHostToDevice));
+		HIP_TRY(g, hipMemcpy(b.d_group_rows, order.data(), sizeof(uint32_t) * n_rows, hipMemcpyHostToDevice));
 	HIP_TRY(g, hipStreamSynchronize(g->stream));
-	std::swap(g->d_row_groups.p, b_lab.p);  // (the old buffers go with the locals)
-	std::swap(g->d_group_keys.p, b_keys.p);
-	std::swap(g->d_group_off.p, b_off.p);
-	std::swap(g->d_group_rows.p, b_rows.p);
-	g->n_groups = (uint32_t)keys.size();
-	g->groups_on = true;
+	b.n_groups = (uint32_t)keys.size();
+	b.groups_on = true;
+	static_cast<GraphRowGroups&>(*g) = std::move(b);  // (the old groups go with the local)
 	return EXPANN_OK;
 }
 
@@ -658,17 +693,7 @@ int graph_enqueue_grouped(expann_graph* g, GraphSearchParams p, const uint32_t* 
 	if (int rc = graph_search_plan(g, gv, p, ctr, &pl))
 		return rc;
 	GraphGroupScanParams s{};
-	s.f.vectors = (const float*)g->d_vectors;
-	s.f.dim = (uint32_t)g->dim;
-	s.f.queries = p.queries;
-	s.f.m = p.m;
-	s.f.k = p.k;
-	s.f.kk = std::min<uint32_t>(p.k, kGraphFlatMaxKeys);
-	s.f.out_ids = p.out_ids;
-	s.f.out_dists = p.out_dists;
-	s.f.out_distcomps = p.out_distcomps;
-	s.f.next_query = ctr + 4;
-	s.f.distcomps_total = p.distcomps_total;
+	s.f = graph_flat_params(p, std::min<uint32_t>(p.k, kGraphFlatMaxKeys), ctr + 4);
 	s.query_groups = d_query_groups;
 	s.group_keys = g->d_group_keys;
 	s.group_off = g->d_group_off;
@@ -715,8 +740,112 @@ int graph_print_stamps(expann_graph* g, int mode, size_t ef_search, float ms, ui
 	             100 * tot[5] / all);
 	return EXPANN_OK;
 }
+
+// ---- the two forms of a search ------------------------------------------------------------------
+// Device buffers: what every such search does before its launches.  The stream (NULL = the handle's own); the
+// handle's first search makes the counter slots; one set of visited arrays, so searches overlap in stream order only
+// -- a search on another stream than the outstanding ones waits for them, one that finds every slot taken drains them,
+// and nothing else is waited for; the byte copy of the rows when the walk will read one (`bytes`; before the
+// parameters: they name it); then the parameters with the caller's buffers and the distcomps total, and the slot.
+struct GraphDevSearch {
+	hipStream_t st = nullptr;
+	uint32_t* ctr = nullptr;
+	GraphSearchParams p{};
+};
+int graph_dev_begin(expann_graph* g, void* stream, int mode, bool bytes, const float* d_queries, size_t m, size_t k,
+                    size_t ef_search, uint64_t* d_ids, float* d_dists, uint32_t* d_distcomps, GraphDevSearch* s) {
+	hipStream_t st = stream ? (hipStream_t)stream : g->stream;
+	if (int rc = graph_dev_init(g))
+		return rc;
+	if (g->dev_outstanding && st != g->dev_stream)
+		HIP_TRY(g, graph_wait_outstanding(g));
+	if (g->dev_outstanding >= kGraphMaxOutstanding)
+		if (int rc = graph_drain(g))
+			return rc;
+	if (bytes)
+		if (int rc = graph_ensure_bytes(g, mode))
+			return rc;
+	s->st = st;
+	s->ctr = g->d_dev_ctr + (size_t)g->dev_outstanding * kGraphCtrWords;
+	s->p = graph_base_params(g, mode, k, ef_search);
+	s->p.queries = d_queries;
+	s->p.m = (uint32_t)m;
+	s->p.out_ids = d_ids;
+	s->p.out_dists = d_dists;
+	s->p.out_distcomps = d_distcomps;
+	s->p.distcomps_total = g->d_dc_total;
+	return EXPANN_OK;
+}
+// ... and after them: the search is outstanding on `st`, and the next sync reads its time from ev_dev (`timed`: [0]
+// and [1] hold it; `timed_redo`: [2] its redo launch)
+void graph_dev_commit(expann_graph* g, hipStream_t st, bool timed, bool timed_redo) {
+	g->dev_stream = st;
+	++g->dev_outstanding;
+	++g->stat_deferred;
+	g->dev_timed = timed;
+	g->dev_timed_redo = timed_redo;
+}
+
+// Host buffers: the staging of one call on the handle's own stream -- device copies of the queries (and of their
+// groups) and of the result arrays, and the host-buffer calls' counter slot: the one behind those of the device-buffer
+// searches, which stay as they are for the next sync.  The caller enqueues and waits between begin() and finish().
+struct GraphHostStage {
+	DevBuf b_q, b_qg, b_ids, b_d, b_dc;
+	uint32_t *ctr = nullptr, *h_ctr = nullptr;
+	size_t m = 0, k = 0;
+	// allocates, uploads (query_groups == nullptr: there are none) and points *p at the buffers
+	int begin(expann_graph* g, const float* queries, const uint32_t* query_groups, size_t m_, size_t k_, GraphSearchParams* p) {
+		m = m_;
+		k = k_;
+		hipStream_t st = g->stream;
+		const size_t qb = m * (size_t)g->dim * sizeof(float);
+		HIP_TRY(g, b_q.alloc(qb));
+		if (query_groups)
+			HIP_TRY(g, b_qg.alloc(sizeof(uint32_t) * m));
+		HIP_TRY(g, b_ids.alloc(sizeof(uint64_t) * m * k));
+		HIP_TRY(g, b_d.alloc(sizeof(float) * m * k));
+		HIP_TRY(g, b_dc.alloc(sizeof(uint32_t) * m));
+		HIP_TRY(g, hipMemcpyAsync(b_q.p, queries, qb, hipMemcpyHostToDevice, st));
+		if (query_groups)
+			HIP_TRY(g, hipMemcpyAsync(b_qg.p, query_groups, sizeof(uint32_t) * m, hipMemcpyHostToDevice, st));
+		p->queries = b_q.as<float>();
+		p->m = (uint32_t)m;
+		p->out_ids = b_ids.as<uint64_t>();
+		p->out_dists = b_d.as<float>();
+		p->out_distcomps = b_dc.as<uint32_t>();
+		ctr = g->d_dev_ctr + (size_t)kGraphMaxOutstanding * kGraphCtrWords;
+		h_ctr = g->h_dev_ctr + (size_t)kGraphMaxOutstanding * kGraphCtrWords;
+		return EXPANN_OK;
+	}
+	// the slot read back behind what was enqueued, and the wait for all of it
+	int read_slot(expann_graph* g) {
+		hipStream_t st = g->stream;
+		HIP_TRY(g, hipMemcpyAsync(h_ctr, ctr, sizeof(uint32_t) * kGraphCtrWords, hipMemcpyDeviceToHost, st));
+		HIP_TRY(g, hipStreamSynchronize(st));
+		return EXPANN_OK;
+	}
+	// the results into the caller's arrays (distcomps may be nullptr)
+	int copy_out(expann_graph* g, uint64_t* ids, float* dists, uint32_t* distcomps) {
+		HIP_TRY(g, hipMemcpy(ids, b_ids.p, sizeof(uint64_t) * m * k, hipMemcpyDeviceToHost));
+		HIP_TRY(g, hipMemcpy(dists, b_d.p, sizeof(float) * m * k, hipMemcpyDeviceToHost));
+		if (distcomps)
+			HIP_TRY(g, hipMemcpy(distcomps, b_dc.p, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
+		return EXPANN_OK;
+	}
+	// ... and what the slot (read_slot) says of the walks: an overflow that no redo launch served is the call's error
+	int finish(expann_graph* g, uint64_t* ids, float* dists, uint32_t* distcomps) {
+		if (int rc = copy_out(g, ids, dists, distcomps))
+			return rc;
+		if (h_ctr[0])
+			return g->fail(EXPANN_ERR_OVERFLOW, "graph search: candidates queue overflowed its LDS capacity");
+		return EXPANN_OK;
+	}
+};
 }  // namespace
 
+struct GraphDeleter {
+	void operator()(expann_graph* g) const { expann_graph_destroy(g); }
+};
 // expann_graph_create (elem_bytes = 4, `fn` its name) and expann_graph_create_f16 (2): one body, so both make the
 // same checks in the same order, all before the device is touched
 static int graph_create(const char* fn_name, size_t elem_bytes, int dim, int device, const void* vectors, size_t n,
@@ -760,7 +889,15 @@ static int graph_create(const char* fn_name, size_t elem_bytes, int dim, int dev
 		g_create_error = "device index out of range";
 		return EXPANN_ERR_INVALID_ARG;
 	}
-	expann_graph* g = new expann_graph();
+	// the validity of every neighbour id is the caller's contract; check it once here so a
+	// corrupt index cannot make the kernel read out of bounds
+	for (uint64_t e = 0; e < n_edges; ++e)
+		if (neighbours[e] >= n) {
+			g_create_error = "neighbour id out of range";
+			return EXPANN_ERR_INVALID_ARG;
+		}
+	// (owned until the last step: every early return destroys the handle and what it holds by then)
+	std::unique_ptr<expann_graph, GraphDeleter> g(new expann_graph());
 	g->dim = dim;
 	g->device = device;
 	g->n = n;
@@ -772,34 +909,25 @@ static int graph_create(const char* fn_name, size_t elem_bytes, int dim, int dev
 		off32[i] = (uint32_t)layer_offsets[i];
 	for (size_t v = 0; v < n; ++v)
 		g->max_degree0 = std::max(g->max_degree0, off32[v + 1] - off32[v]);
-	// the validity of every neighbour id is the caller's contract; check it once here so a
-	// corrupt index cannot make the kernel read out of bounds
-	for (uint64_t e = 0; e < n_edges; ++e)
-		if (neighbours[e] >= n) {
-			g_create_error = "neighbour id out of range";
-			delete g;
-			return EXPANN_ERR_INVALID_ARG;
-		}
-	auto bail = [&](const char* what) {
+	auto hip_failed = [&](const char* what) {  // the HIP call that failed, by name
 		g_create_error = fn + ": " + what;
-		expann_graph_destroy(g);
 		return EXPANN_ERR_HIP;
 	};
 	if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&g->stream) != hipSuccess)
-		return bail("hipSetDevice/hipStreamCreate");
+		return hip_failed("hipSetDevice/hipStreamCreate");
 	if (hipEventCreate(&g->ev0) != hipSuccess || hipEventCreate(&g->ev1) != hipSuccess)
-		return bail("hipEventCreate");
+		return hip_failed("hipEventCreate");
 	const size_t vbytes = n * (size_t)dim * elem_bytes;
 	if (hipMalloc(&g->d_vectors, vbytes) != hipSuccess ||
 	    hipMalloc(&g->d_layer_off, off32.size() * sizeof(uint32_t)) != hipSuccess ||
 	    hipMalloc(&g->d_neighbours, std::max<uint64_t>(n_edges, 1) * sizeof(uint32_t)) != hipSuccess)
-		return bail("hipMalloc");
+		return hip_failed("hipMalloc");
 	if (hipMemcpy(g->d_vectors, vectors, vbytes, hipMemcpyHostToDevice) != hipSuccess ||
 	    hipMemcpy(g->d_layer_off, off32.data(), off32.size() * sizeof(uint32_t),
 	              hipMemcpyHostToDevice) != hipSuccess ||
 	    (n_edges && hipMemcpy(g->d_neighbours, neighbours, n_edges * sizeof(uint32_t),
 	                          hipMemcpyHostToDevice) != hipSuccess))
-		return bail("hipMemcpy");
+		return hip_failed("hipMemcpy");
 	{
 		// layer 0 once more at a fixed stride: a hop then reads its list at cur * stride without first
 		// fetching the row's offsets (one dependent HBM round trip less per hop)
@@ -808,9 +936,9 @@ static int graph_create(const char* fn_name, size_t elem_bytes, int dim, int dev
 		for (size_t v = 0; v < n; ++v)
 			std::copy(neighbours + off32[v], neighbours + off32[v + 1], adj.begin() + v * g->stride0);
 		if (hipMalloc(&g->d_adj0, adj.size() * sizeof(uint32_t)) != hipSuccess)
-			return bail("hipMalloc(adj0)");
+			return hip_failed("hipMalloc(adj0)");
 		if (hipMemcpy(g->d_adj0, adj.data(), adj.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
-			return bail("hipMemcpy(adj0)");
+			return hip_failed("hipMemcpy(adj0)");
 	}
 	// one visited array per workgroup of the (persistent) search grid; bounded to ~1/8 of a 288 GB
 	// HBM.  The walk is a chain of dependent memory round trips: what hides them is waves per CU
@@ -827,11 +955,11 @@ static int graph_create(const char* fn_name, size_t elem_bytes, int dim, int dev
 	g->slots = (uint32_t)slots;
 	if (hipMalloc(&g->d_visited, slots * per_slot) != hipSuccess ||
 	    hipMalloc(&g->d_epochs, slots * sizeof(uint32_t)) != hipSuccess)
-		return bail("hipMalloc(visited)");
+		return hip_failed("hipMalloc(visited)");
 	if (hipMemset(g->d_visited, 0, slots * per_slot) != hipSuccess ||
 	    hipMemset(g->d_epochs, 0, slots * sizeof(uint32_t)) != hipSuccess)
-		return bail("hipMemset");
-	*out = g;
+		return hip_failed("hipMemset");
+	*out = g.release();
 	return EXPANN_OK;
 }
 
@@ -857,20 +985,6 @@ void expann_graph_destroy(expann_graph* g) {
 	hipSetDevice(g->device);
 	if (g->stream) hipStreamSynchronize(g->stream);
 	if (g->dev_outstanding) hipStreamSynchronize(g->dev_stream);
-	if (g->d_vectors) hipFree(g->d_vectors);
-	if (g->d_compressed) hipFree(g->d_compressed);
-	if (g->d_ranged) hipFree(g->d_ranged);
-	if (g->d_layer_off) hipFree(g->d_layer_off);
-	if (g->d_neighbours) hipFree(g->d_neighbours);
-	if (g->d_adj0) hipFree(g->d_adj0);
-	if (g->d_visited) hipFree(g->d_visited);
-	if (g->d_epochs) hipFree(g->d_epochs);
-	for (hipEvent_t ev : g->ev_dev)
-		if (ev) hipEventDestroy(ev);
-	if (g->ev0) hipEventDestroy(g->ev0);
-	if (g->ev1) hipEventDestroy(g->ev1);
-	if (g->ev2) hipEventDestroy(g->ev2);
-	if (g->stream) hipStreamDestroy(g->stream);
 	delete g;
 }
 
@@ -903,8 +1017,6 @@ int expann_graph_ranged_params(expann_graph* g, float* scale_factor, float* offs
 
 int expann_graph_search_mode(expann_graph* g, const float* queries, size_t m, size_t k, size_t ef_search, int mode,
                              uint64_t* ids, float* dists, uint32_t* distcomps) {
-	if (!g)
-		return EXPANN_ERR_INVALID_ARG;
 	bool empty = false;
 	if (int rc = graph_search_args(g, queries, m, k, ef_search, mode, ids, dists, &empty))
 		return rc;
@@ -935,40 +1047,26 @@ int expann_graph_search_mode(expann_graph* g, const float* queries, size_t m, si
 		if (int rc = graph_ensure_bytes(g, mode))
 			return rc;
 	hipStream_t st = g->stream;
-	DevBuf b_q, b_ids, b_d, b_dc, b_stamps;
-	const size_t qb = m * (size_t)g->dim * sizeof(float), stamp_bytes = sizeof(unsigned long long) * 8 * g->slots;
-	HIP_TRY(g, b_q.alloc(qb));
-	HIP_TRY(g, b_ids.alloc(sizeof(uint64_t) * m * k));
-	HIP_TRY(g, b_d.alloc(sizeof(float) * m * k));
-	HIP_TRY(g, b_dc.alloc(sizeof(uint32_t) * m));
+	GraphSearchParams p = graph_base_params(g, mode, k, ef_search);
+	GraphHostStage stage;
+	if (int rc = stage.begin(g, queries, nullptr, m, k, &p))
+		return rc;
+	DevBuf b_stamps;
+	const size_t stamp_bytes = sizeof(unsigned long long) * 8 * g->slots;
 	if (stamps)
 		HIP_TRY(g, b_stamps.alloc(stamp_bytes));
-	HIP_TRY(g, hipMemcpyAsync(b_q.p, queries, qb, hipMemcpyHostToDevice, st));
-	GraphSearchParams p = graph_base_params(g, mode, k, ef_search);
-	p.queries = b_q.as<float>();
-	p.m = (uint32_t)m;
-	p.out_ids = b_ids.as<uint64_t>();
-	p.out_dists = b_d.as<float>();
-	p.out_distcomps = b_dc.as<uint32_t>();
 	p.stamps = b_stamps.as<unsigned long long>();
-	// the slot behind those of the device-buffer searches: theirs stay as they are for the next sync
-	uint32_t* ctr = g->d_dev_ctr + (size_t)kGraphMaxOutstanding * kGraphCtrWords;
-	uint32_t* h_ctr = g->h_dev_ctr + (size_t)kGraphMaxOutstanding * kGraphCtrWords;
 	if (serve == kServeScan) {  // a sparse filter: the exact scan of the allowed rows
-		if (int rc = graph_enqueue_flat(g, p, ctr, st, g->ev0, g->ev1))
+		if (int rc = graph_enqueue_flat(g, p, stage.ctr, st, g->ev0, g->ev1))
 			return rc;
 		HIP_TRY(g, hipStreamSynchronize(st));
 		float ms = 0;
 		HIP_TRY(g, hipEventElapsedTime(&ms, g->ev0, g->ev1));
 		g->last_ms = ms;
-		HIP_TRY(g, hipMemcpy(ids, b_ids.p, sizeof(uint64_t) * m * k, hipMemcpyDeviceToHost));
-		HIP_TRY(g, hipMemcpy(dists, b_d.p, sizeof(float) * m * k, hipMemcpyDeviceToHost));
-		if (distcomps)
-			HIP_TRY(g, hipMemcpy(distcomps, b_dc.p, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
-		return EXPANN_OK;
+		return stage.copy_out(g, ids, dists, distcomps);
 	}
 	GraphSearchPlan pl;
-	if (int rc = graph_search_plan(g, gv, p, ctr, &pl))
+	if (int rc = graph_search_plan(g, gv, p, stage.ctr, &pl))
 		return rc;
 	double ms_total = 0;
 	// a launch, the wait for it and the slot read back
@@ -979,8 +1077,8 @@ int expann_graph_search_mode(expann_graph* g, const float* queries, size_t m, si
 			HIP_TRY(g, hipEventRecord(g->ev0, st));
 		if (int rc = redo ? graph_enqueue_redo(g, pl, st, g->ev1) : graph_enqueue_first(g, pl, st, g->ev0, g->ev1))
 			return rc;
-		HIP_TRY(g, hipMemcpyAsync(h_ctr, ctr, sizeof(uint32_t) * kGraphCtrWords, hipMemcpyDeviceToHost, st));
-		HIP_TRY(g, hipStreamSynchronize(st));
+		if (int rc = stage.read_slot(g))
+			return rc;
 		float ms = 0;
 		HIP_TRY(g, hipEventElapsedTime(&ms, g->ev0, g->ev1));
 		ms_total += ms;
@@ -990,23 +1088,15 @@ int expann_graph_search_mode(expann_graph* g, const float* queries, size_t m, si
 	if (int rc = run(false, m))
 		return rc;
 	// this call has waited anyway, so the redo launch goes out only when the first one listed queries for it
-	if (h_ctr[2])
-		if (int rc = run(true, h_ctr[2]))
+	if (stage.h_ctr[2])
+		if (int rc = run(true, stage.h_ctr[2]))
 			return rc;
 	g->last_ms = ms_total;
-	HIP_TRY(g, hipMemcpy(ids, b_ids.p, sizeof(uint64_t) * m * k, hipMemcpyDeviceToHost));
-	HIP_TRY(g, hipMemcpy(dists, b_d.p, sizeof(float) * m * k, hipMemcpyDeviceToHost));
-	if (distcomps)
-		HIP_TRY(g, hipMemcpy(distcomps, b_dc.p, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
-	if (h_ctr[0])
-		return g->fail(EXPANN_ERR_OVERFLOW, "graph search: candidates queue overflowed its LDS capacity");
-	return EXPANN_OK;
+	return stage.finish(g, ids, dists, distcomps);
 }
 
 int expann_graph_search_device(expann_graph* g, const float* d_queries, size_t m, size_t k, size_t ef_search, int mode,
                                uint64_t* d_ids, float* d_dists, uint32_t* d_distcomps, void* stream) {
-	if (!g)
-		return EXPANN_ERR_INVALID_ARG;
 	bool empty = false;
 	if (int rc = graph_search_args(g, d_queries, m, k, ef_search, mode, d_ids, d_dists, &empty))
 		return rc;
@@ -1017,53 +1107,28 @@ int expann_graph_search_device(expann_graph* g, const float* d_queries, size_t m
 	const GraphVariant* gv = graph_variant(g->dim, mode, g->filter_on ? kFilterBitmap : kFilterNone, g->rows_f16);
 	if (!gv)
 		return g->fail(EXPANN_ERR_UNSUPPORTED, "no graph kernel for this dim");
-	hipStream_t st = stream ? (hipStream_t)stream : g->stream;
-	if (int rc = graph_dev_init(g))
+	GraphDevSearch s;
+	if (int rc = graph_dev_begin(g, stream, mode, serve == kServeWalk, d_queries, m, k, ef_search, d_ids, d_dists, d_distcomps, &s))
 		return rc;
-	// one set of visited arrays: searches overlap in stream order only
-	if (g->dev_outstanding && st != g->dev_stream)
-		HIP_TRY(g, graph_wait_outstanding(g));
-	if (g->dev_outstanding >= kGraphMaxOutstanding)
-		if (int rc = graph_drain(g))
-			return rc;
-	if (serve == kServeWalk)
-		if (int rc = graph_ensure_bytes(g, mode))
-			return rc;
-	GraphSearchParams p = graph_base_params(g, mode, k, ef_search);
-	p.queries = d_queries;
-	p.m = (uint32_t)m;
-	p.out_ids = d_ids;
-	p.out_dists = d_dists;
-	p.out_distcomps = d_distcomps;
-	p.distcomps_total = g->d_dc_total;
 	if (serve != kServeWalk) {  // a sparse or empty filter: the scan, or padding alone, in the same stream order
-		uint32_t* ctr = g->d_dev_ctr + (size_t)g->dev_outstanding * kGraphCtrWords;
-		if (int rc = serve == kServeScan ? graph_enqueue_flat(g, p, ctr, st, g->ev_dev[0], g->ev_dev[1])
-		                                 : graph_enqueue_pad(g, p, ctr, st))
+		if (int rc = serve == kServeScan ? graph_enqueue_flat(g, s.p, s.ctr, s.st, g->ev_dev[0], g->ev_dev[1])
+		                                 : graph_enqueue_pad(g, s.p, s.ctr, s.st))
 			return rc;
-		g->dev_stream = st;
-		++g->dev_outstanding;
-		++g->stat_deferred;
-		g->dev_timed = serve == kServeScan;
-		g->dev_timed_redo = false;
+		graph_dev_commit(g, s.st, serve == kServeScan, false);
 		if (serve == kServePad)
 			g->last_ms = 0;
 		return EXPANN_OK;
 	}
 	GraphSearchPlan pl;
-	if (int rc = graph_search_plan(g, gv, p, g->d_dev_ctr + (size_t)g->dev_outstanding * kGraphCtrWords, &pl))
+	if (int rc = graph_search_plan(g, gv, s.p, s.ctr, &pl))
 		return rc;
 	// both launches go out without a wait: the redo launch finds its queries, or none, in device memory
-	if (int rc = graph_enqueue_first(g, pl, st, g->ev_dev[0], g->ev_dev[1]))
+	if (int rc = graph_enqueue_first(g, pl, s.st, g->ev_dev[0], g->ev_dev[1]))
 		return rc;
 	if (pl.has_redo)
-		if (int rc = graph_enqueue_redo(g, pl, st, g->ev_dev[2]))
+		if (int rc = graph_enqueue_redo(g, pl, s.st, g->ev_dev[2]))
 			return rc;
-	g->dev_stream = st;
-	++g->dev_outstanding;
-	++g->stat_deferred;
-	g->dev_timed = true;
-	g->dev_timed_redo = pl.has_redo;
+	graph_dev_commit(g, s.st, true, pl.has_redo);
 	return EXPANN_OK;
 }
 
@@ -1097,21 +1162,9 @@ int expann_graph_set_option(expann_graph* g, const char* name, long value) {
 		return EXPANN_ERR_INVALID_ARG;
 	if (!name)
 		return g->fail(EXPANN_ERR_INVALID_ARG, "NULL option name");
-	const std::string o(name);
-	if (o == "filter_flat_rows") {  // rows, not a capacity: any count, 0 = auto
-		if (value < 0)
-			return g->fail(EXPANN_ERR_INVALID_ARG, "filter_flat_rows must be >= 0 (0 = auto)");
-		g->opt_flat_rows = value;
-		return EXPANN_OK;
-	}
-	const bool cand = o == "cand_capacity";
-	if (!cand && o != "redo_capacity")
-		return g->fail(EXPANN_ERR_INVALID_ARG, "unknown option: " + o);
-	// 0 = auto, else a power of two >= 8 (the redo launch's at most 8192, the LDS limit of the heap)
-	if (value != 0 && (value < 8 || (value & (value - 1)) != 0 || value > (cand ? (1L << 20) : 8192L)))
-		return g->fail(EXPANN_ERR_INVALID_ARG, o + " must be 0 or a power of two >= 8" + (cand ? "" : " and <= 8192"));
-	(cand ? g->opt_cand_cap : g->opt_redo_cap) = value;
-	return EXPANN_OK;
+	std::string msg;
+	const int rc = set_graph_option(*g, name, value, &msg);  // (graph_options.hpp: the table and its rules)
+	return rc ? g->fail(rc, msg) : EXPANN_OK;
 }
 
 int expann_graph_set_row_filter(expann_graph* g, const uint32_t* allow_bits, size_t n_words) {
@@ -1148,20 +1201,13 @@ int expann_graph_clear_row_groups(expann_graph* g) {
 		HIP_TRY(g, hipSetDevice(g->device));
 		HIP_TRY(g, graph_wait_outstanding(g));
 	}
-	g->groups_on = false;
-	g->n_groups = 0;
-	g->d_row_groups.reset();
-	g->d_group_keys.reset();
-	g->d_group_off.reset();
-	g->d_group_rows.reset();
+	g->forget<GraphRowGroups>();
 	return EXPANN_OK;
 }
 
 int expann_graph_search_grouped_device(expann_graph* g, const float* d_queries, const uint32_t* d_query_groups, size_t m,
                                        size_t k, size_t ef_search, int mode, uint64_t* d_ids, float* d_dists,
                                        uint32_t* d_distcomps, void* stream) {
-	if (!g)
-		return EXPANN_ERR_INVALID_ARG;
 	bool empty = false;
 	if (int rc = graph_search_args(g, d_queries, m, k, ef_search, mode, d_ids, d_dists, &empty))
 		return rc;
@@ -1170,41 +1216,20 @@ int expann_graph_search_grouped_device(expann_graph* g, const float* d_queries, 
 	if (int rc = graph_grouped_args(g, d_query_groups))
 		return rc;
 	HIP_TRY(g, hipSetDevice(g->device));
-	hipStream_t st = stream ? (hipStream_t)stream : g->stream;
-	if (int rc = graph_dev_init(g))
+	GraphDevSearch s;
+	if (int rc = graph_dev_begin(g, stream, mode, true, d_queries, m, k, ef_search, d_ids, d_dists, d_distcomps, &s))
 		return rc;
-	// one set of visited arrays: searches overlap in stream order only
-	if (g->dev_outstanding && st != g->dev_stream)
-		HIP_TRY(g, graph_wait_outstanding(g));
-	if (g->dev_outstanding >= kGraphMaxOutstanding)
-		if (int rc = graph_drain(g))
-			return rc;
-	if (int rc = graph_ensure_bytes(g, mode))  // (before the parameters: they name the byte copy)
-		return rc;
-	GraphSearchParams p = graph_base_params(g, mode, k, ef_search);
-	p.queries = d_queries;
-	p.m = (uint32_t)m;
-	p.out_ids = d_ids;
-	p.out_dists = d_dists;
-	p.out_distcomps = d_distcomps;
-	p.distcomps_total = g->d_dc_total;
+	hipEvent_t ev[3] = {g->ev_dev[0], g->ev_dev[1], g->ev_dev[2]};
 	bool has_redo = false;
-	if (int rc = graph_enqueue_grouped(g, p, d_query_groups, mode, g->d_dev_ctr + (size_t)g->dev_outstanding * kGraphCtrWords,
-	                                   st, g->ev_dev, &has_redo))
+	if (int rc = graph_enqueue_grouped(g, s.p, d_query_groups, mode, s.ctr, s.st, ev, &has_redo))
 		return rc;
-	g->dev_stream = st;
-	++g->dev_outstanding;
-	++g->stat_deferred;
-	g->dev_timed = true;
-	g->dev_timed_redo = has_redo;
+	graph_dev_commit(g, s.st, true, has_redo);
 	return EXPANN_OK;
 }
 
 // host buffers: the same launches on the handle's own stream with the host-buffer calls' counter slot, waited for here
 int expann_graph_search_grouped(expann_graph* g, const float* queries, const uint32_t* query_groups, size_t m, size_t k,
                                 size_t ef_search, int mode, uint64_t* ids, float* dists, uint32_t* distcomps) {
-	if (!g)
-		return EXPANN_ERR_INVALID_ARG;
 	bool empty = false;
 	if (int rc = graph_search_args(g, queries, m, k, ef_search, mode, ids, dists, &empty))
 		return rc;
@@ -1220,44 +1245,24 @@ int expann_graph_search_grouped(expann_graph* g, const float* queries, const uin
 		HIP_TRY(g, hipEventCreate(&g->ev2));
 	if (int rc = graph_ensure_bytes(g, mode))  // (before the parameters: they name the byte copy)
 		return rc;
-	hipStream_t st = g->stream;
-	DevBuf b_q, b_qg, b_ids, b_d, b_dc;
-	const size_t qb = m * (size_t)g->dim * sizeof(float);
-	HIP_TRY(g, b_q.alloc(qb));
-	HIP_TRY(g, b_qg.alloc(sizeof(uint32_t) * m));
-	HIP_TRY(g, b_ids.alloc(sizeof(uint64_t) * m * k));
-	HIP_TRY(g, b_d.alloc(sizeof(float) * m * k));
-	HIP_TRY(g, b_dc.alloc(sizeof(uint32_t) * m));
-	HIP_TRY(g, hipMemcpyAsync(b_q.p, queries, qb, hipMemcpyHostToDevice, st));
-	HIP_TRY(g, hipMemcpyAsync(b_qg.p, query_groups, sizeof(uint32_t) * m, hipMemcpyHostToDevice, st));
 	GraphSearchParams p = graph_base_params(g, mode, k, ef_search);
-	p.queries = b_q.as<float>();
-	p.m = (uint32_t)m;
-	p.out_ids = b_ids.as<uint64_t>();
-	p.out_dists = b_d.as<float>();
-	p.out_distcomps = b_dc.as<uint32_t>();
-	uint32_t* ctr = g->d_dev_ctr + (size_t)kGraphMaxOutstanding * kGraphCtrWords;
-	uint32_t* h_ctr = g->h_dev_ctr + (size_t)kGraphMaxOutstanding * kGraphCtrWords;
+	GraphHostStage stage;
+	if (int rc = stage.begin(g, queries, query_groups, m, k, &p))
+		return rc;
 	hipEvent_t ev[3] = {g->ev0, g->ev1, g->ev2};
 	bool has_redo = false;
-	if (int rc = graph_enqueue_grouped(g, p, b_qg.as<uint32_t>(), mode, ctr, st, ev, &has_redo))
+	if (int rc = graph_enqueue_grouped(g, p, stage.b_qg.as<uint32_t>(), mode, stage.ctr, g->stream, ev, &has_redo))
 		return rc;
-	HIP_TRY(g, hipMemcpyAsync(h_ctr, ctr, sizeof(uint32_t) * kGraphCtrWords, hipMemcpyDeviceToHost, st));
-	HIP_TRY(g, hipStreamSynchronize(st));
+	if (int rc = stage.read_slot(g))
+		return rc;
 	float ms = 0, ms_redo = 0;
 	HIP_TRY(g, hipEventElapsedTime(&ms, g->ev0, g->ev1));
 	if (has_redo)
 		HIP_TRY(g, hipEventElapsedTime(&ms_redo, g->ev1, g->ev2));
 	g->last_ms = (double)ms + (double)ms_redo;
 	for (int j = 0; j < 3; ++j)
-		g->stat_group[j] += h_ctr[5 + j];
-	HIP_TRY(g, hipMemcpy(ids, b_ids.p, sizeof(uint64_t) * m * k, hipMemcpyDeviceToHost));
-	HIP_TRY(g, hipMemcpy(dists, b_d.p, sizeof(float) * m * k, hipMemcpyDeviceToHost));
-	if (distcomps)
-		HIP_TRY(g, hipMemcpy(distcomps, b_dc.p, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
-	if (h_ctr[0])
-		return g->fail(EXPANN_ERR_OVERFLOW, "graph search: candidates queue overflowed its LDS capacity");
-	return EXPANN_OK;
+		g->stat_group[j] += stage.h_ctr[5 + j];
+	return stage.finish(g, ids, dists, distcomps);
 }
 
 int expann_graph_get_stat(expann_graph* g, const char* name, uint64_t* out) {
@@ -1265,38 +1270,33 @@ int expann_graph_get_stat(expann_graph* g, const char* name, uint64_t* out) {
 		return EXPANN_ERR_INVALID_ARG;
 	if (!name || !out)
 		return g->fail(EXPANN_ERR_INVALID_ARG, "NULL pointer");
-	const std::string o(name);
-	if (o == "redo_queries")
-		*out = g->stat_redo_queries;
-	else if (o == "redo_overflows")
-		*out = g->stat_redo_overflows;
-	else if (o == "deferred_searches")
-		*out = g->stat_deferred;
-	else if (o == "distcomps")
-		*out = g->stat_distcomps;
-	else if (o == "redo_kernel_ns")
-		*out = (uint64_t)(g->stat_redo_ms * 1e6);
-	else if (o == "filter_active")
-		*out = g->filter_on ? 1 : 0;
-	else if (o == "filter_rows")
-		*out = g->filter_on ? g->n_allowed : g->n;
-	else if (o == "flat_searches")
-		*out = g->stat_flat;
-	else if (o == "groups_active")
-		*out = g->groups_on ? 1 : 0;
-	else if (o == "group_count")  // distinct labels other than 0xFFFFFFFF
-		*out = g->groups_on ? g->n_groups : 0;
-	else if (o == "group_walk_queries")
-		*out = g->stat_group[0];
-	else if (o == "group_scan_queries")
-		*out = g->stat_group[1];
-	else if (o == "group_pad_queries")
-		*out = g->stat_group[2];
-	else if (o == "vector_bytes")  // the device bytes of the rows themselves
-		*out = (uint64_t)g->n * (uint64_t)g->dim * (g->rows_f16 ? 2u : 4u);
-	else
-		return g->fail(EXPANN_ERR_INVALID_ARG, "unknown stat: " + o);
-	return EXPANN_OK;
+	using G = const expann_graph*;
+	static const struct {
+		const char* name;
+		uint64_t (*read)(G);
+	} kGraphStatTable[] = {
+	    {"redo_queries", [](G g) { return g->stat_redo_queries; }},
+	    {"redo_overflows", [](G g) { return g->stat_redo_overflows; }},
+	    {"deferred_searches", [](G g) { return g->stat_deferred; }},
+	    {"distcomps", [](G g) { return g->stat_distcomps; }},
+	    {"redo_kernel_ns", [](G g) { return (uint64_t)(g->stat_redo_ms * 1e6); }},
+	    {"filter_active", [](G g) -> uint64_t { return g->filter_on ? 1 : 0; }},
+	    {"filter_rows", [](G g) -> uint64_t { return g->filter_on ? g->n_allowed : g->n; }},
+	    {"flat_searches", [](G g) { return g->stat_flat; }},
+	    {"groups_active", [](G g) -> uint64_t { return g->groups_on ? 1 : 0; }},
+	    {"group_count", [](G g) -> uint64_t { return g->groups_on ? g->n_groups : 0; }},  // distinct labels other than 0xFFFFFFFF
+	    {"group_walk_queries", [](G g) { return g->stat_group[0]; }},
+	    {"group_scan_queries", [](G g) { return g->stat_group[1]; }},
+	    {"group_pad_queries", [](G g) { return g->stat_group[2]; }},
+	    // the device bytes of the rows themselves
+	    {"vector_bytes", [](G g) { return (uint64_t)g->n * (uint64_t)g->dim * (g->rows_f16 ? 2u : 4u); }},
+	};
+	for (const auto& s : kGraphStatTable)
+		if (!std::strcmp(name, s.name)) {
+			*out = s.read(g);
+			return EXPANN_OK;
+		}
+	return g->fail(EXPANN_ERR_INVALID_ARG, std::string("unknown stat: ") + name);
 }
 
 // test hook: a queue trace through the device's wave-cooperative heap code (tests/test_heap_pin.py);

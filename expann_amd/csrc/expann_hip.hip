@@ -3746,12 +3746,9 @@ int set_row_groups(expann_index* h, const uint32_t* groups, size_t n, bool on_de
 		HIP_TRY(h, hipStreamSynchronize(h->async_stream));
 	HIP_TRY(h, hipStreamSynchronize(h->stream));
 	hipStream_t st = user_st ? user_st : h->stream;
-	std::vector<uint32_t> lab(n);
-	if (on_device) {
-		HIP_TRY(h, hipMemcpyAsync(lab.data(), groups, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
-		HIP_TRY(h, hipStreamSynchronize(st));
-	} else
-		std::memcpy(lab.data(), groups, sizeof(uint32_t) * n);
+	std::vector<uint32_t> lab;
+	if (int rc = fetch_group_labels(h, groups, n, on_device, st, lab))
+		return rc;
 	GroupDirectory dir = build_group_directory(lab.data(), n);
 	DevPtr<uint32_t> b_lab, b_rows;  // built aside: a failed call leaves the groups as they were
 	HIP_TRY(h, hipMalloc(&b_lab, sizeof(uint32_t) * n));

@@ -4,11 +4,21 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstring>
 #include <string>
 #include <utility>
 #include <vector>
 
 #include "../../include/expann_hip.h"
+
+// every handle type has fail(code, message) -> code
+#define HIP_TRY(h, expr)                                                                   \
+	do {                                                                                   \
+		hipError_t _e = (expr);                                                            \
+		if (_e != hipSuccess)                                                              \
+			return (h)->fail(EXPANN_ERR_HIP, std::string(#expr) + ": " +                   \
+			                                       hipGetErrorString(_e));                 \
+	} while (0)
 
 namespace expann {
 
@@ -137,6 +147,18 @@ inline GroupDirectory build_group_directory(const uint32_t* lab, size_t n) {
 	d.off.push_back((uint32_t)n_rows);
 	return d;
 }
+// The labels a set call was given, on the host: n of them in host (on_device = false) or device memory, the latter
+// read in the order of `st` and waited for.  EXPANN_OK, or the HIP error on the handle `h`.
+template <typename Handle>
+int fetch_group_labels(Handle* h, const uint32_t* groups, size_t n, bool on_device, hipStream_t st, std::vector<uint32_t>& lab) {
+	lab.resize(n);
+	if (on_device) {
+		HIP_TRY(h, hipMemcpyAsync(lab.data(), groups, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
+		HIP_TRY(h, hipStreamSynchronize(st));
+	} else
+		std::memcpy(lab.data(), groups, sizeof(uint32_t) * n);
+	return EXPANN_OK;
+}
 
 // what expann_*_last_error(NULL) reports: the failure of the last create call of this thread
 extern thread_local std::string g_create_error;
@@ -144,12 +166,3 @@ extern thread_local std::string g_create_error;
 int num_cus(int device);
 
 }  // namespace expann
-
-// every handle type has fail(code, message) -> code
-#define HIP_TRY(h, expr)                                                                   \
-	do {                                                                                   \
-		hipError_t _e = (expr);                                                            \
-		if (_e != hipSuccess)                                                              \
-			return (h)->fail(EXPANN_ERR_HIP, std::string(#expr) + ": " +                   \
-			                                       hipGetErrorString(_e));                 \
-	} while (0)

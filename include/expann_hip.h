@@ -344,8 +344,8 @@ int expann_graph_set_option(expann_graph* g, const char* name, long value);
  * searches since create; "distcomps" = distance evaluations of all device-buffer searches since create, as of the
  * last sync; "redo_kernel_ns" = device time of the last search's redo launch, as of the last sync;
  * "filter_active", "filter_rows", "flat_searches": see expann_graph_set_row_filter; "groups_active", "group_count",
- * "group_walk_queries", "group_scan_queries", "group_pad_queries": see expann_graph_set_row_groups.  An unknown name is
- * EXPANN_ERR_INVALID_ARG. */
+ * "group_walk_queries", "group_scan_queries", "group_pad_queries": see expann_graph_set_row_groups; "vector_bytes": see
+ * expann_graph_create_f16.  An unknown name is EXPANN_ERR_INVALID_ARG. */
 int expann_graph_get_stat(expann_graph* g, const char* name, uint64_t* out);
 
 /* GPU-assisted batched construction of the graph (csrc/graph_build.hpp; replaces the inner loop of

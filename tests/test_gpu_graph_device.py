@@ -409,3 +409,182 @@ def test_engine_surface(world, stream):
         hids, hdists = fresh.query_many(w["q"][:m], k)
         _assert_equal((hids, hdists), exp, m, ("query_many", k, mode))
     fresh.close()
+
+
+# ---- the handle's state over its lifetime -------------------------------------------------------------
+LIFE_N, LIFE_D, LIFE_M, LIFE_EF = 4096, 64, 8, 40
+
+
+class _Life:
+    """4 096 rows, d = 64, M = 16: one serial build, its index file, the restatement of the walk
+    (graph_filter_helpers, graph_groups_helpers), a filter that allows every second row, one that allows 7 rows,
+    and two labellings"""
+
+    def __init__(self, tmp, oracle, L):
+        import torch
+        import graph_filter_helpers as H
+        import graph_groups_helpers as G
+        from expann_amd import pack_row_filter
+        self.L, self.H, self.G = L, H, G
+        rng = np.random.RandomState(4096)
+        self.base = _sift_like(rng, LIFE_N, LIFE_D)
+        self.q = _sift_like(rng, LIFE_M, LIFE_D, frac=True)
+        self.idx = str(tmp / "life.index")
+        e = C.c_void_p()
+        assert L.expann_antitopo_create(LIFE_D, 0, 16, 80, 1, 0, 0, C.byref(e)) == 0
+        assert L.expann_antitopo_store(e, self.base.ctypes.data, LIFE_N) == 0
+        assert L.expann_antitopo_save(e, self.idx.encode()) == 0
+        L.expann_antitopo_destroy(e)
+        self.g = H.IndexGraph(self.idx)
+        self.Df = H.dist_f32_matrix(oracle, self.base, self.q)
+        self._Db = {m: H.bottom_matrix(oracle, self.base, self.q, m, self.Df) for m in (0, 1, 2)}
+        self.R = G.Restatement(self.g, self.Df, lambda mode: self._Db[mode])
+        self.dense = np.arange(LIFE_N) % 2 == 0
+        self.few = np.zeros(LIFE_N, bool)
+        self.few[rng.choice(LIFE_N, 7, replace=False)] = True
+        self.words = {name: pack_row_filter(a) for name, a in (("dense", self.dense), ("few", self.few))}
+        self.labels = {"main": G.make_labels(LIFE_N), "other": G.other_labels(LIFE_N)}
+        self.qg = G.query_groups(LIFE_M)
+        self.tq = torch.from_numpy(self.q).cuda()
+        self.tqg = torch.from_numpy(self.qg.view(np.int32)).cuda()
+        torch.cuda.synchronize()
+
+    def create(self):
+        return _graph_from_index(self.L, self.idx, self.base)[0]
+
+    def walk(self, mode, allow=None):
+        ids, dists, dc, _ = self.H.walk(self.g, self.Df, self._Db[mode], allow, K, LIFE_EF, mode)
+        return ids, dists, dc
+
+    def scan(self, allow):
+        """the exact scan of the allowed rows: the min(k, allowed) smallest (distance, id), distcomps = allowed"""
+        ids = np.full((LIFE_M, K), PAD, np.uint64)
+        dists = np.full((LIFE_M, K), np.inf, np.float32)
+        dc = np.zeros(LIFE_M, np.uint64)
+        for i in range(LIFE_M):
+            oi, od, dc[i] = self.G.scan_one(self.Df[i], allow.astype(np.uint32), 1, K)
+            ids[i, :len(oi)], dists[i, :len(od)] = oi, od
+        return ids, dists, dc
+
+    def set_filter(self, h, name):
+        w = self.words[name]
+        assert self.L.expann_graph_set_row_filter(h, w.ctypes.data, w.size) == 0, self.L.expann_graph_last_error(h)
+
+    def set_groups(self, h, name):
+        lab = self.labels[name]
+        assert self.L.expann_graph_set_row_groups(h, lab.ctypes.data, lab.size) == 0, self.L.expann_graph_last_error(h)
+
+    def device(self, h, mode, st):
+        rc, ids, dists, dc = _enqueue(self.L, h, self.tq, LIFE_M, K, LIFE_EF, mode, st)
+        assert rc == 0, self.L.expann_graph_last_error(h)
+        assert self.L.expann_graph_sync(h) == 0, self.L.expann_graph_last_error(h)
+        return _np(ids, dists, dc)
+
+    def host(self, h, mode):
+        from graph_ranged_helpers import search_mode
+        rc, ids, dists, dc = search_mode(self.L, h, self.q, K, LIFE_EF, mode)
+        assert rc == 0, self.L.expann_graph_last_error(h)
+        return ids, dists, dc
+
+    def grouped_device(self, h, mode, st):
+        import torch
+        ids = torch.full((LIFE_M, K), -2, dtype=torch.int64, device="cuda")
+        dists = torch.full((LIFE_M, K), -1.0, dtype=torch.float32, device="cuda")
+        dc = torch.full((LIFE_M,), -3, dtype=torch.int32, device="cuda")
+        st.wait_stream(torch.cuda.current_stream())
+        rc = self.L.expann_graph_search_grouped_device(h, self.tq.data_ptr(), self.tqg.data_ptr(), LIFE_M, K, LIFE_EF, mode,
+                                                       ids.data_ptr(), dists.data_ptr(), dc.data_ptr(), st.cuda_stream)
+        assert rc == 0, self.L.expann_graph_last_error(h)
+        assert self.L.expann_graph_sync(h) == 0, self.L.expann_graph_last_error(h)
+        return _np(ids, dists, dc)
+
+    def grouped_host(self, h, mode):
+        ids, dists, dc = np.zeros((LIFE_M, K), np.uint64), np.zeros((LIFE_M, K), np.float32), np.zeros(LIFE_M, np.uint32)
+        rc = self.L.expann_graph_search_grouped(h, self.q.ctypes.data, self.qg.ctypes.data, LIFE_M, K, LIFE_EF, mode,
+                                                ids.ctypes.data, dists.ctypes.data, dc.ctypes.data)
+        assert rc == 0, self.L.expann_graph_last_error(h)
+        return ids, dists, dc
+
+
+@pytest.fixture(scope="module")
+def life(tmp_path_factory, oracle):
+    from expann_amd import _lib
+    return _Life(tmp_path_factory.mktemp("graph_life"), oracle, _lib.load())
+
+
+def test_state_set_and_forgotten_leaves_the_handle_as_it_was(life, stream):
+    """filter, groups and the byte copies come and go between two plain searches, and the second equals the first
+    bit for bit; every search in between equals the restatement of what is in force at that moment"""
+    L, h = life.L, life.create()
+    try:
+        first_dev, first_host = life.device(h, 0, stream), life.host(h, 0)
+        for got in (first_dev, first_host):
+            _assert_equal(got, life.walk(0), LIFE_M, "first search")
+        # a dense filter is walked ("filter_flat_rows" = 1: only a 1-row filter would be scanned) ...
+        assert L.expann_graph_set_option(h, b"filter_flat_rows", 1) == 0
+        life.set_filter(h, "dense")
+        assert (_stat(L, h, "filter_active"), _stat(L, h, "filter_rows")) == (1, LIFE_N // 2)
+        for got in (life.device(h, 0, stream), life.host(h, 0)):
+            _assert_equal(got, life.walk(0, life.dense), LIFE_M, "dense filter")
+        # ... and one of fewer than k rows is scanned, on auto
+        assert L.expann_graph_set_option(h, b"filter_flat_rows", 0) == 0
+        life.set_filter(h, "few")
+        assert _stat(L, h, "filter_rows") == 7
+        flat = _stat(L, h, "flat_searches")
+        for got in (life.device(h, 0, stream), life.host(h, 0)):
+            _assert_equal(got, life.scan(life.few), LIFE_M, "filter of 7 rows")
+        assert _stat(L, h, "flat_searches") == flat + 2
+        assert L.expann_graph_clear_row_filter(h) == 0
+        for name in ("main", "other"):  # groups, forgotten, other groups, forgotten
+            life.set_groups(h, name)
+            assert _stat(L, h, "groups_active") == 1
+            assert _stat(L, h, "group_count") == len(set(life.labels[name].tolist()) - {0xFFFFFFFF})
+            exp = life.R.expected(life.labels[name], life.qg, K, LIFE_EF, 0, 0, labels_key=name)[:3]
+            _assert_equal(life.grouped_device(h, 0, stream), exp, LIFE_M, (name, "grouped, device buffers"))
+            _assert_equal(life.grouped_host(h, 0), exp, LIFE_M, (name, "grouped, host buffers"))
+            assert L.expann_graph_clear_row_groups(h) == 0
+            assert (_stat(L, h, "groups_active"), _stat(L, h, "group_count")) == (0, 0)
+        for mode in (2, 1):  # the byte copies are made here
+            _assert_equal(life.device(h, mode, stream), life.walk(mode), LIFE_M, ("mode", mode))
+        last_dev, last_host = life.device(h, 0, stream), life.host(h, 0)
+        for first, last in ((first_dev, last_dev), (first_host, last_host)):
+            assert np.array_equal(first[0], last[0])
+            assert np.array_equal(first[1].view(np.uint32), last[1].view(np.uint32))
+            assert np.array_equal(first[2], last[2])
+        assert [_stat(L, h, s) for s in ("filter_active", "groups_active", "group_count")] == [0, 0, 0]
+    finally:
+        L.expann_graph_destroy(h)
+
+
+def test_a_destroyed_handle_gives_its_device_memory_back(life, stream):
+    """20 times: create, filter, searches in every mode on both kinds of buffers, groups, grouped searches, a filter
+    again, destroy.  Free device memory after the 20th cycle is within one handle's footprint -- rows, layer-0 lists
+    at their stride, visited sets -- of what it was after the first: a group of the handle that stopped freeing
+    itself would lose twenty.  This catches a leaked large buffer, not a leaked event or stream."""
+    import torch
+    L = life.L
+    stride0 = max(4, (max(len(x) for x in life.g.adj[0]) + 3) // 4 * 4)
+    slots = torch.cuda.get_device_properties(0).multi_processor_count * 16
+    vis_bytes = (LIFE_N + 8191) // 8192 * 256 * 4  # one bitset
+    footprint = LIFE_N * LIFE_D * 4 + LIFE_N * stride0 * 4 + slots * vis_bytes
+    assert slots * vis_bytes >= 4 << 20 and footprint < 8 << 20
+    free = []
+    for cycle in range(20):
+        h = life.create()
+        assert L.expann_graph_set_option(h, b"filter_flat_rows", 1) == 0  # (the dense filter is walked: byte copies)
+        life.set_filter(h, "dense")
+        for mode in (0, 1, 2):
+            life.device(h, mode, stream)
+            life.host(h, mode)
+        assert L.expann_graph_clear_row_filter(h) == 0
+        assert L.expann_graph_set_option(h, b"filter_flat_rows", 0) == 0
+        life.set_groups(h, "main")
+        for mode in (0, 1, 2):
+            life.grouped_device(h, mode, stream)
+            life.grouped_host(h, mode)
+        life.set_filter(h, "few")
+        L.expann_graph_destroy(h)
+        torch.cuda.synchronize()
+        free.append(torch.cuda.mem_get_info()[0])
+    print(f"free device memory after cycle 1: {free[0]}, after cycle 20: {free[-1]}; one handle: {footprint}")
+    assert abs(free[0] - free[-1]) < footprint
