@@ -12,12 +12,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <iterator>
 #include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "bf_options.hpp"
+#include "bf_plan.hpp"
 #include "host_common.hpp"
 #include "scan_f32.hpp"
 #include "scan_gemm_bf16.hpp"
@@ -104,9 +106,8 @@ struct U8Shadow {
 
 // copies and terms derived from the rows, built lazily, dead when the rows change
 struct RowCopies : U8Shadow {
-	DevPtr<float> d_bnorm;           // ||b||^2 (1-eps) per row (GEMM-form scan), built lazily
-	DevPtr<float> d_bnorm_bf;        // same with the bf16x3 slack
-	DevPtr<float> d_bnmax;           // [2]: max of d_bnorm, max of d_bnorm_bf
+	DevPtr<float> d_bnorm_bf;        // ||b||^2 (1-eps) per row with the bf16x3 slack, built lazily
+	DevPtr<float> d_bnmax;           // [1]: max of d_bnorm_bf ([2]: of the fp16 copy's norms)
 	float f16_bnmax = 0.0f;          // max ||b||^2 (host copy lives in d_bnmax[2])
 	DevPtr<void> d_base_split;       // [n][2][dim] bf16 hi/lo planes (bf16x3 GEMM form), lazily
 	DevPtr<void> d_base_f16;         // [n][dim] fp16 rows scaled by f16_scale (fp16 GEMM form), lazily
@@ -320,40 +321,20 @@ const ScanVariant kScanF32Any[] = {SCAN_ANY_V(1), SCAN_ANY_V(2), SCAN_ANY_V(4)};
 	 scan_filter_f32_any_kernel<TQ, true, kRowsBitmap, _Float16>, scan_filter_f32_any_kernel<TQ, true, kRowsList, _Float16>}
 const ScanVariant kScanF16Any[] = {SCAN_ANY_H(1), SCAN_ANY_H(2), SCAN_ANY_H(4)};
 #undef SCAN_ANY_H
-inline bool any_dim_f32(int d) { return d >= 16 && d <= kMaxAnyDim && d % 16 == 0; }
+static_assert(kPlanMaxDim == kMaxAnyDim, "bf_plan.hpp: the largest run-time dim");
 
-// (rows_f16: binary16 rows -- no compiled-dim instances, the run-time-dim table of that element type at every dim)
-const ScanVariant* pick_scan_f32(int d, bool ip, size_t m, long forced_tq, bool rows_f16 = false) {
-	const ScanVariant* best = nullptr;
-	bool compiled = false;
-	for (const auto& v : kScanF32)
-		compiled = compiled || (v.d == d && !rows_f16);
-	if (!compiled && !any_dim_f32(d))
-		return nullptr;
+// the instance of query tile tq (bf_plan.hpp's direct_tile) -- binary16 rows: no compiled-dim instances, the
+// run-time-dim table of that element type at every dim
+const ScanVariant* find_scan_f32(int d, bool ip, int tq, bool rows_f16) {
 	static_assert(sizeof(kScanF16Any) == sizeof(kScanF32Any), "one F16 instance per run-time-dim F32 instance");
-	const ScanVariant* tab = compiled ? kScanF32 : (rows_f16 ? kScanF16Any : kScanF32Any);
-	const size_t n_tab = compiled ? sizeof(kScanF32) / sizeof(kScanF32[0]) : sizeof(kScanF32Any) / sizeof(kScanF32Any[0]);
-	for (size_t i = 0; i < n_tab; ++i) {
-		const ScanVariant& v = tab[i];
-		if ((compiled && v.d != d) || v.ip != ip)
-			continue;
-		if (forced_tq > 0) {
-			if (v.tq == forced_tq)
-				return &v;
-			continue;
-		}
-		if (!best) {
-			best = &v;
-			continue;
-		}
-		// smallest tile that covers m, else the largest tile
-		const bool v_covers = (size_t)v.tq >= m, b_covers = (size_t)best->tq >= m;
-		if (v_covers && (!b_covers || v.tq < best->tq))
-			best = &v;
-		else if (!v_covers && !b_covers && v.tq > best->tq)
-			best = &v;
-	}
-	return best;
+	const bool compiled = !rows_f16 && tiles_of(kScanF32Tiles, d);
+	for (const auto& v : kScanF32)
+		if (compiled && v.d == d && v.ip == ip && v.tq == tq)
+			return &v;
+	for (size_t i = 0; !compiled && i < sizeof(kScanF32Any) / sizeof(kScanF32Any[0]); ++i)
+		if (kScanF32Any[i].ip == ip && kScanF32Any[i].tq == tq)
+			return rows_f16 ? &kScanF16Any[i] : &kScanF32Any[i];
+	return nullptr;
 }
 
 using ScoreFn = void (*)(ScoreIdsParams);
@@ -398,41 +379,18 @@ const ScanI8Variant kScanI8[] = {SCAN_I8(64, 1),  SCAN_I8(64, 16), SCAN_I8(128, 
 const ScanI8Variant kScanI8Any[] = {SCAN_I8_ANY(1), SCAN_I8_ANY(4), SCAN_I8_ANY(8)};
 #undef SCAN_I8_ANY
 #undef SCAN_I8_ANY_M
-// 8-bit rows (not int16) of a dim without a compiled instance
-inline bool any_dim_i8(int d, int mode) {
-	if (mode < 0 || mode == kI16L2Ref || d < 64 || d > kMaxAnyDim || d % 64 != 0)
-		return false;
-	for (const auto& v : kScanI8)
-		if (v.d == d && v.mode == mode)
-			return false;
-	return true;
-}
-
-const ScanI8Variant* pick_scan_i8(int d, int mode, size_t m, long forced_tq) {
-	const ScanI8Variant* best = nullptr;
+static_assert(kU8L2 == kPlanU8L2 && kI8L2 == kPlanI8L2 && kI8L2Ref == kPlanI8L2Ref && kI8IP == kPlanI8IP &&
+                  kI16L2Ref == kPlanI16L2Ref,
+              "bf_plan.hpp: the 8-bit row modes");
+const ScanI8Variant* find_scan_i8(int d, int mode, int tq) {
 	const bool any = any_dim_i8(d, mode);
-	const ScanI8Variant* tab = any ? kScanI8Any : kScanI8;
-	const size_t n_tab = any ? sizeof(kScanI8Any) / sizeof(kScanI8Any[0]) : sizeof(kScanI8) / sizeof(kScanI8[0]);
-	for (size_t i = 0; i < n_tab; ++i) {
-		const ScanI8Variant& v = tab[i];
-		if ((!any && v.d != d) || v.mode != mode)
-			continue;
-		if (forced_tq > 0) {
-			if (v.tq == forced_tq)
-				return &v;
-			continue;
-		}
-		if (!best) {
-			best = &v;
-			continue;
-		}
-		const bool v_covers = (size_t)v.tq >= m, b_covers = (size_t)best->tq >= m;
-		if (v_covers && (!b_covers || v.tq < best->tq))
-			best = &v;
-		else if (!v_covers && !b_covers && v.tq > best->tq)
-			best = &v;
-	}
-	return best;
+	for (const auto& v : kScanI8)
+		if (!any && v.d == d && v.mode == mode && v.tq == tq)
+			return &v;
+	for (const auto& v : kScanI8Any)
+		if (any && v.mode == mode && v.tq == tq)
+			return &v;
+	return nullptr;
 }
 
 using ScoreI8Fn = void (*)(ScoreIdsI8Params);
@@ -448,13 +406,6 @@ const ScoreI8Variant kScoreI8[] = {SCORE_I8(64), SCORE_I8(128), SCORE_I8(256), S
 #undef SCORE_I8
 const ScoreI8Variant kScoreI8Any[] = {{0, kU8L2, score_ids_i8_any_kernel<kU8L2>}, {0, kI8L2, score_ids_i8_any_kernel<kI8L2>},
                                       {0, kI8L2Ref, score_ids_i8_any_kernel<kI8L2Ref>}, {0, kI8IP, score_ids_i8_any_kernel<kI8IP>}};
-
-uint32_t pow2ceil(uint32_t x) {
-	uint32_t p = 1;
-	while (p < x)
-		p <<= 1;
-	return p;
-}
 
 
 // Does a level of ratio r fit lists of `cap` keys?  A level that scans r times the rows of the level before keeps
@@ -601,35 +552,28 @@ int ensure_workspace(expann_index* h, size_t m, uint32_t cap) {
 }
 
 // ---- GEMM-form (MFMA) scan: dims it is built for ----------------------------------------
-using GemmFn = void (*)(GemmScanParams);
+// the bf16x3 form (fp32 L2 rows), with the kernels of its row and query terms (gemm_terms.hpp)
 using NormFn = void (*)(const float*, uint32_t, float, float*);
 using ThetaFn = void (*)(const float*, uint32_t, const float*, float, float*);
-struct GemmVariant {
-	int d;
-	GemmFn scan;
-	NormFn norms;
-	ThetaFn theta;
-	const char* name;
-};
-// d = 64 / 128: the row / query terms of the bf16x3 fallback form (gemm_terms.hpp); no scan kernel of its own
-const GemmVariant kGemmF32[] = {
-    {64, nullptr, row_norms_kernel<64>, query_theta_kernel<64>, "-"},
-    {128, nullptr, row_norms_kernel<128>, query_theta_kernel<128>, "-"}};
-// dims that only the fp16 form covers: a placeholder without kernels (scan == nullptr) keeps the
-// GEMM branch of the level loop alive; without the fp16 form it counts as "no GEMM form"
-const GemmVariant kGemmF16Only[] = {{256, nullptr, nullptr, nullptr, "-"}, {512, nullptr, nullptr, nullptr, "-"},
-                                    {64, nullptr, nullptr, nullptr, "-"},  {128, nullptr, nullptr, nullptr, "-"},
-                                    {768, nullptr, nullptr, nullptr, "-"}, {832, nullptr, nullptr, nullptr, "-"},
-                                    {960, nullptr, nullptr, nullptr, "-"}};
-
 using GemmBf16Fn = void (*)(GemmBf16Params);
 struct GemmBf16Variant {
 	int d;
 	GemmBf16Fn scan;
+	NormFn norms;
+	ThetaFn theta;
 	const char* name;
 };
-const GemmBf16Variant kGemmBf16[] = {{64, scan_gemm_bf16x3_kernel<64>, "scan_gemm_bf16x3<64>"},
-                                     {128, scan_gemm_bf16x3_kernel<128>, "scan_gemm_bf16x3<128>"}};
+// (The compiler emits a kernel template's instances into the code object in the order in which the source first names
+// them.  Naming the four term kernels here, ahead of the two scans, keeps that order -- terms of 64, of 128, then the
+// scans -- as it was while the terms sat in a table of their own, so the device code of this file stays byte for byte
+// what it was and a comparison of two builds' assembly shows kernel changes only.)
+constexpr struct {
+	NormFn norms;
+	ThetaFn theta;
+} kBf16Terms[] = {{row_norms_kernel<64>, query_theta_kernel<64>}, {row_norms_kernel<128>, query_theta_kernel<128>}};
+const GemmBf16Variant kGemmBf16[] = {
+    {64, scan_gemm_bf16x3_kernel<64>, kBf16Terms[0].norms, kBf16Terms[0].theta, "scan_gemm_bf16x3<64>"},
+    {128, scan_gemm_bf16x3_kernel<128>, kBf16Terms[1].norms, kBf16Terms[1].theta, "scan_gemm_bf16x3<128>"}};
 
 using GemmF16Fn = void (*)(GemmF16Params);
 using SqnormFn = void (*)(const float*, uint32_t, float*);
@@ -671,22 +615,23 @@ const GemmF16Variant kGemmF16X[] = {F16X_V(64), F16X_V(128), F16Y_V(256), F16Y_V
 const GemmF16Variant kGemmF16XDbg[] = {{128, scan_gemm_f16x_kernel<128, false, 1>, scan_gemm_f16x_kernel<128, true>,
                                         sqnorm_kernel<128>, f16_query_prep_kernel<128>, "scan_gemm_f16x<128, false>",
                                         kF16TB, kF16TQ, kF16Threads, 2, gemm_f16_lds_bytes<128>(), 1}};
-inline bool f16_choice(long opt) { return opt == 0 || opt == 4 || opt == 6; }
 // the fp16 filter with the dim known at run time (scan_gemm_kl.hpp, fp16 instances): every f32 dim from 64 up without a
 // form of its own (d = 0 here; prelude: sqnorm_any_kernel / f16_query_prep_any_kernel)
 const GemmF16Variant kGemmF16KL = {0, scan_gemm_kl_kernel<F16Elem, false>, scan_gemm_kl_kernel<F16Elem, true>, nullptr, nullptr,
                                    "scan_gemm_f16kl", kKlTB, kF16TQ, kF16Threads, 1, kKlLds, 1};
-inline bool f16kl_dim(int d) {
-	if (d < 64 || !any_dim_f32(d))
-		return false;
-	for (const auto& v : kGemmF16X)
-		if (v.d == d)
-			return false;
-	return true;
-}
 // row length of the index's fp16 copy: whole 32-element MFMA k-steps for the run-time-dim form
 inline int f16_ld(int d) { return f16kl_dim(d) ? (d + 31) / 32 * 32 : d; }
-const GemmVariant kGemmF16KLOnly = {0, nullptr, nullptr, nullptr, "-"};  // (pick_gemm's placeholder, as kGemmF16Only)
+// the variant of a plan's fp16 family (bf_plan.hpp) at dim d
+const GemmF16Variant* find_f16(ScanFamily f, int d) {
+	if (f == ScanFamily::kF16KL)
+		return &kGemmF16KL;
+	if (f == ScanFamily::kF16Dbg)
+		return &kGemmF16XDbg[0];
+	for (const auto& v : kGemmF16X)
+		if (is_f16(f) && v.d == d)
+			return &v;
+	return nullptr;
+}
 
 // a handful of queries: the same filter streamed from HBM without the matrix cores
 // (scan_direct_f16.hpp); tq = queries per pass
@@ -707,17 +652,12 @@ const DirectF16Variant kDirectF16[] = {DF16_V(64, 2),  DF16_V(64, 4),  DF16_V(12
                                        DF16_VN(768, 1), DF16_VN(832, 1), DF16_VN(960, 1)};
 #undef DF16_V
 #undef DF16_VN
-// the variant for m queries: ONE pass (measured at 1M x d128: a second pass, or 8 queries per
-// pass -- VALU-bound --, loses to the MFMA form), else the other paths take over
-const DirectF16Variant* pick_direct_f16(int d, size_t m) {
-	const DirectF16Variant* best = nullptr;
-	for (const auto& v : kDirectF16) {
-		if (v.d != d)
-			continue;
-		if (!best || ((size_t)best->tq < m && v.tq > best->tq) || ((size_t)v.tq >= m && v.tq < best->tq))
-			best = &v;
-	}
-	return (best && m <= (size_t)best->tq) ? best : nullptr;
+// the variant of tile tq (bf_plan.hpp's direct_f16_tile; 0: none)
+const DirectF16Variant* find_direct_f16(int d, int tq) {
+	for (const auto& v : kDirectF16)
+		if (tq && v.d == d && v.tq == tq)
+			return &v;
+	return nullptr;
 }
 
 // fp16 copy of the base (scaled by a power of two), its slack-adjusted norms, max norm
@@ -821,62 +761,43 @@ void drop_row_filter(expann_index* h) { h->forget<RowFilter>(); }
 // forget the row groups (they belong to the rows they were set for)
 void drop_row_groups(expann_index* h) { h->forget<RowGroups>(); }
 
-const GemmVariant* pick_gemm(const expann_index* h, size_t m) {
-	if (h->opt_scan_kernel == 1 || !float_rows(h))
-		return nullptr;
-	if (f16_rows(h) && !f16_choice(h->opt_scan_kernel))  // (binary16 rows: the fp16 form is the only matrix-core one)
-		return nullptr;
-	if (h->metric == EXPANN_METRIC_IP) {
-		// inner product: only the fp16 form has it (a placeholder variant keeps the GEMM branch alive)
-		const bool ok = f16_choice(h->opt_scan_kernel) && h->f16_scale >= 0.0f &&
-		                !(h->opt_scan_kernel == 0 && ((m < 5 && !pick_direct_f16(h->dim, m)) || h->n < 4096));
-		if (ok) {
-			for (const auto& v : kGemmF16Only)
-				if (v.d == h->dim)
-					return &v;
-			if (f16kl_dim(h->dim))
-				return &kGemmF16KLOnly;
-		}
-		return nullptr;
-	}
-	// measured crossovers at N = 1M, d = 128.  bf16x3 / fp32 forms: m = 16: 0.34 vs 0.37 ms per
-	// step, m = 32: 0.49 vs 0.41 ms -- below ~24 queries the HBM-bound direct scan wins.  fp16
-	// form (half the bytes per row, one sampled pass): 0.175 vs 0.175 ms at m = 4, 0.173 vs 0.199
-	// at m = 8, 0.185 vs 0.31 at m = 16 -- from 5 queries on it wins.
-	bool f16_dims = f16kl_dim(h->dim) && h->f16_scale >= 0.0f;
-	for (const auto& v : kGemmF16Only)
-		f16_dims = f16_dims || (v.d == h->dim && h->f16_scale >= 0.0f);
-	if (h->opt_scan_kernel == 0 &&
-	    ((m < (f16_dims ? 5u : 24u) && !(f16_dims && pick_direct_f16(h->dim, m))) || h->n < 4096))
-		return nullptr;
-	for (const auto& v : kGemmF32)
-		if (v.d == h->dim)
-			return &v;
-	if (f16_choice(h->opt_scan_kernel)) {
-		for (const auto& v : kGemmF16Only)
-			if (v.d == h->dim)
-				return &v;
-		if (f16kl_dim(h->dim))
-			return &kGemmF16KLOnly;
-	}
-	return nullptr;
+// what the planner (bf_plan.hpp) reads of a handle
+PlanIndex plan_index(const expann_index* h) {
+	PlanIndex x;
+	x.dtype = h->dtype;
+	x.int_mode = h->int_mode;
+	x.metric = h->metric;
+	x.dim = h->dim;
+	x.n = h->n;
+	x.scan_kernel = h->opt_scan_kernel;
+	x.query_tile = h->opt_query_tile;
+	x.i8_filter = h->opt_i8_filter;
+	x.u8_exact_opt = h->opt_u8_exact;
+	x.sample_pass = h->opt_sample_pass;
+	x.spec_rank = h->opt_spec_rank;
+	x.debug = h->opt_debug;
+	x.cand_capacity = h->opt_cand_capacity;
+	x.f16_ok = h->f16_scale >= 0.0f;
+	x.i8f_state = h->i8f_state;
+	x.u8_exact = h->u8_exact;
+	x.filter_on = h->filter_on;
+	x.n_allowed = h->n_allowed;
+	return x;
 }
 
-int ensure_bnorm(expann_index* h, const GemmVariant* gv, bool bf16, hipStream_t st) {
-	DevPtr<float>& dst = bf16 ? h->d_bnorm_bf : h->d_bnorm;
+// the bf16x3 form's row terms and planes
+int ensure_bnorm_bf16(expann_index* h, const GemmBf16Variant* gvb, hipStream_t st) {
 	const uint32_t blocks = (uint32_t)((h->n + kRowsPerGroup - 1) / kRowsPerGroup);
-	if (!dst) {
-		HIP_TRY(h, hipMalloc(&dst, sizeof(float) * h->n));
-		const float eps = bf16 ? gemm_bf16_filter_eps(h->dim) : gemm_filter_eps(h->dim);
-		hipLaunchKernelGGL(gv->norms, dim3(blocks), dim3(kBlock), 0, st, (const float*)h->d_base,
-		                   (uint32_t)h->n, 1.0f - eps, dst);
+	if (!h->d_bnorm_bf) {
+		HIP_TRY(h, hipMalloc(&h->d_bnorm_bf, sizeof(float) * h->n));
+		hipLaunchKernelGGL(gvb->norms, dim3(blocks), dim3(kBlock), 0, st, (const float*)h->d_base,
+		                   (uint32_t)h->n, 1.0f - gemm_bf16_filter_eps(h->dim), h->d_bnorm_bf);
 		if (!h->d_bnmax)
 			HIP_TRY(h, hipMalloc(&h->d_bnmax, 4 * sizeof(float)));
-		hipLaunchKernelGGL(max_f32_kernel, dim3(1), dim3(1024), 0, st, (const float*)dst, h->n,
-		                   h->d_bnmax + (bf16 ? 1 : 0));
+		hipLaunchKernelGGL(max_f32_kernel, dim3(1), dim3(1024), 0, st, (const float*)h->d_bnorm_bf, h->n, h->d_bnmax + 1);
 		HIP_TRY(h, hipGetLastError());
 	}
-	if (bf16 && !h->d_base_split) {
+	if (!h->d_base_split) {
 		const size_t nv = h->n * (size_t)h->dim;
 		HIP_TRY(h, hipMalloc(&h->d_base_split, nv * 4));
 		hipLaunchKernelGGL(split_bf16_kernel, dim3((uint32_t)((nv + kBlock - 1) / kBlock)),
@@ -906,13 +827,9 @@ const GemmI8Variant kGemmI8[] = {
     GEMM_I8(768, kU8L2, "U8L2"), GEMM_I8(768, kI8L2, "I8L2"), GEMM_I8(768, kI8IP, "I8IP")};
 #undef GEMM_I8
 
-const GemmI8Variant* pick_gemm_i8(const expann_index* h, size_t m) {
-	if (h->opt_scan_kernel == 1 || float_rows(h))
-		return nullptr;
-	if (h->opt_scan_kernel == 0 && (m < 96 || h->n < 4096))
-		return nullptr;
+const GemmI8Variant* find_gemm_i8(int d, int mode) {
 	for (const auto& v : kGemmI8)
-		if (v.d == h->dim && v.mode == h->int_mode)
+		if (v.d == d && v.mode == mode)
 			return &v;
 	return nullptr;
 }
@@ -1266,24 +1183,51 @@ const GemmI8qVariant kGemmI8KL[] = {GEMM_I8KL(kU8L2, "U8L2"), GEMM_I8KL(kI8L2, "
 constexpr int kRetryGeneric = -1000;  // internal: the caller falls back to the threshold ladder
 constexpr int kStrictReject = -1001;  // internal (uint8 shadow): these queries are not 8-bit integers
 
-const GemmI8qVariant* pick_gemm_i8q(const expann_index* h, size_t m, size_t k) {
-	if (float_rows(h) || !(h->opt_scan_kernel == 0 || h->opt_scan_kernel == 5))
-		return nullptr;
-	if (h->opt_scan_kernel == 0 && (m < 96 || h->n < 65536))
-		return nullptr;
-	if (h->n < 2 * 256 * kF16TB || k > 256)
-		return nullptr;
+// the variant of a plan's q-form family (bf_plan.hpp)
+const GemmI8qVariant* find_gemm_i8q(ScanFamily f, int d, int mode) {
 	for (const auto& v : kGemmI8w)
-		if (v.d == h->dim && v.mode == h->int_mode)
+		if (f == ScanFamily::kI8qW && v.d == d && v.mode == mode)
 			return &v;
 	for (const auto& v : kGemmI8x)
-		if (v.d == h->dim && v.mode == h->int_mode)
+		if (f == ScanFamily::kI8qX && v.d == d && v.mode == mode)
 			return &v;
-	if (any_dim_i8(h->dim, h->int_mode))  // no compiled form: the run-time-dim one
-		for (const auto& v : kGemmI8KL)
-			if (v.mode == h->int_mode)
-				return &v;
+	for (const auto& v : kGemmI8KL)
+		if (f == ScanFamily::kI8qKL && v.mode == mode)
+			return &v;
 	return nullptr;
+}
+
+// Do the variant tables hold what bf_plan.hpp lists as compiled -- every entry listed, and as many as listed?
+// (checked once, at the first expann_create: the planner answers from its lists, the launches from these tables)
+static_assert(kI8MinRows == 2 * 256 * kF16TB, "bf_plan.hpp: two 256-tile chunks of the int8 hit-log forms");
+bool plan_tables_match() {
+	bool ok = kGemmF16XDbg[0].d == kF16DbgDim && kGemmI8F.d == kI8fDim;
+	auto all = [&ok](const auto& tab, size_t listed, auto in) {
+		size_t hits = 0;
+		for (const auto& v : tab)
+			hits += in(v) ? 1 : 0;
+		ok = ok && hits == std::size(tab) && hits == listed;
+	};
+	const auto mfma_mode = [](int mode) { return mode == kU8L2 || mode == kI8L2 || mode == kI8IP; };
+	all(kScanF32, 2 * count_tiles(kScanF32Tiles, std::size(kScanF32Tiles)),
+	    [](const ScanVariant& v) { return has_tile(tiles_of(kScanF32Tiles, v.d), v.tq); });
+	all(kScanF32Any, 2 * count_tiles(&kScanF32AnyTiles, 1), [](const ScanVariant& v) { return has_tile(&kScanF32AnyTiles, v.tq); });
+	all(kScanI8, 4 * count_tiles(kScanI8Tiles, std::size(kScanI8Tiles)) + count_tiles(kScanI16Tiles, std::size(kScanI16Tiles)),
+	    [](const ScanI8Variant& v) {
+		    return has_tile(v.mode == kI16L2Ref ? tiles_of(kScanI16Tiles, v.d) : tiles_of(kScanI8Tiles, v.d), v.tq);
+	    });
+	all(kScanI8Any, 4 * count_tiles(&kScanI8AnyTiles, 1), [](const ScanI8Variant& v) { return has_tile(&kScanI8AnyTiles, v.tq); });
+	all(kDirectF16, count_tiles(kDirectF16Tiles, std::size(kDirectF16Tiles)),
+	    [](const DirectF16Variant& v) { return has_tile(tiles_of(kDirectF16Tiles, v.d), v.tq); });
+	all(kGemmF16X, std::size(kF16XDims) + std::size(kF16YDims) + std::size(kF16KXDims), [](const GemmF16Variant& v) {
+		return (has_dim(kF16XDims, v.d) && v.scan_redo) || has_dim(kF16YDims, v.d) || has_dim(kF16KXDims, v.d);
+	});
+	all(kGemmBf16, std::size(kBf16Dims), [](const GemmBf16Variant& v) { return has_dim(kBf16Dims, v.d); });
+	all(kGemmI8, 3 * std::size(kGemmI8Dims), [&](const GemmI8Variant& v) { return has_dim(kGemmI8Dims, v.d) && mfma_mode(v.mode); });
+	all(kGemmI8w, 3 * std::size(kI8qWDims), [&](const GemmI8qVariant& v) { return has_dim(kI8qWDims, v.d) && mfma_mode(v.mode); });
+	all(kGemmI8x, 3 * std::size(kI8qXDims), [&](const GemmI8qVariant& v) { return has_dim(kI8qXDims, v.d) && mfma_mode(v.mode); });
+	all(kGemmI8KL, 3, [&](const GemmI8qVariant& v) { return v.d == 0 && mfma_mode(v.mode); });
+	return ok;
 }
 
 // int8 filter of fp32 rows: clip of the scale (s = min(max |x|, kI8fClipRms rms) / 127)
@@ -1301,31 +1245,6 @@ constexpr double kI8fListRatio = 2.8;
 // (measured with proven thresholds; under a speculative threshold of rank j the limit scales with j / k as the
 // lists do -- i8f_cand_limit -- and the clustered rows still pass it on their first search)
 constexpr double kI8fBreakEvenRatio = 3.4;
-// The auto region, from the A/B sweep of the two forms over n = 0.5 / 0.75 / 1 / 2 M rows, m = 2 048 / 4 096 / 10 000
-// queries, k = 1 / 10 / 16 / 32 on iid rows (profiles/r06_i8f_sweep.json): every measured point inside is faster
-// by 4.8 % or more; k = 32 lost everywhere (up to -58 %), k = 10 at 500 k rows and at 1 M rows x 2 048 queries lost.
-// Shapes between the grid points take the nearest grid point below them in n and m, above them in k.
-bool i8f_auto_region(size_t n, size_t m, size_t k) {
-	if (k <= 1)
-		return n >= 500000 && m >= 2048;  // (+13 % .. +41 %)
-	if (k <= 10)
-		return (n >= 1000000 && m >= 4096) || (n >= 2000000 && m >= 2048);  // (+10 % .. +27 %)
-	if (k <= 16)
-		return (n >= 2000000 && m >= 2048) || (n >= 1000000 && m >= 10000);  // (+4.8 % .. +20 %)
-	return false;
-}
-// The int8 filter for fp32 rows (scan_gemm_i8f.hpp) serves this search?  fp32 rows, L2, d = 128, the uint8
-// shortcut not serving the index, no debug instance, the scan_kernel option on auto; option i8_filter = 2
-// wherever that holds, 1 (auto) above the thresholds below.
-bool i8f_wanted(const expann_index* h, size_t m, size_t k) {
-	if (h->opt_i8_filter == 0 || h->opt_scan_kernel != 0 || h->dtype != EXPANN_DTYPE_F32 ||
-	    h->metric != EXPANN_METRIC_L2 || h->dim != 128 || h->u8_exact == 1 || (h->opt_debug & ~16L) != 0 ||
-	    h->i8f_state < 0 || k > 256 || h->n < 2 * 256 * kF16TB)
-		return false;
-	if (h->opt_i8_filter == 2)
-		return true;
-	return h->i8f_state != 2 && i8f_auto_region(h->n, m, k);
-}
 // Candidates of one search above which the int8 filter loses to the fp16 form (kI8fBreakEvenRatio): rows in tight
 // clusters give it far longer lists than iid rows do.  Past this total an auto search turns the form off for the
 // index (i8f_state 2, until set_base_device brings other rows): the rows, not the shape, decided, and they do not
@@ -1714,11 +1633,11 @@ int absorb_shadow_profile(expann_index* h) {
 
 // One sampled pass of the fp16 form gives every query the threshold of its full scan (4.6 of
 // DESIGN.md): class maxima of g over 1/frac of the rows, their k-th largest -> tau, theta', and
-// the list counters zeroed.  A handful of queries: sampled pass and thresholds in ONE launch
-// (scan_direct_f16.hpp); otherwise the MFMA SAMPLE kernel + sample_tau_kernel.  *done stays false
+// the list counters zeroed.  A handful of queries (dv, the plan's scan_direct_f16 variant): sampled pass and
+// thresholds in ONE launch (scan_direct_f16.hpp); otherwise the MFMA SAMPLE kernel + sample_tau_kernel.  *done stays false
 // when the index is too small for a sample (the caller runs the threshold ladder instead).
-int sampled_pass_f16(expann_index* h, const GemmF16Variant* gvf, size_t m, size_t k, bool ip, int cus,
-                     float* d_tau, uint32_t* d_tau_row, hipStream_t st, bool* done, bool i8f, bool* i8f_done,
+int sampled_pass_f16(expann_index* h, const GemmF16Variant* gvf, const DirectF16Variant* dv, size_t m, size_t k, bool ip,
+                     int cus, float* d_tau, uint32_t* d_tau_row, hipStream_t st, bool* done, bool i8f, bool* i8f_done,
                      uint32_t* spec_j) {
 	*done = false;
 	*i8f_done = false;
@@ -1763,7 +1682,7 @@ int sampled_pass_f16(expann_index* h, const GemmF16Variant* gvf, size_t m, size_
 	const bool filt = h->filter_on;
 	const double dens = filt ? (double)h->n_allowed / (double)h->n : 1.0;
 	const size_t need_classes = filt ? 2 * k : 8 * k;
-	const DirectF16Variant* dvs = (h->opt_scan_kernel == 0 && !i8f) ? pick_direct_f16(h->dim, m) : nullptr;
+	const DirectF16Variant* dvs = i8f ? nullptr : dv;
 	if (dvs && dvs->sample) {
 		const uint32_t steps_all = (uint32_t)((h->n + dvs->rps - 1) / dvs->rps);
 		uint32_t sel =
@@ -1959,8 +1878,8 @@ int launch_scan_i8f(expann_index* h, size_t m, int cus, uint32_t cap, hipStream_
 
 // The fp16-form scan of one threshold level (theta' is in h->d_theta): the MFMA kernel of the
 // index's dimension over `rows_sel` sampled rows (last: all rows), or -- a handful of queries on
-// the last level -- the same filter streamed from HBM (scan_direct_f16.hpp).
-int launch_scan_f16(expann_index* h, const GemmF16Variant* gvf, uint32_t rows_sel, bool last, size_t m, int cus,
+// the last level: dv, the plan's variant -- the same filter streamed from HBM (scan_direct_f16.hpp).
+int launch_scan_f16(expann_index* h, const GemmF16Variant* gvf, const DirectF16Variant* dv, uint32_t rows_sel, bool last, size_t m, int cus,
                     bool ip, uint32_t cap, hipStream_t st, const char** kname, uint32_t* n_qtiles,
                     uint32_t* query_tile) {
 	*query_tile = (uint32_t)gvf->wgq;
@@ -2017,9 +1936,7 @@ int launch_scan_f16(expann_index* h, const GemmF16Variant* gvf, uint32_t rows_se
 		HIP_TRY(h, hipMemsetAsync(clk.p, 0, (18 + 3 * 65536) * 8, st));
 		fp.clk = clk.as<unsigned long long>();
 	}
-	const DirectF16Variant* dv =
-	    (last && h->opt_scan_kernel == 0) ? pick_direct_f16(h->dim, m) : nullptr;
-	if (dv) {
+	if (dv && last) {
 		// a handful of queries: stream the fp16 rows without the matrix cores, ~16
 		// workgroups per CU, whole RPS-row steps (inside the copy's 64-row padding)
 		fp.n_qtiles = (uint32_t)((m + dv->tq - 1) / dv->tq);
@@ -2119,11 +2036,11 @@ int launch_f16_query_prep(expann_index* h, const GemmF16Variant* gvf, const void
 }
 
 // ---- one pass over <= kMaxQueriesPerPass queries, as a planner + steps -------------------------
-// choose_kernels()   which kernel family serves this pass (the planner: row type, metric, batch size,
+// choose_kernels()   which kernel family serves this pass (plan_scan, bf_plan.hpp: row type, metric, batch size,
 //                    options, what an earlier attempt learned) and the index's derived copies it needs
 // prepare_queries()  the query-side conversions of that family (scaled fp16 / bf16 split)
 // plan_thresholds()  threshold levels of this attempt: the ladder, class minima, or one sampled pass
-// run_level(li)      scan of level li (direct / fp32 / bf16x3 / fp16 / int8 MFMA filter) + selection
+// run_level(li)      scan of level li (direct / bf16x3 / fp16 / int8 MFMA filter) + selection
 // check(attempt)     the one host wait: flags read back, retry with larger lists / another family
 // the redo pass's workspace for R query slots (expann_index::d_redo), offsets in bytes: the failing queries'
 // numbers, the per-slot list counters, theta', ||q||^2, w_q, thp, the bounds S_k' of the failed lists, the thresholds
@@ -2146,18 +2063,10 @@ struct RedoWs {
 		total = cand + 8 * (size_t)R * (size_t)cap;
 	}
 };
-// Where the auto rank speculates (opt_spec_rank = 0), from the A/B against proven thresholds over bench.py's shapes
-// (profiles/r07_spec_tau_ab.txt): the shorter lists have to pay for the redo pass, four launches that cost ~20 us
-// when no query failed and ~100 us when some did (a scan of the index for one query tile, a select of a few lists).
-// They do where the lists are long: the int8 filter's (C2: 501 -> 215 per query, -11 % per step) and the fp16 form's
-// at large k (1.25 M rows, k = 100: 703 -> 183, -5.1 %).  The fp16 form at k = 10 loses ~1 % (d = 64, 1 000 clusters:
-// 176 -> 70 keys saves less than the chain costs), so does any form at 1 000 queries.  Shapes between the measured
-// ones keep proven thresholds.
-bool spec_auto_region(const expann_index* h, size_t m, size_t k, bool i8f) {
-	(void)h;
-	if (m < 4096)
-		return false;
-	return i8f || k > 32;
+// the direct scan's row chunks: ~16 workgroups per CU in total, at least 8 groups (128 rows) per workgroup
+uint32_t direct_scan_chunks(uint32_t n_groups_sel, uint32_t n_qtiles, int cus) {
+	const uint32_t target = (uint32_t)std::max<long>(1, (16L * cus + n_qtiles - 1) / n_qtiles);
+	return std::min(target, std::max<uint32_t>(1, n_groups_sel / 8));
 }
 
 struct ScanSel {
@@ -2178,19 +2087,17 @@ struct SearchPass {
 	uint32_t cap;
 	ScanSel svs;
 	const ScanSel* sv = &svs;
-	// the planner's choice
-	const GemmVariant* gv = nullptr;
+	// the planner's choice (bf_plan.hpp) and its family's variant: at most one of the three is set
+	ScanPlan plan;
+	PlanAttempt learned;        // what the attempts so far learned
 	const GemmI8Variant* gvi = nullptr;
 	const GemmBf16Variant* gvb = nullptr;
 	const GemmF16Variant* gvf = nullptr;
+	const DirectF16Variant* dv = nullptr;  // fp16 form: scan_direct_f16 serves the last level and the sampled pass
 	bool i8f = false;           // the int8 filter runs the full scan (fp16 prelude, scan_gemm_i8f.hpp)
 	bool i8f_ready = false;     // its thresholds of this attempt are written
-	bool i8f_off = false;       // its lists overflowed: the retry runs the fp16 form
 	bool i8f_ran = false;       // the last level of this attempt ran it
-	// what an attempt learned
 	bool flags_clean = false;   // the fp16 prelude has just zeroed the flag block
-	bool force_direct = false;  // a GEMM-form filter overflowed: massive near-ties
-	bool no_f16 = false;        // the queries do not fit the fp16 range of this index
 	// thresholds of the current attempt
 	std::vector<Level> levels;
 	uint32_t n_qtiles = 0;
@@ -2198,11 +2105,11 @@ struct SearchPass {
 	bool theta_ready = false;   // the sampled pass also wrote theta' and zeroed the list counters
 	// speculative thresholds
 	uint32_t spec_j = 0;        // this attempt's lists are filtered with the j-th class maximum, j < k (0: proven thresholds)
-	bool spec_off = false;      // an attempt's failing queries did not fit the redo pass: proven thresholds from here on
 	uint32_t redo_slots = 0;    // R: query slots of the redo pass
 	bool rerank_counted = false;  // "rerank_stats": the last level's selects counted the rows they re-scored
 
 	enum Next { kDone, kRestart, kRetry };
+	ScanPlan replan() const { return plan_scan(plan_index(h), PlanCall{m, k, cap}, learned); }
 	int choose_kernels();
 	int prepare_queries(bool* restart);
 	int plan_thresholds();
@@ -2213,59 +2120,24 @@ struct SearchPass {
 };
 
 int SearchPass::choose_kernels() {
-	// A row filter reaches the matrix cores through the fp16 forms' masked row terms only: no
-	// bf16x3 form (queries outside the fp16 range go to the exact direct scan), no int8 filter, no speculative
-	// thresholds, whatever the options say; a filter selective enough for the list path streams no base at all
-	// Binary16 rows (EXPANN_DTYPE_F16) have neither a bf16x3 form nor an int8 filter -- both build their operands
-	// from fp32 storage -- so "scan_kernel" 3 and queries outside the fp16 range run the exact direct scan there too.
-	const bool filt = h->filter_on;
-	gv = force_direct ? nullptr : pick_gemm(h, m);
-	if (filt && (no_f16 || !f16_choice(h->opt_scan_kernel) || h->n_allowed <= cap))
-		gv = nullptr;
-	gvi = force_direct ? nullptr : pick_gemm_i8(h, m);
-	gvb = nullptr;
-	gvf = nullptr;
-	if (h->opt_scan_kernel == 2 && !gvi)
-		return h->fail(EXPANN_ERR_UNSUPPORTED,
-		               "GEMM-form scan (scan_kernel=2): 8-bit L2/IP with dim 128/256/768 (the fp32-input MFMA form of "
-		               "rounds 1-2 is gone: scan_kernel 3 = bf16x3, 4 = fp16)");
+	plan = replan();
+	gvi = plan.family == ScanFamily::kGemmI8 ? find_gemm_i8(h->dim, h->int_mode) : nullptr;
 	if (gvi) {
 		int rc = ensure_bias_i8(h, gvi, st);
 		if (rc != EXPANN_OK)
 			return rc;
 	}
-	if (gv && h->dtype == EXPANN_DTYPE_F32)
-		for (const auto& v : kGemmBf16)
-			if (v.d == h->dim)
-				gvb = &v;
-	if (h->opt_scan_kernel == 3 && !gvb && !filt && !f16_rows(h))
-		return h->fail(EXPANN_ERR_UNSUPPORTED, "bf16x3 GEMM-form scan: f32 L2 with dim 64 or 128 only");
-	// fp16 single-product form: default when available; a search whose queries leave the fp16
-	// range after scaling is redone with the bf16x3 form (no_f16)
-	if (gv && !no_f16 && f16_choice(h->opt_scan_kernel)) {
-		const bool dbg = (h->opt_debug & ~16L) != 0;  // (the debug instance exists for d = 128 only)
-		for (const auto& v : kGemmF16X)
-			if (v.d == h->dim && !(dbg && v.d == kGemmF16XDbg[0].d))
-				gvf = &v;
-		if (dbg && kGemmF16XDbg[0].d == h->dim)
-			gvf = &kGemmF16XDbg[0];
-		if (!gvf && f16kl_dim(h->dim))
-			gvf = &kGemmF16KL;
-	}
-	i8f = gvf && !i8f_off && !filt && i8f_wanted(h, m, k);
-	if (filt && !gvf)
-		gv = nullptr;
-	if ((h->opt_scan_kernel == 4 || h->opt_scan_kernel == 6) && !gvf && !no_f16 && !(filt && h->n_allowed <= cap))
-		return h->fail(EXPANN_ERR_UNSUPPORTED, "fp16 GEMM-form scan: f32 with dim a multiple of 16 from 64 to 4096 only");
-	if (gvf)
-		gvb = nullptr;
-	else if ((h->opt_scan_kernel == 0 && m < 24) || !gvb)
-		gv = nullptr, gvb = nullptr;  // without the fp16 form only bf16x3 is left (d = 64 / 128; pays from ~24 queries on)
-	if (gv && !gvf) {
-		int rc = ensure_bnorm(h, gv, gvb != nullptr, st);
-		if (rc != EXPANN_OK)
-			return rc;
-	}
+	if (plan.status != EXPANN_OK)
+		return h->fail(plan.status, plan.message);
+	gvf = find_f16(plan.family, h->dim);
+	dv = find_direct_f16(h->dim, plan.direct_f16_tq);
+	i8f = plan.i8f;
+	gvb = nullptr;
+	for (const auto& v : kGemmBf16)
+		if (plan.family == ScanFamily::kBf16x3 && v.d == h->dim)
+			gvb = &v;
+	if (gvb)
+		return ensure_bnorm_bf16(h, gvb, st);
 	return EXPANN_OK;
 }
 
@@ -2276,7 +2148,7 @@ int SearchPass::prepare_queries(bool* restart) {
 		if (rc != EXPANN_OK)
 			return rc;
 		if (h->f16_scale < 0.0f) {  // the index does not fit the fp16 range at any allowed scale
-			no_f16 = true;
+			learned.no_f16 = true;
 			*restart = true;
 			return EXPANN_OK;
 		}
@@ -2291,11 +2163,13 @@ int SearchPass::prepare_queries(bool* restart) {
 			rc = ensure_i8f(h, st);
 			if (rc != EXPANN_OK)
 				return rc;
-			i8f = h->i8f_state > 0;
+			// the plan again, now that the handle knows whether its rows take the int8 filter (i8f_state 1 / 2, or -1:
+			// then without it, with the speculation and the list capacity of the fp16 form alone)
+			plan = replan();
+			i8f = plan.i8f;
 			// (room for the lists of queries with a clipped component; with speculative thresholds the main lists are
 			// shorter -- 819 at most at C2 -- but the redo pass's are proven-threshold lists: 1 178 at most)
-			if (i8f && h->opt_cand_capacity <= 0)
-				cap = std::max<uint32_t>(cap, 4096);
+			cap = std::max(cap, plan.i8f_min_cap);
 		}
 		if (i8f) {  // int8 queries and the per-query terms [A_q | W_q | w_q | thp]
 			HIP_TRY(h, grow_ws(h, h->d_q8f, m * (size_t)h->dim));
@@ -2341,7 +2215,7 @@ int SearchPass::plan_thresholds() {
 	levels = filt ? plan_levels_filtered(h->n, h->n_allowed, h->filter_list_len, k, cap, h->opt_sample_ratio)
 	              : plan_levels(h->n, k, cap, h->opt_sample_ratio);
 	n_qtiles = (uint32_t)((m + sv->tq - 1) / sv->tq);
-	if (!gv && !gvi && levels.size() >= 3 && h->opt_sample_pass && !filt) {
+	if (plan.family == ScanFamily::kDirect && plan.sampled && levels.size() >= 3) {
 		// direct path: ONE sampled level of class minima (1/16 of the rows) instead of the
 		// first two levels of the ladder -- a launch chain shorter by a scan, a select and a
 		// memset, and ~10 k instead of ~32 k candidates in the full scan
@@ -2371,16 +2245,10 @@ int SearchPass::plan_thresholds() {
 	i8f_ready = false;
 	spec_j = 0;
 	h->stat_i8_sample = 0;
-	if (gvf && h->opt_sample_pass && levels.size() >= 2) {
-		// (speculation: the scan_gemm_f16x / i8w streams -- the kernels with the redo pass's early exit --, batches
-		// beyond the latency mode's, no debug instance)
-		const bool spec_form = gvf->hit_log && gvf->scan_redo && (h->opt_debug & ~16L) == 0 && m > 64;
-		if (spec_form && !spec_off && !filt && h->opt_spec_rank >= 0 &&
-		    (h->opt_spec_rank > 0 || spec_auto_region(h, m, k, i8f && !i8f_off)))
-			spec_j = 1;
-		const int rs = sampled_pass_f16(h, gvf, m, k, ip, cus, h->d_tau[levels.size() & 1],
-		                                h->d_tau_row[levels.size() & 1], st, &theta_ready, i8f && !i8f_off, &i8f_ready,
-		                                &spec_j);
+	if (gvf && plan.sampled && levels.size() >= 2) {
+		spec_j = (plan.speculate && !learned.spec_off) ? 1 : 0;  // (spec_off: learned since the plan was made)
+		const int rs = sampled_pass_f16(h, gvf, dv, m, k, ip, cus, h->d_tau[levels.size() & 1],
+		                                h->d_tau_row[levels.size() & 1], st, &theta_ready, i8f, &i8f_ready, &spec_j);
 		if (rs != EXPANN_OK)
 			return rs;
 		if (theta_ready)
@@ -2421,10 +2289,7 @@ int SearchPass::run_level(size_t li) {
 		sp.list_len = L.list_rows;
 		sp.list_stride = L.list_step;
 	}
-	// ~16 workgroups per CU in total, at least 8 groups (128 rows) per workgroup
-	uint32_t target_chunks = (uint32_t)std::max<long>(1, (16L * cus + n_qtiles - 1) / n_qtiles);
-	uint32_t max_chunks = std::max<uint32_t>(1, L.n_groups_sel / 8);
-	uint32_t n_chunks = std::min(target_chunks, max_chunks);
+	uint32_t n_chunks = direct_scan_chunks(L.n_groups_sel, n_qtiles, cus);
 	if (first && L.classmin_blocks) {
 		n_chunks = L.classmin_blocks;
 		sp.classmin = 1;
@@ -2433,7 +2298,7 @@ int SearchPass::run_level(size_t li) {
 	n_chunks = (L.n_groups_sel + sp.groups_per_block - 1) / sp.groups_per_block;
 	if (!first && !theta_ready)
 		HIP_TRY(h, hipMemsetAsync(h->d_cnt, 0, sizeof(uint32_t) * m, st));
-	const bool use_gemm = gv && !first;
+	const bool use_gemm = plan.float_gemm() && !first;
 	const bool use_i8f = use_gemm && gvf && last && i8f && i8f_ready;  // (else the fp16 form scans)
 	if (last)
 		i8f_ran = use_i8f;
@@ -2454,34 +2319,11 @@ int SearchPass::run_level(size_t li) {
 			                   0.5f * h->f16_scale * h->f16_scale, h->d_theta, ip ? 1 : 0,
 			                   ip ? h->d_qscale.as<const float>() : (const float*)nullptr);
 		else
-			hipLaunchKernelGGL(gv->theta, dim3((uint32_t)((m + kRowsPerGroup - 1) / kRowsPerGroup)),
+			hipLaunchKernelGGL(gvb->theta, dim3((uint32_t)((m + kRowsPerGroup - 1) / kRowsPerGroup)),
 			                   dim3(kBlock), 0, st, (const float*)d_queries, (uint32_t)m,
-			                   (const float*)sp.tau,
-			                   1.0f - (gvb ? gemm_bf16_filter_eps(h->dim) : gemm_filter_eps(h->dim)),
-			                   h->d_theta);
-		GemmScanParams gp{};
-		gp.base = (const float*)h->d_base;
-		gp.bnorm = h->d_bnorm;
-		gp.n_rows = (uint32_t)h->n;
-		const uint32_t n_tiles = (uint32_t)((h->n + kGemmTB - 1) / kGemmTB);
-		gp.n_tiles_sel = last ? n_tiles
-		                      : std::min(n_tiles, (L.n_groups_sel * kRowsPerGroup + kGemmTB - 1) / kGemmTB);
-		gp.tile_stride = std::max<uint32_t>(1, n_tiles / gp.n_tiles_sel);
-		const uint32_t tq_wg = gvf ? (uint32_t)gvf->wgq : (gvb ? kGemmBf16TQ : kGemmTQ);
-		uint32_t tq_small = 0;
-		gp.n_qtiles = (uint32_t)((m + tq_wg - 1) / tq_wg);
-		gp.queries = (const float*)d_queries;
-		gp.theta = h->d_theta;
-		gp.m = (uint32_t)m;
-		gp.cand_cnt = h->d_cnt;
-		gp.cand = h->d_cand;
-		gp.cap = cap;
-		// One workgroup per CU is resident (128 KiB of LDS), so the launch runs in rounds
-		// of `cus` workgroups: pick the row-chunk count that minimises
-		// rounds x (steps per workgroup + ~2 steps of prologue).
-		uint32_t gchunks = pick_row_chunks(gp.n_tiles_sel, gp.n_qtiles, (uint32_t)cus, 2.0, 4, 1024, 0, nullptr);
-		gp.tiles_per_block = (gp.n_tiles_sel + gchunks - 1) / gchunks;
-		gchunks = (gp.n_tiles_sel + gp.tiles_per_block - 1) / gp.tiles_per_block;
+			                   (const float*)sp.tau, 1.0f - gemm_bf16_filter_eps(h->dim), h->d_theta);
+		const uint32_t tq_wg = gvf ? (uint32_t)gvf->wgq : kGemmBf16TQ;
+		uint32_t tq_small = 0, gemm_qtiles = (uint32_t)((m + tq_wg - 1) / tq_wg);
 		if (timed)
 			HIP_TRY(h, hipEventRecord(h->ev[h->ev_used][0], st));
 		if (use_i8f) {
@@ -2489,46 +2331,47 @@ int SearchPass::run_level(size_t li) {
 			if (rl != EXPANN_OK)
 				return rl;
 			kname = kGemmI8F.name;
-			gp.n_qtiles = (uint32_t)((m + kF16TQ - 1) / kF16TQ);
+			gemm_qtiles = (uint32_t)((m + kF16TQ - 1) / kF16TQ);
 		} else if (gvf) {
-			const int rl = launch_scan_f16(h, gvf, L.n_groups_sel * kRowsPerGroup, last, m, cus, ip, cap, st, &kname,
-			                               &gp.n_qtiles, &tq_small);
+			const int rl = launch_scan_f16(h, gvf, dv, L.n_groups_sel * kRowsPerGroup, last, m, cus, ip, cap, st, &kname,
+			                               &gemm_qtiles, &tq_small);
 			if (rl != EXPANN_OK)
 				return rl;
-		} else if (gvb) {
+		} else {  // (plan.float_gemm() without the fp16 form: bf16x3)
 			GemmBf16Params bp{};
 			bp.base_split = h->d_base_split;
 			bp.bnorm = h->d_bnorm_bf;
-			bp.n_rows = gp.n_rows;
-			bp.n_tiles_sel = gp.n_tiles_sel;
-			bp.tile_stride = gp.tile_stride;
+			bp.n_rows = (uint32_t)h->n;
+			const uint32_t n_tiles = (uint32_t)((h->n + kGemmTB - 1) / kGemmTB);
+			const uint32_t tiles_sel = last ? n_tiles : std::min(n_tiles, (L.n_groups_sel * kRowsPerGroup + kGemmTB - 1) / kGemmTB);
+			bp.n_tiles_sel = tiles_sel;
+			bp.tile_stride = std::max<uint32_t>(1, n_tiles / tiles_sel);
 			bp.tile_run = 1;
-			if (!last && gp.tile_stride >= 8) {
+			if (!last && bp.tile_stride >= 8 && tiles_sel >= 8) {
 				// sampled level: runs of 8 consecutive tiles (one 2 MiB page each at d=128)
 				// instead of isolated tiles, same number of tiles
 				bp.tile_run = 8;
-				bp.n_tiles_sel = (gp.n_tiles_sel / 8) * 8;
-				if (bp.n_tiles_sel == 0) {
-					bp.n_tiles_sel = gp.n_tiles_sel;
-					bp.tile_run = 1;
-				}
+				bp.n_tiles_sel = (tiles_sel / 8) * 8;
 			}
-			bp.tiles_per_block = gp.tiles_per_block;
-			bp.n_qtiles = gp.n_qtiles;
+			// One workgroup per CU is resident (128 KiB of LDS), so the launch runs in rounds
+			// of `cus` workgroups: pick the row-chunk count that minimises
+			// rounds x (steps per workgroup + ~2 steps of prologue).
+			uint32_t gchunks = pick_row_chunks(tiles_sel, gemm_qtiles, (uint32_t)cus, 2.0, 4, 1024, 0, nullptr);
+			bp.tiles_per_block = (tiles_sel + gchunks - 1) / gchunks;
+			gchunks = (tiles_sel + bp.tiles_per_block - 1) / bp.tiles_per_block;
+			bp.n_qtiles = gemm_qtiles;
 			bp.queries_split = h->d_q_split;
-			bp.theta = gp.theta;
-			bp.m = gp.m;
-			bp.cand_cnt = gp.cand_cnt;
-			bp.cand = gp.cand;
-			bp.cap = gp.cap;
+			bp.theta = h->d_theta;
+			bp.m = (uint32_t)m;
+			bp.cand_cnt = h->d_cnt;
+			bp.cand = h->d_cand;
+			bp.cap = cap;
 			bp.debug = (uint32_t)h->opt_debug;
-			hipLaunchKernelGGL(gvb->scan, dim3(gchunks * gp.n_qtiles), dim3(kGemmThreads),
+			hipLaunchKernelGGL(gvb->scan, dim3(gchunks * gemm_qtiles), dim3(kGemmThreads),
 			                   2 * kGemmTB * h->dim * sizeof(float), st, bp);
 			kname = gvb->name;
-		} else {
-			return h->fail(EXPANN_ERR_UNSUPPORTED, "no GEMM-form scan kernel for this index");  // (choose_kernels rules it out)
 		}
-		passes = gp.n_qtiles;
+		passes = gemm_qtiles;
 		qt_used = tq_small ? tq_small : tq_wg;  // (launch_scan_f16 reports the tile it used)
 	} else if (gvi && !first) {
 		hipLaunchKernelGGL(gvi->theta, dim3((uint32_t)((m + kRowsPerGroup - 1) / kRowsPerGroup)),
@@ -2601,9 +2444,7 @@ int SearchPass::run_level(size_t li) {
 	// (inner product, fp16 form only: the approximate key is off by at most E_q + E_b in
 	// total, half the L2 margins)
 	const float pr = ip ? 1.0f : 2.0f;
-	sel.prune_eps = use_gemm ? (gvf ? pr * gemm_f16_filter_eps(h->dim)
-	                                : (gvb ? gemm_bf16_filter_eps(h->dim) : gemm_filter_eps(h->dim)))
-	                         : 0.0f;
+	sel.prune_eps = use_gemm ? (gvf ? pr * gemm_f16_filter_eps(h->dim) : gemm_bf16_filter_eps(h->dim)) : 0.0f;
 	sel.prune_abs = (use_gemm && gvf)
 	                    ? pr * std::ldexp(1.0f, -24) / h->f16_scale * std::sqrt((float)h->dim)
 	                    : 0.0f;
@@ -2861,7 +2702,7 @@ int SearchPass::check(int attempt, Next* next) {
 		float qmax;  // bit pattern of max |q| (flags word 2, read back with the overflow flags)
 		std::memcpy(&qmax, &h->h_flags[2], sizeof(float));
 		if (!(qmax * h->f16_scale <= 60000.0f)) {
-			no_f16 = true;
+			learned.no_f16 = true;
 			h->prof.retries++;
 			*next = kRestart;
 			return EXPANN_OK;
@@ -2885,7 +2726,7 @@ int SearchPass::check(int attempt, Next* next) {
 	}
 	h->prof.retries++;
 	if (spec_j) {  // (whatever overflowed: no speculation from here on)
-		spec_off = true;
+		learned.spec_off = true;
 		if (redo_word >= kRedoOverflowUnit)
 			h->stat_redo_overflows++;
 		if (h->h_flags[0] == 0) {
@@ -2895,14 +2736,14 @@ int SearchPass::check(int attempt, Next* next) {
 	}
 	// some candidate list overflowed: retry with 4x the capacity
 	if (i8f_ran) {  // the int8 filter's lists: the retry runs the fp16 form at the same capacity
-		i8f_off = true;
+		learned.i8f_off = true;
 		*next = kRestart;
 		return EXPANN_OK;
 	}
 	// (a hit log of the 16x16x32 form that overflowed counts like a list: the logs grow with the lists)
-	if ((cap >= kMaxCap || attempt >= 3) && (gv || gvi) && h->opt_scan_kernel == 0) {
+	if ((cap >= kMaxCap || attempt >= 3) && plan.tie_fallback) {
 		// the GEMM forms cannot break exact ties by row number; the direct scan can
-		force_direct = true;
+		learned.force_direct = true;
 		*next = kRestart;
 		return EXPANN_OK;
 	}
@@ -2956,9 +2797,9 @@ int search_pass(expann_index* h, const void* d_queries, size_t m, size_t k, uint
 			HIP_TRY(h, hipStreamSynchronize(st));
 		return EXPANN_OK;
 	}
-	// (the uint8 shadow is a second handle that knows nothing of a row filter)
-	if (h->dtype == EXPANN_DTYPE_F32 && !ip && h->opt_scan_kernel == 0 && h->opt_u8_exact && !h->filter_on &&
-	    (h->dim == 128 || h->dim == 256) && m >= 96 && h->n >= 65536 && k <= 256 && h->u8_exact >= 0) {
+	uint32_t cap = plan_start_cap(h->opt_cand_capacity, k, kMaxCap);
+	const ScanPlan plan = plan_scan(plan_index(h), PlanCall{m, k, cap}, PlanAttempt{});
+	if (plan.u8_shadow) {
 		// rows that are all integers in [0, 255] (SIFT): with integer queries the uint8 engine's
 		// exact integer scores ARE the fp32 scores (d * 255^2 < 2^24: every partial sum of the
 		// reference is an exactly represented integer), at the 8-bit kernels' speed
@@ -2978,12 +2819,10 @@ int search_pass(expann_index* h, const void* d_queries, size_t m, size_t k, uint
 	}
 	ScanSel svs;
 	if (float_rows(h)) {
-		const ScanVariant* v = pick_scan_f32(h->dim, ip, m, h->opt_query_tile, f16_rows(h));
-		if (v)
+		if (const ScanVariant* v = find_scan_f32(h->dim, ip, plan.direct_tq, f16_rows(h)))
 			svs = ScanSel{v->fn, v->tq, v->name, v->fn_bits, v->fn_list};
 	} else {
-		const ScanI8Variant* v = pick_scan_i8(h->dim, h->int_mode, m, h->opt_query_tile);
-		if (v)
+		if (const ScanI8Variant* v = find_scan_i8(h->dim, h->int_mode, plan.direct_tq))
 			svs = ScanSel{v->fn, v->tq, v->name};
 	}
 	if (!svs.fn)
@@ -3005,16 +2844,10 @@ int search_pass(expann_index* h, const void* d_queries, size_t m, size_t k, uint
 		HIP_TRY(h, hipGetLastError());
 		d_queries = h->d_q8;
 	}
-	uint32_t cap = h->opt_cand_capacity > 0
-	                   ? (uint32_t)h->opt_cand_capacity
-	                   : pow2ceil((uint32_t)std::max<size_t>(2048, 64 * k));
-	cap = std::min(pow2ceil(cap), kMaxCap);
-	if (h->opt_cand_capacity > 0 && (size_t)cap < 2 * k)  // the option is a starting size, never below 2k
-		cap = std::min(pow2ceil((uint32_t)(2 * k)), kMaxCap);
 	if ((size_t)cap < 2 * k)
 		return h->fail(EXPANN_ERR_UNSUPPORTED, k_too_large());
 	const int cus = num_cus(h->device);
-	if (const GemmI8qVariant* gq = pick_gemm_i8q(h, m, k)) {
+	if (const GemmI8qVariant* gq = plan.i8q ? find_gemm_i8q(plan.i8q_family, h->dim, h->int_mode) : nullptr) {
 		const int rq = search_i8q(h, gq, d_queries, m, k, d_ids, d_dists, st, cap);
 		if (rq != kRetryGeneric)
 			return rq;
@@ -3103,8 +2936,16 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 		g_create_error = "device index out of range";
 		return EXPANN_ERR_INVALID_ARG;
 	}
-	if ((int_mode < 0 && !pick_scan_f32(dim, metric == EXPANN_METRIC_IP, 1, 0, dtype == EXPANN_DTYPE_F16)) ||
-	    (int_mode >= 0 && !pick_scan_i8(dim, int_mode, 1, 0))) {
+	PlanIndex px;
+	px.dtype = dtype;
+	px.int_mode = int_mode;
+	px.dim = dim;
+	static const bool tables_match = plan_tables_match();
+	if (!tables_match) {
+		g_create_error = "internal: bf_plan.hpp does not list the compiled scan kernels";
+		return EXPANN_ERR_UNSUPPORTED;
+	}
+	if (!direct_tile(px, 1)) {
 		g_create_error = "unsupported dim " + std::to_string(dim) +
 		                 " (built: f32 any multiple of 16 up to 4096; 8-bit any multiple of 64 up to 4096; int16 64,128)";
 		return EXPANN_ERR_UNSUPPORTED;
@@ -3229,19 +3070,8 @@ int expann_build(expann_index* h) {
 	std::vector<unsigned char>().swap(h->staging);
 	// the fp16 copy every fp32 search of a built dim filters through: made here, inside the
 	// reference's timed build span (basic_bench.h:63-71), not inside the first query
-	if (float_rows(h) && h->n >= 4096 && h->opt_scan_kernel == 0) {
-		for (const auto& v : kGemmF16X)
-			if (v.d == h->dim) {
-				const int rc = ensure_f16(h, &v, h->stream);
-				if (rc != EXPANN_OK)
-					return rc;
-			}
-		if (f16kl_dim(h->dim)) {
-			const int rc = ensure_f16(h, &kGemmF16KL, h->stream);
-			if (rc != EXPANN_OK)
-				return rc;
-		}
-	}
+	if (f16_copy_at_build(plan_index(h)))
+		return ensure_f16(h, find_f16(f16_geometry(h->dim), h->dim), h->stream);
 	return EXPANN_OK;
 }
 
@@ -3382,9 +3212,9 @@ int expann_search(expann_index* h, const void* queries, size_t m, size_t k, uint
 		// prep kernel reads them straight from pinned memory (and makes the device copy); otherwise
 		// one async copy
 		const void* dq = h->d_q;
-		if (float_rows(h) && h->d_base_f16 && h->f16_scale > 0.0f && h->opt_scan_kernel == 0 &&
-		    m <= (size_t)kRowsPerGroup && h->n >= 4096 && pick_gemm(h, m) != nullptr &&
-		    !(h->filter_on && h->n_allowed <= kMaxCap)) {  // (the list path runs no prep kernel)
+		// (a row filter's list path runs no prep kernel: planned with the longest lists, it is not an fp16 family)
+		if (h->d_base_f16 && h->f16_scale > 0.0f && h->opt_scan_kernel == 0 && m <= (size_t)kRowsPerGroup &&
+		    is_f16(plan_scan(plan_index(h), PlanCall{m, k, kMaxCap}, PlanAttempt{}).family)) {
 			h->q_in_pinned_host = true;
 			dq = pin;
 		} else {
@@ -4092,7 +3922,7 @@ int grouped_search_device(expann_index* h, const void* d_queries, const uint32_t
 // The threshold machine with the caller's radii as tau: no sampled pass, no threshold estimate.  A pass of its own
 // beside SearchPass, built from the same launch helpers; the plain and grouped searches launch what they did.
 //   stage 1  every query, lists of cap0 keys: the fp16 single-product form (its keys re-scored exactly by the range
-//            select) where pick_gemm gives one and the queries fit its range, else the exact direct scan
+//            select) where the plan (bf_plan.hpp) gives one and the queries fit its range, else the exact direct scan
 //   stage 2  the queries whose list did not fit, gathered, at kMaxCap keys: the fp16 form again where stage 1 ran it
 //            with shorter lists, then -- for what is left -- the exact direct scan, whose counter goes on counting, so
 //            the count is exact whatever it is, and the range select over exact keys
@@ -4174,29 +4004,25 @@ struct RangePass {
 	uint32_t* mid_list() const { return h->d_range.get() + 4 + m; }        // nor the fp16 form's at kMaxCap keys
 	uint32_t* big_list() const { return h->d_range.get() + 4 + 2 * m; }    // more than kMaxCap rows in range
 
-	const GemmF16Variant* f16_form(size_t mq) const;
-	int direct_scan(const void* d_q, size_t mq, uint32_t cap, const char** kname);
+	ScanPlan plan(size_t mq) const { return plan_scan(plan_index(h), PlanCall{mq, max_results, cap0}, PlanAttempt{}); }
+	const GemmF16Variant* f16_form(const ScanPlan& p) const;
+	int direct_scan(const void* d_q, size_t mq, int tq, uint32_t cap, const char** kname);
 	int filter_stage(bool want_f16, const uint32_t* list, size_t mq, uint32_t cap, int over_word, uint32_t* over_list,
 	                 uint32_t* n_over, bool* used_f16, bool* out_of_range);
 	int stage3();
 	int run();
 };
 
-// the fp16 single-product form that serves this index and a batch of mq queries, or nullptr: the exact direct scan
-// (pick_gemm's crossovers; never the bf16x3 form, whatever "scan_kernel" says)
-const GemmF16Variant* RangePass::f16_form(size_t mq) const {
-	if (!pick_gemm(h, mq) || !f16_choice(h->opt_scan_kernel))
-		return nullptr;
-	for (const auto& v : kGemmF16X)
-		if (v.d == h->dim)
-			return &v;
-	return f16kl_dim(h->dim) ? &kGemmF16KL : nullptr;
+// the fp16 single-product form of a stage's plan (that of a top-k search of as many queries), or nullptr: the exact
+// direct scan (never the bf16x3 form or the debug instance, whatever the options say)
+const GemmF16Variant* RangePass::f16_form(const ScanPlan& p) const {
+	return is_f16(p.family) ? find_f16(f16_geometry(h->dim), h->dim) : nullptr;
 }
 
 // the exact direct scan of every row for the mq queries at d_q: tau = h->d_tau[0], tau_row all ones (every row
-// that ties with the radius is in range), lists and counters in h->d_cand / h->d_cnt
-int RangePass::direct_scan(const void* d_q, size_t mq, uint32_t cap, const char** kname) {
-	const ScanVariant* v = pick_scan_f32(h->dim, ip, mq, h->opt_query_tile, f16_rows(h));
+// that ties with the radius is in range), lists and counters in h->d_cand / h->d_cnt; tq: the plan's query tile
+int RangePass::direct_scan(const void* d_q, size_t mq, int tq, uint32_t cap, const char** kname) {
+	const ScanVariant* v = find_scan_f32(h->dim, ip, tq, f16_rows(h));
 	if (!v)
 		return h->fail(EXPANN_ERR_UNSUPPORTED, "no scan kernel for dim " + std::to_string(h->dim) + " / query_tile " +
 		                                           std::to_string(h->opt_query_tile));
@@ -4216,9 +4042,7 @@ int RangePass::direct_scan(const void* d_q, size_t mq, uint32_t cap, const char*
 	sp.cand = h->d_cand;
 	sp.cap = cap;
 	sp.dim = (uint32_t)h->dim;
-	// ~16 workgroups per CU in total, at least 8 groups (128 rows) per workgroup (SearchPass::run_level)
-	const uint32_t target_chunks = (uint32_t)std::max<long>(1, (16L * cus + sp.n_qtiles - 1) / sp.n_qtiles);
-	uint32_t n_chunks = std::min(target_chunks, std::max<uint32_t>(1, sp.n_groups_sel / 8));
+	uint32_t n_chunks = direct_scan_chunks(sp.n_groups_sel, sp.n_qtiles, cus);
 	sp.groups_per_block = (sp.n_groups_sel + n_chunks - 1) / n_chunks;
 	n_chunks = (sp.n_groups_sel + sp.groups_per_block - 1) / sp.groups_per_block;
 	hipLaunchKernelGGL(v->fn, dim3(n_chunks * sp.n_qtiles), dim3(kBlock), 0, st, sp);
@@ -4235,7 +4059,8 @@ int RangePass::direct_scan(const void* d_q, size_t mq, uint32_t cap, const char*
 int RangePass::filter_stage(bool want_f16, const uint32_t* list, size_t mq, uint32_t cap, int over_word, uint32_t* over_list,
                             uint32_t* n_over, bool* used_f16, bool* out_of_range) {
 	*out_of_range = false;
-	const GemmF16Variant* gvf = want_f16 ? f16_form(mq) : nullptr;
+	const ScanPlan stage = plan(mq);
+	const GemmF16Variant* gvf = want_f16 ? f16_form(stage) : nullptr;
 	if (gvf) {
 		const int rc = ensure_f16(h, gvf, st);
 		if (rc != EXPANN_OK)
@@ -4281,7 +4106,8 @@ int RangePass::filter_stage(bool want_f16, const uint32_t* list, size_t mq, uint
 		HIP_TRY(h, hipMemsetAsync(h->d_cnt, 0, sizeof(uint32_t) * mq, st));
 		if (timed)
 			HIP_TRY(h, hipEventRecord(h->ev[h->ev_used][0], st));
-		rc = launch_scan_f16(h, gvf, (uint32_t)h->n, true, mq, cus, ip, cap, st, &kname, &passes, &qt_used);
+		rc = launch_scan_f16(h, gvf, find_direct_f16(h->dim, stage.direct_f16_tq), (uint32_t)h->n, true, mq, cus, ip, cap, st,
+		                     &kname, &passes, &qt_used);
 		if (rc != EXPANN_OK)
 			return rc;
 	} else {
@@ -4290,7 +4116,7 @@ int RangePass::filter_stage(bool want_f16, const uint32_t* list, size_t mq, uint
 			HIP_TRY(h, hipMemcpyAsync(h->d_tau[0], d_radii, sizeof(float) * mq, hipMemcpyDeviceToDevice, st));
 		if (timed)
 			HIP_TRY(h, hipEventRecord(h->ev[h->ev_used][0], st));
-		rc = direct_scan(dq, mq, cap, &kname);
+		rc = direct_scan(dq, mq, stage.direct_tq, cap, &kname);
 		if (rc != EXPANN_OK)
 			return rc;
 	}
@@ -4406,7 +4232,7 @@ int RangePass::run() {
 	// direct scan of many queries is the slow one -- and the exact direct scan for what is left
 	for (size_t q0 = 0; rc == EXPANN_OK && q0 < n_retry; q0 += kRangeRetryChunk) {
 		const size_t R = std::min(kRangeRetryChunk, (size_t)n_retry - q0);
-		if (f16 && cap0 < kMaxCap && f16_form(R))
+		if (f16 && cap0 < kMaxCap && f16_form(plan(R)))
 			rc = filter_stage(true, retry_list() + q0, R, kMaxCap, 1, mid_list(), &n_mid, &unused, &far);
 		else
 			rc = filter_stage(false, retry_list() + q0, R, kMaxCap, 2, big_list(), &n_big, &unused, &far);

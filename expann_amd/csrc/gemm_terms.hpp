@@ -17,28 +17,7 @@ namespace expann {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kGemmTQ = 128;  // queries per workgroup
 constexpr int kGemmTB = 128;  // base rows per step
-
-__host__ __device__ inline float gemm_filter_eps(int d) {
-	return (float)(4 * d + 128) * 5.9604644775390625e-08f;  // (4d+128) * 2^-24
-}
-
-struct GemmScanParams {
-	const float* base;       // [n_rows][D]
-	const float* bnorm;      // [n_rows] ||b||^2 * (1 - eps)
-	uint32_t n_rows;
-	uint32_t n_tiles_sel;    // 128-row tiles this launch visits ...
-	uint32_t tile_stride;    // ... tile j of the launch is base tile j*tile_stride
-	uint32_t tiles_per_block;
-	uint32_t n_qtiles;
-	const float* queries;    // [m][D]
-	const float* theta;      // [m] tau_q - ||q||^2 (1 - eps)
-	uint32_t m;
-	uint32_t* cand_cnt;      // [m]
-	uint64_t* cand;          // [m][cap]; low 32 bits = row, high = ordered(approx score)
-	uint32_t cap;
-};
 
 // ||b||^2 (1-eps) per row; 16 lanes per row.
 template <int D>
