@@ -49,6 +49,7 @@ ABI_SYMBOLS = [
     "expann_set_row_groups", "expann_set_row_groups_device", "expann_clear_row_groups",
     "expann_search_grouped", "expann_search_grouped_device",
     "expann_range_search", "expann_range_search_device",
+    "expann_append", "expann_append_device", "expann_reserve",
 ]
 GROUP_ANY = 0xFFFFFFFF  # EXPANN_GROUP_ANY: the group a query names to search every row
 
@@ -327,6 +328,13 @@ def load():
         L.expann_range_search.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
         L.expann_range_search_device.restype = C.c_int
         L.expann_range_search_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
+    if hasattr(L, "expann_append"):  # (as above: an older build cannot append to a built index)
+        L.expann_append.restype = C.c_int
+        L.expann_append.argtypes = [vp, vp, sz]
+        L.expann_append_device.restype = C.c_int
+        L.expann_append_device.argtypes = [vp, vp, sz, vp]
+        L.expann_reserve.restype = C.c_int
+        L.expann_reserve.argtypes = [vp, sz]
     if hasattr(L, "expann_graph_create_f16"):  # (as above: an older build has no binary16 graph rows)
         L.expann_graph_create_f16.restype = C.c_int
         L.expann_graph_create_f16.argtypes = [C.c_int, C.c_int, vp, sz, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(vp)]

@@ -18,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "bf_append.hpp"
 #include "bf_options.hpp"
 #include "bf_plan.hpp"
 #include "host_common.hpp"
@@ -36,6 +37,7 @@
 #include "scan_int8_any.hpp"
 #include "filter_rows.hpp"
 #include "scan_groups.hpp"
+#include "append_rows.hpp"
 #include "score_ids.hpp"
 #include "select.hpp"
 #include "select_range.hpp"
@@ -89,6 +91,8 @@ struct Rows {
 	size_t n_staged = 0;
 	MaybeOwnedPtr d_base;
 	size_t n = 0;
+	size_t capacity = 0;  // rows the handle's own allocation holds (>= n: expann_reserve, expann_append); 0 for the caller's memory
+	size_t reserved = 0;  // expann_reserve before build(): expann_build allocates max(staged, reserved) rows
 	uint64_t id_offset = 0;
 };
 
@@ -104,17 +108,28 @@ struct U8Shadow {
 	std::unique_ptr<expann_index, HandleDeleter> u8_shadow;  // (reads d_base_u8: declared after it, so it goes first)
 };
 
-// copies and terms derived from the rows, built lazily, dead when the rows change
-struct RowCopies : U8Shadow {
+// The fp16 copy every fp32 / fp16 search filters through, built lazily: the one derived copy an append extends in
+// place (expann_append), so it is a group of its own.  Allocated for the base's capacity in whole tiles and
+// initialised as a whole (zero rows, NaN terms); the scans read [0, f16_n_pad) and nothing behind it.
+struct F16Copy {
+	// [2]: max ||b||^2 of the rows.  Slot [1] is the bf16x3 form's (max of d_bnorm_bf, OtherCopies), written whenever
+	// d_bnorm_bf is made.  INVARIANT: F16Copy is never forgotten while OtherCopies lives -- forget<F16Copy>() always
+	// follows forget<OtherCopies>() (or both go as RowCopies) --, so slot [1] never dies under a live d_bnorm_bf; the
+	// other way round is fine, ensure_bnorm_bf16 writes [1] again.
+	DevPtr<float> d_bnmax;
+	DevPtr<void> d_base_f16;         // [f16_rows_alloc][f16_ld] fp16 rows scaled by f16_scale (fp16 GEMM form)
+	DevPtr<float> d_bnorm_f16;       // [f16_rows_alloc] ||b||^2 (1-eps) - abs |b|
+	DevPtr<float> d_bns_f16;         // [f16_rows_alloc] ||b||^2 (1+eps) + abs |b|: the sampled pass's row term
+	float f16_scale = 0.0f;          // power of two (bf_append.hpp: f16_scale_for); 0 = not built, < 0 = the rows do not fit
+	float f16_maxabs = 0.0f;         // max |v| of the rows the copy holds: what the scale was chosen for
+	size_t f16_n_pad = 0;            // rows the scans read: n in whole tiles
+	size_t f16_tb = 0;               // ... of this many rows
+	size_t f16_rows_alloc = 0;       // rows allocated: the base's capacity in whole tiles
+};
+// every other copy and term derived from the rows, built lazily, dead when the rows change -- an append included
+struct OtherCopies : U8Shadow {
 	DevPtr<float> d_bnorm_bf;        // ||b||^2 (1-eps) per row with the bf16x3 slack, built lazily
-	DevPtr<float> d_bnmax;           // [1]: max of d_bnorm_bf ([2]: of the fp16 copy's norms)
-	float f16_bnmax = 0.0f;          // max ||b||^2 (host copy lives in d_bnmax[2])
 	DevPtr<void> d_base_split;       // [n][2][dim] bf16 hi/lo planes (bf16x3 GEMM form), lazily
-	DevPtr<void> d_base_f16;         // [n][dim] fp16 rows scaled by f16_scale (fp16 GEMM form), lazily
-	DevPtr<float> d_bnorm_f16;       // [n] ||b||^2 (1-eps) - abs |b|
-	DevPtr<float> d_bns_f16;         // [n] ||b||^2 (1+eps) + abs |b|: the sampled pass's row term
-	float f16_scale = 0.0f;          // power of two; 0 = not built
-	size_t f16_n_pad = 0;            // rows of the fp16 copy and of its row-term arrays (whole tiles)
 	// int8 filter of fp32 rows (scan_gemm_i8f.hpp), built lazily beside the fp16 copy (whose sampled pass
 	// gives its thresholds) and dropped with it
 	DevPtr<void> d_base_i8f;         // [n padded to 64][dim] int8
@@ -128,6 +143,8 @@ struct RowCopies : U8Shadow {
 	MaybeOwnedPtr d_base_i8q;        // padded int8 copy of an 8-bit index (uint8 rows ^ 0x80) or alias of d_base
 	DevPtr<int> d_bp_i8q;            // [n padded] floor(bias/2), scan_gemm_i8q.hpp
 };
+// all that is derived from the rows: forgotten together when the rows are replaced
+struct RowCopies : F16Copy, OtherCopies {};
 
 // row filter (expann_set_row_filter): the engine's copy of the bitmap, the allowed rows'
 // count, an ascending list of them (complete up to kFilterListCap rows, an even sample beyond) and the masked
@@ -221,6 +238,7 @@ struct Workspace {
 	GrowPtr<float> d_range_radii;
 	GrowPtr<uint32_t> d_range_counts;
 	bool range_lds_set = false;      // the range select's 1 024-thread instances have their LDS limit raised
+	DevPtr<uint32_t> d_append_flag;  // [4]: [0] bit pattern of max |v| of an append's rows; [2..3] the 64-bit "copies_digest"
 };
 
 // the counters expann_get_stat reads (kStatTable)
@@ -233,6 +251,9 @@ struct Stats {
 	uint64_t stat_i8_sample = 0;     // 1: the last search's sampled pass ran on int8
 	uint64_t stat_group[5] = {0, 0, 0, 0, 0};  // the last grouped search: list, filter, any, pad queries; filter passes
 	uint64_t stat_range[3] = {0, 0, 0};  // the last range search: queries answered from a list, by the top-k pipeline; stage-1 retries
+	// expann_append since create: calls, rows, appends that extended the fp16 copy in place, appends that had to drop
+	// it (the scale changed), and reallocations of the base (expann_reserve's included)
+	uint64_t stat_append[5] = {0, 0, 0, 0, 0};
 };
 
 // streams, events, profiling, statistics, the last error
@@ -661,9 +682,18 @@ const DirectF16Variant* find_direct_f16(int d, int tq) {
 }
 
 // fp16 copy of the base (scaled by a power of two), its slack-adjusted norms, max norm
+int make_f16(expann_index* h, const GemmF16Variant* gf, hipStream_t st);
+// (a failure on the way leaves no half-made copy behind -- arrays without a scale or a tile size --: the derived
+// copies are forgotten as a whole and the next search starts over)
 int ensure_f16(expann_index* h, const GemmF16Variant* gf, hipStream_t st) {
 	if (h->d_base_f16 || h->f16_scale < 0.0f)
 		return EXPANN_OK;
+	const int rc = make_f16(h, gf, st);
+	if (rc != EXPANN_OK)
+		h->forget<RowCopies>();
+	return rc;
+}
+int make_f16(expann_index* h, const GemmF16Variant* gf, hipStream_t st) {
 	const size_t nv = h->n * (size_t)h->dim;
 	DevBuf tmp, nrm;
 	HIP_TRY(h, tmp.alloc(sizeof(float)));
@@ -679,26 +709,26 @@ int ensure_f16(expann_index* h, const GemmF16Variant* gf, hipStream_t st) {
 	float maxabs = 0.0f;  // (a NaN pattern stays a NaN and fails the range check below)
 	HIP_TRY(h, hipMemcpyAsync(&maxabs, tmp.p, sizeof(float), hipMemcpyDeviceToHost, st));
 	HIP_TRY(h, hipStreamSynchronize(st));
-	float scale = 1.0f;
-	if (maxabs > 0.0f && std::isfinite(maxabs)) {
-		int e = (int)std::floor(std::log2(32768.0 / (double)maxabs));
-		e = std::max(-40, std::min(40, e));  // s^2 and every scaled norm stay finite in fp32
-		scale = std::ldexp(1.0f, e);
-	}
-	if (!(maxabs * scale <= 32768.0f)) {  // non-finite or astronomically large values
+	const F16Scale fs = f16_scale_for(maxabs);  // (bf_append.hpp: the rule an append compares with)
+	const float scale = fs.scale;
+	h->f16_maxabs = maxabs;
+	if (!fs.usable) {  // non-finite or astronomically large values
 		h->f16_scale = -1.0f;
 		return EXPANN_OK;
 	}
-	// padded to whole tiles (64 rows; 128 for scan_gemm_kl): zero rows whose bn' is NaN (never a candidate)
+	// padded to whole tiles (64 rows; 128 for scan_gemm_kl): zero rows whose bn' is NaN (never a candidate).  The
+	// allocation covers the base's capacity (a base that was never reserved or appended to: its n rows), so that an
+	// append finds its tiles initialised; the scans read n_pad rows.
 	const size_t tb = (size_t)std::max(kF16TB, gf->tb);
 	const size_t n_pad = (h->n + tb - 1) / tb * tb;
+	const size_t n_alloc = (std::max(h->n, h->capacity) + tb - 1) / tb * tb;
 	const size_t ld = (size_t)f16_ld(h->dim);
-	HIP_TRY(h, hipMalloc(&h->d_base_f16, n_pad * ld * 2));
-	HIP_TRY(h, hipMalloc(&h->d_bnorm_f16, sizeof(float) * n_pad));
-	HIP_TRY(h, hipMalloc(&h->d_bns_f16, sizeof(float) * n_pad));
-	HIP_TRY(h, hipMemsetAsync(h->d_base_f16, 0, n_pad * ld * 2, st));
-	HIP_TRY(h, hipMemsetAsync(h->d_bnorm_f16, 0xFF, sizeof(float) * n_pad, st));  // 0xFFFFFFFF: a NaN
-	HIP_TRY(h, hipMemsetAsync(h->d_bns_f16, 0xFF, sizeof(float) * n_pad, st));
+	HIP_TRY(h, hipMalloc(&h->d_base_f16, n_alloc * ld * 2));
+	HIP_TRY(h, hipMalloc(&h->d_bnorm_f16, sizeof(float) * n_alloc));
+	HIP_TRY(h, hipMalloc(&h->d_bns_f16, sizeof(float) * n_alloc));
+	HIP_TRY(h, hipMemsetAsync(h->d_base_f16, 0, n_alloc * ld * 2, st));
+	HIP_TRY(h, hipMemsetAsync(h->d_bnorm_f16, 0xFF, sizeof(float) * n_alloc, st));  // 0xFFFFFFFF: a NaN
+	HIP_TRY(h, hipMemsetAsync(h->d_bns_f16, 0xFF, sizeof(float) * n_alloc, st));
 	if (!h->d_bnmax)
 		HIP_TRY(h, hipMalloc(&h->d_bnmax, 4 * sizeof(float)));
 	const uint32_t blocks16 = (uint32_t)((h->n + kRowsPerGroup - 1) / kRowsPerGroup);
@@ -733,6 +763,8 @@ int ensure_f16(expann_index* h, const GemmF16Variant* gf, hipStream_t st) {
 	HIP_TRY(h, hipStreamSynchronize(st));  // tmp/nrm are freed on return
 	h->f16_scale = scale;
 	h->f16_n_pad = n_pad;
+	h->f16_tb = tb;
+	h->f16_rows_alloc = n_alloc;
 	return EXPANN_OK;
 }
 
@@ -3063,8 +3095,10 @@ int expann_build(expann_index* h) {
 	drop_row_filter(h);
 	drop_row_groups(h);
 	void* rows = nullptr;
-	HIP_TRY(h, hipMalloc(&rows, h->staging.size()));
+	const size_t capacity = std::max(h->n_staged, h->reserved);  // (expann_reserve before build(): room for the appends to come)
+	HIP_TRY(h, hipMalloc(&rows, capacity * (size_t)h->dim * h->elem));
 	h->d_base.own(rows);
+	h->capacity = capacity;
 	HIP_TRY(h, hipMemcpy(h->d_base, h->staging.data(), h->staging.size(), hipMemcpyHostToDevice));
 	h->n = h->n_staged;
 	std::vector<unsigned char>().swap(h->staging);
@@ -3089,11 +3123,243 @@ int expann_set_base_device(expann_index* h, const void* d_rows, size_t n, uint64
 	drop_row_groups(h);
 	h->d_base.borrow(d_rows);
 	h->n = n;
+	h->capacity = 0;
 	h->id_offset = id_offset;
 	return EXPANN_OK;
 }
 
 size_t expann_size(const expann_index* h) { return h ? (h->d_base ? h->n : h->n_staged) : 0; }
+
+// ---- append -----------------------------------------------------------------
+extern "C++" {
+namespace {
+// what bf_append.hpp's plans read of a handle
+AppendState append_state(const expann_index* h, bool have_rows) {
+	AppendState s;
+	s.have_rows = have_rows;
+	s.on_device = (bool)h->d_base;
+	s.owned = (bool)h->d_base.mine;
+	s.float_rows = float_rows(h);
+	s.n = h->n;
+	s.capacity = h->capacity;
+	s.f16_scale = h->d_base_f16 || h->f16_scale < 0.0f ? h->f16_scale : 0.0f;
+	s.maxabs = h->f16_maxabs;
+	return s;
+}
+
+// every stream that may still read the rows or their copies has drained (the row filter's rule)
+int append_wait(expann_index* h) {
+	if (h->async_pending > 0)
+		HIP_TRY(h, hipStreamSynchronize(h->async_stream));
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
+	return EXPANN_OK;
+}
+
+// A base of `capacity` rows that holds the handle's rows, and -- where an fp16 copy exists and is shorter than
+// `f16_rows` rows -- a copy of that many rows initialised as ensure_f16 initialises one and holding the current
+// [0, f16_n_pad): built ASIDE in the order of `st`, while the old allocations stay live, and swapped in by commit()
+// once everything has succeeded.  A call that fails on the way frees what it built and leaves the handle as it was.
+struct GrownRows {
+	DevPtr<void> base;
+	DevPtr<void> f16;
+	DevPtr<float> bnorm, bns;
+	size_t capacity = 0, f16_rows = 0;
+
+	int build(expann_index* h, size_t new_capacity, hipStream_t st) {
+		const size_t row_bytes = (size_t)h->dim * h->elem;
+		if (new_capacity > h->capacity) {
+			HIP_TRY(h, hipMalloc(&base, new_capacity * row_bytes));
+			HIP_TRY(h, hipMemcpyAsync(base, h->d_base, h->n * row_bytes, hipMemcpyDeviceToDevice, st));
+			capacity = new_capacity;
+		}
+		const bool have_copy = h->d_base_f16 && h->f16_scale > 0.0f && h->f16_tb > 0;  // (a complete copy)
+		const size_t want = have_copy ? (new_capacity + h->f16_tb - 1) / h->f16_tb * h->f16_tb : 0;
+		if (want > h->f16_rows_alloc) {
+			const size_t ld2 = (size_t)f16_ld(h->dim) * 2;
+			HIP_TRY(h, hipMalloc(&f16, want * ld2));
+			HIP_TRY(h, hipMalloc(&bnorm, sizeof(float) * want));
+			HIP_TRY(h, hipMalloc(&bns, sizeof(float) * want));
+			const size_t keep = h->f16_n_pad;
+			HIP_TRY(h, hipMemcpyAsync(f16, h->d_base_f16, keep * ld2, hipMemcpyDeviceToDevice, st));
+			HIP_TRY(h, hipMemcpyAsync(bnorm, h->d_bnorm_f16, sizeof(float) * keep, hipMemcpyDeviceToDevice, st));
+			HIP_TRY(h, hipMemcpyAsync(bns, h->d_bns_f16, sizeof(float) * keep, hipMemcpyDeviceToDevice, st));
+			HIP_TRY(h, hipMemsetAsync(f16.as<char>() + keep * ld2, 0, (want - keep) * ld2, st));
+			HIP_TRY(h, hipMemsetAsync(bnorm + keep, 0xFF, sizeof(float) * (want - keep), st));  // 0xFFFFFFFF: a NaN
+			HIP_TRY(h, hipMemsetAsync(bns + keep, 0xFF, sizeof(float) * (want - keep), st));
+			f16_rows = want;
+		}
+		return EXPANN_OK;
+	}
+	// (after `st` has drained; keep_f16 = false: the copy is about to be dropped anyway)
+	// THE one place where a handle's base moves: whatever aliases the base is re-pointed here, next to the swap.
+	void commit(expann_index* h, bool keep_f16) {
+		if (base) {
+			h->d_base.own(std::exchange(base.p, nullptr));
+			h->capacity = capacity;
+			h->stat_append[4]++;
+			// an 8-bit index whose rows need neither padding nor mapping filters through the base itself
+			// (ensure_i8q): the alias follows the base; every other derived copy is memory of its own
+			if (h->d_base_i8q && !h->d_base_i8q.mine)
+				h->d_base_i8q.borrow(h->d_base);
+		}
+		if (f16 && keep_f16) {
+			h->d_base_f16 = std::move(f16);
+			h->d_bnorm_f16 = std::move(bnorm);
+			h->d_bns_f16 = std::move(bns);
+			h->f16_rows_alloc = f16_rows;
+		}
+	}
+};
+
+// "copies_digest": the fp16 copy as 64 bits (append_rows.hpp), 0 when there is none; computed on demand, with a host
+// wait, never on a search path
+uint64_t copies_digest(expann_index* h) {
+	if (!h->d_base_f16 || !(h->f16_scale > 0.0f))
+		return 0;
+	const auto run = [h](unsigned long long* out) {
+		HIP_TRY(h, hipSetDevice(h->device));
+		if (!h->d_append_flag)
+			HIP_TRY(h, hipMalloc(&h->d_append_flag, 4 * sizeof(uint32_t)));
+		unsigned long long* d_out = (unsigned long long*)(h->d_append_flag + 2);
+		HIP_TRY(h, hipMemsetAsync(d_out, 0, sizeof(*d_out), h->stream));
+		CopiesDigestParams dp;
+		dp.rows = h->d_base_f16.as<const uint32_t>();
+		dp.n_row_words = (uint64_t)h->f16_n_pad * (uint64_t)f16_ld(h->dim) / 2;
+		dp.bnorm = h->d_bnorm_f16.as<const uint32_t>();
+		dp.bns = h->d_bns_f16.as<const uint32_t>();
+		dp.n_pad = h->f16_n_pad;
+		dp.bnmax = h->d_bnmax.as<const uint32_t>() + 2;
+		dp.scale_bits = __builtin_bit_cast(uint32_t, h->f16_scale);
+		dp.out = d_out;
+		const uint64_t total = dp.n_row_words + 2 * dp.n_pad;
+		hipLaunchKernelGGL(copies_digest_kernel, dim3((uint32_t)std::min<uint64_t>((total + kBlock - 1) / kBlock, 4096)),
+		                   dim3(kBlock), 0, h->stream, dp);
+		HIP_TRY(h, hipGetLastError());
+		HIP_TRY(h, hipMemcpyAsync(out, d_out, sizeof(*out), hipMemcpyDeviceToHost, h->stream));
+		HIP_TRY(h, hipStreamSynchronize(h->stream));
+		return (int)EXPANN_OK;
+	};
+	unsigned long long v = 0;
+	return run(&v) == EXPANN_OK ? (uint64_t)v : 0;
+}
+
+// rows: n_new of them in host (on_device = false) or device memory, read in the order of `user_st`
+int append_rows(expann_index* h, const void* rows, size_t n_new, bool on_device, hipStream_t user_st) {
+	if (!h)
+		return EXPANN_ERR_INVALID_ARG;
+	const AppendState state = append_state(h, rows != nullptr);
+	AppendPlan plan = plan_append(state, n_new, 0.0f);  // (the status and the capacity: no device call before them)
+	if (plan.status != EXPANN_OK)
+		return h->fail(plan.status, plan.message);
+	h->stat_append[0]++;
+	if (n_new == 0)
+		return EXPANN_OK;
+	HIP_TRY(h, hipSetDevice(h->device));
+	if (const int rc = append_wait(h))
+		return rc;
+	hipStream_t st = user_st ? user_st : h->stream;
+	const size_t row_bytes = (size_t)h->dim * h->elem;
+	const bool have_copy = state.float_rows && state.f16_scale > 0.0f;
+	GrownRows grown;
+	if (const int rc = grown.build(h, plan.capacity, st))
+		return rc;
+	// the new rows: to the tail of the base
+	char* const tail = (grown.base ? grown.base.as<char>() : (char*)h->d_base) + h->n * row_bytes;
+	HIP_TRY(h, hipMemcpyAsync(tail, rows, n_new * row_bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+	// ... and, converted with the current scale, to the tail of the fp16 copy: one launch, which also reports max |v|
+	float maxabs_new = 0.0f;
+	if (have_copy) {
+		if (!h->d_append_flag)
+			HIP_TRY(h, hipMalloc(&h->d_append_flag, 4 * sizeof(uint32_t)));
+		HIP_TRY(h, hipMemsetAsync(h->d_append_flag, 0, sizeof(uint32_t), st));
+		const size_t ld = (size_t)f16_ld(h->dim);
+		AppendRowsParams ap;
+		ap.rows = tail;
+		ap.n_new = (uint32_t)n_new;
+		ap.d = (uint32_t)h->dim;
+		ap.ld = (uint32_t)ld;
+		ap.scale = h->f16_scale;
+		ap.out = (grown.f16 ? grown.f16.as<_Float16>() : h->d_base_f16.as<_Float16>()) + h->n * ld;
+		ap.bnorm = (grown.f16 ? grown.bnorm.p : h->d_bnorm_f16.p) + h->n;
+		ap.bns = (grown.f16 ? grown.bns.p : h->d_bns_f16.p) + h->n;
+		ap.eps = gemm_f16_filter_eps(h->dim);
+		ap.abs_coef = std::ldexp(1.0f, -24) / h->f16_scale * std::sqrt((float)h->dim);
+		ap.mul = 0.5f * h->f16_scale * h->f16_scale;
+		ap.ip = h->metric == EXPANN_METRIC_IP ? 1 : 0;
+		ap.bnmax_bits = h->d_bnmax.as<uint32_t>() + 2;
+		ap.maxabs_bits = h->d_append_flag;
+		const dim3 grid((uint32_t)((n_new + kRowsPerGroup - 1) / kRowsPerGroup));
+		if (f16_rows(h))
+			hipLaunchKernelGGL(append_f16_rows_kernel<_Float16>, grid, dim3(kBlock), 0, st, ap);
+		else
+			hipLaunchKernelGGL(append_f16_rows_kernel<float>, grid, dim3(kBlock), 0, st, ap);
+	}
+	// the one host wait of an append.  A failure behind the launch may have left terms of rows the handle does not
+	// count in the live arrays: the derived copies are forgotten, the rows themselves are as they were.
+	hipError_t e = have_copy ? hipGetLastError() : hipSuccess;
+	if (e == hipSuccess && have_copy)
+		e = hipMemcpyAsync(&maxabs_new, h->d_append_flag, sizeof(float), hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess)
+		e = hipStreamSynchronize(st);
+	if (e != hipSuccess) {
+		if (have_copy)
+			h->forget<RowCopies>();
+		return h->fail(EXPANN_ERR_HIP, std::string("append: ") + hipGetErrorString(e));
+	}
+	plan = plan_append(state, n_new, maxabs_new);
+	// the rows are in: everything that described the shorter index goes
+	grown.commit(h, plan.copies == CopyAction::kExtend);
+	h->n = plan.n;
+	h->stat_append[1] += n_new;
+	h->forget<OtherCopies>();
+	drop_row_filter(h);
+	drop_row_groups(h);
+	if (plan.copies == CopyAction::kExtend) {
+		h->f16_n_pad = (plan.n + h->f16_tb - 1) / h->f16_tb * h->f16_tb;
+		h->f16_maxabs = maxabs_of(state.maxabs, maxabs_new);
+		h->stat_append[2]++;
+	} else if (plan.copies == CopyAction::kDrop) {
+		// the scale changed: the speculative rows die with the copy, which is made again now where a build makes it.
+		// The rows are in, so the append has succeeded whatever becomes of the copy: if it cannot be made now,
+		// what is left of the attempt goes and the next search makes it, and reports what fails then.
+		h->forget<F16Copy>();  // (d_bnmax[1] goes with it: OtherCopies, which owns that slot, is forgotten already)
+		h->stat_append[3]++;
+		if (f16_copy_at_build(plan_index(h)))
+			(void)ensure_f16(h, find_f16(f16_geometry(h->dim), h->dim), h->stream);  // (forgets what it began when it fails)
+	}
+	return EXPANN_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int expann_append(expann_index* h, const void* rows, size_t n) { return append_rows(h, rows, n, false, nullptr); }
+
+int expann_append_device(expann_index* h, const void* d_rows, size_t n, void* stream) {
+	return append_rows(h, d_rows, n, true, (hipStream_t)stream);
+}
+
+int expann_reserve(expann_index* h, size_t n_rows) {
+	if (!h)
+		return EXPANN_ERR_INVALID_ARG;
+	const AppendPlan plan = plan_reserve(append_state(h, true), n_rows);
+	if (plan.status != EXPANN_OK)
+		return h->fail(plan.status, plan.message);
+	if (!h->d_base) {  // remembered for expann_build
+		h->reserved = std::max(h->reserved, n_rows);
+		return EXPANN_OK;
+	}
+	if (!plan.realloc)
+		return EXPANN_OK;
+	HIP_TRY(h, hipSetDevice(h->device));
+	if (const int rc = append_wait(h))
+		return rc;
+	GrownRows grown;
+	if (const int rc = grown.build(h, plan.capacity, h->stream))
+		return rc;
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
+	grown.commit(h, true);
+	return EXPANN_OK;
+}
 
 int expann_search_device(expann_index* h, const void* d_queries, size_t m, size_t k,
                          uint64_t* d_ids, float* d_dists, void* stream) {
@@ -3457,6 +3723,13 @@ int expann_get_stat(expann_index* h, const char* name, uint64_t* out) {
 	    {"range_list_queries", [](H h) { return h->stat_range[0]; }},
 	    {"range_topk_queries", [](H h) { return h->stat_range[1]; }},
 	    {"range_retries", [](H h) { return h->stat_range[2]; }},
+	    {"append_calls", [](H h) { return h->stat_append[0]; }},
+	    {"append_rows", [](H h) { return h->stat_append[1]; }},
+	    {"append_extends", [](H h) { return h->stat_append[2]; }},
+	    {"append_rebuilds", [](H h) { return h->stat_append[3]; }},
+	    {"base_reallocs", [](H h) { return h->stat_append[4]; }},
+	    {"base_capacity_rows", [](H h) -> uint64_t { return h->d_base ? h->capacity : h->reserved; }},
+	    {"copies_digest", [](H h) { return copies_digest(const_cast<expann_index*>(h)); }},
 	};
 	for (const auto& s : kStatTable)
 		if (!std::strcmp(name, s.name)) {

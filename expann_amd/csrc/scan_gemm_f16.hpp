@@ -297,7 +297,24 @@ __global__ __launch_bounds__(kBlock) void f16_query_prep_any_kernel(const float*
 	}
 }
 
-// rows:    out = (nrm*(1-eps) - abs*sqrt(nrm)) * mul                (tau == nullptr)
+// The row term of a row with ||b||^2 = v (the formulas: f16_terms_kernel's comment below): what a build writes
+// (f16_terms_kernel, tau == nullptr) and what an append writes for a new row (append_rows.hpp) -- one function, so
+// that an extended array holds the bits a fresh build computes.  Its roundings are spelled out, because contraction
+// into an FMA is otherwise decided per call site and the two kernels differed in the last bit.  They are the ones
+// f16_terms_kernel's row branch compiled to before the function existed, so a build writes the row terms it always
+// wrote: L2 rounds every operation on its own (v_pk_mul_f32 of both products, v_sub_f32); the inner product fuses
+// eps v into the sum, e = fma(v, eps, abs sqrt(v)) (v_mul_f32, v_fmac_f32, then the sign flip).
+__device__ __attribute__((always_inline)) inline float f16_row_term(float v, float eps, float abs_coef, float mul, int ip) {
+#pragma clang fp contract(off)
+	if (ip) {
+		const float e = __builtin_fmaf(v, eps, abs_coef * __builtin_sqrtf(v));
+		return -e * mul;
+	}
+	const float t = v * (1.0f - eps) - abs_coef * __builtin_sqrtf(v);
+	return t * mul;
+}
+
+// rows:    out = (nrm*(1-eps) - abs*sqrt(nrm)) * mul                (tau == nullptr: f16_row_term)
 // queries: out = (tau - (nrm*(1-eps) - abs*sqrt(nrm))) * mul
 // mul = s^2/2, a power of two: the scaling is exact
 // (eps, abs_coef negated: the UPPER row term (nrm*(1+eps) + abs*sqrt(nrm)) * mul of the sampled pass)
@@ -315,13 +332,17 @@ __global__ __launch_bounds__(kBlock) void f16_terms_kernel(const float* nrm, uin
 	if (i >= n)
 		return;
 	const float v = nrm[i];
+	if (!tau) {
+		out[i] = f16_row_term(v, eps, abs_coef, mul, ip);
+		return;
+	}
 	if (ip) {
 		const float e = v * eps + abs_coef * __builtin_sqrtf(v);
-		out[i] = (tau ? 2.0f * tau[i] * (qscale ? qscale[i] : 1.0f) + e : -e) * mul;
+		out[i] = (2.0f * tau[i] * (qscale ? qscale[i] : 1.0f) + e) * mul;
 		return;
 	}
 	const float t = v * (1.0f - eps) - abs_coef * __builtin_sqrtf(v);
-	out[i] = (tau ? tau[i] - t : t) * mul;
+	out[i] = (tau[i] - t) * mul;
 }
 
 struct GemmF16Params {

@@ -50,6 +50,7 @@ class GpuBruteForceEngine:
         rc = self._L.expann_create(self.dim, self.dtype, self.metric, self.device, C.byref(h))
         _lib.check(None, rc)
         self._h = h
+        self._built = False
 
     # ---- the reference interface (src/ann_engine.h:16-29) ---------------------------
     def name(self):
@@ -63,14 +64,37 @@ class GpuBruteForceEngine:
         self.store_many_vectors(np.asarray(v).reshape(1, -1))
 
     def store_many_vectors(self, rows):
+        """Before build(): expann_add.  After build(): expann_append -- the reference's engine has no frozen state
+        (store, build, query, store, query), and neither has this one."""
         rows = np.ascontiguousarray(rows, dtype=_NP_DTYPE[self.dtype])
         if rows.ndim != 2 or rows.shape[1] != self.dim:
             raise ValueError(f"rows must be [n, {self.dim}]")
-        _lib.check(self._h, self._L.expann_add(self._h, rows.ctypes.data, rows.shape[0]))
+        call = self._L.expann_append if self._built else self._L.expann_add
+        _lib.check(self._h, call(self._h, rows.ctypes.data, rows.shape[0]))
 
     def build(self):
         """src/brute_force_engine.h:24-26 (asserts a non-empty index): upload to HBM."""
         _lib.check(self._h, self._L.expann_build(self._h))
+        self._built = True
+
+    def append(self, rows):
+        """expann_append: rows [n, dim] to a built index.  The new rows get the ids size() + i, and every search
+        answers as a freshly built index of all the rows does, bit for bit.  A row filter and row groups are
+        cleared (they describe the rows they were set for)."""
+        rows = np.ascontiguousarray(rows, dtype=_NP_DTYPE[self.dtype])
+        if rows.ndim != 2 or rows.shape[1] != self.dim:
+            raise ValueError(f"rows must be [n, {self.dim}]")
+        _lib.check(self._h, self._L.expann_append(self._h, rows.ctypes.data, rows.shape[0]))
+
+    def append_device(self, ptr, n, stream=0):
+        """expann_append_device: n rows of the index's dtype in device memory, read in the order of `stream` and
+        copied; returns when the index holds them."""
+        _lib.check(self._h, self._L.expann_append_device(self._h, C.c_void_p(ptr), int(n), C.c_void_p(stream)))
+
+    def reserve(self, n):
+        """expann_reserve: room for at least n rows, so that appends up to there do not reallocate the base.
+        Before build() the value is remembered for build()."""
+        _lib.check(self._h, self._L.expann_reserve(self._h, int(n)))
 
     def query_k(self, v, k):
         """src/brute_force_engine.h:28-46: ids of the min(k, n) nearest rows, ascending."""
@@ -219,7 +243,10 @@ class GpuBruteForceEngine:
         "base_bytes" (device bytes of the rows themselves: n * dim * element size);
         "groups_active", "group_count", and of the last grouped search "group_list_queries", "group_filter_queries",
         "group_any_queries", "group_pad_queries", "group_filter_passes";
-        of the last range search "range_list_queries", "range_topk_queries", "range_retries"."""
+        of the last range search "range_list_queries", "range_topk_queries", "range_retries";
+        "append_calls", "append_rows", "append_extends", "append_rebuilds", "base_capacity_rows", "base_reallocs" and
+        "copies_digest" (a digest of the fp16 copy: equal on an appended and on a freshly built index of the same
+        rows; 0 without a copy)."""
         v = C.c_uint64(0)
         _lib.check(self._h, self._L.expann_get_stat(self._h, name.encode(), C.byref(v)))
         return int(v.value)

@@ -65,6 +65,10 @@ struct gpu_brute_force_engine : public ann_engine<T, gpu_brute_force_engine<T>> 
 	expann_sharded* sharded = nullptr;  // conf.devices.size() > 1
 	size_t dimension = 0;
 	size_t stored = 0;
+	// the reference's engine has no frozen state (src/brute_force_engine.h:20-46): rows stored after _build() are
+	// appended to the built index (expann_append) and get the next ids; the sharded form refuses them
+	bool built = false;
+	size_t reserve_rows = 0;  // reserve() before the first row
 
 	gpu_brute_force_engine() = default;
 	explicit gpu_brute_force_engine(config c) : conf(c) {}
@@ -97,6 +101,18 @@ struct gpu_brute_force_engine : public ann_engine<T, gpu_brute_force_engine<T>> 
 		if (!opened())
 			throw std::runtime_error("gpu_brute_force_engine: build() on an empty index");
 		check(sharded ? expann_sharded_build(sharded) : expann_build(handle));
+		built = true;
+	}
+	// Extension: room for at least n rows (expann_reserve), so that rows stored after build() up to there do not
+	// reallocate the base.  Before the first row there is no handle yet: the value is passed on when it is made.
+	void reserve(size_t n) {
+		if (sharded)
+			throw std::runtime_error("gpu_brute_force_engine: reserve: the sharded engine does not grow");
+		if (!handle) {
+			reserve_rows = n;
+			return;
+		}
+		check(expann_reserve(handle, n));
 	}
 	std::vector<size_t> _query_k(const vec<T>& v, size_t k) {
 		std::vector<T> q(dimension);
@@ -183,7 +199,8 @@ private:
 		                                         : EXPANN_DTYPE_I16;
 	}
 	bool opened() const { return handle || sharded; }
-	// n rows of `dimension` elements to the library: as they are, or rounded to binary16 (config::rows_f16)
+	// n rows of `dimension` elements to the library -- staged before _build(), appended after it --: as they are, or
+	// rounded to binary16 (config::rows_f16)
 	void add_rows(const T* rows, size_t n) {
 		const void* src = rows;
 		std::vector<uint16_t> half;
@@ -193,7 +210,10 @@ private:
 				half[i] = expann::f32_to_f16_bits(float(rows[i]));
 			src = half.data();
 		}
-		check(sharded ? expann_sharded_add(sharded, src, n) : expann_add(handle, src, n));
+		if (sharded)
+			check(expann_sharded_add(sharded, src, n));
+		else
+			check(built ? expann_append(handle, src, n) : expann_add(handle, src, n));
 	}
 	// the row filter's entry points: a built single-device engine
 	void single(const char* what) const {
@@ -219,6 +239,8 @@ private:
 			throw std::runtime_error(std::string("expann_create: ") + expann_last_error(nullptr));
 		if (conf.query_tile)
 			check(expann_set_option(handle, "query_tile", conf.query_tile));
+		if (reserve_rows)
+			check(expann_reserve(handle, reserve_rows));
 	}
 	void check(int rc) {
 		if (rc != EXPANN_OK)

@@ -818,6 +818,67 @@ int expann_range_search_device(expann_index* h, const void* d_queries, const flo
                                size_t max_results, uint64_t* d_ids, float* d_dists, uint32_t* d_counts,
                                void* stream);
 
+/* Append rows to a built brute-force index (appended; EXPANN_ABI_VERSION stays 2: nothing that existed changed --
+ * expann_add on a built handle still fails with "index already built").  The reference's brute_force_engine has no
+ * frozen state (src/brute_force_engine.h:20-46: store, build, query, store, query works); these calls give a built
+ * handle the same, without destroying it and staging, uploading and deriving every row again.
+ * THE APPEND RULE.  After expann_append(h, R, r) on a handle that held the rows B -- R in the index's dtype and
+ * layout, [r][dim] -- the new rows have the ids expann_size(h) + i (before the call), in insertion order, and EVERY
+ * entry point returns, bit for bit, what a fresh handle made by expann_add(B), expann_add(R), expann_build with the
+ * same options returns: ids, fp32 distance bits, ties by lower id, padding and counts -- expann_search and
+ * expann_search_device (latency mode, "async_search" with expann_sync, k up to 8192), expann_score_ids (ids of
+ * appended rows are valid), expann_range_search*, and the filter and group calls issued afterwards.  The exact top-k
+ * by (score, id) is unique, so how the derived copies were brought up to date never shows in an answer.
+ * What survives: the options, the profiling state, the statistics and the workspace.  What does not: a row filter
+ * and row groups are CLEARED, as expann_build clears them -- they describe the rows they were set for; the caller
+ * sets them again for the longer index.
+ * All three calls first wait on the host for outstanding deferred searches (the row filter's rule), so every
+ * search runs over the rows that were there when it was enqueued.  Both append calls return after the rows and the
+ * copies are complete: one host wait per append, none per search.  expann_append_device reads d_rows in the order
+ * of `stream` (a hipStream_t; NULL = the handle's own) and copies them: the caller may free them on return.
+ * Errors, in this order, all before the device is touched: h == NULL EXPANN_ERR_INVALID_ARG; rows == NULL with
+ * n > 0 EXPANN_ERR_INVALID_ARG; no rows on the device yet EXPANN_ERR_NOT_BUILT (before build() the call is
+ * expann_add's job); rows adopted by expann_set_base_device EXPANN_ERR_UNSUPPORTED (they are the caller's memory);
+ * n + expann_size(h) >= 2^32 - 32 EXPANN_ERR_UNSUPPORTED.  n == 0 is EXPANN_OK and does nothing.  A failed call
+ * leaves the handle as it was and usable -- a failed allocation too: the larger base is built aside and swapped in.
+ * CAPACITY.  expann_reserve(h, n_rows) makes room for at least n_rows rows: on a built handle that owns its rows it
+ * reallocates now; before expann_build it is remembered and expann_build allocates max(staged, reserved) rows; a
+ * value at or below the current capacity is EXPANN_OK and does nothing; on adopted rows EXPANN_ERR_UNSUPPORTED.
+ * A reserve adds no rows, so it clears nothing: the filter, the groups and every derived copy stay (the fp16 copy
+ * moves to a larger allocation with the base; what reads the base itself follows it to the new one).
+ * Without a reserve, an append that does not fit grows the capacity by HALF (x 1.5, at least to what is needed), so a
+ * run of appends copies O(total rows), at most three times the final size.  While a base is being grown the old
+ * and the new allocation are both live (up to 2.5 x the old base, and the same for the fp16 copy beside it).  An
+ * index that is never reserved or appended to allocates exactly what it allocated before these calls existed.
+ * THE COPIES (csrc/bf_append.hpp is the one list of the rules, csrc/append_rows.hpp the device side).  The scaled
+ * fp16 copy that every fp32 / fp16 search filters through, its two row-term arrays and max ||b||^2 are EXTENDED IN
+ * PLACE by one kernel launch over the new rows when the scale of the longer index -- 2^floor(log2(32768 / max |v|)) --
+ * is the current one; the extended arrays hold the bits a fresh build writes.  When the new rows raise max |v| past
+ * a power of two, the copy is dropped and made again (at once where expann_build would make it, else by the next
+ * search; the rows are in by then, so the append is EXPANN_OK even if that rebuild cannot be done now -- the next
+ * search tries again and reports it).  Every other derived copy -- the uint8 shadow, the bf16x3 planes, the int8 filter's set, the 8-bit
+ * indexes' row terms -- is dropped by every append and rebuilt by its next use.
+ * expann_get_stat: "append_calls" and "append_rows" (accepted calls and their rows since create), "append_extends"
+ * (appends that extended the fp16 copy in place), "append_rebuilds" (appends that had to drop it: the scale
+ * changed), "base_capacity_rows" (rows the handle's own base allocation holds; before build() the reserved value;
+ * 0 for adopted rows), "base_reallocs" (reallocations of the base since create, expann_reserve's included),
+ * "copies_digest" (a 64-bit digest, independent of summation order, of the fp16 copy's rows and row terms over the
+ * whole tiles the scans read, max ||b||^2 and the scale; 0 when there is no copy; computed on demand with a host wait,
+ * never on a search path.  Results are exact whatever the copy holds, so only the digest shows that an extended copy
+ * IS the fresh one: equal digests on an appended and on a freshly built handle of the same rows).
+ * Not offered: appending to rows adopted by expann_set_base_device or to the sharded handles (expann_sharded_add
+ * after build still fails); removing rows (the row filter serves as tombstones); keeping a filter or groups across
+ * an append; a deferred append; in-place extension of the int8 filter's, the uint8 shadow's, the bf16x3 and the
+ * 8-bit copies -- they are rebuilt whole at the next search that uses them.  What that costs, measured on a
+ * 1 M x d128 fp32 index at default options, where 10 000-query batches run the int8 filter
+ * (profiles/bf_append_ab.txt): the first search after an append takes 2.6 .. 2.8 ms against 1.64 ms in steady state,
+ * about 1.0 ms once per append -- more than the append itself (0.84 ms for 1 000 rows, against 139 ms for destroy +
+ * add + build).  Extending that copy in place would be worth building for a caller that alternates single appends
+ * with single batches; at one append per hundred batches it is 0.6 % of the search time. */
+int expann_append(expann_index* h, const void* rows, size_t n);                          /* host rows   */
+int expann_append_device(expann_index* h, const void* d_rows, size_t n, void* stream);   /* device rows */
+int expann_reserve(expann_index* h, size_t n_rows);
+
 #ifdef __cplusplus
 }
 #endif
