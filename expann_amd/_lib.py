@@ -50,6 +50,8 @@ ABI_SYMBOLS = [
     "expann_search_grouped", "expann_search_grouped_device",
     "expann_range_search", "expann_range_search_device",
     "expann_append", "expann_append_device", "expann_reserve",
+    "expann_graph_range_search", "expann_graph_range_search_device",
+    "expann_antitopo_range_query", "expann_antitopo_range_query_device",
 ]
 GROUP_ANY = 0xFFFFFFFF  # EXPANN_GROUP_ANY: the group a query names to search every row
 
@@ -335,6 +337,15 @@ def load():
         L.expann_append_device.argtypes = [vp, vp, sz, vp]
         L.expann_reserve.restype = C.c_int
         L.expann_reserve.argtypes = [vp, sz]
+    if hasattr(L, "expann_graph_range_search"):  # (as above: an older build has no graph range search)
+        L.expann_graph_range_search.restype = C.c_int
+        L.expann_graph_range_search.argtypes = [vp, vp, vp, sz, sz, sz, vp, vp, vp, vp]
+        L.expann_graph_range_search_device.restype = C.c_int
+        L.expann_graph_range_search_device.argtypes = [vp, vp, vp, sz, sz, sz, vp, vp, vp, vp, vp]
+        L.expann_antitopo_range_query.restype = C.c_int
+        L.expann_antitopo_range_query.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
+        L.expann_antitopo_range_query_device.restype = C.c_int
+        L.expann_antitopo_range_query_device.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
     if hasattr(L, "expann_graph_create_f16"):  # (as above: an older build has no binary16 graph rows)
         L.expann_graph_create_f16.restype = C.c_int
         L.expann_graph_create_f16.argtypes = [C.c_int, C.c_int, vp, sz, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(vp)]

@@ -108,6 +108,7 @@ struct GraphStats {
 	// counter slot, folded in when the search is checked
 	uint64_t stat_group[3] = {0, 0, 0};
 	uint64_t stat_redo_queries = 0, stat_redo_overflows = 0, stat_deferred = 0, stat_distcomps = 0;
+	uint64_t stat_range = 0;  // range searches since create, from either entry point
 	double stat_redo_ms = 0;
 };
 
@@ -142,7 +143,8 @@ using GraphFn = void (*)(GraphSearchParams);
 struct GraphVariant {
 	int d;
 	int mode;       // expann_graph_compression
-	int filtered;   // kFilterNone, kFilterBitmap (THE FILTER RULE, graph_search.hpp) or kFilterGroups (THE GROUP RULE)
+	int filtered;   // kFilterNone, kFilterBitmap (THE FILTER RULE, graph_search.hpp), kFilterGroups (THE GROUP RULE) or
+	                // kFilterRange (THE RANGE WALK RULE)
 	bool f16;       // the instance over binary16 rows (TR = _Float16)
 	GraphFn fn;
 };
@@ -154,6 +156,7 @@ struct GraphVariant {
 // binary16 rows: the run-time-dim instances serve every dim and mode; d = 128 has compiled instances as well
 #define GRAPH_HF(D, MODE, F) {D, MODE, F, true, graph_search_kernel<D, MODE, 0, F, _Float16>}
 #define GRAPH_H(D, MODE) GRAPH_HF(D, MODE, kFilterNone), GRAPH_HF(D, MODE, kFilterBitmap)
+#define GRAPH_R(D) {D, kGraphF32, kFilterRange, false, graph_search_kernel<D, kGraphF32, 0, kFilterRange>}
 const GraphVariant kGraph[] = {GRAPH_V(64),  GRAPH_V(128), GRAPH_V(256), GRAPH_V(512),
                                GRAPH_V(768), GRAPH_V(832), GRAPH_V(960), GRAPH_V(0),
                                GRAPH_H(128, kGraphF32), GRAPH_H(128, kGraphU8Cast), GRAPH_H(128, kGraphRangedQ8),
@@ -162,7 +165,13 @@ const GraphVariant kGraph[] = {GRAPH_V(64),  GRAPH_V(128), GRAPH_V(256), GRAPH_V
                                GRAPH_VF(128, kFilterGroups), GRAPH_VF(0, kFilterGroups),
                                GRAPH_HF(128, kGraphF32, kFilterGroups), GRAPH_HF(128, kGraphU8Cast, kFilterGroups),
                                GRAPH_HF(128, kGraphRangedQ8, kFilterGroups), GRAPH_HF(0, kGraphF32, kFilterGroups),
-                               GRAPH_HF(0, kGraphU8Cast, kFilterGroups), GRAPH_HF(0, kGraphRangedQ8, kFilterGroups)};
+                               GRAPH_HF(0, kGraphU8Cast, kFilterGroups), GRAPH_HF(0, kGraphRangedQ8, kFilterGroups),
+                               // the range walk: fp32 bottom layer only, every compiled dim and the run-time-dim instance;
+                               // binary16 rows as above
+                               GRAPH_R(64), GRAPH_R(128), GRAPH_R(256), GRAPH_R(512), GRAPH_R(768), GRAPH_R(832),
+                               GRAPH_R(960), GRAPH_R(0), GRAPH_HF(128, kGraphF32, kFilterRange),
+                               GRAPH_HF(0, kGraphF32, kFilterRange)};
+#undef GRAPH_R
 #undef GRAPH_H
 #undef GRAPH_HF
 #undef GRAPH_V
@@ -329,6 +338,7 @@ GraphSearchParams graph_base_params(const expann_graph* g, int mode, size_t k, s
 	p.starting_vertex = g->starting_vertex;
 	p.k = (uint32_t)k;
 	p.ef = (uint32_t)ef_search;
+	p.near_cap = p.ef;  // (the range walk's is larger: graph_enqueue_range)
 	p.max_degree = g->max_degree0;
 	p.list_cap = std::max<uint32_t>(std::max<uint32_t>(g->stride0, (uint32_t)ef_search), 4);
 	p.visited = g->d_visited;
@@ -344,7 +354,7 @@ GraphSearchParams graph_base_params(const expann_graph* g, int mode, size_t k, s
 
 // dynamic LDS of a launch: the two heaps, a hop's list, and -- run-time-dim instance -- the query (and its bytes)
 size_t graph_lds_bytes(const GraphSearchParams& p, uint32_t cand_cap, bool run_time_dim, bool use_compression) {
-	size_t lds = sizeof(md_pair) * ((size_t)p.ef + 1 + cand_cap + 1) + (sizeof(uint32_t) + sizeof(float)) * p.list_cap;
+	size_t lds = sizeof(md_pair) * ((size_t)p.near_cap + 1 + cand_cap + 1) + (sizeof(uint32_t) + sizeof(float)) * p.list_cap;
 	if (run_time_dim)
 		lds += (size_t)p.dim * (sizeof(float) + (use_compression ? 1 : 0));
 	return lds;
@@ -720,6 +730,59 @@ int graph_enqueue_grouped(expann_graph* g, GraphSearchParams p, const uint32_t* 
 	return EXPANN_OK;
 }
 
+// ---- range search (THE RANGE WALK RULE) -----------------------------------------------------------
+// the argument checks of a range search, a NULL handle first, in the order the header documents, all before the device
+// is touched; *empty: m == 0, nothing to do
+int graph_range_args(expann_graph* g, const void* queries, const void* radii, size_t m, size_t max_results, size_t ef_search,
+                     const void* ids, const void* counts, bool* empty) {
+	*empty = false;
+	if (!g)
+		return EXPANN_ERR_INVALID_ARG;
+	if (ef_search == 0)
+		return g->fail(EXPANN_ERR_INVALID_ARG, "range search: ef_search == 0");
+	if (m == 0) {
+		*empty = true;
+		return EXPANN_OK;
+	}
+	if (!queries || !radii || !counts || (!ids && max_results > 0))
+		return g->fail(EXPANN_ERR_INVALID_ARG, "range search: NULL pointer");
+	if (ef_search > 4096)
+		return g->fail(EXPANN_ERR_UNSUPPORTED, "range search: ef_search > 4096");
+	if (max_results > 4096)
+		return g->fail(EXPANN_ERR_UNSUPPORTED, "range search: max_results > 4096");
+	if (g->filter_on)
+		return g->fail(EXPANN_ERR_UNSUPPORTED, "range search under a row filter is not offered");
+	return EXPANN_OK;
+}
+
+// A range search, enqueued on `st` with the counter slot `ctr` and nothing waited for: the slot's reset, the range
+// walk's first launch and its redo launch as graph_search_plan plans it.  `p` names queries and outputs
+// (graph_base_params at mode 0 with k = max_results); events: before the first launch, after it, after the redo launch
+// (when *has_redo).
+int graph_enqueue_range(expann_graph* g, GraphSearchParams p, const float* d_radii, uint32_t* d_counts, uint32_t* ctr,
+                        hipStream_t st, hipEvent_t* ev, bool* has_redo) {
+	const GraphVariant* gv = graph_variant(g->dim, EXPANN_GRAPH_FP32, kFilterRange, g->rows_f16);
+	if (!gv)
+		return g->fail(EXPANN_ERR_UNSUPPORTED, "no graph kernel for this dim");
+	p.allow_bits = nullptr;
+	p.radii = d_radii;
+	p.max_results = p.k;
+	p.out_counts = d_counts;
+	p.near_cap = std::max(p.ef, p.k);
+	p.list_cap = std::max(p.list_cap, p.near_cap);  // (the drain writes the whole queue to the hop's list)
+	GraphSearchPlan pl;
+	if (int rc = graph_search_plan(g, gv, p, ctr, &pl))
+		return rc;
+	if (int rc = graph_enqueue_first(g, pl, st, ev[0], ev[1]))
+		return rc;
+	*has_redo = pl.has_redo;
+	if (pl.has_redo)
+		if (int rc = graph_enqueue_redo(g, pl, st, ev[2]))
+			return rc;
+	++g->stat_range;
+	return EXPANN_OK;
+}
+
 // EXPANN_GRAPH_STAMPS: a launch's shader clocks, mean over the workgroups of its grid, per hop
 int graph_print_stamps(expann_graph* g, int mode, size_t ef_search, float ms, uint32_t grid, size_t m, const void* d_stamps) {
 	std::vector<unsigned long long> st(8 * (size_t)grid);
@@ -787,14 +850,16 @@ void graph_dev_commit(expann_graph* g, hipStream_t st, bool timed, bool timed_re
 }
 
 // Host buffers: the staging of one call on the handle's own stream -- device copies of the queries (and of their
-// groups) and of the result arrays, and the host-buffer calls' counter slot: the one behind those of the device-buffer
+// groups, or of their radii with the counts to come back) and of the result arrays, and the host-buffer calls' counter slot: the one behind those of the device-buffer
 // searches, which stay as they are for the next sync.  The caller enqueues and waits between begin() and finish().
 struct GraphHostStage {
-	DevBuf b_q, b_qg, b_ids, b_d, b_dc;
+	DevBuf b_q, b_qg, b_ids, b_d, b_dc, b_r, b_cnt;
 	uint32_t *ctr = nullptr, *h_ctr = nullptr;
 	size_t m = 0, k = 0;
-	// allocates, uploads (query_groups == nullptr: there are none) and points *p at the buffers
-	int begin(expann_graph* g, const float* queries, const uint32_t* query_groups, size_t m_, size_t k_, GraphSearchParams* p) {
+	// allocates, uploads (query_groups == nullptr: there are none; radii != nullptr: a range search, b_r and b_cnt) and
+	// points *p at the buffers
+	int begin(expann_graph* g, const float* queries, const uint32_t* query_groups, size_t m_, size_t k_, GraphSearchParams* p,
+	          const float* radii = nullptr) {
 		m = m_;
 		k = k_;
 		hipStream_t st = g->stream;
@@ -808,6 +873,11 @@ struct GraphHostStage {
 		HIP_TRY(g, hipMemcpyAsync(b_q.p, queries, qb, hipMemcpyHostToDevice, st));
 		if (query_groups)
 			HIP_TRY(g, hipMemcpyAsync(b_qg.p, query_groups, sizeof(uint32_t) * m, hipMemcpyHostToDevice, st));
+		if (radii) {
+			HIP_TRY(g, b_r.alloc(sizeof(float) * m));
+			HIP_TRY(g, b_cnt.alloc(sizeof(uint32_t) * m));
+			HIP_TRY(g, hipMemcpyAsync(b_r.p, radii, sizeof(float) * m, hipMemcpyHostToDevice, st));
+		}
 		p->queries = b_q.as<float>();
 		p->m = (uint32_t)m;
 		p->out_ids = b_ids.as<uint64_t>();
@@ -824,17 +894,22 @@ struct GraphHostStage {
 		HIP_TRY(g, hipStreamSynchronize(st));
 		return EXPANN_OK;
 	}
-	// the results into the caller's arrays (distcomps may be nullptr)
-	int copy_out(expann_graph* g, uint64_t* ids, float* dists, uint32_t* distcomps) {
-		HIP_TRY(g, hipMemcpy(ids, b_ids.p, sizeof(uint64_t) * m * k, hipMemcpyDeviceToHost));
-		HIP_TRY(g, hipMemcpy(dists, b_d.p, sizeof(float) * m * k, hipMemcpyDeviceToHost));
+	// the results into the caller's arrays (distcomps may be nullptr; a range search: its counts, and ids -- with no rows
+	// to return -- and dists may be nullptr too)
+	int copy_out(expann_graph* g, uint64_t* ids, float* dists, uint32_t* distcomps, uint32_t* counts = nullptr) {
+		if (ids && m * k)
+			HIP_TRY(g, hipMemcpy(ids, b_ids.p, sizeof(uint64_t) * m * k, hipMemcpyDeviceToHost));
+		if (dists && m * k)
+			HIP_TRY(g, hipMemcpy(dists, b_d.p, sizeof(float) * m * k, hipMemcpyDeviceToHost));
 		if (distcomps)
 			HIP_TRY(g, hipMemcpy(distcomps, b_dc.p, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
+		if (counts)
+			HIP_TRY(g, hipMemcpy(counts, b_cnt.p, sizeof(uint32_t) * m, hipMemcpyDeviceToHost));
 		return EXPANN_OK;
 	}
 	// ... and what the slot (read_slot) says of the walks: an overflow that no redo launch served is the call's error
-	int finish(expann_graph* g, uint64_t* ids, float* dists, uint32_t* distcomps) {
-		if (int rc = copy_out(g, ids, dists, distcomps))
+	int finish(expann_graph* g, uint64_t* ids, float* dists, uint32_t* distcomps, uint32_t* counts = nullptr) {
+		if (int rc = copy_out(g, ids, dists, distcomps, counts))
 			return rc;
 		if (h_ctr[0])
 			return g->fail(EXPANN_ERR_OVERFLOW, "graph search: candidates queue overflowed its LDS capacity");
@@ -1265,16 +1340,70 @@ int expann_graph_search_grouped(expann_graph* g, const float* queries, const uin
 	return stage.finish(g, ids, dists, distcomps);
 }
 
+int expann_graph_range_search_device(expann_graph* g, const float* d_queries, const float* d_radii, size_t m,
+                                     size_t max_results, size_t ef_search, uint64_t* d_ids, float* d_dists,
+                                     uint32_t* d_counts, uint32_t* d_distcomps, void* stream) {
+	bool empty = false;
+	if (int rc = graph_range_args(g, d_queries, d_radii, m, max_results, ef_search, d_ids, d_counts, &empty))
+		return rc;
+	if (empty)
+		return EXPANN_OK;
+	HIP_TRY(g, hipSetDevice(g->device));
+	GraphDevSearch s;
+	if (int rc = graph_dev_begin(g, stream, EXPANN_GRAPH_FP32, false, d_queries, m, max_results, ef_search, d_ids, d_dists,
+	                             d_distcomps, &s))
+		return rc;
+	hipEvent_t ev[3] = {g->ev_dev[0], g->ev_dev[1], g->ev_dev[2]};
+	bool has_redo = false;
+	if (int rc = graph_enqueue_range(g, s.p, d_radii, d_counts, s.ctr, s.st, ev, &has_redo))
+		return rc;
+	graph_dev_commit(g, s.st, true, has_redo);
+	return EXPANN_OK;
+}
+
+// host buffers: the same launches on the handle's own stream with the host-buffer calls' counter slot, waited for here
+int expann_graph_range_search(expann_graph* g, const float* queries, const float* radii, size_t m, size_t max_results,
+                              size_t ef_search, uint64_t* ids, float* dists, uint32_t* counts, uint32_t* distcomps) {
+	bool empty = false;
+	if (int rc = graph_range_args(g, queries, radii, m, max_results, ef_search, ids, counts, &empty))
+		return rc;
+	if (empty)
+		return EXPANN_OK;
+	HIP_TRY(g, hipSetDevice(g->device));
+	HIP_TRY(g, graph_wait_outstanding(g));  // (one set of visited arrays: device-buffer searches in flight go first)
+	if (int rc = graph_dev_init(g))
+		return rc;
+	if (!g->ev2)
+		HIP_TRY(g, hipEventCreate(&g->ev2));
+	GraphSearchParams p = graph_base_params(g, EXPANN_GRAPH_FP32, max_results, ef_search);
+	GraphHostStage stage;
+	if (int rc = stage.begin(g, queries, nullptr, m, max_results, &p, radii))
+		return rc;
+	hipEvent_t ev[3] = {g->ev0, g->ev1, g->ev2};
+	bool has_redo = false;
+	if (int rc = graph_enqueue_range(g, p, stage.b_r.as<float>(), stage.b_cnt.as<uint32_t>(), stage.ctr, g->stream, ev, &has_redo))
+		return rc;
+	if (int rc = stage.read_slot(g))
+		return rc;
+	float ms = 0, ms_redo = 0;
+	HIP_TRY(g, hipEventElapsedTime(&ms, g->ev0, g->ev1));
+	if (has_redo)
+		HIP_TRY(g, hipEventElapsedTime(&ms_redo, g->ev1, g->ev2));
+	g->last_ms = (double)ms + (double)ms_redo;
+	return stage.finish(g, ids, dists, distcomps, counts);
+}
+
 int expann_graph_get_stat(expann_graph* g, const char* name, uint64_t* out) {
 	if (!g)
 		return EXPANN_ERR_INVALID_ARG;
 	if (!name || !out)
 		return g->fail(EXPANN_ERR_INVALID_ARG, "NULL pointer");
 	using G = const expann_graph*;
-	static const struct {
+	struct StatRow {
 		const char* name;
 		uint64_t (*read)(G);
-	} kGraphStatTable[] = {
+	};
+	static const StatRow kGraphStatTable[] = {
 	    {"redo_queries", [](G g) { return g->stat_redo_queries; }},
 	    {"redo_overflows", [](G g) { return g->stat_redo_overflows; }},
 	    {"deferred_searches", [](G g) { return g->stat_deferred; }},
@@ -1291,11 +1420,21 @@ int expann_graph_get_stat(expann_graph* g, const char* name, uint64_t* out) {
 	    // the device bytes of the rows themselves
 	    {"vector_bytes", [](G g) { return (uint64_t)g->n * (uint64_t)g->dim * (g->rows_f16 ? 2u : 4u); }},
 	};
-	for (const auto& s : kGraphStatTable)
-		if (!std::strcmp(name, s.name)) {
-			*out = s.read(g);
-			return EXPANN_OK;
-		}
+	// the range search's rows (tests/test_graph_options.py pins the names of the table above, one by one)
+	static const StatRow kGraphRangeStatTable[] = {
+	    {"range_searches", [](G g) { return g->stat_range; }},  // since create, from either entry point
+	};
+	auto read_from = [&](const StatRow* rows, size_t n_rows) {
+		for (size_t i = 0; i < n_rows; ++i)
+			if (!std::strcmp(name, rows[i].name)) {
+				*out = rows[i].read(g);
+				return true;
+			}
+		return false;
+	};
+	if (read_from(kGraphStatTable, sizeof(kGraphStatTable) / sizeof(StatRow)) ||
+	    read_from(kGraphRangeStatTable, sizeof(kGraphRangeStatTable) / sizeof(StatRow)))
+		return EXPANN_OK;
 	return g->fail(EXPANN_ERR_INVALID_ARG, std::string("unknown stat: ") + name);
 }
 
@@ -1779,6 +1918,27 @@ int expann_antitopo_query_grouped_device(expann_antitopo* e, const float* d_quer
 	if (!e->eng->graph)
 		return e->fail(EXPANN_ERR_NOT_BUILT, "expann_antitopo_query_grouped_device before build()");
 	const int rc = e->eng->query_k_batch_grouped_device(d_queries, d_query_groups, m, k, d_ids, d_dists, stream);
+	return rc == EXPANN_OK ? rc : e->fail(rc, expann_graph_last_error(e->eng->graph));
+}
+
+int expann_antitopo_range_query(expann_antitopo* e, const float* queries, const float* radii, size_t m,
+                                size_t max_results, uint64_t* ids, float* dists, uint32_t* counts) {
+	if (!e)
+		return EXPANN_ERR_INVALID_ARG;
+	if (!e->eng->graph)
+		return e->fail(EXPANN_ERR_NOT_BUILT, "expann_antitopo_range_query before build()");
+	const int rc = e->eng->range_query_batch(queries, radii, m, max_results, ids, dists, counts);
+	return rc == EXPANN_OK ? rc : e->fail(rc, expann_graph_last_error(e->eng->graph));
+}
+
+int expann_antitopo_range_query_device(expann_antitopo* e, const float* d_queries, const float* d_radii, size_t m,
+                                       size_t max_results, uint64_t* d_ids, float* d_dists, uint32_t* d_counts,
+                                       void* stream) {
+	if (!e)
+		return EXPANN_ERR_INVALID_ARG;
+	if (!e->eng->graph)
+		return e->fail(EXPANN_ERR_NOT_BUILT, "expann_antitopo_range_query_device before build()");
+	const int rc = e->eng->range_query_batch_device(d_queries, d_radii, m, max_results, d_ids, d_dists, d_counts, stream);
 	return rc == EXPANN_OK ? rc : e->fail(rc, expann_graph_last_error(e->eng->graph));
 }
 

@@ -101,10 +101,19 @@ struct GraphSearchParams {
 	const uint32_t* group_off;     // [n_groups + 1]
 	uint32_t n_groups, flat_rows;
 	uint32_t* group_walked;        // [1] or nullptr
+	// capacity of `nearest` (LDS): ef in every walk but the range walk, whose queue grows to max(ef, max_results)
+	uint32_t near_cap;
+	// range instances only (THE RANGE WALK RULE below): the radius of every query, the rows a query may return (the
+	// stride of out_ids / out_dists; k holds the same number) and the in-range rows each walk scored
+	const float* radii;            // [m]
+	uint32_t max_results;
+	uint32_t* out_counts;          // [m]
 };
 
-// what a walk instance is filtered by: nothing, the handle's bitmap (THE FILTER RULE), or row groups (THE GROUP RULE)
-constexpr int kFilterNone = 0, kFilterBitmap = 1, kFilterGroups = 2;
+// what a walk instance is filtered by: nothing, the handle's bitmap (THE FILTER RULE), or row groups (THE GROUP RULE);
+// kFilterRange is no filter but the fourth kind of walk: the unfiltered one that keeps what lies within a radius (THE
+// RANGE WALK RULE)
+constexpr int kFilterNone = 0, kFilterBitmap = 1, kFilterGroups = 2, kFilterRange = 3;
 // the group a query names to search every row
 constexpr uint32_t kGroupAny = 0xFFFFFFFFu;
 // min(k, allowed) the exact scan keeps in LDS; beyond it the search walks.  Not measured: the scan's final ranking reads
@@ -627,13 +636,36 @@ template <int MODE, bool GROUPS = false> constexpr int graph_any_dim_waves() { r
 // query that is not walk-served is skipped); for it "allowed" means row_groups[v] == its group, and everything else
 // is THE FILTER RULE word for word.  The label request stands where the allow word's does, beside the visited test;
 // a list's padding reads the last row's label.
+// THE RANGE WALK RULE (kFilterRange instances, MODE kGraphF32 only; the header states it in full).  r = p.radii[qi] in
+// squared-L2 units, ef = p.ef, R = p.max_results, cap = p.near_cap = max(ef, R).  "d > r" below means !(d <= r): a NaN
+// radius is in range of nothing.
+//   Descent: unchanged, never looks at r.
+//   Bottom layer: the plain walk's two queues.  Every scored bottom-layer vertex with d <= r adds 1 to `count`, kept or
+//   not, the entry vertex included.
+//   Stop rule: `candidates` empty, or nearest.size() >= ef && cur.d > nearest.top().d && (cur.d > r || nearest.size()
+//   >= cap).
+//   Neighbour update, unvisited neighbours in adjacency order: accept when nearest.size() < ef || dn < nearest.top().d
+//   || (dn <= r && nearest.size() < cap); an accepted one is pushed on both queues, then `nearest` is popped once if
+//   nearest.size() > ef && (nearest.top().d > r || nearest.size() > cap).  So either nearest.size() <= ef, or every
+//   entry is in range and nearest.size() <= cap.
+//   Pre-drop: with full0 = nearest.size() >= ef, worst0 and n0 taken at the start of the hop, a neighbour is dropped
+//   before the queue update iff full0 && !(dn < worst0) && !(dn <= r && n0 < cap) -- it changes nothing: while the top is
+//   above r it only falls, once every entry is in range it rises only up to r, and at cap it only falls again.  Counted
+//   before it is dropped.
+//   Output: drain `nearest`, reverse; the leading entries with d <= r, at most R of them, padded with UINT64_MAX /
+//   +inf; out_counts = count; distcomps as the plain walk.
+// With R <= ef, or r < 0 or NaN, this is the plain walk at that ef (equal distcomps) cut at r and R.
+// `count` is wave-uniform: the compaction loop's lanes already hold every dn, one ballot per 64 neighbours feeds it, one
+// lane stores it with the distcomps.  Nothing serial and no atomic is added to the hop loop.
 // TR: the element type of p.vectors -- float, or _Float16 for a handle made by expann_graph_create_f16.  It covers
 // every read of the rows (entry evaluation, descent, fp32 bottom layer, final re-score of the byte modes); the
 // arithmetic is the float instance's over (float)row, bit for bit (ref_diff, common.hpp).
 template <int D, int MODE, int DBG = 0, int KIND = kFilterNone, typename TR = float>
 __global__ __launch_bounds__(64, (D == 0 ? graph_any_dim_waves<MODE, (KIND == kFilterGroups)>() : ((MODE != kGraphF32 && D <= 128) ? 4 : 1))) void graph_search_kernel(GraphSearchParams p) {
 	constexpr bool COMPRESSED = MODE != kGraphF32, RANGED = MODE == kGraphRangedQ8;
-	constexpr bool FILTERED = KIND != kFilterNone, GROUPS = KIND == kFilterGroups;
+	constexpr bool FILTERED = KIND == kFilterBitmap || KIND == kFilterGroups, GROUPS = KIND == kFilterGroups;
+	constexpr bool RANGE = KIND == kFilterRange;
+	static_assert(!RANGE || MODE == kGraphF32, "the range walk scores fp32 distances: the byte modes walk on integers");
 	constexpr int DPL = D ? D / 16 : 1;
 	constexpr int NW = D ? D / 64 : 1;
 	unsigned long long seg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ts = DBG ? clock64() : 0;
@@ -645,8 +677,8 @@ __global__ __launch_bounds__(64, (D == 0 ? graph_any_dim_waves<MODE, (KIND == kF
 		}
 	};
 	extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-	md_pair* nearest = reinterpret_cast<md_pair*>(smem_raw);             // [ef + 1]
-	md_pair* candidates = nearest + (p.ef + 1);                          // [cand_cap + 1]
+	md_pair* nearest = reinterpret_cast<md_pair*>(smem_raw);             // [near_cap + 1]
+	md_pair* candidates = nearest + (p.near_cap + 1);                    // [cand_cap + 1]
 	uint32_t* nlist = reinterpret_cast<uint32_t*>(candidates + (p.cand_cap + 1));  // [list_cap]
 	float* ndist = reinterpret_cast<float*>(nlist + p.list_cap);          // [list_cap]
 	float* qs = ndist + p.list_cap;                                       // D = 0: [dim] the query
@@ -698,6 +730,11 @@ __global__ __launch_bounds__(64, (D == 0 ? graph_any_dim_waves<MODE, (KIND == kF
 			++n_walked;
 		}
 		const bool any_group = qgroup == kGroupAny;
+		// RANGE: the query's radius and the in-range vertices its bottom layer scored; wave-uniform
+		float radius = 0.0f;
+		uint32_t in_range = 0;
+		if constexpr (RANGE)
+			radius = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, p.radii[qi])));
 		bool q_overflowed = false;  // wave-uniform: this walk met a full candidates heap
 		// ---- per-query setup ----------------------------------------------------------
 		if (!bits && ++epoch > 255) {  // epoch bytes wrapped: clear this workgroup's visited array
@@ -856,6 +893,8 @@ __global__ __launch_bounds__(64, (D == 0 ? graph_any_dim_waves<MODE, (KIND == kF
 			d_entry = d1[0];
 		}
 		++distcomps;
+		if constexpr (RANGE)
+			in_range += d_entry <= radius ? 1u : 0u;
 		{
 			const md_pair e{d_entry, entry};
 			coop_push<false>(candidates, n_cand, e, lane, p.debug & 1);
@@ -876,11 +915,15 @@ __global__ __launch_bounds__(64, (D == 0 ? graph_any_dim_waves<MODE, (KIND == kF
 				break;
 			const md_pair cur = candidates[0];
 			coop_pop<false>(candidates, n_cand, lane, p.debug & 1);
-			const bool full0 = n_near == p.ef;
+			const bool full0 = RANGE ? n_near >= p.ef : n_near == p.ef;
+			const uint32_t n0 = n_near;  // RANGE: room for in-range neighbours while n0 < near_cap
 			// (FILTERED: `nearest` may be empty, its slot 0 never written; worst0 only counts when the queue is full)
 			const float worst0 = FILTERED ? (full0 ? nearest[0].d : __builtin_inff()) : nearest[0].d;
 			stamp(1);
-			if (cur.d > worst0 && full0)
+			if constexpr (RANGE) {
+				if (full0 && cur.d > worst0 && (!(cur.d <= radius) || n0 >= p.near_cap))
+					break;
+			} else if (cur.d > worst0 && full0)
 				break;
 			if (DBG)
 				seg[6]++;
@@ -981,7 +1024,12 @@ __global__ __launch_bounds__(64, (D == 0 ? graph_any_dim_waves<MODE, (KIND == kF
 				const uint32_t id = i < n_list ? nlist[i] : 0u;
 				const float dn_raw = i < n_list ? ndist[i] : 0.0f;  // FILTERED: with the flag in its sign bit
 				const float dn = FILTERED ? __builtin_fabsf(dn_raw) : dn_raw;
-				const bool keep = i < n_list && !(full0 && !(dn < worst0));
+				bool keep = i < n_list && !(full0 && !(dn < worst0));
+				if constexpr (RANGE) {  // counted before anything is dropped; an in-range neighbour stays while there is room
+					const bool within = i < n_list && dn <= radius;
+					in_range += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(within));
+					keep = keep || (within && n0 < p.near_cap);
+				}
 				wave_lds_sync();
 				const unsigned long long mask = __builtin_amdgcn_ballot_w64(keep);
 				const uint32_t pos = n_s + __builtin_popcountll(mask & ((1ull << lane) - 1ull));
@@ -996,7 +1044,19 @@ __global__ __launch_bounds__(64, (D == 0 ? graph_any_dim_waves<MODE, (KIND == kF
 				const float dn_raw = ndist[j];
 				const float dn = FILTERED ? __builtin_fabsf(dn_raw) : dn_raw;
 				const bool allowed = !FILTERED || !(__builtin_bit_cast(uint32_t, dn_raw) & 0x80000000u);  // wave-uniform
-				if (n_near < p.ef || dn < nearest[0].d) {
+				if constexpr (RANGE) {
+					if (n_near < p.ef || dn < nearest[0].d || (dn <= radius && n_near < p.near_cap)) {
+						const md_pair e{dn, nlist[j]};
+						if (n_cand >= p.cand_cap)
+							q_overflowed = true;
+						else
+							coop_push<false>(candidates, n_cand, e, lane, p.debug & 1);
+						coop_push<true>(nearest, n_near, e, lane, p.debug & 1);
+						wave_lds_sync();
+						if (n_near > p.ef && (!(nearest[0].d <= radius) || n_near > p.near_cap))
+							coop_pop<true>(nearest, n_near, lane, p.debug & 1);
+					}
+				} else if (n_near < p.ef || dn < nearest[0].d) {
 					const md_pair e{dn, nlist[j]};
 					if (n_cand >= p.cand_cap)
 						q_overflowed = true;
@@ -1027,7 +1087,15 @@ __global__ __launch_bounds__(64, (D == 0 ? graph_any_dim_waves<MODE, (KIND == kF
 			}
 		}
 		wave_lds_sync();
-		const uint32_t n_out = cnt < p.k ? cnt : p.k;
+		uint32_t n_out = cnt < p.k ? cnt : p.k;
+		if constexpr (RANGE) {  // the leading entries within the radius (ascending: they are all of them), at most k = R
+			uint32_t n_in = 0;
+			for (uint32_t i0 = 0; i0 < cnt; i0 += 64) {
+				const uint32_t i = i0 + lane;
+				n_in += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(i < cnt && ndist[i] <= radius));
+			}
+			n_out = n_in < p.k ? n_in : p.k;
+		}
 		if (COMPRESSED) {
 			for (uint32_t i0 = 0; i0 < n_out; i0 += 4) {
 				const uint32_t i = i0 + rg;
@@ -1039,10 +1107,15 @@ __global__ __launch_bounds__(64, (D == 0 ? graph_any_dim_waves<MODE, (KIND == kF
 		}
 		for (uint32_t i = lane; i < p.k; i += 64) {
 			p.out_ids[(size_t)qi * p.k + i] = i < n_out ? (uint64_t)nlist[i] : ~0ull;
-			p.out_dists[(size_t)qi * p.k + i] = i < n_out ? ndist[i] : __builtin_inff();
+			if (!RANGE || p.out_dists)
+				p.out_dists[(size_t)qi * p.k + i] = i < n_out ? ndist[i] : __builtin_inff();
 		}
 		if (lane == 0 && p.out_distcomps)
 			p.out_distcomps[qi] = distcomps;
+		if constexpr (RANGE) {
+			if (lane == 0)
+				p.out_counts[qi] = in_range;
+		}
 		// an overflowed walk goes on the redo list when there is one (its row is rewritten by the redo launch, which
 		// also counts its distcomps), else it raises the launch's error flag
 		const bool to_redo = q_overflowed && p.redo_list;

@@ -195,6 +195,40 @@ class AntitopoEngine:
                                                          C.c_void_p(ids_ptr), C.c_void_p(dists_ptr),
                                                          C.c_void_p(stream or None)))
 
+    def range_search(self, queries, radius, max_results):
+        """expann_antitopo_range_query: per query the rows within `radius` (squared L2; a scalar, or an array [m] of
+        per-query radii) that the walk scored -- THE RANGE WALK RULE, include/expann_hip.h.  Returns
+        (ids[m, max_results] uint64, dists[m, max_results] float32, counts[m] uint32): the rows are the
+        min(in range and kept, max_results) nearest ones the walk kept, ascending, padded with 2^64-1 / +inf; counts
+        is the number of in-range rows the walk scored -- never more than the true number, and more than max_results
+        when a row was truncated.  Approximate, as the walk is: every returned row is truly in range, not every
+        in-range row is found.  max_results = 0 only counts.  The sticky ef_search of query_many; fp32 bottom layer
+        whatever the compression mode; no row filter in force."""
+        if self._h is None:
+            raise _lib.ExpannError(_lib.ERR_NOT_BUILT, "range_search() before build()")
+        q = self._pad(queries)
+        m, max_results = q.shape[0], int(max_results)
+        radii = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float32), (m,)))
+        ids = np.empty((m, max_results), dtype=np.uint64)
+        dists = np.empty((m, max_results), dtype=np.float32)
+        counts = np.zeros(m, dtype=np.uint32)
+        nul = C.c_void_p(None)
+        self._check(self._L.expann_antitopo_range_query(
+            self._h, q.ctypes.data, radii.ctypes.data, m, max_results, ids.ctypes.data if max_results else nul,
+            dists.ctypes.data if max_results else nul, counts.ctypes.data))
+        return ids, dists, counts
+
+    def range_search_device(self, q_ptr, radii_ptr, m, max_results, ids_ptr, dists_ptr, counts_ptr, stream=0):
+        """range_search on device buffers, enqueued on `stream` (a hipStream_t as an integer; 0 = the engine's own)
+        without waiting: q_ptr -> m rows of float32 of the engine's padded `dim`, radii_ptr -> float32 [m], ids_ptr ->
+        uint64 [m][max_results], dists_ptr -> float32 [m][max_results] (0 where the C call allows NULL), counts_ptr ->
+        uint32 [m].  The results are valid after sync()."""
+        if self._h is None:
+            raise _lib.ExpannError(_lib.ERR_NOT_BUILT, "range_search_device() before build()")
+        self._check(self._L.expann_antitopo_range_query_device(
+            self._h, C.c_void_p(q_ptr), C.c_void_p(radii_ptr), int(m), int(max_results), C.c_void_p(ids_ptr or None),
+            C.c_void_p(dists_ptr or None), C.c_void_p(counts_ptr), C.c_void_p(stream or None)))
+
     def set_row_filter(self, allow):
         """expann_antitopo_set_row_filter: queries from now on return only rows where the boolean (or 0 / 1 uint8)
         array allow[size()] is true; None clears the filter.  Dense filters are walked under the filter rule of

@@ -10,6 +10,7 @@
 // expann_graph_search.  _query_k keeps the reference's "sticky" ef_search (:858-859).
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <optional>
@@ -311,6 +312,39 @@ struct gpu_antitopo_engine : public ann_engine<T, gpu_antitopo_engine<T>> {
 			set_ef_search(k * conf.ef_search_mult);  // :858-859
 		return expann_graph_search_grouped_device(graph, d_queries, d_query_groups, m, k, ef_search.value(), conf.mode(),
 		                                          d_ids, d_dists, nullptr, stream);
+	}
+	// Extension: range search by the walk (THE RANGE WALK RULE, expann_hip.h): per query the rows within radii[i]
+	// (squared L2) that the walk scored -- ids / dists [m][max_results] ascending and padded, counts[m] the in-range
+	// rows scored.  fp32 bottom layer whatever conf.mode() says; the sticky ef_search of query_k_batch, set when unset
+	// as query_k_batch sets it with k = max(1, max_results).  dists and distcomps may be nullptr, ids too with
+	// max_results == 0.  Returns the expann_status (message: expann_graph_last_error(graph)).
+	int range_query_batch(const float* queries, const float* radii, size_t m, size_t max_results, uint64_t* ids,
+	                      float* dists, uint32_t* counts, uint32_t* distcomps = nullptr) {
+		if (!graph)
+			return EXPANN_ERR_NOT_BUILT;
+		if (!ef_search.has_value())
+			set_ef_search(std::max<size_t>(1, max_results) * conf.ef_search_mult);  // :858-859
+		std::vector<uint32_t> dc(m);
+		const int rc = expann_graph_range_search(graph, queries, radii, m, max_results, ef_search.value(), ids, dists, counts,
+		                                         dc.data());
+		if (rc != EXPANN_OK)
+			return rc;
+		for (size_t i = 0; i < m; ++i) {
+			num_distcomps += dc[i];
+			if (distcomps)
+				distcomps[i] = dc[i];
+		}
+		return rc;
+	}
+	// the same on device buffers, enqueued on `stream` without waiting; results are valid after sync()
+	int range_query_batch_device(const float* d_queries, const float* d_radii, size_t m, size_t max_results, uint64_t* d_ids,
+	                             float* d_dists, uint32_t* d_counts, void* stream) {
+		if (!graph)
+			return EXPANN_ERR_NOT_BUILT;
+		if (!ef_search.has_value())
+			set_ef_search(std::max<size_t>(1, max_results) * conf.ef_search_mult);  // :858-859
+		return expann_graph_range_search_device(graph, d_queries, d_radii, m, max_results, ef_search.value(), d_ids, d_dists,
+		                                        d_counts, nullptr, stream);
 	}
 	// expann_graph_sync; the distance evaluations the device counted since the last sync go to num_distcomps
 	int sync() {

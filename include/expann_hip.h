@@ -345,7 +345,8 @@ int expann_graph_set_option(expann_graph* g, const char* name, long value);
  * last sync; "redo_kernel_ns" = device time of the last search's redo launch, as of the last sync;
  * "filter_active", "filter_rows", "flat_searches": see expann_graph_set_row_filter; "groups_active", "group_count",
  * "group_walk_queries", "group_scan_queries", "group_pad_queries": see expann_graph_set_row_groups; "vector_bytes": see
- * expann_graph_create_f16.  An unknown name is EXPANN_ERR_INVALID_ARG. */
+ * expann_graph_create_f16; "range_searches": see expann_graph_range_search.  An unknown name is
+ * EXPANN_ERR_INVALID_ARG. */
 int expann_graph_get_stat(expann_graph* g, const char* name, uint64_t* out);
 
 /* GPU-assisted batched construction of the graph (csrc/graph_build.hpp; replaces the inner loop of
@@ -809,9 +810,10 @@ int expann_search_grouped_device(expann_index* h, const void* d_queries, const u
  * expann_get_stat, of the last range search: "range_list_queries" (answered from a candidate list, stages 1 and 2),
  * "range_topk_queries" (more than 16 384 rows in range; the two add up to m), "range_retries" (queries that stage
  * 1's lists could not hold).  expann_get_profile's scan_kernel names the scan of stage 1.
- * Not offered: range search under a row filter or per row group, on 8-bit / int16 rows, on the sharded handles, in
- * the graph engine; deferred ("async_search") range searches; a CSR-packed output (lims are the running sum of
- * min(counts, max_results)); more than 8192 rows per query. */
+ * Not offered: range search under a row filter or per row group, on 8-bit / int16 rows, on the sharded handles;
+ * deferred ("async_search") range searches; a CSR-packed output (lims are the running sum of min(counts,
+ * max_results)); more than 8192 rows per query.  (The graph engine has a range search of its own, approximate as its
+ * walk is: expann_graph_range_search, at the end of this header.) */
 int expann_range_search(expann_index* h, const void* queries, const float* radii, size_t m,
                         size_t max_results, uint64_t* ids, float* dists, uint32_t* counts);      /* host buffers */
 int expann_range_search_device(expann_index* h, const void* d_queries, const float* d_radii, size_t m,
@@ -878,6 +880,76 @@ int expann_range_search_device(expann_index* h, const void* d_queries, const flo
 int expann_append(expann_index* h, const void* rows, size_t n);                          /* host rows   */
 int expann_append_device(expann_index* h, const void* d_rows, size_t n, void* stream);   /* device rows */
 int expann_reserve(expann_index* h, size_t n_rows);
+
+/* Range search of the graph engine: the rows within a per-query radius, found by the walk (appended;
+ * EXPANN_ABI_VERSION stays 2: nothing that existed changed).  The reference has no range query: the rule is this
+ * project's, stated so that a CPU restatement pins it bit for bit (tests/graph_range_helpers.py).
+ * THE RANGE WALK RULE.
+ * Inputs.  Per query a radius r = radii[i] in squared-L2 units, the units expann_graph_search reports.  Per call
+ * ef = ef_search >= 1 and R = max_results >= 0; cap = max(ef, R).  Mode 0 only: fp32 bottom layer, over fp32 or
+ * binary16 rows.  Below, "d > r" means "not d <= r": the comparison with the radius is inclusive, and a NaN radius is
+ * in range of nothing.
+ * Descent.  Entry evaluation and greedy descent are unchanged and never look at r.
+ * Bottom layer.  The queues `candidates` (min) and `nearest` (max) are the plain walk's, with the libstdc++ heap
+ * behaviour it reproduces.  `count` starts at 0.
+ *   The entry vertex is scored, marked visited, and pushed on both queues.
+ *   Every scored bottom-layer vertex with d <= r adds 1 to `count`, whether or not it is kept.  The entry vertex counts.
+ *   Stop when `candidates` is empty, or when nearest.size() >= ef && cur.d > nearest.top().d && (cur.d > r ||
+ *   nearest.size() >= cap), cur being the best candidate.
+ *   Neighbour update.  For each unvisited neighbour in adjacency order, with distance dn: accept when nearest.size() <
+ *   ef || dn < nearest.top().d || (dn <= r && nearest.size() < cap).  An accepted neighbour is pushed on `candidates`
+ *   and on `nearest`.  Then `nearest` is popped once if nearest.size() > ef && (nearest.top().d > r || nearest.size() >
+ *   cap).
+ *   Invariant, which follows: either nearest.size() <= ef, or every entry of `nearest` is in range and nearest.size()
+ *   <= cap.
+ * Output.  Drain `nearest` and reverse it: ascending distance, equal distances in the heap's order, as
+ * expann_graph_search returns them, and not by id.  The leading entries with d <= r are the result.
+ *   ids[i][0 .. R) and dists[i][...] hold the first min(that number, R) of them, padded with UINT64_MAX / +inf.
+ *   counts[i] = count.
+ *   distcomps[i] is as for the plain walk: descent plus every scored vertex.
+ * What counts means.  It is the number of distinct in-range rows the walk scored.  It is never more than the true
+ * number.  counts[i] > R tells the caller that the row was truncated; what it holds are the nearest rows the walk
+ * kept.  counts[i] may be smaller than the true number: this is an approximate search.  Every returned row is truly in
+ * range, because the distances are the exact fp32 ones.
+ * Consequences.  With R <= ef, cap equals ef: the walk is the plain walk at that ef, with equal distcomps, and the
+ * output is its result cut at r and at R; so r = +inf gives expann_graph_search(k = R, ef) bit for bit.  With r < 0 or
+ * NaN, at any R, the walk is the plain walk: distcomps equal the plain walk's, counts is 0, the rows are padding.
+ * Pre-drop (the kernel's; it changes nothing).  With full0 = nearest.size() >= ef, worst0 = nearest.top().d and n0 =
+ * nearest.size() at the start of the hop, a neighbour is dropped before the queue update iff full0 && !(dn < worst0)
+ * && !(dn <= r && n0 < cap): while the top is above r it only falls; once every entry is in range it rises only up to
+ * r; at cap it only falls again.  A neighbour is counted before it is dropped.
+ * Binary16 handles return what the fp32 handle of the upcast rows returns, bit for bit (THE F16 ROW RULE).
+ * Arguments.  dists and distcomps may be NULL.  With max_results == 0 the call only counts, and ids may be NULL.
+ * Checks, in this order, all before the device is touched: handle NULL EXPANN_ERR_INVALID_ARG; ef_search == 0
+ * EXPANN_ERR_INVALID_ARG; m == 0 EXPANN_OK, nothing enqueued; queries, radii or counts NULL, or ids NULL with
+ * max_results > 0, EXPANN_ERR_INVALID_ARG; ef_search > 4096 or max_results > 4096 EXPANN_ERR_UNSUPPORTED (by value);
+ * a row filter in force EXPANN_ERR_UNSUPPORTED.  Row groups that are merely set are ignored.  A working set beyond
+ * the LDS is EXPANN_ERR_UNSUPPORTED, as for the plain searches.
+ * The redo launch, "cand_capacity" / "redo_capacity" and EXPANN_ERR_OVERFLOW work as for expann_graph_search_device;
+ * in-range neighbours are pushed on `candidates` while `nearest` is full, so a range walk overflows a capacity sooner
+ * than a plain one.  expann_graph_range_search_device keeps expann_graph_search_device's promises: it enqueues on
+ * `stream` and returns without waiting; in steady state it makes no allocation, copy, query or synchronisation; it
+ * counts towards the 256 outstanding searches; expann_graph_sync reports EXPANN_ERR_OVERFLOW.
+ * expann_graph_range_search (host buffers) enqueues the same launches and waits.  expann_graph_last_kernel_ms covers
+ * the range launches.  expann_graph_get_stat "range_searches" = range searches since create, from either entry point.
+ * The expann_antitopo_* calls search the engine's graph with its sticky ef_search; when that is unset it is set as
+ * expann_antitopo_query sets it, with k = max(1, max_results).  The engine's compression mode is not consulted: the
+ * range walk is fp32.  Before build() they return EXPANN_ERR_NOT_BUILT.
+ * Not offered: the byte modes 1 and 2 -- they walk on integer distances, which a squared-L2 radius does not cut; the
+ * calls have no `mode` argument for that reason; range search under a row filter or per row group; an order by id
+ * among equal distances; more than 4096 rows per query; the sharded handles.  (Exact range search: expann_range_search
+ * on a brute-force index of the same rows.) */
+int expann_graph_range_search(expann_graph* g, const float* queries, const float* radii, size_t m,
+                              size_t max_results, size_t ef_search, uint64_t* ids, float* dists,
+                              uint32_t* counts, uint32_t* distcomps);             /* host buffers */
+int expann_graph_range_search_device(expann_graph* g, const float* d_queries, const float* d_radii, size_t m,
+                                     size_t max_results, size_t ef_search, uint64_t* d_ids, float* d_dists,
+                                     uint32_t* d_counts, uint32_t* d_distcomps, void* stream);
+int expann_antitopo_range_query(expann_antitopo* e, const float* queries, const float* radii, size_t m,
+                                size_t max_results, uint64_t* ids, float* dists, uint32_t* counts);
+int expann_antitopo_range_query_device(expann_antitopo* e, const float* d_queries, const float* d_radii, size_t m,
+                                       size_t max_results, uint64_t* d_ids, float* d_dists, uint32_t* d_counts,
+                                       void* stream);
 
 #ifdef __cplusplus
 }
