@@ -50,6 +50,7 @@ ABI_SYMBOLS = [
     "expann_search_grouped", "expann_search_grouped_device",
     "expann_range_search", "expann_range_search_device",
     "expann_append", "expann_append_device", "expann_reserve",
+    "expann_remove", "expann_remove_device", "expann_compact_row_filter",
     "expann_graph_range_search", "expann_graph_range_search_device",
     "expann_antitopo_range_query", "expann_antitopo_range_query_device",
 ]
@@ -337,6 +338,14 @@ def load():
         L.expann_append_device.argtypes = [vp, vp, sz, vp]
         L.expann_reserve.restype = C.c_int
         L.expann_reserve.argtypes = [vp, sz]
+    if hasattr(L, "expann_remove"):  # (as above: an older build cannot remove rows)
+        szp = C.POINTER(C.c_size_t)
+        L.expann_remove.restype = C.c_int
+        L.expann_remove.argtypes = [vp, vp, sz, szp]
+        L.expann_remove_device.restype = C.c_int
+        L.expann_remove_device.argtypes = [vp, vp, sz, vp, szp]
+        L.expann_compact_row_filter.restype = C.c_int
+        L.expann_compact_row_filter.argtypes = [vp, szp]
     if hasattr(L, "expann_graph_range_search"):  # (as above: an older build has no graph range search)
         L.expann_graph_range_search.restype = C.c_int
         L.expann_graph_range_search.argtypes = [vp, vp, vp, sz, sz, sz, vp, vp, vp, vp]

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "bf_append.hpp"
+#include "bf_remove.hpp"
 #include "bf_options.hpp"
 #include "bf_plan.hpp"
 #include "host_common.hpp"
@@ -38,6 +39,7 @@
 #include "filter_rows.hpp"
 #include "scan_groups.hpp"
 #include "append_rows.hpp"
+#include "remove_rows.hpp"
 #include "score_ids.hpp"
 #include "select.hpp"
 #include "select_range.hpp"
@@ -254,6 +256,9 @@ struct Stats {
 	// expann_append since create: calls, rows, appends that extended the fp16 copy in place, appends that had to drop
 	// it (the scale changed), and reallocations of the base (expann_reserve's included)
 	uint64_t stat_append[5] = {0, 0, 0, 0, 0};
+	// expann_remove / expann_compact_row_filter since create: accepted calls, rows removed, removes that carried the
+	// fp16 copy over, removes that dropped it or forgot an unusable mark
+	uint64_t stat_remove[4] = {0, 0, 0, 0};
 };
 
 // streams, events, profiling, statistics, the last error
@@ -3361,6 +3366,184 @@ int expann_reserve(expann_index* h, size_t n_rows) {
 	return EXPANN_OK;
 }
 
+// ---- remove -----------------------------------------------------------------
+extern "C++" {
+namespace {
+// A base of the SAME capacity that holds the survivors of a remove in their old order, and -- where a usable fp16
+// copy exists -- fp16 arrays of the same f16_rows_alloc, initialised as make_f16 initialises them (zero rows, NaN
+// terms) and holding the survivors' rows and terms, with the two maxima recomputed: built ASIDE in the order of
+// `st`, while the old allocations stay live, and swapped in by commit() once the one host wait has shown that
+// everything succeeded.  GrownRows' shape; a call that fails on the way frees what it built and leaves the handle as
+// it was.  Nothing aliases the base after commit(): the int8 operand that may (d_base_i8q) is forgotten with
+// OtherCopies before the swap.
+struct CompactedRows {
+	DevPtr<uint32_t> keep;  // [2][words]: the keep bitmap, then word_rank
+	DevPtr<uint32_t> stat;  // [4 + kFilterSegs]: survivors, OR of the words, id-out-of-range flag, max |v| bits; segment counts
+	DevPtr<void> base, f16;
+	DevPtr<float> bnorm, bns, bnmax;
+	DevBuf ids;
+	uint32_t seen[4] = {0, 0, 0, 0};  // stat[0..3] on the host
+	size_t words = 0;
+	bool have_copy = false;
+
+	// ids == nullptr: the keep bitmap is the row filter in force
+	int build(expann_index* h, const uint64_t* id_list, size_t n_ids, bool on_device, hipStream_t st) {
+		const size_t n = h->n, row_bytes = (size_t)h->dim * h->elem;
+		words = keep_words(n);
+		HIP_TRY(h, hipMalloc(&keep, sizeof(uint32_t) * 2 * words));
+		HIP_TRY(h, hipMalloc(&stat, sizeof(uint32_t) * (4 + kFilterSegs)));
+		HIP_TRY(h, hipMemsetAsync(stat, 0, sizeof(uint32_t) * (4 + kFilterSegs), st));
+		if (!id_list) {
+			if (h->filter_words != words)
+				return h->fail(EXPANN_ERR_HIP, "compact_row_filter: the bitmap does not cover the rows");  // (both are whole 128-row tiles)
+			HIP_TRY(h, hipMemcpyAsync(keep, h->d_filter_bits, sizeof(uint32_t) * words, hipMemcpyDeviceToDevice, st));
+		} else {
+			HIP_TRY(h, hipMemsetAsync(keep, 0xFF, sizeof(uint32_t) * words, st));
+			if (!on_device) {
+				HIP_TRY(h, ids.alloc(sizeof(uint64_t) * n_ids));
+				HIP_TRY(h, hipMemcpyAsync(ids.p, id_list, sizeof(uint64_t) * n_ids, hipMemcpyHostToDevice, st));
+				id_list = ids.as<const uint64_t>();
+			}
+			hipLaunchKernelGGL(remove_mark_kernel, dim3((uint32_t)std::min<size_t>((n_ids + kBlock - 1) / kBlock, 4096)),
+			                   dim3(kBlock), 0, st, id_list, n_ids, (uint32_t)n, keep.p, stat + 2);
+		}
+		hipLaunchKernelGGL(filter_count_kernel, dim3(kFilterSegs), dim3(kBlock), 0, st, keep.p, (uint32_t)n, (uint32_t)words,
+		                   stat.p, stat + 4);
+		hipLaunchKernelGGL(remove_word_rank_kernel, dim3(kFilterSegs), dim3(kBlock), 0, st, (const uint32_t*)keep.p,
+		                   (uint32_t)words, (const uint32_t*)(stat + 4), keep + words);
+		HIP_TRY(h, hipGetLastError());
+		const dim3 tiles((uint32_t)(words / 4));
+		HIP_TRY(h, hipMalloc(&base, h->capacity * row_bytes));
+		CompactRowsParams cp{};
+		cp.bits = keep;
+		cp.word_rank = keep + words;
+		cp.src = (const uint4*)h->d_base;
+		cp.dst = base.as<uint4>();
+		cp.chunks = (uint32_t)(row_bytes / 16);
+		hipLaunchKernelGGL(compact_rows_kernel, tiles, dim3(kBlock), 0, st, cp);
+		have_copy = float_rows(h) && h->d_base_f16 && h->f16_scale > 0.0f && h->f16_tb > 0;  // (a complete copy)
+		if (have_copy) {
+			const size_t ld2 = (size_t)f16_ld(h->dim) * 2, alloc = h->f16_rows_alloc;
+			HIP_TRY(h, hipMalloc(&f16, alloc * ld2));
+			HIP_TRY(h, hipMalloc(&bnorm, sizeof(float) * alloc));
+			HIP_TRY(h, hipMalloc(&bns, sizeof(float) * alloc));
+			HIP_TRY(h, hipMalloc(&bnmax, 4 * sizeof(float)));
+			HIP_TRY(h, hipMemsetAsync(f16, 0, alloc * ld2, st));
+			HIP_TRY(h, hipMemsetAsync(bnorm, 0xFF, sizeof(float) * alloc, st));  // 0xFFFFFFFF: a NaN
+			HIP_TRY(h, hipMemsetAsync(bns, 0xFF, sizeof(float) * alloc, st));
+			HIP_TRY(h, hipMemsetAsync(bnmax, 0, 4 * sizeof(float), st));
+			cp.src = h->d_base_f16.as<const uint4>();
+			cp.dst = f16.as<uint4>();
+			cp.chunks = (uint32_t)(ld2 / 16);
+			cp.t0_src = h->d_bnorm_f16;
+			cp.t1_src = h->d_bns_f16;
+			cp.t0_dst = bnorm;
+			cp.t1_dst = bns;
+			hipLaunchKernelGGL(compact_rows_kernel, tiles, dim3(kBlock), 0, st, cp);
+			SurvivorMaximaParams mp;
+			mp.rows = h->d_base;
+			mp.bits = keep;
+			mp.n = (uint32_t)n;
+			mp.d = (uint32_t)h->dim;
+			mp.bnmax_bits = bnmax.as<uint32_t>() + 2;
+			mp.maxabs_bits = stat + 3;
+			const dim3 grid((uint32_t)std::min<size_t>((n + kRowsPerGroup - 1) / kRowsPerGroup, 8192));
+			if (f16_rows(h))
+				hipLaunchKernelGGL(survivor_maxima_kernel<_Float16>, grid, dim3(kBlock), 0, st, mp);
+			else
+				hipLaunchKernelGGL(survivor_maxima_kernel<float>, grid, dim3(kBlock), 0, st, mp);
+		}
+		HIP_TRY(h, hipGetLastError());
+		// the one host wait of a remove
+		HIP_TRY(h, hipMemcpyAsync(seen, stat, sizeof(seen), hipMemcpyDeviceToHost, st));
+		HIP_TRY(h, hipStreamSynchronize(st));
+		return EXPANN_OK;
+	}
+	// (after `st` has drained and plan_remove has accepted)  The rows are replaced: everything that described the
+	// longer index goes, the fp16 copy excepted where the plan carries it over.
+	void commit(expann_index* h, const RemovePlan& plan) {
+		h->stat_remove[1] += h->n - plan.n;
+		h->forget<OtherCopies>();
+		drop_row_filter(h);
+		drop_row_groups(h);
+		h->d_base.own(std::exchange(base.p, nullptr));  // (the capacity is the old one: no "base_reallocs")
+		h->n = plan.n;
+		if (plan.copies == RemoveCopy::kCompact) {
+			h->d_base_f16 = std::move(f16);
+			h->d_bnorm_f16 = std::move(bnorm);
+			h->d_bns_f16 = std::move(bns);
+			h->d_bnmax = std::move(bnmax);  // (slot [1] went with OtherCopies)
+			h->f16_n_pad = (plan.n + h->f16_tb - 1) / h->f16_tb * h->f16_tb;
+			h->f16_maxabs = __builtin_bit_cast(float, seen[3]);
+			h->stat_remove[2]++;
+		} else if (plan.copies == RemoveCopy::kDrop) {
+			// append's kDrop: the copy (or the mark) dies and is made again now where a build makes it.  The rows
+			// are out, so the remove has succeeded whatever becomes of the copy.
+			h->forget<F16Copy>();
+			h->stat_remove[3]++;
+			if (f16_copy_at_build(plan_index(h)))
+				(void)ensure_f16(h, find_f16(f16_geometry(h->dim), h->dim), h->stream);  // (forgets what it began when it fails)
+		}
+	}
+};
+
+// ids: n_ids of them in host (on_device = false) or device memory, read in the order of `user_st`; ids == nullptr with
+// from_filter: the rows the row filter in force disallows
+int remove_rows(expann_index* h, const uint64_t* ids, size_t n_ids, bool on_device, hipStream_t user_st, bool from_filter,
+                size_t* n_removed) {
+	if (!h)
+		return EXPANN_ERR_INVALID_ARG;
+	if (from_filter && !h->filter_on)
+		return h->fail(EXPANN_ERR_INVALID_ARG, "compact_row_filter: no row filter in force");
+	const AppendState state = append_state(h, from_filter || ids != nullptr);
+	RemovePlan plan = plan_remove(state, n_ids);  // (no device call before these checks)
+	if (plan.status != EXPANN_OK)
+		return h->fail(plan.status, plan.message);
+	if (from_filter && h->n_allowed == 0)
+		return h->fail(EXPANN_ERR_INVALID_ARG, "compact_row_filter: the filter allows no row (an index is never empty)");
+	if (n_removed)
+		*n_removed = 0;
+	if (n_ids == 0) {
+		h->stat_remove[0]++;
+		return EXPANN_OK;
+	}
+	HIP_TRY(h, hipSetDevice(h->device));
+	if (const int rc = append_wait(h))
+		return rc;
+	if (from_filter && h->n_allowed == h->n) {  // nothing to remove: the filter goes, every copy stays
+		drop_row_filter(h);
+		h->stat_remove[0]++;
+		return EXPANN_OK;
+	}
+	CompactedRows aside;
+	if (const int rc = aside.build(h, from_filter ? nullptr : ids, n_ids, on_device, user_st ? user_st : h->stream))
+		return rc;
+	plan = plan_remove(state, n_ids, aside.seen[2] != 0, aside.seen[0], __builtin_bit_cast(float, aside.seen[3]));
+	if (plan.status != EXPANN_OK)
+		return h->fail(plan.status, plan.message);
+	const size_t removed = h->n - plan.n;
+	h->stat_remove[0]++;
+	if (removed)
+		aside.commit(h, plan);
+	if (n_removed)
+		*n_removed = removed;
+	return EXPANN_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int expann_remove(expann_index* h, const uint64_t* ids, size_t n_ids, size_t* n_removed) {
+	return remove_rows(h, ids, n_ids, false, nullptr, false, n_removed);
+}
+
+int expann_remove_device(expann_index* h, const uint64_t* d_ids, size_t n_ids, void* stream, size_t* n_removed) {
+	return remove_rows(h, d_ids, n_ids, true, (hipStream_t)stream, false, n_removed);
+}
+
+int expann_compact_row_filter(expann_index* h, size_t* n_removed) {
+	return remove_rows(h, nullptr, 1, false, nullptr, true, n_removed);
+}
+
 int expann_search_device(expann_index* h, const void* d_queries, size_t m, size_t k,
                          uint64_t* d_ids, float* d_dists, void* stream) {
 	if (!h)
@@ -3728,6 +3911,10 @@ int expann_get_stat(expann_index* h, const char* name, uint64_t* out) {
 	    {"append_extends", [](H h) { return h->stat_append[2]; }},
 	    {"append_rebuilds", [](H h) { return h->stat_append[3]; }},
 	    {"base_reallocs", [](H h) { return h->stat_append[4]; }},
+	    {"remove_calls", [](H h) { return h->stat_remove[0]; }},
+	    {"remove_rows", [](H h) { return h->stat_remove[1]; }},
+	    {"remove_compacts", [](H h) { return h->stat_remove[2]; }},
+	    {"remove_rebuilds", [](H h) { return h->stat_remove[3]; }},
 	    {"base_capacity_rows", [](H h) -> uint64_t { return h->d_base ? h->capacity : h->reserved; }},
 	    {"copies_digest", [](H h) { return copies_digest(const_cast<expann_index*>(h)); }},
 	};

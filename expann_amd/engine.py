@@ -96,6 +96,35 @@ class GpuBruteForceEngine:
         Before build() the value is remembered for build()."""
         _lib.check(self._h, self._L.expann_reserve(self._h, int(n)))
 
+    def remove(self, ids):
+        """expann_remove: the rows whose ids (as a search returns them: row numbers) are given, in any order, a
+        repeated id counting once.  The survivors keep their order and move down to fill the gaps -- the row that had
+        id i gets i minus the number of removed ids below i; the caller keeps any external id map -- and every search
+        then answers as a freshly built index of the survivors does, bit for bit.  size() drops, the capacity stays
+        (later appends use the freed room), a row filter and row groups are cleared.  An id >= size() or a removal of
+        every row raises and leaves the index as it was.  During the call the rows take twice their device memory.
+        Returns the number of rows removed."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        removed = C.c_size_t(0)
+        _lib.check(self._h, self._L.expann_remove(self._h, ids.ctypes.data, ids.size, C.byref(removed)))
+        return int(removed.value)
+
+    def remove_device(self, ptr, n, stream=0):
+        """expann_remove_device: n uint64 ids in device memory, read in the order of `stream`; returns the number of
+        rows removed, after the index holds the survivors (the ids may be freed then)."""
+        removed = C.c_size_t(0)
+        _lib.check(self._h, self._L.expann_remove_device(self._h, C.c_void_p(ptr), int(n), C.c_void_p(stream),
+                                                         C.byref(removed)))
+        return int(removed.value)
+
+    def compact_row_filter(self):
+        """expann_compact_row_filter: removes every row the row filter in force disallows, as remove() of those ids
+        does, and clears the filter -- tombstones made permanent.  Raises when no filter is set or when the filter
+        allows no row (the filter then stays).  Returns the number of rows removed."""
+        removed = C.c_size_t(0)
+        _lib.check(self._h, self._L.expann_compact_row_filter(self._h, C.byref(removed)))
+        return int(removed.value)
+
     def query_k(self, v, k):
         """src/brute_force_engine.h:28-46: ids of the min(k, n) nearest rows, ascending."""
         ids, _ = self.query_k_batch(np.asarray(v).reshape(1, -1), k)
@@ -246,7 +275,9 @@ class GpuBruteForceEngine:
         of the last range search "range_list_queries", "range_topk_queries", "range_retries";
         "append_calls", "append_rows", "append_extends", "append_rebuilds", "base_capacity_rows", "base_reallocs" and
         "copies_digest" (a digest of the fp16 copy: equal on an appended and on a freshly built index of the same
-        rows; 0 without a copy)."""
+        rows; 0 without a copy);
+        "remove_calls", "remove_rows" (accepted removes and their rows since create), "remove_compacts" (removes that
+        carried the fp16 copy over), "remove_rebuilds" (removes that dropped it or forgot an unusable mark)."""
         v = C.c_uint64(0)
         _lib.check(self._h, self._L.expann_get_stat(self._h, name.encode(), C.byref(v)))
         return int(v.value)

@@ -114,6 +114,25 @@ struct gpu_brute_force_engine : public ann_engine<T, gpu_brute_force_engine<T>> 
 		}
 		check(expann_reserve(handle, n));
 	}
+	// Extension: rows removed from the built index (expann_remove, THE REMOVE RULE).  ids are the ids a query returns,
+	// in any order, repeats counted once; the survivors keep their order and move down to fill the gaps, so the
+	// caller keeps any external id map; the next stored row gets the id size().  A row filter and row groups are
+	// cleared.  Returns the number of rows removed.  One device; the sharded form does not offer it.
+	size_t remove_rows(const uint64_t* ids, size_t n) {
+		single("remove_rows");
+		size_t removed = 0;
+		check(expann_remove(handle, ids, n, &removed));
+		stored -= removed;
+		return removed;
+	}
+	// ... every row the row filter in force disallows (expann_compact_row_filter); the filter is cleared
+	size_t compact_row_filter() {
+		single("compact_row_filter");
+		size_t removed = 0;
+		check(expann_compact_row_filter(handle, &removed));
+		stored -= removed;
+		return removed;
+	}
 	std::vector<size_t> _query_k(const vec<T>& v, size_t k) {
 		std::vector<T> q(dimension);
 		for (size_t i = 0; i < dimension; ++i)

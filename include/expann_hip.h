@@ -869,14 +869,15 @@ int expann_range_search_device(expann_index* h, const void* d_queries, const flo
  * never on a search path.  Results are exact whatever the copy holds, so only the digest shows that an extended copy
  * IS the fresh one: equal digests on an appended and on a freshly built handle of the same rows).
  * Not offered: appending to rows adopted by expann_set_base_device or to the sharded handles (expann_sharded_add
- * after build still fails); removing rows (the row filter serves as tombstones); keeping a filter or groups across
+ * after build still fails); keeping a filter or groups across
  * an append; a deferred append; in-place extension of the int8 filter's, the uint8 shadow's, the bf16x3 and the
  * 8-bit copies -- they are rebuilt whole at the next search that uses them.  What that costs, measured on a
  * 1 M x d128 fp32 index at default options, where 10 000-query batches run the int8 filter
  * (profiles/bf_append_ab.txt): the first search after an append takes 2.6 .. 2.8 ms against 1.64 ms in steady state,
  * about 1.0 ms once per append -- more than the append itself (0.84 ms for 1 000 rows, against 139 ms for destroy +
  * add + build).  Extending that copy in place would be worth building for a caller that alternates single appends
- * with single batches; at one append per hundred batches it is 0.6 % of the search time. */
+ * with single batches; at one append per hundred batches it is 0.6 % of the search time.  (Removing rows:
+ * expann_remove, at the end of this header.) */
 int expann_append(expann_index* h, const void* rows, size_t n);                          /* host rows   */
 int expann_append_device(expann_index* h, const void* d_rows, size_t n, void* stream);   /* device rows */
 int expann_reserve(expann_index* h, size_t n_rows);
@@ -950,6 +951,70 @@ int expann_antitopo_range_query(expann_antitopo* e, const float* queries, const 
 int expann_antitopo_range_query_device(expann_antitopo* e, const float* d_queries, const float* d_radii, size_t m,
                                        size_t max_results, uint64_t* d_ids, float* d_dists, uint32_t* d_counts,
                                        void* stream);
+
+/* Remove rows from a built brute-force index (appended; EXPANN_ABI_VERSION stays 2: nothing that existed changed,
+ * and a handle that never calls these allocates and launches exactly what it did).  With expann_append this
+ * completes the life of a handle: store, build, query, append, remove, query; an upsert is a remove followed by an
+ * append; tombstones set through the row filter become reclaimed space with one call.
+ * THE REMOVE RULE.
+ * What an id is.  `ids` are the ids a search returns: row numbers.  Only a handle that owns its rows can remove,
+ * and such a handle has id_offset 0.  The ids may come in any order and may repeat; a repeated id counts once.
+ * What the handle holds afterwards.  Let S be the set of distinct ids.  The handle holds the rows not in S, in their
+ * old order; expann_size drops by |S|; the survivor that had id i now has id i - |{s in S : s < i}| -- the
+ * order-preserving shift of a flat index: the caller keeps any external id map, and the next append gets ids
+ * starting at the new size.
+ * Exactness.  EVERY entry point then returns, bit for bit, what a fresh handle made by expann_add of the survivors
+ * in that order, expann_build and the same options returns: ids, fp32 distance bits, ties by lower id, padding and
+ * counts -- expann_search and expann_search_device (latency mode, "async_search" with expann_sync, k up to 8192),
+ * expann_score_ids, expann_range_search*, and the filter, group and append calls issued afterwards.
+ * *n_removed may be NULL; when given it receives |S|.
+ * expann_compact_row_filter removes every row the row filter in force disallows -- the same rule with S = the
+ * disallowed rows -- and clears the filter: it makes the tombstones permanent.
+ * What survives: the options, the profiling state, the statistics, the workspace and the base's CAPACITY --
+ * "base_capacity_rows" is unchanged, so the freed room serves later appends without a reallocation, and a remove
+ * does not count in "base_reallocs" (the base did not grow).  What does not: a row filter and row groups are
+ * CLEARED, as an append clears them; every derived copy except the fp16 copy is forgotten and rebuilt by its next
+ * use, as after an append.
+ * All dtypes: F32, F16, U8, I8 and I16 rows can be removed; the base compaction moves bytes.  Only float rows have
+ * an fp16 copy to carry over.
+ * All three calls first wait on the host for outstanding deferred searches (the append's rule), so every search
+ * runs over the rows that were there when it was enqueued.  One host wait per call, none per search.
+ * expann_remove_device reads d_ids in the order of `stream` (a hipStream_t; NULL = the handle's own); the caller may
+ * free them on return.
+ * THE COPIES (csrc/bf_remove.hpp is the one list of the rules, csrc/remove_rows.hpp the device side).  The scaled
+ * fp16 copy, its two row-term arrays, max ||b||^2 and max |v| describe the rows they were made from, and a row's
+ * fp16 row and terms depend on that row, the dim, the metric and the scale alone.  When the survivors' scale --
+ * 2^floor(log2(32768 / max |v| over the survivors)) -- is the current one, the copy is COMPACTED: the survivors'
+ * fp16 rows and terms are gathered to their new positions, both maxima are recomputed over the survivors with the
+ * bits a fresh build computes, the tiles the scans read shrink to the survivors in whole tiles, and everything
+ * behind the new size is what a build initialises (zero rows, NaN terms: later in-place appends rely on it);
+ * "copies_digest" then equals a fresh handle's.  When the removed rows carried max |v| across a power of two, the
+ * copy is dropped and made again (at once where expann_build would make it, else by the next search; the remove has
+ * succeeded by then whatever becomes of the copy).  When the rows were marked unusable for fp16 (a NaN, an inf, an
+ * astronomically large value) the mark is forgotten -- the survivors may fit -- and the copy is treated as dropped.
+ * BUILT ASIDE.  A base of the same capacity and, where the copy is kept, fp16 arrays of the same size are built
+ * aside, the survivors are compacted into them, and the handle swaps them in only after the one host wait has
+ * shown that everything succeeded.  So a call that fails -- a bad id, a failed allocation -- leaves the handle as
+ * it was and usable; and DURING a call the old and the new base, and the two fp16 copies, are both live: the rows
+ * briefly take twice their memory.
+ * Errors, in this order, all before the device is touched: h == NULL EXPANN_ERR_INVALID_ARG; ids == NULL with
+ * n_ids > 0 EXPANN_ERR_INVALID_ARG; no rows on the device EXPANN_ERR_NOT_BUILT; rows adopted by
+ * expann_set_base_device EXPANN_ERR_UNSUPPORTED.  n_ids == 0 is EXPANN_OK and does nothing.  Then, decided before
+ * any row of the handle changes and learnt at the call's one host wait: an id at or beyond expann_size(h), and a
+ * removal that would leave no row (an index is never empty, as expann_build refuses an empty one), both
+ * EXPANN_ERR_INVALID_ARG.  An id out of range is refused by a comparison made before the bitmap is touched.
+ * expann_compact_row_filter with no filter in force is EXPANN_ERR_INVALID_ARG; with a filter that allows no row
+ * EXPANN_ERR_INVALID_ARG, and the filter stays; a filter that allows every row removes nothing, clears the filter
+ * and keeps every copy.
+ * expann_get_stat: "remove_calls" (accepted calls since create), "remove_rows" (rows removed), "remove_compacts"
+ * (removes that carried the fp16 copy over), "remove_rebuilds" (removes that dropped it or forgot an unusable mark).
+ * Not offered: compaction in place (the rows take twice their memory during a call); shrinking the capacity;
+ * the sharded handles; rows adopted by expann_set_base_device; keeping a filter or groups across a remove; a
+ * deferred remove; stable external ids -- they stay the caller's map. */
+int expann_remove(expann_index* h, const uint64_t* ids, size_t n_ids, size_t* n_removed);             /* host ids   */
+int expann_remove_device(expann_index* h, const uint64_t* d_ids, size_t n_ids, void* stream,
+                         size_t* n_removed);                                                          /* device ids */
+int expann_compact_row_filter(expann_index* h, size_t* n_removed);
 
 #ifdef __cplusplus
 }
