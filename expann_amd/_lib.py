@@ -53,6 +53,9 @@ ABI_SYMBOLS = [
     "expann_remove", "expann_remove_device", "expann_compact_row_filter",
     "expann_graph_range_search", "expann_graph_range_search_device",
     "expann_antitopo_range_query", "expann_antitopo_range_query_device",
+    "expann_antitopo_append", "expann_antitopo_reserve", "expann_antitopo_get_stat",
+    "expann_graph_reserve", "expann_graph_adopt_build_state", "expann_graph_append",
+    "expann_graph_build_state_shape", "expann_graph_read_build_state", "expann_graph_note_host_append",
 ]
 GROUP_ANY = 0xFFFFFFFF  # EXPANN_GROUP_ANY: the group a query names to search every row
 
@@ -360,6 +363,27 @@ def load():
         L.expann_graph_create_f16.argtypes = [C.c_int, C.c_int, vp, sz, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(vp)]
         L.expann_antitopo_set_rows_f16.restype = C.c_int
         L.expann_antitopo_set_rows_f16.argtypes = [vp, C.c_int]
+    if hasattr(L, "expann_antitopo_append"):  # (as above: an older build cannot append to a graph)
+        szp = C.POINTER(C.c_size_t)
+        L.expann_antitopo_append.restype = C.c_int
+        L.expann_antitopo_append.argtypes = [vp, vp, sz, szp]
+        L.expann_antitopo_reserve.restype = C.c_int
+        L.expann_antitopo_reserve.argtypes = [vp, sz]
+        L.expann_antitopo_get_stat.restype = C.c_int
+        L.expann_antitopo_get_stat.argtypes = [vp, C.c_char_p, C.POINTER(C.c_uint64)]
+        L.expann_graph_reserve.restype = C.c_int
+        L.expann_graph_reserve.argtypes = [vp, sz]
+        L.expann_graph_adopt_build_state.restype = C.c_int
+        L.expann_graph_adopt_build_state.argtypes = [vp, sz, sz, sz, sz, C.c_float, C.c_float, vp, vp, vp, vp, vp, sz, sz,
+                                                     sz, vp, vp, vp, sz]
+        L.expann_graph_append.restype = C.c_int
+        L.expann_graph_append.argtypes = [vp, vp, sz, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), szp]
+        L.expann_graph_build_state_shape.restype = C.c_int
+        L.expann_graph_build_state_shape.argtypes = [vp, szp]
+        L.expann_graph_read_build_state.restype = C.c_int
+        L.expann_graph_read_build_state.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.expann_graph_note_host_append.restype = C.c_int
+        L.expann_graph_note_host_append.argtypes = [vp, C.POINTER(C.c_uint64), sz]
     _lib = L
     return L
 

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "filter_rows.hpp"
+#include "graph_append.hpp"
 #include "graph_build.hpp"
 #include "graph_flat_scan.hpp"
 #include "graph_options.hpp"
@@ -42,6 +43,9 @@ struct GraphRows {
 	DevPtr<uint32_t> d_neighbours;
 	DevPtr<uint32_t> d_adj0;  // [n][stride0] layer-0 lists at a fixed stride, padded with UINT32_MAX
 	uint32_t stride0 = 0;
+	// rows that d_vectors, d_adj0 and the visited sets have room for: n at create, more after expann_graph_reserve or
+	// an append that grew them (THE GRAPH APPEND RULE)
+	size_t cap_rows = 0;
 };
 
 // the byte copies of the rows, each made at the first use of its mode
@@ -81,6 +85,40 @@ struct GraphDeviceSearches {
 	uint64_t pend_redo_queries = 0, pend_overflows = 0;  // what the drains since the last sync found
 };
 
+// The builder's view of the graph, resident from the handle's first append (expann_graph_adopt_build_state): the
+// fixed-stride rows of graph_build.hpp's BuildGraph, every array sized to GraphRows::cap_rows, and the scratch of a
+// batch.  BuildGraph::vec is d_vectors: the rows are not kept twice.  The CSR and d_adj0 are remade from it after
+// every append (graph_append.hpp); the upper-layer arrays have capacities of their own and are laid out again when
+// the upper vertices or the layers outgrow them.
+struct GraphBuildState {
+	bool resident = false;
+	size_t M = 0, M0 = 0, ef_construction = 0, prune_overflow = 0;
+	float ortho_factor = 0, ortho_bias = 0;
+	uint32_t bstride0 = 0, bstrideu = 0;  // row strides of the builder's arrays: M0 / M plus the slack for reverse edges
+	size_t U = 0;                         // upper-layer vertices
+	size_t U_cap = 0, L_cap = 0;          // the upper arrays hold [L_cap][U_cap] rows: row (l - 1) * U_cap + upper_idx[v]
+	size_t edge_cap = 0, off_cap = 0;     // words of d_neighbours / d_layer_off
+	size_t dirty_cap = 0, tiles_cap = 0;
+	DevPtr<uint8_t> d_level;      // [cap_rows]
+	DevPtr<int32_t> d_upper_idx;  // [cap_rows]
+	DevPtr<uint32_t> d_id0;       // [cap_rows][bstride0]
+	DevPtr<float> d_d0;
+	DevPtr<uint32_t> d_deg0;      // [cap_rows]
+	DevPtr<uint32_t> d_idu;       // [L_cap * U_cap][bstrideu]
+	DevPtr<float> d_du;
+	DevPtr<uint32_t> d_degu;      // [L_cap * U_cap]
+	// a batch's search lists, prune tasks and counters (expann_graph_build_batched makes the same per call)
+	DevPtr<md_pair> d_out;
+	DevPtr<uint32_t> d_out_cnt;
+	DevPtr<PruneTask> d_tasks;
+	DevPtr<int32_t> d_up_slot;
+	DevPtr<uint2> d_dirty;        // [dirty_cap]
+	DevPtr<uint32_t> d_build_ctr; // [8]
+	DevPtr<uint32_t> d_tile_sums; // [tiles_cap] the scan's tile sums
+	OwnedEvent ev_tables[2];      // around the last rebuild of the walk's tables
+	uint64_t tables_ns = 0, n_edges = 0;  // its device time; the edges of the CSR it made
+};
+
 // row filter (expann_graph_set_row_filter): the handle's copy of the bitmap, zero from n on, and the allowed
 // vertices as an ascending list (what the scan of a sparse filter reads), both made at set time
 struct GraphRowFilter {
@@ -110,6 +148,8 @@ struct GraphStats {
 	uint64_t stat_redo_queries = 0, stat_redo_overflows = 0, stat_deferred = 0, stat_distcomps = 0;
 	uint64_t stat_range = 0;  // range searches since create, from either entry point
 	double stat_redo_ms = 0;
+	// appends {calls, rows, batches, served on the device, served by the host route, capacity growths}
+	uint64_t stat_append[6] = {0, 0, 0, 0, 0, 0};
 };
 
 // the handle's own stream, the host-buffer calls' events, launch plans, statistics, the last error
@@ -129,8 +169,8 @@ struct GraphRuntime : GraphStats {
 };
 
 // (base order: the stream and its events outlive every buffer when a handle is deleted)
-struct expann_graph : GraphOptions, GraphRuntime, GraphRows, GraphRowBytes, GraphVisited, GraphDeviceSearches, GraphRowFilter,
-                      GraphRowGroups {
+struct expann_graph : GraphOptions, GraphRuntime, GraphRows, GraphBuildState, GraphRowBytes, GraphVisited,
+                      GraphDeviceSearches, GraphRowFilter, GraphRowGroups {
 	template <typename Group> void forget() { static_cast<Group&>(*this) = Group{}; }
 	int fail(int code, const std::string& msg) const {
 		err = msg;
@@ -975,7 +1015,7 @@ static int graph_create(const char* fn_name, size_t elem_bytes, int dim, int dev
 	std::unique_ptr<expann_graph, GraphDeleter> g(new expann_graph());
 	g->dim = dim;
 	g->device = device;
-	g->n = n;
+	g->n = g->cap_rows = n;
 	g->n_layers = n_layers;
 	g->starting_vertex = starting_vertex;
 	g->rows_f16 = elem_bytes == 2;
@@ -1424,6 +1464,19 @@ int expann_graph_get_stat(expann_graph* g, const char* name, uint64_t* out) {
 	static const StatRow kGraphRangeStatTable[] = {
 	    {"range_searches", [](G g) { return g->stat_range; }},  // since create, from either entry point
 	};
+	// the append's rows (THE GRAPH APPEND RULE)
+	static const StatRow kGraphAppendStatTable[] = {
+	    {"append_calls", [](G g) { return g->stat_append[0]; }},
+	    {"append_rows", [](G g) { return g->stat_append[1]; }},
+	    {"append_batches", [](G g) { return g->stat_append[2]; }},
+	    {"append_device", [](G g) { return g->stat_append[3]; }},
+	    {"append_host", [](G g) { return g->stat_append[4]; }},
+	    {"graph_reallocs", [](G g) { return g->stat_append[5]; }},
+	    {"capacity_rows", [](G g) { return (uint64_t)g->cap_rows; }},
+	    // the last rebuild of the walk's tables from the resident state: device time, edges of all layers
+	    {"append_tables_ns", [](G g) { return g->tables_ns; }},
+	    {"append_edges", [](G g) { return g->n_edges; }},
+	};
 	auto read_from = [&](const StatRow* rows, size_t n_rows) {
 		for (size_t i = 0; i < n_rows; ++i)
 			if (!std::strcmp(name, rows[i].name)) {
@@ -1433,7 +1486,8 @@ int expann_graph_get_stat(expann_graph* g, const char* name, uint64_t* out) {
 		return false;
 	};
 	if (read_from(kGraphStatTable, sizeof(kGraphStatTable) / sizeof(StatRow)) ||
-	    read_from(kGraphRangeStatTable, sizeof(kGraphRangeStatTable) / sizeof(StatRow)))
+	    read_from(kGraphRangeStatTable, sizeof(kGraphRangeStatTable) / sizeof(StatRow)) ||
+	    read_from(kGraphAppendStatTable, sizeof(kGraphAppendStatTable) / sizeof(StatRow)))
 		return EXPANN_OK;
 	return g->fail(EXPANN_ERR_INVALID_ARG, std::string("unknown stat: ") + name);
 }
@@ -1503,6 +1557,179 @@ const BuildVariant kBuild[] = {BUILD_V(64),  BUILD_V(128), BUILD_V(256), BUILD_V
 struct BuildFail {
 	std::string msg;
 };
+const BuildVariant* build_variant(int dim) {
+	const BuildVariant* bv = &kBuild[sizeof(kBuild) / sizeof(kBuild[0]) - 1];  // (d = 0: run-time dim)
+	for (const auto& v : kBuild)
+		if (v.d == dim)
+			bv = &v;
+	return bv;
+}
+
+// The batch loop of THE BATCH RULE over device arrays: expann_graph_build_batched runs it over arrays it makes for
+// the call, expann_graph_append over the handle's resident builder state.  The caller fills everything down to
+// `resident`; build_batches_geometry derives the launch geometry.
+struct BuildBatches {
+	const BuildVariant* bv;
+	BuildGraph g;
+	hipStream_t st;
+	int dim, cus;
+	const uint8_t* levels;  // host: the level of vertex v is levels[v - level_base]
+	size_t level_base;
+	size_t b0, n;           // vertices [b0, n) are inserted; b0 ends behind the last batch that is in
+	uint32_t max_layer, starting_vertex;  // in and out
+	size_t max_batch, ef, prune_overflow;
+	float ortho_factor, ortho_bias;
+	uint32_t* vis_bits;     // [slots][vis_words], all zero between searches
+	uint32_t vis_words;
+	md_pair* out;           // [max_batch + max_up_in_batch][ef]
+	uint32_t* out_cnt;
+	PruneTask* tasks;
+	int32_t* up_slot;       // [max_batch]
+	uint2* dirty;
+	size_t dirty_cap;
+	uint32_t* ctr;          // [8], zero: [0] n_dirty, [1] dropped, [2] search overflow, [3] n_tasks
+	// the resident form: the search's overflow counter is read before the batch's prune and reverse launches, so a
+	// batch that overflows leaves the graph as it was; that wait is the batch's only one
+	bool resident;
+	// geometry
+	size_t max_up_in_batch, search_lds, prune_lds;
+	uint32_t list_cap, cand_cap;
+	uint64_t slots;         // resident search workgroups
+	// out
+	uint64_t n_batches = 0, n_dirty_total = 0;
+};
+extern "C++" {  // (templates: this namespace sits inside the C ABI's linkage block)
+template <typename F> int build_batches_geometry(F* fh, BuildBatches& r, bool upper_layers) {
+	if (r.max_batch == 0)
+		r.max_batch = 32768;
+	// search: one wave per new vertex; LDS = nearest heap + candidates heap + a hop's neighbour list
+	r.list_cap = (uint32_t)std::max<size_t>(r.g.stride0, std::max<size_t>(r.g.strideu, r.ef));
+	r.cand_cap = 8192;
+	r.search_lds = sizeof(md_pair) * (r.ef + 1 + r.cand_cap + 1) + (sizeof(uint32_t) + sizeof(float)) * r.list_cap +
+	               8 * sizeof(uint32_t) +
+	               (r.bv->d == 0 ? (size_t)r.dim * sizeof(float) : 0);  // (run-time dim: the new row in LDS)
+	// the prune kernel of the run-time-dim instance keeps the kept edge's row in dynamic LDS
+	r.prune_lds = r.bv->d == 0 ? (size_t)r.dim * sizeof(float) : 0;
+	HIP_TRY(fh, hipFuncSetAttribute((const void*)r.bv->search, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.search_lds));
+	r.slots = (uint64_t)r.cus * 2;  // resident search workgroups (two 72 KB workgroups per CU)
+	r.max_up_in_batch = r.max_batch * (upper_layers ? 1 : 0) + 64;  // (bounded below per batch)
+	return EXPANN_OK;
+}
+template <typename F> int build_run_batches(F* fh, BuildBatches& r) {
+	const BuildVariant* bv = r.bv;
+	const BuildGraph& g = r.g;
+	hipStream_t st = r.st;
+	uint32_t* ctr = r.ctr;
+	auto level_of = [&](size_t v) { return r.levels[v - r.level_base]; };
+	const char* overflow = "construction search: candidates queue overflowed its LDS capacity";
+	std::vector<PruneTask> tasks;
+	std::vector<int32_t> up_slot;
+	while (r.b0 < r.n) {
+		const size_t b0 = r.b0;
+		// a batch: at most 1/16 of the graph so far (its members do not see each other: measured
+		// recall@10 at ef = 10, 12 k rows, M = 16: serial 0.384, batches of 1/8 0.354); a vertex that
+		// opens a new layer goes alone
+		size_t b1 = std::min(r.n, b0 + std::min(r.max_batch, std::max<size_t>(1, b0 / 16)));
+		for (size_t v = b0; v < b1; ++v)
+			if (level_of(v) >= r.max_layer) {
+				b1 = v == b0 ? v + 1 : v;
+				break;
+			}
+		const uint32_t B = (uint32_t)(b1 - b0);
+		tasks.clear();
+		up_slot.assign(B, -1);
+		uint32_t n_up = 0;
+		for (uint32_t i = 0; i < B; ++i)
+			tasks.push_back(PruneTask{(uint32_t)(b0 + i), 0u, (int32_t)i});
+		for (uint32_t i = 0; i < B; ++i) {
+			const uint32_t lv = std::min<uint32_t>(level_of(b0 + i), r.max_layer - 1);
+			if (lv >= 1) {
+				up_slot[i] = (int32_t)n_up;
+				for (uint32_t l = 1; l <= lv; ++l)
+					tasks.push_back(PruneTask{(uint32_t)(b0 + i), l, (int32_t)(B + n_up + l - 1)});
+				n_up += lv;
+			}
+		}
+		if (n_up > r.max_up_in_batch)
+			return fh->fail(EXPANN_ERR_UNSUPPORTED, "more upper-layer vertices in a batch than provisioned");
+		const uint32_t n_tasks = (uint32_t)tasks.size();
+		HIP_TRY(fh, hipMemcpyAsync(r.tasks, tasks.data(), sizeof(PruneTask) * n_tasks, hipMemcpyHostToDevice, st));
+		HIP_TRY(fh, hipMemcpyAsync(r.up_slot, up_slot.data(), 4 * B, hipMemcpyHostToDevice, st));
+		HIP_TRY(fh, hipMemcpyAsync(ctr + 3, &n_tasks, 4, hipMemcpyHostToDevice, st));
+		HIP_TRY(fh, hipMemsetAsync(ctr, 0, 4, st));
+		BuildSearchParams sp{};
+		sp.g = g;
+		sp.b0 = (uint32_t)b0;
+		sp.b1 = (uint32_t)b1;
+		sp.max_layer = r.max_layer;
+		sp.starting_vertex = r.starting_vertex;
+		sp.ef = (uint32_t)r.ef;
+		sp.cand_cap = r.cand_cap;
+		sp.list_cap = r.list_cap;
+		sp.vis_bits = r.vis_bits;
+		sp.vis_words = r.vis_words;
+		sp.up_slot = r.up_slot;
+		sp.out = r.out;
+		sp.out_cnt = r.out_cnt;
+		sp.error = ctr + 2;
+		sp.dim = (uint32_t)r.dim;
+		hipLaunchKernelGGL(bv->search, dim3((uint32_t)std::min<uint64_t>(B, r.slots)), dim3(64), r.search_lds, st, sp);
+		uint32_t h_ctr[4];
+		if (r.resident) {
+			HIP_TRY(fh, hipGetLastError());
+			HIP_TRY(fh, hipMemcpyAsync(h_ctr, ctr, sizeof(h_ctr), hipMemcpyDeviceToHost, st));
+			HIP_TRY(fh, hipStreamSynchronize(st));
+			if (h_ctr[2])
+				return fh->fail(EXPANN_ERR_OVERFLOW, overflow);
+		}
+		BuildPruneParams pp{};
+		pp.g = g;
+		pp.tasks = r.tasks;
+		pp.n_tasks = ctr + 3;
+		pp.lists = r.out;
+		pp.list_cnt = r.out_cnt;
+		pp.ef = (uint32_t)r.ef;
+		pp.ortho_factor = r.ortho_factor;
+		pp.ortho_bias = r.ortho_bias;
+		pp.prune_overflow = (uint32_t)r.prune_overflow;
+		pp.dim = (uint32_t)r.dim;
+		hipLaunchKernelGGL(bv->prune, dim3(std::min<uint32_t>(n_tasks, (uint32_t)r.cus * 16)), dim3(kPruneThreads), r.prune_lds, st, pp);
+		BuildReverseParams rp{};
+		rp.g = g;
+		rp.tasks = r.tasks;
+		rp.n_tasks = n_tasks;
+		rp.dirty = r.dirty;
+		rp.n_dirty = ctr;
+		rp.dirty_cap = (uint32_t)r.dirty_cap;
+		rp.dropped = ctr + 1;
+		hipLaunchKernelGGL(build_reverse_kernel, dim3((n_tasks + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock), 0, st, rp);
+		// the rows that outgrew their cap: clamp to the slack, prune (grid-stride over the dirty list)
+		hipLaunchKernelGGL(build_clamp_kernel, dim3((uint32_t)((r.dirty_cap + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, g,
+		                   (const uint2*)r.dirty, (const uint32_t*)ctr);
+		BuildPruneParams dp = pp;
+		dp.tasks = nullptr;
+		dp.n_tasks = ctr;
+		dp.dirty = r.dirty;
+		hipLaunchKernelGGL(bv->prune, dim3((uint32_t)r.cus * 16), dim3(kPruneThreads), r.prune_lds, st, dp);
+		HIP_TRY(fh, hipGetLastError());
+		if (!r.resident) {
+			HIP_TRY(fh, hipMemcpyAsync(h_ctr, ctr, sizeof(h_ctr), hipMemcpyDeviceToHost, st));
+			HIP_TRY(fh, hipStreamSynchronize(st));
+			if (h_ctr[2])
+				return fh->fail(EXPANN_ERR_OVERFLOW, overflow);
+			r.n_dirty_total += h_ctr[0];
+		}
+		++r.n_batches;
+		for (size_t v = b0; v < b1; ++v)  // :461-464
+			while (level_of(v) >= r.max_layer) {
+				++r.max_layer;
+				r.starting_vertex = (uint32_t)v;
+			}
+		r.b0 = b1;
+	}
+	return EXPANN_OK;
+}
+}  // extern "C++"
 }  // namespace
 
 int expann_graph_build_batched(int dim, int device, const float* vectors, size_t n, const uint8_t* levels,
@@ -1513,10 +1740,7 @@ int expann_graph_build_batched(int dim, int device, const float* vectors, size_t
                                uint32_t* idsu, float* du, uint32_t* degu, size_t strideu, uint64_t* stats) {
 	if (int rc = graph_dim_error("expann_graph_build_batched", dim))
 		return rc;
-	const BuildVariant* bv = &kBuild[sizeof(kBuild) / sizeof(kBuild[0]) - 1];  // (d = 0: run-time dim)
-	for (const auto& v : kBuild)
-		if (v.d == dim)
-			bv = &v;
+	const BuildVariant* bv = build_variant(dim);
 	if (!vectors || !levels || !max_layer_io || !starting_vertex_io || !ids0 || !d0 || !deg0 || !upper_idx ||
 	    n == 0 || n_built == 0 || n_built > n || n >= (1ull << 32) - 64 || M < 2 || M0 < M || stride0 < M0 ||
 	    (n_upper_layers && (!idsu || !du || !degu || strideu < M)) || ef_construction == 0 ||
@@ -1570,7 +1794,24 @@ int expann_graph_build_batched(int dim, int device, const float* vectors, size_t
 		HIP_TRY(fh, hipMemcpy(b_du.p, du, n_up_rows * strideu * 4, hipMemcpyHostToDevice));
 		HIP_TRY(fh, hipMemcpy(b_degu.p, degu, n_up_rows * 4, hipMemcpyHostToDevice));
 	}
-	BuildGraph g{};
+	BuildBatches r{};
+	r.bv = bv;
+	r.st = st;
+	r.dim = dim;
+	r.cus = num_cus(device);
+	r.levels = levels;
+	r.level_base = 0;
+	r.b0 = n_built;
+	r.n = n;
+	r.max_layer = *max_layer_io;
+	r.starting_vertex = *starting_vertex_io;
+	r.max_batch = max_batch;
+	r.ef = ef_construction;
+	r.prune_overflow = prune_overflow;
+	r.ortho_factor = ortho_factor;
+	r.ortho_bias = ortho_bias;
+	r.resident = false;
+	BuildGraph& g = r.g;
 	g.vec = b_vec.as<float>();
 	g.n = (uint32_t)n;
 	g.level = b_lvl.as<uint8_t>();
@@ -1586,133 +1827,32 @@ int expann_graph_build_batched(int dim, int device, const float* vectors, size_t
 	g.capu = (uint32_t)M;
 	g.strideu = (uint32_t)strideu;
 	g.U = (uint32_t)U;
-
-	const int cus = num_cus(device);
-	if (max_batch == 0)
-		max_batch = 32768;
-	// search: one wave per new vertex; LDS = nearest heap + candidates heap + a hop's neighbour list
-	const uint32_t list_cap = (uint32_t)std::max(stride0, std::max(strideu, ef_construction));
-	uint32_t cand_cap = 8192;
-	const size_t search_lds = sizeof(md_pair) * (ef_construction + 1 + cand_cap + 1) +
-	                          (sizeof(uint32_t) + sizeof(float)) * list_cap + 8 * sizeof(uint32_t) +
-	                          (bv->d == 0 ? (size_t)dim * sizeof(float) : 0);  // (run-time dim: the new row in LDS)
-	// the prune kernel of the run-time-dim instance keeps the kept edge's row in dynamic LDS
-	const size_t prune_lds = bv->d == 0 ? (size_t)dim * sizeof(float) : 0;
-	HIP_TRY(fh, hipFuncSetAttribute((const void*)bv->search, hipFuncAttributeMaxDynamicSharedMemorySize, (int)search_lds));
-	uint64_t slots = (uint64_t)cus * 2;  // resident search workgroups (two 72 KB workgroups per CU)
+	if (int rc = build_batches_geometry(fh, r, n_upper_layers != 0))
+		return rc;
 	// one visited bitset per resident workgroup, all zero between searches (graph_search.hpp)
-	const uint32_t vis_words = (uint32_t)((n + 8191) / 8192 * 256);
-	HIP_TRY(fh, b_vis.alloc(slots * vis_words * 4));
-	HIP_TRY(fh, hipMemset(b_vis.p, 0, slots * vis_words * 4));
-	const size_t max_up_in_batch = max_batch * (n_upper_layers ? 1 : 0) + 64;  // (bounded below per batch)
-	HIP_TRY(fh, b_out.alloc((max_batch + max_up_in_batch) * ef_construction * sizeof(md_pair)));
-	HIP_TRY(fh, b_outc.alloc((max_batch + max_up_in_batch) * 4));
-	HIP_TRY(fh, b_tasks.alloc((max_batch + max_up_in_batch) * sizeof(PruneTask)));
-	HIP_TRY(fh, b_upslot.alloc(max_batch * 4));
-	const size_t dirty_cap = n + n_up_rows + 1;
-	HIP_TRY(fh, b_dirty.alloc(dirty_cap * sizeof(uint2)));
+	r.vis_words = (uint32_t)((n + 8191) / 8192 * 256);
+	HIP_TRY(fh, b_vis.alloc(r.slots * r.vis_words * 4));
+	HIP_TRY(fh, hipMemset(b_vis.p, 0, r.slots * r.vis_words * 4));
+	HIP_TRY(fh, b_out.alloc((r.max_batch + r.max_up_in_batch) * ef_construction * sizeof(md_pair)));
+	HIP_TRY(fh, b_outc.alloc((r.max_batch + r.max_up_in_batch) * 4));
+	HIP_TRY(fh, b_tasks.alloc((r.max_batch + r.max_up_in_batch) * sizeof(PruneTask)));
+	HIP_TRY(fh, b_upslot.alloc(r.max_batch * 4));
+	r.dirty_cap = n + n_up_rows + 1;
+	HIP_TRY(fh, b_dirty.alloc(r.dirty_cap * sizeof(uint2)));
 	HIP_TRY(fh, b_ctr.alloc(8 * 4));  // [0] n_dirty, [1] dropped, [2] search overflow, [3] n_tasks
 	HIP_TRY(fh, hipMemset(b_ctr.p, 0, 8 * 4));
 	uint32_t* ctr = b_ctr.as<uint32_t>();
-
-	uint32_t max_layer = *max_layer_io, starting_vertex = *starting_vertex_io;
-	uint64_t n_batches = 0, n_dirty_total = 0;
-	std::vector<PruneTask> tasks;
-	std::vector<int32_t> up_slot;
-	size_t b0 = n_built;
-	while (b0 < n) {
-		// a batch: at most 1/16 of the graph so far (its members do not see each other: measured
-		// recall@10 at ef = 10, 12 k rows, M = 16: serial 0.384, batches of 1/8 0.354); a vertex that
-		// opens a new layer goes alone
-		size_t b1 = std::min(n, b0 + std::min(max_batch, std::max<size_t>(1, b0 / 16)));
-		for (size_t v = b0; v < b1; ++v)
-			if (levels[v] >= max_layer) {
-				b1 = v == b0 ? v + 1 : v;
-				break;
-			}
-		const uint32_t B = (uint32_t)(b1 - b0);
-		tasks.clear();
-		up_slot.assign(B, -1);
-		uint32_t n_up = 0;
-		for (uint32_t i = 0; i < B; ++i)
-			tasks.push_back(PruneTask{(uint32_t)(b0 + i), 0u, (int32_t)i});
-		for (uint32_t i = 0; i < B; ++i) {
-			const uint32_t lv = std::min<uint32_t>(levels[b0 + i], max_layer - 1);
-			if (lv >= 1) {
-				up_slot[i] = (int32_t)n_up;
-				for (uint32_t l = 1; l <= lv; ++l)
-					tasks.push_back(PruneTask{(uint32_t)(b0 + i), l, (int32_t)(B + n_up + l - 1)});
-				n_up += lv;
-			}
-		}
-		if (n_up > max_up_in_batch)
-			return F.fail(EXPANN_ERR_UNSUPPORTED, "more upper-layer vertices in a batch than provisioned");
-		const uint32_t n_tasks = (uint32_t)tasks.size();
-		HIP_TRY(fh, hipMemcpyAsync(b_tasks.p, tasks.data(), sizeof(PruneTask) * n_tasks, hipMemcpyHostToDevice, st));
-		HIP_TRY(fh, hipMemcpyAsync(b_upslot.p, up_slot.data(), 4 * B, hipMemcpyHostToDevice, st));
-		HIP_TRY(fh, hipMemcpyAsync(ctr + 3, &n_tasks, 4, hipMemcpyHostToDevice, st));
-		HIP_TRY(fh, hipMemsetAsync(ctr, 0, 4, st));
-		BuildSearchParams sp{};
-		sp.g = g;
-		sp.b0 = (uint32_t)b0;
-		sp.b1 = (uint32_t)b1;
-		sp.max_layer = max_layer;
-		sp.starting_vertex = starting_vertex;
-		sp.ef = (uint32_t)ef_construction;
-		sp.cand_cap = cand_cap;
-		sp.list_cap = list_cap;
-		sp.vis_bits = b_vis.as<uint32_t>();
-		sp.vis_words = vis_words;
-		sp.up_slot = b_upslot.as<int32_t>();
-		sp.out = b_out.as<md_pair>();
-		sp.out_cnt = b_outc.as<uint32_t>();
-		sp.error = ctr + 2;
-		sp.dim = (uint32_t)dim;
-		hipLaunchKernelGGL(bv->search, dim3((uint32_t)std::min<uint64_t>(B, slots)), dim3(64), search_lds, st, sp);
-		BuildPruneParams pp{};
-		pp.g = g;
-		pp.tasks = b_tasks.as<PruneTask>();
-		pp.n_tasks = ctr + 3;
-		pp.lists = b_out.as<md_pair>();
-		pp.list_cnt = b_outc.as<uint32_t>();
-		pp.ef = (uint32_t)ef_construction;
-		pp.ortho_factor = ortho_factor;
-		pp.ortho_bias = ortho_bias;
-		pp.prune_overflow = (uint32_t)prune_overflow;
-		pp.dim = (uint32_t)dim;
-		hipLaunchKernelGGL(bv->prune, dim3(std::min<uint32_t>(n_tasks, (uint32_t)cus * 16)), dim3(kPruneThreads), prune_lds, st, pp);
-		BuildReverseParams rp{};
-		rp.g = g;
-		rp.tasks = b_tasks.as<PruneTask>();
-		rp.n_tasks = n_tasks;
-		rp.dirty = b_dirty.as<uint2>();
-		rp.n_dirty = ctr;
-		rp.dirty_cap = (uint32_t)dirty_cap;
-		rp.dropped = ctr + 1;
-		hipLaunchKernelGGL(build_reverse_kernel, dim3((n_tasks + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock), 0, st, rp);
-		// the rows that outgrew their cap: clamp to the slack, prune (grid-stride over the dirty list)
-		hipLaunchKernelGGL(build_clamp_kernel, dim3((uint32_t)((dirty_cap + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, g,
-		                   (const uint2*)b_dirty.p, (const uint32_t*)ctr);
-		BuildPruneParams dp = pp;
-		dp.tasks = nullptr;
-		dp.n_tasks = ctr;
-		dp.dirty = b_dirty.as<uint2>();
-		hipLaunchKernelGGL(bv->prune, dim3((uint32_t)cus * 16), dim3(kPruneThreads), prune_lds, st, dp);
-		HIP_TRY(fh, hipGetLastError());
-		uint32_t h_ctr[4];
-		HIP_TRY(fh, hipMemcpyAsync(h_ctr, ctr, sizeof(h_ctr), hipMemcpyDeviceToHost, st));
-		HIP_TRY(fh, hipStreamSynchronize(st));
-		if (h_ctr[2])
-			return F.fail(EXPANN_ERR_OVERFLOW, "construction search: candidates queue overflowed its LDS capacity");
-		n_dirty_total += h_ctr[0];
-		++n_batches;
-		for (size_t v = b0; v < b1; ++v)  // :461-464
-			while (levels[v] >= max_layer) {
-				++max_layer;
-				starting_vertex = (uint32_t)v;
-			}
-		b0 = b1;
-	}
+	r.vis_bits = b_vis.as<uint32_t>();
+	r.out = b_out.as<md_pair>();
+	r.out_cnt = b_outc.as<uint32_t>();
+	r.tasks = b_tasks.as<PruneTask>();
+	r.up_slot = b_upslot.as<int32_t>();
+	r.dirty = b_dirty.as<uint2>();
+	r.ctr = ctr;
+	if (int rc = build_run_batches(fh, r))
+		return rc;
+	const uint32_t max_layer = r.max_layer, starting_vertex = r.starting_vertex;
+	const uint64_t n_batches = r.n_batches, n_dirty_total = r.n_dirty_total;
 	HIP_TRY(fh, hipMemcpy(ids0, b_id0.p, n * stride0 * 4, hipMemcpyDeviceToHost));
 	HIP_TRY(fh, hipMemcpy(d0, b_d0.p, n * stride0 * 4, hipMemcpyDeviceToHost));
 	HIP_TRY(fh, hipMemcpy(deg0, b_deg0.p, n * 4, hipMemcpyDeviceToHost));
@@ -1731,6 +1871,439 @@ int expann_graph_build_batched(int dim, int device, const float* vectors, size_t
 		stats[2] = n_dirty_total;
 		stats[3] = h_ctr[2];
 	}
+	return EXPANN_OK;
+}
+
+}  // extern "C"
+
+// ---- appends to a built graph: the builder's state resident in the handle (THE GRAPH APPEND RULE) ----------
+namespace {
+// `a` becomes an array of cap_bytes that starts with its first keep_bytes (zero behind them when `zero`); the old
+// block goes once the copy is done
+template <typename T> int graph_regrow(expann_graph* g, DevPtr<T>& a, size_t keep_bytes, size_t cap_bytes, bool zero = false) {
+	DevPtr<T> b;
+	HIP_TRY(g, hipMalloc(&b, std::max<size_t>(cap_bytes, 1)));
+	if (zero)
+		HIP_TRY(g, hipMemsetAsync(b, 0, cap_bytes, g->stream));
+	if (keep_bytes)
+		HIP_TRY(g, hipMemcpyAsync(b, a, keep_bytes, hipMemcpyDeviceToDevice, g->stream));
+	HIP_TRY(g, hipStreamSynchronize(g->stream));
+	a = std::move(b);
+	return EXPANN_OK;
+}
+
+BuildGraph graph_build_view(const expann_graph* g) {
+	BuildGraph b{};
+	b.vec = g->d_vectors.as<const float>();
+	b.n = (uint32_t)g->n;
+	b.level = g->d_level;
+	b.upper_idx = g->d_upper_idx;
+	b.id0 = g->d_id0;
+	b.d0 = g->d_d0;
+	b.deg0 = g->d_deg0;
+	b.cap0 = (uint32_t)g->M0;
+	b.stride0 = g->bstride0;
+	b.idu = g->d_idu;
+	b.du = g->d_du;
+	b.degu = g->d_degu;
+	b.capu = (uint32_t)g->M;
+	b.strideu = g->bstrideu;
+	b.U = (uint32_t)g->U_cap;
+	return b;
+}
+
+// what is sized by (cap_rows, U_cap, L_cap) and holds nothing between two rebuilds of the tables: the CSR, the dirty
+// list, the scan's tile sums.  The CSR's CONTENT is lost when it grows: the caller rebuilds the tables.
+int graph_size_derived(expann_graph* g) {
+	const size_t off = (g->L_cap + 1) * (g->cap_rows + 1), edges = g->cap_rows * g->M0 + g->L_cap * g->U_cap * g->M;
+	if (off >= (1ull << 32) || edges >= (1ull << 32))
+		return g->fail(EXPANN_ERR_UNSUPPORTED, "the capacity would take more than 2^32 edges or offsets");
+	if (off > g->off_cap) {
+		g->d_layer_off.reset();
+		HIP_TRY(g, hipMalloc(&g->d_layer_off, off * sizeof(uint32_t)));
+		g->off_cap = off;
+		g->tiles_cap = (off + kScanTile - 1) / kScanTile;
+		g->d_tile_sums.reset();
+		HIP_TRY(g, hipMalloc(&g->d_tile_sums, g->tiles_cap * sizeof(uint32_t)));
+	}
+	if (edges > g->edge_cap) {
+		g->d_neighbours.reset();
+		HIP_TRY(g, hipMalloc(&g->d_neighbours, std::max<size_t>(edges, 1) * sizeof(uint32_t)));
+		g->edge_cap = edges;
+	}
+	const size_t dirty = g->cap_rows + g->L_cap * g->U_cap + 1;
+	if (dirty > g->dirty_cap) {
+		g->d_dirty.reset();
+		HIP_TRY(g, hipMalloc(&g->d_dirty, dirty * sizeof(uint2)));
+		g->dirty_cap = dirty;
+	}
+	return EXPANN_OK;
+}
+
+// d_adj0 and the CSR remade from the resident state (graph_append.hpp) on the handle's stream, and waited for
+int graph_rebuild_tables(expann_graph* g) {
+	if (g->n > g->cap_rows || g->n_layers == 0 || g->n_layers > g->L_cap + 1 || g->stride0 % 4 != 0 || g->stride0 < g->M0)
+		return g->fail(EXPANN_ERR_INVALID_ARG, "graph append: the builder state does not fit its capacity");
+	AppendTables t{};
+	t.g = graph_build_view(g);
+	t.n_layers = g->n_layers;
+	t.adj0 = g->d_adj0;
+	t.stride0 = g->stride0;
+	t.layer_off = g->d_layer_off;
+	t.neighbours = g->d_neighbours;
+	t.edge_cap = (uint32_t)g->edge_cap;
+	t.tile_sums = g->d_tile_sums;
+	const uint64_t entries = (uint64_t)g->n_layers * (g->n + 1), quads = (uint64_t)g->n * (g->stride0 / 4);
+	const uint32_t n_tiles = (uint32_t)((entries + kScanTile - 1) / kScanTile);
+	hipStream_t st = g->stream;
+	for (OwnedEvent& ev : g->ev_tables)
+		if (!ev)
+			HIP_TRY(g, hipEventCreate(&ev));
+	HIP_TRY(g, hipEventRecord(g->ev_tables[0], st));
+	hipLaunchKernelGGL(append_adj0_kernel, dim3((uint32_t)((quads + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, t);
+	hipLaunchKernelGGL(append_degree_kernel, dim3((uint32_t)((entries + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, t);
+	hipLaunchKernelGGL(append_scan_reduce_kernel, dim3(n_tiles), dim3(kBlock), 0, st, t);
+	hipLaunchKernelGGL(append_scan_sums_kernel, dim3(1), dim3(kBlock), 0, st, t.tile_sums, n_tiles);
+	hipLaunchKernelGGL(append_scan_tiles_kernel, dim3(n_tiles), dim3(kBlock), 0, st, t);
+	hipLaunchKernelGGL(append_fill_kernel, dim3((uint32_t)((entries + kBlock / 16 - 1) / (kBlock / 16))), dim3(kBlock), 0, st, t);
+	HIP_TRY(g, hipGetLastError());
+	HIP_TRY(g, hipEventRecord(g->ev_tables[1], st));
+	uint32_t last = 0;  // (the end entry of the top layer: every edge lies before it)
+	HIP_TRY(g, hipMemcpyAsync(&last, g->d_layer_off.get() + entries - 1, sizeof(last), hipMemcpyDeviceToHost, st));
+	HIP_TRY(g, hipStreamSynchronize(st));
+	float ms = 0;
+	HIP_TRY(g, hipEventElapsedTime(&ms, g->ev_tables[0], g->ev_tables[1]));
+	g->tables_ns = (uint64_t)((double)ms * 1e6);
+	g->n_edges = last;
+	return EXPANN_OK;
+}
+
+// room for `rows` rows in everything that is sized by the row count.  The caller has waited for the searches in
+// flight.  A resident handle's CSR is left without content: the caller rebuilds the tables.
+int graph_grow_rows(expann_graph* g, size_t rows) {
+	if (rows <= g->cap_rows)
+		return EXPANN_OK;
+	if (g->vis_words == 0 || rows > (8u << 20))
+		return g->fail(EXPANN_ERR_UNSUPPORTED, "a graph handle grows up to 8 Mi rows (visited bitsets)");
+	const size_t n = g->n, row_bytes = (size_t)g->dim * (g->rows_f16 ? 2 : 4);
+	if (int rc = graph_regrow(g, g->d_vectors, n * row_bytes, rows * row_bytes))
+		return rc;
+	if (int rc = graph_regrow(g, g->d_adj0, n * g->stride0 * sizeof(uint32_t), rows * g->stride0 * sizeof(uint32_t)))
+		return rc;
+	const uint32_t words = (uint32_t)((rows + 8191) / 8192 * 256);
+	if (words != g->vis_words) {  // (all zero between searches: nothing to keep)
+		if (int rc = graph_regrow(g, g->d_visited, 0, (size_t)g->slots * words * sizeof(uint32_t), true))
+			return rc;
+		g->vis_words = words;
+	}
+	if (g->resident) {
+		if (int rc = graph_regrow(g, g->d_level, n, rows))
+			return rc;
+		if (int rc = graph_regrow(g, g->d_upper_idx, n * 4, rows * 4))
+			return rc;
+		if (int rc = graph_regrow(g, g->d_id0, n * g->bstride0 * 4, rows * g->bstride0 * 4))
+			return rc;
+		if (int rc = graph_regrow(g, g->d_d0, n * g->bstride0 * 4, rows * g->bstride0 * 4))
+			return rc;
+		if (int rc = graph_regrow(g, g->d_deg0, n * 4, rows * 4, true))
+			return rc;
+	}
+	g->cap_rows = rows;
+	return g->resident ? graph_size_derived(g) : EXPANN_OK;
+}
+
+// the upper-layer arrays laid out again for at least U_need vertices and L_need layers
+int graph_grow_upper(expann_graph* g, size_t U_need, size_t L_need) {
+	if (U_need <= g->U_cap && L_need <= g->L_cap)
+		return EXPANN_OK;
+	const size_t U_cap = U_need > g->U_cap ? std::max(U_need, g->U_cap + g->U_cap / 2) + 64 : g->U_cap;
+	const size_t L_cap = L_need > g->L_cap ? L_need + 1 : g->L_cap;
+	const size_t rows = U_cap * L_cap, su = g->bstrideu;
+	DevPtr<uint32_t> idu, degu;
+	DevPtr<float> du;
+	HIP_TRY(g, hipMalloc(&idu, std::max<size_t>(rows * su, 1) * 4));
+	HIP_TRY(g, hipMalloc(&du, std::max<size_t>(rows * su, 1) * 4));
+	HIP_TRY(g, hipMalloc(&degu, std::max<size_t>(rows, 1) * 4));
+	HIP_TRY(g, hipMemsetAsync(degu, 0, rows * 4, g->stream));
+	for (size_t l = 0; l < g->L_cap && g->U; ++l) {
+		HIP_TRY(g, hipMemcpyAsync(idu.get() + l * U_cap * su, g->d_idu.get() + l * g->U_cap * su, g->U * su * 4,
+		                          hipMemcpyDeviceToDevice, g->stream));
+		HIP_TRY(g, hipMemcpyAsync(du.get() + l * U_cap * su, g->d_du.get() + l * g->U_cap * su, g->U * su * 4,
+		                          hipMemcpyDeviceToDevice, g->stream));
+		HIP_TRY(g, hipMemcpyAsync(degu.get() + l * U_cap, g->d_degu.get() + l * g->U_cap, g->U * 4, hipMemcpyDeviceToDevice,
+		                          g->stream));
+	}
+	HIP_TRY(g, hipStreamSynchronize(g->stream));
+	g->d_idu = std::move(idu);
+	g->d_du = std::move(du);
+	g->d_degu = std::move(degu);
+	g->U_cap = U_cap;
+	g->L_cap = L_cap;
+	return graph_size_derived(g);
+}
+}  // namespace
+
+extern "C" {
+
+int expann_graph_reserve(expann_graph* g, size_t n_rows) {
+	if (!g)
+		return EXPANN_ERR_INVALID_ARG;
+	if (n_rows <= g->cap_rows)
+		return EXPANN_OK;
+	if (n_rows >= (1ull << 32) - 64)
+		return g->fail(EXPANN_ERR_INVALID_ARG, "expann_graph_reserve: too many rows");
+	HIP_TRY(g, hipSetDevice(g->device));
+	HIP_TRY(g, graph_wait_outstanding(g));
+	if (int rc = graph_grow_rows(g, n_rows))
+		return rc;
+	if (g->resident) {
+		if (int rc = graph_rebuild_tables(g))
+			return rc;
+	}
+	return EXPANN_OK;
+}
+
+int expann_graph_adopt_build_state(expann_graph* g, size_t M, size_t M0, size_t ef_construction, size_t prune_overflow,
+                                   float ortho_factor, float ortho_bias, const uint8_t* levels, const int32_t* upper_idx,
+                                   const uint32_t* ids0, const float* d0, const uint32_t* deg0, size_t stride0, size_t U,
+                                   size_t n_upper_layers, const uint32_t* idsu, const float* du, const uint32_t* degu,
+                                   size_t strideu) {
+	if (!g)
+		return EXPANN_ERR_INVALID_ARG;
+	const char* fn = "expann_graph_adopt_build_state: ";
+	if (g->rows_f16)
+		return g->fail(EXPANN_ERR_UNSUPPORTED, std::string(fn) + "the builder works on fp32 rows, the handle holds binary16");
+	if (g->vis_words == 0)
+		return g->fail(EXPANN_ERR_UNSUPPORTED, std::string(fn) + "needs the visited bitsets (at most 8 Mi rows)");
+	const size_t n = g->n;
+	if (!levels || !upper_idx || !ids0 || !d0 || !deg0 || M < 2 || M0 < M || stride0 < M0 || strideu < M ||
+	    (U && n_upper_layers && (!idsu || !du || !degu)) || ef_construction == 0 || ef_construction > (size_t)kPruneMaxCand ||
+	    stride0 > (size_t)kPruneMaxCand || strideu > (size_t)kPruneMaxCand || n_upper_layers + 1 < g->n_layers)
+		return g->fail(EXPANN_ERR_INVALID_ARG, std::string(fn) + "bad arguments (ef_construction and row strides <= 1024)");
+	// (what graph_size_derived would refuse, refused before anything of the handle changes)
+	if (g->cap_rows * M0 + (U + U / 2 + 128) * (g->n_layers + 1) * M >= (1ull << 32))
+		return g->fail(EXPANN_ERR_UNSUPPORTED, std::string(fn) + "the capacity would take more than 2^32 edges");
+	// what the kernels index by: every id, level, upper row and degree, checked once here as expann_graph_create
+	// checks its CSR -- a row holds at most M0 / M edges, which is also what the tables' capacities count on
+	for (size_t v = 0; v < n; ++v) {
+		bool ok = deg0[v] <= M0 && levels[v] < g->n_layers;
+		for (uint32_t i = 0; ok && i < deg0[v]; ++i)
+			ok = ids0[v * stride0 + i] < n;
+		if (ok && levels[v] >= 1) {
+			ok = upper_idx[v] >= 0 && (size_t)upper_idx[v] < U;
+			for (size_t l = 1; ok && l <= levels[v]; ++l) {
+				const size_t r = (l - 1) * U + (size_t)upper_idx[v];
+				ok = degu[r] <= M;
+				for (uint32_t i = 0; ok && i < degu[r]; ++i)
+					ok = idsu[r * strideu + i] < n;
+			}
+		}
+		if (!ok)
+			return g->fail(EXPANN_ERR_INVALID_ARG, std::string(fn) + "row " + std::to_string(v) + " is not a row of a graph built with these M / M0");
+	}
+	HIP_TRY(g, hipSetDevice(g->device));
+	HIP_TRY(g, graph_wait_outstanding(g));
+	g->forget<GraphBuildState>();
+	g->M = M;
+	g->M0 = M0;
+	g->ef_construction = ef_construction;
+	g->prune_overflow = prune_overflow;
+	g->ortho_factor = ortho_factor;
+	g->ortho_bias = ortho_bias;
+	g->bstride0 = (uint32_t)stride0;
+	g->bstrideu = (uint32_t)strideu;
+	g->U = U;
+	const size_t cap = g->cap_rows, L_used = g->n_layers - 1;
+	HIP_TRY(g, hipMalloc(&g->d_level, cap));
+	HIP_TRY(g, hipMalloc(&g->d_upper_idx, cap * 4));
+	HIP_TRY(g, hipMalloc(&g->d_id0, cap * stride0 * 4));
+	HIP_TRY(g, hipMalloc(&g->d_d0, cap * stride0 * 4));
+	HIP_TRY(g, hipMalloc(&g->d_deg0, cap * 4));
+	HIP_TRY(g, hipMemset(g->d_deg0, 0, cap * 4));
+	HIP_TRY(g, hipMemcpy(g->d_level, levels, n, hipMemcpyHostToDevice));
+	HIP_TRY(g, hipMemcpy(g->d_upper_idx, upper_idx, n * 4, hipMemcpyHostToDevice));
+	HIP_TRY(g, hipMemcpy(g->d_id0, ids0, n * stride0 * 4, hipMemcpyHostToDevice));
+	HIP_TRY(g, hipMemcpy(g->d_d0, d0, n * stride0 * 4, hipMemcpyHostToDevice));
+	HIP_TRY(g, hipMemcpy(g->d_deg0, deg0, n * 4, hipMemcpyHostToDevice));
+	// the upper arrays: the host's [layer][U] rows at the device's row stride U_cap.  Their first layout also sizes the
+	// CSR to the capacities (graph_size_derived: the one expann_graph_create made holds n rows exactly)
+	g->U = 0;  // (nothing to carry over into the first layout)
+	if (int rc = graph_grow_upper(g, U + U / 2 + 64, L_used + 1))
+		return rc;
+	g->U = U;
+	for (size_t l = 0; l < L_used && U; ++l) {
+		HIP_TRY(g, hipMemcpy(g->d_idu.get() + l * g->U_cap * strideu, idsu + l * U * strideu, U * strideu * 4, hipMemcpyHostToDevice));
+		HIP_TRY(g, hipMemcpy(g->d_du.get() + l * g->U_cap * strideu, du + l * U * strideu, U * strideu * 4, hipMemcpyHostToDevice));
+		HIP_TRY(g, hipMemcpy(g->d_degu.get() + l * g->U_cap, degu + l * U, U * 4, hipMemcpyHostToDevice));
+	}
+	// a batch's scratch, at the largest batch of THE BATCH RULE
+	const size_t max_batch = 32768, lists = 2 * max_batch + 64;
+	HIP_TRY(g, hipMalloc(&g->d_out, lists * ef_construction * sizeof(md_pair)));
+	HIP_TRY(g, hipMalloc(&g->d_out_cnt, lists * 4));
+	HIP_TRY(g, hipMalloc(&g->d_tasks, lists * sizeof(PruneTask)));
+	HIP_TRY(g, hipMalloc(&g->d_up_slot, max_batch * 4));
+	HIP_TRY(g, hipMalloc(&g->d_build_ctr, 8 * 4));
+	// the walk's layer-0 table takes rows of up to M0 ids from now on (the stride it has, when that is larger)
+	const uint32_t stride_adj = std::max<uint32_t>(g->stride0, (uint32_t)((M0 + 3) / 4 * 4));
+	if (stride_adj != g->stride0) {
+		DevPtr<uint32_t> adj;
+		HIP_TRY(g, hipMalloc(&adj, cap * stride_adj * sizeof(uint32_t)));
+		g->d_adj0 = std::move(adj);
+		g->stride0 = stride_adj;
+	}
+	g->resident = true;
+	return graph_rebuild_tables(g);
+}
+
+int expann_graph_append(expann_graph* g, const float* rows, size_t n, const uint8_t* levels, uint32_t* max_layer_out,
+                        uint32_t* starting_vertex_out, size_t* n_appended) {
+	if (n_appended)
+		*n_appended = 0;
+	if (!g)
+		return EXPANN_ERR_INVALID_ARG;
+	if (n && (!rows || !levels))
+		return g->fail(EXPANN_ERR_INVALID_ARG, "expann_graph_append: NULL pointer");
+	if (!g->resident)
+		return g->fail(EXPANN_ERR_NOT_BUILT, "expann_graph_append before expann_graph_adopt_build_state");
+	if (g->n + n >= (1ull << 32) - 64)
+		return g->fail(EXPANN_ERR_INVALID_ARG, "expann_graph_append: too many rows");
+	if (max_layer_out)
+		*max_layer_out = g->n_layers;
+	if (starting_vertex_out)
+		*starting_vertex_out = g->starting_vertex;
+	if (n == 0)
+		return EXPANN_OK;
+	HIP_TRY(g, hipSetDevice(g->device));
+	HIP_TRY(g, graph_wait_outstanding(g));  // (searches in flight read the tables this call remakes)
+	g->forget<GraphRowFilter>();
+	g->forget<GraphRowGroups>();
+	g->forget<GraphRowBytes>();
+	const size_t n_old = g->n, need = n_old + n;
+	if (need > g->cap_rows) {  // a full handle grows by half
+		if (int rc = graph_grow_rows(g, std::max(need, g->cap_rows + g->cap_rows / 2)))
+			return rc;
+		++g->stat_append[5];
+	}
+	std::vector<int32_t> up(n, -1);
+	size_t U_new = g->U, L_need = g->n_layers - 1;
+	for (size_t i = 0; i < n; ++i) {
+		if (levels[i] >= 1)
+			up[i] = (int32_t)U_new++;
+		L_need = std::max<size_t>(L_need, levels[i]);
+	}
+	if (int rc = graph_grow_upper(g, U_new, L_need))
+		return rc;
+	hipStream_t st = g->stream;
+	HIP_TRY(g, hipMemcpyAsync(g->d_vectors.as<float>() + n_old * (size_t)g->dim, rows, n * (size_t)g->dim * 4, hipMemcpyHostToDevice, st));
+	HIP_TRY(g, hipMemcpyAsync(g->d_level.get() + n_old, levels, n, hipMemcpyHostToDevice, st));
+	HIP_TRY(g, hipMemcpyAsync(g->d_upper_idx.get() + n_old, up.data(), n * 4, hipMemcpyHostToDevice, st));
+	HIP_TRY(g, hipMemsetAsync(g->d_deg0.get() + n_old, 0, n * 4, st));
+	HIP_TRY(g, hipMemsetAsync(g->d_build_ctr, 0, 8 * 4, st));
+	BuildBatches r{};
+	r.bv = build_variant(g->dim);
+	r.g = graph_build_view(g);
+	r.g.n = (uint32_t)need;
+	r.st = st;
+	r.dim = g->dim;
+	r.cus = num_cus(g->device);
+	r.levels = levels;
+	r.level_base = n_old;
+	r.b0 = n_old;
+	r.n = need;
+	r.max_layer = g->n_layers;
+	r.starting_vertex = g->starting_vertex;
+	r.max_batch = 0;
+	r.ef = g->ef_construction;
+	r.prune_overflow = g->prune_overflow;
+	r.ortho_factor = g->ortho_factor;
+	r.ortho_bias = g->ortho_bias;
+	r.vis_bits = g->d_visited.as<uint32_t>();  // (the walk's sets: all zero between searches, and none is in flight)
+	r.vis_words = g->vis_words;
+	r.out = g->d_out;
+	r.out_cnt = g->d_out_cnt;
+	r.tasks = g->d_tasks;
+	r.up_slot = g->d_up_slot;
+	r.dirty = g->d_dirty;
+	r.dirty_cap = g->dirty_cap;
+	r.ctr = g->d_build_ctr;
+	r.resident = true;
+	if (int rc = build_batches_geometry(g, r, true))
+		return rc;
+	r.slots = std::min<uint64_t>(r.slots, g->slots);
+	const int brc = build_run_batches(g, r);
+	if (brc != EXPANN_OK && brc != EXPANN_ERR_OVERFLOW)
+		return brc;
+	// the rows of the batches that are in (all of them, unless a construction search overflowed)
+	const size_t done = r.b0 - n_old;
+	for (size_t i = 0; i < done; ++i)
+		g->U += levels[i] >= 1;
+	g->n = r.b0;
+	g->n_layers = r.max_layer;
+	g->starting_vertex = r.starting_vertex;
+	g->max_degree0 = std::max<uint32_t>(g->max_degree0, (uint32_t)g->M0);
+	const std::string overflow = g->err;
+	if (int rc = graph_rebuild_tables(g))
+		return rc;
+	++g->stat_append[0];
+	g->stat_append[1] += done;
+	g->stat_append[2] += r.n_batches;
+	++g->stat_append[3];
+	if (n_appended)
+		*n_appended = done;
+	if (max_layer_out)
+		*max_layer_out = g->n_layers;
+	if (starting_vertex_out)
+		*starting_vertex_out = g->starting_vertex;
+	return brc == EXPANN_OK ? EXPANN_OK : g->fail(brc, overflow);
+}
+
+int expann_graph_build_state_shape(expann_graph* g, size_t* shape) {
+	if (!g)
+		return EXPANN_ERR_INVALID_ARG;
+	if (!shape)
+		return g->fail(EXPANN_ERR_INVALID_ARG, "NULL pointer");
+	if (!g->resident)
+		return g->fail(EXPANN_ERR_NOT_BUILT, "no builder state: expann_graph_adopt_build_state first");
+	shape[0] = g->n;
+	shape[1] = g->U_cap;
+	shape[2] = g->n_layers - 1;
+	shape[3] = g->U;
+	shape[4] = g->bstride0;
+	shape[5] = g->bstrideu;
+	return EXPANN_OK;
+}
+
+int expann_graph_read_build_state(expann_graph* g, uint8_t* levels, int32_t* upper_idx, uint32_t* ids0, float* d0,
+                                  uint32_t* deg0, uint32_t* idsu, float* du, uint32_t* degu) {
+	if (!g)
+		return EXPANN_ERR_INVALID_ARG;
+	if (!g->resident)
+		return g->fail(EXPANN_ERR_NOT_BUILT, "no builder state: expann_graph_adopt_build_state first");
+	const size_t n = g->n, up_rows = (g->n_layers - 1) * g->U_cap;
+	if (!levels || !upper_idx || !ids0 || !d0 || !deg0 || (up_rows && (!idsu || !du || !degu)))
+		return g->fail(EXPANN_ERR_INVALID_ARG, "expann_graph_read_build_state: NULL pointer");
+	HIP_TRY(g, hipSetDevice(g->device));
+	HIP_TRY(g, hipMemcpy(levels, g->d_level, n, hipMemcpyDeviceToHost));
+	HIP_TRY(g, hipMemcpy(upper_idx, g->d_upper_idx, n * 4, hipMemcpyDeviceToHost));
+	HIP_TRY(g, hipMemcpy(ids0, g->d_id0, n * g->bstride0 * 4, hipMemcpyDeviceToHost));
+	HIP_TRY(g, hipMemcpy(d0, g->d_d0, n * g->bstride0 * 4, hipMemcpyDeviceToHost));
+	HIP_TRY(g, hipMemcpy(deg0, g->d_deg0, n * 4, hipMemcpyDeviceToHost));
+	if (up_rows) {
+		HIP_TRY(g, hipMemcpy(idsu, g->d_idu, up_rows * g->bstrideu * 4, hipMemcpyDeviceToHost));
+		HIP_TRY(g, hipMemcpy(du, g->d_du, up_rows * g->bstrideu * 4, hipMemcpyDeviceToHost));
+		HIP_TRY(g, hipMemcpy(degu, g->d_degu, up_rows * 4, hipMemcpyDeviceToHost));
+	}
+	return EXPANN_OK;
+}
+
+int expann_graph_note_host_append(expann_graph* g, const uint64_t* carried, size_t rows) {
+	if (!g)
+		return EXPANN_ERR_INVALID_ARG;
+	if (carried)
+		std::copy(carried, carried + 6, g->stat_append);
+	++g->stat_append[0];
+	g->stat_append[1] += rows;
+	++g->stat_append[4];
 	return EXPANN_OK;
 }
 
@@ -1945,8 +2518,40 @@ int expann_antitopo_range_query_device(expann_antitopo* e, const float* d_querie
 int expann_antitopo_save(expann_antitopo* e, const char* index_path) {
 	if (!e || !index_path)
 		return EXPANN_ERR_INVALID_ARG;
-	ANTITOPO_TRY(e, e->eng->index.write_index(index_path));
+	ANTITOPO_TRY(e, e->eng->save_index(index_path));  // (after an append: the adjacency comes back from the device first)
 	return EXPANN_OK;
+}
+
+int expann_antitopo_append(expann_antitopo* e, const float* rows, size_t n, size_t* n_appended) {
+	if (n_appended)
+		*n_appended = 0;
+	if (!e || (!rows && n))
+		return e ? e->fail(EXPANN_ERR_INVALID_ARG, "expann_antitopo_append: rows == NULL") : EXPANN_ERR_INVALID_ARG;
+	if (!e->eng->graph)
+		return e->fail(EXPANN_ERR_NOT_BUILT, "expann_antitopo_append before build()");
+	int rc = EXPANN_OK;
+	ANTITOPO_TRY(e, rc = e->eng->append_rows(rows, n, n_appended));
+	return rc == EXPANN_OK ? rc : e->fail(rc, expann_graph_last_error(e->eng->graph));
+}
+
+int expann_antitopo_reserve(expann_antitopo* e, size_t n_rows) {
+	if (!e)
+		return EXPANN_ERR_INVALID_ARG;
+	if (!e->eng->graph)
+		return e->fail(EXPANN_ERR_NOT_BUILT, "expann_antitopo_reserve before build()");
+	const int rc = e->eng->reserve(n_rows);
+	return rc == EXPANN_OK ? rc : e->fail(rc, expann_graph_last_error(e->eng->graph));
+}
+
+int expann_antitopo_get_stat(expann_antitopo* e, const char* name, uint64_t* out) {
+	if (!e)
+		return EXPANN_ERR_INVALID_ARG;
+	if (!name || !out)
+		return e->fail(EXPANN_ERR_INVALID_ARG, "NULL pointer");
+	if (!e->eng->graph)
+		return e->fail(EXPANN_ERR_NOT_BUILT, "expann_antitopo_get_stat before build()");
+	const int rc = expann_graph_get_stat(e->eng->graph, name, out);
+	return rc == EXPANN_OK ? rc : e->fail(rc, expann_graph_last_error(e->eng->graph));
 }
 
 int expann_antitopo_load(expann_antitopo* e, const char* index_path) {

@@ -279,6 +279,40 @@ class AntitopoEngine:
             raise _lib.ExpannError(_lib.ERR_NOT_BUILT, "sync() before build()")
         self._check(self._L.expann_antitopo_sync(self._h))
 
+    def append(self, rows):
+        """expann_antitopo_append: `rows` (2-D, padded like stored rows) join the BUILT graph with the ids size() ..
+        size() + len(rows) - 1 -- THE GRAPH APPEND RULE, include/expann_hip.h: the engine is then what
+        store_many_vectors_batched(rows) followed by build() would have made of it, without the graph going to the
+        device again (fp32 rows, ortho_count 1, at least 2048 rows; other engines take exactly that route).  A row
+        filter and row groups are cleared.  Returns the number of rows appended; raises ExpannError with
+        ERR_OVERFLOW -- its `appended` attribute says how many rows are in -- when a construction search overflowed."""
+        if self._h is None:
+            raise _lib.ExpannError(_lib.ERR_NOT_BUILT, "append() before build()")
+        a = self._pad(rows)
+        done = C.c_size_t(0)
+        rc = self._L.expann_antitopo_append(self._h, a.ctypes.data, a.shape[0], C.byref(done))
+        if rc != _lib.OK:
+            err = _lib.ExpannError(rc, self._L.expann_antitopo_last_error(self._h).decode())
+            err.appended = int(done.value)
+            raise err
+        return int(done.value)
+
+    def reserve(self, n):
+        """expann_antitopo_reserve: room on the device for n rows in all, so that appends up to there reallocate
+        nothing ("capacity_rows"); below the current capacity it does nothing."""
+        if self._h is None:
+            raise _lib.ExpannError(_lib.ERR_NOT_BUILT, "reserve() before build()")
+        self._check(self._L.expann_antitopo_reserve(self._h, int(n)))
+
+    def stat(self, name):
+        """expann_antitopo_get_stat: a counter of the engine's graph handle by its expann_graph_get_stat name
+        ("append_device", "capacity_rows", "filter_active", ...)"""
+        if self._h is None:
+            raise _lib.ExpannError(_lib.ERR_NOT_BUILT, "stat() before build()")
+        out = C.c_uint64(0)
+        self._check(self._L.expann_antitopo_get_stat(self._h, name.encode(), C.byref(out)))
+        return int(out.value)
+
     def save_index(self, path):
         self._check(self._L.expann_antitopo_save(self._h, str(path).encode()))
 

@@ -196,6 +196,10 @@ struct antitopo_index {
 	// (:942-949), never loaded (":1000 search-time param, don't load")
 	bool has_ef_search = false;
 	size_t ef_search = 0;
+	// Set by gpu_antitopo_engine after an append served on the device: `vectors`, max_layer and starting_vertex are
+	// current, hadj_* are those of the graph before the appends.  Nothing in this struct reads the flag: the engine
+	// refreshes the adjacency (from_strided of the device's state) before anything reads hadj_*.
+	bool adjacency_stale = false;
 
 	antitopo_index() = default;
 	antitopo_index(size_t _dim, antitopo_config c) : conf(c), dim(_dim) {}
@@ -538,6 +542,7 @@ struct antitopo_index {
 			}
 		}
 		visited.assign(n, 0);
+		adjacency_stale = false;
 	}
 
 	// ---- fixed-stride adjacency arrays, the batched GPU builder's view (expann_graph_build_batched) --

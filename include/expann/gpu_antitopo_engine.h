@@ -61,6 +61,7 @@ struct gpu_antitopo_engine : public ann_engine<T, gpu_antitopo_engine<T>> {
 	std::optional<size_t> ef_search;
 	size_t num_distcomps = 0;  // RECORD_STATS counter (src/antitopo_engine.h:125-129)
 	uint64_t device_distcomps_seen = 0;  // the graph handle's device counter at the last sync()
+	bool resident = false;  // the graph handle holds the builder's state (append_rows; a new handle starts without)
 
 	explicit gpu_antitopo_engine(config c) : conf(c) { index.conf = c; }
 	gpu_antitopo_engine(const gpu_antitopo_engine&) = delete;
@@ -86,9 +87,148 @@ struct gpu_antitopo_engine : public ann_engine<T, gpu_antitopo_engine<T>> {
 		}
 		return r;
 	}
+	// ---- Extension: appends to the built graph (THE GRAPH APPEND RULE, expann_hip.h) ----
+	// the engines append_rows serves with store_rows_batched + _build(), as before: binary16 rows, several ortho entry
+	// points, fewer than store_rows_batched's n_serial rows
+	bool append_on_host() const {
+		return conf.rows_f16 || conf.ortho_count != 1 || conf.read_index || index.size() < 2048 || index.size() > (8u << 20);
+	}
+	// After an append on the device the host's adjacency is that of the graph before it (index.adjacency_stale);
+	// everything that reads index.hadj_* calls this first.  The download is reached through a pointer that
+	// append_rows sets where it sets the flag: a program that never appends does not refer to the append's library
+	// calls (the native test hooks stub the few calls of the library they use).
+	void (gpu_antitopo_engine::*download_fn)() = nullptr;
+	void refresh_host() {
+		if (index.adjacency_stale)
+			(this->*download_fn)();
+	}
+	// the builder's state from the device, from_strided
+	void download_adjacency() {
+		size_t shape[6];
+		auto check = [&](int rc) {
+			if (rc != EXPANN_OK)
+				throw std::runtime_error(std::string("gpu_antitopo_engine: reading the graph back: ") + expann_graph_last_error(graph));
+		};
+		check(expann_graph_build_state_shape(graph, shape));
+		expann::antitopo_index::strided_graph g;
+		g.n = shape[0];
+		g.U = shape[1];  // (the row stride of the upper arrays: the device's capacity)
+		g.n_upper_layers = shape[2];
+		g.stride0 = shape[4];
+		g.strideu = shape[5];
+		g.levels.resize(g.n);
+		g.upper_idx.resize(g.n);
+		g.ids0.resize(g.n * g.stride0);
+		g.d0.resize(g.n * g.stride0);
+		g.deg0.resize(g.n);
+		g.idsu.resize(g.U * g.n_upper_layers * g.strideu);
+		g.du.resize(g.U * g.n_upper_layers * g.strideu);
+		g.degu.resize(g.U * g.n_upper_layers);
+		check(expann_graph_read_build_state(graph, g.levels.data(), g.upper_idx.data(), g.ids0.data(), g.d0.data(),
+		                                    g.deg0.data(), g.idsu.data(), g.du.data(), g.degu.data()));
+		if (g.n != index.size())
+			throw std::runtime_error("gpu_antitopo_engine: the device graph and the host rows differ in size");
+		index.from_strided(g, nullptr, index.max_layer, index.starting_vertex);
+		index.adjacency_stale = false;
+	}
+	// the six append counters of the graph handle (carried over a re-upload by the host route)
+	void read_append_stats(uint64_t* six) const {
+		static const char* const names[6] = {"append_calls", "append_rows", "append_batches",
+		                                     "append_device", "append_host", "graph_reallocs"};
+		for (int i = 0; i < 6; ++i)
+			if (expann_graph_get_stat(graph, names[i], six + i) != EXPANN_OK)
+				six[i] = 0;
+	}
+	// `n` rows appended to the built graph.  Returns the expann_status (message: expann_graph_last_error(graph));
+	// *n_appended: the rows that are in -- n, or fewer with EXPANN_ERR_OVERFLOW.  Throws what store_rows_batched and
+	// _build() throw on the host route.
+	int append_rows(const float* rows, size_t n, size_t* n_appended = nullptr) {
+		if (n_appended)
+			*n_appended = 0;
+		if (!graph)
+			return EXPANN_ERR_NOT_BUILT;
+		if (n == 0)
+			return EXPANN_OK;
+		if (!rows)
+			return EXPANN_ERR_INVALID_ARG;
+		bool on_host = append_on_host();
+		if (!on_host && !resident) {  // the handle's first append: the builder's view, uploaded once
+			const auto g = index.to_strided({}, 64);
+			bool fits = true;  // (rows of a graph built with these M / M0: a foreign index file may hold longer ones)
+			for (size_t v = 0; v < g.n && fits; ++v)
+				fits = g.deg0[v] <= conf.M0;
+			for (size_t r = 0; r < g.degu.size() && fits; ++r)
+				fits = g.degu[r] <= conf.M;
+			const int rc = !fits ? EXPANN_ERR_UNSUPPORTED
+			                     : expann_graph_adopt_build_state(graph, conf.M, conf.M0, conf.ef_construction, conf.prune_overflow,
+			                                                      conf.ortho_factor, conf.ortho_bias, g.levels.data(),
+			                                                      g.upper_idx.data(), g.ids0.data(), g.d0.data(), g.deg0.data(),
+			                                                      g.stride0, g.U, g.n_upper_layers, g.idsu.data(), g.du.data(),
+			                                                      g.degu.data(), g.strideu);
+			if (rc == EXPANN_ERR_UNSUPPORTED)
+				on_host = true;
+			else if (rc != EXPANN_OK)
+				return rc;
+			else
+				resident = true;
+		}
+		if (on_host) {
+			refresh_host();
+			uint64_t carried[6];
+			read_append_stats(carried);
+			store_rows_batched(rows, n);
+			_build();
+			(void)expann_graph_note_host_append(graph, carried, n);
+			if (n_appended)
+				*n_appended = n;
+			return EXPANN_OK;
+		}
+		const expann::mt19937_ref gen_before = index.gen;
+		std::vector<uint8_t> lv(n);
+		for (size_t i = 0; i < n; ++i)
+			lv[i] = (uint8_t)std::min<size_t>(index.draw_level(), 250);
+		uint32_t ml = 0, sv = 0;
+		size_t done = 0;
+		const int rc = expann_graph_append(graph, rows, n, lv.data(), &ml, &sv, &done);
+		if (rc != EXPANN_OK && rc != EXPANN_ERR_OVERFLOW) {
+			index.gen = gen_before;
+			return rc;
+		}
+		if (done < n) {  // the generator stands after the draws of the rows that are in
+			index.gen = gen_before;
+			for (size_t i = 0; i < done; ++i)
+				(void)index.draw_level();
+		}
+		if (done) {
+			index.vectors.insert(index.vectors.end(), rows, rows + done * index.dim);
+			index.visited.resize(index.size(), 0);
+			index.max_layer = ml;
+			index.starting_vertex = sv;
+			index.adjacency_stale = true;
+			download_fn = &gpu_antitopo_engine::download_adjacency;
+		}
+		if (n_appended)
+			*n_appended = done;
+		return rc;
+	}
+	// room for n_rows rows on the device, so that appends up to there reallocate nothing
+	int reserve(size_t n_rows) {
+		if (!graph)
+			return EXPANN_ERR_NOT_BUILT;
+		if (append_on_host())
+			return EXPANN_OK;
+		return expann_graph_reserve(graph, n_rows);
+	}
+	// write_index of the graph as it is now
+	void save_index(const std::string& path) {
+		refresh_host();
+		index.write_index(path);
+	}
+
 	void _store_vector(const vec<T>& v) {
 		if (conf.read_index)
 			return;  // :312-313
+		refresh_host();
 		if (index.dim == 0)
 			index.dim = v.size();
 		std::vector<float> row(index.dim);
@@ -102,6 +242,7 @@ struct gpu_antitopo_engine : public ann_engine<T, gpu_antitopo_engine<T>> {
 	void store_rows(const float* rows, size_t n) {
 		if (conf.read_index || n == 0)
 			return;
+		refresh_host();
 		if (index.dim == 0)
 			throw std::runtime_error("gpu_antitopo_engine: dimension not set");
 		std::vector<float> rounded;
@@ -120,6 +261,7 @@ struct gpu_antitopo_engine : public ann_engine<T, gpu_antitopo_engine<T>> {
 		std::vector<uint64_t> stats(4, 0);
 		if (conf.read_index || n == 0)
 			return stats;
+		refresh_host();
 		if (index.dim == 0)
 			throw std::runtime_error("gpu_antitopo_engine: dimension not set");
 		std::vector<float> rounded;  // (rows_f16: the batched builder receives the upcast fp32 rows)
@@ -157,6 +299,7 @@ struct gpu_antitopo_engine : public ann_engine<T, gpu_antitopo_engine<T>> {
 		return stats;
 	}
 	void _build() {  // :467-493
+		refresh_host();
 		if (conf.write_index && !conf.index_filename.empty())
 			index.write_index(conf.index_filename);
 		if (conf.read_index)
@@ -184,9 +327,11 @@ struct gpu_antitopo_engine : public ann_engine<T, gpu_antitopo_engine<T>> {
 		std::vector<uint16_t> halves;
 		if (conf.rows_f16)
 			halves = pack_rows_f16();  // (throws before the device is touched and before the old graph goes)
+		refresh_host();
 		const auto fg = index.flatten();
 		expann_graph_destroy(graph);
 		graph = nullptr;
+		resident = false;
 		device_distcomps_seen = 0;
 		int rc = conf.rows_f16
 		             ? expann_graph_create_f16(int(index.dim), conf.device, halves.data(), index.size(), fg.n_layers,

@@ -1016,6 +1016,83 @@ int expann_remove_device(expann_index* h, const uint64_t* d_ids, size_t n_ids, v
                          size_t* n_removed);                                                          /* device ids */
 int expann_compact_row_filter(expann_index* h, size_t* n_removed);
 
+/* Append rows to a built graph engine without uploading the graph again (appended; EXPANN_ABI_VERSION stays 2:
+ * nothing that existed changed, and a handle that never calls these allocates and launches exactly what it did).
+ * THE GRAPH APPEND RULE.  After expann_antitopo_append(e, R, r) on a built engine of n rows the new rows have the ids
+ * n .. n + r - 1, and the engine is in the state that expann_antitopo_store_batched(e, R, r, 0) followed by
+ * expann_antitopo_build(e) leaves: the index expann_antitopo_save writes, max_layer and starting_vertex, the state
+ * of the level generator, and the graph the walk sees.  The batches are THE BATCH RULE's with max_batch = 0, the
+ * levels are the same draws, the kernels are the same; "the same" has the freedom THE BATCH RULE leaves -- the order
+ * of the reverse edges within a row that was not re-pruned.
+ *   The device graph is always exactly flatten() of the host graph the engine would save, neighbour for neighbour in
+ * the same order: every search entry point answers, bit for bit, as a fresh engine that loads the saved index.
+ *   An append first waits, on the host, for the handle's outstanding device-buffer searches, as expann_graph_search
+ * does: a search enqueued before the append runs on the graph as it was.
+ *   A row filter and row groups are CLEARED, as expann_antitopo_store clears them; the uint8 and the ranged-int8 copy
+ * of the rows are dropped and made again by their next use (the ranged scale is global: it may change with the rows).
+ * THE DEVICE ROUTE serves engines with fp32 rows, ortho_count == 1 and at least 2048 rows.  The handle's FIRST append
+ * uploads the builder's view of the graph once -- the fixed-stride rows of (id, distance) that
+ * expann_graph_build_batched works on, (M0 + 64) x 8 bytes per row: 1.47 GB at 1 M rows and M = 60 -- and keeps it,
+ * sized to a CAPACITY in rows, beside the walk's tables; the rows themselves are not kept twice.  Every later append
+ * uploads the new rows and their levels, runs the batches on the resident state, and remakes the walk's tables --
+ * the fixed-stride layer-0 table and the CSR -- from it on the device (csrc/graph_append.hpp: a degree pass, an
+ * exclusive scan, a fill); no transfer and no host work is proportional to the rows already in the graph.  The
+ * capacity covers everything that is sized by the row count (rows, tables, builder state, visited sets);
+ * expann_antitopo_reserve sets it, a full handle grows by half, and the upper-layer arrays have a capacity of their
+ * own.  The capacity belongs to the device graph: expann_antitopo_build and expann_antitopo_load make a new one.
+ *   The host index goes stale: an append adds the new rows to the host's vectors and marks the adjacency stale; what
+ * reads the host graph -- expann_antitopo_save, _store, _store_batched, _build -- first downloads the builder's state.
+ * expann_antitopo_size is right at all times.
+ *   A batch whose construction search overflows its candidates queue leaves the graph as it was after the batch
+ * before: the call returns EXPANN_ERR_OVERFLOW, *n_appended says how many rows are in, and the engine answers as if
+ * only those had been given (the level generator stands after that many draws).
+ * THE HOST ROUTE, inside the same call: engines with binary16 rows (the builder works on fp32 rows, the handle holds
+ * halves), with ortho_count != 1, or smaller than 2048 rows take expann_antitopo_store_batched +
+ * expann_antitopo_build as they are -- correct, and no faster.
+ * Errors, all before the device is touched: e == NULL, or rows == NULL with n > 0, EXPANN_ERR_INVALID_ARG; before
+ * expann_antitopo_build EXPANN_ERR_NOT_BUILT; n == 0 is EXPANN_OK and does nothing.  n_appended may be NULL.
+ * expann_antitopo_reserve below the current capacity does nothing; before expann_antitopo_build it is
+ * EXPANN_ERR_NOT_BUILT; on an engine of the host route it is EXPANN_OK and does nothing.
+ * expann_graph_get_stat (expann_antitopo_get_stat reads the engine's graph handle by the same names; before
+ * expann_antitopo_build EXPANN_ERR_NOT_BUILT): "append_calls", "append_rows", "append_batches", "append_device" =
+ * appends served on the device, "append_host" = appends that took the host route, "capacity_rows", "graph_reallocs" =
+ * appends that had to grow the capacity; "append_tables_ns" = device time of the last remake of the walk's tables,
+ * "append_edges" = the edges of all layers it counted.  The host route makes a new graph handle; the counts are
+ * carried over.
+ * Not offered: rows already on the device; removal from a graph; a deferred append; the sharded handles; making the
+ * builder's state from the device CSR instead of the one-time upload; giving the resident state's memory back short
+ * of destroying the engine; more than 8 Mi rows (the host route serves them). */
+int expann_antitopo_append(expann_antitopo* e, const float* rows, size_t n, size_t* n_appended);
+int expann_antitopo_reserve(expann_antitopo* e, size_t n_rows);
+int expann_antitopo_get_stat(expann_antitopo* e, const char* name, uint64_t* out);
+/* The library calls under the device route, for callers that keep their own host graph (gpu_antitopo_engine.h is
+ * one).  expann_graph_adopt_build_state makes the builder's state resident: the arrays of
+ * expann_graph_build_batched for the handle's n rows (levels[n], upper_idx[n], ids0 / d0 [n][stride0], deg0[n], idsu
+ * / du [(l - 1) * U + upper_idx[v]][strideu], degu), which must describe the graph the handle was created from, and
+ * the builder's parameters; every id, level and degree is checked (a row holds at most M0 / M edges).  Binary16
+ * handles and handles beyond 8 Mi rows are EXPANN_ERR_UNSUPPORTED.  expann_graph_append inserts rows[n][dim] with
+ * levels[n] by THE BATCH RULE (max_batch = 0) and remakes the walk's tables; *max_layer_out / *starting_vertex_out /
+ * *n_appended (each may be NULL) receive the graph's after the call, also with EXPANN_ERR_OVERFLOW (above); before
+ * expann_graph_adopt_build_state it is EXPANN_ERR_NOT_BUILT.  expann_graph_build_state_shape fills shape[6] = {rows,
+ * U_stride, n_upper_layers, U, stride0, strideu} and expann_graph_read_build_state downloads the arrays in that
+ * shape: the upper arrays are [n_upper_layers][U_stride] rows, of which the first U per layer are in use.
+ * expann_graph_reserve grows the capacity of any graph handle (EXPANN_ERR_UNSUPPORTED beyond 8 Mi rows).
+ * expann_graph_note_host_append counts one append of `rows` rows served by the host route, on top of carried[6] =
+ * {"append_calls", "append_rows", "append_batches", "append_device", "append_host", "graph_reallocs"} of the handle
+ * it replaces (NULL: on top of its own). */
+int expann_graph_reserve(expann_graph* g, size_t n_rows);
+int expann_graph_adopt_build_state(expann_graph* g, size_t M, size_t M0, size_t ef_construction, size_t prune_overflow,
+                                   float ortho_factor, float ortho_bias, const uint8_t* levels, const int32_t* upper_idx,
+                                   const uint32_t* ids0, const float* d0, const uint32_t* deg0, size_t stride0, size_t U,
+                                   size_t n_upper_layers, const uint32_t* idsu, const float* du, const uint32_t* degu,
+                                   size_t strideu);
+int expann_graph_append(expann_graph* g, const float* rows, size_t n, const uint8_t* levels, uint32_t* max_layer_out,
+                        uint32_t* starting_vertex_out, size_t* n_appended);
+int expann_graph_build_state_shape(expann_graph* g, size_t* shape);
+int expann_graph_read_build_state(expann_graph* g, uint8_t* levels, int32_t* upper_idx, uint32_t* ids0, float* d0,
+                                  uint32_t* deg0, uint32_t* idsu, float* du, uint32_t* degu);
+int expann_graph_note_host_append(expann_graph* g, const uint64_t* carried, size_t rows);
+
 #ifdef __cplusplus
 }
 #endif
