@@ -56,6 +56,8 @@ ABI_SYMBOLS = [
     "expann_antitopo_append", "expann_antitopo_reserve", "expann_antitopo_get_stat",
     "expann_graph_reserve", "expann_graph_adopt_build_state", "expann_graph_append",
     "expann_graph_build_state_shape", "expann_graph_read_build_state", "expann_graph_note_host_append",
+    "expann_antitopo_remove", "expann_antitopo_compact_row_filter", "expann_graph_remove",
+    "expann_graph_note_host_remove", "expann_graph_read_row_filter",
 ]
 GROUP_ANY = 0xFFFFFFFF  # EXPANN_GROUP_ANY: the group a query names to search every row
 
@@ -384,6 +386,18 @@ def load():
         L.expann_graph_read_build_state.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.expann_graph_note_host_append.restype = C.c_int
         L.expann_graph_note_host_append.argtypes = [vp, C.POINTER(C.c_uint64), sz]
+    if hasattr(L, "expann_antitopo_remove"):  # (as above: an older build cannot remove rows from a graph)
+        szp = C.POINTER(C.c_size_t)
+        L.expann_antitopo_remove.restype = C.c_int
+        L.expann_antitopo_remove.argtypes = [vp, vp, sz, szp]
+        L.expann_antitopo_compact_row_filter.restype = C.c_int
+        L.expann_antitopo_compact_row_filter.argtypes = [vp, szp]
+        L.expann_graph_remove.restype = C.c_int
+        L.expann_graph_remove.argtypes = [vp, vp, sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), szp]
+        L.expann_graph_note_host_remove.restype = C.c_int
+        L.expann_graph_note_host_remove.argtypes = [vp, C.POINTER(C.c_uint64), sz]
+        L.expann_graph_read_row_filter.restype = C.c_int
+        L.expann_graph_read_row_filter.argtypes = [vp, vp, sz]
     _lib = L
     return L
 

@@ -15,11 +15,13 @@
 #include <string>
 #include <vector>
 
+#include "bf_remove.hpp"
 #include "filter_rows.hpp"
 #include "graph_append.hpp"
 #include "graph_build.hpp"
 #include "graph_flat_scan.hpp"
 #include "graph_options.hpp"
+#include "graph_remove.hpp"
 #include "graph_search.hpp"
 #include "host_common.hpp"
 #include "quantize.hpp"
@@ -150,6 +152,10 @@ struct GraphStats {
 	double stat_redo_ms = 0;
 	// appends {calls, rows, batches, served on the device, served by the host route, capacity growths}
 	uint64_t stat_append[6] = {0, 0, 0, 0, 0, 0};
+	// removes {calls, rows, touched rows, truncated rows, served on the device, served by the host route}; the device
+	// time of the last call's touch + gather + prune
+	uint64_t stat_remove[6] = {0, 0, 0, 0, 0, 0};
+	uint64_t remove_repair_ns = 0;
 };
 
 // the handle's own stream, the host-buffer calls' events, launch plans, statistics, the last error
@@ -1477,6 +1483,18 @@ int expann_graph_get_stat(expann_graph* g, const char* name, uint64_t* out) {
 	    {"append_tables_ns", [](G g) { return g->tables_ns; }},
 	    {"append_edges", [](G g) { return g->n_edges; }},
 	};
+	// the remove's rows (THE GRAPH REMOVE RULE)
+	static const StatRow kGraphRemoveStatTable[] = {
+	    {"remove_calls", [](G g) { return g->stat_remove[0]; }},
+	    {"remove_rows", [](G g) { return g->stat_remove[1]; }},
+	    {"remove_touched_rows", [](G g) { return g->stat_remove[2]; }},
+	    // touched rows whose distinct candidates exceeded max(ef_construction, M0)
+	    {"remove_truncated_rows", [](G g) { return g->stat_remove[3]; }},
+	    {"remove_device", [](G g) { return g->stat_remove[4]; }},
+	    {"remove_host", [](G g) { return g->stat_remove[5]; }},
+	    // device time of touch + gather + prune of the last call
+	    {"remove_repair_ns", [](G g) { return g->remove_repair_ns; }},
+	};
 	auto read_from = [&](const StatRow* rows, size_t n_rows) {
 		for (size_t i = 0; i < n_rows; ++i)
 			if (!std::strcmp(name, rows[i].name)) {
@@ -1487,7 +1505,8 @@ int expann_graph_get_stat(expann_graph* g, const char* name, uint64_t* out) {
 	};
 	if (read_from(kGraphStatTable, sizeof(kGraphStatTable) / sizeof(StatRow)) ||
 	    read_from(kGraphRangeStatTable, sizeof(kGraphRangeStatTable) / sizeof(StatRow)) ||
-	    read_from(kGraphAppendStatTable, sizeof(kGraphAppendStatTable) / sizeof(StatRow)))
+	    read_from(kGraphAppendStatTable, sizeof(kGraphAppendStatTable) / sizeof(StatRow)) ||
+	    read_from(kGraphRemoveStatTable, sizeof(kGraphRemoveStatTable) / sizeof(StatRow)))
 		return EXPANN_OK;
 	return g->fail(EXPANN_ERR_INVALID_ARG, std::string("unknown stat: ") + name);
 }
@@ -2307,6 +2326,240 @@ int expann_graph_note_host_append(expann_graph* g, const uint64_t* carried, size
 	return EXPANN_OK;
 }
 
+// ---- rows taken out of a built graph (THE GRAPH REMOVE RULE, graph_remove.hpp) ----------------------------------
+int expann_graph_remove(expann_graph* g, const uint64_t* ids, size_t n_ids, uint32_t* max_layer_out,
+                        uint32_t* starting_vertex_out, size_t* n_removed) {
+	if (n_removed)
+		*n_removed = 0;
+	if (!g)
+		return EXPANN_ERR_INVALID_ARG;
+	if (n_ids && !ids)
+		return g->fail(EXPANN_ERR_INVALID_ARG, "expann_graph_remove: ids == NULL");
+	if (!g->resident)
+		return g->fail(EXPANN_ERR_NOT_BUILT, "expann_graph_remove before expann_graph_adopt_build_state");
+	if (max_layer_out)
+		*max_layer_out = g->n_layers;
+	if (starting_vertex_out)
+		*starting_vertex_out = g->starting_vertex;
+	if (n_ids == 0)
+		return EXPANN_OK;
+	const size_t keep_cap = std::max(g->ef_construction, g->M0);
+	if (keep_cap > (size_t)kPruneMaxCand || g->n >= (1ull << 32) - 64)
+		return g->fail(EXPANN_ERR_UNSUPPORTED, "expann_graph_remove: max(ef_construction, M0) <= 1024");
+	HIP_TRY(g, hipSetDevice(g->device));
+	HIP_TRY(g, graph_wait_outstanding(g));  // (searches in flight read the tables this call remakes)
+	hipStream_t st = g->stream;
+	const size_t n = g->n, words = keep_words(n), uwords = keep_words(g->U);
+	const size_t L_used = g->n_layers - 1, task_cap = n + L_used * g->U;
+	const uint64_t entries = (uint64_t)g->n_layers * n;
+	if (entries >= (1ull << 32) * (kBlock / 16))
+		return g->fail(EXPANN_ERR_UNSUPPORTED, "expann_graph_remove: too many rows");
+	const uint32_t chunk = (uint32_t)std::min<size_t>(task_cap, 16384);  // lists of at most 16384 x 1024 x 8 bytes
+	// stat: {survivors, OR, id out of range, -} + segment counts; the same for the upper rows; ctr: {touched rows,
+	// truncated rows, the top key's two words}
+	DevPtr<uint32_t> keep, stat, ukeep, ustat, ctr;
+	DevPtr<PruneTask> tasks;
+	DevBuf d_ids;
+	HIP_TRY(g, hipMalloc(&keep, sizeof(uint32_t) * 2 * words));
+	HIP_TRY(g, hipMalloc(&ukeep, sizeof(uint32_t) * std::max<size_t>(2 * uwords, 1)));
+	HIP_TRY(g, hipMalloc(&stat, sizeof(uint32_t) * (4 + kFilterSegs)));
+	HIP_TRY(g, hipMalloc(&ustat, sizeof(uint32_t) * (4 + kFilterSegs)));
+	HIP_TRY(g, hipMalloc(&ctr, sizeof(uint32_t) * 4));
+	HIP_TRY(g, hipMalloc(&tasks, sizeof(PruneTask) * task_cap));
+	HIP_TRY(g, d_ids.alloc(sizeof(uint64_t) * n_ids));
+	OwnedEvent ev[4];  // around the touch pass; around gather + prune
+	for (OwnedEvent& e : ev)
+		HIP_TRY(g, hipEventCreate(&e));
+	HIP_TRY(g, hipMemsetAsync(stat, 0, sizeof(uint32_t) * (4 + kFilterSegs), st));
+	HIP_TRY(g, hipMemsetAsync(ustat, 0, sizeof(uint32_t) * (4 + kFilterSegs), st));
+	HIP_TRY(g, hipMemsetAsync(ctr, 0, sizeof(uint32_t) * 4, st));
+	HIP_TRY(g, hipMemsetAsync(keep, 0xFF, sizeof(uint32_t) * words, st));
+	if (uwords)
+		HIP_TRY(g, hipMemsetAsync(ukeep, 0xFF, sizeof(uint32_t) * uwords, st));
+	HIP_TRY(g, hipMemcpyAsync(d_ids.p, ids, sizeof(uint64_t) * n_ids, hipMemcpyHostToDevice, st));
+	hipLaunchKernelGGL(remove_mark_kernel, dim3((uint32_t)std::min<size_t>((n_ids + kBlock - 1) / kBlock, 4096)), dim3(kBlock), 0,
+	                   st, d_ids.as<const uint64_t>(), n_ids, (uint32_t)n, keep.get(), stat.get() + 2);
+	hipLaunchKernelGGL(filter_count_kernel, dim3(kFilterSegs), dim3(kBlock), 0, st, keep.get(), (uint32_t)n, (uint32_t)words,
+	                   stat.get(), stat.get() + 4);
+	hipLaunchKernelGGL(remove_word_rank_kernel, dim3(kFilterSegs), dim3(kBlock), 0, st, (const uint32_t*)keep.get(),
+	                   (uint32_t)words, (const uint32_t*)(stat.get() + 4), keep.get() + words);
+	RemoveView rv{};
+	rv.g = graph_build_view(g);
+	rv.n_layers = g->n_layers;
+	rv.bits = keep;
+	rv.word_rank = keep.get() + words;
+	rv.ubits = ukeep;
+	rv.uword_rank = ukeep.get() + uwords;
+	const dim3 row_grid((uint32_t)((n + kBlock - 1) / kBlock)), entry_grid((uint32_t)((entries + kBlock / 16 - 1) / (kBlock / 16)));
+	hipLaunchKernelGGL(graph_remove_mark_upper_kernel, row_grid, dim3(kBlock), 0, st, rv, ukeep.get());
+	hipLaunchKernelGGL(filter_count_kernel, dim3(kFilterSegs), dim3(kBlock), 0, st, ukeep.get(), (uint32_t)g->U, (uint32_t)uwords,
+	                   ustat.get(), ustat.get() + 4);
+	hipLaunchKernelGGL(remove_word_rank_kernel, dim3(kFilterSegs), dim3(kBlock), 0, st, (const uint32_t*)ukeep.get(),
+	                   (uint32_t)uwords, (const uint32_t*)(ustat.get() + 4), ukeep.get() + uwords);
+	HIP_TRY(g, hipEventRecord(ev[0], st));
+	hipLaunchKernelGGL(graph_remove_touch_kernel, entry_grid, dim3(kBlock), 0, st, rv, tasks.get(), (uint32_t)task_cap, chunk,
+	                   ctr.get());
+	HIP_TRY(g, hipEventRecord(ev[1], st));
+	hipLaunchKernelGGL(graph_remove_top_kernel, dim3(std::min<uint32_t>(row_grid.x, 1024)), dim3(kBlock), 0, st, rv,
+	                   (unsigned long long*)(ctr.get() + 2));
+	HIP_TRY(g, hipGetLastError());
+	// the call's one early host wait: nothing of the handle has changed yet
+	uint32_t seen[4] = {0, 0, 0, 0}, useen[4] = {0, 0, 0, 0}, h_ctr[4] = {0, 0, 0, 0};
+	HIP_TRY(g, hipMemcpyAsync(seen, stat, sizeof(seen), hipMemcpyDeviceToHost, st));
+	HIP_TRY(g, hipMemcpyAsync(useen, ustat, sizeof(useen), hipMemcpyDeviceToHost, st));
+	HIP_TRY(g, hipMemcpyAsync(h_ctr, ctr, sizeof(h_ctr), hipMemcpyDeviceToHost, st));
+	HIP_TRY(g, hipStreamSynchronize(st));
+	if (seen[2])
+		return g->fail(EXPANN_ERR_INVALID_ARG, "expann_graph_remove: an id at or beyond the graph's size");
+	const size_t n_new = seen[0], U_new = useen[0], n_touched = h_ctr[0];
+	if (n_new == 0)
+		return g->fail(EXPANN_ERR_INVALID_ARG, "expann_graph_remove: would leave no row (a graph is never empty)");
+	if (n_touched > task_cap)
+		return g->fail(EXPANN_ERR_HIP, "expann_graph_remove: more touched rows than rows");
+	const uint32_t top_level = h_ctr[3], start_new = 0xFFFFFFFFu - h_ctr[2];
+	// everything built aside, allocated before the first row changes
+	const size_t cap = g->cap_rows, s0 = g->bstride0, su = g->bstrideu, up_rows = g->L_cap * g->U_cap;
+	const size_t row_bytes = (size_t)g->dim * 4, n_chunks = (n_touched + chunk - 1) / chunk;
+	DevPtr<void> vec;
+	DevPtr<uint8_t> level;
+	DevPtr<int32_t> upper_idx;
+	DevPtr<uint32_t> id0, deg0, idu, degu, list_cnt;
+	DevPtr<float> d0, du;
+	DevPtr<md_pair> lists;
+	HIP_TRY(g, hipMalloc(&vec, cap * row_bytes));
+	HIP_TRY(g, hipMalloc(&level, cap));
+	HIP_TRY(g, hipMalloc(&upper_idx, cap * 4));
+	HIP_TRY(g, hipMalloc(&id0, cap * s0 * 4));
+	HIP_TRY(g, hipMalloc(&d0, cap * s0 * 4));
+	HIP_TRY(g, hipMalloc(&deg0, cap * 4));
+	HIP_TRY(g, hipMalloc(&idu, std::max<size_t>(up_rows * su, 1) * 4));
+	HIP_TRY(g, hipMalloc(&du, std::max<size_t>(up_rows * su, 1) * 4));
+	HIP_TRY(g, hipMalloc(&degu, std::max<size_t>(up_rows, 1) * 4));
+	HIP_TRY(g, hipMalloc(&lists, std::max<size_t>((size_t)chunk * keep_cap, 1) * sizeof(md_pair)));
+	HIP_TRY(g, hipMalloc(&list_cnt, std::max<size_t>(chunk, 1) * 4));
+	std::vector<uint32_t> h_chunk(std::max<size_t>(n_chunks, 1), 0);
+	for (size_t c = 0; c < n_chunks; ++c)
+		h_chunk[c] = (uint32_t)std::min<size_t>(chunk, n_touched - c * chunk);
+	DevPtr<uint32_t> chunk_cnt;
+	HIP_TRY(g, hipMalloc(&chunk_cnt, h_chunk.size() * 4));
+	HIP_TRY(g, hipMemcpyAsync(chunk_cnt, h_chunk.data(), h_chunk.size() * 4, hipMemcpyHostToDevice, st));
+	HIP_TRY(g, hipMemsetAsync(deg0, 0, cap * 4, st));
+	HIP_TRY(g, hipMemsetAsync(degu, 0, up_rows * 4, st));
+	// from here on the handle changes
+	g->forget<GraphRowFilter>();
+	g->forget<GraphRowGroups>();
+	g->forget<GraphRowBytes>();
+	const BuildVariant* bv = build_variant(g->dim);
+	const uint32_t cus = (uint32_t)num_cus(g->device);
+	HIP_TRY(g, hipEventRecord(ev[2], st));
+	for (size_t c = 0; c < n_chunks; ++c) {
+		RemoveGatherParams gp{};
+		gp.r = rv;
+		gp.tasks = tasks.get() + c * chunk;
+		gp.n_tasks = h_chunk[c];
+		gp.keep_cap = (uint32_t)keep_cap;
+		gp.lists = lists;
+		gp.list_cnt = list_cnt;
+		gp.n_truncated = ctr.get() + 1;
+		gp.dim = (uint32_t)g->dim;
+		hipLaunchKernelGGL(graph_remove_gather_kernel, dim3(std::min<uint32_t>(h_chunk[c], cus * 8)), dim3(kBlock), 0, st, gp);
+		BuildPruneParams pp{};
+		pp.g = rv.g;
+		pp.tasks = gp.tasks;
+		pp.n_tasks = chunk_cnt.get() + c;
+		pp.lists = lists;
+		pp.list_cnt = list_cnt;
+		pp.ef = (uint32_t)keep_cap;
+		pp.ortho_factor = g->ortho_factor;
+		pp.ortho_bias = g->ortho_bias;
+		pp.prune_overflow = (uint32_t)g->prune_overflow;
+		pp.dim = (uint32_t)g->dim;
+		hipLaunchKernelGGL(bv->prune, dim3(std::min<uint32_t>(h_chunk[c], cus * 16)), dim3(kPruneThreads),
+		                   bv->d == 0 ? (size_t)g->dim * sizeof(float) : 0, st, pp);
+	}
+	HIP_TRY(g, hipEventRecord(ev[3], st));
+	CompactRowsParams cp{};
+	cp.bits = keep;
+	cp.word_rank = keep.get() + words;
+	cp.src = g->d_vectors.as<const uint4>();
+	cp.dst = vec.as<uint4>();
+	cp.chunks = (uint32_t)(row_bytes / 16);
+	hipLaunchKernelGGL(compact_rows_kernel, dim3((uint32_t)(words / 4)), dim3(kBlock), 0, st, cp);
+	RemoveCompactParams rc{};
+	rc.r = rv;
+	rc.level = level;
+	rc.upper_idx = upper_idx;
+	rc.id0 = id0;
+	rc.d0 = d0;
+	rc.deg0 = deg0;
+	rc.idu = idu;
+	rc.du = du;
+	rc.degu = degu;
+	hipLaunchKernelGGL(graph_remove_compact_kernel, entry_grid, dim3(kBlock), 0, st, rc);
+	HIP_TRY(g, hipGetLastError());
+	HIP_TRY(g, hipMemcpyAsync(h_ctr, ctr, sizeof(h_ctr), hipMemcpyDeviceToHost, st));
+	HIP_TRY(g, hipStreamSynchronize(st));
+	float ms_touch = 0, ms_repair = 0;
+	HIP_TRY(g, hipEventElapsedTime(&ms_touch, ev[0], ev[1]));
+	HIP_TRY(g, hipEventElapsedTime(&ms_repair, ev[2], ev[3]));
+	g->d_vectors = std::move(vec);
+	g->d_level = std::move(level);
+	g->d_upper_idx = std::move(upper_idx);
+	g->d_id0 = std::move(id0);
+	g->d_d0 = std::move(d0);
+	g->d_deg0 = std::move(deg0);
+	g->d_idu = std::move(idu);
+	g->d_du = std::move(du);
+	g->d_degu = std::move(degu);
+	g->n = n_new;
+	g->U = U_new;
+	g->n_layers = top_level + 1;
+	g->starting_vertex = start_new;
+	if (int rc2 = graph_rebuild_tables(g))
+		return rc2;
+	++g->stat_remove[0];
+	g->stat_remove[1] += n - n_new;
+	g->stat_remove[2] += n_touched;
+	g->stat_remove[3] += h_ctr[1];
+	++g->stat_remove[4];
+	g->remove_repair_ns = (uint64_t)(((double)ms_touch + (double)ms_repair) * 1e6);
+	if (n_removed)
+		*n_removed = n - n_new;
+	if (max_layer_out)
+		*max_layer_out = g->n_layers;
+	if (starting_vertex_out)
+		*starting_vertex_out = g->starting_vertex;
+	return EXPANN_OK;
+}
+
+// carried: the seven remove counters, then the six append counters, of the handle the host route replaced
+int expann_graph_note_host_remove(expann_graph* g, const uint64_t* carried, size_t rows) {
+	if (!g)
+		return EXPANN_ERR_INVALID_ARG;
+	if (carried) {
+		std::copy(carried, carried + 6, g->stat_remove);
+		g->remove_repair_ns = carried[6];
+		std::copy(carried + 7, carried + 13, g->stat_append);
+	}
+	++g->stat_remove[0];
+	g->stat_remove[1] += rows;
+	++g->stat_remove[5];
+	return EXPANN_OK;
+}
+
+int expann_graph_read_row_filter(expann_graph* g, uint32_t* allow_bits, size_t n_words) {
+	if (!g)
+		return EXPANN_ERR_INVALID_ARG;
+	if (!g->filter_on)
+		return g->fail(EXPANN_ERR_INVALID_ARG, "no row filter in force");
+	const size_t words = (g->n + 31) / 32;
+	if (!allow_bits || n_words < words)
+		return g->fail(EXPANN_ERR_INVALID_ARG, "expann_graph_read_row_filter: NULL pointer or too few words");
+	HIP_TRY(g, hipSetDevice(g->device));
+	HIP_TRY(g, hipMemcpy(allow_bits, g->d_allow, words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	return EXPANN_OK;
+}
+
 // ---- the graph engine behind one handle (host build + device queries) --------------------
 }  // extern "C"
 
@@ -2532,6 +2785,32 @@ int expann_antitopo_append(expann_antitopo* e, const float* rows, size_t n, size
 	int rc = EXPANN_OK;
 	ANTITOPO_TRY(e, rc = e->eng->append_rows(rows, n, n_appended));
 	return rc == EXPANN_OK ? rc : e->fail(rc, expann_graph_last_error(e->eng->graph));
+}
+
+int expann_antitopo_remove(expann_antitopo* e, const uint64_t* ids, size_t n_ids, size_t* n_removed) {
+	if (n_removed)
+		*n_removed = 0;
+	if (!e || (!ids && n_ids))
+		return e ? e->fail(EXPANN_ERR_INVALID_ARG, "expann_antitopo_remove: ids == NULL") : EXPANN_ERR_INVALID_ARG;
+	if (!e->eng->graph)
+		return e->fail(EXPANN_ERR_NOT_BUILT, "expann_antitopo_remove before build()");
+	int rc = EXPANN_OK;
+	ANTITOPO_TRY(e, rc = e->eng->remove_rows(ids, n_ids, n_removed));
+	const std::string& why = e->eng->remove_error;
+	return rc == EXPANN_OK ? rc : e->fail(rc, why.empty() ? expann_graph_last_error(e->eng->graph) : why);
+}
+
+int expann_antitopo_compact_row_filter(expann_antitopo* e, size_t* n_removed) {
+	if (n_removed)
+		*n_removed = 0;
+	if (!e)
+		return EXPANN_ERR_INVALID_ARG;
+	if (!e->eng->graph)
+		return e->fail(EXPANN_ERR_NOT_BUILT, "expann_antitopo_compact_row_filter before build()");
+	int rc = EXPANN_OK;
+	ANTITOPO_TRY(e, rc = e->eng->compact_row_filter(n_removed));
+	const std::string& why = e->eng->remove_error;
+	return rc == EXPANN_OK ? rc : e->fail(rc, why.empty() ? expann_graph_last_error(e->eng->graph) : why);
 }
 
 int expann_antitopo_reserve(expann_antitopo* e, size_t n_rows) {

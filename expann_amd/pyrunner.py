@@ -304,6 +304,31 @@ class AntitopoEngine:
             raise _lib.ExpannError(_lib.ERR_NOT_BUILT, "reserve() before build()")
         self._check(self._L.expann_antitopo_reserve(self._h, int(n)))
 
+    def remove(self, ids):
+        """expann_antitopo_remove: the rows `ids` (any order, repeats allowed) leave the BUILT graph -- THE GRAPH REMOVE
+        RULE, include/expann_hip.h: survivors keep their order (id i becomes i minus the removed ids below i), every
+        row that lost a neighbour adopts the surviving neighbours of the neighbours it lost and is pruned again by the
+        builder's rule, on the device (fp32 rows, ortho_count 1, at least 2048 rows; other engines take the host's
+        statement of the same rule and a re-upload).  size() drops, the capacity stays, a row filter and row groups
+        are cleared.  An id >= size() or a removal of every row raises and leaves the engine as it was.  Returns the
+        number of rows removed."""
+        if self._h is None:
+            raise _lib.ExpannError(_lib.ERR_NOT_BUILT, "remove() before build()")
+        a = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        done = C.c_size_t(0)
+        self._check(self._L.expann_antitopo_remove(self._h, a.ctypes.data, a.shape[0], C.byref(done)))
+        return int(done.value)
+
+    def compact_row_filter(self):
+        """expann_antitopo_compact_row_filter: remove() of the rows the bitmap filter in force disallows -- tombstones
+        made permanent.  No filter in force, or one that allows no row, raises; a filter that allows every row removes
+        nothing and is cleared.  Returns the number of rows removed."""
+        if self._h is None:
+            raise _lib.ExpannError(_lib.ERR_NOT_BUILT, "compact_row_filter() before build()")
+        done = C.c_size_t(0)
+        self._check(self._L.expann_antitopo_compact_row_filter(self._h, C.byref(done)))
+        return int(done.value)
+
     def stat(self, name):
         """expann_antitopo_get_stat: a counter of the engine's graph handle by its expann_graph_get_stat name
         ("append_device", "capacity_rows", "filter_active", ...)"""

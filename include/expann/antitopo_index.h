@@ -441,6 +441,106 @@ struct antitopo_index {
 		}
 	}
 
+	// ---- Extension: rows taken out of a built graph (THE GRAPH REMOVE RULE, expann_hip.h) ---------
+	// `ids` in any order, repeats allowed.  Every row that lost a neighbour adopts the surviving neighbours of the
+	// neighbours it lost (one hop, lengths in the reference's lane order), keeps the max(ef_construction, M0) smallest
+	// distinct (length, id) candidates and goes through prune_edges(l, v, false); every other row is only renumbered.
+	// All of it is read from the graph as it was before the call.  Survivors keep their order and their levels; the
+	// level generator is not touched.  Throws std::invalid_argument -- before anything changes -- for an id >= size()
+	// and for a removal that would leave no row.  The host route of the engines, and the C++ statement of the rule.
+	void remove_rows(const uint64_t* ids, size_t n, size_t* n_removed = nullptr) {
+		if (n_removed)
+			*n_removed = 0;
+		if (n == 0)
+			return;
+		if (!ids)
+			throw std::invalid_argument("antitopo_index::remove_rows: ids == NULL");
+		const size_t n_old = size();
+		std::vector<char> gone(n_old, 0);
+		size_t n_gone = 0;
+		for (size_t i = 0; i < n; ++i) {
+			if (ids[i] >= n_old)
+				throw std::invalid_argument("antitopo_index::remove_rows: id " + std::to_string(ids[i]) + " >= size");
+			n_gone += !gone[ids[i]];
+			gone[ids[i]] = 1;
+		}
+		if (n_gone == n_old)
+			throw std::invalid_argument("antitopo_index::remove_rows: the removal would leave no row");
+		const size_t keep_cap = std::max(conf.ef_construction, conf.M0);
+		// the touched rows, repaired in place under the old ids: a repair reads the row itself and rows of removed
+		// vertices, which no repair writes
+		for (size_t v = 0; v < n_old; ++v) {
+			if (gone[v])
+				continue;
+			for (size_t l = 0; l < hadj_flat_with_lengths[v].size(); ++l) {
+				auto& row_vl = hadj_flat_with_lengths[v][l];
+				bool touched = false;
+				for (auto& e : row_vl)
+					touched = touched || gone[e.second];
+				if (!touched)
+					continue;
+				std::vector<edge> cand;
+				std::set<size_t> seen;
+				for (auto& e : row_vl)
+					if (!gone[e.second]) {
+						cand.push_back(e);
+						seen.insert(e.second);
+					}
+				for (auto& e : row_vl) {
+					if (!gone[e.second])
+						continue;
+					for (auto& f : hadj_flat_with_lengths[e.second][l]) {
+						const size_t c = f.second;
+						if (gone[c] || c == v || seen.count(c))
+							continue;
+						seen.insert(c);
+						cand.emplace_back(d2(row(v), row(c)), c);
+					}
+				}
+				std::sort(cand.begin(), cand.end());
+				if (cand.size() > keep_cap)
+					cand.resize(keep_cap);
+				row_vl = cand;
+				prune_edges(l, v, false);
+			}
+		}
+		// survivors moved down in order, ids renumbered
+		std::vector<size_t> new_id(n_old, 0);
+		size_t m = 0;
+		for (size_t v = 0; v < n_old; ++v)
+			if (!gone[v])
+				new_id[v] = m++;
+		size_t top = 0, start = 0;
+		for (size_t v = 0; v < n_old; ++v) {
+			if (gone[v])
+				continue;
+			const size_t to = new_id[v];
+			if (to != v) {
+				std::copy(vectors.begin() + v * dim, vectors.begin() + (v + 1) * dim, vectors.begin() + to * dim);
+				hadj_flat_with_lengths[to] = std::move(hadj_flat_with_lengths[v]);
+				hadj_flat[to] = std::move(hadj_flat[v]);
+			}
+			for (size_t l = 0; l < hadj_flat_with_lengths[to].size(); ++l) {
+				for (auto& e : hadj_flat_with_lengths[to][l])
+					e.second = new_id[e.second];
+				update_edges(l, to);
+			}
+			const size_t lv = hadj_flat_with_lengths[to].size();  // level + 1
+			if (lv > top) {
+				top = lv;
+				start = to;
+			}
+		}
+		vectors.resize(m * dim);
+		hadj_flat_with_lengths.resize(m);
+		hadj_flat.resize(m);
+		visited.assign(m, 0);
+		max_layer = top;
+		starting_vertex = start;
+		if (n_removed)
+			*n_removed = n_gone;
+	}
+
 	// ---- the reference's index file (src/antitopo_engine.h:932-991 / :994-1074) -----------
 	void write_index(const std::string& path) const {
 		std::ofstream out(path, std::ios::binary);

@@ -139,6 +139,32 @@ struct gpu_antitopo_engine : public ann_engine<T, gpu_antitopo_engine<T>> {
 			if (expann_graph_get_stat(graph, names[i], six + i) != EXPANN_OK)
 				six[i] = 0;
 	}
+	// The builder's view of the graph handed to the handle, once (the first append or remove on the device route).
+	// *on_host is set when the handle cannot take it (EXPANN_ERR_UNSUPPORTED): the call goes the host route.
+	int adopt_on_device(bool* on_host) {
+		if (resident)
+			return EXPANN_OK;
+		refresh_host();
+		const auto g = index.to_strided({}, 64);
+		bool fits = true;  // (rows of a graph built with these M / M0: a foreign index file may hold longer ones)
+		for (size_t v = 0; v < g.n && fits; ++v)
+			fits = g.deg0[v] <= conf.M0;
+		for (size_t r = 0; r < g.degu.size() && fits; ++r)
+			fits = g.degu[r] <= conf.M;
+		const int rc = !fits ? EXPANN_ERR_UNSUPPORTED
+		                     : expann_graph_adopt_build_state(graph, conf.M, conf.M0, conf.ef_construction, conf.prune_overflow,
+		                                                      conf.ortho_factor, conf.ortho_bias, g.levels.data(),
+		                                                      g.upper_idx.data(), g.ids0.data(), g.d0.data(), g.deg0.data(),
+		                                                      g.stride0, g.U, g.n_upper_layers, g.idsu.data(), g.du.data(),
+		                                                      g.degu.data(), g.strideu);
+		if (rc == EXPANN_ERR_UNSUPPORTED)
+			*on_host = true;
+		else if (rc != EXPANN_OK)
+			return rc;
+		else
+			resident = true;
+		return EXPANN_OK;
+	}
 	// `n` rows appended to the built graph.  Returns the expann_status (message: expann_graph_last_error(graph));
 	// *n_appended: the rows that are in -- n, or fewer with EXPANN_ERR_OVERFLOW.  Throws what store_rows_batched and
 	// _build() throw on the host route.
@@ -152,25 +178,10 @@ struct gpu_antitopo_engine : public ann_engine<T, gpu_antitopo_engine<T>> {
 		if (!rows)
 			return EXPANN_ERR_INVALID_ARG;
 		bool on_host = append_on_host();
-		if (!on_host && !resident) {  // the handle's first append: the builder's view, uploaded once
-			const auto g = index.to_strided({}, 64);
-			bool fits = true;  // (rows of a graph built with these M / M0: a foreign index file may hold longer ones)
-			for (size_t v = 0; v < g.n && fits; ++v)
-				fits = g.deg0[v] <= conf.M0;
-			for (size_t r = 0; r < g.degu.size() && fits; ++r)
-				fits = g.degu[r] <= conf.M;
-			const int rc = !fits ? EXPANN_ERR_UNSUPPORTED
-			                     : expann_graph_adopt_build_state(graph, conf.M, conf.M0, conf.ef_construction, conf.prune_overflow,
-			                                                      conf.ortho_factor, conf.ortho_bias, g.levels.data(),
-			                                                      g.upper_idx.data(), g.ids0.data(), g.d0.data(), g.deg0.data(),
-			                                                      g.stride0, g.U, g.n_upper_layers, g.idsu.data(), g.du.data(),
-			                                                      g.degu.data(), g.strideu);
-			if (rc == EXPANN_ERR_UNSUPPORTED)
-				on_host = true;
-			else if (rc != EXPANN_OK)
+		if (!on_host) {  // the handle's first append: the builder's view, uploaded once
+			const int rc = adopt_on_device(&on_host);
+			if (rc != EXPANN_OK)
 				return rc;
-			else
-				resident = true;
 		}
 		if (on_host) {
 			refresh_host();
@@ -210,6 +221,111 @@ struct gpu_antitopo_engine : public ann_engine<T, gpu_antitopo_engine<T>> {
 		if (n_appended)
 			*n_appended = done;
 		return rc;
+	}
+	// ---- Extension: rows taken out of the built graph (THE GRAPH REMOVE RULE, expann_hip.h) ----
+	// the seven remove counters, then the six append counters (carried over a re-upload by the host route)
+	void read_remove_stats(uint64_t* thirteen) const {
+		static const char* const names[7] = {"remove_calls", "remove_rows", "remove_touched_rows", "remove_truncated_rows",
+		                                     "remove_device", "remove_host", "remove_repair_ns"};
+		for (int i = 0; i < 7; ++i)
+			if (expann_graph_get_stat(graph, names[i], thirteen + i) != EXPANN_OK)
+				thirteen[i] = 0;
+		read_append_stats(thirteen + 7);
+	}
+	std::string remove_error;  // what an engine-level refusal of the last remove_rows / compact_row_filter said
+	// The rows `ids` (any order, repeats allowed) taken out.  Returns the expann_status (message: remove_error, or when
+	// that is empty expann_graph_last_error(graph)); *n_removed: the distinct ids.  The routes are append_rows'.
+	// Refusals -- an id >= size, a removal that would leave no row -- are decided before anything changes.  Throws
+	// what _build() throws on the host route.
+	int remove_rows(const uint64_t* ids, size_t n, size_t* n_removed = nullptr) {
+		remove_error.clear();
+		if (n_removed)
+			*n_removed = 0;
+		if (!graph)
+			return EXPANN_ERR_NOT_BUILT;
+		if (n == 0)
+			return EXPANN_OK;
+		if (!ids)
+			return EXPANN_ERR_INVALID_ARG;
+		const size_t n_old = index.size();
+		std::vector<char> gone(n_old, 0);
+		size_t n_gone = 0;
+		for (size_t i = 0; i < n; ++i) {
+			if (ids[i] >= n_old) {
+				remove_error = "remove: id " + std::to_string(ids[i]) + " at or beyond size()";
+				return EXPANN_ERR_INVALID_ARG;
+			}
+			n_gone += !gone[ids[i]];
+			gone[ids[i]] = 1;
+		}
+		if (n_gone == n_old) {
+			remove_error = "remove: would leave no row (a graph is never empty)";
+			return EXPANN_ERR_INVALID_ARG;
+		}
+		bool on_host = append_on_host();
+		if (!on_host) {
+			const int rc = adopt_on_device(&on_host);
+			if (rc != EXPANN_OK)
+				return rc;
+		}
+		if (on_host) {
+			refresh_host();
+			uint64_t carried[13];
+			read_remove_stats(carried);
+			size_t removed = 0;
+			index.remove_rows(ids, n, &removed);
+			_build();
+			(void)expann_graph_note_host_remove(graph, carried, removed);
+			if (n_removed)
+				*n_removed = removed;
+			return EXPANN_OK;
+		}
+		uint32_t ml = 0, sv = 0;
+		size_t removed = 0;
+		const int rc = expann_graph_remove(graph, ids, n, &ml, &sv, &removed);
+		if (rc != EXPANN_OK)
+			return rc;
+		// the host's copy of the rows, compacted here: the one piece of work proportional to the size
+		size_t to = 0;
+		for (size_t v = 0; v < n_old; ++v)
+			if (!gone[v]) {
+				if (to != v)
+					std::copy(index.vectors.begin() + v * index.dim, index.vectors.begin() + (v + 1) * index.dim,
+					          index.vectors.begin() + to * index.dim);
+				++to;
+			}
+		index.vectors.resize(to * index.dim);
+		index.visited.assign(to, 0);
+		index.max_layer = ml;
+		index.starting_vertex = sv;
+		index.adjacency_stale = true;
+		download_fn = &gpu_antitopo_engine::download_adjacency;
+		if (n_removed)
+			*n_removed = removed;
+		return rc;
+	}
+	// remove_rows of the rows the bitmap filter in force disallows: tombstones made permanent.  No filter in force, or
+	// one that allows no row: EXPANN_ERR_INVALID_ARG.  A filter that allows every row removes nothing and is cleared.
+	int compact_row_filter(size_t* n_removed = nullptr) {
+		remove_error.clear();
+		if (n_removed)
+			*n_removed = 0;
+		if (!graph)
+			return EXPANN_ERR_NOT_BUILT;
+		const size_t n_old = index.size();
+		std::vector<uint32_t> bits((n_old + 31) / 32);
+		const int rc = expann_graph_read_row_filter(graph, bits.data(), bits.size());
+		if (rc != EXPANN_OK)
+			return rc;
+		std::vector<uint64_t> ids;
+		for (size_t v = 0; v < n_old; ++v)
+			if (!((bits[v >> 5] >> (v & 31)) & 1u))
+				ids.push_back(v);
+		if (ids.empty()) {
+			clear_row_filter();
+			return EXPANN_OK;
+		}
+		return remove_rows(ids.data(), ids.size(), n_removed);
 	}
 	// room for n_rows rows on the device, so that appends up to there reallocate nothing
 	int reserve(size_t n_rows) {

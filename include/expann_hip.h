@@ -614,8 +614,8 @@ int expann_clear_row_filter(expann_index* h);
  * EXPANN_ERR_NOT_BUILT.  expann_antitopo_store*, _build and _load clear the filter: it is a run-time property and is
  * not written to the index file.  expann_antitopo_set_row_filter_device takes device bits as
  * expann_graph_set_row_filter_device does.
- * Not offered: a filter for expann_graph_build_batched's searches, deleting rows.  (Per query: row groups, at the
- * end of this header.) */
+ * Not offered: a filter for expann_graph_build_batched's searches.  (Per query: row groups; deleting the rows a
+ * filter disallows: expann_antitopo_compact_row_filter, both at the end of this header.) */
 int expann_graph_set_row_filter(expann_graph* g, const uint32_t* allow_bits, size_t n_words);
 int expann_graph_set_row_filter_device(expann_graph* g, const uint32_t* d_allow_bits, size_t n_words, void* stream);
 int expann_graph_clear_row_filter(expann_graph* g);
@@ -1059,7 +1059,8 @@ int expann_compact_row_filter(expann_index* h, size_t* n_removed);
  * appends that had to grow the capacity; "append_tables_ns" = device time of the last remake of the walk's tables,
  * "append_edges" = the edges of all layers it counted.  The host route makes a new graph handle; the counts are
  * carried over.
- * Not offered: rows already on the device; removal from a graph; a deferred append; the sharded handles; making the
+ * Not offered: rows already on the device; a deferred append; the sharded handles (rows are taken OUT of a graph by
+ * THE GRAPH REMOVE RULE, at the end of this header); making the
  * builder's state from the device CSR instead of the one-time upload; giving the resident state's memory back short
  * of destroying the engine; more than 8 Mi rows (the host route serves them). */
 int expann_antitopo_append(expann_antitopo* e, const float* rows, size_t n, size_t* n_appended);
@@ -1092,6 +1093,77 @@ int expann_graph_build_state_shape(expann_graph* g, size_t* shape);
 int expann_graph_read_build_state(expann_graph* g, uint8_t* levels, int32_t* upper_idx, uint32_t* ids0, float* d0,
                                   uint32_t* deg0, uint32_t* idsu, float* du, uint32_t* degu);
 int expann_graph_note_host_append(expann_graph* g, const uint64_t* carried, size_t rows);
+
+/* Remove rows from a built graph engine: the neighbours of the removed rows are repaired on the device (appended;
+ * EXPANN_ABI_VERSION stays 2: nothing that existed changed, and a handle that never calls these allocates and
+ * launches exactly what it did).  The reference has no deletion: the rule is this project's own, exact, restated on
+ * the CPU (antitopo_index::remove_rows, include/expann/antitopo_index.h) and in NumPy (tests/graph_remove_helpers.py).
+ * THE GRAPH REMOVE RULE.  Let S be the distinct ids given to expann_antitopo_remove(e, ids, n_ids, &n_removed) -- any
+ * order, repeats allowed, as for expann_remove -- and n the size before the call.
+ *   IDS.  Survivors keep their order: the survivor with id i gets id i - |{s in S : s < i}|.  expann_antitopo_size
+ * drops by |S| = *n_removed, the next append gets ids from the new size on, and the level generator is not touched:
+ * it stands after as many draws as rows were ever inserted.
+ *   LEVELS.  A survivor keeps its level.  max_layer = 1 + the highest level among the survivors; starting_vertex =
+ * the lowest new id among the survivors of that level (what insert_with_level's `while (new_max_layer >= max_layer)`
+ * leaves for those rows in that order: the old starting vertex when nothing at the top is removed).  upper_idx is the
+ * rank among the survivors with level >= 1 in id order (to_strided's rule).
+ *   ROWS, per layer l and surviving vertex v of level >= l, everything read from the graph as it was BEFORE the call.
+ * An UNTOUCHED row -- no neighbour in S -- keeps its entries, their order and their lengths; only the ids are
+ * renumbered.  A TOUCHED row -- at least one neighbour in S -- is made again from these candidates: (1) its surviving
+ * neighbours with their stored lengths; (2) for every removed neighbour r, in row order, r's surviving layer-l
+ * neighbours c != v that are not candidates already, with length dist2(v, c) in the reference's 16-lane FMA order
+ * (the bits of dist2_ref_order, antitopo_index.h).  One hop only: the removed neighbours of a removed neighbour are
+ * not followed.  A candidate is identified by its id; an own entry wins over an adopted duplicate.  Of the distinct
+ * candidates the `cap` smallest in (length, id) order are kept, cap = max(ef_construction, M0) -- at most 1024, which
+ * expann_graph_adopt_build_state enforces: a touched row is pruned from no more candidates than an inserted row is --
+ * and that list goes through prune_edges(l, v, lazy = false) to at most M0 (layer 0) or M (above) edges: the
+ * builder's rule with the builder's arithmetic (ortho_term unfused, first of equals).  A touched row may end up
+ * empty.  No reverse edges are added; all touched rows are computed from the old graph, so the result does not depend
+ * on any order of processing.
+ *   The device graph is always exactly flatten() of the host graph the engine would save, neighbour for neighbour in
+ * the same order: every search entry point answers, bit for bit, as a fresh engine that loads the saved index.
+ *   A remove first waits, on the host, for the handle's outstanding device-buffer searches: a search enqueued before
+ * the remove runs on the graph as it was.  A row filter and row groups are CLEARED; the uint8 and the ranged-int8
+ * copy of the rows are dropped and made again by their next use.  The capacity stays: the freed room serves later
+ * appends.  The host adjacency goes stale exactly as after an append, and the host's copy of the vectors is compacted
+ * on the host -- the one piece of work proportional to n.
+ * THE DEVICE ROUTE serves engines with fp32 rows, ortho_count == 1, at least 2048 and at most 8 Mi rows at the time
+ * of the call; when the builder's state is not resident yet the call uploads it once, as a first append does.  On the
+ * handle's stream (csrc/graph_remove.hpp): the keep bitmap and the id map of expann_remove (csrc/keep_bitmap.hpp), a
+ * touch pass that lists the touched rows, a gather kernel -- one workgroup per touched row: candidates collected,
+ * deduplicated and cut to `cap` in LDS, adopted lengths by 16 lanes per row -- the builder's own build_prune_kernel
+ * over those lists, the compaction of rows, levels and adjacency arrays under the new ids into arrays built aside at
+ * the same capacity, and the append's remake of the walk's tables.  The out-of-range flag, the survivor count and the
+ * touched-row count are read at the call's one early host wait, and everything built aside is allocated before the
+ * first row changes.
+ * THE HOST ROUTE, inside the same call: every other engine takes antitopo_index::remove_rows followed by
+ * expann_antitopo_build -- correct, and no faster than a re-upload.
+ * Refusals, all decided before anything in the engine changes: e == NULL, or ids == NULL with n_ids > 0,
+ * EXPANN_ERR_INVALID_ARG; before expann_antitopo_build EXPANN_ERR_NOT_BUILT; an id >= size EXPANN_ERR_INVALID_ARG; a
+ * removal that would leave no row EXPANN_ERR_INVALID_ARG; n_ids == 0 is EXPANN_OK and nothing happens.  A refused
+ * call leaves the engine as it was and usable.  n_removed may be NULL.
+ * expann_antitopo_compact_row_filter applies the same rule with S = the rows the bitmap filter in force disallows: it
+ * makes tombstones permanent.  No filter in force, or a filter that allows no row: EXPANN_ERR_INVALID_ARG; a filter
+ * that allows every row removes nothing and is cleared.
+ * expann_graph_get_stat / expann_antitopo_get_stat: "remove_calls", "remove_rows", "remove_touched_rows",
+ * "remove_truncated_rows" = touched rows whose distinct candidates exceeded cap, "remove_device" / "remove_host" =
+ * removes by route, "remove_repair_ns" = device time of touch + gather + prune of the last call.  The host route
+ * makes a new graph handle; the counts are carried over.
+ * Not offered: ids already on the device; reverse edges for adopted neighbours; following more than one hop;
+ * shrinking the capacity; a deferred remove; the sharded handles; stable external ids. */
+int expann_antitopo_remove(expann_antitopo* e, const uint64_t* ids, size_t n_ids, size_t* n_removed);
+int expann_antitopo_compact_row_filter(expann_antitopo* e, size_t* n_removed);
+/* The library calls underneath.  expann_graph_remove applies the rule to a handle whose builder state is resident
+ * (before expann_graph_adopt_build_state EXPANN_ERR_NOT_BUILT); *max_layer_out / *starting_vertex_out / *n_removed
+ * (each may be NULL) receive the graph's after the call; the caller compacts its own host rows.
+ * expann_graph_note_host_remove counts one remove of `rows` rows served by the host route, on top of carried[13] = the
+ * seven remove counters above followed by the six append counters of expann_graph_note_host_append, both of the handle
+ * it replaces (NULL: on top of its own).  expann_graph_read_row_filter copies the bitmap filter in force to
+ * allow_bits[ceil(n / 32)] (no filter in force: EXPANN_ERR_INVALID_ARG). */
+int expann_graph_remove(expann_graph* g, const uint64_t* ids, size_t n_ids, uint32_t* max_layer_out,
+                        uint32_t* starting_vertex_out, size_t* n_removed);
+int expann_graph_note_host_remove(expann_graph* g, const uint64_t* carried, size_t rows);
+int expann_graph_read_row_filter(expann_graph* g, uint32_t* allow_bits, size_t n_words);
 
 #ifdef __cplusplus
 }
