@@ -34,7 +34,7 @@ constexpr DimTiles kScanI8AnyTiles = {0, {1, 4, 8}};
 // the fp16 filter streamed without the matrix cores (scan_direct_f16.hpp): queries per pass
 constexpr DimTiles kDirectF16Tiles[] = {{64, {2, 4}}, {128, {2, 4}}, {256, {2, 4}}, {512, {1, 2}},
                                         {768, {1}},   {832, {1}},    {960, {1}}};
-constexpr int kF16XDims[] = {64, 128};        // scan_gemm_f16x.hpp (the only form with a redo instance: speculation)
+constexpr int kF16XDims[] = {64, 128};        // scan_gemm_f16x.hpp (the form with a redo instance of its scan: speculation)
 constexpr int kF16YDims[] = {256, 512};       // scan_gemm_w8.hpp, fp16 instances
 constexpr int kF16KXDims[] = {768, 832, 960};  // scan_gemm_f16kx.hpp
 constexpr int kF16DbgDim = 128;               // the instance with the ablation switches compiled in
@@ -321,7 +321,7 @@ inline ScanPlan plan_scan(const PlanIndex& x, const PlanCall& c, const PlanAttem
 	        (x.i8_filter == 2 || (x.i8f_state != 2 && i8f_auto_region(x.n, c.m, c.k)));
 	// (room for the lists of queries with a clipped component)
 	p.i8f_min_cap = (p.i8f && x.cand_capacity <= 0) ? 4096 : 0;
-	// speculation: the scan_gemm_f16x / i8w streams -- the kernels with the redo pass's early exit --, batches beyond
+	// speculation: the scan_gemm_f16x / i8w streams -- the forms that have a redo pass --, batches beyond
 	// the latency mode's, no debug instance
 	p.speculate = p.family == ScanFamily::kF16X && !dbg && c.m > 64 && !a.spec_off && !filt && x.spec_rank >= 0 &&
 	              (x.spec_rank > 0 || spec_auto_region(c.m, c.k, p.i8f));

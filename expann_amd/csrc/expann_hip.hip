@@ -32,6 +32,7 @@
 #include "scan_gemm_i8.hpp"
 #include "scan_gemm_i8q.hpp"
 #include "scan_gemm_i8w.hpp"
+#include "scan_redo_i8.hpp"
 #include "scan_gemm_w8.hpp"
 #include "scan_gemm_kl.hpp"
 #include "scan_int8.hpp"
@@ -1207,8 +1208,7 @@ const GemmI8qVariant kGemmI8w[] = {
     GEMM_I8W(256, kU8L2, true, "U8L2"), GEMM_I8W(256, kI8L2, true, "I8L2"), GEMM_I8W(256, kI8IP, false, "I8IP")};
 // the int8 filter of fp32 rows (scan_gemm_i8f.hpp): the d = 128 i8w full scan on the index's int8 copy
 const GemmI8qVariant kGemmI8F = GEMM_I8W(128, kI8L2, true, "F32L2");
-// its instance for the redo pass of the speculative thresholds (waves without a live query slot only stage)
-void (*const kGemmI8FRedo)(GemmI8wParams) = scan_gemm_i8w_kernel<128, true, false, true>;
+// (its redo pass of the speculative thresholds has a kernel of its own: redo_stream_i8_kernel, scan_redo_i8.hpp)
 #undef GEMM_I8W
 // every other 8-bit dim (multiples of 64 up to 4096): the K-loop form with the dim known at run time
 // (scan_gemm_kl.hpp, int8 instances; d = 0 here, rows in the index's own d bytes, 128-row tiles, hit logs)
@@ -2537,8 +2537,9 @@ int SearchPass::run_level(size_t li) {
 }
 
 // The redo pass of the speculative thresholds, always enqueued behind the select of a speculating
-// search: compact operands of the failing queries with thresholds from the proven tau, the same scan kernel over
-// R query slots (workgroups of a query tile no failing query took leave at once), the logs' gather, one select
+// search: compact operands of the failing queries with thresholds from the proven tau, a scan over the R query
+// slots -- the int8 filter: a streaming kernel that files its own hits (scan_redo_i8.hpp); the fp16 form: the main
+// scan's kernel (workgroups of a query tile no failing query took leave at once) and the logs' gather --, one select
 // launch that writes the failing queries' output rows.  No host wait: the counts are read on the device.
 int SearchPass::run_redo(bool use_i8f) {
 	const RedoWs ws(redo_slots, h->dim, cap);
@@ -2575,57 +2576,52 @@ int SearchPass::run_redo(bool use_i8f) {
 	}
 	hipLaunchKernelGGL(redo_compact_kernel, dim3(R / (kBlock / 64)), dim3(kBlock), 0, st, cp);
 
-	// the scan: one round of the resident workgroups per query tile (a batch inside the target fills one tile);
-	// its hit logs are the main scan's, which the main gather has read by now
-	const uint32_t nt = (uint32_t)((h->n + kF16TB - 1) / kF16TB);
-	const uint32_t nqt = R / kF16TQ;
-	const uint32_t wg_per_cu = use_i8f ? (uint32_t)kGemmI8F.wg_per_cu_w : (uint32_t)gvf->wg_per_cu;
-	uint32_t chunks = pick_row_chunks(nt, 1, wg_per_cu * (uint32_t)cus, 4.0, 8, 2048, 0, nullptr);
-	chunks = std::min<uint32_t>(chunks, (uint32_t)(h->log_cnt_n / (4 * (size_t)nqt)));
-	if (chunks == 0 || !h->d_log)
-		return h->fail(EXPANN_ERR_HIP, "redo pass: the main scan left no hit logs");  // (both main scans allocate them)
-	const uint32_t tpb = (nt + chunks - 1) / chunks;
-	chunks = (nt + tpb - 1) / tpb;
-	const uint32_t n_logs = chunks * nqt * 4;
-	const uint32_t log_cap = (uint32_t)std::min<size_t>(1u << 16, h->log_bytes / ((size_t)n_logs * 16));
-	GatherLogParams gp{};
-	gp.log = h->d_log.as<const uint4>();
-	gp.log_cnt = h->d_log_cnt.as<const uint32_t>();
-	gp.log_cap = log_cap;
-	gp.n_chunks = chunks;
-	gp.n_qtiles = nqt;
-	gp.m = R;
-	gp.cand_cnt = cp.r_cnt;
-	gp.cand = reinterpret_cast<uint64_t*>(b + ws.cand);
-	gp.cap = cap;
-	gp.live_q = word;
+	uint32_t* const r_cnt = cp.r_cnt;
+	uint64_t* const r_cand = reinterpret_cast<uint64_t*>(b + ws.cand);
 	if (use_i8f) {
-		GemmI8wParams wp{};
-		wp.q.base = h->d_base_i8f;
-		wp.q.bp = h->d_bp_i8f;
-		wp.q.n_rows = (uint32_t)h->n;
-		wp.q.n_tiles_sel = nt;
-		wp.q.tile_stride = 1;
-		wp.q.tile_run = 1;
-		wp.q.tiles_per_block = tpb;
-		wp.q.n_qtiles = nqt;
-		wp.q.queries = cp.rq8;
-		wp.q.thp = cp.r_thp;
-		wp.q.m = R;
-		wp.q.cand_cnt = gp.cand_cnt;
-		wp.q.cand = gp.cand;
-		wp.q.cap = cap;
-		wp.q.live_q = word;
-		wp.log = h->d_log.as<uint4>();
-		wp.log_cnt = h->d_log_cnt;
-		wp.log_cap = log_cap;
-		wp.lost = h->d_overflow;
-		hipLaunchKernelGGL(kGemmI8FRedo, dim3(chunks * nqt), dim3((uint32_t)kGemmI8F.threads_w), kGemmI8F.lds_w, st, wp);
-		gp.i_thp = cp.r_thp;
-		gp.i_bias = h->d_bp_i8f;
-		gp.i_rw = h->d_rw_i8f;
-		gp.i_mode = 3;
+		// the int8 filter's scan (scan_redo_i8.hpp): a streaming read of the copy that files its own hits.  A static
+		// grid; every wave owns one contiguous range of 16-row columns, cut here from the wave count
+		RedoStreamParams rp{};
+		rp.base = h->d_base_i8f;
+		rp.bp = h->d_bp_i8f;
+		rp.n_rows = (uint32_t)h->n;
+		rp.n_cols = (uint32_t)((h->n + kF16TB - 1) / kF16TB) * (kF16TB / 16);  // (the copy is padded to whole 64-row tiles)
+		const uint32_t n_waves = (uint32_t)cus * kRedoStreamWavesPerCu;
+		rp.cols_per_wave = (rp.n_cols + n_waves - 1) / n_waves;
+		rp.cols_per_wave = (rp.cols_per_wave + kRedoStreamU - 1) / kRedoStreamU * kRedoStreamU;  // (whole pipeline stages)
+		rp.queries = cp.rq8;
+		rp.thp = cp.r_thp;
+		rp.n_slots = R;
+		rp.live_q = word;
+		rp.cand_cnt = r_cnt;
+		rp.cand = r_cand;
+		rp.cap = cap;
+		hipLaunchKernelGGL(redo_stream_i8_kernel, dim3(n_waves / kRedoStreamWaves), dim3(kRedoStreamThreads), 0, st, rp);
 	} else {
+		// the fp16 form: the same scan kernel over R query slots, one round of the resident workgroups per query tile
+		// (a batch inside the target fills one tile); its hit logs are the main scan's, which the main gather has
+		// read by now
+		const uint32_t nt = (uint32_t)((h->n + kF16TB - 1) / kF16TB);
+		const uint32_t nqt = R / kF16TQ;
+		uint32_t chunks = pick_row_chunks(nt, 1, (uint32_t)gvf->wg_per_cu * (uint32_t)cus, 4.0, 8, 2048, 0, nullptr);
+		chunks = std::min<uint32_t>(chunks, (uint32_t)(h->log_cnt_n / (4 * (size_t)nqt)));
+		if (chunks == 0 || !h->d_log)
+			return h->fail(EXPANN_ERR_HIP, "redo pass: the main scan left no hit logs");  // (the main scan allocates them)
+		const uint32_t tpb = (nt + chunks - 1) / chunks;
+		chunks = (nt + tpb - 1) / tpb;
+		const uint32_t n_logs = chunks * nqt * 4;
+		const uint32_t log_cap = (uint32_t)std::min<size_t>(1u << 16, h->log_bytes / ((size_t)n_logs * 16));
+		GatherLogParams gp{};
+		gp.log = h->d_log.as<const uint4>();
+		gp.log_cnt = h->d_log_cnt.as<const uint32_t>();
+		gp.log_cap = log_cap;
+		gp.n_chunks = chunks;
+		gp.n_qtiles = nqt;
+		gp.m = R;
+		gp.cand_cnt = r_cnt;
+		gp.cand = r_cand;
+		gp.cap = cap;
+		gp.live_q = word;
 		GemmF16Params fp{};
 		fp.base_f16 = h->d_base_f16;
 		fp.bnorm = h->bnorm_f16();
@@ -2651,17 +2647,17 @@ int SearchPass::run_redo(bool use_i8f) {
 		hipLaunchKernelGGL(gvf->scan_redo, dim3(chunks * nqt), dim3((uint32_t)gvf->threads), gvf->lds, st, fp);
 		gp.theta = cp.r_theta;
 		gp.key_mul = fp.two_inv_s2;
+		const uint32_t want = std::max<uint32_t>(1, (1024 + nqt * 4 - 1) / (nqt * 4));
+		gp.chunks_per_block = std::max<uint32_t>(1, (chunks + want - 1) / want);
+		gp.n_groups = (chunks + gp.chunks_per_block - 1) / gp.chunks_per_block;
+		hipLaunchKernelGGL(gather_logs_kernel, dim3(nqt * 4 * gp.n_groups), dim3(kBlock), 0, st, gp);
 	}
-	const uint32_t want = std::max<uint32_t>(1, (1024 + nqt * 4 - 1) / (nqt * 4));
-	gp.chunks_per_block = std::max<uint32_t>(1, (chunks + want - 1) / want);
-	gp.n_groups = (chunks + gp.chunks_per_block - 1) / gp.chunks_per_block;
-	hipLaunchKernelGGL(gather_logs_kernel, dim3(nqt * 4 * gp.n_groups), dim3(kBlock), 0, st, gp);
 
 	// the select of the R slots in one launch: wave 0 of a slot's workgroup orders a list of <= 2048 keys, the
 	// whole workgroup a longer one; no check (these lists come from thresholds that are proven bounds)
 	SelectParams sel{};
-	sel.cand = gp.cand;
-	sel.cand_cnt = gp.cand_cnt;
+	sel.cand = r_cand;
+	sel.cand_cnt = r_cnt;
 	sel.cap = cap;
 	sel.k = (uint32_t)k;
 	sel.id_offset = h->id_offset;
@@ -3036,8 +3032,6 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 			needs.push_back({(const void*)v.scan_w, v.lds_w, "scan_gemm_i8w_kernel"});
 			needs.push_back({(const void*)v.sample_w, v.lds_w, "scan_gemm_i8w_kernel"});
 		}
-	if (dim == kGemmI8F.d)
-		needs.push_back({(const void*)kGemmI8FRedo, kGemmI8F.lds_w, "scan_gemm_i8w_kernel, redo instance"});
 	if (any_dim_i8(dim, int_mode))
 		for (const auto& v : kGemmI8KL)
 			if (v.mode == int_mode) {

@@ -425,13 +425,14 @@ struct GatherLogParams {
 	// had it in a register), the key is kappa = bp - acc (units of 2 s^2), re-scored exactly by the select; -inf for a
 	// row whose bp sits at a clamp limit -- a clamped row always does, and an unclamped row that lands exactly on a
 	// limit is merely always re-scored.  No read of i_bias / i_rw per hit (two random 4-byte gathers, 2.1 M hits a
-	// step at C2).
+	// step at C2).  redo_stream_i8_kernel (scan_redo_i8.hpp) makes the same key where it files a hit.
 	const int* i_thp;
 	const int* i_bias;
 	const int* i_qself;
 	int i_mode;
 	const float* i_rw;
-	const uint32_t* live_q;  // redo pass: as GemmF16Params::live_q (the query tiles no workgroup scanned have no logs)
+	const uint32_t* live_q;  // redo pass of the fp16 form: as GemmF16Params::live_q (the query tiles no workgroup scanned have no
+	                         // logs).  The int8 filter's redo scan files its own hits (scan_redo_i8.hpp) and has no gather
 };
 __global__ __launch_bounds__(kBlock) void gather_logs_kernel(GatherLogParams p) {
 	__shared__ uint32_t cnt[64], base[64];

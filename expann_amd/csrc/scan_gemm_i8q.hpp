@@ -44,7 +44,9 @@ struct GemmI8qParams {
 	int* sample_out;         // SAMPLE: [(q * n_chunks + chunk) * 32 + class] max g
 	uint32_t n_chunks;
 	uint32_t xcd_map;        // XCD-aware block placement, as GemmF16Params::xcd_map
-	const uint32_t* live_q;  // scan_gemm_i8w_kernel, redo pass (GemmF16Params::live_q): live query slots, or nullptr
+	const uint32_t* live_q;  // scan_gemm_i8w_kernel: live query slots (GemmF16Params::live_q), or nullptr.  No caller sets it since the
+	                         // int8 redo pass has redo_stream_i8_kernel (scan_redo_i8.hpp); the scan's test of it stays so that the
+	                         // main instances are the code they were
 	uint32_t ksteps;         // scan_gemm_kl_kernel only: 64-byte MFMA k-steps per row (= dim / 64)
 };
 

@@ -33,12 +33,9 @@ static_assert(gemm_i8w_lds_bytes<128>() * 3 <= 160 * 1024 && gemm_i8w_lds_bytes<
 // register, row class), class = row mod 32 = 16 (column & 1) + lane & 15, the two columns of equal parity
 // folded by one v_max3.  A padding row's bp is 2^30: its g never wins.  Output: q.sample_out, the layout
 // sample_tau_i8_kernel reads ([(query * n_chunks + chunk) * 32 + class]).
-// REDO (the instance the redo pass of the speculative thresholds launches, as scan_gemm_f16x_kernel's): redo_compact_kernel
-// fills the query slots in order, so of a tile's four waves only those whose 64 slots start below the live count
-// hold a query.  The others take part in the staging alone -- their share of every stage load, every wait and
-// barrier of the step -- and skip the MFMAs, the max trees, the hit test and the queue behind one wave-uniform
-// branch: with <= 64 failing queries one wave of each workgroup multiplies and the pass is the stream of the rows.
-template <int D, bool L2FORM, bool SAMPLE = false, bool REDO = false>
+// (The redo pass of the speculative thresholds does not run this kernel: the int8 filter's redo scan is
+// redo_stream_i8_kernel, scan_redo_i8.hpp -- the same fragments and start values in a streaming loop.)
+template <int D, bool L2FORM, bool SAMPLE = false>
 __global__ __launch_bounds__(kF16Threads, I8wGeom<D>::WG_PER_CU) void scan_gemm_i8w_kernel(GemmI8wParams pw) {
 	static_assert(D == 128 || D == 256, "built for d = 128, 256");
 	const GemmI8qParams& p = pw.q;
@@ -238,30 +235,9 @@ __global__ __launch_bounds__(kF16Threads, I8wGeom<D>::WG_PER_CU) void scan_gemm_
 	};
 
 	// ---- the pipeline: scan_gemm_f16x.hpp's step (ONE barrier, after tile column 1) ---------------
-	const bool idle = REDO && p.live_q && q0 >= (*p.live_q & kRedoCountMask);  // wave-uniform: no live slot in this wave
-	if (REDO && idle && lane == 0)
-		fills[wave] = 0;  // (what the live waves read when they look at the queues: before the first barrier)
 	stage(t0, 0);
 	stage(t0 + 1, 1);
 	asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");  // tiles t0, t0+1 landed
-	if (REDO && idle) {
-		// the step of a wave without a query: the barrier where the live waves have theirs (tile t+1 landed, tile
-		// t-1 released), then this wave's pieces of tile t+2 into the released buffer
-		int ibuf = 0;
-		for (uint32_t t = t0; t < t1; ++t) {
-			const int pbuf = ibuf == 0 ? NBUF - 1 : ibuf - 1;
-			asm volatile("" ::: "memory");
-			__builtin_amdgcn_s_waitcnt(0x0070);  // vmcnt(0) lgkmcnt(0)
-			__builtin_amdgcn_s_barrier();
-			asm volatile("" ::: "memory");
-			stage(t + 2, pbuf);
-			ibuf = ibuf + 1 == NBUF ? 0 : ibuf + 1;
-		}
-		if (lane == 0)
-			*my_log_cnt = 0;
-		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the re-staged tail tiles: LDS must outlive them
-		return;
-	}
 
 	i32x4 acc[4][4];
 	int buf = 0;
