@@ -19,6 +19,7 @@
 #include "filter_rows.hpp"
 #include "graph_append.hpp"
 #include "graph_build.hpp"
+#include "graph_builder_state.hpp"
 #include "graph_flat_scan.hpp"
 #include "graph_options.hpp"
 #include "graph_remove.hpp"
@@ -87,35 +88,19 @@ struct GraphDeviceSearches {
 	uint64_t pend_redo_queries = 0, pend_overflows = 0;  // what the drains since the last sync found
 };
 
-// The builder's view of the graph, resident from the handle's first append (expann_graph_adopt_build_state): the
-// fixed-stride rows of graph_build.hpp's BuildGraph, every array sized to GraphRows::cap_rows, and the scratch of a
-// batch.  BuildGraph::vec is d_vectors: the rows are not kept twice.  The CSR and d_adj0 are remade from it after
-// every append (graph_append.hpp); the upper-layer arrays have capacities of their own and are laid out again when
-// the upper vertices or the layers outgrow them.
+// The builder's view of the graph, resident from the handle's first append (expann_graph_adopt_build_state), in the
+// types of graph_builder_state.hpp: `arrays`, the fixed-stride rows of a BuildGraph sized to GraphRows::cap_rows, with
+// upper-layer capacities of their own ([L_cap][U_cap], laid out again when the upper vertices or the layers outgrow
+// them); `scratch`, a batch's; `cfg`, the parameters it was adopted with.  BuildGraph::vec is d_vectors: the rows are
+// not kept twice.  The CSR and d_adj0 are remade from it after every append and remove (graph_append.hpp).
 struct GraphBuildState {
 	bool resident = false;
-	size_t M = 0, M0 = 0, ef_construction = 0, prune_overflow = 0;
-	float ortho_factor = 0, ortho_bias = 0;
-	uint32_t bstride0 = 0, bstrideu = 0;  // row strides of the builder's arrays: M0 / M plus the slack for reverse edges
+	BuildConfig cfg;
+	BuilderArrays arrays;
+	BuildScratch scratch;
 	size_t U = 0;                         // upper-layer vertices
-	size_t U_cap = 0, L_cap = 0;          // the upper arrays hold [L_cap][U_cap] rows: row (l - 1) * U_cap + upper_idx[v]
 	size_t edge_cap = 0, off_cap = 0;     // words of d_neighbours / d_layer_off
-	size_t dirty_cap = 0, tiles_cap = 0;
-	DevPtr<uint8_t> d_level;      // [cap_rows]
-	DevPtr<int32_t> d_upper_idx;  // [cap_rows]
-	DevPtr<uint32_t> d_id0;       // [cap_rows][bstride0]
-	DevPtr<float> d_d0;
-	DevPtr<uint32_t> d_deg0;      // [cap_rows]
-	DevPtr<uint32_t> d_idu;       // [L_cap * U_cap][bstrideu]
-	DevPtr<float> d_du;
-	DevPtr<uint32_t> d_degu;      // [L_cap * U_cap]
-	// a batch's search lists, prune tasks and counters (expann_graph_build_batched makes the same per call)
-	DevPtr<md_pair> d_out;
-	DevPtr<uint32_t> d_out_cnt;
-	DevPtr<PruneTask> d_tasks;
-	DevPtr<int32_t> d_up_slot;
-	DevPtr<uint2> d_dirty;        // [dirty_cap]
-	DevPtr<uint32_t> d_build_ctr; // [8]
+	size_t tiles_cap = 0;
 	DevPtr<uint32_t> d_tile_sums; // [tiles_cap] the scan's tile sums
 	OwnedEvent ev_tables[2];      // around the last rebuild of the walk's tables
 	uint64_t tables_ns = 0, n_edges = 0;  // its device time; the edges of the CSR it made
@@ -150,12 +135,12 @@ struct GraphStats {
 	uint64_t stat_redo_queries = 0, stat_redo_overflows = 0, stat_deferred = 0, stat_distcomps = 0;
 	uint64_t stat_range = 0;  // range searches since create, from either entry point
 	double stat_redo_ms = 0;
-	// appends {calls, rows, batches, served on the device, served by the host route, capacity growths}
-	uint64_t stat_append[6] = {0, 0, 0, 0, 0, 0};
-	// removes {calls, rows, touched rows, truncated rows, served on the device, served by the host route}; the device
-	// time of the last call's touch + gather + prune
-	uint64_t stat_remove[6] = {0, 0, 0, 0, 0, 0};
-	uint64_t remove_repair_ns = 0;
+	// appends and removes (device / host: the route that served the call; reallocs: capacity growths; touched,
+	// truncated: rows).  The host route re-uploads the graph into a new handle and carries these over as arrays
+	// (expann_graph_note_host_append / _remove), in the order of the fields.
+	struct Appends { uint64_t calls = 0, rows = 0, batches = 0, device = 0, host = 0, reallocs = 0; } stat_append;
+	struct Removes { uint64_t calls = 0, rows = 0, touched = 0, truncated = 0, device = 0, host = 0; } stat_remove;
+	uint64_t remove_repair_ns = 0;  // the device time of the last remove's touch + gather + prune
 };
 
 // the handle's own stream, the host-buffer calls' events, launch plans, statistics, the last error
@@ -1472,12 +1457,12 @@ int expann_graph_get_stat(expann_graph* g, const char* name, uint64_t* out) {
 	};
 	// the append's rows (THE GRAPH APPEND RULE)
 	static const StatRow kGraphAppendStatTable[] = {
-	    {"append_calls", [](G g) { return g->stat_append[0]; }},
-	    {"append_rows", [](G g) { return g->stat_append[1]; }},
-	    {"append_batches", [](G g) { return g->stat_append[2]; }},
-	    {"append_device", [](G g) { return g->stat_append[3]; }},
-	    {"append_host", [](G g) { return g->stat_append[4]; }},
-	    {"graph_reallocs", [](G g) { return g->stat_append[5]; }},
+	    {"append_calls", [](G g) { return g->stat_append.calls; }},
+	    {"append_rows", [](G g) { return g->stat_append.rows; }},
+	    {"append_batches", [](G g) { return g->stat_append.batches; }},
+	    {"append_device", [](G g) { return g->stat_append.device; }},
+	    {"append_host", [](G g) { return g->stat_append.host; }},
+	    {"graph_reallocs", [](G g) { return g->stat_append.reallocs; }},
 	    {"capacity_rows", [](G g) { return (uint64_t)g->cap_rows; }},
 	    // the last rebuild of the walk's tables from the resident state: device time, edges of all layers
 	    {"append_tables_ns", [](G g) { return g->tables_ns; }},
@@ -1485,13 +1470,13 @@ int expann_graph_get_stat(expann_graph* g, const char* name, uint64_t* out) {
 	};
 	// the remove's rows (THE GRAPH REMOVE RULE)
 	static const StatRow kGraphRemoveStatTable[] = {
-	    {"remove_calls", [](G g) { return g->stat_remove[0]; }},
-	    {"remove_rows", [](G g) { return g->stat_remove[1]; }},
-	    {"remove_touched_rows", [](G g) { return g->stat_remove[2]; }},
+	    {"remove_calls", [](G g) { return g->stat_remove.calls; }},
+	    {"remove_rows", [](G g) { return g->stat_remove.rows; }},
+	    {"remove_touched_rows", [](G g) { return g->stat_remove.touched; }},
 	    // touched rows whose distinct candidates exceeded max(ef_construction, M0)
-	    {"remove_truncated_rows", [](G g) { return g->stat_remove[3]; }},
-	    {"remove_device", [](G g) { return g->stat_remove[4]; }},
-	    {"remove_host", [](G g) { return g->stat_remove[5]; }},
+	    {"remove_truncated_rows", [](G g) { return g->stat_remove.truncated; }},
+	    {"remove_device", [](G g) { return g->stat_remove.device; }},
+	    {"remove_host", [](G g) { return g->stat_remove.host; }},
 	    // device time of touch + gather + prune of the last call
 	    {"remove_repair_ns", [](G g) { return g->remove_repair_ns; }},
 	};
@@ -1573,9 +1558,6 @@ struct BuildVariant {
 const BuildVariant kBuild[] = {BUILD_V(64),  BUILD_V(128), BUILD_V(256), BUILD_V(512),
                                BUILD_V(768), BUILD_V(832), BUILD_V(960), BUILD_V(0)};
 #undef BUILD_V
-struct BuildFail {
-	std::string msg;
-};
 const BuildVariant* build_variant(int dim) {
 	const BuildVariant* bv = &kBuild[sizeof(kBuild) / sizeof(kBuild[0]) - 1];  // (d = 0: run-time dim)
 	for (const auto& v : kBuild)
@@ -1585,28 +1567,22 @@ const BuildVariant* build_variant(int dim) {
 }
 
 // The batch loop of THE BATCH RULE over device arrays: expann_graph_build_batched runs it over arrays it makes for
-// the call, expann_graph_append over the handle's resident builder state.  The caller fills everything down to
-// `resident`; build_batches_geometry derives the launch geometry.
+// the call, expann_graph_append over the handle's resident builder state.  build_batches fills what the two share;
+// the caller sets the rest down to `resident`, and build_batches_geometry derives the launch geometry.
 struct BuildBatches {
 	const BuildVariant* bv;
 	BuildGraph g;
+	BuildConfig cfg;
+	const BuildScratch* s;  // sized for max_batch + max_up_in_batch lists before build_run_batches
 	hipStream_t st;
 	int dim, cus;
 	const uint8_t* levels;  // host: the level of vertex v is levels[v - level_base]
 	size_t level_base;
 	size_t b0, n;           // vertices [b0, n) are inserted; b0 ends behind the last batch that is in
 	uint32_t max_layer, starting_vertex;  // in and out
-	size_t max_batch, ef, prune_overflow;
-	float ortho_factor, ortho_bias;
+	size_t max_batch;
 	uint32_t* vis_bits;     // [slots][vis_words], all zero between searches
 	uint32_t vis_words;
-	md_pair* out;           // [max_batch + max_up_in_batch][ef]
-	uint32_t* out_cnt;
-	PruneTask* tasks;
-	int32_t* up_slot;       // [max_batch]
-	uint2* dirty;
-	size_t dirty_cap;
-	uint32_t* ctr;          // [8], zero: [0] n_dirty, [1] dropped, [2] search overflow, [3] n_tasks
 	// the resident form: the search's overflow counter is read before the batch's prune and reverse launches, so a
 	// batch that overflows leaves the graph as it was; that wait is the batch's only one
 	bool resident;
@@ -1617,14 +1593,19 @@ struct BuildBatches {
 	// out
 	uint64_t n_batches = 0, n_dirty_total = 0;
 };
-extern "C++" {  // (templates: this namespace sits inside the C ABI's linkage block)
+extern "C++" {  // (templates, a struct returned: this namespace sits inside the C ABI's linkage block)
+BuildBatches build_batches(const BuildGraph& view, const BuildScratch& scratch, const BuildConfig& cfg, hipStream_t st, int dim,
+                           int device) {
+	return BuildBatches{build_variant(dim), view, cfg, &scratch, st, dim, num_cus(device)};  // (the rest zero)
+}
 template <typename F> int build_batches_geometry(F* fh, BuildBatches& r, bool upper_layers) {
+	const size_t ef = r.cfg.ef_construction;
 	if (r.max_batch == 0)
 		r.max_batch = 32768;
 	// search: one wave per new vertex; LDS = nearest heap + candidates heap + a hop's neighbour list
-	r.list_cap = (uint32_t)std::max<size_t>(r.g.stride0, std::max<size_t>(r.g.strideu, r.ef));
+	r.list_cap = (uint32_t)std::max<size_t>(r.g.stride0, std::max<size_t>(r.g.strideu, ef));
 	r.cand_cap = 8192;
-	r.search_lds = sizeof(md_pair) * (r.ef + 1 + r.cand_cap + 1) + (sizeof(uint32_t) + sizeof(float)) * r.list_cap +
+	r.search_lds = sizeof(md_pair) * (ef + 1 + r.cand_cap + 1) + (sizeof(uint32_t) + sizeof(float)) * r.list_cap +
 	               8 * sizeof(uint32_t) +
 	               (r.bv->d == 0 ? (size_t)r.dim * sizeof(float) : 0);  // (run-time dim: the new row in LDS)
 	// the prune kernel of the run-time-dim instance keeps the kept edge's row in dynamic LDS
@@ -1637,8 +1618,9 @@ template <typename F> int build_batches_geometry(F* fh, BuildBatches& r, bool up
 template <typename F> int build_run_batches(F* fh, BuildBatches& r) {
 	const BuildVariant* bv = r.bv;
 	const BuildGraph& g = r.g;
+	const BuildScratch& s = *r.s;
 	hipStream_t st = r.st;
-	uint32_t* ctr = r.ctr;
+	uint32_t* ctr = s.ctr;
 	auto level_of = [&](size_t v) { return r.levels[v - r.level_base]; };
 	const char* overflow = "construction search: candidates queue overflowed its LDS capacity";
 	std::vector<PruneTask> tasks;
@@ -1672,8 +1654,8 @@ template <typename F> int build_run_batches(F* fh, BuildBatches& r) {
 		if (n_up > r.max_up_in_batch)
 			return fh->fail(EXPANN_ERR_UNSUPPORTED, "more upper-layer vertices in a batch than provisioned");
 		const uint32_t n_tasks = (uint32_t)tasks.size();
-		HIP_TRY(fh, hipMemcpyAsync(r.tasks, tasks.data(), sizeof(PruneTask) * n_tasks, hipMemcpyHostToDevice, st));
-		HIP_TRY(fh, hipMemcpyAsync(r.up_slot, up_slot.data(), 4 * B, hipMemcpyHostToDevice, st));
+		HIP_TRY(fh, hipMemcpyAsync(s.tasks, tasks.data(), sizeof(PruneTask) * n_tasks, hipMemcpyHostToDevice, st));
+		HIP_TRY(fh, hipMemcpyAsync(s.up_slot, up_slot.data(), 4 * B, hipMemcpyHostToDevice, st));
 		HIP_TRY(fh, hipMemcpyAsync(ctr + 3, &n_tasks, 4, hipMemcpyHostToDevice, st));
 		HIP_TRY(fh, hipMemsetAsync(ctr, 0, 4, st));
 		BuildSearchParams sp{};
@@ -1682,14 +1664,14 @@ template <typename F> int build_run_batches(F* fh, BuildBatches& r) {
 		sp.b1 = (uint32_t)b1;
 		sp.max_layer = r.max_layer;
 		sp.starting_vertex = r.starting_vertex;
-		sp.ef = (uint32_t)r.ef;
+		sp.ef = (uint32_t)r.cfg.ef_construction;
 		sp.cand_cap = r.cand_cap;
 		sp.list_cap = r.list_cap;
 		sp.vis_bits = r.vis_bits;
 		sp.vis_words = r.vis_words;
-		sp.up_slot = r.up_slot;
-		sp.out = r.out;
-		sp.out_cnt = r.out_cnt;
+		sp.up_slot = s.up_slot;
+		sp.out = s.out;
+		sp.out_cnt = s.out_cnt;
 		sp.error = ctr + 2;
 		sp.dim = (uint32_t)r.dim;
 		hipLaunchKernelGGL(bv->search, dim3((uint32_t)std::min<uint64_t>(B, r.slots)), dim3(64), r.search_lds, st, sp);
@@ -1703,32 +1685,32 @@ template <typename F> int build_run_batches(F* fh, BuildBatches& r) {
 		}
 		BuildPruneParams pp{};
 		pp.g = g;
-		pp.tasks = r.tasks;
+		pp.tasks = s.tasks;
 		pp.n_tasks = ctr + 3;
-		pp.lists = r.out;
-		pp.list_cnt = r.out_cnt;
-		pp.ef = (uint32_t)r.ef;
-		pp.ortho_factor = r.ortho_factor;
-		pp.ortho_bias = r.ortho_bias;
-		pp.prune_overflow = (uint32_t)r.prune_overflow;
+		pp.lists = s.out;
+		pp.list_cnt = s.out_cnt;
+		pp.ef = (uint32_t)r.cfg.ef_construction;
+		pp.ortho_factor = r.cfg.ortho_factor;
+		pp.ortho_bias = r.cfg.ortho_bias;
+		pp.prune_overflow = (uint32_t)r.cfg.prune_overflow;
 		pp.dim = (uint32_t)r.dim;
 		hipLaunchKernelGGL(bv->prune, dim3(std::min<uint32_t>(n_tasks, (uint32_t)r.cus * 16)), dim3(kPruneThreads), r.prune_lds, st, pp);
 		BuildReverseParams rp{};
 		rp.g = g;
-		rp.tasks = r.tasks;
+		rp.tasks = s.tasks;
 		rp.n_tasks = n_tasks;
-		rp.dirty = r.dirty;
+		rp.dirty = s.dirty;
 		rp.n_dirty = ctr;
-		rp.dirty_cap = (uint32_t)r.dirty_cap;
+		rp.dirty_cap = (uint32_t)s.dirty_cap;
 		rp.dropped = ctr + 1;
 		hipLaunchKernelGGL(build_reverse_kernel, dim3((n_tasks + kBlock / 64 - 1) / (kBlock / 64)), dim3(kBlock), 0, st, rp);
 		// the rows that outgrew their cap: clamp to the slack, prune (grid-stride over the dirty list)
-		hipLaunchKernelGGL(build_clamp_kernel, dim3((uint32_t)((r.dirty_cap + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, g,
-		                   (const uint2*)r.dirty, (const uint32_t*)ctr);
+		hipLaunchKernelGGL(build_clamp_kernel, dim3((uint32_t)((s.dirty_cap + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, g,
+		                   (const uint2*)s.dirty.get(), (const uint32_t*)ctr);
 		BuildPruneParams dp = pp;
 		dp.tasks = nullptr;
 		dp.n_tasks = ctr;
-		dp.dirty = r.dirty;
+		dp.dirty = s.dirty;
 		hipLaunchKernelGGL(bv->prune, dim3((uint32_t)r.cus * 16), dim3(kPruneThreads), r.prune_lds, st, dp);
 		HIP_TRY(fh, hipGetLastError());
 		if (!r.resident) {
@@ -1759,7 +1741,6 @@ int expann_graph_build_batched(int dim, int device, const float* vectors, size_t
                                uint32_t* idsu, float* du, uint32_t* degu, size_t strideu, uint64_t* stats) {
 	if (int rc = graph_dim_error("expann_graph_build_batched", dim))
 		return rc;
-	const BuildVariant* bv = build_variant(dim);
 	if (!vectors || !levels || !max_layer_io || !starting_vertex_io || !ids0 || !d0 || !deg0 || !upper_idx ||
 	    n == 0 || n_built == 0 || n_built > n || n >= (1ull << 32) - 64 || M < 2 || M0 < M || stride0 < M0 ||
 	    (n_upper_layers && (!idsu || !du || !degu || strideu < M)) || ef_construction == 0 ||
@@ -1790,104 +1771,41 @@ int expann_graph_build_batched(int dim, int device, const float* vectors, size_t
 	} sg;
 	HIP_TRY(fh, hipStreamCreate(&sg.s));
 	hipStream_t st = sg.s;
-	DevBuf b_vec, b_lvl, b_up, b_id0, b_d0, b_deg0, b_idu, b_du, b_degu, b_vis, b_out, b_outc, b_tasks, b_upslot,
-	    b_dirty, b_ctr;
-	const size_t n_up_rows = U * n_upper_layers;
+	// the builder's arrays in the host's layout ([layer][U]: U_cap = U, L_cap = n_upper_layers), for this call
+	DevBuf b_vec, b_vis;
+	BuilderArrays arrays;
+	BuildScratch scratch;
 	HIP_TRY(fh, b_vec.alloc(n * (size_t)dim * 4));
-	HIP_TRY(fh, b_lvl.alloc(n));
-	HIP_TRY(fh, b_up.alloc(n * 4));
-	HIP_TRY(fh, b_id0.alloc(n * stride0 * 4));
-	HIP_TRY(fh, b_d0.alloc(n * stride0 * 4));
-	HIP_TRY(fh, b_deg0.alloc(n * 4));
-	HIP_TRY(fh, b_idu.alloc(std::max<size_t>(1, n_up_rows * strideu) * 4));
-	HIP_TRY(fh, b_du.alloc(std::max<size_t>(1, n_up_rows * strideu) * 4));
-	HIP_TRY(fh, b_degu.alloc(std::max<size_t>(1, n_up_rows) * 4));
-	HIP_TRY(fh, hipMemcpy(b_vec.p, vectors, n * (size_t)dim * 4, hipMemcpyHostToDevice));
-	HIP_TRY(fh, hipMemcpy(b_lvl.p, levels, n, hipMemcpyHostToDevice));
-	HIP_TRY(fh, hipMemcpy(b_up.p, upper_idx, n * 4, hipMemcpyHostToDevice));
-	HIP_TRY(fh, hipMemcpy(b_id0.p, ids0, n * stride0 * 4, hipMemcpyHostToDevice));
-	HIP_TRY(fh, hipMemcpy(b_d0.p, d0, n * stride0 * 4, hipMemcpyHostToDevice));
-	HIP_TRY(fh, hipMemcpy(b_deg0.p, deg0, n * 4, hipMemcpyHostToDevice));
-	if (n_up_rows) {
-		HIP_TRY(fh, hipMemcpy(b_idu.p, idsu, n_up_rows * strideu * 4, hipMemcpyHostToDevice));
-		HIP_TRY(fh, hipMemcpy(b_du.p, du, n_up_rows * strideu * 4, hipMemcpyHostToDevice));
-		HIP_TRY(fh, hipMemcpy(b_degu.p, degu, n_up_rows * 4, hipMemcpyHostToDevice));
-	}
-	BuildBatches r{};
-	r.bv = bv;
-	r.st = st;
-	r.dim = dim;
-	r.cus = num_cus(device);
+	HIP_TRY(fh, hipMemcpyAsync(b_vec.p, vectors, n * (size_t)dim * 4, hipMemcpyHostToDevice, st));
+	HIP_TRY(fh, arrays.alloc(n, (uint32_t)stride0, (uint32_t)strideu, U, n_upper_layers, st));
+	HIP_TRY(fh, arrays.copy_host<true>(n, levels, upper_idx, ids0, d0, deg0, U, n_upper_layers, U, idsu, du, degu, st));
+	BuildBatches r = build_batches(arrays.view(b_vec.as<float>(), n, M0, M), scratch,
+	                               BuildConfig{M, M0, ef_construction, prune_overflow, ortho_factor, ortho_bias}, st, dim, device);
 	r.levels = levels;
-	r.level_base = 0;
 	r.b0 = n_built;
 	r.n = n;
 	r.max_layer = *max_layer_io;
 	r.starting_vertex = *starting_vertex_io;
 	r.max_batch = max_batch;
-	r.ef = ef_construction;
-	r.prune_overflow = prune_overflow;
-	r.ortho_factor = ortho_factor;
-	r.ortho_bias = ortho_bias;
-	r.resident = false;
-	BuildGraph& g = r.g;
-	g.vec = b_vec.as<float>();
-	g.n = (uint32_t)n;
-	g.level = b_lvl.as<uint8_t>();
-	g.upper_idx = b_up.as<int32_t>();
-	g.id0 = b_id0.as<uint32_t>();
-	g.d0 = b_d0.as<float>();
-	g.deg0 = b_deg0.as<uint32_t>();
-	g.cap0 = (uint32_t)M0;
-	g.stride0 = (uint32_t)stride0;
-	g.idu = b_idu.as<uint32_t>();
-	g.du = b_du.as<float>();
-	g.degu = b_degu.as<uint32_t>();
-	g.capu = (uint32_t)M;
-	g.strideu = (uint32_t)strideu;
-	g.U = (uint32_t)U;
 	if (int rc = build_batches_geometry(fh, r, n_upper_layers != 0))
 		return rc;
 	// one visited bitset per resident workgroup, all zero between searches (graph_search.hpp)
 	r.vis_words = (uint32_t)((n + 8191) / 8192 * 256);
 	HIP_TRY(fh, b_vis.alloc(r.slots * r.vis_words * 4));
-	HIP_TRY(fh, hipMemset(b_vis.p, 0, r.slots * r.vis_words * 4));
-	HIP_TRY(fh, b_out.alloc((r.max_batch + r.max_up_in_batch) * ef_construction * sizeof(md_pair)));
-	HIP_TRY(fh, b_outc.alloc((r.max_batch + r.max_up_in_batch) * 4));
-	HIP_TRY(fh, b_tasks.alloc((r.max_batch + r.max_up_in_batch) * sizeof(PruneTask)));
-	HIP_TRY(fh, b_upslot.alloc(r.max_batch * 4));
-	r.dirty_cap = n + n_up_rows + 1;
-	HIP_TRY(fh, b_dirty.alloc(r.dirty_cap * sizeof(uint2)));
-	HIP_TRY(fh, b_ctr.alloc(8 * 4));  // [0] n_dirty, [1] dropped, [2] search overflow, [3] n_tasks
-	HIP_TRY(fh, hipMemset(b_ctr.p, 0, 8 * 4));
-	uint32_t* ctr = b_ctr.as<uint32_t>();
+	HIP_TRY(fh, hipMemsetAsync(b_vis.p, 0, r.slots * r.vis_words * 4, st));
 	r.vis_bits = b_vis.as<uint32_t>();
-	r.out = b_out.as<md_pair>();
-	r.out_cnt = b_outc.as<uint32_t>();
-	r.tasks = b_tasks.as<PruneTask>();
-	r.up_slot = b_upslot.as<int32_t>();
-	r.dirty = b_dirty.as<uint2>();
-	r.ctr = ctr;
+	HIP_TRY(fh, scratch.alloc(r.max_batch + r.max_up_in_batch, r.max_batch, ef_construction, n + arrays.upper_rows() + 1, st));
 	if (int rc = build_run_batches(fh, r))
 		return rc;
-	const uint32_t max_layer = r.max_layer, starting_vertex = r.starting_vertex;
-	const uint64_t n_batches = r.n_batches, n_dirty_total = r.n_dirty_total;
-	HIP_TRY(fh, hipMemcpy(ids0, b_id0.p, n * stride0 * 4, hipMemcpyDeviceToHost));
-	HIP_TRY(fh, hipMemcpy(d0, b_d0.p, n * stride0 * 4, hipMemcpyDeviceToHost));
-	HIP_TRY(fh, hipMemcpy(deg0, b_deg0.p, n * 4, hipMemcpyDeviceToHost));
-	if (n_up_rows) {
-		HIP_TRY(fh, hipMemcpy(idsu, b_idu.p, n_up_rows * strideu * 4, hipMemcpyDeviceToHost));
-		HIP_TRY(fh, hipMemcpy(du, b_du.p, n_up_rows * strideu * 4, hipMemcpyDeviceToHost));
-		HIP_TRY(fh, hipMemcpy(degu, b_degu.p, n_up_rows * 4, hipMemcpyDeviceToHost));
-	}
+	HIP_TRY(fh, arrays.copy_host<false>(n, (uint8_t*)nullptr, (int32_t*)nullptr, ids0, d0, deg0, U, n_upper_layers, U, idsu, du, degu, st));
 	uint32_t h_ctr[4];
-	HIP_TRY(fh, hipMemcpy(h_ctr, ctr, sizeof(h_ctr), hipMemcpyDeviceToHost));
-	*max_layer_io = max_layer;
-	*starting_vertex_io = starting_vertex;
+	HIP_TRY(fh, hipMemcpy(h_ctr, scratch.ctr, sizeof(h_ctr), hipMemcpyDeviceToHost));
+	*max_layer_io = r.max_layer;
+	*starting_vertex_io = r.starting_vertex;
 	if (stats) {
-		stats[0] = n_batches;
+		stats[0] = r.n_batches;
 		stats[1] = h_ctr[1];
-		stats[2] = n_dirty_total;
+		stats[2] = r.n_dirty_total;
 		stats[3] = h_ctr[2];
 	}
 	return EXPANN_OK;
@@ -1897,44 +1815,13 @@ int expann_graph_build_batched(int dim, int device, const float* vectors, size_t
 
 // ---- appends to a built graph: the builder's state resident in the handle (THE GRAPH APPEND RULE) ----------
 namespace {
-// `a` becomes an array of cap_bytes that starts with its first keep_bytes (zero behind them when `zero`); the old
-// block goes once the copy is done
-template <typename T> int graph_regrow(expann_graph* g, DevPtr<T>& a, size_t keep_bytes, size_t cap_bytes, bool zero = false) {
-	DevPtr<T> b;
-	HIP_TRY(g, hipMalloc(&b, std::max<size_t>(cap_bytes, 1)));
-	if (zero)
-		HIP_TRY(g, hipMemsetAsync(b, 0, cap_bytes, g->stream));
-	if (keep_bytes)
-		HIP_TRY(g, hipMemcpyAsync(b, a, keep_bytes, hipMemcpyDeviceToDevice, g->stream));
-	HIP_TRY(g, hipStreamSynchronize(g->stream));
-	a = std::move(b);
-	return EXPANN_OK;
-}
-
-BuildGraph graph_build_view(const expann_graph* g) {
-	BuildGraph b{};
-	b.vec = g->d_vectors.as<const float>();
-	b.n = (uint32_t)g->n;
-	b.level = g->d_level;
-	b.upper_idx = g->d_upper_idx;
-	b.id0 = g->d_id0;
-	b.d0 = g->d_d0;
-	b.deg0 = g->d_deg0;
-	b.cap0 = (uint32_t)g->M0;
-	b.stride0 = g->bstride0;
-	b.idu = g->d_idu;
-	b.du = g->d_du;
-	b.degu = g->d_degu;
-	b.capu = (uint32_t)g->M;
-	b.strideu = g->bstrideu;
-	b.U = (uint32_t)g->U_cap;
-	return b;
-}
+BuildGraph graph_build_view(const expann_graph* g) { return g->arrays.view(g->d_vectors.as<const float>(), g->n, g->cfg.M0, g->cfg.M); }
 
 // what is sized by (cap_rows, U_cap, L_cap) and holds nothing between two rebuilds of the tables: the CSR, the dirty
 // list, the scan's tile sums.  The CSR's CONTENT is lost when it grows: the caller rebuilds the tables.
 int graph_size_derived(expann_graph* g) {
-	const size_t off = (g->L_cap + 1) * (g->cap_rows + 1), edges = g->cap_rows * g->M0 + g->L_cap * g->U_cap * g->M;
+	const size_t up_rows = g->arrays.upper_rows(), L_cap = g->arrays.L_cap;
+	const size_t off = (L_cap + 1) * (g->cap_rows + 1), edges = g->cap_rows * g->cfg.M0 + up_rows * g->cfg.M;
 	if (off >= (1ull << 32) || edges >= (1ull << 32))
 		return g->fail(EXPANN_ERR_UNSUPPORTED, "the capacity would take more than 2^32 edges or offsets");
 	if (off > g->off_cap) {
@@ -1950,18 +1837,13 @@ int graph_size_derived(expann_graph* g) {
 		HIP_TRY(g, hipMalloc(&g->d_neighbours, std::max<size_t>(edges, 1) * sizeof(uint32_t)));
 		g->edge_cap = edges;
 	}
-	const size_t dirty = g->cap_rows + g->L_cap * g->U_cap + 1;
-	if (dirty > g->dirty_cap) {
-		g->d_dirty.reset();
-		HIP_TRY(g, hipMalloc(&g->d_dirty, dirty * sizeof(uint2)));
-		g->dirty_cap = dirty;
-	}
+	HIP_TRY(g, g->scratch.size_dirty(g->cap_rows + up_rows + 1));
 	return EXPANN_OK;
 }
 
 // d_adj0 and the CSR remade from the resident state (graph_append.hpp) on the handle's stream, and waited for
 int graph_rebuild_tables(expann_graph* g) {
-	if (g->n > g->cap_rows || g->n_layers == 0 || g->n_layers > g->L_cap + 1 || g->stride0 % 4 != 0 || g->stride0 < g->M0)
+	if (g->n > g->cap_rows || g->n_layers == 0 || g->n_layers > g->arrays.L_cap + 1 || g->stride0 % 4 != 0 || g->stride0 < g->cfg.M0)
 		return g->fail(EXPANN_ERR_INVALID_ARG, "graph append: the builder state does not fit its capacity");
 	AppendTables t{};
 	t.g = graph_build_view(g);
@@ -2005,59 +1887,27 @@ int graph_grow_rows(expann_graph* g, size_t rows) {
 	if (g->vis_words == 0 || rows > (8u << 20))
 		return g->fail(EXPANN_ERR_UNSUPPORTED, "a graph handle grows up to 8 Mi rows (visited bitsets)");
 	const size_t n = g->n, row_bytes = (size_t)g->dim * (g->rows_f16 ? 2 : 4);
-	if (int rc = graph_regrow(g, g->d_vectors, n * row_bytes, rows * row_bytes))
-		return rc;
-	if (int rc = graph_regrow(g, g->d_adj0, n * g->stride0 * sizeof(uint32_t), rows * g->stride0 * sizeof(uint32_t)))
-		return rc;
+	hipStream_t st = g->stream;
+	HIP_TRY(g, dev_regrow(g->d_vectors, n * row_bytes, rows * row_bytes, st));
+	HIP_TRY(g, dev_regrow(g->d_adj0, n * g->stride0 * sizeof(uint32_t), rows * g->stride0 * sizeof(uint32_t), st));
 	const uint32_t words = (uint32_t)((rows + 8191) / 8192 * 256);
 	if (words != g->vis_words) {  // (all zero between searches: nothing to keep)
-		if (int rc = graph_regrow(g, g->d_visited, 0, (size_t)g->slots * words * sizeof(uint32_t), true))
-			return rc;
+		HIP_TRY(g, dev_regrow(g->d_visited, 0, (size_t)g->slots * words * sizeof(uint32_t), st, true));
 		g->vis_words = words;
 	}
-	if (g->resident) {
-		if (int rc = graph_regrow(g, g->d_level, n, rows))
-			return rc;
-		if (int rc = graph_regrow(g, g->d_upper_idx, n * 4, rows * 4))
-			return rc;
-		if (int rc = graph_regrow(g, g->d_id0, n * g->bstride0 * 4, rows * g->bstride0 * 4))
-			return rc;
-		if (int rc = graph_regrow(g, g->d_d0, n * g->bstride0 * 4, rows * g->bstride0 * 4))
-			return rc;
-		if (int rc = graph_regrow(g, g->d_deg0, n * 4, rows * 4, true))
-			return rc;
-	}
+	if (g->resident)
+		HIP_TRY(g, g->arrays.grow_rows(n, rows, st));
 	g->cap_rows = rows;
 	return g->resident ? graph_size_derived(g) : EXPANN_OK;
 }
 
 // the upper-layer arrays laid out again for at least U_need vertices and L_need layers
 int graph_grow_upper(expann_graph* g, size_t U_need, size_t L_need) {
-	if (U_need <= g->U_cap && L_need <= g->L_cap)
+	const BuilderArrays& a = g->arrays;
+	if (U_need <= a.U_cap && L_need <= a.L_cap)
 		return EXPANN_OK;
-	const size_t U_cap = U_need > g->U_cap ? std::max(U_need, g->U_cap + g->U_cap / 2) + 64 : g->U_cap;
-	const size_t L_cap = L_need > g->L_cap ? L_need + 1 : g->L_cap;
-	const size_t rows = U_cap * L_cap, su = g->bstrideu;
-	DevPtr<uint32_t> idu, degu;
-	DevPtr<float> du;
-	HIP_TRY(g, hipMalloc(&idu, std::max<size_t>(rows * su, 1) * 4));
-	HIP_TRY(g, hipMalloc(&du, std::max<size_t>(rows * su, 1) * 4));
-	HIP_TRY(g, hipMalloc(&degu, std::max<size_t>(rows, 1) * 4));
-	HIP_TRY(g, hipMemsetAsync(degu, 0, rows * 4, g->stream));
-	for (size_t l = 0; l < g->L_cap && g->U; ++l) {
-		HIP_TRY(g, hipMemcpyAsync(idu.get() + l * U_cap * su, g->d_idu.get() + l * g->U_cap * su, g->U * su * 4,
-		                          hipMemcpyDeviceToDevice, g->stream));
-		HIP_TRY(g, hipMemcpyAsync(du.get() + l * U_cap * su, g->d_du.get() + l * g->U_cap * su, g->U * su * 4,
-		                          hipMemcpyDeviceToDevice, g->stream));
-		HIP_TRY(g, hipMemcpyAsync(degu.get() + l * U_cap, g->d_degu.get() + l * g->U_cap, g->U * 4, hipMemcpyDeviceToDevice,
-		                          g->stream));
-	}
-	HIP_TRY(g, hipStreamSynchronize(g->stream));
-	g->d_idu = std::move(idu);
-	g->d_du = std::move(du);
-	g->d_degu = std::move(degu);
-	g->U_cap = U_cap;
-	g->L_cap = L_cap;
+	const size_t U_cap = U_need > a.U_cap ? std::max(U_need, a.U_cap + a.U_cap / 2) + 64 : a.U_cap;
+	HIP_TRY(g, g->arrays.relayout_upper(g->U, U_cap, L_need > a.L_cap ? L_need + 1 : a.L_cap, g->stream));
 	return graph_size_derived(g);
 }
 }  // namespace
@@ -2123,45 +1973,20 @@ int expann_graph_adopt_build_state(expann_graph* g, size_t M, size_t M0, size_t 
 	HIP_TRY(g, hipSetDevice(g->device));
 	HIP_TRY(g, graph_wait_outstanding(g));
 	g->forget<GraphBuildState>();
-	g->M = M;
-	g->M0 = M0;
-	g->ef_construction = ef_construction;
-	g->prune_overflow = prune_overflow;
-	g->ortho_factor = ortho_factor;
-	g->ortho_bias = ortho_bias;
-	g->bstride0 = (uint32_t)stride0;
-	g->bstrideu = (uint32_t)strideu;
-	g->U = U;
+	g->cfg = BuildConfig{M, M0, ef_construction, prune_overflow, ortho_factor, ortho_bias};
 	const size_t cap = g->cap_rows, L_used = g->n_layers - 1;
-	HIP_TRY(g, hipMalloc(&g->d_level, cap));
-	HIP_TRY(g, hipMalloc(&g->d_upper_idx, cap * 4));
-	HIP_TRY(g, hipMalloc(&g->d_id0, cap * stride0 * 4));
-	HIP_TRY(g, hipMalloc(&g->d_d0, cap * stride0 * 4));
-	HIP_TRY(g, hipMalloc(&g->d_deg0, cap * 4));
-	HIP_TRY(g, hipMemset(g->d_deg0, 0, cap * 4));
-	HIP_TRY(g, hipMemcpy(g->d_level, levels, n, hipMemcpyHostToDevice));
-	HIP_TRY(g, hipMemcpy(g->d_upper_idx, upper_idx, n * 4, hipMemcpyHostToDevice));
-	HIP_TRY(g, hipMemcpy(g->d_id0, ids0, n * stride0 * 4, hipMemcpyHostToDevice));
-	HIP_TRY(g, hipMemcpy(g->d_d0, d0, n * stride0 * 4, hipMemcpyHostToDevice));
-	HIP_TRY(g, hipMemcpy(g->d_deg0, deg0, n * 4, hipMemcpyHostToDevice));
-	// the upper arrays: the host's [layer][U] rows at the device's row stride U_cap.  Their first layout also sizes the
-	// CSR to the capacities (graph_size_derived: the one expann_graph_create made holds n rows exactly)
-	g->U = 0;  // (nothing to carry over into the first layout)
+	hipStream_t st = g->stream;
+	HIP_TRY(g, g->arrays.alloc(cap, (uint32_t)stride0, (uint32_t)strideu, 0, 0, st));
+	// the host's [layer][U] upper rows go into a first [L_cap][U_cap] layout with room for half again as many upper
+	// vertices and one more layer (g->U is still 0: nothing to carry over).  It also sizes the CSR to the capacities
+	// (graph_size_derived: the one expann_graph_create made holds n rows exactly).
 	if (int rc = graph_grow_upper(g, U + U / 2 + 64, L_used + 1))
 		return rc;
+	HIP_TRY(g, g->arrays.copy_host<true>(n, levels, upper_idx, ids0, d0, deg0, U, L_used, U, idsu, du, degu, st));
 	g->U = U;
-	for (size_t l = 0; l < L_used && U; ++l) {
-		HIP_TRY(g, hipMemcpy(g->d_idu.get() + l * g->U_cap * strideu, idsu + l * U * strideu, U * strideu * 4, hipMemcpyHostToDevice));
-		HIP_TRY(g, hipMemcpy(g->d_du.get() + l * g->U_cap * strideu, du + l * U * strideu, U * strideu * 4, hipMemcpyHostToDevice));
-		HIP_TRY(g, hipMemcpy(g->d_degu.get() + l * g->U_cap, degu + l * U, U * 4, hipMemcpyHostToDevice));
-	}
 	// a batch's scratch, at the largest batch of THE BATCH RULE
-	const size_t max_batch = 32768, lists = 2 * max_batch + 64;
-	HIP_TRY(g, hipMalloc(&g->d_out, lists * ef_construction * sizeof(md_pair)));
-	HIP_TRY(g, hipMalloc(&g->d_out_cnt, lists * 4));
-	HIP_TRY(g, hipMalloc(&g->d_tasks, lists * sizeof(PruneTask)));
-	HIP_TRY(g, hipMalloc(&g->d_up_slot, max_batch * 4));
-	HIP_TRY(g, hipMalloc(&g->d_build_ctr, 8 * 4));
+	const size_t max_batch = 32768;
+	HIP_TRY(g, g->scratch.alloc(2 * max_batch + 64, max_batch, ef_construction, 0, st));
 	// the walk's layer-0 table takes rows of up to M0 ids from now on (the stride it has, when that is larger)
 	const uint32_t stride_adj = std::max<uint32_t>(g->stride0, (uint32_t)((M0 + 3) / 4 * 4));
 	if (stride_adj != g->stride0) {
@@ -2201,7 +2026,7 @@ int expann_graph_append(expann_graph* g, const float* rows, size_t n, const uint
 	if (need > g->cap_rows) {  // a full handle grows by half
 		if (int rc = graph_grow_rows(g, std::max(need, g->cap_rows + g->cap_rows / 2)))
 			return rc;
-		++g->stat_append[5];
+		++g->stat_append.reallocs;
 	}
 	std::vector<int32_t> up(n, -1);
 	size_t U_new = g->U, L_need = g->n_layers - 1;
@@ -2214,37 +2039,20 @@ int expann_graph_append(expann_graph* g, const float* rows, size_t n, const uint
 		return rc;
 	hipStream_t st = g->stream;
 	HIP_TRY(g, hipMemcpyAsync(g->d_vectors.as<float>() + n_old * (size_t)g->dim, rows, n * (size_t)g->dim * 4, hipMemcpyHostToDevice, st));
-	HIP_TRY(g, hipMemcpyAsync(g->d_level.get() + n_old, levels, n, hipMemcpyHostToDevice, st));
-	HIP_TRY(g, hipMemcpyAsync(g->d_upper_idx.get() + n_old, up.data(), n * 4, hipMemcpyHostToDevice, st));
-	HIP_TRY(g, hipMemsetAsync(g->d_deg0.get() + n_old, 0, n * 4, st));
-	HIP_TRY(g, hipMemsetAsync(g->d_build_ctr, 0, 8 * 4, st));
-	BuildBatches r{};
-	r.bv = build_variant(g->dim);
-	r.g = graph_build_view(g);
+	HIP_TRY(g, hipMemcpyAsync(g->arrays.level.get() + n_old, levels, n, hipMemcpyHostToDevice, st));
+	HIP_TRY(g, hipMemcpyAsync(g->arrays.upper_idx.get() + n_old, up.data(), n * 4, hipMemcpyHostToDevice, st));
+	HIP_TRY(g, hipMemsetAsync(g->arrays.deg0.get() + n_old, 0, n * 4, st));
+	HIP_TRY(g, hipMemsetAsync(g->scratch.ctr, 0, 8 * 4, st));
+	BuildBatches r = build_batches(graph_build_view(g), g->scratch, g->cfg, st, g->dim, g->device);
 	r.g.n = (uint32_t)need;
-	r.st = st;
-	r.dim = g->dim;
-	r.cus = num_cus(g->device);
 	r.levels = levels;
 	r.level_base = n_old;
 	r.b0 = n_old;
 	r.n = need;
 	r.max_layer = g->n_layers;
 	r.starting_vertex = g->starting_vertex;
-	r.max_batch = 0;
-	r.ef = g->ef_construction;
-	r.prune_overflow = g->prune_overflow;
-	r.ortho_factor = g->ortho_factor;
-	r.ortho_bias = g->ortho_bias;
 	r.vis_bits = g->d_visited.as<uint32_t>();  // (the walk's sets: all zero between searches, and none is in flight)
 	r.vis_words = g->vis_words;
-	r.out = g->d_out;
-	r.out_cnt = g->d_out_cnt;
-	r.tasks = g->d_tasks;
-	r.up_slot = g->d_up_slot;
-	r.dirty = g->d_dirty;
-	r.dirty_cap = g->dirty_cap;
-	r.ctr = g->d_build_ctr;
 	r.resident = true;
 	if (int rc = build_batches_geometry(g, r, true))
 		return rc;
@@ -2259,14 +2067,14 @@ int expann_graph_append(expann_graph* g, const float* rows, size_t n, const uint
 	g->n = r.b0;
 	g->n_layers = r.max_layer;
 	g->starting_vertex = r.starting_vertex;
-	g->max_degree0 = std::max<uint32_t>(g->max_degree0, (uint32_t)g->M0);
+	g->max_degree0 = std::max<uint32_t>(g->max_degree0, (uint32_t)g->cfg.M0);
 	const std::string overflow = g->err;
 	if (int rc = graph_rebuild_tables(g))
 		return rc;
-	++g->stat_append[0];
-	g->stat_append[1] += done;
-	g->stat_append[2] += r.n_batches;
-	++g->stat_append[3];
+	++g->stat_append.calls;
+	g->stat_append.rows += done;
+	g->stat_append.batches += r.n_batches;
+	++g->stat_append.device;
 	if (n_appended)
 		*n_appended = done;
 	if (max_layer_out)
@@ -2284,11 +2092,11 @@ int expann_graph_build_state_shape(expann_graph* g, size_t* shape) {
 	if (!g->resident)
 		return g->fail(EXPANN_ERR_NOT_BUILT, "no builder state: expann_graph_adopt_build_state first");
 	shape[0] = g->n;
-	shape[1] = g->U_cap;
+	shape[1] = g->arrays.U_cap;
 	shape[2] = g->n_layers - 1;
 	shape[3] = g->U;
-	shape[4] = g->bstride0;
-	shape[5] = g->bstrideu;
+	shape[4] = g->arrays.stride0;
+	shape[5] = g->arrays.strideu;
 	return EXPANN_OK;
 }
 
@@ -2298,35 +2106,182 @@ int expann_graph_read_build_state(expann_graph* g, uint8_t* levels, int32_t* upp
 		return EXPANN_ERR_INVALID_ARG;
 	if (!g->resident)
 		return g->fail(EXPANN_ERR_NOT_BUILT, "no builder state: expann_graph_adopt_build_state first");
-	const size_t n = g->n, up_rows = (g->n_layers - 1) * g->U_cap;
-	if (!levels || !upper_idx || !ids0 || !d0 || !deg0 || (up_rows && (!idsu || !du || !degu)))
+	const size_t L_used = g->n_layers - 1, U_cap = g->arrays.U_cap;
+	if (!levels || !upper_idx || !ids0 || !d0 || !deg0 || (L_used * U_cap && (!idsu || !du || !degu)))
 		return g->fail(EXPANN_ERR_INVALID_ARG, "expann_graph_read_build_state: NULL pointer");
 	HIP_TRY(g, hipSetDevice(g->device));
-	HIP_TRY(g, hipMemcpy(levels, g->d_level, n, hipMemcpyDeviceToHost));
-	HIP_TRY(g, hipMemcpy(upper_idx, g->d_upper_idx, n * 4, hipMemcpyDeviceToHost));
-	HIP_TRY(g, hipMemcpy(ids0, g->d_id0, n * g->bstride0 * 4, hipMemcpyDeviceToHost));
-	HIP_TRY(g, hipMemcpy(d0, g->d_d0, n * g->bstride0 * 4, hipMemcpyDeviceToHost));
-	HIP_TRY(g, hipMemcpy(deg0, g->d_deg0, n * 4, hipMemcpyDeviceToHost));
-	if (up_rows) {
-		HIP_TRY(g, hipMemcpy(idsu, g->d_idu, up_rows * g->bstrideu * 4, hipMemcpyDeviceToHost));
-		HIP_TRY(g, hipMemcpy(du, g->d_du, up_rows * g->bstrideu * 4, hipMemcpyDeviceToHost));
-		HIP_TRY(g, hipMemcpy(degu, g->d_degu, up_rows * 4, hipMemcpyDeviceToHost));
-	}
+	// the device's layout as it is: whole layers of U_cap rows (expann_graph_build_state_shape reports U_cap as the stride)
+	HIP_TRY(g, g->arrays.copy_host<false>(g->n, levels, upper_idx, ids0, d0, deg0, U_cap, L_used, U_cap, idsu, du, degu, g->stream));
 	return EXPANN_OK;
 }
 
+// carried: the six append counters of the handle the host route replaced, in GraphStats::Appends' order
 int expann_graph_note_host_append(expann_graph* g, const uint64_t* carried, size_t rows) {
+	static_assert(sizeof(GraphStats::Appends) == 6 * sizeof(uint64_t), "carried[6]: one word per field of Appends");
 	if (!g)
 		return EXPANN_ERR_INVALID_ARG;
 	if (carried)
-		std::copy(carried, carried + 6, g->stat_append);
-	++g->stat_append[0];
-	g->stat_append[1] += rows;
-	++g->stat_append[4];
+		std::memcpy(&g->stat_append, carried, sizeof(g->stat_append));
+	++g->stat_append.calls;
+	g->stat_append.rows += rows;
+	++g->stat_append.host;
 	return EXPANN_OK;
 }
 
 // ---- rows taken out of a built graph (THE GRAPH REMOVE RULE, graph_remove.hpp) ----------------------------------
+namespace {
+// One expann_graph_remove: what its phases hand on.  Everything here is the call's own; the handle changes in
+// graph_remove_repair (rows re-pruned in place) and graph_remove_compact_swap, and nowhere before.
+struct GraphRemoval {
+	size_t n = 0, keep_cap = 0, task_cap = 0;
+	uint32_t chunk = 0;                // tasks per gather + prune launch: lists of at most 16384 x 1024 x 8 bytes
+	KeepBitmap rows, upper;            // over the rows; over the upper rows (by upper_idx)
+	DevPtr<uint32_t> ctr;              // {touched rows, truncated rows, the top key's two words}
+	DevPtr<PruneTask> tasks;           // [task_cap] the touched rows
+	DevBuf d_ids;
+	OwnedEvent ev[4];                  // around the touch pass; around gather + prune
+	RemoveView rv{};
+	dim3 entry_grid;
+	// read at the early wait
+	size_t n_new = 0, U_new = 0, n_touched = 0;
+	uint32_t top_level = 0, start_new = 0;
+	// built aside
+	DevPtr<void> vec;
+	BuilderArrays arrays;
+	DevPtr<md_pair> lists;             // [chunk][keep_cap]
+	DevPtr<uint32_t> list_cnt, chunk_cnt;
+	std::vector<uint32_t> h_chunk;     // tasks of every chunk
+};
+
+// both keep bitmaps with their ranks, the touched rows as tasks, the key of the new top: all enqueued, nothing read
+int graph_remove_mark_rank(expann_graph* g, const uint64_t* ids, size_t n_ids, GraphRemoval& r) {
+	hipStream_t st = g->stream;
+	HIP_TRY(g, r.rows.alloc(r.n, st));
+	HIP_TRY(g, r.upper.alloc(g->U, st));
+	HIP_TRY(g, hipMalloc(&r.ctr, sizeof(uint32_t) * 4));
+	HIP_TRY(g, hipMalloc(&r.tasks, sizeof(PruneTask) * r.task_cap));
+	HIP_TRY(g, r.d_ids.alloc(sizeof(uint64_t) * n_ids));
+	for (OwnedEvent& e : r.ev)
+		HIP_TRY(g, hipEventCreate(&e));
+	HIP_TRY(g, hipMemsetAsync(r.ctr, 0, sizeof(uint32_t) * 4, st));
+	HIP_TRY(g, r.rows.all_ones(st));
+	HIP_TRY(g, r.upper.all_ones(st));
+	HIP_TRY(g, hipMemcpyAsync(r.d_ids.p, ids, sizeof(uint64_t) * n_ids, hipMemcpyHostToDevice, st));
+	r.rows.mark_ids(r.d_ids.as<const uint64_t>(), n_ids, st);
+	r.rows.count_rank(st);
+	r.rv = RemoveView{graph_build_view(g), g->n_layers, r.rows.bits(), r.rows.word_rank(), r.upper.bits(), r.upper.word_rank()};
+	const dim3 row_grid((uint32_t)((r.n + kBlock - 1) / kBlock));
+	r.entry_grid = dim3((uint32_t)(((uint64_t)g->n_layers * r.n + kBlock / 16 - 1) / (kBlock / 16)));
+	hipLaunchKernelGGL(graph_remove_mark_upper_kernel, row_grid, dim3(kBlock), 0, st, r.rv, r.upper.bits());
+	r.upper.count_rank(st);
+	HIP_TRY(g, hipEventRecord(r.ev[0], st));
+	hipLaunchKernelGGL(graph_remove_touch_kernel, r.entry_grid, dim3(kBlock), 0, st, r.rv, r.tasks.get(), (uint32_t)r.task_cap,
+	                   r.chunk, r.ctr.get());
+	HIP_TRY(g, hipEventRecord(r.ev[1], st));
+	hipLaunchKernelGGL(graph_remove_top_kernel, dim3(std::min<uint32_t>(row_grid.x, 1024)), dim3(kBlock), 0, st, r.rv,
+	                   (unsigned long long*)(r.ctr.get() + 2));
+	HIP_TRY(g, hipGetLastError());
+	return EXPANN_OK;
+}
+
+// the call's one early host wait, and what it can refuse: nothing of the handle has changed yet.  Then everything built
+// aside -- the rows, the builder's arrays at the handle's capacities, a chunk's lists -- is allocated, before the first
+// row changes
+int graph_remove_wait(expann_graph* g, GraphRemoval& r) {
+	hipStream_t st = g->stream;
+	uint32_t seen[4] = {0, 0, 0, 0}, useen[4] = {0, 0, 0, 0}, h_ctr[4] = {0, 0, 0, 0};
+	HIP_TRY(g, hipMemcpyAsync(seen, r.rows.stat(), sizeof(seen), hipMemcpyDeviceToHost, st));
+	HIP_TRY(g, hipMemcpyAsync(useen, r.upper.stat(), sizeof(useen), hipMemcpyDeviceToHost, st));
+	HIP_TRY(g, hipMemcpyAsync(h_ctr, r.ctr, sizeof(h_ctr), hipMemcpyDeviceToHost, st));
+	HIP_TRY(g, hipStreamSynchronize(st));
+	if (seen[2])
+		return g->fail(EXPANN_ERR_INVALID_ARG, "expann_graph_remove: an id at or beyond the graph's size");
+	r.n_new = seen[0], r.U_new = useen[0], r.n_touched = h_ctr[0];
+	if (r.n_new == 0)
+		return g->fail(EXPANN_ERR_INVALID_ARG, "expann_graph_remove: would leave no row (a graph is never empty)");
+	if (r.n_touched > r.task_cap)
+		return g->fail(EXPANN_ERR_HIP, "expann_graph_remove: more touched rows than rows");
+	r.top_level = h_ctr[3], r.start_new = 0xFFFFFFFFu - h_ctr[2];
+	const size_t n_chunks = (r.n_touched + r.chunk - 1) / r.chunk;
+	HIP_TRY(g, hipMalloc(&r.vec, g->cap_rows * (size_t)g->dim * 4));
+	HIP_TRY(g, hipMalloc(&r.lists, std::max<size_t>((size_t)r.chunk * r.keep_cap, 1) * sizeof(md_pair)));
+	HIP_TRY(g, hipMalloc(&r.list_cnt, std::max<size_t>(r.chunk, 1) * 4));
+	r.h_chunk.assign(std::max<size_t>(n_chunks, 1), 0);
+	for (size_t c = 0; c < n_chunks; ++c)
+		r.h_chunk[c] = (uint32_t)std::min<size_t>(r.chunk, r.n_touched - c * r.chunk);
+	HIP_TRY(g, hipMalloc(&r.chunk_cnt, r.h_chunk.size() * 4));
+	HIP_TRY(g, hipMemcpyAsync(r.chunk_cnt, r.h_chunk.data(), r.h_chunk.size() * 4, hipMemcpyHostToDevice, st));
+	HIP_TRY(g, r.arrays.alloc(g->cap_rows, g->arrays.stride0, g->arrays.strideu, g->arrays.U_cap, g->arrays.L_cap, st));
+	return EXPANN_OK;
+}
+
+// the touched rows gathered and pruned in place, a chunk of tasks at a time over one list buffer
+int graph_remove_repair(expann_graph* g, GraphRemoval& r) {
+	hipStream_t st = g->stream;
+	const BuildVariant* bv = build_variant(g->dim);
+	const uint32_t cus = (uint32_t)num_cus(g->device);
+	const size_t n_chunks = (r.n_touched + r.chunk - 1) / r.chunk;
+	HIP_TRY(g, hipEventRecord(r.ev[2], st));
+	for (size_t c = 0; c < n_chunks; ++c) {
+		RemoveGatherParams gp{};
+		gp.r = r.rv;
+		gp.tasks = r.tasks.get() + c * r.chunk;
+		gp.n_tasks = r.h_chunk[c];
+		gp.keep_cap = (uint32_t)r.keep_cap;
+		gp.lists = r.lists;
+		gp.list_cnt = r.list_cnt;
+		gp.n_truncated = r.ctr.get() + 1;
+		gp.dim = (uint32_t)g->dim;
+		hipLaunchKernelGGL(graph_remove_gather_kernel, dim3(std::min<uint32_t>(r.h_chunk[c], cus * 8)), dim3(kBlock), 0, st, gp);
+		BuildPruneParams pp{};
+		pp.g = r.rv.g;
+		pp.tasks = gp.tasks;
+		pp.n_tasks = r.chunk_cnt.get() + c;
+		pp.lists = r.lists;
+		pp.list_cnt = r.list_cnt;
+		pp.ef = (uint32_t)r.keep_cap;
+		pp.ortho_factor = g->cfg.ortho_factor;
+		pp.ortho_bias = g->cfg.ortho_bias;
+		pp.prune_overflow = (uint32_t)g->cfg.prune_overflow;
+		pp.dim = (uint32_t)g->dim;
+		hipLaunchKernelGGL(bv->prune, dim3(std::min<uint32_t>(r.h_chunk[c], cus * 16)), dim3(kPruneThreads),
+		                   bv->d == 0 ? (size_t)g->dim * sizeof(float) : 0, st, pp);
+	}
+	HIP_TRY(g, hipEventRecord(r.ev[3], st));
+	return EXPANN_OK;
+}
+
+// the survivors' rows and graph rows written aside under their new ids, waited for, and moved into the handle; the
+// walk's tables remade
+int graph_remove_compact_swap(expann_graph* g, GraphRemoval& r) {
+	hipStream_t st = g->stream;
+	const CompactRowsParams cp{r.rows.bits(), r.rows.word_rank(), g->d_vectors.as<const uint4>(), r.vec.as<uint4>(),
+	                           (uint32_t)((size_t)g->dim * 4 / 16)};  // (no row terms carried along)
+	hipLaunchKernelGGL(compact_rows_kernel, dim3((uint32_t)(r.rows.words / 4)), dim3(kBlock), 0, st, cp);
+	const BuilderArrays& to = r.arrays;
+	const RemoveCompactParams rc{r.rv, to.level, to.upper_idx, to.id0, to.d0, to.deg0, to.idu, to.du, to.degu};
+	hipLaunchKernelGGL(graph_remove_compact_kernel, r.entry_grid, dim3(kBlock), 0, st, rc);
+	HIP_TRY(g, hipGetLastError());
+	uint32_t h_ctr[4] = {0, 0, 0, 0};
+	HIP_TRY(g, hipMemcpyAsync(h_ctr, r.ctr, sizeof(h_ctr), hipMemcpyDeviceToHost, st));
+	HIP_TRY(g, hipStreamSynchronize(st));
+	float ms_touch = 0, ms_repair = 0;
+	HIP_TRY(g, hipEventElapsedTime(&ms_touch, r.ev[0], r.ev[1]));
+	HIP_TRY(g, hipEventElapsedTime(&ms_repair, r.ev[2], r.ev[3]));
+	g->d_vectors = std::move(r.vec);
+	g->arrays = std::move(r.arrays);
+	g->n = r.n_new;
+	g->U = r.U_new;
+	g->n_layers = r.top_level + 1;
+	g->starting_vertex = r.start_new;
+	if (int rc2 = graph_rebuild_tables(g))
+		return rc2;
+	g->remove_repair_ns = (uint64_t)(((double)ms_touch + (double)ms_repair) * 1e6);
+	g->stat_remove.truncated += h_ctr[1];
+	return EXPANN_OK;
+}
+}  // namespace
+
 int expann_graph_remove(expann_graph* g, const uint64_t* ids, size_t n_ids, uint32_t* max_layer_out,
                         uint32_t* starting_vertex_out, size_t* n_removed) {
 	if (n_removed)
@@ -2343,188 +2298,35 @@ int expann_graph_remove(expann_graph* g, const uint64_t* ids, size_t n_ids, uint
 		*starting_vertex_out = g->starting_vertex;
 	if (n_ids == 0)
 		return EXPANN_OK;
-	const size_t keep_cap = std::max(g->ef_construction, g->M0);
-	if (keep_cap > (size_t)kPruneMaxCand || g->n >= (1ull << 32) - 64)
+	GraphRemoval r;
+	r.keep_cap = std::max(g->cfg.ef_construction, g->cfg.M0);
+	if (r.keep_cap > (size_t)kPruneMaxCand || g->n >= (1ull << 32) - 64)
 		return g->fail(EXPANN_ERR_UNSUPPORTED, "expann_graph_remove: max(ef_construction, M0) <= 1024");
 	HIP_TRY(g, hipSetDevice(g->device));
 	HIP_TRY(g, graph_wait_outstanding(g));  // (searches in flight read the tables this call remakes)
-	hipStream_t st = g->stream;
-	const size_t n = g->n, words = keep_words(n), uwords = keep_words(g->U);
-	const size_t L_used = g->n_layers - 1, task_cap = n + L_used * g->U;
-	const uint64_t entries = (uint64_t)g->n_layers * n;
-	if (entries >= (1ull << 32) * (kBlock / 16))
+	r.n = g->n;
+	r.task_cap = r.n + (g->n_layers - 1) * g->U;
+	if ((uint64_t)g->n_layers * r.n >= (1ull << 32) * (kBlock / 16))
 		return g->fail(EXPANN_ERR_UNSUPPORTED, "expann_graph_remove: too many rows");
-	const uint32_t chunk = (uint32_t)std::min<size_t>(task_cap, 16384);  // lists of at most 16384 x 1024 x 8 bytes
-	// stat: {survivors, OR, id out of range, -} + segment counts; the same for the upper rows; ctr: {touched rows,
-	// truncated rows, the top key's two words}
-	DevPtr<uint32_t> keep, stat, ukeep, ustat, ctr;
-	DevPtr<PruneTask> tasks;
-	DevBuf d_ids;
-	HIP_TRY(g, hipMalloc(&keep, sizeof(uint32_t) * 2 * words));
-	HIP_TRY(g, hipMalloc(&ukeep, sizeof(uint32_t) * std::max<size_t>(2 * uwords, 1)));
-	HIP_TRY(g, hipMalloc(&stat, sizeof(uint32_t) * (4 + kFilterSegs)));
-	HIP_TRY(g, hipMalloc(&ustat, sizeof(uint32_t) * (4 + kFilterSegs)));
-	HIP_TRY(g, hipMalloc(&ctr, sizeof(uint32_t) * 4));
-	HIP_TRY(g, hipMalloc(&tasks, sizeof(PruneTask) * task_cap));
-	HIP_TRY(g, d_ids.alloc(sizeof(uint64_t) * n_ids));
-	OwnedEvent ev[4];  // around the touch pass; around gather + prune
-	for (OwnedEvent& e : ev)
-		HIP_TRY(g, hipEventCreate(&e));
-	HIP_TRY(g, hipMemsetAsync(stat, 0, sizeof(uint32_t) * (4 + kFilterSegs), st));
-	HIP_TRY(g, hipMemsetAsync(ustat, 0, sizeof(uint32_t) * (4 + kFilterSegs), st));
-	HIP_TRY(g, hipMemsetAsync(ctr, 0, sizeof(uint32_t) * 4, st));
-	HIP_TRY(g, hipMemsetAsync(keep, 0xFF, sizeof(uint32_t) * words, st));
-	if (uwords)
-		HIP_TRY(g, hipMemsetAsync(ukeep, 0xFF, sizeof(uint32_t) * uwords, st));
-	HIP_TRY(g, hipMemcpyAsync(d_ids.p, ids, sizeof(uint64_t) * n_ids, hipMemcpyHostToDevice, st));
-	hipLaunchKernelGGL(remove_mark_kernel, dim3((uint32_t)std::min<size_t>((n_ids + kBlock - 1) / kBlock, 4096)), dim3(kBlock), 0,
-	                   st, d_ids.as<const uint64_t>(), n_ids, (uint32_t)n, keep.get(), stat.get() + 2);
-	hipLaunchKernelGGL(filter_count_kernel, dim3(kFilterSegs), dim3(kBlock), 0, st, keep.get(), (uint32_t)n, (uint32_t)words,
-	                   stat.get(), stat.get() + 4);
-	hipLaunchKernelGGL(remove_word_rank_kernel, dim3(kFilterSegs), dim3(kBlock), 0, st, (const uint32_t*)keep.get(),
-	                   (uint32_t)words, (const uint32_t*)(stat.get() + 4), keep.get() + words);
-	RemoveView rv{};
-	rv.g = graph_build_view(g);
-	rv.n_layers = g->n_layers;
-	rv.bits = keep;
-	rv.word_rank = keep.get() + words;
-	rv.ubits = ukeep;
-	rv.uword_rank = ukeep.get() + uwords;
-	const dim3 row_grid((uint32_t)((n + kBlock - 1) / kBlock)), entry_grid((uint32_t)((entries + kBlock / 16 - 1) / (kBlock / 16)));
-	hipLaunchKernelGGL(graph_remove_mark_upper_kernel, row_grid, dim3(kBlock), 0, st, rv, ukeep.get());
-	hipLaunchKernelGGL(filter_count_kernel, dim3(kFilterSegs), dim3(kBlock), 0, st, ukeep.get(), (uint32_t)g->U, (uint32_t)uwords,
-	                   ustat.get(), ustat.get() + 4);
-	hipLaunchKernelGGL(remove_word_rank_kernel, dim3(kFilterSegs), dim3(kBlock), 0, st, (const uint32_t*)ukeep.get(),
-	                   (uint32_t)uwords, (const uint32_t*)(ustat.get() + 4), ukeep.get() + uwords);
-	HIP_TRY(g, hipEventRecord(ev[0], st));
-	hipLaunchKernelGGL(graph_remove_touch_kernel, entry_grid, dim3(kBlock), 0, st, rv, tasks.get(), (uint32_t)task_cap, chunk,
-	                   ctr.get());
-	HIP_TRY(g, hipEventRecord(ev[1], st));
-	hipLaunchKernelGGL(graph_remove_top_kernel, dim3(std::min<uint32_t>(row_grid.x, 1024)), dim3(kBlock), 0, st, rv,
-	                   (unsigned long long*)(ctr.get() + 2));
-	HIP_TRY(g, hipGetLastError());
-	// the call's one early host wait: nothing of the handle has changed yet
-	uint32_t seen[4] = {0, 0, 0, 0}, useen[4] = {0, 0, 0, 0}, h_ctr[4] = {0, 0, 0, 0};
-	HIP_TRY(g, hipMemcpyAsync(seen, stat, sizeof(seen), hipMemcpyDeviceToHost, st));
-	HIP_TRY(g, hipMemcpyAsync(useen, ustat, sizeof(useen), hipMemcpyDeviceToHost, st));
-	HIP_TRY(g, hipMemcpyAsync(h_ctr, ctr, sizeof(h_ctr), hipMemcpyDeviceToHost, st));
-	HIP_TRY(g, hipStreamSynchronize(st));
-	if (seen[2])
-		return g->fail(EXPANN_ERR_INVALID_ARG, "expann_graph_remove: an id at or beyond the graph's size");
-	const size_t n_new = seen[0], U_new = useen[0], n_touched = h_ctr[0];
-	if (n_new == 0)
-		return g->fail(EXPANN_ERR_INVALID_ARG, "expann_graph_remove: would leave no row (a graph is never empty)");
-	if (n_touched > task_cap)
-		return g->fail(EXPANN_ERR_HIP, "expann_graph_remove: more touched rows than rows");
-	const uint32_t top_level = h_ctr[3], start_new = 0xFFFFFFFFu - h_ctr[2];
-	// everything built aside, allocated before the first row changes
-	const size_t cap = g->cap_rows, s0 = g->bstride0, su = g->bstrideu, up_rows = g->L_cap * g->U_cap;
-	const size_t row_bytes = (size_t)g->dim * 4, n_chunks = (n_touched + chunk - 1) / chunk;
-	DevPtr<void> vec;
-	DevPtr<uint8_t> level;
-	DevPtr<int32_t> upper_idx;
-	DevPtr<uint32_t> id0, deg0, idu, degu, list_cnt;
-	DevPtr<float> d0, du;
-	DevPtr<md_pair> lists;
-	HIP_TRY(g, hipMalloc(&vec, cap * row_bytes));
-	HIP_TRY(g, hipMalloc(&level, cap));
-	HIP_TRY(g, hipMalloc(&upper_idx, cap * 4));
-	HIP_TRY(g, hipMalloc(&id0, cap * s0 * 4));
-	HIP_TRY(g, hipMalloc(&d0, cap * s0 * 4));
-	HIP_TRY(g, hipMalloc(&deg0, cap * 4));
-	HIP_TRY(g, hipMalloc(&idu, std::max<size_t>(up_rows * su, 1) * 4));
-	HIP_TRY(g, hipMalloc(&du, std::max<size_t>(up_rows * su, 1) * 4));
-	HIP_TRY(g, hipMalloc(&degu, std::max<size_t>(up_rows, 1) * 4));
-	HIP_TRY(g, hipMalloc(&lists, std::max<size_t>((size_t)chunk * keep_cap, 1) * sizeof(md_pair)));
-	HIP_TRY(g, hipMalloc(&list_cnt, std::max<size_t>(chunk, 1) * 4));
-	std::vector<uint32_t> h_chunk(std::max<size_t>(n_chunks, 1), 0);
-	for (size_t c = 0; c < n_chunks; ++c)
-		h_chunk[c] = (uint32_t)std::min<size_t>(chunk, n_touched - c * chunk);
-	DevPtr<uint32_t> chunk_cnt;
-	HIP_TRY(g, hipMalloc(&chunk_cnt, h_chunk.size() * 4));
-	HIP_TRY(g, hipMemcpyAsync(chunk_cnt, h_chunk.data(), h_chunk.size() * 4, hipMemcpyHostToDevice, st));
-	HIP_TRY(g, hipMemsetAsync(deg0, 0, cap * 4, st));
-	HIP_TRY(g, hipMemsetAsync(degu, 0, up_rows * 4, st));
+	r.chunk = (uint32_t)std::min<size_t>(r.task_cap, 16384);
+	if (int rc = graph_remove_mark_rank(g, ids, n_ids, r))
+		return rc;
+	if (int rc = graph_remove_wait(g, r))
+		return rc;
 	// from here on the handle changes
 	g->forget<GraphRowFilter>();
 	g->forget<GraphRowGroups>();
 	g->forget<GraphRowBytes>();
-	const BuildVariant* bv = build_variant(g->dim);
-	const uint32_t cus = (uint32_t)num_cus(g->device);
-	HIP_TRY(g, hipEventRecord(ev[2], st));
-	for (size_t c = 0; c < n_chunks; ++c) {
-		RemoveGatherParams gp{};
-		gp.r = rv;
-		gp.tasks = tasks.get() + c * chunk;
-		gp.n_tasks = h_chunk[c];
-		gp.keep_cap = (uint32_t)keep_cap;
-		gp.lists = lists;
-		gp.list_cnt = list_cnt;
-		gp.n_truncated = ctr.get() + 1;
-		gp.dim = (uint32_t)g->dim;
-		hipLaunchKernelGGL(graph_remove_gather_kernel, dim3(std::min<uint32_t>(h_chunk[c], cus * 8)), dim3(kBlock), 0, st, gp);
-		BuildPruneParams pp{};
-		pp.g = rv.g;
-		pp.tasks = gp.tasks;
-		pp.n_tasks = chunk_cnt.get() + c;
-		pp.lists = lists;
-		pp.list_cnt = list_cnt;
-		pp.ef = (uint32_t)keep_cap;
-		pp.ortho_factor = g->ortho_factor;
-		pp.ortho_bias = g->ortho_bias;
-		pp.prune_overflow = (uint32_t)g->prune_overflow;
-		pp.dim = (uint32_t)g->dim;
-		hipLaunchKernelGGL(bv->prune, dim3(std::min<uint32_t>(h_chunk[c], cus * 16)), dim3(kPruneThreads),
-		                   bv->d == 0 ? (size_t)g->dim * sizeof(float) : 0, st, pp);
-	}
-	HIP_TRY(g, hipEventRecord(ev[3], st));
-	CompactRowsParams cp{};
-	cp.bits = keep;
-	cp.word_rank = keep.get() + words;
-	cp.src = g->d_vectors.as<const uint4>();
-	cp.dst = vec.as<uint4>();
-	cp.chunks = (uint32_t)(row_bytes / 16);
-	hipLaunchKernelGGL(compact_rows_kernel, dim3((uint32_t)(words / 4)), dim3(kBlock), 0, st, cp);
-	RemoveCompactParams rc{};
-	rc.r = rv;
-	rc.level = level;
-	rc.upper_idx = upper_idx;
-	rc.id0 = id0;
-	rc.d0 = d0;
-	rc.deg0 = deg0;
-	rc.idu = idu;
-	rc.du = du;
-	rc.degu = degu;
-	hipLaunchKernelGGL(graph_remove_compact_kernel, entry_grid, dim3(kBlock), 0, st, rc);
-	HIP_TRY(g, hipGetLastError());
-	HIP_TRY(g, hipMemcpyAsync(h_ctr, ctr, sizeof(h_ctr), hipMemcpyDeviceToHost, st));
-	HIP_TRY(g, hipStreamSynchronize(st));
-	float ms_touch = 0, ms_repair = 0;
-	HIP_TRY(g, hipEventElapsedTime(&ms_touch, ev[0], ev[1]));
-	HIP_TRY(g, hipEventElapsedTime(&ms_repair, ev[2], ev[3]));
-	g->d_vectors = std::move(vec);
-	g->d_level = std::move(level);
-	g->d_upper_idx = std::move(upper_idx);
-	g->d_id0 = std::move(id0);
-	g->d_d0 = std::move(d0);
-	g->d_deg0 = std::move(deg0);
-	g->d_idu = std::move(idu);
-	g->d_du = std::move(du);
-	g->d_degu = std::move(degu);
-	g->n = n_new;
-	g->U = U_new;
-	g->n_layers = top_level + 1;
-	g->starting_vertex = start_new;
-	if (int rc2 = graph_rebuild_tables(g))
-		return rc2;
-	++g->stat_remove[0];
-	g->stat_remove[1] += n - n_new;
-	g->stat_remove[2] += n_touched;
-	g->stat_remove[3] += h_ctr[1];
-	++g->stat_remove[4];
-	g->remove_repair_ns = (uint64_t)(((double)ms_touch + (double)ms_repair) * 1e6);
+	if (int rc = graph_remove_repair(g, r))
+		return rc;
+	if (int rc = graph_remove_compact_swap(g, r))
+		return rc;
+	++g->stat_remove.calls;
+	g->stat_remove.rows += r.n - r.n_new;
+	g->stat_remove.touched += r.n_touched;
+	++g->stat_remove.device;
 	if (n_removed)
-		*n_removed = n - n_new;
+		*n_removed = r.n - r.n_new;
 	if (max_layer_out)
 		*max_layer_out = g->n_layers;
 	if (starting_vertex_out)
@@ -2532,18 +2334,20 @@ int expann_graph_remove(expann_graph* g, const uint64_t* ids, size_t n_ids, uint
 	return EXPANN_OK;
 }
 
-// carried: the seven remove counters, then the six append counters, of the handle the host route replaced
+// carried: the six remove counters in GraphStats::Removes' order, remove_repair_ns, then the six append counters
 int expann_graph_note_host_remove(expann_graph* g, const uint64_t* carried, size_t rows) {
+	static_assert(sizeof(GraphStats::Removes) == 6 * sizeof(uint64_t) && 6 + 1 + sizeof(GraphStats::Appends) / sizeof(uint64_t) == 13,
+	              "carried[13]: one word per field of Removes, remove_repair_ns, one per field of Appends");
 	if (!g)
 		return EXPANN_ERR_INVALID_ARG;
 	if (carried) {
-		std::copy(carried, carried + 6, g->stat_remove);
+		std::memcpy(&g->stat_remove, carried, sizeof(g->stat_remove));
 		g->remove_repair_ns = carried[6];
-		std::copy(carried + 7, carried + 13, g->stat_append);
+		std::memcpy(&g->stat_append, carried + 7, sizeof(g->stat_append));
 	}
-	++g->stat_remove[0];
-	g->stat_remove[1] += rows;
-	++g->stat_remove[5];
+	++g->stat_remove.calls;
+	g->stat_remove.rows += rows;
+	++g->stat_remove.host;
 	return EXPANN_OK;
 }
 

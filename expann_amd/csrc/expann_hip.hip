@@ -3371,46 +3371,37 @@ namespace {
 // it was.  Nothing aliases the base after commit(): the int8 operand that may (d_base_i8q) is forgotten with
 // OtherCopies before the swap.
 struct CompactedRows {
-	DevPtr<uint32_t> keep;  // [2][words]: the keep bitmap, then word_rank
-	DevPtr<uint32_t> stat;  // [4 + kFilterSegs]: survivors, OR of the words, id-out-of-range flag, max |v| bits; segment counts
+	KeepBitmap keep;  // (stat word 3: the max |v| bits of the survivors)
 	DevPtr<void> base, f16;
 	DevPtr<float> bnorm, bns, bnmax;
 	DevBuf ids;
-	uint32_t seen[4] = {0, 0, 0, 0};  // stat[0..3] on the host
-	size_t words = 0;
+	uint32_t seen[4] = {0, 0, 0, 0};  // keep.stat()[0..3] on the host
 	bool have_copy = false;
 
 	// ids == nullptr: the keep bitmap is the row filter in force
 	int build(expann_index* h, const uint64_t* id_list, size_t n_ids, bool on_device, hipStream_t st) {
 		const size_t n = h->n, row_bytes = (size_t)h->dim * h->elem;
-		words = keep_words(n);
-		HIP_TRY(h, hipMalloc(&keep, sizeof(uint32_t) * 2 * words));
-		HIP_TRY(h, hipMalloc(&stat, sizeof(uint32_t) * (4 + kFilterSegs)));
-		HIP_TRY(h, hipMemsetAsync(stat, 0, sizeof(uint32_t) * (4 + kFilterSegs), st));
+		HIP_TRY(h, keep.alloc(n, st));
 		if (!id_list) {
-			if (h->filter_words != words)
+			if (h->filter_words != keep_words(n))
 				return h->fail(EXPANN_ERR_HIP, "compact_row_filter: the bitmap does not cover the rows");  // (both are whole 128-row tiles)
-			HIP_TRY(h, hipMemcpyAsync(keep, h->d_filter_bits, sizeof(uint32_t) * words, hipMemcpyDeviceToDevice, st));
+			HIP_TRY(h, hipMemcpyAsync(keep.bits(), h->d_filter_bits, sizeof(uint32_t) * keep.words, hipMemcpyDeviceToDevice, st));
 		} else {
-			HIP_TRY(h, hipMemsetAsync(keep, 0xFF, sizeof(uint32_t) * words, st));
+			HIP_TRY(h, keep.all_ones(st));
 			if (!on_device) {
 				HIP_TRY(h, ids.alloc(sizeof(uint64_t) * n_ids));
 				HIP_TRY(h, hipMemcpyAsync(ids.p, id_list, sizeof(uint64_t) * n_ids, hipMemcpyHostToDevice, st));
 				id_list = ids.as<const uint64_t>();
 			}
-			hipLaunchKernelGGL(remove_mark_kernel, dim3((uint32_t)std::min<size_t>((n_ids + kBlock - 1) / kBlock, 4096)),
-			                   dim3(kBlock), 0, st, id_list, n_ids, (uint32_t)n, keep.p, stat + 2);
+			keep.mark_ids(id_list, n_ids, st);
 		}
-		hipLaunchKernelGGL(filter_count_kernel, dim3(kFilterSegs), dim3(kBlock), 0, st, keep.p, (uint32_t)n, (uint32_t)words,
-		                   stat.p, stat + 4);
-		hipLaunchKernelGGL(remove_word_rank_kernel, dim3(kFilterSegs), dim3(kBlock), 0, st, (const uint32_t*)keep.p,
-		                   (uint32_t)words, (const uint32_t*)(stat + 4), keep + words);
+		keep.count_rank(st);
 		HIP_TRY(h, hipGetLastError());
-		const dim3 tiles((uint32_t)(words / 4));
+		const dim3 tiles((uint32_t)(keep.words / 4));
 		HIP_TRY(h, hipMalloc(&base, h->capacity * row_bytes));
 		CompactRowsParams cp{};
-		cp.bits = keep;
-		cp.word_rank = keep + words;
+		cp.bits = keep.bits();
+		cp.word_rank = keep.word_rank();
 		cp.src = (const uint4*)h->d_base;
 		cp.dst = base.as<uint4>();
 		cp.chunks = (uint32_t)(row_bytes / 16);
@@ -3436,11 +3427,11 @@ struct CompactedRows {
 			hipLaunchKernelGGL(compact_rows_kernel, tiles, dim3(kBlock), 0, st, cp);
 			SurvivorMaximaParams mp;
 			mp.rows = h->d_base;
-			mp.bits = keep;
+			mp.bits = keep.bits();
 			mp.n = (uint32_t)n;
 			mp.d = (uint32_t)h->dim;
 			mp.bnmax_bits = bnmax.as<uint32_t>() + 2;
-			mp.maxabs_bits = stat + 3;
+			mp.maxabs_bits = keep.stat() + 3;
 			const dim3 grid((uint32_t)std::min<size_t>((n + kRowsPerGroup - 1) / kRowsPerGroup, 8192));
 			if (f16_rows(h))
 				hipLaunchKernelGGL(survivor_maxima_kernel<_Float16>, grid, dim3(kBlock), 0, st, mp);
@@ -3449,7 +3440,7 @@ struct CompactedRows {
 		}
 		HIP_TRY(h, hipGetLastError());
 		// the one host wait of a remove
-		HIP_TRY(h, hipMemcpyAsync(seen, stat, sizeof(seen), hipMemcpyDeviceToHost, st));
+		HIP_TRY(h, hipMemcpyAsync(seen, keep.stat(), sizeof(seen), hipMemcpyDeviceToHost, st));
 		HIP_TRY(h, hipStreamSynchronize(st));
 		return EXPANN_OK;
 	}

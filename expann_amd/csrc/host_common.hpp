@@ -20,6 +20,13 @@
 			                                       hipGetErrorString(_e));                 \
 	} while (0)
 
+// inside a helper that reports a hipError_t itself: the first error ends it (the caller wraps the helper in HIP_TRY)
+#define HIP_OK(expr)                                   \
+	do {                                               \
+		if (hipError_t _e = (expr); _e != hipSuccess)  \
+			return _e;                                 \
+	} while (0)
+
 namespace expann {
 
 // the bound on k of every brute-force search (half the longest candidate list, kMaxCap in bf_options.hpp):

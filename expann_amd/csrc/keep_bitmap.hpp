@@ -9,8 +9,10 @@
 // compact_rows_kernel moves a survivor's row as bytes, 16 per lane, whatever the dtype.
 // (The kernels are `static`: expann_hip.hip and expann_graph.hip both include this header.)
 #pragma once
+#include "bf_remove.hpp"
 #include "common.hpp"
 #include "filter_rows.hpp"
+#include "host_common.hpp"
 
 namespace expann {
 
@@ -64,6 +66,40 @@ static __global__ __launch_bounds__(kBlock) void remove_word_rank_kernel(const u
 		rank += (uint32_t)__builtin_popcount(bits[w]);
 	}
 }
+
+// The host side of the above: keep[2][words] -- the bitmap, then word_rank -- and stat[4 + kFilterSegs] -- {survivors,
+// OR of the words, an id was out of range, a word for the caller}, then filter_count_kernel's segment counts.  Every
+// step is enqueued on `st`; the caller reads stat()[0..3] back behind its own wait.
+struct KeepBitmap {
+	size_t n = 0, words = 0;  // rows covered; words of the bitmap (whole 128-row tiles)
+	DevPtr<uint32_t> keep, stats;
+
+	uint32_t* bits() const { return keep.get(); }
+	uint32_t* word_rank() const { return keep.get() + words; }
+	uint32_t* stat() const { return stats.get(); }
+
+	// for n_rows rows, stat zeroed; the bits are the caller's to set: all_ones(), or a bitmap copied to bits()
+	hipError_t alloc(size_t n_rows, hipStream_t st) {
+		n = n_rows;
+		words = keep_words(n_rows);
+		HIP_OK(hipMalloc(&keep, sizeof(uint32_t) * std::max<size_t>(2 * words, 1)));
+		HIP_OK(hipMalloc(&stats, sizeof(uint32_t) * (4 + kFilterSegs)));
+		return hipMemsetAsync(stats, 0, sizeof(uint32_t) * (4 + kFilterSegs), st);
+	}
+	hipError_t all_ones(hipStream_t st) const { return words ? hipMemsetAsync(keep, 0xFF, sizeof(uint32_t) * words, st) : hipSuccess; }
+	// one bit cleared per id (device memory); an id >= n raises stat()[2] instead
+	void mark_ids(const uint64_t* d_ids, size_t n_ids, hipStream_t st) const {
+		hipLaunchKernelGGL(remove_mark_kernel, dim3((uint32_t)std::min<size_t>((n_ids + kBlock - 1) / kBlock, 4096)), dim3(kBlock), 0,
+		                   st, d_ids, n_ids, (uint32_t)n, bits(), stat() + 2);
+	}
+	// the tail cleared, stat()[0] = survivors, word_rank() filled
+	void count_rank(hipStream_t st) const {
+		hipLaunchKernelGGL(filter_count_kernel, dim3(kFilterSegs), dim3(kBlock), 0, st, bits(), (uint32_t)n, (uint32_t)words, stat(),
+		                   stat() + 4);
+		hipLaunchKernelGGL(remove_word_rank_kernel, dim3(kFilterSegs), dim3(kBlock), 0, st, (const uint32_t*)bits(), (uint32_t)words,
+		                   (const uint32_t*)(stat() + 4), word_rank());
+	}
+};
 
 struct CompactRowsParams {
 	const uint32_t* bits;       // [n_tiles * 4] the keep bitmap

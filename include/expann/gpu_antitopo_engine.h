@@ -131,14 +131,18 @@ struct gpu_antitopo_engine : public ann_engine<T, gpu_antitopo_engine<T>> {
 		index.from_strided(g, nullptr, index.max_layer, index.starting_vertex);
 		index.adjacency_stale = false;
 	}
-	// the six append counters of the graph handle (carried over a re-upload by the host route)
-	void read_append_stats(uint64_t* six) const {
-		static const char* const names[6] = {"append_calls", "append_rows", "append_batches",
-		                                     "append_device", "append_host", "graph_reallocs"};
-		for (int i = 0; i < 6; ++i)
-			if (expann_graph_get_stat(graph, names[i], six + i) != EXPANN_OK)
-				six[i] = 0;
+	// What the host route carries over a re-upload: the graph handle's seven remove counters, then its six append
+	// counters, in the order of GraphStats::Removes, remove_repair_ns and GraphStats::Appends (expann_graph.hip).
+	void read_carried_stats(uint64_t* out, int first, int count) const {
+		static const char* const names[13] = {"remove_calls", "remove_rows", "remove_touched_rows", "remove_truncated_rows",
+		                                      "remove_device", "remove_host", "remove_repair_ns",
+		                                      "append_calls", "append_rows", "append_batches",
+		                                      "append_device", "append_host", "graph_reallocs"};
+		for (int i = 0; i < count; ++i)
+			if (expann_graph_get_stat(graph, names[first + i], out + i) != EXPANN_OK)
+				out[i] = 0;
 	}
+	void read_append_stats(uint64_t* six) const { read_carried_stats(six, 7, 6); }
 	// The builder's view of the graph handed to the handle, once (the first append or remove on the device route).
 	// *on_host is set when the handle cannot take it (EXPANN_ERR_UNSUPPORTED): the call goes the host route.
 	int adopt_on_device(bool* on_host) {
@@ -223,15 +227,7 @@ struct gpu_antitopo_engine : public ann_engine<T, gpu_antitopo_engine<T>> {
 		return rc;
 	}
 	// ---- Extension: rows taken out of the built graph (THE GRAPH REMOVE RULE, expann_hip.h) ----
-	// the seven remove counters, then the six append counters (carried over a re-upload by the host route)
-	void read_remove_stats(uint64_t* thirteen) const {
-		static const char* const names[7] = {"remove_calls", "remove_rows", "remove_touched_rows", "remove_truncated_rows",
-		                                     "remove_device", "remove_host", "remove_repair_ns"};
-		for (int i = 0; i < 7; ++i)
-			if (expann_graph_get_stat(graph, names[i], thirteen + i) != EXPANN_OK)
-				thirteen[i] = 0;
-		read_append_stats(thirteen + 7);
-	}
+	void read_remove_stats(uint64_t* thirteen) const { read_carried_stats(thirteen, 0, 13); }
 	std::string remove_error;  // what an engine-level refusal of the last remove_rows / compact_row_filter said
 	// The rows `ids` (any order, repeats allowed) taken out.  Returns the expann_status (message: remove_error, or when
 	// that is empty expann_graph_last_error(graph)); *n_removed: the distinct ids.  The routes are append_rows'.

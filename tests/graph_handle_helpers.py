@@ -232,9 +232,9 @@ class Handle:
         assert rc == 0, (rc, self.error())
         return ids, dists.view(np.uint32), dc
 
-    def read(self):
-        """the builder's resident state as a Strided: the upper arrays re-strided from [n_upper_layers][U_stride] rows
-        to [(l - 1) * U + upper_idx]"""
+    def read_raw(self):
+        """((levels, upper_idx, ids0, d0, deg0, idsu, du, degu), U_stride, n_upper_layers, U) as the handle holds them:
+        the upper arrays are [n_upper_layers][U_stride] rows, row (l - 1) * U_stride + upper_idx"""
         shape = (C.c_size_t * 6)()
         assert self.L.expann_graph_build_state_shape(self.h, shape) == 0, self.error()
         n, ustride, L, U, s0, su = (int(x) for x in shape)
@@ -243,8 +243,15 @@ class Handle:
         ids0, d0, deg0 = np.zeros((n, s0), np.uint32), np.zeros((n, s0), np.float32), np.zeros(n, np.uint32)
         rows = max(1, L * ustride)
         idsu, du, degu = np.zeros((rows, su), np.uint32), np.zeros((rows, su), np.float32), np.zeros(rows, np.uint32)
-        rc = self.L.expann_graph_read_build_state(self.h, *(a.ctypes.data for a in (levels, upper_idx, ids0, d0, deg0, idsu, du, degu)))
+        arrays = (levels, upper_idx, ids0, d0, deg0, idsu, du, degu)
+        rc = self.L.expann_graph_read_build_state(self.h, *(a.ctypes.data for a in arrays))
         assert rc == 0, (rc, self.error())
+        return arrays, ustride, L, U
+
+    def read(self):
+        """the builder's resident state as a Strided: the upper arrays re-strided from [n_upper_layers][U_stride] rows
+        to [(l - 1) * U + upper_idx]"""
+        (levels, upper_idx, ids0, d0, deg0, idsu, du, degu), ustride, L, U = self.read_raw()
         nu = max(1, L * U)
 
         def cut(a):

@@ -206,6 +206,49 @@ def _raw(st):
                                st.du.view(np.uint32), st.degu)]
 
 
+def test_the_two_upper_layouts():
+    """600 rows, M = 8, ef 40, drawn levels (U = 73, no multiple of 64; top level >= 2).  The host's [layer][U] upper rows
+    adopted into the handle's [L_cap][U_cap] = [top + 2][237] and read back: the eight arrays are the input.  Then 400
+    rows, 300 of level 1 and the first of level top + 4, so that the upper arrays are laid out again in both dimensions:
+    every upper row of an earlier vertex that the oracle's build left as it was is bit-equal to before, the whole row;
+    and every degree of the raw [layers][U_stride] array that no vertex owns -- slots from U on, and the slots of the
+    layers above the old top that the tall vertex did not take -- is zero."""
+    st, rng, q = hh.drawn_case()
+    p = Params(40)
+    top = st.max_layer - 1
+    U_cap, L_cap = st.U + st.U // 2 + 128, top + 2
+    assert top >= 2 and st.U % 64 != 0 and st.L == top
+    lv = np.zeros(400, np.uint8)
+    lv[rng.choice(400, 300, replace=False)] = 1
+    lv[0] = top + 4
+    assert st.U + int((lv >= 1).sum()) > U_cap and top + 4 > L_cap
+    rows = rng.standard_normal((400, 64)).astype(np.float32)
+    ext = hh.extended(st, rows, lv)
+    ext.oracle_build(ext.n, st.n, p)
+    u32 = np.uint32
+    same = [(l, v) for v in np.flatnonzero(st.levels >= 1) for l in range(1, int(st.levels[v]) + 1)
+            if int(ext.degu[ext.urow(l, v)]) == int(st.degu[st.urow(l, v)]) and
+            np.array_equal(ext.idsu[ext.urow(l, v), :st.degu[st.urow(l, v)]], st.idsu[st.urow(l, v), :st.degu[st.urow(l, v)]]) and
+            np.array_equal(ext.du[ext.urow(l, v), :st.degu[st.urow(l, v)]].view(u32), st.du[st.urow(l, v), :st.degu[st.urow(l, v)]].view(u32))]
+    assert len(same) >= 3 and {l for l, _ in same} >= {1, 2}
+    with hh.Handle(st, ef_construction=40) as h:
+        assert h.read_raw()[1] == U_cap
+        before = h.read()
+        assert all(np.array_equal(a, b) for a, b in zip(_raw(before), _raw(st)))
+        after = check_append(h, before, rows, lv, p, q, reallocs=1)
+        for l, v in same:
+            a, b = after.urow(l, v), st.urow(l, v)
+            assert after.degu[a] == st.degu[b] and np.array_equal(after.idsu[a], st.idsu[b]) and \
+                np.array_equal(after.du[a].view(u32), st.du[b].view(u32)), (l, v)
+        (levels, upper_idx, _, _, _, _, _, degu), ustride, L, U = h.read_raw()
+        assert (U, L) == (st.U + int((lv >= 1).sum()), top + 4) and ustride > max(U, U_cap) and L > L_cap
+        owned = np.zeros((L, ustride), bool)
+        for l in range(1, L + 1):
+            owned[l - 1, upper_idx[levels >= l]] = True
+        assert (degu.reshape(L, ustride)[~owned] == 0).all()
+        assert owned[top:].sum() == 4 and not owned[:, U:].any()
+
+
 def test_refusals_at_the_handle():
     """600 rows.  Before adoption an append and a remove are EXPANN_ERR_NOT_BUILT; on the adopted handle an id >= n, a
     remove of every row, and an adoption with M0 + 1 ids in a row or an id >= n are EXPANN_ERR_INVALID_ARG; a binary16
