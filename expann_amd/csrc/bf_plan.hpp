@@ -14,6 +14,7 @@ namespace expann {
 
 // 8-bit row modes (IntMode of scan_int8.hpp; -1: float rows)
 constexpr int kPlanU8L2 = 0, kPlanI8L2 = 1, kPlanI8L2Ref = 2, kPlanI8IP = 3, kPlanI16L2Ref = 4;
+constexpr int kPlanB1Ham = 5;       // packed-bit rows under the Hamming distance (scan_hamming.hpp); dim counts bits
 constexpr int kPlanMaxDim = 4096;  // kMaxAnyDim
 
 // ---- the dims each family is compiled for (the variant tables of expann_hip.hip are checked against these) ----
@@ -43,6 +44,10 @@ constexpr int kGemmI8Dims[] = {128, 256, 768};      // scan_gemm_i8.hpp: U8L2, I
 constexpr int kI8qWDims[] = {128, 256};             // scan_gemm_i8w.hpp: the same three modes
 constexpr int kI8qXDims[] = {768, 832, 960, 896};   // scan_gemm_w8.hpp, int8 instances
 constexpr int kI8fDim = 128;                        // scan_gemm_i8f.hpp: the int8 filter of fp32 rows
+// packed-bit rows (scan_hamming.hpp): the VALU form's query tiles at every multiple of 64 bits; the matrix-core form
+// serves every multiple of 64 up to kPlanHamMfmaMaxDim (its 64 widened queries and a 512-row tile fill the LDS there)
+constexpr DimTiles kScanB1Tiles = {0, {1, 4, 8}};
+constexpr int kPlanHamMfmaMaxDim = 1024;
 constexpr size_t kI8MinRows = 2 * 256 * 64;         // the int8 hit-log forms: two 256-tile chunks of 64 rows at least
 
 template <size_t N> constexpr bool has_dim(const int (&dims)[N], int d) {
@@ -104,7 +109,10 @@ enum class ScanFamily : int {
 	kGemmI8,   // 8-bit rows on the int8 matrix cores, threshold ladder
 	kI8qW,     // 8-bit rows, per-wave hit queues, by geometry: d = 128 / 256,
 	kI8qX,     //   768 / 832 / 896 / 960,
-	kI8qKL     //   every other multiple of 64
+	kI8qKL,    //   every other multiple of 64
+	// packed-bit rows on the int8 matrix cores (scan_hamming_mfma_kernel): the threshold ladder of kGemmI8 over another
+	// row mode, and the same value -- the row mode tells them apart, and a switch over the families stays complete
+	kHamming = kGemmI8
 };
 constexpr bool is_f16(ScanFamily f) { return f >= ScanFamily::kF16X && f <= ScanFamily::kF16Dbg; }
 
@@ -203,6 +211,8 @@ constexpr const char* kRefuseGemm =
     "rounds 1-2 is gone: scan_kernel 3 = bf16x3, 4 = fp16)";
 constexpr const char* kRefuseBf16 = "bf16x3 GEMM-form scan: f32 L2 with dim 64 or 128 only";
 constexpr const char* kRefuseF16 = "fp16 GEMM-form scan: f32 with dim a multiple of 16 from 64 to 4096 only";
+constexpr const char* kRefuseHamMfma = "matrix-core Hamming scan (scan_kernel=2): packed-bit rows of at most 1024 bits";
+constexpr const char* kRefuseHamKernel = "packed-bit rows: scan_kernel is 0 (auto), 1 (VALU form) or 2 (matrix-core form)";
 
 // the direct scan's query tile for m queries (0: none)
 constexpr int direct_tile(const PlanIndex& x, size_t m) {
@@ -212,6 +222,8 @@ constexpr int direct_tile(const PlanIndex& x, size_t m) {
 			return 0;
 		return pick_tile(t ? t : &kScanF32AnyTiles, m, x.query_tile);
 	}
+	if (x.int_mode == kPlanB1Ham)
+		return x.dim >= 64 && x.dim <= kPlanMaxDim && x.dim % 64 == 0 ? pick_tile(&kScanB1Tiles, m, x.query_tile) : 0;
 	if (any_dim_i8(x.dim, x.int_mode))
 		return pick_tile(&kScanI8AnyTiles, m, x.query_tile);
 	return pick_tile(x.int_mode == kPlanI16L2Ref ? tiles_of(kScanI16Tiles, x.dim) : tiles_of(kScanI8Tiles, x.dim), m,
@@ -246,7 +258,39 @@ constexpr bool float_gemm_wanted(const PlanIndex& x, size_t m) {
 	return has_dim(kBf16Dims, x.dim) || (f16_choice && f16_dim);
 }
 
+// Packed-bit rows: which of the two exact forms of scan_hamming.hpp scans.  Both keep (score, row) <= the proven
+// threshold key, so neither needs a tie restart and the thresholds are the ladder's (sampled class minima on the
+// VALU form); no speculation, no q-forms, no shadow.  The auto rule, from the sweep of both forms at 256 bits, k = 10
+// over m = 1 / 8 / 32 / 96 / 512 / 4 096 queries x n = 16 k / 64 k / 1 M rows (profiles/hamming_ab.txt, ms per step
+// VALU / matrix cores): the matrix cores win at 1 M x 512 (1.155 / 0.859), 1 M x 4 096 (8.07 / 4.89) and 64 k x 4 096
+// (0.870 / 0.816) and lose everywhere else -- 1 M x 96: 0.300 / 0.364, 64 k x 512: 0.161 / 0.210, every 16 k point.
+// Shapes between the grid points take the nearest grid point below them in n and m.
+constexpr bool ham_mfma_auto(size_t n, size_t m) { return (n >= 1000000 && m >= 512) || (n >= 65536 && m >= 4096); }
+inline ScanPlan plan_hamming(const PlanIndex& x, const PlanCall& c, const PlanAttempt& a) {
+	ScanPlan p;
+	const long sk = x.scan_kernel;
+	p.direct_tq = direct_tile(x, c.m);
+	if (sk < 0 || sk > 2) {
+		p.status = EXPANN_ERR_INVALID_ARG;
+		p.message = kRefuseHamKernel;
+		return p;
+	}
+	const bool serves = x.dim <= kPlanHamMfmaMaxDim;
+	if (sk == 2 && !serves) {
+		p.status = EXPANN_ERR_UNSUPPORTED;
+		p.message = kRefuseHamMfma;
+		return p;
+	}
+	if (!a.force_direct && serves && (sk == 2 || (sk == 0 && ham_mfma_auto(x.n, c.m))))
+		p.family = ScanFamily::kHamming;
+	p.tie_fallback = p.family != ScanFamily::kDirect && sk == 0;
+	p.sampled = x.sample_pass && p.family == ScanFamily::kDirect;
+	return p;
+}
+
 inline ScanPlan plan_scan(const PlanIndex& x, const PlanCall& c, const PlanAttempt& a) {
+	if (x.int_mode == kPlanB1Ham)
+		return plan_hamming(x, c, a);
 	ScanPlan p;
 	const long sk = x.scan_kernel;
 	const bool flt = x.int_mode < 0, f32 = x.dtype == EXPANN_DTYPE_F32, l2 = x.metric == EXPANN_METRIC_L2;

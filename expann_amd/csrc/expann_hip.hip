@@ -37,6 +37,7 @@
 #include "scan_gemm_kl.hpp"
 #include "scan_int8.hpp"
 #include "scan_int8_any.hpp"
+#include "scan_hamming.hpp"
 #include "filter_rows.hpp"
 #include "scan_groups.hpp"
 #include "append_rows.hpp"
@@ -85,7 +86,13 @@ struct Config : Options {
 	size_t q_elem = 4;  // bytes per query element at the ABI (f32 for F32/U8 rows, int8 for I8)
 	int int_mode = -1;  // IntMode for 8-bit rows
 	bool strict_u8 = false;          // (on the shadow) non-8-bit / fractional queries: hand back, no error
+	// bytes of a stored row and of a query at the ABI (packed-bit rows: dim counts bits, both sides are dim / 8 bytes)
+	size_t row_bytes() const { return int_mode == kPlanB1Ham ? (size_t)dim / 8 : (size_t)dim * elem; }
+	size_t query_bytes() const { return int_mode == kPlanB1Ham ? (size_t)dim / 8 : (size_t)dim * q_elem; }
 };
+inline bool b1_rows(const Config* h) { return h->int_mode == kPlanB1Ham; }
+constexpr const char* kB1NotOffered =
+    "EXPANN_DTYPE_B1 rows: add / build / set_base_device and expann_search / expann_search_device only";
 
 // the rows: staged on the host until build(), then on the device -- the handle's own copy, or the caller's memory
 // (expann_set_base_device)
@@ -145,6 +152,7 @@ struct OtherCopies : U8Shadow {
 	DevPtr<int> d_bias_i;            // [n] sum b^2 per row (8-bit L2 GEMM form), built lazily
 	MaybeOwnedPtr d_base_i8q;        // padded int8 copy of an 8-bit index (uint8 rows ^ 0x80) or alias of d_base
 	DevPtr<int> d_bp_i8q;            // [n padded] floor(bias/2), scan_gemm_i8q.hpp
+	DevPtr<int> d_popb;              // [n] popcount per row (packed-bit rows, matrix-core form), built lazily
 };
 // all that is derived from the rows: forgotten together when the rows are replaced
 struct RowCopies : F16Copy, OtherCopies {};
@@ -260,6 +268,7 @@ struct Stats {
 	// expann_remove / expann_compact_row_filter since create: accepted calls, rows removed, removes that carried the
 	// fp16 copy over, removes that dropped it or forgot an unusable mark
 	uint64_t stat_remove[4] = {0, 0, 0, 0};
+	uint64_t stat_ham[2] = {0, 0};   // launches of scan_hamming_mfma_kernel / scan_hamming_valu_kernel since create
 };
 
 // streams, events, profiling, statistics, the last error
@@ -409,7 +418,16 @@ const ScanI8Variant kScanI8Any[] = {SCAN_I8_ANY(1), SCAN_I8_ANY(4), SCAN_I8_ANY(
 static_assert(kU8L2 == kPlanU8L2 && kI8L2 == kPlanI8L2 && kI8L2Ref == kPlanI8L2Ref && kI8IP == kPlanI8IP &&
                   kI16L2Ref == kPlanI16L2Ref,
               "bf_plan.hpp: the 8-bit row modes");
+// packed-bit rows: the VALU form's query tiles (kScanB1Tiles), every dim at run time
+const ScanI8Variant kScanB1[] = {{0, 1, kPlanB1Ham, scan_hamming_valu_kernel<1>, "scan_hamming_valu<1>"},
+                                 {0, 4, kPlanB1Ham, scan_hamming_valu_kernel<4>, "scan_hamming_valu<4>"},
+                                 {0, 8, kPlanB1Ham, scan_hamming_valu_kernel<8>, "scan_hamming_valu<8>"}};
+static_assert(kHamMaxDim == kPlanMaxDim && ham_mfma_lds_bytes(kPlanHamMfmaMaxDim) <= 160 * 1024,
+              "bf_plan.hpp: the dims of the two Hamming forms");
 const ScanI8Variant* find_scan_i8(int d, int mode, int tq) {
+	for (const auto& v : kScanB1)
+		if (mode == kPlanB1Ham && v.tq == tq)
+			return &v;
 	const bool any = any_dim_i8(d, mode);
 	for (const auto& v : kScanI8)
 		if (!any && v.d == d && v.mode == mode && v.tq == tq)
@@ -1254,6 +1272,7 @@ bool plan_tables_match() {
 		    return has_tile(v.mode == kI16L2Ref ? tiles_of(kScanI16Tiles, v.d) : tiles_of(kScanI8Tiles, v.d), v.tq);
 	    });
 	all(kScanI8Any, 4 * count_tiles(&kScanI8AnyTiles, 1), [](const ScanI8Variant& v) { return has_tile(&kScanI8AnyTiles, v.tq); });
+	all(kScanB1, count_tiles(&kScanB1Tiles, 1), [](const ScanI8Variant& v) { return has_tile(&kScanB1Tiles, v.tq); });
 	all(kDirectF16, count_tiles(kDirectF16Tiles, std::size(kDirectF16Tiles)),
 	    [](const DirectF16Variant& v) { return has_tile(tiles_of(kDirectF16Tiles, v.d), v.tq); });
 	all(kGemmF16X, std::size(kF16XDims) + std::size(kF16YDims) + std::size(kF16KXDims), [](const GemmF16Variant& v) {
@@ -2131,7 +2150,8 @@ struct SearchPass {
 	const GemmBf16Variant* gvb = nullptr;
 	const GemmF16Variant* gvf = nullptr;
 	const DirectF16Variant* dv = nullptr;  // fp16 form: scan_direct_f16 serves the last level and the sampled pass
-	bool i8f = false;           // the int8 filter runs the full scan (fp16 prelude, scan_gemm_i8f.hpp)
+	bool ham_mfma = false;      // packed-bit rows: scan_hamming_mfma_kernel scans every level (else the VALU form)
+	bool i8f = false;          // the int8 filter runs the full scan (fp16 prelude, scan_gemm_i8f.hpp)
 	bool i8f_ready = false;     // its thresholds of this attempt are written
 	bool i8f_ran = false;       // the last level of this attempt ran it
 	bool flags_clean = false;   // the fp16 prelude has just zeroed the flag block
@@ -2166,6 +2186,13 @@ int SearchPass::choose_kernels() {
 	}
 	if (plan.status != EXPANN_OK)
 		return h->fail(plan.status, plan.message);
+	ham_mfma = b1_rows(h) && plan.family == ScanFamily::kHamming;
+	if (ham_mfma && !h->d_popb) {  // the row term pop(b)
+		HIP_TRY(h, hipMalloc(&h->d_popb, sizeof(int) * h->n));
+		hipLaunchKernelGGL(ham_popcount_kernel, dim3((uint32_t)((h->n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+		                   (const void*)h->d_base, (uint32_t)h->n, (uint32_t)h->dim, h->d_popb.p);
+		HIP_TRY(h, hipGetLastError());
+	}
 	gvf = find_f16(plan.family, h->dim);
 	dv = find_direct_f16(h->dim, plan.direct_f16_tq);
 	i8f = plan.i8f;
@@ -2343,6 +2370,7 @@ int SearchPass::run_level(size_t li) {
 	uint32_t passes = n_qtiles;
 	const char* kname = sv->name;
 	uint32_t qt_used = (uint32_t)sv->tq;
+	uint32_t ham_fixed = 0;  // packed-bit rows, matrix-core form: the keys its level 0 leaves per query
 	if (use_gemm) {
 		// theta_q = tau_q - ||q||^2 (1-eps), then the MFMA filter over 128-row tiles
 		const float f16_abs = gvf ? std::ldexp(1.0f, -24) / h->f16_scale * std::sqrt((float)h->dim)
@@ -2441,7 +2469,44 @@ int SearchPass::run_level(size_t li) {
 		passes = gp.n_qtiles;
 		kname = gvi->name;
 		qt_used = kGemmI8TQ;
+	} else if (ham_mfma) {
+		// packed-bit rows on the matrix cores, level 0 included (the keys of its tiles at fixed slots)
+		hipLaunchKernelGGL(ham_theta_kernel, dim3((uint32_t)((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d_queries,
+		                   (uint32_t)m, (uint32_t)h->dim, (const float*)sp.tau, h->d_theta.as<int>(), h->d_qself.p);
+		HamMfmaParams hp{};
+		hp.base = h->d_base;
+		hp.popb = h->d_popb;
+		hp.n_rows = (uint32_t)h->n;
+		const uint32_t n_tiles = (uint32_t)((h->n + kHamTB - 1) / kHamTB), sel_rows = L.n_groups_sel * kRowsPerGroup;
+		hp.n_tiles_sel = last ? n_tiles
+		                      : (first ? std::max<uint32_t>(1, sel_rows / kHamTB) : std::min(n_tiles, (sel_rows + kHamTB - 1) / kHamTB));
+		hp.tile_stride = std::max<uint32_t>(1, n_tiles / hp.n_tiles_sel);
+		hp.n_qtiles = (uint32_t)((m + kHamTQ - 1) / kHamTQ);
+		hp.queries = d_queries;
+		hp.theta = h->d_theta.as<const int>();
+		hp.popq = h->d_qself;
+		hp.tau_row = sp.tau_row;
+		hp.m = (uint32_t)m;
+		hp.cand_cnt = h->d_cnt;
+		hp.cand = h->d_cand;
+		hp.cap = cap;
+		hp.dim = (uint32_t)h->dim;
+		hp.level0 = first ? 1u : 0u;
+		ham_fixed = std::min<uint32_t>(hp.n_tiles_sel * kHamTB, cap);
+		uint32_t gchunks = pick_row_chunks(hp.n_tiles_sel, hp.n_qtiles, (uint32_t)cus, 1.0, 1, 4096, 0, nullptr);
+		hp.tiles_per_block = (hp.n_tiles_sel + gchunks - 1) / gchunks;
+		gchunks = (hp.n_tiles_sel + hp.tiles_per_block - 1) / hp.tiles_per_block;
+		if (timed)
+			HIP_TRY(h, hipEventRecord(h->ev[h->ev_used][0], st));
+		hipLaunchKernelGGL(scan_hamming_mfma_kernel, dim3(gchunks * hp.n_qtiles), dim3(kHamThreads),
+		                   ham_mfma_lds_bytes((uint32_t)h->dim), st, hp);
+		h->stat_ham[0]++;
+		passes = hp.n_qtiles;
+		kname = "scan_hamming_mfma";
+		qt_used = kHamTQ;
 	} else {
+		if (b1_rows(h))
+			h->stat_ham[1]++;
 		if (timed)
 			HIP_TRY(h, hipEventRecord(h->ev[h->ev_used][0], st));
 		hipLaunchKernelGGL(scan_fn, dim3(n_chunks * n_qtiles), dim3(kBlock), 0, st, sp);
@@ -2465,6 +2530,8 @@ int SearchPass::run_level(size_t li) {
 	sel.cand = h->d_cand;
 	sel.cand_cnt = first ? nullptr : h->d_cnt;
 	sel.fixed_count = (first && L.classmin_blocks) ? n_chunks * 16 : L.n_groups_sel * kRowsPerGroup;
+	if (ham_mfma)
+		sel.fixed_count = ham_fixed;
 	sel.cap = cap;
 	sel.k = (uint32_t)k;
 	sel.id_offset = h->id_offset;
@@ -2909,6 +2976,10 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 		return EXPANN_ERR_INVALID_ARG;
 	}
 	*out = nullptr;
+	if ((dtype == EXPANN_DTYPE_B1) != (metric == EXPANN_METRIC_HAMMING)) {
+		g_create_error = "EXPANN_DTYPE_B1 and EXPANN_METRIC_HAMMING go together only";
+		return EXPANN_ERR_INVALID_ARG;
+	}
 	if (dim <= 0 || dim % 16 != 0) {
 		g_create_error = "dim must be a positive multiple of 16 (the reference kernels require it)";
 		return EXPANN_ERR_INVALID_ARG;
@@ -2947,6 +3018,8 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 			g_create_error = "unknown metric for int8 rows";
 			return EXPANN_ERR_INVALID_ARG;
 		}
+	} else if (dtype == EXPANN_DTYPE_B1) {  // (dim counts bits; the 8-bit rows' dim rules below)
+		int_mode = kPlanB1Ham;
 	} else {
 		g_create_error = "unknown dtype";
 		return EXPANN_ERR_INVALID_ARG;
@@ -3038,6 +3111,8 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 				needs.push_back({(const void*)v.scan_w, v.lds_w, "scan_gemm_kl_kernel, int8"});
 				needs.push_back({(const void*)v.sample_w, v.lds_w, "scan_gemm_kl_kernel, int8"});
 			}
+	if (int_mode == kPlanB1Ham && dim <= kPlanHamMfmaMaxDim)
+		needs.push_back({(const void*)scan_hamming_mfma_kernel, (int)ham_mfma_lds_bytes((uint32_t)dim), "scan_hamming_mfma_kernel"});
 	for (const auto& v : kGemmBf16)
 		if (v.d == dim)
 			needs.push_back({(const void*)v.scan, 2 * kGemmTB * dim * (int)sizeof(float), "scan_gemm_bf16x3_kernel"});
@@ -3074,7 +3149,7 @@ int expann_add(expann_index* h, const void* rows, size_t n) {
 		return h->fail(EXPANN_ERR_INVALID_ARG, "rows == NULL");
 	if (h->d_base)
 		return h->fail(EXPANN_ERR_INVALID_ARG, "index already built");
-	const size_t bytes = n * (size_t)h->dim * h->elem;
+	const size_t bytes = n * h->row_bytes();
 	const unsigned char* src = static_cast<const unsigned char*>(rows);
 	h->staging.insert(h->staging.end(), src, src + bytes);
 	h->n_staged += n;
@@ -3095,7 +3170,7 @@ int expann_build(expann_index* h) {
 	drop_row_groups(h);
 	void* rows = nullptr;
 	const size_t capacity = std::max(h->n_staged, h->reserved);  // (expann_reserve before build(): room for the appends to come)
-	HIP_TRY(h, hipMalloc(&rows, capacity * (size_t)h->dim * h->elem));
+	HIP_TRY(h, hipMalloc(&rows, capacity * h->row_bytes()));
 	h->d_base.own(rows);
 	h->capacity = capacity;
 	HIP_TRY(h, hipMemcpy(h->d_base, h->staging.data(), h->staging.size(), hipMemcpyHostToDevice));
@@ -3246,6 +3321,8 @@ uint64_t copies_digest(expann_index* h) {
 int append_rows(expann_index* h, const void* rows, size_t n_new, bool on_device, hipStream_t user_st) {
 	if (!h)
 		return EXPANN_ERR_INVALID_ARG;
+	if (b1_rows(h))
+		return h->fail(EXPANN_ERR_UNSUPPORTED, kB1NotOffered);
 	const AppendState state = append_state(h, rows != nullptr);
 	AppendPlan plan = plan_append(state, n_new, 0.0f);  // (the status and the capacity: no device call before them)
 	if (plan.status != EXPANN_OK)
@@ -3340,6 +3417,8 @@ int expann_append_device(expann_index* h, const void* d_rows, size_t n, void* st
 int expann_reserve(expann_index* h, size_t n_rows) {
 	if (!h)
 		return EXPANN_ERR_INVALID_ARG;
+	if (b1_rows(h))
+		return h->fail(EXPANN_ERR_UNSUPPORTED, kB1NotOffered);
 	const AppendPlan plan = plan_reserve(append_state(h, true), n_rows);
 	if (plan.status != EXPANN_OK)
 		return h->fail(plan.status, plan.message);
@@ -3478,6 +3557,8 @@ int remove_rows(expann_index* h, const uint64_t* ids, size_t n_ids, bool on_devi
                 size_t* n_removed) {
 	if (!h)
 		return EXPANN_ERR_INVALID_ARG;
+	if (b1_rows(h))
+		return h->fail(EXPANN_ERR_UNSUPPORTED, kB1NotOffered);
 	if (from_filter && !h->filter_on)
 		return h->fail(EXPANN_ERR_INVALID_ARG, "compact_row_filter: no row filter in force");
 	const AppendState state = append_state(h, from_filter || ids != nullptr);
@@ -3543,6 +3624,8 @@ int expann_search_device(expann_index* h, const void* d_queries, size_t m, size_
 		return EXPANN_OK;
 	if (!d_queries || !d_ids)
 		return h->fail(EXPANN_ERR_INVALID_ARG, "NULL query/ids pointer");
+	if (b1_rows(h) && h->opt_async && !h->host_call)  // (deferred searches are not offered for packed-bit rows)
+		return h->fail(EXPANN_ERR_UNSUPPORTED, kB1NotOffered);
 	HIP_TRY(h, hipSetDevice(h->device));
 	hipStream_t st = stream ? (hipStream_t)stream : h->stream;
 	// all searches of a handle share one workspace: deferred searches still running on ANOTHER
@@ -3552,7 +3635,7 @@ int expann_search_device(expann_index* h, const void* d_queries, size_t m, size_
 		HIP_TRY(h, hipStreamSynchronize(h->async_stream));
 		h->async_stream = st;
 	}
-	const size_t qbytes = (size_t)h->dim * h->q_elem;
+	const size_t qbytes = h->query_bytes();
 	h->stat_redo_queries = 0;
 	h->stat_redo_candidates = 0;
 	h->stat_rerank_rows = 0;
@@ -3627,7 +3710,7 @@ int expann_search(expann_index* h, const void* queries, size_t m, size_t k, uint
 			return rs;
 	}
 	HIP_TRY(h, hipSetDevice(h->device));
-	const size_t qbytes = m * (size_t)h->dim * h->q_elem;
+	const size_t qbytes = m * h->query_bytes();
 	HIP_TRY(h, h->d_q.ensure(qbytes));
 	if (m * k <= 16384 && qbytes <= (256u << 10) && m <= kMaxQueriesPerPass && h->opt_latency_mode) {
 		const size_t ids_off = (qbytes + 63) / 64 * 64;
@@ -3732,6 +3815,8 @@ int expann_score_ids(expann_index* h, const void* query, const uint64_t* ids, si
                      float cutoff, uint64_t* kept_ids, float* kept_scores, size_t* n_kept) {
 	if (!h)
 		return EXPANN_ERR_INVALID_ARG;
+	if (b1_rows(h))
+		return h->fail(EXPANN_ERR_UNSUPPORTED, kB1NotOffered);
 	if (!h->d_base)
 		return h->fail(EXPANN_ERR_NOT_BUILT, "score_ids before build()");
 	if (!n_kept || (n_ids && (!query || !ids || !kept_ids || !kept_scores)))
@@ -3878,7 +3963,7 @@ int expann_get_stat(expann_index* h, const char* name, uint64_t* out) {
 	    {"spec_rank", [](H h) { return h->stat_spec_rank; }},
 	    {"i8_sample", [](H h) { return h->stat_i8_sample; }},
 	    {"rerank_rows", [](H h) { return h->stat_rerank_rows; }},
-	    {"base_bytes", [](H h) { return h->d_base ? (uint64_t)h->n * (uint64_t)h->dim * h->elem : 0; }},
+	    {"base_bytes", [](H h) { return h->d_base ? (uint64_t)h->n * (uint64_t)h->row_bytes() : 0; }},
 	    {"filter_active", [](H h) -> uint64_t { return h->filter_on ? 1 : 0; }},
 	    {"filter_rows", [](H h) -> uint64_t { return h->filter_on ? h->n_allowed : expann_size(h); }},
 	    {"groups_active", [](H h) -> uint64_t { return h->groups_on ? 1 : 0; }},
@@ -3901,6 +3986,8 @@ int expann_get_stat(expann_index* h, const char* name, uint64_t* out) {
 	    {"remove_compacts", [](H h) { return h->stat_remove[2]; }},
 	    {"remove_rebuilds", [](H h) { return h->stat_remove[3]; }},
 	    {"base_capacity_rows", [](H h) -> uint64_t { return h->d_base ? h->capacity : h->reserved; }},
+	    {"hamming_mfma_launches", [](H h) { return h->stat_ham[0]; }},
+	    {"hamming_valu_launches", [](H h) { return h->stat_ham[1]; }},
 	    {"copies_digest", [](H h) { return copies_digest(const_cast<expann_index*>(h)); }},
 	};
 	for (const auto& s : kStatTable)

@@ -14,9 +14,9 @@ import numpy as np
 from . import _lib
 
 _NP_DTYPE = {_lib.DTYPE_F32: np.float32, _lib.DTYPE_U8: np.uint8, _lib.DTYPE_I8: np.int8,
-             _lib.DTYPE_I16: np.int16, _lib.DTYPE_F16: np.float16}
+             _lib.DTYPE_I16: np.int16, _lib.DTYPE_F16: np.float16, _lib.DTYPE_B1: np.uint8}
 _DTYPE = {"f32": _lib.DTYPE_F32, "u8": _lib.DTYPE_U8, "i8": _lib.DTYPE_I8, "i16": _lib.DTYPE_I16,
-          "f16": _lib.DTYPE_F16}
+          "f16": _lib.DTYPE_F16, "b1": _lib.DTYPE_B1}
 # row types whose queries are fp32 at the ABI (the others take queries of the rows' own type)
 _F32_QUERIES = (_lib.DTYPE_F32, _lib.DTYPE_U8, _lib.DTYPE_F16)
 
@@ -36,14 +36,19 @@ class GpuBruteForceEngine:
 
     dtype="f16": the rows are kept as IEEE binary16 (numpy casts what is stored, rounding to nearest even),
     half the device memory of "f32"; queries stay float32 and every result is, bit for bit, that of an "f32"
-    engine over rows.astype(np.float16).astype(np.float32)."""
+    engine over rows.astype(np.float16).astype(np.float32).
+
+    dtype="b1" with metric="hamming": dim counts bits; rows and queries are uint8 arrays [*, dim / 8] as
+    numpy.packbits(..., bitorder="little") packs them, and the distances are the numbers of differing bits.
+    Add, build, size and the searches only (EXPANN_DTYPE_B1, include/expann_hip.h)."""
 
     def __init__(self, dim, metric="l2", dtype="f32", device=0):
         self._L = _lib.load()
         self.dim = int(dim)
         self.metric = {"l2": _lib.METRIC_L2, "ip": _lib.METRIC_IP,
-                       "l2_i8_refcompat": _lib.METRIC_L2_I8_REFCOMPAT}[metric]
+                       "l2_i8_refcompat": _lib.METRIC_L2_I8_REFCOMPAT, "hamming": _lib.METRIC_HAMMING}[metric]
         self.dtype = _DTYPE[dtype]
+        self._cols = self.dim // 8 if self.dtype == _lib.DTYPE_B1 else self.dim  # elements of a row at the ABI
         self.device = int(device)
         self._metric_name, self._dtype_name = metric, dtype
         h = C.c_void_p()
@@ -67,8 +72,8 @@ class GpuBruteForceEngine:
         """Before build(): expann_add.  After build(): expann_append -- the reference's engine has no frozen state
         (store, build, query, store, query), and neither has this one."""
         rows = np.ascontiguousarray(rows, dtype=_NP_DTYPE[self.dtype])
-        if rows.ndim != 2 or rows.shape[1] != self.dim:
-            raise ValueError(f"rows must be [n, {self.dim}]")
+        if rows.ndim != 2 or rows.shape[1] != self._cols:
+            raise ValueError(f"rows must be [n, {self._cols}]")
         call = self._L.expann_append if self._built else self._L.expann_add
         _lib.check(self._h, call(self._h, rows.ctypes.data, rows.shape[0]))
 
@@ -138,8 +143,8 @@ class GpuBruteForceEngine:
         (expann_search_grouped after set_row_groups; _lib.GROUP_ANY = every row)."""
         qdt = np.float32 if self.dtype in _F32_QUERIES else _NP_DTYPE[self.dtype]
         queries = np.ascontiguousarray(queries, dtype=qdt)
-        if queries.ndim != 2 or queries.shape[1] != self.dim:
-            raise ValueError(f"queries must be [m, {self.dim}]")
+        if queries.ndim != 2 or queries.shape[1] != self._cols:
+            raise ValueError(f"queries must be [m, {self._cols}]")
         m = queries.shape[0]
         ids = np.empty((m, k), dtype=np.uint64)
         dists = np.empty((m, k), dtype=np.float32)
@@ -270,6 +275,7 @@ class GpuBruteForceEngine:
         "rerank_rows" (rows the last search's selects re-scored exactly; counted under the option "rerank_stats");
         "filter_active" (0 / 1) and "filter_rows" (rows the row filter allows; n when none is set);
         "base_bytes" (device bytes of the rows themselves: n * dim * element size);
+        "hamming_mfma_launches", "hamming_valu_launches" (packed-bit rows: scan launches of either form since create);
         "groups_active", "group_count", and of the last grouped search "group_list_queries", "group_filter_queries",
         "group_any_queries", "group_pad_queries", "group_filter_passes";
         of the last range search "range_list_queries", "range_topk_queries", "range_retries";

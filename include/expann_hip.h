@@ -46,9 +46,25 @@ enum expann_dtype {
 	                       * (distance_compare_avx512f_i32: 16-bit wrapping arithmetic,
 	                       * exact only while |a_i - b_i| <= 181); EXPANN_METRIC_L2 only,
 	                       * dim 64 or 128; queries int16                            */
-	EXPANN_DTYPE_F16 = 4  /* IEEE binary16 rows, see below (appended; EXPANN_ABI_VERSION stays 2:
+	EXPANN_DTYPE_F16 = 4, /* IEEE binary16 rows, see below (appended; EXPANN_ABI_VERSION stays 2:
 	                       * nothing that existed changed)                            */
+	EXPANN_DTYPE_B1 = 5   /* packed bits under EXPANN_METRIC_HAMMING, see below (appended likewise) */
 };
+/* EXPANN_DTYPE_B1: rows are packed bits.  `dim` is the number of BITS: any multiple of 64 from 64 to 4096 (not a
+ * multiple of 64: EXPANN_ERR_INVALID_ARG; over 4096: EXPANN_ERR_UNSUPPORTED; both before the device is touched).  A row
+ * is dim / 8 bytes, [n][dim / 8]; dimension j is bit j % 8 of byte j / 8 (numpy.packbits(..., bitorder="little"));
+ * queries are packed the same way, [m][dim / 8].  EXPANN_DTYPE_B1 and EXPANN_METRIC_HAMMING go together only: either
+ * without the other is EXPANN_ERR_INVALID_ARG from expann_create.  The score is popcount(q xor b) as a float (exact:
+ * at most 4096), ascending (score, id), padded with UINT64_MAX / +inf as everywhere.
+ * Served: expann_add, expann_build, expann_set_base_device (with id_offset), expann_size, expann_search and
+ * expann_search_device for 1 <= k <= 8192 with the synchronous overflow check, expann_get_stat ("base_bytes" = n * dim
+ * / 8; "hamming_mfma_launches" / "hamming_valu_launches" = scan launches of either form since create) and
+ * expann_set_option.  "scan_kernel": 0 = auto, 1 = the VALU form (xor + popcount), 2 = the form on the int8 matrix
+ * cores (dim <= 1024; EXPANN_ERR_UNSUPPORTED beyond), any other value is refused by the next search
+ * (EXPANN_ERR_INVALID_ARG); ids and distances are the same for each choice.  Both forms are exact under ties.
+ * NOT offered, each EXPANN_ERR_UNSUPPORTED with a message and the handle untouched: the row filter and row groups,
+ * range search, expann_append* and expann_reserve, expann_remove* and expann_compact_row_filter, expann_score_ids,
+ * the expann_sharded_* handles, and deferred searches (expann_search_device under "async_search" = 1). */
 /* EXPANN_DTYPE_F16: rows are IEEE binary16, [n][dim], 2 bytes per element -- in expann_add's staging, on the
  * device and for expann_set_base_device -- and stay binary16 on the device (expann_get_stat "base_bytes").  Queries
  * are fp32 [m][dim], as for F32 and U8 rows.  Metrics EXPANN_METRIC_L2 and EXPANN_METRIC_IP (anything else
@@ -74,8 +90,9 @@ enum expann_metric {
 	                         i8: true sum (a-b)^2                                      */
 	EXPANN_METRIC_IP = 1, /* score = -dot (src/distance.h:181-190 for f32); largest
 	                         inner product first, ties by lower id                      */
-	EXPANN_METRIC_L2_I8_REFCOMPAT = 2 /* i8 only: src/distance.h:29-53 bit for bit,
+	EXPANN_METRIC_L2_I8_REFCOMPAT = 2, /* i8 only: src/distance.h:29-53 bit for bit,
 	                         including its zero-extension of the wrapped difference     */
+	EXPANN_METRIC_HAMMING = 3 /* EXPANN_DTYPE_B1 only: popcount(q xor b)               */
 };
 
 typedef struct expann_index expann_index;
