@@ -58,6 +58,7 @@ ABI_SYMBOLS = [
     "expann_graph_build_state_shape", "expann_graph_read_build_state", "expann_graph_note_host_append",
     "expann_antitopo_remove", "expann_antitopo_compact_row_filter", "expann_graph_remove",
     "expann_graph_note_host_remove", "expann_graph_read_row_filter",
+    "expann_search_asym_i8", "expann_search_asym_i8_device",
 ]
 GROUP_ANY = 0xFFFFFFFF  # EXPANN_GROUP_ANY: the group a query names to search every row
 
@@ -159,6 +160,11 @@ def load():
     L.expann_sync.argtypes = [vp]
     L.expann_search_device.restype = C.c_int
     L.expann_search_device.argtypes = [vp, vp, sz, sz, vp, vp, vp]
+    if hasattr(L, "expann_search_asym_i8"):  # (EXPANN_LIB may name an older build for an A/B run)
+        L.expann_search_asym_i8.restype = C.c_int
+        L.expann_search_asym_i8.argtypes = [vp, vp, sz, sz, vp, vp]
+        L.expann_search_asym_i8_device.restype = C.c_int
+        L.expann_search_asym_i8_device.argtypes = [vp, vp, sz, sz, vp, vp, vp]
     L.expann_merge_topk_device.restype = C.c_int
     L.expann_merge_topk_device.argtypes = [C.c_int, vp, vp, sz, sz, sz, vp, vp, vp]
     L.expann_merge_topk_strided_device.restype = C.c_int

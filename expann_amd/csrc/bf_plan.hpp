@@ -288,6 +288,42 @@ inline ScanPlan plan_hamming(const PlanIndex& x, const PlanCall& c, const PlanAt
 	return p;
 }
 
+// Packed-bit rows against int8 queries (expann_search_asym_i8, THE ASYMMETRIC RULE): one form, scan_asym_mfma_kernel
+// (scan_asym.hpp), for every m >= 1 and every dim the rows can have; it scans every level of the ladder, level 0
+// included, and keeps (score, row) <= the proven threshold key, so there is no sampled pass, no speculation and no
+// tie restart.  c.cap is the lists' starting capacity (plan_start_cap).  "scan_kernel" is not read: it chooses among
+// the Hamming forms.
+constexpr size_t kPlanAsymMaxK = 8192;
+constexpr uint32_t kPlanAsymTile = 512;  // rows of a tile (kHamTB)
+constexpr const char* kRefuseAsymRows = "expann_search_asym_i8: EXPANN_DTYPE_B1 rows only";
+constexpr const char* kRefuseAsymK = "expann_search_asym_i8: k is at most 8192 (half the longest candidate list)";
+inline ScanPlan plan_asym(const PlanIndex& x, const PlanCall& c) {
+	ScanPlan p;
+	if (x.int_mode != kPlanB1Ham || x.dtype != EXPANN_DTYPE_B1) {
+		p.status = EXPANN_ERR_UNSUPPORTED;
+		p.message = kRefuseAsymRows;
+	} else if (c.k > kPlanAsymMaxK || (size_t)c.cap < 2 * c.k) {
+		p.status = EXPANN_ERR_UNSUPPORTED;
+		p.message = kRefuseAsymK;
+	} else {
+		p.family = ScanFamily::kHamming;  // (the threshold ladder over packed-bit rows; SearchPass::asym names the kernel)
+	}
+	return p;
+}
+// The tiles a level of the ladder visits: the last level every tile; level 0 the whole tiles its sample of sel_rows
+// rows holds (one at least; its keys sit at fixed slots, `fixed` of them per query); a level between, the tiles that
+// cover its sample.  Tile j of the launch is base tile j * tile_stride.
+struct AsymTiles {
+	uint32_t n_tiles_sel, tile_stride, fixed;
+};
+constexpr AsymTiles plan_asym_tiles(size_t n, uint32_t sel_rows, bool first, bool last, uint32_t cap) {
+	const uint32_t T = kPlanAsymTile, n_tiles = (uint32_t)((n + T - 1) / T);
+	const uint32_t cover = (sel_rows + T - 1) / T < n_tiles ? (sel_rows + T - 1) / T : n_tiles;
+	const uint32_t sel = last ? n_tiles : (first ? (sel_rows / T > 1 ? sel_rows / T : 1) : cover);
+	const uint32_t stride = n_tiles / sel > 1 ? n_tiles / sel : 1;
+	return AsymTiles{sel, stride, (uint64_t)sel * T < cap ? sel * T : cap};
+}
+
 inline ScanPlan plan_scan(const PlanIndex& x, const PlanCall& c, const PlanAttempt& a) {
 	if (x.int_mode == kPlanB1Ham)
 		return plan_hamming(x, c, a);

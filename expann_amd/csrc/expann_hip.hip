@@ -38,6 +38,7 @@
 #include "scan_int8.hpp"
 #include "scan_int8_any.hpp"
 #include "scan_hamming.hpp"
+#include "scan_asym.hpp"
 #include "filter_rows.hpp"
 #include "scan_groups.hpp"
 #include "append_rows.hpp"
@@ -269,6 +270,7 @@ struct Stats {
 	// fp16 copy over, removes that dropped it or forgot an unusable mark
 	uint64_t stat_remove[4] = {0, 0, 0, 0};
 	uint64_t stat_ham[2] = {0, 0};   // launches of scan_hamming_mfma_kernel / scan_hamming_valu_kernel since create
+	uint64_t stat_asym = 0;          // launches of scan_asym_mfma_kernel since create
 };
 
 // streams, events, profiling, statistics, the last error
@@ -2151,6 +2153,7 @@ struct SearchPass {
 	const GemmF16Variant* gvf = nullptr;
 	const DirectF16Variant* dv = nullptr;  // fp16 form: scan_direct_f16 serves the last level and the sampled pass
 	bool ham_mfma = false;      // packed-bit rows: scan_hamming_mfma_kernel scans every level (else the VALU form)
+	bool asym = false;          // the query kind: int8 queries [m][dim] on packed-bit rows, scan_asym_mfma_kernel at every level
 	bool i8f = false;          // the int8 filter runs the full scan (fp16 prelude, scan_gemm_i8f.hpp)
 	bool i8f_ready = false;     // its thresholds of this attempt are written
 	bool i8f_ran = false;       // the last level of this attempt ran it
@@ -2166,7 +2169,9 @@ struct SearchPass {
 	bool rerank_counted = false;  // "rerank_stats": the last level's selects counted the rows they re-scored
 
 	enum Next { kDone, kRestart, kRetry };
-	ScanPlan replan() const { return plan_scan(plan_index(h), PlanCall{m, k, cap}, learned); }
+	ScanPlan replan() const {
+		return asym ? plan_asym(plan_index(h), PlanCall{m, k, cap}) : plan_scan(plan_index(h), PlanCall{m, k, cap}, learned);
+	}
 	int choose_kernels();
 	int prepare_queries(bool* restart);
 	int plan_thresholds();
@@ -2186,7 +2191,7 @@ int SearchPass::choose_kernels() {
 	}
 	if (plan.status != EXPANN_OK)
 		return h->fail(plan.status, plan.message);
-	ham_mfma = b1_rows(h) && plan.family == ScanFamily::kHamming;
+	ham_mfma = b1_rows(h) && plan.family == ScanFamily::kHamming && !asym;
 	if (ham_mfma && !h->d_popb) {  // the row term pop(b)
 		HIP_TRY(h, hipMalloc(&h->d_popb, sizeof(int) * h->n));
 		hipLaunchKernelGGL(ham_popcount_kernel, dim3((uint32_t)((h->n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
@@ -2370,7 +2375,7 @@ int SearchPass::run_level(size_t li) {
 	uint32_t passes = n_qtiles;
 	const char* kname = sv->name;
 	uint32_t qt_used = (uint32_t)sv->tq;
-	uint32_t ham_fixed = 0;  // packed-bit rows, matrix-core form: the keys its level 0 leaves per query
+	uint32_t ham_fixed = 0;  // packed-bit rows, matrix-core forms: the keys their level 0 leaves per query
 	if (use_gemm) {
 		// theta_q = tau_q - ||q||^2 (1-eps), then the MFMA filter over 128-row tiles
 		const float f16_abs = gvf ? std::ldexp(1.0f, -24) / h->f16_scale * std::sqrt((float)h->dim)
@@ -2469,6 +2474,39 @@ int SearchPass::run_level(size_t li) {
 		passes = gp.n_qtiles;
 		kname = gvi->name;
 		qt_used = kGemmI8TQ;
+	} else if (asym) {
+		// int8 queries on packed-bit rows, level 0 included (the keys of its tiles at fixed slots)
+		hipLaunchKernelGGL(asym_theta_kernel, dim3((uint32_t)((m + kBlock / 16 - 1) / (kBlock / 16))), dim3(kBlock), 0, st,
+		                   d_queries, (uint32_t)m, (uint32_t)h->dim, (const float*)sp.tau, h->d_theta.as<int>(), h->d_qself.p);
+		const AsymTiles tiles = plan_asym_tiles(h->n, L.n_groups_sel * kRowsPerGroup, first, last, cap);
+		AsymParams ap{};
+		ap.base = h->d_base;
+		ap.n_rows = (uint32_t)h->n;
+		ap.n_tiles_sel = tiles.n_tiles_sel;
+		ap.tile_stride = tiles.tile_stride;
+		ap.n_qtiles = (uint32_t)((m + kHamTQ - 1) / kHamTQ);
+		ap.queries = d_queries;
+		ap.theta = h->d_theta.as<const int>();
+		ap.sumq = h->d_qself;
+		ap.tau_row = sp.tau_row;
+		ap.m = (uint32_t)m;
+		ap.cand_cnt = h->d_cnt;
+		ap.cand = h->d_cand;
+		ap.cap = cap;
+		ap.dim = (uint32_t)h->dim;
+		ap.level0 = first ? 1u : 0u;
+		ham_fixed = tiles.fixed;
+		// (one workgroup per CU is resident: rounds of `cus` workgroups, a stage of prologue each)
+		uint32_t gchunks = pick_row_chunks(ap.n_tiles_sel, ap.n_qtiles, (uint32_t)cus, 1.0, 1, 4096, 0, nullptr);
+		ap.tiles_per_block = (ap.n_tiles_sel + gchunks - 1) / gchunks;
+		gchunks = (ap.n_tiles_sel + ap.tiles_per_block - 1) / ap.tiles_per_block;
+		if (timed)
+			HIP_TRY(h, hipEventRecord(h->ev[h->ev_used][0], st));
+		hipLaunchKernelGGL(scan_asym_mfma_kernel, dim3(gchunks * ap.n_qtiles), dim3(kHamThreads), kAsymLdsBytes, st, ap);
+		h->stat_asym++;
+		passes = ap.n_qtiles;
+		kname = "scan_asym_mfma";
+		qt_used = kHamTQ;
 	} else if (ham_mfma) {
 		// packed-bit rows on the matrix cores, level 0 included (the keys of its tiles at fixed slots)
 		hipLaunchKernelGGL(ham_theta_kernel, dim3((uint32_t)((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d_queries,
@@ -2530,7 +2568,7 @@ int SearchPass::run_level(size_t li) {
 	sel.cand = h->d_cand;
 	sel.cand_cnt = first ? nullptr : h->d_cnt;
 	sel.fixed_count = (first && L.classmin_blocks) ? n_chunks * 16 : L.n_groups_sel * kRowsPerGroup;
-	if (ham_mfma)
+	if (ham_mfma || asym)
 		sel.fixed_count = ham_fixed;
 	sel.cap = cap;
 	sel.k = (uint32_t)k;
@@ -3113,6 +3151,8 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 			}
 	if (int_mode == kPlanB1Ham && dim <= kPlanHamMfmaMaxDim)
 		needs.push_back({(const void*)scan_hamming_mfma_kernel, (int)ham_mfma_lds_bytes((uint32_t)dim), "scan_hamming_mfma_kernel"});
+	if (int_mode == kPlanB1Ham)
+		needs.push_back({(const void*)scan_asym_mfma_kernel, (int)kAsymLdsBytes, "scan_asym_mfma_kernel"});
 	for (const auto& v : kGemmBf16)
 		if (v.d == dim)
 			needs.push_back({(const void*)v.scan, 2 * kGemmTB * dim * (int)sizeof(float), "scan_gemm_bf16x3_kernel"});
@@ -3769,6 +3809,70 @@ int expann_search(expann_index* h, const void* queries, size_t m, size_t k, uint
 	return EXPANN_OK;
 }
 
+// THE ASYMMETRIC RULE (include/expann_hip.h): the checks by value and kind first, before any device work
+static int asym_refusal(expann_index* h, const void* queries, size_t k, const uint64_t* ids) {
+	if (!queries || !ids)
+		return h->fail(EXPANN_ERR_INVALID_ARG, "NULL query/ids pointer");
+	if (k == 0)
+		return h->fail(EXPANN_ERR_INVALID_ARG, "k == 0");
+	const ScanPlan plan = plan_asym(plan_index(h), PlanCall{1, k, plan_start_cap(h->opt_cand_capacity, k, kMaxCap)});
+	if (plan.status != EXPANN_OK)
+		return h->fail(plan.status, plan.message);
+	if (!h->d_base)
+		return h->fail(EXPANN_ERR_NOT_BUILT, "search before build()");
+	return EXPANN_OK;
+}
+
+int expann_search_asym_i8_device(expann_index* h, const int8_t* d_queries, size_t m, size_t k, uint64_t* d_ids,
+                                 float* d_dists, void* stream) {
+	if (!h)
+		return EXPANN_ERR_INVALID_ARG;
+	const int refused = asym_refusal(h, d_queries, k, d_ids);
+	if (refused != EXPANN_OK)
+		return refused;
+	if (h->opt_async && !h->host_call)  // (deferred searches are not offered for packed-bit rows)
+		return h->fail(EXPANN_ERR_UNSUPPORTED, kB1NotOffered);
+	if (m == 0)
+		return EXPANN_OK;
+	HIP_TRY(h, hipSetDevice(h->device));
+	hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+	const int cus = num_cus(h->device);
+	for (size_t q0 = 0; q0 < m; q0 += kMaxQueriesPerPass) {
+		const size_t mm = std::min(kMaxQueriesPerPass, m - q0);
+		SearchPass pass{h, d_queries + q0 * (size_t)h->dim, mm, k, d_ids + q0 * k, d_dists ? d_dists + q0 * k : nullptr, st,
+		                false, cus, plan_start_cap(h->opt_cand_capacity, k, kMaxCap), ScanSel{nullptr, kHamTQ, "scan_asym_mfma"}};
+		pass.asym = true;
+		const int rc = pass.run();
+		if (rc != EXPANN_OK)
+			return rc;
+	}
+	return EXPANN_OK;
+}
+
+int expann_search_asym_i8(expann_index* h, const int8_t* queries, size_t m, size_t k, uint64_t* ids, float* dists) {
+	if (!h)
+		return EXPANN_ERR_INVALID_ARG;
+	const int refused = asym_refusal(h, queries, k, ids);
+	if (refused != EXPANN_OK || m == 0)
+		return refused;
+	HIP_TRY(h, hipSetDevice(h->device));
+	const size_t qbytes = m * (size_t)h->dim;
+	HIP_TRY(h, h->d_q.ensure(qbytes));
+	HIP_TRY(h, h->d_ids.ensure(sizeof(uint64_t) * m * k));
+	HIP_TRY(h, h->d_dists.ensure(sizeof(float) * m * k));
+	HIP_TRY(h, hipMemcpyAsync(h->d_q, queries, qbytes, hipMemcpyHostToDevice, h->stream));
+	h->host_call = true;
+	const int rc = expann_search_asym_i8_device(h, h->d_q.as<const int8_t>(), m, k, h->d_ids, h->d_dists, h->stream);
+	h->host_call = false;
+	if (rc != EXPANN_OK)
+		return rc;
+	HIP_TRY(h, hipMemcpyAsync(ids, h->d_ids, sizeof(uint64_t) * m * k, hipMemcpyDeviceToHost, h->stream));
+	if (dists)
+		HIP_TRY(h, hipMemcpyAsync(dists, h->d_dists, sizeof(float) * m * k, hipMemcpyDeviceToHost, h->stream));
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
+	return EXPANN_OK;
+}
+
 int expann_merge_topk_strided_device(int device, const uint64_t* d_in_ids, const float* d_in_dists,
                                      size_t ids_stride, size_t dists_stride, size_t n_lists, size_t m,
                                      size_t k, uint64_t* d_out_ids, float* d_out_dists, void* stream) {
@@ -3988,6 +4092,7 @@ int expann_get_stat(expann_index* h, const char* name, uint64_t* out) {
 	    {"base_capacity_rows", [](H h) -> uint64_t { return h->d_base ? h->capacity : h->reserved; }},
 	    {"hamming_mfma_launches", [](H h) { return h->stat_ham[0]; }},
 	    {"hamming_valu_launches", [](H h) { return h->stat_ham[1]; }},
+	    {"asym_mfma_launches", [](H h) { return h->stat_asym; }},
 	    {"copies_digest", [](H h) { return copies_digest(const_cast<expann_index*>(h)); }},
 	};
 	for (const auto& s : kStatTable)

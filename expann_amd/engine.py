@@ -180,6 +180,28 @@ class GpuBruteForceEngine:
             self._h, C.c_void_p(q_ptr), m, k, C.c_void_p(ids_ptr), C.c_void_p(dists_ptr),
             C.c_void_p(stream)))
 
+    def query_k_batch_asym(self, queries_int8, k):
+        """expann_search_asym_i8 (dtype="b1" only): int8 queries [m, dim], one signed byte per dimension, against
+        the rows' signs s_j = 2 b_j - 1.  (ids[m,k] uint64, dists[m,k] float32) with dists = -sum_j q_j s_j, an
+        exact integer, ascending by (score, id) and padded as query_k_batch pads.  The array must be int8 of shape
+        [m, dim]: nothing is cast."""
+        queries = np.asarray(queries_int8)
+        if queries.dtype != np.int8 or queries.ndim != 2 or queries.shape[1] != self.dim:
+            raise ValueError(f"queries must be int8 [m, {self.dim}]")
+        queries = np.ascontiguousarray(queries)
+        m = queries.shape[0]
+        ids = np.empty((m, k), dtype=np.uint64)
+        dists = np.empty((m, k), dtype=np.float32)
+        _lib.check(self._h, self._L.expann_search_asym_i8(self._h, queries.ctypes.data, m, k,
+                                                          ids.ctypes.data, dists.ctypes.data))
+        return ids, dists
+
+    def search_asym_device(self, q_ptr, m, k, ids_ptr, dists_ptr, stream=0):
+        """expann_search_asym_i8_device: int8 queries [m, dim] and the outputs are device pointers; returns after
+        `stream` has drained."""
+        _lib.check(self._h, self._L.expann_search_asym_i8_device(
+            self._h, C.c_void_p(q_ptr), m, k, C.c_void_p(ids_ptr), C.c_void_p(dists_ptr), C.c_void_p(stream)))
+
     def range_search(self, queries, radius, max_results):
         """expann_range_search: every row with score <= radius (a scalar, or an array [m] of per-query radii; for
         the inner product the score is -dot).  Returns (ids[m, max_results] uint64, dists[m, max_results] float32,
@@ -276,6 +298,7 @@ class GpuBruteForceEngine:
         "filter_active" (0 / 1) and "filter_rows" (rows the row filter allows; n when none is set);
         "base_bytes" (device bytes of the rows themselves: n * dim * element size);
         "hamming_mfma_launches", "hamming_valu_launches" (packed-bit rows: scan launches of either form since create);
+        "asym_mfma_launches" (packed-bit rows, int8 queries: launches of scan_asym_mfma_kernel since create);
         "groups_active", "group_count", and of the last grouped search "group_list_queries", "group_filter_queries",
         "group_any_queries", "group_pad_queries", "group_filter_passes";
         of the last range search "range_list_queries", "range_topk_queries", "range_retries";

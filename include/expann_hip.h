@@ -59,7 +59,8 @@ enum expann_dtype {
  * Served: expann_add, expann_build, expann_set_base_device (with id_offset), expann_size, expann_search and
  * expann_search_device for 1 <= k <= 8192 with the synchronous overflow check, expann_get_stat ("base_bytes" = n * dim
  * / 8; "hamming_mfma_launches" / "hamming_valu_launches" = scan launches of either form since create) and
- * expann_set_option.  "scan_kernel": 0 = auto, 1 = the VALU form (xor + popcount), 2 = the form on the int8 matrix
+ * expann_set_option; and, with int8 queries, expann_search_asym_i8 / _device (THE ASYMMETRIC RULE, below).
+ * "scan_kernel": 0 = auto, 1 = the VALU form (xor + popcount), 2 = the form on the int8 matrix
  * cores (dim <= 1024; EXPANN_ERR_UNSUPPORTED beyond), any other value is refused by the next search
  * (EXPANN_ERR_INVALID_ARG); ids and distances are the same for each choice.  Both forms are exact under ties.
  * NOT offered, each EXPANN_ERR_UNSUPPORTED with a message and the handle untouched: the row filter and row groups,
@@ -158,6 +159,28 @@ int expann_search_device(expann_index* h, const void* d_queries, size_t m, size_
  * different stream than the outstanding deferred ones first waits (on the host) until those have
  * drained; deferred searches overlap with each other only in stream order. */
 int expann_sync(expann_index* h);
+
+/* Packed-bit rows scored against int8 queries ("asymmetric" search, binary rescoring): the rows keep 1 bit per
+ * dimension, the queries keep their magnitudes.
+ * THE ASYMMETRIC RULE.  On a built handle of EXPANN_DTYPE_B1 rows (dim bits, any multiple of 64 from 64 to 4096) and
+ * queries int8_t [m][dim], one signed byte per dimension (16-byte aligned on the device), with b_j the row's bit j,
+ *     score(q, b) = - sum_j q_j (2 b_j - 1) = sum_j q_j - 2 sum_j q_j b_j ,
+ * an integer returned as float (exact: |score| <= 128 * 4096 = 2^19).  A smaller score is better, as -dot is for
+ * EXPANN_METRIC_IP; ties go to the lower id; lists shorter than k are padded with UINT64_MAX / +inf; 1 <= k <= 8192.
+ * A query of +-1 bytes only scores 2 * hamming - dim: with q_j = 2 c_j - 1 the ids are those of expann_search on the
+ * packed code c.
+ * Refused: a handle of any other dtype EXPANN_ERR_UNSUPPORTED; a handle that is not built EXPANN_ERR_NOT_BUILT; NULL
+ * queries / ids or k == 0 EXPANN_ERR_INVALID_ARG; k > 8192 EXPANN_ERR_UNSUPPORTED -- the NULL and kind checks before
+ * any device work.  The _device form takes device pointers, is enqueued on `stream` (NULL = the index's own) and
+ * returns after the stream has drained, as expann_search_device does; id_offset (expann_set_base_device) is added to
+ * every id.  NOT offered: deferred searches ("async_search" = 1: EXPANN_ERR_UNSUPPORTED), the row filter and row
+ * groups, range search, the expann_sharded_* handles.
+ * One kernel on the int8 matrix cores serves every m >= 1 and every dim (scan_asym_mfma_kernel; there
+ * is no VALU form for small batches); "scan_kernel" is not read.  expann_get_stat "asym_mfma_launches" = its
+ * launches since create. */
+int expann_search_asym_i8(expann_index* h, const int8_t* queries, size_t m, size_t k, uint64_t* ids, float* dists);
+int expann_search_asym_i8_device(expann_index* h, const int8_t* d_queries, size_t m, size_t k, uint64_t* d_ids,
+                                 float* d_dists, void* stream);
 
 /* k-way merge of per-shard results after an all-gather (RCCL): in_ids/in_dists are
  * [n_lists][m][k], each row ascending by (score, id) and padded as above; out is [m][k].
