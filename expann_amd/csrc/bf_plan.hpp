@@ -15,6 +15,7 @@ namespace expann {
 // 8-bit row modes (IntMode of scan_int8.hpp; -1: float rows)
 constexpr int kPlanU8L2 = 0, kPlanI8L2 = 1, kPlanI8L2Ref = 2, kPlanI8IP = 3, kPlanI16L2Ref = 4;
 constexpr int kPlanB1Ham = 5;       // packed-bit rows under the Hamming distance (scan_hamming.hpp); dim counts bits
+constexpr int kPlanI4 = 6;          // 4-bit rows against int8 queries (scan_i4.hpp), inner product or L2 by the metric
 constexpr int kPlanMaxDim = 4096;  // kMaxAnyDim
 
 // ---- the dims each family is compiled for (the variant tables of expann_hip.hip are checked against these) ----
@@ -224,6 +225,8 @@ constexpr int direct_tile(const PlanIndex& x, size_t m) {
 	}
 	if (x.int_mode == kPlanB1Ham)
 		return x.dim >= 64 && x.dim <= kPlanMaxDim && x.dim % 64 == 0 ? pick_tile(&kScanB1Tiles, m, x.query_tile) : 0;
+	if (x.int_mode == kPlanI4)  // (no direct scan: the one form's query tile, kHamTQ)
+		return x.dim >= 64 && x.dim <= kPlanMaxDim && x.dim % 64 == 0 ? 64 : 0;
 	if (any_dim_i8(x.dim, x.int_mode))
 		return pick_tile(&kScanI8AnyTiles, m, x.query_tile);
 	return pick_tile(x.int_mode == kPlanI16L2Ref ? tiles_of(kScanI16Tiles, x.dim) : tiles_of(kScanI8Tiles, x.dim), m,
@@ -324,9 +327,35 @@ constexpr AsymTiles plan_asym_tiles(size_t n, uint32_t sel_rows, bool first, boo
 	return AsymTiles{sel, stride, (uint64_t)sel * T < cap ? sel * T : cap};
 }
 
+// 4-bit rows (EXPANN_DTYPE_I4, THE I4 RULE): one form, scan_i4_mfma_kernel (scan_i4.hpp), for every m >= 1 and every
+// dim the rows can have, under both metrics; like plan_asym's it scans every level of the ladder and keeps (score, row)
+// <= the proven threshold key: no sampled pass, no speculation, no tie restart.  "scan_kernel" is not read.  Its tiles
+// are the asymmetric search's: plan_i4_tiles.
+constexpr const char* kRefuseI4Rows = "scan_i4: EXPANN_DTYPE_I4 rows under EXPANN_METRIC_IP or EXPANN_METRIC_L2 only";
+constexpr const char* kRefuseI4K = "EXPANN_DTYPE_I4 rows: k is at most 8192 (half the longest candidate list)";
+inline ScanPlan plan_i4(const PlanIndex& x, const PlanCall& c) {
+	ScanPlan p;
+	p.direct_tq = direct_tile(x, c.m);
+	if (x.int_mode != kPlanI4 || x.dtype != EXPANN_DTYPE_I4 || (x.metric != EXPANN_METRIC_IP && x.metric != EXPANN_METRIC_L2)) {
+		p.status = EXPANN_ERR_UNSUPPORTED;
+		p.message = kRefuseI4Rows;
+	} else if (c.k > kPlanAsymMaxK || (size_t)c.cap < 2 * c.k) {
+		p.status = EXPANN_ERR_UNSUPPORTED;
+		p.message = kRefuseI4K;
+	} else {
+		p.family = ScanFamily::kHamming;  // (the threshold ladder on the int8 matrix cores; the row mode names the kernel)
+	}
+	return p;
+}
+constexpr AsymTiles plan_i4_tiles(size_t n, uint32_t sel_rows, bool first, bool last, uint32_t cap) {
+	return plan_asym_tiles(n, sel_rows, first, last, cap);  // (the same 512-row tiles and fixed slots)
+}
+
 inline ScanPlan plan_scan(const PlanIndex& x, const PlanCall& c, const PlanAttempt& a) {
 	if (x.int_mode == kPlanB1Ham)
 		return plan_hamming(x, c, a);
+	if (x.int_mode == kPlanI4)
+		return plan_i4(x, c);
 	ScanPlan p;
 	const long sk = x.scan_kernel;
 	const bool flt = x.int_mode < 0, f32 = x.dtype == EXPANN_DTYPE_F32, l2 = x.metric == EXPANN_METRIC_L2;

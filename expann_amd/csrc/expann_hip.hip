@@ -39,6 +39,7 @@
 #include "scan_int8_any.hpp"
 #include "scan_hamming.hpp"
 #include "scan_asym.hpp"
+#include "scan_i4.hpp"
 #include "filter_rows.hpp"
 #include "scan_groups.hpp"
 #include "append_rows.hpp"
@@ -87,13 +88,19 @@ struct Config : Options {
 	size_t q_elem = 4;  // bytes per query element at the ABI (f32 for F32/U8 rows, int8 for I8)
 	int int_mode = -1;  // IntMode for 8-bit rows
 	bool strict_u8 = false;          // (on the shadow) non-8-bit / fractional queries: hand back, no error
-	// bytes of a stored row and of a query at the ABI (packed-bit rows: dim counts bits, both sides are dim / 8 bytes)
-	size_t row_bytes() const { return int_mode == kPlanB1Ham ? (size_t)dim / 8 : (size_t)dim * elem; }
+	// bytes of a stored row and of a query at the ABI (packed-bit rows: dim counts bits, both sides are dim / 8 bytes;
+	// 4-bit rows: dim / 2 bytes against int8 queries of dim bytes)
+	size_t row_bytes() const { return int_mode == kPlanB1Ham ? (size_t)dim / 8 : (int_mode == kPlanI4 ? (size_t)dim / 2 : (size_t)dim * elem); }
 	size_t query_bytes() const { return int_mode == kPlanB1Ham ? (size_t)dim / 8 : (size_t)dim * q_elem; }
 };
 inline bool b1_rows(const Config* h) { return h->int_mode == kPlanB1Ham; }
 constexpr const char* kB1NotOffered =
     "EXPANN_DTYPE_B1 rows: add / build / set_base_device and expann_search / expann_search_device only";
+inline bool i4_rows(const Config* h) { return h->int_mode == kPlanI4; }
+constexpr const char* kI4NotOffered =
+    "EXPANN_DTYPE_I4 rows: add / build / set_base_device and expann_search / expann_search_device only";
+// the entry points neither kind of packed rows is offered: the refusal's text, or nullptr
+inline const char* packed_not_offered(const Config* h) { return b1_rows(h) ? kB1NotOffered : (i4_rows(h) ? kI4NotOffered : nullptr); }
 
 // the rows: staged on the host until build(), then on the device -- the handle's own copy, or the caller's memory
 // (expann_set_base_device)
@@ -154,6 +161,7 @@ struct OtherCopies : U8Shadow {
 	MaybeOwnedPtr d_base_i8q;        // padded int8 copy of an 8-bit index (uint8 rows ^ 0x80) or alias of d_base
 	DevPtr<int> d_bp_i8q;            // [n padded] floor(bias/2), scan_gemm_i8q.hpp
 	DevPtr<int> d_popb;              // [n] popcount per row (packed-bit rows, matrix-core form), built lazily
+	DevPtr<int> d_i4_rowterm;        // [n] sum b^2 per row (4-bit rows under L2), made when the rows arrive
 };
 // all that is derived from the rows: forgotten together when the rows are replaced
 struct RowCopies : F16Copy, OtherCopies {};
@@ -271,6 +279,7 @@ struct Stats {
 	uint64_t stat_remove[4] = {0, 0, 0, 0};
 	uint64_t stat_ham[2] = {0, 0};   // launches of scan_hamming_mfma_kernel / scan_hamming_valu_kernel since create
 	uint64_t stat_asym = 0;          // launches of scan_asym_mfma_kernel since create
+	uint64_t stat_i4 = 0;            // launches of scan_i4_mfma_kernel since create
 };
 
 // streams, events, profiling, statistics, the last error
@@ -2154,6 +2163,7 @@ struct SearchPass {
 	const DirectF16Variant* dv = nullptr;  // fp16 form: scan_direct_f16 serves the last level and the sampled pass
 	bool ham_mfma = false;      // packed-bit rows: scan_hamming_mfma_kernel scans every level (else the VALU form)
 	bool asym = false;          // the query kind: int8 queries [m][dim] on packed-bit rows, scan_asym_mfma_kernel at every level
+	bool i4 = false;            // 4-bit rows: scan_i4_mfma_kernel at every level
 	bool i8f = false;          // the int8 filter runs the full scan (fp16 prelude, scan_gemm_i8f.hpp)
 	bool i8f_ready = false;     // its thresholds of this attempt are written
 	bool i8f_ran = false;       // the last level of this attempt ran it
@@ -2192,6 +2202,7 @@ int SearchPass::choose_kernels() {
 	if (plan.status != EXPANN_OK)
 		return h->fail(plan.status, plan.message);
 	ham_mfma = b1_rows(h) && plan.family == ScanFamily::kHamming && !asym;
+	i4 = i4_rows(h);
 	if (ham_mfma && !h->d_popb) {  // the row term pop(b)
 		HIP_TRY(h, hipMalloc(&h->d_popb, sizeof(int) * h->n));
 		hipLaunchKernelGGL(ham_popcount_kernel, dim3((uint32_t)((h->n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
@@ -2507,6 +2518,44 @@ int SearchPass::run_level(size_t li) {
 		passes = ap.n_qtiles;
 		kname = "scan_asym_mfma";
 		qt_used = kHamTQ;
+	} else if (i4) {
+		// 4-bit rows, level 0 included (the keys of its tiles at fixed slots): the permuted queries and the per-query
+		// terms, then the scan
+		HIP_TRY(h, grow_ws(h, h->d_q8f, m * (size_t)h->dim));
+		hipLaunchKernelGGL(i4_theta_kernel, dim3((uint32_t)((m + kBlock / 16 - 1) / (kBlock / 16))), dim3(kBlock), 0, st,
+		                   d_queries, (uint32_t)m, (uint32_t)h->dim, ip ? 0 : 1, (const float*)sp.tau, (void*)h->d_q8f,
+		                   h->d_theta.as<int>(), h->d_qself.p);
+		const AsymTiles tiles = plan_i4_tiles(h->n, L.n_groups_sel * kRowsPerGroup, first, last, cap);
+		I4Params xp{};
+		xp.base = h->d_base;
+		xp.rowterm = ip ? nullptr : h->d_i4_rowterm.p;
+		xp.n_rows = (uint32_t)h->n;
+		xp.n_tiles_sel = tiles.n_tiles_sel;
+		xp.tile_stride = tiles.tile_stride;
+		xp.n_qtiles = (uint32_t)((m + kHamTQ - 1) / kHamTQ);
+		xp.queries = h->d_q8f;
+		xp.theta = h->d_theta.as<const int>();
+		xp.qterm = h->d_qself;
+		xp.tau = sp.tau;
+		xp.tau_row = sp.tau_row;
+		xp.m = (uint32_t)m;
+		xp.cand_cnt = h->d_cnt;
+		xp.cand = h->d_cand;
+		xp.cap = cap;
+		xp.dim = (uint32_t)h->dim;
+		xp.level0 = first ? 1u : 0u;
+		ham_fixed = tiles.fixed;
+		// (one workgroup per CU is resident: rounds of `cus` workgroups, a stage of prologue each)
+		uint32_t gchunks = pick_row_chunks(xp.n_tiles_sel, xp.n_qtiles, (uint32_t)cus, 1.0, 1, 4096, 0, nullptr);
+		xp.tiles_per_block = (xp.n_tiles_sel + gchunks - 1) / gchunks;
+		gchunks = (xp.n_tiles_sel + xp.tiles_per_block - 1) / xp.tiles_per_block;
+		if (timed)
+			HIP_TRY(h, hipEventRecord(h->ev[h->ev_used][0], st));
+		hipLaunchKernelGGL(scan_i4_mfma_kernel, dim3(gchunks * xp.n_qtiles), dim3(kHamThreads), kI4LdsBytes, st, xp);
+		h->stat_i4++;
+		passes = xp.n_qtiles;
+		kname = "scan_i4_mfma";
+		qt_used = kHamTQ;
 	} else if (ham_mfma) {
 		// packed-bit rows on the matrix cores, level 0 included (the keys of its tiles at fixed slots)
 		hipLaunchKernelGGL(ham_theta_kernel, dim3((uint32_t)((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d_queries,
@@ -2568,7 +2617,7 @@ int SearchPass::run_level(size_t li) {
 	sel.cand = h->d_cand;
 	sel.cand_cnt = first ? nullptr : h->d_cnt;
 	sel.fixed_count = (first && L.classmin_blocks) ? n_chunks * 16 : L.n_groups_sel * kRowsPerGroup;
-	if (ham_mfma || asym)
+	if (ham_mfma || asym || i4)
 		sel.fixed_count = ham_fixed;
 	sel.cap = cap;
 	sel.k = (uint32_t)k;
@@ -2963,7 +3012,9 @@ int search_pass(expann_index* h, const void* d_queries, size_t m, size_t k, uint
 		if (const ScanI8Variant* v = find_scan_i8(h->dim, h->int_mode, plan.direct_tq))
 			svs = ScanSel{v->fn, v->tq, v->name};
 	}
-	if (!svs.fn)
+	if (i4_rows(h))  // (one form, no direct scan: SearchPass::i4 names the kernel)
+		svs = ScanSel{nullptr, kHamTQ, "scan_i4_mfma"};
+	if (!svs.fn && !i4_rows(h))
 		return h->fail(EXPANN_ERR_UNSUPPORTED,
 		               "no scan kernel for dim " + std::to_string(h->dim) +
 		                   " / query_tile " + std::to_string(h->opt_query_tile));
@@ -3058,6 +3109,12 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 		}
 	} else if (dtype == EXPANN_DTYPE_B1) {  // (dim counts bits; the 8-bit rows' dim rules below)
 		int_mode = kPlanB1Ham;
+	} else if (dtype == EXPANN_DTYPE_I4) {  // (THE I4 RULE; the 8-bit rows' dim rules below)
+		if (metric != EXPANN_METRIC_IP && metric != EXPANN_METRIC_L2) {
+			g_create_error = "EXPANN_DTYPE_I4 rows support EXPANN_METRIC_IP and EXPANN_METRIC_L2 only";
+			return EXPANN_ERR_INVALID_ARG;
+		}
+		int_mode = kPlanI4;
 	} else {
 		g_create_error = "unknown dtype";
 		return EXPANN_ERR_INVALID_ARG;
@@ -3101,7 +3158,7 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 	h->metric = metric;
 	h->device = device;
 	h->elem = (dtype == EXPANN_DTYPE_F32) ? 4 : ((dtype == EXPANN_DTYPE_I16 || dtype == EXPANN_DTYPE_F16) ? 2 : 1);
-	h->q_elem = (dtype == EXPANN_DTYPE_I8) ? 1 : (dtype == EXPANN_DTYPE_I16 ? 2 : 4);
+	h->q_elem = (dtype == EXPANN_DTYPE_I8 || dtype == EXPANN_DTYPE_I4) ? 1 : (dtype == EXPANN_DTYPE_I16 ? 2 : 4);
 	h->int_mode = int_mode;
 	static_cast<Options&>(*h) = options_from_env();
 	if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&h->stream) != hipSuccess) {
@@ -3153,6 +3210,8 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 		needs.push_back({(const void*)scan_hamming_mfma_kernel, (int)ham_mfma_lds_bytes((uint32_t)dim), "scan_hamming_mfma_kernel"});
 	if (int_mode == kPlanB1Ham)
 		needs.push_back({(const void*)scan_asym_mfma_kernel, (int)kAsymLdsBytes, "scan_asym_mfma_kernel"});
+	if (int_mode == kPlanI4)
+		needs.push_back({(const void*)scan_i4_mfma_kernel, (int)kI4LdsBytes, "scan_i4_mfma_kernel"});
 	for (const auto& v : kGemmBf16)
 		if (v.d == dim)
 			needs.push_back({(const void*)v.scan, 2 * kGemmTB * dim * (int)sizeof(float), "scan_gemm_bf16x3_kernel"});
@@ -3180,6 +3239,20 @@ void expann_destroy(expann_index* h) {
 
 const char* expann_last_error(const expann_index* h) {
 	return h ? h->err.c_str() : g_create_error.c_str();
+}
+
+// 4-bit rows under L2: the row term sum b^2 of scan_i4.hpp, made when the rows arrive (the handle's stream, waited
+// for: a search may run on any stream).  The inner product has no row term.
+static int make_i4_rowterm(expann_index* h) {
+	if (h->metric != EXPANN_METRIC_L2)
+		return EXPANN_OK;
+	HIP_TRY(h, hipSetDevice(h->device));
+	HIP_TRY(h, hipMalloc(&h->d_i4_rowterm, sizeof(int) * h->n));
+	hipLaunchKernelGGL(i4_rowterm_kernel, dim3((uint32_t)((h->n + kBlock - 1) / kBlock)), dim3(kBlock), 0, h->stream,
+	                   (const void*)h->d_base, (uint32_t)h->n, (uint32_t)h->dim, h->d_i4_rowterm.p);
+	HIP_TRY(h, hipGetLastError());
+	HIP_TRY(h, hipStreamSynchronize(h->stream));
+	return EXPANN_OK;
 }
 
 int expann_add(expann_index* h, const void* rows, size_t n) {
@@ -3216,6 +3289,8 @@ int expann_build(expann_index* h) {
 	HIP_TRY(h, hipMemcpy(h->d_base, h->staging.data(), h->staging.size(), hipMemcpyHostToDevice));
 	h->n = h->n_staged;
 	std::vector<unsigned char>().swap(h->staging);
+	if (i4_rows(h))
+		return make_i4_rowterm(h);
 	// the fp16 copy every fp32 search of a built dim filters through: made here, inside the
 	// reference's timed build span (basic_bench.h:63-71), not inside the first query
 	if (f16_copy_at_build(plan_index(h)))
@@ -3239,6 +3314,8 @@ int expann_set_base_device(expann_index* h, const void* d_rows, size_t n, uint64
 	h->n = n;
 	h->capacity = 0;
 	h->id_offset = id_offset;
+	if (i4_rows(h))
+		return make_i4_rowterm(h);
 	return EXPANN_OK;
 }
 
@@ -3361,8 +3438,8 @@ uint64_t copies_digest(expann_index* h) {
 int append_rows(expann_index* h, const void* rows, size_t n_new, bool on_device, hipStream_t user_st) {
 	if (!h)
 		return EXPANN_ERR_INVALID_ARG;
-	if (b1_rows(h))
-		return h->fail(EXPANN_ERR_UNSUPPORTED, kB1NotOffered);
+	if (const char* refusal = packed_not_offered(h))
+		return h->fail(EXPANN_ERR_UNSUPPORTED, refusal);
 	const AppendState state = append_state(h, rows != nullptr);
 	AppendPlan plan = plan_append(state, n_new, 0.0f);  // (the status and the capacity: no device call before them)
 	if (plan.status != EXPANN_OK)
@@ -3457,8 +3534,8 @@ int expann_append_device(expann_index* h, const void* d_rows, size_t n, void* st
 int expann_reserve(expann_index* h, size_t n_rows) {
 	if (!h)
 		return EXPANN_ERR_INVALID_ARG;
-	if (b1_rows(h))
-		return h->fail(EXPANN_ERR_UNSUPPORTED, kB1NotOffered);
+	if (const char* refusal = packed_not_offered(h))
+		return h->fail(EXPANN_ERR_UNSUPPORTED, refusal);
 	const AppendPlan plan = plan_reserve(append_state(h, true), n_rows);
 	if (plan.status != EXPANN_OK)
 		return h->fail(plan.status, plan.message);
@@ -3597,8 +3674,8 @@ int remove_rows(expann_index* h, const uint64_t* ids, size_t n_ids, bool on_devi
                 size_t* n_removed) {
 	if (!h)
 		return EXPANN_ERR_INVALID_ARG;
-	if (b1_rows(h))
-		return h->fail(EXPANN_ERR_UNSUPPORTED, kB1NotOffered);
+	if (const char* refusal = packed_not_offered(h))
+		return h->fail(EXPANN_ERR_UNSUPPORTED, refusal);
 	if (from_filter && !h->filter_on)
 		return h->fail(EXPANN_ERR_INVALID_ARG, "compact_row_filter: no row filter in force");
 	const AppendState state = append_state(h, from_filter || ids != nullptr);
@@ -3664,8 +3741,8 @@ int expann_search_device(expann_index* h, const void* d_queries, size_t m, size_
 		return EXPANN_OK;
 	if (!d_queries || !d_ids)
 		return h->fail(EXPANN_ERR_INVALID_ARG, "NULL query/ids pointer");
-	if (b1_rows(h) && h->opt_async && !h->host_call)  // (deferred searches are not offered for packed-bit rows)
-		return h->fail(EXPANN_ERR_UNSUPPORTED, kB1NotOffered);
+	if (packed_not_offered(h) && h->opt_async && !h->host_call)  // (deferred searches are not offered for packed-bit / 4-bit rows)
+		return h->fail(EXPANN_ERR_UNSUPPORTED, packed_not_offered(h));
 	HIP_TRY(h, hipSetDevice(h->device));
 	hipStream_t st = stream ? (hipStream_t)stream : h->stream;
 	// all searches of a handle share one workspace: deferred searches still running on ANOTHER
@@ -3919,8 +3996,8 @@ int expann_score_ids(expann_index* h, const void* query, const uint64_t* ids, si
                      float cutoff, uint64_t* kept_ids, float* kept_scores, size_t* n_kept) {
 	if (!h)
 		return EXPANN_ERR_INVALID_ARG;
-	if (b1_rows(h))
-		return h->fail(EXPANN_ERR_UNSUPPORTED, kB1NotOffered);
+	if (const char* refusal = packed_not_offered(h))
+		return h->fail(EXPANN_ERR_UNSUPPORTED, refusal);
 	if (!h->d_base)
 		return h->fail(EXPANN_ERR_NOT_BUILT, "score_ids before build()");
 	if (!n_kept || (n_ids && (!query || !ids || !kept_ids || !kept_scores)))
@@ -4093,6 +4170,7 @@ int expann_get_stat(expann_index* h, const char* name, uint64_t* out) {
 	    {"hamming_mfma_launches", [](H h) { return h->stat_ham[0]; }},
 	    {"hamming_valu_launches", [](H h) { return h->stat_ham[1]; }},
 	    {"asym_mfma_launches", [](H h) { return h->stat_asym; }},
+	    {"i4_mfma_launches", [](H h) { return h->stat_i4; }},
 	    {"copies_digest", [](H h) { return copies_digest(const_cast<expann_index*>(h)); }},
 	};
 	for (const auto& s : kStatTable)

@@ -14,9 +14,10 @@ import numpy as np
 from . import _lib
 
 _NP_DTYPE = {_lib.DTYPE_F32: np.float32, _lib.DTYPE_U8: np.uint8, _lib.DTYPE_I8: np.int8,
-             _lib.DTYPE_I16: np.int16, _lib.DTYPE_F16: np.float16, _lib.DTYPE_B1: np.uint8}
+             _lib.DTYPE_I16: np.int16, _lib.DTYPE_F16: np.float16, _lib.DTYPE_B1: np.uint8,
+             _lib.DTYPE_I4: np.uint8}
 _DTYPE = {"f32": _lib.DTYPE_F32, "u8": _lib.DTYPE_U8, "i8": _lib.DTYPE_I8, "i16": _lib.DTYPE_I16,
-          "f16": _lib.DTYPE_F16, "b1": _lib.DTYPE_B1}
+          "f16": _lib.DTYPE_F16, "b1": _lib.DTYPE_B1, "i4": _lib.DTYPE_I4}
 # row types whose queries are fp32 at the ABI (the others take queries of the rows' own type)
 _F32_QUERIES = (_lib.DTYPE_F32, _lib.DTYPE_U8, _lib.DTYPE_F16)
 
@@ -31,6 +32,25 @@ def pack_row_filter(allow):
     return out.view("<u4").astype(np.uint32)
 
 
+def pack_i4(values):
+    """int8 values [n, dim] in [-8, 7] (dim even) as the rows of dtype="i4": uint8 [n, dim / 2], element 2 j in the
+    low nibble of byte j and element 2 j + 1 in the high nibble, two's complement.  A pure function."""
+    v = np.asarray(values)
+    if v.ndim != 2 or v.shape[1] % 2 or v.dtype != np.int8 or v.min(initial=0) < -8 or v.max(initial=0) > 7:
+        raise ValueError("values must be int8 [n, dim] in [-8, 7] with an even dim")
+    u = v.view(np.uint8) & 0x0F
+    return np.ascontiguousarray(u[:, 0::2] | (u[:, 1::2] << 4))
+
+
+def unpack_i4(rows):
+    """The inverse of pack_i4: uint8 [n, dim / 2] to int8 [n, dim] in [-8, 7]."""
+    r = np.asarray(rows, dtype=np.uint8)
+    out = np.empty((r.shape[0], 2 * r.shape[1]), dtype=np.int8)
+    out[:, 0::2] = ((r & 0x0F) ^ 8).astype(np.int8) - 8
+    out[:, 1::2] = ((r >> 4) ^ 8).astype(np.int8) - 8
+    return out
+
+
 class GpuBruteForceEngine:
     """Exact k-NN by a full scan on one MI355X (drop-in for brute_force_engine<float>).
 
@@ -40,7 +60,13 @@ class GpuBruteForceEngine:
 
     dtype="b1" with metric="hamming": dim counts bits; rows and queries are uint8 arrays [*, dim / 8] as
     numpy.packbits(..., bitorder="little") packs them, and the distances are the numbers of differing bits.
-    Add, build, size and the searches only (EXPANN_DTYPE_B1, include/expann_hip.h)."""
+    Add, build, size and the searches only (EXPANN_DTYPE_B1, include/expann_hip.h).
+
+    dtype="i4" with metric "ip" or "l2": 4-bit rows, half the device memory of "i8".  Rows are uint8 arrays
+    [n, dim / 2] as pack_i4 packs int8 values in [-8, 7]; queries are int8 [m, dim].  Scores are exact integers
+    returned as float32 -- for "ip" at every dim and for "l2" up to dim 896 bit for bit those of an "i8" engine over
+    unpack_i4(rows).  Add, build, set_base_device, size and query_k_batch / search_device only (THE I4 RULE,
+    include/expann_hip.h); ShardedBruteForceEngine and the C++ engine classes do not take the dtype."""
 
     def __init__(self, dim, metric="l2", dtype="f32", device=0):
         self._L = _lib.load()
@@ -48,7 +74,9 @@ class GpuBruteForceEngine:
         self.metric = {"l2": _lib.METRIC_L2, "ip": _lib.METRIC_IP,
                        "l2_i8_refcompat": _lib.METRIC_L2_I8_REFCOMPAT, "hamming": _lib.METRIC_HAMMING}[metric]
         self.dtype = _DTYPE[dtype]
-        self._cols = self.dim // 8 if self.dtype == _lib.DTYPE_B1 else self.dim  # elements of a row at the ABI
+        # elements of a row, and of a query, at the ABI
+        self._cols = {_lib.DTYPE_B1: self.dim // 8, _lib.DTYPE_I4: self.dim // 2}.get(self.dtype, self.dim)
+        self._qcols = self.dim if self.dtype == _lib.DTYPE_I4 else self._cols
         self.device = int(device)
         self._metric_name, self._dtype_name = metric, dtype
         h = C.c_void_p()
@@ -141,10 +169,10 @@ class GpuBruteForceEngine:
         """(ids[m,k] uint64, dists[m,k] float32); short rows padded with 2^64-1 / +inf.
         groups: a uint32 array [m] (host) -- query i returns only rows of the group it names
         (expann_search_grouped after set_row_groups; _lib.GROUP_ANY = every row)."""
-        qdt = np.float32 if self.dtype in _F32_QUERIES else _NP_DTYPE[self.dtype]
+        qdt = np.float32 if self.dtype in _F32_QUERIES else (np.int8 if self.dtype == _lib.DTYPE_I4 else _NP_DTYPE[self.dtype])
         queries = np.ascontiguousarray(queries, dtype=qdt)
-        if queries.ndim != 2 or queries.shape[1] != self._cols:
-            raise ValueError(f"queries must be [m, {self._cols}]")
+        if queries.ndim != 2 or queries.shape[1] != self._qcols:
+            raise ValueError(f"queries must be [m, {self._qcols}]")
         m = queries.shape[0]
         ids = np.empty((m, k), dtype=np.uint64)
         dists = np.empty((m, k), dtype=np.float32)
@@ -299,6 +327,7 @@ class GpuBruteForceEngine:
         "base_bytes" (device bytes of the rows themselves: n * dim * element size);
         "hamming_mfma_launches", "hamming_valu_launches" (packed-bit rows: scan launches of either form since create);
         "asym_mfma_launches" (packed-bit rows, int8 queries: launches of scan_asym_mfma_kernel since create);
+        "i4_mfma_launches" (4-bit rows: launches of scan_i4_mfma_kernel since create);
         "groups_active", "group_count", and of the last grouped search "group_list_queries", "group_filter_queries",
         "group_any_queries", "group_pad_queries", "group_filter_passes";
         of the last range search "range_list_queries", "range_topk_queries", "range_retries";

@@ -48,8 +48,31 @@ enum expann_dtype {
 	                       * dim 64 or 128; queries int16                            */
 	EXPANN_DTYPE_F16 = 4, /* IEEE binary16 rows, see below (appended; EXPANN_ABI_VERSION stays 2:
 	                       * nothing that existed changed)                            */
-	EXPANN_DTYPE_B1 = 5   /* packed bits under EXPANN_METRIC_HAMMING, see below (appended likewise) */
+	EXPANN_DTYPE_B1 = 5,  /* packed bits under EXPANN_METRIC_HAMMING, see below (appended likewise) */
+	EXPANN_DTYPE_I4 = 6   /* 4-bit rows against int8 queries, THE I4 RULE below (appended likewise) */
 };
+/* EXPANN_DTYPE_I4: 4-bit scalar-quantised rows, half the bytes of EXPANN_DTYPE_I8, scored against int8 queries.
+ * THE I4 RULE.  `dim` counts elements: any multiple of 64 from 64 to 4096 (not a multiple of 64:
+ * EXPANN_ERR_INVALID_ARG; over 4096: EXPANN_ERR_UNSUPPORTED; both before the device is touched).  A row is dim / 2
+ * bytes, [n][dim / 2]; element 2 j is the low nibble of byte j and element 2 j + 1 the high nibble, each a
+ * two's-complement value in [-8, 7].  Queries are int8_t [m][dim], one signed byte per element, 16-byte aligned on the
+ * device; rows adopted by expann_set_base_device must be 16-byte aligned too.
+ * Metrics: EXPANN_METRIC_IP (score = -sum q_j b_j) and EXPANN_METRIC_L2 (score = sum (q_j - b_j)^2); anything else is
+ * EXPANN_ERR_INVALID_ARG from expann_create.  The score is computed as an exact int32 and reported and ranked as
+ * (float)score, then by lower id.  That float is the integer itself whenever |score| < 2^24: for IP at every dim (at
+ * most 4096 * 128 * 8 = 2^22), for L2 up to dim 896 (135^2 * 896 < 2^24).  Above dim 896, L2 scores that round to
+ * one float are ties and go to the lower id.  Padding is UINT64_MAX / +inf as everywhere; 1 <= k <= 8192.
+ * Consequence: for IP at every dim, and for L2 up to dim 896, an I4 handle returns bit for bit what an
+ * EXPANN_DTYPE_I8 handle holding the unpacked rows returns.
+ * Served: expann_add, expann_build, expann_set_base_device (with id_offset), expann_size, expann_search and
+ * expann_search_device with the synchronous overflow check, expann_get_stat ("base_bytes" = n * dim / 2;
+ * "i4_mfma_launches" = launches of scan_i4_mfma_kernel since create) and expann_set_option ("scan_kernel" is not
+ * read).  One kernel on the int8 matrix cores serves every m >= 1 and every dim (scan_i4_mfma_kernel, DESIGN.md 4.6n;
+ * there is no VALU form for small batches).
+ * NOT offered, each EXPANN_ERR_UNSUPPORTED with a message and the handle untouched: the row filter and row groups,
+ * range search, expann_append* and expann_reserve, expann_remove* and expann_compact_row_filter, expann_score_ids,
+ * expann_search_asym_i8, the expann_sharded_* handles, and deferred searches (expann_search_device under
+ * "async_search" = 1).  The C++ engine classes of include/expann/ do not take the dtype either. */
 /* EXPANN_DTYPE_B1: rows are packed bits.  `dim` is the number of BITS: any multiple of 64 from 64 to 4096 (not a
  * multiple of 64: EXPANN_ERR_INVALID_ARG; over 4096: EXPANN_ERR_UNSUPPORTED; both before the device is touched).  A row
  * is dim / 8 bytes, [n][dim / 8]; dimension j is bit j % 8 of byte j / 8 (numpy.packbits(..., bitorder="little"));
