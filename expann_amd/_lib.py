@@ -9,7 +9,7 @@ LIB_PATH = os.environ.get("EXPANN_LIB") or os.path.join(_HERE, "libexpann_hip.so
 
 OK = 0
 ERR_INVALID_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_NOT_BUILT, ERR_UNSUPPORTED, ERR_OVERFLOW = 1, 2, 3, 4, 5, 6
-DTYPE_F32, DTYPE_U8, DTYPE_I8, DTYPE_I16, DTYPE_F16, DTYPE_B1, DTYPE_I4 = 0, 1, 2, 3, 4, 5, 6
+DTYPE_F32, DTYPE_U8, DTYPE_I8, DTYPE_I16, DTYPE_F16, DTYPE_B1, DTYPE_I4, DTYPE_PQ8 = 0, 1, 2, 3, 4, 5, 6, 7
 METRIC_L2, METRIC_IP, METRIC_L2_I8_REFCOMPAT, METRIC_HAMMING = 0, 1, 2, 3
 GRAPH_FP32, GRAPH_U8_CAST, GRAPH_RANGED_Q8 = 0, 1, 2  # expann_graph_compression
 
@@ -58,7 +58,7 @@ ABI_SYMBOLS = [
     "expann_graph_build_state_shape", "expann_graph_read_build_state", "expann_graph_note_host_append",
     "expann_antitopo_remove", "expann_antitopo_compact_row_filter", "expann_graph_remove",
     "expann_graph_note_host_remove", "expann_graph_read_row_filter",
-    "expann_search_asym_i8", "expann_search_asym_i8_device",
+    "expann_search_asym_i8", "expann_search_asym_i8_device", "expann_set_codebooks",
 ]
 GROUP_ANY = 0xFFFFFFFF  # EXPANN_GROUP_ANY: the group a query names to search every row
 
@@ -165,6 +165,9 @@ def load():
         L.expann_search_asym_i8.argtypes = [vp, vp, sz, sz, vp, vp]
         L.expann_search_asym_i8_device.restype = C.c_int
         L.expann_search_asym_i8_device.argtypes = [vp, vp, sz, sz, vp, vp, vp]
+    if hasattr(L, "expann_set_codebooks"):
+        L.expann_set_codebooks.restype = C.c_int
+        L.expann_set_codebooks.argtypes = [vp, vp, sz]
     L.expann_merge_topk_device.restype = C.c_int
     L.expann_merge_topk_device.argtypes = [C.c_int, vp, vp, sz, sz, sz, vp, vp, vp]
     L.expann_merge_topk_strided_device.restype = C.c_int

@@ -16,6 +16,7 @@ namespace expann {
 constexpr int kPlanU8L2 = 0, kPlanI8L2 = 1, kPlanI8L2Ref = 2, kPlanI8IP = 3, kPlanI16L2Ref = 4;
 constexpr int kPlanB1Ham = 5;       // packed-bit rows under the Hamming distance (scan_hamming.hpp); dim counts bits
 constexpr int kPlanI4 = 6;          // 4-bit rows against int8 queries (scan_i4.hpp), inner product or L2 by the metric
+constexpr int kPlanPQ = 7;          // product-quantised rows (scan_pq.hpp): M one-byte codes against fp32 queries
 constexpr int kPlanMaxDim = 4096;  // kMaxAnyDim
 
 // ---- the dims each family is compiled for (the variant tables of expann_hip.hip are checked against these) ----
@@ -140,6 +141,7 @@ struct PlanIndex {
 	int u8_exact = 0;     // uint8 shadow: 0 unknown, 1 serving, -1 the rows are not 8-bit integers
 	bool filter_on = false;
 	size_t n_allowed = 0;
+	int pq_m = 0;         // product-quantised rows: codes per row (0: expann_set_codebooks has not been called)
 };
 struct PlanCall {
 	size_t m = 0, k = 0;
@@ -215,6 +217,49 @@ constexpr const char* kRefuseF16 = "fp16 GEMM-form scan: f32 with dim a multiple
 constexpr const char* kRefuseHamMfma = "matrix-core Hamming scan (scan_kernel=2): packed-bit rows of at most 1024 bits";
 constexpr const char* kRefuseHamKernel = "packed-bit rows: scan_kernel is 0 (auto), 1 (VALU form) or 2 (matrix-core form)";
 
+// Product-quantised rows (EXPANN_DTYPE_PQ8, THE PQ RULE; scan_pq.hpp).  A workgroup keeps the lookup tables of its TQ
+// queries in LDS, [M][256][TQ] fp32 = TQ * M KB, inside 128 KB of the CU's 160: the class of M is the largest of
+// 8 / 4 / 2 / 1 that fits (8 up to M = 16, 4 up to 32, 2 up to 64, 1 up to 128); a batch smaller than its class takes
+// the smallest tile that covers it (one query: TQ = 1), "query_tile" forces one of the class.
+constexpr int kPlanPQMinM = 8, kPlanPQMaxM = 128, kPlanPQMinDim = 8;
+constexpr uint32_t kPlanPQTableBytes = 128 * 1024;
+constexpr DimTiles kScanPQTiles = {0, {1, 2, 4, 8}};
+constexpr bool pq_shape_ok(int dim, int M) {
+	return M >= kPlanPQMinM && M <= kPlanPQMaxM && M % 8 == 0 && dim >= kPlanPQMinDim && dim <= kPlanMaxDim && dim % M == 0;
+}
+constexpr int pq_tile_class(int M) {
+	int tq = 8;
+	while (tq > 1 && (uint32_t)tq * (uint32_t)M * 1024u > kPlanPQTableBytes)
+		tq /= 2;
+	return tq;
+}
+constexpr int pq_tile(int dim, int M, size_t m, long forced_tq) {
+	if (!pq_shape_ok(dim, M))
+		return 0;
+	const int cls = pq_tile_class(M);
+	if (forced_tq > 0)
+		return has_tile(&kScanPQTiles, (int)forced_tq) && forced_tq <= cls ? (int)forced_tq : 0;
+	int tq = 1;
+	while (tq < cls && (size_t)tq < m)
+		tq *= 2;
+	return tq;
+}
+// Rows per workgroup.  The prologue builds TQ * M * 256 table entries of dsub steps of three VALU operations:
+// TQ * 256 * dim * 3 lane-operations; a scanned row costs about 2 * TQ * M (an address and an add per code and query).
+// So the prologue is worth 384 * dsub rows -- 3 072 at dsub = 8, where 32 K rows put it near a tenth of the workgroup.
+// The chunks: as few as keep every slot (a CU times the workgroups whose tables fit its LDS together) busy once --
+// rounds x (rows per chunk + prologue) grows with every further round --, and beyond that no more than leave a
+// workgroup ten prologues of rows; a chunk is one step of 256 rows (16 groups) at least.
+constexpr uint32_t pq_prologue_rows(int dim, int M) { return 384u * (uint32_t)(dim / M); }
+constexpr uint32_t plan_pq_chunks(uint32_t n_groups_sel, uint32_t n_qtiles, uint32_t slots, int dim, int M) {
+	const uint64_t rows = (uint64_t)n_groups_sel * 16;
+	const uint32_t tenth = (uint32_t)(rows / (10ull * pq_prologue_rows(dim, M)));
+	const uint32_t fill = (slots + n_qtiles - 1) / n_qtiles;
+	const uint32_t most = n_groups_sel / 16 > 1 ? n_groups_sel / 16 : 1;
+	const uint32_t want = tenth > fill ? tenth : fill;
+	return want < most ? want : most;
+}
+
 // the direct scan's query tile for m queries (0: none)
 constexpr int direct_tile(const PlanIndex& x, size_t m) {
 	if (x.int_mode < 0) {
@@ -227,6 +272,8 @@ constexpr int direct_tile(const PlanIndex& x, size_t m) {
 		return x.dim >= 64 && x.dim <= kPlanMaxDim && x.dim % 64 == 0 ? pick_tile(&kScanB1Tiles, m, x.query_tile) : 0;
 	if (x.int_mode == kPlanI4)  // (no direct scan: the one form's query tile, kHamTQ)
 		return x.dim >= 64 && x.dim <= kPlanMaxDim && x.dim % 64 == 0 ? 64 : 0;
+	if (x.int_mode == kPlanPQ)
+		return pq_tile(x.dim, x.pq_m, m, x.query_tile);
 	if (any_dim_i8(x.dim, x.int_mode))
 		return pick_tile(&kScanI8AnyTiles, m, x.query_tile);
 	return pick_tile(x.int_mode == kPlanI16L2Ref ? tiles_of(kScanI16Tiles, x.dim) : tiles_of(kScanI8Tiles, x.dim), m,
@@ -351,9 +398,31 @@ constexpr AsymTiles plan_i4_tiles(size_t n, uint32_t sel_rows, bool first, bool 
 	return plan_asym_tiles(n, sel_rows, first, last, cap);  // (the same 512-row tiles and fixed slots)
 }
 
+// Product-quantised rows: one exact form, scan_pq_kernel, under the direct scan's contract -- the direct family with
+// its sampled class minima, no matrix-core form, no speculation, no tie restart ((score, row) <= the threshold key
+// is kept).  "scan_kernel" is not read.  c.cap is the lists' starting capacity (plan_start_cap).
+constexpr const char* kRefusePQRows = "scan_pq: EXPANN_DTYPE_PQ8 rows under EXPANN_METRIC_L2 or EXPANN_METRIC_IP only";
+constexpr const char* kRefusePQK = "EXPANN_DTYPE_PQ8 rows: k is at most 8192 (half the longest candidate list)";
+inline ScanPlan plan_pq(const PlanIndex& x, const PlanCall& c) {
+	ScanPlan p;
+	p.direct_tq = direct_tile(x, c.m);
+	if (x.int_mode != kPlanPQ || x.dtype != EXPANN_DTYPE_PQ8 || (x.metric != EXPANN_METRIC_IP && x.metric != EXPANN_METRIC_L2)) {
+		p.status = EXPANN_ERR_UNSUPPORTED;
+		p.message = kRefusePQRows;
+	} else if (c.k > kPlanAsymMaxK || (size_t)c.cap < 2 * c.k) {
+		p.status = EXPANN_ERR_UNSUPPORTED;
+		p.message = kRefusePQK;
+	} else {
+		p.sampled = x.sample_pass != 0;
+	}
+	return p;
+}
+
 inline ScanPlan plan_scan(const PlanIndex& x, const PlanCall& c, const PlanAttempt& a) {
 	if (x.int_mode == kPlanB1Ham)
 		return plan_hamming(x, c, a);
+	if (x.int_mode == kPlanPQ)
+		return plan_pq(x, c);
 	if (x.int_mode == kPlanI4)
 		return plan_i4(x, c);
 	ScanPlan p;

@@ -40,6 +40,7 @@
 #include "scan_hamming.hpp"
 #include "scan_asym.hpp"
 #include "scan_i4.hpp"
+#include "scan_pq.hpp"
 #include "filter_rows.hpp"
 #include "scan_groups.hpp"
 #include "append_rows.hpp"
@@ -88,9 +89,14 @@ struct Config : Options {
 	size_t q_elem = 4;  // bytes per query element at the ABI (f32 for F32/U8 rows, int8 for I8)
 	int int_mode = -1;  // IntMode for 8-bit rows
 	bool strict_u8 = false;          // (on the shadow) non-8-bit / fractional queries: hand back, no error
+	int pq_m = 0;                    // product-quantised rows: codes per row, 0 until expann_set_codebooks
 	// bytes of a stored row and of a query at the ABI (packed-bit rows: dim counts bits, both sides are dim / 8 bytes;
-	// 4-bit rows: dim / 2 bytes against int8 queries of dim bytes)
-	size_t row_bytes() const { return int_mode == kPlanB1Ham ? (size_t)dim / 8 : (int_mode == kPlanI4 ? (size_t)dim / 2 : (size_t)dim * elem); }
+	// 4-bit rows: dim / 2 bytes against int8 queries of dim bytes; product-quantised rows: M bytes against fp32 queries)
+	size_t row_bytes() const {
+		if (int_mode == kPlanPQ)
+			return (size_t)pq_m;
+		return int_mode == kPlanB1Ham ? (size_t)dim / 8 : (int_mode == kPlanI4 ? (size_t)dim / 2 : (size_t)dim * elem);
+	}
 	size_t query_bytes() const { return int_mode == kPlanB1Ham ? (size_t)dim / 8 : (size_t)dim * q_elem; }
 };
 inline bool b1_rows(const Config* h) { return h->int_mode == kPlanB1Ham; }
@@ -99,8 +105,13 @@ constexpr const char* kB1NotOffered =
 inline bool i4_rows(const Config* h) { return h->int_mode == kPlanI4; }
 constexpr const char* kI4NotOffered =
     "EXPANN_DTYPE_I4 rows: add / build / set_base_device and expann_search / expann_search_device only";
-// the entry points neither kind of packed rows is offered: the refusal's text, or nullptr
-inline const char* packed_not_offered(const Config* h) { return b1_rows(h) ? kB1NotOffered : (i4_rows(h) ? kI4NotOffered : nullptr); }
+inline bool pq_rows(const Config* h) { return h->int_mode == kPlanPQ; }
+constexpr const char* kPQNotOffered =
+    "EXPANN_DTYPE_PQ8 rows: set_codebooks / add / build / set_base_device and expann_search / expann_search_device only";
+// the entry points no kind of packed rows is offered: the refusal's text, or nullptr
+inline const char* packed_not_offered(const Config* h) {
+	return b1_rows(h) ? kB1NotOffered : (i4_rows(h) ? kI4NotOffered : (pq_rows(h) ? kPQNotOffered : nullptr));
+}
 
 // the rows: staged on the host until build(), then on the device -- the handle's own copy, or the caller's memory
 // (expann_set_base_device)
@@ -280,6 +291,7 @@ struct Stats {
 	uint64_t stat_ham[2] = {0, 0};   // launches of scan_hamming_mfma_kernel / scan_hamming_valu_kernel since create
 	uint64_t stat_asym = 0;          // launches of scan_asym_mfma_kernel since create
 	uint64_t stat_i4 = 0;            // launches of scan_i4_mfma_kernel since create
+	uint64_t stat_pq = 0;            // launches of scan_pq_kernel since create
 };
 
 // streams, events, profiling, statistics, the last error
@@ -299,8 +311,13 @@ struct Runtime : Stats {
 	mutable std::string err;
 };
 
+// product-quantised rows: the codebooks on the device, [pq_m][256][dim / pq_m]; they outlive a change of rows
+struct Codebooks {
+	DevPtr<float> d_codebooks;
+};
+
 // (base order: the streams and events outlive every buffer when a handle is deleted)
-struct expann_index : Config, Runtime, Workspace, Rows, RowCopies, RowFilter, RowGroups {
+struct expann_index : Config, Runtime, Workspace, Rows, RowCopies, RowFilter, RowGroups, Codebooks {
 	// the row terms the fp16 forms read: the masked copies while a filter is set
 	const float* bnorm_f16() const { return filter_on ? d_bnorm_f16_m.p : d_bnorm_f16.p; }
 	const float* bns_f16() const { return filter_on ? d_bns_f16_m.p : d_bns_f16.p; }
@@ -435,6 +452,26 @@ const ScanI8Variant kScanB1[] = {{0, 1, kPlanB1Ham, scan_hamming_valu_kernel<1>,
                                  {0, 8, kPlanB1Ham, scan_hamming_valu_kernel<8>, "scan_hamming_valu<8>"}};
 static_assert(kHamMaxDim == kPlanMaxDim && ham_mfma_lds_bytes(kPlanHamMfmaMaxDim) <= 160 * 1024,
               "bf_plan.hpp: the dims of the two Hamming forms");
+// product-quantised rows: the query tiles of scan_pq_kernel (kScanPQTiles) under either metric, every dim and M at
+// run time
+struct ScanPQVariant {
+	int tq;
+	bool ip;
+	ScanFn fn;
+	const char* name;
+};
+#define SCAN_PQ(TQ) {TQ, false, scan_pq_kernel<TQ, false>, "scan_pq<" #TQ ",L2>"}, {TQ, true, scan_pq_kernel<TQ, true>, "scan_pq<" #TQ ",IP>"}
+const ScanPQVariant kScanPQ[] = {SCAN_PQ(1), SCAN_PQ(2), SCAN_PQ(4), SCAN_PQ(8)};
+#undef SCAN_PQ
+static_assert(pq_lds_bytes(pq_tile_class(kPlanPQMaxM), kPlanPQMaxM) <= kPlanPQTableBytes &&
+                  pq_lds_bytes(8, 16) == kPlanPQTableBytes && pq_tile_class(24) == 4 && pq_tile_class(72) == 1,
+              "bf_plan.hpp: the tables of a PQ tile fit 128 KB of LDS");
+const ScanPQVariant* find_scan_pq(int tq, bool ip) {
+	for (const auto& v : kScanPQ)
+		if (v.tq == tq && v.ip == ip)
+			return &v;
+	return nullptr;
+}
 const ScanI8Variant* find_scan_i8(int d, int mode, int tq) {
 	for (const auto& v : kScanB1)
 		if (mode == kPlanB1Ham && v.tq == tq)
@@ -849,6 +886,7 @@ PlanIndex plan_index(const expann_index* h) {
 	x.u8_exact = h->u8_exact;
 	x.filter_on = h->filter_on;
 	x.n_allowed = h->n_allowed;
+	x.pq_m = h->pq_m;
 	return x;
 }
 
@@ -1284,6 +1322,7 @@ bool plan_tables_match() {
 	    });
 	all(kScanI8Any, 4 * count_tiles(&kScanI8AnyTiles, 1), [](const ScanI8Variant& v) { return has_tile(&kScanI8AnyTiles, v.tq); });
 	all(kScanB1, count_tiles(&kScanB1Tiles, 1), [](const ScanI8Variant& v) { return has_tile(&kScanB1Tiles, v.tq); });
+	all(kScanPQ, 2 * count_tiles(&kScanPQTiles, 1), [](const ScanPQVariant& v) { return has_tile(&kScanPQTiles, v.tq); });
 	all(kDirectF16, count_tiles(kDirectF16Tiles, std::size(kDirectF16Tiles)),
 	    [](const DirectF16Variant& v) { return has_tile(tiles_of(kDirectF16Tiles, v.d), v.tq); });
 	all(kGemmF16X, std::size(kF16XDims) + std::size(kF16YDims) + std::size(kF16KXDims), [](const GemmF16Variant& v) {
@@ -2370,6 +2409,16 @@ int SearchPass::run_level(size_t li) {
 		sp.list_stride = L.list_step;
 	}
 	uint32_t n_chunks = direct_scan_chunks(L.n_groups_sel, n_qtiles, cus);
+	uint32_t pq_lds = 0;  // product-quantised rows: the tile's tables, dynamic LDS of scan_pq_kernel
+	if (pq_rows(h)) {
+		// (a workgroup pays for its tables before its first row: the chunks by plan_pq_chunks; as many workgroups per
+		// CU as tables fit its 160 KB, eight at most -- 32 waves)
+		pq_lds = pq_lds_bytes((uint32_t)sv->tq, (uint32_t)h->pq_m);
+		const uint32_t per_cu = std::max(1u, std::min(8u, 160u * 1024u / pq_lds));
+		n_chunks = plan_pq_chunks(L.n_groups_sel, n_qtiles, (uint32_t)cus * per_cu, h->dim, h->pq_m);
+		sp.pq_codebooks = h->d_codebooks.p;
+		sp.pq_m = (uint32_t)h->pq_m;
+	}
 	if (first && L.classmin_blocks) {
 		n_chunks = L.classmin_blocks;
 		sp.classmin = 1;
@@ -2594,9 +2643,11 @@ int SearchPass::run_level(size_t li) {
 	} else {
 		if (b1_rows(h))
 			h->stat_ham[1]++;
+		if (pq_rows(h))
+			h->stat_pq++;
 		if (timed)
 			HIP_TRY(h, hipEventRecord(h->ev[h->ev_used][0], st));
-		hipLaunchKernelGGL(scan_fn, dim3(n_chunks * n_qtiles), dim3(kBlock), 0, st, sp);
+		hipLaunchKernelGGL(scan_fn, dim3(n_chunks * n_qtiles), dim3(kBlock), pq_lds, st, sp);
 	}
 	if (timed) {
 		HIP_TRY(h, hipEventRecord(h->ev[h->ev_used][1], st));
@@ -3008,6 +3059,9 @@ int search_pass(expann_index* h, const void* d_queries, size_t m, size_t k, uint
 	if (float_rows(h)) {
 		if (const ScanVariant* v = find_scan_f32(h->dim, ip, plan.direct_tq, f16_rows(h)))
 			svs = ScanSel{v->fn, v->tq, v->name, v->fn_bits, v->fn_list};
+	} else if (pq_rows(h)) {
+		if (const ScanPQVariant* v = find_scan_pq(plan.direct_tq, ip))
+			svs = ScanSel{v->fn, v->tq, v->name};
 	} else {
 		if (const ScanI8Variant* v = find_scan_i8(h->dim, h->int_mode, plan.direct_tq))
 			svs = ScanSel{v->fn, v->tq, v->name};
@@ -3069,7 +3123,20 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 		g_create_error = "EXPANN_DTYPE_B1 and EXPANN_METRIC_HAMMING go together only";
 		return EXPANN_ERR_INVALID_ARG;
 	}
-	if (dim <= 0 || dim % 16 != 0) {
+	if (dtype == EXPANN_DTYPE_PQ8) {  // (THE PQ RULE: dim = M * dsub, no multiple of 16 or 64 asked)
+		if (metric != EXPANN_METRIC_IP && metric != EXPANN_METRIC_L2) {
+			g_create_error = "EXPANN_DTYPE_PQ8 rows support EXPANN_METRIC_L2 and EXPANN_METRIC_IP only";
+			return EXPANN_ERR_INVALID_ARG;
+		}
+		if (dim < kPlanPQMinDim) {
+			g_create_error = "EXPANN_DTYPE_PQ8 rows need dim >= 8";
+			return EXPANN_ERR_INVALID_ARG;
+		}
+		if (dim > kMaxAnyDim) {
+			g_create_error = "unsupported dim " + std::to_string(dim) + ": EXPANN_DTYPE_PQ8 rows take dim <= " + std::to_string(kMaxAnyDim);
+			return EXPANN_ERR_UNSUPPORTED;
+		}
+	} else if (dim <= 0 || dim % 16 != 0) {
 		g_create_error = "dim must be a positive multiple of 16 (the reference kernels require it)";
 		return EXPANN_ERR_INVALID_ARG;
 	}
@@ -3115,11 +3182,13 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 			return EXPANN_ERR_INVALID_ARG;
 		}
 		int_mode = kPlanI4;
+	} else if (dtype == EXPANN_DTYPE_PQ8) {  // (checked above)
+		int_mode = kPlanPQ;
 	} else {
 		g_create_error = "unknown dtype";
 		return EXPANN_ERR_INVALID_ARG;
 	}
-	if (int_mode >= 0 && dim % 64 != 0) {
+	if (int_mode >= 0 && int_mode != kPlanPQ && dim % 64 != 0) {
 		g_create_error = "8-bit rows need dim % 64 == 0 (src/distance.h:29-53, antitopo_engine.h:726)";
 		return EXPANN_ERR_INVALID_ARG;
 	}
@@ -3146,7 +3215,7 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 		g_create_error = "internal: bf_plan.hpp does not list the compiled scan kernels";
 		return EXPANN_ERR_UNSUPPORTED;
 	}
-	if (!direct_tile(px, 1)) {
+	if (int_mode != kPlanPQ && !direct_tile(px, 1)) {  // (product-quantised rows: the tile waits for M, expann_set_codebooks)
 		g_create_error = "unsupported dim " + std::to_string(dim) +
 		                 " (built: f32 any multiple of 16 up to 4096; 8-bit any multiple of 64 up to 4096; int16 64,128)";
 		return EXPANN_ERR_UNSUPPORTED;
@@ -3212,6 +3281,9 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 		needs.push_back({(const void*)scan_asym_mfma_kernel, (int)kAsymLdsBytes, "scan_asym_mfma_kernel"});
 	if (int_mode == kPlanI4)
 		needs.push_back({(const void*)scan_i4_mfma_kernel, (int)kI4LdsBytes, "scan_i4_mfma_kernel"});
+	if (int_mode == kPlanPQ)
+		for (const auto& v : kScanPQ)
+			needs.push_back({(const void*)v.fn, (int)kPlanPQTableBytes, "scan_pq_kernel"});
 	for (const auto& v : kGemmBf16)
 		if (v.d == dim)
 			needs.push_back({(const void*)v.scan, 2 * kGemmTB * dim * (int)sizeof(float), "scan_gemm_bf16x3_kernel"});
@@ -3255,9 +3327,30 @@ static int make_i4_rowterm(expann_index* h) {
 	return EXPANN_OK;
 }
 
+constexpr const char* kPQNoCodebooks = "EXPANN_DTYPE_PQ8 rows: expann_set_codebooks comes first";
+
+int expann_set_codebooks(expann_index* h, const float* codebooks, size_t M) {
+	if (!h)
+		return EXPANN_ERR_INVALID_ARG;
+	if (!pq_rows(h))
+		return h->fail(EXPANN_ERR_UNSUPPORTED, "expann_set_codebooks: EXPANN_DTYPE_PQ8 rows only");
+	if (h->pq_m || h->d_base || h->n_staged)
+		return h->fail(EXPANN_ERR_INVALID_ARG, "expann_set_codebooks: once, before the first row");
+	if (!codebooks || M > (size_t)kPlanPQMaxM || !pq_shape_ok(h->dim, (int)M))
+		return h->fail(EXPANN_ERR_INVALID_ARG, "expann_set_codebooks: codebooks [M][256][dim / M], M a multiple of 8 in [8, 128] that divides dim");
+	HIP_TRY(h, hipSetDevice(h->device));
+	const size_t bytes = sizeof(float) * 256 * (size_t)h->dim;  // M * 256 * dsub floats
+	HIP_TRY(h, hipMalloc(&h->d_codebooks, bytes));
+	HIP_TRY(h, hipMemcpy(h->d_codebooks, codebooks, bytes, hipMemcpyHostToDevice));
+	h->pq_m = (int)M;
+	return EXPANN_OK;
+}
+
 int expann_add(expann_index* h, const void* rows, size_t n) {
 	if (!h)
 		return EXPANN_ERR_INVALID_ARG;
+	if (pq_rows(h) && !h->pq_m)
+		return h->fail(EXPANN_ERR_INVALID_ARG, kPQNoCodebooks);
 	if (!rows && n)
 		return h->fail(EXPANN_ERR_INVALID_ARG, "rows == NULL");
 	if (h->d_base)
@@ -3301,6 +3394,8 @@ int expann_build(expann_index* h) {
 int expann_set_base_device(expann_index* h, const void* d_rows, size_t n, uint64_t id_offset) {
 	if (!h)
 		return EXPANN_ERR_INVALID_ARG;
+	if (pq_rows(h) && !h->pq_m)
+		return h->fail(EXPANN_ERR_INVALID_ARG, kPQNoCodebooks);
 	if (!d_rows || n == 0)
 		return h->fail(EXPANN_ERR_INVALID_ARG, "empty device base");
 	if (n >= (1ull << 32) - 32)
@@ -3731,6 +3826,8 @@ int expann_search_device(expann_index* h, const void* d_queries, size_t m, size_
                          uint64_t* d_ids, float* d_dists, void* stream) {
 	if (!h)
 		return EXPANN_ERR_INVALID_ARG;
+	if (pq_rows(h) && !h->pq_m)
+		return h->fail(EXPANN_ERR_INVALID_ARG, kPQNoCodebooks);
 	if (!h->d_base)
 		return h->fail(EXPANN_ERR_NOT_BUILT, "search before build()");
 	if (k == 0)
@@ -3811,6 +3908,8 @@ int expann_search(expann_index* h, const void* queries, size_t m, size_t k, uint
                   float* dists) {
 	if (!h)
 		return EXPANN_ERR_INVALID_ARG;
+	if (pq_rows(h) && !h->pq_m)
+		return h->fail(EXPANN_ERR_INVALID_ARG, kPQNoCodebooks);
 	if (!h->d_base)
 		return h->fail(EXPANN_ERR_NOT_BUILT, "search before build()");
 	if (k == 0)
@@ -3892,6 +3991,8 @@ static int asym_refusal(expann_index* h, const void* queries, size_t k, const ui
 		return h->fail(EXPANN_ERR_INVALID_ARG, "NULL query/ids pointer");
 	if (k == 0)
 		return h->fail(EXPANN_ERR_INVALID_ARG, "k == 0");
+	if (pq_rows(h))
+		return h->fail(EXPANN_ERR_UNSUPPORTED, kPQNotOffered);
 	const ScanPlan plan = plan_asym(plan_index(h), PlanCall{1, k, plan_start_cap(h->opt_cand_capacity, k, kMaxCap)});
 	if (plan.status != EXPANN_OK)
 		return h->fail(plan.status, plan.message);
@@ -4171,6 +4272,8 @@ int expann_get_stat(expann_index* h, const char* name, uint64_t* out) {
 	    {"hamming_valu_launches", [](H h) { return h->stat_ham[1]; }},
 	    {"asym_mfma_launches", [](H h) { return h->stat_asym; }},
 	    {"i4_mfma_launches", [](H h) { return h->stat_i4; }},
+	    {"pq_launches", [](H h) { return h->stat_pq; }},
+	    {"pq_m", [](H h) -> uint64_t { return (uint64_t)h->pq_m; }},
 	    {"copies_digest", [](H h) { return copies_digest(const_cast<expann_index*>(h)); }},
 	};
 	for (const auto& s : kStatTable)
@@ -4238,6 +4341,8 @@ int set_row_filter(expann_index* h, const uint32_t* bits, size_t n_words, bool o
 		return EXPANN_ERR_INVALID_ARG;
 	if (!bits)
 		return h->fail(EXPANN_ERR_INVALID_ARG, "row filter: NULL bits");
+	if (pq_rows(h))
+		return h->fail(EXPANN_ERR_UNSUPPORTED, kPQNotOffered);
 	if (!float_rows(h))
 		return h->fail(EXPANN_ERR_UNSUPPORTED,
 		               "row filter: fp32 / fp16 rows only (8-bit and int16 rows have integer row terms)");
@@ -4277,6 +4382,8 @@ int set_row_groups(expann_index* h, const uint32_t* groups, size_t n, bool on_de
 		return EXPANN_ERR_INVALID_ARG;
 	if (!groups)
 		return h->fail(EXPANN_ERR_INVALID_ARG, "row groups: NULL labels");
+	if (pq_rows(h))
+		return h->fail(EXPANN_ERR_UNSUPPORTED, kPQNotOffered);
 	if (!float_rows(h))
 		return h->fail(EXPANN_ERR_UNSUPPORTED,
 		               "row groups: fp32 / fp16 rows only (the filter passes of large groups need the row filter)");
@@ -4975,6 +5082,8 @@ int range_args(expann_index* h, const void* queries, const float* radii, size_t 
 		return h->fail(EXPANN_ERR_INVALID_ARG, "range search: NULL queries / radii / counts / ids pointer");
 	if (max_results > kMaxK)  // (by value, before any GPU work, as k is)
 		return h->fail(EXPANN_ERR_UNSUPPORTED, "range search: max_results beyond " + std::to_string(kMaxK));
+	if (pq_rows(h))
+		return h->fail(EXPANN_ERR_UNSUPPORTED, kPQNotOffered);
 	if (!float_rows(h))
 		return h->fail(EXPANN_ERR_UNSUPPORTED, "range search: EXPANN_DTYPE_F32 and EXPANN_DTYPE_F16 rows only");
 	if (!h->d_base)

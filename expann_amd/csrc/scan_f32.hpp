@@ -46,6 +46,9 @@ struct ScanParams {
 	const uint32_t* row_list;    // kRowsList: step g visits the rows row_list[(g * 16 + i) * list_stride], i < 16 ...
 	uint32_t list_len;           // ... while g * 16 + i < list_len (level 0 only: every key at its list position)
 	uint32_t list_stride;
+	// product-quantised rows (scan_pq.hpp; trailing, so every other kernel reads its fields where they were)
+	const float* pq_codebooks;   // [pq_m][256][dim / pq_m]
+	uint32_t pq_m;               // codes per row
 };
 
 // which rows a launch of the f32 scans may keep

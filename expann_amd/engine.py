@@ -15,11 +15,11 @@ from . import _lib
 
 _NP_DTYPE = {_lib.DTYPE_F32: np.float32, _lib.DTYPE_U8: np.uint8, _lib.DTYPE_I8: np.int8,
              _lib.DTYPE_I16: np.int16, _lib.DTYPE_F16: np.float16, _lib.DTYPE_B1: np.uint8,
-             _lib.DTYPE_I4: np.uint8}
+             _lib.DTYPE_I4: np.uint8, _lib.DTYPE_PQ8: np.uint8}
 _DTYPE = {"f32": _lib.DTYPE_F32, "u8": _lib.DTYPE_U8, "i8": _lib.DTYPE_I8, "i16": _lib.DTYPE_I16,
-          "f16": _lib.DTYPE_F16, "b1": _lib.DTYPE_B1, "i4": _lib.DTYPE_I4}
+          "f16": _lib.DTYPE_F16, "b1": _lib.DTYPE_B1, "i4": _lib.DTYPE_I4, "pq8": _lib.DTYPE_PQ8}
 # row types whose queries are fp32 at the ABI (the others take queries of the rows' own type)
-_F32_QUERIES = (_lib.DTYPE_F32, _lib.DTYPE_U8, _lib.DTYPE_F16)
+_F32_QUERIES = (_lib.DTYPE_F32, _lib.DTYPE_U8, _lib.DTYPE_F16, _lib.DTYPE_PQ8)
 
 
 def pack_row_filter(allow):
@@ -66,9 +66,18 @@ class GpuBruteForceEngine:
     [n, dim / 2] as pack_i4 packs int8 values in [-8, 7]; queries are int8 [m, dim].  Scores are exact integers
     returned as float32 -- for "ip" at every dim and for "l2" up to dim 896 bit for bit those of an "i8" engine over
     unpack_i4(rows).  Add, build, set_base_device, size and query_k_batch / search_device only (THE I4 RULE,
-    include/expann_hip.h); ShardedBruteForceEngine and the C++ engine classes do not take the dtype."""
+    include/expann_hip.h); ShardedBruteForceEngine and the C++ engine classes do not take the dtype.
 
-    def __init__(self, dim, metric="l2", dtype="f32", device=0):
+    dtype="pq8" with metric "l2" or "ip" and codebooks=array[M, 256, dim / M] (float32; the layout of FAISS's
+    ProductQuantizer centroids): product-quantised rows, M bytes each.  Rows are uint8 [n, M] -- code i selects
+    centroid codebooks[i, code] --, queries float32 [m, dim]; M is a multiple of 8 from 8 to 128 that divides dim,
+    8 <= dim <= 4096.  The score is the sum of M entries of per-query lookup tables, every step one float32
+    operation in a fixed order (THE PQ RULE, include/expann_hip.h): the ids and distance bits are those of a dozen
+    lines of float32 NumPy.  The keyword is required for this dtype and refused for every other.  Add, build,
+    set_base_device, size and query_k_batch / search_device only; training the codebooks and encoding the rows is
+    the caller's."""
+
+    def __init__(self, dim, metric="l2", dtype="f32", device=0, codebooks=None):
         self._L = _lib.load()
         self.dim = int(dim)
         self.metric = {"l2": _lib.METRIC_L2, "ip": _lib.METRIC_IP,
@@ -77,6 +86,13 @@ class GpuBruteForceEngine:
         # elements of a row, and of a query, at the ABI
         self._cols = {_lib.DTYPE_B1: self.dim // 8, _lib.DTYPE_I4: self.dim // 2}.get(self.dtype, self.dim)
         self._qcols = self.dim if self.dtype == _lib.DTYPE_I4 else self._cols
+        if (self.dtype == _lib.DTYPE_PQ8) != (codebooks is not None):
+            raise ValueError('codebooks=array[M, 256, dim / M] goes with dtype="pq8", and only with it')
+        if codebooks is not None:
+            codebooks = np.ascontiguousarray(codebooks, dtype=np.float32)
+            if codebooks.ndim != 3 or codebooks.shape[1] != 256 or codebooks.shape[0] * codebooks.shape[2] != self.dim:
+                raise ValueError("codebooks must be [M, 256, dim / M]")
+            self._cols = codebooks.shape[0]
         self.device = int(device)
         self._metric_name, self._dtype_name = metric, dtype
         h = C.c_void_p()
@@ -84,6 +100,12 @@ class GpuBruteForceEngine:
         _lib.check(None, rc)
         self._h = h
         self._built = False
+        if codebooks is not None:
+            try:
+                _lib.check(h, self._L.expann_set_codebooks(h, codebooks.ctypes.data, codebooks.shape[0]))
+            except _lib.ExpannError:
+                self.close()
+                raise
 
     # ---- the reference interface (src/ann_engine.h:16-29) ---------------------------
     def name(self):
@@ -328,6 +350,7 @@ class GpuBruteForceEngine:
         "hamming_mfma_launches", "hamming_valu_launches" (packed-bit rows: scan launches of either form since create);
         "asym_mfma_launches" (packed-bit rows, int8 queries: launches of scan_asym_mfma_kernel since create);
         "i4_mfma_launches" (4-bit rows: launches of scan_i4_mfma_kernel since create);
+        "pq_launches", "pq_m" (product-quantised rows: launches of scan_pq_kernel since create; codes per row);
         "groups_active", "group_count", and of the last grouped search "group_list_queries", "group_filter_queries",
         "group_any_queries", "group_pad_queries", "group_filter_passes";
         of the last range search "range_list_queries", "range_topk_queries", "range_retries";

@@ -49,8 +49,38 @@ enum expann_dtype {
 	EXPANN_DTYPE_F16 = 4, /* IEEE binary16 rows, see below (appended; EXPANN_ABI_VERSION stays 2:
 	                       * nothing that existed changed)                            */
 	EXPANN_DTYPE_B1 = 5,  /* packed bits under EXPANN_METRIC_HAMMING, see below (appended likewise) */
-	EXPANN_DTYPE_I4 = 6   /* 4-bit rows against int8 queries, THE I4 RULE below (appended likewise) */
+	EXPANN_DTYPE_I4 = 6,  /* 4-bit rows against int8 queries, THE I4 RULE below (appended likewise) */
+	EXPANN_DTYPE_PQ8 = 7  /* product-quantised rows, M one-byte codes, THE PQ RULE below (appended likewise) */
 };
+/* EXPANN_DTYPE_PQ8: product-quantised rows scored by lookup tables (ADC), 16 to 64 times smaller than fp32 rows.
+ * THE PQ RULE.  `dim` counts the elements of a query: 8 <= dim <= 4096 (below 8: EXPANN_ERR_INVALID_ARG; over 4096:
+ * EXPANN_ERR_UNSUPPORTED; both before the device is touched); no multiple of 16 or 64 is asked of it.
+ * Codebooks: expann_set_codebooks(h, codebooks, M), once, before the first expann_add / expann_set_base_device.
+ * `codebooks` is host memory float [M][256][dsub] with dsub = dim / M (the layout of FAISS's ProductQuantizer
+ * centroids), copied to the device; M is a multiple of 8 from 8 to 128 that divides dim; every codebook and query
+ * value is finite.  Rows are uint8_t [n][M] (FAISS's 8-bit codes): code i of a row selects centroid
+ * codebooks[i][code].  Rows adopted by expann_set_base_device are 8-byte aligned.  Queries are float [m][dim].
+ * Metrics: EXPANN_METRIC_L2 and EXPANN_METRIC_IP; anything else is EXPANN_ERR_INVALID_ARG from expann_create.
+ * Score -- every operation below is ONE fp32 operation rounded to nearest, never contracted to an FMA; q is the
+ * query, cb the codebooks, c a centroid number:
+ *     L2 table:  T[i][c] = 0.0f; for j = 0 .. dsub-1 in order:  t = q[i*dsub + j] - cb[i][c][j];  T[i][c] = T[i][c] + t*t
+ *     IP table:  T[i][c] = 0.0f; for j in order:  T[i][c] = T[i][c] + q[i*dsub + j] * cb[i][c][j]
+ *     sum:       S = T[0][code_0]; for i = 1 .. M-1 in order:  S = S + T[i][code_i]
+ *     L2 score:  S          IP score:  0.0f - S   (never -0.0: the float key and a sort of the floats agree)
+ * Results ascend by (score, id), ties to the lower id; 1 <= k <= 8192; lists shorter than k are padded with
+ * UINT64_MAX / +inf as everywhere.  The rule is what a dozen lines of float32 NumPy compute, and the tests compare
+ * ids and distance bits with exactly that.
+ * Served: expann_create, expann_set_codebooks, expann_add, expann_build, expann_set_base_device (with id_offset),
+ * expann_size, expann_search and expann_search_device with the synchronous overflow check, expann_get_stat
+ * ("base_bytes" = n * M; "pq_m" = M; "pq_launches" = launches of scan_pq_kernel since create) and
+ * expann_set_option ("scan_kernel" is not read; "query_tile" 1 / 2 / 4 / 8 within the class of M).  One kernel gathers
+ * from tables in LDS (scan_pq_kernel).  A search before expann_set_codebooks, and rows offered before
+ * it (their width is not known), are EXPANN_ERR_INVALID_ARG.
+ * NOT offered, each EXPANN_ERR_UNSUPPORTED with a message and the handle untouched: the row filter and row groups,
+ * range search, expann_append* and expann_reserve, expann_remove* and expann_compact_row_filter, expann_score_ids,
+ * expann_search_asym_i8, the expann_sharded_* handles, and deferred searches (expann_search_device under
+ * "async_search" = 1).  The C++ engine classes of include/expann/ do not take the dtype either.  Out of scope:
+ * training codebooks and encoding rows (the caller brings both), other code widths, residual / IVF forms, re-ranking. */
 /* EXPANN_DTYPE_I4: 4-bit scalar-quantised rows, half the bytes of EXPANN_DTYPE_I8, scored against int8 queries.
  * THE I4 RULE.  `dim` counts elements: any multiple of 64 from 64 to 4096 (not a multiple of 64:
  * EXPANN_ERR_INVALID_ARG; over 4096: EXPANN_ERR_UNSUPPORTED; both before the device is touched).  A row is dim / 2
@@ -204,6 +234,12 @@ int expann_sync(expann_index* h);
 int expann_search_asym_i8(expann_index* h, const int8_t* queries, size_t m, size_t k, uint64_t* ids, float* dists);
 int expann_search_asym_i8_device(expann_index* h, const int8_t* d_queries, size_t m, size_t k, uint64_t* d_ids,
                                  float* d_dists, void* stream);
+
+/* The codebooks of an EXPANN_DTYPE_PQ8 handle (THE PQ RULE above): host memory float [M][256][dim / M], copied to
+ * the device before the call returns.  Once per handle, before any row: a second call, a call after expann_add or
+ * expann_set_base_device, NULL codebooks, or an M that is not a multiple of 8 in [8, 128] dividing dim is
+ * EXPANN_ERR_INVALID_ARG; a handle of any other dtype is EXPANN_ERR_UNSUPPORTED. */
+int expann_set_codebooks(expann_index* h, const float* codebooks, size_t M);
 
 /* k-way merge of per-shard results after an all-gather (RCCL): in_ids/in_dists are
  * [n_lists][m][k], each row ascending by (score, id) and padded as above; out is [m][k].
