@@ -17,6 +17,7 @@ constexpr int kPlanU8L2 = 0, kPlanI8L2 = 1, kPlanI8L2Ref = 2, kPlanI8IP = 3, kPl
 constexpr int kPlanB1Ham = 5;       // packed-bit rows under the Hamming distance (scan_hamming.hpp); dim counts bits
 constexpr int kPlanI4 = 6;          // 4-bit rows against int8 queries (scan_i4.hpp), inner product or L2 by the metric
 constexpr int kPlanPQ = 7;          // product-quantised rows (scan_pq.hpp): M one-byte codes against fp32 queries
+constexpr int kPlanPQ4 = 8;         // 4-bit product-quantised rows (scan_pq4.hpp): M nibbles against fp32 queries
 constexpr int kPlanMaxDim = 4096;  // kMaxAnyDim
 
 // ---- the dims each family is compiled for (the variant tables of expann_hip.hip are checked against these) ----
@@ -260,6 +261,13 @@ constexpr uint32_t plan_pq_chunks(uint32_t n_groups_sel, uint32_t n_qtiles, uint
 	return want < most ? want : most;
 }
 
+// 4-bit product-quantised rows (EXPANN_DTYPE_PQ4, THE PQ4 RULE): M nibbles per row, 16 centroids per sub-quantiser.  M is
+// a multiple of 16 (a chunk of scan_pq4.hpp: 16 sub-quantisers, 8 row bytes, 4 k-steps) up to 256 (S <= 255 * 256).
+constexpr int kPlanPQ4MinM = 16, kPlanPQ4MaxM = 256, kPlanPQ4MinDim = 16;
+constexpr bool pq4_shape_ok(int dim, int M) {
+	return M >= kPlanPQ4MinM && M <= kPlanPQ4MaxM && M % 16 == 0 && dim >= kPlanPQ4MinDim && dim <= kPlanMaxDim && dim % M == 0;
+}
+
 // the direct scan's query tile for m queries (0: none)
 constexpr int direct_tile(const PlanIndex& x, size_t m) {
 	if (x.int_mode < 0) {
@@ -274,6 +282,8 @@ constexpr int direct_tile(const PlanIndex& x, size_t m) {
 		return x.dim >= 64 && x.dim <= kPlanMaxDim && x.dim % 64 == 0 ? 64 : 0;
 	if (x.int_mode == kPlanPQ)
 		return pq_tile(x.dim, x.pq_m, m, x.query_tile);
+	if (x.int_mode == kPlanPQ4)  // (no direct scan: the one form's query tile, kHamTQ)
+		return pq4_shape_ok(x.dim, x.pq_m) ? 64 : 0;
 	if (any_dim_i8(x.dim, x.int_mode))
 		return pick_tile(&kScanI8AnyTiles, m, x.query_tile);
 	return pick_tile(x.int_mode == kPlanI16L2Ref ? tiles_of(kScanI16Tiles, x.dim) : tiles_of(kScanI8Tiles, x.dim), m,
@@ -418,9 +428,32 @@ inline ScanPlan plan_pq(const PlanIndex& x, const PlanCall& c) {
 	return p;
 }
 
+// 4-bit product-quantised rows: one form, scan_pq4_mfma_kernel (scan_pq4.hpp), for every m >= 1 and every M, under
+// both metrics.  The family is plan_i4's: every level of the ladder on the int8 matrix cores, (S, row) <= the proven
+// threshold key kept, no sampled pass, no speculation, no tie restart.  "scan_kernel" is not read.  Its tiles are the
+// asymmetric search's, plan_asym_tiles.
+constexpr const char* kRefusePQ4Rows = "scan_pq4: EXPANN_DTYPE_PQ4 rows under EXPANN_METRIC_L2 or EXPANN_METRIC_IP only";
+constexpr const char* kRefusePQ4K = "EXPANN_DTYPE_PQ4 rows: k is at most 8192 (half the longest candidate list)";
+inline ScanPlan plan_pq4(const PlanIndex& x, const PlanCall& c) {
+	ScanPlan p;
+	p.direct_tq = direct_tile(x, c.m);
+	if (x.int_mode != kPlanPQ4 || x.dtype != EXPANN_DTYPE_PQ4 || (x.metric != EXPANN_METRIC_IP && x.metric != EXPANN_METRIC_L2)) {
+		p.status = EXPANN_ERR_UNSUPPORTED;
+		p.message = kRefusePQ4Rows;
+	} else if (c.k > kPlanAsymMaxK || (size_t)c.cap < 2 * c.k) {
+		p.status = EXPANN_ERR_UNSUPPORTED;
+		p.message = kRefusePQ4K;
+	} else {
+		p.family = ScanFamily::kHamming;  // (as plan_i4: the threshold ladder on the int8 matrix cores)
+	}
+	return p;
+}
+
 inline ScanPlan plan_scan(const PlanIndex& x, const PlanCall& c, const PlanAttempt& a) {
 	if (x.int_mode == kPlanB1Ham)
 		return plan_hamming(x, c, a);
+	if (x.int_mode == kPlanPQ4)
+		return plan_pq4(x, c);
 	if (x.int_mode == kPlanPQ)
 		return plan_pq(x, c);
 	if (x.int_mode == kPlanI4)

@@ -41,6 +41,7 @@
 #include "scan_asym.hpp"
 #include "scan_i4.hpp"
 #include "scan_pq.hpp"
+#include "scan_pq4.hpp"
 #include "filter_rows.hpp"
 #include "scan_groups.hpp"
 #include "append_rows.hpp"
@@ -95,6 +96,8 @@ struct Config : Options {
 	size_t row_bytes() const {
 		if (int_mode == kPlanPQ)
 			return (size_t)pq_m;
+		if (int_mode == kPlanPQ4)  // (two codes a byte)
+			return (size_t)pq_m / 2;
 		return int_mode == kPlanB1Ham ? (size_t)dim / 8 : (int_mode == kPlanI4 ? (size_t)dim / 2 : (size_t)dim * elem);
 	}
 	size_t query_bytes() const { return int_mode == kPlanB1Ham ? (size_t)dim / 8 : (size_t)dim * q_elem; }
@@ -108,9 +111,14 @@ constexpr const char* kI4NotOffered =
 inline bool pq_rows(const Config* h) { return h->int_mode == kPlanPQ; }
 constexpr const char* kPQNotOffered =
     "EXPANN_DTYPE_PQ8 rows: set_codebooks / add / build / set_base_device and expann_search / expann_search_device only";
+inline bool pq4_rows(const Config* h) { return h->int_mode == kPlanPQ4; }
+constexpr const char* kPQ4NotOffered =
+    "EXPANN_DTYPE_PQ4 rows: set_codebooks / add / build / set_base_device and expann_search / expann_search_device only";
+// product-quantised rows of either code width: the refusal's text, or nullptr
+inline const char* pq_not_offered(const Config* h) { return pq_rows(h) ? kPQNotOffered : (pq4_rows(h) ? kPQ4NotOffered : nullptr); }
 // the entry points no kind of packed rows is offered: the refusal's text, or nullptr
 inline const char* packed_not_offered(const Config* h) {
-	return b1_rows(h) ? kB1NotOffered : (i4_rows(h) ? kI4NotOffered : (pq_rows(h) ? kPQNotOffered : nullptr));
+	return b1_rows(h) ? kB1NotOffered : (i4_rows(h) ? kI4NotOffered : pq_not_offered(h));
 }
 
 // the rows: staged on the host until build(), then on the device -- the handle's own copy, or the caller's memory
@@ -292,6 +300,7 @@ struct Stats {
 	uint64_t stat_asym = 0;          // launches of scan_asym_mfma_kernel since create
 	uint64_t stat_i4 = 0;            // launches of scan_i4_mfma_kernel since create
 	uint64_t stat_pq = 0;            // launches of scan_pq_kernel since create
+	uint64_t stat_pq4 = 0;           // launches of scan_pq4_mfma_kernel since create
 };
 
 // streams, events, profiling, statistics, the last error
@@ -311,7 +320,8 @@ struct Runtime : Stats {
 	mutable std::string err;
 };
 
-// product-quantised rows: the codebooks on the device, [pq_m][256][dim / pq_m]; they outlive a change of rows
+// product-quantised rows: the codebooks on the device, [pq_m][256][dim / pq_m] (4-bit codes: [pq_m][16][dim / pq_m]);
+// they outlive a change of rows
 struct Codebooks {
 	DevPtr<float> d_codebooks;
 };
@@ -2203,6 +2213,7 @@ struct SearchPass {
 	bool ham_mfma = false;      // packed-bit rows: scan_hamming_mfma_kernel scans every level (else the VALU form)
 	bool asym = false;          // the query kind: int8 queries [m][dim] on packed-bit rows, scan_asym_mfma_kernel at every level
 	bool i4 = false;            // 4-bit rows: scan_i4_mfma_kernel at every level
+	bool pq4 = false;           // 4-bit product-quantised rows: scan_pq4_mfma_kernel at every level
 	bool i8f = false;          // the int8 filter runs the full scan (fp16 prelude, scan_gemm_i8f.hpp)
 	bool i8f_ready = false;     // its thresholds of this attempt are written
 	bool i8f_ran = false;       // the last level of this attempt ran it
@@ -2242,6 +2253,7 @@ int SearchPass::choose_kernels() {
 		return h->fail(plan.status, plan.message);
 	ham_mfma = b1_rows(h) && plan.family == ScanFamily::kHamming && !asym;
 	i4 = i4_rows(h);
+	pq4 = pq4_rows(h);
 	if (ham_mfma && !h->d_popb) {  // the row term pop(b)
 		HIP_TRY(h, hipMalloc(&h->d_popb, sizeof(int) * h->n));
 		hipLaunchKernelGGL(ham_popcount_kernel, dim3((uint32_t)((h->n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
@@ -2605,6 +2617,52 @@ int SearchPass::run_level(size_t li) {
 		passes = xp.n_qtiles;
 		kname = "scan_i4_mfma";
 		qt_used = kHamTQ;
+	} else if (pq4) {
+		// 4-bit product-quantised rows, level 0 included (the keys of its tiles at fixed slots).  The first level
+		// builds the byte tables, bias and step of every query (steps 1-5 of THE PQ4 RULE; bias and step borrow the
+		// fp16 forms' per-query arrays); the later ones only turn tau into theta.
+		const uint32_t M = (uint32_t)h->pq_m;
+		const int qterm = 128 * (int)M;
+		if (first) {
+			HIP_TRY(h, grow_ws(h, h->d_q8f, m * (size_t)16 * M));
+			hipLaunchKernelGGL(ip ? pq4_tables_kernel<true> : pq4_tables_kernel<false>, dim3((uint32_t)m), dim3(kBlock), 0, st,
+			                   (const float*)d_queries, (const float*)h->d_codebooks.p, M, (uint32_t)h->dim / M, (void*)h->d_q8f,
+			                   h->d_qnrm.p, h->d_qscale.p);
+		} else {
+			hipLaunchKernelGGL(pq4_theta_kernel, dim3((uint32_t)((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+			                   (const float*)sp.tau, (uint32_t)m, qterm, h->d_theta.as<int>());
+		}
+		const AsymTiles tiles = plan_asym_tiles(h->n, L.n_groups_sel * kRowsPerGroup, first, last, cap);
+		PQ4Params xp{};
+		xp.base = h->d_base;
+		xp.n_rows = (uint32_t)h->n;
+		xp.n_tiles_sel = tiles.n_tiles_sel;
+		xp.tile_stride = tiles.tile_stride;
+		xp.n_qtiles = (uint32_t)((m + kHamTQ - 1) / kHamTQ);
+		xp.tables = h->d_q8f;
+		xp.theta = h->d_theta.as<const int>();
+		xp.tau = sp.tau;
+		xp.tau_row = sp.tau_row;
+		xp.m = (uint32_t)m;
+		xp.cand_cnt = h->d_cnt;
+		xp.cand = h->d_cand;
+		xp.cap = cap;
+		xp.M = M;
+		xp.qterm = qterm;
+		xp.level0 = first ? 1u : 0u;
+		ham_fixed = tiles.fixed;
+		// (one or two workgroups per CU are resident: rounds of `cus` workgroups, a prologue of tables each)
+		uint32_t gchunks = pick_row_chunks(xp.n_tiles_sel, xp.n_qtiles, (uint32_t)cus, 1.0, 1, 4096, 0, nullptr);
+		xp.tiles_per_block = (xp.n_tiles_sel + gchunks - 1) / gchunks;
+		gchunks = (xp.n_tiles_sel + xp.tiles_per_block - 1) / xp.tiles_per_block;
+		if (timed)
+			HIP_TRY(h, hipEventRecord(h->ev[h->ev_used][0], st));
+		hipLaunchKernelGGL(pq4_resident(M) ? scan_pq4_mfma_kernel<true> : scan_pq4_mfma_kernel<false>, dim3(gchunks * xp.n_qtiles),
+		                   dim3(kHamThreads), pq4_lds_bytes(M), st, xp);
+		h->stat_pq4++;
+		passes = xp.n_qtiles;
+		kname = "scan_pq4_mfma";
+		qt_used = kHamTQ;
 	} else if (ham_mfma) {
 		// packed-bit rows on the matrix cores, level 0 included (the keys of its tiles at fixed slots)
 		hipLaunchKernelGGL(ham_theta_kernel, dim3((uint32_t)((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d_queries,
@@ -2668,7 +2726,7 @@ int SearchPass::run_level(size_t li) {
 	sel.cand = h->d_cand;
 	sel.cand_cnt = first ? nullptr : h->d_cnt;
 	sel.fixed_count = (first && L.classmin_blocks) ? n_chunks * 16 : L.n_groups_sel * kRowsPerGroup;
-	if (ham_mfma || asym || i4)
+	if (ham_mfma || asym || i4 || pq4)
 		sel.fixed_count = ham_fixed;
 	sel.cap = cap;
 	sel.k = (uint32_t)k;
@@ -2734,6 +2792,11 @@ int SearchPass::run_level(size_t li) {
 		if (m <= 64)
 			sel.wave0_short = 1;  // latency mode: one launch, wave 0 orders the short lists
 		hipLaunchKernelGGL(select_topk_fn(h, sel), dim3((uint32_t)m), dim3(kBlock), sizeof(uint64_t) * cap + 16, st, sel);
+		HIP_TRY(h, hipGetLastError());
+	}
+	if (last && pq4 && d_dists) {  // step 7 of THE PQ4 RULE on the selected (float)S
+		hipLaunchKernelGGL(pq4_finish_kernel, dim3((uint32_t)std::min<size_t>((m * k + kBlock - 1) / kBlock, 1024)), dim3(kBlock), 0, st,
+		                   d_dists, m * k, (uint32_t)k, (const float*)h->d_qnrm.p, (const float*)h->d_qscale.p);
 		HIP_TRY(h, hipGetLastError());
 	}
 	if (last && spec_j)
@@ -3068,7 +3131,9 @@ int search_pass(expann_index* h, const void* d_queries, size_t m, size_t k, uint
 	}
 	if (i4_rows(h))  // (one form, no direct scan: SearchPass::i4 names the kernel)
 		svs = ScanSel{nullptr, kHamTQ, "scan_i4_mfma"};
-	if (!svs.fn && !i4_rows(h))
+	if (pq4_rows(h) && plan.direct_tq)  // (likewise: SearchPass::pq4)
+		svs = ScanSel{nullptr, kHamTQ, "scan_pq4_mfma"};
+	if (!svs.fn && !i4_rows(h) && !(pq4_rows(h) && plan.direct_tq))
 		return h->fail(EXPANN_ERR_UNSUPPORTED,
 		               "no scan kernel for dim " + std::to_string(h->dim) +
 		                   " / query_tile " + std::to_string(h->opt_query_tile));
@@ -3136,6 +3201,19 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 			g_create_error = "unsupported dim " + std::to_string(dim) + ": EXPANN_DTYPE_PQ8 rows take dim <= " + std::to_string(kMaxAnyDim);
 			return EXPANN_ERR_UNSUPPORTED;
 		}
+	} else if (dtype == EXPANN_DTYPE_PQ4) {  // (THE PQ4 RULE: dim = M * dsub, M a multiple of 16)
+		if (metric != EXPANN_METRIC_IP && metric != EXPANN_METRIC_L2) {
+			g_create_error = "EXPANN_DTYPE_PQ4 rows support EXPANN_METRIC_L2 and EXPANN_METRIC_IP only";
+			return EXPANN_ERR_INVALID_ARG;
+		}
+		if (dim < kPlanPQ4MinDim) {
+			g_create_error = "EXPANN_DTYPE_PQ4 rows need dim >= 16";
+			return EXPANN_ERR_INVALID_ARG;
+		}
+		if (dim > kMaxAnyDim) {
+			g_create_error = "unsupported dim " + std::to_string(dim) + ": EXPANN_DTYPE_PQ4 rows take dim <= " + std::to_string(kMaxAnyDim);
+			return EXPANN_ERR_UNSUPPORTED;
+		}
 	} else if (dim <= 0 || dim % 16 != 0) {
 		g_create_error = "dim must be a positive multiple of 16 (the reference kernels require it)";
 		return EXPANN_ERR_INVALID_ARG;
@@ -3184,11 +3262,13 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 		int_mode = kPlanI4;
 	} else if (dtype == EXPANN_DTYPE_PQ8) {  // (checked above)
 		int_mode = kPlanPQ;
+	} else if (dtype == EXPANN_DTYPE_PQ4) {  // (checked above)
+		int_mode = kPlanPQ4;
 	} else {
 		g_create_error = "unknown dtype";
 		return EXPANN_ERR_INVALID_ARG;
 	}
-	if (int_mode >= 0 && int_mode != kPlanPQ && dim % 64 != 0) {
+	if (int_mode >= 0 && int_mode != kPlanPQ && int_mode != kPlanPQ4 && dim % 64 != 0) {
 		g_create_error = "8-bit rows need dim % 64 == 0 (src/distance.h:29-53, antitopo_engine.h:726)";
 		return EXPANN_ERR_INVALID_ARG;
 	}
@@ -3215,7 +3295,7 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 		g_create_error = "internal: bf_plan.hpp does not list the compiled scan kernels";
 		return EXPANN_ERR_UNSUPPORTED;
 	}
-	if (int_mode != kPlanPQ && !direct_tile(px, 1)) {  // (product-quantised rows: the tile waits for M, expann_set_codebooks)
+	if (int_mode != kPlanPQ && int_mode != kPlanPQ4 && !direct_tile(px, 1)) {  // (product-quantised rows: the tile waits for M, expann_set_codebooks)
 		g_create_error = "unsupported dim " + std::to_string(dim) +
 		                 " (built: f32 any multiple of 16 up to 4096; 8-bit any multiple of 64 up to 4096; int16 64,128)";
 		return EXPANN_ERR_UNSUPPORTED;
@@ -3281,6 +3361,10 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 		needs.push_back({(const void*)scan_asym_mfma_kernel, (int)kAsymLdsBytes, "scan_asym_mfma_kernel"});
 	if (int_mode == kPlanI4)
 		needs.push_back({(const void*)scan_i4_mfma_kernel, (int)kI4LdsBytes, "scan_i4_mfma_kernel"});
+	if (int_mode == kPlanPQ4) {  // (the resident form at its largest M; the streamed form's two stages)
+		needs.push_back({(const void*)scan_pq4_mfma_kernel<true>, (int)pq4_lds_bytes(kPQ4ResidentMaxM), "scan_pq4_mfma_kernel"});
+		needs.push_back({(const void*)scan_pq4_mfma_kernel<false>, (int)pq4_lds_bytes(kPlanPQ4MaxM), "scan_pq4_mfma_kernel"});
+	}
 	if (int_mode == kPlanPQ)
 		for (const auto& v : kScanPQ)
 			needs.push_back({(const void*)v.fn, (int)kPlanPQTableBytes, "scan_pq_kernel"});
@@ -3328,14 +3412,25 @@ static int make_i4_rowterm(expann_index* h) {
 }
 
 constexpr const char* kPQNoCodebooks = "EXPANN_DTYPE_PQ8 rows: expann_set_codebooks comes first";
+constexpr const char* kPQ4NoCodebooks = "EXPANN_DTYPE_PQ4 rows: expann_set_codebooks comes first";
 
 int expann_set_codebooks(expann_index* h, const float* codebooks, size_t M) {
 	if (!h)
 		return EXPANN_ERR_INVALID_ARG;
-	if (!pq_rows(h))
+	if (!pq_rows(h) && !pq4_rows(h))
 		return h->fail(EXPANN_ERR_UNSUPPORTED, "expann_set_codebooks: EXPANN_DTYPE_PQ8 rows only");
 	if (h->pq_m || h->d_base || h->n_staged)
 		return h->fail(EXPANN_ERR_INVALID_ARG, "expann_set_codebooks: once, before the first row");
+	if (pq4_rows(h)) {  // (THE PQ4 RULE: 16 centroids per sub-quantiser)
+		if (!codebooks || M > (size_t)kPlanPQ4MaxM || !pq4_shape_ok(h->dim, (int)M))
+			return h->fail(EXPANN_ERR_INVALID_ARG, "expann_set_codebooks: EXPANN_DTYPE_PQ4 codebooks [M][16][dim / M], M a multiple of 16 in [16, 256] that divides dim");
+		HIP_TRY(h, hipSetDevice(h->device));
+		const size_t bytes4 = sizeof(float) * 16 * (size_t)h->dim;  // M * 16 * dsub floats
+		HIP_TRY(h, hipMalloc(&h->d_codebooks, bytes4));
+		HIP_TRY(h, hipMemcpy(h->d_codebooks, codebooks, bytes4, hipMemcpyHostToDevice));
+		h->pq_m = (int)M;
+		return EXPANN_OK;
+	}
 	if (!codebooks || M > (size_t)kPlanPQMaxM || !pq_shape_ok(h->dim, (int)M))
 		return h->fail(EXPANN_ERR_INVALID_ARG, "expann_set_codebooks: codebooks [M][256][dim / M], M a multiple of 8 in [8, 128] that divides dim");
 	HIP_TRY(h, hipSetDevice(h->device));
@@ -3349,8 +3444,8 @@ int expann_set_codebooks(expann_index* h, const float* codebooks, size_t M) {
 int expann_add(expann_index* h, const void* rows, size_t n) {
 	if (!h)
 		return EXPANN_ERR_INVALID_ARG;
-	if (pq_rows(h) && !h->pq_m)
-		return h->fail(EXPANN_ERR_INVALID_ARG, kPQNoCodebooks);
+	if (pq_not_offered(h) && !h->pq_m)
+		return h->fail(EXPANN_ERR_INVALID_ARG, pq4_rows(h) ? kPQ4NoCodebooks : kPQNoCodebooks);
 	if (!rows && n)
 		return h->fail(EXPANN_ERR_INVALID_ARG, "rows == NULL");
 	if (h->d_base)
@@ -3394,8 +3489,8 @@ int expann_build(expann_index* h) {
 int expann_set_base_device(expann_index* h, const void* d_rows, size_t n, uint64_t id_offset) {
 	if (!h)
 		return EXPANN_ERR_INVALID_ARG;
-	if (pq_rows(h) && !h->pq_m)
-		return h->fail(EXPANN_ERR_INVALID_ARG, kPQNoCodebooks);
+	if (pq_not_offered(h) && !h->pq_m)
+		return h->fail(EXPANN_ERR_INVALID_ARG, pq4_rows(h) ? kPQ4NoCodebooks : kPQNoCodebooks);
 	if (!d_rows || n == 0)
 		return h->fail(EXPANN_ERR_INVALID_ARG, "empty device base");
 	if (n >= (1ull << 32) - 32)
@@ -3826,8 +3921,8 @@ int expann_search_device(expann_index* h, const void* d_queries, size_t m, size_
                          uint64_t* d_ids, float* d_dists, void* stream) {
 	if (!h)
 		return EXPANN_ERR_INVALID_ARG;
-	if (pq_rows(h) && !h->pq_m)
-		return h->fail(EXPANN_ERR_INVALID_ARG, kPQNoCodebooks);
+	if (pq_not_offered(h) && !h->pq_m)
+		return h->fail(EXPANN_ERR_INVALID_ARG, pq4_rows(h) ? kPQ4NoCodebooks : kPQNoCodebooks);
 	if (!h->d_base)
 		return h->fail(EXPANN_ERR_NOT_BUILT, "search before build()");
 	if (k == 0)
@@ -3908,8 +4003,8 @@ int expann_search(expann_index* h, const void* queries, size_t m, size_t k, uint
                   float* dists) {
 	if (!h)
 		return EXPANN_ERR_INVALID_ARG;
-	if (pq_rows(h) && !h->pq_m)
-		return h->fail(EXPANN_ERR_INVALID_ARG, kPQNoCodebooks);
+	if (pq_not_offered(h) && !h->pq_m)
+		return h->fail(EXPANN_ERR_INVALID_ARG, pq4_rows(h) ? kPQ4NoCodebooks : kPQNoCodebooks);
 	if (!h->d_base)
 		return h->fail(EXPANN_ERR_NOT_BUILT, "search before build()");
 	if (k == 0)
@@ -3991,8 +4086,8 @@ static int asym_refusal(expann_index* h, const void* queries, size_t k, const ui
 		return h->fail(EXPANN_ERR_INVALID_ARG, "NULL query/ids pointer");
 	if (k == 0)
 		return h->fail(EXPANN_ERR_INVALID_ARG, "k == 0");
-	if (pq_rows(h))
-		return h->fail(EXPANN_ERR_UNSUPPORTED, kPQNotOffered);
+	if (const char* refusal = pq_not_offered(h))
+		return h->fail(EXPANN_ERR_UNSUPPORTED, refusal);
 	const ScanPlan plan = plan_asym(plan_index(h), PlanCall{1, k, plan_start_cap(h->opt_cand_capacity, k, kMaxCap)});
 	if (plan.status != EXPANN_OK)
 		return h->fail(plan.status, plan.message);
@@ -4273,6 +4368,7 @@ int expann_get_stat(expann_index* h, const char* name, uint64_t* out) {
 	    {"asym_mfma_launches", [](H h) { return h->stat_asym; }},
 	    {"i4_mfma_launches", [](H h) { return h->stat_i4; }},
 	    {"pq_launches", [](H h) { return h->stat_pq; }},
+	    {"pq4_launches", [](H h) { return h->stat_pq4; }},
 	    {"pq_m", [](H h) -> uint64_t { return (uint64_t)h->pq_m; }},
 	    {"copies_digest", [](H h) { return copies_digest(const_cast<expann_index*>(h)); }},
 	};
@@ -4341,8 +4437,8 @@ int set_row_filter(expann_index* h, const uint32_t* bits, size_t n_words, bool o
 		return EXPANN_ERR_INVALID_ARG;
 	if (!bits)
 		return h->fail(EXPANN_ERR_INVALID_ARG, "row filter: NULL bits");
-	if (pq_rows(h))
-		return h->fail(EXPANN_ERR_UNSUPPORTED, kPQNotOffered);
+	if (const char* refusal = pq_not_offered(h))
+		return h->fail(EXPANN_ERR_UNSUPPORTED, refusal);
 	if (!float_rows(h))
 		return h->fail(EXPANN_ERR_UNSUPPORTED,
 		               "row filter: fp32 / fp16 rows only (8-bit and int16 rows have integer row terms)");
@@ -4382,8 +4478,8 @@ int set_row_groups(expann_index* h, const uint32_t* groups, size_t n, bool on_de
 		return EXPANN_ERR_INVALID_ARG;
 	if (!groups)
 		return h->fail(EXPANN_ERR_INVALID_ARG, "row groups: NULL labels");
-	if (pq_rows(h))
-		return h->fail(EXPANN_ERR_UNSUPPORTED, kPQNotOffered);
+	if (const char* refusal = pq_not_offered(h))
+		return h->fail(EXPANN_ERR_UNSUPPORTED, refusal);
 	if (!float_rows(h))
 		return h->fail(EXPANN_ERR_UNSUPPORTED,
 		               "row groups: fp32 / fp16 rows only (the filter passes of large groups need the row filter)");
@@ -5082,8 +5178,8 @@ int range_args(expann_index* h, const void* queries, const float* radii, size_t 
 		return h->fail(EXPANN_ERR_INVALID_ARG, "range search: NULL queries / radii / counts / ids pointer");
 	if (max_results > kMaxK)  // (by value, before any GPU work, as k is)
 		return h->fail(EXPANN_ERR_UNSUPPORTED, "range search: max_results beyond " + std::to_string(kMaxK));
-	if (pq_rows(h))
-		return h->fail(EXPANN_ERR_UNSUPPORTED, kPQNotOffered);
+	if (const char* refusal = pq_not_offered(h))
+		return h->fail(EXPANN_ERR_UNSUPPORTED, refusal);
 	if (!float_rows(h))
 		return h->fail(EXPANN_ERR_UNSUPPORTED, "range search: EXPANN_DTYPE_F32 and EXPANN_DTYPE_F16 rows only");
 	if (!h->d_base)

@@ -213,6 +213,10 @@ int common_create(int dim, int dtype, int metric, expann_sharded** out, expann_s
 		g_create_error = "EXPANN_DTYPE_PQ8 rows are not offered by the expann_sharded_* handles";
 		return EXPANN_ERR_UNSUPPORTED;
 	}
+	if (dtype == EXPANN_DTYPE_PQ4) {
+		g_create_error = "EXPANN_DTYPE_PQ4 rows are not offered by the expann_sharded_* handles";
+		return EXPANN_ERR_UNSUPPORTED;
+	}
 	h = new expann_sharded();
 	h->dim = dim;
 	h->dtype = dtype;

@@ -15,11 +15,12 @@ from . import _lib
 
 _NP_DTYPE = {_lib.DTYPE_F32: np.float32, _lib.DTYPE_U8: np.uint8, _lib.DTYPE_I8: np.int8,
              _lib.DTYPE_I16: np.int16, _lib.DTYPE_F16: np.float16, _lib.DTYPE_B1: np.uint8,
-             _lib.DTYPE_I4: np.uint8, _lib.DTYPE_PQ8: np.uint8}
+             _lib.DTYPE_I4: np.uint8, _lib.DTYPE_PQ8: np.uint8, _lib.DTYPE_PQ4: np.uint8}
 _DTYPE = {"f32": _lib.DTYPE_F32, "u8": _lib.DTYPE_U8, "i8": _lib.DTYPE_I8, "i16": _lib.DTYPE_I16,
-          "f16": _lib.DTYPE_F16, "b1": _lib.DTYPE_B1, "i4": _lib.DTYPE_I4, "pq8": _lib.DTYPE_PQ8}
+          "f16": _lib.DTYPE_F16, "b1": _lib.DTYPE_B1, "i4": _lib.DTYPE_I4, "pq8": _lib.DTYPE_PQ8,
+          "pq4": _lib.DTYPE_PQ4}
 # row types whose queries are fp32 at the ABI (the others take queries of the rows' own type)
-_F32_QUERIES = (_lib.DTYPE_F32, _lib.DTYPE_U8, _lib.DTYPE_F16, _lib.DTYPE_PQ8)
+_F32_QUERIES = (_lib.DTYPE_F32, _lib.DTYPE_U8, _lib.DTYPE_F16, _lib.DTYPE_PQ8, _lib.DTYPE_PQ4)
 
 
 def pack_row_filter(allow):
@@ -51,6 +52,25 @@ def unpack_i4(rows):
     return out
 
 
+def pack_pq4(codes):
+    """PQ codes [n, M] in [0, 15] (M even) as the rows of dtype="pq4": uint8 [n, M / 2], code 2 j in the low nibble of
+    byte j and code 2 j + 1 in the high nibble (FAISS's 4-bit packing).  A pure function."""
+    c = np.asarray(codes)
+    if c.ndim != 2 or c.shape[1] % 2 or c.dtype.kind not in "iu" or c.min(initial=0) < 0 or c.max(initial=0) > 15:
+        raise ValueError("codes must be integers [n, M] in [0, 15] with an even M")
+    c = c.astype(np.uint8)
+    return np.ascontiguousarray(c[:, 0::2] | (c[:, 1::2] << 4))
+
+
+def unpack_pq4(rows):
+    """The inverse of pack_pq4: uint8 [n, M / 2] to uint8 codes [n, M] in [0, 15]."""
+    r = np.asarray(rows, dtype=np.uint8)
+    out = np.empty((r.shape[0], 2 * r.shape[1]), dtype=np.uint8)
+    out[:, 0::2] = r & 0x0F
+    out[:, 1::2] = r >> 4
+    return out
+
+
 class GpuBruteForceEngine:
     """Exact k-NN by a full scan on one MI355X (drop-in for brute_force_engine<float>).
 
@@ -75,7 +95,14 @@ class GpuBruteForceEngine:
     operation in a fixed order (THE PQ RULE, include/expann_hip.h): the ids and distance bits are those of a dozen
     lines of float32 NumPy.  The keyword is required for this dtype and refused for every other.  Add, build,
     set_base_device, size and query_k_batch / search_device only; training the codebooks and encoding the rows is
-    the caller's."""
+    the caller's.
+
+    dtype="pq4" with metric "l2" or "ip" and codebooks=array[M, 16, dim / M]: product-quantised rows with 4-bit codes
+    (FAISS's ProductQuantizer(d, M, 4)), M / 2 bytes each, scored on the int8 matrix cores.  Rows are uint8 [n, M / 2]
+    as pack_pq4 packs codes in [0, 15]; queries float32 [m, dim]; M is a multiple of 16 from 16 to 256 that divides
+    dim, 16 <= dim <= 4096.  Each query's tables are quantised to bytes with one step per query (THE PQ4 RULE,
+    include/expann_hip.h); the ids and distance bits are those of its float32 NumPy restatement.  The same entry
+    points as "pq8"."""
 
     def __init__(self, dim, metric="l2", dtype="f32", device=0, codebooks=None):
         self._L = _lib.load()
@@ -86,9 +113,16 @@ class GpuBruteForceEngine:
         # elements of a row, and of a query, at the ABI
         self._cols = {_lib.DTYPE_B1: self.dim // 8, _lib.DTYPE_I4: self.dim // 2}.get(self.dtype, self.dim)
         self._qcols = self.dim if self.dtype == _lib.DTYPE_I4 else self._cols
-        if (self.dtype == _lib.DTYPE_PQ8) != (codebooks is not None):
+        if self.dtype == _lib.DTYPE_PQ4:
+            if codebooks is None:
+                raise ValueError('dtype="pq4" needs codebooks=array[M, 16, dim / M]')
+            codebooks = np.ascontiguousarray(codebooks, dtype=np.float32)
+            if codebooks.ndim != 3 or codebooks.shape[1] != 16 or codebooks.shape[0] * codebooks.shape[2] != self.dim:
+                raise ValueError("codebooks must be [M, 16, dim / M]")
+            self._cols = codebooks.shape[0] // 2
+        elif (self.dtype == _lib.DTYPE_PQ8) != (codebooks is not None):
             raise ValueError('codebooks=array[M, 256, dim / M] goes with dtype="pq8", and only with it')
-        if codebooks is not None:
+        elif codebooks is not None:
             codebooks = np.ascontiguousarray(codebooks, dtype=np.float32)
             if codebooks.ndim != 3 or codebooks.shape[1] != 256 or codebooks.shape[0] * codebooks.shape[2] != self.dim:
                 raise ValueError("codebooks must be [M, 256, dim / M]")
@@ -351,6 +385,7 @@ class GpuBruteForceEngine:
         "asym_mfma_launches" (packed-bit rows, int8 queries: launches of scan_asym_mfma_kernel since create);
         "i4_mfma_launches" (4-bit rows: launches of scan_i4_mfma_kernel since create);
         "pq_launches", "pq_m" (product-quantised rows: launches of scan_pq_kernel since create; codes per row);
+        "pq4_launches" (4-bit product-quantised rows: launches of scan_pq4_mfma_kernel since create);
         "groups_active", "group_count", and of the last grouped search "group_list_queries", "group_filter_queries",
         "group_any_queries", "group_pad_queries", "group_filter_passes";
         of the last range search "range_list_queries", "range_topk_queries", "range_retries";

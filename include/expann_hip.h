@@ -50,7 +50,8 @@ enum expann_dtype {
 	                       * nothing that existed changed)                            */
 	EXPANN_DTYPE_B1 = 5,  /* packed bits under EXPANN_METRIC_HAMMING, see below (appended likewise) */
 	EXPANN_DTYPE_I4 = 6,  /* 4-bit rows against int8 queries, THE I4 RULE below (appended likewise) */
-	EXPANN_DTYPE_PQ8 = 7  /* product-quantised rows, M one-byte codes, THE PQ RULE below (appended likewise) */
+	EXPANN_DTYPE_PQ8 = 7, /* product-quantised rows, M one-byte codes, THE PQ RULE below (appended likewise) */
+	EXPANN_DTYPE_PQ4 = 8  /* product-quantised rows, M 4-bit codes, THE PQ4 RULE below (appended likewise) */
 };
 /* EXPANN_DTYPE_PQ8: product-quantised rows scored by lookup tables (ADC), 16 to 64 times smaller than fp32 rows.
  * THE PQ RULE.  `dim` counts the elements of a query: 8 <= dim <= 4096 (below 8: EXPANN_ERR_INVALID_ARG; over 4096:
@@ -80,7 +81,43 @@ enum expann_dtype {
  * range search, expann_append* and expann_reserve, expann_remove* and expann_compact_row_filter, expann_score_ids,
  * expann_search_asym_i8, the expann_sharded_* handles, and deferred searches (expann_search_device under
  * "async_search" = 1).  The C++ engine classes of include/expann/ do not take the dtype either.  Out of scope:
- * training codebooks and encoding rows (the caller brings both), other code widths, residual / IVF forms, re-ranking. */
+ * training codebooks and encoding rows (the caller brings both), code widths other than 8 and 4 bits (EXPANN_DTYPE_PQ4 below), residual / IVF forms, re-ranking. */
+/* EXPANN_DTYPE_PQ4: product-quantised rows with 4-bit codes (FAISS's ProductQuantizer(d, M, 4), the format behind its
+ * "fast scan" indexes), scored on the int8 matrix cores: with 16 centroids per sub-quantiser the ADC sum is the dot
+ * product of the query's byte tables with the row's one-hot vector.
+ * THE PQ4 RULE.  `dim` counts the elements of a query: 16 <= dim <= 4096 (below 16: EXPANN_ERR_INVALID_ARG; over 4096:
+ * EXPANN_ERR_UNSUPPORTED; both before the device is touched).  Codebooks: expann_set_codebooks(h, codebooks, M), once,
+ * before the first row; `codebooks` is host memory float [M][16][dsub] with dsub = dim / M; M is a multiple of 16 from
+ * 16 to 256 that divides dim.  Rows are uint8_t [n][M / 2]: code 2 j is the low nibble of byte j, code 2 j + 1 the
+ * high one (FAISS's 4-bit packing).  Rows adopted by expann_set_base_device are 8-byte aligned.  Queries are
+ * float [m][dim].  Every codebook and query value is finite, and so is every value below.
+ * Metrics: EXPANN_METRIC_L2 and EXPANN_METRIC_IP; anything else is EXPANN_ERR_INVALID_ARG from expann_create.
+ * Every line is ONE fp32 operation rounded to nearest, never contracted to an FMA:
+ *   1. Tables.  L2:  T[i][c] = 0.0f; for j = 0 .. dsub-1 in order:  t = q[i*dsub + j] - cb[i][c][j];  T[i][c] = T[i][c] + t*t
+ *               IP:  P = 0.0f; for j in order:  P = P + q[i*dsub + j] * cb[i][c][j];  then  T[i][c] = 0.0f - P
+ *      (smaller is better under both metrics; no entry is -0.0).
+ *   2. lo_i = min_c T[i][c].   span = max_i (max_c T[i][c] - lo_i).
+ *   3. If span > 0:  r = 255.0f / span  and  step = span / 255.0f, both IEEE divisions.  Otherwise r = step = 0.0f.
+ *   4. u[i][c] = min(255, rint((T[i][c] - lo_i) * r)), ties to even: an integer in [0, 255].
+ *   5. bias = (..((lo_0 + lo_1) + lo_2) .. + lo_{M-1}).
+ *   6. S(row) = sum_i u[i][code_i], an exact integer, at most 255 * 256 = 65 280.
+ *   7. The reported distance is  bias + step * (float)S : one multiply, one add.
+ * Results ascend by (S, id), ties to the lower id; 1 <= k <= 8192; lists shorter than k are padded with UINT64_MAX /
+ * +inf as everywhere.  (float)S is exact, so the ranking is the integer's; the distances of step 7 are written after
+ * the selection.  The rule is what a float32 NumPy restatement computes, and the tests compare ids and distance bits
+ * with exactly that.
+ * Precision: one global step per query and per-sub-quantiser offsets, which is FAISS fast-scan's choice; the table
+ * entries lose up to half a step each.  Sixteen-bit tables (two int8 planes), re-ranking, training the codebooks and
+ * encoding the rows are out of scope.
+ * Served: expann_create, expann_set_codebooks, expann_add, expann_build, expann_set_base_device (with id_offset),
+ * expann_size, expann_search and expann_search_device with the synchronous overflow check, expann_get_stat
+ * ("base_bytes" = n * M / 2; "pq_m" = M; "pq4_launches" = launches of scan_pq4_mfma_kernel since create) and
+ * expann_set_option ("scan_kernel" is not read).  One kernel serves every m >= 1 and every M (scan_pq4_mfma_kernel,
+ * DESIGN.md 4.6p).  A search before expann_set_codebooks, and rows offered before it, are EXPANN_ERR_INVALID_ARG.
+ * NOT offered, each EXPANN_ERR_UNSUPPORTED with a message and the handle untouched: the row filter and row groups,
+ * range search, expann_append* and expann_reserve, expann_remove* and expann_compact_row_filter, expann_score_ids,
+ * expann_search_asym_i8, the expann_sharded_* handles, and deferred searches (expann_search_device under
+ * "async_search" = 1).  The C++ engine classes of include/expann/ do not take the dtype either. */
 /* EXPANN_DTYPE_I4: 4-bit scalar-quantised rows, half the bytes of EXPANN_DTYPE_I8, scored against int8 queries.
  * THE I4 RULE.  `dim` counts elements: any multiple of 64 from 64 to 4096 (not a multiple of 64:
  * EXPANN_ERR_INVALID_ARG; over 4096: EXPANN_ERR_UNSUPPORTED; both before the device is touched).  A row is dim / 2
@@ -238,7 +275,9 @@ int expann_search_asym_i8_device(expann_index* h, const int8_t* d_queries, size_
 /* The codebooks of an EXPANN_DTYPE_PQ8 handle (THE PQ RULE above): host memory float [M][256][dim / M], copied to
  * the device before the call returns.  Once per handle, before any row: a second call, a call after expann_add or
  * expann_set_base_device, NULL codebooks, or an M that is not a multiple of 8 in [8, 128] dividing dim is
- * EXPANN_ERR_INVALID_ARG; a handle of any other dtype is EXPANN_ERR_UNSUPPORTED. */
+ * EXPANN_ERR_INVALID_ARG; a handle of any other dtype is EXPANN_ERR_UNSUPPORTED.
+ * An EXPANN_DTYPE_PQ4 handle (THE PQ4 RULE) reads float [M][16][dim / M] under the same conditions, M a multiple of 16
+ * in [16, 256] dividing dim. */
 int expann_set_codebooks(expann_index* h, const float* codebooks, size_t M);
 
 /* k-way merge of per-shard results after an all-gather (RCCL): in_ids/in_dists are
