@@ -5,8 +5,9 @@ into libexpann_hip.so) and the host-side mirror of the reference's engine interf
 """
 from . import _lib  # noqa: F401
 from .engine import (GpuBruteForceEngine, ShardedBruteForceEngine, merge_topk_device,  # noqa: F401
-                     merge_topk_strided_device, pack_i4, pack_pq4, pack_row_filter, unpack_i4, unpack_pq4)
+                     merge_topk_strided_device, pack_i4, pack_pq4, pack_row_filter, train_pq_codebooks,
+                     unpack_i4, unpack_pq4)
 from .pyrunner import AntitopoEngine  # noqa: F401
 
 __all__ = ["GpuBruteForceEngine", "ShardedBruteForceEngine", "merge_topk_device", "merge_topk_strided_device", "AntitopoEngine",
-           "pack_row_filter", "pack_i4", "unpack_i4", "pack_pq4", "unpack_pq4"]
+           "pack_row_filter", "pack_i4", "unpack_i4", "pack_pq4", "unpack_pq4", "train_pq_codebooks"]

@@ -60,6 +60,7 @@ ABI_SYMBOLS = [
     "expann_antitopo_remove", "expann_antitopo_compact_row_filter", "expann_graph_remove",
     "expann_graph_note_host_remove", "expann_graph_read_row_filter",
     "expann_search_asym_i8", "expann_search_asym_i8_device", "expann_set_codebooks",
+    "expann_pq_encode", "expann_pq_encode_device", "expann_pq_train",
 ]
 GROUP_ANY = 0xFFFFFFFF  # EXPANN_GROUP_ANY: the group a query names to search every row
 
@@ -169,6 +170,13 @@ def load():
     if hasattr(L, "expann_set_codebooks"):
         L.expann_set_codebooks.restype = C.c_int
         L.expann_set_codebooks.argtypes = [vp, vp, sz]
+    if hasattr(L, "expann_pq_encode"):  # (as above: an older build has no encoder)
+        L.expann_pq_encode.restype = C.c_int
+        L.expann_pq_encode.argtypes = [vp, vp, sz, vp]
+        L.expann_pq_encode_device.restype = C.c_int
+        L.expann_pq_encode_device.argtypes = [vp, vp, sz, vp, vp]
+        L.expann_pq_train.restype = C.c_int
+        L.expann_pq_train.argtypes = [C.c_int, vp, sz, sz, sz, C.c_int, sz, vp]
     L.expann_merge_topk_device.restype = C.c_int
     L.expann_merge_topk_device.argtypes = [C.c_int, vp, vp, sz, sz, sz, vp, vp, vp]
     L.expann_merge_topk_strided_device.restype = C.c_int

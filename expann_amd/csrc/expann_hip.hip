@@ -42,6 +42,7 @@
 #include "scan_i4.hpp"
 #include "scan_pq.hpp"
 #include "scan_pq4.hpp"
+#include "pq_encode.hpp"
 #include "filter_rows.hpp"
 #include "scan_groups.hpp"
 #include "append_rows.hpp"
@@ -301,6 +302,7 @@ struct Stats {
 	uint64_t stat_i4 = 0;            // launches of scan_i4_mfma_kernel since create
 	uint64_t stat_pq = 0;            // launches of scan_pq_kernel since create
 	uint64_t stat_pq4 = 0;           // launches of scan_pq4_mfma_kernel since create
+	uint64_t stat_pq_encode = 0;     // launches of pq_encode_kernel since create
 };
 
 // streams, events, profiling, statistics, the last error
@@ -324,6 +326,7 @@ struct Runtime : Stats {
 // they outlive a change of rows
 struct Codebooks {
 	DevPtr<float> d_codebooks;
+	DevPtr<float> d_codebooks_t;  // [pq_m][dim / pq_m][ncent], what pq_encode_kernel reads: made by the first expann_pq_encode*
 };
 
 // (base order: the streams and events outlive every buffer when a handle is deleted)
@@ -3441,6 +3444,140 @@ int expann_set_codebooks(expann_index* h, const float* codebooks, size_t M) {
 	return EXPANN_OK;
 }
 
+// ---- codes and codebooks from fp32 rows (THE ENCODE RULE, THE TRAIN RULE; pq_encode.hpp) ----------
+extern "C++" {
+namespace {
+constexpr size_t kPQTrainMaxRows = (size_t)1 << 24, kPQTrainMaxIters = 1000;
+constexpr size_t kPQEncodeStageBytes = (size_t)64 << 20;  // fp32 rows the host form of expann_pq_encode stages at a time
+
+void launch_pq_transpose(const float* d_cb, float* d_cbt, uint32_t M, uint32_t ncent, uint32_t dsub, hipStream_t st) {
+	const uint32_t total = M * ncent * dsub;
+	hipLaunchKernelGGL(pq_transpose_kernel, dim3(std::min<uint32_t>((total + kBlock - 1) / kBlock, 1024)), dim3(kBlock), 0, st, d_cb,
+	                   d_cbt, M, ncent, dsub);
+}
+// n rows (1 <= n < 2^32) against the transposed codebooks: the codes, their transposed copy, or both
+void launch_pq_encode(uint32_t ncent, const float* d_rows, const float* d_cbt, uint8_t* d_codes, uint8_t* d_codes_t, size_t n,
+                      uint32_t dim, uint32_t M, hipStream_t st) {
+	const dim3 grid((uint32_t)((n + kEncRows - 1) / kEncRows), (M + kEncGroup - 1) / kEncGroup);
+	hipLaunchKernelGGL(ncent == 16 ? pq_encode_kernel<16> : pq_encode_kernel<256>, grid, dim3(kBlock), 0, st, d_rows, d_cbt, d_codes,
+	                   d_codes_t, (uint32_t)n, dim, M);
+}
+inline uint32_t pq_ncent(const expann_index* h) { return pq4_rows(h) ? 16u : 256u; }
+}  // namespace
+}  // extern "C++"
+
+int expann_pq_encode_device(expann_index* h, const float* d_rows, size_t n, uint8_t* d_codes, void* stream) {
+	if (!h)
+		return EXPANN_ERR_INVALID_ARG;
+	if (!pq_rows(h) && !pq4_rows(h))
+		return h->fail(EXPANN_ERR_UNSUPPORTED, "expann_pq_encode: EXPANN_DTYPE_PQ8 and EXPANN_DTYPE_PQ4 handles only");
+	if (!h->pq_m)
+		return h->fail(EXPANN_ERR_INVALID_ARG, pq4_rows(h) ? kPQ4NoCodebooks : kPQNoCodebooks);
+	if (n == 0)
+		return EXPANN_OK;
+	if (!d_rows || !d_codes)
+		return h->fail(EXPANN_ERR_INVALID_ARG, "expann_pq_encode: NULL rows / codes pointer");
+	if (((uintptr_t)d_rows | (uintptr_t)d_codes) & 15)
+		return h->fail(EXPANN_ERR_INVALID_ARG, "expann_pq_encode_device: rows and codes must be 16-byte aligned");
+	if (n >= (1ull << 32) - 32)
+		return h->fail(EXPANN_ERR_UNSUPPORTED, "more than 2^32 rows per call");
+	HIP_TRY(h, hipSetDevice(h->device));
+	hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+	const uint32_t M = (uint32_t)h->pq_m, ncent = pq_ncent(h), dsub = (uint32_t)h->dim / M;
+	if (!h->d_codebooks_t) {
+		HIP_TRY(h, hipMalloc(&h->d_codebooks_t, sizeof(float) * ncent * (size_t)h->dim));
+		launch_pq_transpose(h->d_codebooks, h->d_codebooks_t, M, ncent, dsub, st);
+		HIP_TRY(h, hipGetLastError());
+		HIP_TRY(h, hipStreamSynchronize(st));  // (a later call may come on another stream)
+	}
+	launch_pq_encode(ncent, d_rows, h->d_codebooks_t, d_codes, nullptr, n, (uint32_t)h->dim, M, st);
+	HIP_TRY(h, hipGetLastError());
+	h->stat_pq_encode++;
+	HIP_TRY(h, hipStreamSynchronize(st));
+	return EXPANN_OK;
+}
+
+int expann_pq_encode(expann_index* h, const float* rows, size_t n, uint8_t* codes) {
+	if (!h)
+		return EXPANN_ERR_INVALID_ARG;
+	if (!pq_rows(h) && !pq4_rows(h))
+		return h->fail(EXPANN_ERR_UNSUPPORTED, "expann_pq_encode: EXPANN_DTYPE_PQ8 and EXPANN_DTYPE_PQ4 handles only");
+	if (!h->pq_m)
+		return h->fail(EXPANN_ERR_INVALID_ARG, pq4_rows(h) ? kPQ4NoCodebooks : kPQNoCodebooks);
+	if (n == 0)
+		return EXPANN_OK;
+	if (!rows || !codes)
+		return h->fail(EXPANN_ERR_INVALID_ARG, "expann_pq_encode: NULL rows / codes pointer");
+	HIP_TRY(h, hipSetDevice(h->device));
+	// staged in pieces of at most kPQEncodeStageBytes of rows (a multiple of the kernel's row tile)
+	const size_t in_row = sizeof(float) * (size_t)h->dim, out_row = h->row_bytes();
+	const size_t piece = std::min(n, std::max<size_t>(kEncRows, kPQEncodeStageBytes / in_row / kEncRows * kEncRows));
+	DevBuf d_in, d_out;
+	HIP_TRY(h, d_in.alloc(piece * in_row));
+	HIP_TRY(h, d_out.alloc(piece * out_row));
+	for (size_t r0 = 0; r0 < n; r0 += piece) {
+		const size_t cnt = std::min(piece, n - r0);
+		HIP_TRY(h, hipMemcpyAsync(d_in.p, rows + r0 * (size_t)h->dim, cnt * in_row, hipMemcpyHostToDevice, h->stream));
+		if (const int rc = expann_pq_encode_device(h, d_in.as<float>(), cnt, d_out.as<uint8_t>(), nullptr))
+			return rc;
+		HIP_TRY(h, hipMemcpy(codes + r0 * out_row, d_out.p, cnt * out_row, hipMemcpyDeviceToHost));
+	}
+	return EXPANN_OK;
+}
+
+int expann_pq_train(int device, const float* rows, size_t n, size_t dim, size_t M, int code_bits, size_t iters, float* codebooks) {
+	auto refuse = [](const char* why) {
+		g_create_error = std::string("expann_pq_train: ") + why;
+		return EXPANN_ERR_INVALID_ARG;
+	};
+	if (!rows || !codebooks)
+		return refuse("NULL rows / codebooks pointer");
+	if (code_bits != 8 && code_bits != 4)
+		return refuse("code_bits is 8 or 4");
+	if (dim > (size_t)kMaxAnyDim || M > (size_t)kPlanPQ4MaxM || !(code_bits == 8 ? pq_shape_ok((int)dim, (int)M) : pq4_shape_ok((int)dim, (int)M)))
+		return refuse(code_bits == 8 ? "M a multiple of 8 in [8, 128] that divides dim, 8 <= dim <= 4096"
+		                             : "M a multiple of 16 in [16, 256] that divides dim, 16 <= dim <= 4096");
+	const uint32_t ncent = code_bits == 8 ? 256u : 16u;
+	if (n < ncent || n > kPQTrainMaxRows)
+		return refuse("ncent <= n <= 2^24 training rows");
+	if (iters > kPQTrainMaxIters)
+		return refuse("iters <= 1000");
+	auto hip = [](hipError_t e, const char* what) {
+		if (e != hipSuccess)
+			g_create_error = std::string("expann_pq_train: ") + what + ": " + hipGetErrorString(e);
+		return e != hipSuccess;
+	};
+	if (expann_device_count() < 1) {
+		g_create_error = "no HIP device (there is no CPU fallback)";
+		return EXPANN_ERR_NO_DEVICE;
+	}
+	if (hip(hipSetDevice(device), "hipSetDevice"))
+		return EXPANN_ERR_HIP;
+	const size_t cb_bytes = sizeof(float) * ncent * dim;
+	const uint32_t dsub = (uint32_t)(dim / M);
+	DevBuf d_x, d_cb, d_cbt, d_codes_t;
+	if (hip(d_x.alloc(sizeof(float) * n * dim), "hipMalloc(rows)") || hip(d_cb.alloc(cb_bytes), "hipMalloc(codebooks)") ||
+	    hip(d_cbt.alloc(cb_bytes), "hipMalloc(codebooks)") || hip(d_codes_t.alloc(M * n), "hipMalloc(codes)"))
+		return EXPANN_ERR_HIP;
+	if (hip(hipMemcpy(d_x.p, rows, sizeof(float) * n * dim, hipMemcpyHostToDevice), "hipMemcpy(rows)"))
+		return EXPANN_ERR_HIP;
+	hipStream_t st = nullptr;
+	hipLaunchKernelGGL(pq_init_kernel, dim3(std::min<uint32_t>((uint32_t)((ncent * dim + kBlock - 1) / kBlock), 1024)), dim3(kBlock), 0, st,
+	                   d_x.as<float>(), d_cb.as<float>(), (uint32_t)n, (uint32_t)dim, (uint32_t)M, ncent);
+	for (size_t it = 0; it < iters; ++it) {
+		launch_pq_transpose(d_cb.as<float>(), d_cbt.as<float>(), (uint32_t)M, ncent, dsub, st);
+		launch_pq_encode(ncent, d_x.as<float>(), d_cbt.as<float>(), nullptr, d_codes_t.as<uint8_t>(), n, (uint32_t)dim, (uint32_t)M, st);
+		hipLaunchKernelGGL(pq_update_kernel, dim3((uint32_t)((M * ncent + kBlock / 64 - 1) / (kBlock / 64))), dim3(kBlock), 0, st,
+		                   d_x.as<float>(), d_codes_t.as<uint8_t>(), d_cb.as<float>(), (uint32_t)n, (uint32_t)dim, (uint32_t)M, ncent);
+		if (hip(hipGetLastError(), "launch"))
+			return EXPANN_ERR_HIP;
+	}
+	if (hip(hipGetLastError(), "launch") || hip(hipStreamSynchronize(st), "hipStreamSynchronize") ||
+	    hip(hipMemcpy(codebooks, d_cb.p, cb_bytes, hipMemcpyDeviceToHost), "hipMemcpy(codebooks)"))
+		return EXPANN_ERR_HIP;
+	return EXPANN_OK;
+}
+
 int expann_add(expann_index* h, const void* rows, size_t n) {
 	if (!h)
 		return EXPANN_ERR_INVALID_ARG;
@@ -4369,6 +4506,7 @@ int expann_get_stat(expann_index* h, const char* name, uint64_t* out) {
 	    {"i4_mfma_launches", [](H h) { return h->stat_i4; }},
 	    {"pq_launches", [](H h) { return h->stat_pq; }},
 	    {"pq4_launches", [](H h) { return h->stat_pq4; }},
+	    {"pq_encode_launches", [](H h) { return h->stat_pq_encode; }},
 	    {"pq_m", [](H h) -> uint64_t { return (uint64_t)h->pq_m; }},
 	    {"copies_digest", [](H h) { return copies_digest(const_cast<expann_index*>(h)); }},
 	};

@@ -33,15 +33,16 @@ namespace expann {
 constexpr int kPQRowsStep = kBlock;  // rows of a workgroup step: one per lane
 __host__ __device__ constexpr uint32_t pq_lds_bytes(uint32_t tq, uint32_t M) { return tq * M * 256u * 4u; }
 
-// one step of a table entry, THE PQ RULE: every operation rounds by itself
-template <bool IP> __device__ __attribute__((always_inline)) inline float pq_term(float T, float q, float c) {
+// one step of a table entry, THE PQ RULE: every operation rounds by itself (F: float, or a vector of floats taken
+// element by element -- pq_encode.hpp steps two centroids at once)
+template <bool IP, typename F = float> __device__ __attribute__((always_inline)) inline F pq_term(F T, F q, F c) {
 #pragma clang fp contract(off)
 	if (IP) {
-		const float pr = q * c;
+		const F pr = q * c;
 		return T + pr;
 	}
-	const float t = q - c;
-	const float sq = t * t;
+	const F t = q - c;
+	const F sq = t * t;
 	return T + sq;
 }
 

@@ -71,6 +71,21 @@ def unpack_pq4(rows):
     return out
 
 
+def train_pq_codebooks(rows, M, code_bits=8, iters=20, device=0):
+    """expann_pq_train: the codebooks array[M, ncent, dim / M] (float32; ncent = 256 for code_bits=8, 16 for
+    code_bits=4) of a product quantiser trained on rows [n, dim] (float32, finite) by THE TRAIN RULE of
+    include/expann_hip.h: k-means per sub-quantiser, the initial centroids rows floor(c n / ncent), `iters` rounds of
+    exact assignment and fp64 means in row order, empty clusters left as they are -- deterministic, bit for bit what
+    its NumPy restatement gives.  ncent <= n <= 2^24, iters <= 1000; (dim, M) as dtype "pq8" / "pq4" ask."""
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    if rows.ndim != 2 or code_bits not in (8, 4) or M <= 0 or rows.shape[1] % M:
+        raise ValueError("rows must be [n, dim] with M dividing dim, code_bits 8 or 4")
+    cb = np.empty((M, 256 if code_bits == 8 else 16, rows.shape[1] // M), dtype=np.float32)
+    _lib.check(None, _lib.load().expann_pq_train(int(device), rows.ctypes.data, rows.shape[0], rows.shape[1], int(M),
+                                                 int(code_bits), int(iters), cb.ctypes.data))
+    return cb
+
+
 class GpuBruteForceEngine:
     """Exact k-NN by a full scan on one MI355X (drop-in for brute_force_engine<float>).
 
@@ -94,15 +109,15 @@ class GpuBruteForceEngine:
     8 <= dim <= 4096.  The score is the sum of M entries of per-query lookup tables, every step one float32
     operation in a fixed order (THE PQ RULE, include/expann_hip.h): the ids and distance bits are those of a dozen
     lines of float32 NumPy.  The keyword is required for this dtype and refused for every other.  Add, build,
-    set_base_device, size and query_k_batch / search_device only; training the codebooks and encoding the rows is
-    the caller's.
+    set_base_device, size, query_k_batch / search_device and encode / encode_device only.  From float32 rows:
+    codebooks = train_pq_codebooks(rows, M, 8), then store_many_vectors(encode(rows)).
 
     dtype="pq4" with metric "l2" or "ip" and codebooks=array[M, 16, dim / M]: product-quantised rows with 4-bit codes
     (FAISS's ProductQuantizer(d, M, 4)), M / 2 bytes each, scored on the int8 matrix cores.  Rows are uint8 [n, M / 2]
     as pack_pq4 packs codes in [0, 15]; queries float32 [m, dim]; M is a multiple of 16 from 16 to 256 that divides
     dim, 16 <= dim <= 4096.  Each query's tables are quantised to bytes with one step per query (THE PQ4 RULE,
     include/expann_hip.h); the ids and distance bits are those of its float32 NumPy restatement.  The same entry
-    points as "pq8"."""
+    points as "pq8" (train_pq_codebooks(rows, M, 4); encode returns the packed rows)."""
 
     def __init__(self, dim, metric="l2", dtype="f32", device=0, codebooks=None):
         self._L = _lib.load()
@@ -160,6 +175,24 @@ class GpuBruteForceEngine:
             raise ValueError(f"rows must be [n, {self._cols}]")
         call = self._L.expann_append if self._built else self._L.expann_add
         _lib.check(self._h, call(self._h, rows.ctypes.data, rows.shape[0]))
+
+    def encode(self, rows_f32):
+        """expann_pq_encode (dtype "pq8" / "pq4"): float32 rows [n, dim] to the codes store_many_vectors takes --
+        uint8 [n, M], or [n, M / 2] packed as pack_pq4 packs -- by THE ENCODE RULE of include/expann_hip.h: per
+        sub-quantiser the nearest centroid in L2, float32 operations in a fixed order, ties to the lower centroid.
+        The index itself is not touched."""
+        rows = np.ascontiguousarray(rows_f32, dtype=np.float32)
+        if rows.ndim != 2 or rows.shape[1] != self.dim:
+            raise ValueError(f"rows must be [n, {self.dim}]")
+        codes = np.empty((rows.shape[0], self._cols), dtype=np.uint8)
+        _lib.check(self._h, self._L.expann_pq_encode(self._h, rows.ctypes.data, rows.shape[0], codes.ctypes.data))
+        return codes
+
+    def encode_device(self, rows_ptr, n, codes_ptr, stream=0):
+        """expann_pq_encode_device: n float32 rows and the codes are device pointers, 16-byte aligned; returns after
+        `stream` has drained."""
+        _lib.check(self._h, self._L.expann_pq_encode_device(self._h, C.c_void_p(rows_ptr), int(n), C.c_void_p(codes_ptr),
+                                                            C.c_void_p(stream)))
 
     def build(self):
         """src/brute_force_engine.h:24-26 (asserts a non-empty index): upload to HBM."""
@@ -386,6 +419,7 @@ class GpuBruteForceEngine:
         "i4_mfma_launches" (4-bit rows: launches of scan_i4_mfma_kernel since create);
         "pq_launches", "pq_m" (product-quantised rows: launches of scan_pq_kernel since create; codes per row);
         "pq4_launches" (4-bit product-quantised rows: launches of scan_pq4_mfma_kernel since create);
+        "pq_encode_launches" (launches of pq_encode_kernel since create: encode / encode_device);
         "groups_active", "group_count", and of the last grouped search "group_list_queries", "group_filter_queries",
         "group_any_queries", "group_pad_queries", "group_filter_passes";
         of the last range search "range_list_queries", "range_topk_queries", "range_retries";

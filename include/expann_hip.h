@@ -80,8 +80,27 @@ enum expann_dtype {
  * NOT offered, each EXPANN_ERR_UNSUPPORTED with a message and the handle untouched: the row filter and row groups,
  * range search, expann_append* and expann_reserve, expann_remove* and expann_compact_row_filter, expann_score_ids,
  * expann_search_asym_i8, the expann_sharded_* handles, and deferred searches (expann_search_device under
- * "async_search" = 1).  The C++ engine classes of include/expann/ do not take the dtype either.  Out of scope:
- * training codebooks and encoding rows (the caller brings both), code widths other than 8 and 4 bits (EXPANN_DTYPE_PQ4 below), residual / IVF forms, re-ranking. */
+ * "async_search" = 1).  The C++ engine classes of include/expann/ do not take the dtype either.  Codebooks and codes
+ * from fp32 rows: expann_pq_train and expann_pq_encode (THE TRAIN RULE, THE ENCODE RULE below).  Out of scope:
+ * code widths other than 8 and 4 bits (EXPANN_DTYPE_PQ4 below), residual / IVF forms, re-ranking.
+ * THE ENCODE RULE.  ncent is 256 for EXPANN_DTYPE_PQ8 and 16 for EXPANN_DTYPE_PQ4, dsub = dim / M; x is a finite row
+ * float [dim], cb the codebooks float [M][ncent][dsub].  For sub-quantiser i and centroid c, D[i][c] is the L2 table
+ * entry of THE PQ RULE with the row as the query -- every operation ONE fp32 operation rounded to nearest, never
+ * contracted to an FMA:
+ *     D[i][c] = 0.0f; for j = 0 .. dsub-1 in order:  t = x[i*dsub + j] - cb[i][c][j];  D[i][c] = D[i][c] + t*t
+ *     code_i = the SMALLEST c that minimises D[i][c]
+ * L2 whatever the handle's metric is, as FAISS does: the code minimises the reconstruction error.  PQ8 codes are
+ * uint8_t [n][M]; PQ4 codes uint8_t [n][M / 2], code 2 j in the low nibble of byte j (the rows of THE PQ4 RULE).
+ * THE TRAIN RULE.  Training rows X float [n][dim], finite; M, ncent, iters.
+ *     init:  centroid c of sub-quantiser i is sub-vector i of row floor(c * n / ncent), computed in 64-bit integers.
+ *     then iters times:
+ *       (a) every row is encoded by THE ENCODE RULE against the current codebooks;
+ *       (b) for every (i, c) with cnt rows assigned: cnt == 0 leaves the centroid as it is; otherwise for every j:
+ *           s = 0.0 (double); for the assigned rows r in ASCENDING order  s = s + (double)X[r][i*dsub + j];
+ *           the centroid becomes (float)(s / (double)cnt).
+ * Both rules are what a few lines of NumPy compute (np.cumsum in float64 is the sequential sum), and the tests compare
+ * code bytes and codebook bits with exactly that.  Out of scope: splitting empty clusters, k-means++, sampling of the
+ * training rows, OPQ. */
 /* EXPANN_DTYPE_PQ4: product-quantised rows with 4-bit codes (FAISS's ProductQuantizer(d, M, 4), the format behind its
  * "fast scan" indexes), scored on the int8 matrix cores: with 16 centroids per sub-quantiser the ADC sum is the dot
  * product of the query's byte tables with the row's one-hot vector.
@@ -107,8 +126,8 @@ enum expann_dtype {
  * the selection.  The rule is what a float32 NumPy restatement computes, and the tests compare ids and distance bits
  * with exactly that.
  * Precision: one global step per query and per-sub-quantiser offsets, which is FAISS fast-scan's choice; the table
- * entries lose up to half a step each.  Sixteen-bit tables (two int8 planes), re-ranking, training the codebooks and
- * encoding the rows are out of scope.
+ * entries lose up to half a step each.  Sixteen-bit tables (two int8 planes) and re-ranking are out of scope; codebooks
+ * and rows come from fp32 data by expann_pq_train and expann_pq_encode (THE TRAIN RULE, THE ENCODE RULE above).
  * Served: expann_create, expann_set_codebooks, expann_add, expann_build, expann_set_base_device (with id_offset),
  * expann_size, expann_search and expann_search_device with the synchronous overflow check, expann_get_stat
  * ("base_bytes" = n * M / 2; "pq_m" = M; "pq4_launches" = launches of scan_pq4_mfma_kernel since create) and
@@ -279,6 +298,26 @@ int expann_search_asym_i8_device(expann_index* h, const int8_t* d_queries, size_
  * An EXPANN_DTYPE_PQ4 handle (THE PQ4 RULE) reads float [M][16][dim / M] under the same conditions, M a multiple of 16
  * in [16, 256] dividing dim. */
 int expann_set_codebooks(expann_index* h, const float* codebooks, size_t M);
+
+/* THE ENCODE RULE on an EXPANN_DTYPE_PQ8 / EXPANN_DTYPE_PQ4 handle after expann_set_codebooks, before or after
+ * expann_build: `rows` float [n][dim] (finite) to `codes` uint8_t [n][M] / [n][M / 2], what expann_add takes.  The
+ * handle's own rows are not touched.  A handle of any other dtype is EXPANN_ERR_UNSUPPORTED; no codebooks yet or a NULL
+ * pointer EXPANN_ERR_INVALID_ARG; n = 0 is EXPANN_OK.  The host form stages the rows in pieces of at most 64 MB, so a
+ * large n needs no n * dim * 4 device bytes.  The _device form takes device pointers, both 16-byte aligned (else
+ * EXPANN_ERR_INVALID_ARG), n < 2^32 - 32, is enqueued on `stream` (NULL = the index's own) and returns after the stream
+ * has drained.  One kernel on the vector ALUs (pq_encode_kernel); expann_get_stat "pq_encode_launches"
+ * = its launches since create. */
+int expann_pq_encode(expann_index* h, const float* rows, size_t n, uint8_t* codes);
+int expann_pq_encode_device(expann_index* h, const float* d_rows, size_t n, uint8_t* d_codes, void* stream);
+
+/* THE TRAIN RULE on device `device`, without a handle: `rows` float [n][dim] and `codebooks` float [M][ncent][dim / M]
+ * (written) are host memory; the caller then creates a handle and passes the codebooks to expann_set_codebooks.
+ * code_bits is 8 (ncent = 256; dim and M as THE PQ RULE asks) or 4 (ncent = 16; as THE PQ4 RULE asks);
+ * ncent <= n <= 2^24; iters <= 1000 (0: the initial centroids).  Anything else, or a NULL pointer, is
+ * EXPANN_ERR_INVALID_ARG before the device is touched (message: expann_last_error(NULL)).  The rows stay on the device
+ * for the call: n * (dim * 4 + M) bytes. */
+int expann_pq_train(int device, const float* rows, size_t n, size_t dim, size_t M, int code_bits, size_t iters,
+                    float* codebooks);
 
 /* k-way merge of per-shard results after an all-gather (RCCL): in_ids/in_dists are
  * [n_lists][m][k], each row ascending by (score, id) and padded as above; out is [m][k].
