@@ -354,7 +354,7 @@ inline ScanPlan plan_hamming(const PlanIndex& x, const PlanCall& c, const PlanAt
 // tie restart.  c.cap is the lists' starting capacity (plan_start_cap).  "scan_kernel" is not read: it chooses among
 // the Hamming forms.
 constexpr size_t kPlanAsymMaxK = 8192;
-constexpr uint32_t kPlanAsymTile = 512;  // rows of a tile (kHamTB)
+constexpr uint32_t kPlanAsymTile = 512;  // rows of a tile (kHamTB: scan_tile.hpp asserts it)
 constexpr const char* kRefuseAsymRows = "expann_search_asym_i8: EXPANN_DTYPE_B1 rows only";
 constexpr const char* kRefuseAsymK = "expann_search_asym_i8: k is at most 8192 (half the longest candidate list)";
 inline ScanPlan plan_asym(const PlanIndex& x, const PlanCall& c) {
@@ -366,7 +366,7 @@ inline ScanPlan plan_asym(const PlanIndex& x, const PlanCall& c) {
 		p.status = EXPANN_ERR_UNSUPPORTED;
 		p.message = kRefuseAsymK;
 	} else {
-		p.family = ScanFamily::kHamming;  // (the threshold ladder over packed-bit rows; SearchPass::asym names the kernel)
+		p.family = ScanFamily::kHamming;  // (the threshold ladder over packed-bit rows; SearchPass::tile = kAsym names the kernel)
 	}
 	return p;
 }
@@ -387,7 +387,7 @@ constexpr AsymTiles plan_asym_tiles(size_t n, uint32_t sel_rows, bool first, boo
 // 4-bit rows (EXPANN_DTYPE_I4, THE I4 RULE): one form, scan_i4_mfma_kernel (scan_i4.hpp), for every m >= 1 and every
 // dim the rows can have, under both metrics; like plan_asym's it scans every level of the ladder and keeps (score, row)
 // <= the proven threshold key: no sampled pass, no speculation, no tie restart.  "scan_kernel" is not read.  Its tiles
-// are the asymmetric search's: plan_i4_tiles.
+// are the asymmetric search's, plan_asym_tiles.
 constexpr const char* kRefuseI4Rows = "scan_i4: EXPANN_DTYPE_I4 rows under EXPANN_METRIC_IP or EXPANN_METRIC_L2 only";
 constexpr const char* kRefuseI4K = "EXPANN_DTYPE_I4 rows: k is at most 8192 (half the longest candidate list)";
 inline ScanPlan plan_i4(const PlanIndex& x, const PlanCall& c) {
@@ -403,9 +403,6 @@ inline ScanPlan plan_i4(const PlanIndex& x, const PlanCall& c) {
 		p.family = ScanFamily::kHamming;  // (the threshold ladder on the int8 matrix cores; the row mode names the kernel)
 	}
 	return p;
-}
-constexpr AsymTiles plan_i4_tiles(size_t n, uint32_t sel_rows, bool first, bool last, uint32_t cap) {
-	return plan_asym_tiles(n, sel_rows, first, last, cap);  // (the same 512-row tiles and fixed slots)
 }
 
 // Product-quantised rows: one exact form, scan_pq_kernel, under the direct scan's contract -- the direct family with

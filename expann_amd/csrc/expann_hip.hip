@@ -2194,6 +2194,42 @@ struct ScanSel {
 	const char* name = "";
 	ScanFn fn_bits = nullptr, fn_list = nullptr;  // (f32 rows: the row filter's instances)
 };
+// The packed-row scans of the 512-row-tile geometry (scan_tile.hpp).  A search that takes one of them runs it at every
+// level of the ladder, level 0 included (the keys of its tiles at fixed slots).
+enum class TileForm { kNone, kHamming, kAsym, kI4, kPQ4 };
+using TileScanFn = void (*)(TileScanParams);
+struct TileFormInfo {
+	TileForm form;
+	int int_mode;                          // the rows it scans
+	const char* profile;                   // the profile's "scan_kernel"
+	const char* label;                     // the kernel's name in expann_create's message
+	uint64_t& (*launches)(expann_index*);  // its launches since create
+	uint32_t (*lds)(uint32_t klen);        // dynamic LDS bytes at a reduction length (dim; M of 4-bit PQ)
+	TileScanFn kernel;                     // serves klen <= klen_max
+	uint32_t klen_max;
+	TileScanFn kernel_above;               // serves klen in (klen_max, klen_above_max]; nullptr: none
+	uint32_t klen_above_max;
+};
+constexpr TileFormInfo kTileForms[] = {
+    {TileForm::kHamming, kPlanB1Ham, "scan_hamming_mfma", "scan_hamming_mfma_kernel", [](expann_index* h) -> uint64_t& { return h->stat_ham[0]; },
+     [](uint32_t dim) { return ham_mfma_lds_bytes(dim); }, scan_hamming_mfma_kernel, kPlanHamMfmaMaxDim, nullptr, 0},
+    {TileForm::kAsym, kPlanB1Ham, "scan_asym_mfma", "scan_asym_mfma_kernel", [](expann_index* h) -> uint64_t& { return h->stat_asym; },
+     [](uint32_t) { return kAsymLdsBytes; }, scan_asym_mfma_kernel, kPlanMaxDim, nullptr, 0},
+    {TileForm::kI4, kPlanI4, "scan_i4_mfma", "scan_i4_mfma_kernel", [](expann_index* h) -> uint64_t& { return h->stat_i4; },
+     [](uint32_t) { return kI4LdsBytes; }, scan_i4_mfma_kernel, kPlanMaxDim, nullptr, 0},
+    // (the resident tables up to kPQ4ResidentMaxM, the streamed form's two stages above)
+    {TileForm::kPQ4, kPlanPQ4, "scan_pq4_mfma", "scan_pq4_mfma_kernel", [](expann_index* h) -> uint64_t& { return h->stat_pq4; },
+     [](uint32_t M) { return pq4_lds_bytes(M); }, scan_pq4_mfma_kernel<true>, kPQ4ResidentMaxM, scan_pq4_mfma_kernel<false>, kPlanPQ4MaxM},
+};
+// (row f - 1 is form f)
+static_assert(std::size(kTileForms) == 4 && kTileForms[0].form == TileForm::kHamming && kTileForms[1].form == TileForm::kAsym &&
+                  kTileForms[2].form == TileForm::kI4 && kTileForms[3].form == TileForm::kPQ4,
+              "kTileForms is indexed by the enum");
+struct TileLaunch {  // what a tile form's launch leaves for the profile and the select
+	uint32_t passes, qt_used, fixed;
+	const char* kname;
+};
+
 struct SearchPass {
 	expann_index* h;
 	const void* d_queries;
@@ -2213,10 +2249,9 @@ struct SearchPass {
 	const GemmBf16Variant* gvb = nullptr;
 	const GemmF16Variant* gvf = nullptr;
 	const DirectF16Variant* dv = nullptr;  // fp16 form: scan_direct_f16 serves the last level and the sampled pass
-	bool ham_mfma = false;      // packed-bit rows: scan_hamming_mfma_kernel scans every level (else the VALU form)
-	bool asym = false;          // the query kind: int8 queries [m][dim] on packed-bit rows, scan_asym_mfma_kernel at every level
-	bool i4 = false;            // 4-bit rows: scan_i4_mfma_kernel at every level
-	bool pq4 = false;           // 4-bit product-quantised rows: scan_pq4_mfma_kernel at every level
+	// the tile form that scans every level.  kAsym is the query kind, set by the caller (int8 queries [m][dim] on
+	// packed-bit rows); the others follow from the rows (packed bits: kHamming, else the VALU form scans)
+	TileForm tile = TileForm::kNone;
 	bool i8f = false;          // the int8 filter runs the full scan (fp16 prelude, scan_gemm_i8f.hpp)
 	bool i8f_ready = false;     // its thresholds of this attempt are written
 	bool i8f_ran = false;       // the last level of this attempt ran it
@@ -2233,8 +2268,10 @@ struct SearchPass {
 
 	enum Next { kDone, kRestart, kRetry };
 	ScanPlan replan() const {
-		return asym ? plan_asym(plan_index(h), PlanCall{m, k, cap}) : plan_scan(plan_index(h), PlanCall{m, k, cap}, learned);
+		return tile == TileForm::kAsym ? plan_asym(plan_index(h), PlanCall{m, k, cap})
+		                               : plan_scan(plan_index(h), PlanCall{m, k, cap}, learned);
 	}
+	int launch_tile_scan(TileScanParams tp, const Level& L, bool first, bool last, bool timed, TileLaunch& out);
 	int choose_kernels();
 	int prepare_queries(bool* restart);
 	int plan_thresholds();
@@ -2254,10 +2291,10 @@ int SearchPass::choose_kernels() {
 	}
 	if (plan.status != EXPANN_OK)
 		return h->fail(plan.status, plan.message);
-	ham_mfma = b1_rows(h) && plan.family == ScanFamily::kHamming && !asym;
-	i4 = i4_rows(h);
-	pq4 = pq4_rows(h);
-	if (ham_mfma && !h->d_popb) {  // the row term pop(b)
+	if (tile != TileForm::kAsym)
+		tile = (b1_rows(h) && plan.family == ScanFamily::kHamming) ? TileForm::kHamming
+		       : (i4_rows(h) ? TileForm::kI4 : (pq4_rows(h) ? TileForm::kPQ4 : TileForm::kNone));
+	if (tile == TileForm::kHamming && !h->d_popb) {  // the row term pop(b)
 		HIP_TRY(h, hipMalloc(&h->d_popb, sizeof(int) * h->n));
 		hipLaunchKernelGGL(ham_popcount_kernel, dim3((uint32_t)((h->n + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
 		                   (const void*)h->d_base, (uint32_t)h->n, (uint32_t)h->dim, h->d_popb.p);
@@ -2396,6 +2433,35 @@ int SearchPass::plan_thresholds() {
 	return EXPANN_OK;
 }
 
+// The launch the tile forms share: the tiles of the level (plan_asym_tiles), the common fields, the row chunks, the
+// timed event, the kernel of the form's table row and its counter.
+int SearchPass::launch_tile_scan(TileScanParams tp, const Level& L, bool first, bool last, bool timed, TileLaunch& out) {
+	const TileFormInfo& info = kTileForms[(int)tile - 1];
+	const AsymTiles tiles = plan_asym_tiles(h->n, L.n_groups_sel * kRowsPerGroup, first, last, cap);
+	tp.base = h->d_base;
+	tp.n_rows = (uint32_t)h->n;
+	tp.n_tiles_sel = tiles.n_tiles_sel;
+	tp.tile_stride = tiles.tile_stride;
+	tp.n_qtiles = (uint32_t)((m + kHamTQ - 1) / kHamTQ);
+	tp.m = (uint32_t)m;
+	tp.cand_cnt = h->d_cnt;
+	tp.cand = h->d_cand;
+	tp.cap = cap;
+	tp.level0 = first ? 1u : 0u;
+	// (one workgroup per CU is resident, two with small PQ4 tables: rounds of `cus` workgroups, a stage or the tables
+	// of prologue each)
+	uint32_t gchunks = pick_row_chunks(tp.n_tiles_sel, tp.n_qtiles, (uint32_t)cus, 1.0, 1, 4096, 0, nullptr);
+	tp.tiles_per_block = (tp.n_tiles_sel + gchunks - 1) / gchunks;
+	gchunks = (tp.n_tiles_sel + tp.tiles_per_block - 1) / tp.tiles_per_block;
+	if (timed)
+		HIP_TRY(h, hipEventRecord(h->ev[h->ev_used][0], st));
+	hipLaunchKernelGGL(tp.klen <= info.klen_max ? info.kernel : info.kernel_above, dim3(gchunks * tp.n_qtiles), dim3(kHamThreads),
+	                   info.lds(tp.klen), st, tp);
+	info.launches(h)++;
+	out = TileLaunch{tp.n_qtiles, (uint32_t)kHamTQ, tiles.fixed, info.profile};
+	return EXPANN_OK;
+}
+
 int SearchPass::run_level(size_t li) {
 	const Level& L = levels[li];
 	const bool first = (li == 0), last = (li + 1 == levels.size());
@@ -2450,7 +2516,7 @@ int SearchPass::run_level(size_t li) {
 	uint32_t passes = n_qtiles;
 	const char* kname = sv->name;
 	uint32_t qt_used = (uint32_t)sv->tq;
-	uint32_t ham_fixed = 0;  // packed-bit rows, matrix-core forms: the keys their level 0 leaves per query
+	uint32_t ham_fixed = 0;  // tile forms: the keys their level 0 leaves per query
 	if (use_gemm) {
 		// theta_q = tau_q - ||q||^2 (1-eps), then the MFMA filter over 128-row tiles
 		const float f16_abs = gvf ? std::ldexp(1.0f, -24) / h->f16_scale * std::sqrt((float)h->dim)
@@ -2549,158 +2615,55 @@ int SearchPass::run_level(size_t li) {
 		passes = gp.n_qtiles;
 		kname = gvi->name;
 		qt_used = kGemmI8TQ;
-	} else if (asym) {
-		// int8 queries on packed-bit rows, level 0 included (the keys of its tiles at fixed slots)
-		hipLaunchKernelGGL(asym_theta_kernel, dim3((uint32_t)((m + kBlock / 16 - 1) / (kBlock / 16))), dim3(kBlock), 0, st,
-		                   d_queries, (uint32_t)m, (uint32_t)h->dim, (const float*)sp.tau, h->d_theta.as<int>(), h->d_qself.p);
-		const AsymTiles tiles = plan_asym_tiles(h->n, L.n_groups_sel * kRowsPerGroup, first, last, cap);
-		AsymParams ap{};
-		ap.base = h->d_base;
-		ap.n_rows = (uint32_t)h->n;
-		ap.n_tiles_sel = tiles.n_tiles_sel;
-		ap.tile_stride = tiles.tile_stride;
-		ap.n_qtiles = (uint32_t)((m + kHamTQ - 1) / kHamTQ);
-		ap.queries = d_queries;
-		ap.theta = h->d_theta.as<const int>();
-		ap.sumq = h->d_qself;
-		ap.tau_row = sp.tau_row;
-		ap.m = (uint32_t)m;
-		ap.cand_cnt = h->d_cnt;
-		ap.cand = h->d_cand;
-		ap.cap = cap;
-		ap.dim = (uint32_t)h->dim;
-		ap.level0 = first ? 1u : 0u;
-		ham_fixed = tiles.fixed;
-		// (one workgroup per CU is resident: rounds of `cus` workgroups, a stage of prologue each)
-		uint32_t gchunks = pick_row_chunks(ap.n_tiles_sel, ap.n_qtiles, (uint32_t)cus, 1.0, 1, 4096, 0, nullptr);
-		ap.tiles_per_block = (ap.n_tiles_sel + gchunks - 1) / gchunks;
-		gchunks = (ap.n_tiles_sel + ap.tiles_per_block - 1) / ap.tiles_per_block;
-		if (timed)
-			HIP_TRY(h, hipEventRecord(h->ev[h->ev_used][0], st));
-		hipLaunchKernelGGL(scan_asym_mfma_kernel, dim3(gchunks * ap.n_qtiles), dim3(kHamThreads), kAsymLdsBytes, st, ap);
-		h->stat_asym++;
-		passes = ap.n_qtiles;
-		kname = "scan_asym_mfma";
-		qt_used = kHamTQ;
-	} else if (i4) {
-		// 4-bit rows, level 0 included (the keys of its tiles at fixed slots): the permuted queries and the per-query
-		// terms, then the scan
-		HIP_TRY(h, grow_ws(h, h->d_q8f, m * (size_t)h->dim));
-		hipLaunchKernelGGL(i4_theta_kernel, dim3((uint32_t)((m + kBlock / 16 - 1) / (kBlock / 16))), dim3(kBlock), 0, st,
-		                   d_queries, (uint32_t)m, (uint32_t)h->dim, ip ? 0 : 1, (const float*)sp.tau, (void*)h->d_q8f,
-		                   h->d_theta.as<int>(), h->d_qself.p);
-		const AsymTiles tiles = plan_i4_tiles(h->n, L.n_groups_sel * kRowsPerGroup, first, last, cap);
-		I4Params xp{};
-		xp.base = h->d_base;
-		xp.rowterm = ip ? nullptr : h->d_i4_rowterm.p;
-		xp.n_rows = (uint32_t)h->n;
-		xp.n_tiles_sel = tiles.n_tiles_sel;
-		xp.tile_stride = tiles.tile_stride;
-		xp.n_qtiles = (uint32_t)((m + kHamTQ - 1) / kHamTQ);
-		xp.queries = h->d_q8f;
-		xp.theta = h->d_theta.as<const int>();
-		xp.qterm = h->d_qself;
-		xp.tau = sp.tau;
-		xp.tau_row = sp.tau_row;
-		xp.m = (uint32_t)m;
-		xp.cand_cnt = h->d_cnt;
-		xp.cand = h->d_cand;
-		xp.cap = cap;
-		xp.dim = (uint32_t)h->dim;
-		xp.level0 = first ? 1u : 0u;
-		ham_fixed = tiles.fixed;
-		// (one workgroup per CU is resident: rounds of `cus` workgroups, a stage of prologue each)
-		uint32_t gchunks = pick_row_chunks(xp.n_tiles_sel, xp.n_qtiles, (uint32_t)cus, 1.0, 1, 4096, 0, nullptr);
-		xp.tiles_per_block = (xp.n_tiles_sel + gchunks - 1) / gchunks;
-		gchunks = (xp.n_tiles_sel + xp.tiles_per_block - 1) / xp.tiles_per_block;
-		if (timed)
-			HIP_TRY(h, hipEventRecord(h->ev[h->ev_used][0], st));
-		hipLaunchKernelGGL(scan_i4_mfma_kernel, dim3(gchunks * xp.n_qtiles), dim3(kHamThreads), kI4LdsBytes, st, xp);
-		h->stat_i4++;
-		passes = xp.n_qtiles;
-		kname = "scan_i4_mfma";
-		qt_used = kHamTQ;
-	} else if (pq4) {
-		// 4-bit product-quantised rows, level 0 included (the keys of its tiles at fixed slots).  The first level
-		// builds the byte tables, bias and step of every query (steps 1-5 of THE PQ4 RULE; bias and step borrow the
-		// fp16 forms' per-query arrays); the later ones only turn tau into theta.
-		const uint32_t M = (uint32_t)h->pq_m;
-		const int qterm = 128 * (int)M;
-		if (first) {
-			HIP_TRY(h, grow_ws(h, h->d_q8f, m * (size_t)16 * M));
-			hipLaunchKernelGGL(ip ? pq4_tables_kernel<true> : pq4_tables_kernel<false>, dim3((uint32_t)m), dim3(kBlock), 0, st,
-			                   (const float*)d_queries, (const float*)h->d_codebooks.p, M, (uint32_t)h->dim / M, (void*)h->d_q8f,
-			                   h->d_qnrm.p, h->d_qscale.p);
+	} else if (tile != TileForm::kNone) {
+		// a tile form: its own prep and operands, then the launch they share
+		TileScanParams tp{};
+		tp.a_operand = d_queries;
+		tp.theta = h->d_theta.as<const int>();
+		tp.qterm = h->d_qself;
+		tp.tau = sp.tau;
+		tp.tau_row = sp.tau_row;
+		tp.klen = (uint32_t)h->dim;
+		const dim3 per16((uint32_t)((m + kBlock / 16 - 1) / (kBlock / 16))), per1((uint32_t)((m + kBlock - 1) / kBlock));
+		if (tile == TileForm::kHamming) {
+			tp.rowterm = h->d_popb;
+			hipLaunchKernelGGL(ham_theta_kernel, per1, dim3(kBlock), 0, st, d_queries, (uint32_t)m, (uint32_t)h->dim,
+			                   (const float*)sp.tau, h->d_theta.as<int>(), h->d_qself.p);
+		} else if (tile == TileForm::kAsym) {
+			hipLaunchKernelGGL(asym_theta_kernel, per16, dim3(kBlock), 0, st, d_queries, (uint32_t)m, (uint32_t)h->dim,
+			                   (const float*)sp.tau, h->d_theta.as<int>(), h->d_qself.p);
+		} else if (tile == TileForm::kI4) {  // the permuted queries and the per-query terms
+			HIP_TRY(h, grow_ws(h, h->d_q8f, m * (size_t)h->dim));
+			hipLaunchKernelGGL(i4_theta_kernel, per16, dim3(kBlock), 0, st, d_queries, (uint32_t)m, (uint32_t)h->dim, ip ? 0 : 1,
+			                   (const float*)sp.tau, (void*)h->d_q8f, h->d_theta.as<int>(), h->d_qself.p);
+			tp.rowterm = ip ? nullptr : h->d_i4_rowterm.p;
+			tp.a_operand = h->d_q8f;
 		} else {
-			hipLaunchKernelGGL(pq4_theta_kernel, dim3((uint32_t)((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
-			                   (const float*)sp.tau, (uint32_t)m, qterm, h->d_theta.as<int>());
+			// 4-bit PQ.  The first level builds the byte tables, bias and step of every query (steps 1-5 of THE PQ4 RULE;
+			// bias and step borrow the fp16 forms' per-query arrays); the later ones only turn tau into theta.
+			const uint32_t M = (uint32_t)h->pq_m;
+			tp.klen = M;
+			tp.qterm = nullptr;
+			tp.qterm_const = 128 * (int)M;
+			if (first) {
+				HIP_TRY(h, grow_ws(h, h->d_q8f, m * (size_t)16 * M));
+				hipLaunchKernelGGL(ip ? pq4_tables_kernel<true> : pq4_tables_kernel<false>, dim3((uint32_t)m), dim3(kBlock), 0, st,
+				                   (const float*)d_queries, (const float*)h->d_codebooks.p, M, (uint32_t)h->dim / M, (void*)h->d_q8f,
+				                   h->d_qnrm.p, h->d_qscale.p);
+			} else {
+				hipLaunchKernelGGL(pq4_theta_kernel, per1, dim3(kBlock), 0, st, (const float*)sp.tau, (uint32_t)m, tp.qterm_const,
+				                   h->d_theta.as<int>());
+			}
+			tp.a_operand = h->d_q8f;
 		}
-		const AsymTiles tiles = plan_asym_tiles(h->n, L.n_groups_sel * kRowsPerGroup, first, last, cap);
-		PQ4Params xp{};
-		xp.base = h->d_base;
-		xp.n_rows = (uint32_t)h->n;
-		xp.n_tiles_sel = tiles.n_tiles_sel;
-		xp.tile_stride = tiles.tile_stride;
-		xp.n_qtiles = (uint32_t)((m + kHamTQ - 1) / kHamTQ);
-		xp.tables = h->d_q8f;
-		xp.theta = h->d_theta.as<const int>();
-		xp.tau = sp.tau;
-		xp.tau_row = sp.tau_row;
-		xp.m = (uint32_t)m;
-		xp.cand_cnt = h->d_cnt;
-		xp.cand = h->d_cand;
-		xp.cap = cap;
-		xp.M = M;
-		xp.qterm = qterm;
-		xp.level0 = first ? 1u : 0u;
-		ham_fixed = tiles.fixed;
-		// (one or two workgroups per CU are resident: rounds of `cus` workgroups, a prologue of tables each)
-		uint32_t gchunks = pick_row_chunks(xp.n_tiles_sel, xp.n_qtiles, (uint32_t)cus, 1.0, 1, 4096, 0, nullptr);
-		xp.tiles_per_block = (xp.n_tiles_sel + gchunks - 1) / gchunks;
-		gchunks = (xp.n_tiles_sel + xp.tiles_per_block - 1) / xp.tiles_per_block;
-		if (timed)
-			HIP_TRY(h, hipEventRecord(h->ev[h->ev_used][0], st));
-		hipLaunchKernelGGL(pq4_resident(M) ? scan_pq4_mfma_kernel<true> : scan_pq4_mfma_kernel<false>, dim3(gchunks * xp.n_qtiles),
-		                   dim3(kHamThreads), pq4_lds_bytes(M), st, xp);
-		h->stat_pq4++;
-		passes = xp.n_qtiles;
-		kname = "scan_pq4_mfma";
-		qt_used = kHamTQ;
-	} else if (ham_mfma) {
-		// packed-bit rows on the matrix cores, level 0 included (the keys of its tiles at fixed slots)
-		hipLaunchKernelGGL(ham_theta_kernel, dim3((uint32_t)((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, d_queries,
-		                   (uint32_t)m, (uint32_t)h->dim, (const float*)sp.tau, h->d_theta.as<int>(), h->d_qself.p);
-		HamMfmaParams hp{};
-		hp.base = h->d_base;
-		hp.popb = h->d_popb;
-		hp.n_rows = (uint32_t)h->n;
-		const uint32_t n_tiles = (uint32_t)((h->n + kHamTB - 1) / kHamTB), sel_rows = L.n_groups_sel * kRowsPerGroup;
-		hp.n_tiles_sel = last ? n_tiles
-		                      : (first ? std::max<uint32_t>(1, sel_rows / kHamTB) : std::min(n_tiles, (sel_rows + kHamTB - 1) / kHamTB));
-		hp.tile_stride = std::max<uint32_t>(1, n_tiles / hp.n_tiles_sel);
-		hp.n_qtiles = (uint32_t)((m + kHamTQ - 1) / kHamTQ);
-		hp.queries = d_queries;
-		hp.theta = h->d_theta.as<const int>();
-		hp.popq = h->d_qself;
-		hp.tau_row = sp.tau_row;
-		hp.m = (uint32_t)m;
-		hp.cand_cnt = h->d_cnt;
-		hp.cand = h->d_cand;
-		hp.cap = cap;
-		hp.dim = (uint32_t)h->dim;
-		hp.level0 = first ? 1u : 0u;
-		ham_fixed = std::min<uint32_t>(hp.n_tiles_sel * kHamTB, cap);
-		uint32_t gchunks = pick_row_chunks(hp.n_tiles_sel, hp.n_qtiles, (uint32_t)cus, 1.0, 1, 4096, 0, nullptr);
-		hp.tiles_per_block = (hp.n_tiles_sel + gchunks - 1) / gchunks;
-		gchunks = (hp.n_tiles_sel + hp.tiles_per_block - 1) / hp.tiles_per_block;
-		if (timed)
-			HIP_TRY(h, hipEventRecord(h->ev[h->ev_used][0], st));
-		hipLaunchKernelGGL(scan_hamming_mfma_kernel, dim3(gchunks * hp.n_qtiles), dim3(kHamThreads),
-		                   ham_mfma_lds_bytes((uint32_t)h->dim), st, hp);
-		h->stat_ham[0]++;
-		passes = hp.n_qtiles;
-		kname = "scan_hamming_mfma";
-		qt_used = kHamTQ;
+		TileLaunch tl{};
+		const int rl = launch_tile_scan(tp, L, first, last, timed, tl);
+		if (rl != EXPANN_OK)
+			return rl;
+		passes = tl.passes;
+		kname = tl.kname;
+		qt_used = tl.qt_used;
+		ham_fixed = tl.fixed;
 	} else {
 		if (b1_rows(h))
 			h->stat_ham[1]++;
@@ -2729,7 +2692,7 @@ int SearchPass::run_level(size_t li) {
 	sel.cand = h->d_cand;
 	sel.cand_cnt = first ? nullptr : h->d_cnt;
 	sel.fixed_count = (first && L.classmin_blocks) ? n_chunks * 16 : L.n_groups_sel * kRowsPerGroup;
-	if (ham_mfma || asym || i4 || pq4)
+	if (tile != TileForm::kNone)
 		sel.fixed_count = ham_fixed;
 	sel.cap = cap;
 	sel.k = (uint32_t)k;
@@ -2797,7 +2760,7 @@ int SearchPass::run_level(size_t li) {
 		hipLaunchKernelGGL(select_topk_fn(h, sel), dim3((uint32_t)m), dim3(kBlock), sizeof(uint64_t) * cap + 16, st, sel);
 		HIP_TRY(h, hipGetLastError());
 	}
-	if (last && pq4 && d_dists) {  // step 7 of THE PQ4 RULE on the selected (float)S
+	if (last && tile == TileForm::kPQ4 && d_dists) {  // step 7 of THE PQ4 RULE on the selected (float)S
 		hipLaunchKernelGGL(pq4_finish_kernel, dim3((uint32_t)std::min<size_t>((m * k + kBlock - 1) / kBlock, 1024)), dim3(kBlock), 0, st,
 		                   d_dists, m * k, (uint32_t)k, (const float*)h->d_qnrm.p, (const float*)h->d_qscale.p);
 		HIP_TRY(h, hipGetLastError());
@@ -3132,9 +3095,9 @@ int search_pass(expann_index* h, const void* d_queries, size_t m, size_t k, uint
 		if (const ScanI8Variant* v = find_scan_i8(h->dim, h->int_mode, plan.direct_tq))
 			svs = ScanSel{v->fn, v->tq, v->name};
 	}
-	if (i4_rows(h))  // (one form, no direct scan: SearchPass::i4 names the kernel)
+	if (i4_rows(h))  // (one form, no direct scan: SearchPass::tile names the kernel)
 		svs = ScanSel{nullptr, kHamTQ, "scan_i4_mfma"};
-	if (pq4_rows(h) && plan.direct_tq)  // (likewise: SearchPass::pq4)
+	if (pq4_rows(h) && plan.direct_tq)  // (likewise)
 		svs = ScanSel{nullptr, kHamTQ, "scan_pq4_mfma"};
 	if (!svs.fn && !i4_rows(h) && !(pq4_rows(h) && plan.direct_tq))
 		return h->fail(EXPANN_ERR_UNSUPPORTED,
@@ -3358,16 +3321,14 @@ int expann_create(int dim, int dtype, int metric, int device, expann_index** out
 				needs.push_back({(const void*)v.scan_w, v.lds_w, "scan_gemm_kl_kernel, int8"});
 				needs.push_back({(const void*)v.sample_w, v.lds_w, "scan_gemm_kl_kernel, int8"});
 			}
-	if (int_mode == kPlanB1Ham && dim <= kPlanHamMfmaMaxDim)
-		needs.push_back({(const void*)scan_hamming_mfma_kernel, (int)ham_mfma_lds_bytes((uint32_t)dim), "scan_hamming_mfma_kernel"});
-	if (int_mode == kPlanB1Ham)
-		needs.push_back({(const void*)scan_asym_mfma_kernel, (int)kAsymLdsBytes, "scan_asym_mfma_kernel"});
-	if (int_mode == kPlanI4)
-		needs.push_back({(const void*)scan_i4_mfma_kernel, (int)kI4LdsBytes, "scan_i4_mfma_kernel"});
-	if (int_mode == kPlanPQ4) {  // (the resident form at its largest M; the streamed form's two stages)
-		needs.push_back({(const void*)scan_pq4_mfma_kernel<true>, (int)pq4_lds_bytes(kPQ4ResidentMaxM), "scan_pq4_mfma_kernel"});
-		needs.push_back({(const void*)scan_pq4_mfma_kernel<false>, (int)pq4_lds_bytes(kPlanPQ4MaxM), "scan_pq4_mfma_kernel"});
-	}
+	for (const TileFormInfo& t : kTileForms)
+		if (t.int_mode == int_mode) {  // (4-bit PQ: M comes with the codebooks; each kernel at its largest M)
+			const uint32_t klen = int_mode == kPlanPQ4 ? t.klen_max : (uint32_t)dim;
+			if (klen <= t.klen_max)
+				needs.push_back({(const void*)t.kernel, (int)t.lds(klen), t.label});
+			if (t.kernel_above)
+				needs.push_back({(const void*)t.kernel_above, (int)t.lds(t.klen_above_max), t.label});
+		}
 	if (int_mode == kPlanPQ)
 		for (const auto& v : kScanPQ)
 			needs.push_back({(const void*)v.fn, (int)kPlanPQTableBytes, "scan_pq_kernel"});
@@ -4251,7 +4212,7 @@ int expann_search_asym_i8_device(expann_index* h, const int8_t* d_queries, size_
 		const size_t mm = std::min(kMaxQueriesPerPass, m - q0);
 		SearchPass pass{h, d_queries + q0 * (size_t)h->dim, mm, k, d_ids + q0 * k, d_dists ? d_dists + q0 * k : nullptr, st,
 		                false, cus, plan_start_cap(h->opt_cand_capacity, k, kMaxCap), ScanSel{nullptr, kHamTQ, "scan_asym_mfma"}};
-		pass.asym = true;
+		pass.tile = TileForm::kAsym;
 		const int rc = pass.run();
 		if (rc != EXPANN_OK)
 			return rc;

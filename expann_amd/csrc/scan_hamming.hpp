@@ -29,26 +29,18 @@
 //    widens it (12 VALU) and issues 4 MFMAs -- 48 VALU instructions against 16 MFMAs of 8 passes per k-step, the
 //    widening of a row fragment used by the four query fragments.  64 accumulator registers; no scratch.
 //    (One residency rule instead of registers up to 512 bits and LDS beyond: the LDS reads are 4 per 16 MFMAs.)
-//    Level 0 (no thresholds) writes every key of the sampled tiles at its row's slot, so a search forced onto this
-//    form launches nothing else.  Hits are counted per query with one ballot: the 16 lanes of a quarter wave share
-//    a query, the first of them reserves the quarter's slots with one atomic.
+//    The tile range, the thresholds and the epilogue (level 0 at fixed slots, so a search forced onto this form
+//    launches nothing else; the rare hit with one ballot and one atomic per quarter wave) are scan_tile.hpp's.
 //    LDS at dim = 1024: 66 560 + 67 584 bytes, one workgroup (two waves per SIMD) per CU; kPlanHamMfmaMaxDim
 //    (bf_plan.hpp) is where this form ends.
 #pragma once
-#include "common.hpp"
-#include "scan_f32.hpp"
+#include "scan_tile.hpp"
 
 namespace expann {
 
-typedef int ham_i32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kHamMaxDim = 4096;    // bits per row
 constexpr int kHamValuRows = 256;   // rows of a workgroup step of the VALU form at one lane per row
-constexpr int kHamThreads = 512;    // matrix-core form: 8 waves
-constexpr int kHamTQ = 64;          // ... queries per workgroup (four 16-query fragments)
-constexpr int kHamNT = 4;           // ... 16-row columns per wave
-constexpr int kHamTB = (kHamThreads / 64) * 16 * kHamNT;  // ... rows per tile
-static_assert(kHamTB == 512, "tile rows");
+static_assert(kHamTB == 512, "tile rows");  // (the matrix-core form's geometry: scan_tile.hpp)
 
 __host__ __device__ constexpr uint32_t ham_lanes_per_row(uint32_t dim) {
 	return dim >= 512 ? 8u : (dim >= 256 ? 4u : (dim >= 128 ? 2u : 1u));
@@ -179,24 +171,12 @@ template <int TQ> __global__ __launch_bounds__(kBlock) void scan_hamming_valu_ke
 }
 
 // ---- 2. matrix-core form ----------------------------------------------------------------------------------------
-struct HamMfmaParams {
-	const void* base;         // [n_rows][dim / 8]
-	const int* popb;          // [n_rows] popcount of each row
-	uint32_t n_rows;
-	uint32_t n_tiles_sel;     // kHamTB-row tiles this launch visits: tile j of the launch is base tile j * tile_stride
-	uint32_t tile_stride;
-	uint32_t tiles_per_block;
-	uint32_t n_qtiles;
-	const void* queries;      // [m][dim / 8]
-	const int* theta;         // [m] floor(tau) - pop(q); unused at level 0
-	const int* popq;          // [m]
-	const uint32_t* tau_row;  // [m] row of the threshold key
-	uint32_t m;
-	uint32_t* cand_cnt;
-	uint64_t* cand;
-	uint32_t cap;
-	uint32_t dim;             // bits
-	uint32_t level0;          // 1: no thresholds, the key of (query, row) goes to slot j * kHamTB + row in tile
+// score = pop(q) + pop(b) - 2 acc: integers in [0, dim], exact as floats
+struct HamPolicy {
+	static constexpr bool kFloatTies = false;
+	__device__ static int row_term(const TileScanParams& p, uint32_t row, bool valid) { return valid ? p.rowterm[row] : 0; }
+	__device__ static int combine(const TileScanParams&, int rt, int acc) { return rt - 2 * acc; }
+	__device__ static int query_term(const TileScanParams& p, uint32_t qi) { return p.qterm[qi]; }
 };
 
 // 16 bits -> 16 bytes in {0, 1}, bit j in byte j
@@ -243,52 +223,36 @@ static __global__ __launch_bounds__(kBlock) void ham_theta_kernel(const void* qu
 	}
 }
 
-__global__ __launch_bounds__(kHamThreads) void scan_hamming_mfma_kernel(HamMfmaParams p) {
+__global__ __launch_bounds__(kHamThreads) void scan_hamming_mfma_kernel(TileScanParams p) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char ham_smem[];
-	const uint32_t KS = p.dim / 64;   // k-steps
-	const uint32_t P16 = p.dim / 16;  // uint16 pieces per row
-	const uint32_t DWR = p.dim / 32;  // dwords per packed row
-	const uint32_t QS = ham_q_stride(p.dim), RS = ham_row_stride(p.dim);
+	const uint32_t KS = p.klen / 64;   // k-steps
+	const uint32_t P16 = p.klen / 16;  // uint16 pieces per row
+	const uint32_t DWR = p.klen / 32;  // dwords per packed row
+	const uint32_t QS = ham_q_stride(p.klen), RS = ham_row_stride(p.klen);
 	unsigned char* const qbytes = ham_smem;
 	unsigned char* const rows_lds = ham_smem + kHamTQ * QS;
-	const uint32_t tid = threadIdx.x;
-	const uint32_t lane = tid & 63;
-	const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-	const uint32_t i = lane & 15, g = lane >> 4;
-	const uint32_t qtile = blockIdx.x % p.n_qtiles;
-	const uint32_t chunk = blockIdx.x / p.n_qtiles;
-	const uint32_t q0 = qtile * kHamTQ;
-	constexpr int kNever = -2147483647 - 1;
+	TileLane w;
+	if (!tile_range(p, w))
+		return;
 
 	// the workgroup's queries, widened once
-	for (uint32_t pi = tid; pi < kHamTQ * P16; pi += kHamThreads) {
+	for (uint32_t pi = w.tid; pi < kHamTQ * P16; pi += kHamThreads) {
 		const uint32_t qq = pi / P16, c = pi - qq * P16;
-		const uint32_t qi = (q0 + qq < p.m) ? q0 + qq : p.m - 1;
-		const uint32_t bits = ((const uint16_t*)p.queries)[(size_t)qi * P16 + c];
+		const uint32_t qi = (w.q0 + qq < p.m) ? w.q0 + qq : p.m - 1;
+		const uint32_t bits = ((const uint16_t*)p.a_operand)[(size_t)qi * P16 + c];
 		*reinterpret_cast<ham_i32x4*>(qbytes + qq * QS + c * 16) = ham_widen16(bits);
 	}
-	// thresholds of the lane's 16 queries: fragment tq, register e = query 16 tq + 4 g + e (a padded slot never matches)
 	int th[4][4];
-#pragma unroll
-	for (int tq = 0; tq < 4; ++tq)
-#pragma unroll
-		for (int e = 0; e < 4; ++e) {
-			const uint32_t qi = q0 + 16 * tq + 4 * g + e;
-			th[tq][e] = (qi < p.m && !p.level0) ? p.theta[qi] : kNever;
-		}
+	tile_thresholds(p, w, th);
 
-	const uint32_t t0 = chunk * p.tiles_per_block;
-	uint32_t t1 = t0 + p.tiles_per_block;
-	if (t1 > p.n_tiles_sel)
-		t1 = p.n_tiles_sel;
 	const uint32_t* __restrict__ base_dw = (const uint32_t*)p.base;
 	uint32_t* const rows_dw = reinterpret_cast<uint32_t*>(rows_lds);
 	const uint32_t RSW = RS / 4;  // = DWR + 1: odd strides, the 16 rows of a column read 16 banks
 
-	for (uint32_t t = t0; t < t1; ++t) {
+	for (uint32_t t = w.t0; t < w.t1; ++t) {
 		const uint32_t row0 = t * p.tile_stride * kHamTB;
 		__syncthreads();  // (the queries are in place; the tile before has been read)
-		for (uint32_t d = tid; d < kHamTB * DWR; d += kHamThreads) {
+		for (uint32_t d = w.tid; d < kHamTB * DWR; d += kHamThreads) {
 			const uint32_t r = d / DWR, c = d - r * DWR;
 			const uint32_t grow = (row0 + r < p.n_rows) ? row0 + r : p.n_rows - 1;
 			rows_dw[r * RSW + c] = base_dw[(size_t)grow * DWR + c];
@@ -296,13 +260,9 @@ __global__ __launch_bounds__(kHamThreads) void scan_hamming_mfma_kernel(HamMfmaP
 		__syncthreads();
 
 		ham_i32x4 acc[4][kHamNT];
-#pragma unroll
-		for (int tq = 0; tq < 4; ++tq)
-#pragma unroll
-			for (int tc = 0; tc < kHamNT; ++tc)
-				acc[tq][tc] = ham_i32x4{0, 0, 0, 0};
-		const unsigned char* const qf = qbytes + i * QS + 16 * g;
-		const unsigned char* const rf = rows_lds + (wave * 64 + i) * RS + 2 * g;
+		tile_clear(acc);
+		const unsigned char* const qf = qbytes + w.i * QS + 16 * w.g;
+		const unsigned char* const rf = rows_lds + (w.wave * 64 + w.i) * RS + 2 * w.g;
 		for (uint32_t s = 0; s < KS; ++s) {
 			ham_i32x4 a[4];
 #pragma unroll
@@ -317,44 +277,7 @@ __global__ __launch_bounds__(kHamThreads) void scan_hamming_mfma_kernel(HamMfmaP
 					acc[tq][tc] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[tq], f, acc[tq][tc], 0, 0, 0);
 			}
 		}
-
-		// epilogue: lane (i, g) holds, for column tc, row 16 tc + i of the wave against queries 16 tq + 4 g + e
-#pragma unroll
-		for (int tc = 0; tc < kHamNT; ++tc) {
-			const uint32_t local = wave * 64 + 16 * tc + i;
-			const uint32_t brow = row0 + local;
-			const bool bvalid = brow < p.n_rows;
-			const int pb = bvalid ? p.popb[brow] : 0;
-#pragma unroll
-			for (int tq = 0; tq < 4; ++tq) {
-#pragma unroll
-				for (int e = 0; e < 4; ++e) {
-					const int tv = pb - 2 * acc[tq][tc][e];
-					const uint32_t qi = q0 + 16 * tq + 4 * g + e;
-					if (p.level0) {
-						const uint32_t slot = t * kHamTB + local;
-						if (qi < p.m && slot < p.cap)
-							p.cand[(size_t)qi * p.cap + slot] =
-							    bvalid ? make_key((float)(tv + p.popq[qi]), brow) : kSentinelKey;
-						continue;
-					}
-					bool hit = bvalid && tv <= th[tq][e];
-					if (__builtin_amdgcn_ballot_w64(hit) == 0)
-						continue;
-					// rare path: the tie rule, then one atomic per quarter wave (its 16 lanes share the query)
-					hit = hit && (tv < th[tq][e] || brow <= p.tau_row[qi]);
-					const unsigned long long mask = __builtin_amdgcn_ballot_w64(hit);
-					const uint32_t seg = (uint32_t)(mask >> (lane & 48)) & 0xFFFFu;
-					uint32_t slot0 = 0;
-					if (i == 0 && seg)
-						slot0 = atomicAdd(&p.cand_cnt[qi], (uint32_t)__builtin_popcount(seg));
-					slot0 = __shfl(slot0, lane & 48);
-					const uint32_t slot = slot0 + (uint32_t)__builtin_popcount(seg & ((1u << i) - 1u));
-					if (hit && slot < p.cap)
-						p.cand[(size_t)qi * p.cap + slot] = make_key((float)(tv + p.popq[qi]), brow);
-				}
-			}
-		}
+		tile_epilogue<HamPolicy>(p, w, t, acc, th);
 	}
 }
 

@@ -4,12 +4,9 @@
 //     EXPANN_METRIC_IP: score = - sum_j q_j b_j          EXPANN_METRIC_L2: score = sum_j (q_j - b_j)^2
 // an exact int32, reported and ranked as (float)score, then by lower id.
 //
-// gfx950 has no int4 matrix instruction: scan_i4_mfma_kernel widens the nibbles to bytes in registers in front of
-// v_mfma_i32_16x16x64_i8.  Geometry (scan_hamming.hpp's): 512 threads in 8 waves, kHamTQ = 64 queries per workgroup
-// as four 16-query A fragments, tiles of kHamTB = 512 rows; wave w owns rows [64 w, 64 w + 64) of the tile as four
-// 16-row columns; 64 accumulator registers, no scratch.  Level 0 (no thresholds) writes the key of every (query,
-// row) of its tiles at the row's fixed slot; the rare-hit epilogue applies the tie rule with one ballot and one
-// atomic per quarter wave.  Its own design is in three places.
+// gfx950 has no int4 matrix instruction: scan_i4_mfma_kernel = scan_stream_mfma_kernel<I4Codec> (scan_tile.hpp: the
+// geometry, the streamed stage loop, the epilogue) widens the nibbles to bytes in registers in front of
+// v_mfma_i32_16x16x64_i8.  Its own design is in three places.
 //
 // 1. Widening in offset binary, and a permuted query so that it costs nothing more.  A lane's B operand for one
 //    k-step is 16 elements = 8 packed bytes = two dwords x.  y = x ^ 0x88888888 turns every nibble s into u = s + 8
@@ -42,11 +39,7 @@
 //    Two stages, not three: the loads of stage i + 1 are in registers (4 x 16 B of rows + 16 B of queries per
 //    thread) while stage i is multiplied, so global latency is covered by one stage of 32 MFMAs per wave already; a
 //    third stage would only move the LDS store earlier, and the store is 5 ds_write_b128 per thread.
-//    Overlap: the global loads of stage i + 1 are issued BEFORE the k-steps of stage i and stored to the other
-//    stage's LDS after them.  No load sits under a branch.  One barrier per stage: it publishes stage i and says
-//    that the buffer about to be overwritten has been read.
-//    dim <= kI4KC: one chunk per tile, and the query chunk is staged ONCE per workgroup (in stage 0's query area).
-//    A last chunk shorter than kI4KC (64 elements) is simply shorter: fewer loads kept, one k-step.
+//    A chunk shorter than kI4KC is 64 elements: one k-step.
 //
 // One form for every m >= 1: a batch below 64 queries pays for the whole 64-query fragment set.
 // Rows and queries must be 16-byte aligned on the device (read as 16-byte pieces; dim % 64 == 0 keeps every row so).
@@ -65,27 +58,6 @@ static_assert((kI4RowStride / 4) % 64 == 20 && (kI4QStride / 4) % 64 == 36, "the
 static_assert(kI4StageBytes == 40960 + 9216 && kI4LdsBytes == 100352 && kI4LdsBytes <= 160 * 1024, "LDS budget per CU");
 static_assert(kHamTB * (256 / 2 + 16) + kHamTQ * (256 + 16) == 91136 && 2 * 91136 > 160 * 1024, "why not 256-element chunks");
 static_assert(kHamThreads == 512 && kHamTB == 512 && kHamTQ == 64, "the staging below: 4 threads per row, 8 per query");
-
-struct I4Params {
-	const void* base;         // [n_rows][dim / 2] packed nibbles
-	const int* rowterm;       // [n_rows] sum b^2 (L2); nullptr: inner product
-	uint32_t n_rows;
-	uint32_t n_tiles_sel;     // kHamTB-row tiles this launch visits: tile j of the launch is base tile j * tile_stride
-	uint32_t tile_stride;
-	uint32_t tiles_per_block;
-	uint32_t n_qtiles;
-	const void* queries;      // [m][dim] int8, permuted inside every 16-byte group (i4_theta_kernel)
-	const int* theta;         // [m] floor(tau) - qterm (+ the float slack); unused at level 0
-	const int* qterm;         // [m]
-	const float* tau;         // [m] the threshold itself (rare path); unused at level 0
-	const uint32_t* tau_row;  // [m] row of the threshold key
-	uint32_t m;
-	uint32_t* cand_cnt;
-	uint64_t* cand;
-	uint32_t cap;
-	uint32_t dim;             // elements of a row = bytes of a query
-	uint32_t level0;          // 1: no thresholds, the key of (query, row) goes to slot j * kHamTB + row in tile
-};
 
 // sum b^2 per row -- one thread per row, 16-byte loads (rows arrive: expann_build, expann_set_base_device)
 static __global__ __launch_bounds__(kBlock) void i4_rowterm_kernel(const void* rows, uint32_t n, uint32_t dim, int* out) {
@@ -154,180 +126,73 @@ static __global__ __launch_bounds__(kBlock) void i4_theta_kernel(const void* que
 	}
 }
 
+// IP (no row terms): score = -acc + qterm.  L2: score = rowterm - 2 acc + qterm, which passes 2^24 above dim 896 --
+// float ties (2. of the header comment).
+struct I4Policy {
+	static constexpr bool kFloatTies = true;
+	__device__ static int row_term(const TileScanParams& p, uint32_t row, bool valid) {
+		return (p.rowterm != nullptr && valid) ? p.rowterm[row] : 0;
+	}
+	__device__ static int combine(const TileScanParams& p, int rt, int acc) {
+		return rt - (int)((uint32_t)acc << (p.rowterm != nullptr ? 1u : 0u));  // (rt is 0 without row terms)
+	}
+	__device__ static int query_term(const TileScanParams& p, uint32_t qi) { return p.qterm[qi]; }
+};
+
 // The staging of one (tile, chunk): global -> registers, registers -> LDS.  kw = the chunk's elements (64 or 128).
 // Rows: a chunk is kw / 32 pieces of 16 bytes; 4 lanes share a row, so a wave's load covers runs of 64 consecutive
 // bytes, and a thread holds 4 pieces: r = tid / 4 + 128 j.  Queries: 8 lanes per query read its kw / 16 pieces.
-struct I4Stage {
-	ham_i32x4 rows[4];
-	ham_i32x4 q;
+struct I4Codec {
+	using Policy = I4Policy;
+	static constexpr uint32_t kKC = kI4KC, kRowStride = kI4RowStride, kQStride = kI4QStride, kStageBytes = kI4StageBytes;
+	static constexpr uint32_t kLaneBytes = 8;  // of a row, per lane and k-step: 16 nibbles
+	struct Stage {
+		ham_i32x4 rows[4];
+		ham_i32x4 q;
+	};
+	__device__ __attribute__((always_inline)) static void load(Stage& s, const TileScanParams& p, uint32_t tid, uint32_t row0,
+	                                                          uint32_t q0, uint32_t c, uint32_t kw, bool with_q) {
+		const uint32_t U = kw / 32, RP = p.klen / 32;
+		const uint32_t u = tid & 3, rsub = tid >> 2;
+		const ham_i32x4* __restrict__ base = (const ham_i32x4*)p.base;
+		// No load sits under a branch (scan_asym.hpp: a guarded load serialises the loads).  The pieces store() will not
+		// use come from an address of the same tile and chunk that is valid anyway (a cache hit).
+		const uint32_t uc = u < U ? u : U - 1;
+#pragma unroll
+		for (uint32_t j = 0; j < 4; ++j) {
+			const uint32_t r = rsub + j * (kHamTB / 4);
+			const uint32_t grow = (row0 + r < p.n_rows) ? row0 + r : p.n_rows - 1;
+			s.rows[j] = base[(size_t)grow * RP + c * (kI4KC / 32) + uc];
+		}
+		if (with_q) {
+			const uint32_t v = tid & 7, V = kw / 16;
+			const uint32_t vc = v < V ? v : V - 1;
+			const uint32_t qq = tid >> 3;
+			const uint32_t qi = (q0 + qq < p.m) ? q0 + qq : p.m - 1;
+			s.q = ((const ham_i32x4*)p.a_operand)[(size_t)qi * (p.klen / 16) + c * (kI4KC / 16) + vc];
+		}
+	}
+	__device__ __attribute__((always_inline)) static void store(const Stage& s, unsigned char* rbuf, unsigned char* qbuf, uint32_t tid,
+	                                                           uint32_t kw, bool with_q) {
+		const uint32_t U = kw / 32;
+		const uint32_t u = tid & 3, rsub = tid >> 2;
+		if (u < U) {
+#pragma unroll
+			for (uint32_t j = 0; j < 4; ++j)
+				*reinterpret_cast<ham_i32x4*>(rbuf + (rsub + j * (kHamTB / 4)) * kI4RowStride + 16 * u) = s.rows[j];
+		}
+		if (with_q && (tid & 7) < kw / 16)
+			*reinterpret_cast<ham_i32x4*>(qbuf + (tid >> 3) * kI4QStride + 16 * (tid & 7)) = s.q;
+	}
+	// (1. of the header comment: offset binary, the even elements and the odd ones)
+	__device__ __attribute__((always_inline)) static ham_i32x4 b_fragment(const unsigned char* at) {
+		const uint2 x = *reinterpret_cast<const uint2*>(at);
+		const uint32_t y0 = x.x ^ 0x88888888u, y1 = x.y ^ 0x88888888u;
+		return ham_i32x4{(int)(y0 & 0x0F0F0F0Fu), (int)((y0 >> 4) & 0x0F0F0F0Fu), (int)(y1 & 0x0F0F0F0Fu),
+		                 (int)((y1 >> 4) & 0x0F0F0F0Fu)};
+	}
 };
-__device__ __attribute__((always_inline)) inline void i4_load(I4Stage& s, const I4Params& p, uint32_t tid, uint32_t row0,
-                                                              uint32_t q0, uint32_t c, uint32_t kw, bool with_q) {
-	const uint32_t U = kw / 32, RP = p.dim / 32;
-	const uint32_t u = tid & 3, rsub = tid >> 2;
-	const ham_i32x4* __restrict__ base = (const ham_i32x4*)p.base;
-	// No load sits under a branch (scan_asym.hpp: a guarded load serialises the loads).  The pieces i4_store will not
-	// use come from an address of the same tile and chunk that is valid anyway (a cache hit).
-	const uint32_t uc = u < U ? u : U - 1;
-#pragma unroll
-	for (uint32_t j = 0; j < 4; ++j) {
-		const uint32_t r = rsub + j * (kHamTB / 4);
-		const uint32_t grow = (row0 + r < p.n_rows) ? row0 + r : p.n_rows - 1;
-		s.rows[j] = base[(size_t)grow * RP + c * (kI4KC / 32) + uc];
-	}
-	if (with_q) {
-		const uint32_t v = tid & 7, V = kw / 16;
-		const uint32_t vc = v < V ? v : V - 1;
-		const uint32_t qq = tid >> 3;
-		const uint32_t qi = (q0 + qq < p.m) ? q0 + qq : p.m - 1;
-		s.q = ((const ham_i32x4*)p.queries)[(size_t)qi * (p.dim / 16) + c * (kI4KC / 16) + vc];
-	}
-}
-__device__ __attribute__((always_inline)) inline void i4_store(const I4Stage& s, unsigned char* rbuf, unsigned char* qbuf,
-                                                               uint32_t tid, uint32_t kw, bool with_q) {
-	const uint32_t U = kw / 32;
-	const uint32_t u = tid & 3, rsub = tid >> 2;
-	if (u < U) {
-#pragma unroll
-		for (uint32_t j = 0; j < 4; ++j)
-			*reinterpret_cast<ham_i32x4*>(rbuf + (rsub + j * (kHamTB / 4)) * kI4RowStride + 16 * u) = s.rows[j];
-	}
-	if (with_q && (tid & 7) < kw / 16)
-		*reinterpret_cast<ham_i32x4*>(qbuf + (tid >> 3) * kI4QStride + 16 * (tid & 7)) = s.q;
-}
 
-__global__ __launch_bounds__(kHamThreads) void scan_i4_mfma_kernel(I4Params p) {
-	extern __shared__ __attribute__((aligned(16))) unsigned char i4_smem[];
-	constexpr uint32_t RS = kI4RowStride, QS = kI4QStride, QOFF = kHamTB * kI4RowStride;
-	const uint32_t tid = threadIdx.x;
-	const uint32_t lane = tid & 63;
-	const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-	const uint32_t i = lane & 15, g = lane >> 4;
-	const uint32_t qtile = blockIdx.x % p.n_qtiles;
-	const uint32_t chunk = blockIdx.x / p.n_qtiles;
-	const uint32_t q0 = qtile * kHamTQ;
-	const uint32_t NC = (p.dim + kI4KC - 1) / kI4KC;  // chunks of the reduction dimension
-	const bool stream_q = NC > 1;                    // (one chunk: the queries are staged once, in stage 0)
-	const bool l2 = p.rowterm != nullptr;
-	constexpr int kNever = -2147483647 - 1;
-
-	const uint32_t t0 = chunk * p.tiles_per_block;
-	uint32_t t1 = t0 + p.tiles_per_block;
-	if (t1 > p.n_tiles_sel)
-		t1 = p.n_tiles_sel;
-	if (t0 >= t1)
-		return;
-	const uint32_t n_items = (t1 - t0) * NC;
-
-	// thresholds of the lane's 16 queries: fragment tq, register e = query 16 tq + 4 g + e (a padded slot never matches)
-	int th[4][4];
-#pragma unroll
-	for (int tq = 0; tq < 4; ++tq)
-#pragma unroll
-		for (int e = 0; e < 4; ++e) {
-			const uint32_t qi = q0 + 16 * tq + 4 * g + e;
-			th[tq][e] = (qi < p.m && !p.level0) ? p.theta[qi] : kNever;
-		}
-
-	I4Stage st;
-	uint32_t t = t0, c = 0;
-	uint32_t kw = p.dim < kI4KC ? p.dim : kI4KC;
-	i4_load(st, p, tid, t * p.tile_stride * kHamTB, q0, 0, kw, true);
-	i4_store(st, i4_smem, i4_smem + QOFF, tid, kw, true);
-
-	ham_i32x4 acc[4][kHamNT];
-	for (uint32_t it = 0; it < n_items; ++it) {
-		const uint32_t row0 = t * p.tile_stride * kHamTB;
-		uint32_t tn = t, cn = c + 1;
-		if (cn == NC) {
-			cn = 0;
-			tn = t + 1;
-		}
-		const bool more = it + 1 < n_items;
-		const uint32_t kwn = (p.dim - cn * kI4KC) < kI4KC ? (p.dim - cn * kI4KC) : kI4KC;
-		if (more)  // in flight while this stage is multiplied
-			i4_load(st, p, tid, tn * p.tile_stride * kHamTB, q0, cn, kwn, stream_q);
-		__syncthreads();  // this stage is in place; the other one has been read
-
-		unsigned char* const sbuf = i4_smem + (it & 1) * kI4StageBytes;
-		unsigned char* const obuf = i4_smem + ((it + 1) & 1) * kI4StageBytes;
-		if (c == 0) {
-#pragma unroll
-			for (int tq = 0; tq < 4; ++tq)
-#pragma unroll
-				for (int tc = 0; tc < kHamNT; ++tc)
-					acc[tq][tc] = ham_i32x4{0, 0, 0, 0};
-		}
-		const unsigned char* const qf = (stream_q ? sbuf : i4_smem) + QOFF + i * QS + 16 * g;
-		const unsigned char* const rf = sbuf + (wave * 64 + i) * RS + 8 * g;
-		const uint32_t KS = kw / 64;
-		for (uint32_t s = 0; s < KS; ++s) {
-			ham_i32x4 a[4];
-#pragma unroll
-			for (int tq = 0; tq < 4; ++tq)
-				a[tq] = *reinterpret_cast<const ham_i32x4*>(qf + 16 * tq * QS + 64 * s);
-#pragma unroll
-			for (int tc = 0; tc < kHamNT; ++tc) {
-				const uint2 x = *reinterpret_cast<const uint2*>(rf + 16 * tc * RS + 32 * s);
-				const uint32_t y0 = x.x ^ 0x88888888u, y1 = x.y ^ 0x88888888u;
-				const ham_i32x4 f = {(int)(y0 & 0x0F0F0F0Fu), (int)((y0 >> 4) & 0x0F0F0F0Fu), (int)(y1 & 0x0F0F0F0Fu),
-				                     (int)((y1 >> 4) & 0x0F0F0F0Fu)};
-#pragma unroll
-				for (int tq = 0; tq < 4; ++tq)
-					acc[tq][tc] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[tq], f, acc[tq][tc], 0, 0, 0);
-			}
-		}
-		if (more)
-			i4_store(st, obuf, obuf + QOFF, tid, kwn, stream_q);
-
-		if (c == NC - 1) {
-			// epilogue: lane (i, g) holds, for column tc, row 16 tc + i of the wave against queries 16 tq + 4 g + e
-#pragma unroll
-			for (int tc = 0; tc < kHamNT; ++tc) {
-				const uint32_t local = wave * 64 + 16 * tc + i;
-				const uint32_t brow = row0 + local;
-				const bool bvalid = brow < p.n_rows;
-				const int rt = (l2 && bvalid) ? p.rowterm[brow] : 0;
-#pragma unroll
-				for (int tq = 0; tq < 4; ++tq) {
-#pragma unroll
-					for (int e = 0; e < 4; ++e) {
-						const int tv = l2 ? rt - 2 * acc[tq][tc][e] : -acc[tq][tc][e];
-						const uint32_t qi = q0 + 16 * tq + 4 * g + e;
-						if (p.level0) {
-							const uint32_t slot = t * kHamTB + local;
-							if (qi < p.m && slot < p.cap)
-								p.cand[(size_t)qi * p.cap + slot] =
-								    bvalid ? make_key((float)(tv + p.qterm[qi]), brow) : kSentinelKey;
-							continue;
-						}
-						bool hit = bvalid && tv <= th[tq][e];
-						if (__builtin_amdgcn_ballot_w64(hit) == 0)
-							continue;
-						// rare path: the tie rule on the floats, then one atomic per quarter wave (its 16 lanes share the query)
-						float sf = 0.0f;
-						if (hit) {
-							sf = (float)(tv + p.qterm[qi]);
-							const float tau = p.tau[qi];
-							hit = sf < tau || (sf == tau && brow <= p.tau_row[qi]);
-						}
-						const unsigned long long mask = __builtin_amdgcn_ballot_w64(hit);
-						const uint32_t seg = (uint32_t)(mask >> (lane & 48)) & 0xFFFFu;
-						uint32_t slot0 = 0;
-						if (i == 0 && seg)
-							slot0 = atomicAdd(&p.cand_cnt[qi], (uint32_t)__builtin_popcount(seg));
-						slot0 = __shfl(slot0, lane & 48);
-						const uint32_t slot = slot0 + (uint32_t)__builtin_popcount(seg & ((1u << i) - 1u));
-						if (hit && slot < p.cap)
-							p.cand[(size_t)qi * p.cap + slot] = make_key((float)(tv + p.qterm[qi]), brow);
-					}
-				}
-			}
-		}
-		t = tn;
-		c = cn;
-		kw = kwn;
-	}
-}
+constexpr auto scan_i4_mfma_kernel = scan_stream_mfma_kernel<I4Codec>;
 
 }  // namespace expann

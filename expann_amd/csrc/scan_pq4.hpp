@@ -6,11 +6,9 @@
 // 2-4 of the rule) it is an int8 GEMM with K = 16 M, exact in int32, on v_mfma_i32_16x16x64_i8.  scan_pq.hpp's "no
 // matrix instruction fits" holds for 256 centroids, not for 16.
 //
-// Geometry (scan_hamming.hpp's): 512 threads in 8 waves, kHamTQ = 64 queries per workgroup as four 16-query A
-// fragments, tiles of kHamTB = 512 rows; wave w owns rows [64 w, 64 w + 64) of the tile as four 16-row columns; 64
-// accumulator registers, no scratch.  Level 0, the integer compare against theta, the rare-hit tie path and the ladder
-// contract are scan_i4_mfma_kernel's.  The data movement is its opposite: a row gives 1/32 of a byte per k-element,
-// a query's table a whole byte.
+// The geometry, the tile range, the thresholds and the epilogue are scan_tile.hpp's, the float ties scan_i4.hpp's.
+// The data movement is the opposite of the 4-bit rows': a row gives 1/32 of a byte per k-element, a query's table a
+// whole byte -- so the tile loop is this kernel's own.
 //
 // 1. The B operand is made in registers and never touches LDS.  Lane (i, g) of the instruction holds, for one k-step,
 //    the 16 k-bytes [16 g, 16 g + 16) of column i: exactly the one-hot of ONE nibble c -- four dwords, of which dword
@@ -36,7 +34,7 @@
 // 3. Prep.  pq4_tables_kernel (one workgroup per query, lane = (sub-quantiser mod 16, centroid)) builds T by the rule
 //    with pq_term, takes min / max over the 16 centroids as DPP row reductions, the span as a max (exact in any
 //    order), the bias as the rule's serial sum, and writes the A operand, bias and step.  S = acc + 128 M; the
-//    constant 128 M travels as PQ4Params::qterm.  pq4_theta_kernel writes theta = floor(tau) - 128 M before every
+//    constant 128 M travels as TileScanParams::qterm_const.  pq4_theta_kernel writes theta = floor(tau) - 128 M before every
 //    level that has thresholds (tau is (float)S of the proven key, an exact integer or +inf).  pq4_finish_kernel
 //    applies step 7 to the selected [m][k] outputs.
 //
@@ -67,24 +65,12 @@ static_assert(pq4_lds_bytes(kPQ4ResidentMaxM) == 132096 && pq4_lds_bytes(kPQ4Res
               "LDS budget per CU: where the resident form ends");
 static_assert(kHamThreads == 512 && kHamTB == 512 && kHamTQ == 64 && kHamNT == 4, "the staging below: 2 pieces of 16 bytes per thread and chunk");
 
-struct PQ4Params {
-	const void* base;         // [n_rows][M / 2] packed codes
-	uint32_t n_rows;
-	uint32_t n_tiles_sel;     // kHamTB-row tiles this launch visits: tile j of the launch is base tile j * tile_stride
-	uint32_t tile_stride;
-	uint32_t tiles_per_block;
-	uint32_t n_qtiles;
-	const void* tables;       // [m][16 M] signed bytes u - 128 in the scan's k order (pq4_tables_kernel)
-	const int* theta;         // [m] floor(tau) - qterm; unused at level 0
-	const float* tau;         // [m] the threshold itself (rare path); unused at level 0
-	const uint32_t* tau_row;  // [m] row of the threshold key
-	uint32_t m;
-	uint32_t* cand_cnt;
-	uint64_t* cand;
-	uint32_t cap;
-	uint32_t M;               // codes per row
-	int qterm;                // 128 M: S = acc + qterm
-	uint32_t level0;          // 1: no thresholds, the key of (query, row) goes to slot j * kHamTB + row in tile
+// S = acc + 128 M, ranked as (float)S (ties on the floats, as the 4-bit rows')
+struct PQ4Policy {
+	static constexpr bool kFloatTies = true;
+	__device__ static int row_term(const TileScanParams&, uint32_t, bool) { return 0; }
+	__device__ static int combine(const TileScanParams&, int, int acc) { return acc; }
+	__device__ static int query_term(const TileScanParams& p, uint32_t) { return p.qterm_const; }
 };
 
 __device__ __attribute__((always_inline)) inline float pq4_min16(float v) {
@@ -191,36 +177,17 @@ struct PQ4Codes {
 	uint32_t w[kHamNT];  // per column: the lane's four nibbles of the chunk
 };
 
-template <bool RESIDENT> __global__ __launch_bounds__(kHamThreads) void scan_pq4_mfma_kernel(PQ4Params p) {
+template <bool RESIDENT> __global__ __launch_bounds__(kHamThreads) void scan_pq4_mfma_kernel(TileScanParams p) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char pq4_smem[];
-	const uint32_t tid = threadIdx.x;
-	const uint32_t lane = tid & 63;
-	const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-	const uint32_t i = lane & 15, g = lane >> 4;
-	const uint32_t qtile = blockIdx.x % p.n_qtiles;
-	const uint32_t chunk = blockIdx.x / p.n_qtiles;
-	const uint32_t q0 = qtile * kHamTQ;
-	const uint32_t M = p.M, NC = M / 16;  // chunks of the reduction dimension
-	const uint32_t QS = RESIDENT ? pq4_q_stride(M) : kPQ4StageStride;
-	constexpr int kNever = -2147483647 - 1;
-
-	const uint32_t t0 = chunk * p.tiles_per_block;
-	uint32_t t1 = t0 + p.tiles_per_block;
-	if (t1 > p.n_tiles_sel)
-		t1 = p.n_tiles_sel;
-	if (t0 >= t1)
+	TileLane w;
+	if (!tile_range(p, w))
 		return;
+	const uint32_t tid = w.tid, wave = w.wave, i = w.i, g = w.g, q0 = w.q0, t0 = w.t0, t1 = w.t1;
+	const uint32_t M = p.klen, NC = M / 16;  // chunks of the reduction dimension
+	const uint32_t QS = RESIDENT ? pq4_q_stride(M) : kPQ4StageStride;
 	const uint32_t n_items = (t1 - t0) * NC;
-
-	// thresholds of the lane's 16 queries: fragment tq, register e = query 16 tq + 4 g + e (a padded slot never matches)
 	int th[4][4];
-#pragma unroll
-	for (int tq = 0; tq < 4; ++tq)
-#pragma unroll
-		for (int e = 0; e < 4; ++e) {
-			const uint32_t qi = q0 + 16 * tq + 4 * g + e;
-			th[tq][e] = (qi < p.m && !p.level0) ? p.theta[qi] : kNever;
-		}
+	tile_thresholds(p, w, th);
 
 	// the stream of row codes, (tile, chunk) by (tile, chunk): ushort 4 u + g of the lane's row in each column
 	const unsigned short* __restrict__ rows = (const unsigned short*)p.base;
@@ -244,7 +211,7 @@ template <bool RESIDENT> __global__ __launch_bounds__(kHamThreads) void scan_pq4
 	fetch(w1);
 
 	// the tables: 16-byte pieces, M per query (16 per chunk); slots past m repeat the last query and never file
-	const ham_i32x4* __restrict__ tab = (const ham_i32x4*)p.tables;
+	const ham_i32x4* __restrict__ tab = (const ham_i32x4*)p.a_operand;
 	ham_i32x4 av[2];
 	auto a_load = [&](uint32_t c) {
 #pragma unroll
@@ -291,13 +258,8 @@ template <bool RESIDENT> __global__ __launch_bounds__(kHamThreads) void scan_pq4
 			__syncthreads();  // this stage is in place; the other one has been read
 		}
 		const unsigned char* const abuf = RESIDENT ? pq4_smem + c * kPQ4ChunkBytes : pq4_smem + (it & 1) * kPQ4StageBytes;
-		if (c == 0) {
-#pragma unroll
-			for (int tq = 0; tq < 4; ++tq)
-#pragma unroll
-				for (int tc = 0; tc < kHamNT; ++tc)
-					acc[tq][tc] = ham_i32x4{0, 0, 0, 0};
-		}
+		if (c == 0)
+			tile_clear(acc);
 		const unsigned char* const qf = abuf + i * QS + 16 * g;
 #pragma unroll
 		for (int j = 0; j < 4; ++j) {  // k-step j of the chunk: nibble j of the lane's ushort
@@ -315,49 +277,8 @@ template <bool RESIDENT> __global__ __launch_bounds__(kHamThreads) void scan_pq4
 		}
 		if (!RESIDENT && more)
 			a_store(pq4_smem + ((it + 1) & 1) * kPQ4StageBytes);
-
-		if (c == NC - 1) {
-			// epilogue: lane (i, g) holds, for column tc, row 16 tc + i of the wave against queries 16 tq + 4 g + e
-			const uint32_t row0 = t * p.tile_stride * kHamTB;
-#pragma unroll
-			for (int tc = 0; tc < kHamNT; ++tc) {
-				const uint32_t local = wave * 64 + 16 * tc + i;
-				const uint32_t brow = row0 + local;
-				const bool bvalid = brow < p.n_rows;
-#pragma unroll
-				for (int tq = 0; tq < 4; ++tq) {
-#pragma unroll
-					for (int e = 0; e < 4; ++e) {
-						const int tv = acc[tq][tc][e];
-						const uint32_t qi = q0 + 16 * tq + 4 * g + e;
-						if (p.level0) {
-							const uint32_t slot = t * kHamTB + local;
-							if (qi < p.m && slot < p.cap)
-								p.cand[(size_t)qi * p.cap + slot] = bvalid ? make_key((float)(tv + p.qterm), brow) : kSentinelKey;
-							continue;
-						}
-						bool hit = bvalid && tv <= th[tq][e];
-						if (__builtin_amdgcn_ballot_w64(hit) == 0)
-							continue;
-						// rare path: the tie rule on the floats, then one atomic per quarter wave (its 16 lanes share the query)
-						const float sf = (float)(tv + p.qterm);
-						if (hit) {
-							const float tau = p.tau[qi];
-							hit = sf < tau || (sf == tau && brow <= p.tau_row[qi]);
-						}
-						const unsigned long long mask = __builtin_amdgcn_ballot_w64(hit);
-						const uint32_t seg = (uint32_t)(mask >> (lane & 48)) & 0xFFFFu;
-						uint32_t slot0 = 0;
-						if (i == 0 && seg)
-							slot0 = atomicAdd(&p.cand_cnt[qi], (uint32_t)__builtin_popcount(seg));
-						slot0 = __shfl(slot0, lane & 48);
-						const uint32_t slot = slot0 + (uint32_t)__builtin_popcount(seg & ((1u << i) - 1u));
-						if (hit && slot < p.cap)
-							p.cand[(size_t)qi * p.cap + slot] = make_key(sf, brow);
-					}
-				}
-			}
-		}
+		if (c == NC - 1)
+			tile_epilogue<PQ4Policy>(p, w, t, acc, th);
 		t = tn;
 		c = cn;
 	}
